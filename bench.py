@@ -6,8 +6,13 @@
 
 A step = one micro-step of the reference's training loop (base_strategy_mla.py:303-379): forward + backward of the whole
 MLA model on a synthetic batch of 8 samples per GPU (x4 diffusion repeats = 32 sequences of 548 tokens), global grad-norm
-clip, AdamW step. Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (MFMA GEMM family, timed
-with HIP events around every launch on the launch stream) and `cpu_baseline` (the oracle's decoder layer on the host cores).
+clip, AdamW step. Rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+
+A plain run only sets up, warms up, times --steps steps and prints that line. --full adds everything else the benchmark
+measures: `roofline` (MFMA GEMM family, timed with HIP events around every launch on the launch stream), `box` (clock / power
+sampler and MFMA calibrations), `secondary` (configs[3] / [4] and inference in child processes), `cpu_baseline` (the oracle's
+decoder layer on the host cores) and, with N > 1 ranks, `per_rank` (step times, collective stalls, replica check).
+--dump-outputs DIR writes what the last timed step computed as .npy files (see dump_outputs).
 """
 import argparse
 import json
@@ -265,7 +270,7 @@ def secondary_configs(steps=3, warmup=1, timeout_s=420):
     res = {}
     for cfg, extra in ((3, []), (4, ["--keep-layers", "0"]), (4, ["--keep-layers", "0", "--share-prefix"]), (1, ["--readout-rows"])):
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--config", str(cfg), "--steps", str(steps), "--warmup", str(warmup),
-               "--no-cpu-baseline", "--no-secondary", "--no-box"] + extra
+               "--full", "--no-cpu-baseline", "--no-secondary", "--no-box"] + extra
         t0 = time.time()
         try:
             cp = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout_s, text=True)
@@ -303,6 +308,35 @@ def secondary_configs(steps=3, warmup=1, timeout_s=420):
     return res
 
 
+def dump_outputs(out_dir, strat, losses, max_bytes=64 << 20):
+    """--dump-outputs DIR: what the last timed step computed, as .npy files, so that two builds can be compared output for output.
+      loss_<name>.npy   float64 scalars: the loss dict train_step returns to its caller;
+      grad_norm.npy     float64 scalar: the global gradient norm before clipping;
+      grad_sample.npy   float32: the step's fp32 gradient (as the optimizer read it) at fixed, seeded positions of every trainable
+                        sharding unit (all of a unit that is small enough), units in model order;
+      param_sample.npy  float32: the fp32 master weights after the step's AdamW update at the same positions.
+    The positions depend only on the unit sizes (torch.Generator seeded with the unit's index), and together the files stay under
+    max_bytes. With N ranks, each rank's own shard is sampled and rank 0's is written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in losses.items():
+        if torch.is_tensor(v) and v.numel() == 1:
+            np.save(os.path.join(out_dir, f"loss_{k}.npy"), v.detach().double().cpu().numpy().reshape(()))
+    sm = strat.sharded
+    np.save(os.path.join(out_dir, "grad_norm.npy"), sm._norm.double().cpu().numpy().reshape(()))
+    units = [u for u in sm.units if u.trainable]
+    per_unit = min(1 << 17, (max_bytes - (1 << 20)) // (2 * 4 * max(len(units), 1)))
+    grads, params = [], []
+    for i, u in enumerate(units):
+        n = u.master_train.numel()
+        idx = (torch.arange(n) if n <= per_unit else
+               torch.randint(0, n, (per_unit,), generator=torch.Generator().manual_seed(i)).sort().values).to(u.master_train.device)
+        grads.append(u.gshard[idx].float().cpu())
+        params.append(u.master_train[idx].float().cpu())
+    np.save(os.path.join(out_dir, "grad_sample.npy"), torch.cat(grads).numpy())
+    np.save(os.path.join(out_dir, "param_sample.npy"), torch.cat(params).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -335,8 +369,19 @@ def main():
                          "action read-out rows only, the one thing the diffusion objective reads of the final hidden state")
     ap.add_argument("--no-box", action="store_true", help="skip the `box` block (sclk / power sampler + the two 300 ms MFMA calibrations)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the `secondary` block (configs[3] and configs[4] at 3 timed steps each) the default 1-GPU configs[1] run appends")
+                    help="skip the `secondary` block (configs[3] and configs[4] at 3 timed steps each) the --full 1-GPU configs[1] run appends")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: `roofline`, `box`, `secondary`, `cpu_baseline` and, with N > 1 "
+                         "ranks, `per_rank` (the --no-* switches above still take single blocks out). Off by default: a plain run sets up, "
+                         "warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/*.npy (losses, grad norm, seeded samples of the "
+                         "gradients and updated weights; bench.dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_gemm_profile = args.no_box = args.no_secondary = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -363,9 +408,11 @@ def main():
             with socket.socket() as sk:
                 sk.bind(("127.0.0.1", 0))
                 port = sk.getsockname()[1]
+            # (a fresh child process, not exec: this process has already opened the GPU runtime to count devices)
+            import subprocess
             os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-            os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                      "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+            raise SystemExit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                                              "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
         raise SystemExit(f"--gpus {args.gpus} does not match WORLD_SIZE={world}")
     # stdout carries exactly ONE line, the JSON: native libraries that print to fd 1 (RCCL's version banner at communicator
     # creation) are pointed at stderr for the whole run, the line itself goes to the saved descriptor
@@ -454,14 +501,15 @@ def main():
         # (cold) calibration before the warm-up, 300 ms: the random-operand MFMA stream from a chip that has been idle
         strat.synchronize()
         torch.cuda.synchronize()
-        box = {"mfma_random_pflops_cold": round(hip.calib_mfma(device)["pflops"], 4)}
+        with torch.random.fork_rng(devices=[dev_index]):     # its random operands leave the steps' noise / timestep draws as in a plain run
+            box = {"mfma_random_pflops_cold": round(hip.calib_mfma(device)["pflops"], 4)}
     for _ in range(args.warmup):
         losses = strat.train_step(batch)
     prof = None if args.no_gemm_profile else []
     sampler = BoxSampler(dev_index) if box is not None else None
     strat.synchronize()                        # flush the warm-up's deferred optimizer updates: the timed region owns exactly K of them
     sync()
-    if strat.sharded.coll:
+    if strat.sharded.coll and args.full:
         # time every stall of the compute stream behind a reduce-scatter / all-gather event -- switched on AFTER the flush above, so the
         # warm-up's exposed all-gather waits are not divided into the K timed steps (advisor, round 4)
         strat.sharded.wait_profile = []
@@ -500,8 +548,10 @@ def main():
         box.update({"mfma_random_pflops": round(cal["pflops"], 4), "mfma_calibration": f"{cal['launches']} launches x {cal['ms_per_launch']:.1f} ms on "
                     f"{cal['blocks']} workgroups x 8 waves, v_mfma_f32_16x16x32_bf16 on N(0,1) operands from registers (mla_calib_mfma), last 200 ms of 300",
                     "device": torch.cuda.get_device_name(dev_index)})
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, strat, losses)
     per_rank = None
-    if strat.sharded.coll:
+    if strat.sharded.coll and args.full:
         # first-run diagnosis for N > 1 (VERDICT r3 #3d): every rank's own step time and how long ITS compute stream sat behind
         # collectives -- rs_event = the backward's reduce-scatters not finished when clipping starts (exposed communication),
         # gather_event = a layer's bf16 all-gather (issued behind AdamW) not finished when the next forward reaches the layer

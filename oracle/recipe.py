@@ -156,3 +156,38 @@ def make_rlds_sample(window: int = 1, with_wrist: bool = False, with_tactile: bo
 
 RLDS_CASES = {"plain": dict(), "window3_wrist": dict(window=3, with_wrist=True), "tactile_pc": dict(with_tactile=True, with_pc=True),
               "no_action_tok": dict(), "no_stop": dict(window=2)}
+
+
+def collator_batches(seed: int = 0) -> dict:
+    """Instances for PaddedCollatorForActionPrediction (util/data_utils.py:88-196), model_max_length 12, pad id 512: three of
+    lengths 9 / 14 / 5 (one padded, one truncated) without and with the tactile fields. {tactile: [instance, ...]}; the golden
+    tests/golden/collator.npz holds the reference collator's output on exactly these (oracle/capture_golden_collator.py)."""
+    g = torch.Generator().manual_seed(seed)
+
+    def inst(n, tactile):
+        d = dict(input_ids=torch.randint(3, 100, (n,), generator=g), labels=torch.randint(3, 100, (n,), generator=g),
+                 images={"front_image": torch.randn(4, 8, 8, generator=g)}, next_images={"front_image": torch.randn(3, 8, 8, generator=g)},
+                 point_cloud=torch.randn(16, 3, generator=g), next_point_cloud=torch.randn(16, 3, generator=g),
+                 actions=torch.randn(1, 7, generator=g), action_masks=torch.ones(1, dtype=torch.bool), proprio=torch.randn(1, 7, generator=g),
+                 dataset_name="rlbench")
+        if tactile:
+            d.update(tactile=torch.randn(12, generator=g), gripper_xyz=torch.randn(3, generator=g), next_tactile=torch.randn(12, generator=g))
+        return d
+    return {tactile: [inst(9, tactile), inst(14, tactile), inst(5, tactile)] for tactile in (False, True)}
+
+
+def collator_to_arrays(out: dict, prefix: str) -> dict:
+    """A collated batch as plain numpy arrays (no pickled objects): tensors as they are, dict fields per key, None as the string
+    "None", lists as string arrays; `<prefix>::__keys__` lists the batch's keys."""
+    res = {f"{prefix}::__keys__": np.array(sorted(out))}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            res[f"{prefix}::{k}"] = v.numpy()
+        elif isinstance(v, dict):
+            for kk, t in v.items():
+                res[f"{prefix}::{k}.{kk}"] = t.numpy()
+        elif v is None:
+            res[f"{prefix}::{k}"] = np.array("None")
+        else:
+            res[f"{prefix}::{k}"] = np.array([str(x) for x in v])
+    return res

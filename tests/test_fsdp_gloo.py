@@ -7,6 +7,7 @@ identical fp32 master weights after gathering the shards, global grad-norm clip,
 import os
 import socket
 
+import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
@@ -173,6 +174,44 @@ def test_sharded_model_world1_matches_adamw():
     sm.begin_step()
     sm.finish_backward()
     assert all(float(p.main_grad.abs().max()) == 0.0 for p in model.parameters() if p.requires_grad)
+
+
+def test_bench_dump_outputs_writes_the_last_step(tmp_path):
+    """bench.py --dump-outputs: the loss dict, the grad norm and seeded samples of the gradient / updated fp32 weights, as float64 /
+    float32 .npy files; the positions depend only on the layout, so two dumps of the same state are identical."""
+    import bench
+    from mla_amd.fsdp import ShardedModel
+    model = _make()
+    sm = ShardedModel(model, lambda mod: isinstance(mod, Block), torch.device("cpu"), ops=TorchLocalOps())
+    sm.begin_step()
+    loss = model(torch.randn(4, 10).to(torch.bfloat16)).float().pow(2).mean()
+    loss.backward()
+    for p in model.parameters():
+        if p.requires_grad:
+            p.main_grad.copy_(p.grad.float())
+            p._mg_touched = True
+            p.grad = None
+    sm.finish_backward()
+    sm.grad_norm_and_clip(1.0)
+    sm.optimizer_step(1e-2)
+    strat = type("Strat", (), {"sharded": sm})()
+    losses = {"total_loss": loss.detach(), "unused": None}
+    units = [u for u in sm.units if u.trainable]
+    bench.dump_outputs(str(tmp_path / "a"), strat, losses)
+    for d in "bc":
+        bench.dump_outputs(str(tmp_path / d), strat, losses, max_bytes=(1 << 20) + 2 * 4 * 4 * len(units))
+    a = {f.name: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert set(a) == {"loss_total_loss.npy", "grad_norm.npy", "grad_sample.npy", "param_sample.npy"}
+    assert a["loss_total_loss.npy"].dtype == np.float64 and float(a["loss_total_loss.npy"]) == float(loss)
+    assert a["grad_norm.npy"].dtype == np.float64 and float(a["grad_norm.npy"]) == float(sm._norm)
+    assert a["grad_sample.npy"].dtype == a["param_sample.npy"].dtype == np.float32
+    assert a["grad_sample.npy"].size == sum(u.master_train.numel() for u in units)      # small units: every element
+    assert np.array_equal(a["param_sample.npy"], torch.cat([u.master_train for u in units]).numpy())
+    assert np.array_equal(a["grad_sample.npy"], torch.cat([u.gshard for u in units]).numpy())
+    b = {f.name: np.load(f) for f in (tmp_path / "b").iterdir()}
+    assert b["grad_sample.npy"].size == 4 * len(units)                                 # the byte budget caps the sample
+    assert np.array_equal(b["loss_total_loss.npy"], a["loss_total_loss.npy"])
+    assert all(np.array_equal(np.load(tmp_path / "c" / f), b[f]) for f in b)             # seeded positions: same sample again
 
 
 def test_hook_launched_reduce_scatter_zeroes_stale_gradients_and_locks_the_unit():

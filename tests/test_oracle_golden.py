@@ -286,8 +286,15 @@ def test_mla_e2e_pretrain_stage_matches_reference(pc):
     assert abs(float(out["total_loss"]) - float(gold["A_total_loss"])) < (1e-4 if pc else 2e-5)
     out["total_loss"].backward()
     norms = np.array([0.0 if sd[n].grad is None else float(sd[n].grad.norm()) for n in names])
-    # a convolution bias in front of a train-mode BatchNorm has an exactly-zero gradient: the 1e-7 the reference holds there is rounding
-    assert np.allclose(norms, gold["A_gradnorms"], rtol=3e-3, atol=2e-6 if pc else 1e-7)
+    # a convolution bias in front of a train-mode BatchNorm has an exactly-zero gradient: what either side holds there is the rounding of
+    # a 165888-row fp32 sum, set by the summation order (1e-8 .. 3e-6 on one and the same host, by thread count), not a value to match.
+    # It must be zero to rounding on both sides: <= 2e-5 of the same convolution's weight gradient (the reference's worst is 7.7e-6)
+    zero = np.array([n.endswith(".0.bias") and "EncP" in n for n in names])
+    ix = {n: i for i, n in enumerate(names)}
+    for n in np.array(names)[zero]:
+        w = ix[n[:-len("bias")] + "weight"]
+        assert norms[ix[n]] <= 2e-5 * norms[w] and gold["A_gradnorms"][ix[n]] <= 2e-5 * gold["A_gradnorms"][w], n
+    assert np.allclose(norms[~zero], gold["A_gradnorms"][~zero], rtol=3e-3, atol=1e-7)
     for key in gold.files:
         if key.startswith("A_grad::"):
             n = key[len("A_grad::"):]

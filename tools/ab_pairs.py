@@ -14,7 +14,7 @@ def run(spec, steps, warmup, config):
     for kv in envs.split():
         k, _, v = kv.partition("=")
         env[k] = v
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--config", str(config), "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--config", str(config), "--full", "--no-cpu-baseline",
            "--no-secondary", "--no-gemm-profile"] + flags.split()
     cp = subprocess.run(cmd, capture_output=True, text=True, env=env)
     line = [ln for ln in cp.stdout.splitlines() if ln.startswith("{")]

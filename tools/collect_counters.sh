@@ -11,12 +11,12 @@ cd /tmp; export TMPDIR=/tmp
 # (c) first: un-profiled run with the sampler beside it
 ( for i in $(seq 1 400); do rocm-smi --showpower --showclocks --json 2>/dev/null | tr -d '\n'; echo; sleep 0.2; done ) > $O/${TAG}_power_samples.jsonl &
 SP=$!
-python $R/bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-secondary > $O/${TAG}_bench_config1_power_run.json 2> /dev/null
+python $R/bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-secondary > $O/${TAG}_bench_config1_power_run.json 2> /dev/null
 kill $SP 2>/dev/null
 python $R/tools/power_summary.py $O/${TAG}_power_samples.jsonl $O/${TAG}_bench_config1_power_run.json > $O/${TAG}_power_trace.txt
 # (a)
 rm -rf /tmp/prof_$TAG
-rocprofv3 --kernel-trace --stats --output-format csv rocpd -d /tmp/prof_$TAG -o p -- python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-secondary > $O/${TAG}_bench_config1_profiled.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv rocpd -d /tmp/prof_$TAG -o p -- python $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-secondary > $O/${TAG}_bench_config1_profiled.json 2>/dev/null
 python $R/tools/step_breakdown.py $(find /tmp/prof_$TAG -name "*.db" | head -1) 1 60 > $O/${TAG}_step_breakdown_config1.txt
 cp $(find /tmp/prof_$TAG -name "*kernel_stats.csv" | head -1) $O/${TAG}_bench7b_config1_kernel_stats.csv
 python $R/tools/roofline_table.py $O/${TAG}_step_breakdown_config1.txt > $O/${TAG}_roofline_table.txt

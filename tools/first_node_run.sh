@@ -56,10 +56,10 @@ bench() {   # bench <tag> <N> [ENV=VAL ...]
   local tag=$1 n=$2; shift 2
   local port=$((29600 + RANDOM % 300))
   if [ "$n" = 1 ]; then
-    env "$@" timeout 1500 python "$R/bench.py" --gpus 1 --steps $STEPS --warmup $WARMUP --no-cpu-baseline --no-secondary > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err"
+    env "$@" timeout 1500 python "$R/bench.py" --full --gpus 1 --steps $STEPS --warmup $WARMUP --no-cpu-baseline --no-secondary > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err"
   else
     env "$@" timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $port \
-      "$R/bench.py" --gpus $n --steps $STEPS --warmup $WARMUP > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err"
+      "$R/bench.py" --full --gpus $n --steps $STEPS --warmup $WARMUP > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err"
   fi
   local rc=$?
   log "   bench $tag (N=$n $*): rc=$rc $(python -c "import json,sys; d=json.loads(open('$OUT/bench_$tag.json').read().strip().splitlines()[-1]); print(d['ms_per_step'], 'ms', d['value'], d['unit'], (d.get('per_rank') or {}).get('rs_event_wait_ms_per_step'))" 2>/dev/null)"
