@@ -273,6 +273,19 @@ int mla_gemv_bf16(const void* x, long long ldx, const void* W, long long ldw, vo
  *   Replaces the attention of modeling_llama.py:371-380 for the suffix rows. */
 int mla_attn_decode(const void* q, const void* k, const void* v, void* o, int B, int H, int head_dim, int S_kv, int R, long long ld,
                     long long batch_stride, long long ld_o, float scale, mla_stream_t stream);
+/* mla_gemm_skinny_bf16: mla_gemv_bf16's contract (same arguments, output addressing, pre modes and RoPE epilogue) for 1 <= M <= 64 rows
+ *   and any K % 8 == 0: W is read exactly once (16 B per lane, non-temporal, straight into the A operands of v_mfma_f32_16x16x32_bf16),
+ *   the x rows are the B operands (read per 16-row W tile, nothing staged: LDS does not grow with K), fp32 accumulation. Deterministic:
+ *   every output is one fixed-order sum of the K-range partials of 8 waves, no atomics, no workspace. With pre = 1 / 2 the operand values
+ *   are bit for bit what mla_rmsnorm_fwd / mla_swiglu_fwd write. The suffix pass of an action chunk of 8 .. 63 rows. */
+int mla_gemm_skinny_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
+                         int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre, const void* pre_w, float eps,
+                         const float* rope_cos, const float* rope_sin, int rope_cols, mla_stream_t stream);
+/* mla_attn_chunk: mla_attn_decode's contract for 1 <= R <= 64 query rows and any S_kv >= R: online softmax over key tiles of 64 (LDS does
+ *   not grow with S_kv), QK^T and PV on the MFMA pipe, P rounded to bf16 before P V like the flash kernel; the key tiles are shared out
+ *   over 4 waves per (sample, head, 16 queries) and their softmax states merged in a fixed order (deterministic, graph-capturable). */
+int mla_attn_chunk(const void* q, const void* k, const void* v, void* o, int B, int H, int head_dim, int S_kv, int R, long long ld,
+                   long long batch_stride, long long ld_o, float scale, mla_stream_t stream);
 
 /* ---- losses: CrossEntropyLoss modeling_llama.py:1258-1269; InfoNCE models/mla/fuser/contrastive.py:208-215 */
 int mla_ce_fwd(const void* logits, int logits_fp32, long long ld, const long long* labels, float* loss, float* lse, int rows,

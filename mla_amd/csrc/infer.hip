@@ -7,7 +7,11 @@
 //                      one wave per row pair, 256 B per lane in flight; x lives in LDS as bf16; fp32 accumulation.
 //   mla_attn_decode    R <= 8 new query rows per (sample, head) against the cached keys / values [0, S_kv - R + r]: scores -> LDS,
 //                      softmax per query, P V with 4 key slices per block; head_dim 128.
-// Both are HBM-bound by construction: algorithmic bytes = the weight matrix (gemv) / the K and V rows of the head (decode).
+//   mla_gemm_skinny_bf16  the gemv contract for 1 <= M <= 64 rows and any K: W straight into MFMA A operands, x rows as B operands, no
+//                      staging; 8 waves split K per 16-row tile.
+//   mla_attn_chunk     the decode contract for 1 <= R <= 64 rows and any S_kv: online softmax over 64-key tiles, MFMA QK^T / PV.
+// infer.py keeps gemv / decode for every shape they accept and uses the other two beyond (action chunks of 8..63 steps).
+// All are HBM-bound by construction: algorithmic bytes = the weight matrix (gemv) / the K and V rows of the head (decode).
 #include "common.h"
 
 namespace {
@@ -317,6 +321,298 @@ __global__ __launch_bounds__(64 * DEC_NW) void attn_decode_kernel(const bf16_t* 
   }
 }
 
+// ---- skinny GEMM for 1 <= M <= 64 rows (the suffix pass of an action chunk of up to 63 rows): same contract as gemv_kernel.
+// One workgroup per 16-row W tile, SK_NW waves splitting K into contiguous ranges of 32-wide steps; per step and lane one 16-B
+// non-temporal load of W straight into the A fragment of v_mfma_f32_16x16x32_bf16 (lane l: W row l & 15, k = 8 (l >> 4) .. + 7) and one
+// 16-B load of each 16-row block of x into the B fragment (x row l & 15 of the block, the same k), so every W byte is read once per pass
+// and nothing of x is staged: LDS holds only the waves' partial tiles (fixed-order sum over the waves), the rstd of the fused RMSNorm and
+// its reduction scratch, whatever K is. x is re-read once per tile from L2 (M / 16 times the W bytes).
+// PRE 1 computes each row's rstd in a prologue in rmsnorm_fwd_kernel's exact order (256 "threads" x 8-element chunks, wave sums,
+// wave partials summed in order), PRE 2 forms silu(gate) * up per element with swiglu_fwd_elem: the B fragments hold the same bf16
+// values the separate kernels would write. In the rotary columns a tile is rows d .. d + 7 and d + 64 .. d + 71 of one head (d = 8 j),
+// so that the epilogue holds both halves of every rotate-half pair.
+constexpr int SK_MMAX = 64;
+constexpr int SK_NW = 8;
+__device__ __forceinline__ bf16x8_t as_frag(const u32x4_t v) { return __builtin_bit_cast(bf16x8_t, v); }
+template <int MB, int PRE>
+__global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* __restrict__ x, long long ldx, const bf16_t* __restrict__ W,
+                                                                 long long ldw, bf16_t* __restrict__ out, long long ldo, long long out_bs, int rpb,
+                                                                 const bf16_t* __restrict__ res, long long ld_res, int M, int N, int K,
+                                                                 const bf16_t* __restrict__ pre_w, float eps, const float* __restrict__ rope_cos,
+                                                                 const float* __restrict__ rope_sin, int rope_cols) {
+  constexpr int NB = MB * (PRE == 2 ? 2 : 1);                        // x loads per K step
+  constexpr int U = NB <= 2 ? 8 : (NB <= 4 ? 4 : 2);                 // K steps whose loads are issued before the first MFMA
+  __shared__ __attribute__((aligned(16))) float lds[SK_NW * MB * 256 + SK_MMAX + 32];   // ONE array: partial tiles | rstd | scratch
+  float* rstd = lds + SK_NW * MB * 256;
+  float* scr = rstd + SK_MMAX;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
+  if (PRE == 1) {
+    // two rows at a time per 8-row round (threads 0-255 and 256-511 each play rmsnorm_fwd_kernel's 256 threads on one row)
+    const int half = threadIdx.x >> 8, vt = threadIdx.x & 255, kc = K >> 3;
+    for (int m0 = 0; m0 < M; m0 += 8) {
+      float ss[4] = {0.f, 0.f, 0.f, 0.f};
+      for (int c = vt; c < kc; c += 256) {
+        u32x4_t v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int m = m0 + half + 2 * i;
+          v[i] = *(const u32x4_t*)(x + (long long)(m < M ? m : M - 1) * ldx + c * 8);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          float f[8];
+          unpack8f(v[i], f);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) ss[i] += f[j] * f[j];
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) ss[i] = wave_sum(ss[i]);
+      if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) scr[(i * 2 + half) * 4 + (vt >> 6)] = ss[i];
+      }
+      __syncthreads();
+      if (threadIdx.x < 8) {
+        const int i = threadIdx.x >> 1, hh = threadIdx.x & 1, m = m0 + hh + 2 * i;
+        if (m < M) {
+          float r = 0.f;
+          for (int w = 0; w < 4; ++w) r += scr[(i * 2 + hh) * 4 + w];
+          rstd[m] = 1.0f / sqrtf(r / (float)K + eps);
+        }
+      }
+      __syncthreads();
+    }
+  }
+  const int tile = blockIdx.x;
+  const bool rot = rope_cos != nullptr && tile * 16 < rope_cols;
+  const int nrow = rot ? (tile >> 3) * 128 + ((li & 8) ? 64 : 0) + (tile & 7) * 8 + (li & 7) : tile * 16 + li;
+  const bf16_t* wr = W + (long long)(nrow < N ? nrow : N - 1) * ldw;
+  const bf16_t* xr[MB];
+  bool xok[MB];
+  float xrs[MB];
+#pragma unroll
+  for (int mb = 0; mb < MB; ++mb) {
+    const int m = mb * 16 + li;
+    xok[mb] = m < M;
+    xr[mb] = x + (long long)(xok[mb] ? m : 0) * ldx;
+    xrs[mb] = (PRE == 1 && xok[mb]) ? rstd[m] : 0.f;
+  }
+  const int steps = (K + 31) >> 5, spw = (steps + SK_NW - 1) / SK_NW;
+  const int s_beg = wave * spw, s_end = s_beg + spw < steps ? s_beg + spw : steps;
+  f32x4_t acc[MB];
+#pragma unroll
+  for (int mb = 0; mb < MB; ++mb) acc[mb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  const u32x4_t zero = {0u, 0u, 0u, 0u};
+  for (int s0 = s_beg; s0 < s_end; s0 += U) {
+    u32x4_t a[U], b[U][NB], nw[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int k = (s0 + u) * 32 + g * 8;
+      const bool ok = s0 + u < s_end && k < K;
+      a[u] = ok ? __builtin_nontemporal_load((const u32x4_t*)(wr + k)) : zero;
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb) {
+        b[u][mb] = ok && xok[mb] ? *(const u32x4_t*)(xr[mb] + k) : zero;
+        if (PRE == 2) b[u][MB + mb] = ok && xok[mb] ? *(const u32x4_t*)(xr[mb] + K + k) : zero;
+      }
+      if (PRE == 1) nw[u] = ok ? *(const u32x4_t*)(pre_w + k) : zero;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (s0 + u < s_end) {                                          // wave-uniform
+        float wv[8];
+        if (PRE == 1) unpack8f(nw[u], wv);
+#pragma unroll
+        for (int mb = 0; mb < MB; ++mb) {
+          u32x4_t bv = b[u][mb];
+          if (PRE == 1) {
+            float f[8], o[8];
+            unpack8f(bv, f);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = wv[j] * bf2f(f2bf(f[j] * xrs[mb]));
+            bv = pack8f(o);
+          } else if (PRE == 2) {
+            float gg[8], uu[8], o[8];
+            unpack8f(bv, gg);
+            unpack8f(b[u][MB + mb], uu);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = swiglu_fwd_elem(gg[j], uu[j]);
+            bv = pack8f(o);
+          }
+          acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(a[u]), as_frag(bv), acc[mb], 0, 0, 0);
+        }
+      }
+    }
+  }
+  // partial tiles -> LDS; D[n][m] of block mb sits in lane (n >> 2) * 16 + (m & 15), register n & 3
+#pragma unroll
+  for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) lds[((wave * MB + mb) * 4 + r) * 64 + lane] = acc[mb][r];
+  __syncthreads();
+  for (int e = threadIdx.x; e < 16 * MB * 16; e += 64 * SK_NW) {
+    const int m = e % (MB * 16), i = e / (MB * 16);
+    const int n = rot ? (tile >> 3) * 128 + ((i & 8) ? 64 : 0) + (tile & 7) * 8 + (i & 7) : tile * 16 + i;
+    if (m >= M || n >= N) continue;
+    const int mb = m >> 4, col = m & 15;
+    float v = 0.f, partner = 0.f;
+#pragma unroll
+    for (int w = 0; w < SK_NW; ++w) v += lds[((w * MB + mb) * 4 + (i & 3)) * 64 + (i >> 2) * 16 + col];
+    if (res) v += bf2f(res[(long long)m * ld_res + n]);
+    if (rot) {
+      const int ip = i ^ 8;
+#pragma unroll
+      for (int w = 0; w < SK_NW; ++w) partner += lds[((w * MB + mb) * 4 + (ip & 3)) * 64 + (ip >> 2) * 16 + col];
+      // gemv_kernel's epilogue: rope_kernel's arithmetic on the bf16-rounded projection
+      const int d = n & 63, pos = m % rpb;
+      const float c = rope_cos[pos * 64 + d], sn = rope_sin[pos * 64 + d];
+      const float me = bf2f(f2bf(v)), other = bf2f(f2bf(partner));
+      v = i < 8 ? fmaf(me, c, -(other * sn)) : fmaf(me, c, other * sn);
+    }
+    out[(long long)(m / rpb) * out_bs + (long long)(m % rpb) * ldo + n] = f2bf(v);
+  }
+}
+
+// ---- suffix attention for 1 <= R <= 64 query rows: one workgroup per (sample, head, block of 16 queries), CH_NW waves taking the key
+// tiles of 64 in turn, each with its own online softmax (running max / sum per query, exp2 with the scale folded in); the waves' states
+// are merged in a fixed order at the end, so LDS does not grow with S_kv. The forward flash kernel's fragment layout: S^T = K Q^T (K rows
+// straight from global memory into the A fragments, Q in registers as the B fragments), P^T packed from the score registers as they are
+// (key order of pack_frag), O^T = V^T P^T with V^T read from a per-wave LDS transpose of the 64-row V tile. Every lane owns one query
+// (l & 15): the softmax needs two cross-lane steps per tile.
+constexpr int CH_RMAX = 64;
+constexpr int CH_NW = 4;
+constexpr int CH_VP = 68;                                              // V^T row pitch in keys (136 B: 8-B aligned, staggered banks)
+__device__ __forceinline__ bf16x8_t pack_pfrag(const f32x4_t lo, const f32x4_t hi) {
+  u32x4_t u;
+  u[0] = pack2bf(lo[0], lo[1]); u[1] = pack2bf(lo[2], lo[3]);
+  u[2] = pack2bf(hi[0], hi[1]); u[3] = pack2bf(hi[2], hi[3]);
+  return as_frag(u);
+}
+__global__ __launch_bounds__(64 * CH_NW) void attn_chunk_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+                                                                bf16_t* __restrict__ o, int H, int S_kv, int R, long long ld, long long bs,
+                                                                long long ld_o, float scale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int QB = (R + 15) >> 4;
+  const int qb = blockIdx.x % QB, bh = blockIdx.x / QB, h = bh % H, b = bh / H;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
+  bf16_t* vt = (bf16_t*)smem + wave * 128 * CH_VP;                    // this wave's V tile, transposed: [128 channels][CH_VP keys]
+  const bf16_t* kb = k + b * bs + h * 128;
+  const bf16_t* vb = v + b * bs + h * 128;
+  const int r = qb * 16 + li;
+  const bool qok = r < R;
+  const int qpos = S_kv - R + (qok ? r : R - 1);                       // last key this query sees (padding queries: the last row's)
+  const u32x4_t zero = {0u, 0u, 0u, 0u};
+  bf16x8_t qf[4];
+  {
+    const bf16_t* qr = q + b * bs + (long long)(S_kv - R + (qok ? r : 0)) * ld + h * 128;
+#pragma unroll
+    for (int ds = 0; ds < 4; ++ds) qf[ds] = as_frag(qok ? *(const u32x4_t*)(qr + ds * 32 + g * 8) : zero);
+  }
+  const float sc2 = scale * 1.4426950408889634f;
+  f32x4_t ot[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ot[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;
+  const int ntiles = (S_kv + 63) >> 6, iters = (ntiles + CH_NW - 1) / CH_NW;
+  for (int it = 0; it < iters; ++it) {                                  // same trip count in every wave: the barriers below are uniform
+    const int j0 = (it * CH_NW + wave) * 64;                            // beyond S_kv: clamped loads, every score masked
+    u32x4_t kf[4][4], vv[16];
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      const int j = j0 + f * 16 + li;
+      const bf16_t* kr = kb + (long long)(j < S_kv ? j : S_kv - 1) * ld + g * 8;
+#pragma unroll
+      for (int ds = 0; ds < 4; ++ds) kf[f][ds] = *(const u32x4_t*)(kr + ds * 32);
+    }
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int j = j0 + u * 4 + g;
+      vv[u] = *(const u32x4_t*)(vb + (long long)(j < S_kv ? j : S_kv - 1) * ld + li * 8);
+    }
+    f32x4_t st[4];
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      st[f] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ds = 0; ds < 4; ++ds) st[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(kf[f][ds]), qf[ds], st[f], 0, 0, 0);
+    }
+    // S^T[key][query]: lane holds query li, keys j0 + 16 f + 4 g + reg; key j visible iff j <= qpos (< S_kv)
+    float mx = -INFINITY;
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        if (j0 + f * 16 + g * 4 + rr > qpos) st[f][rr] = -INFINITY;
+        mx = fmaxf(mx, st[f][rr]);
+      }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float mnew = fmaxf(m, mx * sc2);
+    const float msafe = mnew == -INFINITY ? 0.f : mnew;
+    const float alpha = __builtin_amdgcn_exp2f(m - msafe);
+    float ps = 0.f;
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        st[f][rr] = __builtin_amdgcn_exp2f(fmaf(st[f][rr], sc2, -msafe));
+        ps += st[f][rr];
+      }
+    ps += __shfl_xor(ps, 16, 64);
+    ps += __shfl_xor(ps, 32, 64);
+    l = l * alpha + ps;
+    m = mnew;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ot[i] *= alpha;
+    const bf16x8_t pf0 = pack_pfrag(st[0], st[1]), pf1 = pack_pfrag(st[2], st[3]);
+    // V tile -> LDS transposed (lane: key 4 u + g, channels 8 li .. + 7)
+#pragma unroll
+    for (int u = 0; u < 16; ++u)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        vt[(li * 8 + 2 * e) * CH_VP + u * 4 + g] = (bf16_t)(vv[u][e] & 0xffffu);
+        vt[(li * 8 + 2 * e + 1) * CH_VP + u * 4 + g] = (bf16_t)(vv[u][e] >> 16);
+      }
+    __syncthreads();
+#pragma unroll
+    for (int fd = 0; fd < 8; ++fd) {
+      const bf16_t* vr = vt + (fd * 16 + li) * CH_VP + g * 4;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const u32x2_t lo = *(const u32x2_t*)(vr + ks * 32), hi = *(const u32x2_t*)(vr + ks * 32 + 16);
+        const u32x4_t av = {lo[0], lo[1], hi[0], hi[1]};
+        ot[fd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(av), ks ? pf1 : pf0, ot[fd], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+  // merge the waves' (max, sum, O^T) in wave order; O^T[d][query] of wave w: lane (d & 15) >> 2 ... as the MFMA left it
+  float* mo = (float*)smem;                                             // [CH_NW][128][16]
+  float* ml = mo + CH_NW * 128 * 16;                                    // [CH_NW][16] max, then [CH_NW][16] sum
+#pragma unroll
+  for (int fd = 0; fd < 8; ++fd)
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) mo[(wave * 128 + fd * 16 + g * 4 + rr) * 16 + li] = ot[fd][rr];
+  if (g == 0) { ml[wave * 16 + li] = m; ml[CH_NW * 16 + wave * 16 + li] = l; }
+  __syncthreads();
+  for (int e = threadIdx.x; e < 128 * 16; e += 64 * CH_NW) {
+    const int qq = e & 15, d = e >> 4, rq = qb * 16 + qq;
+    if (rq >= R) continue;
+    float mm = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < CH_NW; ++w) mm = fmaxf(mm, ml[w * 16 + qq]);    // finite: wave 0's first tile holds key 0, seen by every query
+    float L = 0.f, O = 0.f;
+#pragma unroll
+    for (int w = 0; w < CH_NW; ++w) {
+      const float fw = __builtin_amdgcn_exp2f(ml[w * 16 + qq] - mm);
+      L += fw * ml[CH_NW * 16 + w * 16 + qq];
+      O += fw * mo[(w * 128 + d) * 16 + qq];
+    }
+    o[(long long)(b * R + rq) * ld_o + h * 128 + d] = f2bf(O / L);
+  }
+}
+
 }  // namespace
 
 #define AL16(p) ((((uintptr_t)(p)) & 15) == 0)
@@ -372,5 +668,45 @@ extern "C" int mla_attn_decode(const void* q, const void* k, const void* v, void
   if (!attr) { (void)hipFuncSetAttribute((const void*)attn_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
   hipLaunchKernelGGL(attn_decode_kernel, dim3(B * H), dim3(64 * DEC_NW), lds, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, H, S_kv,
                      R, ld, batch_stride, ld_o, scale);
+  MLA_LAUNCH_CHECK();
+}
+
+extern "C" int mla_gemm_skinny_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
+                                    int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre, const void* pre_w,
+                                    float eps, const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
+  MLA_CHECK_ARG(x && W && out, "mla_gemm_skinny_bf16: null pointer");
+  MLA_CHECK_ARG((rope_cos == nullptr) == (rope_sin == nullptr) && (!rope_cos || (rope_cols > 0 && rope_cols % 128 == 0 && rope_cols <= N && !residual)),
+                "mla_gemm_skinny_bf16: the RoPE epilogue needs both tables, rope_cols a multiple of 128 and <= N, and no residual");
+  MLA_CHECK_ARG(pre >= 0 && pre <= 2 && (pre != 1 || (pre_w && AL16(pre_w))),
+                "mla_gemm_skinny_bf16: pre must be 0, 1 (RMSNorm: 16-B aligned weight needed) or 2 (SwiGLU)");
+  MLA_CHECK_ARG(M >= 1 && M <= SK_MMAX && N >= 1 && K >= 8 && K % 8 == 0 && rows_per_batch >= 1,
+                "mla_gemm_skinny_bf16: 1 <= M <= 64, K %% 8 == 0 required (M %d, N %d, K %d)", M, N, K);
+  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && ldw % 8 == 0, "mla_gemm_skinny_bf16: x / W rows must be 16-B aligned");
+  const int tiles = (N + 15) / 16;
+#define MLA_SK_LAUNCH(MB, PP)                                                                                                          \
+  hipLaunchKernelGGL((gemm_skinny_kernel<MB, PP>), dim3(tiles), dim3(64 * SK_NW), 0, stream, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw,     \
+                     (bf16_t*)out, ldo, out_batch_stride, rows_per_batch, (const bf16_t*)residual, ld_res, M, N, K, (const bf16_t*)pre_w, eps, \
+                     rope_cos, rope_sin, rope_cos ? rope_cols : 0)
+#define MLA_SK_CASE(MB)                                                                                                                \
+  case MB:                                                                                                                             \
+    if (pre == 0) MLA_SK_LAUNCH(MB, 0); else if (pre == 1) MLA_SK_LAUNCH(MB, 1); else MLA_SK_LAUNCH(MB, 2);                              \
+    break;
+  switch ((M + 15) / 16) { MLA_SK_CASE(1) MLA_SK_CASE(2) MLA_SK_CASE(3) MLA_SK_CASE(4) }
+#undef MLA_SK_CASE
+#undef MLA_SK_LAUNCH
+  MLA_LAUNCH_CHECK();
+}
+
+extern "C" int mla_attn_chunk(const void* q, const void* k, const void* v, void* o, int B, int H, int head_dim, int S_kv, int R, long long ld,
+                              long long batch_stride, long long ld_o, float scale, hipStream_t stream) {
+  MLA_CHECK_ARG(q && k && v && o, "mla_attn_chunk: null pointer");
+  MLA_CHECK_ARG(head_dim == 128, "mla_attn_chunk: head_dim must be 128 (got %d)", head_dim);
+  MLA_CHECK_ARG(B >= 1 && H >= 1 && R >= 1 && R <= CH_RMAX && S_kv >= R, "mla_attn_chunk: 1 <= R <= 64, R <= S_kv required (R %d, S_kv %d)", R, S_kv);
+  MLA_CHECK_ARG(AL16(q) && AL16(k) && AL16(v) && ld % 8 == 0 && batch_stride % 8 == 0 && ld_o % 2 == 0, "mla_attn_chunk: 16-B aligned rows required");
+  const size_t lds = (size_t)CH_NW * 128 * CH_VP * 2;                  // >= the merge buffers ((CH_NW * 128 * 16 + 2 * CH_NW * 16) * 4)
+  static bool attr = false;
+  if (!attr) { (void)hipFuncSetAttribute((const void*)attn_chunk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
+  hipLaunchKernelGGL(attn_chunk_kernel, dim3(B * H * ((R + 15) / 16)), dim3(64 * CH_NW), lds, stream, (const bf16_t*)q, (const bf16_t*)k,
+                     (const bf16_t*)v, (bf16_t*)o, H, S_kv, R, ld, batch_stride, ld_o, scale);
   MLA_LAUNCH_CHECK();
 }

@@ -35,6 +35,10 @@ _SIGNATURES = {
                       c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
     "mla_attn_decode": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_float,
                         c_void_p],
+    "mla_gemm_skinny_bf16": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_longlong, c_int,
+                             c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
+    "mla_attn_chunk": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_float,
+                       c_void_p],
     "mla_gemm_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                       c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
     "mla_gemm_bf16_ws": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -789,33 +793,51 @@ def attn_bwd(q, k, v, o, dout, lse, seqlens, dq, dk, dv, B, S, H, D, ld_qkv, sca
 
 
 # --------------------------------------------------------------------------------------------- inference (mla_amd/infer.py)
-def gemv(x, W, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, norm_weight=None, eps=0.0, swiglu=False, rope=None):
-    """out row m (at out + (m // rows_per_batch) * out_batch_stride + (m % rows_per_batch) * ldo + out_col) = f(x[m]) @ W^T (+ residual[m]);
-    M <= 8 rows, every weight row read once (mla_gemv_bf16). `out` is a base tensor: only its data pointer is used.
-    f = identity; or LlamaRMSNorm(x; norm_weight, eps); or (swiglu=True, x = packed gate|up rows [M, 2 K]) silu(gate) * up.
-    rope = (cos [rows_per_batch, 64], sin, rope_cols): output columns [0, rope_cols) are rotated per head of 128 in the epilogue."""
-    _req(x, torch.bfloat16, "gemv x")
-    _req(W, torch.bfloat16, "gemv W")
-    _req(out, torch.bfloat16, "gemv out")
+def _skinny_call(name, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope):
+    _req(x, torch.bfloat16, f"{name} x")
+    _req(W, torch.bfloat16, f"{name} W")
+    _req(out, torch.bfloat16, f"{name} out")
     M = x.shape[0]
     K = x.shape[1] // 2 if swiglu else x.shape[1]
     N = W.shape[0]
     assert W.shape[1] == K and x.stride(1) == 1 and W.stride(1) == 1 and not (swiglu and norm_weight is not None)
     pre = 2 if swiglu else (1 if norm_weight is not None else 0)
     if norm_weight is not None:
-        _req(norm_weight, torch.bfloat16, "gemv norm weight")
+        _req(norm_weight, torch.bfloat16, f"{name} norm weight")
         assert norm_weight.numel() == K and norm_weight.is_contiguous()
     if rope is not None:
-        _req(rope[0], torch.float32, "gemv rope cos")
-        _req(rope[1], torch.float32, "gemv rope sin")
+        _req(rope[0], torch.float32, f"{name} rope cos")
+        _req(rope[1], torch.float32, f"{name} rope sin")
         assert rope[0].shape == (rows_per_batch, 64) and rope[1].shape == rope[0].shape and rope[0].is_contiguous() and rope[1].is_contiguous()
         assert out_col == 0 and residual is None
     if residual is not None:
-        _req(residual, torch.bfloat16, "gemv residual")
+        _req(residual, torch.bfloat16, f"{name} residual")
         assert residual.shape[0] == M and residual.stride(1) == 1
-    call("mla_gemv_bf16", _p(x), x.stride(0), _p(W), W.stride(0), c_void_p(out.data_ptr() + 2 * out_col), ldo, out_batch_stride, rows_per_batch,
+    call(name, _p(x), x.stride(0), _p(W), W.stride(0), c_void_p(out.data_ptr() + 2 * out_col), ldo, out_batch_stride, rows_per_batch,
          _p(residual), residual.stride(0) if residual is not None else 0, M, N, K, pre, _p(norm_weight), float(eps),
          _p(rope[0]) if rope is not None else None, _p(rope[1]) if rope is not None else None, int(rope[2]) if rope is not None else 0)
+
+
+GEMV_MMAX, GEMV_LDS = 8, 160 * 1024
+
+
+def gemv_fits(M: int, K: int) -> bool:
+    """True when mla_gemv_bf16 accepts M rows of K inputs (M <= 8, the M x K bf16 rows + 64 B in LDS)."""
+    return 1 <= M <= GEMV_MMAX and M * K * 2 + 64 <= GEMV_LDS
+
+
+def gemv(x, W, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, norm_weight=None, eps=0.0, swiglu=False, rope=None):
+    """out row m (at out + (m // rows_per_batch) * out_batch_stride + (m % rows_per_batch) * ldo + out_col) = f(x[m]) @ W^T (+ residual[m]);
+    M <= 8 rows, every weight row read once (mla_gemv_bf16). `out` is a base tensor: only its data pointer is used.
+    f = identity; or LlamaRMSNorm(x; norm_weight, eps); or (swiglu=True, x = packed gate|up rows [M, 2 K]) silu(gate) * up.
+    rope = (cos [rows_per_batch, 64], sin, rope_cols): output columns [0, rope_cols) are rotated per head of 128 in the epilogue."""
+    _skinny_call("mla_gemv_bf16", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope)
+
+
+def gemm_skinny(x, W, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, norm_weight=None, eps=0.0, swiglu=False, rope=None):
+    """gemv's contract for 1 <= M <= 64 rows and any K (mla_gemm_skinny_bf16): every weight row read once, on the MFMA pipe, x never
+    staged in LDS. Same arguments, output addressing, fused RMSNorm / SwiGLU inputs and RoPE epilogue as gemv."""
+    _skinny_call("mla_gemm_skinny_bf16", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope)
 
 
 def attn_decode(cache, B, nheads, D, S_kv, R, scale):
@@ -827,6 +849,27 @@ def attn_decode(cache, B, nheads, D, S_kv, R, scale):
     o = torch.empty((B * R, H), dtype=torch.bfloat16, device=cache.device)
     base = cache.data_ptr()
     call("mla_attn_decode", c_void_p(base), c_void_p(base + 2 * H), c_void_p(base + 4 * H), _p(o), B, nheads, D, S_kv, R, cache.stride(1),
+         cache.stride(0), H, float(scale))
+    return o
+
+
+DEC_RMAX = 8
+
+
+def attn_decode_fits(R: int, S_kv: int) -> bool:
+    """True when mla_attn_decode accepts R query rows against S_kv keys (R <= 8, the R x S_kv fp32 scores + 8 R x 128 partials in LDS)."""
+    return 1 <= R <= DEC_RMAX and R <= S_kv and (R * S_kv + 8 * R * 128) * 4 <= 160 * 1024
+
+
+def attn_chunk(cache, B, nheads, D, S_kv, R, scale):
+    """attn_decode's contract for 1 <= R <= 64 query rows and any S_kv (mla_attn_chunk: online softmax over key tiles, MFMA QK^T / PV).
+    Returns o [B * R, nheads * D] bf16."""
+    _req(cache, torch.bfloat16, "attn_chunk cache")
+    H = nheads * D
+    assert cache.shape[0] == B and cache.shape[2] == 3 * H and cache.stride(2) == 1 and cache.shape[1] >= S_kv
+    o = torch.empty((B * R, H), dtype=torch.bfloat16, device=cache.device)
+    base = cache.data_ptr()
+    call("mla_attn_chunk", c_void_p(base), c_void_p(base + 2 * H), c_void_p(base + 4 * H), _p(o), B, nheads, D, S_kv, R, cache.stride(1),
          cache.stride(0), H, float(scale))
     return o
 

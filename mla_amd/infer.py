@@ -9,7 +9,8 @@ them (`text[k:]`) cannot influence the rows that are read out (`noise_pred = fin
 `PrefixCachedEps(vlm, **model_kwargs)` runs the encoders and ONE prefill over the prefix rows with the training kernels
 (`ops.DecoderLayerFn._fwd`: fused RMSNorm / QKV + RoPE GEMM / flash attention / SwiGLU GEMMs), keeps every layer's packed post-RoPE
 q|k|v rows, and then serves each `model(x, t)` call with a pass over the `1 + T` suffix rows per sample: skinny weight-streaming GEMMs
-(`mla_gemv_bf16`, every weight read once per pass), `mla_attn_decode` against the cached keys / values, the same RMSNorm / RoPE / SwiGLU
+(`mla_gemv_bf16` up to 8 rows, `mla_gemm_skinny_bf16` up to 64; every weight read once per pass), `mla_attn_decode` (up to 8 rows)
+or `mla_attn_chunk` (up to 64) against the cached keys / values, the same RMSNorm / RoPE / SwiGLU
 kernels' arithmetic as training (RMSNorm and SwiGLU are applied inside the projections' input staging). The 6 x 32 launches of a pass
 (5 with the rotary embedding in the QKV kernel's epilogue) are captured once into a HIP graph and replayed per DDIM step.
 
@@ -21,6 +22,7 @@ from __future__ import annotations
 
 import math
 import os
+import warnings
 from typing import Optional
 
 import torch
@@ -47,6 +49,23 @@ class PrefixCachedEps:
             raise ValueError("PrefixCachedEps needs the same splice position in every row (predict_action_diff is batch 1)")
         return int(k[0])
 
+    MAX_ROWS = 64                    # B * (1 + T) suffix rows: mla_gemm_skinny_bf16 / mla_attn_chunk serve up to 64
+
+    @classmethod
+    def supports(cls, vlm, batch: int, n_action_rows: int) -> bool:
+        """Whether the suffix pass's kernels serve this shape: B * (1 + T) <= 64 rows and head_dim 128. Otherwise the caller runs the
+        reference's control flow (a whole forward per sampler step); warns once per shape."""
+        cfg = vlm.llm_backbone.llm.config
+        rows, D = batch * (1 + n_action_rows), cfg.hidden_size // cfg.num_attention_heads
+        if rows <= cls.MAX_ROWS and D == 128:
+            return True
+        seen = vlm.__dict__.setdefault("_prefix_unsupported", set())
+        if (rows, D) not in seen:
+            seen.add((rows, D))
+            warnings.warn(f"PrefixCachedEps: {rows} suffix rows (max {cls.MAX_ROWS}) / head_dim {D} (needs 128) are beyond the cached-prefix "
+                          "kernels; sampling with a whole forward per step", RuntimeWarning, stacklevel=3)
+        return False
+
     @classmethod
     def for_inputs(cls, vlm, input_ids, n_action_rows: int = 1, **model_kwargs):
         k = cls._splice_position(input_ids)
@@ -70,6 +89,7 @@ class PrefixCachedEps:
         self.cache = None
         self.graph = None
         self._graph_failed = False
+        self.graph_error = None      # why the suffix pass could not be captured (eager launches then), for diagnostics
         self._packed = None          # per layer: the 9 weights with q|k|v and gate|up as views of ONE buffer each (see _weights)
         self._packed_key = None
 
@@ -139,12 +159,15 @@ class PrefixCachedEps:
             out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
             rpb, out_bs = M, 0
         ldo = out.stride(-2)
+        # mla_gemv_bf16 wherever it accepts the rows (the results of every configuration it served stay bit for bit the same), the MFMA
+        # skinny GEMM beyond (M > 8, or the M x K input rows do not fit its LDS: 7B down projection at M = 8)
+        gemv = hip.gemv if hip.gemv_fits(M, weights[0].shape[1]) else hip.gemm_skinny
         if wcat is not None:
-            hip.gemv(x, wcat, out, ldo, out_bs, rpb, residual, **pre)
+            gemv(x, wcat, out, ldo, out_bs, rpb, residual, **pre)
         else:                                                                # parameters not laid out back to back (no FlatUnit): one launch each
             off = 0
             for w in weights:
-                hip.gemv(x, w, out, ldo, out_bs, rpb, None if residual is None else residual[:, off:], out_col=off, **pre)
+                gemv(x, w, out, ldo, out_bs, rpb, None if residual is None else residual[:, off:], out_col=off, **pre)
                 off += w.shape[0]
         return out
 
@@ -152,6 +175,7 @@ class PrefixCachedEps:
         B, R, H, S_p, S_cap = self.B, self.R, self.H, self.S_p, self.S_cap
         h = self.h_in
         scale = 1.0 / math.sqrt(self.D)
+        attn = hip.attn_decode if hip.attn_decode_fits(R, S_cap) else hip.attn_chunk   # R x S_kv scores in LDS vs online softmax
         for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd), c in zip(self._packed, self.cache):
             # north_star's "fused RMSNorm + RoPE + QKV" as ONE kernel: RMSNorm inside the projection's input staging, the rotary embedding of
             # the q and k columns in its epilogue; the rows go straight into the cache slots [S_p, S_p + R) of every sample
@@ -161,7 +185,7 @@ class PrefixCachedEps:
             if not fused:
                 for b in range(B):
                     hip.rope_inplace(c[b, S_p:], self.cos_s, self.sin_s, R, self.nheads, self.D, 0, H)
-            o = hip.attn_decode(c, B, self.nheads, self.D, S_cap, R, scale)
+            o = attn(c, B, self.nheads, self.D, S_cap, R, scale)
             h1 = self._gemv(o, (wo,), residual=h)
             gu = self._gemv(h1, (wg, wu), norm_weight=ln2, eps=self.eps)
             h = self._gemv(gu, (wd,), residual=h1, swiglu=True)                # SwiGLU inside the down projection's input staging
@@ -178,8 +202,8 @@ class PrefixCachedEps:
                     with torch.cuda.graph(g):
                         self._suffix_pass()
                     self.graph = g
-                except Exception:   # noqa: BLE001 -- a failed capture is not fatal: the eager launches compute the same thing
-                    self._graph_failed = True
+                except Exception as e:   # noqa: BLE001 -- a failed capture is not fatal: the eager launches compute the same thing
+                    self._graph_failed, self.graph_error = True, repr(e)
                     self.graph = None
                     torch.cuda.synchronize()
             if self.graph is not None:

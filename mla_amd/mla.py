@@ -333,6 +333,8 @@ class MLA(nn.Module):
         eps_model = self.vlm.forward
         if reuse_prefix:
             from .infer import PrefixCachedEps
+            reuse_prefix = PrefixCachedEps.supports(self.vlm, int(input_ids.shape[0]), self.future_action_window_size + 1)
+        if reuse_prefix:
             eps_model = PrefixCachedEps.for_inputs(self.vlm, n_action_rows=self.future_action_window_size + 1, **model_kwargs)
         if use_ddim and num_ddim_steps is not None:
             if self.ddim_diffusion is None:
