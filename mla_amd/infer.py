@@ -8,7 +8,7 @@ them (`text[k:]`) cannot influence the rows that are read out (`noise_pred = fin
 
 `PrefixCachedEps(vlm, **model_kwargs)` runs the encoders and ONE prefill over the prefix rows with the training kernels
 (`ops.DecoderLayerFn._fwd`: fused RMSNorm / QKV + RoPE GEMM / flash attention / SwiGLU GEMMs), keeps every layer's packed post-RoPE
-q|k|v rows, and then serves each `model(x, t)` call with a pass over the `1 + T` suffix rows per sample: skinny weight-streaming GEMMs
+q|k|v rows (`LayerActs.qkv`), and then serves each `model(x, t)` call with a pass over the `1 + T` suffix rows per sample: skinny weight-streaming GEMMs
 (`mla_gemv_bf16` up to 8 rows, `mla_gemm_skinny_bf16` up to 64; every weight read once per pass), `mla_attn_decode` (up to 8 rows)
 or `mla_attn_chunk` (up to 64) against the cached keys / values, the same RMSNorm / RoPE / SwiGLU
 kernels' arithmetic as training (RMSNorm and SwiGLU are applied inside the projections' input staging). The 6 x 32 launches of a pass
@@ -144,9 +144,9 @@ class PrefixCachedEps:
             # ---- prefill: the training forward kernels, one layer at a time; keep the packed post-RoPE q|k|v rows
             h = prefix.reshape(B * S_p, H)
             for w, c in zip(self._weights(), self.cache):
-                h, saved = ops.DecoderLayerFn._fwd(h, None, self.cos_p, self.sin_p, B, S_p, self.nheads, self.eps, w)
-                c[:, :S_p].copy_(saved[2][:B * S_p].view(B, S_p, 3 * H))
-                del saved
+                h, acts = ops.DecoderLayerFn._fwd(h, None, self.cos_p, self.sin_p, B, S_p, self.nheads, self.eps, w)
+                c[:, :S_p].copy_(acts.qkv[:B * S_p].view(B, S_p, 3 * H))
+                del acts
 
     # ------------------------------------------------------------------------------------------ one pass over the suffix rows
     def _gemv(self, x, weights, out=None, residual=None, rpb=1, out_bs=0, **pre):

@@ -12,6 +12,8 @@ from __future__ import annotations
 import math
 import threading
 import os
+from collections import namedtuple
+from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
 import torch
@@ -216,6 +218,66 @@ def _check_bf16_cuda(*ts):
             raise RuntimeError("mla_amd ops run on the GPU only (no CPU fallback)")
         if t.dtype != BF16:
             raise TypeError(f"mla_amd ops expect bfloat16 tensors, got {t.dtype}")
+
+
+def _pad_rows(x):
+    """[B, S, H] (or [T, H]) -> contiguous [Tp, H], Tp = T padded as _pad_tokens says. The tile transposes of the all-NT backward move
+    8 tokens per 16-B access: an odd token count (per-device batch 1 with an odd padded length) runs on zero rows appended here; they
+    stay zero through every row-wise op, contribute zero to every weight gradient, and are cut off again by _cut_rows."""
+    x2 = _as2d(x)
+    T, Tp = x2.shape[0], _pad_tokens(x2.shape[0])
+    return x2 if Tp == T else torch.cat([x2, x2.new_zeros(Tp - T, x2.shape[1])], 0)
+
+
+def _cut_rows(x2, B, S):
+    return x2[:B * S].view(B, S, x2.shape[1])
+
+
+def _project(x2, weights, out=None):
+    """x2 @ cat(W_i)^T: one GEMM when the weights are adjacent in the flat buffer (cat_view), else one per weight into its column slice
+    of `out`."""
+    if out is None:
+        out = torch.empty((x2.shape[0], sum(w.shape[0] for w in weights)), dtype=BF16, device=x2.device)
+    wcat = cat_view(weights)
+    if wcat is not None:
+        return hip.gemm(x2, wcat, out=out)
+    off = 0
+    for w in weights:
+        n = w.shape[0]
+        hip.gemm(x2, w, out=out[:, off:off + n])
+        off += n
+    return out
+
+
+def _transposed(weights):
+    """cat(W_i)^T, k-contiguous for the dgrad of the all-NT backward: dx = dy @ _transposed(weights)^T on the fast NT kernel."""
+    wcat = cat_view(weights)
+    return hip.transpose(wcat if wcat is not None else torch.cat(list(weights), 0))
+
+
+def _dgrad_rows(dy, weights):
+    """dx = dy @ cat(W_i) with the weights as they are stored (b_mode=1: reduction-major B operand; cheap for the few read-out rows).
+    Weights that are not adjacent: one GEMM per weight on its (contiguous) column slice of dy, accumulated through the residual input."""
+    wcat = cat_view(weights)
+    if wcat is not None:
+        return hip.gemm(dy, wcat, b_mode=1)
+    dx, off = None, 0
+    for w in weights:
+        n = w.shape[0]
+        dx = hip.gemm(dy[:, off:off + n].contiguous(), w, b_mode=1, residual=dx)
+        off += n
+    return dx
+
+
+def _rmsnorm_bwd(dy, x2, w, rstd, dres, want_w):
+    """(dx (+ dres), dw) of an RMSNorm in one launch; dw is delivered (main_grad, or returned) only when wanted."""
+    dx = []
+
+    def run(dw_out, acc):
+        dx.append(hip.rmsnorm_bwd(dy, x2, w, rstd, dres=dres, dw_out=dw_out, dw_accumulate=acc))
+
+    dw = deliver_vec_grad(w, run) if want_w else run(None, False)
+    return dx[0], dw
 
 
 # ------------------------------------------------------------------------------------------------- linear
@@ -593,6 +655,98 @@ class attn_groups:
         _ATTN_GROUPS.value = self.prev
 
 
+# The nine parameters of a LlamaDecoderLayer in the order the layer functions take them (`*w`); also the shape of the per-weight
+# needs_input_grad flags and of the gradients returned for them.
+LayerWeights = namedtuple("LayerWeights", "ln1 wq wk wv wo ln2 wg wu wd")
+
+
+@dataclass
+class LayerActs:
+    """What a decoder-layer forward leaves for its backward. None: the form / save level does not produce or keep it (the folded
+    forward has no xn1 / xn2; gu, act, actT depend on need_gu / need_out / save_t). Mutable: the backward of a checkpointed layer
+    owns the only reference and releases fields as it goes."""
+    xn1: Optional[torch.Tensor] = None
+    rstd1: Optional[torch.Tensor] = None
+    qkv: Optional[torch.Tensor] = None
+    o: Optional[torch.Tensor] = None
+    lse: Optional[torch.Tensor] = None
+    h1: Optional[torch.Tensor] = None
+    xn2: Optional[torch.Tensor] = None
+    rstd2: Optional[torch.Tensor] = None
+    gu: Optional[torch.Tensor] = None
+    act: Optional[torch.Tensor] = None
+    actT: Optional[torch.Tensor] = None
+
+
+# ---- stages shared by the dense (DecoderLayerFn._fwd / .backward), folded (_fwd_folded) and read-out (ReadoutLayerFn) forms of the layer.
+# A backward stage ends where its caller releases a tensor it handed in (`del do`, `del dqkv, tr`): a callee cannot drop its caller's
+# reference, and when an activation is released is part of the layer's peak memory.
+def _attn_fwd(qkv, seqlens, B, S, nheads, groups):
+    H = qkv.shape[1] // 3
+    D = H // nheads
+    return hip.attn_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, S, nheads, D, 3 * H, seqlens, 1.0 / math.sqrt(D),
+                        rows=qkv.shape[0], groups=groups)
+
+
+def _attn_front(h2, seqlens, cos, sin, B, S, nheads, eps, w, groups, keep_xn1=True):
+    """Dense front half of a layer's forward: RMSNorm -> q|k|v projection + RoPE -> causal attention. Returns (xn1, rstd1, qkv, o, lse);
+    keep_xn1=False releases the normalised input in front of the attention's allocations (xn1 comes back as None)."""
+    H = h2.shape[1]
+    D = H // nheads
+    xn1, rstd1 = hip.rmsnorm_fwd(h2, w.ln1, eps)
+    qkv = torch.empty((h2.shape[0], 3 * H), dtype=BF16, device=h2.device)
+    wqkv = cat_view((w.wq, w.wk, w.wv))
+    # fused RMSNorm-output x [Wq|Wk|Wv]^T + RoPE: the rotary embedding of q and k happens in the GEMM epilogue (north_star's
+    # "fused RoPE + QKV"); shapes outside the fused kernel's contract take the two separate launches
+    # (tables with B * S rows = per-sample positions, shared-prefix sequences of ragged prompts: position = row % (B * S) = the row)
+    Sr = cos.shape[0]
+    assert Sr == S or (Sr == B * S and groups is not None), (Sr, S, B)
+    if not (wqkv is not None and D == 128 and _ROPE_EPILOGUE and hip.gemm_qkv_rope(xn1, wqkv, qkv, cos, sin, Sr, 2 * H)):
+        _project(xn1, (w.wq, w.wk, w.wv), out=qkv)
+        hip.rope_inplace(qkv, cos, sin, Sr, nheads, D, 0, H)
+    if not keep_xn1:
+        xn1 = None
+    o, lse = _attn_fwd(qkv, seqlens, B, S, nheads, groups)
+    return xn1, rstd1, qkv, o, lse
+
+
+def _attn_bwd(qkv, o, lse, do, seqlens, cos, sin, B, S, nheads, groups, want_t):
+    """Attention backward with the RoPE backward of dq / dk. Returns (dqkv, tr): tr = (dqkv^T, o^T), the wgrad operands of the q|k|v and
+    o projections, written by the same kernels when want_t and their contract allow it (all four transposed outputs or none), else
+    None. Rows beyond B * S (row padding) come out zero."""
+    T, H = qkv.shape[0], qkv.shape[1] // 3
+    D = H // nheads
+    dqkv = torch.empty_like(qkv)
+    if T != B * S:
+        dqkv[B * S:].zero_()
+    # the RoPE backward of dq / dk is applied in the attention-backward epilogues (no separate in-place pass over dqkv)
+    fuse_rope = cos.shape[0] in (S, B * S) and cos.is_contiguous() and sin.is_contiguous() and cos.dtype == torch.float32
+    # dqkv^T and o^T leave the attention-backward kernels with the rows: no transpose passes over them
+    tr = None
+    if _ATTN_BWD_T and fuse_rope and S % 4 == 0 and want_t:
+        tr = (torch.empty((3 * H, T), dtype=BF16, device=qkv.device), torch.empty((H, T), dtype=BF16, device=qkv.device))
+        if T != B * S:
+            tr[0][:, B * S:].zero_()
+            tr[1][:, B * S:].zero_()
+    hip.attn_bwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], o, do, lse, seqlens, dqkv[:, :H], dqkv[:, H:2 * H],
+                 dqkv[:, 2 * H:], B, S, nheads, D, 3 * H, 1.0 / math.sqrt(D), rope_cos=cos if fuse_rope else None,
+                 rope_sin=sin if fuse_rope else None, transposed=tr, groups=groups)
+    if not fuse_rope:
+        hip.rope_inplace(dqkv, cos, sin, cos.shape[0], nheads, D, 0, H, backward=True)
+    return dqkv, tr
+
+
+def _qkv_bwd(dqkv, tr, h2, xn1, rstd1, w, need):
+    """q | k | v projection backward: (dxn1 [T, H], (dWq, dWk, dWv)); the weight gradients are delivered when any is wanted, from tr[0] =
+    dqkv^T when the attention backward left it. xn1 None: the normalised input is rebuilt, already transposed, from h2 and rstd1."""
+    dxn1 = hip.gemm(dqkv, _transposed((w.wq, w.wk, w.wv)))               # [T, H], K = 3H
+    grads = (None, None, None)
+    if need.wq or need.wk or need.wv:
+        xn1T = hip.rmsnorm_apply_t(h2, w.ln1, rstd1) if xn1 is None else hip.transpose(xn1)
+        grads = deliver_wgrad_nt((w.wq, w.wk, w.wv), tr[0] if tr is not None else hip.transpose(dqkv), xn1T, (need.wq, need.wk, need.wv))
+    return dxn1, grads
+
+
 class DecoderLayerFn(torch.autograd.Function):
     """One whole LlamaDecoderLayer (transformers/models/llama/modeling_llama.py:695-767) as a single autograd node.
 
@@ -606,93 +760,71 @@ class DecoderLayerFn(torch.autograd.Function):
                 and recompute the whole forward (activation checkpointing, training/strategies/fsdp.py:211-223).
                 Every level runs the same kernels on the same inputs: outputs and gradients are bit-identical across levels.
     """
+    N_ARGS = 8           # arguments of forward() in front of the nine weights: h, seqlens, cos, sin, nheads, eps, save_level, fold_io
 
     @staticmethod
     def _fold_ok(h2, cos, sin, Sr, nheads, w, save_t) -> bool:
         """The folded-RMSNorm forward needs all four GEMMs of the layer inside the 256x256 kernel's fused-epilogue contracts."""
-        ln1, wq, wk, wv, wo, ln2, wg, wu, wd = w
         T, H = h2.shape
-        wqkv, wgu = cat_view((wq, wk, wv)), cat_view((wg, wu))
+        wqkv, wgu = cat_view((w.wq, w.wk, w.wv)), cat_view((w.wg, w.wu))
         if wqkv is None or wgu is None or H // nheads != 128 or not (_ROPE_EPILOGUE and _SWIGLU_FWD_EPILOGUE):
             return False
-        if T < 256 or H % 256 != 0 or any(t.data_ptr() % 16 for t in (ln1, ln2, wo, wd)) or wo.stride(0) % 8 or wd.stride(0) % 8:
+        if (T < 256 or H % 256 != 0 or any(t.data_ptr() % 16 for t in (w.ln1, w.ln2, w.wo, w.wd)) or w.wo.stride(0) % 8 or
+                w.wd.stride(0) % 8):
             return False
         qkv_like = torch.empty((0, 3 * H), dtype=BF16, device=h2.device)
         return (hip.qkv_rope_ok(h2, wqkv, qkv_like, cos, sin, Sr, 2 * H) and hip.gateup_swiglu_ok(h2, wgu, save_t and T % 8 == 0) and
-                wd.shape[1] % 64 == 0)
+                w.wd.shape[1] % 64 == 0)
 
     @staticmethod
     def _fwd_folded(h2, seqlens, cos, sin, B, S, nheads, eps, w, save_t, groups, fold, need_out=True, need_gu=True):
         """_fwd with both RMSNorms folded into the projections (mla_hip.h "RMSNorm folded into the projections"): no stand-alone norm
         pass; rstd1 / rstd2 come out of the QKV and gate|up launches. fold = NormFoldIO, or a saved rstd1 tensor (recomputation of a
         checkpointed layer: the same row scale as in the forward, whatever produced it there)."""
-        ln1, wq, wk, wv, wo, ln2, wg, wu, wd = w
         T, H = h2.shape
-        D = H // nheads
-        Sr = cos.shape[0]
-        wqkv, wgu = cat_view((wq, wk, wv)), cat_view((wg, wu))
+        wqkv, wgu = cat_view((w.wq, w.wk, w.wv)), cat_view((w.wg, w.wu))
         io = fold if isinstance(fold, NormFoldIO) else None
         pre = io.pre if io is not None else None
-        if pre is not None and not (pre[0] == h2.data_ptr() and pre[1].data_ptr() == ln1.data_ptr() and pre[2].shape == h2.shape):
+        if pre is not None and not (pre[0] == h2.data_ptr() and pre[1].data_ptr() == w.ln1.data_ptr() and pre[2].shape == h2.shape):
             pre = None                                   # made for other rows / another weight: ignore it
         if pre is not None:
             xg1, norm1 = pre[2], (pre[3], None, eps)
         elif io is None and fold is not None:
-            xg1, norm1 = hip.rmsnorm_prep(h2, ln1, eps, want_rstd=False)[0], (None, fold, eps)
+            xg1, norm1 = hip.rmsnorm_prep(h2, w.ln1, eps, want_rstd=False)[0], (None, fold, eps)
         else:
-            xg1, r1 = hip.rmsnorm_prep(h2, ln1, eps)
+            xg1, r1 = hip.rmsnorm_prep(h2, w.ln1, eps)
             norm1 = (None, r1, eps)
         qkv = torch.empty((T, 3 * H), dtype=BF16, device=h2.device)
-        rstd1 = hip.gemm_qkv_rope(xg1, wqkv, qkv, cos, sin, Sr, 2 * H, norm=norm1)      # fused RMSNorm + QKV + RoPE
+        rstd1 = hip.gemm_qkv_rope(xg1, wqkv, qkv, cos, sin, cos.shape[0], 2 * H, norm=norm1)      # fused RMSNorm + QKV + RoPE
         assert rstd1 is not False
         del xg1
-        o, lse = hip.attn_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, S, nheads, D, 3 * H, seqlens, 1.0 / math.sqrt(D),
-                              rows=T, groups=groups)
-        h1, xg2, ss2 = hip.gemm_res_norm(o, wo, h2, ln2)
+        o, lse = _attn_fwd(qkv, seqlens, B, S, nheads, groups)
+        h1, xg2, ss2 = hip.gemm_res_norm(o, w.wo, h2, w.ln2)
         gu, act_, actT, rstd2 = hip.gemm_gateup_swiglu(xg2, wgu, save_t and T % 8 == 0, norm=(ss2, None, eps), want_act=need_out, want_gu=need_gu)
         del xg2, ss2
         if not need_out:
             out = None
         elif io is not None and io.next_ln is not None and io.next_ln.data_ptr() % 16 == 0:
-            out, xgn, ssn = hip.gemm_res_norm(act_, wd, h1, io.next_ln)
+            out, xgn, ssn = hip.gemm_res_norm(act_, w.wd, h1, io.next_ln)
             io.out = (out.data_ptr(), io.next_ln, xgn, ssn)
         else:
-            out = hip.gemm(act_, wd, residual=h1)
-        return out, (None, rstd1, qkv, o, lse, h1, None, rstd2, gu, act_, actT)
+            out = hip.gemm(act_, w.wd, residual=h1)
+        return out, LayerActs(rstd1=rstd1, qkv=qkv, o=o, lse=lse, h1=h1, rstd2=rstd2, gu=gu, act=act_, actT=actT)
 
     @staticmethod
     def _fwd(h2, seqlens, cos, sin, B, S, nheads, eps, w, save_t=False, groups=None, fold=None, need_out=True, need_gu=True):
-        """need_out=False: the recomputation of a checkpointed layer inside its backward -- everything up to the SwiGLU product, NOT the
+        """(layer output, LayerActs) for rows h2 [T, H]; w = the nine weights in LayerWeights order.
+        need_out=False: the recomputation of a checkpointed layer inside its backward -- everything up to the SwiGLU product, NOT the
         down projection (its output is the layer output, which the backward never reads; torch.utils.checkpoint, the reference's
         fsdp.py:211-223, recomputes it anyway: 22 % of a layer's forward FLOPs). need_gu=False: the FORWARD of a checkpointed layer --
         gate|up never leaves the chip (only the SwiGLU product does; nothing but the layer input is kept)."""
-        ln1, wq, wk, wv, wo, ln2, wg, wu, wd = w
-        H = h2.shape[1]
-        D = H // nheads
+        w = LayerWeights(*w)
         if fold is not None:
             return DecoderLayerFn._fwd_folded(h2, seqlens, cos, sin, B, S, nheads, eps, w, save_t, groups, fold, need_out, need_gu)
-        xn1, rstd1 = hip.rmsnorm_fwd(h2, ln1, eps)
-        qkv = torch.empty((h2.shape[0], 3 * H), dtype=BF16, device=h2.device)
-        wqkv = cat_view((wq, wk, wv))
-        # fused RMSNorm-output x [Wq|Wk|Wv]^T + RoPE: the rotary embedding of q and k happens in the GEMM epilogue (north_star's
-        # "fused RoPE + QKV"); shapes outside the fused kernel's contract take the two separate launches
-        # (tables with B * S rows = per-sample positions, shared-prefix sequences of ragged prompts: position = row % (B * S) = the row)
-        Sr = cos.shape[0]
-        assert Sr == S or (Sr == B * S and groups is not None), (Sr, S, B)
-        if not (wqkv is not None and D == 128 and _ROPE_EPILOGUE and
-                hip.gemm_qkv_rope(xn1, wqkv, qkv, cos, sin, Sr, 2 * H)):
-            if wqkv is not None:
-                hip.gemm(xn1, wqkv, out=qkv)
-            else:
-                for i, wi in enumerate((wq, wk, wv)):
-                    hip.gemm(xn1, wi, out=qkv[:, i * H:(i + 1) * H])
-            hip.rope_inplace(qkv, cos, sin, Sr, nheads, D, 0, H)
-        o, lse = hip.attn_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, S, nheads, D, 3 * H, seqlens, 1.0 / math.sqrt(D),
-                              rows=h2.shape[0], groups=groups)
-        h1 = hip.gemm(o, wo, residual=h2)
-        xn2, rstd2 = hip.rmsnorm_fwd(h1, ln2, eps)
-        I = wg.shape[0]
-        wgu = cat_view((wg, wu))
+        xn1, rstd1, qkv, o, lse = _attn_front(h2, seqlens, cos, sin, B, S, nheads, eps, w, groups)
+        h1 = hip.gemm(o, w.wo, residual=h2)
+        xn2, rstd2 = hip.rmsnorm_fwd(h1, w.ln2, eps)
+        wgu = cat_view((w.wg, w.wu))
         # fused gate|up projection + SwiGLU: the product (and, with save_t, its transposed copy for the backward's wgrad) is formed in the
         # GEMM epilogue -- gu is written once and not read again in the forward pass
         fused = (hip.gemm_gateup_swiglu(xn2, wgu, save_t and h2.shape[0] % 8 == 0, want_act=need_out, want_gu=need_gu)
@@ -700,62 +832,49 @@ class DecoderLayerFn(torch.autograd.Function):
         if fused is not None:
             gu, act_, actT = fused
         else:
-            if wgu is not None:
-                gu = hip.gemm(xn2, wgu)
-            else:
-                gu = torch.empty((h2.shape[0], 2 * I), dtype=BF16, device=h2.device)
-                hip.gemm(xn2, wg, out=gu[:, :I])
-                hip.gemm(xn2, wu, out=gu[:, I:])
+            gu = _project(xn2, (w.wg, w.wu))
             # save_t: the caller keeps the SwiGLU product for the backward in TRANSPOSED layout (the wgrad operand), written by the
             # same pass that produces the row-major copy for the down projection
             if save_t and gu.shape[0] % 8 == 0:
                 act_, actT = hip.swiglu_fwd_dual(gu)
             else:
                 act_, actT = hip.swiglu_fwd(gu), None
-        out = hip.gemm(act_, wd, residual=h1) if need_out else None
-        return out, (xn1, rstd1, qkv, o, lse, h1, xn2, rstd2, gu, act_, actT)
+        out = hip.gemm(act_, w.wd, residual=h1) if need_out else None
+        return out, LayerActs(xn1, rstd1, qkv, o, lse, h1, xn2, rstd2, gu, act_, actT)
 
     @staticmethod
     def forward(ctx, h, seqlens, cos, sin, nheads, eps, save_level, fold_io, *w):
         _check_bf16_cuda(h, *w)
+        w = LayerWeights(*w)
         B, S, H = h.shape
-        h2 = h.reshape(B * S, H)
-        if not h2.is_contiguous():
-            h2 = h2.contiguous()
-        T, Tp = B * S, _pad_tokens(B * S)
-        if Tp != T:
-            # the tile transposes of the all-NT backward move 8 tokens per 16-B access: an odd token count (per-device batch 1 with
-            # an odd padded length) runs on zero rows appended here; they stay zero through every row-wise op, contribute zero to
-            # every weight gradient, and are cut off again below
-            h2 = torch.cat([h2, h2.new_zeros(Tp - T, H)], 0)
-        keep_t = save_level == 1 and ctx.needs_input_grad[8 + 8] and _SWIGLU_DUAL   # down_proj trainable: its wgrad wants act^T
+        h2 = _pad_rows(h)
+        Tp = h2.shape[0]
+        # down_proj trainable: its wgrad wants act^T
+        keep_t = save_level == 1 and LayerWeights(*ctx.needs_input_grad[DecoderLayerFn.N_ARGS:]).wd and _SWIGLU_DUAL
         if save_level == 3:
             save_level = 1                         # "1-lean": same saved set as level 1 minus act^T
         ctx.groups = current_attn_groups()
         # RMSNorms folded into the projections: when the caller hands a NormFoldIO and every GEMM of the layer is inside the fused kernels'
         # contracts. The padded rows of a handed-over x * g belong to the previous layer's padded output: same zero rows.
         fold = fold_io if (fold_io is not None and DecoderLayerFn._fold_ok(h2, cos, sin, cos.shape[0], nheads, w, keep_t)) else None
-        if fold is not None and fold.pre is not None and Tp != T and fold.pre[0] == h.data_ptr() and fold.pre[2].shape[0] == Tp:
+        if fold is not None and fold.pre is not None and Tp != B * S and fold.pre[0] == h.data_ptr() and fold.pre[2].shape[0] == Tp:
             fold.pre = (h2.data_ptr(),) + tuple(fold.pre[1:])
         ctx.folded = fold is not None
-        out, (xn1, rstd1, qkv, o, lse, h1, xn2, rstd2, gu, act_, actT) = DecoderLayerFn._fwd(
-            h2, seqlens, cos, sin, B, S, nheads, eps, w, save_t=keep_t, groups=ctx.groups, fold=fold,
-            need_gu=not (save_level == 0 and _RECOMPUTE_LEAN))
-        out = out[:T]
+        out, a = DecoderLayerFn._fwd(h2, seqlens, cos, sin, B, S, nheads, eps, w, save_t=keep_t, groups=ctx.groups, fold=fold,
+                                     need_gu=not (save_level == 0 and _RECOMPUTE_LEAN))
         ctx.w, ctx.dims, ctx.save_level = w, (B, S, H, nheads, eps), save_level
         ctx.aux = (seqlens, cos, sin)
-        ctx.has_actT = actT is not None
         if save_level >= 2:
-            ctx.save_for_backward(h2, xn1, rstd1, qkv, o, lse, h1, xn2, rstd2, gu, act_)
+            ctx.save_for_backward(h2, a.xn1, a.rstd1, a.qkv, a.o, a.lse, a.h1, a.xn2, a.rstd2, a.gu, a.act)
         elif save_level == 1:
             # level 1 = recompute the two normalised inputs in the backward (one HBM-bound pass each, written straight into the
             # transposed layout) and KEEP the SwiGLU product, already transposed (+0.39 GB per layer at 7B; 288 GB of HBM)
-            ctx.save_for_backward(*((h2, rstd1, qkv, o, lse, h1, rstd2, gu) + ((actT,) if actT is not None else ())))
+            ctx.save_for_backward(*((h2, a.rstd1, a.qkv, a.o, a.lse, a.h1, a.rstd2, a.gu) + ((a.actT,) if a.actT is not None else ())))
         elif ctx.folded:
-            ctx.save_for_backward(h2, rstd1)       # the recomputation scales the QKV rows by the SAME rstd the forward used
+            ctx.save_for_backward(h2, a.rstd1)     # the recomputation scales the QKV rows by the SAME rstd the forward used
         else:
             ctx.save_for_backward(h2)
-        return out.view(B, S, H)
+        return _cut_rows(out, B, S)
 
     @staticmethod
     def backward(ctx, dout):
@@ -763,124 +882,67 @@ class DecoderLayerFn(torch.autograd.Function):
         kernels; x^T of the normalised inputs and of the SwiGLU product are recomputed straight into transposed layout),
         so dgrad and wgrad run on the same 256x256 ds_read_b128 kernel as the forward (mla_amd/csrc/transpose.hip)."""
         w = ctx.w
-        ln1, wq, wk, wv, wo, ln2, wg, wu, wd = w
         B, S, H, nheads, eps = ctx.dims
         seqlens, cos, sin = ctx.aux
-        D = H // nheads
-        T = B * S
-        lvl = ctx.save_level
-        xn1 = xn2 = act_ = actT_saved = None
-        if lvl >= 2:
-            h2, xn1, rstd1, qkv, o, lse, h1, xn2, rstd2, gu, act_ = ctx.saved_tensors
-        elif lvl == 1:
-            if ctx.has_actT:
-                h2, rstd1, qkv, o, lse, h1, rstd2, gu, actT_saved = ctx.saved_tensors
-            else:
-                h2, rstd1, qkv, o, lse, h1, rstd2, gu = ctx.saved_tensors
+        need = LayerWeights(*ctx.needs_input_grad[DecoderLayerFn.N_ARGS:])
+        h2, *saved = ctx.saved_tensors
+        if ctx.save_level >= 2:
+            a = LayerActs(*saved)
+        elif ctx.save_level == 1:
+            rstd1, qkv, o, lse, h1, rstd2, gu, *kept_t = saved
+            a = LayerActs(rstd1=rstd1, qkv=qkv, o=o, lse=lse, h1=h1, rstd2=rstd2, gu=gu, actT=kept_t[0] if kept_t else None)
         else:
-            if ctx.folded:
-                h2, rstd1_f = ctx.saved_tensors
-            else:
-                (h2,), rstd1_f = ctx.saved_tensors, None
             # the recomputation stops in front of the down projection and asks the gate|up epilogue for the SwiGLU product in the
-            # layout the down-projection wgrad wants (round 6: was a full forward + a transpose pass over act)
-            want_t = ctx.needs_input_grad[8 + 8] and _SWIGLU_DUAL and _RECOMPUTE_LEAN
-            _, (xn1, rstd1, qkv, o, lse, h1, xn2, rstd2, gu, act_, actT_saved) = DecoderLayerFn._fwd(
-                h2, seqlens, cos, sin, B, S, nheads, eps, w, save_t=want_t, groups=ctx.groups, fold=rstd1_f, need_out=not _RECOMPUTE_LEAN)
-        need = ctx.needs_input_grad[8:]
-        d2 = dout.reshape(T, H)
-        if not d2.is_contiguous():
-            d2 = d2.contiguous()
-        Tr, T = T, _pad_tokens(T)               # row padding of forward(): zero gradient rows
-        if T != Tr:
-            d2 = torch.cat([d2, d2.new_zeros(T - Tr, H)], 0)
-        grads: List[Optional[torch.Tensor]] = [None] * 9
-
-        def wT(ws):
-            wc = cat_view(ws)
-            return hip.transpose(wc if wc is not None else torch.cat(list(ws), 0))
+            # layout the down-projection wgrad wants (round 6: was a full forward + a transpose pass over act); a folded layer
+            # saved the rstd1 its forward used
+            want_t = need.wd and _SWIGLU_DUAL and _RECOMPUTE_LEAN
+            _, a = DecoderLayerFn._fwd(h2, seqlens, cos, sin, B, S, nheads, eps, w, save_t=want_t, groups=ctx.groups,
+                                       fold=saved[0] if ctx.folded else None, need_out=not _RECOMPUTE_LEAN)
+        d2 = _pad_rows(dout)                    # row padding of forward(): zero gradient rows
+        g = dict.fromkeys(LayerWeights._fields)
 
         # ---- MLP: down projection
-        want_w = need[6] or need[7]
-        wdT = wT((wd,))
-        fused = hip.gemm_dact_swiglu_bwd(d2, wdT, gu) if (want_w and _SWIGLU_BWD_EPILOGUE) else None   # d(act) never leaves the chip
+        want_w = need.wg or need.wu
+        wdT = _transposed((w.wd,))
+        fused = hip.gemm_dact_swiglu_bwd(d2, wdT, a.gu) if (want_w and _SWIGLU_BWD_EPILOGUE) else None   # d(act) never leaves the chip
         dact = hip.gemm(d2, wdT) if fused is None else None              # [T, I]
         del wdT
-        if need[8]:
-            actT = actT_saved if actT_saved is not None else (hip.swiglu_fwd_t(gu) if act_ is None else hip.transpose(act_))
-            grads[8] = deliver_wgrad_nt((wd,), hip.transpose(d2), actT, need[8:9])[0]
+        if need.wd:
+            actT = a.actT if a.actT is not None else (hip.swiglu_fwd_t(a.gu) if a.act is None else hip.transpose(a.act))
+            g["wd"] = deliver_wgrad_nt((w.wd,), hip.transpose(d2), actT, (True,))[0]
             del actT
-        act_ = actT_saved = None
-        fuse_t = want_w and gu.shape[0] % 8 == 0         # dgu and dgu^T from one pass (saves re-reading the 2I-wide gradient)
+        a.act = a.actT = None
+        fuse_t = want_w and a.gu.shape[0] % 8 == 0       # dgu and dgu^T from one pass (saves re-reading the 2I-wide gradient)
         if fused is not None:
             dgu, dguT = fused
         elif fuse_t:
-            dgu, dguT = hip.swiglu_bwd_t(dact, gu)
+            dgu, dguT = hip.swiglu_bwd_t(dact, a.gu)
         else:
-            dgu, _ = hip.swiglu_bwd(dact, gu)
+            dgu, _ = hip.swiglu_bwd(dact, a.gu)
         del dact, fused
         # ---- MLP: gate | up projection
-        dxn2 = hip.gemm(dgu, wT((wg, wu)))                               # [T, H], K = 2I
+        dxn2 = hip.gemm(dgu, _transposed((w.wg, w.wu)))                  # [T, H], K = 2I
         if want_w:
-            xn2T = hip.rmsnorm_apply_t(h1, ln2, rstd2) if xn2 is None else hip.transpose(xn2)
-            grads[6], grads[7] = deliver_wgrad_nt((wg, wu), dguT if fuse_t else hip.transpose(dgu), xn2T, need[6:8])
+            xn2T = hip.rmsnorm_apply_t(a.h1, w.ln2, a.rstd2) if a.xn2 is None else hip.transpose(a.xn2)
+            g["wg"], g["wu"] = deliver_wgrad_nt((w.wg, w.wu), dguT if fuse_t else hip.transpose(dgu), xn2T, (need.wg, need.wu))
             del xn2T
             dguT = None
         del dgu
-        xn2 = None
-        holder = {}
-
-        def ln2_run(dw_out, acc):
-            holder["dh1"] = hip.rmsnorm_bwd(dxn2, h1, ln2, rstd2, dres=d2, dw_out=dw_out, dw_accumulate=acc)
-
-        if need[5]:
-            grads[5] = deliver_vec_grad(ln2, ln2_run)
-        else:
-            ln2_run(None, False)
-        dh1 = holder["dh1"]
+        a.xn2 = None
+        dh1, g["ln2"] = _rmsnorm_bwd(dxn2, a.h1, w.ln2, a.rstd2, d2, need.ln2)
         del dxn2
 
-        # ---- attention output projection
-        do = hip.gemm(dh1, wT((wo,)))
-        dqkv = torch.empty_like(qkv)
-        if T != Tr:
-            dqkv[Tr:].zero_()
-        # the RoPE backward of dq / dk is applied in the attention-backward epilogues (no separate in-place pass over dqkv)
-        fuse_rope = cos.shape[0] in (S, B * S) and cos.is_contiguous() and sin.is_contiguous() and cos.dtype == torch.float32
-        want_qkv_w = need[1] or need[2] or need[3]
-        # dqkv^T and o^T (wgrad operands) leave the attention-backward kernels with the rows: no transpose passes over them
-        tr = None
-        if _ATTN_BWD_T and fuse_rope and S % 4 == 0 and want_qkv_w and need[4]:
-            tr = (torch.empty((3 * H, T), dtype=BF16, device=qkv.device), torch.empty((H, T), dtype=BF16, device=qkv.device))
-            if T != Tr:
-                tr[0][:, Tr:].zero_()
-                tr[1][:, Tr:].zero_()
-        hip.attn_bwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], o, do, lse, seqlens, dqkv[:, :H], dqkv[:, H:2 * H],
-                     dqkv[:, 2 * H:], B, S, nheads, D, 3 * H, 1.0 / math.sqrt(D), rope_cos=cos if fuse_rope else None,
-                     rope_sin=sin if fuse_rope else None, transposed=tr, groups=ctx.groups)
+        # ---- attention output projection, attention, q | k | v projection, input norm
+        do = hip.gemm(dh1, _transposed((w.wo,)))
+        dqkv, tr = _attn_bwd(a.qkv, a.o, a.lse, do, seqlens, cos, sin, B, S, nheads, ctx.groups,
+                             want_t=(need.wq or need.wk or need.wv) and need.wo)
         del do
-        if not fuse_rope:
-            hip.rope_inplace(dqkv, cos, sin, cos.shape[0], nheads, D, 0, H, backward=True)
-        if need[4]:
-            grads[4] = deliver_wgrad_nt((wo,), hip.transpose(dh1), tr[1] if tr is not None else hip.transpose(o), need[4:5])[0]
-        # ---- q | k | v projection
-        dxn1 = hip.gemm(dqkv, wT((wq, wk, wv)))                          # [T, H], K = 3H
-        if want_qkv_w:
-            xn1T = hip.rmsnorm_apply_t(h2, ln1, rstd1) if xn1 is None else hip.transpose(xn1)
-            grads[1], grads[2], grads[3] = deliver_wgrad_nt((wq, wk, wv), tr[0] if tr is not None else hip.transpose(dqkv), xn1T,
-                                                            need[1:4])
-            del xn1T
+        if need.wo:
+            g["wo"] = deliver_wgrad_nt((w.wo,), hip.transpose(dh1), tr[1] if tr is not None else hip.transpose(a.o), (True,))[0]
+        dxn1, (g["wq"], g["wk"], g["wv"]) = _qkv_bwd(dqkv, tr, h2, a.xn1, a.rstd1, w, need)
         del dqkv, tr
-
-        def ln1_run(dw_out, acc):
-            holder["dh"] = hip.rmsnorm_bwd(dxn1, h2, ln1, rstd1, dres=dh1, dw_out=dw_out, dw_accumulate=acc)
-
-        if need[0]:
-            grads[0] = deliver_vec_grad(ln1, ln1_run)
-        else:
-            ln1_run(None, False)
-        dh = holder["dh"][:Tr].view(B, S, H) if ctx.needs_input_grad[0] else None
-        return (dh, None, None, None, None, None, None, None, *grads)
+        dh, g["ln1"] = _rmsnorm_bwd(dxn1, h2, w.ln1, a.rstd1, dh1, need.ln1)
+        return (_cut_rows(dh, B, S) if ctx.needs_input_grad[0] else None, *[None] * (DecoderLayerFn.N_ARGS - 1), *LayerWeights(**g))
 
 
 class ReadoutLayerFn(torch.autograd.Function):
@@ -897,137 +959,69 @@ class ReadoutLayerFn(torch.autograd.Function):
     GEMMs run on the 128-tile kernel: another accumulation order) -- at 9 of 12 units of the layer's forward GEMM work and 18 of 24 of
     its backward's saved (one unit = rows x H x H): 2.3 % of the step's GEMM FLOPs at 32 layers.
     forward(h [B, S, H], seqlens, cos, sin, nheads, eps, rows int64 [n] (flat indices into B * S), *w) -> [n, H]."""
+    N_ARGS = 7           # arguments of forward() in front of the nine weights: h, seqlens, cos, sin, nheads, eps, rows
 
     @staticmethod
     def forward(ctx, h, seqlens, cos, sin, nheads, eps, rows, *w):
         _check_bf16_cuda(h, *w)
-        ln1, wq, wk, wv, wo, ln2, wg, wu, wd = w
+        w = LayerWeights(*w)
         B, S, H = h.shape
-        D = H // nheads
-        h2 = h.reshape(B * S, H)
-        if not h2.is_contiguous():
-            h2 = h2.contiguous()
-        T, Tp = B * S, _pad_tokens(B * S)
-        if Tp != T:
-            h2 = torch.cat([h2, h2.new_zeros(Tp - T, H)], 0)
+        h2 = _pad_rows(h)
         groups = current_attn_groups()
-        # ---- dense half (DecoderLayerFn._fwd up to the attention output)
-        xn1, rstd1 = hip.rmsnorm_fwd(h2, ln1, eps)
-        qkv = torch.empty((Tp, 3 * H), dtype=BF16, device=h2.device)
-        wqkv = cat_view((wq, wk, wv))
-        Sr = cos.shape[0]
-        if not (wqkv is not None and D == 128 and _ROPE_EPILOGUE and hip.gemm_qkv_rope(xn1, wqkv, qkv, cos, sin, Sr, 2 * H)):
-            if wqkv is not None:
-                hip.gemm(xn1, wqkv, out=qkv)
-            else:
-                for i, wi in enumerate((wq, wk, wv)):
-                    hip.gemm(xn1, wi, out=qkv[:, i * H:(i + 1) * H])
-            hip.rope_inplace(qkv, cos, sin, Sr, nheads, D, 0, H)
-        del xn1
-        o, lse = hip.attn_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, S, nheads, D, 3 * H, seqlens, 1.0 / math.sqrt(D),
-                              rows=Tp, groups=groups)
+        # ---- all rows: the dense layer's front half; the normalised input is not kept (the backward rebuilds it transposed)
+        _, rstd1, qkv, o, lse = _attn_front(h2, seqlens, cos, sin, B, S, nheads, eps, w, groups, keep_xn1=False)
         # ---- read rows only: zero rows pad n to a multiple of 64 (they stay zero through every row-wise op and add nothing to any
         # weight gradient), so every small GEMM has MFMA-friendly row / reduction counts
         n = rows.numel()
         npad = (n + 63) // 64 * 64
         o_r = hip.gather_rows(o, rows, out_rows=npad)
         h_r = hip.gather_rows(h2, rows, out_rows=npad)
-        h1_r = hip.gemm(o_r, wo, residual=h_r)
-        xn2_r, rstd2_r = hip.rmsnorm_fwd(h1_r, ln2, eps)
-        wgu = cat_view((wg, wu))
-        if wgu is not None:
-            gu_r = hip.gemm(xn2_r, wgu)
-        else:
-            I = wg.shape[0]
-            gu_r = torch.empty((npad, 2 * I), dtype=BF16, device=h2.device)
-            hip.gemm(xn2_r, wg, out=gu_r[:, :I])
-            hip.gemm(xn2_r, wu, out=gu_r[:, I:])
+        h1_r = hip.gemm(o_r, w.wo, residual=h_r)
+        xn2_r, rstd2_r = hip.rmsnorm_fwd(h1_r, w.ln2, eps)
+        gu_r = _project(xn2_r, (w.wg, w.wu))
         act_r = hip.swiglu_fwd(gu_r)
-        out_r = hip.gemm(act_r, wd, residual=h1_r)
+        out_r = hip.gemm(act_r, w.wd, residual=h1_r)
         ctx.w, ctx.dims, ctx.aux, ctx.groups, ctx.n = w, (B, S, H, nheads, eps), (seqlens, cos, sin), groups, n
         ctx.save_for_backward(h2, rstd1, qkv, o, lse, rows, o_r, h1_r, rstd2_r, gu_r, act_r)
         return out_r[:n]
 
     @staticmethod
     def backward(ctx, dout_r):
-        ln1, wq, wk, wv, wo, ln2, wg, wu, wd = ctx.w
+        w = ctx.w
         B, S, H, nheads, eps = ctx.dims
         seqlens, cos, sin = ctx.aux
-        D = H // nheads
         h2, rstd1, qkv, o, lse, rows, o_r, h1_r, rstd2_r, gu_r, act_r = ctx.saved_tensors
-        need = ctx.needs_input_grad[7:]
+        need = LayerWeights(*ctx.needs_input_grad[ReadoutLayerFn.N_ARGS:])
         n, npad, T = ctx.n, o_r.shape[0], h2.shape[0]
-        Tr = B * S
         d_r = dout_r.reshape(n, H)
         if npad != n or not d_r.is_contiguous():
             d_r = torch.cat([d_r, d_r.new_zeros(npad - n, H)], 0) if npad != n else d_r.contiguous()
-        grads: List[Optional[torch.Tensor]] = [None] * 9
+        g = dict.fromkeys(LayerWeights._fields)
         # ---- MLP on the read rows (dgrad with the weights as they are stored: reduction-major B operand, npad rows make it cheap)
-        dact_r = hip.gemm(d_r, wd, b_mode=1)                                     # [npad, I]
-        if need[8]:
-            grads[8] = deliver_wgrad((wd,), d_r, act_r, need[8:9])[0]
+        dact_r = _dgrad_rows(d_r, (w.wd,))                                       # [npad, I]
+        if need.wd:
+            g["wd"] = deliver_wgrad((w.wd,), d_r, act_r, (True,))[0]
         dgu_r, _ = hip.swiglu_bwd(dact_r, gu_r)
-        wgu = cat_view((wg, wu))
-        if wgu is not None:
-            dxn2_r = hip.gemm(dgu_r, wgu, b_mode=1)                              # [npad, H]
-        else:
-            I = wg.shape[0]
-            dxn2_r = hip.gemm(dgu_r[:, :I].contiguous(), wg, b_mode=1)
-            dxn2_r = hip.gemm(dgu_r[:, I:].contiguous(), wu, b_mode=1, residual=dxn2_r)
-        if need[6] or need[7]:
-            xn2_r, _ = hip.rmsnorm_fwd(h1_r, ln2, eps)
-            grads[6], grads[7] = deliver_wgrad((wg, wu), dgu_r, xn2_r, need[6:8])
-        holder = {}
-
-        def ln2_run(dw_out, acc):
-            holder["dh1"] = hip.rmsnorm_bwd(dxn2_r, h1_r, ln2, rstd2_r, dres=d_r, dw_out=dw_out, dw_accumulate=acc)
-
-        if need[5]:
-            grads[5] = deliver_vec_grad(ln2, ln2_run)
-        else:
-            ln2_run(None, False)
-        dh1_r = holder["dh1"]                                                    # [npad, H]: gradient of the residual stream on the read rows
+        dxn2_r = _dgrad_rows(dgu_r, (w.wg, w.wu))                                # [npad, H]
+        if need.wg or need.wu:
+            xn2_r, _ = hip.rmsnorm_fwd(h1_r, w.ln2, eps)
+            g["wg"], g["wu"] = deliver_wgrad((w.wg, w.wu), dgu_r, xn2_r, (need.wg, need.wu))
+        # [npad, H]: gradient of the residual stream on the read rows
+        dh1_r, g["ln2"] = _rmsnorm_bwd(dxn2_r, h1_r, w.ln2, rstd2_r, d_r, need.ln2)
         # ---- attention output projection on the read rows; its input gradient goes back into a dense zero matrix
-        do_r = hip.gemm(dh1_r, wo, b_mode=1)
-        if need[4]:
-            grads[4] = deliver_wgrad((wo,), dh1_r, o_r, need[4:5])[0]
+        do_r = _dgrad_rows(dh1_r, (w.wo,))
+        if need.wo:
+            g["wo"] = deliver_wgrad((w.wo,), dh1_r, o_r, (True,))[0]
         do = hip.gather_rows(do_r[:n], rows, out_rows=T, scatter=True)
         dres = hip.gather_rows(dh1_r[:n], rows, out_rows=T, scatter=True)        # residual path into the layer input
-        # ---- dense half: attention backward, q|k|v backward, input norm backward (DecoderLayerFn.backward)
-        dqkv = torch.empty_like(qkv)
-        if T != Tr:
-            dqkv[Tr:].zero_()
-        fuse_rope = cos.shape[0] in (S, B * S) and cos.is_contiguous() and sin.is_contiguous() and cos.dtype == torch.float32
-        want_qkv_w = need[1] or need[2] or need[3]
-        tr = None
-        if _ATTN_BWD_T and fuse_rope and S % 4 == 0 and want_qkv_w:
-            tr = (torch.empty((3 * H, T), dtype=BF16, device=qkv.device), torch.empty((H, T), dtype=BF16, device=qkv.device))
-            if T != Tr:
-                tr[0][:, Tr:].zero_()
-                tr[1][:, Tr:].zero_()
-        hip.attn_bwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], o, do, lse, seqlens, dqkv[:, :H], dqkv[:, H:2 * H],
-                     dqkv[:, 2 * H:], B, S, nheads, D, 3 * H, 1.0 / math.sqrt(D), rope_cos=cos if fuse_rope else None,
-                     rope_sin=sin if fuse_rope else None, transposed=tr, groups=ctx.groups)
+        # ---- all rows: the dense layer's attention, q | k | v projection and input norm backward. The transposed pair is asked for
+        # whenever dqkv^T is wanted (o^T comes with it and is not used: the o projection's wgrad ran on the read rows above)
+        dqkv, tr = _attn_bwd(qkv, o, lse, do, seqlens, cos, sin, B, S, nheads, ctx.groups, want_t=need.wq or need.wk or need.wv)
         del do
-        if not fuse_rope:
-            hip.rope_inplace(dqkv, cos, sin, cos.shape[0], nheads, D, 0, H, backward=True)
-        wqkv = cat_view((wq, wk, wv))
-        dxn1 = hip.gemm(dqkv, hip.transpose(wqkv if wqkv is not None else torch.cat([wq, wk, wv], 0)))
-        if want_qkv_w:
-            xn1T = hip.rmsnorm_apply_t(h2, ln1, rstd1)
-            grads[1], grads[2], grads[3] = deliver_wgrad_nt((wq, wk, wv), tr[0] if tr is not None else hip.transpose(dqkv), xn1T, need[1:4])
-            del xn1T
+        dxn1, (g["wq"], g["wk"], g["wv"]) = _qkv_bwd(dqkv, tr, h2, None, rstd1, w, need)
         del dqkv, tr
-
-        def ln1_run(dw_out, acc):
-            holder["dh"] = hip.rmsnorm_bwd(dxn1, h2, ln1, rstd1, dres=dres, dw_out=dw_out, dw_accumulate=acc)
-
-        if need[0]:
-            grads[0] = deliver_vec_grad(ln1, ln1_run)
-        else:
-            ln1_run(None, False)
-        dh = holder["dh"][:Tr].view(B, S, H) if ctx.needs_input_grad[0] else None
-        return (dh, None, None, None, None, None, None, *grads)
+        dh, g["ln1"] = _rmsnorm_bwd(dxn1, h2, w.ln1, rstd1, dres, need.ln1)
+        return (_cut_rows(dh, B, S) if ctx.needs_input_grad[0] else None, *[None] * (ReadoutLayerFn.N_ARGS - 1), *LayerWeights(**g))
 
 
 def decoder_layer_readout(h, seqlens, cos, sin, nheads, eps, rows, weights):
