@@ -99,8 +99,13 @@ __global__ __launch_bounds__(256) void fps_kernel(const float* __restrict__ xyz,
     for (int i = 0; i < FPS_MAXP; ++i) {
       const int p = tid + i * 256;
       if (p < N) {
-        const float dx = __fsub_rn(px[i], cx), dy = __fsub_rn(py[i], cy), dz = __fsub_rn(pz[i], cz);
-        const float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+        // every product rounded on its own, (dx*dx + dy*dy) + dz*dz like the reference's sum: __fmul_rn / __fadd_rn are plain `*` / `+`
+        // here and the compiler contracted them into v_fma_f32 -- a distance one ulp off the reference's turns its exact ties into an
+        // order (and back), and the selection took the HIGHER index of two points tied to the bit (uniform cloud, N = 1000)
+#pragma clang fp contract(off)
+        const float dx = px[i] - cx, dy = py[i] - cy, dz = pz[i] - cz;
+        const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+        const float d = (xx + yy) + zz;
         if (d < dist[i]) dist[i] = d;
         // non-negative floats order like their bit patterns; ~p makes the LOWER index the larger key among equal distances
         const unsigned long long k = ((unsigned long long)__float_as_uint(dist[i]) << 32) | (unsigned)(~(unsigned)p);
@@ -354,10 +359,10 @@ __global__ __launch_bounds__(256) void colstats_partial_kernel(const bf16_t* __r
   const int ch = blockIdx.x * 64 + c;
   const long long per = (rows + gridDim.y - 1) / gridDim.y;
   const long long r0 = blockIdx.y * per, r1 = (r0 + per) < rows ? (r0 + per) : rows;
-  float a = 0.f, q = 0.f;
+  double a = 0.0, q = 0.0;                           // fp64 running sums: see colstats_partial_vec_kernel
   if (ch < C)
-    for (long long r = r0 + rl; r < r1; r += 4) { const float v = bf2f(x[r * ld + ch]); a += v; q += v * v; }
-  s1[rl][c] = a; s2[rl][c] = q;
+    for (long long r = r0 + rl; r < r1; r += 4) { const double v = (double)bf2f(x[r * ld + ch]); a += v; q += v * v; }
+  s1[rl][c] = (float)a; s2[rl][c] = (float)q;
   __syncthreads();
   if (rl == 0 && ch < C) {
     partial[((size_t)blockIdx.y * 2) * C + ch] = s1[0][c] + s1[1][c] + s1[2][c] + s1[3][c];
@@ -366,6 +371,9 @@ __global__ __launch_bounds__(256) void colstats_partial_kernel(const bf16_t* __r
 }
 // same partials from 16-B loads: lane = (row lane rl, 8-channel chunk cg) with RL = 256 / (C/8) row lanes (blockDim = RL * C/8);
 // the RL per-lane sums of a column are combined in a fixed order (deterministic). Needs C % 8 == 0, C <= 2048, ld % 8 == 0.
+// The per-lane running sums are fp64, rounded to fp32 once per lane: a lane adds up to rows / (blocks * RL) values in a row -- 2047 at
+// rows = 2047, C = 2048 (one block, RL = 1), where the fp32 chain left the variance ~1e-6 off and bn_apply's output five times as far
+// from fp64 as a plain fp32 evaluation is (tests/test_tokenizer_kernels_gpu.py::test_bn_zero_mean[2047-2048]). Bandwidth-bound either way.
 __global__ __launch_bounds__(256) void colstats_partial_vec_kernel(const bf16_t* __restrict__ x, float* __restrict__ partial,
                                                                    long long rows, int C, int ld) {
   extern __shared__ float sh[];                      // [2][RL][C]
@@ -373,9 +381,9 @@ __global__ __launch_bounds__(256) void colstats_partial_vec_kernel(const bf16_t*
   const int cg = threadIdx.x % C8, rl = threadIdx.x / C8;
   const long long per = (rows + gridDim.x - 1) / gridDim.x;
   const long long r0 = blockIdx.x * per, r1 = (r0 + per) < rows ? (r0 + per) : rows;
-  float a[8], q[8];
+  double a[8], q[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) a[j] = q[j] = 0.f;
+  for (int j = 0; j < 8; ++j) a[j] = q[j] = 0.0;
   long long r = r0 + rl;
   for (; r + 3LL * RL < r1; r += 4LL * RL) {         // four rows in flight per lane (round 6: one was latency-bound); same order of adds
     u32x4_t w4[4];
@@ -386,19 +394,19 @@ __global__ __launch_bounds__(256) void colstats_partial_vec_kernel(const bf16_t*
       float v[8];
       unpack8(w4[u], v);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { a[j] += v[j]; q[j] += v[j] * v[j]; }
+      for (int j = 0; j < 8; ++j) { const double d = (double)v[j]; a[j] += d; q[j] += d * d; }
     }
   }
   for (; r < r1; r += RL) {
     float v[8];
     unpack8(*(const u32x4_t*)(x + r * ld + cg * 8), v);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { a[j] += v[j]; q[j] += v[j] * v[j]; }
+    for (int j = 0; j < 8; ++j) { const double d = (double)v[j]; a[j] += d; q[j] += d * d; }
   }
   float* s1 = sh + (size_t)rl * C + cg * 8;
   float* s2 = sh + (size_t)(RL + rl) * C + cg * 8;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) { s1[j] = a[j]; s2[j] = q[j]; }
+  for (int j = 0; j < 8; ++j) { s1[j] = (float)a[j]; s2[j] = (float)q[j]; }
   __syncthreads();
   for (int ch = threadIdx.x; ch < C; ch += blockDim.x) {
     float ta = 0.f, tq = 0.f;
