@@ -286,6 +286,26 @@ int mla_gemm_skinny_bf16(const void* x, long long ldx, const void* W, long long 
  *   over 4 waves per (sample, head, 16 queries) and their softmax states merged in a fixed order (deterministic, graph-capturable). */
 int mla_attn_chunk(const void* q, const void* k, const void* v, void* o, int B, int H, int head_dim, int S_kv, int R, long long ld,
                    long long batch_stride, long long ld_o, float scale, mla_stream_t stream);
+/* ---- batched action sampling (mla_amd/infer.py BatchedPrefixCachedEps): B observations with prompts of different lengths on ONE
+ * cached-prefix pass. The per-sample lengths are DEVICE arrays, so a captured graph serves any mix of lengths.
+ * mla_attn_chunk_ragged: mla_attn_chunk with the key count of sample b read from kv_len[b] (int32 [B] on the device, clamped to
+ *   [R, S_cap]; S_cap = rows per sample the caller owns): the R queries of sample b are cache rows [kv_len[b] - R, kv_len[b]), query r
+ *   sees keys [0, kv_len[b] - R + r]. Same grid, same LDS (independent of the lengths), same fixed-order merge: the output rows of
+ *   sample b are bit for bit those of mla_attn_chunk with B = 1 and S_kv = kv_len[b] on that sample's rows. */
+int mla_attn_chunk_ragged(const void* q, const void* k, const void* v, void* o, int B, int H, int head_dim, const int* kv_len, int S_cap,
+                          int R, long long ld, long long batch_stride, long long ld_o, float scale, mla_stream_t stream);
+/* mla_gemm_suffix_bf16: the weight-streaming projection out row m = x[m] . W^T (+ residual[m]) for 1 <= M <= 256 rows and any
+ *   K % 8 == 0, plain input only (RMSNorm / SwiGLU are formed once per projection by mla_rmsnorm_fwd / mla_swiglu_fwd). Row m is row
+ *   p = m % rows_per_batch of sample b = m / rows_per_batch and is written at out + b * out_batch_stride + (slot[b] + p) * ldo; with
+ *   the RoPE epilogue (columns [0, rope_cols), no residual) it is rotated with table row slot[b] + p of rope_cos / rope_sin
+ *   ([cap_rows, 64] fp32). slot: int32 [B] on the device (the sample's prefix length), or NULL = all zero (mla_gemm_skinny_bf16's
+ *   addressing, cap_rows ignored). Rows with slot[b] + p outside [0, cap_rows) are not written. Deterministic (fixed-order sums, no
+ *   atomics, no workspace). M <= 64: mla_gemm_skinny_bf16's K split and summation order -- bit-identical to it when every slot[b] is
+ *   the same (out and the tables offset by that slot). M > 64: 32 W rows per workgroup and up to 16 x blocks per wave, so that x is
+ *   re-read from L2 once per 32 weight rows. Every W fragment is loaded by exactly one wave of one workgroup. */
+int mla_gemm_suffix_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
+                         int rows_per_batch, const int* slot, int cap_rows, const void* residual, long long ld_res, int M, int N, int K,
+                         const float* rope_cos, const float* rope_sin, int rope_cols, mla_stream_t stream);
 
 /* ---- losses: CrossEntropyLoss modeling_llama.py:1258-1269; InfoNCE models/mla/fuser/contrastive.py:208-215 */
 int mla_ce_fwd(const void* logits, int logits_fp32, long long ld, const long long* labels, float* loss, float* lse, int rows,

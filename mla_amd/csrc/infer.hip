@@ -10,7 +10,11 @@
 //   mla_gemm_skinny_bf16  the gemv contract for 1 <= M <= 64 rows and any K: W straight into MFMA A operands, x rows as B operands, no
 //                      staging; 8 waves split K per 16-row tile.
 //   mla_attn_chunk     the decode contract for 1 <= R <= 64 rows and any S_kv: online softmax over 64-key tiles, MFMA QK^T / PV.
-// infer.py keeps gemv / decode for every shape they accept and uses the other two beyond (action chunks of 8..63 steps).
+//   mla_gemm_suffix_bf16  plain-input projection for 1 <= M <= 256 rows of a batch of samples: the skinny kernel's fragments with 1 / 2 / 4
+//                      W tiles per workgroup, per-sample cache slots and rotary positions read from a device array.
+//   mla_attn_chunk_ragged  mla_attn_chunk with one key count per sample, read from a device array.
+// infer.py keeps gemv / decode for every shape they accept and uses the other two beyond (action chunks of 8..63 steps); the last two
+// serve batched sampling (B observations with prompts of different lengths on one pass).
 // All are HBM-bound by construction: algorithmic bytes = the weight matrix (gemv) / the K and V rows of the head (decode).
 #include "common.h"
 
@@ -474,6 +478,118 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* _
   }
 }
 
+// ---- suffix GEMM for 1 <= M <= 256 rows of a BATCH of samples (plain input: the batched pass forms RMSNorm / SwiGLU once per projection
+// with the stand-alone kernels): gemm_skinny_kernel's fragments and K loop -- 8 waves split K, every wave holds the whole tile -- with
+//   NT  16-row W tiles per workgroup (NT A fragments per K step: x is re-read from L2 once per NT * 16 W rows instead of once per 16),
+//   MB  16-row x blocks (up to 16: 256 rows),
+//   ragged addressing: row m is row p = m % rpb of sample b = m / rpb and goes to cache row slot[b] + p of that sample (out + b * out_bs +
+//   (slot[b] + p) * ldo), rotated with table row slot[b] + p; slot lives on the device, so a captured graph serves any mix of prefix
+//   lengths. Rows outside [0, cap_rows) are not written.
+// Every W fragment is loaded by exactly one wave of one workgroup: each weight byte is requested once per call.
+// NT = 1 (M <= 64) is gemm_skinny_kernel<MB, 0>'s arithmetic: the same K ranges per wave, the same MFMA order inside a wave, the same
+// fixed-order sum over the 8 waves -> bit-identical outputs. The partial tiles go through LDS one W tile and at most 8 x blocks at a
+// time (64 KiB at most).
+template <int NT, int MB>
+__global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* __restrict__ x, long long ldx, const bf16_t* __restrict__ W, long long ldw,
+                                                                 bf16_t* __restrict__ out, long long ldo, long long out_bs, int rpb,
+                                                                 const int* __restrict__ slot, int cap_rows, const bf16_t* __restrict__ res,
+                                                                 long long ld_res, int M, int N, int K, const float* __restrict__ rope_cos,
+                                                                 const float* __restrict__ rope_sin, int rope_cols) {
+  constexpr int NL = NT + MB;                                          // 16-B loads per lane and K step
+  constexpr int U = NL <= 3 ? 8 : (NL <= 5 ? 4 : (NL <= 10 ? 2 : 1));  // K steps whose loads are issued before the first MFMA
+  constexpr int MG = MB < 8 ? MB : 8;                                  // x blocks per epilogue round
+  static_assert(MB % MG == 0, "x blocks come in whole epilogue rounds");
+  __shared__ __attribute__((aligned(16))) float lds[SK_NW * MG * 256];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
+  const int tile0 = blockIdx.x * NT;
+  const bf16_t* wr[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int tile = tile0 + nt;
+    const bool rot = rope_cos != nullptr && tile * 16 < rope_cols;
+    const int nrow = rot ? (tile >> 3) * 128 + ((li & 8) ? 64 : 0) + (tile & 7) * 8 + (li & 7) : tile * 16 + li;
+    wr[nt] = W + (long long)(nrow < N ? nrow : N - 1) * ldw;
+  }
+  const bf16_t* xr[MB];
+  bool xok[MB];
+#pragma unroll
+  for (int mb = 0; mb < MB; ++mb) {
+    const int m = mb * 16 + li;
+    xok[mb] = m < M;
+    xr[mb] = x + (long long)(xok[mb] ? m : 0) * ldx;
+  }
+  const int steps = (K + 31) >> 5, spw = (steps + SK_NW - 1) / SK_NW;
+  const int s_beg = wave * spw, s_end = s_beg + spw < steps ? s_beg + spw : steps;
+  f32x4_t acc[NT][MB];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) acc[nt][mb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  const u32x4_t zero = {0u, 0u, 0u, 0u};
+  for (int s0 = s_beg; s0 < s_end; s0 += U) {
+    u32x4_t a[U][NT], b[U][MB];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int k = (s0 + u) * 32 + g * 8;
+      const bool ok = s0 + u < s_end && k < K;
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) a[u][nt] = ok ? __builtin_nontemporal_load((const u32x4_t*)(wr[nt] + k)) : zero;
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb) b[u][mb] = ok && xok[mb] ? *(const u32x4_t*)(xr[mb] + k) : zero;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (s0 + u < s_end) {                                            // wave-uniform
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+          for (int mb = 0; mb < MB; ++mb)
+            acc[nt][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(a[u][nt]), as_frag(b[u][mb]), acc[nt][mb], 0, 0, 0);
+      }
+    }
+  }
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int tile = tile0 + nt;
+    const bool rot = rope_cos != nullptr && tile * 16 < rope_cols;
+#pragma unroll
+    for (int mg = 0; mg < MB; mg += MG) {
+      // partial tiles of W tile nt, x blocks mg .. mg + MG - 1 -> LDS; D[n][m] of a block sits in lane (n >> 2) * 16 + (m & 15), register n & 3
+#pragma unroll
+      for (int mb = 0; mb < MG; ++mb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) lds[((wave * MG + mb) * 4 + r) * 64 + lane] = acc[nt][mg + mb][r];
+      __syncthreads();
+      for (int e = threadIdx.x; e < 16 * MG * 16; e += 64 * SK_NW) {
+        const int ml = e % (MG * 16), i = e / (MG * 16);
+        const int m = mg * 16 + ml;
+        const int n = rot ? (tile >> 3) * 128 + ((i & 8) ? 64 : 0) + (tile & 7) * 8 + (i & 7) : tile * 16 + i;
+        if (m >= M || n >= N) continue;
+        const int mb = ml >> 4, col = ml & 15;
+        const int sb = m / rpb, p = m - sb * rpb;
+        const int row = (slot ? slot[sb] : 0) + p;
+        if (row < 0 || row >= cap_rows) continue;
+        float v = 0.f, partner = 0.f;
+#pragma unroll
+        for (int w = 0; w < SK_NW; ++w) v += lds[((w * MG + mb) * 4 + (i & 3)) * 64 + (i >> 2) * 16 + col];
+        if (res) v += bf2f(res[(long long)m * ld_res + n]);
+        if (rot) {
+          const int ip = i ^ 8;
+#pragma unroll
+          for (int w = 0; w < SK_NW; ++w) partner += lds[((w * MG + mb) * 4 + (ip & 3)) * 64 + (ip >> 2) * 16 + col];
+          // gemv_kernel's epilogue: rope_kernel's arithmetic on the bf16-rounded projection, at the row's position in its sample
+          const int d = n & 63;
+          const float c = rope_cos[(long long)row * 64 + d], sn = rope_sin[(long long)row * 64 + d];
+          const float me = bf2f(f2bf(v)), other = bf2f(f2bf(partner));
+          v = i < 8 ? fmaf(me, c, -(other * sn)) : fmaf(me, c, other * sn);
+        }
+        out[(long long)sb * out_bs + (long long)row * ldo + n] = f2bf(v);
+      }
+      if (nt + 1 < NT || mg + MG < MB) __syncthreads();
+    }
+  }
+}
+
 // ---- suffix attention for 1 <= R <= 64 query rows: one workgroup per (sample, head, block of 16 queries), CH_NW waves taking the key
 // tiles of 64 in turn, each with its own online softmax (running max / sum per query, exp2 with the scale folded in); the waves' states
 // are merged in a fixed order at the end, so LDS does not grow with S_kv. The forward flash kernel's fragment layout: S^T = K Q^T (K rows
@@ -489,12 +605,20 @@ __device__ __forceinline__ bf16x8_t pack_pfrag(const f32x4_t lo, const f32x4_t h
   u[2] = pack2bf(hi[0], hi[1]); u[3] = pack2bf(hi[2], hi[3]);
   return as_frag(u);
 }
+// RAGGED (mla_attn_chunk_ragged): the sample's key count comes from kv_len[b] on the device (clamped to [R, S_cap], the rows the caller owns)
+// instead of the launch argument; everything behind that line is the same code, so a sample's output is the B = 1 launch's bit for bit
+// (the waves' tile assignment starts at key 0 either way), and a captured graph serves any mix of lengths.
+template <bool RAGGED>
 __global__ __launch_bounds__(64 * CH_NW) void attn_chunk_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                                 bf16_t* __restrict__ o, int H, int S_kv, int R, long long ld, long long bs,
-                                                                long long ld_o, float scale) {
+                                                                long long ld_o, float scale, const int* __restrict__ kv_len) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int QB = (R + 15) >> 4;
   const int qb = blockIdx.x % QB, bh = blockIdx.x / QB, h = bh % H, b = bh / H;
+  if (RAGGED) {
+    const int n = kv_len[b];
+    S_kv = n < R ? R : (n > S_kv ? S_kv : n);                            // S_kv arrives as the capacity S_cap
+  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
   bf16_t* vt = (bf16_t*)smem + wave * 128 * CH_VP;                    // this wave's V tile, transposed: [128 channels][CH_VP keys]
   const bf16_t* kb = k + b * bs + h * 128;
@@ -705,8 +829,49 @@ extern "C" int mla_attn_chunk(const void* q, const void* k, const void* v, void*
   MLA_CHECK_ARG(AL16(q) && AL16(k) && AL16(v) && ld % 8 == 0 && batch_stride % 8 == 0 && ld_o % 2 == 0, "mla_attn_chunk: 16-B aligned rows required");
   const size_t lds = (size_t)CH_NW * 128 * CH_VP * 2;                  // >= the merge buffers ((CH_NW * 128 * 16 + 2 * CH_NW * 16) * 4)
   static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute((const void*)attn_chunk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-  hipLaunchKernelGGL(attn_chunk_kernel, dim3(B * H * ((R + 15) / 16)), dim3(64 * CH_NW), lds, stream, (const bf16_t*)q, (const bf16_t*)k,
-                     (const bf16_t*)v, (bf16_t*)o, H, S_kv, R, ld, batch_stride, ld_o, scale);
+  if (!attr) { (void)hipFuncSetAttribute((const void*)attn_chunk_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
+  hipLaunchKernelGGL(attn_chunk_kernel<false>, dim3(B * H * ((R + 15) / 16)), dim3(64 * CH_NW), lds, stream, (const bf16_t*)q, (const bf16_t*)k,
+                     (const bf16_t*)v, (bf16_t*)o, H, S_kv, R, ld, batch_stride, ld_o, scale, (const int*)nullptr);
+  MLA_LAUNCH_CHECK();
+}
+
+extern "C" int mla_attn_chunk_ragged(const void* q, const void* k, const void* v, void* o, int B, int H, int head_dim, const int* kv_len, int S_cap,
+                                     int R, long long ld, long long batch_stride, long long ld_o, float scale, hipStream_t stream) {
+  MLA_CHECK_ARG(q && k && v && o && kv_len, "mla_attn_chunk_ragged: null pointer");
+  MLA_CHECK_ARG(head_dim == 128, "mla_attn_chunk_ragged: head_dim must be 128 (got %d)", head_dim);
+  MLA_CHECK_ARG(B >= 1 && H >= 1 && R >= 1 && R <= CH_RMAX && S_cap >= R, "mla_attn_chunk_ragged: 1 <= R <= 64, R <= S_cap required (R %d, S_cap %d)", R, S_cap);
+  MLA_CHECK_ARG(AL16(q) && AL16(k) && AL16(v) && ld % 8 == 0 && batch_stride % 8 == 0 && ld_o % 2 == 0, "mla_attn_chunk_ragged: 16-B aligned rows required");
+  const size_t lds = (size_t)CH_NW * 128 * CH_VP * 2;
+  static bool attr = false;
+  if (!attr) { (void)hipFuncSetAttribute((const void*)attn_chunk_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
+  hipLaunchKernelGGL(attn_chunk_kernel<true>, dim3(B * H * ((R + 15) / 16)), dim3(64 * CH_NW), lds, stream, (const bf16_t*)q, (const bf16_t*)k,
+                     (const bf16_t*)v, (bf16_t*)o, H, S_cap, R, ld, batch_stride, ld_o, scale, kv_len);
+  MLA_LAUNCH_CHECK();
+}
+
+extern "C" int mla_gemm_suffix_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
+                                    int rows_per_batch, const int* slot, int cap_rows, const void* residual, long long ld_res, int M, int N, int K,
+                                    const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
+  MLA_CHECK_ARG(x && W && out, "mla_gemm_suffix_bf16: null pointer");
+  MLA_CHECK_ARG((rope_cos == nullptr) == (rope_sin == nullptr) && (!rope_cos || (rope_cols > 0 && rope_cols % 128 == 0 && rope_cols <= N && !residual)),
+                "mla_gemm_suffix_bf16: the RoPE epilogue needs both tables, rope_cols a multiple of 128 and <= N, and no residual");
+  MLA_CHECK_ARG(M >= 1 && M <= 256 && N >= 1 && K >= 8 && K % 8 == 0 && rows_per_batch >= 1,
+                "mla_gemm_suffix_bf16: 1 <= M <= 256, K %% 8 == 0 required (M %d, N %d, K %d)", M, N, K);
+  MLA_CHECK_ARG(!slot || cap_rows >= rows_per_batch, "mla_gemm_suffix_bf16: cap_rows (%d) must hold the %d rows of a sample", cap_rows, rows_per_batch);
+  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && ldw % 8 == 0, "mla_gemm_suffix_bf16: x / W rows must be 16-B aligned");
+  if (!slot) cap_rows = rows_per_batch;
+  const int tiles = (N + 15) / 16, blocks = (M + 15) / 16;
+#define MLA_SX_LAUNCH(NT, MB)                                                                                                          \
+  hipLaunchKernelGGL((gemm_suffix_kernel<NT, MB>), dim3((tiles + NT - 1) / NT), dim3(64 * SK_NW), 0, stream, (const bf16_t*)x, ldx,      \
+                     (const bf16_t*)W, ldw, (bf16_t*)out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows, (const bf16_t*)residual,  \
+                     ld_res, M, N, K, rope_cos, rope_sin, rope_cos ? rope_cols : 0)
+  if (blocks <= 1) MLA_SX_LAUNCH(1, 1);
+  else if (blocks == 2) MLA_SX_LAUNCH(1, 2);
+  else if (blocks == 3) MLA_SX_LAUNCH(1, 3);
+  else if (blocks == 4) MLA_SX_LAUNCH(1, 4);
+  else if (blocks <= 6) MLA_SX_LAUNCH(2, 6);
+  else if (blocks <= 8) MLA_SX_LAUNCH(2, 8);
+  else MLA_SX_LAUNCH(2, 16);
+#undef MLA_SX_LAUNCH
   MLA_LAUNCH_CHECK();
 }

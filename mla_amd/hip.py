@@ -39,6 +39,10 @@ _SIGNATURES = {
                              c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
     "mla_attn_chunk": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_float,
                        c_void_p],
+    "mla_attn_chunk_ragged": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_longlong, c_longlong,
+                              c_longlong, c_float, c_void_p],
+    "mla_gemm_suffix_bf16": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_int, c_void_p,
+                             c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
     "mla_gemm_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                       c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
     "mla_gemm_bf16_ws": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -871,6 +875,52 @@ def attn_chunk(cache, B, nheads, D, S_kv, R, scale):
     base = cache.data_ptr()
     call("mla_attn_chunk", c_void_p(base), c_void_p(base + 2 * H), c_void_p(base + 4 * H), _p(o), B, nheads, D, S_kv, R, cache.stride(1),
          cache.stride(0), H, float(scale))
+    return o
+
+
+SUFFIX_MMAX = 256
+
+
+def gemm_suffix(x, W, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, rope=None, slot=None, cap_rows=None):
+    """out row m = x[m] @ W^T (+ residual[m]) for 1 <= M <= 256 rows of a batch of samples (mla_gemm_suffix_bf16; plain input only).
+    Row m is row p = m % rows_per_batch of sample b = m // rows_per_batch and lands at out + b * out_batch_stride + (slot[b] + p) * ldo
+    + out_col. slot: int32 [B] device tensor (the sample's prefix length) with cap_rows = rows per sample that `out` (and the tables) hold;
+    None = every slot 0. rope = (cos [cap_rows or rows_per_batch, 64], sin, rope_cols): row slot[b] + p of the tables rotates the row."""
+    name = "gemm_suffix"
+    _req(x, torch.bfloat16, f"{name} x")
+    _req(W, torch.bfloat16, f"{name} W")
+    _req(out, torch.bfloat16, f"{name} out")
+    M, K = x.shape
+    N = W.shape[0]
+    assert W.shape[1] == K and x.stride(1) == 1 and W.stride(1) == 1
+    if slot is not None:
+        _req(slot, torch.int32, f"{name} slot")
+        assert cap_rows is not None and slot.is_contiguous() and slot.numel() * rows_per_batch >= M
+    cap = int(cap_rows) if slot is not None else int(rows_per_batch)
+    if rope is not None:
+        _req(rope[0], torch.float32, f"{name} rope cos")
+        _req(rope[1], torch.float32, f"{name} rope sin")
+        assert rope[0].shape == (cap, 64) and rope[1].shape == rope[0].shape and rope[0].is_contiguous() and rope[1].is_contiguous()
+        assert out_col == 0 and residual is None
+    if residual is not None:
+        _req(residual, torch.bfloat16, f"{name} residual")
+        assert residual.shape[0] == M and residual.stride(1) == 1
+    call("mla_gemm_suffix_bf16", _p(x), x.stride(0), _p(W), W.stride(0), c_void_p(out.data_ptr() + 2 * out_col), ldo, out_batch_stride,
+         rows_per_batch, _p(slot), cap, _p(residual), residual.stride(0) if residual is not None else 0, M, N, K,
+         _p(rope[0]) if rope is not None else None, _p(rope[1]) if rope is not None else None, int(rope[2]) if rope is not None else 0)
+
+
+def attn_chunk_ragged(cache, B, nheads, D, kv_len, R, scale):
+    """attn_chunk with one key count per sample: kv_len int32 [B] on the device, the R queries of sample b are cache rows
+    [kv_len[b] - R, kv_len[b]) (mla_attn_chunk_ragged; lengths are clamped to [R, cache.shape[1]]). Returns o [B * R, nheads * D] bf16."""
+    _req(cache, torch.bfloat16, "attn_chunk_ragged cache")
+    _req(kv_len, torch.int32, "attn_chunk_ragged kv_len")
+    H = nheads * D
+    assert cache.shape[0] == B and cache.shape[2] == 3 * H and cache.stride(2) == 1 and kv_len.numel() == B and kv_len.is_contiguous()
+    o = torch.empty((B * R, H), dtype=torch.bfloat16, device=cache.device)
+    base = cache.data_ptr()
+    call("mla_attn_chunk_ragged", c_void_p(base), c_void_p(base + 2 * H), c_void_p(base + 4 * H), _p(o), B, nheads, D, _p(kv_len),
+         cache.shape[1], R, cache.stride(1), cache.stride(0), H, float(scale))
     return o
 
 

@@ -23,7 +23,7 @@ from __future__ import annotations
 import math
 import os
 import warnings
-from typing import Optional
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -32,7 +32,88 @@ from . import hip, ops
 _USE_GRAPH = os.environ.get("MLA_INFER_GRAPH", "1") != "0"
 
 
-class PrefixCachedEps:
+class _CachedEpsBase:
+    """What the cached-prefix engines share: the packed weights, the captured suffix pass and the `model(x, t)` call of the samplers.
+    A subclass provides prefill() and _suffix_pass() and sets B, R, T, H, h_in, h_out, cache."""
+
+    def __init__(self, vlm, n_action_rows: int = 1):
+        self.vlm = vlm
+        llm = vlm.llm_backbone.llm
+        self.model, self.cfg = llm.model, llm.config
+        self.T = n_action_rows
+        self.R = 1 + self.T
+        self.nheads, self.eps = self.cfg.num_attention_heads, self.cfg.rms_norm_eps
+        self.cache = None
+        self.graph = None
+        self._graph_failed = False
+        self.graph_error = None      # why the suffix pass could not be captured (eager launches then), for diagnostics
+        self._packed = None          # per layer: the 9 weights with q|k|v and gate|up as views of ONE buffer each (see _weights)
+        self._packed_key = None
+
+    def _weights(self):
+        """Every layer's (ln1, wq, wk, wv, wo, ln2, wg, wu, wd) with q|k|v and gate|up adjacent in memory, so that the prefill runs the
+        fused QKV + RoPE and gate|up + SwiGLU GEMMs and a suffix pass needs one GEMV each instead of three / two (33 MB projections are
+        ~40 % launch + ramp). Under FSDPStrategy the parameters already live like that in the unit's flat buffer (views are used as they
+        are); otherwise the engine keeps packed COPIES (9.4 GB at 7B), rebuilt when a parameter's storage or version changes."""
+        key = tuple((p.data_ptr(), p._version) for layer in self.model.layers for p in layer._weights())
+        shared = self.vlm.__dict__.setdefault("_prefix_packed", {})          # one packed copy per model, shared by its engines
+        if shared.get("key") != key:
+            packed = []
+            with torch.no_grad(), torch.inference_mode(False):
+                for layer in self.model.layers:
+                    ln1, wq, wk, wv, wo, ln2, wg, wu, wd = layer._weights()
+                    if ops.cat_view((wq, wk, wv)) is None:
+                        buf = torch.cat([wq.detach(), wk.detach(), wv.detach()], 0)
+                        H = wq.shape[0]
+                        wq, wk, wv = buf[:H], buf[H:H + wk.shape[0]], buf[H + wk.shape[0]:]
+                    if ops.cat_view((wg, wu)) is None:
+                        buf = torch.cat([wg.detach(), wu.detach()], 0)
+                        wg, wu = buf[:wg.shape[0]], buf[wg.shape[0]:]
+                    packed.append((ln1, wq, wk, wv, wo, ln2, wg, wu, wd))
+            shared["key"], shared["packed"] = key, packed
+        if self._packed is not shared["packed"]:
+            self.graph = None            # a captured pass holds the previous buffers' addresses
+            self._packed, self._packed_key = shared["packed"], key
+        return self._packed
+
+    def _run(self):
+        if _USE_GRAPH and not self._graph_failed:
+            if self.graph is None:
+                try:
+                    self._suffix_pass()                                      # warm-up outside the capture (function attributes, allocator)
+                    torch.cuda.synchronize()
+                    g = torch.cuda.CUDAGraph()
+                    # captured outside inference mode: the generator's graph-state tensors are created by the first capture of a
+                    # process and live as long as any graph does -- as inference tensors they would make every later capture that
+                    # runs outside inference mode fail; the pass itself only touches the engine's (normal) buffers
+                    with torch.inference_mode(False), torch.no_grad(), torch.cuda.graph(g):
+                        self._suffix_pass()
+                    self.graph = g
+                except Exception as e:   # noqa: BLE001 -- a failed capture is not fatal: the eager launches compute the same thing
+                    self._graph_failed, self.graph_error = True, repr(e)
+                    self.graph = None
+                    torch.cuda.synchronize()
+            if self.graph is not None:
+                self.graph.replay()
+                return
+        self._suffix_pass()
+
+    # ------------------------------------------------------------------------------------------ the model(x, t, **kw) the samplers call
+    def __call__(self, x, t, **ignored):
+        """Same contract as PrismaticVLM.forward in eval mode: returns (None, noise_pred [B, T, action_dim])."""
+        vlm, bf16 = self.vlm, torch.bfloat16
+        with torch.no_grad():
+            x_e = vlm.x_embedder(x.to(bf16))                                  # [B, T, H]   (prismatic.py:873-880 casts)
+            t_e = vlm.t_embedder(t.to(bf16)).unsqueeze(1)                     # [B, 1, H]
+            assert x_e.shape[1] == self.T, (x_e.shape, self.T)
+            self.h_in.copy_(torch.cat([t_e, x_e], dim=1).reshape(self.B * self.R, self.H))
+            self._run()
+            picked = self.h_out.view(self.B, self.R, self.H)[:, 1:].reshape(self.B * self.T, self.H).contiguous()
+            noise_pred = vlm.final_layer(picked).view(self.B, self.T, -1)
+        return None, noise_pred
+
+
+class PrefixCachedEps(_CachedEpsBase):
     """One engine per (batch, prefix length, action rows): the per-layer q|k|v cache, the suffix pass's static input / output rows and its
     captured graph live as long as the engine, `prefill()` refreshes the cache for a new observation (the graph stays valid: same
     addresses). `PrefixCachedEps.for_inputs(vlm, ...)` returns the vlm's engine for the given inputs, prefilled."""
@@ -78,46 +159,6 @@ class PrefixCachedEps:
             eng = engines[key] = cls(vlm, n_action_rows)
         eng.prefill(input_ids, k, **model_kwargs)
         return eng
-
-    def __init__(self, vlm, n_action_rows: int = 1):
-        self.vlm = vlm
-        llm = vlm.llm_backbone.llm
-        self.model, self.cfg = llm.model, llm.config
-        self.T = n_action_rows
-        self.R = 1 + self.T
-        self.nheads, self.eps = self.cfg.num_attention_heads, self.cfg.rms_norm_eps
-        self.cache = None
-        self.graph = None
-        self._graph_failed = False
-        self.graph_error = None      # why the suffix pass could not be captured (eager launches then), for diagnostics
-        self._packed = None          # per layer: the 9 weights with q|k|v and gate|up as views of ONE buffer each (see _weights)
-        self._packed_key = None
-
-    def _weights(self):
-        """Every layer's (ln1, wq, wk, wv, wo, ln2, wg, wu, wd) with q|k|v and gate|up adjacent in memory, so that the prefill runs the
-        fused QKV + RoPE and gate|up + SwiGLU GEMMs and a suffix pass needs one GEMV each instead of three / two (33 MB projections are
-        ~40 % launch + ramp). Under FSDPStrategy the parameters already live like that in the unit's flat buffer (views are used as they
-        are); otherwise the engine keeps packed COPIES (9.4 GB at 7B), rebuilt when a parameter's storage or version changes."""
-        key = tuple((p.data_ptr(), p._version) for layer in self.model.layers for p in layer._weights())
-        shared = self.vlm.__dict__.setdefault("_prefix_packed", {})          # one packed copy per model, shared by its engines
-        if shared.get("key") != key:
-            packed = []
-            with torch.no_grad(), torch.inference_mode(False):
-                for layer in self.model.layers:
-                    ln1, wq, wk, wv, wo, ln2, wg, wu, wd = layer._weights()
-                    if ops.cat_view((wq, wk, wv)) is None:
-                        buf = torch.cat([wq.detach(), wk.detach(), wv.detach()], 0)
-                        H = wq.shape[0]
-                        wq, wk, wv = buf[:H], buf[H:H + wk.shape[0]], buf[H + wk.shape[0]:]
-                    if ops.cat_view((wg, wu)) is None:
-                        buf = torch.cat([wg.detach(), wu.detach()], 0)
-                        wg, wu = buf[:wg.shape[0]], buf[wg.shape[0]:]
-                    packed.append((ln1, wq, wk, wv, wo, ln2, wg, wu, wd))
-            shared["key"], shared["packed"] = key, packed
-        if self._packed is not shared["packed"]:
-            self.graph = None            # a captured pass holds the previous buffers' addresses
-            self._packed, self._packed_key = shared["packed"], key
-        return self._packed
 
     def prefill(self, input_ids, k, images=None, point_cloud=None, camera_name=None, proprio=None, tactile=None, gripper_xyz=None, **unused):
         vlm, bf16, dev = self.vlm, torch.bfloat16, input_ids.device
@@ -192,35 +233,173 @@ class PrefixCachedEps:
         hn, _ = hip.rmsnorm_fwd(h, self.model.norm.weight, self.eps)
         self.h_out.copy_(hn)
 
-    def _run(self):
-        if _USE_GRAPH and not self._graph_failed:
-            if self.graph is None:
-                try:
-                    self._suffix_pass()                                      # warm-up outside the capture (function attributes, allocator)
-                    torch.cuda.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        self._suffix_pass()
-                    self.graph = g
-                except Exception as e:   # noqa: BLE001 -- a failed capture is not fatal: the eager launches compute the same thing
-                    self._graph_failed, self.graph_error = True, repr(e)
-                    self.graph = None
-                    torch.cuda.synchronize()
-            if self.graph is not None:
-                self.graph.replay()
-                return
-        self._suffix_pass()
 
-    # ------------------------------------------------------------------------------------------ the model(x, t, **kw) the samplers call
-    def __call__(self, x, t, **ignored):
-        """Same contract as PrismaticVLM.forward in eval mode: returns (None, noise_pred [B, T, action_dim])."""
-        vlm, bf16 = self.vlm, torch.bfloat16
+
+# ================================================================================================ batched action sampling
+# B observations with prompts of different lengths on ONE cached-prefix pass (MLA.predict_action_diff_batch; the reference's
+# `predict_action_batch`, models/mla/model_mla.py:994, names the use case -- "batch inference in the simulators" -- but reads an attribute
+# MLA never defines). A pass streams the decoder weights once whatever the row count, so N environments cost one prefill on the
+# training GEMMs plus 8 weight passes instead of N prefills plus 8 N passes.
+SPLICE_TAG = 29871                                  # prismatic.py:882-887 (eval): the [t, x] tokens go in front of its last occurrence
+PROMPT_TAIL = (29871, 32001, 32002, 29871)          # model_mla.py:640-645: appended unless the row already ends with the tag, then [:-3]
+
+
+class SubBatchPlan(NamedTuple):
+    """One cached-prefix pass of `plan_batch`: samples [start, stop) of the call. Per sample b: ids[b] the final prompt ids, k[b] the splice
+    position (the last tag), S_p[b] prefix rows ([BOS | front tokens | text[1:k] | proprio]), slot[b] = S_p[b] the first cache row of its
+    suffix rows, kv_len[b] = S_p[b] + R the keys its last suffix row sees. S_pmax: rows every prefix is right-padded to for the prefill;
+    S_cap: rows per sample of the cache (S_pmax + R rounded up to the bucket), part of the engine's key."""
+    start: int
+    stop: int
+    ids: Tuple[Tuple[int, ...], ...]
+    k: Tuple[int, ...]
+    S_p: Tuple[int, ...]
+    slot: Tuple[int, ...]
+    kv_len: Tuple[int, ...]
+    S_pmax: int
+    S_cap: int
+    R: int
+
+
+def plan_batch(ids_rows: Sequence[Sequence[int]], n_action_rows: int, n_front: int, max_rows: int = 256, bucket: int = 64,
+               add_tail: bool = True):
+    """Pure host planning of a batched sampling call -> list of SubBatchPlan, in order.
+    ids_rows: one id sequence per sample (different lengths). add_tail: predict_action_diff's prompt handling per row -- a row that does
+    not end with the tag gets PROMPT_TAIL appended and the last three ids dropped again. A row without the tag raises IndexError (as the
+    splice of prismatic.py:983 would). n_front: fused tokens between BOS and the text (513 at 7B). R = 1 + n_action_rows suffix rows per
+    sample; consecutive samples are grouped into passes of at most max_rows suffix rows."""
+    R = 1 + int(n_action_rows)
+    if R > max_rows:
+        raise ValueError(f"{R} suffix rows per sample exceed the {max_rows} rows of a pass")
+    if len(ids_rows) == 0:
+        raise ValueError("plan_batch: no samples")
+    rows, ks = [], []
+    for b, row in enumerate(ids_rows):
+        row = [int(t) for t in row]
+        if add_tail and (len(row) == 0 or row[-1] != SPLICE_TAG):
+            row = (row + list(PROMPT_TAIL))[:-3]
+        if SPLICE_TAG not in row:
+            raise IndexError(f"input_ids row {b} without the splice tag {SPLICE_TAG} (models/vlm/prismatic.py:983)")
+        k = len(row) - 1 - row[::-1].index(SPLICE_TAG)                    # last occurrence
+        if k < 1:
+            raise IndexError(f"input_ids row {b}: the splice tag {SPLICE_TAG} must not be the first id")
+        rows.append(tuple(row))
+        ks.append(k)
+    per = max_rows // R
+    plans = []
+    for start in range(0, len(rows), per):
+        stop = min(start + per, len(rows))
+        k = tuple(ks[start:stop])
+        S_p = tuple(1 + n_front + (kk - 1) + 1 for kk in k)
+        S_pmax = max(S_p)
+        S_cap = -(-(S_pmax + R) // bucket) * bucket
+        plans.append(SubBatchPlan(start, stop, tuple(rows[start:stop]), k, S_p, S_p, tuple(v + R for v in S_p), S_pmax, S_cap, R))
+    return plans
+
+
+class BatchedPrefixCachedEps(_CachedEpsBase):
+    """PrefixCachedEps for B samples whose splice tags sit at different positions. The prefixes are right-padded to S_pmax and prefilled in
+    one varlen pass per layer (ops.DecoderLayerFn._fwd with seqlens); the cache is [B, S_cap, 3H] and the suffix rows of sample b live at
+    rows S_p[b] .. S_p[b] + R (rows behind them are never read). `slot` and `kv_len` are device tensors the kernels read
+    (mla_gemm_suffix_bf16, mla_attn_chunk_ragged), refreshed by copy_ in prefill(): one engine -- and one captured graph -- per
+    (B, S_cap, R, device) serves every mix of prompt lengths in that capacity bucket. RMSNorm / SwiGLU are formed once per projection by
+    the stand-alone kernels (the values the fused forms produce), then the plain weight-streaming GEMM runs over up to 256 rows."""
+
+    MAX_ROWS = 256                   # suffix rows per pass (mla_gemm_suffix_bf16); larger batches are served as consecutive sub-batches
+    MAX_R = 64                       # rows per sample (mla_attn_chunk_ragged)
+    BUCKET = 64                      # cache capacity granularity in rows
+
+    @classmethod
+    def supports_batch(cls, vlm, n_action_rows: int) -> bool:
+        """head_dim 128 and at most 64 suffix rows per sample; otherwise the caller loops over whole-forward batch-1 calls (warns once)."""
+        cfg = vlm.llm_backbone.llm.config
+        R, D = 1 + n_action_rows, cfg.hidden_size // cfg.num_attention_heads
+        if R <= cls.MAX_R and D == 128:
+            return True
+        seen = vlm.__dict__.setdefault("_prefix_unsupported", set())
+        if ("batch", R, D) not in seen:
+            seen.add(("batch", R, D))
+            warnings.warn(f"BatchedPrefixCachedEps: {R} suffix rows per sample (max {cls.MAX_R}) / head_dim {D} (needs 128) are beyond the "
+                          "batched cached-prefix kernels; sampling every observation with a whole forward per step", RuntimeWarning, stacklevel=3)
+        return False
+
+    @classmethod
+    def for_batch(cls, vlm, ids_rows, n_action_rows: int, images=None, point_cloud=None, camera_name=None, proprio=None, add_tail=True,
+                  **unused):
+        """Generator over the passes of one call: runs the encoders once over all samples, plans (plan_batch: ids_rows are the prompts as
+        the caller has them, the prompt tail is handled there) and yields
+        (SubBatchPlan, prefilled engine) per sub-batch. Two sub-batches may share an engine: finish sampling one before taking the next."""
         with torch.no_grad():
-            x_e = vlm.x_embedder(x.to(bf16))                                  # [B, T, H]   (prismatic.py:873-880 casts)
-            t_e = vlm.t_embedder(t.to(bf16)).unsqueeze(1)                     # [B, 1, H]
-            assert x_e.shape[1] == self.T, (x_e.shape, self.T)
-            self.h_in.copy_(torch.cat([t_e, x_e], dim=1).reshape(self.B * self.R, self.H))
-            self._run()
-            picked = self.h_out.view(self.B, self.R, self.H)[:, 1:].reshape(self.B * self.T, self.H).contiguous()
-            noise_pred = vlm.final_layer(picked).view(self.B, self.T, -1)
-        return None, noise_pred
+            parts, _, _, _, _, _ = vlm.get_fused_tokens(images, point_cloud, None, None, camera_name)
+            vlm.vision_tower_2d.assert_masks_ok()
+            front = torch.cat(parts, dim=1)                                   # [B, n_front, H]
+        plans = plan_batch(ids_rows, n_action_rows, int(front.shape[1]), cls.MAX_ROWS, cls.BUCKET, add_tail=add_tail)
+        engines = vlm.__dict__.setdefault("_prefix_engines_batched", {})
+        for sub in plans:
+            key = (sub.stop - sub.start, sub.S_cap, sub.R, str(front.device))
+            eng = engines.get(key)
+            if eng is None:
+                if len(engines) >= 4:
+                    engines.pop(next(iter(engines)))
+                eng = engines[key] = cls(vlm, n_action_rows)
+            eng.prefill(sub, front[sub.start:sub.stop], proprio[sub.start:sub.stop])
+            yield sub, eng
+
+    def prefill(self, sub: SubBatchPlan, front, proprio):
+        vlm, bf16, dev = self.vlm, torch.bfloat16, front.device
+        B, S_pmax = sub.stop - sub.start, sub.S_pmax
+        with torch.no_grad():
+            proprio_e = vlm.proprio_embedder(proprio.to(bf16))                # [B, 1, H]
+            H = front.shape[2]
+            prefix = torch.zeros((B, S_pmax, H), dtype=bf16, device=dev)
+            for b in range(B):
+                e = vlm.llm_backbone.embed_input_ids(torch.tensor([sub.ids[b]], dtype=torch.long, device=dev))[0]
+                prefix[b, :sub.S_p[b]] = torch.cat([e[:1], front[b], e[1:sub.k[b]], proprio_e[b]], dim=0)
+            if self.cache is None:
+                self.B, self.H, self.S_cap = B, H, sub.S_cap
+                self.D = H // self.nheads
+                self.rot = self.model.layers[0].self_attn.rotary_emb
+                self.cos_c, self.sin_c = self.rot.tables(self.S_cap, dev)    # the epilogue rotates row slot[b] + p with table row slot[b] + p
+                with torch.inference_mode(False):                            # the engine outlives the (inference-mode) call that creates it
+                    self.cache = [torch.zeros((B, self.S_cap, 3 * H), dtype=bf16, device=dev) for _ in self.model.layers]
+                    self.h_in = torch.zeros((B * self.R, H), dtype=bf16, device=dev)
+                    self.h_out = torch.zeros((B * self.R, H), dtype=bf16, device=dev)
+                    self.slot = torch.zeros(B, dtype=torch.int32, device=dev)
+                    self.kv_len = torch.full((B,), self.R, dtype=torch.int32, device=dev)
+            assert (B, H, sub.S_cap, sub.R) == (self.B, self.H, self.S_cap, self.R) and S_pmax + self.R <= self.S_cap
+            self.slot.copy_(torch.tensor(sub.slot, dtype=torch.int32))
+            self.kv_len.copy_(torch.tensor(sub.kv_len, dtype=torch.int32))
+            seqlens = torch.tensor(sub.S_p, dtype=torch.int32, device=dev)
+            cos_p, sin_p = self.rot.tables(S_pmax, dev)
+            h = prefix.reshape(B * S_pmax, H)
+            for w, c in zip(self._weights(), self.cache):
+                h, acts = ops.DecoderLayerFn._fwd(h, seqlens, cos_p, sin_p, B, S_pmax, self.nheads, self.eps, w)
+                c[:, :S_pmax].copy_(acts.qkv[:B * S_pmax].view(B, S_pmax, 3 * H))
+                del acts
+
+    def _proj(self, x, weights, out=None, residual=None, **kw):
+        wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
+        assert wcat is not None, "the packed weights are adjacent in memory (_weights)"
+        M = x.shape[0]
+        if out is None:
+            out = torch.empty((M, wcat.shape[0]), dtype=torch.bfloat16, device=x.device)
+            hip.gemm_suffix(x, wcat, out, out.stride(0), 0, M, residual)
+        else:
+            hip.gemm_suffix(x, wcat, out, out.stride(-2), out.stride(0), self.R, residual, **kw)
+        return out
+
+    def _suffix_pass(self):
+        B, R, H = self.B, self.R, self.H
+        h = self.h_in
+        scale = 1.0 / math.sqrt(self.D)
+        for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd), c in zip(self._packed, self.cache):
+            xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
+            # q|k|v rows of sample b -> cache rows slot[b] .. slot[b] + R, q and k rotated at those positions in the epilogue
+            self._proj(xn, (wq, wk, wv), out=c, slot=self.slot, cap_rows=self.S_cap, rope=(self.cos_c, self.sin_c, 2 * H))
+            o = hip.attn_chunk_ragged(c, B, self.nheads, self.D, self.kv_len, R, scale)
+            h1 = self._proj(o, (wo,), residual=h)
+            xn2, _ = hip.rmsnorm_fwd(h1, ln2, self.eps)
+            gu = self._proj(xn2, (wg, wu))
+            h = self._proj(hip.swiglu_fwd(gu), (wd,), residual=h1)
+        hn, _ = hip.rmsnorm_fwd(h, self.model.norm.weight, self.eps)
+        self.h_out.copy_(hn)

@@ -270,6 +270,62 @@ class MLA(nn.Module):
             a[..., g] = np.where(a[..., g] < 0.5, 0, 1)
         return np.where(mask, 0.5 * (a + 1) * (hi - lo) + lo, a)
 
+    # ---- the per-sample preprocessing of predict_action_diff, shared with predict_action_diff_batch
+    def _prompt_ids(self, instruction, who):
+        # :626-632 -- prompt text from the backbone's builder, ids from the backbone's tokenizer (the Llama tokenizer files are not
+        # in this image: attach one as vlm.llm_backbone.tokenizer, or pass input_ids)
+        tokenizer = getattr(self.vlm.llm_backbone, "tokenizer", None)
+        if instruction is None or tokenizer is None or not callable(tokenizer):
+            raise ValueError(f"{who} needs `input_ids`, or `instruction` plus a callable vlm.llm_backbone.tokenizer")
+        builder = self.vlm.llm_backbone.prompt_builder_fn("openvla")
+        builder.add_turn(role="human", message=f"What action should the robot take to {instruction.lower()}?")
+        return tokenizer(builder.get_prompt(), truncation=True, return_tensors="pt").input_ids
+
+    @staticmethod
+    def _check_cfg_scale(cfg_scale):
+        if cfg_scale > 1.0:
+            raise NotImplementedError("classifier-free guidance: the reference calls self.vlm.forward_with_cfg (model_mla.py:718-729), which "
+                                      "PrismaticVLM does not define -- cfg_scale > 1 raises there too; the shipped evaluation uses cfg_scale=0")
+
+    def _preprocessed_image(self, image):
+        if not (torch.is_tensor(image) and image.is_floating_point()):
+            # PIL image / uint8 HWC frame: the reference's CLIPImageProcessor step (:656-657), PIL-exact on the GPU
+            image = self.vlm.get_vision_tower_2d().image_processor.preprocess(image, return_tensors="pt")["pixel_values"][0]
+        return image
+
+    @staticmethod
+    def _ids_with_tail(input_ids, device):
+        input_ids = input_ids.to(device)
+        if not bool(torch.all(input_ids[:, -1] == 29871)):
+            tail = torch.tensor([[29871, 32001, 32002, 29871]], dtype=torch.long, device=device)
+            input_ids = torch.cat((input_ids, tail), dim=1)[:, :-3]
+        return input_ids
+
+    @staticmethod
+    def _image_batch(image, device):
+        img = image.to(device)
+        if img.dim() == 3:
+            img = img.unsqueeze(0)
+        if img.shape[1] == 3:
+            img = torch.cat([img, torch.ones_like(img[:, :1])], dim=1)
+        return img
+
+    @staticmethod
+    def _pointcloud_batch(pointcloud, device):
+        if isinstance(pointcloud, np.ndarray):
+            pointcloud = torch.from_numpy(pointcloud)
+        if pointcloud is not None:
+            pointcloud = pointcloud.to(device).contiguous()
+            if pointcloud.dim() == 2:
+                pointcloud = pointcloud.unsqueeze(0)
+        return pointcloud
+
+    def _proprio_token(self, cur_robot_state, unnorm_key, device):
+        if cur_robot_state is None:
+            raise ValueError("cur_robot_state is required: the proprio token is always spliced in (prismatic.py:985-990)")
+        st = self.normalize_proprio(np.asarray(cur_robot_state), unnorm_key) if self.norm_stats is not None else np.asarray(cur_robot_state)
+        return torch.tensor(st, dtype=torch.float32).reshape(1, 1, -1).to(device)
+
     @torch.inference_mode()
     def predict_action_diff(self, image=None, pointcloud=None, instruction: Optional[str] = None, cur_robot_state=None,
                             unnorm_key: Optional[str] = None, cfg_scale: float = 0.0, use_ddim: bool = True, num_ddim_steps: int = 8,
@@ -292,41 +348,14 @@ class MLA(nn.Module):
         self.vlm.eval()
         device = next(self.vlm.parameters()).device
         if input_ids is None:
-            # :626-632 -- prompt text from the backbone's builder, ids from the backbone's tokenizer (the Llama tokenizer files are not
-            # in this image: attach one as vlm.llm_backbone.tokenizer, or pass input_ids)
-            tokenizer = getattr(self.vlm.llm_backbone, "tokenizer", None)
-            if instruction is None or tokenizer is None or not callable(tokenizer):
-                raise ValueError("predict_action_diff needs `input_ids`, or `instruction` plus a callable vlm.llm_backbone.tokenizer")
-            builder = self.vlm.llm_backbone.prompt_builder_fn("openvla")
-            builder.add_turn(role="human", message=f"What action should the robot take to {instruction.lower()}?")
-            input_ids = tokenizer(builder.get_prompt(), truncation=True, return_tensors="pt").input_ids
-        if cfg_scale > 1.0:
-            raise NotImplementedError("classifier-free guidance: the reference calls self.vlm.forward_with_cfg (model_mla.py:718-729), which "
-                                      "PrismaticVLM does not define -- cfg_scale > 1 raises there too; the shipped evaluation uses cfg_scale=0")
-        if not (torch.is_tensor(image) and image.is_floating_point()):
-            # PIL image / uint8 HWC frame: the reference's CLIPImageProcessor step (:656-657), PIL-exact on the GPU
-            image = self.vlm.get_vision_tower_2d().image_processor.preprocess(image, return_tensors="pt")["pixel_values"][0]
-        input_ids = input_ids.to(device)
-        if not bool(torch.all(input_ids[:, -1] == 29871)):
-            tail = torch.tensor([[29871, 32001, 32002, 29871]], dtype=torch.long, device=device)
-            input_ids = torch.cat((input_ids, tail), dim=1)[:, :-3]
-        img = image.to(device)
-        if img.dim() == 3:
-            img = img.unsqueeze(0)
-        if img.shape[1] == 3:
-            img = torch.cat([img, torch.ones_like(img[:, :1])], dim=1)
-        if isinstance(pointcloud, np.ndarray):
-            pointcloud = torch.from_numpy(pointcloud)
-        if pointcloud is not None:
-            pointcloud = pointcloud.to(device).contiguous()
-            if pointcloud.dim() == 2:
-                pointcloud = pointcloud.unsqueeze(0)
+            input_ids = self._prompt_ids(instruction, "predict_action_diff")
+        self._check_cfg_scale(cfg_scale)
+        image = self._preprocessed_image(image)
+        input_ids = self._ids_with_tail(input_ids, device)
+        img = self._image_batch(image, device)
+        pointcloud = self._pointcloud_batch(pointcloud, device)
         model_kwargs = {"input_ids": input_ids, "images": img, "point_cloud": pointcloud, "camera_name": camera_name}
-        if cur_robot_state is not None:
-            st = self.normalize_proprio(np.asarray(cur_robot_state), unnorm_key) if self.norm_stats is not None else np.asarray(cur_robot_state)
-            model_kwargs["proprio"] = torch.tensor(st, dtype=torch.float32).reshape(1, 1, -1).to(device)
-        else:
-            raise ValueError("cur_robot_state is required: the proprio token is always spliced in (prismatic.py:985-990)")
+        model_kwargs["proprio"] = self._proprio_token(cur_robot_state, unnorm_key, device)
         if noise is None:
             noise = torch.randn(1, self.future_action_window_size + 1, action_dim, device=device)
         _ = torch.randint(0, self.diffusion.num_timesteps, (self.future_action_window_size + 1,), device=device)  # drawn, unused (:708)
@@ -345,4 +374,73 @@ class MLA(nn.Module):
             samples = self.diffusion.p_sample_loop(eps_model, noise.shape, noise.to(device).float(), clip_denoised=False,
                                                    model_kwargs=model_kwargs, progress=False, device=device)
         normalized = samples[0].float().cpu().numpy()
+        return self.unnormalize_actions(normalized, unnorm_key) if self.norm_stats is not None else normalized
+
+    @torch.inference_mode()
+    def predict_action_diff_batch(self, images, pointclouds, instructions=None, cur_robot_states=None, unnorm_key: Optional[str] = None,
+                                  cfg_scale: float = 0.0, use_ddim: bool = True, num_ddim_steps: int = 8, action_dim: int = 7, *,
+                                  input_ids=None, noise: Optional[torch.Tensor] = None, camera_name: str = "rlbench_front",
+                                  reuse_prefix: bool = True) -> np.ndarray:
+        """B observations -> [B, T, action_dim]: by definition B independent `predict_action_diff` calls (the reference's
+        `predict_action_batch`, model_mla.py:994, is dead code), computed on ONE cached prefix pass per DDIM step
+        (mla_amd/infer.py:BatchedPrefixCachedEps): the prompts may have different lengths, the FPS start indices are drawn once per chunk.
+        ``images`` / ``pointclouds`` / ``cur_robot_states``: sequences of B per-sample values in the forms predict_action_diff takes (or
+        stacked arrays); ``input_ids``: a list of B tensors ([L_b] or [1, L_b]) of different lengths, or ``instructions`` (B strings) plus
+        the attached tokenizer; ``noise``: [B, T, action_dim]. Every per-sample step (image pre-processing, mask channel, prompt tail,
+        proprio normalisation, un-normalisation) is predict_action_diff's. B = 1 IS predict_action_diff; ``reuse_prefix=False`` loops the
+        reference's control flow; more than 256 suffix rows are served as consecutive sub-batches; head_dim != 128 warns once and loops
+        over whole-forward batch-1 calls."""
+        B = len(images)
+        T = self.future_action_window_size + 1
+        if input_ids is None:
+            if instructions is None or len(instructions) != B:
+                raise ValueError("predict_action_diff_batch needs `input_ids` (one tensor per sample), or B `instructions` plus a callable "
+                                 "vlm.llm_backbone.tokenizer")
+            input_ids = [self._prompt_ids(ins, "predict_action_diff_batch") for ins in instructions]
+        if pointclouds is None:
+            pointclouds = [None] * B
+        if not (len(input_ids) == B and len(pointclouds) == B and cur_robot_states is not None and len(cur_robot_states) == B):
+            raise ValueError("predict_action_diff_batch: images, pointclouds, cur_robot_states and input_ids / instructions need one entry per sample")
+        if noise is not None and tuple(noise.shape[:2]) != (B, T):
+            raise ValueError(f"noise must be [B, T, action_dim] = [{B}, {T}, ...], got {tuple(noise.shape)}")
+        self._check_cfg_scale(cfg_scale)
+        ids_rows = [ids.reshape(1, -1) for ids in input_ids]
+
+        def one(b, **kw):
+            return self.predict_action_diff(images[b], pointclouds[b], None, cur_robot_states[b], unnorm_key, cfg_scale, use_ddim, num_ddim_steps,
+                                            action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b:b + 1],
+                                            camera_name=camera_name, **kw)
+        if B == 1:
+            return one(0, reuse_prefix=reuse_prefix)[None]
+        if reuse_prefix:
+            from .infer import BatchedPrefixCachedEps
+            reuse_prefix = BatchedPrefixCachedEps.supports_batch(self.vlm, T)
+        if not reuse_prefix:
+            return np.stack([one(b, reuse_prefix=False) for b in range(B)])
+        self.vlm.eval()
+        device = next(self.vlm.parameters()).device
+        pre = [self._preprocessed_image(im) for im in images]
+        ids_rows = [ids.reshape(-1).tolist() for ids in ids_rows]             # the prompt tail per row: infer.plan_batch (:640-645)
+        img = torch.cat([self._image_batch(im, device) for im in pre], dim=0)
+        pcs = [self._pointcloud_batch(pc, device) for pc in pointclouds]
+        pc = None if any(p is None for p in pcs) else torch.cat(pcs, dim=0)
+        proprio = torch.cat([self._proprio_token(st, unnorm_key, device) for st in cur_robot_states], dim=0)
+        draws = []
+        for b in range(B):                                                   # the RNG draws of B calls, in their order (:707-708)
+            draws.append(torch.randn(1, T, action_dim, device=device) if noise is None else noise[b:b + 1].to(device))
+            _ = torch.randint(0, self.diffusion.num_timesteps, (T,), device=device)
+        x0 = torch.cat(draws, dim=0).float()
+        if use_ddim and num_ddim_steps is not None and self.ddim_diffusion is None:
+            self.create_ddim(ddim_step=num_ddim_steps)
+        out = []
+        for sub, eng in BatchedPrefixCachedEps.for_batch(self.vlm, ids_rows, T, images=img, point_cloud=pc, camera_name=camera_name,
+                                                         proprio=proprio):
+            xs = x0[sub.start:sub.stop].contiguous()
+            if use_ddim and num_ddim_steps is not None:
+                samples = self.ddim_diffusion.ddim_sample_loop(eng, xs.shape, xs, clip_denoised=False, model_kwargs={}, progress=False,
+                                                               device=device, eta=0.0)
+            else:
+                samples = self.diffusion.p_sample_loop(eng, xs.shape, xs, clip_denoised=False, model_kwargs={}, progress=False, device=device)
+            out.append(samples.float().cpu().numpy())
+        normalized = np.concatenate(out, axis=0)
         return self.unnormalize_actions(normalized, unnorm_key) if self.norm_stats is not None else normalized
