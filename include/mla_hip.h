@@ -141,7 +141,10 @@ int mla_layernorm_fwd(const void* x, const void* w, const void* b, void* y, int 
 int mla_rope_inplace(void* buf, const float* cos_t, const float* sin_t, long long tokens, int S, int nheads, int D, int ld,
                      int q_off, int k_off, int backward, mla_stream_t stream);
 
-/* ---- SwiGLU: LlamaMLP.forward modeling_llama.py:240; gu = [gate | up] per row */
+/* ---- SwiGLU: LlamaMLP.forward modeling_llama.py:240; gu = [gate | up] per row
+ * Limit: sigmoid(gate) comes from the hardware exponential and reciprocal (1 ulp each), and the reciprocal flushes a result below 2^-126
+ * to 0. For gate < -87.3 the outputs (act, dgu) are therefore exactly 0 where the exact values are of magnitude 87 x 2^-126 x up. The
+ * fused GEMM epilogues share the definition (common.h) and the limit. */
 int mla_swiglu_fwd(const void* gu, void* act, long long rows, int I, mla_stream_t stream);
 int mla_swiglu_bwd(const void* dact, const void* gu, void* dgu, void* act_out, long long rows, int I, mla_stream_t stream);
 /* ---- activations of the small heads: kind 0 GELU(erf) (MLPProjector util/nn_utils.py:21-34), 1 GELU(tanh) (timm Mlp in ActionEmbedder /
@@ -177,7 +180,9 @@ int mla_embedding_fwd(const long long* ids, const void* table, void* out, long l
 int mla_embedding_bwd(const long long* ids, const void* dy, float* grad, float* workspace, long long tokens, int H, int vocab,
                       mla_stream_t stream);
 
-/* ---- optimizer: AdamW (training/strategies/fsdp.py:257) over the local fp32 shard + bf16 compute copy; clip (:308-310) */
+/* ---- optimizer: AdamW (training/strategies/fsdp.py:257) over the local fp32 shard + bf16 compute copy; clip (:308-310)
+ * The bias corrections 1 - beta^step are formed in double on the host and cast once (as torch.optim.AdamW does); the element update is
+ * fp32 with p16 = bf16(p). grad_scale (device scalar or null) multiplies g before both moments. */
 int mla_adamw_step(float* p, const float* g, float* m, float* v, void* p16, long long n, float lr, float beta1, float beta2,
                    float eps, float weight_decay, int step, const float* grad_scale, mla_stream_t stream);
 /* the same update over a flat range laid out [weight-decayed | not decayed]: elements [0, n_decay) get weight_decay, the rest none --
@@ -307,7 +312,10 @@ int mla_gemm_suffix_bf16(const void* x, long long ldx, const void* W, long long 
                          int rows_per_batch, const int* slot, int cap_rows, const void* residual, long long ld_res, int M, int N, int K,
                          const float* rope_cos, const float* rope_sin, int rope_cols, mla_stream_t stream);
 
-/* ---- losses: CrossEntropyLoss modeling_llama.py:1258-1269; InfoNCE models/mla/fuser/contrastive.py:208-215 */
+/* ---- losses: CrossEntropyLoss modeling_llama.py:1258-1269; InfoNCE models/mla/fuser/contrastive.py:208-215
+ * mla_ce_fwd: lse[r] = logsumexp(logits[r, :ncols]), loss[r] = lse - logits[r, label] (0 for ignore_index or a label outside [0, ncols);
+ * labels == null: label = r). A logit of -inf is a masked column and adds nothing, on bf16 and fp32 rows alike (as F.cross_entropy);
+ * loss or lse may be null. */
 int mla_ce_fwd(const void* logits, int logits_fp32, long long ld, const long long* labels, float* loss, float* lse, int rows,
                int ncols, long long ignore_index, mla_stream_t stream);
 int mla_ce_bwd(const void* logits, int logits_fp32, long long ld, const long long* labels, const float* lse, const float* gscale,

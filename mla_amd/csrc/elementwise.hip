@@ -496,7 +496,14 @@ __device__ __forceinline__ float act_df(int kind, float x) {
       return 0.5f * (1.f + t) + 0.5f * x * (1.f - t * t) * 0.7978845608028654f * (1.f + 3.f * 0.044715f * x * x);
     }
     case 2: return x > 0.f ? 1.f : 0.f;
-    default: { const float s = mla_sigmoid(x); return s + x * s * (1.f - s); }
+    default: {
+      // s (1 + x (1 - s)) with true divisions by t = 1 + e^-x and the factor s applied last, as (...) / t: v_rcp_f32 flushes a
+      // sigmoid below 2^-126 (x < -87.3) to 0, which lost x s ~ 87 x 2^-126 of the derivative; the quotient itself stays a normal
+      // number down to x = -88.7 (tests/test_trunk_kernels_gpu.py)
+      const float t = 1.f + __expf(-x);
+      const float s = 1.f / t;
+      return (1.f + x * (1.f - s)) / t;
+    }
   }
 }
 __global__ __launch_bounds__(256) void act_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, long long n,
@@ -1043,7 +1050,9 @@ static int adamw_impl(float* p, const float* g, float* m, float* v, void* p16, l
                       float beta2, float eps, float weight_decay, int step, const float* grad_scale, hipStream_t stream) {
   MLA_CHECK_ARG(p && g && m && v && n >= 0 && step >= 1 && n_decay >= 0 && n_decay <= n, "mla_adamw_step: bad args");
   if (n == 0) return 0;
-  const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+  // formed in double and cast once: in fp32, 1 - beta2^step cancels at small step numbers (beta2 = 0.999, step 2: the correction was
+  // off by 112 x 2^-24, the update by half that -- tests/test_trunk_cases_host.py); torch.optim.AdamW and the host backend use double too
+  const float bc1 = (float)(1.0 - pow((double)beta1, step)), bc2 = (float)(1.0 - pow((double)beta2, step));
   // (the decay boundary must not cut a 16-B group: otherwise everything goes through the scalar kernel)
   const long long n4 = (AL16(p) && AL16(g) && AL16(m) && AL16(v) && (p16 == nullptr || ((uintptr_t)p16 & 7) == 0) && (n_decay & 3) == 0) ? n / 4 : 0;
   if (n4) {

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logit
   for (int j = j0 + threadIdx.x; j < ncols; j += 256) {
     const float x = ldf<T>(row + j);
     if (x > m) { s = s * __expf(m - x) + 1.f; m = x; }
-    else s += __expf(x - m);
+    else if (x != -INFINITY) s += __expf(x - m);    // a masked logit adds nothing (m may still be -inf: exp(-inf + inf) is NaN)
   }
   const float gm = block_max(m, scratch);
   const float contrib = (m == -INFINITY) ? 0.f : s * __expf(m - gm);
