@@ -286,6 +286,28 @@ int mla_attn_decode(const void* q, const void* k, const void* v, void* o, int B,
 int mla_gemm_skinny_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
                          int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre, const void* pre_w, float eps,
                          const float* rope_cos, const float* rope_sin, int rope_cols, mla_stream_t stream);
+/* ---- weight-only FP8 for the suffix projections (opt-in: MLA.predict_action_diff(suffix_weights="fp8")). Format: per row n of W [N, K],
+ *   amax[n] = max_k |W[n, k]|, scale[n] = amax[n] / 448.0f (1.0f when amax[n] == 0), q[n, k] = e4m3fn_rne(clamp(float(W[n, k]) / scale[n],
+ *   -448, 448)): OCP e4m3fn bytes (gfx950's format; NOT MI300's e4m3fnuz) and fp32 scales [N]. Both divisions are correctly rounded fp32
+ *   divisions, so (W.float() / scale[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn) on the CPU reproduces the bytes.
+ * mla_quant_fp8_rows: W [N, K] bf16 (row stride ldw elements) -> q [N, K] bytes (row stride ldq bytes) + scale [N]. K % 16 == 0, 16-B aligned
+ *   rows. One workgroup per row (row absmax, then encode), deterministic, no workspace, no atomics, no allocation. Non-finite input is NOT
+ *   supported (finite input never produces a NaN code: the clamp is in front of the conversion). Runs once per weight version.
+ * mla_gemv_w8 / mla_gemm_skinny_w8: mla_gemv_bf16 / mla_gemm_skinny_bf16 -- the same argument meaning, rows_per_batch / out_batch_stride
+ *   addressing, pre modes 0 / 1 / 2 (bit for bit the operand values of mla_rmsnorm_fwd / mla_swiglu_fwd), residual and q|k rotary epilogue
+ *   -- with W [N, K] e4m3fn bytes (ldw in elements = bytes, 16-B aligned rows) and w_scale [N] fp32. K % 16 == 0; M <= 8 with the bf16 x
+ *   rows in LDS (gemv) resp. 1 <= M <= 64 (skinny). Arithmetic: fp32 sum of x[m, k] * float(q[n, k]) over the UNSCALED codes (every e4m3
+ *   value is a bf16 value: decoding is exact), the finished sum times w_scale[n], then the residual add or the rotation, one bf16 rounding;
+ *   no scale touches a partial sum. Half the weight bytes of the bf16 forms per call: 16 weights per 16-B load, decoded in registers
+ *   (v_cvt_pk_f32_fp8 in the gemv, v_cvt_scalef32_pk_bf16_fp8 into the MFMA A fragments in the skinny form, whose k order inside a
+ *   64-wide step differs from the bf16 kernel's). Fixed-order sums, no atomics, graph-capturable. */
+int mla_quant_fp8_rows(const void* W, long long ldw, void* q, long long ldq, float* scale, int N, int K, mla_stream_t stream);
+int mla_gemv_w8(const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
+                long long out_batch_stride, int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre,
+                const void* pre_w, float eps, const float* rope_cos, const float* rope_sin, int rope_cols, mla_stream_t stream);
+int mla_gemm_skinny_w8(const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
+                       long long out_batch_stride, int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre,
+                       const void* pre_w, float eps, const float* rope_cos, const float* rope_sin, int rope_cols, mla_stream_t stream);
 /* mla_attn_chunk: mla_attn_decode's contract for 1 <= R <= 64 query rows and any S_kv >= R: online softmax over key tiles of 64 (LDS does
  *   not grow with S_kv), QK^T and PV on the MFMA pipe, P rounded to bf16 before P V like the flash kernel; the key tiles are shared out
  *   over 4 waves per (sample, head, 16 queries) and their softmax states merged in a fixed order (deterministic, graph-capturable). */

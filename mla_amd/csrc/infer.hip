@@ -13,6 +13,10 @@
 //   mla_gemm_suffix_bf16  plain-input projection for 1 <= M <= 256 rows of a batch of samples: the skinny kernel's fragments with 1 / 2 / 4
 //                      W tiles per workgroup, per-sample cache slots and rotary positions read from a device array.
 //   mla_attn_chunk_ragged  mla_attn_chunk with one key count per sample, read from a device array.
+//   mla_gemv_w8 / mla_gemm_skinny_w8  the first two projection contracts over weight-only FP8: W is [N, K] OCP e4m3fn bytes with one fp32
+//                      scale per row (mla_quant_fp8_rows writes both); same kernels, W8 = true: half the bytes per weight, decoded in
+//                      registers (v_cvt_pk_f32_fp8 / v_cvt_scalef32_pk_bf16_fp8), fp32 sum over the UNSCALED codes, one multiply by the
+//                      row scale behind the finished sum.
 // infer.py keeps gemv / decode for every shape they accept and uses the other two beyond (action chunks of 8..63 steps); the last two
 // serve batched sampling (B observations with prompts of different lengths on one pass).
 // All are HBM-bound by construction: algorithmic bytes = the weight matrix (gemv) / the K and V rows of the head (decode).
@@ -49,10 +53,72 @@ __device__ __forceinline__ u32x4_t pack8f(const float* f) {
   for (int j = 0; j < 4; ++j) v[j] = pack2bf(f[2 * j], f[2 * j + 1]);
   return v;
 }
-template <int M, int PRE>
-__global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x, long long ldx, const bf16_t* __restrict__ W, long long ldw,
-                                                   bf16_t* __restrict__ out, long long ldo, long long out_bs, int rpb,
-                                                   const bf16_t* __restrict__ res, long long ld_res, int N, int K,
+// W8: the weight operand is OCP e4m3fn (one byte per element, ldw in elements = bytes) with one fp32 scale per W row. Every e4m3 value is
+// a bf16 value, so decoding loses nothing; the scale multiplies the FINISHED fp32 sum (never a partial one), in front of the residual add /
+// the rotation and the one bf16 rounding. 16 B per lane and load as in the bf16 form = 16 weights instead of 8: K % 16 == 0.
+template <bool W8> struct welem { typedef bf16_t t; };
+template <> struct welem<true> { typedef uint8_t t; };
+// the 4 codes of one 32-bit word -> floats (v_cvt_pk_f32_fp8: bytes 0, 1 / bytes 2, 3)
+__device__ __forceinline__ void fp8x4_to_f32(const uint32_t w, float* f) {
+  const mla_f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8(w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
+  f[0] = lo[0]; f[1] = lo[1]; f[2] = hi[0]; f[3] = hi[1];
+}
+// 8 codes (two words) -> one bf16 MFMA fragment, element order = byte order (v_cvt_scalef32_pk_bf16_fp8 at scale 1: exact)
+__device__ __forceinline__ u32x4_t fp8x8_to_bf16(const uint32_t w0, const uint32_t w1) {
+  u32x4_t v;
+  v[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false));
+  v[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true));
+  v[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false));
+  v[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true));
+  return v;
+}
+// The W8 form of gemv_kernel's K loop for one wave's GEMV_ROWS rows: a lane's 16 B are the codes of k = 16 c .. 16 c + 15, i.e. the x chunks
+// 2 c and 2 c + 1 of xs ([M][kc] chunks of 8 bf16); a K step is 64 lanes x 16 = 1024 weights. Same batching as the bf16 loop: the loads of
+// GEMV_UNR steps are issued before the first use.
+template <int M>
+__device__ __forceinline__ void gemv_w8_rows(const uint8_t* const* wr, const u32x4_t* xs, int kc, int lane, float (*acc)[M]) {
+  const int kc16 = kc >> 1;
+  for (int s0 = 0; s0 < ((kc16 + 63) >> 6); s0 += GEMV_UNR) {
+    u32x4_t w[GEMV_UNR][GEMV_ROWS];
+#pragma unroll
+    for (int u = 0; u < GEMV_UNR; ++u) {
+      const int c = (s0 + u) * 64 + lane;
+#pragma unroll
+      for (int r = 0; r < GEMV_ROWS; ++r)
+        w[u][r] = c < kc16 ? __builtin_nontemporal_load((const u32x4_t*)(wr[r] + c * 16)) : u32x4_t{0u, 0u, 0u, 0u};   // code 0 = +0
+    }
+#pragma unroll
+    for (int u = 0; u < GEMV_UNR; ++u) {
+      const int c = (s0 + u) * 64 + lane;
+      if ((s0 + u) * 64 < kc16) {                       // (wave-uniform: whole steps beyond K are skipped)
+        const int cc = c < kc16 ? c : kc16 - 1;          // lanes past the end read valid chunks against their zero weights
+        float wf[GEMV_ROWS][16];
+#pragma unroll
+        for (int r = 0; r < GEMV_ROWS; ++r)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) fp8x4_to_f32(w[u][r][j], &wf[r][4 * j]);
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const u32x4_t xv = xs[m * kc + 2 * cc + h];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const float xl = bflo(xv[j]), xh = bfhi(xv[j]);
+#pragma unroll
+              for (int r = 0; r < GEMV_ROWS; ++r)
+                acc[r][m] = fmaf(wf[r][8 * h + 2 * j + 1], xh, fmaf(wf[r][8 * h + 2 * j], xl, acc[r][m]));
+            }
+          }
+        }
+      }
+    }
+  }
+}
+template <int M, int PRE, bool W8>
+__global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x, long long ldx, const typename welem<W8>::t* __restrict__ W,
+                                                   long long ldw, const float* __restrict__ w_scale, bf16_t* __restrict__ out, long long ldo,
+                                                   long long out_bs, int rpb, const bf16_t* __restrict__ res, long long ld_res, int N, int K,
                                                    const bf16_t* __restrict__ pre_w, float eps, const float* __restrict__ rope_cos,
                                                    const float* __restrict__ rope_sin, int rope_cols) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -127,13 +193,15 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
     const int n0 = rot ? (set >> 6) * 128 + (set & 63) : set * GEMV_ROWS;
     const int nstep = rot ? 64 : 1;
     float acc[GEMV_ROWS][M];
-    const bf16_t* wr[GEMV_ROWS];
+    const typename welem<W8>::t* wr[GEMV_ROWS];
 #pragma unroll
     for (int r = 0; r < GEMV_ROWS; ++r) {
       wr[r] = W + (long long)(n0 + r * nstep < N ? n0 + r * nstep : N - 1) * ldw;
 #pragma unroll
       for (int m = 0; m < M; ++m) acc[r][m] = 0.f;
     }
+    if constexpr (W8) gemv_w8_rows<M>(wr, xs, kc, lane, acc);
+    else
     for (int s0 = 0; s0 < steps; s0 += GEMV_UNR) {
       u32x4_t w[GEMV_UNR][GEMV_ROWS];
 #pragma unroll
@@ -176,6 +244,10 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
             v = (rr == r && mm == m) ? acc[rr][mm] : v;
             partner = (rr != r && mm == m) ? acc[rr][mm] : partner;
           }
+        if constexpr (W8) {
+          v = __fmul_rn(v, w_scale[n0 + r * nstep]);
+          if (rot) partner = __fmul_rn(partner, w_scale[n0 + (1 - r) * nstep]);
+        }
         if (res) v += bf2f(res[(long long)m * ld_res + n0 + r * nstep]);
         if (rot) {
           // the arithmetic of rope_kernel (elementwise.hip) on the bf16-rounded projection: a' = a cos - b sin, b' = b cos + a sin
@@ -338,9 +410,14 @@ __global__ __launch_bounds__(64 * DEC_NW) void attn_decode_kernel(const bf16_t* 
 constexpr int SK_MMAX = 64;
 constexpr int SK_NW = 8;
 __device__ __forceinline__ bf16x8_t as_frag(const u32x4_t v) { return __builtin_bit_cast(bf16x8_t, v); }
-template <int MB, int PRE>
-__global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* __restrict__ x, long long ldx, const bf16_t* __restrict__ W,
-                                                                 long long ldw, bf16_t* __restrict__ out, long long ldo, long long out_bs, int rpb,
+// W8 (e4m3fn weights, see gemv_kernel): a lane's 16-B load is 16 codes, k = 64 s + 16 (l >> 4) .. + 15 of a 64-wide step, decoded to bf16 into
+// the A fragments of TWO MFMAs (codes 0-7, then 8-15); the B fragments are the x elements of the same k, so the k order inside a step is a
+// permutation of the bf16 form's -- the sum is the same set of products. The conversions do not depend on M. K % 16 == 0: a lane's chunk is
+// inside K or beyond it as a whole.
+template <int MB, int PRE, bool W8>
+__global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* __restrict__ x, long long ldx, const typename welem<W8>::t* __restrict__ W,
+                                                                 long long ldw, const float* __restrict__ w_scale, bf16_t* __restrict__ out,
+                                                                 long long ldo, long long out_bs, int rpb,
                                                                  const bf16_t* __restrict__ res, long long ld_res, int M, int N, int K,
                                                                  const bf16_t* __restrict__ pre_w, float eps, const float* __restrict__ rope_cos,
                                                                  const float* __restrict__ rope_sin, int rope_cols) {
@@ -391,7 +468,7 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* _
   const int tile = blockIdx.x;
   const bool rot = rope_cos != nullptr && tile * 16 < rope_cols;
   const int nrow = rot ? (tile >> 3) * 128 + ((li & 8) ? 64 : 0) + (tile & 7) * 8 + (li & 7) : tile * 16 + li;
-  const bf16_t* wr = W + (long long)(nrow < N ? nrow : N - 1) * ldw;
+  const typename welem<W8>::t* wr = W + (long long)(nrow < N ? nrow : N - 1) * ldw;
   const bf16_t* xr[MB];
   bool xok[MB];
   float xrs[MB];
@@ -402,12 +479,73 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* _
     xr[mb] = x + (long long)(xok[mb] ? m : 0) * ldx;
     xrs[mb] = (PRE == 1 && xok[mb]) ? rstd[m] : 0.f;
   }
-  const int steps = (K + 31) >> 5, spw = (steps + SK_NW - 1) / SK_NW;
+  const int steps = W8 ? (K + 63) >> 6 : (K + 31) >> 5, spw = (steps + SK_NW - 1) / SK_NW;
   const int s_beg = wave * spw, s_end = s_beg + spw < steps ? s_beg + spw : steps;
   f32x4_t acc[MB];
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb) acc[mb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   const u32x4_t zero = {0u, 0u, 0u, 0u};
+  if constexpr (W8) {
+    // the W loads of UW steps are issued first (the bytes in flight per lane of the bf16 form at MB <= 2), the x / norm-weight loads
+    // (L2 hits, twice as many per W load as in the bf16 form) in rounds of UX steps behind them
+    constexpr int UW = 8, UX = NB <= 1 ? 8 : (NB <= 2 ? 4 : (NB <= 4 ? 2 : 1));
+    for (int s0 = s_beg; s0 < s_end; s0 += UW) {
+      u32x4_t a[UW];
+#pragma unroll
+      for (int u = 0; u < UW; ++u) {
+        const int k = (s0 + u) * 64 + g * 16;
+        a[u] = (s0 + u < s_end && k < K) ? __builtin_nontemporal_load((const u32x4_t*)(wr + k)) : zero;   // code 0 = +0
+      }
+#pragma unroll
+      for (int u0 = 0; u0 < UW; u0 += UX) {
+        u32x4_t b[UX][2][NB], nw[UX][2];
+#pragma unroll
+        for (int u = 0; u < UX; ++u) {
+          const int k = (s0 + u0 + u) * 64 + g * 16;
+          const bool ok = s0 + u0 + u < s_end && k < K;
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb) {
+              b[u][h][mb] = ok && xok[mb] ? *(const u32x4_t*)(xr[mb] + k + 8 * h) : zero;
+              if (PRE == 2) b[u][h][MB + mb] = ok && xok[mb] ? *(const u32x4_t*)(xr[mb] + K + k + 8 * h) : zero;
+            }
+            if (PRE == 1) nw[u][h] = ok ? *(const u32x4_t*)(pre_w + k + 8 * h) : zero;
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < UX; ++u) {
+          if (s0 + u0 + u < s_end) {                                   // wave-uniform
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              const u32x4_t af = fp8x8_to_bf16(a[u0 + u][2 * h], a[u0 + u][2 * h + 1]);
+              float wv[8];
+              if (PRE == 1) unpack8f(nw[u][h], wv);
+#pragma unroll
+              for (int mb = 0; mb < MB; ++mb) {
+                u32x4_t bv = b[u][h][mb];
+                if (PRE == 1) {
+                  float f[8], o[8];
+                  unpack8f(bv, f);
+#pragma unroll
+                  for (int j = 0; j < 8; ++j) o[j] = wv[j] * bf2f(f2bf(f[j] * xrs[mb]));
+                  bv = pack8f(o);
+                } else if (PRE == 2) {
+                  float gg[8], uu[8], o[8];
+                  unpack8f(bv, gg);
+                  unpack8f(b[u][h][MB + mb], uu);
+#pragma unroll
+                  for (int j = 0; j < 8; ++j) o[j] = swiglu_fwd_elem(gg[j], uu[j]);
+                  bv = pack8f(o);
+                }
+                acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(af), as_frag(bv), acc[mb], 0, 0, 0);
+              }
+            }
+          }
+        }
+      }
+    }
+  } else
   for (int s0 = s_beg; s0 < s_end; s0 += U) {
     u32x4_t a[U], b[U][NB], nw[U];
 #pragma unroll
@@ -463,11 +601,13 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* _
     float v = 0.f, partner = 0.f;
 #pragma unroll
     for (int w = 0; w < SK_NW; ++w) v += lds[((w * MB + mb) * 4 + (i & 3)) * 64 + (i >> 2) * 16 + col];
+    if constexpr (W8) v = __fmul_rn(v, w_scale[n]);
     if (res) v += bf2f(res[(long long)m * ld_res + n]);
     if (rot) {
       const int ip = i ^ 8;
 #pragma unroll
       for (int w = 0; w < SK_NW; ++w) partner += lds[((w * MB + mb) * 4 + (ip & 3)) * 64 + (ip >> 2) * 16 + col];
+      if constexpr (W8) partner = __fmul_rn(partner, w_scale[n ^ 64]);  // the rotation partner's row: d <-> d + 64 of the same head
       // gemv_kernel's epilogue: rope_kernel's arithmetic on the bf16-rounded projection
       const int d = n & 63, pos = m % rpb;
       const float c = rope_cos[pos * 64 + d], sn = rope_sin[pos * 64 + d];
@@ -737,21 +877,76 @@ __global__ __launch_bounds__(64 * CH_NW) void attn_chunk_kernel(const bf16_t* __
   }
 }
 
+// ---- weight quantiser for the W8 projections: one workgroup per row of W [N, K] bf16.
+//   amax = max_k |W[n, k]|;  scale[n] = amax / 448 (1 when the row is all zero);  q[n, k] = e4m3fn_rne(clamp(W[n, k] / scale[n], -448, 448))
+// Both divisions are IEEE fp32 divisions (__fdiv_rn: no v_rcp, no multiply by a reciprocal), so that
+// (W.float() / scale[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn) on the CPU gives the same bytes. The clamp is in front of the
+// conversion: v_cvt_pk_fp8_f32 never sees a value beyond 448, so no NaN code can come out of finite input. Non-finite input is not
+// supported. Two passes over the row (the second one hits L2); fixed-order max, no atomics, no workspace.
+__global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16_t* __restrict__ W, long long ldw, uint8_t* __restrict__ q, long long ldq,
+                                                             float* __restrict__ scale, int K) {
+  __shared__ float scratch[16];
+  const bf16_t* wr = W + (long long)blockIdx.x * ldw;
+  uint8_t* qr = q + (long long)blockIdx.x * ldq;
+  const int kc16 = K >> 4;
+  float amax = 0.f;
+  for (int c = threadIdx.x; c < kc16; c += 256) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      float f[8];
+      unpack8f(*(const u32x4_t*)(wr + c * 16 + h * 8), f);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(f[j]));
+    }
+  }
+  amax = block_max(amax, scratch);
+  const float s = amax == 0.f ? 1.0f : __fdiv_rn(amax, 448.0f);
+  if (threadIdx.x == 0) scale[blockIdx.x] = s;
+  for (int c = threadIdx.x; c < kc16; c += 256) {
+    u32x4_t o;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      float f[8];
+      unpack8f(*(const u32x4_t*)(wr + c * 16 + h * 8), f);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f[j] = fminf(fmaxf(__fdiv_rn(f[j], s), -448.0f), 448.0f);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        int w = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * j], f[4 * j + 1], 0, false);
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * j + 2], f[4 * j + 3], w, true);
+        o[2 * h + j] = (uint32_t)w;
+      }
+    }
+    *(u32x4_t*)(qr + c * 16) = o;
+  }
+}
+
 }  // namespace
+
+// launch epilogue of the entry points that serve two exported names (MLA_LAUNCH_CHECK reports __func__)
+static int launch_status(const char* name) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return 0;
+  mla_set_error("%s: launch failed: %s", name, hipGetErrorString(e));
+  return (int)e;
+}
 
 #define AL16(p) ((((uintptr_t)(p)) & 15) == 0)
 
-extern "C" int mla_gemv_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
-                             int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre, const void* pre_w, float eps,
-                             const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
-  MLA_CHECK_ARG(x && W && out, "mla_gemv_bf16: null pointer");
+// mla_gemv_bf16 / mla_gemv_w8: one validation + launch path, W8 selects the weight format (ldw in elements of it)
+template <bool W8>
+static int gemv_entry(const char* name, const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
+                      long long out_batch_stride, int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre,
+                      const void* pre_w, float eps, const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
+  constexpr int KQ = W8 ? 16 : 8;                                         // weights per 16-B load
+  MLA_CHECK_ARG(x && W && out && (!W8 || w_scale), "%s: null pointer", name);
   MLA_CHECK_ARG((rope_cos == nullptr) == (rope_sin == nullptr) && (!rope_cos || (rope_cols > 0 && rope_cols % 128 == 0 && rope_cols <= N && !residual)),
-                "mla_gemv_bf16: the RoPE epilogue needs both tables, rope_cols a multiple of 128 and <= N, and no residual");
-  MLA_CHECK_ARG(pre >= 0 && pre <= 2 && (pre != 1 || (pre_w && AL16(pre_w))), "mla_gemv_bf16: pre must be 0, 1 (RMSNorm: 16-B aligned weight needed) or 2 (SwiGLU)");
-  MLA_CHECK_ARG(M >= 1 && M <= GEMV_MMAX && N >= 1 && K >= 8 && K % 8 == 0 && rows_per_batch >= 1, "mla_gemv_bf16: 1 <= M <= 8, K %% 8 == 0 required (M %d, N %d, K %d)", M, N, K);
-  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && ldw % 8 == 0, "mla_gemv_bf16: x / W rows must be 16-B aligned");
+                "%s: the RoPE epilogue needs both tables, rope_cols a multiple of 128 and <= N, and no residual", name);
+  MLA_CHECK_ARG(pre >= 0 && pre <= 2 && (pre != 1 || (pre_w && AL16(pre_w))), "%s: pre must be 0, 1 (RMSNorm: 16-B aligned weight needed) or 2 (SwiGLU)", name);
+  MLA_CHECK_ARG(M >= 1 && M <= GEMV_MMAX && N >= 1 && K >= KQ && K % KQ == 0 && rows_per_batch >= 1, "%s: 1 <= M <= 8, K %% %d == 0 required (M %d, N %d, K %d)", name, KQ, M, N, K);
+  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && ldw % KQ == 0, "%s: x / W rows must be 16-B aligned", name);
   const size_t lds = (size_t)M * K * 2 + 64;
-  MLA_CHECK_ARG(lds <= 160 * 1024, "mla_gemv_bf16: M x K x 2 bytes of input rows (+ 64) must fit the 160 KiB of LDS (M %d, K %d)", M, K);
+  MLA_CHECK_ARG(lds <= 160 * 1024, "%s: M x K x 2 bytes of input rows (+ 64) must fit the 160 KiB of LDS (M %d, K %d)", name, M, K);
   static int cus = 0;
   if (!cus) { hipDeviceProp_t p; int d = 0; (void)hipGetDevice(&d); cus = (hipGetDeviceProperties(&p, d) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256; }
   const int sets = (N + GEMV_ROWS - 1) / GEMV_ROWS;
@@ -763,10 +958,10 @@ extern "C" int mla_gemv_bf16(const void* x, long long ldx, const void* W, long l
 #define MLA_GEMV_LAUNCH(MM, PP)                                                                                                        \
   {                                                                                                                                    \
     static bool attr = false;                                                                                                          \
-    if (!attr) { (void)hipFuncSetAttribute((const void*)gemv_kernel<MM, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-    hipLaunchKernelGGL((gemv_kernel<MM, PP>), dim3(blocks), dim3(256), lds, stream, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw, (bf16_t*)out, ldo, \
-                       out_batch_stride, rows_per_batch, (const bf16_t*)residual, ld_res, N, K, (const bf16_t*)pre_w, eps, rope_cos, rope_sin, \
-                       rope_cos ? rope_cols : 0);                                                                                      \
+    if (!attr) { (void)hipFuncSetAttribute((const void*)gemv_kernel<MM, PP, W8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
+    hipLaunchKernelGGL((gemv_kernel<MM, PP, W8>), dim3(blocks), dim3(256), lds, stream, (const bf16_t*)x, ldx, (const typename welem<W8>::t*)W, ldw, \
+                       w_scale, (bf16_t*)out, ldo, out_batch_stride, rows_per_batch, (const bf16_t*)residual, ld_res, N, K, (const bf16_t*)pre_w, eps, \
+                       rope_cos, rope_sin, rope_cos ? rope_cols : 0);                                                                  \
   }
 #define MLA_GEMV_CASE(MM)                                                                                                              \
   case MM:                                                                                                                             \
@@ -777,7 +972,21 @@ extern "C" int mla_gemv_bf16(const void* x, long long ldx, const void* W, long l
   }
 #undef MLA_GEMV_CASE
 #undef MLA_GEMV_LAUNCH
-  MLA_LAUNCH_CHECK();
+  return launch_status(name);
+}
+
+extern "C" int mla_gemv_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
+                             int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre, const void* pre_w, float eps,
+                             const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
+  return gemv_entry<false>("mla_gemv_bf16", x, ldx, W, ldw, nullptr, out, ldo, out_batch_stride, rows_per_batch, residual, ld_res, M, N, K, pre, pre_w,
+                           eps, rope_cos, rope_sin, rope_cols, stream);
+}
+
+extern "C" int mla_gemv_w8(const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
+                           long long out_batch_stride, int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre,
+                           const void* pre_w, float eps, const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
+  return gemv_entry<true>("mla_gemv_w8", x, ldx, W, ldw, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual, ld_res, M, N, K, pre, pre_w,
+                          eps, rope_cos, rope_sin, rope_cols, stream);
 }
 
 extern "C" int mla_attn_decode(const void* q, const void* k, const void* v, void* o, int B, int H, int head_dim, int S_kv, int R, long long ld,
@@ -795,22 +1004,25 @@ extern "C" int mla_attn_decode(const void* q, const void* k, const void* v, void
   MLA_LAUNCH_CHECK();
 }
 
-extern "C" int mla_gemm_skinny_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
-                                    int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre, const void* pre_w,
-                                    float eps, const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
-  MLA_CHECK_ARG(x && W && out, "mla_gemm_skinny_bf16: null pointer");
+// mla_gemm_skinny_bf16 / mla_gemm_skinny_w8: one validation + launch path, W8 selects the weight format
+template <bool W8>
+static int skinny_entry(const char* name, const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
+                        long long out_batch_stride, int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre,
+                        const void* pre_w, float eps, const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
+  constexpr int KQ = W8 ? 16 : 8;
+  MLA_CHECK_ARG(x && W && out && (!W8 || w_scale), "%s: null pointer", name);
   MLA_CHECK_ARG((rope_cos == nullptr) == (rope_sin == nullptr) && (!rope_cos || (rope_cols > 0 && rope_cols % 128 == 0 && rope_cols <= N && !residual)),
-                "mla_gemm_skinny_bf16: the RoPE epilogue needs both tables, rope_cols a multiple of 128 and <= N, and no residual");
+                "%s: the RoPE epilogue needs both tables, rope_cols a multiple of 128 and <= N, and no residual", name);
   MLA_CHECK_ARG(pre >= 0 && pre <= 2 && (pre != 1 || (pre_w && AL16(pre_w))),
-                "mla_gemm_skinny_bf16: pre must be 0, 1 (RMSNorm: 16-B aligned weight needed) or 2 (SwiGLU)");
-  MLA_CHECK_ARG(M >= 1 && M <= SK_MMAX && N >= 1 && K >= 8 && K % 8 == 0 && rows_per_batch >= 1,
-                "mla_gemm_skinny_bf16: 1 <= M <= 64, K %% 8 == 0 required (M %d, N %d, K %d)", M, N, K);
-  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && ldw % 8 == 0, "mla_gemm_skinny_bf16: x / W rows must be 16-B aligned");
+                "%s: pre must be 0, 1 (RMSNorm: 16-B aligned weight needed) or 2 (SwiGLU)", name);
+  MLA_CHECK_ARG(M >= 1 && M <= SK_MMAX && N >= 1 && K >= KQ && K % KQ == 0 && rows_per_batch >= 1,
+                "%s: 1 <= M <= 64, K %% %d == 0 required (M %d, N %d, K %d)", name, KQ, M, N, K);
+  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && ldw % KQ == 0, "%s: x / W rows must be 16-B aligned", name);
   const int tiles = (N + 15) / 16;
 #define MLA_SK_LAUNCH(MB, PP)                                                                                                          \
-  hipLaunchKernelGGL((gemm_skinny_kernel<MB, PP>), dim3(tiles), dim3(64 * SK_NW), 0, stream, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw,     \
-                     (bf16_t*)out, ldo, out_batch_stride, rows_per_batch, (const bf16_t*)residual, ld_res, M, N, K, (const bf16_t*)pre_w, eps, \
-                     rope_cos, rope_sin, rope_cos ? rope_cols : 0)
+  hipLaunchKernelGGL((gemm_skinny_kernel<MB, PP, W8>), dim3(tiles), dim3(64 * SK_NW), 0, stream, (const bf16_t*)x, ldx,                 \
+                     (const typename welem<W8>::t*)W, ldw, w_scale, (bf16_t*)out, ldo, out_batch_stride, rows_per_batch,                \
+                     (const bf16_t*)residual, ld_res, M, N, K, (const bf16_t*)pre_w, eps, rope_cos, rope_sin, rope_cos ? rope_cols : 0)
 #define MLA_SK_CASE(MB)                                                                                                                \
   case MB:                                                                                                                             \
     if (pre == 0) MLA_SK_LAUNCH(MB, 0); else if (pre == 1) MLA_SK_LAUNCH(MB, 1); else MLA_SK_LAUNCH(MB, 2);                              \
@@ -818,6 +1030,30 @@ extern "C" int mla_gemm_skinny_bf16(const void* x, long long ldx, const void* W,
   switch ((M + 15) / 16) { MLA_SK_CASE(1) MLA_SK_CASE(2) MLA_SK_CASE(3) MLA_SK_CASE(4) }
 #undef MLA_SK_CASE
 #undef MLA_SK_LAUNCH
+  return launch_status(name);
+}
+
+extern "C" int mla_gemm_skinny_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
+                                    int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre, const void* pre_w,
+                                    float eps, const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
+  return skinny_entry<false>("mla_gemm_skinny_bf16", x, ldx, W, ldw, nullptr, out, ldo, out_batch_stride, rows_per_batch, residual, ld_res, M, N, K,
+                             pre, pre_w, eps, rope_cos, rope_sin, rope_cols, stream);
+}
+
+extern "C" int mla_gemm_skinny_w8(const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
+                                  long long out_batch_stride, int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K,
+                                  int pre, const void* pre_w, float eps, const float* rope_cos, const float* rope_sin, int rope_cols,
+                                  hipStream_t stream) {
+  return skinny_entry<true>("mla_gemm_skinny_w8", x, ldx, W, ldw, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual, ld_res, M, N, K,
+                            pre, pre_w, eps, rope_cos, rope_sin, rope_cols, stream);
+}
+
+// W [N, K] bf16 (ldw) -> q [N, K] e4m3fn codes (ldq, bytes) + scale [N] fp32; see quant_fp8_rows_kernel
+extern "C" int mla_quant_fp8_rows(const void* W, long long ldw, void* q, long long ldq, float* scale, int N, int K, hipStream_t stream) {
+  MLA_CHECK_ARG(W && q && scale, "mla_quant_fp8_rows: null pointer");
+  MLA_CHECK_ARG(N >= 1 && K >= 16 && K % 16 == 0, "mla_quant_fp8_rows: N >= 1, K %% 16 == 0 required (N %d, K %d)", N, K);
+  MLA_CHECK_ARG(AL16(W) && AL16(q) && ldw % 8 == 0 && ldq % 16 == 0 && ldw >= K && ldq >= K, "mla_quant_fp8_rows: W / q rows must be 16-B aligned and hold K elements");
+  hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3(N), dim3(256), 0, stream, (const bf16_t*)W, ldw, (uint8_t*)q, ldq, scale, K);
   MLA_LAUNCH_CHECK();
 }
 

@@ -37,6 +37,11 @@ _SIGNATURES = {
                         c_void_p],
     "mla_gemm_skinny_bf16": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_longlong, c_int,
                              c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
+    "mla_quant_fp8_rows": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_int, c_int, c_void_p],
+    "mla_gemv_w8": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_longlong, c_int,
+                    c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
+    "mla_gemm_skinny_w8": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_longlong,
+                           c_int, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
     "mla_attn_chunk": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_float,
                        c_void_p],
     "mla_attn_chunk_ragged": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_longlong, c_longlong,
@@ -797,9 +802,15 @@ def attn_bwd(q, k, v, o, dout, lse, seqlens, dq, dk, dv, B, S, H, D, ld_qkv, sca
 
 
 # --------------------------------------------------------------------------------------------- inference (mla_amd/infer.py)
-def _skinny_call(name, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope):
+def _skinny_call(name, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope, w_scale=None):
+    """The shared call of the four suffix projections; w_scale (fp32 [N]) selects the `_w8` argument list (W: float8_e4m3fn)."""
     _req(x, torch.bfloat16, f"{name} x")
-    _req(W, torch.bfloat16, f"{name} W")
+    _req(W, torch.bfloat16 if w_scale is None else torch.float8_e4m3fn, f"{name} W")
+    scale_arg = ()
+    if w_scale is not None:
+        _req(w_scale, torch.float32, f"{name} w_scale")
+        assert w_scale.numel() == W.shape[0] and w_scale.is_contiguous()
+        scale_arg = (_p(w_scale),)
     _req(out, torch.bfloat16, f"{name} out")
     M = x.shape[0]
     K = x.shape[1] // 2 if swiglu else x.shape[1]
@@ -817,7 +828,7 @@ def _skinny_call(name, x, W, out, ldo, out_batch_stride, rows_per_batch, residua
     if residual is not None:
         _req(residual, torch.bfloat16, f"{name} residual")
         assert residual.shape[0] == M and residual.stride(1) == 1
-    call(name, _p(x), x.stride(0), _p(W), W.stride(0), c_void_p(out.data_ptr() + 2 * out_col), ldo, out_batch_stride, rows_per_batch,
+    call(name, _p(x), x.stride(0), _p(W), W.stride(0), *scale_arg, c_void_p(out.data_ptr() + 2 * out_col), ldo, out_batch_stride, rows_per_batch,
          _p(residual), residual.stride(0) if residual is not None else 0, M, N, K, pre, _p(norm_weight), float(eps),
          _p(rope[0]) if rope is not None else None, _p(rope[1]) if rope is not None else None, int(rope[2]) if rope is not None else 0)
 
@@ -842,6 +853,40 @@ def gemm_skinny(x, W, out, ldo, out_batch_stride, rows_per_batch, residual=None,
     """gemv's contract for 1 <= M <= 64 rows and any K (mla_gemm_skinny_bf16): every weight row read once, on the MFMA pipe, x never
     staged in LDS. Same arguments, output addressing, fused RMSNorm / SwiGLU inputs and RoPE epilogue as gemv."""
     _skinny_call("mla_gemm_skinny_bf16", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope)
+
+
+def quant_fp8_rows(W, q=None, scale=None):
+    """Per-row FP8 quantisation of W [N, K] bf16 (rows may be strided; K % 16 == 0) for the `_w8` projections (mla_quant_fp8_rows):
+    scale[n] = amax[n] / 448 (1 for an all-zero row), q = e4m3fn_rne(clamp(W / scale, -448, 448)); the CPU statement
+    (W.float() / scale[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn) gives the same bytes. Returns (q [N, K] float8_e4m3fn,
+    scale [N] fp32); q / scale may be given (views of a packed buffer). Non-finite input is not supported."""
+    _req(W, torch.bfloat16, "quant_fp8_rows W")
+    N, K = W.shape
+    assert W.stride(1) == 1
+    if q is None:
+        q = torch.empty((N, K), dtype=torch.float8_e4m3fn, device=W.device)
+    if scale is None:
+        scale = torch.empty(N, dtype=torch.float32, device=W.device)
+    _req(q, torch.float8_e4m3fn, "quant_fp8_rows q")
+    _req(scale, torch.float32, "quant_fp8_rows scale")
+    assert q.shape == (N, K) and q.stride(1) == 1 and scale.numel() == N and scale.is_contiguous()
+    call("mla_quant_fp8_rows", _p(W), W.stride(0), _p(q), q.stride(0), _p(scale), N, K)
+    return q, scale
+
+
+def gemv_w8(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, norm_weight=None, eps=0.0, swiglu=False,
+            rope=None):
+    """gemv over FP8 weights (mla_gemv_w8): W [N, K] float8_e4m3fn, w_scale [N] fp32 as quant_fp8_rows writes them; out row m =
+    w_scale * (f(x[m]) @ float(W)^T) (+ residual[m]), the scale applied to the finished fp32 sum. K % 16 == 0; everything else is gemv's."""
+    _skinny_call("mla_gemv_w8", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope, w_scale)
+
+
+def gemm_skinny_w8(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, norm_weight=None, eps=0.0,
+                   swiglu=False, rope=None):
+    """gemv_w8's contract for 1 <= M <= 64 rows and any K % 16 == 0 (mla_gemm_skinny_w8): the codes are decoded to bf16 into the MFMA
+    operands."""
+    _skinny_call("mla_gemm_skinny_w8", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope,
+                 w_scale)
 
 
 def attn_decode(cache, B, nheads, D, S_kv, R, scale):

@@ -14,12 +14,16 @@ or `mla_attn_chunk` (up to 64) against the cached keys / values, the same RMSNor
 kernels' arithmetic as training (RMSNorm and SwiGLU are applied inside the projections' input staging). The 6 x 32 launches of a pass
 (5 with the rotary embedding in the QKV kernel's epilogue) are captured once into a HIP graph and replayed per DDIM step.
 
+Opt-in (`suffix_weights="fp8"`, see SUFFIX_WEIGHT_MODES): the sampler steps stream a per-row e4m3fn copy of the projections through
+`mla_gemv_w8` / `mla_gemm_skinny_w8` -- half the weight bytes per step; prefill, activations, cache and attention are untouched.
+
 Semantics vs the reference: identical arithmetic up to summation order (fp32 accumulation everywhere), with ONE stated difference -- the
 reference's point tokenizer draws fresh random FPS start indices inside every one of the 8 forwards (Point_PN.py:10); here they are
 drawn once per action chunk (the prefix is computed once). With given start indices (`fps_starts_override`, as in
 tests/test_inference_gpu.py) the two are the same function."""
 from __future__ import annotations
 
+import logging
 import math
 import os
 import warnings
@@ -30,13 +34,34 @@ import torch
 from . import hip, ops
 
 _USE_GRAPH = os.environ.get("MLA_INFER_GRAPH", "1") != "0"
+_LOG = logging.getLogger(__name__)
+
+# What the suffix pass streams (MLA.predict_action_diff(suffix_weights=...)); the prefill always runs the training kernels on the bf16 weights,
+# so the prefix keys / values keep bf16-weight precision:
+#   "bf16"         the decoder weights as they are (default)
+#   "fp8"          a per-row e4m3fn copy (hip.quant_fp8_rows) through mla_gemv_w8 / mla_gemm_skinny_w8: half the bytes per sampler step
+#   "fp8_as_bf16"  the bf16 kernels on bf16(q * scale): the reference of the "fp8" path, and what the format costs on a checkpoint
+SUFFIX_WEIGHT_MODES = ("bf16", "fp8", "fp8_as_bf16")
+
+
+def check_suffix_weights(mode):
+    if mode not in SUFFIX_WEIGHT_MODES:
+        raise ValueError(f"suffix_weights must be one of {SUFFIX_WEIGHT_MODES}, got {mode!r}")
+
+
+class W8(NamedTuple):
+    """A quantised projection weight: q [N, K] float8_e4m3fn codes, scale [N] fp32 (one per output channel)."""
+    q: torch.Tensor
+    scale: torch.Tensor
 
 
 class _CachedEpsBase:
     """What the cached-prefix engines share: the packed weights, the captured suffix pass and the `model(x, t)` call of the samplers.
     A subclass provides prefill() and _suffix_pass() and sets B, R, T, H, h_in, h_out, cache."""
 
-    def __init__(self, vlm, n_action_rows: int = 1):
+    def __init__(self, vlm, n_action_rows: int = 1, suffix_weights: str = "bf16"):
+        check_suffix_weights(suffix_weights)
+        self.suffix_weights = suffix_weights
         self.vlm = vlm
         llm = vlm.llm_backbone.llm
         self.model, self.cfg = llm.model, llm.config
@@ -49,6 +74,7 @@ class _CachedEpsBase:
         self.graph_error = None      # why the suffix pass could not be captured (eager launches then), for diagnostics
         self._packed = None          # per layer: the 9 weights with q|k|v and gate|up as views of ONE buffer each (see _weights)
         self._packed_key = None
+        self._suffix = None          # per layer: what the suffix pass streams -- _packed itself ("bf16") or a quantised copy (_quantised)
 
     def _weights(self):
         """Every layer's (ln1, wq, wk, wv, wo, ln2, wg, wu, wd) with q|k|v and gate|up adjacent in memory, so that the prefill runs the
@@ -74,7 +100,38 @@ class _CachedEpsBase:
         if self._packed is not shared["packed"]:
             self.graph = None            # a captured pass holds the previous buffers' addresses
             self._packed, self._packed_key = shared["packed"], key
+        suffix = self._packed if self.suffix_weights == "bf16" else self._quantised(key)
+        if self._suffix is not suffix:
+            self.graph = None
+            self._suffix = suffix
         return self._packed
+
+    def _quantised(self, key):
+        """The suffix pass's weights in the modes "fp8" / "fp8_as_bf16": per layer q|k|v, o, gate|up and down of the packed copy quantised
+        per output channel (hip.quant_fp8_rows; the scale is per row, so the packed matrices quantise as one), kept beside the packed copy:
+        one per model, shared by its engines, keyed like it on (data_ptr, _version) of the layer weights and rebuilt when that changes.
+        "fp8": per layer (ln1, W8 qkv, W8 o, ln2, W8 gate|up, W8 down). "fp8_as_bf16": the packed tuple's layout with bf16(q * scale) in
+        place of every projection (built from the same codes on first use)."""
+        shared = self.vlm.__dict__.setdefault("_prefix_fp8", {})
+        if shared.get("key") != key:
+            layers, nbytes = [], 0
+            with torch.no_grad(), torch.inference_mode(False):
+                for ln1, wq, wk, wv, wo, ln2, wg, wu, wd in self._packed:
+                    mats = [W8(*hip.quant_fp8_rows(m)) for m in (ops.cat_view((wq, wk, wv)), wo, ops.cat_view((wg, wu)), wd)]
+                    nbytes += sum(m.q.numel() + 4 * m.scale.numel() for m in mats)
+                    layers.append((ln1, mats[0], mats[1], ln2, mats[2], mats[3]))
+            shared.clear()
+            shared["key"], shared["fp8"] = key, layers
+            _LOG.info("suffix_weights: FP8 copy of the decoder projections, %.2f GB beside the bf16 weights", nbytes / 1e9)
+        if self.suffix_weights == "fp8_as_bf16" and "fp8_as_bf16" not in shared:
+            deq = []
+            with torch.no_grad(), torch.inference_mode(False):
+                for (ln1, qkv, o, ln2, gu, d), packed in zip(shared["fp8"], self._packed):
+                    qkv, o, gu, d = ((m.q.float() * m.scale[:, None]).to(torch.bfloat16) for m in (qkv, o, gu, d))
+                    nq, nk, ng = packed[1].shape[0], packed[2].shape[0], packed[6].shape[0]
+                    deq.append((ln1, qkv[:nq], qkv[nq:nq + nk], qkv[nq + nk:], o, ln2, gu[:ng], gu[ng:], d))
+            shared["fp8_as_bf16"] = deq
+        return shared[self.suffix_weights]
 
     def _run(self):
         if _USE_GRAPH and not self._graph_failed:
@@ -148,15 +205,18 @@ class PrefixCachedEps(_CachedEpsBase):
         return False
 
     @classmethod
-    def for_inputs(cls, vlm, input_ids, n_action_rows: int = 1, **model_kwargs):
+    def for_inputs(cls, vlm, input_ids, n_action_rows: int = 1, suffix_weights: str = "bf16", **model_kwargs):
+        check_suffix_weights(suffix_weights)
         k = cls._splice_position(input_ids)
         engines = vlm.__dict__.setdefault("_prefix_engines", {})
         key = (int(input_ids.shape[0]), k, int(n_action_rows), str(input_ids.device))
+        if suffix_weights != "bf16":
+            key += (suffix_weights,)                                          # a captured graph holds the addresses of ITS weights
         eng = engines.get(key)
         if eng is None:
             if len(engines) >= 4:                                             # a handful of prompt lengths per process; each engine holds 0.4 GB at 7B
                 engines.pop(next(iter(engines)))
-            eng = engines[key] = cls(vlm, n_action_rows)
+            eng = engines[key] = cls(vlm, n_action_rows, suffix_weights)
         eng.prefill(input_ids, k, **model_kwargs)
         return eng
 
@@ -194,6 +254,8 @@ class PrefixCachedEps(_CachedEpsBase):
         """f(x) [M, K] @ cat(weights)^T (+ residual) -> [M, sum N]; one launch when the weights are adjacent in memory.
         pre: norm_weight= / eps= (RMSNorm of the rows) or swiglu=True (x = packed gate|up rows), applied inside the kernel's input staging."""
         M = x.shape[0]
+        if isinstance(weights, W8):
+            return self._gemv_w8(x, weights, out, residual, rpb, out_bs, **pre)
         wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
         N = sum(w.shape[0] for w in weights)
         if out is None:
@@ -212,12 +274,46 @@ class PrefixCachedEps(_CachedEpsBase):
                 off += w.shape[0]
         return out
 
+    def _gemv_w8(self, x, w, out, residual, rpb, out_bs, **pre):
+        """_gemv over a quantised (always packed) weight: one launch. Kernel choice: the bf16 rule -- mla_gemv_w8 where the rows fit its LDS,
+        the MFMA form beyond. Measured at 7B (profiles/fp8_infer_latency.txt): right at M = 2; at M = 5 .. 8 the MFMA form
+        would be 2-7 % faster per layer, M = 3, 4 not measured -- the switch point is left here until they are."""
+        M = x.shape[0]
+        if out is None:
+            out = torch.empty((M, w.q.shape[0]), dtype=torch.bfloat16, device=x.device)
+            rpb, out_bs = M, 0
+        kern = hip.gemv_w8 if hip.gemv_fits(M, w.q.shape[1]) else hip.gemm_skinny_w8
+        kern(x, w.q, w.scale, out, out.stride(-2), out_bs, rpb, residual, **pre)
+        return out
+
+    def _suffix_pass_w8(self):
+        """_suffix_pass over the FP8 copy: the same five launches per layer, activations / cache / attention untouched."""
+        B, R, H, S_p, S_cap = self.B, self.R, self.H, self.S_p, self.S_cap
+        h = self.h_in
+        scale = 1.0 / math.sqrt(self.D)
+        attn = hip.attn_decode if hip.attn_decode_fits(R, S_cap) else hip.attn_chunk
+        fused = self.D == 128
+        for (ln1, qkv, wo, ln2, gu, wd), c in zip(self._suffix, self.cache):
+            self._gemv(h, qkv, out=c[:, S_p:], rpb=R, out_bs=c.stride(0), norm_weight=ln1, eps=self.eps,
+                       **({"rope": (self.cos_s, self.sin_s, 2 * H)} if fused else {}))
+            if not fused:
+                for b in range(B):
+                    hip.rope_inplace(c[b, S_p:], self.cos_s, self.sin_s, R, self.nheads, self.D, 0, H)
+            o = attn(c, B, self.nheads, self.D, S_cap, R, scale)
+            h1 = self._gemv(o, wo, residual=h)
+            g = self._gemv(h1, gu, norm_weight=ln2, eps=self.eps)
+            h = self._gemv(g, wd, residual=h1, swiglu=True)
+        hn, _ = hip.rmsnorm_fwd(h, self.model.norm.weight, self.eps)
+        self.h_out.copy_(hn)
+
     def _suffix_pass(self):
+        if self.suffix_weights == "fp8":
+            return self._suffix_pass_w8()
         B, R, H, S_p, S_cap = self.B, self.R, self.H, self.S_p, self.S_cap
         h = self.h_in
         scale = 1.0 / math.sqrt(self.D)
         attn = hip.attn_decode if hip.attn_decode_fits(R, S_cap) else hip.attn_chunk   # R x S_kv scores in LDS vs online softmax
-        for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd), c in zip(self._packed, self.cache):
+        for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd), c in zip(self._suffix, self.cache):
             # north_star's "fused RMSNorm + RoPE + QKV" as ONE kernel: RMSNorm inside the projection's input staging, the rotary embedding of
             # the q and k columns in its epilogue; the rows go straight into the cache slots [S_p, S_p + R) of every sample
             fused = ops.cat_view((wq, wk, wv)) is not None and self.D == 128

@@ -330,7 +330,8 @@ class MLA(nn.Module):
     def predict_action_diff(self, image=None, pointcloud=None, instruction: Optional[str] = None, cur_robot_state=None,
                             unnorm_key: Optional[str] = None, cfg_scale: float = 0.0, use_ddim: bool = True, num_ddim_steps: int = 8,
                             action_dim: int = 7, *, input_ids: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
-                            camera_name: str = "rlbench_front", reuse_prefix: bool = True, **kwargs) -> np.ndarray:
+                            camera_name: str = "rlbench_front", reuse_prefix: bool = True, suffix_weights: str = "bf16",
+                            **kwargs) -> np.ndarray:
         """model_mla.py:592-775: 8-step DDIM (eta = 0) over the action chunk with the VLM as the epsilon model, then
         un-normalisation.
         * ``image`` is a PIL image / uint8 HWC frame (pre-processed here like the reference does, :656-660) or an already
@@ -344,7 +345,13 @@ class MLA(nn.Module):
         FPS start indices drawn once per chunk instead of once per step); False = the reference's control flow, a whole forward per step.
         ``noise`` optionally fixes the initial sample (the reference draws it with torch.randn, :707). ``camera_name``: the shipped
         method does not forward it, so the reference's get_camera_params(None) raises (camera.py:54-56); it is an explicit
-        argument here (the evaluation scripts use the RLBench front camera)."""
+        argument here (the evaluation scripts use the RLBench front camera).
+        ``suffix_weights`` (opt-in, cached prefix only): "bf16" (default) | "fp8": the sampler steps stream a per-row e4m3fn copy of the
+        decoder weights (mla_gemv_w8 / mla_gemm_skinny_w8: half the bytes per step; the prefill keeps the bf16 weights) | "fp8_as_bf16":
+        the bf16 kernels on the dequantised copy -- what the format costs on a checkpoint, without the FP8 kernels. Anything but "bf16"
+        raises when the cached prefix is off or does not serve the shape: there is no silent bf16 fallback."""
+        from .infer import check_suffix_weights
+        check_suffix_weights(suffix_weights)
         self.vlm.eval()
         device = next(self.vlm.parameters()).device
         if input_ids is None:
@@ -363,8 +370,12 @@ class MLA(nn.Module):
         if reuse_prefix:
             from .infer import PrefixCachedEps
             reuse_prefix = PrefixCachedEps.supports(self.vlm, int(input_ids.shape[0]), self.future_action_window_size + 1)
+        if suffix_weights != "bf16" and not reuse_prefix:
+            raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached-prefix engine (reuse_prefix=True and a shape "
+                             "PrefixCachedEps.supports); the whole-forward sampler has bf16 weights only")
         if reuse_prefix:
-            eps_model = PrefixCachedEps.for_inputs(self.vlm, n_action_rows=self.future_action_window_size + 1, **model_kwargs)
+            eps_model = PrefixCachedEps.for_inputs(self.vlm, n_action_rows=self.future_action_window_size + 1,
+                                                   suffix_weights=suffix_weights, **model_kwargs)
         if use_ddim and num_ddim_steps is not None:
             if self.ddim_diffusion is None:
                 self.create_ddim(ddim_step=num_ddim_steps)
@@ -380,7 +391,7 @@ class MLA(nn.Module):
     def predict_action_diff_batch(self, images, pointclouds, instructions=None, cur_robot_states=None, unnorm_key: Optional[str] = None,
                                   cfg_scale: float = 0.0, use_ddim: bool = True, num_ddim_steps: int = 8, action_dim: int = 7, *,
                                   input_ids=None, noise: Optional[torch.Tensor] = None, camera_name: str = "rlbench_front",
-                                  reuse_prefix: bool = True) -> np.ndarray:
+                                  reuse_prefix: bool = True, suffix_weights: str = "bf16") -> np.ndarray:
         """B observations -> [B, T, action_dim]: by definition B independent `predict_action_diff` calls (the reference's
         `predict_action_batch`, model_mla.py:994, is dead code), computed on ONE cached prefix pass per DDIM step
         (mla_amd/infer.py:BatchedPrefixCachedEps): the prompts may have different lengths, the FPS start indices are drawn once per chunk.
@@ -389,7 +400,10 @@ class MLA(nn.Module):
         the attached tokenizer; ``noise``: [B, T, action_dim]. Every per-sample step (image pre-processing, mask channel, prompt tail,
         proprio normalisation, un-normalisation) is predict_action_diff's. B = 1 IS predict_action_diff; ``reuse_prefix=False`` loops the
         reference's control flow; more than 256 suffix rows are served as consecutive sub-batches; head_dim != 128 warns once and loops
-        over whole-forward batch-1 calls."""
+        over whole-forward batch-1 calls. ``suffix_weights``: predict_action_diff's, forwarded for B = 1; the batched engine has bf16
+        weights only, so B >= 2 with another mode raises NotImplementedError."""
+        from .infer import check_suffix_weights
+        check_suffix_weights(suffix_weights)
         B = len(images)
         T = self.future_action_window_size + 1
         if input_ids is None:
@@ -411,7 +425,10 @@ class MLA(nn.Module):
                                             action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b:b + 1],
                                             camera_name=camera_name, **kw)
         if B == 1:
-            return one(0, reuse_prefix=reuse_prefix)[None]
+            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights)[None]
+        if suffix_weights != "bf16":
+            raise NotImplementedError(f"suffix_weights={suffix_weights!r}: the batched engine (BatchedPrefixCachedEps, mla_gemm_suffix_bf16) "
+                                      "streams bf16 weights only; sample B >= 2 observations with \"bf16\" or one at a time")
         if reuse_prefix:
             from .infer import BatchedPrefixCachedEps
             reuse_prefix = BatchedPrefixCachedEps.supports_batch(self.vlm, T)

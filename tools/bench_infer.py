@@ -5,6 +5,12 @@
     python tools/bench_infer.py --batch B [--chunk C]     MLA.predict_action_diff_batch on B observations with ragged prompts (lengths
                                                           drawn from a fixed seed) AND, in the same process, B sequential
                                                           predict_action_diff calls on the same observations
+    python tools/bench_infer.py --suffix-weights fp8      the sampler steps stream the FP8 copy of the decoder weights (infer.py)
+    python tools/bench_infer.py --pair-fp8 [--pairs P] [--chunk C] [--kernel-table]
+                                                          bf16 and fp8 chunks alternating in one process (same box, same clocks): per-chunk
+                                                          latency and the suffix pass alone, per pair, with the 95 % interval of the pair
+                                                          differences; --kernel-table adds mla_gemv_w8 vs mla_gemm_skinny_w8 per 7B
+                                                          projection shape at M = 2, 5, 8, 17 (the engine's selection rule is set from it)
 Prints one JSON line (not the driver's bench contract -- that is bench.py)."""
 import argparse
 import json
@@ -24,9 +30,15 @@ def main():
     ap.add_argument("--chunk", type=int, default=1, help="future_action_window_size + 1")
     ap.add_argument("--no-reuse-prefix", action="store_true", help="the reference's control flow: a whole forward per DDIM step")
     ap.add_argument("--batch", type=int, default=0, help="B > 0: predict_action_diff_batch on B observations vs B sequential calls")
+    ap.add_argument("--suffix-weights", choices=["bf16", "fp8", "fp8_as_bf16"], default="bf16")
+    ap.add_argument("--pair-fp8", action="store_true", help="alternate bf16 and fp8 chunks in one process, in pairs")
+    ap.add_argument("--pairs", type=int, default=6)
+    ap.add_argument("--kernel-table", action="store_true", help="with --pair-fp8: the two _w8 kernels per projection shape and M")
     args = ap.parse_args()
     if args.batch > 0:
         return main_batch(args)
+    if args.pair_fp8:
+        return main_pair(args)
     from bench import build
     from mla_amd.synthetic import make_batch
     dev = torch.device("cuda", 0)
@@ -39,7 +51,7 @@ def main():
     b = make_batch(B=1, device=dev)
     ids = torch.cat([b["input_ids"][:, :-4], torch.tensor([[29871]], device=dev)], dim=1)   # prompt + the '▁' tag the splice looks for
     kw = dict(image=b["images"]["front_image"][0], pointcloud=b["point_cloud"][0], cur_robot_state=b["proprio"][0, 0].cpu().numpy(),
-              input_ids=ids, num_ddim_steps=args.steps, reuse_prefix=not args.no_reuse_prefix)
+              input_ids=ids, num_ddim_steps=args.steps, reuse_prefix=not args.no_reuse_prefix, suffix_weights=args.suffix_weights)
     m.predict_action_diff(**kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -55,7 +67,7 @@ def main():
                   proprio=b["proprio"][:1])
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         ev[0].record()
-        eng = PrefixCachedEps.for_inputs(m.vlm, n_action_rows=args.chunk, **mk)
+        eng = PrefixCachedEps.for_inputs(m.vlm, n_action_rows=args.chunk, suffix_weights=args.suffix_weights, **mk)
         ev[1].record()
         x = torch.randn(1, args.chunk, 7, device=dev)
         t = torch.tensor([91], device=dev)
@@ -65,14 +77,133 @@ def main():
             eng._run()
         ev[3].record()
         torch.cuda.synchronize()
+        wbytes = _stream_bytes(m, args.suffix_weights)
         parts = {"prefill_ms": round(ev[0].elapsed_time(ev[1]), 2), "one_eps_call_ms": round(ev[1].elapsed_time(ev[2]), 2),
                  "suffix_pass_graph_replay_ms": round(ev[2].elapsed_time(ev[3]) / 8, 3),
-                 "weights_streamed_per_pass_gb": round(sum(p.numel() for l in m.vlm.llm_backbone.llm.model.layers for p in l.parameters()) * 2 / 1e9, 2),
-                 "suffix_pass_weight_stream_tbps": round(sum(p.numel() for l in m.vlm.llm_backbone.llm.model.layers for p in l.parameters()) * 2 / 1e12 /
-                                                         (ev[2].elapsed_time(ev[3]) / 8 * 1e-3), 2)}
-    print(json.dumps({"metric": "predict_action_diff latency, MLA-Llama2-7B bf16, batch 1", "value": round(ms, 1), "unit": "ms",
+                 "weights_streamed_per_pass_gb": round(wbytes / 1e9, 2),
+                 "suffix_pass_weight_stream_tbps": round(wbytes / 1e12 / (ev[2].elapsed_time(ev[3]) / 8 * 1e-3), 2)}
+    print(json.dumps({"metric": "predict_action_diff latency, MLA-Llama2-7B bf16, batch 1", "suffix_weights": args.suffix_weights,
+                      "value": round(ms, 1), "unit": "ms",
                       "ddim_steps": args.steps, "ms_per_ddim_step": round(ms / args.steps, 1), "seq_len": int(ids.shape[1]) + 513 + 2 + args.chunk,
                       "action_chunk": args.chunk, "reuse_prefix": not args.no_reuse_prefix, **parts, "action": [round(float(v), 4) for v in act.reshape(-1)[:7]], "data": "synthetic"}))
+
+
+def _stream_bytes(m, mode):
+    """Bytes of decoder weights one suffix pass streams: every layer parameter in bf16, or one byte per weight in the "fp8" mode (the
+    per-row scales and the norm weights are noise next to it)."""
+    n = sum(p.numel() for l in m.vlm.llm_backbone.llm.model.layers for p in l.parameters())
+    return n * (1 if mode == "fp8" else 2)
+
+
+_T95 = {2: 12.71, 3: 4.30, 4: 3.18, 5: 2.78, 6: 2.57, 7: 2.45, 8: 2.36, 9: 2.31, 10: 2.26}      # two-sided Student t, n - 1 degrees of freedom
+
+
+def _pair_stats(a, b):
+    """a, b: the two arms' values per pair -> mean difference b - a and its 95 % interval."""
+    d = [y - x for x, y in zip(a, b)]
+    n = len(d)
+    mean = sum(d) / n
+    if n < 2:
+        return {"mean_diff": round(mean, 4), "ci95": None}
+    se = (sum((v - mean) ** 2 for v in d) / (n - 1)) ** 0.5 / n ** 0.5
+    h = _T95.get(n, 1.96) * se
+    return {"mean_diff": round(mean, 4), "ci95": [round(mean - h, 4), round(mean + h, 4)], "excludes_zero": bool(mean + h < 0 or mean - h > 0)}
+
+
+def main_pair(args):
+    from bench import build
+    from mla_amd import hip
+    from mla_amd.infer import PrefixCachedEps
+    from mla_amd.synthetic import make_batch
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    m = build(dev, 1)
+    m.future_action_window_size = m.vlm.future_action_window_size = args.chunk - 1
+    m.eval()
+    for p in m.parameters():
+        p.data = p.data.to(torch.bfloat16)
+    b = make_batch(B=1, device=dev)
+    ids = torch.cat([b["input_ids"][:, :-4], torch.tensor([[29871]], device=dev)], dim=1)
+    noise = torch.randn(1, args.chunk, 7, device=dev)
+    kw = dict(image=b["images"]["front_image"][0], pointcloud=b["point_cloud"][0], cur_robot_state=b["proprio"][0, 0].cpu().numpy(),
+              input_ids=ids, num_ddim_steps=args.steps, noise=noise)
+    mk = dict(input_ids=ids, images=b["images"]["front_image"][:1], point_cloud=b["point_cloud"][:1], camera_name="rlbench_front",
+              proprio=b["proprio"][:1])
+    modes = ("bf16", "fp8")
+    acts = {mode: m.predict_action_diff(suffix_weights=mode, **kw) for mode in modes}          # engines, graphs, packed + quantised weights
+    t91 = torch.tensor([91], device=dev)
+
+    def chunk_ms(mode):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.iters):
+            m.predict_action_diff(suffix_weights=mode, **kw)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.iters * 1e3
+
+    def pass_ms(mode):
+        with torch.inference_mode():
+            eng = PrefixCachedEps.for_inputs(m.vlm, n_action_rows=args.chunk, suffix_weights=mode, **mk)
+            eng(noise, t91)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(8):
+                eng._run()
+            e1.record()
+            torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / 8
+    chunk = {mode: [] for mode in modes}
+    suffix = {mode: [] for mode in modes}
+    for _ in range(args.pairs):                                             # bf16, fp8, bf16, fp8, ...: same box, interleaved
+        for mode in modes:
+            chunk[mode].append(chunk_ms(mode))
+        for mode in modes:
+            suffix[mode].append(pass_ms(mode))
+    out = {"metric": "predict_action_diff, MLA-Llama2-7B, batch 1: bf16 vs fp8 suffix weights in alternating pairs", "action_chunk": args.chunk,
+           "suffix_rows": args.chunk + 1, "ddim_steps": args.steps, "pairs": args.pairs, "unit": "ms",
+           "chunk_ms": {k: [round(v, 2) for v in vs] for k, vs in chunk.items()}, "chunk_fp8_minus_bf16": _pair_stats(chunk["bf16"], chunk["fp8"]),
+           "suffix_pass_ms": {k: [round(v, 3) for v in vs] for k, vs in suffix.items()},
+           "suffix_pass_fp8_minus_bf16": _pair_stats(suffix["bf16"], suffix["fp8"]),
+           "weights_streamed_per_pass_gb": {k: round(_stream_bytes(m, k) / 1e9, 2) for k in modes},
+           "suffix_pass_weight_stream_tbps": {k: round(_stream_bytes(m, k) / 1e12 / (min(suffix[k]) * 1e-3), 2) for k in modes},
+           "fp8_vs_bf16_chunk_rel_diff_random_weights": round(float(((acts["fp8"] - acts["bf16"]) ** 2).sum() ** 0.5 / (acts["bf16"] ** 2).sum() ** 0.5), 4),
+           "data": "synthetic"}
+    if args.kernel_table:
+        # the two _w8 kernels per projection shape of a 7B layer, cycling through the 32 layers' weights (1.6 GB: nothing stays in the caches)
+        layers = m.vlm.__dict__["_prefix_fp8"]["fp8"]
+        names = {1: "qkv(norm)", 2: "o(res)", 4: "gate_up(norm)", 5: "down(swiglu,res)"}
+        table = {}
+        for M in (2, 5, 8, 17):
+            row = {}
+            for idx, name in names.items():
+                N, K = layers[0][idx].q.shape
+                x = (torch.randn(M, 2 * K if idx == 5 else K, device=dev) * 0.5).to(torch.bfloat16)
+                res = torch.randn(M, N, device=dev).to(torch.bfloat16) if idx in (2, 5) else None
+                o = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
+                pre = {"norm_weight": layers[0][0], "eps": 1e-5} if idx in (1, 4) else ({"swiglu": True} if idx == 5 else {})
+                cell = {}
+                for kname, fn in (("gemv", hip.gemv_w8), ("skinny", hip.gemm_skinny_w8)):
+                    if kname == "gemv" and not hip.gemv_fits(M, K):
+                        continue
+                    for L in layers[:2]:                                    # function attributes, allocator
+                        fn(x, L[idx].q, L[idx].scale, o, N, 0, M, res, **pre)
+                    torch.cuda.synchronize()
+                    g = torch.cuda.CUDAGraph()                              # as the engine launches them: eager launches from Python
+                    with torch.cuda.graph(g):                               # are host-bound below ~15 us per kernel
+                        for L in layers:
+                            fn(x, L[idx].q, L[idx].scale, o, N, 0, M, res, **pre)
+                    g.replay()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(3):
+                        g.replay()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    cell[kname] = round(e0.elapsed_time(e1) / (3 * len(layers)) * 1e3, 1)
+                row[name] = cell
+            table[f"M{M}"] = row
+        out["w8_kernel_us_per_launch"] = table
+    print(json.dumps(out))
 
 
 def main_batch(args):
