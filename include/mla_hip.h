@@ -333,6 +333,24 @@ int mla_attn_chunk_ragged(const void* q, const void* k, const void* v, void* o, 
 int mla_gemm_suffix_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
                          int rows_per_batch, const int* slot, int cap_rows, const void* residual, long long ld_res, int M, int N, int K,
                          const float* rope_cos, const float* rope_sin, int rope_cols, mla_stream_t stream);
+/* ---- N action chunks for ONE observation (mla_amd/infer.py SampleGroupsEps): G groups of R suffix rows behind one shared prefix.
+ * mla_attn_chunk_groups: q / k / v point at the packed post-RoPE q|k|v cache of one sample, [S_p + G * R, 3 H] with row stride ld:
+ *   rows [0, S_p) are the prefix, row S_p + g * R + p is suffix row p of group g. Query (g, p) sees the logical keys j = 0 .. S_p + p,
+ *   where logical key j is memory row j (j < S_p) or j + g * R (j >= S_p): the prefix and, causally, the group's own rows. Output row
+ *   g * R + p of o (row stride ld_o), bf16. 1 <= R <= 64, G >= 1, S_p >= 0, head_dim 128, 16-B aligned rows. mla_attn_chunk's arithmetic
+ *   over the logical key sequence (64-key tiles from key 0 shared out over 4 waves, fixed-order merge): group g's rows are bit for bit
+ *   mla_attn_chunk with B = 1 and S_kv = S_p + R on cat(rows [0, S_p), rows [S_p + g R, S_p + (g + 1) R)). Masked and padding loads stay
+ *   inside the group's own key set: no output depends on another group's rows. No allocation, no atomics, no workspace;
+ *   graph-capturable.
+ * mla_attn_chunk_groups_gw: the same with the launch form given -- gw: groups one workgroup serves (1, 2, 4; 0 = the library's choice,
+ *   which is what mla_attn_chunk_groups launches): prefix-only key tiles are loaded, and their V tile transposed, once per workgroup;
+ *   order: 0 = head-major work items in dispatch order, 1 = one contiguous chunk of the head-major order per XCD (block b takes item
+ *   (b % 8) * (grid / 8) + b / 8; only when grid % 8 == 0), -1 = the library's choice. Same bits for every form; kept for measurement
+ *   (tools/bench_infer.py --samples). */
+int mla_attn_chunk_groups(const void* q, const void* k, const void* v, void* o, int G, int H, int head_dim, int S_p, int R, long long ld,
+                          long long ld_o, float scale, mla_stream_t stream);
+int mla_attn_chunk_groups_gw(const void* q, const void* k, const void* v, void* o, int G, int H, int head_dim, int S_p, int R, long long ld,
+                             long long ld_o, float scale, int gw, int order, mla_stream_t stream);
 
 /* ---- losses: CrossEntropyLoss modeling_llama.py:1258-1269; InfoNCE models/mla/fuser/contrastive.py:208-215
  * mla_ce_fwd: lse[r] = logsumexp(logits[r, :ncols]), loss[r] = lse - logits[r, label] (0 for ignore_index or a label outside [0, ncols);

@@ -13,6 +13,8 @@
 //   mla_gemm_suffix_bf16  plain-input projection for 1 <= M <= 256 rows of a batch of samples: the skinny kernel's fragments with 1 / 2 / 4
 //                      W tiles per workgroup, per-sample cache slots and rotary positions read from a device array.
 //   mla_attn_chunk_ragged  mla_attn_chunk with one key count per sample, read from a device array.
+//   mla_attn_chunk_groups  mla_attn_chunk for G groups of R query rows that share ONE sample's prefix rows (N action chunks drawn for one
+//                      observation): every group sees the prefix and, causally, its own rows only.
 //   mla_gemv_w8 / mla_gemm_skinny_w8  the first two projection contracts over weight-only FP8: W is [N, K] OCP e4m3fn bytes with one fp32
 //                      scale per row (mla_quant_fp8_rows writes both); same kernels, W8 = true: half the bytes per weight, decoded in
 //                      registers (v_cvt_pk_f32_fp8 / v_cvt_scalef32_pk_bf16_fp8), fp32 sum over the UNSCALED codes, one multiply by the
@@ -877,6 +879,169 @@ __global__ __launch_bounds__(64 * CH_NW) void attn_chunk_kernel(const bf16_t* __
   }
 }
 
+// ---- suffix attention for G groups of R query rows on ONE sample's cache (mla_attn_chunk_groups): rows [0, S_p) are the prefix every
+// group sees, row S_p + g R + p is suffix row p of group g. Query (g, p) sees the logical keys 0 .. S_p + p; logical key j is memory row
+// j (j < S_p) or j + g R (the group's own rows). attn_chunk_kernel's arithmetic over the logical key sequence of every group -- tiles of
+// 64 logical keys from key 0, tile t on wave t % 4 in iteration t / 4, the same online softmax, P rounding and fixed-order merge -- so
+// group g's rows are bit for bit mla_attn_chunk (B = 1, S_kv = S_p + R) on cat(cache[:S_p], cache[S_p + g R : S_p + (g + 1) R]).
+// One workgroup serves one head, one block of 16 query rows and GW groups: a tile that lies wholly inside the prefix (64 (t + 1) <= S_p)
+// has its K fragments loaded and its V tile transposed into LDS ONCE for the GW query blocks (state per block: qf 16, ot 32, m, l
+// registers); tiles that hold logical keys >= S_p are loaded per group. Masked-key and padding loads clamp to the last logical key of
+// the query's OWN group, so no output depends on another group's rows. Groups beyond G (G % GW != 0) recompute group G - 1 and store nothing.
+constexpr int ATTN_GROUPS_GW = 1;                                      // groups per workgroup mla_attn_chunk_groups launches
+constexpr int ATTN_GROUPS_XCD_CHUNKS = 0;                              // its work order: 0 as dispatched, 1 one chunk of the grid per XCD
+template <int GW>
+__global__ __launch_bounds__(64 * CH_NW) void attn_chunk_groups_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+                                                                       const bf16_t* __restrict__ v, bf16_t* __restrict__ o, int G, int H,
+                                                                       int S_p, int R, long long ld, long long ld_o, float scale, int xcd_chunks) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int QB = (R + 15) >> 4, NGB = (G + GW - 1) / GW;
+  // head-major work order: the workgroups of one head (its 2 S_p x 128 prefix K / V elements) are neighbours. Blocks are dealt out
+  // round-robin over the 8 XCDs (observed, not a contract: only speed depends on it), so with xcd_chunks (host: grid % 8 == 0) block b
+  // takes work item (b % 8) * (grid / 8) + b / 8 -- a bijection -- and the neighbours share one XCD's L2 instead of eight.
+  const int bid = xcd_chunks ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+  const int qb = bid % QB, gb = (bid / QB) % NGB, h = bid / (QB * NGB);
+  const int S_kv = S_p + R;                                             // logical keys of a group
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
+  bf16_t* vt = (bf16_t*)smem + wave * 128 * CH_VP;
+  const bf16_t* kb = k + h * 128;
+  const bf16_t* vb = v + h * 128;
+  const int r = qb * 16 + li;
+  const bool qok = r < R;
+  const int qpos = S_kv - R + (qok ? r : R - 1);
+  const u32x4_t zero = {0u, 0u, 0u, 0u};
+  int goff[GW];                                                         // memory row of logical key j >= S_p: j + goff
+  bf16x8_t qf[GW][4];
+#pragma unroll
+  for (int gi = 0; gi < GW; ++gi) {
+    const int gg = gb * GW + gi;
+    goff[gi] = (gg < G ? gg : G - 1) * R;
+    const bf16_t* qr = q + (long long)(S_p + goff[gi] + (qok ? r : 0)) * ld + h * 128;
+#pragma unroll
+    for (int ds = 0; ds < 4; ++ds) qf[gi][ds] = as_frag(qok ? *(const u32x4_t*)(qr + ds * 32 + g * 8) : zero);
+  }
+  const float sc2 = scale * 1.4426950408889634f;
+  f32x4_t ot[GW][8];
+  float m[GW], l[GW];
+#pragma unroll
+  for (int gi = 0; gi < GW; ++gi) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ot[gi][i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    m[gi] = -INFINITY;
+    l[gi] = 0.f;
+  }
+  const int ntiles = (S_kv + 63) >> 6, iters = (ntiles + CH_NW - 1) / CH_NW;
+  for (int it = 0; it < iters; ++it) {                                  // same trip count and barrier count in every wave
+    const int j0 = (it * CH_NW + wave) * 64;
+    const bool shared = j0 + 64 <= S_p;                                 // wave-uniform: the tile holds prefix rows only
+    u32x4_t kf[4][4];
+#pragma unroll
+    for (int gi = 0; gi < GW; ++gi) {
+      const bool fresh = gi == 0 || !shared;                            // load K / V and rebuild the V tile, or reuse group 0's
+      u32x4_t vv[16];
+      if (fresh) {
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+          const int j = j0 + f * 16 + li, jc = j < S_kv ? j : S_kv - 1;
+          const bf16_t* kr = kb + (long long)(jc < S_p ? jc : jc + goff[gi]) * ld + g * 8;
+#pragma unroll
+          for (int ds = 0; ds < 4; ++ds) kf[f][ds] = *(const u32x4_t*)(kr + ds * 32);
+        }
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+          const int j = j0 + u * 4 + g, jc = j < S_kv ? j : S_kv - 1;
+          vv[u] = *(const u32x4_t*)(vb + (long long)(jc < S_p ? jc : jc + goff[gi]) * ld + li * 8);
+        }
+      }
+      f32x4_t st[4];
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        st[f] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ds = 0; ds < 4; ++ds) st[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(kf[f][ds]), qf[gi][ds], st[f], 0, 0, 0);
+      }
+      float mx = -INFINITY;
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          if (j0 + f * 16 + g * 4 + rr > qpos) st[f][rr] = -INFINITY;
+          mx = fmaxf(mx, st[f][rr]);
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float mnew = fmaxf(m[gi], mx * sc2);
+      const float msafe = mnew == -INFINITY ? 0.f : mnew;
+      const float alpha = __builtin_amdgcn_exp2f(m[gi] - msafe);
+      float ps = 0.f;
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          st[f][rr] = __builtin_amdgcn_exp2f(fmaf(st[f][rr], sc2, -msafe));
+          ps += st[f][rr];
+        }
+      ps += __shfl_xor(ps, 16, 64);
+      ps += __shfl_xor(ps, 32, 64);
+      l[gi] = l[gi] * alpha + ps;
+      m[gi] = mnew;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) ot[gi][i] *= alpha;
+      const bf16x8_t pf0 = pack_pfrag(st[0], st[1]), pf1 = pack_pfrag(st[2], st[3]);
+      if (fresh) {
+#pragma unroll
+        for (int u = 0; u < 16; ++u)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            vt[(li * 8 + 2 * e) * CH_VP + u * 4 + g] = (bf16_t)(vv[u][e] & 0xffffu);
+            vt[(li * 8 + 2 * e + 1) * CH_VP + u * 4 + g] = (bf16_t)(vv[u][e] >> 16);
+          }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int fd = 0; fd < 8; ++fd) {
+        const bf16_t* vr = vt + (fd * 16 + li) * CH_VP + g * 4;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          const u32x2_t lo = *(const u32x2_t*)(vr + ks * 32), hi = *(const u32x2_t*)(vr + ks * 32 + 16);
+          const u32x4_t av = {lo[0], lo[1], hi[0], hi[1]};
+          ot[gi][fd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(av), ks ? pf1 : pf0, ot[gi][fd], 0, 0, 0);
+        }
+      }
+      __syncthreads();
+    }
+  }
+  // attn_chunk_kernel's merge, one group after the other through the same buffers
+  float* mo = (float*)smem;                                             // [CH_NW][128][16]
+  float* ml = mo + CH_NW * 128 * 16;                                    // [CH_NW][16] max, then [CH_NW][16] sum
+#pragma unroll
+  for (int gi = 0; gi < GW; ++gi) {
+    const int gg = gb * GW + gi;
+#pragma unroll
+    for (int fd = 0; fd < 8; ++fd)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) mo[(wave * 128 + fd * 16 + g * 4 + rr) * 16 + li] = ot[gi][fd][rr];
+    if (g == 0) { ml[wave * 16 + li] = m[gi]; ml[CH_NW * 16 + wave * 16 + li] = l[gi]; }
+    __syncthreads();
+    for (int e = threadIdx.x; e < 128 * 16; e += 64 * CH_NW) {
+      const int qq = e & 15, d = e >> 4, rq = qb * 16 + qq;
+      if (rq >= R || gg >= G) continue;
+      float mm = -INFINITY;
+#pragma unroll
+      for (int w = 0; w < CH_NW; ++w) mm = fmaxf(mm, ml[w * 16 + qq]);
+      float L = 0.f, O = 0.f;
+#pragma unroll
+      for (int w = 0; w < CH_NW; ++w) {
+        const float fw = __builtin_amdgcn_exp2f(ml[w * 16 + qq] - mm);
+        L += fw * ml[CH_NW * 16 + w * 16 + qq];
+        O += fw * mo[(w * 128 + d) * 16 + qq];
+      }
+      o[(long long)(gg * R + rq) * ld_o + h * 128 + d] = f2bf(O / L);
+    }
+    if (gi + 1 < GW) __syncthreads();
+  }
+}
+
 // ---- weight quantiser for the W8 projections: one workgroup per row of W [N, K] bf16.
 //   amax = max_k |W[n, k]|;  scale[n] = amax / 448 (1 when the row is all zero);  q[n, k] = e4m3fn_rne(clamp(W[n, k] / scale[n], -448, 448))
 // Both divisions are IEEE fp32 divisions (__fdiv_rn: no v_rcp, no multiply by a reciprocal), so that
@@ -1083,6 +1248,43 @@ extern "C" int mla_attn_chunk_ragged(const void* q, const void* k, const void* v
   hipLaunchKernelGGL(attn_chunk_kernel<true>, dim3(B * H * ((R + 15) / 16)), dim3(64 * CH_NW), lds, stream, (const bf16_t*)q, (const bf16_t*)k,
                      (const bf16_t*)v, (bf16_t*)o, H, S_cap, R, ld, batch_stride, ld_o, scale, kv_len);
   MLA_LAUNCH_CHECK();
+}
+
+// mla_attn_chunk_groups / mla_attn_chunk_groups_gw: one validation + launch path; gw = groups per workgroup (0: the library's choice)
+static int attn_groups_entry(const char* name, const void* q, const void* k, const void* v, void* o, int G, int H, int head_dim, int S_p, int R,
+                             long long ld, long long ld_o, float scale, int gw, int order, hipStream_t stream) {
+  MLA_CHECK_ARG(q && k && v && o, "%s: null pointer", name);
+  MLA_CHECK_ARG(head_dim == 128, "%s: head_dim must be 128 (got %d)", name, head_dim);
+  MLA_CHECK_ARG(G >= 1 && H >= 1 && R >= 1 && R <= CH_RMAX && S_p >= 0, "%s: G >= 1, 1 <= R <= 64, S_p >= 0 required (G %d, R %d, S_p %d)", name, G, R, S_p);
+  MLA_CHECK_ARG((long long)S_p + (long long)G * R <= 0x7fffffffLL, "%s: S_p + G * R rows exceed the int range (G %d, R %d, S_p %d)", name, G, R, S_p);
+  MLA_CHECK_ARG(AL16(q) && AL16(k) && AL16(v) && ld % 8 == 0 && ld_o % 2 == 0, "%s: 16-B aligned rows required", name);
+  MLA_CHECK_ARG(gw == 0 || gw == 1 || gw == 2 || gw == 4, "%s: groups per workgroup must be 0 (default), 1, 2 or 4 (got %d)", name, gw);
+  MLA_CHECK_ARG(order >= -1 && order <= 1, "%s: order must be -1 (default), 0 (as dispatched) or 1 (one chunk of the grid per XCD) (got %d)", name, order);
+  if (gw == 0) gw = ATTN_GROUPS_GW;
+  if (order < 0) order = ATTN_GROUPS_XCD_CHUNKS;
+  const size_t lds = (size_t)CH_NW * 128 * CH_VP * 2;                  // >= the merge buffers, as in mla_attn_chunk
+  const int QB = (R + 15) / 16;
+  const int xcd_chunks = order == 1 && (H * ((G + gw - 1) / gw) * QB) % 8 == 0;
+#define MLA_AG_LAUNCH(GW)                                                                                                              \
+  {                                                                                                                                    \
+    static bool attr = false;                                                                                                          \
+    if (!attr) { (void)hipFuncSetAttribute((const void*)attn_chunk_groups_kernel<GW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; } \
+    hipLaunchKernelGGL(attn_chunk_groups_kernel<GW>, dim3(H * ((G + GW - 1) / GW) * QB), dim3(64 * CH_NW), lds, stream, (const bf16_t*)q,   \
+                       (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, G, H, S_p, R, ld, ld_o, scale, xcd_chunks);                       \
+  }
+  if (gw == 1) MLA_AG_LAUNCH(1) else if (gw == 2) MLA_AG_LAUNCH(2) else MLA_AG_LAUNCH(4)
+#undef MLA_AG_LAUNCH
+  return launch_status(name);
+}
+
+extern "C" int mla_attn_chunk_groups(const void* q, const void* k, const void* v, void* o, int G, int H, int head_dim, int S_p, int R, long long ld,
+                                     long long ld_o, float scale, hipStream_t stream) {
+  return attn_groups_entry("mla_attn_chunk_groups", q, k, v, o, G, H, head_dim, S_p, R, ld, ld_o, scale, 0, -1, stream);
+}
+
+extern "C" int mla_attn_chunk_groups_gw(const void* q, const void* k, const void* v, void* o, int G, int H, int head_dim, int S_p, int R,
+                                        long long ld, long long ld_o, float scale, int gw, int order, hipStream_t stream) {
+  return attn_groups_entry("mla_attn_chunk_groups_gw", q, k, v, o, G, H, head_dim, S_p, R, ld, ld_o, scale, gw, order, stream);
 }
 
 extern "C" int mla_gemm_suffix_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,

@@ -46,6 +46,10 @@ _SIGNATURES = {
                        c_void_p],
     "mla_attn_chunk_ragged": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_longlong, c_longlong,
                               c_longlong, c_float, c_void_p],
+    "mla_attn_chunk_groups": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_float,
+                              c_void_p],
+    "mla_attn_chunk_groups_gw": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_float,
+                                 c_int, c_int, c_void_p],
     "mla_gemm_suffix_bf16": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_int, c_void_p,
                              c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
     "mla_gemm_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -966,6 +970,30 @@ def attn_chunk_ragged(cache, B, nheads, D, kv_len, R, scale):
     base = cache.data_ptr()
     call("mla_attn_chunk_ragged", c_void_p(base), c_void_p(base + 2 * H), c_void_p(base + 4 * H), _p(o), B, nheads, D, _p(kv_len),
          cache.shape[1], R, cache.stride(1), cache.stride(0), H, float(scale))
+    return o
+
+
+def attn_chunk_groups(cache, G, nheads, D, S_p, R, scale, gw=None, order=None):
+    """Attention of G groups of R suffix rows behind ONE sample's prefix (mla_attn_chunk_groups): cache [S_p + G * R, 3H] (or with a
+    leading 1) packed post-RoPE q|k|v, rows [0, S_p) the prefix, row S_p + g * R + p suffix row p of group g, which sees the prefix and
+    rows S_p + g * R .. S_p + g * R + p. Group g's rows are bit for bit attn_chunk(B = 1, S_kv = S_p + R) on cat(prefix, group g's rows).
+    gw: groups per workgroup (1, 2, 4), order: 0 head-major work items as dispatched / 1 one chunk of them per XCD (measurement only --
+    the bits depend on neither), None = the library's choice.
+    Returns o [G * R, nheads * D] bf16."""
+    _req(cache, torch.bfloat16, "attn_chunk_groups cache")
+    if cache.dim() == 3:
+        assert cache.shape[0] == 1
+        cache = cache[0]
+    H = nheads * D
+    assert cache.dim() == 2 and cache.shape[1] == 3 * H and cache.stride(1) == 1 and G >= 1 and R >= 1 and S_p >= 0
+    assert cache.shape[0] >= S_p + G * R, (tuple(cache.shape), S_p, G, R)
+    o = torch.empty((G * R, H), dtype=torch.bfloat16, device=cache.device)
+    base = cache.data_ptr()
+    args = (c_void_p(base), c_void_p(base + 2 * H), c_void_p(base + 4 * H), _p(o), G, nheads, D, S_p, R, cache.stride(0), H, float(scale))
+    if gw is None and order is None:
+        call("mla_attn_chunk_groups", *args)
+    else:
+        call("mla_attn_chunk_groups_gw", *args, int(gw or 0), -1 if order is None else int(order))
     return o
 
 

@@ -133,6 +133,15 @@ class _CachedEpsBase:
             shared["fp8_as_bf16"] = deq
         return shared[self.suffix_weights]
 
+    def _prefix_rows(self, input_ids, k, images, point_cloud, camera_name, proprio, tactile=None, gripper_xyz=None):
+        """The decoder's input rows in front of the [t, x] tokens, [B, S_p, H]: [BOS | fused tokens | text[1:k] | proprio] (call under no_grad)."""
+        vlm = self.vlm
+        parts, _, _, _, _, _ = vlm.get_fused_tokens(images, point_cloud, tactile, gripper_xyz, camera_name)
+        vlm.vision_tower_2d.assert_masks_ok()
+        text_emb = vlm.llm_backbone.embed_input_ids(input_ids)
+        proprio_e = vlm.proprio_embedder(proprio.to(torch.bfloat16))
+        return torch.cat([text_emb[:, :1]] + parts + [text_emb[:, 1:k], proprio_e], dim=1).contiguous()
+
     def _run(self):
         if _USE_GRAPH and not self._graph_failed:
             if self.graph is None:
@@ -221,13 +230,9 @@ class PrefixCachedEps(_CachedEpsBase):
         return eng
 
     def prefill(self, input_ids, k, images=None, point_cloud=None, camera_name=None, proprio=None, tactile=None, gripper_xyz=None, **unused):
-        vlm, bf16, dev = self.vlm, torch.bfloat16, input_ids.device
+        bf16, dev = torch.bfloat16, input_ids.device
         with torch.no_grad():
-            parts, _, _, _, _, _ = vlm.get_fused_tokens(images, point_cloud, tactile, gripper_xyz, camera_name)
-            vlm.vision_tower_2d.assert_masks_ok()
-            text_emb = vlm.llm_backbone.embed_input_ids(input_ids)
-            proprio_e = vlm.proprio_embedder(proprio.to(bf16))
-            prefix = torch.cat([text_emb[:, :1]] + parts + [text_emb[:, 1:k], proprio_e], dim=1).contiguous()       # [B, S_p, H]
+            prefix = self._prefix_rows(input_ids, k, images, point_cloud, camera_name, proprio, tactile, gripper_xyz)       # [B, S_p, H]
             B, S_p, H = prefix.shape
             if self.cache is None:
                 self.B, self.S_p, self.H = B, S_p, H
@@ -493,6 +498,139 @@ class BatchedPrefixCachedEps(_CachedEpsBase):
             # q|k|v rows of sample b -> cache rows slot[b] .. slot[b] + R, q and k rotated at those positions in the epilogue
             self._proj(xn, (wq, wk, wv), out=c, slot=self.slot, cap_rows=self.S_cap, rope=(self.cos_c, self.sin_c, 2 * H))
             o = hip.attn_chunk_ragged(c, B, self.nheads, self.D, self.kv_len, R, scale)
+            h1 = self._proj(o, (wo,), residual=h)
+            xn2, _ = hip.rmsnorm_fwd(h1, ln2, self.eps)
+            gu = self._proj(xn2, (wg, wu))
+            h = self._proj(hip.swiglu_fwd(gu), (wd,), residual=h1)
+        hn, _ = hip.rmsnorm_fwd(h, self.model.norm.weight, self.eps)
+        self.h_out.copy_(hn)
+
+
+# ================================================================================================ N action chunks for one observation
+# MLA.predict_action_diff_samples: N independent draws for ONE observation. Everything in front of the [t, x] tokens is the same in all
+# of them, so the encoders and the prefill run once (batch 1, S_p rows) and the cache holds ONE prefix followed by G groups of R suffix
+# rows: [S_p + G R, 3H] per layer. A pass is the batched engine's eight launches over the G R suffix rows, with the projection writing
+# group g's rows at S_p + g R + p (mla_gemm_suffix_bf16 with the "samples" overlapping: batch stride R rows, every slot S_p) and
+# mla_attn_chunk_groups as the attention.
+def plan_sample_groups(num_samples: int, R: int, max_rows: int = 256):
+    """Pure host planning: the passes [(start, stop), ...] that serve samples [0, num_samples) in order, at most max_rows // R groups
+    (R suffix rows each) per pass."""
+    num_samples, R, max_rows = int(num_samples), int(R), int(max_rows)
+    if num_samples < 1:
+        raise ValueError(f"num_samples must be >= 1, got {num_samples}")
+    if R < 1 or R > max_rows:
+        raise ValueError(f"{R} suffix rows per sample do not fit the {max_rows} rows of a pass")
+    per = max_rows // R
+    return [(start, min(start + per, num_samples)) for start in range(0, num_samples, per)]
+
+
+class SampleGroupsEps(_CachedEpsBase):
+    """One engine per (splice position, action rows, group capacity, device): ONE cache per layer with the prefix rows and room for
+    `capacity` groups, prefilled once per call; `set_groups(G)` selects how many groups the next `model(x [G, T, D], t [G])` calls serve
+    (G <= capacity: the sub-batches of a call whose N exceeds a pass share the cache and the prefill) and one captured graph is kept per
+    distinct G. Rows of groups >= G are neither written nor read by a pass of G groups."""
+
+    MAX_ROWS = 256                   # suffix rows per pass (mla_gemm_suffix_bf16)
+    MAX_R = 64                       # rows per group (mla_attn_chunk_groups)
+
+    @classmethod
+    def supports_samples(cls, vlm, n_action_rows: int) -> bool:
+        """head_dim 128 and at most 64 suffix rows per sample; otherwise the caller loops over batch-1 calls (warns once per shape)."""
+        cfg = vlm.llm_backbone.llm.config
+        R, D = 1 + n_action_rows, cfg.hidden_size // cfg.num_attention_heads
+        if R <= cls.MAX_R and D == 128:
+            return True
+        seen = vlm.__dict__.setdefault("_prefix_unsupported", set())
+        if ("samples", R, D) not in seen:
+            seen.add(("samples", R, D))
+            warnings.warn(f"SampleGroupsEps: {R} suffix rows per sample (max {cls.MAX_R}) / head_dim {D} (needs 128) are beyond the "
+                          "shared-prefix kernels; drawing every sample with its own predict_action_diff call", RuntimeWarning, stacklevel=3)
+        return False
+
+    @classmethod
+    def for_inputs(cls, vlm, input_ids, n_action_rows: int, num_samples: int, **model_kwargs):
+        """-> (engine, prefilled for this observation; passes [(start, stop), ...] of plan_sample_groups)."""
+        k = PrefixCachedEps._splice_position(input_ids)
+        passes = plan_sample_groups(num_samples, 1 + n_action_rows, cls.MAX_ROWS)
+        capacity = max(stop - start for start, stop in passes)
+        engines = vlm.__dict__.setdefault("_prefix_engines_samples", {})
+        key = (k, int(n_action_rows), capacity, str(input_ids.device))
+        eng = engines.get(key)
+        if eng is None:
+            if len(engines) >= 4:
+                engines.pop(next(iter(engines)))
+            eng = engines[key] = cls(vlm, n_action_rows, capacity)
+        eng.prefill(input_ids, k, **model_kwargs)
+        return eng, passes
+
+    def __init__(self, vlm, n_action_rows: int, capacity: int):
+        super().__init__(vlm, n_action_rows)
+        self.capacity = int(capacity)
+        self._graphs = {}            # G -> captured pass over G groups
+        self._graphs_packed = None   # the packed weights those graphs hold the addresses of
+
+    def set_groups(self, G: int):
+        assert 1 <= G <= self.capacity and self.cache is not None
+        self.B = G
+        self.h_in, self.h_out = self._h_in[:G * self.R], self._h_out[:G * self.R]
+        self.graph = self._graphs.get(G)
+
+    def prefill(self, input_ids, k, images=None, point_cloud=None, camera_name=None, proprio=None, tactile=None, gripper_xyz=None, **unused):
+        bf16, dev = torch.bfloat16, input_ids.device
+        assert input_ids.shape[0] == 1, "one observation"
+        with torch.no_grad():
+            prefix = self._prefix_rows(input_ids, k, images, point_cloud, camera_name, proprio, tactile, gripper_xyz)
+            _, S_p, H = prefix.shape
+            if self.cache is None:
+                self.S_p, self.H = S_p, H
+                self.D = H // self.nheads
+                rot = self.model.layers[0].self_attn.rotary_emb
+                self.cos_p, self.sin_p = rot.tables(S_p, dev)
+                self.cos_c, self.sin_c = rot.tables(S_p + self.R, dev)        # the epilogue rotates row S_p + p of a group with table row S_p + p
+                rows = self.capacity * self.R
+                with torch.inference_mode(False):                            # the engine outlives the (inference-mode) call that creates it
+                    self.cache = [torch.zeros((S_p + rows, 3 * H), dtype=bf16, device=dev) for _ in self.model.layers]
+                    self._h_in = torch.zeros((rows, H), dtype=bf16, device=dev)
+                    self._h_out = torch.zeros((rows, H), dtype=bf16, device=dev)
+                    self.slot = torch.full((self.capacity,), S_p, dtype=torch.int32, device=dev)
+                self.set_groups(self.capacity)
+            assert (S_p, H) == (self.S_p, self.H)
+            weights = self._weights()
+            if self._graphs_packed is not self._suffix:                      # new weights: every captured pass holds stale addresses
+                self._graphs.clear()
+                self._graphs_packed = self._suffix
+                self.graph = None
+            h = prefix.reshape(S_p, H)
+            for w, c in zip(weights, self.cache):
+                h, acts = ops.DecoderLayerFn._fwd(h, None, self.cos_p, self.sin_p, 1, S_p, self.nheads, self.eps, w)
+                c[:S_p].copy_(acts.qkv[:S_p])
+                del acts
+
+    def _run(self):
+        super()._run()
+        if self.graph is not None:
+            self._graphs[self.B] = self.graph
+
+    def _proj(self, x, weights, out=None, residual=None, **kw):
+        wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
+        assert wcat is not None, "the packed weights are adjacent in memory (_weights)"
+        M = x.shape[0]
+        if out is None:
+            out = torch.empty((M, wcat.shape[0]), dtype=torch.bfloat16, device=x.device)
+            hip.gemm_suffix(x, wcat, out, out.stride(0), 0, M, residual)
+        else:                                                                # group g = "sample" g of the kernel: base row g R, slot S_p
+            hip.gemm_suffix(x, wcat, out, out.stride(0), self.R * out.stride(0), self.R, residual, **kw)
+        return out
+
+    def _suffix_pass(self):
+        G, R, H, S_p = self.B, self.R, self.H, self.S_p
+        h = self.h_in
+        scale = 1.0 / math.sqrt(self.D)
+        for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd), c in zip(self._packed, self.cache):
+            xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
+            # q|k|v row p of group g -> cache row S_p + g R + p, q and k rotated at position S_p + p in the epilogue
+            self._proj(xn, (wq, wk, wv), out=c, slot=self.slot, cap_rows=S_p + R, rope=(self.cos_c, self.sin_c, 2 * H))
+            o = hip.attn_chunk_groups(c, G, self.nheads, self.D, S_p, R, scale)
             h1 = self._proj(o, (wo,), residual=h)
             xn2, _ = hip.rmsnorm_fwd(h1, ln2, self.eps)
             gu = self._proj(xn2, (wg, wu))

@@ -461,3 +461,66 @@ class MLA(nn.Module):
             out.append(samples.float().cpu().numpy())
         normalized = np.concatenate(out, axis=0)
         return self.unnormalize_actions(normalized, unnorm_key) if self.norm_stats is not None else normalized
+
+    @torch.inference_mode()
+    def predict_action_diff_samples(self, image=None, pointcloud=None, instruction: Optional[str] = None, cur_robot_state=None,
+                                    unnorm_key: Optional[str] = None, num_samples: int = 1, cfg_scale: float = 0.0, use_ddim: bool = True,
+                                    num_ddim_steps: int = 8, action_dim: int = 7, *, input_ids: Optional[torch.Tensor] = None,
+                                    noise: Optional[torch.Tensor] = None, camera_name: str = "rlbench_front",
+                                    reuse_prefix: bool = True) -> np.ndarray:
+        """N action chunks for ONE observation -> [N, T, action_dim]: by definition N independent `predict_action_diff` calls on the same
+        observation with the initial samples ``noise[n]`` (critic / best-of-N choice, uncertainty estimates, temporal ensembling), computed
+        on ONE cached prefix (mla_amd/infer.py:SampleGroupsEps): the encoders and the decoder prefill run once per call, every sampler step
+        is one pass over the N * (1 + T) suffix rows (mla_attn_chunk_groups: every sample sees the prefix and its own rows), the FPS start
+        indices are drawn once per call. Every per-observation step (image pre-processing, mask channel, prompt tail, proprio
+        normalisation, un-normalisation) is predict_action_diff's. RNG: the draws of N calls in their order (randn(1, T, D), then the
+        unused randint, per sample). ``num_samples=1`` IS predict_action_diff; ``reuse_prefix=False``, head_dim != 128 or more than 64
+        suffix rows per sample loop N predict_action_diff calls (a shape reason warns once); more than 256 suffix rows are served as
+        consecutive passes on the same prefill. bf16 weights only."""
+        N = int(num_samples)
+        T = self.future_action_window_size + 1
+        if N < 1:
+            raise ValueError(f"num_samples must be >= 1, got {num_samples}")
+        if noise is not None and tuple(noise.shape) != (N, T, action_dim):
+            raise ValueError(f"noise must be [N, T, action_dim] = [{N}, {T}, {action_dim}], got {tuple(noise.shape)}")
+        self._check_cfg_scale(cfg_scale)
+
+        def one(n, **kw):
+            return self.predict_action_diff(image, pointcloud, instruction, cur_robot_state, unnorm_key, cfg_scale, use_ddim, num_ddim_steps,
+                                            action_dim, input_ids=input_ids, noise=None if noise is None else noise[n:n + 1],
+                                            camera_name=camera_name, **kw)
+        if N == 1:
+            return one(0, reuse_prefix=reuse_prefix)[None]
+        if reuse_prefix:
+            from .infer import SampleGroupsEps
+            reuse_prefix = SampleGroupsEps.supports_samples(self.vlm, T)
+        if not reuse_prefix:
+            return np.stack([one(n, reuse_prefix=False) for n in range(N)])
+        self.vlm.eval()
+        device = next(self.vlm.parameters()).device
+        if input_ids is None:
+            input_ids = self._prompt_ids(instruction, "predict_action_diff_samples")
+        image = self._preprocessed_image(image)
+        input_ids = self._ids_with_tail(input_ids, device)
+        model_kwargs = {"images": self._image_batch(image, device), "point_cloud": self._pointcloud_batch(pointcloud, device),
+                        "camera_name": camera_name, "proprio": self._proprio_token(cur_robot_state, unnorm_key, device)}
+        draws = []
+        for n in range(N):                                                   # the RNG draws of N calls, in their order (:707-708)
+            draws.append(torch.randn(1, T, action_dim, device=device) if noise is None else noise[n:n + 1].to(device))
+            _ = torch.randint(0, self.diffusion.num_timesteps, (T,), device=device)
+        x0 = torch.cat(draws, dim=0).float()
+        if use_ddim and num_ddim_steps is not None and self.ddim_diffusion is None:
+            self.create_ddim(ddim_step=num_ddim_steps)
+        eng, passes = SampleGroupsEps.for_inputs(self.vlm, input_ids, T, N, **model_kwargs)
+        out = []
+        for start, stop in passes:                                           # one prefill, then the passes' sampler loops one after the other
+            eng.set_groups(stop - start)
+            xs = x0[start:stop].contiguous()
+            if use_ddim and num_ddim_steps is not None:
+                samples = self.ddim_diffusion.ddim_sample_loop(eng, xs.shape, xs, clip_denoised=False, model_kwargs={}, progress=False,
+                                                               device=device, eta=0.0)
+            else:
+                samples = self.diffusion.p_sample_loop(eng, xs.shape, xs, clip_denoised=False, model_kwargs={}, progress=False, device=device)
+            out.append(samples.float().cpu().numpy())
+        normalized = np.concatenate(out, axis=0)
+        return self.unnormalize_actions(normalized, unnorm_key) if self.norm_stats is not None else normalized

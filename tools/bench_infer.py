@@ -11,13 +11,21 @@
                                                           latency and the suffix pass alone, per pair, with the 95 % interval of the pair
                                                           differences; --kernel-table adds mla_gemv_w8 vs mla_gemm_skinny_w8 per 7B
                                                           projection shape at M = 2, 5, 8, 17 (the engine's selection rule is set from it)
-Prints one JSON line (not the driver's bench contract -- that is bench.py)."""
+    python tools/bench_infer.py --samples N[,N..] [--chunks C[,C..]] [--pairs P] [--kernel-table]
+                                                          N action chunks for ONE observation, three forms of the same work alternating in
+                                                          one process (same box, same clocks), per pair, with the 95 % interval of the pair
+                                                          differences: (a) predict_action_diff_samples, (b) predict_action_diff_batch on N
+                                                          copies of the observation, (c) N sequential predict_action_diff calls;
+                                                          --kernel-table adds mla_attn_chunk_groups alone at 1 / 2 / 4 groups per workgroup
+                                                          against mla_attn_chunk_ragged on N copies of the prefix
+Prints one JSON line per measurement (not the driver's bench contract -- that is bench.py)."""
 import argparse
 import json
 import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -33,8 +41,13 @@ def main():
     ap.add_argument("--suffix-weights", choices=["bf16", "fp8", "fp8_as_bf16"], default="bf16")
     ap.add_argument("--pair-fp8", action="store_true", help="alternate bf16 and fp8 chunks in one process, in pairs")
     ap.add_argument("--pairs", type=int, default=6)
-    ap.add_argument("--kernel-table", action="store_true", help="with --pair-fp8: the two _w8 kernels per projection shape and M")
+    ap.add_argument("--kernel-table", action="store_true", help="with --pair-fp8: the two _w8 kernels per projection shape and M; with "
+                    "--samples: mla_attn_chunk_groups per groups-per-workgroup against mla_attn_chunk_ragged")
+    ap.add_argument("--samples", type=str, default="", help="N[,N..]: predict_action_diff_samples vs the batched call on N copies vs N calls")
+    ap.add_argument("--chunks", type=str, default="", help="with --samples: action chunk lengths to measure in one process (default: --chunk)")
     args = ap.parse_args()
+    if args.samples:
+        return main_samples(args)
     if args.batch > 0:
         return main_batch(args)
     if args.pair_fp8:
@@ -204,6 +217,113 @@ def main_pair(args):
             table[f"M{M}"] = row
         out["w8_kernel_us_per_launch"] = table
     print(json.dumps(out))
+
+
+def _attn_groups_table(dev, Ns, chunks, H=32, S_p=545, layers=32, reps=5, rounds=3):
+    """mla_attn_chunk_groups alone at the 7B shapes (32 heads, 545 prefix rows), gw = 1 / 2 / 4 groups per workgroup x both work orders, against
+    mla_attn_chunk_ragged on N copies of the prefix. As the engines launch them: one launch per layer on that layer's own cache (32
+    caches: nothing of a layer's prefix is left in the caches when its turn comes again), captured into a graph; the arms alternate and
+    every arm is measured `rounds` times. us per launch, the minimum and all rounds. Algorithmic bytes: the prefix K and V once plus
+    every group's rows for the groups kernel, N copies of everything for the ragged one."""
+    import math
+    from mla_amd import hip
+    scale = 1 / math.sqrt(128)
+    table = {}
+    for chunk in chunks:
+        R = chunk + 1
+        for N in Ns:
+            rows = S_p + N * R
+            shared = [(torch.randn(rows, 3 * H * 128, device=dev) * 0.7).to(torch.bfloat16) for _ in range(layers)]
+            copies = [(torch.randn(N, S_p + R, 3 * H * 128, device=dev) * 0.7).to(torch.bfloat16) for _ in range(layers)]
+            kv_len = torch.full((N,), S_p + R, dtype=torch.int32, device=dev)
+            arms = {"ragged_N_copies": lambda c=copies: [hip.attn_chunk_ragged(x, N, H, 128, kv_len, R, scale) for x in c]}
+            for gw in (1, 2, 4):                                            # order 0: head-major work items as dispatched, 1: one chunk per XCD
+                for order in (0, 1):
+                    arms[f"groups_gw{gw}_order{order}"] = lambda gw=gw, order=order, c=shared: [
+                        hip.attn_chunk_groups(x, N, H, 128, S_p, R, scale, gw=gw, order=order) for x in c]
+            graphs = {}
+            for name, fn in arms.items():
+                fn()
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    keep = fn()
+                g.replay()
+                graphs[name] = (g, keep)
+            us = {name: [] for name in arms}
+            for _ in range(rounds):
+                for name, (g, _) in graphs.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(reps):
+                        g.replay()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    us[name].append(round(e0.elapsed_time(e1) / (reps * layers) * 1e3, 1))
+            kv_row = 2 * H * 128 * 2                                        # K and V bytes of one cache row, all heads
+            table[f"chunk{chunk}_N{N}"] = {"us_per_launch_min": {k: min(v) for k, v in us.items()}, "us_per_launch_rounds": us,
+                                           "algorithmic_kv_mb": {"groups": round((S_p + N * R) * kv_row / 1e6, 2),
+                                                                 "ragged_N_copies": round(N * (S_p + R) * kv_row / 1e6, 2)}}
+            del graphs, shared, copies
+            torch.cuda.empty_cache()
+    return table
+
+
+def main_samples(args):
+    from bench import build
+    from mla_amd.synthetic import make_batch
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    Ns = [int(v) for v in args.samples.split(",")]
+    chunks = [int(v) for v in args.chunks.split(",")] if args.chunks else [args.chunk]
+    if args.kernel_table:
+        print(json.dumps({"metric": "mla_attn_chunk_groups vs mla_attn_chunk_ragged on N copies, 32 heads, S_p 545, one launch per layer cache",
+                          "unit": "us", "table": _attn_groups_table(dev, Ns, chunks), "data": "synthetic"}), flush=True)
+    m = build(dev, 1)
+    m.eval()
+    for p in m.parameters():
+        p.data = p.data.to(torch.bfloat16)
+    b = make_batch(B=1, device=dev)
+    ids = torch.cat([b["input_ids"][:, :-4], torch.tensor([[29871]], device=dev)], dim=1)
+    image, pc, state = b["images"]["front_image"][0], b["point_cloud"][0], b["proprio"][0, 0].cpu().numpy()
+    for chunk in chunks:
+        m.future_action_window_size = m.vlm.future_action_window_size = chunk - 1
+        for N in Ns:
+            noise = torch.randn(N, chunk, 7, device=dev)
+            forms = {
+                "a_samples": lambda: m.predict_action_diff_samples(image, pc, cur_robot_state=state, num_samples=N, input_ids=ids, noise=noise,
+                                                                   num_ddim_steps=args.steps),
+                "b_batch_of_copies": lambda: m.predict_action_diff_batch([image] * N, [pc] * N, cur_robot_states=[state] * N,
+                                                                         input_ids=[ids[0]] * N, noise=noise, num_ddim_steps=args.steps),
+                "c_sequential": lambda: np.stack([m.predict_action_diff(image, pc, cur_robot_state=state, input_ids=ids, noise=noise[n:n + 1],
+                                                                        num_ddim_steps=args.steps) for n in range(N)])}
+            outs = {k: fn() for k, fn in forms.items()}                       # engines, graphs, packed weights
+            ms = {k: [] for k in forms}
+            for _ in range(args.pairs):                                       # a, b, c, a, b, c, ...: same box, interleaved
+                for k, fn in forms.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(args.iters):
+                        fn()
+                    torch.cuda.synchronize()
+                    ms[k].append((time.perf_counter() - t0) / args.iters * 1e3)
+            rel = lambda x, y: round(float(((x - y) ** 2).sum() ** 0.5 / (y ** 2).sum() ** 0.5), 5)  # noqa: E731
+            eng = next(iter(m.vlm.__dict__.get("_prefix_engines_samples", {}).values()), None)
+            print(json.dumps({"metric": "N action chunks for one observation, MLA-Llama2-7B bf16: (a) predict_action_diff_samples, (b) "
+                                        "predict_action_diff_batch on N copies, (c) N sequential predict_action_diff calls; alternating",
+                              "samples": N, "action_chunk": chunk, "suffix_rows": N * (chunk + 1), "ddim_steps": args.steps, "pairs": args.pairs,
+                              "iters_per_timing": args.iters, "unit": "ms", "ms": {k: [round(v, 1) for v in vs] for k, vs in ms.items()},
+                              "min_ms": {k: round(min(vs), 1) for k, vs in ms.items()},
+                              "a_minus_b": _pair_stats(ms["b_batch_of_copies"], ms["a_samples"]),
+                              "a_minus_c": _pair_stats(ms["c_sequential"], ms["a_samples"]),
+                              "speedup_vs_b": round(min(ms["b_batch_of_copies"]) / min(ms["a_samples"]), 2),
+                              "speedup_vs_c": round(min(ms["c_sequential"]) / min(ms["a_samples"]), 2),
+                              "a_vs_c_rel_diff_random_weights": rel(outs["a_samples"], outs["c_sequential"]),
+                              "a_vs_b_rel_diff_random_weights": rel(outs["a_samples"], outs["b_batch_of_copies"]),
+                              "samples_engine_graph": bool(eng is not None and eng.graph is not None), "data": "synthetic"}), flush=True)
+            for store in ("_prefix_engines_samples", "_prefix_engines_batched"):   # the caches of this (N, chunk): 6.5 GB at N = 15 for (b)
+                m.vlm.__dict__.get(store, {}).clear()
+            torch.cuda.empty_cache()
 
 
 def main_batch(args):
