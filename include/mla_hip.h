@@ -333,6 +333,17 @@ int mla_attn_chunk_ragged(const void* q, const void* k, const void* v, void* o, 
 int mla_gemm_suffix_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
                          int rows_per_batch, const int* slot, int cap_rows, const void* residual, long long ld_res, int M, int N, int K,
                          const float* rope_cos, const float* rope_sin, int rope_cols, mla_stream_t stream);
+/* mla_gemm_suffix_w8: mla_gemm_suffix_bf16 -- the same rows, slot / cap_rows addressing (the overlapping "groups" form included), residual
+ *   and q|k rotary epilogue, launch forms and unwritten rows outside [0, cap_rows) -- over weight-only FP8: W [N, K] e4m3fn bytes (ldw in
+ *   elements = bytes, ldw % 16 == 0: a row starts on 16 B) and w_scale [N] fp32 as mla_quant_fp8_rows writes them. K >= 16, K % 16 == 0.
+ *   Arithmetic: mla_gemm_skinny_w8's -- 64-wide K steps split over the 8 waves as there, a lane's 16 codes decoded at scale 1 into the A
+ *   fragments of two MFMAs, the 8 partial sums added in the same order, the finished sum times w_scale[n] (the rotation partner's times
+ *   w_scale[n ^ 64]), then the residual add or the rotation and one bf16 rounding. Every output element depends on its own x row, its own
+ *   W row and that K split only: for any M <= 256 rows [64 i, 64 i + 64) are bit for bit what mla_gemm_skinny_w8 (pre 0) writes for
+ *   that slice. Half the weight bytes of the bf16 form per call; no scratch, no workspace, no atomics, graph-capturable. */
+int mla_gemm_suffix_w8(const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
+                       long long out_batch_stride, int rows_per_batch, const int* slot, int cap_rows, const void* residual, long long ld_res,
+                       int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols, mla_stream_t stream);
 /* ---- N action chunks for ONE observation (mla_amd/infer.py SampleGroupsEps): G groups of R suffix rows behind one shared prefix.
  * mla_attn_chunk_groups: q / k / v point at the packed post-RoPE q|k|v cache of one sample, [S_p + G * R, 3 H] with row stride ld:
  *   rows [0, S_p) are the prefix, row S_p + g * R + p is suffix row p of group g. Query (g, p) sees the logical keys j = 0 .. S_p + p,

@@ -19,6 +19,9 @@
 //                      scale per row (mla_quant_fp8_rows writes both); same kernels, W8 = true: half the bytes per weight, decoded in
 //                      registers (v_cvt_pk_f32_fp8 / v_cvt_scalef32_pk_bf16_fp8), fp32 sum over the UNSCALED codes, one multiply by the
 //                      row scale behind the finished sum.
+//   mla_gemm_suffix_w8  the third projection contract (1 <= M <= 256 plain rows, ragged / groups slot addressing) over the same FP8 weights:
+//                      gemm_suffix_kernel with W8 = true -- the skinny W8 kernel's 64-wide K steps, wave split and summation order, so every
+//                      64-row slice is bit for bit mla_gemm_skinny_w8's output; serves N action chunks per observation (SampleGroupsEps).
 // infer.py keeps gemv / decode for every shape they accept and uses the other two beyond (action chunks of 8..63 steps); the last two
 // serve batched sampling (B observations with prompts of different lengths on one pass).
 // All are HBM-bound by construction: algorithmic bytes = the weight matrix (gemv) / the K and V rows of the head (decode).
@@ -631,8 +634,15 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* _
 // NT = 1 (M <= 64) is gemm_skinny_kernel<MB, 0>'s arithmetic: the same K ranges per wave, the same MFMA order inside a wave, the same
 // fixed-order sum over the 8 waves -> bit-identical outputs. The partial tiles go through LDS one W tile and at most 8 x blocks at a
 // time (64 KiB at most).
-template <int NT, int MB>
-__global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* __restrict__ x, long long ldx, const bf16_t* __restrict__ W, long long ldw,
+// W8 (e4m3fn weights, see gemm_skinny_kernel): a 64-wide K step, a lane's 16-B load = the 16 codes k = 64 s + 16 (l >> 4) .. + 15 of every W tile,
+// decoded at scale 1 into the A fragments of two MFMAs per tile (h = 0: codes 0-7, h = 1: codes 8-15) against the x elements at k + 8 h; an
+// x load round holds at most 16 loads -- HX half steps of MX <= 8 blocks; at MB = 16 a half step takes two rounds of 8 blocks (32 registers:
+// all 16 at once spilled; the decode of its A fragments is common to both rounds and compiled once: 16 conversions per 64 MFMAs of a
+// K step in the gfx950 code) --, the W loads of UW steps are issued in front of them. Per accumulator the MFMA order is (s, h) ascending over gemm_skinny_kernel<MB, 0, true>'s K ranges, the
+// waves are summed in its order and w_scale[n] multiplies the finished sum: every 64-row slice is bit for bit that kernel's output.
+template <int NT, int MB, bool W8>
+__global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* __restrict__ x, long long ldx, const typename welem<W8>::t* __restrict__ W,
+                                                                 long long ldw, const float* __restrict__ w_scale,
                                                                  bf16_t* __restrict__ out, long long ldo, long long out_bs, int rpb,
                                                                  const int* __restrict__ slot, int cap_rows, const bf16_t* __restrict__ res,
                                                                  long long ld_res, int M, int N, int K, const float* __restrict__ rope_cos,
@@ -644,7 +654,7 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* _
   __shared__ __attribute__((aligned(16))) float lds[SK_NW * MG * 256];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
   const int tile0 = blockIdx.x * NT;
-  const bf16_t* wr[NT];
+  const typename welem<W8>::t* wr[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     const int tile = tile0 + nt;
@@ -660,7 +670,7 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* _
     xok[mb] = m < M;
     xr[mb] = x + (long long)(xok[mb] ? m : 0) * ldx;
   }
-  const int steps = (K + 31) >> 5, spw = (steps + SK_NW - 1) / SK_NW;
+  const int steps = W8 ? (K + 63) >> 6 : (K + 31) >> 5, spw = (steps + SK_NW - 1) / SK_NW;
   const int s_beg = wave * spw, s_end = s_beg + spw < steps ? s_beg + spw : steps;
   f32x4_t acc[NT][MB];
 #pragma unroll
@@ -668,6 +678,50 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* _
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) acc[nt][mb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   const u32x4_t zero = {0u, 0u, 0u, 0u};
+  if constexpr (W8) {
+    constexpr int UW = U;                                              // the bf16 form's W bytes in flight per lane
+    constexpr int HX = MB <= 1 ? 16 : (MB <= 2 ? 8 : (MB <= 4 ? 4 : (MB <= 8 ? 2 : 1)));   // half steps per x load round: <= 16 loads
+    constexpr int MX = MB <= 8 ? MB : 8;                               // x blocks per load round (16 blocks: two rounds per half step)
+    static_assert((2 * UW) % HX == 0 && HX <= 2 * UW && MB % MX == 0, "x load rounds tile the W batch");
+    for (int s0 = s_beg; s0 < s_end; s0 += UW) {
+      u32x4_t a[UW][NT];
+#pragma unroll
+      for (int u = 0; u < UW; ++u) {
+        const int k = (s0 + u) * 64 + g * 16;
+        const bool ok = s0 + u < s_end && k < K;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) a[u][nt] = ok ? __builtin_nontemporal_load((const u32x4_t*)(wr[nt] + k)) : zero;   // code 0 = +0
+      }
+#pragma unroll
+      for (int q0 = 0; q0 < 2 * UW; q0 += HX) {
+#pragma unroll
+        for (int m0 = 0; m0 < MB; m0 += MX) {
+          u32x4_t b[HX][MX];
+#pragma unroll
+          for (int j = 0; j < HX; ++j) {
+            const int u = (q0 + j) >> 1, h = (q0 + j) & 1;
+            const int k = (s0 + u) * 64 + g * 16;
+            const bool ok = s0 + u < s_end && k < K;
+#pragma unroll
+            for (int mb = 0; mb < MX; ++mb) b[j][mb] = ok && xok[m0 + mb] ? *(const u32x4_t*)(xr[m0 + mb] + k + 8 * h) : zero;
+          }
+#pragma unroll
+          for (int j = 0; j < HX; ++j) {
+            const int u = (q0 + j) >> 1, h = (q0 + j) & 1;
+            if (s0 + u < s_end) {                                      // wave-uniform
+#pragma unroll
+              for (int nt = 0; nt < NT; ++nt) {
+                const u32x4_t af = fp8x8_to_bf16(a[u][nt][2 * h], a[u][nt][2 * h + 1]);
+#pragma unroll
+                for (int mb = 0; mb < MX; ++mb)
+                  acc[nt][m0 + mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(af), as_frag(b[j][mb]), acc[nt][m0 + mb], 0, 0, 0);
+              }
+            }
+          }
+        }
+      }
+    }
+  } else
   for (int s0 = s_beg; s0 < s_end; s0 += U) {
     u32x4_t a[U][NT], b[U][MB];
 #pragma unroll
@@ -714,11 +768,13 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* _
         float v = 0.f, partner = 0.f;
 #pragma unroll
         for (int w = 0; w < SK_NW; ++w) v += lds[((w * MG + mb) * 4 + (i & 3)) * 64 + (i >> 2) * 16 + col];
+        if constexpr (W8) v = __fmul_rn(v, w_scale[n]);
         if (res) v += bf2f(res[(long long)m * ld_res + n]);
         if (rot) {
           const int ip = i ^ 8;
 #pragma unroll
           for (int w = 0; w < SK_NW; ++w) partner += lds[((w * MG + mb) * 4 + (ip & 3)) * 64 + (ip >> 2) * 16 + col];
+          if constexpr (W8) partner = __fmul_rn(partner, w_scale[n ^ 64]);   // the rotation partner's row: d <-> d + 64 of the same head
           // gemv_kernel's epilogue: rope_kernel's arithmetic on the bf16-rounded projection, at the row's position in its sample
           const int d = n & 63;
           const float c = rope_cos[(long long)row * 64 + d], sn = rope_sin[(long long)row * 64 + d];
@@ -1287,22 +1343,25 @@ extern "C" int mla_attn_chunk_groups_gw(const void* q, const void* k, const void
   return attn_groups_entry("mla_attn_chunk_groups_gw", q, k, v, o, G, H, head_dim, S_p, R, ld, ld_o, scale, gw, order, stream);
 }
 
-extern "C" int mla_gemm_suffix_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
-                                    int rows_per_batch, const int* slot, int cap_rows, const void* residual, long long ld_res, int M, int N, int K,
-                                    const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
-  MLA_CHECK_ARG(x && W && out, "mla_gemm_suffix_bf16: null pointer");
+// mla_gemm_suffix_bf16 / mla_gemm_suffix_w8: one validation + launch path, W8 selects the weight format
+template <bool W8>
+static int suffix_entry(const char* name, const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
+                        long long out_batch_stride, int rows_per_batch, const int* slot, int cap_rows, const void* residual, long long ld_res,
+                        int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
+  constexpr int KQ = W8 ? 16 : 8;                                      // elements per 16-B load of W (fp8: ldw is in bytes)
+  MLA_CHECK_ARG(x && W && out && (!W8 || w_scale), "%s: null pointer", name);
   MLA_CHECK_ARG((rope_cos == nullptr) == (rope_sin == nullptr) && (!rope_cos || (rope_cols > 0 && rope_cols % 128 == 0 && rope_cols <= N && !residual)),
-                "mla_gemm_suffix_bf16: the RoPE epilogue needs both tables, rope_cols a multiple of 128 and <= N, and no residual");
-  MLA_CHECK_ARG(M >= 1 && M <= 256 && N >= 1 && K >= 8 && K % 8 == 0 && rows_per_batch >= 1,
-                "mla_gemm_suffix_bf16: 1 <= M <= 256, K %% 8 == 0 required (M %d, N %d, K %d)", M, N, K);
-  MLA_CHECK_ARG(!slot || cap_rows >= rows_per_batch, "mla_gemm_suffix_bf16: cap_rows (%d) must hold the %d rows of a sample", cap_rows, rows_per_batch);
-  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && ldw % 8 == 0, "mla_gemm_suffix_bf16: x / W rows must be 16-B aligned");
+                "%s: the RoPE epilogue needs both tables, rope_cols a multiple of 128 and <= N, and no residual", name);
+  MLA_CHECK_ARG(M >= 1 && M <= 256 && N >= 1 && K >= KQ && K % KQ == 0 && rows_per_batch >= 1,
+                "%s: 1 <= M <= 256, K %% %d == 0 required (M %d, N %d, K %d)", name, KQ, M, N, K);
+  MLA_CHECK_ARG(!slot || cap_rows >= rows_per_batch, "%s: cap_rows (%d) must hold the %d rows of a sample", name, cap_rows, rows_per_batch);
+  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && ldw % KQ == 0, "%s: x / W rows must be 16-B aligned", name);
   if (!slot) cap_rows = rows_per_batch;
   const int tiles = (N + 15) / 16, blocks = (M + 15) / 16;
 #define MLA_SX_LAUNCH(NT, MB)                                                                                                          \
-  hipLaunchKernelGGL((gemm_suffix_kernel<NT, MB>), dim3((tiles + NT - 1) / NT), dim3(64 * SK_NW), 0, stream, (const bf16_t*)x, ldx,      \
-                     (const bf16_t*)W, ldw, (bf16_t*)out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows, (const bf16_t*)residual,  \
-                     ld_res, M, N, K, rope_cos, rope_sin, rope_cos ? rope_cols : 0)
+  hipLaunchKernelGGL((gemm_suffix_kernel<NT, MB, W8>), dim3((tiles + NT - 1) / NT), dim3(64 * SK_NW), 0, stream, (const bf16_t*)x, ldx,  \
+                     (const typename welem<W8>::t*)W, ldw, w_scale, (bf16_t*)out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows, \
+                     (const bf16_t*)residual, ld_res, M, N, K, rope_cos, rope_sin, rope_cos ? rope_cols : 0)
   if (blocks <= 1) MLA_SX_LAUNCH(1, 1);
   else if (blocks == 2) MLA_SX_LAUNCH(1, 2);
   else if (blocks == 3) MLA_SX_LAUNCH(1, 3);
@@ -1311,5 +1370,20 @@ extern "C" int mla_gemm_suffix_bf16(const void* x, long long ldx, const void* W,
   else if (blocks <= 8) MLA_SX_LAUNCH(2, 8);
   else MLA_SX_LAUNCH(2, 16);
 #undef MLA_SX_LAUNCH
-  MLA_LAUNCH_CHECK();
+  return launch_status(name);
+}
+
+extern "C" int mla_gemm_suffix_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
+                                    int rows_per_batch, const int* slot, int cap_rows, const void* residual, long long ld_res, int M, int N, int K,
+                                    const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
+  return suffix_entry<false>("mla_gemm_suffix_bf16", x, ldx, W, ldw, nullptr, out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows, residual,
+                             ld_res, M, N, K, rope_cos, rope_sin, rope_cols, stream);
+}
+
+extern "C" int mla_gemm_suffix_w8(const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
+                                  long long out_batch_stride, int rows_per_batch, const int* slot, int cap_rows, const void* residual,
+                                  long long ld_res, int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols,
+                                  hipStream_t stream) {
+  return suffix_entry<true>("mla_gemm_suffix_w8", x, ldx, W, ldw, w_scale, out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows, residual,
+                            ld_res, M, N, K, rope_cos, rope_sin, rope_cols, stream);
 }

@@ -52,6 +52,8 @@ _SIGNATURES = {
                                  c_int, c_int, c_void_p],
     "mla_gemm_suffix_bf16": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_int, c_void_p,
                              c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
+    "mla_gemm_suffix_w8": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_int,
+                           c_void_p, c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
     "mla_gemm_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                       c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
     "mla_gemm_bf16_ws": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -930,14 +932,15 @@ def attn_chunk(cache, B, nheads, D, S_kv, R, scale):
 SUFFIX_MMAX = 256
 
 
-def gemm_suffix(x, W, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, rope=None, slot=None, cap_rows=None):
-    """out row m = x[m] @ W^T (+ residual[m]) for 1 <= M <= 256 rows of a batch of samples (mla_gemm_suffix_bf16; plain input only).
-    Row m is row p = m % rows_per_batch of sample b = m // rows_per_batch and lands at out + b * out_batch_stride + (slot[b] + p) * ldo
-    + out_col. slot: int32 [B] device tensor (the sample's prefix length) with cap_rows = rows per sample that `out` (and the tables) hold;
-    None = every slot 0. rope = (cos [cap_rows or rows_per_batch, 64], sin, rope_cols): row slot[b] + p of the tables rotates the row."""
-    name = "gemm_suffix"
+def _suffix_call(sym, name, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows, w_scale=None):
+    """The shared call of the two batched suffix projections; w_scale (fp32 [N]) selects the `_w8` argument list (W: float8_e4m3fn)."""
     _req(x, torch.bfloat16, f"{name} x")
-    _req(W, torch.bfloat16, f"{name} W")
+    _req(W, torch.bfloat16 if w_scale is None else torch.float8_e4m3fn, f"{name} W")
+    scale_arg = ()
+    if w_scale is not None:
+        _req(w_scale, torch.float32, f"{name} w_scale")
+        assert w_scale.numel() == W.shape[0] and w_scale.is_contiguous()
+        scale_arg = (_p(w_scale),)
     _req(out, torch.bfloat16, f"{name} out")
     M, K = x.shape
     N = W.shape[0]
@@ -954,9 +957,25 @@ def gemm_suffix(x, W, out, ldo, out_batch_stride, rows_per_batch, residual=None,
     if residual is not None:
         _req(residual, torch.bfloat16, f"{name} residual")
         assert residual.shape[0] == M and residual.stride(1) == 1
-    call("mla_gemm_suffix_bf16", _p(x), x.stride(0), _p(W), W.stride(0), c_void_p(out.data_ptr() + 2 * out_col), ldo, out_batch_stride,
+    call(sym, _p(x), x.stride(0), _p(W), W.stride(0), *scale_arg, c_void_p(out.data_ptr() + 2 * out_col), ldo, out_batch_stride,
          rows_per_batch, _p(slot), cap, _p(residual), residual.stride(0) if residual is not None else 0, M, N, K,
          _p(rope[0]) if rope is not None else None, _p(rope[1]) if rope is not None else None, int(rope[2]) if rope is not None else 0)
+
+
+def gemm_suffix(x, W, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, rope=None, slot=None, cap_rows=None):
+    """out row m = x[m] @ W^T (+ residual[m]) for 1 <= M <= 256 rows of a batch of samples (mla_gemm_suffix_bf16; plain input only).
+    Row m is row p = m % rows_per_batch of sample b = m // rows_per_batch and lands at out + b * out_batch_stride + (slot[b] + p) * ldo
+    + out_col. slot: int32 [B] device tensor (the sample's prefix length) with cap_rows = rows per sample that `out` (and the tables) hold;
+    None = every slot 0. rope = (cos [cap_rows or rows_per_batch, 64], sin, rope_cols): row slot[b] + p of the tables rotates the row."""
+    _suffix_call("mla_gemm_suffix_bf16", "gemm_suffix", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows)
+
+
+def gemm_suffix_w8(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, rope=None, slot=None, cap_rows=None):
+    """gemm_suffix over FP8 weights (mla_gemm_suffix_w8): W [N, K] float8_e4m3fn, w_scale [N] fp32 as quant_fp8_rows writes them; out row m =
+    w_scale * (x[m] @ float(W)^T) (+ residual[m]), the scale applied to the finished fp32 sum (gemm_skinny_w8's arithmetic: every 64-row
+    slice is bit for bit its output). K % 16 == 0; rows, slots, rope and addressing are gemm_suffix's."""
+    _suffix_call("mla_gemm_suffix_w8", "gemm_suffix_w8", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows,
+                 w_scale)
 
 
 def attn_chunk_ragged(cache, B, nheads, D, kv_len, R, scale):

@@ -15,7 +15,8 @@ kernels' arithmetic as training (RMSNorm and SwiGLU are applied inside the proje
 (5 with the rotary embedding in the QKV kernel's epilogue) are captured once into a HIP graph and replayed per DDIM step.
 
 Opt-in (`suffix_weights="fp8"`, see SUFFIX_WEIGHT_MODES): the sampler steps stream a per-row e4m3fn copy of the projections through
-`mla_gemv_w8` / `mla_gemm_skinny_w8` -- half the weight bytes per step; prefill, activations, cache and attention are untouched.
+`mla_gemv_w8` / `mla_gemm_skinny_w8` (one chunk per call) or `mla_gemm_suffix_w8` (N chunks per observation, SampleGroupsEps) -- half the
+weight bytes per step; prefill, activations, cache and attention are untouched.
 
 Semantics vs the reference: identical arithmetic up to summation order (fp32 accumulation everywhere), with ONE stated difference -- the
 reference's point tokenizer draws fresh random FPS start indices inside every one of the 8 forwards (Point_PN.py:10); here they are
@@ -23,6 +24,7 @@ drawn once per action chunk (the prefix is computed once). With given start indi
 tests/test_inference_gpu.py) the two are the same function."""
 from __future__ import annotations
 
+import functools
 import logging
 import math
 import os
@@ -39,7 +41,8 @@ _LOG = logging.getLogger(__name__)
 # What the suffix pass streams (MLA.predict_action_diff(suffix_weights=...)); the prefill always runs the training kernels on the bf16 weights,
 # so the prefix keys / values keep bf16-weight precision:
 #   "bf16"         the decoder weights as they are (default)
-#   "fp8"          a per-row e4m3fn copy (hip.quant_fp8_rows) through mla_gemv_w8 / mla_gemm_skinny_w8: half the bytes per sampler step
+#   "fp8"          a per-row e4m3fn copy (hip.quant_fp8_rows) through mla_gemv_w8 / mla_gemm_skinny_w8 (PrefixCachedEps) or
+#                  mla_gemm_suffix_w8 (SampleGroupsEps): half the bytes per sampler step
 #   "fp8_as_bf16"  the bf16 kernels on bf16(q * scale): the reference of the "fp8" path, and what the format costs on a checkpoint
 SUFFIX_WEIGHT_MODES = ("bf16", "fp8", "fp8_as_bf16")
 
@@ -511,7 +514,8 @@ class BatchedPrefixCachedEps(_CachedEpsBase):
 # of them, so the encoders and the prefill run once (batch 1, S_p rows) and the cache holds ONE prefix followed by G groups of R suffix
 # rows: [S_p + G R, 3H] per layer. A pass is the batched engine's eight launches over the G R suffix rows, with the projection writing
 # group g's rows at S_p + g R + p (mla_gemm_suffix_bf16 with the "samples" overlapping: batch stride R rows, every slot S_p) and
-# mla_attn_chunk_groups as the attention.
+# mla_attn_chunk_groups as the attention. suffix_weights="fp8" swaps the four projections for mla_gemm_suffix_w8 over the model's FP8 copy
+# (_quantised); the prefill stays on the bf16 weights.
 def plan_sample_groups(num_samples: int, R: int, max_rows: int = 256):
     """Pure host planning: the passes [(start, stop), ...] that serve samples [0, num_samples) in order, at most max_rows // R groups
     (R suffix rows each) per pass."""
@@ -530,41 +534,46 @@ class SampleGroupsEps(_CachedEpsBase):
     (G <= capacity: the sub-batches of a call whose N exceeds a pass share the cache and the prefill) and one captured graph is kept per
     distinct G. Rows of groups >= G are neither written nor read by a pass of G groups."""
 
-    MAX_ROWS = 256                   # suffix rows per pass (mla_gemm_suffix_bf16)
+    MAX_ROWS = 256                   # suffix rows per pass (mla_gemm_suffix_bf16 / mla_gemm_suffix_w8)
     MAX_R = 64                       # rows per group (mla_attn_chunk_groups)
 
     @classmethod
-    def supports_samples(cls, vlm, n_action_rows: int) -> bool:
-        """head_dim 128 and at most 64 suffix rows per sample; otherwise the caller loops over batch-1 calls (warns once per shape)."""
+    def supports_samples(cls, vlm, n_action_rows: int, warn: bool = True) -> bool:
+        """head_dim 128 and at most 64 suffix rows per sample; otherwise the bf16 caller loops over batch-1 calls (warns once per shape;
+        warn=False: the plain predicate, for the callers that raise instead)."""
         cfg = vlm.llm_backbone.llm.config
         R, D = 1 + n_action_rows, cfg.hidden_size // cfg.num_attention_heads
         if R <= cls.MAX_R and D == 128:
             return True
         seen = vlm.__dict__.setdefault("_prefix_unsupported", set())
-        if ("samples", R, D) not in seen:
+        if warn and ("samples", R, D) not in seen:
             seen.add(("samples", R, D))
             warnings.warn(f"SampleGroupsEps: {R} suffix rows per sample (max {cls.MAX_R}) / head_dim {D} (needs 128) are beyond the "
                           "shared-prefix kernels; drawing every sample with its own predict_action_diff call", RuntimeWarning, stacklevel=3)
         return False
 
     @classmethod
-    def for_inputs(cls, vlm, input_ids, n_action_rows: int, num_samples: int, **model_kwargs):
-        """-> (engine, prefilled for this observation; passes [(start, stop), ...] of plan_sample_groups)."""
+    def for_inputs(cls, vlm, input_ids, n_action_rows: int, num_samples: int, suffix_weights: str = "bf16", **model_kwargs):
+        """-> (engine, prefilled for this observation; passes [(start, stop), ...] of plan_sample_groups). One engine -- and its graphs --
+        per suffix_weights mode, as in PrefixCachedEps.for_inputs."""
+        check_suffix_weights(suffix_weights)
         k = PrefixCachedEps._splice_position(input_ids)
         passes = plan_sample_groups(num_samples, 1 + n_action_rows, cls.MAX_ROWS)
         capacity = max(stop - start for start, stop in passes)
         engines = vlm.__dict__.setdefault("_prefix_engines_samples", {})
         key = (k, int(n_action_rows), capacity, str(input_ids.device))
+        if suffix_weights != "bf16":
+            key += (suffix_weights,)                                          # a captured graph holds the addresses of ITS weights
         eng = engines.get(key)
         if eng is None:
             if len(engines) >= 4:
                 engines.pop(next(iter(engines)))
-            eng = engines[key] = cls(vlm, n_action_rows, capacity)
+            eng = engines[key] = cls(vlm, n_action_rows, capacity, suffix_weights)
         eng.prefill(input_ids, k, **model_kwargs)
         return eng, passes
 
-    def __init__(self, vlm, n_action_rows: int, capacity: int):
-        super().__init__(vlm, n_action_rows)
+    def __init__(self, vlm, n_action_rows: int, capacity: int, suffix_weights: str = "bf16"):
+        super().__init__(vlm, n_action_rows, suffix_weights)
         self.capacity = int(capacity)
         self._graphs = {}            # G -> captured pass over G groups
         self._graphs_packed = None   # the packed weights those graphs hold the addresses of
@@ -612,28 +621,37 @@ class SampleGroupsEps(_CachedEpsBase):
             self._graphs[self.B] = self.graph
 
     def _proj(self, x, weights, out=None, residual=None, **kw):
-        wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
-        assert wcat is not None, "the packed weights are adjacent in memory (_weights)"
+        """x [M, K] @ W^T (+ residual): `weights` is a tuple of adjacent bf16 views (mla_gemm_suffix_bf16) or one W8 (mla_gemm_suffix_w8)."""
+        if isinstance(weights, W8):
+            N, gemm = weights.q.shape[0], functools.partial(hip.gemm_suffix_w8, x, weights.q, weights.scale)
+        else:
+            wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
+            assert wcat is not None, "the packed weights are adjacent in memory (_weights)"
+            N, gemm = wcat.shape[0], functools.partial(hip.gemm_suffix, x, wcat)
         M = x.shape[0]
         if out is None:
-            out = torch.empty((M, wcat.shape[0]), dtype=torch.bfloat16, device=x.device)
-            hip.gemm_suffix(x, wcat, out, out.stride(0), 0, M, residual)
+            out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+            gemm(out, out.stride(0), 0, M, residual)
         else:                                                                # group g = "sample" g of the kernel: base row g R, slot S_p
-            hip.gemm_suffix(x, wcat, out, out.stride(0), self.R * out.stride(0), self.R, residual, **kw)
+            gemm(out, out.stride(0), self.R * out.stride(0), self.R, residual, **kw)
         return out
 
     def _suffix_pass(self):
         G, R, H, S_p = self.B, self.R, self.H, self.S_p
         h = self.h_in
         scale = 1.0 / math.sqrt(self.D)
-        for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd), c in zip(self._packed, self.cache):
+        for w, c in zip(self._suffix, self.cache):
+            if self.suffix_weights == "fp8":                                 # _quantised: the packed q|k|v and gate|up as one W8 each
+                ln1, qkv, wo, ln2, gu_w, wd = w
+            else:                                                            # the packed 9-tuple ("bf16") or its dequantised twin
+                ln1, qkv, wo, ln2, gu_w, wd = w[0], w[1:4], w[4:5], w[5], w[6:8], w[8:9]
             xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
             # q|k|v row p of group g -> cache row S_p + g R + p, q and k rotated at position S_p + p in the epilogue
-            self._proj(xn, (wq, wk, wv), out=c, slot=self.slot, cap_rows=S_p + R, rope=(self.cos_c, self.sin_c, 2 * H))
+            self._proj(xn, qkv, out=c, slot=self.slot, cap_rows=S_p + R, rope=(self.cos_c, self.sin_c, 2 * H))
             o = hip.attn_chunk_groups(c, G, self.nheads, self.D, S_p, R, scale)
-            h1 = self._proj(o, (wo,), residual=h)
+            h1 = self._proj(o, wo, residual=h)
             xn2, _ = hip.rmsnorm_fwd(h1, ln2, self.eps)
-            gu = self._proj(xn2, (wg, wu))
-            h = self._proj(hip.swiglu_fwd(gu), (wd,), residual=h1)
+            gu = self._proj(xn2, gu_w)
+            h = self._proj(hip.swiglu_fwd(gu), wd, residual=h1)
         hn, _ = hip.rmsnorm_fwd(h, self.model.norm.weight, self.eps)
         self.h_out.copy_(hn)

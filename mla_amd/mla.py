@@ -467,7 +467,7 @@ class MLA(nn.Module):
                                     unnorm_key: Optional[str] = None, num_samples: int = 1, cfg_scale: float = 0.0, use_ddim: bool = True,
                                     num_ddim_steps: int = 8, action_dim: int = 7, *, input_ids: Optional[torch.Tensor] = None,
                                     noise: Optional[torch.Tensor] = None, camera_name: str = "rlbench_front",
-                                    reuse_prefix: bool = True) -> np.ndarray:
+                                    reuse_prefix: bool = True, suffix_weights: str = "bf16") -> np.ndarray:
         """N action chunks for ONE observation -> [N, T, action_dim]: by definition N independent `predict_action_diff` calls on the same
         observation with the initial samples ``noise[n]`` (critic / best-of-N choice, uncertainty estimates, temporal ensembling), computed
         on ONE cached prefix (mla_amd/infer.py:SampleGroupsEps): the encoders and the decoder prefill run once per call, every sampler step
@@ -476,7 +476,13 @@ class MLA(nn.Module):
         normalisation, un-normalisation) is predict_action_diff's. RNG: the draws of N calls in their order (randn(1, T, D), then the
         unused randint, per sample). ``num_samples=1`` IS predict_action_diff; ``reuse_prefix=False``, head_dim != 128 or more than 64
         suffix rows per sample loop N predict_action_diff calls (a shape reason warns once); more than 256 suffix rows are served as
-        consecutive passes on the same prefill. bf16 weights only."""
+        consecutive passes on the same prefill.
+        ``suffix_weights`` (opt-in): predict_action_diff's modes. "fp8": every pass streams the per-row e4m3fn copy of the decoder weights
+        (mla_gemm_suffix_w8: half the weight bytes per sampler step; the prefill and the prefix keys / values keep the bf16 weights);
+        "fp8_as_bf16": the bf16 kernel on the dequantised copy. Forwarded for ``num_samples=1``. Anything but "bf16" raises ValueError
+        when ``reuse_prefix=False`` or the shared-prefix engine does not serve the shape: no silent bf16 fallback, no silent loop."""
+        from .infer import check_suffix_weights
+        check_suffix_weights(suffix_weights)
         N = int(num_samples)
         T = self.future_action_window_size + 1
         if N < 1:
@@ -490,9 +496,16 @@ class MLA(nn.Module):
                                             action_dim, input_ids=input_ids, noise=None if noise is None else noise[n:n + 1],
                                             camera_name=camera_name, **kw)
         if N == 1:
-            return one(0, reuse_prefix=reuse_prefix)[None]
+            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights)[None]
+        if suffix_weights != "bf16" and not reuse_prefix:
+            raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
+                             "bf16 weights only")
         if reuse_prefix:
             from .infer import SampleGroupsEps
+            if suffix_weights != "bf16" and not SampleGroupsEps.supports_samples(self.vlm, T, warn=False):   # raised, not a warned loop of batch-1 calls
+                raise ValueError(f"suffix_weights={suffix_weights!r}: the shared-prefix engine (SampleGroupsEps) does not serve {1 + T} "
+                                 "suffix rows per sample at this head_dim; draw the samples with \"bf16\" or one predict_action_diff call "
+                                 "each")
             reuse_prefix = SampleGroupsEps.supports_samples(self.vlm, T)
         if not reuse_prefix:
             return np.stack([one(n, reuse_prefix=False) for n in range(N)])
@@ -511,7 +524,7 @@ class MLA(nn.Module):
         x0 = torch.cat(draws, dim=0).float()
         if use_ddim and num_ddim_steps is not None and self.ddim_diffusion is None:
             self.create_ddim(ddim_step=num_ddim_steps)
-        eng, passes = SampleGroupsEps.for_inputs(self.vlm, input_ids, T, N, **model_kwargs)
+        eng, passes = SampleGroupsEps.for_inputs(self.vlm, input_ids, T, N, suffix_weights=suffix_weights, **model_kwargs)
         out = []
         for start, stop in passes:                                           # one prefill, then the passes' sampler loops one after the other
             eng.set_groups(stop - start)

@@ -18,6 +18,11 @@
                                                           copies of the observation, (c) N sequential predict_action_diff calls;
                                                           --kernel-table adds mla_attn_chunk_groups alone at 1 / 2 / 4 groups per workgroup
                                                           against mla_attn_chunk_ragged on N copies of the prefix
+    python tools/bench_infer.py --samples N[,N..] --pair-fp8 [--chunks C[,C..]] [--pairs P] [--kernel-table]
+                                                          predict_action_diff_samples with bf16 and fp8 suffix weights alternating in one
+                                                          process, in pairs: per-call latency and the suffix pass alone with the 95 %
+                                                          interval of the pair differences; --kernel-table adds mla_gemm_suffix_w8 against
+                                                          mla_gemm_suffix_bf16 per 7B projection shape at M = 34, 68, 136, 255
 Prints one JSON line per measurement (not the driver's bench contract -- that is bench.py)."""
 import argparse
 import json
@@ -47,7 +52,7 @@ def main():
     ap.add_argument("--chunks", type=str, default="", help="with --samples: action chunk lengths to measure in one process (default: --chunk)")
     args = ap.parse_args()
     if args.samples:
-        return main_samples(args)
+        return main_samples_pair(args) if args.pair_fp8 else main_samples(args)
     if args.batch > 0:
         return main_batch(args)
     if args.pair_fp8:
@@ -323,6 +328,129 @@ def main_samples(args):
                               "samples_engine_graph": bool(eng is not None and eng.graph is not None), "data": "synthetic"}), flush=True)
             for store in ("_prefix_engines_samples", "_prefix_engines_batched"):   # the caches of this (N, chunk): 6.5 GB at N = 15 for (b)
                 m.vlm.__dict__.get(store, {}).clear()
+            torch.cuda.empty_cache()
+
+
+def _suffix_kernel_table(m, dev, Ms=(34, 68, 136, 255), rounds=3, reps=3):
+    """mla_gemm_suffix_w8 against mla_gemm_suffix_bf16 per projection shape of a 7B layer (plain input, as SampleGroupsEps launches them),
+    cycling through the 32 layers' weights (nothing stays in the caches), captured into a graph; the arms alternate, us per launch, the
+    minimum over `rounds`."""
+    from mla_amd import hip, ops
+    assert "_prefix_fp8" in m.vlm.__dict__ and "_prefix_packed" in m.vlm.__dict__, "call the model with \"bf16\" and \"fp8\" first: they build the copies"
+    fp8 = m.vlm.__dict__["_prefix_fp8"]["fp8"]
+    packed = m.vlm.__dict__["_prefix_packed"]["packed"]
+    bf16 = [(ops.cat_view(w[1:4]), w[4], ops.cat_view(w[6:8]), w[8]) for w in packed]
+    names = ("qkv", "o(res)", "gate_up", "down(res)")
+    table = {}
+    for M in Ms:
+        row = {}
+        for i, (name, idx) in enumerate(zip(names, (1, 2, 4, 5))):
+            N, K = fp8[0][idx].q.shape
+            x = (torch.randn(M, K, device=dev) * 0.5).to(torch.bfloat16)
+            res = torch.randn(M, N, device=dev).to(torch.bfloat16) if "res" in name else None
+            o = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
+            arms = {"bf16": lambda: [hip.gemm_suffix(x, L[i], o, N, 0, M, res) for L in bf16],
+                    "w8": lambda: [hip.gemm_suffix_w8(x, L[idx].q, L[idx].scale, o, N, 0, M, res) for L in fp8]}
+            graphs = {}
+            for k, fn in arms.items():
+                fn()
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    fn()
+                g.replay()
+                graphs[k] = g
+            us = {k: [] for k in arms}
+            for _ in range(rounds):
+                for k, g in graphs.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _rep in range(reps):
+                        g.replay()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    us[k].append(e0.elapsed_time(e1) / (reps * len(fp8)) * 1e3)
+            row[name] = {k: round(min(v), 1) for k, v in us.items()}
+        table[f"M{M}"] = row
+    return table
+
+
+def main_samples_pair(args):
+    from bench import build
+    from mla_amd.infer import SampleGroupsEps
+    from mla_amd.synthetic import make_batch
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    Ns = [int(v) for v in args.samples.split(",")]
+    chunks = [int(v) for v in args.chunks.split(",")] if args.chunks else [args.chunk]
+    m = build(dev, 1)
+    m.eval()
+    for p in m.parameters():
+        p.data = p.data.to(torch.bfloat16)
+    b = make_batch(B=1, device=dev)
+    ids = torch.cat([b["input_ids"][:, :-4], torch.tensor([[29871]], device=dev)], dim=1)
+    image, pc, state = b["images"]["front_image"][0], b["point_cloud"][0], b["proprio"][0, 0].cpu().numpy()
+    mk = dict(images=b["images"]["front_image"][:1], point_cloud=b["point_cloud"][:1], camera_name="rlbench_front", proprio=b["proprio"][:1])
+    modes = ("bf16", "fp8")
+    table_done = not args.kernel_table
+    for chunk in chunks:
+        m.future_action_window_size = m.vlm.future_action_window_size = chunk - 1
+        for N in Ns:
+            noise = torch.randn(N, chunk, 7, device=dev)
+            t91 = torch.full((N,), 91, device=dev)
+
+            def call(mode):
+                return m.predict_action_diff_samples(image, pc, cur_robot_state=state, num_samples=N, input_ids=ids, noise=noise,
+                                                     num_ddim_steps=args.steps, suffix_weights=mode)
+
+            def call_ms(mode):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.iters):
+                    call(mode)
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / args.iters * 1e3
+
+            def pass_ms(mode):
+                with torch.inference_mode():
+                    eng, passes = SampleGroupsEps.for_inputs(m.vlm, ids, chunk, N, suffix_weights=mode, **mk)
+                    assert len(passes) == 1, "one pass per sampler step: N * (chunk + 1) <= 256"
+                    eng.set_groups(N)
+                    eng(noise, t91)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(8):
+                        eng._run()
+                    e1.record()
+                    torch.cuda.synchronize()
+                return e0.elapsed_time(e1) / 8, eng.graph is not None
+            outs = {mode: call(mode) for mode in modes}                       # engines, graphs, packed + quantised weights
+            if not table_done:
+                print(json.dumps({"metric": "mla_gemm_suffix_w8 vs mla_gemm_suffix_bf16 per 7B projection shape, one launch per layer's weights",
+                                  "unit": "us", "table": _suffix_kernel_table(m, dev), "data": "synthetic"}), flush=True)
+                table_done = True
+            total = {mode: [] for mode in modes}
+            suffix = {mode: [] for mode in modes}
+            graphs = {}
+            for _ in range(args.pairs):                                       # bf16, fp8, bf16, fp8, ...: same box, interleaved
+                for mode in modes:
+                    total[mode].append(call_ms(mode))
+                for mode in modes:
+                    ms, graphs[mode] = pass_ms(mode)
+                    suffix[mode].append(ms)
+            rel = float(((outs["fp8"] - outs["bf16"]) ** 2).sum() ** 0.5 / (outs["bf16"] ** 2).sum() ** 0.5)
+            print(json.dumps({"metric": "predict_action_diff_samples, MLA-Llama2-7B: bf16 vs fp8 suffix weights in alternating pairs",
+                              "samples": N, "action_chunk": chunk, "suffix_rows": N * (chunk + 1), "ddim_steps": args.steps, "pairs": args.pairs,
+                              "iters_per_timing": args.iters, "unit": "ms",
+                              "call_ms": {k: [round(v, 2) for v in vs] for k, vs in total.items()},
+                              "call_fp8_minus_bf16": _pair_stats(total["bf16"], total["fp8"]),
+                              "call_fp8_minus_bf16_per_sample": round(_pair_stats(total["bf16"], total["fp8"])["mean_diff"] / N, 3),
+                              "suffix_pass_ms": {k: [round(v, 3) for v in vs] for k, vs in suffix.items()},
+                              "suffix_pass_fp8_minus_bf16": _pair_stats(suffix["bf16"], suffix["fp8"]),
+                              "weights_streamed_per_pass_gb": {k: round(_stream_bytes(m, k) / 1e9, 2) for k in modes},
+                              "suffix_pass_weight_stream_tbps": {k: round(_stream_bytes(m, k) / 1e12 / (min(suffix[k]) * 1e-3), 2) for k in modes},
+                              "engine_graph": graphs, "fp8_vs_bf16_rel_diff_random_weights": round(rel, 4), "data": "synthetic"}), flush=True)
+            m.vlm.__dict__.get("_prefix_engines_samples", {}).clear()         # the caches of this (N, chunk)
             torch.cuda.empty_cache()
 
 
