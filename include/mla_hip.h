@@ -362,6 +362,39 @@ int mla_attn_chunk_groups(const void* q, const void* k, const void* v, void* o, 
                           long long ld_o, float scale, mla_stream_t stream);
 int mla_attn_chunk_groups_gw(const void* q, const void* k, const void* v, void* o, int G, int H, int head_dim, int S_p, int R, long long ld,
                              long long ld_o, float scale, int gw, int order, mla_stream_t stream);
+/* ---- N action chunks for each of B observations (mla_amd/infer.py BatchedSampleGroupsEps): the two forms above composed. The cache is
+ * [B, S_cap, 3 H] (row stride ld, sample stride batch_stride); in sample b rows [0, S_p[b]) are its prefix and row S_p[b] + g * R + p is
+ * suffix row p of group g; rows behind S_p[b] + G * R are never read. All per-sample lengths are DEVICE arrays.
+ * mla_attn_chunk_ragged_groups: mla_attn_chunk_groups per sample with S_p[b] = clamp(prefix_len[b], 0, S_cap - G * R), prefix_len int32 [B]
+ *   on the device (S_cap >= G * R: the clamp keeps every read inside the sample's S_cap rows). Query (b, g, p) sees the logical keys
+ *   0 .. S_p[b] + p of its sample, logical key j being memory row j (j < S_p[b]) or j + g * R; output row (b * G + g) * R + p of o.
+ *   1 <= R <= 64, G >= 1, B >= 1, head_dim 128. One workgroup serves one sample and derives the clamped S_p[b] once, wave-uniformly; the
+ *   grid (B * H * ceil(G / gw) * ceil(R / 16)) and the LDS do not depend on the lengths: graph-capturable for any mix of them. The rows
+ *   of (b, g) are bit for bit mla_attn_chunk with B = 1 and S_kv = S_p[b] + R on cat(prefix rows of b, rows of group g) -- equivalently
+ *   mla_attn_chunk_groups on sample b's slice with S_p = S_p[b]. No output depends on another group's rows, another sample's rows or the
+ *   tail rows [S_p[b] + G * R, S_cap) of its own sample. No allocation, no atomics, no workspace.
+ * mla_attn_chunk_ragged_groups_gw: the same with mla_attn_chunk_groups_gw's launch form arguments (same bits for every form).
+ * mla_gemm_suffix_bf16_pos / mla_gemm_suffix_w8_pos: mla_gemm_suffix_bf16 / _w8 with the rotary position separated from the cache row:
+ *   row m = (s, p) (s = m / rows_per_batch) is written at row slot[s] + p as there (rows outside [0, cap_rows) are not written) and, with
+ *   the RoPE epilogue, rotated with table row rope_pos[s] + p of rope_cos / rope_sin ([rope_rows, 64] fp32); rope_pos: int32
+ *   [ceil(M / rows_per_batch)] on the device. A row whose position falls outside [0, rope_rows) is not written (no column of it).
+ *   rope_pos == NULL is mla_gemm_suffix_bf16 / _w8 itself (same kernel, same bits; rope_rows ignored). The engine's addressing: out the
+ *   flat [B * S_cap, 3 H] cache with out_batch_stride 0, s = b * G + g, slot[s] = b * S_cap + S_p[b] + g * R, cap_rows = B * S_cap,
+ *   rope_pos[s] = S_p[b], rope_rows = S_cap. */
+int mla_attn_chunk_ragged_groups(const void* q, const void* k, const void* v, void* o, int B, int G, int H, int head_dim,
+                                 const int* prefix_len, int S_cap, int R, long long ld, long long batch_stride, long long ld_o, float scale,
+                                 mla_stream_t stream);
+int mla_attn_chunk_ragged_groups_gw(const void* q, const void* k, const void* v, void* o, int B, int G, int H, int head_dim,
+                                    const int* prefix_len, int S_cap, int R, long long ld, long long batch_stride, long long ld_o, float scale,
+                                    int gw, int order, mla_stream_t stream);
+int mla_gemm_suffix_bf16_pos(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
+                             int rows_per_batch, const int* slot, int cap_rows, const void* residual, long long ld_res, int M, int N, int K,
+                             const float* rope_cos, const float* rope_sin, int rope_cols, const int* rope_pos, int rope_rows,
+                             mla_stream_t stream);
+int mla_gemm_suffix_w8_pos(const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
+                           long long out_batch_stride, int rows_per_batch, const int* slot, int cap_rows, const void* residual,
+                           long long ld_res, int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols,
+                           const int* rope_pos, int rope_rows, mla_stream_t stream);
 
 /* ---- losses: CrossEntropyLoss modeling_llama.py:1258-1269; InfoNCE models/mla/fuser/contrastive.py:208-215
  * mla_ce_fwd: lse[r] = logsumexp(logits[r, :ncols]), loss[r] = lse - logits[r, label] (0 for ignore_index or a label outside [0, ncols);

@@ -22,6 +22,9 @@
 //   mla_gemm_suffix_w8  the third projection contract (1 <= M <= 256 plain rows, ragged / groups slot addressing) over the same FP8 weights:
 //                      gemm_suffix_kernel with W8 = true -- the skinny W8 kernel's 64-wide K steps, wave split and summation order, so every
 //                      64-row slice is bit for bit mla_gemm_skinny_w8's output; serves N action chunks per observation (SampleGroupsEps).
+//   mla_attn_chunk_ragged_groups  mla_attn_chunk_groups for B samples, each with its own prefix length read from a device array;
+//                      mla_gemm_suffix_bf16_pos / _w8_pos write its rows: the cache row and the rotary position come from two arrays
+//                      (N action chunks for each of B observations, BatchedSampleGroupsEps).
 // infer.py keeps gemv / decode for every shape they accept and uses the other two beyond (action chunks of 8..63 steps); the last two
 // serve batched sampling (B observations with prompts of different lengths on one pass).
 // All are HBM-bound by construction: algorithmic bytes = the weight matrix (gemv) / the K and V rows of the head (decode).
@@ -628,8 +631,9 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* _
 //   NT  16-row W tiles per workgroup (NT A fragments per K step: x is re-read from L2 once per NT * 16 W rows instead of once per 16),
 //   MB  16-row x blocks (up to 16: 256 rows),
 //   ragged addressing: row m is row p = m % rpb of sample b = m / rpb and goes to cache row slot[b] + p of that sample (out + b * out_bs +
-//   (slot[b] + p) * ldo), rotated with table row slot[b] + p; slot lives on the device, so a captured graph serves any mix of prefix
-//   lengths. Rows outside [0, cap_rows) are not written.
+//   (slot[b] + p) * ldo), rotated with table row slot[b] + p (or rope_pos[b] + p where the rotary position is not the cache row: the
+//   groups of several samples, BatchedSampleGroupsEps); slot and rope_pos live on the device, so a captured graph serves any mix of prefix
+//   lengths. Rows outside [0, cap_rows), and positions outside [0, rope_rows), are not written.
 // Every W fragment is loaded by exactly one wave of one workgroup: each weight byte is requested once per call.
 // NT = 1 (M <= 64) is gemm_skinny_kernel<MB, 0>'s arithmetic: the same K ranges per wave, the same MFMA order inside a wave, the same
 // fixed-order sum over the 8 waves -> bit-identical outputs. The partial tiles go through LDS one W tile and at most 8 x blocks at a
@@ -646,7 +650,8 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* _
                                                                  bf16_t* __restrict__ out, long long ldo, long long out_bs, int rpb,
                                                                  const int* __restrict__ slot, int cap_rows, const bf16_t* __restrict__ res,
                                                                  long long ld_res, int M, int N, int K, const float* __restrict__ rope_cos,
-                                                                 const float* __restrict__ rope_sin, int rope_cols) {
+                                                                 const float* __restrict__ rope_sin, int rope_cols,
+                                                                 const int* __restrict__ rope_pos, int rope_rows) {
   constexpr int NL = NT + MB;                                          // 16-B loads per lane and K step
   constexpr int U = NL <= 3 ? 8 : (NL <= 5 ? 4 : (NL <= 10 ? 2 : 1));  // K steps whose loads are issued before the first MFMA
   constexpr int MG = MB < 8 ? MB : 8;                                  // x blocks per epilogue round
@@ -765,6 +770,10 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* _
         const int sb = m / rpb, p = m - sb * rpb;
         const int row = (slot ? slot[sb] : 0) + p;
         if (row < 0 || row >= cap_rows) continue;
+        // rope_pos (the _pos entry points): the table row is rope_pos[sb] + p instead of the cache row -- several groups of suffix rows
+        // behind one prefix sit at different rows but share their positions; a position outside the tables writes nothing
+        const int pos = rope_pos ? rope_pos[sb] + p : row;
+        if (rope_pos && (pos < 0 || pos >= rope_rows)) continue;
         float v = 0.f, partner = 0.f;
 #pragma unroll
         for (int w = 0; w < SK_NW; ++w) v += lds[((w * MG + mb) * 4 + (i & 3)) * 64 + (i >> 2) * 16 + col];
@@ -777,7 +786,7 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* _
           if constexpr (W8) partner = __fmul_rn(partner, w_scale[n ^ 64]);   // the rotation partner's row: d <-> d + 64 of the same head
           // gemv_kernel's epilogue: rope_kernel's arithmetic on the bf16-rounded projection, at the row's position in its sample
           const int d = n & 63;
-          const float c = rope_cos[(long long)row * 64 + d], sn = rope_sin[(long long)row * 64 + d];
+          const float c = rope_cos[(long long)pos * 64 + d], sn = rope_sin[(long long)pos * 64 + d];
           const float me = bf2f(f2bf(v)), other = bf2f(f2bf(partner));
           v = i < 8 ? fmaf(me, c, -(other * sn)) : fmaf(me, c, other * sn);
         }
@@ -946,17 +955,29 @@ __global__ __launch_bounds__(64 * CH_NW) void attn_chunk_kernel(const bf16_t* __
 // the query's OWN group, so no output depends on another group's rows. Groups beyond G (G % GW != 0) recompute group G - 1 and store nothing.
 constexpr int ATTN_GROUPS_GW = 1;                                      // groups per workgroup mla_attn_chunk_groups launches
 constexpr int ATTN_GROUPS_XCD_CHUNKS = 0;                              // its work order: 0 as dispatched, 1 one chunk of the grid per XCD
-template <int GW>
+// RAGGED (mla_attn_chunk_ragged_groups): B samples of G groups each, [B, S_cap, 3H] with sample stride bs; the work order gets the sample
+// as its slowest index and S_p comes from prefix_len[b] on the device, clamped to [0, S_cap - G R] (the rows the caller owns). One
+// workgroup serves one sample, so the clamped S_p -- and with it the trip count, the barrier count and `shared` -- is the same in every
+// wave (readfirstlane keeps it in a scalar register). Everything behind that line is the same code: sample b's rows are bit for bit the
+// plain launch on its slice with S_p = S_p[b], the grid does not depend on the lengths and a captured graph serves any mix of them.
+template <int GW, bool RAGGED>
 __global__ __launch_bounds__(64 * CH_NW) void attn_chunk_groups_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                                        const bf16_t* __restrict__ v, bf16_t* __restrict__ o, int G, int H,
-                                                                       int S_p, int R, long long ld, long long ld_o, float scale, int xcd_chunks) {
+                                                                       int S_p, int R, long long ld, long long ld_o, float scale, int xcd_chunks,
+                                                                       const int* __restrict__ prefix_len, int S_cap, long long bs) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int QB = (R + 15) >> 4, NGB = (G + GW - 1) / GW;
   // head-major work order: the workgroups of one head (its 2 S_p x 128 prefix K / V elements) are neighbours. Blocks are dealt out
   // round-robin over the 8 XCDs (observed, not a contract: only speed depends on it), so with xcd_chunks (host: grid % 8 == 0) block b
   // takes work item (b % 8) * (grid / 8) + b / 8 -- a bijection -- and the neighbours share one XCD's L2 instead of eight.
   const int bid = xcd_chunks ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-  const int qb = bid % QB, gb = (bid / QB) % NGB, h = bid / (QB * NGB);
+  const int qb = bid % QB, gb = (bid / QB) % NGB, h = RAGGED ? (bid / (QB * NGB)) % H : bid / (QB * NGB);
+  const int b = RAGGED ? bid / (QB * NGB * H) : 0;
+  if (RAGGED) {
+    const int n = prefix_len[b], room = S_cap - G * R;                  // host: room >= 0
+    S_p = __builtin_amdgcn_readfirstlane(n < 0 ? 0 : (n > room ? room : n));
+    q += b * bs; k += b * bs; v += b * bs;
+  }
   const int S_kv = S_p + R;                                             // logical keys of a group
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
   bf16_t* vt = (bf16_t*)smem + wave * 128 * CH_VP;
@@ -1092,7 +1113,7 @@ __global__ __launch_bounds__(64 * CH_NW) void attn_chunk_groups_kernel(const bf1
         L += fw * ml[CH_NW * 16 + w * 16 + qq];
         O += fw * mo[(w * 128 + d) * 16 + qq];
       }
-      o[(long long)(gg * R + rq) * ld_o + h * 128 + d] = f2bf(O / L);
+      o[(long long)((b * G + gg) * R + rq) * ld_o + h * 128 + d] = f2bf(O / L);
     }
     if (gi + 1 < GW) __syncthreads();
   }
@@ -1306,13 +1327,23 @@ extern "C" int mla_attn_chunk_ragged(const void* q, const void* k, const void* v
   MLA_LAUNCH_CHECK();
 }
 
-// mla_attn_chunk_groups / mla_attn_chunk_groups_gw: one validation + launch path; gw = groups per workgroup (0: the library's choice)
-static int attn_groups_entry(const char* name, const void* q, const void* k, const void* v, void* o, int G, int H, int head_dim, int S_p, int R,
-                             long long ld, long long ld_o, float scale, int gw, int order, hipStream_t stream) {
+// mla_attn_chunk_groups(_gw) / mla_attn_chunk_ragged_groups(_gw): one validation + launch path; gw = groups per workgroup (0: the library's
+// choice). prefix_len != nullptr selects the ragged form: B samples, S_p_or_cap is then S_cap, the rows per sample.
+static int attn_groups_entry(const char* name, const void* q, const void* k, const void* v, void* o, int B, int G, int H, int head_dim,
+                             const int* prefix_len, int S_p_or_cap, int R, long long ld, long long bs, long long ld_o, float scale, int gw,
+                             int order, hipStream_t stream) {
+  const bool ragged = prefix_len != nullptr;
   MLA_CHECK_ARG(q && k && v && o, "%s: null pointer", name);
   MLA_CHECK_ARG(head_dim == 128, "%s: head_dim must be 128 (got %d)", name, head_dim);
-  MLA_CHECK_ARG(G >= 1 && H >= 1 && R >= 1 && R <= CH_RMAX && S_p >= 0, "%s: G >= 1, 1 <= R <= 64, S_p >= 0 required (G %d, R %d, S_p %d)", name, G, R, S_p);
-  MLA_CHECK_ARG((long long)S_p + (long long)G * R <= 0x7fffffffLL, "%s: S_p + G * R rows exceed the int range (G %d, R %d, S_p %d)", name, G, R, S_p);
+  MLA_CHECK_ARG(B >= 1 && G >= 1 && H >= 1 && R >= 1 && R <= CH_RMAX, "%s: B >= 1, G >= 1, 1 <= R <= 64 required (B %d, G %d, R %d)", name, B, G, R);
+  if (ragged) {
+    MLA_CHECK_ARG((long long)G * R <= (long long)S_p_or_cap, "%s: S_cap (%d) must hold the G * R suffix rows of a sample (G %d, R %d)", name,
+                  S_p_or_cap, G, R);
+    MLA_CHECK_ARG((long long)B * G * R <= 0x7fffffffLL && bs % 8 == 0, "%s: B * G * R output rows exceed the int range, or the sample stride is not 16-B aligned", name);
+  } else {
+    MLA_CHECK_ARG(S_p_or_cap >= 0, "%s: S_p >= 0 required (S_p %d)", name, S_p_or_cap);
+    MLA_CHECK_ARG((long long)S_p_or_cap + (long long)G * R <= 0x7fffffffLL, "%s: S_p + G * R rows exceed the int range (G %d, R %d, S_p %d)", name, G, R, S_p_or_cap);
+  }
   MLA_CHECK_ARG(AL16(q) && AL16(k) && AL16(v) && ld % 8 == 0 && ld_o % 2 == 0, "%s: 16-B aligned rows required", name);
   MLA_CHECK_ARG(gw == 0 || gw == 1 || gw == 2 || gw == 4, "%s: groups per workgroup must be 0 (default), 1, 2 or 4 (got %d)", name, gw);
   MLA_CHECK_ARG(order >= -1 && order <= 1, "%s: order must be -1 (default), 0 (as dispatched) or 1 (one chunk of the grid per XCD) (got %d)", name, order);
@@ -1320,34 +1351,59 @@ static int attn_groups_entry(const char* name, const void* q, const void* k, con
   if (order < 0) order = ATTN_GROUPS_XCD_CHUNKS;
   const size_t lds = (size_t)CH_NW * 128 * CH_VP * 2;                  // >= the merge buffers, as in mla_attn_chunk
   const int QB = (R + 15) / 16;
-  const int xcd_chunks = order == 1 && (H * ((G + gw - 1) / gw) * QB) % 8 == 0;
-#define MLA_AG_LAUNCH(GW)                                                                                                              \
+  const long long grid = (long long)B * H * ((G + gw - 1) / gw) * QB;
+  MLA_CHECK_ARG(grid <= 0x7fffffffLL, "%s: %lld workgroups exceed the grid range", name, grid);
+  const int xcd_chunks = order == 1 && grid % 8 == 0;
+#define MLA_AG_LAUNCH(GW, RG)                                                                                                          \
   {                                                                                                                                    \
     static bool attr = false;                                                                                                          \
-    if (!attr) { (void)hipFuncSetAttribute((const void*)attn_chunk_groups_kernel<GW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; } \
-    hipLaunchKernelGGL(attn_chunk_groups_kernel<GW>, dim3(H * ((G + GW - 1) / GW) * QB), dim3(64 * CH_NW), lds, stream, (const bf16_t*)q,   \
-                       (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, G, H, S_p, R, ld, ld_o, scale, xcd_chunks);                       \
+    if (!attr) { (void)hipFuncSetAttribute((const void*)attn_chunk_groups_kernel<GW, RG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; } \
+    hipLaunchKernelGGL((attn_chunk_groups_kernel<GW, RG>), dim3((unsigned)grid), dim3(64 * CH_NW), lds, stream, (const bf16_t*)q,       \
+                       (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, G, H, RG ? 0 : S_p_or_cap, R, ld, ld_o, scale, xcd_chunks,         \
+                       prefix_len, RG ? S_p_or_cap : 0, RG ? bs : 0LL);                                                                 \
   }
-  if (gw == 1) MLA_AG_LAUNCH(1) else if (gw == 2) MLA_AG_LAUNCH(2) else MLA_AG_LAUNCH(4)
+  if (ragged) {
+    if (gw == 1) MLA_AG_LAUNCH(1, true) else if (gw == 2) MLA_AG_LAUNCH(2, true) else MLA_AG_LAUNCH(4, true)
+  } else {
+    if (gw == 1) MLA_AG_LAUNCH(1, false) else if (gw == 2) MLA_AG_LAUNCH(2, false) else MLA_AG_LAUNCH(4, false)
+  }
 #undef MLA_AG_LAUNCH
   return launch_status(name);
 }
 
 extern "C" int mla_attn_chunk_groups(const void* q, const void* k, const void* v, void* o, int G, int H, int head_dim, int S_p, int R, long long ld,
                                      long long ld_o, float scale, hipStream_t stream) {
-  return attn_groups_entry("mla_attn_chunk_groups", q, k, v, o, G, H, head_dim, S_p, R, ld, ld_o, scale, 0, -1, stream);
+  return attn_groups_entry("mla_attn_chunk_groups", q, k, v, o, 1, G, H, head_dim, nullptr, S_p, R, ld, 0, ld_o, scale, 0, -1, stream);
 }
 
 extern "C" int mla_attn_chunk_groups_gw(const void* q, const void* k, const void* v, void* o, int G, int H, int head_dim, int S_p, int R,
                                         long long ld, long long ld_o, float scale, int gw, int order, hipStream_t stream) {
-  return attn_groups_entry("mla_attn_chunk_groups_gw", q, k, v, o, G, H, head_dim, S_p, R, ld, ld_o, scale, gw, order, stream);
+  return attn_groups_entry("mla_attn_chunk_groups_gw", q, k, v, o, 1, G, H, head_dim, nullptr, S_p, R, ld, 0, ld_o, scale, gw, order, stream);
 }
 
-// mla_gemm_suffix_bf16 / mla_gemm_suffix_w8: one validation + launch path, W8 selects the weight format
+extern "C" int mla_attn_chunk_ragged_groups(const void* q, const void* k, const void* v, void* o, int B, int G, int H, int head_dim,
+                                            const int* prefix_len, int S_cap, int R, long long ld, long long batch_stride, long long ld_o,
+                                            float scale, hipStream_t stream) {
+  MLA_CHECK_ARG(prefix_len, "mla_attn_chunk_ragged_groups: null pointer");
+  return attn_groups_entry("mla_attn_chunk_ragged_groups", q, k, v, o, B, G, H, head_dim, prefix_len, S_cap, R, ld, batch_stride, ld_o, scale, 0,
+                           -1, stream);
+}
+
+extern "C" int mla_attn_chunk_ragged_groups_gw(const void* q, const void* k, const void* v, void* o, int B, int G, int H, int head_dim,
+                                               const int* prefix_len, int S_cap, int R, long long ld, long long batch_stride, long long ld_o,
+                                               float scale, int gw, int order, hipStream_t stream) {
+  MLA_CHECK_ARG(prefix_len, "mla_attn_chunk_ragged_groups_gw: null pointer");
+  return attn_groups_entry("mla_attn_chunk_ragged_groups_gw", q, k, v, o, B, G, H, head_dim, prefix_len, S_cap, R, ld, batch_stride, ld_o, scale,
+                           gw, order, stream);
+}
+
+// mla_gemm_suffix_bf16(_pos) / mla_gemm_suffix_w8(_pos): one validation + launch path, W8 selects the weight format; rope_pos == nullptr
+// is the form without a separate rotary position (the table row is the cache row)
 template <bool W8>
 static int suffix_entry(const char* name, const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
                         long long out_batch_stride, int rows_per_batch, const int* slot, int cap_rows, const void* residual, long long ld_res,
-                        int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
+                        int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols, const int* rope_pos, int rope_rows,
+                        hipStream_t stream) {
   constexpr int KQ = W8 ? 16 : 8;                                      // elements per 16-B load of W (fp8: ldw is in bytes)
   MLA_CHECK_ARG(x && W && out && (!W8 || w_scale), "%s: null pointer", name);
   MLA_CHECK_ARG((rope_cos == nullptr) == (rope_sin == nullptr) && (!rope_cos || (rope_cols > 0 && rope_cols % 128 == 0 && rope_cols <= N && !residual)),
@@ -1355,13 +1411,14 @@ static int suffix_entry(const char* name, const void* x, long long ldx, const vo
   MLA_CHECK_ARG(M >= 1 && M <= 256 && N >= 1 && K >= KQ && K % KQ == 0 && rows_per_batch >= 1,
                 "%s: 1 <= M <= 256, K %% %d == 0 required (M %d, N %d, K %d)", name, KQ, M, N, K);
   MLA_CHECK_ARG(!slot || cap_rows >= rows_per_batch, "%s: cap_rows (%d) must hold the %d rows of a sample", name, cap_rows, rows_per_batch);
+  MLA_CHECK_ARG(!rope_pos || (rope_cos && rope_rows >= 1), "%s: rope_pos needs the RoPE tables and rope_rows >= 1 (got %d)", name, rope_rows);
   MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && ldw % KQ == 0, "%s: x / W rows must be 16-B aligned", name);
   if (!slot) cap_rows = rows_per_batch;
   const int tiles = (N + 15) / 16, blocks = (M + 15) / 16;
 #define MLA_SX_LAUNCH(NT, MB)                                                                                                          \
   hipLaunchKernelGGL((gemm_suffix_kernel<NT, MB, W8>), dim3((tiles + NT - 1) / NT), dim3(64 * SK_NW), 0, stream, (const bf16_t*)x, ldx,  \
                      (const typename welem<W8>::t*)W, ldw, w_scale, (bf16_t*)out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows, \
-                     (const bf16_t*)residual, ld_res, M, N, K, rope_cos, rope_sin, rope_cos ? rope_cols : 0)
+                     (const bf16_t*)residual, ld_res, M, N, K, rope_cos, rope_sin, rope_cos ? rope_cols : 0, rope_pos, rope_rows)
   if (blocks <= 1) MLA_SX_LAUNCH(1, 1);
   else if (blocks == 2) MLA_SX_LAUNCH(1, 2);
   else if (blocks == 3) MLA_SX_LAUNCH(1, 3);
@@ -1377,7 +1434,15 @@ extern "C" int mla_gemm_suffix_bf16(const void* x, long long ldx, const void* W,
                                     int rows_per_batch, const int* slot, int cap_rows, const void* residual, long long ld_res, int M, int N, int K,
                                     const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
   return suffix_entry<false>("mla_gemm_suffix_bf16", x, ldx, W, ldw, nullptr, out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows, residual,
-                             ld_res, M, N, K, rope_cos, rope_sin, rope_cols, stream);
+                             ld_res, M, N, K, rope_cos, rope_sin, rope_cols, nullptr, 0, stream);
+}
+
+extern "C" int mla_gemm_suffix_bf16_pos(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo,
+                                        long long out_batch_stride, int rows_per_batch, const int* slot, int cap_rows, const void* residual,
+                                        long long ld_res, int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols,
+                                        const int* rope_pos, int rope_rows, hipStream_t stream) {
+  return suffix_entry<false>("mla_gemm_suffix_bf16_pos", x, ldx, W, ldw, nullptr, out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows,
+                             residual, ld_res, M, N, K, rope_cos, rope_sin, rope_cols, rope_pos, rope_rows, stream);
 }
 
 extern "C" int mla_gemm_suffix_w8(const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
@@ -1385,5 +1450,13 @@ extern "C" int mla_gemm_suffix_w8(const void* x, long long ldx, const void* W, l
                                   long long ld_res, int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols,
                                   hipStream_t stream) {
   return suffix_entry<true>("mla_gemm_suffix_w8", x, ldx, W, ldw, w_scale, out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows, residual,
-                            ld_res, M, N, K, rope_cos, rope_sin, rope_cols, stream);
+                            ld_res, M, N, K, rope_cos, rope_sin, rope_cols, nullptr, 0, stream);
+}
+
+extern "C" int mla_gemm_suffix_w8_pos(const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
+                                      long long out_batch_stride, int rows_per_batch, const int* slot, int cap_rows, const void* residual,
+                                      long long ld_res, int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols,
+                                      const int* rope_pos, int rope_rows, hipStream_t stream) {
+  return suffix_entry<true>("mla_gemm_suffix_w8_pos", x, ldx, W, ldw, w_scale, out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows,
+                            residual, ld_res, M, N, K, rope_cos, rope_sin, rope_cols, rope_pos, rope_rows, stream);
 }

@@ -54,6 +54,14 @@ _SIGNATURES = {
                              c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
     "mla_gemm_suffix_w8": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_int,
                            c_void_p, c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
+    "mla_attn_chunk_ragged_groups": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_longlong,
+                                     c_longlong, c_longlong, c_float, c_void_p],
+    "mla_attn_chunk_ragged_groups_gw": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_longlong,
+                                        c_longlong, c_longlong, c_float, c_int, c_int, c_void_p],
+    "mla_gemm_suffix_bf16_pos": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_int, c_void_p,
+                                 c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p],
+    "mla_gemm_suffix_w8_pos": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_int,
+                               c_void_p, c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p],
     "mla_gemm_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                       c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
     "mla_gemm_bf16_ws": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -932,8 +940,10 @@ def attn_chunk(cache, B, nheads, D, S_kv, R, scale):
 SUFFIX_MMAX = 256
 
 
-def _suffix_call(sym, name, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows, w_scale=None):
-    """The shared call of the two batched suffix projections; w_scale (fp32 [N]) selects the `_w8` argument list (W: float8_e4m3fn)."""
+def _suffix_call(sym, name, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows, w_scale=None,
+                 rope_pos=None, rope_rows=None):
+    """The shared call of the two batched suffix projections; w_scale (fp32 [N]) selects the `_w8` argument list (W: float8_e4m3fn),
+    rope_pos (int32, one rotary position per sample) the `_pos` entry point."""
     _req(x, torch.bfloat16, f"{name} x")
     _req(W, torch.bfloat16 if w_scale is None else torch.float8_e4m3fn, f"{name} W")
     scale_arg = ()
@@ -949,33 +959,46 @@ def _suffix_call(sym, name, x, W, out, ldo, out_batch_stride, rows_per_batch, re
         _req(slot, torch.int32, f"{name} slot")
         assert cap_rows is not None and slot.is_contiguous() and slot.numel() * rows_per_batch >= M
     cap = int(cap_rows) if slot is not None else int(rows_per_batch)
+    pos_arg = ()
+    if rope_pos is not None:
+        _req(rope_pos, torch.int32, f"{name} rope_pos")
+        assert rope is not None and rope_rows is not None and rope_pos.is_contiguous() and rope_pos.numel() * rows_per_batch >= M
+        pos_arg = (_p(rope_pos), int(rope_rows))
+        sym += "_pos"
     if rope is not None:
         _req(rope[0], torch.float32, f"{name} rope cos")
         _req(rope[1], torch.float32, f"{name} rope sin")
-        assert rope[0].shape == (cap, 64) and rope[1].shape == rope[0].shape and rope[0].is_contiguous() and rope[1].is_contiguous()
+        assert rope[0].shape == (cap if rope_pos is None else int(rope_rows), 64) and rope[1].shape == rope[0].shape
+        assert rope[0].is_contiguous() and rope[1].is_contiguous()
         assert out_col == 0 and residual is None
     if residual is not None:
         _req(residual, torch.bfloat16, f"{name} residual")
         assert residual.shape[0] == M and residual.stride(1) == 1
     call(sym, _p(x), x.stride(0), _p(W), W.stride(0), *scale_arg, c_void_p(out.data_ptr() + 2 * out_col), ldo, out_batch_stride,
          rows_per_batch, _p(slot), cap, _p(residual), residual.stride(0) if residual is not None else 0, M, N, K,
-         _p(rope[0]) if rope is not None else None, _p(rope[1]) if rope is not None else None, int(rope[2]) if rope is not None else 0)
+         _p(rope[0]) if rope is not None else None, _p(rope[1]) if rope is not None else None, int(rope[2]) if rope is not None else 0,
+         *pos_arg)
 
 
-def gemm_suffix(x, W, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, rope=None, slot=None, cap_rows=None):
+def gemm_suffix(x, W, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, rope=None, slot=None, cap_rows=None,
+                rope_pos=None, rope_rows=None):
     """out row m = x[m] @ W^T (+ residual[m]) for 1 <= M <= 256 rows of a batch of samples (mla_gemm_suffix_bf16; plain input only).
     Row m is row p = m % rows_per_batch of sample b = m // rows_per_batch and lands at out + b * out_batch_stride + (slot[b] + p) * ldo
     + out_col. slot: int32 [B] device tensor (the sample's prefix length) with cap_rows = rows per sample that `out` (and the tables) hold;
-    None = every slot 0. rope = (cos [cap_rows or rows_per_batch, 64], sin, rope_cols): row slot[b] + p of the tables rotates the row."""
-    _suffix_call("mla_gemm_suffix_bf16", "gemm_suffix", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows)
+    None = every slot 0. rope = (cos [cap_rows or rows_per_batch, 64], sin, rope_cols): row slot[b] + p of the tables rotates the row.
+    rope_pos (mla_gemm_suffix_bf16_pos): int32 [B] device tensor with rope_rows = rows of the tables ([rope_rows, 64]); the row is then
+    rotated with table row rope_pos[b] + p instead, and not written when that lies outside [0, rope_rows). None = the call above."""
+    _suffix_call("mla_gemm_suffix_bf16", "gemm_suffix", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows,
+                 rope_pos=rope_pos, rope_rows=rope_rows)
 
 
-def gemm_suffix_w8(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, rope=None, slot=None, cap_rows=None):
+def gemm_suffix_w8(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, rope=None, slot=None, cap_rows=None,
+                   rope_pos=None, rope_rows=None):
     """gemm_suffix over FP8 weights (mla_gemm_suffix_w8): W [N, K] float8_e4m3fn, w_scale [N] fp32 as quant_fp8_rows writes them; out row m =
     w_scale * (x[m] @ float(W)^T) (+ residual[m]), the scale applied to the finished fp32 sum (gemm_skinny_w8's arithmetic: every 64-row
-    slice is bit for bit its output). K % 16 == 0; rows, slots, rope and addressing are gemm_suffix's."""
+    slice is bit for bit its output). K % 16 == 0; rows, slots, rope, rope_pos (mla_gemm_suffix_w8_pos) and addressing are gemm_suffix's."""
     _suffix_call("mla_gemm_suffix_w8", "gemm_suffix_w8", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows,
-                 w_scale)
+                 w_scale, rope_pos=rope_pos, rope_rows=rope_rows)
 
 
 def attn_chunk_ragged(cache, B, nheads, D, kv_len, R, scale):
@@ -1013,6 +1036,27 @@ def attn_chunk_groups(cache, G, nheads, D, S_p, R, scale, gw=None, order=None):
         call("mla_attn_chunk_groups", *args)
     else:
         call("mla_attn_chunk_groups_gw", *args, int(gw or 0), -1 if order is None else int(order))
+    return o
+
+
+def attn_chunk_ragged_groups(cache, B, G, nheads, D, prefix_len, R, scale, gw=None, order=None):
+    """attn_chunk_groups for B samples with their own prefix lengths (mla_attn_chunk_ragged_groups): cache [B, S_cap, 3H] packed post-RoPE
+    q|k|v, prefix_len int32 [B] on the device (clamped to [0, S_cap - G * R]); in sample b rows [0, S_p[b]) are the prefix and row
+    S_p[b] + g * R + p is suffix row p of group g. The rows of (b, g) are bit for bit attn_chunk_groups on cache[b] with S_p = S_p[b].
+    gw / order: attn_chunk_groups' launch form arguments (same bits). Returns o [B * G * R, nheads * D] bf16, row (b * G + g) * R + p."""
+    _req(cache, torch.bfloat16, "attn_chunk_ragged_groups cache")
+    _req(prefix_len, torch.int32, "attn_chunk_ragged_groups prefix_len")
+    H = nheads * D
+    assert cache.dim() == 3 and cache.shape[0] == B and cache.shape[2] == 3 * H and cache.stride(2) == 1 and G >= 1 and R >= 1
+    assert cache.shape[1] >= G * R and prefix_len.numel() == B and prefix_len.is_contiguous()
+    o = torch.empty((B * G * R, H), dtype=torch.bfloat16, device=cache.device)
+    base = cache.data_ptr()
+    args = (c_void_p(base), c_void_p(base + 2 * H), c_void_p(base + 4 * H), _p(o), B, G, nheads, D, _p(prefix_len), cache.shape[1], R,
+            cache.stride(1), cache.stride(0), H, float(scale))
+    if gw is None and order is None:
+        call("mla_attn_chunk_ragged_groups", *args)
+    else:
+        call("mla_attn_chunk_ragged_groups_gw", *args, int(gw or 0), -1 if order is None else int(order))
     return o
 
 

@@ -655,3 +655,186 @@ class SampleGroupsEps(_CachedEpsBase):
             h = self._proj(hip.swiglu_fwd(gu), wd, residual=h1)
         hn, _ = hip.rmsnorm_fwd(h, self.model.norm.weight, self.eps)
         self.h_out.copy_(hn)
+
+
+# ================================================================================================ N action chunks for each of B observations
+# MLA.predict_action_diff_batch(num_samples=N): the two engines above composed. The encoders and ONE varlen prefill serve the B prefixes of
+# a pass (BatchedPrefixCachedEps), every sample's cache holds its prefix followed by G = N groups of R suffix rows (SampleGroupsEps): the
+# cache is [B, S_cap, 3H], row S_p[b] + g R + p of sample b is suffix row p of group g. With several groups behind a per-sample prefix the
+# cache row and the rotary position of a suffix row differ (row S_p[b] + g R + p rotates at S_p[b] + p), hence mla_gemm_suffix_bf16_pos /
+# _w8_pos with two device arrays, and mla_attn_chunk_ragged_groups as the attention. A pass streams the decoder weights once over the
+# B G R <= 256 rows: B N chunks cost one prefill pass per sub-batch and 8 weight passes, not B prefills and 8 B passes.
+class SampleSubBatchPlan(NamedTuple):
+    """One pass of `plan_batch_samples`: observations [start, stop) of the call with G groups each. ids / k / S_p / S_pmax / R as in
+    SubBatchPlan; prefix_len[b] = S_p[b]; per group s = b * G + g (b counted inside the pass): slot[s] = b * S_cap + S_p[b] + g * R its
+    first row in the flat [B * S_cap, 3H] cache, rope_pos[s] = S_p[b] its first rotary position; S_cap = S_pmax + G * R rounded up to the
+    bucket, part of the engine's key."""
+    start: int
+    stop: int
+    ids: Tuple[Tuple[int, ...], ...]
+    k: Tuple[int, ...]
+    S_p: Tuple[int, ...]
+    prefix_len: Tuple[int, ...]
+    slot: Tuple[int, ...]
+    rope_pos: Tuple[int, ...]
+    S_pmax: int
+    S_cap: int
+    R: int
+    G: int
+
+
+def plan_batch_samples(ids_rows: Sequence[Sequence[int]], n_action_rows: int, n_front: int, num_samples: int, max_rows: int = 256,
+                       bucket: int = 64, add_tail: bool = True):
+    """Pure host planning of predict_action_diff_batch(num_samples=N) -> list of SampleSubBatchPlan, in order, or None when one
+    observation's N groups exceed a pass (N > max_rows // R: the caller then loops predict_action_diff_samples per observation, which
+    splits its passes on one prefill). Prompt handling, splice position and errors per row are plan_batch's; a pass holds
+    (max_rows // R) // N consecutive observations with all N groups each."""
+    N, R = int(num_samples), 1 + int(n_action_rows)
+    if N < 1:
+        raise ValueError(f"num_samples must be >= 1, got {num_samples}")
+    if R > max_rows:
+        raise ValueError(f"{R} suffix rows per sample exceed the {max_rows} rows of a pass")
+    per = max_rows // R
+    if N > per:
+        plan_batch(ids_rows, n_action_rows, n_front, max_rows, bucket, add_tail)      # the rows' errors do not depend on N
+        return None
+    plans = []
+    for sub in plan_batch(ids_rows, n_action_rows, n_front, (per // N) * R, bucket, add_tail):
+        S_cap = -(-(sub.S_pmax + N * R) // bucket) * bucket
+        slot = tuple(b * S_cap + s + g * R for b, s in enumerate(sub.S_p) for g in range(N))
+        rope_pos = tuple(s for s in sub.S_p for _ in range(N))
+        plans.append(SampleSubBatchPlan(sub.start, sub.stop, sub.ids, sub.k, sub.S_p, sub.S_p, slot, rope_pos, sub.S_pmax, S_cap, R, N))
+    return plans
+
+
+class BatchedSampleGroupsEps(_CachedEpsBase):
+    """One engine -- and one captured graph -- per (observations NB, groups G, S_cap, R, device[, suffix_weights]) serves every mix of
+    prompt lengths of a capacity bucket: `prefix_len` [NB], `slot` and `rope_pos` [NB * G] are device tensors the kernels read
+    (mla_attn_chunk_ragged_groups, mla_gemm_suffix_bf16_pos / mla_gemm_suffix_w8_pos), refreshed by copy_ in prefill(). The prefill is
+    BatchedPrefixCachedEps's (right-padded prefixes, one varlen pass per layer, bf16 weights whatever the mode); the suffix pass is the
+    batched engine's eight launches per layer over the NB * G * R rows, in the order (b, g, p). `model(x [NB * G, T, D], t [NB * G])`:
+    self.B = NB * G is the sampler's batch."""
+
+    MAX_ROWS = 256                   # suffix rows per pass (mla_gemm_suffix_bf16_pos / mla_gemm_suffix_w8_pos)
+    MAX_R = 64                       # rows per group (mla_attn_chunk_ragged_groups)
+    BUCKET = 64                      # cache capacity granularity in rows
+
+    @classmethod
+    def supports_batch_samples(cls, vlm, n_action_rows: int, warn: bool = True) -> bool:
+        """head_dim 128 and at most 64 suffix rows per group; otherwise the bf16 caller loops predict_action_diff_samples per observation
+        (warns once per shape; warn=False: the plain predicate, for the callers that raise instead)."""
+        cfg = vlm.llm_backbone.llm.config
+        R, D = 1 + n_action_rows, cfg.hidden_size // cfg.num_attention_heads
+        if R <= cls.MAX_R and D == 128:
+            return True
+        seen = vlm.__dict__.setdefault("_prefix_unsupported", set())
+        if warn and ("batch_samples", R, D) not in seen:
+            seen.add(("batch_samples", R, D))
+            warnings.warn(f"BatchedSampleGroupsEps: {R} suffix rows per sample (max {cls.MAX_R}) / head_dim {D} (needs 128) are beyond the "
+                          "batched shared-prefix kernels; drawing every observation's samples with its own call", RuntimeWarning, stacklevel=3)
+        return False
+
+    @classmethod
+    def fits_pass(cls, n_action_rows: int, num_samples: int) -> bool:
+        """Whether one observation's N groups fit a pass (plan_batch_samples would not return None)."""
+        return int(num_samples) <= cls.MAX_ROWS // (1 + int(n_action_rows))
+
+    @classmethod
+    def for_batch(cls, vlm, ids_rows, n_action_rows: int, num_samples: int, suffix_weights: str = "bf16", images=None, point_cloud=None,
+                  camera_name=None, proprio=None, add_tail=True, **unused):
+        """Generator over the passes of one call: runs the encoders once over all observations, plans (plan_batch_samples) and yields
+        (SampleSubBatchPlan, prefilled engine) per sub-batch. Two sub-batches may share an engine: finish sampling one before taking the
+        next."""
+        check_suffix_weights(suffix_weights)
+        with torch.no_grad():
+            parts, _, _, _, _, _ = vlm.get_fused_tokens(images, point_cloud, None, None, camera_name)
+            vlm.vision_tower_2d.assert_masks_ok()
+            front = torch.cat(parts, dim=1)                                   # [B, n_front, H]
+        plans = plan_batch_samples(ids_rows, n_action_rows, int(front.shape[1]), num_samples, cls.MAX_ROWS, cls.BUCKET, add_tail=add_tail)
+        if plans is None:
+            raise ValueError(f"{num_samples} groups of {1 + n_action_rows} rows exceed the {cls.MAX_ROWS} rows of a pass (fits_pass)")
+        engines = vlm.__dict__.setdefault("_prefix_engines_batch_samples", {})
+        for sub in plans:
+            key = (sub.stop - sub.start, sub.G, sub.S_cap, sub.R, str(front.device))
+            if suffix_weights != "bf16":
+                key += (suffix_weights,)                                      # a captured graph holds the addresses of ITS weights
+            eng = engines.get(key)
+            if eng is None:
+                if len(engines) >= 4:
+                    engines.pop(next(iter(engines)))
+                eng = engines[key] = cls(vlm, n_action_rows, suffix_weights)
+            eng.prefill(sub, front[sub.start:sub.stop], proprio[sub.start:sub.stop])
+            yield sub, eng
+
+    def prefill(self, sub: SampleSubBatchPlan, front, proprio):
+        vlm, bf16, dev = self.vlm, torch.bfloat16, front.device
+        NB, G, S_pmax = sub.stop - sub.start, sub.G, sub.S_pmax
+        with torch.no_grad():
+            proprio_e = vlm.proprio_embedder(proprio.to(bf16))                # [NB, 1, H]
+            H = front.shape[2]
+            prefix = torch.zeros((NB, S_pmax, H), dtype=bf16, device=dev)
+            for b in range(NB):
+                e = vlm.llm_backbone.embed_input_ids(torch.tensor([sub.ids[b]], dtype=torch.long, device=dev))[0]
+                prefix[b, :sub.S_p[b]] = torch.cat([e[:1], front[b], e[1:sub.k[b]], proprio_e[b]], dim=0)
+            if self.cache is None:
+                self.NB, self.G, self.B, self.H, self.S_cap = NB, G, NB * G, H, sub.S_cap
+                self.D = H // self.nheads
+                self.rot = self.model.layers[0].self_attn.rotary_emb
+                self.cos_c, self.sin_c = self.rot.tables(self.S_cap, dev)    # the epilogue rotates row p of a group with table row rope_pos + p
+                rows = NB * G * self.R
+                with torch.inference_mode(False):                            # the engine outlives the (inference-mode) call that creates it
+                    self.cache = [torch.zeros((NB, self.S_cap, 3 * H), dtype=bf16, device=dev) for _ in self.model.layers]
+                    self.h_in = torch.zeros((rows, H), dtype=bf16, device=dev)
+                    self.h_out = torch.zeros((rows, H), dtype=bf16, device=dev)
+                    self.prefix_len = torch.zeros(NB, dtype=torch.int32, device=dev)
+                    self.slot = torch.zeros(NB * G, dtype=torch.int32, device=dev)
+                    self.rope_pos = torch.zeros(NB * G, dtype=torch.int32, device=dev)
+            assert (NB, G, H, sub.S_cap, sub.R) == (self.NB, self.G, self.H, self.S_cap, self.R) and S_pmax + G * self.R <= self.S_cap
+            self.prefix_len.copy_(torch.tensor(sub.prefix_len, dtype=torch.int32))
+            self.slot.copy_(torch.tensor(sub.slot, dtype=torch.int32))
+            self.rope_pos.copy_(torch.tensor(sub.rope_pos, dtype=torch.int32))
+            seqlens = torch.tensor(sub.S_p, dtype=torch.int32, device=dev)
+            cos_p, sin_p = self.rot.tables(S_pmax, dev)
+            h = prefix.reshape(NB * S_pmax, H)
+            for w, c in zip(self._weights(), self.cache):                    # the bf16 weights, whatever the suffix pass streams
+                h, acts = ops.DecoderLayerFn._fwd(h, seqlens, cos_p, sin_p, NB, S_pmax, self.nheads, self.eps, w)
+                c[:, :S_pmax].copy_(acts.qkv[:NB * S_pmax].view(NB, S_pmax, 3 * H))
+                del acts
+
+    def _proj(self, x, weights, out=None, residual=None, **kw):
+        """x [M, K] @ W^T (+ residual): `weights` is a tuple of adjacent bf16 views (mla_gemm_suffix_bf16) or one W8 (mla_gemm_suffix_w8);
+        out = a layer's cache: the q|k|v rows go to their groups' slots (the `_pos` entry points)."""
+        if isinstance(weights, W8):
+            N, gemm = weights.q.shape[0], functools.partial(hip.gemm_suffix_w8, x, weights.q, weights.scale)
+        else:
+            wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
+            assert wcat is not None, "the packed weights are adjacent in memory (_weights)"
+            N, gemm = wcat.shape[0], functools.partial(hip.gemm_suffix, x, wcat)
+        M = x.shape[0]
+        if out is None:
+            out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+            gemm(out, out.stride(0), 0, M, residual)
+        else:                                                                # flat [NB * S_cap, 3H] cache: slot holds the sample's base row
+            gemm(out, out.stride(-2), 0, self.R, residual, **kw)
+        return out
+
+    def _suffix_pass(self):
+        NB, G, R, H = self.NB, self.G, self.R, self.H
+        h = self.h_in
+        scale = 1.0 / math.sqrt(self.D)
+        for w, c in zip(self._suffix, self.cache):
+            if self.suffix_weights == "fp8":                                 # _quantised: the packed q|k|v and gate|up as one W8 each
+                ln1, qkv, wo, ln2, gu_w, wd = w
+            else:                                                            # the packed 9-tuple ("bf16") or its dequantised twin
+                ln1, qkv, wo, ln2, gu_w, wd = w[0], w[1:4], w[4:5], w[5], w[6:8], w[8:9]
+            xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
+            # q|k|v row p of group (b, g) -> cache row slot = b S_cap + S_p[b] + g R + p, q and k rotated at position S_p[b] + p
+            self._proj(xn, qkv, out=c, slot=self.slot, cap_rows=NB * self.S_cap, rope=(self.cos_c, self.sin_c, 2 * H),
+                       rope_pos=self.rope_pos, rope_rows=self.S_cap)
+            o = hip.attn_chunk_ragged_groups(c, NB, G, self.nheads, self.D, self.prefix_len, R, scale)
+            h1 = self._proj(o, wo, residual=h)
+            xn2, _ = hip.rmsnorm_fwd(h1, ln2, self.eps)
+            gu = self._proj(xn2, gu_w)
+            h = self._proj(hip.swiglu_fwd(gu), wd, residual=h1)
+        hn, _ = hip.rmsnorm_fwd(h, self.model.norm.weight, self.eps)
+        self.h_out.copy_(hn)

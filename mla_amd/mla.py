@@ -391,7 +391,8 @@ class MLA(nn.Module):
     def predict_action_diff_batch(self, images, pointclouds, instructions=None, cur_robot_states=None, unnorm_key: Optional[str] = None,
                                   cfg_scale: float = 0.0, use_ddim: bool = True, num_ddim_steps: int = 8, action_dim: int = 7, *,
                                   input_ids=None, noise: Optional[torch.Tensor] = None, camera_name: str = "rlbench_front",
-                                  reuse_prefix: bool = True, suffix_weights: str = "bf16") -> np.ndarray:
+                                  reuse_prefix: bool = True, suffix_weights: str = "bf16",
+                                  num_samples: Optional[int] = None) -> np.ndarray:
         """B observations -> [B, T, action_dim]: by definition B independent `predict_action_diff` calls (the reference's
         `predict_action_batch`, model_mla.py:994, is dead code), computed on ONE cached prefix pass per DDIM step
         (mla_amd/infer.py:BatchedPrefixCachedEps): the prompts may have different lengths, the FPS start indices are drawn once per chunk.
@@ -401,11 +402,24 @@ class MLA(nn.Module):
         proprio normalisation, un-normalisation) is predict_action_diff's. B = 1 IS predict_action_diff; ``reuse_prefix=False`` loops the
         reference's control flow; more than 256 suffix rows are served as consecutive sub-batches; head_dim != 128 warns once and loops
         over whole-forward batch-1 calls. ``suffix_weights``: predict_action_diff's, forwarded for B = 1; the batched engine has bf16
-        weights only, so B >= 2 with another mode raises NotImplementedError."""
+        weights only, so B >= 2 with another mode raises NotImplementedError (unless ``num_samples`` is given).
+        ``num_samples`` = N >= 1 (default None: everything above, unchanged): N action chunks for EACH observation -> [B, N, T, action_dim],
+        by definition ``out[b] == predict_action_diff_samples(observation b, num_samples=N, noise=noise[b])``, computed on one prefill
+        over the B prefixes and one pass per sampler step over the B * N * (1 + T) suffix rows (mla_amd/infer.py:BatchedSampleGroupsEps;
+        at most 256 rows per pass, more observations are served as consecutive sub-batches). ``noise``: [B, N, T, action_dim]; RNG: for b:
+        for n: randn(1, T, D), then the unused randint. B = 1 IS predict_action_diff_samples; ``reuse_prefix=False`` loops the reference's
+        control flow; N > 256 // (1 + T) loops predict_action_diff_samples per observation (it splits its passes on one prefill); a shape
+        the engine does not serve warns once and loops the same way. All three ``suffix_weights`` modes are accepted (N = 1 included: this
+        is how B >= 2 observations get FP8 suffix weights); anything but "bf16" raises ValueError when ``reuse_prefix=False`` or the
+        engine does not serve the shape."""
         from .infer import check_suffix_weights
         check_suffix_weights(suffix_weights)
         B = len(images)
         T = self.future_action_window_size + 1
+        if num_samples is not None:
+            return self._predict_action_diff_batch_samples(images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
+                                                           num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix,
+                                                           suffix_weights, num_samples)
         if input_ids is None:
             if instructions is None or len(instructions) != B:
                 raise ValueError("predict_action_diff_batch needs `input_ids` (one tensor per sample), or B `instructions` plus a callable "
@@ -428,7 +442,8 @@ class MLA(nn.Module):
             return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights)[None]
         if suffix_weights != "bf16":
             raise NotImplementedError(f"suffix_weights={suffix_weights!r}: the batched engine (BatchedPrefixCachedEps, mla_gemm_suffix_bf16) "
-                                      "streams bf16 weights only; sample B >= 2 observations with \"bf16\" or one at a time")
+                                      "streams bf16 weights only; sample B >= 2 observations with \"bf16\", one at a time, or pass "
+                                      "`num_samples` (BatchedSampleGroupsEps serves every mode)")
         if reuse_prefix:
             from .infer import BatchedPrefixCachedEps
             reuse_prefix = BatchedPrefixCachedEps.supports_batch(self.vlm, T)
@@ -459,6 +474,74 @@ class MLA(nn.Module):
             else:
                 samples = self.diffusion.p_sample_loop(eng, xs.shape, xs, clip_denoised=False, model_kwargs={}, progress=False, device=device)
             out.append(samples.float().cpu().numpy())
+        normalized = np.concatenate(out, axis=0)
+        return self.unnormalize_actions(normalized, unnorm_key) if self.norm_stats is not None else normalized
+
+    def _predict_action_diff_batch_samples(self, images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
+                                           num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix, suffix_weights, num_samples):
+        """predict_action_diff_batch(num_samples=N) -> [B, N, T, action_dim] (called inside its inference mode; see its docstring)."""
+        B, N, T = len(images), int(num_samples), self.future_action_window_size + 1
+        if N < 1:
+            raise ValueError(f"num_samples must be >= 1, got {num_samples}")
+        if input_ids is None:
+            if instructions is None or len(instructions) != B:
+                raise ValueError("predict_action_diff_batch needs `input_ids` (one tensor per sample), or B `instructions` plus a callable "
+                                 "vlm.llm_backbone.tokenizer")
+            input_ids = [self._prompt_ids(ins, "predict_action_diff_batch") for ins in instructions]
+        if pointclouds is None:
+            pointclouds = [None] * B
+        if not (len(input_ids) == B and len(pointclouds) == B and cur_robot_states is not None and len(cur_robot_states) == B):
+            raise ValueError("predict_action_diff_batch: images, pointclouds, cur_robot_states and input_ids / instructions need one entry per sample")
+        if noise is not None and tuple(noise.shape) != (B, N, T, action_dim):
+            raise ValueError(f"noise must be [B, N, T, action_dim] = [{B}, {N}, {T}, {action_dim}], got {tuple(noise.shape)}")
+        self._check_cfg_scale(cfg_scale)
+        ids_rows = [ids.reshape(1, -1) for ids in input_ids]
+
+        def samples_of(b, **kw):
+            return self.predict_action_diff_samples(images[b], pointclouds[b], None, cur_robot_states[b], unnorm_key, N, cfg_scale, use_ddim,
+                                                    num_ddim_steps, action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b],
+                                                    camera_name=camera_name, **kw)
+        if B == 1:
+            return samples_of(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights)[None]
+        if suffix_weights != "bf16" and not reuse_prefix:
+            raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
+                             "bf16 weights only")
+        if reuse_prefix:
+            from .infer import BatchedSampleGroupsEps
+            if suffix_weights != "bf16" and not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T, warn=False):
+                raise ValueError(f"suffix_weights={suffix_weights!r}: the batched shared-prefix engine (BatchedSampleGroupsEps) does not serve "
+                                 f"{1 + T} suffix rows per sample at this head_dim; draw the samples with \"bf16\"")
+            if not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T) or not BatchedSampleGroupsEps.fits_pass(T, N):
+                # one observation at a time: predict_action_diff_samples serves (or refuses) the shape and the mode itself
+                return np.stack([samples_of(b, suffix_weights=suffix_weights) for b in range(B)])
+        else:
+            return np.stack([samples_of(b, reuse_prefix=False) for b in range(B)])
+        self.vlm.eval()
+        device = next(self.vlm.parameters()).device
+        pre = [self._preprocessed_image(im) for im in images]
+        ids_rows = [ids.reshape(-1).tolist() for ids in ids_rows]             # the prompt tail per row: infer.plan_batch (:640-645)
+        img = torch.cat([self._image_batch(im, device) for im in pre], dim=0)
+        pcs = [self._pointcloud_batch(pc, device) for pc in pointclouds]
+        pc = None if any(p is None for p in pcs) else torch.cat(pcs, dim=0)
+        proprio = torch.cat([self._proprio_token(st, unnorm_key, device) for st in cur_robot_states], dim=0)
+        draws = []
+        for b in range(B):                                                   # the RNG draws of B calls of N samples, in their order (:707-708)
+            for n in range(N):
+                draws.append(torch.randn(1, T, action_dim, device=device) if noise is None else noise[b, n:n + 1].to(device))
+                _ = torch.randint(0, self.diffusion.num_timesteps, (T,), device=device)
+        x0 = torch.cat(draws, dim=0).float()                                 # [B * N, T, D], rows (b, n)
+        if use_ddim and num_ddim_steps is not None and self.ddim_diffusion is None:
+            self.create_ddim(ddim_step=num_ddim_steps)
+        out = []
+        for sub, eng in BatchedSampleGroupsEps.for_batch(self.vlm, ids_rows, T, N, suffix_weights, images=img, point_cloud=pc,
+                                                         camera_name=camera_name, proprio=proprio):
+            xs = x0[sub.start * N:sub.stop * N].contiguous()
+            if use_ddim and num_ddim_steps is not None:
+                samples = self.ddim_diffusion.ddim_sample_loop(eng, xs.shape, xs, clip_denoised=False, model_kwargs={}, progress=False,
+                                                               device=device, eta=0.0)
+            else:
+                samples = self.diffusion.p_sample_loop(eng, xs.shape, xs, clip_denoised=False, model_kwargs={}, progress=False, device=device)
+            out.append(samples.float().cpu().numpy().reshape(sub.stop - sub.start, N, T, -1))
         normalized = np.concatenate(out, axis=0)
         return self.unnormalize_actions(normalized, unnorm_key) if self.norm_stats is not None else normalized
 

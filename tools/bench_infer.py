@@ -23,6 +23,14 @@
                                                           process, in pairs: per-call latency and the suffix pass alone with the 95 %
                                                           interval of the pair differences; --kernel-table adds mla_gemm_suffix_w8 against
                                                           mla_gemm_suffix_bf16 per 7B projection shape at M = 34, 68, 136, 255
+    python tools/bench_infer.py --batch B[,B..] --samples N[,N..] [--pair-fp8] [--chunk C] [--pairs P] [--kernel-table]
+                                                          N action chunks for EACH of B observations with ragged prompts (the lists are
+                                                          paired element-wise: --batch 2,4 --samples 4,3 measures (2, 4) and (4, 3)): two
+                                                          forms of the same work alternating in one process, per pair, with the 95 %
+                                                          interval of the pair differences: (a) predict_action_diff_batch(num_samples=N),
+                                                          (b) B sequential predict_action_diff_samples calls; --pair-fp8 measures both forms
+                                                          with bf16 and with fp8 suffix weights; --kernel-table adds
+                                                          mla_attn_chunk_ragged_groups per launch against mla_attn_chunk_groups run per sample
 Prints one JSON line per measurement (not the driver's bench contract -- that is bench.py)."""
 import argparse
 import json
@@ -42,7 +50,8 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--chunk", type=int, default=1, help="future_action_window_size + 1")
     ap.add_argument("--no-reuse-prefix", action="store_true", help="the reference's control flow: a whole forward per DDIM step")
-    ap.add_argument("--batch", type=int, default=0, help="B > 0: predict_action_diff_batch on B observations vs B sequential calls")
+    ap.add_argument("--batch", type=str, default="0", help="B > 0: predict_action_diff_batch on B observations vs B sequential calls; with "
+                    "--samples: B[,B..] paired with N[,N..]")
     ap.add_argument("--suffix-weights", choices=["bf16", "fp8", "fp8_as_bf16"], default="bf16")
     ap.add_argument("--pair-fp8", action="store_true", help="alternate bf16 and fp8 chunks in one process, in pairs")
     ap.add_argument("--pairs", type=int, default=6)
@@ -51,6 +60,10 @@ def main():
     ap.add_argument("--samples", type=str, default="", help="N[,N..]: predict_action_diff_samples vs the batched call on N copies vs N calls")
     ap.add_argument("--chunks", type=str, default="", help="with --samples: action chunk lengths to measure in one process (default: --chunk)")
     args = ap.parse_args()
+    batches = [int(v) for v in args.batch.split(",")]
+    if args.samples and batches != [0]:
+        return main_batch_samples(args, batches)
+    args.batch = batches[0]
     if args.samples:
         return main_samples_pair(args) if args.pair_fp8 else main_samples(args)
     if args.batch > 0:
@@ -451,6 +464,118 @@ def main_samples_pair(args):
                               "suffix_pass_weight_stream_tbps": {k: round(_stream_bytes(m, k) / 1e12 / (min(suffix[k]) * 1e-3), 2) for k in modes},
                               "engine_graph": graphs, "fp8_vs_bf16_rel_diff_random_weights": round(rel, 4), "data": "synthetic"}), flush=True)
             m.vlm.__dict__.get("_prefix_engines_samples", {}).clear()         # the caches of this (N, chunk)
+            torch.cuda.empty_cache()
+
+
+def _ragged_groups_table(dev, cases, chunk, H=32, layers=32, reps=5, rounds=3):
+    """mla_attn_chunk_ragged_groups alone at the 7B shapes (32 heads, prefixes around 545 rows) against mla_attn_chunk_groups launched once
+    per sample on that sample's slice (what B predict_action_diff_samples calls issue). As the engines launch them: one launch per layer
+    on that layer's own cache, captured into a graph; the arms alternate, every arm is measured `rounds` times. us per layer (one ragged
+    launch vs B per-sample launches), the minimum and all rounds."""
+    import math
+    from mla_amd import hip
+    scale = 1 / math.sqrt(128)
+    R = chunk + 1
+    table = {}
+    for B, N in cases:
+        S_p = [545 - (5 * b) % 13 for b in range(B)]
+        S_cap = -(-(max(S_p) + N * R) // 64) * 64
+        caches = [(torch.randn(B, S_cap, 3 * H * 128, device=dev) * 0.7).to(torch.bfloat16) for _ in range(layers)]
+        lens = torch.tensor(S_p, dtype=torch.int32, device=dev)
+        arms = {"ragged_groups": lambda: [hip.attn_chunk_ragged_groups(c, B, N, H, 128, lens, R, scale) for c in caches],
+                "groups_per_sample": lambda: [hip.attn_chunk_groups(c[b], N, H, 128, S_p[b], R, scale) for c in caches for b in range(B)]}
+        graphs = {}
+        for name, fn in arms.items():
+            fn()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                keep = fn()
+            g.replay()
+            graphs[name] = (g, keep)
+        us = {name: [] for name in arms}
+        for _ in range(rounds):
+            for name, (g, _) in graphs.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(reps):
+                    g.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                us[name].append(round(e0.elapsed_time(e1) / (reps * layers) * 1e3, 1))
+        table[f"B{B}_N{N}_chunk{chunk}"] = {"us_per_layer_min": {k: min(v) for k, v in us.items()}, "us_per_layer_rounds": us,
+                                            "launches_per_layer": {"ragged_groups": 1, "groups_per_sample": B}, "prefix_rows": S_p}
+        del graphs, caches
+        torch.cuda.empty_cache()
+    return table
+
+
+def main_batch_samples(args, batches):
+    from bench import build
+    from mla_amd.synthetic import make_batch
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    Ns = [int(v) for v in args.samples.split(",")]
+    assert len(Ns) == len(batches) and min(Ns) >= 1 and min(batches) >= 1, "--batch B[,B..] and --samples N[,N..] are paired element-wise"
+    cases = list(zip(batches, Ns))
+    chunk = args.chunk
+    if args.kernel_table:
+        print(json.dumps({"metric": "mla_attn_chunk_ragged_groups (one launch) vs mla_attn_chunk_groups per sample (B launches), 32 heads, one "
+                                    "layer cache each", "unit": "us", "table": _ragged_groups_table(dev, cases, chunk), "data": "synthetic"}),
+              flush=True)
+    m = build(dev, 1)
+    m.future_action_window_size = m.vlm.future_action_window_size = chunk - 1
+    m.eval()
+    for p in m.parameters():
+        p.data = p.data.to(torch.bfloat16)
+    modes = ("bf16", "fp8") if args.pair_fp8 else ("bf16",)
+    wbytes = {mode: _stream_bytes(m, mode) for mode in modes}
+    for B, N in cases:
+        b = make_batch(B=B, device=dev)
+        g = torch.Generator().manual_seed(1234)
+        drop = torch.randint(0, 13, (B,), generator=g).tolist()             # ragged prompts: 0 .. 12 ids shorter than the synthetic prompt
+        ids = [torch.cat([b["input_ids"][i, :b["input_ids"].shape[1] - 4 - drop[i]], torch.tensor([29871], device=dev)]) for i in range(B)]
+        images = [b["images"]["front_image"][i] for i in range(B)]
+        pcs = [b["point_cloud"][i] for i in range(B)]
+        states = [b["proprio"][i, 0].cpu().numpy() for i in range(B)]
+        noise = torch.randn(B, N, chunk, 7, device=dev)
+
+        def batched(mode):
+            return m.predict_action_diff_batch(images, pcs, cur_robot_states=states, input_ids=ids, noise=noise, num_ddim_steps=args.steps,
+                                               num_samples=N, suffix_weights=mode)
+
+        def sequential(mode):
+            return np.stack([m.predict_action_diff_samples(images[i], pcs[i], cur_robot_state=states[i], num_samples=N, input_ids=ids[i][None],
+                                                           noise=noise[i], num_ddim_steps=args.steps, suffix_weights=mode) for i in range(B)])
+
+        def timed(fn, mode):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.iters):
+                fn(mode)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / args.iters * 1e3
+        for mode in modes:
+            outs = {"a": batched(mode), "b": sequential(mode)}                # engines, graphs, packed (+ quantised) weights
+            ms = {"a_batch_samples": [], "b_sequential_samples": []}
+            for _ in range(args.pairs):                                       # a, b, a, b, ...: same box, interleaved
+                ms["a_batch_samples"].append(timed(batched, mode))
+                ms["b_sequential_samples"].append(timed(sequential, mode))
+            engines = m.vlm.__dict__.get("_prefix_engines_batch_samples", {})
+            rel = float(((outs["a"] - outs["b"]) ** 2).sum() ** 0.5 / (outs["b"] ** 2).sum() ** 0.5)
+            print(json.dumps({"metric": "N action chunks for each of B observations, MLA-Llama2-7B: (a) predict_action_diff_batch(num_samples=N), "
+                                        "(b) B sequential predict_action_diff_samples calls; alternating", "suffix_weights": mode, "batch": B,
+                              "samples": N, "action_chunk": chunk, "suffix_rows": B * N * (chunk + 1), "ddim_steps": args.steps,
+                              "pairs": args.pairs, "iters_per_timing": args.iters, "unit": "ms",
+                              "ms": {k: [round(v, 1) for v in vs] for k, vs in ms.items()}, "min_ms": {k: round(min(vs), 1) for k, vs in ms.items()},
+                              "a_minus_b": _pair_stats(ms["b_sequential_samples"], ms["a_batch_samples"]),
+                              "speedup_vs_b": round(min(ms["b_sequential_samples"]) / min(ms["a_batch_samples"]), 2),
+                              "ms_per_chunk": round(min(ms["a_batch_samples"]) / (B * N), 1), "prompt_ids": [int(r.numel()) for r in ids],
+                              "passes": len(engines), "engine_graph": bool(engines) and all(e.graph is not None for e in engines.values()),
+                              "weights_streamed_per_pass_gb": round(wbytes[mode] / 1e9, 2), "a_vs_b_rel_diff_random_weights": round(rel, 5),
+                              "data": "synthetic"}), flush=True)
+            for store in ("_prefix_engines_batch_samples", "_prefix_engines_samples"):     # the caches of this (B, N, mode)
+                m.vlm.__dict__.get(store, {}).clear()
             torch.cuda.empty_cache()
 
 
