@@ -395,6 +395,39 @@ int mla_gemm_suffix_w8_pos(const void* x, long long ldx, const void* W, long lon
                            long long out_batch_stride, int rows_per_batch, const int* slot, int cap_rows, const void* residual,
                            long long ld_res, int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols,
                            const int* rope_pos, int rope_rows, mla_stream_t stream);
+/* ---- compact prefill for ONE observation (mla_amd/infer.py, prefill="compact"; mla_amd/csrc/prefill.hip): row-sized MFMA GEMMs for the
+ * ~545 prefix rows, for which the training GEMM's 256-row tiles leave most of the chip idle. out[M, N] = x[M, K] . W^T with W [N, K]
+ * row-major (ldw), 1 <= M <= 1024, N % 128 == 0 (the column tile), K >= 32 and K % 32 == 0, x / W / out / residual rows 16-B aligned
+ * (pointers, ldx, ldw, ldo, out_batch_stride, ld_res multiples of 8 elements). fp32 accumulation, ONE rounding to bf16. Tile 64 rows x
+ * 128 columns x 64 k per workgroup; split-K until tiles x split >= 2 x 256 CUs (at least 8 K tiles per slice, split <= 16): slice s of a
+ * tile writes its fp32 partial to workspace [split][ceil(M / 64) * 64][N], a second launch adds the slices in the order s = 0, 1, ... and
+ * runs the epilogue. No atomics, no counters, no library-owned memory, no state: the same inputs give the same bits on every run; both
+ * launches go on `stream` and are graph-capturable.
+ *   mla_gemm_prefill_ws_bytes: the workspace bytes the launches need for a shape (0 when the plan does not split), -1 for a shape outside
+ *     the contract. A launch with a smaller (or NULL, or misaligned) workspace returns -1 and launches nothing; split = 1 ignores it.
+ *   mla_gemm_prefill_plan: out4 = {row tile, column tile, split, workgroups of the main launch} as the launcher chooses them for `cus`
+ *     CUs (the launcher itself plans for 256); the pure-Python mirror is mla_amd/hip.py:plan_gemm_prefill.
+ *   mla_gemm_prefill_bf16: out = x W^T (+ residual[m], addressed like x with ld_res). Row m is row m % rows_per_batch of sample
+ *     m / rows_per_batch and is written at out + (m / rows_per_batch) * out_batch_stride + (m % rows_per_batch) * ldo, as in
+ *     mla_gemm_skinny_bf16.
+ *   mla_gemm_prefill_qkv_rope: the same addressing (the rows land straight in a cache's slots); columns [0, rope_cols) are rotated per head
+ *     of 128 in the epilogue, ON THE FP32 SUMS (a' = a cos - b sin, b' = b cos + a sin with b = channel + 64; mla_gemm_qkv_rope rotates the
+ *     bf16-rounded projection: the results differ by that rounding), with table row m % rows_per_batch of rope_cos / rope_sin
+ *     ([rows_per_batch, 64] fp32). rope_cols % 128 == 0, rope_cols <= N, head_dim must be 128.
+ *   mla_gemm_prefill_gateup_swiglu: wgu = the packed [2 I, K] gate|up matrix, I % 64 == 0; act[m, i] = silu(gate) * up with
+ *     swiglu_fwd_elem's arithmetic on the fp32 sums, one rounding. Writes act [M, I] only: no gu, no transposed copy. */
+int mla_gemm_prefill_plan(int M, int N, int K, int cus, int* out4);
+long long mla_gemm_prefill_ws_bytes(int M, int N, int K);
+int mla_gemm_prefill_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
+                          int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, void* workspace,
+                          size_t workspace_bytes, mla_stream_t stream);
+int mla_gemm_prefill_qkv_rope(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo,
+                              long long out_batch_stride, int rows_per_batch, int M, int N, int K, const float* rope_cos,
+                              const float* rope_sin, int rope_cols, int head_dim, void* workspace, size_t workspace_bytes,
+                              mla_stream_t stream);
+int mla_gemm_prefill_gateup_swiglu(const void* x, long long ldx, const void* wgu, long long ldw, void* act, long long ldo,
+                                   long long out_batch_stride, int rows_per_batch, int M, int I, int K, void* workspace,
+                                   size_t workspace_bytes, mla_stream_t stream);
 
 /* ---- losses: CrossEntropyLoss modeling_llama.py:1258-1269; InfoNCE models/mla/fuser/contrastive.py:208-215
  * mla_ce_fwd: lse[r] = logsumexp(logits[r, :ncols]), loss[r] = lse - logits[r, label] (0 for ignore_index or a label outside [0, ncols);

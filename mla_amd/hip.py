@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 from ctypes import c_float, c_int, c_longlong, c_size_t, c_void_p
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -62,6 +62,14 @@ _SIGNATURES = {
                                  c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p],
     "mla_gemm_suffix_w8_pos": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_int,
                                c_void_p, c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p],
+    "mla_gemm_prefill_plan": [c_int, c_int, c_int, c_int, c_void_p],
+    "mla_gemm_prefill_ws_bytes": [c_int, c_int, c_int],      # returns long long (restype fixed up in lib())
+    "mla_gemm_prefill_bf16": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_longlong, c_int,
+                              c_int, c_int, c_void_p, c_size_t, c_void_p],
+    "mla_gemm_prefill_qkv_rope": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_int, c_int, c_int,
+                                  c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p],
+    "mla_gemm_prefill_gateup_swiglu": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_int, c_int,
+                                       c_int, c_void_p, c_size_t, c_void_p],
     "mla_gemm_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                       c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
     "mla_gemm_bf16_ws": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -177,6 +185,7 @@ def lib():
             fn.restype = c_int
         L.mla_attn_bwd_ws_bytes.restype = c_longlong
         L.mla_attn_bwd_sync_ints.restype = c_longlong
+        L.mla_gemm_prefill_ws_bytes.restype = c_longlong
         _lib = L
     return _lib
 
@@ -999,6 +1008,99 @@ def gemm_suffix_w8(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, re
     slice is bit for bit its output). K % 16 == 0; rows, slots, rope, rope_pos (mla_gemm_suffix_w8_pos) and addressing are gemm_suffix's."""
     _suffix_call("mla_gemm_suffix_w8", "gemm_suffix_w8", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows,
                  w_scale, rope_pos=rope_pos, rope_rows=rope_rows)
+
+
+# ---- compact prefill GEMMs (mla_amd/csrc/prefill.hip): 1 <= M <= 1024 rows, 64 x 128 tiles, deterministic split-K through a workspace
+PREFILL_MMAX, PREFILL_BM, PREFILL_BN, PREFILL_BK = 1024, 64, 128, 64
+PREFILL_MAX_SPLIT, PREFILL_MIN_KTILES = 16, 8
+
+
+class PrefillGemmPlan(NamedTuple):
+    """What the prefill launcher does with a shape: tile (rows, columns), split-K factor, workgroups of the main launch, rows covered
+    (M rounded up to the row tile), workspace bytes = split * rows_covered * N * 4 (0 when split == 1), and a note when the plan stays
+    under two workgroups per CU."""
+    tile_m: int
+    tile_n: int
+    split: int
+    workgroups: int
+    rows_covered: int
+    ws_bytes: int
+    note: str
+
+
+def gemm_prefill_fits(M: int, N: int, K: int) -> bool:
+    """True when the compact prefill GEMMs accept the shape: 1 <= M <= 1024, N % 128 == 0 (2 I for the SwiGLU form), K % 32 == 0."""
+    return 1 <= M <= PREFILL_MMAX and N >= PREFILL_BN and N % PREFILL_BN == 0 and K >= 32 and K % 32 == 0
+
+
+def plan_gemm_prefill(M: int, N: int, K: int, cus: int = 256) -> PrefillGemmPlan:
+    """Pure-Python mirror of the launcher's choice (prefill.hip:prefill_plan; mla_gemm_prefill_plan returns the library's): 64 x 128
+    tiles, split-K doubled while tiles x split < 2 x cus, split < 16 and every slice keeps at least 8 K tiles of 64."""
+    if not gemm_prefill_fits(M, N, K):
+        raise ValueError(f"plan_gemm_prefill: 1 <= M <= {PREFILL_MMAX}, N % {PREFILL_BN} == 0, K % 32 == 0 required (M {M}, N {N}, K {K})")
+    mt, nt = -(-M // PREFILL_BM), N // PREFILL_BN
+    tiles, ktiles = mt * nt, -(-K // PREFILL_BK)
+    split = 1
+    while tiles * split < 2 * cus and split < PREFILL_MAX_SPLIT and ktiles // (split * 2) >= PREFILL_MIN_KTILES:
+        split *= 2
+    wgs = tiles * split
+    note = ""
+    if wgs < cus:
+        note = (f"{wgs} workgroups < {cus} CUs: " +
+                (f"split-K is capped at {PREFILL_MAX_SPLIT}" if split == PREFILL_MAX_SPLIT else
+                 f"K = {K} has {ktiles} K tiles, a slice keeps at least {PREFILL_MIN_KTILES}"))
+    return PrefillGemmPlan(PREFILL_BM, PREFILL_BN, split, wgs, mt * PREFILL_BM, split * mt * PREFILL_BM * N * 4 if split > 1 else 0, note)
+
+
+def gemm_prefill_ws_bytes(M: int, N: int, K: int) -> int:
+    """Workspace bytes the library's launcher needs for the shape (mla_gemm_prefill_ws_bytes); -1 outside the contract."""
+    return int(lib().mla_gemm_prefill_ws_bytes(int(M), int(N), int(K)))
+
+
+def _prefill_common(name, x, W, out, ws):
+    _req(x, torch.bfloat16, f"{name} x")
+    _req(W, torch.bfloat16, f"{name} W")
+    _req(out, torch.bfloat16, f"{name} out")
+    assert x.dim() == 2 and W.dim() == 2 and W.shape[1] == x.shape[1] and x.stride(1) == 1 and W.stride(1) == 1
+    if ws is not None:
+        assert ws.is_cuda and ws.is_contiguous()
+    return _p(ws), (ws.numel() * ws.element_size() if ws is not None else 0)
+
+
+def gemm_prefill(x, W, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, ws=None):
+    """out row m (at out + (m // rows_per_batch) * out_batch_stride + (m % rows_per_batch) * ldo + out_col) = x[m] @ W^T (+ residual[m])
+    for 1 <= M <= 1024 rows (mla_gemm_prefill_bf16). `out` is a base tensor: only its data pointer is used. ws: caller-owned scratch of
+    at least gemm_prefill_ws_bytes(M, N, K) bytes (any dtype; may be None when the plan does not split)."""
+    wp, wb = _prefill_common("gemm_prefill", x, W, out, ws)
+    M, K = x.shape
+    if residual is not None:
+        _req(residual, torch.bfloat16, "gemm_prefill residual")
+        assert residual.shape[0] == M and residual.stride(1) == 1
+    call("mla_gemm_prefill_bf16", _p(x), x.stride(0), _p(W), W.stride(0), c_void_p(out.data_ptr() + 2 * out_col), ldo, out_batch_stride,
+         rows_per_batch, _p(residual), residual.stride(0) if residual is not None else 0, M, W.shape[0], K, wp, wb)
+
+
+def gemm_prefill_qkv_rope(x, W, out, ldo, out_batch_stride, rows_per_batch, rope, head_dim=128, ws=None):
+    """gemm_prefill's rows and addressing with the rotary embedding of columns [0, rope_cols) in the epilogue (mla_gemm_prefill_qkv_rope):
+    rope = (cos [rows_per_batch, 64] fp32, sin, rope_cols); row m is rotated with table row m % rows_per_batch, per head of 128."""
+    wp, wb = _prefill_common("gemm_prefill_qkv_rope", x, W, out, ws)
+    cos, sin, rope_cols = rope
+    _req(cos, torch.float32, "gemm_prefill_qkv_rope cos")
+    _req(sin, torch.float32, "gemm_prefill_qkv_rope sin")
+    assert cos.shape == (rows_per_batch, 64) and sin.shape == cos.shape and cos.is_contiguous() and sin.is_contiguous()
+    M, K = x.shape
+    call("mla_gemm_prefill_qkv_rope", _p(x), x.stride(0), _p(W), W.stride(0), _p(out), ldo, out_batch_stride, rows_per_batch, M, W.shape[0], K,
+         _p(cos), _p(sin), int(rope_cols), int(head_dim), wp, wb)
+
+
+def gemm_prefill_gateup_swiglu(x, wgu, act, ldo=None, out_batch_stride=0, rows_per_batch=None, ws=None):
+    """act[m] = silu(x[m] @ Wg^T) * (x[m] @ Wu^T) for the packed wgu = [Wg; Wu] [2 I, K] (mla_gemm_prefill_gateup_swiglu): the product is
+    formed in the epilogue on the fp32 sums; nothing but act [M, I] is written. Addressing as gemm_prefill (default: act's own rows)."""
+    wp, wb = _prefill_common("gemm_prefill_gateup_swiglu", x, wgu, act, ws)
+    M, K = x.shape
+    assert wgu.shape[0] % 2 == 0
+    call("mla_gemm_prefill_gateup_swiglu", _p(x), x.stride(0), _p(wgu), wgu.stride(0), _p(act), act.stride(0) if ldo is None else ldo,
+         out_batch_stride, M if rows_per_batch is None else rows_per_batch, M, wgu.shape[0] // 2, K, wp, wb)
 
 
 def attn_chunk_ragged(cache, B, nheads, D, kv_len, R, scale):

@@ -52,6 +52,18 @@ def check_suffix_weights(mode):
         raise ValueError(f"suffix_weights must be one of {SUFFIX_WEIGHT_MODES}, got {mode!r}")
 
 
+# How the prefix rows are prefilled (MLA.predict_action_diff(prefill=...)):
+#   "train"    the training forward kernels (ops.DecoderLayerFn._fwd: 256-row GEMM tiles built for 17 536 rows), default
+#   "compact"  the row-sized GEMMs of mla_amd/csrc/prefill.hip (64 x 128 tiles, deterministic split-K): q|k|v + RoPE written straight into
+#              the cache, gate|up + SwiGLU writing the product only; same function up to summation order and rounding points
+PREFILL_MODES = ("train", "compact")
+
+
+def check_prefill(mode):
+    if mode not in PREFILL_MODES:
+        raise ValueError(f"prefill must be one of {PREFILL_MODES}, got {mode!r}")
+
+
 class W8(NamedTuple):
     """A quantised projection weight: q [N, K] float8_e4m3fn codes, scale [N] fp32 (one per output channel)."""
     q: torch.Tensor
@@ -62,9 +74,12 @@ class _CachedEpsBase:
     """What the cached-prefix engines share: the packed weights, the captured suffix pass and the `model(x, t)` call of the samplers.
     A subclass provides prefill() and _suffix_pass() and sets B, R, T, H, h_in, h_out, cache."""
 
-    def __init__(self, vlm, n_action_rows: int = 1, suffix_weights: str = "bf16"):
+    def __init__(self, vlm, n_action_rows: int = 1, suffix_weights: str = "bf16", prefill: str = "train"):
         check_suffix_weights(suffix_weights)
+        check_prefill(prefill)
         self.suffix_weights = suffix_weights
+        self.prefill_mode = prefill
+        self._prefill_ws = None      # "compact": the split-K workspace of the prefill GEMMs, allocated once beside h_in / h_out
         self.vlm = vlm
         llm = vlm.llm_backbone.llm
         self.model, self.cfg = llm.model, llm.config
@@ -145,6 +160,50 @@ class _CachedEpsBase:
         proprio_e = vlm.proprio_embedder(proprio.to(torch.bfloat16))
         return torch.cat([text_emb[:, :1]] + parts + [text_emb[:, 1:k], proprio_e], dim=1).contiguous()
 
+    # ------------------------------------------------------------------------------------------ the compact prefill
+    def _check_compact(self, rows: int):
+        """prefill="compact" serves at most 1024 prefix rows at head_dim 128; anything else is an error, never a silent "train" prefill."""
+        if self.prefill_mode != "compact":
+            return
+        D = self.cfg.hidden_size // self.nheads
+        if rows > hip.PREFILL_MMAX or D != 128:
+            raise ValueError(f"prefill=\"compact\" serves at most {hip.PREFILL_MMAX} prefix rows at head_dim 128 (got {rows} rows, head_dim "
+                             f"{D}); use prefill=\"train\"")
+
+    def _compact_ws(self, rows: int, dev):
+        """One workspace for the four projections of a layer at `rows` rows (the launches of a prefill run one after the other)."""
+        H, I = self.cfg.hidden_size, self.cfg.intermediate_size
+        need = max(hip.gemm_prefill_ws_bytes(rows, N, K) for N, K in ((3 * H, H), (H, H), (2 * I, H), (H, I)))
+        if need < 0:
+            raise ValueError(f"prefill=\"compact\": the projections of this model (hidden {H}, intermediate {I}) are outside the compact "
+                             "GEMMs' contract (N % 128 == 0, K % 32 == 0); use prefill=\"train\"")
+        return torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+
+    def _compact_prefill(self, h, B, S_p, cache_out, out_bs):
+        """The decoder layers over the B * S_p prefix rows h [B * S_p, H] on the compact GEMMs; cache_out[l] is layer l's cache tensor whose
+        sample b holds its rows at element offset b * out_bs + p * row stride. Per layer: rmsnorm_fwd, q|k|v + RoPE into the cache, the
+        training flash attention on the cache's q / k / v views, o + residual, rmsnorm_fwd, gate|up + SwiGLU (the product only), down +
+        residual."""
+        H, nh, D, ws = self.H, self.nheads, self.D, self._prefill_ws
+        scale = 1.0 / math.sqrt(D)
+        for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd), c in zip(self._weights(), cache_out):
+            wqkv, wgu = ops.cat_view((wq, wk, wv)), ops.cat_view((wg, wu))
+            assert wqkv is not None and wgu is not None, "the packed weights are adjacent in memory (_weights)"
+            ld = c.stride(-2)
+            xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
+            hip.gemm_prefill_qkv_rope(xn, wqkv, c, ld, out_bs, S_p, (self.cos_p, self.sin_p, 2 * H), D, ws=ws)
+            flat = c.reshape(-1)
+            o = [hip.attn_fwd(*(flat[b * out_bs + j * H:] for j in range(3)), 1, S_p, nh, D, ld, None, scale)[0] for b in range(B)]
+            o = o[0] if B == 1 else torch.cat(o, 0)
+            h1 = torch.empty_like(h)
+            hip.gemm_prefill(o, wo, h1, H, 0, B * S_p, residual=h, ws=ws)
+            xn2, _ = hip.rmsnorm_fwd(h1, ln2, self.eps)
+            act = torch.empty((B * S_p, wg.shape[0]), dtype=torch.bfloat16, device=h.device)
+            hip.gemm_prefill_gateup_swiglu(xn2, wgu, act, ws=ws)
+            h = torch.empty_like(h1)
+            hip.gemm_prefill(act, wd, h, H, 0, B * S_p, residual=h1, ws=ws)
+        return h
+
     def _run(self):
         if _USE_GRAPH and not self._graph_failed:
             if self.graph is None:
@@ -217,18 +276,21 @@ class PrefixCachedEps(_CachedEpsBase):
         return False
 
     @classmethod
-    def for_inputs(cls, vlm, input_ids, n_action_rows: int = 1, suffix_weights: str = "bf16", **model_kwargs):
+    def for_inputs(cls, vlm, input_ids, n_action_rows: int = 1, suffix_weights: str = "bf16", prefill: str = "train", **model_kwargs):
         check_suffix_weights(suffix_weights)
+        check_prefill(prefill)
         k = cls._splice_position(input_ids)
         engines = vlm.__dict__.setdefault("_prefix_engines", {})
         key = (int(input_ids.shape[0]), k, int(n_action_rows), str(input_ids.device))
         if suffix_weights != "bf16":
             key += (suffix_weights,)                                          # a captured graph holds the addresses of ITS weights
+        if prefill != "train":
+            key += ("prefill:" + prefill,)                                    # the mode is part of the key: the engines coexist
         eng = engines.get(key)
         if eng is None:
             if len(engines) >= 4:                                             # a handful of prompt lengths per process; each engine holds 0.4 GB at 7B
                 engines.pop(next(iter(engines)))
-            eng = engines[key] = cls(vlm, n_action_rows, suffix_weights)
+            eng = engines[key] = cls(vlm, n_action_rows, suffix_weights, prefill)
         eng.prefill(input_ids, k, **model_kwargs)
         return eng
 
@@ -237,6 +299,7 @@ class PrefixCachedEps(_CachedEpsBase):
         with torch.no_grad():
             prefix = self._prefix_rows(input_ids, k, images, point_cloud, camera_name, proprio, tactile, gripper_xyz)       # [B, S_p, H]
             B, S_p, H = prefix.shape
+            self._check_compact(B * S_p)
             if self.cache is None:
                 self.B, self.S_p, self.H = B, S_p, H
                 self.S_cap = S_p + self.R
@@ -249,9 +312,14 @@ class PrefixCachedEps(_CachedEpsBase):
                     self.cache = [torch.empty((B, self.S_cap, 3 * H), dtype=bf16, device=dev) for _ in self.model.layers]
                     self.h_in = torch.zeros((B * self.R, H), dtype=bf16, device=dev)
                     self.h_out = torch.zeros((B * self.R, H), dtype=bf16, device=dev)
+                    if self.prefill_mode == "compact":
+                        self._prefill_ws = self._compact_ws(B * S_p, dev)
             assert (B, S_p, H) == (self.B, self.S_p, self.H)
-            # ---- prefill: the training forward kernels, one layer at a time; keep the packed post-RoPE q|k|v rows
             h = prefix.reshape(B * S_p, H)
+            if self.prefill_mode == "compact":                               # the row-sized GEMMs write the cache rows themselves
+                self._compact_prefill(h, B, S_p, self.cache, self.cache[0].stride(0))
+                return
+            # ---- prefill: the training forward kernels, one layer at a time; keep the packed post-RoPE q|k|v rows
             for w, c in zip(self._weights(), self.cache):
                 h, acts = ops.DecoderLayerFn._fwd(h, None, self.cos_p, self.sin_p, B, S_p, self.nheads, self.eps, w)
                 c[:, :S_p].copy_(acts.qkv[:B * S_p].view(B, S_p, 3 * H))
@@ -553,10 +621,12 @@ class SampleGroupsEps(_CachedEpsBase):
         return False
 
     @classmethod
-    def for_inputs(cls, vlm, input_ids, n_action_rows: int, num_samples: int, suffix_weights: str = "bf16", **model_kwargs):
+    def for_inputs(cls, vlm, input_ids, n_action_rows: int, num_samples: int, suffix_weights: str = "bf16", prefill: str = "train",
+                   **model_kwargs):
         """-> (engine, prefilled for this observation; passes [(start, stop), ...] of plan_sample_groups). One engine -- and its graphs --
-        per suffix_weights mode, as in PrefixCachedEps.for_inputs."""
+        per suffix_weights and prefill mode, as in PrefixCachedEps.for_inputs."""
         check_suffix_weights(suffix_weights)
+        check_prefill(prefill)
         k = PrefixCachedEps._splice_position(input_ids)
         passes = plan_sample_groups(num_samples, 1 + n_action_rows, cls.MAX_ROWS)
         capacity = max(stop - start for start, stop in passes)
@@ -564,16 +634,18 @@ class SampleGroupsEps(_CachedEpsBase):
         key = (k, int(n_action_rows), capacity, str(input_ids.device))
         if suffix_weights != "bf16":
             key += (suffix_weights,)                                          # a captured graph holds the addresses of ITS weights
+        if prefill != "train":
+            key += ("prefill:" + prefill,)
         eng = engines.get(key)
         if eng is None:
             if len(engines) >= 4:
                 engines.pop(next(iter(engines)))
-            eng = engines[key] = cls(vlm, n_action_rows, capacity, suffix_weights)
+            eng = engines[key] = cls(vlm, n_action_rows, capacity, suffix_weights, prefill)
         eng.prefill(input_ids, k, **model_kwargs)
         return eng, passes
 
-    def __init__(self, vlm, n_action_rows: int, capacity: int, suffix_weights: str = "bf16"):
-        super().__init__(vlm, n_action_rows, suffix_weights)
+    def __init__(self, vlm, n_action_rows: int, capacity: int, suffix_weights: str = "bf16", prefill: str = "train"):
+        super().__init__(vlm, n_action_rows, suffix_weights, prefill)
         self.capacity = int(capacity)
         self._graphs = {}            # G -> captured pass over G groups
         self._graphs_packed = None   # the packed weights those graphs hold the addresses of
@@ -590,6 +662,7 @@ class SampleGroupsEps(_CachedEpsBase):
         with torch.no_grad():
             prefix = self._prefix_rows(input_ids, k, images, point_cloud, camera_name, proprio, tactile, gripper_xyz)
             _, S_p, H = prefix.shape
+            self._check_compact(S_p)
             if self.cache is None:
                 self.S_p, self.H = S_p, H
                 self.D = H // self.nheads
@@ -602,6 +675,8 @@ class SampleGroupsEps(_CachedEpsBase):
                     self._h_in = torch.zeros((rows, H), dtype=bf16, device=dev)
                     self._h_out = torch.zeros((rows, H), dtype=bf16, device=dev)
                     self.slot = torch.full((self.capacity,), S_p, dtype=torch.int32, device=dev)
+                    if self.prefill_mode == "compact":
+                        self._prefill_ws = self._compact_ws(S_p, dev)
                 self.set_groups(self.capacity)
             assert (S_p, H) == (self.S_p, self.H)
             weights = self._weights()
@@ -610,6 +685,9 @@ class SampleGroupsEps(_CachedEpsBase):
                 self._graphs_packed = self._suffix
                 self.graph = None
             h = prefix.reshape(S_p, H)
+            if self.prefill_mode == "compact":
+                self._compact_prefill(h, 1, S_p, self.cache, 0)
+                return
             for w, c in zip(weights, self.cache):
                 h, acts = ops.DecoderLayerFn._fwd(h, None, self.cos_p, self.sin_p, 1, S_p, self.nheads, self.eps, w)
                 c[:S_p].copy_(acts.qkv[:S_p])

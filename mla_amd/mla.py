@@ -331,7 +331,7 @@ class MLA(nn.Module):
                             unnorm_key: Optional[str] = None, cfg_scale: float = 0.0, use_ddim: bool = True, num_ddim_steps: int = 8,
                             action_dim: int = 7, *, input_ids: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                             camera_name: str = "rlbench_front", reuse_prefix: bool = True, suffix_weights: str = "bf16",
-                            **kwargs) -> np.ndarray:
+                            prefill: str = "train", **kwargs) -> np.ndarray:
         """model_mla.py:592-775: 8-step DDIM (eta = 0) over the action chunk with the VLM as the epsilon model, then
         un-normalisation.
         * ``image`` is a PIL image / uint8 HWC frame (pre-processed here like the reference does, :656-660) or an already
@@ -349,9 +349,17 @@ class MLA(nn.Module):
         ``suffix_weights`` (opt-in, cached prefix only): "bf16" (default) | "fp8": the sampler steps stream a per-row e4m3fn copy of the
         decoder weights (mla_gemv_w8 / mla_gemm_skinny_w8: half the bytes per step; the prefill keeps the bf16 weights) | "fp8_as_bf16":
         the bf16 kernels on the dequantised copy -- what the format costs on a checkpoint, without the FP8 kernels. Anything but "bf16"
-        raises when the cached prefix is off or does not serve the shape: there is no silent bf16 fallback."""
-        from .infer import check_suffix_weights
+        raises when the cached prefix is off or does not serve the shape: there is no silent bf16 fallback.
+        ``prefill`` (opt-in, cached prefix only): "train" (default) runs the prefix rows on the training kernels; "compact" on the
+        row-sized GEMMs of mla_amd/csrc/prefill.hip (q|k|v + RoPE written straight into the cache, gate|up + SwiGLU writing the product
+        only): the same function up to summation order and rounding points. "compact" raises ValueError when ``reuse_prefix=False``, the
+        cached-prefix engine does not serve the shape, the prefix has more than 1024 rows or head_dim is not 128: no silent fallback."""
+        from .infer import check_prefill, check_suffix_weights
         check_suffix_weights(suffix_weights)
+        check_prefill(prefill)
+        if prefill != "train" and not reuse_prefix:
+            raise ValueError(f"prefill={prefill!r} needs the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has no "
+                             "separate prefill")
         self.vlm.eval()
         device = next(self.vlm.parameters()).device
         if input_ids is None:
@@ -373,9 +381,12 @@ class MLA(nn.Module):
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached-prefix engine (reuse_prefix=True and a shape "
                              "PrefixCachedEps.supports); the whole-forward sampler has bf16 weights only")
+        if prefill != "train" and not reuse_prefix:
+            raise ValueError(f"prefill={prefill!r}: the cached-prefix engine does not serve this shape (PrefixCachedEps.supports: at most "
+                             "64 suffix rows, head_dim 128); use prefill=\"train\"")
         if reuse_prefix:
             eps_model = PrefixCachedEps.for_inputs(self.vlm, n_action_rows=self.future_action_window_size + 1,
-                                                   suffix_weights=suffix_weights, **model_kwargs)
+                                                   suffix_weights=suffix_weights, prefill=prefill, **model_kwargs)
         if use_ddim and num_ddim_steps is not None:
             if self.ddim_diffusion is None:
                 self.create_ddim(ddim_step=num_ddim_steps)
@@ -392,7 +403,7 @@ class MLA(nn.Module):
                                   cfg_scale: float = 0.0, use_ddim: bool = True, num_ddim_steps: int = 8, action_dim: int = 7, *,
                                   input_ids=None, noise: Optional[torch.Tensor] = None, camera_name: str = "rlbench_front",
                                   reuse_prefix: bool = True, suffix_weights: str = "bf16",
-                                  num_samples: Optional[int] = None) -> np.ndarray:
+                                  num_samples: Optional[int] = None, prefill: str = "train") -> np.ndarray:
         """B observations -> [B, T, action_dim]: by definition B independent `predict_action_diff` calls (the reference's
         `predict_action_batch`, model_mla.py:994, is dead code), computed on ONE cached prefix pass per DDIM step
         (mla_amd/infer.py:BatchedPrefixCachedEps): the prompts may have different lengths, the FPS start indices are drawn once per chunk.
@@ -411,9 +422,15 @@ class MLA(nn.Module):
         control flow; N > 256 // (1 + T) loops predict_action_diff_samples per observation (it splits its passes on one prefill); a shape
         the engine does not serve warns once and loops the same way. All three ``suffix_weights`` modes are accepted (N = 1 included: this
         is how B >= 2 observations get FP8 suffix weights); anything but "bf16" raises ValueError when ``reuse_prefix=False`` or the
-        engine does not serve the shape."""
-        from .infer import check_suffix_weights
+        engine does not serve the shape.
+        ``prefill``: only "train" -- the batched prefill has B x S rows and belongs to the training GEMMs; "compact" raises
+        NotImplementedError (use predict_action_diff / predict_action_diff_samples per observation)."""
+        from .infer import check_prefill, check_suffix_weights
         check_suffix_weights(suffix_weights)
+        check_prefill(prefill)
+        if prefill != "train":
+            raise NotImplementedError(f"prefill={prefill!r}: the batched engines prefill B x S rows on the training GEMMs; the compact "
+                                      "prefill serves one observation (predict_action_diff, predict_action_diff_samples)")
         B = len(images)
         T = self.future_action_window_size + 1
         if num_samples is not None:
@@ -550,7 +567,7 @@ class MLA(nn.Module):
                                     unnorm_key: Optional[str] = None, num_samples: int = 1, cfg_scale: float = 0.0, use_ddim: bool = True,
                                     num_ddim_steps: int = 8, action_dim: int = 7, *, input_ids: Optional[torch.Tensor] = None,
                                     noise: Optional[torch.Tensor] = None, camera_name: str = "rlbench_front",
-                                    reuse_prefix: bool = True, suffix_weights: str = "bf16") -> np.ndarray:
+                                    reuse_prefix: bool = True, suffix_weights: str = "bf16", prefill: str = "train") -> np.ndarray:
         """N action chunks for ONE observation -> [N, T, action_dim]: by definition N independent `predict_action_diff` calls on the same
         observation with the initial samples ``noise[n]`` (critic / best-of-N choice, uncertainty estimates, temporal ensembling), computed
         on ONE cached prefix (mla_amd/infer.py:SampleGroupsEps): the encoders and the decoder prefill run once per call, every sampler step
@@ -563,9 +580,16 @@ class MLA(nn.Module):
         ``suffix_weights`` (opt-in): predict_action_diff's modes. "fp8": every pass streams the per-row e4m3fn copy of the decoder weights
         (mla_gemm_suffix_w8: half the weight bytes per sampler step; the prefill and the prefix keys / values keep the bf16 weights);
         "fp8_as_bf16": the bf16 kernel on the dequantised copy. Forwarded for ``num_samples=1``. Anything but "bf16" raises ValueError
-        when ``reuse_prefix=False`` or the shared-prefix engine does not serve the shape: no silent bf16 fallback, no silent loop."""
-        from .infer import check_suffix_weights
+        when ``reuse_prefix=False`` or the shared-prefix engine does not serve the shape: no silent bf16 fallback, no silent loop.
+        ``prefill`` (opt-in): predict_action_diff's modes; "compact" runs the one prefill of the call on the row-sized GEMMs. Forwarded
+        for ``num_samples=1``; raises ValueError when ``reuse_prefix=False``, the shared-prefix engine does not serve the shape, the prefix
+        has more than 1024 rows or head_dim is not 128."""
+        from .infer import check_prefill, check_suffix_weights
         check_suffix_weights(suffix_weights)
+        check_prefill(prefill)
+        if prefill != "train" and not reuse_prefix:
+            raise ValueError(f"prefill={prefill!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has no separate "
+                             "prefill")
         N = int(num_samples)
         T = self.future_action_window_size + 1
         if N < 1:
@@ -579,12 +603,15 @@ class MLA(nn.Module):
                                             action_dim, input_ids=input_ids, noise=None if noise is None else noise[n:n + 1],
                                             camera_name=camera_name, **kw)
         if N == 1:
-            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights)[None]
+            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, prefill=prefill)[None]
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
                              "bf16 weights only")
         if reuse_prefix:
             from .infer import SampleGroupsEps
+            if prefill != "train" and not SampleGroupsEps.supports_samples(self.vlm, T, warn=False):
+                raise ValueError(f"prefill={prefill!r}: the shared-prefix engine (SampleGroupsEps) does not serve {1 + T} suffix rows per "
+                                 "sample at this head_dim; use prefill=\"train\"")
             if suffix_weights != "bf16" and not SampleGroupsEps.supports_samples(self.vlm, T, warn=False):   # raised, not a warned loop of batch-1 calls
                 raise ValueError(f"suffix_weights={suffix_weights!r}: the shared-prefix engine (SampleGroupsEps) does not serve {1 + T} "
                                  "suffix rows per sample at this head_dim; draw the samples with \"bf16\" or one predict_action_diff call "
@@ -607,7 +634,7 @@ class MLA(nn.Module):
         x0 = torch.cat(draws, dim=0).float()
         if use_ddim and num_ddim_steps is not None and self.ddim_diffusion is None:
             self.create_ddim(ddim_step=num_ddim_steps)
-        eng, passes = SampleGroupsEps.for_inputs(self.vlm, input_ids, T, N, suffix_weights=suffix_weights, **model_kwargs)
+        eng, passes = SampleGroupsEps.for_inputs(self.vlm, input_ids, T, N, suffix_weights=suffix_weights, prefill=prefill, **model_kwargs)
         out = []
         for start, stop in passes:                                           # one prefill, then the passes' sampler loops one after the other
             eng.set_groups(stop - start)

@@ -31,6 +31,12 @@
                                                           (b) B sequential predict_action_diff_samples calls; --pair-fp8 measures both forms
                                                           with bf16 and with fp8 suffix weights; --kernel-table adds
                                                           mla_attn_chunk_ragged_groups per launch against mla_attn_chunk_groups run per sample
+    python tools/bench_infer.py --pair-prefill [--pairs P] [--chunk C] [--kernel-table]
+                                                          prefill="train" and prefill="compact" alternating in one process, in pairs, with
+                                                          bf16 and with fp8 suffix weights: per-chunk latency, the whole prefill (encoders +
+                                                          decoder rows) and the decoder rows alone, with the 95 % interval of the pair
+                                                          differences; --kernel-table adds the four projections of a 7B layer at the
+                                                          prefix's row count, training kernel vs compact kernel, per launch
 Prints one JSON line per measurement (not the driver's bench contract -- that is bench.py)."""
 import argparse
 import json
@@ -54,6 +60,7 @@ def main():
                     "--samples: B[,B..] paired with N[,N..]")
     ap.add_argument("--suffix-weights", choices=["bf16", "fp8", "fp8_as_bf16"], default="bf16")
     ap.add_argument("--pair-fp8", action="store_true", help="alternate bf16 and fp8 chunks in one process, in pairs")
+    ap.add_argument("--pair-prefill", action="store_true", help="alternate prefill=\"train\" and prefill=\"compact\" in one process, in pairs")
     ap.add_argument("--pairs", type=int, default=6)
     ap.add_argument("--kernel-table", action="store_true", help="with --pair-fp8: the two _w8 kernels per projection shape and M; with "
                     "--samples: mla_attn_chunk_groups per groups-per-workgroup against mla_attn_chunk_ragged")
@@ -68,6 +75,8 @@ def main():
         return main_samples_pair(args) if args.pair_fp8 else main_samples(args)
     if args.batch > 0:
         return main_batch(args)
+    if args.pair_prefill:
+        return main_pair_prefill(args)
     if args.pair_fp8:
         return main_pair(args)
     from bench import build
@@ -234,6 +243,140 @@ def main_pair(args):
                 row[name] = cell
             table[f"M{M}"] = row
         out["w8_kernel_us_per_launch"] = table
+    print(json.dumps(out))
+
+
+def main_pair_prefill(args):
+    """prefill="train" vs prefill="compact" on the same box, alternating: (a) predict_action_diff per chunk with bf16 and with fp8 suffix
+    weights, (b) engine.prefill() = encoders + the decoder rows of the prefix, (c) the decoder rows alone on given prefix rows."""
+    from bench import build
+    from mla_amd import hip, ops
+    from mla_amd.infer import PrefixCachedEps
+    from mla_amd.synthetic import make_batch
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    m = build(dev, 1)
+    m.future_action_window_size = m.vlm.future_action_window_size = args.chunk - 1
+    m.eval()
+    for p in m.parameters():
+        p.data = p.data.to(torch.bfloat16)
+    b = make_batch(B=1, device=dev)
+    ids = torch.cat([b["input_ids"][:, :-4], torch.tensor([[29871]], device=dev)], dim=1)
+    noise = torch.randn(1, args.chunk, 7, device=dev)
+    kw = dict(image=b["images"]["front_image"][0], pointcloud=b["point_cloud"][0], cur_robot_state=b["proprio"][0, 0].cpu().numpy(),
+              input_ids=ids, num_ddim_steps=args.steps, noise=noise)
+    mk = dict(input_ids=ids, images=b["images"]["front_image"][:1], point_cloud=b["point_cloud"][:1], camera_name="rlbench_front",
+              proprio=b["proprio"][:1])
+    modes, weights = ("train", "compact"), ("bf16", "fp8")
+    acts = {(w, mode): m.predict_action_diff(suffix_weights=w, prefill=mode, **kw) for w in weights for mode in modes}   # engines, graphs
+    k = PrefixCachedEps._splice_position(ids)
+    with torch.inference_mode():
+        eng = {mode: PrefixCachedEps.for_inputs(m.vlm, n_action_rows=args.chunk, prefill=mode, **mk) for mode in modes}
+        prefix = eng["train"]._prefix_rows(ids, k, mk["images"], mk["point_cloud"], mk["camera_name"], mk["proprio"])
+    S_p, H = eng["train"].S_p, eng["train"].H
+
+    def chunk_ms(w, mode):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.iters):
+            m.predict_action_diff(suffix_weights=w, prefill=mode, **kw)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.iters * 1e3
+
+    def timed(fn, reps=3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.inference_mode():
+            fn()
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    def layers_only(mode):
+        e = eng[mode]
+        h = prefix.reshape(S_p, H)
+        if mode == "compact":
+            return lambda: e._compact_prefill(h, 1, S_p, e.cache, e.cache[0].stride(0))
+
+        def train():
+            x = h
+            for w, c in zip(e._weights(), e.cache):
+                x, a = ops.DecoderLayerFn._fwd(x, None, e.cos_p, e.sin_p, 1, S_p, e.nheads, e.eps, w)
+                c[:, :S_p].copy_(a.qkv[:S_p].view(1, S_p, 3 * H))
+        return train
+    chunk = {(w, mode): [] for w in weights for mode in modes}
+    prefill = {mode: [] for mode in modes}
+    layers = {mode: [] for mode in modes}
+    for _ in range(args.pairs):                                             # train, compact, train, compact, ...: same box, interleaved
+        for w in weights:
+            for mode in modes:
+                chunk[(w, mode)].append(chunk_ms(w, mode))
+        for mode in modes:
+            prefill[mode].append(timed(lambda: eng[mode].prefill(ids, k, **{a: v for a, v in mk.items() if a != "input_ids"})))
+        for mode in modes:
+            layers[mode].append(timed(layers_only(mode)))
+    rel = lambda a, b: round(float(((a - b) ** 2).sum() ** 0.5 / (b ** 2).sum() ** 0.5), 4)
+    out = {"metric": "predict_action_diff, MLA-Llama2-7B, batch 1: prefill=train vs prefill=compact in alternating pairs",
+           "action_chunk": args.chunk, "prefix_rows": S_p, "ddim_steps": args.steps, "pairs": args.pairs, "unit": "ms",
+           "chunk_ms": {f"{w}/{mode}": [round(v, 2) for v in vs] for (w, mode), vs in chunk.items()},
+           "chunk_compact_minus_train": {w: _pair_stats(chunk[(w, "train")], chunk[(w, "compact")]) for w in weights},
+           "prefill_with_encoders_ms": {mode: [round(v, 2) for v in vs] for mode, vs in prefill.items()},
+           "prefill_with_encoders_compact_minus_train": _pair_stats(prefill["train"], prefill["compact"]),
+           "decoder_rows_only_ms": {mode: [round(v, 2) for v in vs] for mode, vs in layers.items()},
+           "decoder_rows_only_compact_minus_train": _pair_stats(layers["train"], layers["compact"]),
+           "compact_vs_train_chunk_rel_diff_random_weights": {w: rel(acts[(w, "compact")], acts[(w, "train")]) for w in weights},
+           "data": "synthetic"}
+    if args.kernel_table:
+        # the four projections of a layer at the prefix's row count, cycling through the 32 layers' weights (nothing stays in the caches),
+        # captured into a graph as a run of launches: training kernel vs compact kernel, us per launch
+        packed = eng["train"]._weights()
+        ws = eng["compact"]._prefill_ws
+        I = packed[0][6].shape[0]
+        xh = (torch.randn(S_p, H, device=dev) * 0.5).to(torch.bfloat16)
+        xi = (torch.randn(S_p, I, device=dev) * 0.5).to(torch.bfloat16)
+        res = torch.randn(S_p, H, device=dev).to(torch.bfloat16)
+        qkv = torch.empty(S_p, 3 * H, dtype=torch.bfloat16, device=dev)
+        oh = torch.empty(S_p, H, dtype=torch.bfloat16, device=dev)
+        act = torch.empty(S_p, I, dtype=torch.bfloat16, device=dev)
+        cos, sin = eng["train"].cos_p, eng["train"].sin_p
+        forms = {
+            "qkv_rope": (lambda L: hip.gemm_qkv_rope(xh, ops.cat_view(L[1:4]), qkv, cos, sin, S_p, 2 * H),
+                         lambda L: hip.gemm_prefill_qkv_rope(xh, ops.cat_view(L[1:4]), qkv, 3 * H, 0, S_p, (cos, sin, 2 * H), 128, ws=ws)),
+            "o_res": (lambda L: hip.gemm(xh, L[4], oh, residual=res),
+                      lambda L: hip.gemm_prefill(xh, L[4], oh, H, 0, S_p, residual=res, ws=ws)),
+            "gateup_swiglu": (lambda L: hip.gemm_gateup_swiglu(xh, ops.cat_view(L[6:8]), False),
+                              lambda L: hip.gemm_prefill_gateup_swiglu(xh, ops.cat_view(L[6:8]), act, ws=ws)),
+            "down_res": (lambda L: hip.gemm(xi, L[8], oh, residual=res),
+                         lambda L: hip.gemm_prefill(xi, L[8], oh, H, 0, S_p, residual=res, ws=ws)),
+        }
+        table = {}
+        for name, fns in forms.items():
+            cell = {}
+            for kname, fn in zip(modes, fns):
+                for L in packed[:2]:
+                    fn(L)
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    for L in packed:
+                        fn(L)
+                g.replay()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(3):
+                    g.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                cell[kname] = round(e0.elapsed_time(e1) / (3 * len(packed)) * 1e3, 1)
+            N, K = {"qkv_rope": (3 * H, H), "o_res": (H, H), "gateup_swiglu": (2 * I, H), "down_res": (H, I)}[name]
+            p = hip.plan_gemm_prefill(S_p, N, K)
+            cell["compact_plan"] = {"split": p.split, "workgroups": p.workgroups}
+            cell["compact_tflops"] = round(2.0 * S_p * N * K / (cell["compact"] * 1e-6) / 1e12, 1)
+            cell["train_tflops"] = round(2.0 * S_p * N * K / (cell["train"] * 1e-6) / 1e12, 1)
+            table[name] = cell
+        out["projection_us_per_launch"] = table
     print(json.dumps(out))
 
 
