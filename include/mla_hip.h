@@ -429,6 +429,22 @@ int mla_gemm_prefill_gateup_swiglu(const void* x, long long ldx, const void* wgu
                                    long long out_batch_stride, int rows_per_batch, int M, int I, int K, void* workspace,
                                    size_t workspace_bytes, mla_stream_t stream);
 
+/* ---- device-resident DDIM loop (mla_amd/infer.py _CachedEpsBase.sample_ddim, opt-in sampler="device"; mla_amd/csrc/sampler.hip): the
+ * sampler's glue between two suffix passes with the step index in device memory, so that a captured sampler step can be replayed
+ * num_ddim_steps times without a host round trip. Stateless, no allocation, no host access, on `stream`, graph-capturable.
+ *   mla_ddim_step: s = *step; for 0 <= s < steps the eta = 0 DDIM update of GaussianDiffusion.ddim_sample (gaussian_diffusion.py:520-568,
+ *     clip_denoised = False) with coef[s] = {a, b, c, d} ([steps, 4] fp32: sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod,
+ *     sqrt(alphas_cumprod_prev), sqrt(1 - alphas_cumprod_prev), GaussianDiffusion.ddim_tables): ax = a x; px = ax - b eps;
+ *     e2 = (ax - px) / b; x = px c + d e2, every operation rounded on its own (no FMA contraction): the host loop's bits. x [n] fp32 is
+ *     updated in place, eps [n] bf16, x_bf16 [n] = bf16_rne(x) is written; with `advance` the counter then becomes s - 1 (thread 0, behind
+ *     a workgroup barrier). Any other s: nothing is written, the counter stays. One workgroup; 1 <= n <= 65 536.
+ *   mla_sampler_rows: with R = 1 + T, for 0 <= *step < steps: h_in row g R = t_table[*step] ([steps, H] bf16), row g R + 1 + p =
+ *     x_e[g T + p] (g < G, p < T); any other *step writes nothing. h_in [G R, H], x_e [G T, H] bf16, H % 8 == 0, 16-B aligned rows. */
+int mla_ddim_step(float* x, const void* eps, void* x_bf16, const float* coef, int* step, int n, int steps, int advance,
+                  mla_stream_t stream);
+int mla_sampler_rows(void* h_in, const void* t_table, const void* x_e, const int* step, int G, int T, int H, int steps,
+                     mla_stream_t stream);
+
 /* ---- losses: CrossEntropyLoss modeling_llama.py:1258-1269; InfoNCE models/mla/fuser/contrastive.py:208-215
  * mla_ce_fwd: lse[r] = logsumexp(logits[r, :ncols]), loss[r] = lse - logits[r, label] (0 for ignore_index or a label outside [0, ncols);
  * labels == null: label = r). A logit of -inf is a masked column and adds nothing, on bf16 and fp32 rows alike (as F.cross_entropy);

@@ -1,0 +1,78 @@
+// The DDIM sampler's glue on the device (mla_amd/infer.py:_CachedEpsBase.sample_ddim): the per-step update of the action chunk and the
+// assembly of the suffix pass's input rows. The step index lives in device memory and is counted down by the update kernel, so a sampler
+// step depends on nothing the host knows: the host enqueues `steps` replays of one captured step and reads the result.
+// Both kernels are stateless, allocate nothing, launch on the caller's stream and are graph-capturable.
+#include "common.h"
+
+namespace {
+
+// GaussianDiffusion.ddim_sample at eta = 0, clip_denoised = False (models/diffusion/gaussian_diffusion.py:520-568) with the four per-step
+// values coef[s] = {sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, sqrt(alphas_cumprod_prev), sqrt(1 - alphas_cumprod_prev)}:
+//   ax = a x;  px = ax - b eps;  e2 = (ax - px) / b;  x' = px c + d e2
+// every product, difference, quotient and sum rounded on its own, as the sampler's one-operation-per-kernel torch expressions round them:
+// the result is the host loop's, bit for bit. Contraction is switched off for the function (hipcc would fuse a x - b eps into an FMA; the
+// __f*_rn spellings are plain operators in this toolchain and would be fused just the same).
+// ONE workgroup: the counter is read by every thread in front of the barrier and written by thread 0 behind it.
+__global__ __launch_bounds__(256) void ddim_step_kernel(float* __restrict__ x, const bf16_t* __restrict__ eps, bf16_t* __restrict__ x_bf16,
+                                                        const float* __restrict__ coef, int* step, int n, int steps, int advance) {
+#pragma clang fp contract(off)
+  const int s = *(const volatile int*)step;
+  const bool live = s >= 0 && s < steps;                                      // a stale counter never indexes outside the table
+  if (live) {
+    const float a = coef[4 * s + 0], b = coef[4 * s + 1], c = coef[4 * s + 2], d = coef[4 * s + 3];
+    for (int i = threadIdx.x; i < n; i += 256) {
+      const float e = bf2f(eps[i]);
+      const float ax = a * x[i];
+      const float be = b * e;
+      const float px = ax - be;
+      const float df = ax - px;
+      const float e2 = df / b;
+      const float pc = px * c;
+      const float de = d * e2;
+      const float out = pc + de;
+      x[i] = out;
+      x_bf16[i] = f2bf(out);
+    }
+  }
+  __syncthreads();
+  if (live && advance && threadIdx.x == 0) *step = s - 1;
+}
+
+// h_in row g R <- t_table[*step], rows g R + 1 + p <- x_e[g T + p] (R = 1 + T): cat([t_e, x_e], 1).reshape(G R, H) of the sampler's
+// model call, with the timestep embedding looked up instead of recomputed. One workgroup per row, 16 B per lane.
+__global__ __launch_bounds__(256) void sampler_rows_kernel(bf16_t* __restrict__ h_in, const bf16_t* __restrict__ t_table,
+                                                           const bf16_t* __restrict__ x_e, const int* __restrict__ step, int T, int H,
+                                                           int steps) {
+  const int s = *step;
+  if (s < 0 || s >= steps) return;
+  const int R = 1 + T, row = blockIdx.x, g = row / R, p = row - g * R;
+  const bf16_t* src = p == 0 ? t_table + (size_t)s * H : x_e + ((size_t)g * T + (p - 1)) * H;
+  bf16_t* dst = h_in + (size_t)row * H;
+  for (int ch = threadIdx.x; ch < (H >> 3); ch += 256) *(u32x4_t*)(dst + ch * 8) = *(const u32x4_t*)(src + ch * 8);
+}
+
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" int mla_ddim_step(float* x, const void* eps, void* x_bf16, const float* coef, int* step, int n, int steps, int advance,
+                             hipStream_t stream) {
+  MLA_CHECK_ARG(x && eps && x_bf16 && coef && step, "mla_ddim_step: null pointer");
+  MLA_CHECK_ARG(n >= 1 && n <= 65536, "mla_ddim_step: n = %d outside [1, 65536] (one workgroup walks the chunk)", n);
+  MLA_CHECK_ARG(steps >= 1, "mla_ddim_step: steps = %d", steps);
+  hipLaunchKernelGGL(ddim_step_kernel, dim3(1), dim3(256), 0, stream, x, (const bf16_t*)eps, (bf16_t*)x_bf16, coef, step, n, steps,
+                     advance ? 1 : 0);
+  MLA_LAUNCH_CHECK();
+}
+
+extern "C" int mla_sampler_rows(void* h_in, const void* t_table, const void* x_e, const int* step, int G, int T, int H, int steps,
+                                hipStream_t stream) {
+  MLA_CHECK_ARG(h_in && t_table && x_e && step, "mla_sampler_rows: null pointer");
+  MLA_CHECK_ARG(G >= 1 && T >= 1 && steps >= 1 && (long long)G * (1 + T) <= 65536, "mla_sampler_rows: G = %d, T = %d, steps = %d", G, T,
+                steps);
+  MLA_CHECK_ARG(H >= 8 && H % 8 == 0 && al16(h_in) && al16(t_table) && al16(x_e),
+                "mla_sampler_rows: H = %d must be a multiple of 8 and the rows 16-byte aligned", H);
+  hipLaunchKernelGGL(sampler_rows_kernel, dim3(G * (1 + T)), dim3(256), 0, stream, (bf16_t*)h_in, (const bf16_t*)t_table,
+                     (const bf16_t*)x_e, step, T, H, steps);
+  MLA_LAUNCH_CHECK();
+}

@@ -124,6 +124,29 @@ class GaussianDiffusion:
         nonzero = (t != 0).float().view(-1, *([1] * (x.dim() - 1)))
         return {"sample": mean_pred + nonzero * sigma * noise, "pred_xstart": pred_xstart}
 
+    def ddim_tables(self, device, eta=0.0):
+        """-> (coef [steps, 4] fp32, timesteps [steps] long) on `device`, cached per device like _tables: what ddim_sample uses of step i
+        at eta = 0 and clip_denoised=False, row i = [a, b, c, d] = [sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod,
+        sqrt(alphas_cumprod_prev), sqrt(1 - alphas_cumprod_prev - sigma^2)], built with ddim_sample's own expressions on the target
+        device (float64 table -> float32 value as _at does, torch.sqrt on the fp32 values), and timestep_map. With
+            ax = a * x;  px = ax - b * eps;  e2 = (ax - px) / b;  out = px * c + d * e2
+        rounded one operation at a time, `out` is ddim_sample(...)["sample"] bit for bit (hip.ddim_step, tests/test_sampler_device_host.py).
+        eta != 0 needs the per-step noise values and raises ValueError."""
+        if eta != 0.0:
+            raise ValueError(f"ddim_tables: eta = {eta} needs the noise drawn in every step; the four-coefficient form is eta = 0 only")
+        key = ("ddim", str(device))
+        if key not in self._dev_tables:
+            with torch.inference_mode(False), torch.no_grad():
+                t = torch.arange(self.num_timesteps, device=device)
+                at = lambda table: torch.from_numpy(table).to(device=device)[t].float()  # noqa: E731 -- _at without the broadcast
+                a, b = at(self.sqrt_recip_alphas_cumprod), at(self.sqrt_recipm1_alphas_cumprod)
+                ab, ab_prev = at(self.alphas_cumprod), at(self.alphas_cumprod_prev)
+                sigma = eta * torch.sqrt((1 - ab_prev) / (1 - ab)) * torch.sqrt(1 - ab / ab_prev)
+                c, d = torch.sqrt(ab_prev), torch.sqrt(1 - ab_prev - sigma ** 2)
+                self._dev_tables[key] = (torch.stack([a, b, c, d], dim=1).contiguous(),
+                                         torch.tensor(self.timestep_map, dtype=torch.long, device=device))
+        return self._dev_tables[key]
+
     def p_sample(self, model, x, t, clip_denoised=True, model_kwargs=None):
         """gaussian_diffusion.py:395-440 with the fixed-small posterior variance."""
         pred_xstart = self._pred_xstart(x, t, self._eps(model, x, t, model_kwargs), clip_denoised)

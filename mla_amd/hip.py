@@ -70,6 +70,8 @@ _SIGNATURES = {
                                   c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p],
     "mla_gemm_prefill_gateup_swiglu": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_int, c_int,
                                        c_int, c_void_p, c_size_t, c_void_p],
+    "mla_ddim_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    "mla_sampler_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "mla_gemm_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                       c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
     "mla_gemm_bf16_ws": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -1101,6 +1103,44 @@ def gemm_prefill_gateup_swiglu(x, wgu, act, ldo=None, out_batch_stride=0, rows_p
     assert wgu.shape[0] % 2 == 0
     call("mla_gemm_prefill_gateup_swiglu", _p(x), x.stride(0), _p(wgu), wgu.stride(0), _p(act), act.stride(0) if ldo is None else ldo,
          out_batch_stride, M if rows_per_batch is None else rows_per_batch, M, wgu.shape[0] // 2, K, wp, wb)
+
+
+# --------------------------------------------------------------------------------------------- device-resident DDIM loop (sampler.hip)
+DDIM_NMAX = 65536
+
+
+def ddim_step(x, eps, x_bf16, coef, step, advance=True):
+    """mla_ddim_step: the eta = 0 DDIM update of the chunk x (fp32, in place; any shape, contiguous) with row step[0] of coef [steps, 4] and
+    the bf16 epsilons eps (same number of elements); x_bf16 <- bf16(x); advance: step[0] -= 1. A step[0] outside [0, steps) writes nothing."""
+    _req(x, torch.float32, "ddim_step x")
+    _req(eps, torch.bfloat16, "ddim_step eps")
+    _req(x_bf16, torch.bfloat16, "ddim_step x_bf16")
+    _req(coef, torch.float32, "ddim_step coef")
+    _req(step, torch.int32, "ddim_step step")
+    n = x.numel()
+    if not (x.is_contiguous() and eps.is_contiguous() and x_bf16.is_contiguous() and coef.is_contiguous()):
+        raise ValueError("ddim_step: x, eps, x_bf16 and coef must be contiguous")
+    if eps.numel() != n or x_bf16.numel() != n or coef.dim() != 2 or coef.shape[1] != 4 or step.numel() != 1:
+        raise ValueError(f"ddim_step: x {tuple(x.shape)}, eps {tuple(eps.shape)}, x_bf16 {tuple(x_bf16.shape)}, coef {tuple(coef.shape)}, "
+                         f"step {tuple(step.shape)}")
+    if not 1 <= n <= DDIM_NMAX:
+        raise ValueError(f"ddim_step: {n} elements outside [1, {DDIM_NMAX}]")
+    call("mla_ddim_step", _p(x), _p(eps), _p(x_bf16), _p(coef), _p(step), n, coef.shape[0], 1 if advance else 0)
+
+
+def sampler_rows(h_in, t_table, x_e, step, G, T):
+    """mla_sampler_rows: rows [0, G (1 + T)) of h_in <- per group [t_table[step[0]] | x_e rows g T .. g T + T); rows behind them are not
+    touched. h_in [>= G (1 + T), H], t_table [steps, H], x_e [>= G T, H] (or [G, T, H]) bf16, contiguous."""
+    for t, name in ((h_in, "h_in"), (t_table, "t_table"), (x_e, "x_e")):
+        _req(t, torch.bfloat16, "sampler_rows " + name)
+        if not t.is_contiguous():
+            raise ValueError(f"sampler_rows: {name} must be contiguous")
+    _req(step, torch.int32, "sampler_rows step")
+    H = t_table.shape[-1]
+    if G < 1 or T < 1 or h_in.dim() != 2 or t_table.dim() != 2 or h_in.shape[1] != H or x_e.shape[-1] != H or step.numel() != 1 \
+            or h_in.shape[0] < G * (1 + T) or x_e.numel() < G * T * H:
+        raise ValueError(f"sampler_rows: G {G}, T {T}, h_in {tuple(h_in.shape)}, t_table {tuple(t_table.shape)}, x_e {tuple(x_e.shape)}")
+    call("mla_sampler_rows", _p(h_in), _p(t_table), _p(x_e), _p(step), G, T, H, t_table.shape[0])
 
 
 def attn_chunk_ragged(cache, B, nheads, D, kv_len, R, scale):

@@ -18,6 +18,10 @@ Opt-in (`suffix_weights="fp8"`, see SUFFIX_WEIGHT_MODES): the sampler steps stre
 `mla_gemv_w8` / `mla_gemm_skinny_w8` (one chunk per call) or `mla_gemm_suffix_w8` (N chunks per observation, SampleGroupsEps) -- half the
 weight bytes per step; prefill, activations, cache and attention are untouched.
 
+Opt-in (`sampler="device"`, see SAMPLER_MODES): the DDIM loop around the suffix passes runs on the device -- `sample_ddim` replays one
+captured sampler step (x_embedder, `mla_sampler_rows`, the suffix pass, final_layer, `mla_ddim_step`) per DDIM step with the step index in
+device memory: no copy to the device and no host wait between the steps, bit for bit the host loop's result.
+
 Semantics vs the reference: identical arithmetic up to summation order (fp32 accumulation everywhere), with ONE stated difference -- the
 reference's point tokenizer draws fresh random FPS start indices inside every one of the 8 forwards (Point_PN.py:10); here they are
 drawn once per action chunk (the prefix is computed once). With given start indices (`fps_starts_override`, as in
@@ -64,6 +68,43 @@ def check_prefill(mode):
         raise ValueError(f"prefill must be one of {PREFILL_MODES}, got {mode!r}")
 
 
+# Who runs the DDIM loop around the suffix passes (MLA.predict_action_diff(sampler=...)):
+#   "host"    GaussianDiffusion.ddim_sample_loop: torch expressions per step, tables copied to the device per step (default)
+#   "device"  _CachedEpsBase.sample_ddim: one captured sampler step replayed num_ddim_steps times, the step index in device memory; no copy
+#             to the device and no host wait between the steps; the same bits
+SAMPLER_MODES = ("host", "device")
+
+
+def check_sampler(mode, reuse_prefix=True, use_ddim=True, num_ddim_steps=8):
+    """The argument errors of sampler=: an unknown value; "device" without the cached prefix or without the DDIM sampler (the DDPM sampler
+    needs per-step noise values). A shape the engine does not serve is the caller's ValueError (sampler_needs_engine)."""
+    if mode not in SAMPLER_MODES:
+        raise ValueError(f"sampler must be one of {SAMPLER_MODES}, got {mode!r}")
+    if mode == "device":
+        if not reuse_prefix:
+            raise ValueError("sampler=\"device\" runs on the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has the "
+                             "host loop only")
+        if not use_ddim or num_ddim_steps is None:
+            raise ValueError("sampler=\"device\" is the DDIM loop at eta = 0 (use_ddim=True and num_ddim_steps); the DDPM sampler needs "
+                             "per-step noise values")
+
+
+def sampler_needs_engine(mode, engine: str, n_action_rows: int):
+    """sampler="device" on a shape the cached-prefix engine does not serve: an error, never the warned loop of whole-forward calls."""
+    if mode == "device":
+        raise ValueError(f"sampler=\"device\": the cached-prefix engine ({engine}) does not serve {1 + n_action_rows} suffix rows per "
+                         "sample at this head_dim; use sampler=\"host\"")
+
+
+_GRAPH_OFF = "MLA_INFER_GRAPH=0: the device sampler launches its steps one by one"      # graph_error of an eager sample_ddim
+
+
+class _DdimState:
+    """What sample_ddim keeps per (engine, batch, action_dim, diffusion): the chunk x fp32 and its bf16 cast, the step counter, the
+    coefficient and timestep-embedding tables, and the captured step. All device tensors are allocated outside inference mode."""
+    __slots__ = ("diffusion", "steps", "x", "x_bf16", "step", "coef", "timesteps", "t_table", "t_key", "graph", "graph_key", "failed")
+
+
 class W8(NamedTuple):
     """A quantised projection weight: q [N, K] float8_e4m3fn codes, scale [N] fp32 (one per output channel)."""
     q: torch.Tensor
@@ -93,6 +134,7 @@ class _CachedEpsBase:
         self._packed = None          # per layer: the 9 weights with q|k|v and gate|up as views of ONE buffer each (see _weights)
         self._packed_key = None
         self._suffix = None          # per layer: what the suffix pass streams -- _packed itself ("bf16") or a quantised copy (_quantised)
+        self._ddim = {}              # sample_ddim's state per (B, action_dim): see _DdimState
 
     def _weights(self):
         """Every layer's (ln1, wq, wk, wv, wo, ln2, wg, wu, wd) with q|k|v and gate|up adjacent in memory, so that the prefill runs the
@@ -239,6 +281,108 @@ class _CachedEpsBase:
             picked = self.h_out.view(self.B, self.R, self.H)[:, 1:].reshape(self.B * self.T, self.H).contiguous()
             noise_pred = vlm.final_layer(picked).view(self.B, self.T, -1)
         return None, noise_pred
+
+    # ------------------------------------------------------------------------------------------ the DDIM loop on the device (sampler="device")
+    def _ddim_state(self, x0, diffusion):
+        """The persistent state for chunks shaped like x0 [B, T, D] under `diffusion` (per B: the group engines keep one per set_groups G)."""
+        B, T, D = x0.shape
+        assert B == self.B and T == self.T, (tuple(x0.shape), self.B, self.T)
+        st = self._ddim.get((B, D))
+        if st is None or st.diffusion is not diffusion:
+            dev = self.h_in.device
+            coef, timesteps = diffusion.ddim_tables(dev, eta=0.0)
+            st = _DdimState()
+            st.diffusion, st.steps, st.timesteps = diffusion, int(coef.shape[0]), timesteps
+            with torch.inference_mode(False), torch.no_grad():                # the state outlives the (inference-mode) call that creates it
+                st.x = torch.zeros((B, T, D), dtype=torch.float32, device=dev)
+                st.x_bf16 = torch.zeros((B, T, D), dtype=torch.bfloat16, device=dev)
+                st.step = torch.full((1,), st.steps - 1, dtype=torch.int32, device=dev)
+                st.coef = coef.clone()
+                st.t_table = torch.zeros((st.steps, self.H), dtype=torch.bfloat16, device=dev)
+            st.t_key = st.graph = st.graph_key = None
+            st.failed = False
+            self._ddim[(B, D)] = st
+        return st
+
+    def _ddim_t_table(self, st):
+        """Row i of t_table = the timestep token of step i: vlm.t_embedder on the [B] batch of the mapped timestep cast to bf16, exactly
+        as __call__ forms it per step (row 0 of B equal rows, checked once per build: the bits do not depend on how the GEMM treats the
+        row count). Rebuilt in place -- a captured step keeps its address -- when a t_embedder parameter changes."""
+        key = tuple((p.data_ptr(), p._version) for p in self.vlm.t_embedder.parameters())
+        if st.t_key == key:
+            return
+        with torch.no_grad():
+            rows = torch.stack([self.vlm.t_embedder(st.timesteps[i].expand(self.B).to(torch.bfloat16)) for i in range(st.steps)])
+            if not bool((rows == rows[:, :1]).all()):
+                raise RuntimeError("sample_ddim: t_embedder gives different rows for the same timestep; the device sampler keeps one row "
+                                   "per step (use sampler=\"host\")")
+            st.t_table.copy_(rows[:, 0])
+        st.t_key = key
+
+    def _ddim_one_step(self, st):
+        """One sampler step, every launch on the current stream and none of them waiting for the host: the launches of __call__ with the
+        timestep token looked up (mla_sampler_rows), then the DDIM update, which counts the device-side step index down."""
+        vlm = self.vlm
+        x_e = vlm.x_embedder(st.x_bf16)                                       # [B, T, H]
+        hip.sampler_rows(self.h_in, st.t_table, x_e.contiguous(), st.step, self.B, self.T)
+        self._suffix_pass()                                                   # launched directly: a graph cannot replay inside a capture
+        picked = self.h_out.view(self.B, self.R, self.H)[:, 1:].reshape(self.B * self.T, self.H).contiguous()
+        noise_pred = vlm.final_layer(picked)                                  # [B * T, D] bf16
+        hip.ddim_step(st.x, noise_pred.contiguous(), st.x_bf16, st.coef, st.step, advance=True)
+
+    def _ddim_graph(self, st):
+        """The captured step for the current weights, or None (MLA_INFER_GRAPH=0 or a failed capture: eager launches of the same sequence,
+        the reason in graph_error). Captured under _run's conditions; the warm-up launch runs a real step on the state, so this is called
+        in front of the reset of a call."""
+        if not _USE_GRAPH:
+            if self.graph_error is None:
+                self.graph_error = _GRAPH_OFF
+            return None
+        if st.failed:
+            return None
+        if self.graph_error == _GRAPH_OFF:
+            self.graph_error = None
+        key = (self._packed_key, self.suffix_weights,
+               tuple(p.data_ptr() for m in (self.vlm.x_embedder, self.vlm.final_layer) for p in m.parameters()))
+        if st.graph is None or st.graph_key != key:
+            st.graph = None
+            try:
+                with torch.no_grad():
+                    self._ddim_one_step(st)                                   # warm-up outside the capture (function attributes, allocator)
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.inference_mode(False), torch.no_grad(), torch.cuda.graph(g):
+                    self._ddim_one_step(st)
+                st.graph, st.graph_key = g, key
+            except Exception as e:   # noqa: BLE001 -- a failed capture is not fatal: the eager launches compute the same thing
+                st.failed, self.graph_error = True, repr(e)
+                st.graph = None
+                torch.cuda.synchronize()
+        return st.graph
+
+    def sample_ddim(self, x0, diffusion):
+        """ddim_sample_loop(self, x0.shape, x0, clip_denoised=False, eta=0.0) of `diffusion` with the loop on the device -> samples
+        [B, T, D] fp32, the same bits. After the (already done) prefill the host enqueues diffusion.num_timesteps replays of one captured
+        sampler step (x_embedder, mla_sampler_rows, the suffix pass, final_layer, mla_ddim_step) and returns; nothing is copied to the
+        device and the host never waits for the device between the steps. The generator ends where the host loop leaves it (one unused
+        randn_like per step)."""
+        x0 = x0.float()
+        st = self._ddim_state(x0, diffusion)
+        self._ddim_t_table(st)
+        graph = self._ddim_graph(st)
+        with torch.no_grad():
+            st.x.copy_(x0)
+            st.x_bf16.copy_(x0.to(torch.bfloat16))
+            st.step.fill_(st.steps - 1)
+            for _ in range(st.steps):
+                if graph is not None:
+                    graph.replay()
+                else:
+                    self._ddim_one_step(st)
+            for _ in range(st.steps):
+                torch.randn_like(st.x)                                        # ddim_sample draws its noise even at eta = 0
+            return st.x.clone()
+
 
 
 class PrefixCachedEps(_CachedEpsBase):

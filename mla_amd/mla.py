@@ -331,7 +331,7 @@ class MLA(nn.Module):
                             unnorm_key: Optional[str] = None, cfg_scale: float = 0.0, use_ddim: bool = True, num_ddim_steps: int = 8,
                             action_dim: int = 7, *, input_ids: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                             camera_name: str = "rlbench_front", reuse_prefix: bool = True, suffix_weights: str = "bf16",
-                            prefill: str = "train", **kwargs) -> np.ndarray:
+                            prefill: str = "train", sampler: str = "host", **kwargs) -> np.ndarray:
         """model_mla.py:592-775: 8-step DDIM (eta = 0) over the action chunk with the VLM as the epsilon model, then
         un-normalisation.
         * ``image`` is a PIL image / uint8 HWC frame (pre-processed here like the reference does, :656-660) or an already
@@ -353,10 +353,17 @@ class MLA(nn.Module):
         ``prefill`` (opt-in, cached prefix only): "train" (default) runs the prefix rows on the training kernels; "compact" on the
         row-sized GEMMs of mla_amd/csrc/prefill.hip (q|k|v + RoPE written straight into the cache, gate|up + SwiGLU writing the product
         only): the same function up to summation order and rounding points. "compact" raises ValueError when ``reuse_prefix=False``, the
-        cached-prefix engine does not serve the shape, the prefix has more than 1024 rows or head_dim is not 128: no silent fallback."""
-        from .infer import check_prefill, check_suffix_weights
+        cached-prefix engine does not serve the shape, the prefix has more than 1024 rows or head_dim is not 128: no silent fallback.
+        ``sampler`` (opt-in, cached prefix only): "host" (default) runs the reference's DDIM loop in torch expressions on the host;
+        "device" keeps the loop on the device (mla_amd/infer.py:_CachedEpsBase.sample_ddim): one captured sampler step replayed
+        ``num_ddim_steps`` times with the step index in device memory, no copy to the device and no host wait between the steps, the same
+        bits. It composes with every ``suffix_weights`` and ``prefill`` mode; it raises ValueError when ``reuse_prefix=False``, the
+        cached-prefix engine does not serve the shape, ``use_ddim=False`` or ``num_ddim_steps=None`` (the DDPM sampler needs per-step
+        noise values), and for an unknown value."""
+        from .infer import check_prefill, check_sampler, check_suffix_weights, sampler_needs_engine
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
+        check_sampler(sampler, reuse_prefix, use_ddim, num_ddim_steps)
         if prefill != "train" and not reuse_prefix:
             raise ValueError(f"prefill={prefill!r} needs the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has no "
                              "separate prefill")
@@ -384,14 +391,19 @@ class MLA(nn.Module):
         if prefill != "train" and not reuse_prefix:
             raise ValueError(f"prefill={prefill!r}: the cached-prefix engine does not serve this shape (PrefixCachedEps.supports: at most "
                              "64 suffix rows, head_dim 128); use prefill=\"train\"")
+        if not reuse_prefix:
+            sampler_needs_engine(sampler, "PrefixCachedEps", self.future_action_window_size + 1)
         if reuse_prefix:
             eps_model = PrefixCachedEps.for_inputs(self.vlm, n_action_rows=self.future_action_window_size + 1,
                                                    suffix_weights=suffix_weights, prefill=prefill, **model_kwargs)
         if use_ddim and num_ddim_steps is not None:
             if self.ddim_diffusion is None:
                 self.create_ddim(ddim_step=num_ddim_steps)
-            samples = self.ddim_diffusion.ddim_sample_loop(eps_model, noise.shape, noise.to(device).float(), clip_denoised=False,
-                                                           model_kwargs=model_kwargs, progress=False, device=device, eta=0.0)
+            if sampler == "device":
+                samples = eps_model.sample_ddim(noise.to(device).float(), self.ddim_diffusion)
+            else:
+                samples = self.ddim_diffusion.ddim_sample_loop(eps_model, noise.shape, noise.to(device).float(), clip_denoised=False,
+                                                               model_kwargs=model_kwargs, progress=False, device=device, eta=0.0)
         else:
             samples = self.diffusion.p_sample_loop(eps_model, noise.shape, noise.to(device).float(), clip_denoised=False,
                                                    model_kwargs=model_kwargs, progress=False, device=device)
@@ -403,7 +415,7 @@ class MLA(nn.Module):
                                   cfg_scale: float = 0.0, use_ddim: bool = True, num_ddim_steps: int = 8, action_dim: int = 7, *,
                                   input_ids=None, noise: Optional[torch.Tensor] = None, camera_name: str = "rlbench_front",
                                   reuse_prefix: bool = True, suffix_weights: str = "bf16",
-                                  num_samples: Optional[int] = None, prefill: str = "train") -> np.ndarray:
+                                  num_samples: Optional[int] = None, prefill: str = "train", sampler: str = "host") -> np.ndarray:
         """B observations -> [B, T, action_dim]: by definition B independent `predict_action_diff` calls (the reference's
         `predict_action_batch`, model_mla.py:994, is dead code), computed on ONE cached prefix pass per DDIM step
         (mla_amd/infer.py:BatchedPrefixCachedEps): the prompts may have different lengths, the FPS start indices are drawn once per chunk.
@@ -424,10 +436,14 @@ class MLA(nn.Module):
         is how B >= 2 observations get FP8 suffix weights); anything but "bf16" raises ValueError when ``reuse_prefix=False`` or the
         engine does not serve the shape.
         ``prefill``: only "train" -- the batched prefill has B x S rows and belongs to the training GEMMs; "compact" raises
-        NotImplementedError (use predict_action_diff / predict_action_diff_samples per observation)."""
-        from .infer import check_prefill, check_suffix_weights
+        NotImplementedError (use predict_action_diff / predict_action_diff_samples per observation).
+        ``sampler``: predict_action_diff's, with and without ``num_samples``: "device" runs every pass's DDIM loop on the device (the same
+        bits) and raises ValueError where "host" would loop over whole-forward calls (``reuse_prefix=False``, a shape the batched engine
+        does not serve) or run the DDPM sampler."""
+        from .infer import check_prefill, check_sampler, check_suffix_weights, sampler_needs_engine
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
+        check_sampler(sampler, reuse_prefix, use_ddim, num_ddim_steps)
         if prefill != "train":
             raise NotImplementedError(f"prefill={prefill!r}: the batched engines prefill B x S rows on the training GEMMs; the compact "
                                       "prefill serves one observation (predict_action_diff, predict_action_diff_samples)")
@@ -436,7 +452,7 @@ class MLA(nn.Module):
         if num_samples is not None:
             return self._predict_action_diff_batch_samples(images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix,
-                                                           suffix_weights, num_samples)
+                                                           suffix_weights, num_samples, sampler)
         if input_ids is None:
             if instructions is None or len(instructions) != B:
                 raise ValueError("predict_action_diff_batch needs `input_ids` (one tensor per sample), or B `instructions` plus a callable "
@@ -456,7 +472,7 @@ class MLA(nn.Module):
                                             action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b:b + 1],
                                             camera_name=camera_name, **kw)
         if B == 1:
-            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights)[None]
+            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler)[None]
         if suffix_weights != "bf16":
             raise NotImplementedError(f"suffix_weights={suffix_weights!r}: the batched engine (BatchedPrefixCachedEps, mla_gemm_suffix_bf16) "
                                       "streams bf16 weights only; sample B >= 2 observations with \"bf16\", one at a time, or pass "
@@ -465,6 +481,7 @@ class MLA(nn.Module):
             from .infer import BatchedPrefixCachedEps
             reuse_prefix = BatchedPrefixCachedEps.supports_batch(self.vlm, T)
         if not reuse_prefix:
+            sampler_needs_engine(sampler, "BatchedPrefixCachedEps", T)
             return np.stack([one(b, reuse_prefix=False) for b in range(B)])
         self.vlm.eval()
         device = next(self.vlm.parameters()).device
@@ -485,7 +502,9 @@ class MLA(nn.Module):
         for sub, eng in BatchedPrefixCachedEps.for_batch(self.vlm, ids_rows, T, images=img, point_cloud=pc, camera_name=camera_name,
                                                          proprio=proprio):
             xs = x0[sub.start:sub.stop].contiguous()
-            if use_ddim and num_ddim_steps is not None:
+            if sampler == "device":
+                samples = eng.sample_ddim(xs, self.ddim_diffusion)
+            elif use_ddim and num_ddim_steps is not None:
                 samples = self.ddim_diffusion.ddim_sample_loop(eng, xs.shape, xs, clip_denoised=False, model_kwargs={}, progress=False,
                                                                device=device, eta=0.0)
             else:
@@ -495,7 +514,8 @@ class MLA(nn.Module):
         return self.unnormalize_actions(normalized, unnorm_key) if self.norm_stats is not None else normalized
 
     def _predict_action_diff_batch_samples(self, images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
-                                           num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix, suffix_weights, num_samples):
+                                           num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix, suffix_weights, num_samples,
+                                           sampler="host"):
         """predict_action_diff_batch(num_samples=N) -> [B, N, T, action_dim] (called inside its inference mode; see its docstring)."""
         B, N, T = len(images), int(num_samples), self.future_action_window_size + 1
         if N < 1:
@@ -519,18 +539,20 @@ class MLA(nn.Module):
                                                     num_ddim_steps, action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b],
                                                     camera_name=camera_name, **kw)
         if B == 1:
-            return samples_of(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights)[None]
+            return samples_of(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler)[None]
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
                              "bf16 weights only")
         if reuse_prefix:
-            from .infer import BatchedSampleGroupsEps
+            from .infer import BatchedSampleGroupsEps, sampler_needs_engine
+            if not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T, warn=False):
+                sampler_needs_engine(sampler, "BatchedSampleGroupsEps", T)
             if suffix_weights != "bf16" and not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T, warn=False):
                 raise ValueError(f"suffix_weights={suffix_weights!r}: the batched shared-prefix engine (BatchedSampleGroupsEps) does not serve "
                                  f"{1 + T} suffix rows per sample at this head_dim; draw the samples with \"bf16\"")
             if not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T) or not BatchedSampleGroupsEps.fits_pass(T, N):
                 # one observation at a time: predict_action_diff_samples serves (or refuses) the shape and the mode itself
-                return np.stack([samples_of(b, suffix_weights=suffix_weights) for b in range(B)])
+                return np.stack([samples_of(b, suffix_weights=suffix_weights, sampler=sampler) for b in range(B)])
         else:
             return np.stack([samples_of(b, reuse_prefix=False) for b in range(B)])
         self.vlm.eval()
@@ -553,7 +575,9 @@ class MLA(nn.Module):
         for sub, eng in BatchedSampleGroupsEps.for_batch(self.vlm, ids_rows, T, N, suffix_weights, images=img, point_cloud=pc,
                                                          camera_name=camera_name, proprio=proprio):
             xs = x0[sub.start * N:sub.stop * N].contiguous()
-            if use_ddim and num_ddim_steps is not None:
+            if sampler == "device":
+                samples = eng.sample_ddim(xs, self.ddim_diffusion)
+            elif use_ddim and num_ddim_steps is not None:
                 samples = self.ddim_diffusion.ddim_sample_loop(eng, xs.shape, xs, clip_denoised=False, model_kwargs={}, progress=False,
                                                                device=device, eta=0.0)
             else:
@@ -567,7 +591,8 @@ class MLA(nn.Module):
                                     unnorm_key: Optional[str] = None, num_samples: int = 1, cfg_scale: float = 0.0, use_ddim: bool = True,
                                     num_ddim_steps: int = 8, action_dim: int = 7, *, input_ids: Optional[torch.Tensor] = None,
                                     noise: Optional[torch.Tensor] = None, camera_name: str = "rlbench_front",
-                                    reuse_prefix: bool = True, suffix_weights: str = "bf16", prefill: str = "train") -> np.ndarray:
+                                    reuse_prefix: bool = True, suffix_weights: str = "bf16", prefill: str = "train",
+                                    sampler: str = "host") -> np.ndarray:
         """N action chunks for ONE observation -> [N, T, action_dim]: by definition N independent `predict_action_diff` calls on the same
         observation with the initial samples ``noise[n]`` (critic / best-of-N choice, uncertainty estimates, temporal ensembling), computed
         on ONE cached prefix (mla_amd/infer.py:SampleGroupsEps): the encoders and the decoder prefill run once per call, every sampler step
@@ -583,10 +608,14 @@ class MLA(nn.Module):
         when ``reuse_prefix=False`` or the shared-prefix engine does not serve the shape: no silent bf16 fallback, no silent loop.
         ``prefill`` (opt-in): predict_action_diff's modes; "compact" runs the one prefill of the call on the row-sized GEMMs. Forwarded
         for ``num_samples=1``; raises ValueError when ``reuse_prefix=False``, the shared-prefix engine does not serve the shape, the prefix
-        has more than 1024 rows or head_dim is not 128."""
-        from .infer import check_prefill, check_suffix_weights
+        has more than 1024 rows or head_dim is not 128.
+        ``sampler`` (opt-in): predict_action_diff's modes; "device" runs the DDIM loop of every pass on the device (the same bits).
+        Forwarded for ``num_samples=1``; raises ValueError when ``reuse_prefix=False``, the shared-prefix engine does not serve the shape,
+        ``use_ddim=False`` or ``num_ddim_steps=None``."""
+        from .infer import check_prefill, check_sampler, check_suffix_weights, sampler_needs_engine
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
+        check_sampler(sampler, reuse_prefix, use_ddim, num_ddim_steps)
         if prefill != "train" and not reuse_prefix:
             raise ValueError(f"prefill={prefill!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has no separate "
                              "prefill")
@@ -603,12 +632,14 @@ class MLA(nn.Module):
                                             action_dim, input_ids=input_ids, noise=None if noise is None else noise[n:n + 1],
                                             camera_name=camera_name, **kw)
         if N == 1:
-            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, prefill=prefill)[None]
+            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, prefill=prefill, sampler=sampler)[None]
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
                              "bf16 weights only")
         if reuse_prefix:
             from .infer import SampleGroupsEps
+            if not SampleGroupsEps.supports_samples(self.vlm, T, warn=False):
+                sampler_needs_engine(sampler, "SampleGroupsEps", T)
             if prefill != "train" and not SampleGroupsEps.supports_samples(self.vlm, T, warn=False):
                 raise ValueError(f"prefill={prefill!r}: the shared-prefix engine (SampleGroupsEps) does not serve {1 + T} suffix rows per "
                                  "sample at this head_dim; use prefill=\"train\"")
@@ -639,7 +670,9 @@ class MLA(nn.Module):
         for start, stop in passes:                                           # one prefill, then the passes' sampler loops one after the other
             eng.set_groups(stop - start)
             xs = x0[start:stop].contiguous()
-            if use_ddim and num_ddim_steps is not None:
+            if sampler == "device":
+                samples = eng.sample_ddim(xs, self.ddim_diffusion)
+            elif use_ddim and num_ddim_steps is not None:
                 samples = self.ddim_diffusion.ddim_sample_loop(eng, xs.shape, xs, clip_denoised=False, model_kwargs={}, progress=False,
                                                                device=device, eta=0.0)
             else:

@@ -37,6 +37,12 @@
                                                           decoder rows) and the decoder rows alone, with the 95 % interval of the pair
                                                           differences; --kernel-table adds the four projections of a 7B layer at the
                                                           prefix's row count, training kernel vs compact kernel, per launch
+    python tools/bench_infer.py --pair-sampler [--pairs P] [--chunks C[,C..]]
+                                                          sampler="host" and sampler="device" chunks alternating in one process, in pairs,
+                                                          for every chunk length (default 1,16) with bf16 and with fp8 suffix weights:
+                                                          per-chunk latency with the 95 % interval of the pair differences, the prefill
+                                                          (encoders + prefix rows) alone, and the per-step share (chunk - prefill) / steps
+                                                          of both arms; also whether the two arms returned the same bits
 Prints one JSON line per measurement (not the driver's bench contract -- that is bench.py)."""
 import argparse
 import json
@@ -61,12 +67,15 @@ def main():
     ap.add_argument("--suffix-weights", choices=["bf16", "fp8", "fp8_as_bf16"], default="bf16")
     ap.add_argument("--pair-fp8", action="store_true", help="alternate bf16 and fp8 chunks in one process, in pairs")
     ap.add_argument("--pair-prefill", action="store_true", help="alternate prefill=\"train\" and prefill=\"compact\" in one process, in pairs")
+    ap.add_argument("--pair-sampler", action="store_true", help="alternate sampler=\"host\" and sampler=\"device\" in one process, in pairs")
     ap.add_argument("--pairs", type=int, default=6)
     ap.add_argument("--kernel-table", action="store_true", help="with --pair-fp8: the two _w8 kernels per projection shape and M; with "
                     "--samples: mla_attn_chunk_groups per groups-per-workgroup against mla_attn_chunk_ragged")
     ap.add_argument("--samples", type=str, default="", help="N[,N..]: predict_action_diff_samples vs the batched call on N copies vs N calls")
-    ap.add_argument("--chunks", type=str, default="", help="with --samples: action chunk lengths to measure in one process (default: --chunk)")
+    ap.add_argument("--chunks", type=str, default="", help="with --samples / --pair-sampler: action chunk lengths to measure in one process (default: --chunk; --pair-sampler: 1,16)")
     args = ap.parse_args()
+    if args.pair_sampler:
+        return main_pair_sampler(args)
     batches = [int(v) for v in args.batch.split(",")]
     if args.samples and batches != [0]:
         return main_batch_samples(args, batches)
@@ -244,6 +253,73 @@ def main_pair(args):
             table[f"M{M}"] = row
         out["w8_kernel_us_per_launch"] = table
     print(json.dumps(out))
+
+
+def main_pair_sampler(args):
+    """sampler="host" vs sampler="device" on the same box, alternating, per chunk length and suffix-weight mode: predict_action_diff per
+    chunk (host clock around `iters` calls that end in a device synchronise), the prefill alone (PrefixCachedEps.for_inputs: encoders +
+    prefix rows, the same for both arms) and from the two the per-step share (chunk - prefill) / steps of each arm -- the suffix pass
+    plus the sampler's glue, which is what the mode changes."""
+    from bench import build
+    from mla_amd.infer import PrefixCachedEps
+    from mla_amd.synthetic import make_batch
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    m = build(dev, 1)
+    m.eval()
+    for p in m.parameters():
+        p.data = p.data.to(torch.bfloat16)
+    b = make_batch(B=1, device=dev)
+    ids = torch.cat([b["input_ids"][:, :-4], torch.tensor([[29871]], device=dev)], dim=1)
+    mk = dict(input_ids=ids, images=b["images"]["front_image"][:1], point_cloud=b["point_cloud"][:1], camera_name="rlbench_front",
+              proprio=b["proprio"][:1])
+    arms = ("host", "device")
+    for C in ([int(v) for v in args.chunks.split(",")] if args.chunks else [1, 16]):
+        m.future_action_window_size = m.vlm.future_action_window_size = C - 1
+        noise = torch.randn(1, C, 7, device=dev)
+        kw = dict(image=b["images"]["front_image"][0], pointcloud=b["point_cloud"][0], cur_robot_state=b["proprio"][0, 0].cpu().numpy(),
+                  input_ids=ids, num_ddim_steps=args.steps, noise=noise)
+        for w in ("bf16", "fp8"):
+            acts = {}
+            for arm in arms:                                                # engines, graphs, tables; the same seed: the same FPS start indices
+                torch.manual_seed(1)
+                acts[arm] = m.predict_action_diff(suffix_weights=w, sampler=arm, **kw)
+            with torch.inference_mode():
+                eng = PrefixCachedEps.for_inputs(m.vlm, n_action_rows=C, suffix_weights=w, **mk)
+
+            def chunk_ms(arm):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.iters):
+                    m.predict_action_diff(suffix_weights=w, sampler=arm, **kw)
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / args.iters * 1e3
+
+            def prefill_ms():
+                with torch.inference_mode():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(args.iters):
+                        PrefixCachedEps.for_inputs(m.vlm, n_action_rows=C, suffix_weights=w, **mk)
+                    torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / args.iters * 1e3
+            chunk, prefill = {arm: [] for arm in arms}, []
+            for _ in range(args.pairs):                                     # host, device, host, device, ...: same box, interleaved
+                for arm in arms:
+                    chunk[arm].append(chunk_ms(arm))
+                prefill.append(prefill_ms())
+            step = {arm: [(c - p) / args.steps for c, p in zip(chunk[arm], prefill)] for arm in arms}
+            print(json.dumps({"metric": "predict_action_diff, MLA-Llama2-7B, batch 1: sampler=host vs sampler=device in alternating pairs",
+                              "action_chunk": C, "suffix_rows": C + 1, "suffix_weights": w, "ddim_steps": args.steps, "pairs": args.pairs,
+                              "iters_per_arm_and_pair": args.iters, "unit": "ms",
+                              "chunk_ms": {k: [round(v, 2) for v in vs] for k, vs in chunk.items()},
+                              "chunk_device_minus_host": _pair_stats(chunk["host"], chunk["device"]),
+                              "prefill_with_encoders_ms": [round(v, 2) for v in prefill],
+                              "per_step_share_ms": {k: [round(v, 3) for v in vs] for k, vs in step.items()},
+                              "per_step_share_device_minus_host": _pair_stats(step["host"], step["device"]),
+                              "same_bits": bool(np.array_equal(acts["host"], acts["device"])),
+                              "step_captured": all(st.graph is not None for st in eng._ddim.values()), "graph_error": eng.graph_error,
+                              "data": "synthetic"}), flush=True)
 
 
 def main_pair_prefill(args):
