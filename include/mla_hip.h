@@ -445,6 +445,34 @@ int mla_ddim_step(float* x, const void* eps, void* x_bf16, const float* coef, in
 int mla_sampler_rows(void* h_in, const void* t_table, const void* x_e, const int* step, int G, int T, int H, int steps,
                      mla_stream_t stream);
 
+/* ---- split-key suffix attention (mla_amd/infer.py PrefixCachedEps, opt-in suffix_attention="split"; mla_amd/csrc/attn_split.hip):
+ * mla_attn_chunk's contract -- packed post-RoPE q|k|v cache, the last R rows of S_kv are the queries, query r sees keys
+ * [0, S_kv - R + r], 1 <= R <= 64, any S_kv >= R, head_dim 128, B >= 1, P rounded to bf16 before P V -- with every head's key range read
+ * by several workgroups instead of one per 16 queries.
+ *   mla_attn_chunk_split: the nT = ceil(S_kv / 64) key tiles are cut into `splits` contiguous ranges (sizes differ by at most one tile, the
+ *     first nT % splits ranges take one more). Launch 1: workgroup (b, h, 16 queries, s) runs mla_attn_chunk's arithmetic over range s --
+ *     wave w takes the range's tiles t0 + w, t0 + w + 4, ..., the four wave states are merged in the order 0..3 -- and writes the
+ *     un-normalised state (m, l, 128 fp32 sums) of its valid query rows to `ws`; a range wholly behind a query's causal limit writes the
+ *     empty state (m = -inf, l = 0). Launch 2: one wave per (b, h, query): M = max_s m_s, numerator and denominator summed over
+ *     s = 0, 1, ... with the weight exp2(m_s - M) (an empty state adds exactly zero, no inf - inf is formed), one division, one bf16
+ *     rounding, the row of o ([B * R, H * 128], row stride ld_o, 4-B aligned). splits = 0: the plan's. splits == 1: launch 1 alone in its
+ *     finishing form -- no workspace access, no second launch, o bit for bit mla_attn_chunk's. ws: caller-owned, 16-B aligned, at least
+ *     mla_attn_chunk_split_ws_bytes(...) bytes (may be null when splits resolves to 1); no word of it is read that this call did not
+ *     write, nothing behind the needed bytes is touched. No allocation, no state between calls, no counters, no atomics, no workgroup
+ *     waits on another; deterministic, graph-capturable. Masked and padding loads never touch rows at or behind S_kv. All argument checks
+ *     (R, S_kv, head_dim, splits in [0, nT], ws / ws_bytes) run on the host before any launch.
+ *   mla_attn_chunk_split_plan: out4 = {splits, tiles per split (the larger ranges'), workgroups of launch 1 = B H ceil(R / 16) splits,
+ *     workgroups of launch 2 (0 when splits == 1)} for `cus` compute units (the launcher plans for 256): splits grows by one while
+ *     launch 1 still fits one workgroup per CU, splits < nT and the largest range has more than 4 tiles (a workgroup takes 4 tiles per
+ *     pass; below one pass a cut saves nothing), so every range keeps at least 2 tiles; 1 when twice the unsplit grid no longer fits the
+ *     chip. Pure host function.
+ *   mla_attn_chunk_split_ws_bytes: B H R splits 130 fp32 words for splits > 1 (0 = the plan's), 0 for splits == 1, -1 outside the
+ *     contract. Pure host function. */
+int mla_attn_chunk_split_plan(int B, int H, int R, int S_kv, int cus, int* out4);
+long long mla_attn_chunk_split_ws_bytes(int B, int H, int R, int S_kv, int splits);
+int mla_attn_chunk_split(const void* q, const void* k, const void* v, void* o, int B, int H, int head_dim, int S_kv, int R, long long ld,
+                         long long batch_stride, long long ld_o, float scale, int splits, void* ws, size_t ws_bytes, mla_stream_t stream);
+
 /* ---- losses: CrossEntropyLoss modeling_llama.py:1258-1269; InfoNCE models/mla/fuser/contrastive.py:208-215
  * mla_ce_fwd: lse[r] = logsumexp(logits[r, :ncols]), loss[r] = lse - logits[r, label] (0 for ignore_index or a label outside [0, ncols);
  * labels == null: label = r). A logit of -inf is a masked column and adds nothing, on bf16 and fp32 rows alike (as F.cross_entropy);

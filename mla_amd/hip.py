@@ -72,6 +72,10 @@ _SIGNATURES = {
                                        c_int, c_void_p, c_size_t, c_void_p],
     "mla_ddim_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "mla_sampler_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "mla_attn_chunk_split_plan": [c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "mla_attn_chunk_split_ws_bytes": [c_int, c_int, c_int, c_int, c_int],      # returns long long (restype fixed up in lib())
+    "mla_attn_chunk_split": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong,
+                             c_float, c_int, c_void_p, c_size_t, c_void_p],
     "mla_gemm_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                       c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
     "mla_gemm_bf16_ws": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -188,6 +192,7 @@ def lib():
         L.mla_attn_bwd_ws_bytes.restype = c_longlong
         L.mla_attn_bwd_sync_ints.restype = c_longlong
         L.mla_gemm_prefill_ws_bytes.restype = c_longlong
+        L.mla_attn_chunk_split_ws_bytes.restype = c_longlong
         _lib = L
     return _lib
 
@@ -945,6 +950,68 @@ def attn_chunk(cache, B, nheads, D, S_kv, R, scale):
     base = cache.data_ptr()
     call("mla_attn_chunk", c_void_p(base), c_void_p(base + 2 * H), c_void_p(base + 4 * H), _p(o), B, nheads, D, S_kv, R, cache.stride(1),
          cache.stride(0), H, float(scale))
+    return o
+
+
+# ---- split-key suffix attention (mla_amd/csrc/attn_split.hip): attn_chunk with every head's key tiles cut over several workgroups
+ATTN_SPLIT_WAVES, ATTN_SPLIT_STATE_WORDS, ATTN_SPLIT_COMBINE_WAVES = 4, 130, 4
+
+
+class AttnSplitPlan(NamedTuple):
+    """What mla_attn_chunk_split does with a shape: ranges the 64-key tiles are cut into, tiles of the larger ranges, workgroups of the
+    first launch (B * H * ceil(R / 16) * splits), workgroups of the combine launch and workspace bytes (both 0 when splits == 1)."""
+    splits: int
+    tiles_per_split: int
+    workgroups: int
+    combine_workgroups: int
+    ws_bytes: int
+
+
+def plan_attn_split(B: int, H: int, R: int, S_kv: int, cus: int = 256) -> AttnSplitPlan:
+    """Pure-Python mirror of the launcher's choice (attn_split.hip:sp_plan; mla_attn_chunk_split_plan returns the library's): splits grows
+    by one while the first launch still fits one workgroup per CU, splits < nT and the largest range has more than 4 tiles of 64 keys (one
+    tile per wave and pass: cutting below one pass saves nothing)."""
+    if not (B >= 1 and H >= 1 and 1 <= R <= 64 and S_kv >= R and cus >= 1):
+        raise ValueError(f"plan_attn_split: B, H, cus >= 1 and 1 <= R <= 64, R <= S_kv required (B {B}, H {H}, R {R}, S_kv {S_kv}, cus {cus})")
+    base, nT = B * H * -(-R // 16), -(-S_kv // 64)
+    splits = 1
+    while base * (splits + 1) <= cus and splits < nT and -(-nT // splits) > ATTN_SPLIT_WAVES:
+        splits += 1
+    return AttnSplitPlan(splits, -(-nT // splits), base * splits, -(-B * H * R // ATTN_SPLIT_COMBINE_WAVES) if splits > 1 else 0,
+                         B * H * R * splits * ATTN_SPLIT_STATE_WORDS * 4 if splits > 1 else 0)
+
+
+def attn_split_plan(B: int, H: int, R: int, S_kv: int, cus: int = 256) -> tuple:
+    """The library's plan (mla_attn_chunk_split_plan): (splits, tiles per split, workgroups, combine workgroups)."""
+    out = (c_int * 4)()
+    _check(lib().mla_attn_chunk_split_plan(int(B), int(H), int(R), int(S_kv), int(cus), out), "mla_attn_chunk_split_plan")
+    return tuple(out)
+
+
+def attn_split_ws_bytes(B: int, H: int, R: int, S_kv: int, splits: int = 0) -> int:
+    """Workspace bytes mla_attn_chunk_split needs (mla_attn_chunk_split_ws_bytes; splits 0 = the plan's); -1 outside the contract."""
+    return int(lib().mla_attn_chunk_split_ws_bytes(int(B), int(H), int(R), int(S_kv), int(splits)))
+
+
+def attn_chunk_split(cache, B, nheads, D, S_kv, R, scale, splits=None, ws=None):
+    """attn_chunk's contract with every head's key tiles cut into `splits` ranges read by their own workgroups, and a second launch that
+    merges the partial softmax states in a fixed order (mla_attn_chunk_split). splits None = the library's plan; an explicit value
+    (1 .. ceil(S_kv / 64)) is for tests and the kernel table; 1 gives attn_chunk's bits. ws: caller-owned scratch of at least
+    attn_split_ws_bytes(...) bytes (any dtype); None allocates one for this call. Returns o [B * R, nheads * D] bf16."""
+    _req(cache, torch.bfloat16, "attn_chunk_split cache")
+    H = nheads * D
+    assert cache.shape[0] == B and cache.shape[2] == 3 * H and cache.stride(2) == 1 and cache.shape[1] >= S_kv
+    sp = 0 if splits is None else int(splits)
+    if ws is None:
+        need = attn_split_ws_bytes(B, nheads, R, S_kv, sp)
+        if need > 0:
+            ws = torch.empty(need, dtype=torch.uint8, device=cache.device)
+    else:
+        assert ws.is_cuda and ws.is_contiguous()
+    o = torch.empty((B * R, H), dtype=torch.bfloat16, device=cache.device)
+    base = cache.data_ptr()
+    call("mla_attn_chunk_split", c_void_p(base), c_void_p(base + 2 * H), c_void_p(base + 4 * H), _p(o), B, nheads, D, S_kv, R, cache.stride(1),
+         cache.stride(0), H, float(scale), sp, _p(ws), ws.numel() * ws.element_size() if ws is not None else 0)
     return o
 
 

@@ -22,6 +22,10 @@ Opt-in (`sampler="device"`, see SAMPLER_MODES): the DDIM loop around the suffix 
 captured sampler step (x_embedder, `mla_sampler_rows`, the suffix pass, final_layer, `mla_ddim_step`) per DDIM step with the step index in
 device memory: no copy to the device and no host wait between the steps, bit for bit the host loop's result.
 
+Opt-in (`suffix_attention="split"`, see SUFFIX_ATTENTION_MODES; PrefixCachedEps only): the attention launch of the suffix pass becomes
+`mla_attn_chunk_split` -- every head's key tiles cut over several workgroups, the partial softmax states merged in a fixed order by a
+second launch -- for every R; the same function up to summation order.
+
 Semantics vs the reference: identical arithmetic up to summation order (fp32 accumulation everywhere), with ONE stated difference -- the
 reference's point tokenizer draws fresh random FPS start indices inside every one of the 8 forwards (Point_PN.py:10); here they are
 drawn once per action chunk (the prefix is computed once). With given start indices (`fps_starts_override`, as in
@@ -66,6 +70,39 @@ PREFILL_MODES = ("train", "compact")
 def check_prefill(mode):
     if mode not in PREFILL_MODES:
         raise ValueError(f"prefill must be one of {PREFILL_MODES}, got {mode!r}")
+
+
+# Which attention launch the sampler steps of PrefixCachedEps use (MLA.predict_action_diff(suffix_attention=...)):
+#   "head"   mla_attn_decode / mla_attn_chunk: one workgroup per (sample, head, 16 queries) reads the head's whole key range (default)
+#   "split"  mla_attn_chunk_split with the library's plan for every R: each head's key tiles cut over several workgroups, the partial
+#            softmax states merged in a fixed order by a second launch; same function up to summation order
+SUFFIX_ATTENTION_MODES = ("head", "split")
+
+
+def check_suffix_attention(mode, reuse_prefix=True):
+    """The argument errors of suffix_attention=: an unknown value; "split" without the cached prefix. A shape the engine does not serve is
+    the caller's ValueError (suffix_attention_needs_engine)."""
+    if mode not in SUFFIX_ATTENTION_MODES:
+        raise ValueError(f"suffix_attention must be one of {SUFFIX_ATTENTION_MODES}, got {mode!r}")
+    if mode == "split" and not reuse_prefix:
+        raise ValueError("suffix_attention=\"split\" runs on the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has no "
+                         "suffix pass")
+
+
+def suffix_attention_needs_engine(mode, n_action_rows: int):
+    """suffix_attention="split" on a shape PrefixCachedEps does not serve: an error, never the warned loop of whole-forward calls."""
+    if mode == "split":
+        raise ValueError(f"suffix_attention=\"split\": the cached-prefix engine (PrefixCachedEps) does not serve {1 + n_action_rows} suffix "
+                         "rows per sample at this head_dim; use suffix_attention=\"head\"")
+
+
+def suffix_attention_single_only(mode, route: str):
+    """suffix_attention="split" on a route that does not end in predict_action_diff: the ragged and groups engines keep their own
+    attention launches."""
+    if mode == "split":
+        raise NotImplementedError(f"suffix_attention=\"split\": {route} runs the ragged / groups engines, whose attention launches "
+                                  "(mla_attn_chunk_ragged, mla_attn_chunk_groups and their batched forms) have no split-key form yet; "
+                                  "it serves predict_action_diff (one observation, one chunk) only")
 
 
 # Who runs the DDIM loop around the suffix passes (MLA.predict_action_diff(sampler=...)):
@@ -115,11 +152,14 @@ class _CachedEpsBase:
     """What the cached-prefix engines share: the packed weights, the captured suffix pass and the `model(x, t)` call of the samplers.
     A subclass provides prefill() and _suffix_pass() and sets B, R, T, H, h_in, h_out, cache."""
 
-    def __init__(self, vlm, n_action_rows: int = 1, suffix_weights: str = "bf16", prefill: str = "train"):
+    def __init__(self, vlm, n_action_rows: int = 1, suffix_weights: str = "bf16", prefill: str = "train", suffix_attention: str = "head"):
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
+        check_suffix_attention(suffix_attention)
         self.suffix_weights = suffix_weights
         self.prefill_mode = prefill
+        self.suffix_attention = suffix_attention
+        self._attn_ws = None         # "split": the partial softmax states of mla_attn_chunk_split, allocated once beside h_in / h_out
         self._prefill_ws = None      # "compact": the split-K workspace of the prefill GEMMs, allocated once beside h_in / h_out
         self.vlm = vlm
         llm = vlm.llm_backbone.llm
@@ -420,9 +460,11 @@ class PrefixCachedEps(_CachedEpsBase):
         return False
 
     @classmethod
-    def for_inputs(cls, vlm, input_ids, n_action_rows: int = 1, suffix_weights: str = "bf16", prefill: str = "train", **model_kwargs):
+    def for_inputs(cls, vlm, input_ids, n_action_rows: int = 1, suffix_weights: str = "bf16", prefill: str = "train",
+                   suffix_attention: str = "head", **model_kwargs):
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
+        check_suffix_attention(suffix_attention)
         k = cls._splice_position(input_ids)
         engines = vlm.__dict__.setdefault("_prefix_engines", {})
         key = (int(input_ids.shape[0]), k, int(n_action_rows), str(input_ids.device))
@@ -430,11 +472,13 @@ class PrefixCachedEps(_CachedEpsBase):
             key += (suffix_weights,)                                          # a captured graph holds the addresses of ITS weights
         if prefill != "train":
             key += ("prefill:" + prefill,)                                    # the mode is part of the key: the engines coexist
+        if suffix_attention != "head":
+            key += ("attention:" + suffix_attention,)                         # a captured graph holds ITS attention launches
         eng = engines.get(key)
         if eng is None:
             if len(engines) >= 4:                                             # a handful of prompt lengths per process; each engine holds 0.4 GB at 7B
                 engines.pop(next(iter(engines)))
-            eng = engines[key] = cls(vlm, n_action_rows, suffix_weights, prefill)
+            eng = engines[key] = cls(vlm, n_action_rows, suffix_weights, prefill, suffix_attention)
         eng.prefill(input_ids, k, **model_kwargs)
         return eng
 
@@ -458,6 +502,11 @@ class PrefixCachedEps(_CachedEpsBase):
                     self.h_out = torch.zeros((B * self.R, H), dtype=bf16, device=dev)
                     if self.prefill_mode == "compact":
                         self._prefill_ws = self._compact_ws(B * S_p, dev)
+                    if self.suffix_attention == "split":
+                        need = hip.attn_split_ws_bytes(B, self.nheads, self.R, self.S_cap)
+                        if need < 0:
+                            raise RuntimeError(f"mla_attn_chunk_split_ws_bytes: {hip.lib().mla_last_error().decode()}")
+                        self._attn_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
             assert (B, S_p, H) == (self.B, self.S_p, self.H)
             h = prefix.reshape(B * S_p, H)
             if self.prefill_mode == "compact":                               # the row-sized GEMMs write the cache rows themselves
@@ -468,6 +517,15 @@ class PrefixCachedEps(_CachedEpsBase):
                 h, acts = ops.DecoderLayerFn._fwd(h, None, self.cos_p, self.sin_p, B, S_p, self.nheads, self.eps, w)
                 c[:, :S_p].copy_(acts.qkv[:B * S_p].view(B, S_p, 3 * H))
                 del acts
+
+    def _suffix_attn(self):
+        """The attention launch of the suffix pass: "head" -- mla_attn_decode where the R x S_kv scores fit LDS, mla_attn_chunk's online
+        softmax beyond; "split" -- mla_attn_chunk_split with the library's plan for every R, on the engine's workspace. No fallback: with
+        head_dim other than 128 the launcher refuses (PrefixCachedEps.supports keeps such models off the engine)."""
+        if self.suffix_attention == "split":
+            ws = self._attn_ws
+            return lambda c, B, nheads, D, S_kv, R, scale: hip.attn_chunk_split(c, B, nheads, D, S_kv, R, scale, ws=ws)
+        return hip.attn_decode if hip.attn_decode_fits(self.R, self.S_cap) else hip.attn_chunk
 
     # ------------------------------------------------------------------------------------------ one pass over the suffix rows
     def _gemv(self, x, weights, out=None, residual=None, rpb=1, out_bs=0, **pre):
@@ -511,7 +569,7 @@ class PrefixCachedEps(_CachedEpsBase):
         B, R, H, S_p, S_cap = self.B, self.R, self.H, self.S_p, self.S_cap
         h = self.h_in
         scale = 1.0 / math.sqrt(self.D)
-        attn = hip.attn_decode if hip.attn_decode_fits(R, S_cap) else hip.attn_chunk
+        attn = self._suffix_attn()
         fused = self.D == 128
         for (ln1, qkv, wo, ln2, gu, wd), c in zip(self._suffix, self.cache):
             self._gemv(h, qkv, out=c[:, S_p:], rpb=R, out_bs=c.stride(0), norm_weight=ln1, eps=self.eps,
@@ -532,7 +590,7 @@ class PrefixCachedEps(_CachedEpsBase):
         B, R, H, S_p, S_cap = self.B, self.R, self.H, self.S_p, self.S_cap
         h = self.h_in
         scale = 1.0 / math.sqrt(self.D)
-        attn = hip.attn_decode if hip.attn_decode_fits(R, S_cap) else hip.attn_chunk   # R x S_kv scores in LDS vs online softmax
+        attn = self._suffix_attn()                                             # "head": R x S_kv scores in LDS vs online softmax
         for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd), c in zip(self._suffix, self.cache):
             # north_star's "fused RMSNorm + RoPE + QKV" as ONE kernel: RMSNorm inside the projection's input staging, the rotary embedding of
             # the q and k columns in its epilogue; the rows go straight into the cache slots [S_p, S_p + R) of every sample

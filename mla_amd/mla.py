@@ -331,7 +331,7 @@ class MLA(nn.Module):
                             unnorm_key: Optional[str] = None, cfg_scale: float = 0.0, use_ddim: bool = True, num_ddim_steps: int = 8,
                             action_dim: int = 7, *, input_ids: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                             camera_name: str = "rlbench_front", reuse_prefix: bool = True, suffix_weights: str = "bf16",
-                            prefill: str = "train", sampler: str = "host", **kwargs) -> np.ndarray:
+                            prefill: str = "train", sampler: str = "host", suffix_attention: str = "head", **kwargs) -> np.ndarray:
         """model_mla.py:592-775: 8-step DDIM (eta = 0) over the action chunk with the VLM as the epsilon model, then
         un-normalisation.
         * ``image`` is a PIL image / uint8 HWC frame (pre-processed here like the reference does, :656-660) or an already
@@ -359,11 +359,18 @@ class MLA(nn.Module):
         ``num_ddim_steps`` times with the step index in device memory, no copy to the device and no host wait between the steps, the same
         bits. It composes with every ``suffix_weights`` and ``prefill`` mode; it raises ValueError when ``reuse_prefix=False``, the
         cached-prefix engine does not serve the shape, ``use_ddim=False`` or ``num_ddim_steps=None`` (the DDPM sampler needs per-step
-        noise values), and for an unknown value."""
-        from .infer import check_prefill, check_sampler, check_suffix_weights, sampler_needs_engine
+        noise values), and for an unknown value.
+        ``suffix_attention`` (opt-in, cached prefix only): "head" (default) runs the sampler steps' attention as one workgroup per (head,
+        16 queries) (mla_attn_decode / mla_attn_chunk); "split" cuts every head's key range over several workgroups and merges the partial
+        softmax states in a fixed order with a second launch (mla_attn_chunk_split with the library's plan): the same function up to
+        summation order. It composes with every ``suffix_weights``, ``prefill`` and ``sampler`` mode; it raises ValueError for an unknown
+        value, and for "split" when ``reuse_prefix=False`` or the cached-prefix engine does not serve the shape: no silent fallback."""
+        from .infer import (check_prefill, check_sampler, check_suffix_attention, check_suffix_weights, sampler_needs_engine,
+                            suffix_attention_needs_engine)
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
         check_sampler(sampler, reuse_prefix, use_ddim, num_ddim_steps)
+        check_suffix_attention(suffix_attention, reuse_prefix)
         if prefill != "train" and not reuse_prefix:
             raise ValueError(f"prefill={prefill!r} needs the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has no "
                              "separate prefill")
@@ -393,9 +400,11 @@ class MLA(nn.Module):
                              "64 suffix rows, head_dim 128); use prefill=\"train\"")
         if not reuse_prefix:
             sampler_needs_engine(sampler, "PrefixCachedEps", self.future_action_window_size + 1)
+            suffix_attention_needs_engine(suffix_attention, self.future_action_window_size + 1)
         if reuse_prefix:
             eps_model = PrefixCachedEps.for_inputs(self.vlm, n_action_rows=self.future_action_window_size + 1,
-                                                   suffix_weights=suffix_weights, prefill=prefill, **model_kwargs)
+                                                   suffix_weights=suffix_weights, prefill=prefill, suffix_attention=suffix_attention,
+                                                   **model_kwargs)
         if use_ddim and num_ddim_steps is not None:
             if self.ddim_diffusion is None:
                 self.create_ddim(ddim_step=num_ddim_steps)
@@ -415,7 +424,8 @@ class MLA(nn.Module):
                                   cfg_scale: float = 0.0, use_ddim: bool = True, num_ddim_steps: int = 8, action_dim: int = 7, *,
                                   input_ids=None, noise: Optional[torch.Tensor] = None, camera_name: str = "rlbench_front",
                                   reuse_prefix: bool = True, suffix_weights: str = "bf16",
-                                  num_samples: Optional[int] = None, prefill: str = "train", sampler: str = "host") -> np.ndarray:
+                                  num_samples: Optional[int] = None, prefill: str = "train", sampler: str = "host",
+                                  suffix_attention: str = "head") -> np.ndarray:
         """B observations -> [B, T, action_dim]: by definition B independent `predict_action_diff` calls (the reference's
         `predict_action_batch`, model_mla.py:994, is dead code), computed on ONE cached prefix pass per DDIM step
         (mla_amd/infer.py:BatchedPrefixCachedEps): the prompts may have different lengths, the FPS start indices are drawn once per chunk.
@@ -439,20 +449,26 @@ class MLA(nn.Module):
         NotImplementedError (use predict_action_diff / predict_action_diff_samples per observation).
         ``sampler``: predict_action_diff's, with and without ``num_samples``: "device" runs every pass's DDIM loop on the device (the same
         bits) and raises ValueError where "host" would loop over whole-forward calls (``reuse_prefix=False``, a shape the batched engine
-        does not serve) or run the DDPM sampler."""
-        from .infer import check_prefill, check_sampler, check_suffix_weights, sampler_needs_engine
+        does not serve) or run the DDPM sampler.
+        ``suffix_attention``: predict_action_diff's, forwarded for B = 1; B >= 2 with "split" raises NotImplementedError (the ragged and
+        groups engines keep their own attention launches)."""
+        from .infer import (check_prefill, check_sampler, check_suffix_attention, check_suffix_weights, sampler_needs_engine,
+                            suffix_attention_single_only)
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
         check_sampler(sampler, reuse_prefix, use_ddim, num_ddim_steps)
+        check_suffix_attention(suffix_attention, reuse_prefix)
         if prefill != "train":
             raise NotImplementedError(f"prefill={prefill!r}: the batched engines prefill B x S rows on the training GEMMs; the compact "
                                       "prefill serves one observation (predict_action_diff, predict_action_diff_samples)")
         B = len(images)
+        if B != 1:
+            suffix_attention_single_only(suffix_attention, f"predict_action_diff_batch with {B} observations")
         T = self.future_action_window_size + 1
         if num_samples is not None:
             return self._predict_action_diff_batch_samples(images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix,
-                                                           suffix_weights, num_samples, sampler)
+                                                           suffix_weights, num_samples, sampler, suffix_attention)
         if input_ids is None:
             if instructions is None or len(instructions) != B:
                 raise ValueError("predict_action_diff_batch needs `input_ids` (one tensor per sample), or B `instructions` plus a callable "
@@ -472,7 +488,7 @@ class MLA(nn.Module):
                                             action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b:b + 1],
                                             camera_name=camera_name, **kw)
         if B == 1:
-            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler)[None]
+            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler, suffix_attention=suffix_attention)[None]
         if suffix_weights != "bf16":
             raise NotImplementedError(f"suffix_weights={suffix_weights!r}: the batched engine (BatchedPrefixCachedEps, mla_gemm_suffix_bf16) "
                                       "streams bf16 weights only; sample B >= 2 observations with \"bf16\", one at a time, or pass "
@@ -515,7 +531,7 @@ class MLA(nn.Module):
 
     def _predict_action_diff_batch_samples(self, images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix, suffix_weights, num_samples,
-                                           sampler="host"):
+                                           sampler="host", suffix_attention="head"):
         """predict_action_diff_batch(num_samples=N) -> [B, N, T, action_dim] (called inside its inference mode; see its docstring)."""
         B, N, T = len(images), int(num_samples), self.future_action_window_size + 1
         if N < 1:
@@ -539,7 +555,8 @@ class MLA(nn.Module):
                                                     num_ddim_steps, action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b],
                                                     camera_name=camera_name, **kw)
         if B == 1:
-            return samples_of(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler)[None]
+            return samples_of(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler,
+                              suffix_attention=suffix_attention)[None]
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
                              "bf16 weights only")
@@ -592,7 +609,7 @@ class MLA(nn.Module):
                                     num_ddim_steps: int = 8, action_dim: int = 7, *, input_ids: Optional[torch.Tensor] = None,
                                     noise: Optional[torch.Tensor] = None, camera_name: str = "rlbench_front",
                                     reuse_prefix: bool = True, suffix_weights: str = "bf16", prefill: str = "train",
-                                    sampler: str = "host") -> np.ndarray:
+                                    sampler: str = "host", suffix_attention: str = "head") -> np.ndarray:
         """N action chunks for ONE observation -> [N, T, action_dim]: by definition N independent `predict_action_diff` calls on the same
         observation with the initial samples ``noise[n]`` (critic / best-of-N choice, uncertainty estimates, temporal ensembling), computed
         on ONE cached prefix (mla_amd/infer.py:SampleGroupsEps): the encoders and the decoder prefill run once per call, every sampler step
@@ -611,11 +628,17 @@ class MLA(nn.Module):
         has more than 1024 rows or head_dim is not 128.
         ``sampler`` (opt-in): predict_action_diff's modes; "device" runs the DDIM loop of every pass on the device (the same bits).
         Forwarded for ``num_samples=1``; raises ValueError when ``reuse_prefix=False``, the shared-prefix engine does not serve the shape,
-        ``use_ddim=False`` or ``num_ddim_steps=None``."""
-        from .infer import check_prefill, check_sampler, check_suffix_weights, sampler_needs_engine
+        ``use_ddim=False`` or ``num_ddim_steps=None``.
+        ``suffix_attention``: predict_action_diff's, forwarded for ``num_samples=1``; more samples with "split" raise NotImplementedError
+        (the groups engine keeps mla_attn_chunk_groups)."""
+        from .infer import (check_prefill, check_sampler, check_suffix_attention, check_suffix_weights, sampler_needs_engine,
+                            suffix_attention_single_only)
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
         check_sampler(sampler, reuse_prefix, use_ddim, num_ddim_steps)
+        check_suffix_attention(suffix_attention, reuse_prefix)
+        if int(num_samples) != 1:
+            suffix_attention_single_only(suffix_attention, f"predict_action_diff_samples with num_samples={num_samples}")
         if prefill != "train" and not reuse_prefix:
             raise ValueError(f"prefill={prefill!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has no separate "
                              "prefill")
@@ -632,7 +655,8 @@ class MLA(nn.Module):
                                             action_dim, input_ids=input_ids, noise=None if noise is None else noise[n:n + 1],
                                             camera_name=camera_name, **kw)
         if N == 1:
-            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, prefill=prefill, sampler=sampler)[None]
+            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, prefill=prefill, sampler=sampler,
+                       suffix_attention=suffix_attention)[None]
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
                              "bf16 weights only")

@@ -43,6 +43,14 @@
                                                           per-chunk latency with the 95 % interval of the pair differences, the prefill
                                                           (encoders + prefix rows) alone, and the per-step share (chunk - prefill) / steps
                                                           of both arms; also whether the two arms returned the same bits
+    python tools/bench_infer.py --pair-attention [--pairs P] [--chunks C[,C..]] [--kernel-table]
+                                                          suffix_attention="head" and "split" chunks alternating in one process, in pairs,
+                                                          for every chunk length (default 1,16) with bf16 and with fp8 suffix weights (the
+                                                          device sampler in both arms): per-chunk latency and the suffix pass alone with the
+                                                          95 % interval of the pair differences; --kernel-table first prints, without the
+                                                          model, one launch pair (split + combine) per splits in {1, 2, 3, plan, nT} against
+                                                          mla_attn_decode / mla_attn_chunk at 32 heads for (R, S_kv) = (2, 547), (17, 562);
+                                                          --pairs 0 stops after the table
 Prints one JSON line per measurement (not the driver's bench contract -- that is bench.py)."""
 import argparse
 import json
@@ -68,6 +76,7 @@ def main():
     ap.add_argument("--pair-fp8", action="store_true", help="alternate bf16 and fp8 chunks in one process, in pairs")
     ap.add_argument("--pair-prefill", action="store_true", help="alternate prefill=\"train\" and prefill=\"compact\" in one process, in pairs")
     ap.add_argument("--pair-sampler", action="store_true", help="alternate sampler=\"host\" and sampler=\"device\" in one process, in pairs")
+    ap.add_argument("--pair-attention", action="store_true", help="alternate suffix_attention=\"head\" and \"split\" in one process, in pairs")
     ap.add_argument("--pairs", type=int, default=6)
     ap.add_argument("--kernel-table", action="store_true", help="with --pair-fp8: the two _w8 kernels per projection shape and M; with "
                     "--samples: mla_attn_chunk_groups per groups-per-workgroup against mla_attn_chunk_ragged")
@@ -76,6 +85,8 @@ def main():
     args = ap.parse_args()
     if args.pair_sampler:
         return main_pair_sampler(args)
+    if args.pair_attention:
+        return main_pair_attention(args)
     batches = [int(v) for v in args.batch.split(",")]
     if args.samples and batches != [0]:
         return main_batch_samples(args, batches)
@@ -320,6 +331,131 @@ def main_pair_sampler(args):
                               "same_bits": bool(np.array_equal(acts["host"], acts["device"])),
                               "step_captured": all(st.graph is not None for st in eng._ddim.values()), "graph_error": eng.graph_error,
                               "data": "synthetic"}), flush=True)
+
+
+def _attn_split_table(dev, shapes=((2, 547), (17, 562)), H=32, layers=32, reps=5, rounds=3):
+    """One attention launch of a sampler step at 7B head count, per form: "head" = what the engine picks today (mla_attn_decode where the
+    scores fit LDS, else mla_attn_chunk), "split<s>" = mla_attn_chunk_split (both launches; one for s = 1). Every form is captured as
+    `layers` launches over `layers` different caches (442 MB at S_kv 562: nothing stays in the caches), the forms alternate per round;
+    microseconds per launch (pair) = replay time / layers, median over the rounds and every round's value."""
+    import math
+    from mla_amd import hip
+    table = {}
+    for R, S_kv in shapes:
+        caches = [(torch.randn(1, S_kv, 3 * H * 128, device=dev) * 0.7).to(torch.bfloat16) for _ in range(layers)]
+        scale = 1 / math.sqrt(128)
+        nT = -(-S_kv // 64)
+        plan = hip.plan_attn_split(1, H, R, S_kv)
+        ws = torch.empty(max(hip.attn_split_ws_bytes(1, H, R, S_kv, nT), 16), dtype=torch.uint8, device=dev)
+        head = hip.attn_decode if hip.attn_decode_fits(R, S_kv) else hip.attn_chunk
+        forms = {"head": lambda c: head(c, 1, H, 128, S_kv, R, scale)}
+        for s in sorted({1, 2, 3, plan.splits, nT}):
+            forms[f"split{s}"] = lambda c, s=s: hip.attn_chunk_split(c, 1, H, 128, S_kv, R, scale, splits=s, ws=ws)
+        graphs = {}
+        for name, fn in forms.items():
+            for c in caches[:2]:                                           # function attributes, allocator
+                fn(c)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for c in caches:
+                    fn(c)
+            g.replay()
+            graphs[name] = g
+        us = {name: [] for name in forms}
+        for _ in range(rounds):
+            for name, g in graphs.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(reps):
+                    g.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                us[name].append(round(e0.elapsed_time(e1) / (reps * layers) * 1e3, 2))
+        ref = hip.attn_chunk(caches[0], 1, H, 128, S_kv, R, scale).float()
+        table[f"R{R}_S{S_kv}"] = {"head_kernel": "mla_attn_decode" if head is hip.attn_decode else "mla_attn_chunk", "key_tiles": nT,
+                                  "plan_splits": plan.splits, "plan_workgroups": plan.workgroups,
+                                  "us_per_launch_median": {k: sorted(v)[len(v) // 2] for k, v in us.items()}, "us_per_launch_rounds": us,
+                                  "max_abs_diff_vs_attn_chunk": {k: round(float((fn(caches[0]).float() - ref).abs().max()), 5)
+                                                                 for k, fn in forms.items()},
+                                  "cache_bytes_per_launch": S_kv * 3 * H * 128 * 2}
+    return table
+
+
+def main_pair_attention(args):
+    """suffix_attention="head" vs "split" on the same box, alternating, per chunk length and suffix-weight mode: predict_action_diff per
+    chunk with the device sampler in both arms (host clock around `iters` calls that end in a device synchronise) and the captured
+    suffix pass alone (device events around 8 replays). Every figure's reference is the "head" arm of the same process."""
+    dev = torch.device("cuda", 0)
+    if args.kernel_table:
+        print(json.dumps({"metric": "suffix attention per launch, 32 heads of 128, batch 1: head vs split forms", "unit": "us",
+                          "table": _attn_split_table(dev), "data": "synthetic"}), flush=True)
+    if args.pairs < 1:
+        return
+    from bench import build
+    from mla_amd import hip
+    from mla_amd.infer import PrefixCachedEps
+    from mla_amd.synthetic import make_batch
+    torch.manual_seed(0)
+    m = build(dev, 1)
+    m.eval()
+    for p in m.parameters():
+        p.data = p.data.to(torch.bfloat16)
+    b = make_batch(B=1, device=dev)
+    ids = torch.cat([b["input_ids"][:, :-4], torch.tensor([[29871]], device=dev)], dim=1)
+    mk = dict(input_ids=ids, images=b["images"]["front_image"][:1], point_cloud=b["point_cloud"][:1], camera_name="rlbench_front",
+              proprio=b["proprio"][:1])
+    arms = ("head", "split")
+    t91 = torch.tensor([91], device=dev)
+    for C in ([int(v) for v in args.chunks.split(",")] if args.chunks else [1, 16]):
+        m.future_action_window_size = m.vlm.future_action_window_size = C - 1
+        noise = torch.randn(1, C, 7, device=dev)
+        kw = dict(image=b["images"]["front_image"][0], pointcloud=b["point_cloud"][0], cur_robot_state=b["proprio"][0, 0].cpu().numpy(),
+                  input_ids=ids, num_ddim_steps=args.steps, noise=noise, sampler="device")
+        for w in ("bf16", "fp8"):
+            acts = {}
+            for arm in arms:                                                # engines, graphs, tables; the same seed: the same FPS start indices
+                torch.manual_seed(1)
+                acts[arm] = m.predict_action_diff(suffix_weights=w, suffix_attention=arm, **kw)
+
+            def chunk_ms(arm):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.iters):
+                    m.predict_action_diff(suffix_weights=w, suffix_attention=arm, **kw)
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / args.iters * 1e3
+
+            def pass_ms(arm):
+                with torch.inference_mode():
+                    eng = PrefixCachedEps.for_inputs(m.vlm, n_action_rows=C, suffix_weights=w, suffix_attention=arm, **mk)
+                    eng(noise, t91)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(8):
+                        eng._run()
+                    e1.record()
+                    torch.cuda.synchronize()
+                return e0.elapsed_time(e1) / 8, eng
+            chunk, suffix = {arm: [] for arm in arms}, {arm: [] for arm in arms}
+            for _ in range(args.pairs):                                     # head, split, head, split, ...: same box, interleaved
+                for arm in arms:
+                    chunk[arm].append(chunk_ms(arm))
+                for arm in arms:
+                    suffix[arm].append(pass_ms(arm)[0])
+            eng = pass_ms("split")[1]
+            plan = hip.plan_attn_split(1, eng.nheads, eng.R, eng.S_cap)
+            print(json.dumps({"metric": "predict_action_diff, MLA-Llama2-7B, batch 1: suffix_attention=head vs split in alternating pairs",
+                              "action_chunk": C, "suffix_rows": C + 1, "suffix_weights": w, "sampler": "device", "ddim_steps": args.steps,
+                              "pairs": args.pairs, "iters_per_arm_and_pair": args.iters, "unit": "ms", "S_kv": eng.S_cap,
+                              "plan_splits": plan.splits, "plan_workgroups": plan.workgroups,
+                              "chunk_ms": {k: [round(v, 2) for v in vs] for k, vs in chunk.items()},
+                              "chunk_split_minus_head": _pair_stats(chunk["head"], chunk["split"]),
+                              "suffix_pass_ms": {k: [round(v, 3) for v in vs] for k, vs in suffix.items()},
+                              "suffix_pass_split_minus_head": _pair_stats(suffix["head"], suffix["split"]),
+                              "split_vs_head_chunk_rel_diff_random_weights":
+                                  round(float(((acts["split"] - acts["head"]) ** 2).sum() ** 0.5 / (acts["head"] ** 2).sum() ** 0.5), 5),
+                              "pass_captured": eng.graph is not None, "graph_error": eng.graph_error, "data": "synthetic"}), flush=True)
 
 
 def main_pair_prefill(args):
