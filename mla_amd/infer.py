@@ -46,6 +46,9 @@ from . import hip, ops
 _USE_GRAPH = os.environ.get("MLA_INFER_GRAPH", "1") != "0"
 _LOG = logging.getLogger(__name__)
 
+SPLICE_TAG = 29871                                  # prismatic.py:882-887 (eval): the [t, x] tokens go in front of its last occurrence
+PROMPT_TAIL = (29871, 32001, 32002, 29871)          # model_mla.py:640-645: appended unless the row already ends with the tag, then [:-3]
+
 # What the suffix pass streams (MLA.predict_action_diff(suffix_weights=...)); the prefill always runs the training kernels on the bf16 weights,
 # so the prefix keys / values keep bf16-weight precision:
 #   "bf16"         the decoder weights as they are (default)
@@ -176,6 +179,39 @@ class _CachedEpsBase:
         self._suffix = None          # per layer: what the suffix pass streams -- _packed itself ("bf16") or a quantised copy (_quantised)
         self._ddim = {}              # sample_ddim's state per (B, action_dim): see _DdimState
 
+    @classmethod
+    def _serves(cls, vlm, rows: int, limit: int, tag: tuple, message: str, warn: bool = True) -> bool:
+        """The shape predicate of every engine (supports*): `rows` suffix rows within `limit` and head_dim 128. Otherwise False, with
+        `message` as a RuntimeWarning once per (tag, rows, head_dim) and model unless warn=False."""
+        cfg = vlm.llm_backbone.llm.config
+        D = cfg.hidden_size // cfg.num_attention_heads
+        if rows <= limit and D == 128:
+            return True
+        seen = vlm.__dict__.setdefault("_prefix_unsupported", set())
+        if warn and tag + (rows, D) not in seen:
+            seen.add(tag + (rows, D))
+            warnings.warn(message.format(rows=rows, limit=limit, D=D), RuntimeWarning, stacklevel=4)
+        return False
+
+    @classmethod
+    def _engine(cls, vlm, store: str, key: tuple, ctor: tuple, suffix_weights="bf16", prefill="train", suffix_attention="head"):
+        """The vlm's engine for `key` in vlm.__dict__[store], constructed as cls(vlm, *ctor) on first use; at most 4 per store, the oldest
+        leaves first. A mode other than the default is part of the key -- the engines coexist: a captured graph holds the addresses of
+        ITS weights and ITS attention launches. The caller prefills."""
+        engines = vlm.__dict__.setdefault(store, {})
+        if suffix_weights != "bf16":
+            key += (suffix_weights,)
+        if prefill != "train":
+            key += ("prefill:" + prefill,)
+        if suffix_attention != "head":
+            key += ("attention:" + suffix_attention,)
+        eng = engines.get(key)
+        if eng is None:
+            if len(engines) >= 4:
+                engines.pop(next(iter(engines)))
+            eng = engines[key] = cls(vlm, *ctor)
+        return eng
+
     def _weights(self):
         """Every layer's (ln1, wq, wk, wv, wo, ln2, wg, wu, wd) with q|k|v and gate|up adjacent in memory, so that the prefill runs the
         fused QKV + RoPE and gate|up + SwiGLU GEMMs and a suffix pass needs one GEMV each instead of three / two (33 MB projections are
@@ -232,6 +268,31 @@ class _CachedEpsBase:
                     deq.append((ln1, qkv[:nq], qkv[nq:nq + nk], qkv[nq + nk:], o, ln2, gu[:ng], gu[ng:], d))
             shared["fp8_as_bf16"] = deq
         return shared[self.suffix_weights]
+
+    def _suffix_layers(self):
+        """Per layer ((ln1, qkv, o, ln2, gate_up, down), cache) of a suffix pass: every projection one W8 ("fp8", _quantised) or a tuple
+        of bf16 matrices -- views of the packed 9-tuple ("bf16") or of its dequantised twin ("fp8_as_bf16")."""
+        for w, c in zip(self._suffix, self.cache):
+            yield (w if self.suffix_weights == "fp8" else (w[0], w[1:4], w[4:5], w[5], w[6:8], w[8:9])), c
+
+    def _finish(self, h):
+        """The end of every suffix pass: the model's final norm over the rows, into the static output rows."""
+        hn, _ = hip.rmsnorm_fwd(h, self.model.norm.weight, self.eps)
+        self.h_out.copy_(hn)
+
+    def _prefill_rows(self, h, B, S_p, out_bs, weights=None):
+        """The decoder layers over the prefix rows h [B * S_p, H] of B samples with S_p rows each, every layer's packed post-RoPE q|k|v
+        rows (`LayerActs.qkv`) into rows [0, S_p) of its cache ([B, S_cap, 3H], or [rows, 3H] for one sample): on the training forward
+        kernels, one layer at a time, or ("compact") on the row-sized GEMMs, which write the cache rows themselves (sample b at element
+        offset b * out_bs). weights: what _weights() returned, when the caller has called it already."""
+        if self.prefill_mode == "compact":
+            self._compact_prefill(h, B, S_p, self.cache, out_bs)
+            return
+        for w, c in zip(self._weights() if weights is None else weights, self.cache):
+            h, acts = ops.DecoderLayerFn._fwd(h, None, self.cos_p, self.sin_p, B, S_p, self.nheads, self.eps, w)
+            rows = c[:, :S_p] if c.dim() == 3 else c[:S_p]
+            rows.copy_(acts.qkv[:B * S_p].view(rows.shape))
+            del acts
 
     def _prefix_rows(self, input_ids, k, images, point_cloud, camera_name, proprio, tactile=None, gripper_xyz=None):
         """The decoder's input rows in front of the [t, x] tokens, [B, S_p, H]: [BOS | fused tokens | text[1:k] | proprio] (call under no_grad)."""
@@ -432,11 +493,10 @@ class PrefixCachedEps(_CachedEpsBase):
 
     @staticmethod
     def _splice_position(input_ids):
-        tag_0 = 29871                                                        # prismatic.py:882-887 (eval)
         L = input_ids.shape[1]
-        is_tag = input_ids == tag_0
+        is_tag = input_ids == SPLICE_TAG
         if not bool(is_tag.any(dim=1).all()):
-            raise IndexError(f"input_ids row without the splice tag {tag_0} (models/vlm/prismatic.py:983)")
+            raise IndexError(f"input_ids row without the splice tag {SPLICE_TAG} (models/vlm/prismatic.py:983)")
         k = (L - 1 - torch.flip(is_tag, dims=[1]).int().argmax(dim=1))       # last occurrence per row
         if not bool((k == k[0]).all()):
             raise ValueError("PrefixCachedEps needs the same splice position in every row (predict_action_diff is batch 1)")
@@ -448,16 +508,8 @@ class PrefixCachedEps(_CachedEpsBase):
     def supports(cls, vlm, batch: int, n_action_rows: int) -> bool:
         """Whether the suffix pass's kernels serve this shape: B * (1 + T) <= 64 rows and head_dim 128. Otherwise the caller runs the
         reference's control flow (a whole forward per sampler step); warns once per shape."""
-        cfg = vlm.llm_backbone.llm.config
-        rows, D = batch * (1 + n_action_rows), cfg.hidden_size // cfg.num_attention_heads
-        if rows <= cls.MAX_ROWS and D == 128:
-            return True
-        seen = vlm.__dict__.setdefault("_prefix_unsupported", set())
-        if (rows, D) not in seen:
-            seen.add((rows, D))
-            warnings.warn(f"PrefixCachedEps: {rows} suffix rows (max {cls.MAX_ROWS}) / head_dim {D} (needs 128) are beyond the cached-prefix "
-                          "kernels; sampling with a whole forward per step", RuntimeWarning, stacklevel=3)
-        return False
+        return cls._serves(vlm, batch * (1 + n_action_rows), cls.MAX_ROWS, (), "PrefixCachedEps: {rows} suffix rows (max {limit}) / head_dim "
+                           "{D} (needs 128) are beyond the cached-prefix kernels; sampling with a whole forward per step")
 
     @classmethod
     def for_inputs(cls, vlm, input_ids, n_action_rows: int = 1, suffix_weights: str = "bf16", prefill: str = "train",
@@ -466,19 +518,9 @@ class PrefixCachedEps(_CachedEpsBase):
         check_prefill(prefill)
         check_suffix_attention(suffix_attention)
         k = cls._splice_position(input_ids)
-        engines = vlm.__dict__.setdefault("_prefix_engines", {})
-        key = (int(input_ids.shape[0]), k, int(n_action_rows), str(input_ids.device))
-        if suffix_weights != "bf16":
-            key += (suffix_weights,)                                          # a captured graph holds the addresses of ITS weights
-        if prefill != "train":
-            key += ("prefill:" + prefill,)                                    # the mode is part of the key: the engines coexist
-        if suffix_attention != "head":
-            key += ("attention:" + suffix_attention,)                         # a captured graph holds ITS attention launches
-        eng = engines.get(key)
-        if eng is None:
-            if len(engines) >= 4:                                             # a handful of prompt lengths per process; each engine holds 0.4 GB at 7B
-                engines.pop(next(iter(engines)))
-            eng = engines[key] = cls(vlm, n_action_rows, suffix_weights, prefill, suffix_attention)
+        # a handful of prompt lengths per process; each engine holds 0.4 GB at 7B
+        eng = cls._engine(vlm, "_prefix_engines", (int(input_ids.shape[0]), k, int(n_action_rows), str(input_ids.device)),
+                          (n_action_rows, suffix_weights, prefill, suffix_attention), suffix_weights, prefill, suffix_attention)
         eng.prefill(input_ids, k, **model_kwargs)
         return eng
 
@@ -508,15 +550,7 @@ class PrefixCachedEps(_CachedEpsBase):
                             raise RuntimeError(f"mla_attn_chunk_split_ws_bytes: {hip.lib().mla_last_error().decode()}")
                         self._attn_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
             assert (B, S_p, H) == (self.B, self.S_p, self.H)
-            h = prefix.reshape(B * S_p, H)
-            if self.prefill_mode == "compact":                               # the row-sized GEMMs write the cache rows themselves
-                self._compact_prefill(h, B, S_p, self.cache, self.cache[0].stride(0))
-                return
-            # ---- prefill: the training forward kernels, one layer at a time; keep the packed post-RoPE q|k|v rows
-            for w, c in zip(self._weights(), self.cache):
-                h, acts = ops.DecoderLayerFn._fwd(h, None, self.cos_p, self.sin_p, B, S_p, self.nheads, self.eps, w)
-                c[:, :S_p].copy_(acts.qkv[:B * S_p].view(B, S_p, 3 * H))
-                del acts
+            self._prefill_rows(prefix.reshape(B * S_p, H), B, S_p, self.cache[0].stride(0))
 
     def _suffix_attn(self):
         """The attention launch of the suffix pass: "head" -- mla_attn_decode where the R x S_kv scores fit LDS, mla_attn_chunk's online
@@ -529,20 +563,25 @@ class PrefixCachedEps(_CachedEpsBase):
 
     # ------------------------------------------------------------------------------------------ one pass over the suffix rows
     def _gemv(self, x, weights, out=None, residual=None, rpb=1, out_bs=0, **pre):
-        """f(x) [M, K] @ cat(weights)^T (+ residual) -> [M, sum N]; one launch when the weights are adjacent in memory.
+        """f(x) [M, K] @ W^T (+ residual) -> [M, N]; `weights` is a tuple of bf16 matrices (one launch when they are adjacent in memory) or
+        one W8 (always packed: one launch).
         pre: norm_weight= / eps= (RMSNorm of the rows) or swiglu=True (x = packed gate|up rows), applied inside the kernel's input staging."""
-        M = x.shape[0]
-        if isinstance(weights, W8):
-            return self._gemv_w8(x, weights, out, residual, rpb, out_bs, **pre)
-        wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
-        N = sum(w.shape[0] for w in weights)
+        M, w8 = x.shape[0], isinstance(weights, W8)
+        N, K = weights.q.shape if w8 else (sum(w.shape[0] for w in weights), weights[0].shape[1])
         if out is None:
             out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
             rpb, out_bs = M, 0
         ldo = out.stride(-2)
-        # mla_gemv_bf16 wherever it accepts the rows (the results of every configuration it served stay bit for bit the same), the MFMA
-        # skinny GEMM beyond (M > 8, or the M x K input rows do not fit its LDS: 7B down projection at M = 8)
-        gemv = hip.gemv if hip.gemv_fits(M, weights[0].shape[1]) else hip.gemm_skinny
+        # mla_gemv_bf16 / mla_gemv_w8 wherever they accept the rows (the results of every configuration they served stay bit for bit the
+        # same), the MFMA skinny GEMM beyond (M > 8, or the M x K input rows do not fit the LDS: 7B down projection at M = 8). Measured
+        # for w8 at 7B (DESIGN 3.5, profiles/fp8_infer_latency.txt): right at M = 2; at M = 5 .. 8 the MFMA form would be 2-7 % faster per
+        # layer, M = 3, 4 not measured -- the switch point is left here until they are.
+        fits = hip.gemv_fits(M, K)
+        if w8:
+            (hip.gemv_w8 if fits else hip.gemm_skinny_w8)(x, weights.q, weights.scale, out, ldo, out_bs, rpb, residual, **pre)
+            return out
+        gemv = hip.gemv if fits else hip.gemm_skinny
+        wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
         if wcat is not None:
             gemv(x, wcat, out, ldo, out_bs, rpb, residual, **pre)
         else:                                                                # parameters not laid out back to back (no FlatUnit): one launch each
@@ -552,26 +591,17 @@ class PrefixCachedEps(_CachedEpsBase):
                 off += w.shape[0]
         return out
 
-    def _gemv_w8(self, x, w, out, residual, rpb, out_bs, **pre):
-        """_gemv over a quantised (always packed) weight: one launch. Kernel choice: the bf16 rule -- mla_gemv_w8 where the rows fit its LDS,
-        the MFMA form beyond. Measured at 7B (profiles/fp8_infer_latency.txt): right at M = 2; at M = 5 .. 8 the MFMA form
-        would be 2-7 % faster per layer, M = 3, 4 not measured -- the switch point is left here until they are."""
-        M = x.shape[0]
-        if out is None:
-            out = torch.empty((M, w.q.shape[0]), dtype=torch.bfloat16, device=x.device)
-            rpb, out_bs = M, 0
-        kern = hip.gemv_w8 if hip.gemv_fits(M, w.q.shape[1]) else hip.gemm_skinny_w8
-        kern(x, w.q, w.scale, out, out.stride(-2), out_bs, rpb, residual, **pre)
-        return out
-
-    def _suffix_pass_w8(self):
-        """_suffix_pass over the FP8 copy: the same five launches per layer, activations / cache / attention untouched."""
+    def _suffix_pass(self):
+        """Five launches per layer, whatever the suffix pass streams (bf16 views or the FP8 copy: activations / cache / attention are the
+        same)."""
         B, R, H, S_p, S_cap = self.B, self.R, self.H, self.S_p, self.S_cap
         h = self.h_in
         scale = 1.0 / math.sqrt(self.D)
-        attn = self._suffix_attn()
-        fused = self.D == 128
-        for (ln1, qkv, wo, ln2, gu, wd), c in zip(self._suffix, self.cache):
+        attn = self._suffix_attn()                                             # "head": R x S_kv scores in LDS vs online softmax
+        for (ln1, qkv, wo, ln2, gu_w, wd), c in self._suffix_layers():
+            # north_star's "fused RMSNorm + RoPE + QKV" as ONE kernel: RMSNorm inside the projection's input staging, the rotary embedding of
+            # the q and k columns in its epilogue; the rows go straight into the cache slots [S_p, S_p + R) of every sample
+            fused = self.D == 128 and (isinstance(qkv, W8) or ops.cat_view(qkv) is not None)
             self._gemv(h, qkv, out=c[:, S_p:], rpb=R, out_bs=c.stride(0), norm_weight=ln1, eps=self.eps,
                        **({"rope": (self.cos_s, self.sin_s, 2 * H)} if fused else {}))
             if not fused:
@@ -579,45 +609,16 @@ class PrefixCachedEps(_CachedEpsBase):
                     hip.rope_inplace(c[b, S_p:], self.cos_s, self.sin_s, R, self.nheads, self.D, 0, H)
             o = attn(c, B, self.nheads, self.D, S_cap, R, scale)
             h1 = self._gemv(o, wo, residual=h)
-            g = self._gemv(h1, gu, norm_weight=ln2, eps=self.eps)
-            h = self._gemv(g, wd, residual=h1, swiglu=True)
-        hn, _ = hip.rmsnorm_fwd(h, self.model.norm.weight, self.eps)
-        self.h_out.copy_(hn)
-
-    def _suffix_pass(self):
-        if self.suffix_weights == "fp8":
-            return self._suffix_pass_w8()
-        B, R, H, S_p, S_cap = self.B, self.R, self.H, self.S_p, self.S_cap
-        h = self.h_in
-        scale = 1.0 / math.sqrt(self.D)
-        attn = self._suffix_attn()                                             # "head": R x S_kv scores in LDS vs online softmax
-        for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd), c in zip(self._suffix, self.cache):
-            # north_star's "fused RMSNorm + RoPE + QKV" as ONE kernel: RMSNorm inside the projection's input staging, the rotary embedding of
-            # the q and k columns in its epilogue; the rows go straight into the cache slots [S_p, S_p + R) of every sample
-            fused = ops.cat_view((wq, wk, wv)) is not None and self.D == 128
-            self._gemv(h, (wq, wk, wv), out=c[:, S_p:], rpb=R, out_bs=c.stride(0), norm_weight=ln1, eps=self.eps,
-                       **({"rope": (self.cos_s, self.sin_s, 2 * H)} if fused else {}))
-            if not fused:
-                for b in range(B):
-                    hip.rope_inplace(c[b, S_p:], self.cos_s, self.sin_s, R, self.nheads, self.D, 0, H)
-            o = attn(c, B, self.nheads, self.D, S_cap, R, scale)
-            h1 = self._gemv(o, (wo,), residual=h)
-            gu = self._gemv(h1, (wg, wu), norm_weight=ln2, eps=self.eps)
-            h = self._gemv(gu, (wd,), residual=h1, swiglu=True)                # SwiGLU inside the down projection's input staging
-        hn, _ = hip.rmsnorm_fwd(h, self.model.norm.weight, self.eps)
-        self.h_out.copy_(hn)
+            gu = self._gemv(h1, gu_w, norm_weight=ln2, eps=self.eps)
+            h = self._gemv(gu, wd, residual=h1, swiglu=True)                   # SwiGLU inside the down projection's input staging
+        self._finish(h)
 
 
-
-# ================================================================================================ batched action sampling
-# B observations with prompts of different lengths on ONE cached-prefix pass (MLA.predict_action_diff_batch; the reference's
+# ================================================================================================ the row-GEMM engines
+# More than one chunk per pass: B observations with prompts of different lengths (MLA.predict_action_diff_batch; the reference's
 # `predict_action_batch`, models/mla/model_mla.py:994, names the use case -- "batch inference in the simulators" -- but reads an attribute
-# MLA never defines). A pass streams the decoder weights once whatever the row count, so N environments cost one prefill on the
-# training GEMMs plus 8 weight passes instead of N prefills plus 8 N passes.
-SPLICE_TAG = 29871                                  # prismatic.py:882-887 (eval): the [t, x] tokens go in front of its last occurrence
-PROMPT_TAIL = (29871, 32001, 32002, 29871)          # model_mla.py:640-645: appended unless the row already ends with the tag, then [:-3]
-
-
+# MLA never defines), N draws for one observation (predict_action_diff_samples), or both. A pass streams the decoder weights once whatever
+# the row count, so the chunks of a pass cost one prefill plus 8 weight passes instead of one prefill and 8 passes each.
 class SubBatchPlan(NamedTuple):
     """One cached-prefix pass of `plan_batch`: samples [start, stop) of the call. Per sample b: ids[b] the final prompt ids, k[b] the splice
     position (the last tag), S_p[b] prefix rows ([BOS | front tokens | text[1:k] | proprio]), slot[b] = S_p[b] the first cache row of its
@@ -671,31 +672,116 @@ def plan_batch(ids_rows: Sequence[Sequence[int]], n_action_rows: int, n_front: i
     return plans
 
 
-class BatchedPrefixCachedEps(_CachedEpsBase):
-    """PrefixCachedEps for B samples whose splice tags sit at different positions. The prefixes are right-padded to S_pmax and prefilled in
-    one varlen pass per layer (ops.DecoderLayerFn._fwd with seqlens); the cache is [B, S_cap, 3H] and the suffix rows of sample b live at
-    rows S_p[b] .. S_p[b] + R (rows behind them are never read). `slot` and `kv_len` are device tensors the kernels read
-    (mla_gemm_suffix_bf16, mla_attn_chunk_ragged), refreshed by copy_ in prefill(): one engine -- and one captured graph -- per
-    (B, S_cap, R, device) serves every mix of prompt lengths in that capacity bucket. RMSNorm / SwiGLU are formed once per projection by
-    the stand-alone kernels (the values the fused forms produce), then the plain weight-streaming GEMM runs over up to 256 rows."""
+class _RowGemmEps(_CachedEpsBase):
+    """What BatchedPrefixCachedEps, SampleGroupsEps and BatchedSampleGroupsEps share: the suffix pass over up to 256 rows. RMSNorm / SwiGLU
+    are formed once per projection by the stand-alone kernels (the values the fused forms produce), then the plain weight-streaming GEMM
+    (mla_gemm_suffix_bf16, or mla_gemm_suffix_w8 over the model's FP8 copy) runs over all M suffix rows of the pass. Per layer, c = the
+    layer's cache:
+        rmsnorm_fwd -> q|k|v into the cache, q and k rotated in the epilogue -> attention -> o + residual -> rmsnorm_fwd -> gate|up ->
+        swiglu_fwd -> down + residual
+    An engine says where the q|k|v rows land (_cache_write) and which attention reads them (_attention); everything else is the same.
+    The two engines with ragged prompts also share the prefill: right-padded prefixes, one varlen pass per layer (_varlen_prefill)."""
 
-    MAX_ROWS = 256                   # suffix rows per pass (mla_gemm_suffix_bf16); larger batches are served as consecutive sub-batches
-    MAX_R = 64                       # rows per sample (mla_attn_chunk_ragged)
-    BUCKET = 64                      # cache capacity granularity in rows
+    MAX_ROWS = 256                   # suffix rows per pass (mla_gemm_suffix_bf16 / _w8 and their `_pos` forms); more are served as consecutive passes
+    MAX_R = 64                       # rows per sample / group (mla_attn_chunk_ragged, mla_attn_chunk_groups, mla_attn_chunk_ragged_groups)
+    BUCKET = 64                      # cache capacity granularity in rows (the engines with ragged prompts)
+
+    def _cache_write(self, c):
+        """-> (ldo, out_batch_stride, keywords) of the q|k|v projection into the layer's cache c (rows_per_batch is R)."""
+        raise NotImplementedError
+
+    def _attention(self, c, scale):
+        raise NotImplementedError
+
+    def _proj(self, x, weights, out=None, residual=None):
+        """x [M, K] @ W^T (+ residual): `weights` is a tuple of adjacent bf16 views (mla_gemm_suffix_bf16) or one W8 (mla_gemm_suffix_w8);
+        out = a layer's cache: the q|k|v rows go to their samples' / groups' slots."""
+        if isinstance(weights, W8):
+            N, gemm = weights.q.shape[0], functools.partial(hip.gemm_suffix_w8, x, weights.q, weights.scale)
+        else:
+            wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
+            assert wcat is not None, "the packed weights are adjacent in memory (_weights)"
+            N, gemm = wcat.shape[0], functools.partial(hip.gemm_suffix, x, wcat)
+        M = x.shape[0]
+        if out is None:
+            out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+            gemm(out, out.stride(0), 0, M, residual)
+        else:
+            ldo, out_bs, kw = self._cache_write(out)
+            gemm(out, ldo, out_bs, self.R, residual, **kw)
+        return out
+
+    def _suffix_pass(self):
+        h = self.h_in
+        scale = 1.0 / math.sqrt(self.D)
+        for (ln1, qkv, wo, ln2, gu_w, wd), c in self._suffix_layers():
+            xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
+            self._proj(xn, qkv, out=c)
+            o = self._attention(c, scale)
+            h1 = self._proj(o, wo, residual=h)
+            xn2, _ = hip.rmsnorm_fwd(h1, ln2, self.eps)
+            gu = self._proj(xn2, gu_w)
+            h = self._proj(hip.swiglu_fwd(gu), wd, residual=h1)
+        self._finish(h)
+
+    @staticmethod
+    def _front_tokens(vlm, images, point_cloud, camera_name):
+        """The encoders once over all observations of a call -> [B, n_front, H], the fused tokens between BOS and the text."""
+        with torch.no_grad():
+            parts, _, _, _, _, _ = vlm.get_fused_tokens(images, point_cloud, None, None, camera_name)
+            vlm.vision_tower_2d.assert_masks_ok()
+            return torch.cat(parts, dim=1)
+
+    def _varlen_prefill(self, sub, front, proprio, G, index):
+        """The prefill of observations [sub.start, sub.stop) with G groups of suffix rows each: the prefixes right-padded to S_pmax, one
+        varlen pass per layer on the training kernels (ops.DecoderLayerFn._fwd with seqlens; the bf16 weights, whatever the suffix pass
+        streams), the rows copied into the [NB, S_cap, 3H] cache. index: {attribute: values} of the int32 device tensors the suffix
+        pass's kernels read, allocated on the first call and refreshed by copy_ (a captured graph keeps their addresses)."""
+        vlm, bf16, dev = self.vlm, torch.bfloat16, front.device
+        NB, S_pmax = sub.stop - sub.start, sub.S_pmax
+        with torch.no_grad():
+            proprio_e = vlm.proprio_embedder(proprio.to(bf16))                # [NB, 1, H]
+            H = front.shape[2]
+            prefix = torch.zeros((NB, S_pmax, H), dtype=bf16, device=dev)
+            for b in range(NB):
+                e = vlm.llm_backbone.embed_input_ids(torch.tensor([sub.ids[b]], dtype=torch.long, device=dev))[0]
+                prefix[b, :sub.S_p[b]] = torch.cat([e[:1], front[b], e[1:sub.k[b]], proprio_e[b]], dim=0)
+            if self.cache is None:
+                self.NB, self.G, self.B, self.H, self.S_cap = NB, G, NB * G, H, sub.S_cap        # B = NB * G is the sampler's batch
+                self.D = H // self.nheads
+                self.rot = self.model.layers[0].self_attn.rotary_emb
+                self.cos_c, self.sin_c = self.rot.tables(self.S_cap, dev)    # the epilogue rotates a suffix row with the table row of its position
+                rows = NB * G * self.R
+                with torch.inference_mode(False):                            # the engine outlives the (inference-mode) call that creates it
+                    self.cache = [torch.zeros((NB, self.S_cap, 3 * H), dtype=bf16, device=dev) for _ in self.model.layers]
+                    self.h_in = torch.zeros((rows, H), dtype=bf16, device=dev)
+                    self.h_out = torch.zeros((rows, H), dtype=bf16, device=dev)
+                    for name, values in index.items():
+                        setattr(self, name, torch.zeros(len(values), dtype=torch.int32, device=dev))
+            assert (NB, G, H, sub.S_cap, sub.R) == (self.NB, self.G, self.H, self.S_cap, self.R) and S_pmax + G * self.R <= self.S_cap
+            for name, values in index.items():
+                getattr(self, name).copy_(torch.tensor(values, dtype=torch.int32))
+            seqlens = torch.tensor(sub.S_p, dtype=torch.int32, device=dev)
+            cos_p, sin_p = self.rot.tables(S_pmax, dev)
+            h = prefix.reshape(NB * S_pmax, H)
+            for w, c in zip(self._weights(), self.cache):
+                h, acts = ops.DecoderLayerFn._fwd(h, seqlens, cos_p, sin_p, NB, S_pmax, self.nheads, self.eps, w)
+                c[:, :S_pmax].copy_(acts.qkv[:NB * S_pmax].view(NB, S_pmax, 3 * H))
+                del acts
+
+
+class BatchedPrefixCachedEps(_RowGemmEps):
+    """PrefixCachedEps for B samples whose splice tags sit at different positions (bf16 weights only). The cache is [B, S_cap, 3H] and the
+    suffix rows of sample b live at rows S_p[b] .. S_p[b] + R (rows behind them are never read). `slot` and `kv_len` are device tensors
+    the kernels read (mla_gemm_suffix_bf16, mla_attn_chunk_ragged), refreshed by copy_ in prefill(): one engine -- and one captured graph
+    -- per (B, S_cap, R, device) serves every mix of prompt lengths in that capacity bucket."""
 
     @classmethod
     def supports_batch(cls, vlm, n_action_rows: int) -> bool:
         """head_dim 128 and at most 64 suffix rows per sample; otherwise the caller loops over whole-forward batch-1 calls (warns once)."""
-        cfg = vlm.llm_backbone.llm.config
-        R, D = 1 + n_action_rows, cfg.hidden_size // cfg.num_attention_heads
-        if R <= cls.MAX_R and D == 128:
-            return True
-        seen = vlm.__dict__.setdefault("_prefix_unsupported", set())
-        if ("batch", R, D) not in seen:
-            seen.add(("batch", R, D))
-            warnings.warn(f"BatchedPrefixCachedEps: {R} suffix rows per sample (max {cls.MAX_R}) / head_dim {D} (needs 128) are beyond the "
-                          "batched cached-prefix kernels; sampling every observation with a whole forward per step", RuntimeWarning, stacklevel=3)
-        return False
+        return cls._serves(vlm, 1 + n_action_rows, cls.MAX_R, ("batch",), "BatchedPrefixCachedEps: {rows} suffix rows per sample (max {limit}) "
+                           "/ head_dim {D} (needs 128) are beyond the batched cached-prefix kernels; sampling every observation with a whole "
+                           "forward per step")
 
     @classmethod
     def for_batch(cls, vlm, ids_rows, n_action_rows: int, images=None, point_cloud=None, camera_name=None, proprio=None, add_tail=True,
@@ -703,89 +789,28 @@ class BatchedPrefixCachedEps(_CachedEpsBase):
         """Generator over the passes of one call: runs the encoders once over all samples, plans (plan_batch: ids_rows are the prompts as
         the caller has them, the prompt tail is handled there) and yields
         (SubBatchPlan, prefilled engine) per sub-batch. Two sub-batches may share an engine: finish sampling one before taking the next."""
-        with torch.no_grad():
-            parts, _, _, _, _, _ = vlm.get_fused_tokens(images, point_cloud, None, None, camera_name)
-            vlm.vision_tower_2d.assert_masks_ok()
-            front = torch.cat(parts, dim=1)                                   # [B, n_front, H]
-        plans = plan_batch(ids_rows, n_action_rows, int(front.shape[1]), cls.MAX_ROWS, cls.BUCKET, add_tail=add_tail)
-        engines = vlm.__dict__.setdefault("_prefix_engines_batched", {})
-        for sub in plans:
-            key = (sub.stop - sub.start, sub.S_cap, sub.R, str(front.device))
-            eng = engines.get(key)
-            if eng is None:
-                if len(engines) >= 4:
-                    engines.pop(next(iter(engines)))
-                eng = engines[key] = cls(vlm, n_action_rows)
+        front = cls._front_tokens(vlm, images, point_cloud, camera_name)
+        for sub in plan_batch(ids_rows, n_action_rows, int(front.shape[1]), cls.MAX_ROWS, cls.BUCKET, add_tail=add_tail):
+            eng = cls._engine(vlm, "_prefix_engines_batched", (sub.stop - sub.start, sub.S_cap, sub.R, str(front.device)), (n_action_rows,))
             eng.prefill(sub, front[sub.start:sub.stop], proprio[sub.start:sub.stop])
             yield sub, eng
 
     def prefill(self, sub: SubBatchPlan, front, proprio):
-        vlm, bf16, dev = self.vlm, torch.bfloat16, front.device
-        B, S_pmax = sub.stop - sub.start, sub.S_pmax
-        with torch.no_grad():
-            proprio_e = vlm.proprio_embedder(proprio.to(bf16))                # [B, 1, H]
-            H = front.shape[2]
-            prefix = torch.zeros((B, S_pmax, H), dtype=bf16, device=dev)
-            for b in range(B):
-                e = vlm.llm_backbone.embed_input_ids(torch.tensor([sub.ids[b]], dtype=torch.long, device=dev))[0]
-                prefix[b, :sub.S_p[b]] = torch.cat([e[:1], front[b], e[1:sub.k[b]], proprio_e[b]], dim=0)
-            if self.cache is None:
-                self.B, self.H, self.S_cap = B, H, sub.S_cap
-                self.D = H // self.nheads
-                self.rot = self.model.layers[0].self_attn.rotary_emb
-                self.cos_c, self.sin_c = self.rot.tables(self.S_cap, dev)    # the epilogue rotates row slot[b] + p with table row slot[b] + p
-                with torch.inference_mode(False):                            # the engine outlives the (inference-mode) call that creates it
-                    self.cache = [torch.zeros((B, self.S_cap, 3 * H), dtype=bf16, device=dev) for _ in self.model.layers]
-                    self.h_in = torch.zeros((B * self.R, H), dtype=bf16, device=dev)
-                    self.h_out = torch.zeros((B * self.R, H), dtype=bf16, device=dev)
-                    self.slot = torch.zeros(B, dtype=torch.int32, device=dev)
-                    self.kv_len = torch.full((B,), self.R, dtype=torch.int32, device=dev)
-            assert (B, H, sub.S_cap, sub.R) == (self.B, self.H, self.S_cap, self.R) and S_pmax + self.R <= self.S_cap
-            self.slot.copy_(torch.tensor(sub.slot, dtype=torch.int32))
-            self.kv_len.copy_(torch.tensor(sub.kv_len, dtype=torch.int32))
-            seqlens = torch.tensor(sub.S_p, dtype=torch.int32, device=dev)
-            cos_p, sin_p = self.rot.tables(S_pmax, dev)
-            h = prefix.reshape(B * S_pmax, H)
-            for w, c in zip(self._weights(), self.cache):
-                h, acts = ops.DecoderLayerFn._fwd(h, seqlens, cos_p, sin_p, B, S_pmax, self.nheads, self.eps, w)
-                c[:, :S_pmax].copy_(acts.qkv[:B * S_pmax].view(B, S_pmax, 3 * H))
-                del acts
+        self._varlen_prefill(sub, front, proprio, 1, {"slot": sub.slot, "kv_len": sub.kv_len})
 
-    def _proj(self, x, weights, out=None, residual=None, **kw):
-        wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
-        assert wcat is not None, "the packed weights are adjacent in memory (_weights)"
-        M = x.shape[0]
-        if out is None:
-            out = torch.empty((M, wcat.shape[0]), dtype=torch.bfloat16, device=x.device)
-            hip.gemm_suffix(x, wcat, out, out.stride(0), 0, M, residual)
-        else:
-            hip.gemm_suffix(x, wcat, out, out.stride(-2), out.stride(0), self.R, residual, **kw)
-        return out
+    def _cache_write(self, c):
+        # q|k|v rows of sample b -> cache rows slot[b] .. slot[b] + R, q and k rotated at those positions
+        return c.stride(-2), c.stride(0), {"slot": self.slot, "cap_rows": self.S_cap, "rope": (self.cos_c, self.sin_c, 2 * self.H)}
 
-    def _suffix_pass(self):
-        B, R, H = self.B, self.R, self.H
-        h = self.h_in
-        scale = 1.0 / math.sqrt(self.D)
-        for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd), c in zip(self._packed, self.cache):
-            xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
-            # q|k|v rows of sample b -> cache rows slot[b] .. slot[b] + R, q and k rotated at those positions in the epilogue
-            self._proj(xn, (wq, wk, wv), out=c, slot=self.slot, cap_rows=self.S_cap, rope=(self.cos_c, self.sin_c, 2 * H))
-            o = hip.attn_chunk_ragged(c, B, self.nheads, self.D, self.kv_len, R, scale)
-            h1 = self._proj(o, (wo,), residual=h)
-            xn2, _ = hip.rmsnorm_fwd(h1, ln2, self.eps)
-            gu = self._proj(xn2, (wg, wu))
-            h = self._proj(hip.swiglu_fwd(gu), (wd,), residual=h1)
-        hn, _ = hip.rmsnorm_fwd(h, self.model.norm.weight, self.eps)
-        self.h_out.copy_(hn)
+    def _attention(self, c, scale):
+        return hip.attn_chunk_ragged(c, self.B, self.nheads, self.D, self.kv_len, self.R, scale)
 
 
 # ================================================================================================ N action chunks for one observation
 # MLA.predict_action_diff_samples: N independent draws for ONE observation. Everything in front of the [t, x] tokens is the same in all
 # of them, so the encoders and the prefill run once (batch 1, S_p rows) and the cache holds ONE prefix followed by G groups of R suffix
-# rows: [S_p + G R, 3H] per layer. A pass is the batched engine's eight launches over the G R suffix rows, with the projection writing
-# group g's rows at S_p + g R + p (mla_gemm_suffix_bf16 with the "samples" overlapping: batch stride R rows, every slot S_p) and
-# mla_attn_chunk_groups as the attention. suffix_weights="fp8" swaps the four projections for mla_gemm_suffix_w8 over the model's FP8 copy
-# (_quantised); the prefill stays on the bf16 weights.
+# rows: [S_p + G R, 3H] per layer. The projection writes group g's rows at S_p + g R + p (the kernel's "samples" overlapping: batch
+# stride R rows, every slot S_p) and mla_attn_chunk_groups is the attention. The prefill stays on the bf16 weights in every mode.
 def plan_sample_groups(num_samples: int, R: int, max_rows: int = 256):
     """Pure host planning: the passes [(start, stop), ...] that serve samples [0, num_samples) in order, at most max_rows // R groups
     (R suffix rows each) per pass."""
@@ -798,29 +823,19 @@ def plan_sample_groups(num_samples: int, R: int, max_rows: int = 256):
     return [(start, min(start + per, num_samples)) for start in range(0, num_samples, per)]
 
 
-class SampleGroupsEps(_CachedEpsBase):
+class SampleGroupsEps(_RowGemmEps):
     """One engine per (splice position, action rows, group capacity, device): ONE cache per layer with the prefix rows and room for
     `capacity` groups, prefilled once per call; `set_groups(G)` selects how many groups the next `model(x [G, T, D], t [G])` calls serve
     (G <= capacity: the sub-batches of a call whose N exceeds a pass share the cache and the prefill) and one captured graph is kept per
     distinct G. Rows of groups >= G are neither written nor read by a pass of G groups."""
 
-    MAX_ROWS = 256                   # suffix rows per pass (mla_gemm_suffix_bf16 / mla_gemm_suffix_w8)
-    MAX_R = 64                       # rows per group (mla_attn_chunk_groups)
-
     @classmethod
     def supports_samples(cls, vlm, n_action_rows: int, warn: bool = True) -> bool:
         """head_dim 128 and at most 64 suffix rows per sample; otherwise the bf16 caller loops over batch-1 calls (warns once per shape;
         warn=False: the plain predicate, for the callers that raise instead)."""
-        cfg = vlm.llm_backbone.llm.config
-        R, D = 1 + n_action_rows, cfg.hidden_size // cfg.num_attention_heads
-        if R <= cls.MAX_R and D == 128:
-            return True
-        seen = vlm.__dict__.setdefault("_prefix_unsupported", set())
-        if warn and ("samples", R, D) not in seen:
-            seen.add(("samples", R, D))
-            warnings.warn(f"SampleGroupsEps: {R} suffix rows per sample (max {cls.MAX_R}) / head_dim {D} (needs 128) are beyond the "
-                          "shared-prefix kernels; drawing every sample with its own predict_action_diff call", RuntimeWarning, stacklevel=3)
-        return False
+        return cls._serves(vlm, 1 + n_action_rows, cls.MAX_R, ("samples",), "SampleGroupsEps: {rows} suffix rows per sample (max {limit}) / "
+                           "head_dim {D} (needs 128) are beyond the shared-prefix kernels; drawing every sample with its own "
+                           "predict_action_diff call", warn)
 
     @classmethod
     def for_inputs(cls, vlm, input_ids, n_action_rows: int, num_samples: int, suffix_weights: str = "bf16", prefill: str = "train",
@@ -832,17 +847,8 @@ class SampleGroupsEps(_CachedEpsBase):
         k = PrefixCachedEps._splice_position(input_ids)
         passes = plan_sample_groups(num_samples, 1 + n_action_rows, cls.MAX_ROWS)
         capacity = max(stop - start for start, stop in passes)
-        engines = vlm.__dict__.setdefault("_prefix_engines_samples", {})
-        key = (k, int(n_action_rows), capacity, str(input_ids.device))
-        if suffix_weights != "bf16":
-            key += (suffix_weights,)                                          # a captured graph holds the addresses of ITS weights
-        if prefill != "train":
-            key += ("prefill:" + prefill,)
-        eng = engines.get(key)
-        if eng is None:
-            if len(engines) >= 4:
-                engines.pop(next(iter(engines)))
-            eng = engines[key] = cls(vlm, n_action_rows, capacity, suffix_weights, prefill)
+        eng = cls._engine(vlm, "_prefix_engines_samples", (k, int(n_action_rows), capacity, str(input_ids.device)),
+                          (n_action_rows, capacity, suffix_weights, prefill), suffix_weights, prefill)
         eng.prefill(input_ids, k, **model_kwargs)
         return eng, passes
 
@@ -850,7 +856,7 @@ class SampleGroupsEps(_CachedEpsBase):
         super().__init__(vlm, n_action_rows, suffix_weights, prefill)
         self.capacity = int(capacity)
         self._graphs = {}            # G -> captured pass over G groups
-        self._graphs_packed = None   # the packed weights those graphs hold the addresses of
+        self._graphs_packed = None   # the weights those graphs hold the addresses of
 
     def set_groups(self, G: int):
         assert 1 <= G <= self.capacity and self.cache is not None
@@ -886,55 +892,19 @@ class SampleGroupsEps(_CachedEpsBase):
                 self._graphs.clear()
                 self._graphs_packed = self._suffix
                 self.graph = None
-            h = prefix.reshape(S_p, H)
-            if self.prefill_mode == "compact":
-                self._compact_prefill(h, 1, S_p, self.cache, 0)
-                return
-            for w, c in zip(weights, self.cache):
-                h, acts = ops.DecoderLayerFn._fwd(h, None, self.cos_p, self.sin_p, 1, S_p, self.nheads, self.eps, w)
-                c[:S_p].copy_(acts.qkv[:S_p])
-                del acts
+            self._prefill_rows(prefix.reshape(S_p, H), 1, S_p, 0, weights)
 
     def _run(self):
         super()._run()
         if self.graph is not None:
             self._graphs[self.B] = self.graph
 
-    def _proj(self, x, weights, out=None, residual=None, **kw):
-        """x [M, K] @ W^T (+ residual): `weights` is a tuple of adjacent bf16 views (mla_gemm_suffix_bf16) or one W8 (mla_gemm_suffix_w8)."""
-        if isinstance(weights, W8):
-            N, gemm = weights.q.shape[0], functools.partial(hip.gemm_suffix_w8, x, weights.q, weights.scale)
-        else:
-            wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
-            assert wcat is not None, "the packed weights are adjacent in memory (_weights)"
-            N, gemm = wcat.shape[0], functools.partial(hip.gemm_suffix, x, wcat)
-        M = x.shape[0]
-        if out is None:
-            out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-            gemm(out, out.stride(0), 0, M, residual)
-        else:                                                                # group g = "sample" g of the kernel: base row g R, slot S_p
-            gemm(out, out.stride(0), self.R * out.stride(0), self.R, residual, **kw)
-        return out
+    def _cache_write(self, c):
+        # group g = "sample" g of the kernel: base row g R, slot S_p; q|k|v row p of group g -> cache row S_p + g R + p, rotated at S_p + p
+        return c.stride(0), self.R * c.stride(0), {"slot": self.slot, "cap_rows": self.S_p + self.R, "rope": (self.cos_c, self.sin_c, 2 * self.H)}
 
-    def _suffix_pass(self):
-        G, R, H, S_p = self.B, self.R, self.H, self.S_p
-        h = self.h_in
-        scale = 1.0 / math.sqrt(self.D)
-        for w, c in zip(self._suffix, self.cache):
-            if self.suffix_weights == "fp8":                                 # _quantised: the packed q|k|v and gate|up as one W8 each
-                ln1, qkv, wo, ln2, gu_w, wd = w
-            else:                                                            # the packed 9-tuple ("bf16") or its dequantised twin
-                ln1, qkv, wo, ln2, gu_w, wd = w[0], w[1:4], w[4:5], w[5], w[6:8], w[8:9]
-            xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
-            # q|k|v row p of group g -> cache row S_p + g R + p, q and k rotated at position S_p + p in the epilogue
-            self._proj(xn, qkv, out=c, slot=self.slot, cap_rows=S_p + R, rope=(self.cos_c, self.sin_c, 2 * H))
-            o = hip.attn_chunk_groups(c, G, self.nheads, self.D, S_p, R, scale)
-            h1 = self._proj(o, wo, residual=h)
-            xn2, _ = hip.rmsnorm_fwd(h1, ln2, self.eps)
-            gu = self._proj(xn2, gu_w)
-            h = self._proj(hip.swiglu_fwd(gu), wd, residual=h1)
-        hn, _ = hip.rmsnorm_fwd(h, self.model.norm.weight, self.eps)
-        self.h_out.copy_(hn)
+    def _attention(self, c, scale):
+        return hip.attn_chunk_groups(c, self.B, self.nheads, self.D, self.S_p, self.R, scale)
 
 
 # ================================================================================================ N action chunks for each of B observations
@@ -987,32 +957,19 @@ def plan_batch_samples(ids_rows: Sequence[Sequence[int]], n_action_rows: int, n_
     return plans
 
 
-class BatchedSampleGroupsEps(_CachedEpsBase):
+class BatchedSampleGroupsEps(_RowGemmEps):
     """One engine -- and one captured graph -- per (observations NB, groups G, S_cap, R, device[, suffix_weights]) serves every mix of
     prompt lengths of a capacity bucket: `prefix_len` [NB], `slot` and `rope_pos` [NB * G] are device tensors the kernels read
-    (mla_attn_chunk_ragged_groups, mla_gemm_suffix_bf16_pos / mla_gemm_suffix_w8_pos), refreshed by copy_ in prefill(). The prefill is
-    BatchedPrefixCachedEps's (right-padded prefixes, one varlen pass per layer, bf16 weights whatever the mode); the suffix pass is the
-    batched engine's eight launches per layer over the NB * G * R rows, in the order (b, g, p). `model(x [NB * G, T, D], t [NB * G])`:
-    self.B = NB * G is the sampler's batch."""
-
-    MAX_ROWS = 256                   # suffix rows per pass (mla_gemm_suffix_bf16_pos / mla_gemm_suffix_w8_pos)
-    MAX_R = 64                       # rows per group (mla_attn_chunk_ragged_groups)
-    BUCKET = 64                      # cache capacity granularity in rows
+    (mla_attn_chunk_ragged_groups, mla_gemm_suffix_bf16_pos / mla_gemm_suffix_w8_pos), refreshed by copy_ in prefill(). The suffix pass
+    runs over the NB * G * R rows in the order (b, g, p). `model(x [NB * G, T, D], t [NB * G])`: self.B = NB * G is the sampler's batch."""
 
     @classmethod
     def supports_batch_samples(cls, vlm, n_action_rows: int, warn: bool = True) -> bool:
         """head_dim 128 and at most 64 suffix rows per group; otherwise the bf16 caller loops predict_action_diff_samples per observation
         (warns once per shape; warn=False: the plain predicate, for the callers that raise instead)."""
-        cfg = vlm.llm_backbone.llm.config
-        R, D = 1 + n_action_rows, cfg.hidden_size // cfg.num_attention_heads
-        if R <= cls.MAX_R and D == 128:
-            return True
-        seen = vlm.__dict__.setdefault("_prefix_unsupported", set())
-        if warn and ("batch_samples", R, D) not in seen:
-            seen.add(("batch_samples", R, D))
-            warnings.warn(f"BatchedSampleGroupsEps: {R} suffix rows per sample (max {cls.MAX_R}) / head_dim {D} (needs 128) are beyond the "
-                          "batched shared-prefix kernels; drawing every observation's samples with its own call", RuntimeWarning, stacklevel=3)
-        return False
+        return cls._serves(vlm, 1 + n_action_rows, cls.MAX_R, ("batch_samples",), "BatchedSampleGroupsEps: {rows} suffix rows per sample (max "
+                           "{limit}) / head_dim {D} (needs 128) are beyond the batched shared-prefix kernels; drawing every observation's "
+                           "samples with its own call", warn)
 
     @classmethod
     def fits_pass(cls, n_action_rows: int, num_samples: int) -> bool:
@@ -1026,95 +983,23 @@ class BatchedSampleGroupsEps(_CachedEpsBase):
         (SampleSubBatchPlan, prefilled engine) per sub-batch. Two sub-batches may share an engine: finish sampling one before taking the
         next."""
         check_suffix_weights(suffix_weights)
-        with torch.no_grad():
-            parts, _, _, _, _, _ = vlm.get_fused_tokens(images, point_cloud, None, None, camera_name)
-            vlm.vision_tower_2d.assert_masks_ok()
-            front = torch.cat(parts, dim=1)                                   # [B, n_front, H]
+        front = cls._front_tokens(vlm, images, point_cloud, camera_name)
         plans = plan_batch_samples(ids_rows, n_action_rows, int(front.shape[1]), num_samples, cls.MAX_ROWS, cls.BUCKET, add_tail=add_tail)
         if plans is None:
             raise ValueError(f"{num_samples} groups of {1 + n_action_rows} rows exceed the {cls.MAX_ROWS} rows of a pass (fits_pass)")
-        engines = vlm.__dict__.setdefault("_prefix_engines_batch_samples", {})
         for sub in plans:
-            key = (sub.stop - sub.start, sub.G, sub.S_cap, sub.R, str(front.device))
-            if suffix_weights != "bf16":
-                key += (suffix_weights,)                                      # a captured graph holds the addresses of ITS weights
-            eng = engines.get(key)
-            if eng is None:
-                if len(engines) >= 4:
-                    engines.pop(next(iter(engines)))
-                eng = engines[key] = cls(vlm, n_action_rows, suffix_weights)
+            eng = cls._engine(vlm, "_prefix_engines_batch_samples", (sub.stop - sub.start, sub.G, sub.S_cap, sub.R, str(front.device)),
+                              (n_action_rows, suffix_weights), suffix_weights)
             eng.prefill(sub, front[sub.start:sub.stop], proprio[sub.start:sub.stop])
             yield sub, eng
 
     def prefill(self, sub: SampleSubBatchPlan, front, proprio):
-        vlm, bf16, dev = self.vlm, torch.bfloat16, front.device
-        NB, G, S_pmax = sub.stop - sub.start, sub.G, sub.S_pmax
-        with torch.no_grad():
-            proprio_e = vlm.proprio_embedder(proprio.to(bf16))                # [NB, 1, H]
-            H = front.shape[2]
-            prefix = torch.zeros((NB, S_pmax, H), dtype=bf16, device=dev)
-            for b in range(NB):
-                e = vlm.llm_backbone.embed_input_ids(torch.tensor([sub.ids[b]], dtype=torch.long, device=dev))[0]
-                prefix[b, :sub.S_p[b]] = torch.cat([e[:1], front[b], e[1:sub.k[b]], proprio_e[b]], dim=0)
-            if self.cache is None:
-                self.NB, self.G, self.B, self.H, self.S_cap = NB, G, NB * G, H, sub.S_cap
-                self.D = H // self.nheads
-                self.rot = self.model.layers[0].self_attn.rotary_emb
-                self.cos_c, self.sin_c = self.rot.tables(self.S_cap, dev)    # the epilogue rotates row p of a group with table row rope_pos + p
-                rows = NB * G * self.R
-                with torch.inference_mode(False):                            # the engine outlives the (inference-mode) call that creates it
-                    self.cache = [torch.zeros((NB, self.S_cap, 3 * H), dtype=bf16, device=dev) for _ in self.model.layers]
-                    self.h_in = torch.zeros((rows, H), dtype=bf16, device=dev)
-                    self.h_out = torch.zeros((rows, H), dtype=bf16, device=dev)
-                    self.prefix_len = torch.zeros(NB, dtype=torch.int32, device=dev)
-                    self.slot = torch.zeros(NB * G, dtype=torch.int32, device=dev)
-                    self.rope_pos = torch.zeros(NB * G, dtype=torch.int32, device=dev)
-            assert (NB, G, H, sub.S_cap, sub.R) == (self.NB, self.G, self.H, self.S_cap, self.R) and S_pmax + G * self.R <= self.S_cap
-            self.prefix_len.copy_(torch.tensor(sub.prefix_len, dtype=torch.int32))
-            self.slot.copy_(torch.tensor(sub.slot, dtype=torch.int32))
-            self.rope_pos.copy_(torch.tensor(sub.rope_pos, dtype=torch.int32))
-            seqlens = torch.tensor(sub.S_p, dtype=torch.int32, device=dev)
-            cos_p, sin_p = self.rot.tables(S_pmax, dev)
-            h = prefix.reshape(NB * S_pmax, H)
-            for w, c in zip(self._weights(), self.cache):                    # the bf16 weights, whatever the suffix pass streams
-                h, acts = ops.DecoderLayerFn._fwd(h, seqlens, cos_p, sin_p, NB, S_pmax, self.nheads, self.eps, w)
-                c[:, :S_pmax].copy_(acts.qkv[:NB * S_pmax].view(NB, S_pmax, 3 * H))
-                del acts
+        self._varlen_prefill(sub, front, proprio, sub.G, {"prefix_len": sub.prefix_len, "slot": sub.slot, "rope_pos": sub.rope_pos})
 
-    def _proj(self, x, weights, out=None, residual=None, **kw):
-        """x [M, K] @ W^T (+ residual): `weights` is a tuple of adjacent bf16 views (mla_gemm_suffix_bf16) or one W8 (mla_gemm_suffix_w8);
-        out = a layer's cache: the q|k|v rows go to their groups' slots (the `_pos` entry points)."""
-        if isinstance(weights, W8):
-            N, gemm = weights.q.shape[0], functools.partial(hip.gemm_suffix_w8, x, weights.q, weights.scale)
-        else:
-            wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
-            assert wcat is not None, "the packed weights are adjacent in memory (_weights)"
-            N, gemm = wcat.shape[0], functools.partial(hip.gemm_suffix, x, wcat)
-        M = x.shape[0]
-        if out is None:
-            out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-            gemm(out, out.stride(0), 0, M, residual)
-        else:                                                                # flat [NB * S_cap, 3H] cache: slot holds the sample's base row
-            gemm(out, out.stride(-2), 0, self.R, residual, **kw)
-        return out
+    def _cache_write(self, c):
+        # flat [NB * S_cap, 3H] cache: q|k|v row p of group (b, g) -> row slot = b S_cap + S_p[b] + g R + p, rotated at position S_p[b] + p
+        return c.stride(-2), 0, {"slot": self.slot, "cap_rows": self.NB * self.S_cap, "rope": (self.cos_c, self.sin_c, 2 * self.H),
+                                 "rope_pos": self.rope_pos, "rope_rows": self.S_cap}
 
-    def _suffix_pass(self):
-        NB, G, R, H = self.NB, self.G, self.R, self.H
-        h = self.h_in
-        scale = 1.0 / math.sqrt(self.D)
-        for w, c in zip(self._suffix, self.cache):
-            if self.suffix_weights == "fp8":                                 # _quantised: the packed q|k|v and gate|up as one W8 each
-                ln1, qkv, wo, ln2, gu_w, wd = w
-            else:                                                            # the packed 9-tuple ("bf16") or its dequantised twin
-                ln1, qkv, wo, ln2, gu_w, wd = w[0], w[1:4], w[4:5], w[5], w[6:8], w[8:9]
-            xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
-            # q|k|v row p of group (b, g) -> cache row slot = b S_cap + S_p[b] + g R + p, q and k rotated at position S_p[b] + p
-            self._proj(xn, qkv, out=c, slot=self.slot, cap_rows=NB * self.S_cap, rope=(self.cos_c, self.sin_c, 2 * H),
-                       rope_pos=self.rope_pos, rope_rows=self.S_cap)
-            o = hip.attn_chunk_ragged_groups(c, NB, G, self.nheads, self.D, self.prefix_len, R, scale)
-            h1 = self._proj(o, wo, residual=h)
-            xn2, _ = hip.rmsnorm_fwd(h1, ln2, self.eps)
-            gu = self._proj(xn2, gu_w)
-            h = self._proj(hip.swiglu_fwd(gu), wd, residual=h1)
-        hn, _ = hip.rmsnorm_fwd(h, self.model.norm.weight, self.eps)
-        self.h_out.copy_(hn)
+    def _attention(self, c, scale):
+        return hip.attn_chunk_ragged_groups(c, self.NB, self.G, self.nheads, self.D, self.prefix_len, self.R, scale)

@@ -295,9 +295,10 @@ class MLA(nn.Module):
 
     @staticmethod
     def _ids_with_tail(input_ids, device):
+        from .infer import PROMPT_TAIL, SPLICE_TAG
         input_ids = input_ids.to(device)
-        if not bool(torch.all(input_ids[:, -1] == 29871)):
-            tail = torch.tensor([[29871, 32001, 32002, 29871]], dtype=torch.long, device=device)
+        if not bool(torch.all(input_ids[:, -1] == SPLICE_TAG)):
+            tail = torch.tensor([PROMPT_TAIL], dtype=torch.long, device=device)
             input_ids = torch.cat((input_ids, tail), dim=1)[:, :-3]
         return input_ids
 
@@ -325,6 +326,69 @@ class MLA(nn.Module):
             raise ValueError("cur_robot_state is required: the proprio token is always spliced in (prismatic.py:985-990)")
         st = self.normalize_proprio(np.asarray(cur_robot_state), unnorm_key) if self.norm_stats is not None else np.asarray(cur_robot_state)
         return torch.tensor(st, dtype=torch.float32).reshape(1, 1, -1).to(device)
+
+    # ---- what the four sampling entry points share (called as MLA._check_modes: the mode errors come before `self` is touched)
+    @staticmethod
+    def _check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps):
+        from .infer import check_prefill, check_sampler, check_suffix_attention, check_suffix_weights
+        check_suffix_weights(suffix_weights)
+        check_prefill(prefill)
+        check_sampler(sampler, reuse_prefix, use_ddim, num_ddim_steps)
+        check_suffix_attention(suffix_attention, reuse_prefix)
+
+    def _draw_x0(self, given, T, action_dim, device):
+        """The initial samples [len(given), T, action_dim] fp32 and the RNG draws of one predict_action_diff call per chunk, in call order
+        (:707-708): randn(1, T, D) unless the chunk's noise row [1, T, D] is given, then the unused randint."""
+        draws = []
+        for noise in given:
+            draws.append(torch.randn(1, T, action_dim, device=device) if noise is None else noise.to(device))
+            _ = torch.randint(0, self.diffusion.num_timesteps, (T,), device=device)
+        return torch.cat(draws, dim=0).float()
+
+    def _sample(self, eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs):
+        """x0 [B, T, D] -> samples: the DDIM loop (eta = 0) on the device (an engine's sample_ddim) or on the host, or the DDPM loop."""
+        device = x0.device
+        if use_ddim and num_ddim_steps is not None:
+            if self.ddim_diffusion is None:
+                self.create_ddim(ddim_step=num_ddim_steps)
+            if sampler == "device":
+                return eps_model.sample_ddim(x0, self.ddim_diffusion)
+            return self.ddim_diffusion.ddim_sample_loop(eps_model, x0.shape, x0, clip_denoised=False, model_kwargs=model_kwargs,
+                                                        progress=False, device=device, eta=0.0)
+        return self.diffusion.p_sample_loop(eps_model, x0.shape, x0, clip_denoised=False, model_kwargs=model_kwargs, progress=False,
+                                            device=device)
+
+    def _actions(self, chunks, unnorm_key):
+        """The sampled chunks of a call, in order (numpy, stacked on axis 0) -> un-normalised actions."""
+        normalized = np.concatenate(chunks, axis=0)
+        return self.unnormalize_actions(normalized, unnorm_key) if self.norm_stats is not None else normalized
+
+    def _batch_prompts(self, B, instructions, input_ids, pointclouds, cur_robot_states):
+        """The argument checks of a batched call -> (input_ids, pointclouds), one entry per observation each. Called as
+        MLA._batch_prompts(self, ...): the host tests reach these errors with a stand-in `self` that has no methods of its own."""
+        if input_ids is None:
+            if instructions is None or len(instructions) != B:
+                raise ValueError("predict_action_diff_batch needs `input_ids` (one tensor per sample), or B `instructions` plus a callable "
+                                 "vlm.llm_backbone.tokenizer")
+            input_ids = [self._prompt_ids(ins, "predict_action_diff_batch") for ins in instructions]
+        if pointclouds is None:
+            pointclouds = [None] * B
+        if not (len(input_ids) == B and len(pointclouds) == B and cur_robot_states is not None and len(cur_robot_states) == B):
+            raise ValueError("predict_action_diff_batch: images, pointclouds, cur_robot_states and input_ids / instructions need one entry per sample")
+        return input_ids, pointclouds
+
+    def _batch_inputs(self, images, pointclouds, cur_robot_states, ids_rows, unnorm_key, camera_name):
+        """B observations stacked for an engine's for_batch -> (device, prompt id lists, its keyword arguments). Every per-sample step is
+        predict_action_diff's; the prompt tail per row is infer.plan_batch's (:640-645)."""
+        self.vlm.eval()
+        device = next(self.vlm.parameters()).device
+        pre = [self._preprocessed_image(im) for im in images]
+        ids_rows = [ids.reshape(-1).tolist() for ids in ids_rows]
+        img = torch.cat([self._image_batch(im, device) for im in pre], dim=0)
+        pcs = [self._pointcloud_batch(pc, device) for pc in pointclouds]
+        pc = None if any(p is None for p in pcs) else torch.cat(pcs, dim=0)
+        proprio = torch.cat([self._proprio_token(st, unnorm_key, device) for st in cur_robot_states], dim=0)
+        return device, ids_rows, {"images": img, "point_cloud": pc, "camera_name": camera_name, "proprio": proprio}
 
     @torch.inference_mode()
     def predict_action_diff(self, image=None, pointcloud=None, instruction: Optional[str] = None, cur_robot_state=None,
@@ -365,15 +429,12 @@ class MLA(nn.Module):
         softmax states in a fixed order with a second launch (mla_attn_chunk_split with the library's plan): the same function up to
         summation order. It composes with every ``suffix_weights``, ``prefill`` and ``sampler`` mode; it raises ValueError for an unknown
         value, and for "split" when ``reuse_prefix=False`` or the cached-prefix engine does not serve the shape: no silent fallback."""
-        from .infer import (check_prefill, check_sampler, check_suffix_attention, check_suffix_weights, sampler_needs_engine,
-                            suffix_attention_needs_engine)
-        check_suffix_weights(suffix_weights)
-        check_prefill(prefill)
-        check_sampler(sampler, reuse_prefix, use_ddim, num_ddim_steps)
-        check_suffix_attention(suffix_attention, reuse_prefix)
+        from .infer import PrefixCachedEps, sampler_needs_engine, suffix_attention_needs_engine
+        MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps)
         if prefill != "train" and not reuse_prefix:
             raise ValueError(f"prefill={prefill!r} needs the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has no "
                              "separate prefill")
+        T = self.future_action_window_size + 1
         self.vlm.eval()
         device = next(self.vlm.parameters()).device
         if input_ids is None:
@@ -385,13 +446,10 @@ class MLA(nn.Module):
         pointcloud = self._pointcloud_batch(pointcloud, device)
         model_kwargs = {"input_ids": input_ids, "images": img, "point_cloud": pointcloud, "camera_name": camera_name}
         model_kwargs["proprio"] = self._proprio_token(cur_robot_state, unnorm_key, device)
-        if noise is None:
-            noise = torch.randn(1, self.future_action_window_size + 1, action_dim, device=device)
-        _ = torch.randint(0, self.diffusion.num_timesteps, (self.future_action_window_size + 1,), device=device)  # drawn, unused (:708)
+        x0 = self._draw_x0([noise], T, action_dim, device)
         eps_model = self.vlm.forward
         if reuse_prefix:
-            from .infer import PrefixCachedEps
-            reuse_prefix = PrefixCachedEps.supports(self.vlm, int(input_ids.shape[0]), self.future_action_window_size + 1)
+            reuse_prefix = PrefixCachedEps.supports(self.vlm, int(input_ids.shape[0]), T)
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached-prefix engine (reuse_prefix=True and a shape "
                              "PrefixCachedEps.supports); the whole-forward sampler has bf16 weights only")
@@ -399,25 +457,13 @@ class MLA(nn.Module):
             raise ValueError(f"prefill={prefill!r}: the cached-prefix engine does not serve this shape (PrefixCachedEps.supports: at most "
                              "64 suffix rows, head_dim 128); use prefill=\"train\"")
         if not reuse_prefix:
-            sampler_needs_engine(sampler, "PrefixCachedEps", self.future_action_window_size + 1)
-            suffix_attention_needs_engine(suffix_attention, self.future_action_window_size + 1)
+            sampler_needs_engine(sampler, "PrefixCachedEps", T)
+            suffix_attention_needs_engine(suffix_attention, T)
         if reuse_prefix:
-            eps_model = PrefixCachedEps.for_inputs(self.vlm, n_action_rows=self.future_action_window_size + 1,
-                                                   suffix_weights=suffix_weights, prefill=prefill, suffix_attention=suffix_attention,
-                                                   **model_kwargs)
-        if use_ddim and num_ddim_steps is not None:
-            if self.ddim_diffusion is None:
-                self.create_ddim(ddim_step=num_ddim_steps)
-            if sampler == "device":
-                samples = eps_model.sample_ddim(noise.to(device).float(), self.ddim_diffusion)
-            else:
-                samples = self.ddim_diffusion.ddim_sample_loop(eps_model, noise.shape, noise.to(device).float(), clip_denoised=False,
-                                                               model_kwargs=model_kwargs, progress=False, device=device, eta=0.0)
-        else:
-            samples = self.diffusion.p_sample_loop(eps_model, noise.shape, noise.to(device).float(), clip_denoised=False,
-                                                   model_kwargs=model_kwargs, progress=False, device=device)
-        normalized = samples[0].float().cpu().numpy()
-        return self.unnormalize_actions(normalized, unnorm_key) if self.norm_stats is not None else normalized
+            eps_model = PrefixCachedEps.for_inputs(self.vlm, n_action_rows=T, suffix_weights=suffix_weights, prefill=prefill,
+                                                   suffix_attention=suffix_attention, **model_kwargs)
+        samples = self._sample(eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs)
+        return self._actions([samples[:1].float().cpu().numpy()], unnorm_key)[0]
 
     @torch.inference_mode()
     def predict_action_diff_batch(self, images, pointclouds, instructions=None, cur_robot_states=None, unnorm_key: Optional[str] = None,
@@ -452,12 +498,8 @@ class MLA(nn.Module):
         does not serve) or run the DDPM sampler.
         ``suffix_attention``: predict_action_diff's, forwarded for B = 1; B >= 2 with "split" raises NotImplementedError (the ragged and
         groups engines keep their own attention launches)."""
-        from .infer import (check_prefill, check_sampler, check_suffix_attention, check_suffix_weights, sampler_needs_engine,
-                            suffix_attention_single_only)
-        check_suffix_weights(suffix_weights)
-        check_prefill(prefill)
-        check_sampler(sampler, reuse_prefix, use_ddim, num_ddim_steps)
-        check_suffix_attention(suffix_attention, reuse_prefix)
+        from .infer import BatchedPrefixCachedEps, sampler_needs_engine, suffix_attention_single_only
+        MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps)
         if prefill != "train":
             raise NotImplementedError(f"prefill={prefill!r}: the batched engines prefill B x S rows on the training GEMMs; the compact "
                                       "prefill serves one observation (predict_action_diff, predict_action_diff_samples)")
@@ -469,15 +511,7 @@ class MLA(nn.Module):
             return self._predict_action_diff_batch_samples(images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix,
                                                            suffix_weights, num_samples, sampler, suffix_attention)
-        if input_ids is None:
-            if instructions is None or len(instructions) != B:
-                raise ValueError("predict_action_diff_batch needs `input_ids` (one tensor per sample), or B `instructions` plus a callable "
-                                 "vlm.llm_backbone.tokenizer")
-            input_ids = [self._prompt_ids(ins, "predict_action_diff_batch") for ins in instructions]
-        if pointclouds is None:
-            pointclouds = [None] * B
-        if not (len(input_ids) == B and len(pointclouds) == B and cur_robot_states is not None and len(cur_robot_states) == B):
-            raise ValueError("predict_action_diff_batch: images, pointclouds, cur_robot_states and input_ids / instructions need one entry per sample")
+        input_ids, pointclouds = MLA._batch_prompts(self, B, instructions, input_ids, pointclouds, cur_robot_states)
         if noise is not None and tuple(noise.shape[:2]) != (B, T):
             raise ValueError(f"noise must be [B, T, action_dim] = [{B}, {T}, ...], got {tuple(noise.shape)}")
         self._check_cfg_scale(cfg_scale)
@@ -494,40 +528,17 @@ class MLA(nn.Module):
                                       "streams bf16 weights only; sample B >= 2 observations with \"bf16\", one at a time, or pass "
                                       "`num_samples` (BatchedSampleGroupsEps serves every mode)")
         if reuse_prefix:
-            from .infer import BatchedPrefixCachedEps
             reuse_prefix = BatchedPrefixCachedEps.supports_batch(self.vlm, T)
         if not reuse_prefix:
             sampler_needs_engine(sampler, "BatchedPrefixCachedEps", T)
             return np.stack([one(b, reuse_prefix=False) for b in range(B)])
-        self.vlm.eval()
-        device = next(self.vlm.parameters()).device
-        pre = [self._preprocessed_image(im) for im in images]
-        ids_rows = [ids.reshape(-1).tolist() for ids in ids_rows]             # the prompt tail per row: infer.plan_batch (:640-645)
-        img = torch.cat([self._image_batch(im, device) for im in pre], dim=0)
-        pcs = [self._pointcloud_batch(pc, device) for pc in pointclouds]
-        pc = None if any(p is None for p in pcs) else torch.cat(pcs, dim=0)
-        proprio = torch.cat([self._proprio_token(st, unnorm_key, device) for st in cur_robot_states], dim=0)
-        draws = []
-        for b in range(B):                                                   # the RNG draws of B calls, in their order (:707-708)
-            draws.append(torch.randn(1, T, action_dim, device=device) if noise is None else noise[b:b + 1].to(device))
-            _ = torch.randint(0, self.diffusion.num_timesteps, (T,), device=device)
-        x0 = torch.cat(draws, dim=0).float()
-        if use_ddim and num_ddim_steps is not None and self.ddim_diffusion is None:
-            self.create_ddim(ddim_step=num_ddim_steps)
+        device, ids_rows, inputs = self._batch_inputs(images, pointclouds, cur_robot_states, ids_rows, unnorm_key, camera_name)
+        x0 = self._draw_x0([None if noise is None else noise[b:b + 1] for b in range(B)], T, action_dim, device)
         out = []
-        for sub, eng in BatchedPrefixCachedEps.for_batch(self.vlm, ids_rows, T, images=img, point_cloud=pc, camera_name=camera_name,
-                                                         proprio=proprio):
-            xs = x0[sub.start:sub.stop].contiguous()
-            if sampler == "device":
-                samples = eng.sample_ddim(xs, self.ddim_diffusion)
-            elif use_ddim and num_ddim_steps is not None:
-                samples = self.ddim_diffusion.ddim_sample_loop(eng, xs.shape, xs, clip_denoised=False, model_kwargs={}, progress=False,
-                                                               device=device, eta=0.0)
-            else:
-                samples = self.diffusion.p_sample_loop(eng, xs.shape, xs, clip_denoised=False, model_kwargs={}, progress=False, device=device)
+        for sub, eng in BatchedPrefixCachedEps.for_batch(self.vlm, ids_rows, T, **inputs):
+            samples = self._sample(eng, x0[sub.start:sub.stop].contiguous(), sampler, use_ddim, num_ddim_steps, {})
             out.append(samples.float().cpu().numpy())
-        normalized = np.concatenate(out, axis=0)
-        return self.unnormalize_actions(normalized, unnorm_key) if self.norm_stats is not None else normalized
+        return self._actions(out, unnorm_key)
 
     def _predict_action_diff_batch_samples(self, images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix, suffix_weights, num_samples,
@@ -536,15 +547,7 @@ class MLA(nn.Module):
         B, N, T = len(images), int(num_samples), self.future_action_window_size + 1
         if N < 1:
             raise ValueError(f"num_samples must be >= 1, got {num_samples}")
-        if input_ids is None:
-            if instructions is None or len(instructions) != B:
-                raise ValueError("predict_action_diff_batch needs `input_ids` (one tensor per sample), or B `instructions` plus a callable "
-                                 "vlm.llm_backbone.tokenizer")
-            input_ids = [self._prompt_ids(ins, "predict_action_diff_batch") for ins in instructions]
-        if pointclouds is None:
-            pointclouds = [None] * B
-        if not (len(input_ids) == B and len(pointclouds) == B and cur_robot_states is not None and len(cur_robot_states) == B):
-            raise ValueError("predict_action_diff_batch: images, pointclouds, cur_robot_states and input_ids / instructions need one entry per sample")
+        input_ids, pointclouds = MLA._batch_prompts(self, B, instructions, input_ids, pointclouds, cur_robot_states)
         if noise is not None and tuple(noise.shape) != (B, N, T, action_dim):
             raise ValueError(f"noise must be [B, N, T, action_dim] = [{B}, {N}, {T}, {action_dim}], got {tuple(noise.shape)}")
         self._check_cfg_scale(cfg_scale)
@@ -572,36 +575,13 @@ class MLA(nn.Module):
                 return np.stack([samples_of(b, suffix_weights=suffix_weights, sampler=sampler) for b in range(B)])
         else:
             return np.stack([samples_of(b, reuse_prefix=False) for b in range(B)])
-        self.vlm.eval()
-        device = next(self.vlm.parameters()).device
-        pre = [self._preprocessed_image(im) for im in images]
-        ids_rows = [ids.reshape(-1).tolist() for ids in ids_rows]             # the prompt tail per row: infer.plan_batch (:640-645)
-        img = torch.cat([self._image_batch(im, device) for im in pre], dim=0)
-        pcs = [self._pointcloud_batch(pc, device) for pc in pointclouds]
-        pc = None if any(p is None for p in pcs) else torch.cat(pcs, dim=0)
-        proprio = torch.cat([self._proprio_token(st, unnorm_key, device) for st in cur_robot_states], dim=0)
-        draws = []
-        for b in range(B):                                                   # the RNG draws of B calls of N samples, in their order (:707-708)
-            for n in range(N):
-                draws.append(torch.randn(1, T, action_dim, device=device) if noise is None else noise[b, n:n + 1].to(device))
-                _ = torch.randint(0, self.diffusion.num_timesteps, (T,), device=device)
-        x0 = torch.cat(draws, dim=0).float()                                 # [B * N, T, D], rows (b, n)
-        if use_ddim and num_ddim_steps is not None and self.ddim_diffusion is None:
-            self.create_ddim(ddim_step=num_ddim_steps)
+        device, ids_rows, inputs = self._batch_inputs(images, pointclouds, cur_robot_states, ids_rows, unnorm_key, camera_name)
+        x0 = self._draw_x0([None if noise is None else noise[b, n:n + 1] for b in range(B) for n in range(N)], T, action_dim, device)   # rows (b, n)
         out = []
-        for sub, eng in BatchedSampleGroupsEps.for_batch(self.vlm, ids_rows, T, N, suffix_weights, images=img, point_cloud=pc,
-                                                         camera_name=camera_name, proprio=proprio):
-            xs = x0[sub.start * N:sub.stop * N].contiguous()
-            if sampler == "device":
-                samples = eng.sample_ddim(xs, self.ddim_diffusion)
-            elif use_ddim and num_ddim_steps is not None:
-                samples = self.ddim_diffusion.ddim_sample_loop(eng, xs.shape, xs, clip_denoised=False, model_kwargs={}, progress=False,
-                                                               device=device, eta=0.0)
-            else:
-                samples = self.diffusion.p_sample_loop(eng, xs.shape, xs, clip_denoised=False, model_kwargs={}, progress=False, device=device)
+        for sub, eng in BatchedSampleGroupsEps.for_batch(self.vlm, ids_rows, T, N, suffix_weights, **inputs):
+            samples = self._sample(eng, x0[sub.start * N:sub.stop * N].contiguous(), sampler, use_ddim, num_ddim_steps, {})
             out.append(samples.float().cpu().numpy().reshape(sub.stop - sub.start, N, T, -1))
-        normalized = np.concatenate(out, axis=0)
-        return self.unnormalize_actions(normalized, unnorm_key) if self.norm_stats is not None else normalized
+        return self._actions(out, unnorm_key)
 
     @torch.inference_mode()
     def predict_action_diff_samples(self, image=None, pointcloud=None, instruction: Optional[str] = None, cur_robot_state=None,
@@ -631,12 +611,8 @@ class MLA(nn.Module):
         ``use_ddim=False`` or ``num_ddim_steps=None``.
         ``suffix_attention``: predict_action_diff's, forwarded for ``num_samples=1``; more samples with "split" raise NotImplementedError
         (the groups engine keeps mla_attn_chunk_groups)."""
-        from .infer import (check_prefill, check_sampler, check_suffix_attention, check_suffix_weights, sampler_needs_engine,
-                            suffix_attention_single_only)
-        check_suffix_weights(suffix_weights)
-        check_prefill(prefill)
-        check_sampler(sampler, reuse_prefix, use_ddim, num_ddim_steps)
-        check_suffix_attention(suffix_attention, reuse_prefix)
+        from .infer import SampleGroupsEps, sampler_needs_engine, suffix_attention_single_only
+        MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps)
         if int(num_samples) != 1:
             suffix_attention_single_only(suffix_attention, f"predict_action_diff_samples with num_samples={num_samples}")
         if prefill != "train" and not reuse_prefix:
@@ -661,7 +637,6 @@ class MLA(nn.Module):
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
                              "bf16 weights only")
         if reuse_prefix:
-            from .infer import SampleGroupsEps
             if not SampleGroupsEps.supports_samples(self.vlm, T, warn=False):
                 sampler_needs_engine(sampler, "SampleGroupsEps", T)
             if prefill != "train" and not SampleGroupsEps.supports_samples(self.vlm, T, warn=False):
@@ -682,25 +657,11 @@ class MLA(nn.Module):
         input_ids = self._ids_with_tail(input_ids, device)
         model_kwargs = {"images": self._image_batch(image, device), "point_cloud": self._pointcloud_batch(pointcloud, device),
                         "camera_name": camera_name, "proprio": self._proprio_token(cur_robot_state, unnorm_key, device)}
-        draws = []
-        for n in range(N):                                                   # the RNG draws of N calls, in their order (:707-708)
-            draws.append(torch.randn(1, T, action_dim, device=device) if noise is None else noise[n:n + 1].to(device))
-            _ = torch.randint(0, self.diffusion.num_timesteps, (T,), device=device)
-        x0 = torch.cat(draws, dim=0).float()
-        if use_ddim and num_ddim_steps is not None and self.ddim_diffusion is None:
-            self.create_ddim(ddim_step=num_ddim_steps)
+        x0 = self._draw_x0([None if noise is None else noise[n:n + 1] for n in range(N)], T, action_dim, device)
         eng, passes = SampleGroupsEps.for_inputs(self.vlm, input_ids, T, N, suffix_weights=suffix_weights, prefill=prefill, **model_kwargs)
         out = []
         for start, stop in passes:                                           # one prefill, then the passes' sampler loops one after the other
             eng.set_groups(stop - start)
-            xs = x0[start:stop].contiguous()
-            if sampler == "device":
-                samples = eng.sample_ddim(xs, self.ddim_diffusion)
-            elif use_ddim and num_ddim_steps is not None:
-                samples = self.ddim_diffusion.ddim_sample_loop(eng, xs.shape, xs, clip_denoised=False, model_kwargs={}, progress=False,
-                                                               device=device, eta=0.0)
-            else:
-                samples = self.diffusion.p_sample_loop(eng, xs.shape, xs, clip_denoised=False, model_kwargs={}, progress=False, device=device)
+            samples = self._sample(eng, x0[start:stop].contiguous(), sampler, use_ddim, num_ddim_steps, {})
             out.append(samples.float().cpu().numpy())
-        normalized = np.concatenate(out, axis=0)
-        return self.unnormalize_actions(normalized, unnorm_key) if self.norm_stats is not None else normalized
+        return self._actions(out, unnorm_key)

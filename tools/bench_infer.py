@@ -64,6 +64,62 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def _setup(args_or_chunk=None, B=1, model=None):
+    """-> (model, synthetic batch of B observations, prompt ids): MLA-Llama2-7B with random weights cast to bf16 (built once: pass it back
+    as `model` for further batches), future_action_window_size = chunk - 1 when a chunk (or the parsed arguments) is given. B = 1: ids
+    [1, L] = the synthetic prompt + the tag the splice looks for; B > 1: a list of B ragged prompts, 0 .. 12 ids shorter each (fixed seed)."""
+    from bench import build
+    from mla_amd.infer import SPLICE_TAG
+    from mla_amd.synthetic import make_batch
+    dev = torch.device("cuda", 0)
+    m = model
+    if m is None:
+        torch.manual_seed(0)
+        m = build(dev, 1)
+        m.eval()
+        for p in m.parameters():
+            p.data = p.data.to(torch.bfloat16)
+    chunk = getattr(args_or_chunk, "chunk", args_or_chunk)
+    if chunk is not None:
+        m.future_action_window_size = m.vlm.future_action_window_size = chunk - 1
+    b = make_batch(B=B, device=dev)
+    if B == 1:
+        return m, b, torch.cat([b["input_ids"][:, :-4], torch.tensor([[SPLICE_TAG]], device=dev)], dim=1)
+    drop = torch.randint(0, 13, (B,), generator=torch.Generator().manual_seed(1234)).tolist()
+    return m, b, [torch.cat([b["input_ids"][i, :b["input_ids"].shape[1] - 4 - drop[i]], torch.tensor([SPLICE_TAG], device=dev)]) for i in range(B)]
+
+
+def _observation(b, i=0):
+    """Observation i of the synthetic batch as predict_action_diff takes it: (image, pointcloud, cur_robot_state)."""
+    return b["images"]["front_image"][i], b["point_cloud"][i], b["proprio"][i, 0].cpu().numpy()
+
+
+def _engine_kw(b):
+    """Observation 0 as an engine's for_inputs / prefill takes it."""
+    return dict(images=b["images"]["front_image"][:1], point_cloud=b["point_cloud"][:1], camera_name="rlbench_front", proprio=b["proprio"][:1])
+
+
+def _time_ms(fn, iters):
+    """Host clock around `iters` calls between two device synchronisations -> ms per call."""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters * 1e3
+
+
+def _replay_ms(eng, n=8):
+    """Device events around n runs of the engine's (captured) suffix pass -> ms per pass."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        eng._run()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=8)
@@ -99,49 +155,30 @@ def main():
         return main_pair_prefill(args)
     if args.pair_fp8:
         return main_pair(args)
-    from bench import build
-    from mla_amd.synthetic import make_batch
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(0)
-    m = build(dev, 1)
-    m.future_action_window_size = m.vlm.future_action_window_size = args.chunk - 1
-    m.eval()
-    for p in m.parameters():
-        p.data = p.data.to(torch.bfloat16)
-    b = make_batch(B=1, device=dev)
-    ids = torch.cat([b["input_ids"][:, :-4], torch.tensor([[29871]], device=dev)], dim=1)   # prompt + the '▁' tag the splice looks for
-    kw = dict(image=b["images"]["front_image"][0], pointcloud=b["point_cloud"][0], cur_robot_state=b["proprio"][0, 0].cpu().numpy(),
-              input_ids=ids, num_ddim_steps=args.steps, reuse_prefix=not args.no_reuse_prefix, suffix_weights=args.suffix_weights)
-    m.predict_action_diff(**kw)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.iters):
-        act = m.predict_action_diff(**kw)
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) / args.iters * 1e3
+    m, b, ids = _setup(args)
+    dev = ids.device
+    image, pc, state = _observation(b)
+    kw = dict(image=image, pointcloud=pc, cur_robot_state=state, input_ids=ids, num_ddim_steps=args.steps,
+              reuse_prefix=not args.no_reuse_prefix, suffix_weights=args.suffix_weights)
+    act = m.predict_action_diff(**kw)
+    ms = _time_ms(lambda: m.predict_action_diff(**kw), args.iters)
     parts = {}
     if not args.no_reuse_prefix:
         # where the cached path's time goes: the prefill (encoders + one 545-row pass) and one graph replay over the suffix rows
         from mla_amd.infer import PrefixCachedEps
-        mk = dict(input_ids=ids, images=b["images"]["front_image"][:1], point_cloud=b["point_cloud"][:1], camera_name="rlbench_front",
-                  proprio=b["proprio"][:1])
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
-        eng = PrefixCachedEps.for_inputs(m.vlm, n_action_rows=args.chunk, suffix_weights=args.suffix_weights, **mk)
+        eng = PrefixCachedEps.for_inputs(m.vlm, ids, n_action_rows=args.chunk, suffix_weights=args.suffix_weights, **_engine_kw(b))
         ev[1].record()
         x = torch.randn(1, args.chunk, 7, device=dev)
         t = torch.tensor([91], device=dev)
         eng(x, t)
         ev[2].record()
-        for _ in range(8):
-            eng._run()
-        ev[3].record()
-        torch.cuda.synchronize()
+        pass_ms = _replay_ms(eng)
         wbytes = _stream_bytes(m, args.suffix_weights)
         parts = {"prefill_ms": round(ev[0].elapsed_time(ev[1]), 2), "one_eps_call_ms": round(ev[1].elapsed_time(ev[2]), 2),
-                 "suffix_pass_graph_replay_ms": round(ev[2].elapsed_time(ev[3]) / 8, 3),
-                 "weights_streamed_per_pass_gb": round(wbytes / 1e9, 2),
-                 "suffix_pass_weight_stream_tbps": round(wbytes / 1e12 / (ev[2].elapsed_time(ev[3]) / 8 * 1e-3), 2)}
+                 "suffix_pass_graph_replay_ms": round(pass_ms, 3), "weights_streamed_per_pass_gb": round(wbytes / 1e9, 2),
+                 "suffix_pass_weight_stream_tbps": round(wbytes / 1e12 / (pass_ms * 1e-3), 2)}
     print(json.dumps({"metric": "predict_action_diff latency, MLA-Llama2-7B bf16, batch 1", "suffix_weights": args.suffix_weights,
                       "value": round(ms, 1), "unit": "ms",
                       "ddim_steps": args.steps, "ms_per_ddim_step": round(ms / args.steps, 1), "seq_len": int(ids.shape[1]) + 513 + 2 + args.chunk,
@@ -171,47 +208,26 @@ def _pair_stats(a, b):
 
 
 def main_pair(args):
-    from bench import build
     from mla_amd import hip
     from mla_amd.infer import PrefixCachedEps
-    from mla_amd.synthetic import make_batch
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(0)
-    m = build(dev, 1)
-    m.future_action_window_size = m.vlm.future_action_window_size = args.chunk - 1
-    m.eval()
-    for p in m.parameters():
-        p.data = p.data.to(torch.bfloat16)
-    b = make_batch(B=1, device=dev)
-    ids = torch.cat([b["input_ids"][:, :-4], torch.tensor([[29871]], device=dev)], dim=1)
+    m, b, ids = _setup(args)
+    dev = ids.device
     noise = torch.randn(1, args.chunk, 7, device=dev)
-    kw = dict(image=b["images"]["front_image"][0], pointcloud=b["point_cloud"][0], cur_robot_state=b["proprio"][0, 0].cpu().numpy(),
-              input_ids=ids, num_ddim_steps=args.steps, noise=noise)
-    mk = dict(input_ids=ids, images=b["images"]["front_image"][:1], point_cloud=b["point_cloud"][:1], camera_name="rlbench_front",
-              proprio=b["proprio"][:1])
+    image, pc, state = _observation(b)
+    kw = dict(image=image, pointcloud=pc, cur_robot_state=state, input_ids=ids, num_ddim_steps=args.steps, noise=noise)
+    mk = dict(input_ids=ids, **_engine_kw(b))
     modes = ("bf16", "fp8")
     acts = {mode: m.predict_action_diff(suffix_weights=mode, **kw) for mode in modes}          # engines, graphs, packed + quantised weights
     t91 = torch.tensor([91], device=dev)
 
     def chunk_ms(mode):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.iters):
-            m.predict_action_diff(suffix_weights=mode, **kw)
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / args.iters * 1e3
+        return _time_ms(lambda: m.predict_action_diff(suffix_weights=mode, **kw), args.iters)
 
     def pass_ms(mode):
         with torch.inference_mode():
             eng = PrefixCachedEps.for_inputs(m.vlm, n_action_rows=args.chunk, suffix_weights=mode, **mk)
             eng(noise, t91)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(8):
-                eng._run()
-            e1.record()
-            torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / 8
+            return _replay_ms(eng)
     chunk = {mode: [] for mode in modes}
     suffix = {mode: [] for mode in modes}
     for _ in range(args.pairs):                                             # bf16, fp8, bf16, fp8, ...: same box, interleaved
@@ -271,25 +287,16 @@ def main_pair_sampler(args):
     chunk (host clock around `iters` calls that end in a device synchronise), the prefill alone (PrefixCachedEps.for_inputs: encoders +
     prefix rows, the same for both arms) and from the two the per-step share (chunk - prefill) / steps of each arm -- the suffix pass
     plus the sampler's glue, which is what the mode changes."""
-    from bench import build
     from mla_amd.infer import PrefixCachedEps
-    from mla_amd.synthetic import make_batch
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(0)
-    m = build(dev, 1)
-    m.eval()
-    for p in m.parameters():
-        p.data = p.data.to(torch.bfloat16)
-    b = make_batch(B=1, device=dev)
-    ids = torch.cat([b["input_ids"][:, :-4], torch.tensor([[29871]], device=dev)], dim=1)
-    mk = dict(input_ids=ids, images=b["images"]["front_image"][:1], point_cloud=b["point_cloud"][:1], camera_name="rlbench_front",
-              proprio=b["proprio"][:1])
+    m, b, ids = _setup()
+    dev = ids.device
+    image, pc, state = _observation(b)
+    mk = dict(input_ids=ids, **_engine_kw(b))
     arms = ("host", "device")
     for C in ([int(v) for v in args.chunks.split(",")] if args.chunks else [1, 16]):
         m.future_action_window_size = m.vlm.future_action_window_size = C - 1
         noise = torch.randn(1, C, 7, device=dev)
-        kw = dict(image=b["images"]["front_image"][0], pointcloud=b["point_cloud"][0], cur_robot_state=b["proprio"][0, 0].cpu().numpy(),
-                  input_ids=ids, num_ddim_steps=args.steps, noise=noise)
+        kw = dict(image=image, pointcloud=pc, cur_robot_state=state, input_ids=ids, num_ddim_steps=args.steps, noise=noise)
         for w in ("bf16", "fp8"):
             acts = {}
             for arm in arms:                                                # engines, graphs, tables; the same seed: the same FPS start indices
@@ -299,21 +306,11 @@ def main_pair_sampler(args):
                 eng = PrefixCachedEps.for_inputs(m.vlm, n_action_rows=C, suffix_weights=w, **mk)
 
             def chunk_ms(arm):
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(args.iters):
-                    m.predict_action_diff(suffix_weights=w, sampler=arm, **kw)
-                torch.cuda.synchronize()
-                return (time.perf_counter() - t0) / args.iters * 1e3
+                return _time_ms(lambda: m.predict_action_diff(suffix_weights=w, sampler=arm, **kw), args.iters)
 
             def prefill_ms():
                 with torch.inference_mode():
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    for _ in range(args.iters):
-                        PrefixCachedEps.for_inputs(m.vlm, n_action_rows=C, suffix_weights=w, **mk)
-                    torch.cuda.synchronize()
-                return (time.perf_counter() - t0) / args.iters * 1e3
+                    return _time_ms(lambda: PrefixCachedEps.for_inputs(m.vlm, n_action_rows=C, suffix_weights=w, **mk), args.iters)
             chunk, prefill = {arm: [] for arm in arms}, []
             for _ in range(args.pairs):                                     # host, device, host, device, ...: same box, interleaved
                 for arm in arms:
@@ -392,26 +389,17 @@ def main_pair_attention(args):
                           "table": _attn_split_table(dev), "data": "synthetic"}), flush=True)
     if args.pairs < 1:
         return
-    from bench import build
     from mla_amd import hip
     from mla_amd.infer import PrefixCachedEps
-    from mla_amd.synthetic import make_batch
-    torch.manual_seed(0)
-    m = build(dev, 1)
-    m.eval()
-    for p in m.parameters():
-        p.data = p.data.to(torch.bfloat16)
-    b = make_batch(B=1, device=dev)
-    ids = torch.cat([b["input_ids"][:, :-4], torch.tensor([[29871]], device=dev)], dim=1)
-    mk = dict(input_ids=ids, images=b["images"]["front_image"][:1], point_cloud=b["point_cloud"][:1], camera_name="rlbench_front",
-              proprio=b["proprio"][:1])
+    m, b, ids = _setup()
+    image, pc, state = _observation(b)
+    mk = dict(input_ids=ids, **_engine_kw(b))
     arms = ("head", "split")
     t91 = torch.tensor([91], device=dev)
     for C in ([int(v) for v in args.chunks.split(",")] if args.chunks else [1, 16]):
         m.future_action_window_size = m.vlm.future_action_window_size = C - 1
         noise = torch.randn(1, C, 7, device=dev)
-        kw = dict(image=b["images"]["front_image"][0], pointcloud=b["point_cloud"][0], cur_robot_state=b["proprio"][0, 0].cpu().numpy(),
-                  input_ids=ids, num_ddim_steps=args.steps, noise=noise, sampler="device")
+        kw = dict(image=image, pointcloud=pc, cur_robot_state=state, input_ids=ids, num_ddim_steps=args.steps, noise=noise, sampler="device")
         for w in ("bf16", "fp8"):
             acts = {}
             for arm in arms:                                                # engines, graphs, tables; the same seed: the same FPS start indices
@@ -419,24 +407,13 @@ def main_pair_attention(args):
                 acts[arm] = m.predict_action_diff(suffix_weights=w, suffix_attention=arm, **kw)
 
             def chunk_ms(arm):
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(args.iters):
-                    m.predict_action_diff(suffix_weights=w, suffix_attention=arm, **kw)
-                torch.cuda.synchronize()
-                return (time.perf_counter() - t0) / args.iters * 1e3
+                return _time_ms(lambda: m.predict_action_diff(suffix_weights=w, suffix_attention=arm, **kw), args.iters)
 
             def pass_ms(arm):
                 with torch.inference_mode():
                     eng = PrefixCachedEps.for_inputs(m.vlm, n_action_rows=C, suffix_weights=w, suffix_attention=arm, **mk)
                     eng(noise, t91)
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(8):
-                        eng._run()
-                    e1.record()
-                    torch.cuda.synchronize()
-                return e0.elapsed_time(e1) / 8, eng
+                    return _replay_ms(eng), eng
             chunk, suffix = {arm: [] for arm in arms}, {arm: [] for arm in arms}
             for _ in range(args.pairs):                                     # head, split, head, split, ...: same box, interleaved
                 for arm in arms:
@@ -461,24 +438,14 @@ def main_pair_attention(args):
 def main_pair_prefill(args):
     """prefill="train" vs prefill="compact" on the same box, alternating: (a) predict_action_diff per chunk with bf16 and with fp8 suffix
     weights, (b) engine.prefill() = encoders + the decoder rows of the prefix, (c) the decoder rows alone on given prefix rows."""
-    from bench import build
     from mla_amd import hip, ops
     from mla_amd.infer import PrefixCachedEps
-    from mla_amd.synthetic import make_batch
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(0)
-    m = build(dev, 1)
-    m.future_action_window_size = m.vlm.future_action_window_size = args.chunk - 1
-    m.eval()
-    for p in m.parameters():
-        p.data = p.data.to(torch.bfloat16)
-    b = make_batch(B=1, device=dev)
-    ids = torch.cat([b["input_ids"][:, :-4], torch.tensor([[29871]], device=dev)], dim=1)
+    m, b, ids = _setup(args)
+    dev = ids.device
     noise = torch.randn(1, args.chunk, 7, device=dev)
-    kw = dict(image=b["images"]["front_image"][0], pointcloud=b["point_cloud"][0], cur_robot_state=b["proprio"][0, 0].cpu().numpy(),
-              input_ids=ids, num_ddim_steps=args.steps, noise=noise)
-    mk = dict(input_ids=ids, images=b["images"]["front_image"][:1], point_cloud=b["point_cloud"][:1], camera_name="rlbench_front",
-              proprio=b["proprio"][:1])
+    image, pc, state = _observation(b)
+    kw = dict(image=image, pointcloud=pc, cur_robot_state=state, input_ids=ids, num_ddim_steps=args.steps, noise=noise)
+    mk = dict(input_ids=ids, **_engine_kw(b))
     modes, weights = ("train", "compact"), ("bf16", "fp8")
     acts = {(w, mode): m.predict_action_diff(suffix_weights=w, prefill=mode, **kw) for w in weights for mode in modes}   # engines, graphs
     k = PrefixCachedEps._splice_position(ids)
@@ -488,12 +455,7 @@ def main_pair_prefill(args):
     S_p, H = eng["train"].S_p, eng["train"].H
 
     def chunk_ms(w, mode):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.iters):
-            m.predict_action_diff(suffix_weights=w, prefill=mode, **kw)
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / args.iters * 1e3
+        return _time_ms(lambda: m.predict_action_diff(suffix_weights=w, prefill=mode, **kw), args.iters)
 
     def timed(fn, reps=3):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -643,8 +605,6 @@ def _attn_groups_table(dev, Ns, chunks, H=32, S_p=545, layers=32, reps=5, rounds
 
 
 def main_samples(args):
-    from bench import build
-    from mla_amd.synthetic import make_batch
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     Ns = [int(v) for v in args.samples.split(",")]
@@ -652,13 +612,8 @@ def main_samples(args):
     if args.kernel_table:
         print(json.dumps({"metric": "mla_attn_chunk_groups vs mla_attn_chunk_ragged on N copies, 32 heads, S_p 545, one launch per layer cache",
                           "unit": "us", "table": _attn_groups_table(dev, Ns, chunks), "data": "synthetic"}), flush=True)
-    m = build(dev, 1)
-    m.eval()
-    for p in m.parameters():
-        p.data = p.data.to(torch.bfloat16)
-    b = make_batch(B=1, device=dev)
-    ids = torch.cat([b["input_ids"][:, :-4], torch.tensor([[29871]], device=dev)], dim=1)
-    image, pc, state = b["images"]["front_image"][0], b["point_cloud"][0], b["proprio"][0, 0].cpu().numpy()
+    m, b, ids = _setup()
+    image, pc, state = _observation(b)
     for chunk in chunks:
         m.future_action_window_size = m.vlm.future_action_window_size = chunk - 1
         for N in Ns:
@@ -674,12 +629,7 @@ def main_samples(args):
             ms = {k: [] for k in forms}
             for _ in range(args.pairs):                                       # a, b, c, a, b, c, ...: same box, interleaved
                 for k, fn in forms.items():
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    for _ in range(args.iters):
-                        fn()
-                    torch.cuda.synchronize()
-                    ms[k].append((time.perf_counter() - t0) / args.iters * 1e3)
+                    ms[k].append(_time_ms(fn, args.iters))
             rel = lambda x, y: round(float(((x - y) ** 2).sum() ** 0.5 / (y ** 2).sum() ** 0.5), 5)  # noqa: E731
             eng = next(iter(m.vlm.__dict__.get("_prefix_engines_samples", {}).values()), None)
             print(json.dumps({"metric": "N action chunks for one observation, MLA-Llama2-7B bf16: (a) predict_action_diff_samples, (b) "
@@ -744,21 +694,13 @@ def _suffix_kernel_table(m, dev, Ms=(34, 68, 136, 255), rounds=3, reps=3):
 
 
 def main_samples_pair(args):
-    from bench import build
     from mla_amd.infer import SampleGroupsEps
-    from mla_amd.synthetic import make_batch
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(0)
     Ns = [int(v) for v in args.samples.split(",")]
     chunks = [int(v) for v in args.chunks.split(",")] if args.chunks else [args.chunk]
-    m = build(dev, 1)
-    m.eval()
-    for p in m.parameters():
-        p.data = p.data.to(torch.bfloat16)
-    b = make_batch(B=1, device=dev)
-    ids = torch.cat([b["input_ids"][:, :-4], torch.tensor([[29871]], device=dev)], dim=1)
-    image, pc, state = b["images"]["front_image"][0], b["point_cloud"][0], b["proprio"][0, 0].cpu().numpy()
-    mk = dict(images=b["images"]["front_image"][:1], point_cloud=b["point_cloud"][:1], camera_name="rlbench_front", proprio=b["proprio"][:1])
+    m, b, ids = _setup()
+    dev = ids.device
+    image, pc, state = _observation(b)
+    mk = _engine_kw(b)
     modes = ("bf16", "fp8")
     table_done = not args.kernel_table
     for chunk in chunks:
@@ -772,12 +714,7 @@ def main_samples_pair(args):
                                                      num_ddim_steps=args.steps, suffix_weights=mode)
 
             def call_ms(mode):
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(args.iters):
-                    call(mode)
-                torch.cuda.synchronize()
-                return (time.perf_counter() - t0) / args.iters * 1e3
+                return _time_ms(lambda: call(mode), args.iters)
 
             def pass_ms(mode):
                 with torch.inference_mode():
@@ -785,13 +722,7 @@ def main_samples_pair(args):
                     assert len(passes) == 1, "one pass per sampler step: N * (chunk + 1) <= 256"
                     eng.set_groups(N)
                     eng(noise, t91)
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(8):
-                        eng._run()
-                    e1.record()
-                    torch.cuda.synchronize()
-                return e0.elapsed_time(e1) / 8, eng.graph is not None
+                    return _replay_ms(eng), eng.graph is not None
             outs = {mode: call(mode) for mode in modes}                       # engines, graphs, packed + quantised weights
             if not table_done:
                 print(json.dumps({"metric": "mla_gemm_suffix_w8 vs mla_gemm_suffix_bf16 per 7B projection shape, one launch per layer's weights",
@@ -866,8 +797,6 @@ def _ragged_groups_table(dev, cases, chunk, H=32, layers=32, reps=5, rounds=3):
 
 
 def main_batch_samples(args, batches):
-    from bench import build
-    from mla_amd.synthetic import make_batch
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     Ns = [int(v) for v in args.samples.split(",")]
@@ -878,21 +807,13 @@ def main_batch_samples(args, batches):
         print(json.dumps({"metric": "mla_attn_chunk_ragged_groups (one launch) vs mla_attn_chunk_groups per sample (B launches), 32 heads, one "
                                     "layer cache each", "unit": "us", "table": _ragged_groups_table(dev, cases, chunk), "data": "synthetic"}),
               flush=True)
-    m = build(dev, 1)
-    m.future_action_window_size = m.vlm.future_action_window_size = chunk - 1
-    m.eval()
-    for p in m.parameters():
-        p.data = p.data.to(torch.bfloat16)
+    m, wbytes = None, None
     modes = ("bf16", "fp8") if args.pair_fp8 else ("bf16",)
-    wbytes = {mode: _stream_bytes(m, mode) for mode in modes}
     for B, N in cases:
-        b = make_batch(B=B, device=dev)
-        g = torch.Generator().manual_seed(1234)
-        drop = torch.randint(0, 13, (B,), generator=g).tolist()             # ragged prompts: 0 .. 12 ids shorter than the synthetic prompt
-        ids = [torch.cat([b["input_ids"][i, :b["input_ids"].shape[1] - 4 - drop[i]], torch.tensor([29871], device=dev)]) for i in range(B)]
-        images = [b["images"]["front_image"][i] for i in range(B)]
-        pcs = [b["point_cloud"][i] for i in range(B)]
-        states = [b["proprio"][i, 0].cpu().numpy() for i in range(B)]
+        m, b, ids = _setup(chunk, B, model=m)                                 # the model once, a batch per case
+        ids = list(ids)
+        wbytes = wbytes or {mode: _stream_bytes(m, mode) for mode in modes}
+        images, pcs, states = (list(v) for v in zip(*(_observation(b, i) for i in range(B))))
         noise = torch.randn(B, N, chunk, 7, device=dev)
 
         def batched(mode):
@@ -904,12 +825,7 @@ def main_batch_samples(args, batches):
                                                            noise=noise[i], num_ddim_steps=args.steps, suffix_weights=mode) for i in range(B)])
 
         def timed(fn, mode):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(args.iters):
-                fn(mode)
-            torch.cuda.synchronize()
-            return (time.perf_counter() - t0) / args.iters * 1e3
+            return _time_ms(lambda: fn(mode), args.iters)
         for mode in modes:
             outs = {"a": batched(mode), "b": sequential(mode)}                # engines, graphs, packed (+ quantised) weights
             ms = {"a_batch_samples": [], "b_sequential_samples": []}
@@ -935,24 +851,11 @@ def main_batch_samples(args, batches):
 
 
 def main_batch(args):
-    from bench import build
     from mla_amd.infer import BatchedPrefixCachedEps
-    from mla_amd.synthetic import make_batch
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(0)
-    m = build(dev, 1)
-    m.future_action_window_size = m.vlm.future_action_window_size = args.chunk - 1
-    m.eval()
-    for p in m.parameters():
-        p.data = p.data.to(torch.bfloat16)
     B = args.batch
-    b = make_batch(B=B, device=dev)
-    g = torch.Generator().manual_seed(1234)
-    drop = torch.randint(0, 13, (B,), generator=g).tolist()               # ragged prompts: 0 .. 12 ids shorter than the synthetic prompt
-    ids = [torch.cat([b["input_ids"][i, :b["input_ids"].shape[1] - 4 - drop[i]], torch.tensor([29871], device=dev)]) for i in range(B)]
-    images = [b["images"]["front_image"][i] for i in range(B)]
-    pcs = [b["point_cloud"][i] for i in range(B)]
-    states = [b["proprio"][i, 0].cpu().numpy() for i in range(B)]
+    m, b, ids = _setup(args, B)
+    ids, dev = list(ids), ids[0].device
+    images, pcs, states = (list(v) for v in zip(*(_observation(b, i) for i in range(B))))
     noise = torch.randn(B, args.chunk, 7, device=dev)
 
     def batched():
@@ -962,19 +865,10 @@ def main_batch(args):
         return [m.predict_action_diff(image=images[i], pointcloud=pcs[i], cur_robot_state=states[i], input_ids=ids[i][None], noise=noise[i:i + 1],
                                       num_ddim_steps=args.steps) for i in range(B)]
 
-    def timed(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.iters):
-            out = fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / args.iters * 1e3, out
-    batched(), sequential()                                                # engines, graphs, packed weights
+    act = batched()                                                        # engines, graphs, packed weights
+    sequential()
     # alternating pairs in one process: batched, sequential, batched, sequential
-    ms_b1, act = timed(batched)
-    ms_s1, _ = timed(sequential)
-    ms_b2, _ = timed(batched)
-    ms_s2, _ = timed(sequential)
+    ms_b1, ms_s1, ms_b2, ms_s2 = (_time_ms(fn, args.iters) for fn in (batched, sequential, batched, sequential))
     parts = {}
     engines = m.vlm.__dict__.get("_prefix_engines_batched", {})
     if engines:
@@ -991,14 +885,8 @@ def main_batch(args):
             ev[1].record()
             torch.cuda.synchronize()
             for sub, eng in BatchedPrefixCachedEps.for_batch(m.vlm, rows, args.chunk, **mk):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 eng(noise[sub.start:sub.stop], torch.full((sub.stop - sub.start,), 91, device=dev))
-                e0.record()
-                for _ in range(8):
-                    eng._run()
-                e1.record()
-                torch.cuda.synchronize()
-                pass_ms += e0.elapsed_time(e1) / 8
+                pass_ms += _replay_ms(eng)
         parts = {"sub_batches": n_sub, "prefill_ms": round(ev[0].elapsed_time(ev[1]), 2), "suffix_pass_graph_replay_ms": round(pass_ms, 3),
                  "weights_streamed_per_pass_gb": round(wbytes * n_sub / 1e9, 2),
                  "suffix_pass_weight_stream_tbps": round(wbytes * n_sub / 1e12 / (pass_ms * 1e-3), 2)}
