@@ -428,6 +428,27 @@ int mla_gemm_prefill_qkv_rope(const void* x, long long ldx, const void* W, long 
 int mla_gemm_prefill_gateup_swiglu(const void* x, long long ldx, const void* wgu, long long ldw, void* act, long long ldo,
                                    long long out_batch_stride, int rows_per_batch, int M, int I, int K, void* workspace,
                                    size_t workspace_bytes, mla_stream_t stream);
+/* ---- the same family over FP8 codes (opt-in prefill_precision="fp8"; mla_amd/csrc/prefill_f8.hip): xq [M, K] and Wq [N, K] are e4m3fn
+ * codes with one fp32 scale per row (x_scale [M], w_scale [N]), exactly what mla_quant_fp8_rows writes. out[m, n] =
+ * bf16((sum_k xq[m, k] Wq[n, k]) * x_scale[m] * w_scale[n] ...): the sums run over the unscaled codes in fp32 on
+ * v_mfma_f32_16x16x128_f8f6f4, the two scales are applied to the finished sum, in that order, BEFORE the rotation (the partner channel
+ * with its own w_scale), before silu(gate) * up (gate and up with the scales of their own rows of the packed matrix) and before the
+ * residual; one rounding. 1 <= M <= 1024, N % 128 == 0, K >= 128 and K % 128 == 0 (one K tile is 128 codes); xq / Wq rows 16-B aligned
+ * (ldx, ldw multiples of 16 codes), out / residual as in the bf16 family; output addressing, RoPE tables, split-K rule (on K tiles of
+ * 128), workspace layout, determinism and the -1 refusals that launch nothing are the bf16 family's. mla_gemm_prefill_f8_plan /
+ * _ws_bytes answer for this family; the pure-Python mirror is mla_amd/hip.py:plan_gemm_prefill_f8. */
+int mla_gemm_prefill_f8_plan(int M, int N, int K, int cus, int* out4);
+long long mla_gemm_prefill_f8_ws_bytes(int M, int N, int K);
+int mla_gemm_prefill_f8(const void* xq, long long ldx, const float* x_scale, const void* Wq, long long ldw, const float* w_scale, void* out,
+                        long long ldo, long long out_batch_stride, int rows_per_batch, const void* residual, long long ld_res, int M, int N,
+                        int K, void* workspace, size_t workspace_bytes, mla_stream_t stream);
+int mla_gemm_prefill_f8_qkv_rope(const void* xq, long long ldx, const float* x_scale, const void* Wq, long long ldw, const float* w_scale,
+                                 void* out, long long ldo, long long out_batch_stride, int rows_per_batch, int M, int N, int K,
+                                 const float* rope_cos, const float* rope_sin, int rope_cols, int head_dim, void* workspace,
+                                 size_t workspace_bytes, mla_stream_t stream);
+int mla_gemm_prefill_f8_gateup_swiglu(const void* xq, long long ldx, const float* x_scale, const void* wgu_q, long long ldw,
+                                      const float* w_scale, void* act, long long ldo, long long out_batch_stride, int rows_per_batch, int M,
+                                      int I, int K, void* workspace, size_t workspace_bytes, mla_stream_t stream);
 
 /* ---- device-resident DDIM loop (mla_amd/infer.py _CachedEpsBase.sample_ddim, opt-in sampler="device"; mla_amd/csrc/sampler.hip): the
  * sampler's glue between two suffix passes with the step index in device memory, so that a captured sampler step can be replayed

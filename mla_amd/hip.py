@@ -70,6 +70,14 @@ _SIGNATURES = {
                                   c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p],
     "mla_gemm_prefill_gateup_swiglu": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_int, c_int,
                                        c_int, c_void_p, c_size_t, c_void_p],
+    "mla_gemm_prefill_f8_plan": [c_int, c_int, c_int, c_int, c_void_p],
+    "mla_gemm_prefill_f8_ws_bytes": [c_int, c_int, c_int],   # returns long long (restype fixed up in lib())
+    "mla_gemm_prefill_f8": [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_void_p,
+                            c_longlong, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p],
+    "mla_gemm_prefill_f8_qkv_rope": [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int,
+                                     c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p],
+    "mla_gemm_prefill_f8_gateup_swiglu": [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong,
+                                          c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p],
     "mla_ddim_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "mla_sampler_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "mla_attn_chunk_split_plan": [c_int, c_int, c_int, c_int, c_int, c_void_p],
@@ -192,6 +200,7 @@ def lib():
         L.mla_attn_bwd_ws_bytes.restype = c_longlong
         L.mla_attn_bwd_sync_ints.restype = c_longlong
         L.mla_gemm_prefill_ws_bytes.restype = c_longlong
+        L.mla_gemm_prefill_f8_ws_bytes.restype = c_longlong
         L.mla_attn_chunk_split_ws_bytes.restype = c_longlong
         _lib = L
     return _lib
@@ -1107,8 +1116,13 @@ def plan_gemm_prefill(M: int, N: int, K: int, cus: int = 256) -> PrefillGemmPlan
     tiles, split-K doubled while tiles x split < 2 x cus, split < 16 and every slice keeps at least 8 K tiles of 64."""
     if not gemm_prefill_fits(M, N, K):
         raise ValueError(f"plan_gemm_prefill: 1 <= M <= {PREFILL_MMAX}, N % {PREFILL_BN} == 0, K % 32 == 0 required (M {M}, N {N}, K {K})")
+    return _prefill_plan(M, N, K, -(-K // PREFILL_BK), cus)
+
+
+def _prefill_plan(M, N, K, ktiles, cus):
+    """The split-K rule both prefill GEMM families share, on `ktiles` K tiles (of 64 bf16 or 128 FP8 codes)."""
     mt, nt = -(-M // PREFILL_BM), N // PREFILL_BN
-    tiles, ktiles = mt * nt, -(-K // PREFILL_BK)
+    tiles = mt * nt
     split = 1
     while tiles * split < 2 * cus and split < PREFILL_MAX_SPLIT and ktiles // (split * 2) >= PREFILL_MIN_KTILES:
         split *= 2
@@ -1170,6 +1184,80 @@ def gemm_prefill_gateup_swiglu(x, wgu, act, ldo=None, out_batch_stride=0, rows_p
     assert wgu.shape[0] % 2 == 0
     call("mla_gemm_prefill_gateup_swiglu", _p(x), x.stride(0), _p(wgu), wgu.stride(0), _p(act), act.stride(0) if ldo is None else ldo,
          out_batch_stride, M if rows_per_batch is None else rows_per_batch, M, wgu.shape[0] // 2, K, wp, wb)
+
+
+# ---- FP8 compact prefill GEMMs (mla_amd/csrc/prefill_f8.hip): prefill.hip's tiles and split-K over e4m3fn codes of BOTH operands with one
+# fp32 scale per row (quant_fp8_rows), on v_mfma_f32_16x16x128_f8f6f4; a K tile is 128 codes
+PREFILL_F8_BK = 128
+
+
+def gemm_prefill_f8_fits(M: int, N: int, K: int) -> bool:
+    """True when the FP8 prefill GEMMs accept the shape: 1 <= M <= 1024, N % 128 == 0 (2 I for the SwiGLU form), K % 128 == 0."""
+    return 1 <= M <= PREFILL_MMAX and N >= PREFILL_BN and N % PREFILL_BN == 0 and K >= PREFILL_F8_BK and K % PREFILL_F8_BK == 0
+
+
+def plan_gemm_prefill_f8(M: int, N: int, K: int, cus: int = 256) -> PrefillGemmPlan:
+    """Pure-Python mirror of the FP8 launcher's choice (prefill_f8.hip:f8_plan; mla_gemm_prefill_f8_plan returns the library's):
+    plan_gemm_prefill's rule on K tiles of 128 codes."""
+    if not gemm_prefill_f8_fits(M, N, K):
+        raise ValueError(f"plan_gemm_prefill_f8: 1 <= M <= {PREFILL_MMAX}, N % {PREFILL_BN} == 0, K % {PREFILL_F8_BK} == 0 required "
+                         f"(M {M}, N {N}, K {K})")
+    return _prefill_plan(M, N, K, K // PREFILL_F8_BK, cus)
+
+
+def gemm_prefill_f8_ws_bytes(M: int, N: int, K: int) -> int:
+    """Workspace bytes the FP8 launcher needs for the shape (mla_gemm_prefill_f8_ws_bytes); -1 outside the contract."""
+    return int(lib().mla_gemm_prefill_f8_ws_bytes(int(M), int(N), int(K)))
+
+
+def _prefill_f8_common(name, xq, x_scale, Wq, w_scale, out, ws):
+    _req(xq, torch.float8_e4m3fn, f"{name} xq")
+    _req(Wq, torch.float8_e4m3fn, f"{name} Wq")
+    _req(x_scale, torch.float32, f"{name} x_scale")
+    _req(w_scale, torch.float32, f"{name} w_scale")
+    _req(out, torch.bfloat16, f"{name} out")
+    assert xq.dim() == 2 and Wq.dim() == 2 and Wq.shape[1] == xq.shape[1] and xq.stride(1) == 1 and Wq.stride(1) == 1
+    assert x_scale.numel() == xq.shape[0] and x_scale.is_contiguous() and w_scale.numel() == Wq.shape[0] and w_scale.is_contiguous()
+    if ws is not None:
+        assert ws.is_cuda and ws.is_contiguous()
+    return _p(ws), (ws.numel() * ws.element_size() if ws is not None else 0)
+
+
+def gemm_prefill_f8(xq, x_scale, Wq, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, ws=None):
+    """gemm_prefill over FP8 codes of both operands (mla_gemm_prefill_f8): out row m = bf16((xq[m] @ Wq^T) * x_scale[m] * w_scale
+    (+ residual[m])), xq [M, K] / Wq [N, K] float8_e4m3fn and x_scale [M] / w_scale [N] fp32 as quant_fp8_rows writes them; the sums run
+    over the codes in fp32. Addressing and ws as gemm_prefill, with gemm_prefill_f8_ws_bytes(M, N, K)."""
+    wp, wb = _prefill_f8_common("gemm_prefill_f8", xq, x_scale, Wq, w_scale, out, ws)
+    M, K = xq.shape
+    if residual is not None:
+        _req(residual, torch.bfloat16, "gemm_prefill_f8 residual")
+        assert residual.shape[0] == M and residual.stride(1) == 1
+    call("mla_gemm_prefill_f8", _p(xq), xq.stride(0), _p(x_scale), _p(Wq), Wq.stride(0), _p(w_scale), c_void_p(out.data_ptr() + 2 * out_col),
+         ldo, out_batch_stride, rows_per_batch, _p(residual), residual.stride(0) if residual is not None else 0, M, Wq.shape[0], K, wp, wb)
+
+
+def gemm_prefill_f8_qkv_rope(xq, x_scale, Wq, w_scale, out, ldo, out_batch_stride, rows_per_batch, rope, head_dim=128, ws=None):
+    """gemm_prefill_qkv_rope over FP8 codes (mla_gemm_prefill_f8_qkv_rope): both scales are applied to the fp32 sums before the rotation,
+    the partner channel with its own w_scale."""
+    wp, wb = _prefill_f8_common("gemm_prefill_f8_qkv_rope", xq, x_scale, Wq, w_scale, out, ws)
+    cos, sin, rope_cols = rope
+    _req(cos, torch.float32, "gemm_prefill_f8_qkv_rope cos")
+    _req(sin, torch.float32, "gemm_prefill_f8_qkv_rope sin")
+    assert cos.shape == (rows_per_batch, 64) and sin.shape == cos.shape and cos.is_contiguous() and sin.is_contiguous()
+    M, K = xq.shape
+    call("mla_gemm_prefill_f8_qkv_rope", _p(xq), xq.stride(0), _p(x_scale), _p(Wq), Wq.stride(0), _p(w_scale), _p(out), ldo, out_batch_stride,
+         rows_per_batch, M, Wq.shape[0], K, _p(cos), _p(sin), int(rope_cols), int(head_dim), wp, wb)
+
+
+def gemm_prefill_f8_gateup_swiglu(xq, x_scale, wgu_q, w_scale, act, ldo=None, out_batch_stride=0, rows_per_batch=None, ws=None):
+    """gemm_prefill_gateup_swiglu over FP8 codes (mla_gemm_prefill_f8_gateup_swiglu): wgu_q = the packed [2 I, K] gate|up codes, w_scale
+    [2 I]; gate and up are scaled with the scales of their own rows before silu(gate) * up."""
+    wp, wb = _prefill_f8_common("gemm_prefill_f8_gateup_swiglu", xq, x_scale, wgu_q, w_scale, act, ws)
+    M, K = xq.shape
+    assert wgu_q.shape[0] % 2 == 0
+    call("mla_gemm_prefill_f8_gateup_swiglu", _p(xq), xq.stride(0), _p(x_scale), _p(wgu_q), wgu_q.stride(0), _p(w_scale), _p(act),
+         act.stride(0) if ldo is None else ldo, out_batch_stride, M if rows_per_batch is None else rows_per_batch, M, wgu_q.shape[0] // 2, K,
+         wp, wb)
 
 
 # --------------------------------------------------------------------------------------------- device-resident DDIM loop (sampler.hip)

@@ -26,6 +26,10 @@ Opt-in (`suffix_attention="split"`, see SUFFIX_ATTENTION_MODES; PrefixCachedEps 
 `mla_attn_chunk_split` -- every head's key tiles cut over several workgroups, the partial softmax states merged in a fixed order by a
 second launch -- for every R; the same function up to summation order.
 
+Opt-in (`prefill="compact"`, `prefill_precision="fp8"`, see PREFILL_MODES / PREFILL_PRECISION_MODES; PrefixCachedEps and SampleGroupsEps):
+the prefix rows of one observation run on the row-sized GEMMs of csrc/prefill.hip, and with "fp8" their four projections per layer on
+e4m3fn codes of weights AND activations (csrc/prefill_f8.hip, the K = 128 FP8 MFMA) -- the same FP8 weight copy the suffix pass streams.
+
 Semantics vs the reference: identical arithmetic up to summation order (fp32 accumulation everywhere), with ONE stated difference -- the
 reference's point tokenizer draws fresh random FPS start indices inside every one of the 8 forwards (Point_PN.py:10); here they are
 drawn once per action chunk (the prefix is computed once). With given start indices (`fps_starts_override`, as in
@@ -49,8 +53,8 @@ _LOG = logging.getLogger(__name__)
 SPLICE_TAG = 29871                                  # prismatic.py:882-887 (eval): the [t, x] tokens go in front of its last occurrence
 PROMPT_TAIL = (29871, 32001, 32002, 29871)          # model_mla.py:640-645: appended unless the row already ends with the tag, then [:-3]
 
-# What the suffix pass streams (MLA.predict_action_diff(suffix_weights=...)); the prefill always runs the training kernels on the bf16 weights,
-# so the prefix keys / values keep bf16-weight precision:
+# What the suffix pass streams (MLA.predict_action_diff(suffix_weights=...)); the prefill does not depend on it (bf16 weights unless
+# prefill_precision says otherwise), so the prefix keys / values keep bf16-weight precision:
 #   "bf16"         the decoder weights as they are (default)
 #   "fp8"          a per-row e4m3fn copy (hip.quant_fp8_rows) through mla_gemv_w8 / mla_gemm_skinny_w8 (PrefixCachedEps) or
 #                  mla_gemm_suffix_w8 (SampleGroupsEps): half the bytes per sampler step
@@ -73,6 +77,26 @@ PREFILL_MODES = ("train", "compact")
 def check_prefill(mode):
     if mode not in PREFILL_MODES:
         raise ValueError(f"prefill must be one of {PREFILL_MODES}, got {mode!r}")
+
+
+# What the compact prefill's four projections per layer compute on (MLA.predict_action_diff(prefill="compact", prefill_precision=...)):
+#   "bf16"         the bf16 weights and activations as they are (default)
+#   "fp8"          e4m3fn codes of BOTH operands on the K = 128 MFMA (mla_amd/csrc/prefill_f8.hip): the model's FP8 weight copy (one scale
+#                  per output channel, shared with suffix_weights="fp8") and the projection inputs quantised per row (hip.quant_fp8_rows);
+#                  attention, cache, norms and residual stream stay bf16
+#   "fp8_as_bf16"  the bf16 compact kernels on bf16(code * scale) of the same weight codes, the projection inputs quantised and
+#                  dequantised by the same statement: the reference of the "fp8" path, and what the format costs on a checkpoint
+PREFILL_PRECISION_MODES = ("bf16", "fp8", "fp8_as_bf16")
+
+
+def check_prefill_precision(mode, prefill="compact"):
+    """The argument errors of prefill_precision=: an unknown value; anything but "bf16" without prefill="compact" (there is never a silent
+    bf16 prefill)."""
+    if mode not in PREFILL_PRECISION_MODES:
+        raise ValueError(f"prefill_precision must be one of {PREFILL_PRECISION_MODES}, got {mode!r}")
+    if mode != "bf16" and prefill != "compact":
+        raise ValueError(f"prefill_precision={mode!r} runs on the compact prefill (prefill=\"compact\"); prefill={prefill!r} has the bf16 "
+                         "kernels only")
 
 
 # Which attention launch the sampler steps of PrefixCachedEps use (MLA.predict_action_diff(suffix_attention=...)):
@@ -145,6 +169,12 @@ class _DdimState:
     __slots__ = ("diffusion", "steps", "x", "x_bf16", "step", "coef", "timesteps", "t_table", "t_key", "graph", "graph_key", "failed")
 
 
+def _fake_quant_rows(x):
+    """bf16(code * scale) of hip.quant_fp8_rows(x): what a projection of prefill_precision="fp8" sees of its input rows, as bf16."""
+    q, scale = hip.quant_fp8_rows(x)
+    return (q.float() * scale[:, None]).to(torch.bfloat16)
+
+
 class W8(NamedTuple):
     """A quantised projection weight: q [N, K] float8_e4m3fn codes, scale [N] fp32 (one per output channel)."""
     q: torch.Tensor
@@ -155,15 +185,20 @@ class _CachedEpsBase:
     """What the cached-prefix engines share: the packed weights, the captured suffix pass and the `model(x, t)` call of the samplers.
     A subclass provides prefill() and _suffix_pass() and sets B, R, T, H, h_in, h_out, cache."""
 
-    def __init__(self, vlm, n_action_rows: int = 1, suffix_weights: str = "bf16", prefill: str = "train", suffix_attention: str = "head"):
+    def __init__(self, vlm, n_action_rows: int = 1, suffix_weights: str = "bf16", prefill: str = "train", suffix_attention: str = "head",
+                 prefill_precision: str = "bf16"):
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
         check_suffix_attention(suffix_attention)
+        check_prefill_precision(prefill_precision, prefill)
         self.suffix_weights = suffix_weights
         self.prefill_mode = prefill
+        self.prefill_precision = prefill_precision
         self.suffix_attention = suffix_attention
         self._attn_ws = None         # "split": the partial softmax states of mla_attn_chunk_split, allocated once beside h_in / h_out
         self._prefill_ws = None      # "compact": the split-K workspace of the prefill GEMMs, allocated once beside h_in / h_out
+        self._prefill_xq = None      # prefill_precision "fp8": the projection inputs' codes (one buffer, viewed [rows, K]) ...
+        self._prefill_xs = None      # ... and their scales [rows], allocated once beside _prefill_ws
         self.vlm = vlm
         llm = vlm.llm_backbone.llm
         self.model, self.cfg = llm.model, llm.config
@@ -194,7 +229,8 @@ class _CachedEpsBase:
         return False
 
     @classmethod
-    def _engine(cls, vlm, store: str, key: tuple, ctor: tuple, suffix_weights="bf16", prefill="train", suffix_attention="head"):
+    def _engine(cls, vlm, store: str, key: tuple, ctor: tuple, suffix_weights="bf16", prefill="train", suffix_attention="head",
+                prefill_precision="bf16"):
         """The vlm's engine for `key` in vlm.__dict__[store], constructed as cls(vlm, *ctor) on first use; at most 4 per store, the oldest
         leaves first. A mode other than the default is part of the key -- the engines coexist: a captured graph holds the addresses of
         ITS weights and ITS attention launches. The caller prefills."""
@@ -205,6 +241,8 @@ class _CachedEpsBase:
             key += ("prefill:" + prefill,)
         if suffix_attention != "head":
             key += ("attention:" + suffix_attention,)
+        if prefill_precision != "bf16":
+            key += ("precision:" + prefill_precision,)
         eng = engines.get(key)
         if eng is None:
             if len(engines) >= 4:
@@ -242,9 +280,10 @@ class _CachedEpsBase:
             self._suffix = suffix
         return self._packed
 
-    def _quantised(self, key):
-        """The suffix pass's weights in the modes "fp8" / "fp8_as_bf16": per layer q|k|v, o, gate|up and down of the packed copy quantised
-        per output channel (hip.quant_fp8_rows; the scale is per row, so the packed matrices quantise as one), kept beside the packed copy:
+    def _quantised(self, key, mode=None):
+        """The model's FP8 weight copy in the form `mode` ("fp8" / "fp8_as_bf16"; default: what the suffix pass streams) -- also what the
+        prefill of prefill_precision "fp8" / "fp8_as_bf16" runs on, whatever self.suffix_weights is: per layer q|k|v, o, gate|up and down
+        of the packed copy quantised per output channel (hip.quant_fp8_rows; the scale is per row, so the packed matrices quantise as one), kept beside the packed copy:
         one per model, shared by its engines, keyed like it on (data_ptr, _version) of the layer weights and rebuilt when that changes.
         "fp8": per layer (ln1, W8 qkv, W8 o, ln2, W8 gate|up, W8 down). "fp8_as_bf16": the packed tuple's layout with bf16(q * scale) in
         place of every projection (built from the same codes on first use)."""
@@ -259,7 +298,8 @@ class _CachedEpsBase:
             shared.clear()
             shared["key"], shared["fp8"] = key, layers
             _LOG.info("suffix_weights: FP8 copy of the decoder projections, %.2f GB beside the bf16 weights", nbytes / 1e9)
-        if self.suffix_weights == "fp8_as_bf16" and "fp8_as_bf16" not in shared:
+        mode = self.suffix_weights if mode is None else mode
+        if mode == "fp8_as_bf16" and "fp8_as_bf16" not in shared:
             deq = []
             with torch.no_grad(), torch.inference_mode(False):
                 for (ln1, qkv, o, ln2, gu, d), packed in zip(shared["fp8"], self._packed):
@@ -267,7 +307,7 @@ class _CachedEpsBase:
                     nq, nk, ng = packed[1].shape[0], packed[2].shape[0], packed[6].shape[0]
                     deq.append((ln1, qkv[:nq], qkv[nq:nq + nk], qkv[nq + nk:], o, ln2, gu[:ng], gu[ng:], d))
             shared["fp8_as_bf16"] = deq
-        return shared[self.suffix_weights]
+        return shared[mode]
 
     def _suffix_layers(self):
         """Per layer ((ln1, qkv, o, ln2, gate_up, down), cache) of a suffix pass: every projection one W8 ("fp8", _quantised) or a tuple
@@ -313,38 +353,87 @@ class _CachedEpsBase:
             raise ValueError(f"prefill=\"compact\" serves at most {hip.PREFILL_MMAX} prefix rows at head_dim 128 (got {rows} rows, head_dim "
                              f"{D}); use prefill=\"train\"")
 
-    def _compact_ws(self, rows: int, dev):
-        """One workspace for the four projections of a layer at `rows` rows (the launches of a prefill run one after the other)."""
+    def _compact_buffers(self, rows: int, dev):
+        """What the compact prefill keeps per engine, allocated once (call outside inference mode): ONE split-K workspace for the four
+        projections of a layer at `rows` rows (the launches of a prefill run one after the other) and, for prefill_precision "fp8", the
+        projection inputs' codes and scales."""
         H, I = self.cfg.hidden_size, self.cfg.intermediate_size
-        need = max(hip.gemm_prefill_ws_bytes(rows, N, K) for N, K in ((3 * H, H), (H, H), (2 * I, H), (H, I)))
-        if need < 0:
+        fp8 = self.prefill_precision == "fp8"
+        ws_bytes = hip.gemm_prefill_f8_ws_bytes if fp8 else hip.gemm_prefill_ws_bytes
+        need = [ws_bytes(rows, N, K) for N, K in ((3 * H, H), (H, H), (2 * I, H), (H, I))]
+        if min(need) < 0:
             raise ValueError(f"prefill=\"compact\": the projections of this model (hidden {H}, intermediate {I}) are outside the compact "
-                             "GEMMs' contract (N % 128 == 0, K % 32 == 0); use prefill=\"train\"")
-        return torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+                             f"GEMMs' contract (N % 128 == 0, K % {hip.PREFILL_F8_BK if fp8 else 32} == 0); use prefill=\"train\"")
+        self._prefill_ws = torch.empty(max(max(need), 16), dtype=torch.uint8, device=dev)
+        if fp8:
+            self._prefill_xq = torch.empty(rows * max(H, I), dtype=torch.float8_e4m3fn, device=dev)
+            self._prefill_xs = torch.empty(rows, dtype=torch.float32, device=dev)
+
+    def _prefill_layers(self):
+        """Per layer what _compact_layer runs on: the packed 9-tuple ("bf16"), its dequantised twin ("fp8_as_bf16") or the W8 6-tuple
+        ("fp8") of the model's FP8 copy (_quantised)."""
+        packed = self._weights()
+        return packed if self.prefill_precision == "bf16" else self._quantised(self._packed_key, self.prefill_precision)
 
     def _compact_prefill(self, h, B, S_p, cache_out, out_bs):
         """The decoder layers over the B * S_p prefix rows h [B * S_p, H] on the compact GEMMs; cache_out[l] is layer l's cache tensor whose
-        sample b holds its rows at element offset b * out_bs + p * row stride. Per layer: rmsnorm_fwd, q|k|v + RoPE into the cache, the
-        training flash attention on the cache's q / k / v views, o + residual, rmsnorm_fwd, gate|up + SwiGLU (the product only), down +
-        residual."""
+        sample b holds its rows at element offset b * out_bs + p * row stride."""
+        for w, c in zip(self._prefill_layers(), cache_out):
+            h = self._compact_layer(w, h, B, S_p, c, out_bs)
+        return h
+
+    def _compact_layer(self, w, h, B, S_p, c, out_bs):
+        """One decoder layer of the compact prefill on its weights w (an entry of _prefill_layers()) -> the layer's output rows: rmsnorm_fwd,
+        q|k|v + RoPE into the cache c, the training flash attention on the cache's q / k / v views, o + residual, rmsnorm_fwd, gate|up +
+        SwiGLU (the product only), down + residual. "fp8": _compact_layer_fp8. "fp8_as_bf16": the same launches on the dequantised weights,
+        every projection input quantised and dequantised per row."""
+        if self.prefill_precision == "fp8":
+            return self._compact_layer_fp8(w, h, B, S_p, c, out_bs)
         H, nh, D, ws = self.H, self.nheads, self.D, self._prefill_ws
-        scale = 1.0 / math.sqrt(D)
-        for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd), c in zip(self._weights(), cache_out):
-            wqkv, wgu = ops.cat_view((wq, wk, wv)), ops.cat_view((wg, wu))
-            assert wqkv is not None and wgu is not None, "the packed weights are adjacent in memory (_weights)"
-            ld = c.stride(-2)
-            xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
-            hip.gemm_prefill_qkv_rope(xn, wqkv, c, ld, out_bs, S_p, (self.cos_p, self.sin_p, 2 * H), D, ws=ws)
-            flat = c.reshape(-1)
-            o = [hip.attn_fwd(*(flat[b * out_bs + j * H:] for j in range(3)), 1, S_p, nh, D, ld, None, scale)[0] for b in range(B)]
-            o = o[0] if B == 1 else torch.cat(o, 0)
-            h1 = torch.empty_like(h)
-            hip.gemm_prefill(o, wo, h1, H, 0, B * S_p, residual=h, ws=ws)
-            xn2, _ = hip.rmsnorm_fwd(h1, ln2, self.eps)
-            act = torch.empty((B * S_p, wg.shape[0]), dtype=torch.bfloat16, device=h.device)
-            hip.gemm_prefill_gateup_swiglu(xn2, wgu, act, ws=ws)
-            h = torch.empty_like(h1)
-            hip.gemm_prefill(act, wd, h, H, 0, B * S_p, residual=h1, ws=ws)
+        fq = _fake_quant_rows if self.prefill_precision == "fp8_as_bf16" else (lambda x: x)
+        ln1, wq, wk, wv, wo, ln2, wg, wu, wd = w
+        wqkv, wgu = ops.cat_view((wq, wk, wv)), ops.cat_view((wg, wu))
+        assert wqkv is not None and wgu is not None, "the packed weights are adjacent in memory (_weights)"
+        ld = c.stride(-2)
+        xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
+        hip.gemm_prefill_qkv_rope(fq(xn), wqkv, c, ld, out_bs, S_p, (self.cos_p, self.sin_p, 2 * H), D, ws=ws)
+        o = self._prefill_attention(c, B, S_p, ld, out_bs)
+        h1 = torch.empty_like(h)
+        hip.gemm_prefill(fq(o), wo, h1, H, 0, B * S_p, residual=h, ws=ws)
+        xn2, _ = hip.rmsnorm_fwd(h1, ln2, self.eps)
+        act = torch.empty((B * S_p, wg.shape[0]), dtype=torch.bfloat16, device=h.device)
+        hip.gemm_prefill_gateup_swiglu(fq(xn2), wgu, act, ws=ws)
+        h = torch.empty_like(h1)
+        hip.gemm_prefill(fq(act), wd, h, H, 0, B * S_p, residual=h1, ws=ws)
+        return h
+
+    def _prefill_attention(self, c, B, S_p, ld, out_bs):
+        """The training flash attention over the prefix rows of the cache c, per sample -> o [B * S_p, H]."""
+        H, flat = self.H, c.reshape(-1)
+        o = [hip.attn_fwd(*(flat[b * out_bs + j * H:] for j in range(3)), 1, S_p, self.nheads, self.D, ld, None, 1.0 / math.sqrt(self.D))[0]
+             for b in range(B)]
+        return o[0] if B == 1 else torch.cat(o, 0)
+
+    def _compact_layer_fp8(self, w, h, B, S_p, c, out_bs):
+        """_compact_layer on the FP8 GEMMs (mla_amd/csrc/prefill_f8.hip): every projection input is quantised per row into the engine's
+        code / scale buffers (mla_quant_fp8_rows) and multiplied with the W8 codes; norms, attention, cache and residual stream are bf16."""
+        H, D, ws, M = self.H, self.D, self._prefill_ws, B * S_p
+        ln1, qkv, wo, ln2, gu, wd = w
+
+        def quant(x):
+            K = x.shape[1]
+            return hip.quant_fp8_rows(x, self._prefill_xq[:M * K].view(M, K), self._prefill_xs)
+        ld = c.stride(-2)
+        xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
+        hip.gemm_prefill_f8_qkv_rope(*quant(xn), qkv.q, qkv.scale, c, ld, out_bs, S_p, (self.cos_p, self.sin_p, 2 * H), D, ws=ws)
+        o = self._prefill_attention(c, B, S_p, ld, out_bs)
+        h1 = torch.empty_like(h)
+        hip.gemm_prefill_f8(*quant(o), wo.q, wo.scale, h1, H, 0, M, residual=h, ws=ws)
+        xn2, _ = hip.rmsnorm_fwd(h1, ln2, self.eps)
+        act = torch.empty((M, gu.q.shape[0] // 2), dtype=torch.bfloat16, device=h.device)
+        hip.gemm_prefill_f8_gateup_swiglu(*quant(xn2), gu.q, gu.scale, act, ws=ws)
+        h = torch.empty_like(h1)
+        hip.gemm_prefill_f8(*quant(act), wd.q, wd.scale, h, H, 0, M, residual=h1, ws=ws)
         return h
 
     def _run(self):
@@ -513,14 +602,16 @@ class PrefixCachedEps(_CachedEpsBase):
 
     @classmethod
     def for_inputs(cls, vlm, input_ids, n_action_rows: int = 1, suffix_weights: str = "bf16", prefill: str = "train",
-                   suffix_attention: str = "head", **model_kwargs):
+                   suffix_attention: str = "head", prefill_precision: str = "bf16", **model_kwargs):
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
         check_suffix_attention(suffix_attention)
+        check_prefill_precision(prefill_precision, prefill)
         k = cls._splice_position(input_ids)
         # a handful of prompt lengths per process; each engine holds 0.4 GB at 7B
         eng = cls._engine(vlm, "_prefix_engines", (int(input_ids.shape[0]), k, int(n_action_rows), str(input_ids.device)),
-                          (n_action_rows, suffix_weights, prefill, suffix_attention), suffix_weights, prefill, suffix_attention)
+                          (n_action_rows, suffix_weights, prefill, suffix_attention, prefill_precision), suffix_weights, prefill,
+                          suffix_attention, prefill_precision)
         eng.prefill(input_ids, k, **model_kwargs)
         return eng
 
@@ -543,7 +634,7 @@ class PrefixCachedEps(_CachedEpsBase):
                     self.h_in = torch.zeros((B * self.R, H), dtype=bf16, device=dev)
                     self.h_out = torch.zeros((B * self.R, H), dtype=bf16, device=dev)
                     if self.prefill_mode == "compact":
-                        self._prefill_ws = self._compact_ws(B * S_p, dev)
+                        self._compact_buffers(B * S_p, dev)
                     if self.suffix_attention == "split":
                         need = hip.attn_split_ws_bytes(B, self.nheads, self.R, self.S_cap)
                         if need < 0:
@@ -839,21 +930,24 @@ class SampleGroupsEps(_RowGemmEps):
 
     @classmethod
     def for_inputs(cls, vlm, input_ids, n_action_rows: int, num_samples: int, suffix_weights: str = "bf16", prefill: str = "train",
-                   **model_kwargs):
+                   prefill_precision: str = "bf16", **model_kwargs):
         """-> (engine, prefilled for this observation; passes [(start, stop), ...] of plan_sample_groups). One engine -- and its graphs --
         per suffix_weights and prefill mode, as in PrefixCachedEps.for_inputs."""
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
+        check_prefill_precision(prefill_precision, prefill)
         k = PrefixCachedEps._splice_position(input_ids)
         passes = plan_sample_groups(num_samples, 1 + n_action_rows, cls.MAX_ROWS)
         capacity = max(stop - start for start, stop in passes)
         eng = cls._engine(vlm, "_prefix_engines_samples", (k, int(n_action_rows), capacity, str(input_ids.device)),
-                          (n_action_rows, capacity, suffix_weights, prefill), suffix_weights, prefill)
+                          (n_action_rows, capacity, suffix_weights, prefill, prefill_precision), suffix_weights, prefill,
+                          prefill_precision=prefill_precision)
         eng.prefill(input_ids, k, **model_kwargs)
         return eng, passes
 
-    def __init__(self, vlm, n_action_rows: int, capacity: int, suffix_weights: str = "bf16", prefill: str = "train"):
-        super().__init__(vlm, n_action_rows, suffix_weights, prefill)
+    def __init__(self, vlm, n_action_rows: int, capacity: int, suffix_weights: str = "bf16", prefill: str = "train",
+                 prefill_precision: str = "bf16"):
+        super().__init__(vlm, n_action_rows, suffix_weights, prefill, prefill_precision=prefill_precision)
         self.capacity = int(capacity)
         self._graphs = {}            # G -> captured pass over G groups
         self._graphs_packed = None   # the weights those graphs hold the addresses of
@@ -884,7 +978,7 @@ class SampleGroupsEps(_RowGemmEps):
                     self._h_out = torch.zeros((rows, H), dtype=bf16, device=dev)
                     self.slot = torch.full((self.capacity,), S_p, dtype=torch.int32, device=dev)
                     if self.prefill_mode == "compact":
-                        self._prefill_ws = self._compact_ws(S_p, dev)
+                        self._compact_buffers(S_p, dev)
                 self.set_groups(self.capacity)
             assert (S_p, H) == (self.S_p, self.H)
             weights = self._weights()

@@ -329,10 +329,11 @@ class MLA(nn.Module):
 
     # ---- what the four sampling entry points share (called as MLA._check_modes: the mode errors come before `self` is touched)
     @staticmethod
-    def _check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps):
-        from .infer import check_prefill, check_sampler, check_suffix_attention, check_suffix_weights
+    def _check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision="bf16"):
+        from .infer import check_prefill, check_prefill_precision, check_sampler, check_suffix_attention, check_suffix_weights
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
+        check_prefill_precision(prefill_precision, prefill)
         check_sampler(sampler, reuse_prefix, use_ddim, num_ddim_steps)
         check_suffix_attention(suffix_attention, reuse_prefix)
 
@@ -395,7 +396,8 @@ class MLA(nn.Module):
                             unnorm_key: Optional[str] = None, cfg_scale: float = 0.0, use_ddim: bool = True, num_ddim_steps: int = 8,
                             action_dim: int = 7, *, input_ids: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                             camera_name: str = "rlbench_front", reuse_prefix: bool = True, suffix_weights: str = "bf16",
-                            prefill: str = "train", sampler: str = "host", suffix_attention: str = "head", **kwargs) -> np.ndarray:
+                            prefill: str = "train", sampler: str = "host", suffix_attention: str = "head",
+                            prefill_precision: str = "bf16", **kwargs) -> np.ndarray:
         """model_mla.py:592-775: 8-step DDIM (eta = 0) over the action chunk with the VLM as the epsilon model, then
         un-normalisation.
         * ``image`` is a PIL image / uint8 HWC frame (pre-processed here like the reference does, :656-660) or an already
@@ -428,9 +430,17 @@ class MLA(nn.Module):
         16 queries) (mla_attn_decode / mla_attn_chunk); "split" cuts every head's key range over several workgroups and merges the partial
         softmax states in a fixed order with a second launch (mla_attn_chunk_split with the library's plan): the same function up to
         summation order. It composes with every ``suffix_weights``, ``prefill`` and ``sampler`` mode; it raises ValueError for an unknown
-        value, and for "split" when ``reuse_prefix=False`` or the cached-prefix engine does not serve the shape: no silent fallback."""
+        value, and for "split" when ``reuse_prefix=False`` or the cached-prefix engine does not serve the shape: no silent fallback.
+        ``prefill_precision`` (opt-in, ``prefill="compact"`` only): "bf16" (default) | "fp8": the four projections of every prefill layer
+        run over e4m3fn codes of BOTH operands on the K = 128 MFMA (mla_amd/csrc/prefill_f8.hip) -- the model's FP8 weight copy (one per
+        model, shared with ``suffix_weights="fp8"``) and the projection inputs quantised per row; attention, cache and residual stream
+        stay bf16 | "fp8_as_bf16": the bf16 compact kernels on the dequantised weight codes and on quantised-and-dequantised inputs --
+        the same function as "fp8" up to rounding, and what the format costs on a checkpoint. The effect on a trained policy is not
+        measured. It composes with every ``suffix_weights``, ``sampler`` and ``suffix_attention`` mode; it raises ValueError for an
+        unknown value and for anything but "bf16" unless ``prefill="compact"`` (hence also when ``reuse_prefix=False``): there is never
+        a silent bf16 prefill."""
         from .infer import PrefixCachedEps, sampler_needs_engine, suffix_attention_needs_engine
-        MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps)
+        MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision)
         if prefill != "train" and not reuse_prefix:
             raise ValueError(f"prefill={prefill!r} needs the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has no "
                              "separate prefill")
@@ -461,7 +471,7 @@ class MLA(nn.Module):
             suffix_attention_needs_engine(suffix_attention, T)
         if reuse_prefix:
             eps_model = PrefixCachedEps.for_inputs(self.vlm, n_action_rows=T, suffix_weights=suffix_weights, prefill=prefill,
-                                                   suffix_attention=suffix_attention, **model_kwargs)
+                                                   suffix_attention=suffix_attention, prefill_precision=prefill_precision, **model_kwargs)
         samples = self._sample(eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs)
         return self._actions([samples[:1].float().cpu().numpy()], unnorm_key)[0]
 
@@ -471,7 +481,7 @@ class MLA(nn.Module):
                                   input_ids=None, noise: Optional[torch.Tensor] = None, camera_name: str = "rlbench_front",
                                   reuse_prefix: bool = True, suffix_weights: str = "bf16",
                                   num_samples: Optional[int] = None, prefill: str = "train", sampler: str = "host",
-                                  suffix_attention: str = "head") -> np.ndarray:
+                                  suffix_attention: str = "head", prefill_precision: str = "bf16") -> np.ndarray:
         """B observations -> [B, T, action_dim]: by definition B independent `predict_action_diff` calls (the reference's
         `predict_action_batch`, model_mla.py:994, is dead code), computed on ONE cached prefix pass per DDIM step
         (mla_amd/infer.py:BatchedPrefixCachedEps): the prompts may have different lengths, the FPS start indices are drawn once per chunk.
@@ -493,16 +503,23 @@ class MLA(nn.Module):
         engine does not serve the shape.
         ``prefill``: only "train" -- the batched prefill has B x S rows and belongs to the training GEMMs; "compact" raises
         NotImplementedError (use predict_action_diff / predict_action_diff_samples per observation).
+        ``prefill_precision``: only "bf16", for the same reason; "fp8" / "fp8_as_bf16" raise NotImplementedError, an unknown value
+        ValueError.
         ``sampler``: predict_action_diff's, with and without ``num_samples``: "device" runs every pass's DDIM loop on the device (the same
         bits) and raises ValueError where "host" would loop over whole-forward calls (``reuse_prefix=False``, a shape the batched engine
         does not serve) or run the DDPM sampler.
         ``suffix_attention``: predict_action_diff's, forwarded for B = 1; B >= 2 with "split" raises NotImplementedError (the ragged and
         groups engines keep their own attention launches)."""
-        from .infer import BatchedPrefixCachedEps, sampler_needs_engine, suffix_attention_single_only
+        from .infer import BatchedPrefixCachedEps, check_prefill_precision, sampler_needs_engine, suffix_attention_single_only
         MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps)
+        check_prefill_precision(prefill_precision)                           # an unknown value only: no mode but "bf16" is served here
         if prefill != "train":
             raise NotImplementedError(f"prefill={prefill!r}: the batched engines prefill B x S rows on the training GEMMs; the compact "
                                       "prefill serves one observation (predict_action_diff, predict_action_diff_samples)")
+        if prefill_precision != "bf16":
+            raise NotImplementedError(f"prefill_precision={prefill_precision!r}: the batched engines prefill B x S rows on the training "
+                                      "GEMMs; the compact prefill serves one observation (predict_action_diff, "
+                                      "predict_action_diff_samples)")
         B = len(images)
         if B != 1:
             suffix_attention_single_only(suffix_attention, f"predict_action_diff_batch with {B} observations")
@@ -589,7 +606,8 @@ class MLA(nn.Module):
                                     num_ddim_steps: int = 8, action_dim: int = 7, *, input_ids: Optional[torch.Tensor] = None,
                                     noise: Optional[torch.Tensor] = None, camera_name: str = "rlbench_front",
                                     reuse_prefix: bool = True, suffix_weights: str = "bf16", prefill: str = "train",
-                                    sampler: str = "host", suffix_attention: str = "head") -> np.ndarray:
+                                    sampler: str = "host", suffix_attention: str = "head",
+                                    prefill_precision: str = "bf16") -> np.ndarray:
         """N action chunks for ONE observation -> [N, T, action_dim]: by definition N independent `predict_action_diff` calls on the same
         observation with the initial samples ``noise[n]`` (critic / best-of-N choice, uncertainty estimates, temporal ensembling), computed
         on ONE cached prefix (mla_amd/infer.py:SampleGroupsEps): the encoders and the decoder prefill run once per call, every sampler step
@@ -610,9 +628,12 @@ class MLA(nn.Module):
         Forwarded for ``num_samples=1``; raises ValueError when ``reuse_prefix=False``, the shared-prefix engine does not serve the shape,
         ``use_ddim=False`` or ``num_ddim_steps=None``.
         ``suffix_attention``: predict_action_diff's, forwarded for ``num_samples=1``; more samples with "split" raise NotImplementedError
-        (the groups engine keeps mla_attn_chunk_groups)."""
+        (the groups engine keeps mla_attn_chunk_groups).
+        ``prefill_precision`` (opt-in, ``prefill="compact"`` only): predict_action_diff's modes; "fp8" runs the projections of the one
+        prefill of the call over e4m3fn codes of both operands. Forwarded for ``num_samples=1``; raises ValueError for an unknown value
+        and for anything but "bf16" unless ``prefill="compact"``."""
         from .infer import SampleGroupsEps, sampler_needs_engine, suffix_attention_single_only
-        MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps)
+        MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision)
         if int(num_samples) != 1:
             suffix_attention_single_only(suffix_attention, f"predict_action_diff_samples with num_samples={num_samples}")
         if prefill != "train" and not reuse_prefix:
@@ -632,7 +653,7 @@ class MLA(nn.Module):
                                             camera_name=camera_name, **kw)
         if N == 1:
             return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, prefill=prefill, sampler=sampler,
-                       suffix_attention=suffix_attention)[None]
+                       suffix_attention=suffix_attention, prefill_precision=prefill_precision)[None]
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
                              "bf16 weights only")
@@ -658,7 +679,8 @@ class MLA(nn.Module):
         model_kwargs = {"images": self._image_batch(image, device), "point_cloud": self._pointcloud_batch(pointcloud, device),
                         "camera_name": camera_name, "proprio": self._proprio_token(cur_robot_state, unnorm_key, device)}
         x0 = self._draw_x0([None if noise is None else noise[n:n + 1] for n in range(N)], T, action_dim, device)
-        eng, passes = SampleGroupsEps.for_inputs(self.vlm, input_ids, T, N, suffix_weights=suffix_weights, prefill=prefill, **model_kwargs)
+        eng, passes = SampleGroupsEps.for_inputs(self.vlm, input_ids, T, N, suffix_weights=suffix_weights, prefill=prefill,
+                                                 prefill_precision=prefill_precision, **model_kwargs)
         out = []
         for start, stop in passes:                                           # one prefill, then the passes' sampler loops one after the other
             eng.set_groups(stop - start)

@@ -32,11 +32,13 @@
                                                           with bf16 and with fp8 suffix weights; --kernel-table adds
                                                           mla_attn_chunk_ragged_groups per launch against mla_attn_chunk_groups run per sample
     python tools/bench_infer.py --pair-prefill [--pairs P] [--chunk C] [--kernel-table]
-                                                          prefill="train" and prefill="compact" alternating in one process, in pairs, with
-                                                          bf16 and with fp8 suffix weights: per-chunk latency, the whole prefill (encoders +
-                                                          decoder rows) and the decoder rows alone, with the 95 % interval of the pair
-                                                          differences; --kernel-table adds the four projections of a 7B layer at the
-                                                          prefix's row count, training kernel vs compact kernel, per launch
+                                                          prefill="train", prefill="compact" and prefill="compact" with
+                                                          prefill_precision="fp8" alternating in one process, with bf16 and with fp8 suffix
+                                                          weights: per-chunk latency, the whole prefill (encoders + decoder rows) and the
+                                                          decoder rows alone, with the 95 % interval of the pair differences (compact -
+                                                          train, fp8 - compact, fp8 - train); --kernel-table adds the four projections of a
+                                                          7B layer at the prefix's row count, training kernel vs compact kernel vs FP8
+                                                          compact kernel (and the activation quantiser it needs), per launch
     python tools/bench_infer.py --pair-sampler [--pairs P] [--chunks C[,C..]]
                                                           sampler="host" and sampler="device" chunks alternating in one process, in pairs,
                                                           for every chunk length (default 1,16) with bf16 and with fp8 suffix weights:
@@ -130,7 +132,7 @@ def main():
                     "--samples: B[,B..] paired with N[,N..]")
     ap.add_argument("--suffix-weights", choices=["bf16", "fp8", "fp8_as_bf16"], default="bf16")
     ap.add_argument("--pair-fp8", action="store_true", help="alternate bf16 and fp8 chunks in one process, in pairs")
-    ap.add_argument("--pair-prefill", action="store_true", help="alternate prefill=\"train\" and prefill=\"compact\" in one process, in pairs")
+    ap.add_argument("--pair-prefill", action="store_true", help="alternate prefill=\"train\", \"compact\" and \"compact\" with prefill_precision=\"fp8\" in one process")
     ap.add_argument("--pair-sampler", action="store_true", help="alternate sampler=\"host\" and sampler=\"device\" in one process, in pairs")
     ap.add_argument("--pair-attention", action="store_true", help="alternate suffix_attention=\"head\" and \"split\" in one process, in pairs")
     ap.add_argument("--pairs", type=int, default=6)
@@ -436,8 +438,10 @@ def main_pair_attention(args):
 
 
 def main_pair_prefill(args):
-    """prefill="train" vs prefill="compact" on the same box, alternating: (a) predict_action_diff per chunk with bf16 and with fp8 suffix
-    weights, (b) engine.prefill() = encoders + the decoder rows of the prefix, (c) the decoder rows alone on given prefix rows."""
+    """prefill="train" vs prefill="compact" vs prefill="compact" with prefill_precision="fp8" (arm "fp8") on the same box, alternating:
+    (a) predict_action_diff per chunk with bf16 and with fp8 suffix weights, (b) engine.prefill() = encoders + the decoder rows of the
+    prefix, (c) the decoder rows alone on given prefix rows. The chunks of one suffix_weights mode are measured before the other's: three
+    engines at a time (a model keeps four)."""
     from mla_amd import hip, ops
     from mla_amd.infer import PrefixCachedEps
     m, b, ids = _setup(args)
@@ -446,16 +450,16 @@ def main_pair_prefill(args):
     image, pc, state = _observation(b)
     kw = dict(image=image, pointcloud=pc, cur_robot_state=state, input_ids=ids, num_ddim_steps=args.steps, noise=noise)
     mk = dict(input_ids=ids, **_engine_kw(b))
-    modes, weights = ("train", "compact"), ("bf16", "fp8")
-    acts = {(w, mode): m.predict_action_diff(suffix_weights=w, prefill=mode, **kw) for w in weights for mode in modes}   # engines, graphs
+    arms = {"train": dict(prefill="train"), "compact": dict(prefill="compact"), "fp8": dict(prefill="compact", prefill_precision="fp8")}
+    modes, weights = tuple(arms), ("bf16", "fp8")
     k = PrefixCachedEps._splice_position(ids)
     with torch.inference_mode():
-        eng = {mode: PrefixCachedEps.for_inputs(m.vlm, n_action_rows=args.chunk, prefill=mode, **mk) for mode in modes}
+        eng = {mode: PrefixCachedEps.for_inputs(m.vlm, n_action_rows=args.chunk, **arms[mode], **mk) for mode in modes}
         prefix = eng["train"]._prefix_rows(ids, k, mk["images"], mk["point_cloud"], mk["camera_name"], mk["proprio"])
     S_p, H = eng["train"].S_p, eng["train"].H
 
     def chunk_ms(w, mode):
-        return _time_ms(lambda: m.predict_action_diff(suffix_weights=w, prefill=mode, **kw), args.iters)
+        return _time_ms(lambda: m.predict_action_diff(suffix_weights=w, **arms[mode], **kw), args.iters)
 
     def timed(fn, reps=3):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -471,7 +475,7 @@ def main_pair_prefill(args):
     def layers_only(mode):
         e = eng[mode]
         h = prefix.reshape(S_p, H)
-        if mode == "compact":
+        if mode != "train":
             return lambda: e._compact_prefill(h, 1, S_p, e.cache, e.cache[0].stride(0))
 
         def train():
@@ -483,30 +487,38 @@ def main_pair_prefill(args):
     chunk = {(w, mode): [] for w in weights for mode in modes}
     prefill = {mode: [] for mode in modes}
     layers = {mode: [] for mode in modes}
-    for _ in range(args.pairs):                                             # train, compact, train, compact, ...: same box, interleaved
-        for w in weights:
+    acts = {}
+    for w in weights:                                                       # train, compact, fp8, train, ...: same box, interleaved
+        for mode in modes:
+            acts[(w, mode)] = m.predict_action_diff(suffix_weights=w, **arms[mode], **kw)     # engines, graphs
+        for _ in range(args.pairs):
             for mode in modes:
                 chunk[(w, mode)].append(chunk_ms(w, mode))
+    for _ in range(args.pairs):
         for mode in modes:
             prefill[mode].append(timed(lambda: eng[mode].prefill(ids, k, **{a: v for a, v in mk.items() if a != "input_ids"})))
         for mode in modes:
             layers[mode].append(timed(layers_only(mode)))
     rel = lambda a, b: round(float(((a - b) ** 2).sum() ** 0.5 / (b ** 2).sum() ** 0.5), 4)
-    out = {"metric": "predict_action_diff, MLA-Llama2-7B, batch 1: prefill=train vs prefill=compact in alternating pairs",
+    diffs = (("compact", "train"), ("fp8", "compact"), ("fp8", "train"))
+    out = {"metric": "predict_action_diff, MLA-Llama2-7B, batch 1: prefill=train vs prefill=compact vs prefill=compact + "
+                     "prefill_precision=fp8 (arm \"fp8\") in alternating order",
            "action_chunk": args.chunk, "prefix_rows": S_p, "ddim_steps": args.steps, "pairs": args.pairs, "unit": "ms",
            "chunk_ms": {f"{w}/{mode}": [round(v, 2) for v in vs] for (w, mode), vs in chunk.items()},
-           "chunk_compact_minus_train": {w: _pair_stats(chunk[(w, "train")], chunk[(w, "compact")]) for w in weights},
+           **{f"chunk_{b}_minus_{a}": {w: _pair_stats(chunk[(w, a)], chunk[(w, b)]) for w in weights} for b, a in diffs},
            "prefill_with_encoders_ms": {mode: [round(v, 2) for v in vs] for mode, vs in prefill.items()},
-           "prefill_with_encoders_compact_minus_train": _pair_stats(prefill["train"], prefill["compact"]),
+           **{f"prefill_with_encoders_{b}_minus_{a}": _pair_stats(prefill[a], prefill[b]) for b, a in diffs},
            "decoder_rows_only_ms": {mode: [round(v, 2) for v in vs] for mode, vs in layers.items()},
-           "decoder_rows_only_compact_minus_train": _pair_stats(layers["train"], layers["compact"]),
+           **{f"decoder_rows_only_{b}_minus_{a}": _pair_stats(layers[a], layers[b]) for b, a in diffs},
            "compact_vs_train_chunk_rel_diff_random_weights": {w: rel(acts[(w, "compact")], acts[(w, "train")]) for w in weights},
+           "fp8_vs_compact_chunk_rel_diff_random_weights": {w: rel(acts[(w, "fp8")], acts[(w, "compact")]) for w in weights},
            "data": "synthetic"}
     if args.kernel_table:
         # the four projections of a layer at the prefix's row count, cycling through the 32 layers' weights (nothing stays in the caches),
         # captured into a graph as a run of launches: training kernel vs compact kernel, us per launch
         packed = eng["train"]._weights()
-        ws = eng["compact"]._prefill_ws
+        packed8 = eng["fp8"]._prefill_layers()                                  # per layer (ln1, W8 qkv, W8 o, ln2, W8 gate|up, W8 down)
+        ws, ws8 = eng["compact"]._prefill_ws, eng["fp8"]._prefill_ws
         I = packed[0][6].shape[0]
         xh = (torch.randn(S_p, H, device=dev) * 0.5).to(torch.bfloat16)
         xi = (torch.randn(S_p, I, device=dev) * 0.5).to(torch.bfloat16)
@@ -515,26 +527,39 @@ def main_pair_prefill(args):
         oh = torch.empty(S_p, H, dtype=torch.bfloat16, device=dev)
         act = torch.empty(S_p, I, dtype=torch.bfloat16, device=dev)
         cos, sin = eng["train"].cos_p, eng["train"].sin_p
+        (xh8, xhs), (xi8, xis) = hip.quant_fp8_rows(xh), hip.quant_fp8_rows(xi)
+        # per form: training kernel, compact kernel (both on the packed bf16 layer L), FP8 compact kernel on the layer's W8 tuple, and
+        # the activation quantiser the FP8 launch needs in front of it (mla_quant_fp8_rows on the projection's input rows)
         forms = {
             "qkv_rope": (lambda L: hip.gemm_qkv_rope(xh, ops.cat_view(L[1:4]), qkv, cos, sin, S_p, 2 * H),
-                         lambda L: hip.gemm_prefill_qkv_rope(xh, ops.cat_view(L[1:4]), qkv, 3 * H, 0, S_p, (cos, sin, 2 * H), 128, ws=ws)),
+                         lambda L: hip.gemm_prefill_qkv_rope(xh, ops.cat_view(L[1:4]), qkv, 3 * H, 0, S_p, (cos, sin, 2 * H), 128, ws=ws),
+                         lambda L: hip.gemm_prefill_f8_qkv_rope(xh8, xhs, L[1].q, L[1].scale, qkv, 3 * H, 0, S_p, (cos, sin, 2 * H), 128,
+                                                                ws=ws8),
+                         lambda L: hip.quant_fp8_rows(xh, xh8, xhs)),
             "o_res": (lambda L: hip.gemm(xh, L[4], oh, residual=res),
-                      lambda L: hip.gemm_prefill(xh, L[4], oh, H, 0, S_p, residual=res, ws=ws)),
+                      lambda L: hip.gemm_prefill(xh, L[4], oh, H, 0, S_p, residual=res, ws=ws),
+                      lambda L: hip.gemm_prefill_f8(xh8, xhs, L[2].q, L[2].scale, oh, H, 0, S_p, residual=res, ws=ws8),
+                      lambda L: hip.quant_fp8_rows(xh, xh8, xhs)),
             "gateup_swiglu": (lambda L: hip.gemm_gateup_swiglu(xh, ops.cat_view(L[6:8]), False),
-                              lambda L: hip.gemm_prefill_gateup_swiglu(xh, ops.cat_view(L[6:8]), act, ws=ws)),
+                              lambda L: hip.gemm_prefill_gateup_swiglu(xh, ops.cat_view(L[6:8]), act, ws=ws),
+                              lambda L: hip.gemm_prefill_f8_gateup_swiglu(xh8, xhs, L[4].q, L[4].scale, act, ws=ws8),
+                              lambda L: hip.quant_fp8_rows(xh, xh8, xhs)),
             "down_res": (lambda L: hip.gemm(xi, L[8], oh, residual=res),
-                         lambda L: hip.gemm_prefill(xi, L[8], oh, H, 0, S_p, residual=res, ws=ws)),
+                         lambda L: hip.gemm_prefill(xi, L[8], oh, H, 0, S_p, residual=res, ws=ws),
+                         lambda L: hip.gemm_prefill_f8(xi8, xis, L[5].q, L[5].scale, oh, H, 0, S_p, residual=res, ws=ws8),
+                         lambda L: hip.quant_fp8_rows(xi, xi8, xis)),
         }
         table = {}
         for name, fns in forms.items():
             cell = {}
-            for kname, fn in zip(modes, fns):
-                for L in packed[:2]:
+            for kname, fn in zip(("train", "compact", "fp8", "fp8_input_quantiser"), fns):
+                layers_w = packed8 if kname == "fp8" else packed
+                for L in layers_w[:2]:
                     fn(L)
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    for L in packed:
+                    for L in layers_w:
                         fn(L)
                 g.replay()
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -547,6 +572,9 @@ def main_pair_prefill(args):
             N, K = {"qkv_rope": (3 * H, H), "o_res": (H, H), "gateup_swiglu": (2 * I, H), "down_res": (H, I)}[name]
             p = hip.plan_gemm_prefill(S_p, N, K)
             cell["compact_plan"] = {"split": p.split, "workgroups": p.workgroups}
+            p8 = hip.plan_gemm_prefill_f8(S_p, N, K)
+            cell["fp8_plan"] = {"split": p8.split, "workgroups": p8.workgroups}
+            cell["fp8_tflops"] = round(2.0 * S_p * N * K / (cell["fp8"] * 1e-6) / 1e12, 1)
             cell["compact_tflops"] = round(2.0 * S_p * N * K / (cell["compact"] * 1e-6) / 1e12, 1)
             cell["train_tflops"] = round(2.0 * S_p * N * K / (cell["train"] * 1e-6) / 1e12, 1)
             table[name] = cell
