@@ -428,7 +428,7 @@ int mla_gemm_prefill_qkv_rope(const void* x, long long ldx, const void* W, long 
 int mla_gemm_prefill_gateup_swiglu(const void* x, long long ldx, const void* wgu, long long ldw, void* act, long long ldo,
                                    long long out_batch_stride, int rows_per_batch, int M, int I, int K, void* workspace,
                                    size_t workspace_bytes, mla_stream_t stream);
-/* ---- the same family over FP8 codes (opt-in prefill_precision="fp8"; mla_amd/csrc/prefill_f8.hip): xq [M, K] and Wq [N, K] are e4m3fn
+/* ---- the same kernels over FP8 codes (opt-in prefill_precision="fp8"; OpF8 of mla_amd/csrc/prefill.hip): xq [M, K], Wq [N, K] are e4m3fn
  * codes with one fp32 scale per row (x_scale [M], w_scale [N]), exactly what mla_quant_fp8_rows writes. out[m, n] =
  * bf16((sum_k xq[m, k] Wq[n, k]) * x_scale[m] * w_scale[n] ...): the sums run over the unscaled codes in fp32 on
  * v_mfma_f32_16x16x128_f8f6f4, the two scales are applied to the finished sum, in that order, BEFORE the rotation (the partner channel

@@ -1088,9 +1088,29 @@ def gemm_suffix_w8(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, re
                  w_scale, rope_pos=rope_pos, rope_rows=rope_rows)
 
 
-# ---- compact prefill GEMMs (mla_amd/csrc/prefill.hip): 1 <= M <= 1024 rows, 64 x 128 tiles, deterministic split-K through a workspace
+# ---- compact prefill GEMMs (mla_amd/csrc/prefill.hip): 1 <= M <= 1024 rows, 64 x 128 tiles, deterministic split-K through a workspace. Two
+# operand kinds: bf16 x and W, or ("_f8" names) e4m3fn codes of BOTH operands with one fp32 scale per row (quant_fp8_rows) on
+# v_mfma_f32_16x16x128_f8f6f4; a K tile is 64 bf16 or 128 codes
 PREFILL_MMAX, PREFILL_BM, PREFILL_BN, PREFILL_BK = 1024, 64, 128, 64
+PREFILL_F8_BK = 128
 PREFILL_MAX_SPLIT, PREFILL_MIN_KTILES = 16, 8
+
+
+class PrefillKind(NamedTuple):
+    """An operand kind: what follows "gemm_prefill" in its Python and library names, K granularity, K tile, operand dtype."""
+    infix: str
+    k_gran: int
+    k_tile: int
+    dtype: torch.dtype
+
+    def ws_bytes(self, M: int, N: int, K: int) -> int:
+        """Workspace bytes the library's launcher needs for the shape (mla_gemm_prefill[_f8]_ws_bytes); -1 outside the contract."""
+        return int(getattr(lib(), f"mla_gemm_prefill{self.infix}_ws_bytes")(int(M), int(N), int(K)))
+
+
+PREFILL_KINDS = {"bf16": PrefillKind("", 32, PREFILL_BK, torch.bfloat16),
+                 "fp8": PrefillKind("_f8", PREFILL_F8_BK, PREFILL_F8_BK, torch.float8_e4m3fn)}
+_PF_BF16, _PF_F8 = PREFILL_KINDS["bf16"], PREFILL_KINDS["fp8"]
 
 
 class PrefillGemmPlan(NamedTuple):
@@ -1106,22 +1126,17 @@ class PrefillGemmPlan(NamedTuple):
     note: str
 
 
-def gemm_prefill_fits(M: int, N: int, K: int) -> bool:
-    """True when the compact prefill GEMMs accept the shape: 1 <= M <= 1024, N % 128 == 0 (2 I for the SwiGLU form), K % 32 == 0."""
-    return 1 <= M <= PREFILL_MMAX and N >= PREFILL_BN and N % PREFILL_BN == 0 and K >= 32 and K % 32 == 0
+def _prefill_fits(kind, M, N, K):
+    return 1 <= M <= PREFILL_MMAX and N >= PREFILL_BN and N % PREFILL_BN == 0 and K >= kind.k_gran and K % kind.k_gran == 0
 
 
-def plan_gemm_prefill(M: int, N: int, K: int, cus: int = 256) -> PrefillGemmPlan:
-    """Pure-Python mirror of the launcher's choice (prefill.hip:prefill_plan; mla_gemm_prefill_plan returns the library's): 64 x 128
-    tiles, split-K doubled while tiles x split < 2 x cus, split < 16 and every slice keeps at least 8 K tiles of 64."""
-    if not gemm_prefill_fits(M, N, K):
-        raise ValueError(f"plan_gemm_prefill: 1 <= M <= {PREFILL_MMAX}, N % {PREFILL_BN} == 0, K % 32 == 0 required (M {M}, N {N}, K {K})")
-    return _prefill_plan(M, N, K, -(-K // PREFILL_BK), cus)
-
-
-def _prefill_plan(M, N, K, ktiles, cus):
-    """The split-K rule both prefill GEMM families share, on `ktiles` K tiles (of 64 bf16 or 128 FP8 codes)."""
-    mt, nt = -(-M // PREFILL_BM), N // PREFILL_BN
+def _prefill_plan(kind, M, N, K, cus):
+    """The launcher's choice (prefill.hip:plan) for an operand kind: 64 x 128 tiles, split-K doubled while tiles x split < 2 x cus,
+    split < 16 and every slice keeps at least 8 K tiles."""
+    if not _prefill_fits(kind, M, N, K):
+        raise ValueError(f"plan_gemm_prefill{kind.infix}: 1 <= M <= {PREFILL_MMAX}, N % {PREFILL_BN} == 0, K % {kind.k_gran} == 0 required "
+                         f"(M {M}, N {N}, K {K})")
+    mt, nt, ktiles = -(-M // PREFILL_BM), N // PREFILL_BN, -(-K // kind.k_tile)
     tiles = mt * nt
     split = 1
     while tiles * split < 2 * cus and split < PREFILL_MAX_SPLIT and ktiles // (split * 2) >= PREFILL_MIN_KTILES:
@@ -1135,129 +1150,110 @@ def _prefill_plan(M, N, K, ktiles, cus):
     return PrefillGemmPlan(PREFILL_BM, PREFILL_BN, split, wgs, mt * PREFILL_BM, split * mt * PREFILL_BM * N * 4 if split > 1 else 0, note)
 
 
+def gemm_prefill_fits(M: int, N: int, K: int) -> bool:
+    """True when the compact prefill GEMMs accept the shape: 1 <= M <= 1024, N % 128 == 0 (2 I for the SwiGLU form), K % 32 == 0."""
+    return _prefill_fits(_PF_BF16, M, N, K)
+
+
+def gemm_prefill_f8_fits(M: int, N: int, K: int) -> bool:
+    """As gemm_prefill_fits, over codes: K % 128 == 0."""
+    return _prefill_fits(_PF_F8, M, N, K)
+
+
+def plan_gemm_prefill(M: int, N: int, K: int, cus: int = 256) -> PrefillGemmPlan:
+    """Pure-Python mirror of the launcher's choice on K tiles of 64 bf16 (mla_gemm_prefill_plan returns the library's)."""
+    return _prefill_plan(_PF_BF16, M, N, K, cus)
+
+
+def plan_gemm_prefill_f8(M: int, N: int, K: int, cus: int = 256) -> PrefillGemmPlan:
+    """As plan_gemm_prefill, on K tiles of 128 codes (mla_gemm_prefill_f8_plan returns the library's)."""
+    return _prefill_plan(_PF_F8, M, N, K, cus)
+
+
 def gemm_prefill_ws_bytes(M: int, N: int, K: int) -> int:
     """Workspace bytes the library's launcher needs for the shape (mla_gemm_prefill_ws_bytes); -1 outside the contract."""
-    return int(lib().mla_gemm_prefill_ws_bytes(int(M), int(N), int(K)))
+    return _PF_BF16.ws_bytes(M, N, K)
 
 
-def _prefill_common(name, x, W, out, ws):
-    _req(x, torch.bfloat16, f"{name} x")
-    _req(W, torch.bfloat16, f"{name} W")
+def gemm_prefill_f8_ws_bytes(M: int, N: int, K: int) -> int:
+    """As gemm_prefill_ws_bytes, over codes (mla_gemm_prefill_f8_ws_bytes)."""
+    return _PF_F8.ws_bytes(M, N, K)
+
+
+def _prefill(form, scales, x, W, out, ldo, out_batch_stride, rows_per_batch, ws, residual=None, out_col=0, rope=None, head_dim=128):
+    """One launch of the family in the form "" (plain + residual), "_qkv_rope" or "_gateup_swiglu", over bf16 operands x [M, K] / W [N, K]
+    (scales None) or over their FP8 codes with scales = (x_scale [M], w_scale [N])."""
+    kind, q = (_PF_BF16, "") if scales is None else (_PF_F8, "q")
+    name = f"gemm_prefill{kind.infix}{form}"
+    _req(x, kind.dtype, f"{name} x{q}")
+    _req(W, kind.dtype, f"{name} W{q}")
+    for t, what in zip(scales or (), ("x_scale", "w_scale")):
+        _req(t, torch.float32, f"{name} {what}")
     _req(out, torch.bfloat16, f"{name} out")
     assert x.dim() == 2 and W.dim() == 2 and W.shape[1] == x.shape[1] and x.stride(1) == 1 and W.stride(1) == 1
+    operands = [_p(x), x.stride(0), _p(W), W.stride(0)]
+    if scales is not None:
+        x_scale, w_scale = scales
+        assert x_scale.numel() == x.shape[0] and x_scale.is_contiguous() and w_scale.numel() == W.shape[0] and w_scale.is_contiguous()
+        operands = [*operands[:2], _p(x_scale), *operands[2:], _p(w_scale)]
     if ws is not None:
         assert ws.is_cuda and ws.is_contiguous()
-    return _p(ws), (ws.numel() * ws.element_size() if ws is not None else 0)
+    (M, K), N = x.shape, W.shape[0]
+    if form == "_qkv_rope":
+        cos, sin, rope_cols = rope
+        _req(cos, torch.float32, f"{name} cos")
+        _req(sin, torch.float32, f"{name} sin")
+        assert cos.shape == (rows_per_batch, 64) and sin.shape == cos.shape and cos.is_contiguous() and sin.is_contiguous()
+        shape = [M, N, K, _p(cos), _p(sin), int(rope_cols), int(head_dim)]
+    elif form == "_gateup_swiglu":
+        assert N % 2 == 0
+        ldo, rows_per_batch = out.stride(0) if ldo is None else ldo, M if rows_per_batch is None else rows_per_batch
+        shape = [M, N // 2, K]
+    else:
+        if residual is not None:
+            _req(residual, torch.bfloat16, f"{name} residual")
+            assert residual.shape[0] == M and residual.stride(1) == 1
+        shape = [_p(residual), residual.stride(0) if residual is not None else 0, M, N, K]
+    call(f"mla_{name}" + ("_bf16" if name == "gemm_prefill" else ""), *operands, c_void_p(out.data_ptr() + 2 * out_col), ldo, out_batch_stride,
+         rows_per_batch, *shape, _p(ws), ws.numel() * ws.element_size() if ws is not None else 0)
 
 
 def gemm_prefill(x, W, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, ws=None):
     """out row m (at out + (m // rows_per_batch) * out_batch_stride + (m % rows_per_batch) * ldo + out_col) = x[m] @ W^T (+ residual[m])
     for 1 <= M <= 1024 rows (mla_gemm_prefill_bf16). `out` is a base tensor: only its data pointer is used. ws: caller-owned scratch of
     at least gemm_prefill_ws_bytes(M, N, K) bytes (any dtype; may be None when the plan does not split)."""
-    wp, wb = _prefill_common("gemm_prefill", x, W, out, ws)
-    M, K = x.shape
-    if residual is not None:
-        _req(residual, torch.bfloat16, "gemm_prefill residual")
-        assert residual.shape[0] == M and residual.stride(1) == 1
-    call("mla_gemm_prefill_bf16", _p(x), x.stride(0), _p(W), W.stride(0), c_void_p(out.data_ptr() + 2 * out_col), ldo, out_batch_stride,
-         rows_per_batch, _p(residual), residual.stride(0) if residual is not None else 0, M, W.shape[0], K, wp, wb)
+    _prefill("", None, x, W, out, ldo, out_batch_stride, rows_per_batch, ws, residual=residual, out_col=out_col)
 
 
 def gemm_prefill_qkv_rope(x, W, out, ldo, out_batch_stride, rows_per_batch, rope, head_dim=128, ws=None):
     """gemm_prefill's rows and addressing with the rotary embedding of columns [0, rope_cols) in the epilogue (mla_gemm_prefill_qkv_rope):
     rope = (cos [rows_per_batch, 64] fp32, sin, rope_cols); row m is rotated with table row m % rows_per_batch, per head of 128."""
-    wp, wb = _prefill_common("gemm_prefill_qkv_rope", x, W, out, ws)
-    cos, sin, rope_cols = rope
-    _req(cos, torch.float32, "gemm_prefill_qkv_rope cos")
-    _req(sin, torch.float32, "gemm_prefill_qkv_rope sin")
-    assert cos.shape == (rows_per_batch, 64) and sin.shape == cos.shape and cos.is_contiguous() and sin.is_contiguous()
-    M, K = x.shape
-    call("mla_gemm_prefill_qkv_rope", _p(x), x.stride(0), _p(W), W.stride(0), _p(out), ldo, out_batch_stride, rows_per_batch, M, W.shape[0], K,
-         _p(cos), _p(sin), int(rope_cols), int(head_dim), wp, wb)
+    _prefill("_qkv_rope", None, x, W, out, ldo, out_batch_stride, rows_per_batch, ws, rope=rope, head_dim=head_dim)
 
 
 def gemm_prefill_gateup_swiglu(x, wgu, act, ldo=None, out_batch_stride=0, rows_per_batch=None, ws=None):
     """act[m] = silu(x[m] @ Wg^T) * (x[m] @ Wu^T) for the packed wgu = [Wg; Wu] [2 I, K] (mla_gemm_prefill_gateup_swiglu): the product is
     formed in the epilogue on the fp32 sums; nothing but act [M, I] is written. Addressing as gemm_prefill (default: act's own rows)."""
-    wp, wb = _prefill_common("gemm_prefill_gateup_swiglu", x, wgu, act, ws)
-    M, K = x.shape
-    assert wgu.shape[0] % 2 == 0
-    call("mla_gemm_prefill_gateup_swiglu", _p(x), x.stride(0), _p(wgu), wgu.stride(0), _p(act), act.stride(0) if ldo is None else ldo,
-         out_batch_stride, M if rows_per_batch is None else rows_per_batch, M, wgu.shape[0] // 2, K, wp, wb)
-
-
-# ---- FP8 compact prefill GEMMs (mla_amd/csrc/prefill_f8.hip): prefill.hip's tiles and split-K over e4m3fn codes of BOTH operands with one
-# fp32 scale per row (quant_fp8_rows), on v_mfma_f32_16x16x128_f8f6f4; a K tile is 128 codes
-PREFILL_F8_BK = 128
-
-
-def gemm_prefill_f8_fits(M: int, N: int, K: int) -> bool:
-    """True when the FP8 prefill GEMMs accept the shape: 1 <= M <= 1024, N % 128 == 0 (2 I for the SwiGLU form), K % 128 == 0."""
-    return 1 <= M <= PREFILL_MMAX and N >= PREFILL_BN and N % PREFILL_BN == 0 and K >= PREFILL_F8_BK and K % PREFILL_F8_BK == 0
-
-
-def plan_gemm_prefill_f8(M: int, N: int, K: int, cus: int = 256) -> PrefillGemmPlan:
-    """Pure-Python mirror of the FP8 launcher's choice (prefill_f8.hip:f8_plan; mla_gemm_prefill_f8_plan returns the library's):
-    plan_gemm_prefill's rule on K tiles of 128 codes."""
-    if not gemm_prefill_f8_fits(M, N, K):
-        raise ValueError(f"plan_gemm_prefill_f8: 1 <= M <= {PREFILL_MMAX}, N % {PREFILL_BN} == 0, K % {PREFILL_F8_BK} == 0 required "
-                         f"(M {M}, N {N}, K {K})")
-    return _prefill_plan(M, N, K, K // PREFILL_F8_BK, cus)
-
-
-def gemm_prefill_f8_ws_bytes(M: int, N: int, K: int) -> int:
-    """Workspace bytes the FP8 launcher needs for the shape (mla_gemm_prefill_f8_ws_bytes); -1 outside the contract."""
-    return int(lib().mla_gemm_prefill_f8_ws_bytes(int(M), int(N), int(K)))
-
-
-def _prefill_f8_common(name, xq, x_scale, Wq, w_scale, out, ws):
-    _req(xq, torch.float8_e4m3fn, f"{name} xq")
-    _req(Wq, torch.float8_e4m3fn, f"{name} Wq")
-    _req(x_scale, torch.float32, f"{name} x_scale")
-    _req(w_scale, torch.float32, f"{name} w_scale")
-    _req(out, torch.bfloat16, f"{name} out")
-    assert xq.dim() == 2 and Wq.dim() == 2 and Wq.shape[1] == xq.shape[1] and xq.stride(1) == 1 and Wq.stride(1) == 1
-    assert x_scale.numel() == xq.shape[0] and x_scale.is_contiguous() and w_scale.numel() == Wq.shape[0] and w_scale.is_contiguous()
-    if ws is not None:
-        assert ws.is_cuda and ws.is_contiguous()
-    return _p(ws), (ws.numel() * ws.element_size() if ws is not None else 0)
+    _prefill("_gateup_swiglu", None, x, wgu, act, ldo, out_batch_stride, rows_per_batch, ws)
 
 
 def gemm_prefill_f8(xq, x_scale, Wq, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, ws=None):
     """gemm_prefill over FP8 codes of both operands (mla_gemm_prefill_f8): out row m = bf16((xq[m] @ Wq^T) * x_scale[m] * w_scale
     (+ residual[m])), xq [M, K] / Wq [N, K] float8_e4m3fn and x_scale [M] / w_scale [N] fp32 as quant_fp8_rows writes them; the sums run
     over the codes in fp32. Addressing and ws as gemm_prefill, with gemm_prefill_f8_ws_bytes(M, N, K)."""
-    wp, wb = _prefill_f8_common("gemm_prefill_f8", xq, x_scale, Wq, w_scale, out, ws)
-    M, K = xq.shape
-    if residual is not None:
-        _req(residual, torch.bfloat16, "gemm_prefill_f8 residual")
-        assert residual.shape[0] == M and residual.stride(1) == 1
-    call("mla_gemm_prefill_f8", _p(xq), xq.stride(0), _p(x_scale), _p(Wq), Wq.stride(0), _p(w_scale), c_void_p(out.data_ptr() + 2 * out_col),
-         ldo, out_batch_stride, rows_per_batch, _p(residual), residual.stride(0) if residual is not None else 0, M, Wq.shape[0], K, wp, wb)
+    _prefill("", (x_scale, w_scale), xq, Wq, out, ldo, out_batch_stride, rows_per_batch, ws, residual=residual, out_col=out_col)
 
 
 def gemm_prefill_f8_qkv_rope(xq, x_scale, Wq, w_scale, out, ldo, out_batch_stride, rows_per_batch, rope, head_dim=128, ws=None):
-    """gemm_prefill_qkv_rope over FP8 codes (mla_gemm_prefill_f8_qkv_rope): both scales are applied to the fp32 sums before the rotation,
-    the partner channel with its own w_scale."""
-    wp, wb = _prefill_f8_common("gemm_prefill_f8_qkv_rope", xq, x_scale, Wq, w_scale, out, ws)
-    cos, sin, rope_cols = rope
-    _req(cos, torch.float32, "gemm_prefill_f8_qkv_rope cos")
-    _req(sin, torch.float32, "gemm_prefill_f8_qkv_rope sin")
-    assert cos.shape == (rows_per_batch, 64) and sin.shape == cos.shape and cos.is_contiguous() and sin.is_contiguous()
-    M, K = xq.shape
-    call("mla_gemm_prefill_f8_qkv_rope", _p(xq), xq.stride(0), _p(x_scale), _p(Wq), Wq.stride(0), _p(w_scale), _p(out), ldo, out_batch_stride,
-         rows_per_batch, M, Wq.shape[0], K, _p(cos), _p(sin), int(rope_cols), int(head_dim), wp, wb)
+    """gemm_prefill_qkv_rope over codes (mla_gemm_prefill_f8_qkv_rope): both scales are applied before the rotation, the partner channel
+    with its own w_scale."""
+    _prefill("_qkv_rope", (x_scale, w_scale), xq, Wq, out, ldo, out_batch_stride, rows_per_batch, ws, rope=rope, head_dim=head_dim)
 
 
 def gemm_prefill_f8_gateup_swiglu(xq, x_scale, wgu_q, w_scale, act, ldo=None, out_batch_stride=0, rows_per_batch=None, ws=None):
-    """gemm_prefill_gateup_swiglu over FP8 codes (mla_gemm_prefill_f8_gateup_swiglu): wgu_q = the packed [2 I, K] gate|up codes, w_scale
-    [2 I]; gate and up are scaled with the scales of their own rows before silu(gate) * up."""
-    wp, wb = _prefill_f8_common("gemm_prefill_f8_gateup_swiglu", xq, x_scale, wgu_q, w_scale, act, ws)
-    M, K = xq.shape
-    assert wgu_q.shape[0] % 2 == 0
-    call("mla_gemm_prefill_f8_gateup_swiglu", _p(xq), xq.stride(0), _p(x_scale), _p(wgu_q), wgu_q.stride(0), _p(w_scale), _p(act),
-         act.stride(0) if ldo is None else ldo, out_batch_stride, M if rows_per_batch is None else rows_per_batch, M, wgu_q.shape[0] // 2, K,
-         wp, wb)
+    """gemm_prefill_gateup_swiglu over codes (mla_gemm_prefill_f8_gateup_swiglu): wgu_q = the packed [2 I, K] gate|up codes, w_scale [2 I];
+    gate and up are scaled with the scales of their own rows before silu(gate) * up."""
+    _prefill("_gateup_swiglu", (x_scale, w_scale), xq, wgu_q, act, ldo, out_batch_stride, rows_per_batch, ws)
 
 
 # --------------------------------------------------------------------------------------------- device-resident DDIM loop (sampler.hip)

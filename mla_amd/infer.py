@@ -28,7 +28,7 @@ second launch -- for every R; the same function up to summation order.
 
 Opt-in (`prefill="compact"`, `prefill_precision="fp8"`, see PREFILL_MODES / PREFILL_PRECISION_MODES; PrefixCachedEps and SampleGroupsEps):
 the prefix rows of one observation run on the row-sized GEMMs of csrc/prefill.hip, and with "fp8" their four projections per layer on
-e4m3fn codes of weights AND activations (csrc/prefill_f8.hip, the K = 128 FP8 MFMA) -- the same FP8 weight copy the suffix pass streams.
+e4m3fn codes of weights AND activations (csrc/prefill.hip, the K = 128 FP8 MFMA) -- the same FP8 weight copy the suffix pass streams.
 
 Semantics vs the reference: identical arithmetic up to summation order (fp32 accumulation everywhere), with ONE stated difference -- the
 reference's point tokenizer draws fresh random FPS start indices inside every one of the 8 forwards (Point_PN.py:10); here they are
@@ -81,7 +81,7 @@ def check_prefill(mode):
 
 # What the compact prefill's four projections per layer compute on (MLA.predict_action_diff(prefill="compact", prefill_precision=...)):
 #   "bf16"         the bf16 weights and activations as they are (default)
-#   "fp8"          e4m3fn codes of BOTH operands on the K = 128 MFMA (mla_amd/csrc/prefill_f8.hip): the model's FP8 weight copy (one scale
+#   "fp8"          e4m3fn codes of BOTH operands on the K = 128 MFMA (mla_amd/csrc/prefill.hip): the model's FP8 weight copy (one scale
 #                  per output channel, shared with suffix_weights="fp8") and the projection inputs quantised per row (hip.quant_fp8_rows);
 #                  attention, cache, norms and residual stream stay bf16
 #   "fp8_as_bf16"  the bf16 compact kernels on bf16(code * scale) of the same weight codes, the projection inputs quantised and
@@ -359,11 +359,11 @@ class _CachedEpsBase:
         projection inputs' codes and scales."""
         H, I = self.cfg.hidden_size, self.cfg.intermediate_size
         fp8 = self.prefill_precision == "fp8"
-        ws_bytes = hip.gemm_prefill_f8_ws_bytes if fp8 else hip.gemm_prefill_ws_bytes
-        need = [ws_bytes(rows, N, K) for N, K in ((3 * H, H), (H, H), (2 * I, H), (H, I))]
+        kind = hip.PREFILL_KINDS["fp8" if fp8 else "bf16"]
+        need = [kind.ws_bytes(rows, N, K) for N, K in ((3 * H, H), (H, H), (2 * I, H), (H, I))]
         if min(need) < 0:
             raise ValueError(f"prefill=\"compact\": the projections of this model (hidden {H}, intermediate {I}) are outside the compact "
-                             f"GEMMs' contract (N % 128 == 0, K % {hip.PREFILL_F8_BK if fp8 else 32} == 0); use prefill=\"train\"")
+                             f"GEMMs' contract (N % 128 == 0, K % {kind.k_gran} == 0); use prefill=\"train\"")
         self._prefill_ws = torch.empty(max(max(need), 16), dtype=torch.uint8, device=dev)
         if fp8:
             self._prefill_xq = torch.empty(rows * max(H, I), dtype=torch.float8_e4m3fn, device=dev)
@@ -385,26 +385,36 @@ class _CachedEpsBase:
     def _compact_layer(self, w, h, B, S_p, c, out_bs):
         """One decoder layer of the compact prefill on its weights w (an entry of _prefill_layers()) -> the layer's output rows: rmsnorm_fwd,
         q|k|v + RoPE into the cache c, the training flash attention on the cache's q / k / v views, o + residual, rmsnorm_fwd, gate|up +
-        SwiGLU (the product only), down + residual. "fp8": _compact_layer_fp8. "fp8_as_bf16": the same launches on the dequantised weights,
-        every projection input quantised and dequantised per row."""
-        if self.prefill_precision == "fp8":
-            return self._compact_layer_fp8(w, h, B, S_p, c, out_bs)
-        H, nh, D, ws = self.H, self.nheads, self.D, self._prefill_ws
-        fq = _fake_quant_rows if self.prefill_precision == "fp8_as_bf16" else (lambda x: x)
-        ln1, wq, wk, wv, wo, ln2, wg, wu, wd = w
-        wqkv, wgu = ops.cat_view((wq, wk, wv)), ops.cat_view((wg, wu))
-        assert wqkv is not None and wgu is not None, "the packed weights are adjacent in memory (_weights)"
+        SwiGLU (the product only), down + residual. The precision only decides how a projection's input and weight are presented:
+        "bf16" as they are; "fp8_as_bf16" the dequantised weights, every input quantised and dequantised per row; "fp8" the W8 codes and
+        scales, every input quantised per row into the engine's code / scale buffers (mla_quant_fp8_rows) for the GEMMs over codes.
+        Norms, attention, cache and residual stream are bf16 throughout."""
+        H, D, ws, M, precision = self.H, self.D, self._prefill_ws, B * S_p, self.prefill_precision
+        if precision == "fp8":
+            ln1, wqkv, wo, ln2, wgu, wd = w
+            plain, qkv_rope, gateup_swiglu = hip.gemm_prefill_f8, hip.gemm_prefill_f8_qkv_rope, hip.gemm_prefill_f8_gateup_swiglu
+        else:
+            ln1, wq, wk, wv, wo, ln2, wg, wu, wd = w
+            wqkv, wgu = ops.cat_view((wq, wk, wv)), ops.cat_view((wg, wu))
+            assert wqkv is not None and wgu is not None, "the packed weights are adjacent in memory (_weights)"
+            plain, qkv_rope, gateup_swiglu = hip.gemm_prefill, hip.gemm_prefill_qkv_rope, hip.gemm_prefill_gateup_swiglu
+
+        def operands(x, W):
+            if precision == "fp8":
+                K = x.shape[1]
+                return (*hip.quant_fp8_rows(x, self._prefill_xq[:M * K].view(M, K), self._prefill_xs), W.q, W.scale)
+            return (_fake_quant_rows(x) if precision == "fp8_as_bf16" else x), W
         ld = c.stride(-2)
         xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
-        hip.gemm_prefill_qkv_rope(fq(xn), wqkv, c, ld, out_bs, S_p, (self.cos_p, self.sin_p, 2 * H), D, ws=ws)
+        qkv_rope(*operands(xn, wqkv), c, ld, out_bs, S_p, (self.cos_p, self.sin_p, 2 * H), D, ws=ws)
         o = self._prefill_attention(c, B, S_p, ld, out_bs)
         h1 = torch.empty_like(h)
-        hip.gemm_prefill(fq(o), wo, h1, H, 0, B * S_p, residual=h, ws=ws)
+        plain(*operands(o, wo), h1, H, 0, M, residual=h, ws=ws)
         xn2, _ = hip.rmsnorm_fwd(h1, ln2, self.eps)
-        act = torch.empty((B * S_p, wg.shape[0]), dtype=torch.bfloat16, device=h.device)
-        hip.gemm_prefill_gateup_swiglu(fq(xn2), wgu, act, ws=ws)
+        act = torch.empty((M, self.cfg.intermediate_size), dtype=torch.bfloat16, device=h.device)
+        gateup_swiglu(*operands(xn2, wgu), act, ws=ws)
         h = torch.empty_like(h1)
-        hip.gemm_prefill(fq(act), wd, h, H, 0, B * S_p, residual=h1, ws=ws)
+        plain(*operands(act, wd), h, H, 0, M, residual=h1, ws=ws)
         return h
 
     def _prefill_attention(self, c, B, S_p, ld, out_bs):
@@ -413,28 +423,6 @@ class _CachedEpsBase:
         o = [hip.attn_fwd(*(flat[b * out_bs + j * H:] for j in range(3)), 1, S_p, self.nheads, self.D, ld, None, 1.0 / math.sqrt(self.D))[0]
              for b in range(B)]
         return o[0] if B == 1 else torch.cat(o, 0)
-
-    def _compact_layer_fp8(self, w, h, B, S_p, c, out_bs):
-        """_compact_layer on the FP8 GEMMs (mla_amd/csrc/prefill_f8.hip): every projection input is quantised per row into the engine's
-        code / scale buffers (mla_quant_fp8_rows) and multiplied with the W8 codes; norms, attention, cache and residual stream are bf16."""
-        H, D, ws, M = self.H, self.D, self._prefill_ws, B * S_p
-        ln1, qkv, wo, ln2, gu, wd = w
-
-        def quant(x):
-            K = x.shape[1]
-            return hip.quant_fp8_rows(x, self._prefill_xq[:M * K].view(M, K), self._prefill_xs)
-        ld = c.stride(-2)
-        xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
-        hip.gemm_prefill_f8_qkv_rope(*quant(xn), qkv.q, qkv.scale, c, ld, out_bs, S_p, (self.cos_p, self.sin_p, 2 * H), D, ws=ws)
-        o = self._prefill_attention(c, B, S_p, ld, out_bs)
-        h1 = torch.empty_like(h)
-        hip.gemm_prefill_f8(*quant(o), wo.q, wo.scale, h1, H, 0, M, residual=h, ws=ws)
-        xn2, _ = hip.rmsnorm_fwd(h1, ln2, self.eps)
-        act = torch.empty((M, gu.q.shape[0] // 2), dtype=torch.bfloat16, device=h.device)
-        hip.gemm_prefill_f8_gateup_swiglu(*quant(xn2), gu.q, gu.scale, act, ws=ws)
-        h = torch.empty_like(h1)
-        hip.gemm_prefill_f8(*quant(act), wd.q, wd.scale, h, H, 0, M, residual=h1, ws=ws)
-        return h
 
     def _run(self):
         if _USE_GRAPH and not self._graph_failed:

@@ -432,7 +432,7 @@ class MLA(nn.Module):
         summation order. It composes with every ``suffix_weights``, ``prefill`` and ``sampler`` mode; it raises ValueError for an unknown
         value, and for "split" when ``reuse_prefix=False`` or the cached-prefix engine does not serve the shape: no silent fallback.
         ``prefill_precision`` (opt-in, ``prefill="compact"`` only): "bf16" (default) | "fp8": the four projections of every prefill layer
-        run over e4m3fn codes of BOTH operands on the K = 128 MFMA (mla_amd/csrc/prefill_f8.hip) -- the model's FP8 weight copy (one per
+        run over e4m3fn codes of BOTH operands on the K = 128 MFMA (mla_amd/csrc/prefill.hip) -- the model's FP8 weight copy (one per
         model, shared with ``suffix_weights="fp8"``) and the projection inputs quantised per row; attention, cache and residual stream
         stay bf16 | "fp8_as_bf16": the bf16 compact kernels on the dequantised weight codes and on quantised-and-dequantised inputs --
         the same function as "fp8" up to rounding, and what the format costs on a checkpoint. The effect on a trained policy is not

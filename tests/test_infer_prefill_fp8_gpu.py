@@ -1,5 +1,5 @@
 """GPU: the opt-in FP8 prefill of the cached-prefix engines (MLA.predict_action_diff(prefill="compact", prefill_precision="fp8"),
-mla_amd/infer.py _compact_layer_fp8 on the GEMMs of mla_amd/csrc/prefill_f8.hip) against its yardstick "fp8_as_bf16" (the bf16 compact
+mla_amd/infer.py _compact_layer on the GEMMs of mla_amd/csrc/prefill.hip) against its yardstick "fp8_as_bf16" (the bf16 compact
 kernels on the dequantised codes), an fp32 statement of the fake-quantised decoder layer, and the bf16 compact prefill; the default paths
 stay bit for bit what they were. Tiny model (hidden 256, intermediate 512, 9 layers, 2 heads of 128), windows 1 and 15."""
 import numpy as np

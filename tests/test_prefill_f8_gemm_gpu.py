@@ -1,4 +1,4 @@
-"""GPU: the FP8 prefill GEMMs (mla_amd/csrc/prefill_f8.hip: mla_gemm_prefill_f8 / _qkv_rope / _gateup_swiglu; e4m3fn codes of both operands
+"""GPU: the FP8 prefill GEMMs (mla_amd/csrc/prefill.hip: mla_gemm_prefill_f8 / _qkv_rope / _gateup_swiglu; e4m3fn codes of both operands
 on v_mfma_f32_16x16x128_f8f6f4, one fp32 scale per row of either operand applied to the finished sums).
 
 1. Exact: integer codes in [-8, 8] with unit scales give integer sums below 2^24 -- the output is bf16(integer product) bit for bit. This

@@ -1,5 +1,5 @@
 """CPU: the FP8 prefill's host side -- the `prefill_precision` argument of the samplers, the launch plan of the FP8 prefill GEMMs
-(mla_amd/csrc/prefill_f8.hip; hip.plan_gemm_prefill_f8 mirrors the launcher, mla_gemm_prefill_f8_plan is the launcher's own answer), their
+(mla_amd/csrc/prefill.hip; hip.plan_gemm_prefill_f8 mirrors the launcher, mla_gemm_prefill_f8_plan is the launcher's own answer), their
 argument checks, and the quantiser fact the exact GPU test rests on. Nothing here launches a kernel."""
 import ctypes
 
