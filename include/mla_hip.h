@@ -466,7 +466,8 @@ int mla_ddim_step(float* x, const void* eps, void* x_bf16, const float* coef, in
 int mla_sampler_rows(void* h_in, const void* t_table, const void* x_e, const int* step, int G, int T, int H, int steps,
                      mla_stream_t stream);
 
-/* ---- split-key suffix attention (mla_amd/infer.py PrefixCachedEps, opt-in suffix_attention="split"; mla_amd/csrc/attn_split.hip):
+/* ---- split-key suffix attention (mla_amd/infer.py: PrefixCachedEps, opt-in suffix_attention="split"; the multi-row engines, opt-in
+ * groups_attention="split": mla_attn_groups_split below; mla_amd/csrc/attn_split.hip):
  * mla_attn_chunk's contract -- packed post-RoPE q|k|v cache, the last R rows of S_kv are the queries, query r sees keys
  * [0, S_kv - R + r], 1 <= R <= 64, any S_kv >= R, head_dim 128, B >= 1, P rounded to bf16 before P V -- with every head's key range read
  * by several workgroups instead of one per 16 queries.
@@ -488,11 +489,29 @@ int mla_sampler_rows(void* h_in, const void* t_table, const void* x_e, const int
  *     pass; below one pass a cut saves nothing), so every range keeps at least 2 tiles; 1 when twice the unsplit grid no longer fits the
  *     chip. Pure host function.
  *   mla_attn_chunk_split_ws_bytes: B H R splits 130 fp32 words for splits > 1 (0 = the plan's), 0 for splits == 1, -1 outside the
- *     contract. Pure host function. */
+ *     contract. Pure host function.
+ *   mla_attn_groups_split: the split for the multi-row engines (opt-in groups_attention="split"). Addressing and masking are exactly
+ *     mla_attn_chunk_groups' (prefix_len == NULL: B must be 1, S_p_or_cap = S_p) or mla_attn_chunk_ragged_groups' (prefix_len int32 [B] on
+ *     the device, S_p_or_cap = S_cap, S_p[b] = clamp(prefix_len[b], 0, S_cap - G R)): query (b, g, p) sees the logical keys
+ *     0 .. S_p[b] + p, logical key j is memory row j (j < S_p[b]) or j + g R, output row (b G + g) R + p; G = 1 with prefix_len[b] =
+ *     kv_len[b] - R is mla_attn_chunk_ragged. Per (b, g) the nT_b = ceil((S_p[b] + R) / 64) logical key tiles are cut as
+ *     mla_attn_chunk_split cuts them (same ranges, wave order, state, combine launch with B G as its samples), so a (b, g) block with
+ *     splits <= nT_b is bit for bit mla_attn_chunk_split (B = 1, the same splits) on cat(prefix rows of b, rows of group g). `splits` is
+ *     fixed on the host and nT_b derived on the device: grid, LDS and workspace do not depend on the lengths; a sample with
+ *     nT_b < splits gives its trailing ranges no tile and they write the empty state; range 0 always holds key 0. Plan and workspace are
+ *     mla_attn_chunk_split_plan / _ws_bytes at (B G, H, R, S_max), S_max = S_p + R without prefix_len and S_cap - (G - 1) R with it;
+ *     splits = 0 resolves to that plan, valid values are 0 .. ceil(S_max / 64). When splits resolves to 1 the call IS the head form
+ *     (mla_attn_chunk_groups / mla_attn_chunk_ragged_groups in the library's default launch form): its bits, no workspace access, no
+ *     second launch. One group per workgroup only. Everything else -- ws ownership and alignment, no allocation / state / counters /
+ *     atomics / waiting, graph capture, all argument checks on the host before any launch, masked and padding loads clamped inside the
+ *     query's own key set -- as for mla_attn_chunk_split. 1 <= R <= 64, head_dim 128, 16-B aligned rows. */
 int mla_attn_chunk_split_plan(int B, int H, int R, int S_kv, int cus, int* out4);
 long long mla_attn_chunk_split_ws_bytes(int B, int H, int R, int S_kv, int splits);
 int mla_attn_chunk_split(const void* q, const void* k, const void* v, void* o, int B, int H, int head_dim, int S_kv, int R, long long ld,
                          long long batch_stride, long long ld_o, float scale, int splits, void* ws, size_t ws_bytes, mla_stream_t stream);
+int mla_attn_groups_split(const void* q, const void* k, const void* v, void* o, int B, int G, int H, int head_dim, const int* prefix_len,
+                          int S_p_or_cap, int R, long long ld, long long batch_stride, long long ld_o, float scale, int splits, void* ws,
+                          size_t ws_bytes, mla_stream_t stream);
 
 /* ---- losses: CrossEntropyLoss modeling_llama.py:1258-1269; InfoNCE models/mla/fuser/contrastive.py:208-215
  * mla_ce_fwd: lse[r] = logsumexp(logits[r, :ncols]), loss[r] = lse - logits[r, label] (0 for ignore_index or a label outside [0, ncols);

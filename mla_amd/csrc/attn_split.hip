@@ -8,6 +8,9 @@
 //                          order s = 0, 1, ..., divides once, rounds once. No counters, no atomics, no workgroup waits on another: the
 //                          dependency is the kernel boundary (~1.2 us), which in-launch combines measured dearer than.
 //                          splits == 1: launch 1 alone in its finishing form -- no workspace access, and mla_attn_chunk's bits.
+//   mla_attn_groups_split  the same two launches under the addressing of mla_attn_chunk_groups / mla_attn_chunk_ragged_groups (G groups of R
+//                          rows behind one prefix per sample, the prefix length optionally read on the device): opt-in
+//                          groups_attention="split" of the batched and N-sample calls. One split is the head form's own launch.
 //   mla_attn_chunk_split_plan / _ws_bytes   pure host functions: the launcher's choice of splits, and the workspace it needs.
 //
 // Nothing here allocates, keeps state between calls or reads a workspace word this call did not write: graph-capturable, deterministic.
@@ -61,158 +64,46 @@ inline SplitPlan sp_plan(int B, int H, int R, int S_kv, int cus, int forced) {
 // nT % splits ranges take one more). FINISH (splits == 1): the range is every tile, the trip count, the masks and the merge are
 // attn_chunk_kernel's, and so is every bit of o. Otherwise a wave whose tile lies behind the range skips the tile (it still meets the
 // barriers), and the merged, un-normalised state goes to ws: sums [(b H + h) R + r][s][128], then (m, l) [(b H + h) R + r][s][2].
+// GROUPS (mla_attn_groups_split, never with FINISH): attn_chunk_groups_kernel's addressing (infer.hip) under the same arithmetic. The
+// launch's "samples" are the B G (sample, group) pairs, S_kv arrives as S_p -- or, with prefix_len, is read from prefix_len[b] and clamped
+// to [0, S_cap - G R], one value per workgroup (readfirstlane), so trip and barrier counts stay uniform -- and a group's S_p + R logical
+// keys are tiled from key 0: logical key j is memory row j (j < S_p) or j + g R. ntiles then depends on the sample: a range behind the
+// sample's last tile has cnt == 0, skips the loop and writes the empty state. State and output rows need no map: (b G + g) is the sample
+// index of the layout above, and of the combine launch. The groups form is a kernel of its own over the same text
+// (attn_split_body.inc): the plain instantiations keep their argument list, and their code.
+template <bool GROUPS>
+struct SpRows {                                                         // memory row of logical key j: j, or behind the prefix j + g R
+  int S_p, goff;
+  __device__ __forceinline__ int operator()(int j) const { return j >= S_p ? j + goff : j; }
+};
+template <>
+struct SpRows<false> {
+  int S_p, goff;
+  __device__ __forceinline__ int operator()(int j) const { return j; }
+};
+struct SpGroups { int G; const int* prefix_len; int S_cap; };
+
 template <bool FINISH>
 __global__ __launch_bounds__(64 * SP_NW) void attn_chunk_split_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                                       const bf16_t* __restrict__ v, bf16_t* __restrict__ o, int H, int S_kv,
                                                                       int R, long long ld, long long bs, long long ld_o, float scale,
                                                                       int splits, float* __restrict__ ws, long long nstates) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int QB = (R + 15) >> 4;
-  const int s = FINISH ? 0 : (int)(blockIdx.x % splits);
-  const int wg = FINISH ? (int)blockIdx.x : (int)(blockIdx.x / splits);
-  const int qb = wg % QB, bh = wg / QB, h = bh % H, b = bh / H;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
-  bf16_t* vt = (bf16_t*)smem + wave * 128 * SP_VP;                    // this wave's V tile, transposed: [128 channels][SP_VP keys]
-  const bf16_t* kb = k + b * bs + h * 128;
-  const bf16_t* vb = v + b * bs + h * 128;
-  const int r = qb * 16 + li;
-  const bool qok = r < R;
-  const int qpos = S_kv - R + (qok ? r : R - 1);                       // last key this query sees (padding queries: the last row's)
-  const u32x4_t zero = {0u, 0u, 0u, 0u};
-  bf16x8_t qf[4];
-  {
-    const bf16_t* qr = q + b * bs + (long long)(S_kv - R + (qok ? r : 0)) * ld + h * 128;
-#pragma unroll
-    for (int ds = 0; ds < 4; ++ds) qf[ds] = as_frag(qok ? *(const u32x4_t*)(qr + ds * 32 + g * 8) : zero);
-  }
-  const float sc2 = scale * 1.4426950408889634f;
-  f32x4_t ot[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) ot[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  float m = -INFINITY, l = 0.f;
-  const int ntiles = (S_kv + 63) >> 6;
-  const int tbase = ntiles / splits, trem = ntiles % splits;
-  const int t0 = s * tbase + (s < trem ? s : trem), cnt = tbase + (s < trem ? 1 : 0);
-  const int iters = (cnt + SP_NW - 1) / SP_NW;
-  for (int it = 0; it < iters; ++it) {                                  // same trip count in every wave: the barriers below are uniform
-    const int tl = it * SP_NW + wave;                                   // tile of the range; behind it (FINISH: beyond S_kv): nothing visible
-    const bool live = tl < cnt;
-    const int j0 = (t0 + tl) * 64;
-    bf16x8_t pf0, pf1;
-    if (FINISH || live) {
-      u32x4_t kf[4][4], vv[16];
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        const int j = j0 + f * 16 + li;
-        const bf16_t* kr = kb + (long long)(j < S_kv ? j : S_kv - 1) * ld + g * 8;
-#pragma unroll
-        for (int ds = 0; ds < 4; ++ds) kf[f][ds] = *(const u32x4_t*)(kr + ds * 32);
-      }
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const int j = j0 + u * 4 + g;
-        vv[u] = *(const u32x4_t*)(vb + (long long)(j < S_kv ? j : S_kv - 1) * ld + li * 8);
-      }
-      f32x4_t st[4];
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        st[f] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ds = 0; ds < 4; ++ds) st[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(kf[f][ds]), qf[ds], st[f], 0, 0, 0);
-      }
-      // S^T[key][query]: lane holds query li, keys j0 + 16 f + 4 g + reg; key j visible iff j <= qpos (< S_kv)
-      float mx = -INFINITY;
-#pragma unroll
-      for (int f = 0; f < 4; ++f)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          if (j0 + f * 16 + g * 4 + rr > qpos) st[f][rr] = -INFINITY;
-          mx = fmaxf(mx, st[f][rr]);
-        }
-      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float mnew = fmaxf(m, mx * sc2);
-      const float msafe = mnew == -INFINITY ? 0.f : mnew;
-      const float alpha = __builtin_amdgcn_exp2f(m - msafe);
-      float ps = 0.f;
-#pragma unroll
-      for (int f = 0; f < 4; ++f)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          st[f][rr] = __builtin_amdgcn_exp2f(fmaf(st[f][rr], sc2, -msafe));
-          ps += st[f][rr];
-        }
-      ps += __shfl_xor(ps, 16, 64);
-      ps += __shfl_xor(ps, 32, 64);
-      l = l * alpha + ps;
-      m = mnew;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) ot[i] *= alpha;
-      pf0 = pack_pfrag(st[0], st[1]);
-      pf1 = pack_pfrag(st[2], st[3]);
-      // V tile -> LDS transposed (lane: key 4 u + g, channels 8 li .. + 7)
-#pragma unroll
-      for (int u = 0; u < 16; ++u)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          vt[(li * 8 + 2 * e) * SP_VP + u * 4 + g] = (bf16_t)(vv[u][e] & 0xffffu);
-          vt[(li * 8 + 2 * e + 1) * SP_VP + u * 4 + g] = (bf16_t)(vv[u][e] >> 16);
-        }
-    }
-    __syncthreads();
-    if (FINISH || live) {
-#pragma unroll
-      for (int fd = 0; fd < 8; ++fd) {
-        const bf16_t* vr = vt + (fd * 16 + li) * SP_VP + g * 4;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const u32x2_t lo = *(const u32x2_t*)(vr + ks * 32), hi = *(const u32x2_t*)(vr + ks * 32 + 16);
-          const u32x4_t av = {lo[0], lo[1], hi[0], hi[1]};
-          ot[fd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(av), ks ? pf1 : pf0, ot[fd], 0, 0, 0);
-        }
-      }
-    }
-    __syncthreads();
-  }
-  // merge the waves' (max, sum, O^T) in wave order; O^T[d][query] of wave w: lane (d & 15) >> 2 ... as the MFMA left it. The split form
-  // pads the query pitch to 17 words: its read-out below walks d on the lanes (coalesced state rows)
-  constexpr int QP = FINISH ? 16 : 17;
-  float* mo = (float*)smem;                                             // [SP_NW][128][QP]
-  float* ml = mo + SP_NW * 128 * QP;                                    // [SP_NW][16] max, then [SP_NW][16] sum
-#pragma unroll
-  for (int fd = 0; fd < 8; ++fd)
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) mo[(wave * 128 + fd * 16 + g * 4 + rr) * QP + li] = ot[fd][rr];
-  if (g == 0) { ml[wave * 16 + li] = m; ml[SP_NW * 16 + wave * 16 + li] = l; }
-  __syncthreads();
-  for (int e = threadIdx.x; e < 128 * 16; e += 64 * SP_NW) {
-    const int qq = FINISH ? (e & 15) : (e >> 7), d = FINISH ? (e >> 4) : (e & 127), rq = qb * 16 + qq;
-    if (rq >= R) continue;
-    float mm = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < SP_NW; ++w) mm = fmaxf(mm, ml[w * 16 + qq]);    // FINISH: finite -- wave 0's first tile holds key 0, seen by every query
-    if (!FINISH && mm == -INFINITY) mm = 0.f;                           // a range wholly behind the query's causal limit: every weight exp2(-inf) = 0
-    float L = 0.f, O = 0.f;
-#pragma unroll
-    for (int w = 0; w < SP_NW; ++w) {
-      const float fw = __builtin_amdgcn_exp2f(ml[w * 16 + qq] - mm);
-      L += fw * ml[SP_NW * 16 + w * 16 + qq];
-      O += fw * mo[(w * 128 + d) * QP + qq];
-    }
-    if (FINISH) {
-      o[(long long)(b * R + rq) * ld_o + h * 128 + d] = sp_finish(O, L);
-    } else {
-      const long long st = ((long long)bh * R + rq) * splits + s;
-      ws[st * 128 + d] = O;                                             // the empty state: O = 0, l = 0, m = -inf
-      if (d == 0) {
-        float mw = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < SP_NW; ++w) mw = fmaxf(mw, ml[w * 16 + qq]);
-        ws[nstates * 128 + st * 2] = mw;
-        ws[nstates * 128 + st * 2 + 1] = L;
-      }
-    }
-  }
+  constexpr bool GROUPS = false;
+  const SpGroups gr = {1, nullptr, 0};
+#include "attn_split_body.inc"
+}
+
+// launch 1 of mla_attn_groups_split (splits > 1 only: one split is the head form's own launch); S_kv is S_p without prefix_len
+__global__ __launch_bounds__(64 * SP_NW) void attn_groups_split_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+                                                                       const bf16_t* __restrict__ v, int G, int H, int S_kv, int R,
+                                                                       long long ld, long long bs, float scale, int splits,
+                                                                       float* __restrict__ ws, long long nstates,
+                                                                       const int* __restrict__ prefix_len, int S_cap) {
+  constexpr bool FINISH = false, GROUPS = true;
+  bf16_t* const o = nullptr;                                            // the combine launch writes o
+  const long long ld_o = 0;
+  const SpGroups gr = {G, prefix_len, S_cap};
+#include "attn_split_body.inc"
 }
 
 // one wave per (b, h, query): M = max_s m_s, numerator and denominator summed over s = 0, 1, ... with the weight exp2(m_s - M); an empty
@@ -299,5 +190,60 @@ extern "C" int mla_attn_chunk_split(const void* q, const void* k, const void* v,
     hipLaunchKernelGGL(attn_split_combine_kernel, dim3(p.cwgs), dim3(64 * SP_CW), 0, stream, (const float*)ws, (bf16_t*)o, H, R, ld_o, p.splits,
                        nrows);
   }
+  MLA_LAUNCH_CHECK();
+}
+
+// the head forms a single split resolves to (infer.hip)
+extern "C" int mla_attn_chunk_groups(const void* q, const void* k, const void* v, void* o, int G, int H, int head_dim, int S_p, int R, long long ld,
+                                     long long ld_o, float scale, hipStream_t stream);
+extern "C" int mla_attn_chunk_ragged_groups(const void* q, const void* k, const void* v, void* o, int B, int G, int H, int head_dim,
+                                            const int* prefix_len, int S_cap, int R, long long ld, long long batch_stride, long long ld_o,
+                                            float scale, hipStream_t stream);
+
+// mla_attn_chunk_groups' (prefix_len == nullptr: B == 1, S_p_or_cap = S_p) or mla_attn_chunk_ragged_groups' contract with the split of
+// mla_attn_chunk_split per (sample, group). Plan and workspace are mla_attn_chunk_split's at (B G, H, R, S_max), S_max the most logical keys
+// a group can have: the grid, the LDS and the workspace do not depend on the lengths in device memory.
+extern "C" int mla_attn_groups_split(const void* q, const void* k, const void* v, void* o, int B, int G, int H, int head_dim,
+                                     const int* prefix_len, int S_p_or_cap, int R, long long ld, long long batch_stride, long long ld_o,
+                                     float scale, int splits, void* ws, size_t ws_bytes, hipStream_t stream) {
+  const bool ragged = prefix_len != nullptr;
+  MLA_CHECK_ARG(q && k && v && o, "mla_attn_groups_split: null pointer");
+  MLA_CHECK_ARG(head_dim == 128, "mla_attn_groups_split: head_dim must be 128 (got %d)", head_dim);
+  MLA_CHECK_ARG(B >= 1 && G >= 1 && H >= 1 && R >= 1 && R <= SP_RMAX, "mla_attn_groups_split: B >= 1, G >= 1, 1 <= R <= 64 required (B %d, G %d, R %d)",
+                B, G, R);
+  MLA_CHECK_ARG((long long)B * G * R <= 0x7fffffffLL, "mla_attn_groups_split: B * G * R output rows exceed the int range (B %d, G %d, R %d)", B, G, R);
+  long long smax;
+  if (ragged) {
+    MLA_CHECK_ARG((long long)G * R <= (long long)S_p_or_cap, "mla_attn_groups_split: S_cap (%d) must hold the G * R suffix rows of a sample (G %d, R %d)",
+                  S_p_or_cap, G, R);
+    MLA_CHECK_ARG(batch_stride % 8 == 0, "mla_attn_groups_split: the sample stride is not 16-B aligned");
+    smax = (long long)S_p_or_cap - (long long)(G - 1) * R;
+  } else {
+    MLA_CHECK_ARG(B == 1, "mla_attn_groups_split: one sample without prefix_len (B %d)", B);
+    MLA_CHECK_ARG(S_p_or_cap >= 0, "mla_attn_groups_split: S_p >= 0 required (S_p %d)", S_p_or_cap);
+    MLA_CHECK_ARG((long long)S_p_or_cap + (long long)G * R <= 0x7fffffffLL, "mla_attn_groups_split: S_p + G * R rows exceed the int range (G %d, R %d, S_p %d)",
+                  G, R, S_p_or_cap);
+    smax = (long long)S_p_or_cap + R;
+  }
+  MLA_CHECK_ARG(AL16(q) && AL16(k) && AL16(v) && ld % 8 == 0 && ld_o % 2 == 0 && (((uintptr_t)o) & 3) == 0,
+                "mla_attn_groups_split: 16-B aligned rows required");
+  const int S_max = (int)smax, nT = (S_max + 63) / 64;
+  MLA_CHECK_ARG(splits >= 0 && splits <= nT, "mla_attn_groups_split: splits must be in [0, %d] (0 = the plan's) for at most %d keys per group, got %d", nT,
+                S_max, splits);
+  const SplitPlan p = sp_plan(B * G, H, R, S_max, SP_CUS, splits);
+  MLA_CHECK_ARG(p.wgs > 0, "mla_attn_groups_split: grid too large (B %d, G %d, H %d, splits %d)", B, G, H, p.splits);
+  if (p.splits == 1)                                                    // the head form itself: no workspace access, no second launch
+    return ragged ? mla_attn_chunk_ragged_groups(q, k, v, o, B, G, H, head_dim, prefix_len, S_p_or_cap, R, ld, batch_stride, ld_o, scale, stream)
+                  : mla_attn_chunk_groups(q, k, v, o, G, H, head_dim, S_p_or_cap, R, ld, ld_o, scale, stream);
+  MLA_CHECK_ARG(ws, "mla_attn_groups_split: splits %d needs a workspace (null)", p.splits);
+  MLA_CHECK_ARG(AL16(ws) && (long long)ws_bytes >= p.ws_bytes, "mla_attn_groups_split: workspace of %lld bytes (16-B aligned) needed for splits %d, got %lld",
+                p.ws_bytes, p.splits, (long long)ws_bytes);
+  const size_t lds = (size_t)SP_NW * 128 * SP_VP * 2;
+  const long long nrows = (long long)B * G * H * R;
+  (void)hipFuncSetAttribute((const void*)attn_groups_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(attn_groups_split_kernel, dim3(p.wgs), dim3(64 * SP_NW), lds, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, G, H,
+                     ragged ? 0 : S_p_or_cap, R, ld, ragged ? batch_stride : 0LL, scale, p.splits, (float*)ws, nrows * p.splits, prefix_len,
+                     ragged ? S_p_or_cap : 0);
+  hipLaunchKernelGGL(attn_split_combine_kernel, dim3(p.cwgs), dim3(64 * SP_CW), 0, stream, (const float*)ws, (bf16_t*)o, H, R, ld_o, p.splits, nrows);
   MLA_LAUNCH_CHECK();
 }

@@ -84,6 +84,8 @@ _SIGNATURES = {
     "mla_attn_chunk_split_ws_bytes": [c_int, c_int, c_int, c_int, c_int],      # returns long long (restype fixed up in lib())
     "mla_attn_chunk_split": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong,
                              c_float, c_int, c_void_p, c_size_t, c_void_p],
+    "mla_attn_groups_split": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_longlong, c_longlong,
+                              c_longlong, c_float, c_int, c_void_p, c_size_t, c_void_p],
     "mla_gemm_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                       c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
     "mla_gemm_bf16_ws": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -1350,6 +1352,58 @@ def attn_chunk_ragged_groups(cache, B, G, nheads, D, prefix_len, R, scale, gw=No
         call("mla_attn_chunk_ragged_groups", *args)
     else:
         call("mla_attn_chunk_ragged_groups_gw", *args, int(gw or 0), -1 if order is None else int(order))
+    return o
+
+
+def attn_groups_split_plan(B: int, G: int, H: int, R: int, S_p_or_cap: int, ragged: bool, cus: int = 256) -> tuple:
+    """(S_max, the library's plan) of mla_attn_groups_split for a groups shape: the plan is mla_attn_chunk_split_plan at (B * G, H, R,
+    S_max) -- (splits, tiles per split, workgroups, combine workgroups) -- and S_max the most logical keys a group can have: S_p + R for
+    one sample with S_p prefix rows (ragged=False, B must be 1), S_cap - (G - 1) * R for B samples of S_cap cache rows with their prefix
+    lengths in device memory (ragged=True)."""
+    B, G, R, S = int(B), int(G), int(R), int(S_p_or_cap)
+    if B < 1 or G < 1 or (not ragged and (B != 1 or S < 0)) or (ragged and S < G * R):
+        raise ValueError(f"attn_groups_split_plan: B, G >= 1, B == 1 and S_p >= 0 (plain) or S_cap >= G * R (ragged) required (B {B}, G {G}, "
+                         f"R {R}, S_p / S_cap {S}, ragged {bool(ragged)})")
+    S_max = S - (G - 1) * R if ragged else S + R
+    return S_max, attn_split_plan(B * G, H, R, S_max, cus)
+
+
+def attn_groups_split(cache, B, G, nheads, D, prefix, R, scale, splits=None, ws=None):
+    """attn_chunk_groups / attn_chunk_ragged_groups with every (sample, group)'s key tiles cut into `splits` ranges read by their own
+    workgroups and merged in a fixed order by a second launch (mla_attn_groups_split). prefix: an int S_p with cache [S_p + G * R, 3H] (or
+    with a leading 1; B must be 1), or an int32 device tensor [B] with cache [B, S_cap, 3H] (clamped to [0, S_cap - G * R]); G = 1 with
+    prefix = kv_len - R is attn_chunk_ragged. splits None = the library's plan (attn_groups_split_plan), fixed on the host whatever the
+    lengths; an explicit value (1 .. ceil(S_max / 64)) is for tests and the kernel table; 1 is the head form itself. A (b, g) block with
+    splits <= its own tile count is bit for bit attn_chunk_split (B = 1, the same splits) on cat(prefix rows of b, rows of group g).
+    ws: caller-owned scratch of at least attn_split_ws_bytes(B * G, nheads, R, S_max, splits) bytes; None allocates one for this call.
+    Returns o [B * G * R, nheads * D] bf16, row (b * G + g) * R + p."""
+    _req(cache, torch.bfloat16, "attn_groups_split cache")
+    H = nheads * D
+    ragged = isinstance(prefix, torch.Tensor)
+    if ragged:
+        _req(prefix, torch.int32, "attn_groups_split prefix")
+        assert cache.dim() == 3 and cache.shape[0] == B and cache.shape[2] == 3 * H and cache.stride(2) == 1 and G >= 1 and R >= 1
+        assert cache.shape[1] >= G * R and prefix.numel() == B and prefix.is_contiguous()
+        S, ld, bs = cache.shape[1], cache.stride(1), cache.stride(0)
+    else:
+        if cache.dim() == 3:
+            assert cache.shape[0] == 1
+            cache = cache[0]
+        S = int(prefix)
+        assert B == 1 and cache.dim() == 2 and cache.shape[1] == 3 * H and cache.stride(1) == 1 and G >= 1 and R >= 1 and S >= 0
+        assert cache.shape[0] >= S + G * R, (tuple(cache.shape), S, G, R)
+        ld, bs = cache.stride(0), 0
+    sp = 0 if splits is None else int(splits)
+    if ws is None:
+        need = attn_split_ws_bytes(B * G, nheads, R, S - (G - 1) * R if ragged else S + R, sp)
+        if need > 0:
+            ws = torch.empty(need, dtype=torch.uint8, device=cache.device)
+    else:
+        assert ws.is_cuda and ws.is_contiguous()
+    o = torch.empty((B * G * R, H), dtype=torch.bfloat16, device=cache.device)
+    base = cache.data_ptr()
+    call("mla_attn_groups_split", c_void_p(base), c_void_p(base + 2 * H), c_void_p(base + 4 * H), _p(o), B, G, nheads, D,
+         _p(prefix) if ragged else None, S, R, ld, bs, H, float(scale), sp, _p(ws), ws.numel() * ws.element_size() if ws is not None else 0)
     return o
 
 

@@ -24,7 +24,9 @@ device memory: no copy to the device and no host wait between the steps, bit for
 
 Opt-in (`suffix_attention="split"`, see SUFFIX_ATTENTION_MODES; PrefixCachedEps only): the attention launch of the suffix pass becomes
 `mla_attn_chunk_split` -- every head's key tiles cut over several workgroups, the partial softmax states merged in a fixed order by a
-second launch -- for every R; the same function up to summation order.
+second launch -- for every R; the same function up to summation order. The multi-row engines (BatchedPrefixCachedEps, SampleGroupsEps,
+BatchedSampleGroupsEps) take the same argument from the public `groups_attention="split"` (GROUPS_ATTENTION_MODES) and launch
+`mla_attn_groups_split`: that split per (sample, group), the prefix lengths still read on the device.
 
 Opt-in (`prefill="compact"`, `prefill_precision="fp8"`, see PREFILL_MODES / PREFILL_PRECISION_MODES; PrefixCachedEps and SampleGroupsEps):
 the prefix rows of one observation run on the row-sized GEMMs of csrc/prefill.hip, and with "fp8" their four projections per layer on
@@ -128,8 +130,36 @@ def suffix_attention_single_only(mode, route: str):
     attention launches."""
     if mode == "split":
         raise NotImplementedError(f"suffix_attention=\"split\": {route} runs the ragged / groups engines, whose attention launches "
-                                  "(mla_attn_chunk_ragged, mla_attn_chunk_groups and their batched forms) have no split-key form yet; "
-                                  "it serves predict_action_diff (one observation, one chunk) only")
+                                  "(mla_attn_chunk_ragged, mla_attn_chunk_groups and their batched forms) take their split-key form from "
+                                  "groups_attention=\"split\"; suffix_attention serves predict_action_diff (one observation, one chunk) only")
+
+
+# Which attention launch the sampler steps of the multi-row engines use (MLA.predict_action_diff_batch / predict_action_diff_samples
+# (groups_attention=...); BatchedPrefixCachedEps, SampleGroupsEps, BatchedSampleGroupsEps):
+#   "head"   mla_attn_chunk_ragged / mla_attn_chunk_groups / mla_attn_chunk_ragged_groups: one workgroup per (sample, group, head, 16
+#            queries) reads its whole key range (default)
+#   "split"  mla_attn_groups_split with the library's plan at the engine's capacity: the key tiles of every (sample, group, head) cut over
+#            several workgroups, the partial softmax states merged in a fixed order by a second launch; same function up to summation
+#            order. The plan splits for B * G <= 4 at R <= 16 and B * G <= 2 at 17 <= R <= 32 (32 heads, 256 CUs); beyond, it is the
+#            head launch by construction
+GROUPS_ATTENTION_MODES = ("head", "split")
+
+
+def check_groups_attention(mode, reuse_prefix=True):
+    """The argument errors of groups_attention=: an unknown value; "split" without the cached prefix. A shape the engine does not serve is
+    the caller's ValueError (groups_attention_needs_engine)."""
+    if mode not in GROUPS_ATTENTION_MODES:
+        raise ValueError(f"groups_attention must be one of {GROUPS_ATTENTION_MODES}, got {mode!r}")
+    if mode == "split" and not reuse_prefix:
+        raise ValueError("groups_attention=\"split\" runs on the cached-prefix engines (reuse_prefix=True); the whole-forward sampler has no "
+                         "suffix pass")
+
+
+def groups_attention_needs_engine(mode, engine: str, n_action_rows: int):
+    """groups_attention="split" on a shape the cached-prefix engine does not serve: an error, never the warned loop."""
+    if mode == "split":
+        raise ValueError(f"groups_attention=\"split\": the cached-prefix engine ({engine}) does not serve {1 + n_action_rows} suffix rows per "
+                         "sample at this head_dim; use groups_attention=\"head\"")
 
 
 # Who runs the DDIM loop around the suffix passes (MLA.predict_action_diff(sampler=...)):
@@ -772,6 +802,21 @@ class _RowGemmEps(_CachedEpsBase):
     def _attention(self, c, scale):
         raise NotImplementedError
 
+    def _split_workspace(self, B: int, G: int, S_p_or_cap: int, ragged: bool, dev):
+        """suffix_attention "split": the workspace of mla_attn_groups_split at the engine's capacity (B samples of G groups; S_p of the
+        one prefix, or S_cap with the lengths in device memory), allocated once beside h_in / h_out (call outside inference mode), and
+        attn_plan = (S_max, the library's plan there). Shorter prefixes need no more (the split count is fixed on the host), so one captured
+        graph serves every length mix of a bucket. Fewer groups on one prefix (set_groups) may: the plan cuts a smaller launch into more
+        ranges, so that form takes the largest need over 1 .. G groups."""
+        if self.suffix_attention != "split":
+            return
+        self.attn_plan = hip.attn_groups_split_plan(B, G, self.nheads, self.R, S_p_or_cap, ragged)
+        S_max = self.attn_plan[0]
+        need = max(hip.attn_split_ws_bytes(B * g, self.nheads, self.R, S_max) for g in (range(1, G + 1) if not ragged else (G,)))
+        if need < 0:
+            raise RuntimeError(f"mla_attn_chunk_split_ws_bytes: {hip.lib().mla_last_error().decode()}")
+        self._attn_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+
     def _proj(self, x, weights, out=None, residual=None):
         """x [M, K] @ W^T (+ residual): `weights` is a tuple of adjacent bf16 views (mla_gemm_suffix_bf16) or one W8 (mla_gemm_suffix_w8);
         out = a layer's cache: the q|k|v rows go to their samples' / groups' slots."""
@@ -837,6 +882,7 @@ class _RowGemmEps(_CachedEpsBase):
                     self.h_out = torch.zeros((rows, H), dtype=bf16, device=dev)
                     for name, values in index.items():
                         setattr(self, name, torch.zeros(len(values), dtype=torch.int32, device=dev))
+                    self._split_workspace(NB, G, self.S_cap, True, dev)
             assert (NB, G, H, sub.S_cap, sub.R) == (self.NB, self.G, self.H, self.S_cap, self.R) and S_pmax + G * self.R <= self.S_cap
             for name, values in index.items():
                 getattr(self, name).copy_(torch.tensor(values, dtype=torch.int32))
@@ -856,32 +902,41 @@ class BatchedPrefixCachedEps(_RowGemmEps):
     -- per (B, S_cap, R, device) serves every mix of prompt lengths in that capacity bucket."""
 
     @classmethod
-    def supports_batch(cls, vlm, n_action_rows: int) -> bool:
-        """head_dim 128 and at most 64 suffix rows per sample; otherwise the caller loops over whole-forward batch-1 calls (warns once)."""
+    def supports_batch(cls, vlm, n_action_rows: int, warn: bool = True) -> bool:
+        """head_dim 128 and at most 64 suffix rows per sample; otherwise the caller loops over whole-forward batch-1 calls (warns once;
+        warn=False: the plain predicate, for the callers that raise instead)."""
         return cls._serves(vlm, 1 + n_action_rows, cls.MAX_R, ("batch",), "BatchedPrefixCachedEps: {rows} suffix rows per sample (max {limit}) "
                            "/ head_dim {D} (needs 128) are beyond the batched cached-prefix kernels; sampling every observation with a whole "
-                           "forward per step")
+                           "forward per step", warn)
 
     @classmethod
     def for_batch(cls, vlm, ids_rows, n_action_rows: int, images=None, point_cloud=None, camera_name=None, proprio=None, add_tail=True,
-                  **unused):
+                  suffix_attention: str = "head", **unused):
         """Generator over the passes of one call: runs the encoders once over all samples, plans (plan_batch: ids_rows are the prompts as
         the caller has them, the prompt tail is handled there) and yields
-        (SubBatchPlan, prefilled engine) per sub-batch. Two sub-batches may share an engine: finish sampling one before taking the next."""
+        (SubBatchPlan, prefilled engine) per sub-batch. Two sub-batches may share an engine: finish sampling one before taking the next.
+        suffix_attention: "head" (mla_attn_chunk_ragged) or "split" (mla_attn_groups_split, one group per sample); one engine per mode."""
+        check_groups_attention(suffix_attention)
         front = cls._front_tokens(vlm, images, point_cloud, camera_name)
         for sub in plan_batch(ids_rows, n_action_rows, int(front.shape[1]), cls.MAX_ROWS, cls.BUCKET, add_tail=add_tail):
-            eng = cls._engine(vlm, "_prefix_engines_batched", (sub.stop - sub.start, sub.S_cap, sub.R, str(front.device)), (n_action_rows,))
+            eng = cls._engine(vlm, "_prefix_engines_batched", (sub.stop - sub.start, sub.S_cap, sub.R, str(front.device)),
+                              (n_action_rows, "bf16", "train", suffix_attention), suffix_attention=suffix_attention)
             eng.prefill(sub, front[sub.start:sub.stop], proprio[sub.start:sub.stop])
             yield sub, eng
 
     def prefill(self, sub: SubBatchPlan, front, proprio):
-        self._varlen_prefill(sub, front, proprio, 1, {"slot": sub.slot, "kv_len": sub.kv_len})
+        index = {"slot": sub.slot, "kv_len": sub.kv_len}
+        if self.suffix_attention == "split":                                  # the groups form counts a sample's prefix rows
+            index["prefix_len"] = tuple(n - sub.R for n in sub.kv_len)
+        self._varlen_prefill(sub, front, proprio, 1, index)
 
     def _cache_write(self, c):
         # q|k|v rows of sample b -> cache rows slot[b] .. slot[b] + R, q and k rotated at those positions
         return c.stride(-2), c.stride(0), {"slot": self.slot, "cap_rows": self.S_cap, "rope": (self.cos_c, self.sin_c, 2 * self.H)}
 
     def _attention(self, c, scale):
+        if self.suffix_attention == "split":
+            return hip.attn_groups_split(c, self.B, 1, self.nheads, self.D, self.prefix_len, self.R, scale, ws=self._attn_ws)
         return hip.attn_chunk_ragged(c, self.B, self.nheads, self.D, self.kv_len, self.R, scale)
 
 
@@ -918,24 +973,26 @@ class SampleGroupsEps(_RowGemmEps):
 
     @classmethod
     def for_inputs(cls, vlm, input_ids, n_action_rows: int, num_samples: int, suffix_weights: str = "bf16", prefill: str = "train",
-                   prefill_precision: str = "bf16", **model_kwargs):
+                   prefill_precision: str = "bf16", suffix_attention: str = "head", **model_kwargs):
         """-> (engine, prefilled for this observation; passes [(start, stop), ...] of plan_sample_groups). One engine -- and its graphs --
-        per suffix_weights and prefill mode, as in PrefixCachedEps.for_inputs."""
+        per suffix_weights, prefill and attention mode, as in PrefixCachedEps.for_inputs. suffix_attention: "head"
+        (mla_attn_chunk_groups) or "split" (mla_attn_groups_split)."""
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
         check_prefill_precision(prefill_precision, prefill)
+        check_groups_attention(suffix_attention)
         k = PrefixCachedEps._splice_position(input_ids)
         passes = plan_sample_groups(num_samples, 1 + n_action_rows, cls.MAX_ROWS)
         capacity = max(stop - start for start, stop in passes)
         eng = cls._engine(vlm, "_prefix_engines_samples", (k, int(n_action_rows), capacity, str(input_ids.device)),
-                          (n_action_rows, capacity, suffix_weights, prefill, prefill_precision), suffix_weights, prefill,
-                          prefill_precision=prefill_precision)
+                          (n_action_rows, capacity, suffix_weights, prefill, prefill_precision, suffix_attention), suffix_weights, prefill,
+                          suffix_attention, prefill_precision)
         eng.prefill(input_ids, k, **model_kwargs)
         return eng, passes
 
     def __init__(self, vlm, n_action_rows: int, capacity: int, suffix_weights: str = "bf16", prefill: str = "train",
-                 prefill_precision: str = "bf16"):
-        super().__init__(vlm, n_action_rows, suffix_weights, prefill, prefill_precision=prefill_precision)
+                 prefill_precision: str = "bf16", suffix_attention: str = "head"):
+        super().__init__(vlm, n_action_rows, suffix_weights, prefill, suffix_attention, prefill_precision)
         self.capacity = int(capacity)
         self._graphs = {}            # G -> captured pass over G groups
         self._graphs_packed = None   # the weights those graphs hold the addresses of
@@ -967,6 +1024,7 @@ class SampleGroupsEps(_RowGemmEps):
                     self.slot = torch.full((self.capacity,), S_p, dtype=torch.int32, device=dev)
                     if self.prefill_mode == "compact":
                         self._compact_buffers(S_p, dev)
+                    self._split_workspace(1, self.capacity, S_p, False, dev)
                 self.set_groups(self.capacity)
             assert (S_p, H) == (self.S_p, self.H)
             weights = self._weights()
@@ -986,6 +1044,8 @@ class SampleGroupsEps(_RowGemmEps):
         return c.stride(0), self.R * c.stride(0), {"slot": self.slot, "cap_rows": self.S_p + self.R, "rope": (self.cos_c, self.sin_c, 2 * self.H)}
 
     def _attention(self, c, scale):
+        if self.suffix_attention == "split":
+            return hip.attn_groups_split(c, 1, self.B, self.nheads, self.D, self.S_p, self.R, scale, ws=self._attn_ws)
         return hip.attn_chunk_groups(c, self.B, self.nheads, self.D, self.S_p, self.R, scale)
 
 
@@ -1060,18 +1120,20 @@ class BatchedSampleGroupsEps(_RowGemmEps):
 
     @classmethod
     def for_batch(cls, vlm, ids_rows, n_action_rows: int, num_samples: int, suffix_weights: str = "bf16", images=None, point_cloud=None,
-                  camera_name=None, proprio=None, add_tail=True, **unused):
+                  camera_name=None, proprio=None, add_tail=True, suffix_attention: str = "head", **unused):
         """Generator over the passes of one call: runs the encoders once over all observations, plans (plan_batch_samples) and yields
         (SampleSubBatchPlan, prefilled engine) per sub-batch. Two sub-batches may share an engine: finish sampling one before taking the
-        next."""
+        next. suffix_attention: "head" (mla_attn_chunk_ragged_groups) or "split" (mla_attn_groups_split); one engine per mode."""
         check_suffix_weights(suffix_weights)
+        check_groups_attention(suffix_attention)
         front = cls._front_tokens(vlm, images, point_cloud, camera_name)
         plans = plan_batch_samples(ids_rows, n_action_rows, int(front.shape[1]), num_samples, cls.MAX_ROWS, cls.BUCKET, add_tail=add_tail)
         if plans is None:
             raise ValueError(f"{num_samples} groups of {1 + n_action_rows} rows exceed the {cls.MAX_ROWS} rows of a pass (fits_pass)")
         for sub in plans:
             eng = cls._engine(vlm, "_prefix_engines_batch_samples", (sub.stop - sub.start, sub.G, sub.S_cap, sub.R, str(front.device)),
-                              (n_action_rows, suffix_weights), suffix_weights)
+                              (n_action_rows, suffix_weights, "train", suffix_attention), suffix_weights,
+                              suffix_attention=suffix_attention)
             eng.prefill(sub, front[sub.start:sub.stop], proprio[sub.start:sub.stop])
             yield sub, eng
 
@@ -1084,4 +1146,6 @@ class BatchedSampleGroupsEps(_RowGemmEps):
                                  "rope_pos": self.rope_pos, "rope_rows": self.S_cap}
 
     def _attention(self, c, scale):
+        if self.suffix_attention == "split":
+            return hip.attn_groups_split(c, self.NB, self.G, self.nheads, self.D, self.prefix_len, self.R, scale, ws=self._attn_ws)
         return hip.attn_chunk_ragged_groups(c, self.NB, self.G, self.nheads, self.D, self.prefix_len, self.R, scale)

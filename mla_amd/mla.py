@@ -329,13 +329,16 @@ class MLA(nn.Module):
 
     # ---- what the four sampling entry points share (called as MLA._check_modes: the mode errors come before `self` is touched)
     @staticmethod
-    def _check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision="bf16"):
-        from .infer import check_prefill, check_prefill_precision, check_sampler, check_suffix_attention, check_suffix_weights
+    def _check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision="bf16",
+                     groups_attention="head"):
+        from .infer import (check_groups_attention, check_prefill, check_prefill_precision, check_sampler, check_suffix_attention,
+                            check_suffix_weights)
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
         check_prefill_precision(prefill_precision, prefill)
         check_sampler(sampler, reuse_prefix, use_ddim, num_ddim_steps)
         check_suffix_attention(suffix_attention, reuse_prefix)
+        check_groups_attention(groups_attention, reuse_prefix)
 
     def _draw_x0(self, given, T, action_dim, device):
         """The initial samples [len(given), T, action_dim] fp32 and the RNG draws of one predict_action_diff call per chunk, in call order
@@ -481,7 +484,8 @@ class MLA(nn.Module):
                                   input_ids=None, noise: Optional[torch.Tensor] = None, camera_name: str = "rlbench_front",
                                   reuse_prefix: bool = True, suffix_weights: str = "bf16",
                                   num_samples: Optional[int] = None, prefill: str = "train", sampler: str = "host",
-                                  suffix_attention: str = "head", prefill_precision: str = "bf16") -> np.ndarray:
+                                  suffix_attention: str = "head", prefill_precision: str = "bf16",
+                                  groups_attention: str = "head") -> np.ndarray:
         """B observations -> [B, T, action_dim]: by definition B independent `predict_action_diff` calls (the reference's
         `predict_action_batch`, model_mla.py:994, is dead code), computed on ONE cached prefix pass per DDIM step
         (mla_amd/infer.py:BatchedPrefixCachedEps): the prompts may have different lengths, the FPS start indices are drawn once per chunk.
@@ -509,9 +513,20 @@ class MLA(nn.Module):
         bits) and raises ValueError where "host" would loop over whole-forward calls (``reuse_prefix=False``, a shape the batched engine
         does not serve) or run the DDPM sampler.
         ``suffix_attention``: predict_action_diff's, forwarded for B = 1; B >= 2 with "split" raises NotImplementedError (the ragged and
-        groups engines keep their own attention launches)."""
-        from .infer import BatchedPrefixCachedEps, check_prefill_precision, sampler_needs_engine, suffix_attention_single_only
-        MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps)
+        groups engines take their split-key form from ``groups_attention``).
+        ``groups_attention`` (opt-in, cached prefix only), with and without ``num_samples``: "head" (default) runs the sampler steps'
+        attention as one workgroup per (sample, group, head, 16 queries) (mla_attn_chunk_ragged / mla_attn_chunk_ragged_groups); "split"
+        cuts every (sample, group, head)'s key range over several workgroups and merges the partial softmax states in a fixed order with
+        a second launch (mla_attn_groups_split with the library's plan at the engine's capacity): the same function up to summation
+        order. The plan splits while the launch fits the chip -- at 7B for B * N <= 4 chunks at window <= 15 and B * N <= 2 up to window
+        31; beyond, "split" is the head launch by construction. It composes with every ``suffix_weights`` and ``sampler`` mode; where the
+        call ends in predict_action_diff (B = 1, no ``num_samples`` or N = 1) it is forwarded as ``suffix_attention="split"``; it raises
+        ValueError for an unknown value, and for "split" when ``reuse_prefix=False`` or the batched engine does not serve the shape: it is
+        never the warned loop."""
+        from .infer import (BatchedPrefixCachedEps, check_prefill_precision, groups_attention_needs_engine, sampler_needs_engine,
+                            suffix_attention_single_only)
+        MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps,
+                         groups_attention=groups_attention)
         check_prefill_precision(prefill_precision)                           # an unknown value only: no mode but "bf16" is served here
         if prefill != "train":
             raise NotImplementedError(f"prefill={prefill!r}: the batched engines prefill B x S rows on the training GEMMs; the compact "
@@ -527,7 +542,7 @@ class MLA(nn.Module):
         if num_samples is not None:
             return self._predict_action_diff_batch_samples(images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix,
-                                                           suffix_weights, num_samples, sampler, suffix_attention)
+                                                           suffix_weights, num_samples, sampler, suffix_attention, groups_attention)
         input_ids, pointclouds = MLA._batch_prompts(self, B, instructions, input_ids, pointclouds, cur_robot_states)
         if noise is not None and tuple(noise.shape[:2]) != (B, T):
             raise ValueError(f"noise must be [B, T, action_dim] = [{B}, {T}, ...], got {tuple(noise.shape)}")
@@ -539,12 +554,15 @@ class MLA(nn.Module):
                                             action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b:b + 1],
                                             camera_name=camera_name, **kw)
         if B == 1:
-            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler, suffix_attention=suffix_attention)[None]
+            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler,
+                       suffix_attention="split" if groups_attention == "split" else suffix_attention)[None]
         if suffix_weights != "bf16":
             raise NotImplementedError(f"suffix_weights={suffix_weights!r}: the batched engine (BatchedPrefixCachedEps, mla_gemm_suffix_bf16) "
                                       "streams bf16 weights only; sample B >= 2 observations with \"bf16\", one at a time, or pass "
                                       "`num_samples` (BatchedSampleGroupsEps serves every mode)")
         if reuse_prefix:
+            if not BatchedPrefixCachedEps.supports_batch(self.vlm, T, warn=False):     # raised, not a warned loop of batch-1 calls
+                groups_attention_needs_engine(groups_attention, "BatchedPrefixCachedEps", T)
             reuse_prefix = BatchedPrefixCachedEps.supports_batch(self.vlm, T)
         if not reuse_prefix:
             sampler_needs_engine(sampler, "BatchedPrefixCachedEps", T)
@@ -552,14 +570,14 @@ class MLA(nn.Module):
         device, ids_rows, inputs = self._batch_inputs(images, pointclouds, cur_robot_states, ids_rows, unnorm_key, camera_name)
         x0 = self._draw_x0([None if noise is None else noise[b:b + 1] for b in range(B)], T, action_dim, device)
         out = []
-        for sub, eng in BatchedPrefixCachedEps.for_batch(self.vlm, ids_rows, T, **inputs):
+        for sub, eng in BatchedPrefixCachedEps.for_batch(self.vlm, ids_rows, T, suffix_attention=groups_attention, **inputs):
             samples = self._sample(eng, x0[sub.start:sub.stop].contiguous(), sampler, use_ddim, num_ddim_steps, {})
             out.append(samples.float().cpu().numpy())
         return self._actions(out, unnorm_key)
 
     def _predict_action_diff_batch_samples(self, images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix, suffix_weights, num_samples,
-                                           sampler="host", suffix_attention="head"):
+                                           sampler="host", suffix_attention="head", groups_attention="head"):
         """predict_action_diff_batch(num_samples=N) -> [B, N, T, action_dim] (called inside its inference mode; see its docstring)."""
         B, N, T = len(images), int(num_samples), self.future_action_window_size + 1
         if N < 1:
@@ -576,26 +594,28 @@ class MLA(nn.Module):
                                                     camera_name=camera_name, **kw)
         if B == 1:
             return samples_of(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler,
-                              suffix_attention=suffix_attention)[None]
+                              suffix_attention=suffix_attention, groups_attention=groups_attention)[None]
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
                              "bf16 weights only")
         if reuse_prefix:
-            from .infer import BatchedSampleGroupsEps, sampler_needs_engine
+            from .infer import BatchedSampleGroupsEps, groups_attention_needs_engine, sampler_needs_engine
             if not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T, warn=False):
                 sampler_needs_engine(sampler, "BatchedSampleGroupsEps", T)
+                groups_attention_needs_engine(groups_attention, "BatchedSampleGroupsEps", T)
             if suffix_weights != "bf16" and not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T, warn=False):
                 raise ValueError(f"suffix_weights={suffix_weights!r}: the batched shared-prefix engine (BatchedSampleGroupsEps) does not serve "
                                  f"{1 + T} suffix rows per sample at this head_dim; draw the samples with \"bf16\"")
             if not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T) or not BatchedSampleGroupsEps.fits_pass(T, N):
                 # one observation at a time: predict_action_diff_samples serves (or refuses) the shape and the mode itself
-                return np.stack([samples_of(b, suffix_weights=suffix_weights, sampler=sampler) for b in range(B)])
+                return np.stack([samples_of(b, suffix_weights=suffix_weights, sampler=sampler, groups_attention=groups_attention)
+                                 for b in range(B)])
         else:
             return np.stack([samples_of(b, reuse_prefix=False) for b in range(B)])
         device, ids_rows, inputs = self._batch_inputs(images, pointclouds, cur_robot_states, ids_rows, unnorm_key, camera_name)
         x0 = self._draw_x0([None if noise is None else noise[b, n:n + 1] for b in range(B) for n in range(N)], T, action_dim, device)   # rows (b, n)
         out = []
-        for sub, eng in BatchedSampleGroupsEps.for_batch(self.vlm, ids_rows, T, N, suffix_weights, **inputs):
+        for sub, eng in BatchedSampleGroupsEps.for_batch(self.vlm, ids_rows, T, N, suffix_weights, suffix_attention=groups_attention, **inputs):
             samples = self._sample(eng, x0[sub.start * N:sub.stop * N].contiguous(), sampler, use_ddim, num_ddim_steps, {})
             out.append(samples.float().cpu().numpy().reshape(sub.stop - sub.start, N, T, -1))
         return self._actions(out, unnorm_key)
@@ -607,7 +627,7 @@ class MLA(nn.Module):
                                     noise: Optional[torch.Tensor] = None, camera_name: str = "rlbench_front",
                                     reuse_prefix: bool = True, suffix_weights: str = "bf16", prefill: str = "train",
                                     sampler: str = "host", suffix_attention: str = "head",
-                                    prefill_precision: str = "bf16") -> np.ndarray:
+                                    prefill_precision: str = "bf16", groups_attention: str = "head") -> np.ndarray:
         """N action chunks for ONE observation -> [N, T, action_dim]: by definition N independent `predict_action_diff` calls on the same
         observation with the initial samples ``noise[n]`` (critic / best-of-N choice, uncertainty estimates, temporal ensembling), computed
         on ONE cached prefix (mla_amd/infer.py:SampleGroupsEps): the encoders and the decoder prefill run once per call, every sampler step
@@ -631,9 +651,15 @@ class MLA(nn.Module):
         (the groups engine keeps mla_attn_chunk_groups).
         ``prefill_precision`` (opt-in, ``prefill="compact"`` only): predict_action_diff's modes; "fp8" runs the projections of the one
         prefill of the call over e4m3fn codes of both operands. Forwarded for ``num_samples=1``; raises ValueError for an unknown value
-        and for anything but "bf16" unless ``prefill="compact"``."""
-        from .infer import SampleGroupsEps, sampler_needs_engine, suffix_attention_single_only
-        MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision)
+        and for anything but "bf16" unless ``prefill="compact"``.
+        ``groups_attention`` (opt-in): predict_action_diff_batch's modes; "split" runs every pass's attention as mla_attn_groups_split
+        with the library's plan (at 7B it splits for N <= 4 at window <= 15 and N <= 2 up to window 31; beyond, it is the head launch).
+        It composes with every ``suffix_weights``, ``sampler``, ``prefill`` and ``prefill_precision`` mode; forwarded as
+        ``suffix_attention="split"`` for ``num_samples=1``; raises ValueError for an unknown value, and for "split" when
+        ``reuse_prefix=False`` or the shared-prefix engine does not serve the shape."""
+        from .infer import SampleGroupsEps, groups_attention_needs_engine, sampler_needs_engine, suffix_attention_single_only
+        MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision,
+                         groups_attention)
         if int(num_samples) != 1:
             suffix_attention_single_only(suffix_attention, f"predict_action_diff_samples with num_samples={num_samples}")
         if prefill != "train" and not reuse_prefix:
@@ -653,13 +679,15 @@ class MLA(nn.Module):
                                             camera_name=camera_name, **kw)
         if N == 1:
             return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, prefill=prefill, sampler=sampler,
-                       suffix_attention=suffix_attention, prefill_precision=prefill_precision)[None]
+                       suffix_attention="split" if groups_attention == "split" else suffix_attention,
+                       prefill_precision=prefill_precision)[None]
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
                              "bf16 weights only")
         if reuse_prefix:
             if not SampleGroupsEps.supports_samples(self.vlm, T, warn=False):
                 sampler_needs_engine(sampler, "SampleGroupsEps", T)
+                groups_attention_needs_engine(groups_attention, "SampleGroupsEps", T)
             if prefill != "train" and not SampleGroupsEps.supports_samples(self.vlm, T, warn=False):
                 raise ValueError(f"prefill={prefill!r}: the shared-prefix engine (SampleGroupsEps) does not serve {1 + T} suffix rows per "
                                  "sample at this head_dim; use prefill=\"train\"")
@@ -680,7 +708,7 @@ class MLA(nn.Module):
                         "camera_name": camera_name, "proprio": self._proprio_token(cur_robot_state, unnorm_key, device)}
         x0 = self._draw_x0([None if noise is None else noise[n:n + 1] for n in range(N)], T, action_dim, device)
         eng, passes = SampleGroupsEps.for_inputs(self.vlm, input_ids, T, N, suffix_weights=suffix_weights, prefill=prefill,
-                                                 prefill_precision=prefill_precision, **model_kwargs)
+                                                 prefill_precision=prefill_precision, suffix_attention=groups_attention, **model_kwargs)
         out = []
         for start, stop in passes:                                           # one prefill, then the passes' sampler loops one after the other
             eng.set_groups(stop - start)

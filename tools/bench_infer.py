@@ -53,6 +53,16 @@
                                                           model, one launch pair (split + combine) per splits in {1, 2, 3, plan, nT} against
                                                           mla_attn_decode / mla_attn_chunk at 32 heads for (R, S_kv) = (2, 547), (17, 562);
                                                           --pairs 0 stops after the table
+    python tools/bench_infer.py --pair-attention --samples N[,N..] [--chunks C[,C..]] [--pairs P] [--kernel-table]
+    python tools/bench_infer.py --pair-attention --batch B[,B..] [--samples N[,N..]] [--chunks C[,C..]] [--pairs P] [--kernel-table]
+                                                          groups_attention="head" and "split" alternating in one process, in pairs, on
+                                                          predict_action_diff_samples / predict_action_diff_batch (the lists paired
+                                                          element-wise) with bf16 and with fp8 suffix weights (the device sampler in both
+                                                          arms; --batch without --samples takes its fp8 arm through num_samples=1): per-call
+                                                          latency and the suffix pass alone with the 95 % interval of the pair differences;
+                                                          --kernel-table first prints, without the model, one launch (pair) per splits in
+                                                          {1, 2, 3, plan} of mla_attn_groups_split against the route's head launch at 32
+                                                          heads and 545 prefix rows; --pairs 0 stops after the table
 Prints one JSON line per measurement (not the driver's bench contract -- that is bench.py)."""
 import argparse
 import json
@@ -134,7 +144,8 @@ def main():
     ap.add_argument("--pair-fp8", action="store_true", help="alternate bf16 and fp8 chunks in one process, in pairs")
     ap.add_argument("--pair-prefill", action="store_true", help="alternate prefill=\"train\", \"compact\" and \"compact\" with prefill_precision=\"fp8\" in one process")
     ap.add_argument("--pair-sampler", action="store_true", help="alternate sampler=\"host\" and sampler=\"device\" in one process, in pairs")
-    ap.add_argument("--pair-attention", action="store_true", help="alternate suffix_attention=\"head\" and \"split\" in one process, in pairs")
+    ap.add_argument("--pair-attention", action="store_true", help="alternate suffix_attention=\"head\" and \"split\" in one process, in pairs; with --samples / --batch: groups_attention "
+                    "on the multi-row routes")
     ap.add_argument("--pairs", type=int, default=6)
     ap.add_argument("--kernel-table", action="store_true", help="with --pair-fp8: the two _w8 kernels per projection shape and M; with "
                     "--samples: mla_attn_chunk_groups per groups-per-workgroup against mla_attn_chunk_ragged")
@@ -143,9 +154,9 @@ def main():
     args = ap.parse_args()
     if args.pair_sampler:
         return main_pair_sampler(args)
-    if args.pair_attention:
-        return main_pair_attention(args)
     batches = [int(v) for v in args.batch.split(",")]
+    if args.pair_attention:
+        return main_pair_groups_attention(args, batches) if args.samples or batches != [0] else main_pair_attention(args)
     if args.samples and batches != [0]:
         return main_batch_samples(args, batches)
     args.batch = batches[0]
@@ -435,6 +446,143 @@ def main_pair_attention(args):
                               "split_vs_head_chunk_rel_diff_random_weights":
                                   round(float(((acts["split"] - acts["head"]) ** 2).sum() ** 0.5 / (acts["head"] ** 2).sum() ** 0.5), 5),
                               "pass_captured": eng.graph is not None, "graph_error": eng.graph_error, "data": "synthetic"}), flush=True)
+
+
+def _groups_split_table(dev, cases, H=32, S_p=545, layers=32, reps=5, rounds=3):
+    """One attention launch of a multi-row sampler step at 7B head count, per form, for every (B, G, R) of `cases`: "head" = the engine's
+    launch today (mla_attn_chunk_groups for B = 1, mla_attn_chunk_ragged for G = 1, else mla_attn_chunk_ragged_groups), "split<s>" =
+    mla_attn_groups_split (both launches; s = 1 is the head form). Prefixes of S_p rows (B > 1: S_p - 3 b). As _attn_split_table:
+    `layers` launches over `layers` caches per graph, forms alternating per round, microseconds per launch (pair)."""
+    import math
+    from mla_amd import hip
+    table, scale = {}, 1 / math.sqrt(128)
+    for B, G, R in cases:
+        ragged = B > 1
+        S_cap = -(-(S_p + G * R) // 64) * 64
+        shape = (B, S_cap, 3 * H * 128) if ragged else (S_p + G * R, 3 * H * 128)
+        caches = [(torch.randn(*shape, device=dev) * 0.7).to(torch.bfloat16) for _ in range(layers)]
+        prefix = torch.tensor([S_p - 3 * b for b in range(B)], dtype=torch.int32, device=dev) if ragged else S_p
+        S_max, plan = hip.attn_groups_split_plan(B, G, H, R, S_cap if ragged else S_p, ragged)
+        counts = sorted({1, 2, 3, plan[0]})
+        ws = torch.empty(max(hip.attn_split_ws_bytes(B * G, H, R, S_max, max(counts)), 16), dtype=torch.uint8, device=dev)
+        if not ragged:
+            forms = {"head": lambda c: hip.attn_chunk_groups(c, G, H, 128, S_p, R, scale)}
+        elif G == 1:
+            kv_len = prefix + R
+            forms = {"head": lambda c: hip.attn_chunk_ragged(c, B, H, 128, kv_len, R, scale)}
+        else:
+            forms = {"head": lambda c: hip.attn_chunk_ragged_groups(c, B, G, H, 128, prefix, R, scale)}
+        for s in counts:
+            forms[f"split{s}"] = lambda c, s=s: hip.attn_groups_split(c, B, G, H, 128, prefix, R, scale, splits=s, ws=ws)
+        graphs = {}
+        for name, fn in forms.items():
+            for c in caches[:2]:                                           # function attributes, allocator
+                fn(c)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for c in caches:
+                    fn(c)
+            g.replay()
+            graphs[name] = g
+        us = {name: [] for name in forms}
+        for _ in range(rounds):
+            for name, g in graphs.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(reps):
+                    g.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                us[name].append(round(e0.elapsed_time(e1) / (reps * layers) * 1e3, 2))
+        ref = forms["head"](caches[0]).float()
+        table[f"B{B}_G{G}_R{R}"] = {"key_tiles": -(-S_max // 64), "plan_splits": plan[0], "plan_workgroups": plan[2],
+                                    "head_workgroups": B * G * H * -(-R // 16),
+                                    "us_per_launch_median": {k: sorted(v)[len(v) // 2] for k, v in us.items()}, "us_per_launch_rounds": us,
+                                    "max_abs_diff_vs_head": {k: round(float((fn(caches[0]).float() - ref).abs().max()), 5)
+                                                             for k, fn in forms.items()}}
+        del caches, graphs
+        torch.cuda.empty_cache()
+    return table
+
+
+def main_pair_groups_attention(args, batches):
+    """groups_attention="head" vs "split" on the multi-row routes, on the same box, alternating: --samples N
+    (predict_action_diff_samples), --batch B (predict_action_diff_batch; the fp8 arm goes through num_samples=1, the route that serves
+    FP8 weights for B >= 2) and --batch B --samples N (the lists paired element-wise), for every chunk length (default: --chunk) with
+    bf16 and with fp8 suffix weights, the device sampler in both arms: per-call latency (host clock around `iters` calls that end in a
+    device synchronise) and the captured suffix pass alone (device events around 8 replays of the engine the call left prefilled).
+    Every figure's reference is the "head" arm of the same process."""
+    dev = torch.device("cuda", 0)
+    Ns = [int(v) for v in args.samples.split(",")] if args.samples else []
+    if batches == [0]:
+        cases = [(1, n) for n in Ns]
+    else:
+        if Ns and len(Ns) != len(batches):
+            raise SystemExit("--batch B[,B..] and --samples N[,N..] are paired element-wise: give as many of one as of the other")
+        cases = list(zip(batches, Ns if Ns else [None] * len(batches)))
+    chunks = [int(v) for v in args.chunks.split(",")] if args.chunks else [args.chunk]
+    if args.kernel_table:
+        shapes = [(B, N or 1, C + 1) for C in chunks for B, N in cases]
+        print(json.dumps({"metric": "multi-row suffix attention per launch, 32 heads of 128, prefixes of 545 rows: head vs split forms",
+                          "unit": "us", "table": _groups_split_table(dev, shapes), "data": "synthetic"}), flush=True)
+    if args.pairs < 1:
+        return
+    arms, m = ("head", "split"), None
+    stores = ("_prefix_engines_samples", "_prefix_engines_batched", "_prefix_engines_batch_samples")
+    for C in chunks:
+        for B, N in cases:
+            m, b, ids = _setup(C, B, model=m)
+            images, pcs, states = (list(v) for v in zip(*(_observation(b, i) for i in range(B))))
+            for w in ("bf16", "fp8"):
+                if B == 1:
+                    route, store = "predict_action_diff_samples", stores[0]
+                    noise = torch.randn(N, C, 7, device=dev)
+
+                    def call(arm):
+                        return m.predict_action_diff_samples(images[0], pcs[0], cur_robot_state=states[0], num_samples=N, input_ids=ids,
+                                                             noise=noise, num_ddim_steps=args.steps, suffix_weights=w, sampler="device",
+                                                             groups_attention=arm)
+                else:
+                    n = N if N is not None else (1 if w == "fp8" else None)
+                    route, store = ("predict_action_diff_batch", stores[1]) if n is None else (f"predict_action_diff_batch(num_samples={n})", stores[2])
+                    noise = torch.randn(*((B, C, 7) if n is None else (B, n, C, 7)), device=dev)
+
+                    def call(arm):
+                        return m.predict_action_diff_batch(images, pcs, cur_robot_states=states, input_ids=list(ids), noise=noise,
+                                                           num_ddim_steps=args.steps, suffix_weights=w, sampler="device", num_samples=n,
+                                                           groups_attention=arm)
+
+                def engine(arm):
+                    eng, = [e for e in m.vlm.__dict__[store].values() if e.suffix_attention == arm and e.suffix_weights == w]
+                    return eng
+                acts = {}
+                for arm in arms:                                            # engines, graphs, tables; the same seed: the same FPS start indices
+                    torch.manual_seed(1)
+                    acts[arm] = call(arm)
+                ms, suffix = {arm: [] for arm in arms}, {arm: [] for arm in arms}
+                for _ in range(args.pairs):                                 # head, split, head, split, ...: same box, interleaved
+                    for arm in arms:
+                        ms[arm].append(_time_ms(lambda: call(arm), args.iters))
+                    for arm in arms:
+                        with torch.inference_mode():
+                            suffix[arm].append(_replay_ms(engine(arm)))
+                eng = engine("split")
+                S_max, plan = eng.attn_plan
+                print(json.dumps({"metric": f"{route}, MLA-Llama2-7B: groups_attention=head vs split in alternating pairs", "batch": B,
+                                  "samples": N, "action_chunk": C, "suffix_rows": eng.h_in.shape[0], "suffix_weights": w, "sampler": "device",
+                                  "ddim_steps": args.steps, "pairs": args.pairs, "iters_per_arm_and_pair": args.iters, "unit": "ms",
+                                  "S_max": S_max, "plan_splits": plan[0], "plan_workgroups": plan[2],
+                                  "call_ms": {k: [round(v, 2) for v in vs] for k, vs in ms.items()},
+                                  "call_split_minus_head": _pair_stats(ms["head"], ms["split"]),
+                                  "suffix_pass_ms": {k: [round(v, 3) for v in vs] for k, vs in suffix.items()},
+                                  "suffix_pass_split_minus_head": _pair_stats(suffix["head"], suffix["split"]),
+                                  "split_vs_head_rel_diff_random_weights":
+                                      round(float(((acts["split"] - acts["head"]) ** 2).sum() ** 0.5 / (acts["head"] ** 2).sum() ** 0.5), 5),
+                                  "pass_captured": eng.graph is not None, "graph_error": eng.graph_error, "data": "synthetic"}), flush=True)
+                for s in stores:                                            # the caches of this (B, N, C, weights)
+                    m.vlm.__dict__.get(s, {}).clear()
+                torch.cuda.empty_cache()
 
 
 def main_pair_prefill(args):
