@@ -736,5 +736,83 @@ class ShardedModel:
             full[u.n_train:] = torch.cat(parts_f)
         return full
 
+    # ------------------------------------------------------------------------------------------ optimizer state (resume)
+    def _gather_moments(self, u: FlatUnit):
+        """The unit's two AdamW moments over the whole trainable region (n_train elements each), on the device of every rank."""
+        if not self.coll:
+            return u.exp_avg, u.exp_avg_sq           # world 1 without collectives: the shard IS the region
+        out = []
+        for shard in (u.exp_avg, u.exp_avg_sq):
+            parts = [torch.empty(u.shard_train, dtype=torch.float32, device=self.device) for _ in range(self.world)]
+            dist.all_gather(parts, shard, group=self.pg)
+            out.append(torch.cat(parts))
+        return out[0], out[1]
+
+    def iter_optimizer_state(self, to_cpu_on_rank0: bool = False):
+        """Twin of ``iter_full_state_fp32`` for AdamW's moments: yields ``(name, exp_avg, exp_avg_sq)`` as fp32 tensors in the parameter's
+        shape for every TRAINABLE parameter, one unit at a time (every rank takes part in the gathers; the peak extra device memory is
+        one unit's two moments). The 8-element padding between tensors is dropped. With ``to_cpu_on_rank0`` only rank 0 receives
+        (host) tensors, the other ranks ``(name, None, None)``. The layouts differ only in where the GRADIENT shard lives (no
+        collectives / separate shard / in-place reduce-scatter); the moments are 1/world shards of the trainable region in all three."""
+        if self.on_gpu:
+            self.wait_all()
+        keep = (not to_cpu_on_rank0) or self.rank == 0
+        for u in self.units:
+            if not u.trainable:
+                continue
+            m, v = self._gather_moments(u)
+            for n, p, o in u.params:
+                if not p.requires_grad:
+                    continue
+                if not keep:
+                    yield n, None, None
+                    continue
+                a, b = m[o:o + p.numel()].view(p.shape), v[o:o + p.numel()].view(p.shape)
+                # (never a view of the live shard: .cpu() of a host tensor would be one)
+                yield (n, a.cpu(), b.cpu()) if (to_cpu_on_rank0 and a.is_cuda) else (n, a.clone(), b.clone())
+            del m, v
+
+    def load_optimizer_state(self, state, step_count: int) -> None:
+        """Inverse of ``iter_optimizer_state``: ``state`` maps parameter name -> ``(exp_avg, exp_avg_sq)`` as FULL tensors (host or
+        device); every rank copies its own ``[rank * shard_train, (rank + 1) * shard_train)`` slice of every unit into its moment
+        shards (padding = 0) and ``step_count`` is restored. The mapping is keyed by name, not by shard, so a state written at one
+        world size loads at any other. Only the pieces that intersect the rank's shard are moved, tensor by tensor: no rank ever holds
+        a unit's full moments on the device. Everything is validated BEFORE the first write: a missing name, an unknown name or a
+        shape mismatch raises ValueError and leaves the optimizer state as it was."""
+        want = {n: p for u in self.units if u.trainable for n, p, _ in u.params if p.requires_grad}
+        missing = [n for n in want if n not in state]
+        extra = [n for n in state if n not in want]
+        bad = []
+        for n, p in want.items():
+            if n in state:
+                pair = state[n]
+                if not (isinstance(pair, (tuple, list)) and len(pair) == 2 and all(torch.is_tensor(t) for t in pair)):
+                    bad.append(f"{n} (not an (exp_avg, exp_avg_sq) pair of tensors)")
+                    continue
+                for kind, t in zip(("exp_avg", "exp_avg_sq"), pair):
+                    if tuple(t.shape) != tuple(p.shape):
+                        bad.append(f"{n}.{kind} {tuple(t.shape)} != {tuple(p.shape)}")
+        if missing or extra or bad:
+            raise ValueError("optimizer state does not match the model's trainable parameters: "
+                             + "; ".join(f"{k}: {', '.join(v)}" for k, v in (("missing", missing), ("unexpected", extra), ("wrong shape", bad)) if v))
+        if self.on_gpu:
+            self.wait_all()
+        for u in self.units:
+            if not u.trainable:
+                continue
+            lo = self.rank * u.shard_train
+            hi = lo + u.shard_train
+            u.exp_avg.zero_()
+            u.exp_avg_sq.zero_()
+            for n, p, o in u.params:
+                if not p.requires_grad:
+                    continue
+                a, b = max(o, lo), min(o + p.numel(), hi)
+                if b <= a:
+                    continue
+                for dst, src in zip((u.exp_avg, u.exp_avg_sq), state[n]):
+                    dst[a - lo:b - lo].copy_(src.detach().reshape(-1)[a - o:b - o])
+        self.step_count = int(step_count)
+
     def state_bytes(self):
         return sum(u.state_bytes() for u in self.units)

@@ -33,7 +33,7 @@ class FSDPStrategy:
                  enable_mixed_precision_training: bool = True, reduce_in_full_precision: bool = True,
                  repeated_diffusion_steps: int = 4, cast_forward_inputs: bool = True, local_ops=None,
                  mixed_precision_dtype: torch.dtype = torch.bfloat16, worker_init_fn=None, requires_cliploss: bool = False,
-                 sharding_strategy: str = "full-shard", **_):
+                 sharding_strategy: str = "full-shard", save_optimizer_state: bool = False, **_):
         """Constructor arguments of the reference's FSDPStrategy (training/strategies/fsdp.py:47-96) -- get_train_strategy passes
         them through unchanged. `sharding_strategy` "full-shard" and "shard-grad-op" run the same schedule here: bf16 weights stay
         replicated between the optimizer step and the next use (13.5 GB of 288 GB), master weights / gradients / AdamW moments are
@@ -76,6 +76,9 @@ class FSDPStrategy:
         self.step = 0               # optimizer steps taken
         self._micro = 0             # micro-batches seen inside the current accumulation window
         self.num_training_steps = self.num_warmup_steps = 0
+        # opt-in: save_checkpoint also writes `<stem>-optimizer.pt` (AdamW moments, step counters, generator states) so that a run can
+        # be continued bit for bit; off by default as in the reference, whose write side is commented out
+        self.save_optimizer_state = bool(save_optimizer_state)
 
     def run_setup(self, n_train_examples: int = 0, run_dir=None) -> None:
         """fsdp.py:176-306: shard, (checkpointing), AdamW groups (no decay on <2-D / bias), LR schedule."""
@@ -201,9 +204,25 @@ class FSDPStrategy:
             if metrics.global_step >= self.epochs * steps_per_epoch:
                 return
 
-    def load_optimizer_and_scheduler(self, checkpoint_path) -> None:
+    OPTIMIZER_FORMAT = "mla_amd.optimizer/1"
+
+    def _hyper(self) -> Dict:
+        return dict(lr_scheduler_type=self.lr_scheduler_type, learning_rate=float(self.learning_rate), weight_decay=float(self.weight_decay),
+                    num_training_steps=int(self.num_training_steps), num_warmup_steps=int(self.num_warmup_steps))
+
+    def _rng_states(self):
+        """This rank's generator states: (CPU uint8 tensor, device uint8 tensor or None)."""
+        dev = torch.cuda.get_rng_state(self.device) if self.device.type == "cuda" else None
+        return torch.get_rng_state(), dev
+
+    def load_optimizer_and_scheduler(self, checkpoint_path, restore_rng: bool = True) -> None:
         """training/strategies/fsdp.py:161-174: the reference looks for `<checkpoint stem>-optimizer.pt`, warns and returns when it
-        is absent -- which it always is, because the write side is commented out (fsdp.py:143-159) here as there."""
+        is absent -- which it always is there, because its write side is commented out (fsdp.py:143-159). Here
+        ``save_checkpoint(save_optimizer=True)`` writes that file, and this call continues the run from it: AdamW moments and
+        ``step_count`` (every rank takes its own slice of every tensor: the file is keyed by parameter name, so the world size may
+        differ from the saving run's), ``self.step`` (the schedule continues), and -- with ``restore_rng`` and an unchanged world size --
+        each rank's CPU and device generator state. The fp32 masters are NOT in this file: load the model file into the module before
+        ``run_setup()``. The strategy's own hyper-parameters win over the saved ones; a difference is a warning."""
         import warnings
         from pathlib import Path
         cp = Path(checkpoint_path)
@@ -211,7 +230,34 @@ class FSDPStrategy:
         if not opt.exists():
             warnings.warn(f"Optimizer checkpoint not found at {opt}!")
             return
-        raise NotImplementedError("optimizer state files are never written by the reference's save_checkpoint (fsdp.py:143-159)")
+        if self.sharded is None:
+            raise RuntimeError("load_optimizer_and_scheduler needs run_setup() first (the moments are loaded into the sharded model)")
+        # memory-mapped: every rank opens the file, but only the slices it copies are ever read into (shared, page-cache) memory
+        blob = torch.load(opt, map_location="cpu", weights_only=True, mmap=True)
+        fmt = blob.get("format") if isinstance(blob, dict) else None
+        if fmt != self.OPTIMIZER_FORMAT:
+            raise ValueError(f"{opt}: unknown optimizer checkpoint format {fmt!r} (this build reads {self.OPTIMIZER_FORMAT!r})")
+        self.sharded.load_optimizer_state({n: (d["exp_avg"], d["exp_avg_sq"]) for n, d in blob["state"].items()}, int(blob["step_count"]))
+        self.step = int(blob["step"])
+        self._micro = 0
+        mine = self._hyper()
+        diff = {k: (blob["hyper"].get(k), v) for k, v in mine.items() if blob["hyper"].get(k) != v}
+        if diff:
+            warnings.warn("optimizer checkpoint was written with other hyper-parameters (saved, current -- the current ones are used): "
+                          + ", ".join(f"{k}: {a!r} != {b!r}" for k, (a, b) in diff.items()))
+        if restore_rng:
+            rng = blob.get("rng") or {}
+            rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+            if rng.get("world") != self.world:
+                warnings.warn(f"optimizer checkpoint holds generator states of {rng.get('world')} rank(s), this run has {self.world}: "
+                              "the random generators are left as they are")
+            else:
+                torch.set_rng_state(rng["cpu"][rank].clone())
+                dev_state = rng["device"][rank]
+                if self.device.type == "cuda" and dev_state is not None:
+                    torch.cuda.set_rng_state(dev_state.clone(), self.device)
+        if dist.is_available() and dist.is_initialized():
+            dist.barrier()
 
     def synchronize(self) -> None:
         """Main stream waits for every outstanding side-stream all-gather (module forwards do this per unit on their own). Call it
@@ -220,14 +266,26 @@ class FSDPStrategy:
             self.sharded.wait_all()
 
     # ------------------------------------------------------------------------------------------ checkpoints
-    def save_checkpoint(self, run_dir, global_step: int, epoch: int, train_loss: Optional[float] = None, only_trainable: bool = True):
+    def save_checkpoint(self, run_dir, global_step: int, epoch: int, train_loss: Optional[float] = None, only_trainable: bool = True,
+                        save_optimizer: Optional[bool] = None):
         """training/strategies/fsdp.py:100-141: gather the full fp32 state dict (every rank takes part in the gathers), split it
         by module key (``vlm.`` prefix dropped), rank 0 writes ``{"model": {mkey: OrderedDict}}`` to
-        ``run_dir/checkpoints/step-XXXXXX-epoch-XX-loss=....pt``. Optimizer state is not saved (commented out in the reference).
-        Returns the path (rank 0) or None."""
+        ``run_dir/checkpoints/step-XXXXXX-epoch-XX-loss=....pt``. Returns the path (rank 0) or None.
+
+        ``save_optimizer`` (None = ``self.save_optimizer_state``, off by default: the reference's write side is commented out): rank 0
+        also writes ``<same stem>-optimizer.pt``, the file ``load_optimizer_and_scheduler`` looks for -- plain containers and tensors
+        (``torch.load(..., weights_only=True)``): format tag, ``step`` / ``step_count``, the schedule's hyper-parameters, both AdamW moments per
+        trainable parameter under the names of the model file's gather (full tensors: loads at any world size), every rank's generator
+        states. Weights are not repeated there. Summed gradients of an open accumulation window are not part of the format, so
+        saving inside one raises."""
         from collections import OrderedDict
         from pathlib import Path
         assert self.sharded is not None, "save_checkpoint needs run_setup() first"
+        if save_optimizer is None:
+            save_optimizer = self.save_optimizer_state
+        if save_optimizer and self._micro != 0:
+            raise RuntimeError(f"optimizer state cannot be saved inside an accumulation window ({self._micro} of "
+                               f"{self.grad_accumulation_steps} micro-batches seen): the summed gradients are not part of the file")
         # one unit at a time; only rank 0 keeps (host) copies -- FullStateDictConfig(offload_to_cpu=True, rank0_only=True)
         full = {k: v for k, v in self.sharded.iter_full_state_fp32(to_cpu_on_rank0=True) if v is not None}
         mkeys = list(self.vlm.trainable_module_keys if only_trainable else self.vlm.all_module_keys)
@@ -246,6 +304,23 @@ class FSDPStrategy:
             path = ckpt_dir / f"step-{global_step:06d}-epoch-{epoch:02d}-loss={tag}.pt"
             out = OrderedDict((k[4:] if k.startswith("vlm.") else k, v) for k, v in model_state_dicts.items())
             torch.save({"model": out}, path)
+            del out
+        del full, model_state_dicts          # rank 0's host copy of the weights goes before the moments arrive
+        if save_optimizer:
+            # same route as the weights: one unit at a time through the device, host copies on rank 0 only
+            state = OrderedDict((n, {"exp_avg": m, "exp_avg_sq": v})
+                                for n, m, v in self.sharded.iter_optimizer_state(to_cpu_on_rank0=True) if m is not None)
+            mine = self._rng_states()
+            if dist.is_available() and dist.is_initialized():
+                every = [None] * self.world
+                dist.all_gather_object(every, tuple(None if t is None else t.cpu() for t in mine))
+            else:
+                every = [mine]
+            if rank == 0:
+                torch.save({"format": self.OPTIMIZER_FORMAT, "step": int(self.step), "step_count": int(self.sharded.step_count),
+                            "hyper": self._hyper(), "state": state,
+                            "rng": {"world": int(self.world), "cpu": [c for c, _ in every], "device": [d for _, d in every]}},
+                           path.with_name(path.stem + "-optimizer.pt"))
         if dist.is_available() and dist.is_initialized():
             dist.barrier()
         return path
