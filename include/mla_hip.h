@@ -63,7 +63,8 @@ int mla_gemm_bf16_ws(const void* A, const void* B, void* C, const void* R, const
  * weight gradient to the clipping norm (training/strategies/fsdp.py:308-310) without a second pass over the fp32 gradient buffer.
  * Fixed partial order, deterministic. Shapes of the 256x256 kernel only (M, N >= 256, K % 64 == 0, N % 8 == 0): error otherwise. */
 int mla_gemm_sq_slots(int M, int N, int K, size_t workspace_bytes);   /* partials the launch below writes; -1 = shape not supported */
-/* Main loop of the 256x256 kernel's k-contiguous instantiations (all fused forms included): 1 = hand-scheduled assembly (default; needs
+/* Main loop of the 256x256 kernel (k-contiguous instantiations, all fused forms included, and the plain kernel on reduction-major
+ * operands): 1 = hand-scheduled assembly (default; needs
  * K % 128 == 0 and the whole-row epilogue, otherwise the launch uses the other one by itself), 0 = compiler-scheduled; any other value
  * only queries. Returns the mode in force. Results are bit-identical either way -- the switch exists for A/B measurements and tests.
  * Environment MLA_GEMM_KLOOP=0 sets the initial mode. */
@@ -76,6 +77,11 @@ int mla_gemm_cus(int n);
 int mla_gemm_bf16_ws_sq(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, int accumulate,
                         float alpha, float* workspace, size_t workspace_bytes, float* sq_out, int sq_capacity, int* sq_slots,
                         mla_stream_t stream);
+/* the same launch with the operand layouts of mla_gemm_bf16 (a_mode / b_mode 1 = stored [K][rows]): the wgrad dW = dy^T x on row-major
+ * dy and x, without transposed copies of either; M % 8 == 0 / N % 8 == 0 for a reduction-major A / B */
+int mla_gemm_bf16_ws_sq_rm(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, int a_mode, int b_mode,
+                           int accumulate, float alpha, float* workspace, size_t workspace_bytes, float* sq_out, int sq_capacity,
+                           int* sq_slots, mla_stream_t stream);
 
 /* fused q|k|v projection + rotary embedding (LlamaAttention.forward modeling_llama.py:351-361 + apply_rotary_pos_emb :184-208):
  * C[M, N] = A[M, K] B[N, K]^T in bf16 with columns [0, rope_cols) rotated per head of 128 (position = row % S, tables [S, 64]
@@ -92,7 +98,8 @@ int mla_gemm_gateup_swiglu(const void* x, const void* wgu, void* gu, void* act, 
                            long long ldt, mla_stream_t stream);
 /* fused down-projection dgrad + SwiGLU backward (autograd of LlamaMLP.forward modeling_llama.py:240): d(act) = dy[M, K] wT[I, K]^T is
  * consumed in the GEMM epilogue -- gate|up (gu [M, 2I]) is read there and d(gate|up) is written in both layouts, dgu [M, 2I] and
- * dguT [2I, ldt]; bit-identical to mla_gemm_bf16 followed by mla_swiglu_bwd_t. M, I >= 256, K % 64 == 0, M % 8 == 0. */
+ * dguT [2I, ldt]; bit-identical to mla_gemm_bf16 followed by mla_swiglu_bwd_t. M, I >= 256, K % 64 == 0, M % 8 == 0. dguT may be NULL
+ * (the wgrad then reads dgu as a reduction-major operand): the transposed strip and its LDS staging are skipped. */
 int mla_gemm_dact_swiglu_bwd(const void* dy, const void* wT, const void* gu, void* dgu, void* dguT, int M, int I, int K, int lda,
                              int ldb, long long ldt, mla_stream_t stream);
 
@@ -117,6 +124,9 @@ int mla_rmsnorm_prep(const void* x, const void* w, void* xg, float* rstd, int ro
 
 /* ---- RMSNorm: LlamaRMSNorm.forward modeling_llama.py:76-90; timm RmsNorm in FinalLayer (models/diffusion/models.py:177) */
 int mla_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int rows, int H, float eps, mla_stream_t stream);
+/* y [rows, H] = w * bf16(x * rstd[row]) with the rstd a forward saved: the normalised input rebuilt row-major, bit for bit what
+ * mla_rmsnorm_fwd wrote (the row-major twin of mla_rmsnorm_apply_t, for the wgrad on reduction-major operands). H % 8 == 0. */
+int mla_rmsnorm_apply(const void* x, const void* w, const float* rstd, void* y, long long rows, int H, mla_stream_t stream);
 int mla_rmsnorm_bwd_blocks(int rows);
 /* dx = dres + d(rmsnorm)/dx ; dw (+)= sum_rows dy * x_hat ; workspace >= mla_rmsnorm_bwd_blocks(rows)*H floats */
 int mla_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx, float* dw,

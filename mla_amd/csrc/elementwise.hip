@@ -48,6 +48,25 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const bf16_t* __restri
   }
 }
 
+// y = w * bf16(x * rstd[row]) with the statistic the forward saved, row-major (the arithmetic of rmsnorm_fwd_kernel's second half and of
+// transpose.hip's RmsApplyOp): the wgrad on reduction-major operands reads the normalised input as rows. 256 threads x 16 B, grid-stride.
+__global__ __launch_bounds__(256) void rmsnorm_apply_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
+                                                            const float* __restrict__ rstd, bf16_t* __restrict__ y, long long rows, int H) {
+  const int nchunk = H >> 3;
+  const long long total = rows * nchunk;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long row = i / nchunk;
+    const int ch = (int)(i - row * nchunk);
+    float xv[8], wv[8], o[8];
+    unpack8(*(const u32x4_t*)(x + row * H + ch * 8), xv);
+    unpack8(*(const u32x4_t*)(w + ch * 8), wv);
+    const float rs = rstd[row];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = wv[j] * bf2f(f2bf(xv[j] * rs));
+    *(u32x4_t*)(y + row * H + ch * 8) = pack8(o);
+  }
+}
+
 // The two halves of a FOLDED RMSNorm (gemm_args.h nrm_* / rs_*, gemm256.hip mla_gemm_res_norm) for rows that do not come out of a GEMM
 // epilogue (the first decoder layer's input; recomputation of a checkpointed layer): xg = bf16(x * w) -- the column scale, which does not
 // commute with the projection -- and rstd per row, which the projection applies to its fp32 accumulator rows. One 256-thread block per row.
@@ -871,6 +890,17 @@ extern "C" int mla_rmsnorm_fwd(const void* x, const void* w, void* y, float* rst
   MLA_CHECK_ARG(AL16(x) && AL16(w) && AL16(y), "mla_rmsnorm_fwd: pointers must be 16-B aligned");
   hipLaunchKernelGGL(rmsnorm_fwd_kernel, dim3(rows), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y,
                      rstd, rows, H, eps);
+  MLA_LAUNCH_CHECK();
+}
+
+// y [rows, H] = LlamaRMSNorm(x) with the saved rstd [rows]: bit for bit what mla_rmsnorm_fwd wrote when it produced that rstd
+extern "C" int mla_rmsnorm_apply(const void* x, const void* w, const float* rstd, void* y, long long rows, int H, hipStream_t stream) {
+  MLA_CHECK_ARG(x && w && rstd && y, "mla_rmsnorm_apply: null pointer");
+  MLA_CHECK_ARG(rows > 0 && H > 0 && H % 8 == 0, "mla_rmsnorm_apply: need H%%8==0 (H=%d)", H);
+  MLA_CHECK_ARG(AL16(x) && AL16(w) && AL16(y), "mla_rmsnorm_apply: pointers must be 16-B aligned");
+  const long long blocks = (rows * (H >> 3) + 255) / 256;
+  hipLaunchKernelGGL(rmsnorm_apply_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, (const bf16_t*)x,
+                     (const bf16_t*)w, rstd, (bf16_t*)y, rows, H);
   MLA_LAUNCH_CHECK();
 }
 

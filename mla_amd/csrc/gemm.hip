@@ -376,6 +376,16 @@ extern "C" int mla_gemm_bf16_ws_sq(const void* A, const void* B, void* C, int M,
                         stream, sq_out, sq_capacity, sq_slots);
 }
 
+// The same launch on reduction-major operands (a_mode / b_mode as in mla_gemm_bf16): the wgrad on row-major dY and X.
+extern "C" int mla_gemm_bf16_ws_sq_rm(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, int a_mode,
+                                      int b_mode, int accumulate, float alpha, float* workspace, size_t workspace_bytes, float* sq_out,
+                                      int sq_capacity, int* sq_slots, hipStream_t stream) {
+  MLA_CHECK_ARG(sq_out && sq_slots, "mla_gemm_bf16_ws_sq_rm: null sq_out / sq_slots");
+  MLA_CHECK_ARG(workspace == nullptr || (((uintptr_t)workspace & 15) == 0), "mla_gemm_bf16_ws_sq_rm: workspace must be 16-byte aligned");
+  return gemm_bf16_impl(A, B, C, nullptr, nullptr, M, N, K, lda, ldb, ldc, 0, a_mode, b_mode, 1, accumulate, alpha, 0, workspace,
+                        workspace_bytes, stream, sq_out, sq_capacity, sq_slots);
+}
+
 // Batched form (no bias / residual): for z = (outer, inner) in [0, n_outer) x [0, n_inner):
 //   C + o*sCo + i*sCi = alpha * Aop(A + o*sAo + i*sAi) * Bop(B + o*sBo + i*sBi)^T      (strides in elements)
 // Used for multi-head attention with arbitrary head_dim in the post-training generation heads

@@ -23,6 +23,7 @@
 #include "gemm_args.h"
 
 #include "gemm256_kloop_clobbers.inc"
+#include "gemm256_kloop_rm_clobbers.inc"
 // bf16 epilogue outputs (and the residual / gate|up rows the epilogues read) are touched once per launch and consumed by a LATER kernel:
 // non-temporal accesses keep them from displacing the operand panels 4-8 CUs of an XCD share through its L2. Round 3, same-box A/B of
 // whole steps: 587.4 -> 581.6 ms (-1.0 %), fused-epilogue kernels +4.7 % (GEMM flops over their duration); non-temporal fp32 stores
@@ -142,14 +143,15 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs p) {
 
   f32x4_t acc[8][4];
   if constexpr (ASM) {
-    // ---- hand-scheduled main loop (gemm256_kloop.inc, generated by tools/gen_gemm_asm.py; k-contiguous operands, an even number of
-    // K-tiles). Same LDS operand image, same K order and the same accumulation order per output as the compiler-scheduled loop below:
+    // ---- hand-scheduled main loop (gemm256_kloop.inc, generated by tools/gen_gemm_asm.py; an even number of K-tiles; k-contiguous
+    // operands, or -- plain epilogue only -- the gemm256_kloop_rm*.inc forms with a reduction-major side, further down).
+    // Same LDS operand image, same K order and the same accumulation order per output as the compiler-scheduled loop below:
     // bit-identical results. Three barriers per K-tile instead of eight, no vmcnt(0) in the loop, and the 8 loads of a wave spread over
     // 43 of its 64 MFMA gaps (one per 6): the waves of a workgroup run in lockstep, so a burst of loads in one wave is a burst of eight
     // times as many in the CU's single address path and stalls every issuer (round 3: MfmaUtil 65 % -> 84 % on the 4-wave form of this
     // loop). The last pair of K-tiles runs in a peeled copy of the loop body that prefetches nothing.
     // The accumulators leave the assembly through LDS: the loop's tail writes the tile image the epilogues below read.
-    static_assert(AMODE == 0 && BMODE == 0, "the assembly loop takes k-contiguous operands");
+    static_assert(EPI == 0 || (AMODE == 0 && BMODE == 0), "the fused epilogues take k-contiguous operands");
     const unsigned c0 = ((unsigned)lg ^ ((unsigned)li & 7u)) << 4;
     const unsigned vA0 = (unsigned)((wr * 64 + li) * 128) + c0, vB0 = 32768u + (unsigned)((wc * 32 + li) * 128) + c0;
     // staging: instruction q (0..3) of this wave writes LDS rows wave*32 + q*8 + (lane >> 3) of A and of B, lane's 16-B chunk pre-swizzled
@@ -192,6 +194,54 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs p) {
     const float alpha = part ? 1.f : p.alpha;
     const unsigned vImg = img_bf16 ? (unsigned)((wr * 64 + li) * 512) + ((((unsigned)(wc * 4 + (lg >> 1))) ^ (unsigned)li) << 4) + (unsigned)(lg & 1) * 8u
                                    : (unsigned)((wr * 64 + li) * 1024) + ((((unsigned)(wc * 8 + lg)) ^ (unsigned)li) << 4);
+    if constexpr (AMODE != 0 || BMODE != 0) {
+      // ---- reduction-major side(s): gemm256_kloop_rm<AMODE><BMODE>.inc, the same loop with that side's LDS image, staging pattern and
+      // ds_read_b64_tr_b16 fragment addresses taken from the compiler-scheduled loop below (stage_src, offA / offB), so the k-slot map,
+      // the K order and with them the bits are the same. A reduction-major operand advances 64 ROWS per K-tile (the loop multiplies
+      // its k offset by the leading dimension); columns past the edge were redirected to column 0 by stage_src.
+      const int hs = ((li >> 2) & 3) | ((lg & 1) << 2);
+      const unsigned rmrow = (unsigned)((lg * 8 + (li >> 2)) * 16), rmsub = (unsigned)((li & 3) >> 1), rmlo = (unsigned)(li & 1) * 8u;
+      const unsigned vA = AMODE ? (rmrow + (((unsigned)(wr * 8) + rmsub) ^ ((unsigned)hs << 1))) * 16u + rmlo : vA0;
+      const unsigned vB = BMODE ? 32768u + (rmrow + (((unsigned)(wc * 4) + rmsub) ^ ((unsigned)hs << 1))) * 16u + rmlo : vB0;
+      // load offsets: a reduction-major side passes the offsets of its two 128-row halves (loads 0 / 2; loads 1 / 3 are four k-rows
+      // further down), a k-contiguous side its first row and the clamp as above
+      const unsigned oAh0 = AMODE ? (unsigned)((const char*)stage_src<1, true>(p.A, p.lda, m0, p.M, 0, wave * 2, lane) - (const char*)p.A) : oA0;
+      const unsigned oAh1 = AMODE ? (unsigned)((const char*)stage_src<1, true>(p.A, p.lda, m0, p.M, 1, wave * 2, lane) - (const char*)p.A) : oAmax;
+      const unsigned oBh0 = BMODE ? (unsigned)((const char*)stage_src<1, false>(p.B, p.ldb, n0, p.N, 0, wave * 2, lane) - (const char*)p.B) : oB0;
+      const unsigned oBh1 = BMODE ? (unsigned)((const char*)stage_src<1, false>(p.B, p.ldb, n0, p.N, 1, wave * 2, lane) - (const char*)p.B) : oBmax;
+      const bf16_t* pAr = AMODE ? p.A + (size_t)kt0 * 64 * p.lda : pA;
+      const bf16_t* pBr = BMODE ? p.B + (size_t)kt0 * 64 * p.ldb : pB;
+      const int ldswA = AMODE ? wave * 2048 : ldsw, ldswB = BMODE ? wave * 2048 : ldsw;
+      const int sA4 = p.lda * 8, sB4 = p.ldb * 8;
+      // The loop's own registers, the VGPR operands and what the epilogue keeps live have to fit the kernel's 128 without a spill
+      // (build.sh checks): the uniform operands are made scalar here, and the loop uses a reduction-major side's vA0 / vB0 / o?0 / o?2
+      // operands in place (no copies)
+      const int nit_s = __builtin_amdgcn_readfirstlane(nit), emode_s = __builtin_amdgcn_readfirstlane(emode);
+      const int alpha_s = __builtin_amdgcn_readfirstlane(__float_as_int(alpha));
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MLA_KLOOP_RM_OPERANDS                                                                                                              \
+        : : [pA] "s"(pAr), [pB] "s"(pBr), [nit] "s"(nit_s), [ldsw] "s"(ldswA), [ldswB] "s"(ldswB), [kA] "s"(p.lda), [kB] "s"(p.ldb),          \
+            [sA8] "s"(sA8), [sB8] "s"(sB8), [sA4] "s"(sA4), [sB4] "s"(sB4), [emode] "s"(emode_s), [alpha] "s"(alpha_s), [vA0] "v"(vA),         \
+            [vB0] "v"(vB), [oA0] "v"(oAh0), [oA2] "v"(oAh1), [oAmax] "v"(oAh1), [oB0] "v"(oBh0), [oB2] "v"(oBh1), [oBmax] "v"(oBh1),        \
+            [vImg] "v"(vImg)                                                                                                                \
+        : "memory", "scc", "vcc", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54",  \
+          "s55", "s56", "s57", "s58"
+      if constexpr (AMODE != 0 && BMODE != 0) {
+        asm volatile(
+#include "gemm256_kloop_rm11.inc"
+            MLA_KLOOP_RM_OPERANDS, G256K_RM11_CLOBBERS);
+      } else if constexpr (AMODE != 0) {
+        asm volatile(
+#include "gemm256_kloop_rm10.inc"
+            MLA_KLOOP_RM_OPERANDS, G256K_RM10_CLOBBERS);
+      } else {
+        asm volatile(
+#include "gemm256_kloop_rm01.inc"
+            MLA_KLOOP_RM_OPERANDS, G256K_RM01_CLOBBERS);
+      }
+#undef MLA_KLOOP_RM_OPERANDS
+#endif
+    } else {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass would validate the register names against x86
     asm volatile(
 #include "gemm256_kloop.inc"
@@ -200,6 +250,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs p) {
             [oBmax] "v"(oBmax), [vImg] "v"(vImg)
         : "memory", "scc", "vcc", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", G256K_CLOBBERS);
 #endif
+    }
     if constexpr (EPI == 0) if (part) {     // K-slice of a tail tile: the raw fp32 image leaves as whole rows of the tile-local [256][256] partial
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
@@ -591,6 +642,13 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs p) {
               MLA_ST16(p.sw_dgu + (size_t)m * ld2 + n, pg[k4]);
               MLA_ST16(p.sw_dgu + (size_t)m * ld2 + I + n, pu[k4]);
             }
+          }
+          if (p.sw_dguT == nullptr) {          // uniform: the caller's wgrad reads d(gate|up) row-major -- no transposed strip, no LDS staging,
+            if constexpr (ASM) {               // no barriers (every strip touches only its own rows of the image)
+#pragma unroll
+              for (int k4 = 0; k4 < 4; ++k4) { gq[k4] = gn[k4]; uq[k4] = un[k4]; }
+            }
+            continue;
           }
           __syncthreads();           // the strip's rows of the d(act) image have been consumed by everyone
 #pragma unroll
@@ -1255,7 +1313,8 @@ int planned_cus(int device_cus) {
   return (g_ncu_plan > 0 && g_ncu_plan < device_cus) ? g_ncu_plan : device_cus;
 }
 
-// Main loop of the k-contiguous instantiations: 1 = hand-scheduled assembly (default), 0 = compiler-scheduled. Both give the same bits;
+// Main loop of the plain-epilogue (any operand layout) and fused-epilogue instantiations: 1 = hand-scheduled assembly (default), 0 =
+// compiler-scheduled. Both give the same bits;
 // MLA_GEMM_KLOOP=0 in the environment or mla_gemm_kloop(0) select the compiler's (A/B measurements, tests).
 int g_kloop = -1;
 int kloop_mode() {
@@ -1266,26 +1325,38 @@ int kloop_mode() {
   return g_kloop;
 }
 
-template <int EPI>
+template <int EPI, int AM = 0, int BM_ = 0>
 void launch_asm(const GemmArgs& p, dim3 grid, size_t lds, hipStream_t stream) {
   static bool attr = false;
   if (!attr) {
-    hipFuncSetAttribute((const void*)gemm256_kernel<0, 0, EPI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipFuncSetAttribute((const void*)gemm256_kernel<AM, BM_, EPI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr = true;
   }
-  hipLaunchKernelGGL((gemm256_kernel<0, 0, EPI, true>), grid, dim3(512), lds, stream, p);
+  hipLaunchKernelGGL((gemm256_kernel<AM, BM_, EPI, true>), grid, dim3(512), lds, stream, p);
 }
 
 template <int AM, int BM_>
 int launch256(const GemmArgs& p, hipStream_t stream, int persistent_grid) {
-  if constexpr (AM != 0 || BM_ != 0) {   // reduction-major operands: the plain one-tile-per-workgroup launch only
+  if constexpr (AM != 0 || BM_ != 0) {   // reduction-major operands: the plain epilogue, one tile per workgroup (+ split-K tail)
     static bool attr_rm = false;
     if (!attr_rm) {
       hipFuncSetAttribute((const void*)gemm256_kernel<AM, BM_>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * BUF);
       attr_rm = true;
     }
     const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-    if (p.sk_split > 1) {
+    // hand-scheduled main loop (gemm256_kloop_rm<AM><BM_>.inc) under the conditions of the k-contiguous one: an even number of K-tiles
+    // and the whole-row epilogue (the loop's tail writes the tile image). Same bits as the compiler-scheduled loop below.
+    const bool fast = (p.N & 7) == 0 && (p.ldc & 7) == 0 && (((uintptr_t)p.C) & 15) == 0 &&
+                      (p.R == nullptr || ((p.ldr & 7) == 0 && (((uintptr_t)p.R) & 15) == 0)) && (p.bias == nullptr || (((uintptr_t)p.bias) & 15) == 0);
+    if (kloop_mode() && (p.K % 128) == 0 && fast) {
+      if (p.sk_split > 1) {
+        const int tail = tiles - p.sk_full;
+        launch_asm<0, AM, BM_>(p, dim3(p.sk_full + tail * p.sk_split), 2 * BUF, stream);
+        hipLaunchKernelGGL(gemm256_fixup_kernel, dim3(tail * 64), dim3(256), 0, stream, p);
+      } else {
+        launch_asm<0, AM, BM_>(p, dim3(tiles), 2 * BUF, stream);
+      }
+    } else if (p.sk_split > 1) {
       const int tail = tiles - p.sk_full;
       hipLaunchKernelGGL((gemm256_kernel<AM, BM_>), dim3(p.sk_full + tail * p.sk_split), dim3(512), 2 * BUF, stream, p);
       hipLaunchKernelGGL(gemm256_fixup_kernel, dim3(tail * 64), dim3(256), 0, stream, p);
@@ -1417,7 +1488,7 @@ extern "C" int mla_gemm_gateup_swiglu(const void* x, const void* wgu, void* gu, 
 // [2I, ldt]. Replaces hip.gemm + mla_swiglu_bwd_t in the MLP backward (autograd of modeling_llama.py:240); bit-identical to them.
 extern "C" int mla_gemm_dact_swiglu_bwd(const void* dy, const void* wT, const void* gu, void* dgu, void* dguT, int M, int I, int K,
                                         int lda, int ldb, long long ldt, hipStream_t stream) {
-  MLA_CHECK_ARG(dy && wT && gu && dgu && dguT, "mla_gemm_dact_swiglu_bwd: null pointer");
+  MLA_CHECK_ARG(dy && wT && gu && dgu, "mla_gemm_dact_swiglu_bwd: null pointer");      // (dguT may be null: row-major output only)
   MLA_CHECK_ARG(M >= 256 && I >= 256 && K > 0 && K % 64 == 0 && I % 8 == 0 && M % 8 == 0,
                 "mla_gemm_dact_swiglu_bwd: needs M, I >= 256, K %% 64 == 0, I %% 8 == 0, M %% 8 == 0");
   MLA_CHECK_ARG(lda >= K && ldb >= K && lda % 8 == 0 && ldb % 8 == 0 && ldt >= M && ldt % 8 == 0,
@@ -1569,8 +1640,8 @@ int mla_gemm256_dispatch(const void* args, int a_mode, int b_mode, size_t ws_byt
   }
 #endif
   const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-  if (p.sq_out) {   // sum-of-squares partials: fp32 output through the whole-row (fast) epilogue, plain instantiation only
-    const bool ok = p.out_fp32 && a_mode == 0 && b_mode == 0 && !p.sf_I && !p.sw_gu && !p.rope_cos && (p.N & 7) == 0 && (p.ldc & 7) == 0 &&
+  if (p.sq_out) {   // sum-of-squares partials: fp32 output through the whole-row (fast) epilogue, plain instantiations only (any operand layout)
+    const bool ok = p.out_fp32 && !p.sf_I && !p.sw_gu && !p.rope_cos && (p.N & 7) == 0 && (p.ldc & 7) == 0 &&
                     (((uintptr_t)p.C) & 15) == 0 && (p.R == nullptr || ((p.ldr & 7) == 0 && (((uintptr_t)p.R) & 15) == 0)) &&
                     (p.bias == nullptr || (((uintptr_t)p.bias) & 15) == 0);
     if (!ok) {

@@ -94,6 +94,8 @@ _SIGNATURES = {
                           c_void_p],
     "mla_gemm_bf16_ws_sq": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_size_t,
                             c_void_p, c_int, c_void_p, c_void_p],
+    "mla_gemm_bf16_ws_sq_rm": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                               c_size_t, c_void_p, c_int, c_void_p, c_void_p],
     "mla_sum_partials": [c_void_p, c_int, c_void_p, c_int, c_void_p],
     "mla_gemm_sq_slots": [c_int, c_int, c_int, c_size_t],
     "mla_gemm_kloop": [c_int],
@@ -104,6 +106,7 @@ _SIGNATURES = {
     "mla_gemm_dact_swiglu_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong,
                                  c_void_p],
     "mla_rmsnorm_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
+    "mla_rmsnorm_apply": [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p],
     "mla_rmsnorm_prep": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
     "mla_gemm_res_norm": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                           c_int, c_void_p, c_size_t, c_void_p],
@@ -324,11 +327,12 @@ def gemm_kloop(mode: int = -1) -> int:
     return int(lib().mla_gemm_kloop(int(mode)))
 
 
-def gemm_sq_slots(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> int:
+def gemm_sq_slots(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, a_mode: int = 0, b_mode: int = 0) -> int:
     """Number of sum-of-squares partials gemm_sq() writes for these operands, or -1 when the shape is outside its contract."""
-    M, K = a.shape
-    N = b.shape[0]
-    ok = (a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and out.dtype == torch.float32 and b.shape[1] == K and
+    M, K = a.shape if a_mode == 0 else (a.shape[1], a.shape[0])
+    N, kb = b.shape if b_mode == 0 else (b.shape[1], b.shape[0])
+    ok = (a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and out.dtype == torch.float32 and kb == K and
+          (a_mode == 0 or M % 8 == 0) and
           a.stride(1) == 1 and b.stride(1) == 1 and out.stride(1) == 1 and M >= 256 and N >= 256 and K % 64 == 0 and N % 8 == 0 and
           a.stride(0) % 8 == 0 and b.stride(0) % 8 == 0 and out.stride(0) % 8 == 0 and
           all(t.data_ptr() % 16 == 0 for t in (a, b, out)) and tuple(out.shape) == (M, N))
@@ -337,16 +341,17 @@ def gemm_sq_slots(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> int:
     return int(lib().mla_gemm_sq_slots(M, N, K, SPLITK_WS_BYTES if SPLITK else 0))
 
 
-def gemm_sq(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, accumulate: bool, part: Optional[torch.Tensor] = None):
+def gemm_sq(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, accumulate: bool, part: Optional[torch.Tensor] = None,
+            a_mode: int = 0, b_mode: int = 0):
     """out[M, N] (fp32) (+)= a[M, K] b[N, K]^T like gemm(), and sum(out^2) of the FINAL values as partial sums written to `part`
     (fp32, >= gemm_sq_slots() elements; allocated here when None): returns (part, number of valid partials) -- or None when the shape
     is outside the 256x256 kernel (the caller then runs gemm() and the gradient norm reads the buffer as before).
-    mla_sum_partials adds the partials up in a fixed order."""
-    need = gemm_sq_slots(a, b, out)
+    mla_sum_partials adds the partials up in a fixed order. a_mode / b_mode as in gemm(): 1 = that operand is stored [K, rows]."""
+    need = gemm_sq_slots(a, b, out, a_mode, b_mode)
     if need < 0:
         return None
-    M, K = a.shape
-    N = b.shape[0]
+    M, K = a.shape if a_mode == 0 else (a.shape[1], a.shape[0])
+    N = b.shape[0] if b_mode == 0 else b.shape[1]
     if part is None:
         part = torch.empty(need, dtype=torch.float32, device=out.device)
     assert part.dtype == torch.float32 and part.is_contiguous() and part.numel() >= need
@@ -356,12 +361,16 @@ def gemm_sq(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, accumulate: boo
     if prof is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-    call("mla_gemm_bf16_ws_sq", _p(a), _p(b), _p(out), M, N, K, a.stride(0), b.stride(0), out.stride(0), 1 if accumulate else 0, 1.0,
-         _p(ws), SPLITK_WS_BYTES if ws is not None else 0, _p(part), part.numel(), ctypes.byref(slots))
+    if a_mode or b_mode:
+        call("mla_gemm_bf16_ws_sq_rm", _p(a), _p(b), _p(out), M, N, K, a.stride(0), b.stride(0), out.stride(0), int(a_mode), int(b_mode),
+             1 if accumulate else 0, 1.0, _p(ws), SPLITK_WS_BYTES if ws is not None else 0, _p(part), part.numel(), ctypes.byref(slots))
+    else:
+        call("mla_gemm_bf16_ws_sq", _p(a), _p(b), _p(out), M, N, K, a.stride(0), b.stride(0), out.stride(0), 1 if accumulate else 0, 1.0,
+             _p(ws), SPLITK_WS_BYTES if ws is not None else 0, _p(part), part.numel(), ctypes.byref(slots))
     assert int(slots.value) == need
     if prof is not None:
         ev1.record()
-        prof.append((ev0, ev1, 2.0 * M * N * K, (0, 0, M, N, K)))
+        prof.append((ev0, ev1, 2.0 * M * N * K, (a_mode, b_mode, M, N, K)))
     return part, need
 
 
@@ -464,9 +473,9 @@ def gemm_gateup_swiglu(x2d, wgu, want_t, norm=None, want_act=True, want_gu=True)
     return (gu, act, actT) if norm is None else (gu, act, actT, rstd)
 
 
-def gemm_dact_swiglu_bwd(dy2d, wT, gu2d):
+def gemm_dact_swiglu_bwd(dy2d, wT, gu2d, want_t=True):
     """(dgu [T, 2I], dguT [2I, T]) = SwiGLU backward of d(act) = dy2d @ wT^T without ever writing d(act); None when the shape is outside
-    the fused kernel's contract (the caller then runs gemm + swiglu_bwd_t)."""
+    the fused kernel's contract (the caller then runs gemm + swiglu_bwd_t). want_t=False: dguT is None and never produced."""
     T, K = dy2d.shape
     I = wT.shape[0]
     ok = (T >= 256 and I >= 256 and K % 64 == 0 and I % 8 == 0 and T % 8 == 0 and gu2d.shape == (T, 2 * I) and gu2d.is_contiguous() and
@@ -476,7 +485,7 @@ def gemm_dact_swiglu_bwd(dy2d, wT, gu2d):
     _req(dy2d, torch.bfloat16, "gemm_dact_swiglu_bwd dy")
     _req(wT, torch.bfloat16, "gemm_dact_swiglu_bwd wT")
     dgu = torch.empty_like(gu2d)
-    dguT = torch.empty((2 * I, T), dtype=torch.bfloat16, device=gu2d.device)
+    dguT = torch.empty((2 * I, T), dtype=torch.bfloat16, device=gu2d.device) if want_t else None
     prof = GEMM_PROFILE
     if prof is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1530,6 +1539,14 @@ def transpose(x2d, out=None):
     if out is None:
         out = torch.empty((C, R), dtype=torch.bfloat16, device=x2d.device)
     call("mla_transpose_bf16", _p(x2d), _p(out), R, C, x2d.stride(0), out.stride(0))
+    return out
+
+
+def rmsnorm_apply(x2d, w, rstd):
+    """[T, H] = rmsnorm(x) with the saved rstd, row-major: bit for bit the y of the rmsnorm_fwd that made rstd."""
+    rows, H = x2d.shape
+    out = torch.empty_like(x2d)
+    call("mla_rmsnorm_apply", _p(x2d), _p(w), _p(rstd), _p(out), rows, H)
     return out
 
 

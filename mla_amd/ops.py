@@ -134,7 +134,7 @@ def deliver_wgrad(weights: Sequence[torch.Tensor], dy2: torch.Tensor, x2: torch.
 _WGRAD_SQ = os.environ.get("MLA_WGRAD_SQ", "1") != "0"      # A/B switch (tools): gradient-norm partials from the wgrad epilogues
 
 
-def _gemm_into_main_grad(weights, dyT, xT, out, accumulate: bool) -> None:
+def _gemm_into_main_grad(weights, dyT, xT, out, accumulate: bool, a_mode: int = 0, b_mode: int = 0) -> None:
     """dW (+)= dyT xT^T into the fp32 gradient buffer. When the owner of the buffer collects the clipping norm itself (one process,
     no reduce-scatter: FlatUnit.sq_sink) the same launch also leaves sum(dW^2) of the final values as partial sums, so the norm
     never re-reads these 4 bytes per parameter (training/strategies/fsdp.py:308-310)."""
@@ -143,21 +143,23 @@ def _gemm_into_main_grad(weights, dyT, xT, out, accumulate: bool) -> None:
     owner = getattr(sink, "__self__", None)      # (a bound method is a fresh object per access: compare the owners)
     if sink is not None and all(getattr(getattr(w, "_sq_sink", None), "__self__", None) is owner and
                                 getattr(w, "_mg_region", None) is None for w in weights):
-        need = hip.gemm_sq_slots(dyT, xT, out)
+        need = hip.gemm_sq_slots(dyT, xT, out, a_mode, b_mode)
         if need > 0:
             part = sink(weights, need)                       # `need` floats of the owner's partial-sum arena (None: arena full)
             if part is not None:
-                hip.gemm_sq(dyT, xT, out, accumulate, part)
+                hip.gemm_sq(dyT, xT, out, accumulate, part, a_mode, b_mode)
                 return
     # no partials from this launch (odd shape, arena full, param_view region, foreign owner): whatever an earlier micro-batch of this
     # window recorded for the range is stale once this launch has added to / overwritten it
     _sq_stale(*weights)
-    hip.gemm(dyT, xT, out=out, accumulate=accumulate)
+    hip.gemm(dyT, xT, out=out, accumulate=accumulate, a_mode=a_mode, b_mode=b_mode)
 
 
-def deliver_wgrad_nt(weights: Sequence[torch.Tensor], dyT: torch.Tensor, xT: torch.Tensor, needs: Sequence[bool]):
+def deliver_wgrad_nt(weights: Sequence[torch.Tensor], dyT: torch.Tensor, xT: torch.Tensor, needs: Sequence[bool], a_mode: int = 0,
+                     b_mode: int = 0):
     """Same as deliver_wgrad with pre-transposed operands: dW_i = dyT[rows_i] @ xT^T  (dyT [sum N_i, T], xT [K, T], both
-    k-contiguous -> the fast NT kernel)."""
+    k-contiguous -> the fast NT kernel). a_mode / b_mode 1 (MLA_WGRAD_RM): that operand is the row-major dy [T, sum N_i] / x [T, K] as
+    its producer left it, read by the reduction-major form of the same kernel -- same bits, no transposed copy."""
     grads: List[Optional[torch.Tensor]] = [None] * len(weights)
     mgs = [getattr(w, "main_grad", None) for w in weights]
     _assert_unlocked(*[w for w, m, n in zip(weights, mgs, needs) if m is not None and n])
@@ -165,7 +167,7 @@ def deliver_wgrad_nt(weights: Sequence[torch.Tensor], dyT: torch.Tensor, xT: tor
         mcat = cat_view(mgs)
         states = {_is_touched(w) for w in weights}
         if mcat is not None and len(states) == 1:
-            _gemm_into_main_grad(weights, dyT, xT, mcat, states.pop())
+            _gemm_into_main_grad(weights, dyT, xT, mcat, states.pop(), a_mode, b_mode)
             for w in weights:
                 _mark_touched(w)
             return grads
@@ -173,10 +175,11 @@ def deliver_wgrad_nt(weights: Sequence[torch.Tensor], dyT: torch.Tensor, xT: tor
     for i, w in enumerate(weights):
         n = w.shape[0]
         if needs[i]:
+            dys = dyT[:, off:off + n] if a_mode else dyT[off:off + n]
             if mgs[i] is not None:
-                _gemm_into_main_grad((w,), dyT[off:off + n], xT, mgs[i], _touch(w))
+                _gemm_into_main_grad((w,), dys, xT, mgs[i], _touch(w), a_mode, b_mode)
             else:
-                grads[i] = hip.gemm(dyT[off:off + n], xT, out_dtype=torch.float32).to(w.dtype)
+                grads[i] = hip.gemm(dys, xT, out_dtype=torch.float32, a_mode=a_mode, b_mode=b_mode).to(w.dtype)
         off += n
     return grads
 
@@ -598,6 +601,40 @@ _SWIGLU_DUAL = os.environ.get("MLA_SWIGLU_DUAL", "1") != "0"     # A/B switch (t
 _RECOMPUTE_LEAN = os.environ.get("MLA_RECOMPUTE_LEAN", "1") != "0"   # A/B switch: 0 = a checkpointed layer recomputes its WHOLE forward (incl. the unused down projection)
 
 
+# Weight-gradient GEMMs of DecoderLayerFn on the operands as their producers leave them (reduction-major, gemm256's generated main loop
+# for a_mode / b_mode 1) instead of on transposed copies. Per GEMM (wd, wgu = wg|wu, wo, wqkv = wq|wk|wv): 0 = today's all-NT path;
+# 1 = dy AND x row-major, no transposed buffer is made for that GEMM at all; "a" = dy row-major, x^T where a producer leaves it for free
+# (rmsnorm_apply_t at save levels 0 / 1 / 3, o^T next to dqkv^T out of the attention backward), x row-major otherwise.
+# MLA_WGRAD_RM = 0 | 1 | comma list of name[=0|1|a]; unnamed GEMMs of a list are off. The results do not depend on it (same K order, same
+# bits). Default = what won its pair at T = 17 536 (profiles/wgrad_rm_gemm_pairs.txt): the reduction-major launch costs +1.8 ... +4.1 %
+# with both operands as stored, +1.0 ... +2.0 % with dy alone, against the price of the copies it removes; wq|wk|wv has no copy of its own
+# to remove while wo keeps the attention backward's transposed outputs.
+_WGRAD_RM_NAMES = ("wd", "wgu", "wo", "wqkv")
+
+
+def _parse_wgrad_rm(spec: str):
+    spec = spec.strip()
+    if spec in ("0", "1"):
+        return dict.fromkeys(_WGRAD_RM_NAMES, int(spec))
+    out = dict.fromkeys(_WGRAD_RM_NAMES, 0)
+    for item in filter(None, (s.strip() for s in spec.split(","))):
+        name, _, val = item.partition("=")
+        if name not in out or val not in ("", "0", "1", "a"):
+            raise ValueError(f"MLA_WGRAD_RM: bad item {item!r} (names {_WGRAD_RM_NAMES}, values 0 / 1 / a)")
+        out[name] = "a" if val == "a" else int(val or "1")
+    return out
+
+
+_WGRAD_RM = _parse_wgrad_rm(os.environ.get("MLA_WGRAD_RM", "wd=1,wgu=a,wo=a"))
+
+
+def set_wgrad_rm(spec) -> dict:
+    """A/B switch for tests and tools (MLA_WGRAD_RM syntax, or a dict a previous call returned); returns the previous setting."""
+    global _WGRAD_RM
+    prev, _WGRAD_RM = _WGRAD_RM, (dict(spec) if isinstance(spec, dict) else _parse_wgrad_rm(str(spec)))
+    return prev
+
+
 # RMSNorm folded into the projections (round 6, mla_hip.h: mla_gemm_res_norm / _qkv_rope_rs / _gateup_swiglu_rs): the stand-alone norm passes
 # of the decoder layer's FORWARD disappear -- the GEMM that produces the residual-stream rows leaves x * g and the partials of sum(x^2), the
 # projection applies rstd to its accumulator rows. Opt-in: MLA_NORM_FOLD=1 (or set_norm_fold(True)).
@@ -736,12 +773,21 @@ def _attn_bwd(qkv, o, lse, do, seqlens, cos, sin, B, S, nheads, groups, want_t):
     return dqkv, tr
 
 
-def _qkv_bwd(dqkv, tr, h2, xn1, rstd1, w, need):
+def _qkv_bwd(dqkv, tr, h2, xn1, rstd1, w, need, wgrad_rm=False):
     """q | k | v projection backward: (dxn1 [T, H], (dWq, dWk, dWv)); the weight gradients are delivered when any is wanted, from tr[0] =
     dqkv^T when the attention backward left it. xn1 None: the normalised input is rebuilt, already transposed, from h2 and rstd1."""
     dxn1 = hip.gemm(dqkv, _transposed((w.wq, w.wk, w.wv)))               # [T, H], K = 3H
     grads = (None, None, None)
-    if need.wq or need.wk or need.wv:
+    rm = _WGRAD_RM["wqkv"] if (wgrad_rm and dqkv.shape[0] % 8 == 0) else 0      # (DecoderLayerFn only; the read-out layer keeps its own path)
+    if (need.wq or need.wk or need.wv) and rm:
+        if xn1 is not None:
+            x, bm = xn1, 1
+        elif rm == 1:
+            x, bm = hip.rmsnorm_apply(h2, w.ln1, rstd1), 1
+        else:
+            x, bm = hip.rmsnorm_apply_t(h2, w.ln1, rstd1), 0
+        grads = deliver_wgrad_nt((w.wq, w.wk, w.wv), dqkv, x, (need.wq, need.wk, need.wv), 1, bm)
+    elif need.wq or need.wk or need.wv:
         xn1T = hip.rmsnorm_apply_t(h2, w.ln1, rstd1) if xn1 is None else hip.transpose(xn1)
         grads = deliver_wgrad_nt((w.wq, w.wk, w.wv), tr[0] if tr is not None else hip.transpose(dqkv), xn1T, (need.wq, need.wk, need.wv))
     return dxn1, grads
@@ -851,6 +897,9 @@ class DecoderLayerFn(torch.autograd.Function):
         Tp = h2.shape[0]
         # down_proj trainable: its wgrad wants act^T
         keep_t = save_level == 1 and LayerWeights(*ctx.needs_input_grad[DecoderLayerFn.N_ARGS:]).wd and _SWIGLU_DUAL
+        # MLA_WGRAD_RM: the down-projection wgrad reads the product row-major -- level 1 keeps act in place of act^T (the same bytes)
+        keep_act = keep_t and bool(_WGRAD_RM["wd"]) and Tp % 8 == 0
+        keep_t = keep_t and not keep_act
         if save_level == 3:
             save_level = 1                         # "1-lean": same saved set as level 1 minus act^T
         ctx.groups = current_attn_groups()
@@ -869,7 +918,9 @@ class DecoderLayerFn(torch.autograd.Function):
         elif save_level == 1:
             # level 1 = recompute the two normalised inputs in the backward (one HBM-bound pass each, written straight into the
             # transposed layout) and KEEP the SwiGLU product, already transposed (+0.39 GB per layer at 7B; 288 GB of HBM)
-            ctx.save_for_backward(*((h2, a.rstd1, a.qkv, a.o, a.lse, a.h1, a.rstd2, a.gu) + ((a.actT,) if a.actT is not None else ())))
+            ctx.kept_act = keep_act
+            ctx.save_for_backward(*((h2, a.rstd1, a.qkv, a.o, a.lse, a.h1, a.rstd2, a.gu) +
+                                    ((a.act,) if keep_act else (a.actT,) if a.actT is not None else ())))
         elif ctx.folded:
             ctx.save_for_backward(h2, a.rstd1)     # the recomputation scales the QKV rows by the SAME rstd the forward used
         else:
@@ -880,7 +931,8 @@ class DecoderLayerFn(torch.autograd.Function):
     def backward(ctx, dout):
         """All-NT backward: every large GEMM gets k-contiguous operands (W^T, x^T, dy^T from the HBM-bound tile-transpose
         kernels; x^T of the normalised inputs and of the SwiGLU product are recomputed straight into transposed layout),
-        so dgrad and wgrad run on the same 256x256 ds_read_b128 kernel as the forward (mla_amd/csrc/transpose.hip)."""
+        so dgrad and wgrad run on the same 256x256 ds_read_b128 kernel as the forward (mla_amd/csrc/transpose.hip).
+        Except the weight gradients MLA_WGRAD_RM names: those read dy (and x) as stored and their copies are never made."""
         w = ctx.w
         B, S, H, nheads, eps = ctx.dims
         seqlens, cos, sin = ctx.aux
@@ -890,12 +942,14 @@ class DecoderLayerFn(torch.autograd.Function):
             a = LayerActs(*saved)
         elif ctx.save_level == 1:
             rstd1, qkv, o, lse, h1, rstd2, gu, *kept_t = saved
-            a = LayerActs(rstd1=rstd1, qkv=qkv, o=o, lse=lse, h1=h1, rstd2=rstd2, gu=gu, actT=kept_t[0] if kept_t else None)
+            a = LayerActs(rstd1=rstd1, qkv=qkv, o=o, lse=lse, h1=h1, rstd2=rstd2, gu=gu)
+            if kept_t:
+                a.act, a.actT = (kept_t[0], None) if ctx.kept_act else (None, kept_t[0])
         else:
             # the recomputation stops in front of the down projection and asks the gate|up epilogue for the SwiGLU product in the
             # layout the down-projection wgrad wants (round 6: was a full forward + a transpose pass over act); a folded layer
             # saved the rstd1 its forward used
-            want_t = need.wd and _SWIGLU_DUAL and _RECOMPUTE_LEAN
+            want_t = need.wd and _SWIGLU_DUAL and _RECOMPUTE_LEAN and not (_WGRAD_RM["wd"] and h2.shape[0] % 8 == 0)
             _, a = DecoderLayerFn._fwd(h2, seqlens, cos, sin, B, S, nheads, eps, w, save_t=want_t, groups=ctx.groups,
                                        fold=saved[0] if ctx.folded else None, need_out=not _RECOMPUTE_LEAN)
         d2 = _pad_rows(dout)                    # row padding of forward(): zero gradient rows
@@ -903,16 +957,25 @@ class DecoderLayerFn(torch.autograd.Function):
 
         # ---- MLP: down projection
         want_w = need.wg or need.wu
+        # MLA_WGRAD_RM per GEMM; a reduction-major operand's row count (the tokens) has to be a multiple of 8, as for the tile transposes
+        rm = _WGRAD_RM if d2.shape[0] % 8 == 0 else dict.fromkeys(_WGRAD_RM_NAMES, 0)
         wdT = _transposed((w.wd,))
-        fused = hip.gemm_dact_swiglu_bwd(d2, wdT, a.gu) if (want_w and _SWIGLU_BWD_EPILOGUE) else None   # d(act) never leaves the chip
+        fused = hip.gemm_dact_swiglu_bwd(d2, wdT, a.gu, want_t=not rm["wgu"]) if (want_w and _SWIGLU_BWD_EPILOGUE) else None   # d(act) never leaves the chip
         dact = hip.gemm(d2, wdT) if fused is None else None              # [T, I]
         del wdT
-        if need.wd:
+        if need.wd and rm["wd"]:
+            if a.act is not None or (a.actT is None and rm["wd"] == 1):
+                act, bm = (a.act if a.act is not None else hip.swiglu_fwd(a.gu)), 1
+            else:
+                act, bm = (a.actT if a.actT is not None else hip.swiglu_fwd_t(a.gu)), 0
+            g["wd"] = deliver_wgrad_nt((w.wd,), d2, act, (True,), 1, bm)[0]
+            del act
+        elif need.wd:
             actT = a.actT if a.actT is not None else (hip.swiglu_fwd_t(a.gu) if a.act is None else hip.transpose(a.act))
             g["wd"] = deliver_wgrad_nt((w.wd,), hip.transpose(d2), actT, (True,))[0]
             del actT
         a.act = a.actT = None
-        fuse_t = want_w and a.gu.shape[0] % 8 == 0       # dgu and dgu^T from one pass (saves re-reading the 2I-wide gradient)
+        fuse_t = want_w and a.gu.shape[0] % 8 == 0 and not rm["wgu"]      # dgu and dgu^T from one pass (saves re-reading the 2I-wide gradient)
         if fused is not None:
             dgu, dguT = fused
         elif fuse_t:
@@ -922,7 +985,16 @@ class DecoderLayerFn(torch.autograd.Function):
         del dact, fused
         # ---- MLP: gate | up projection
         dxn2 = hip.gemm(dgu, _transposed((w.wg, w.wu)))                  # [T, H], K = 2I
-        if want_w:
+        if want_w and rm["wgu"]:
+            if a.xn2 is not None:
+                x, bm = a.xn2, 1
+            elif rm["wgu"] == 1:
+                x, bm = hip.rmsnorm_apply(a.h1, w.ln2, a.rstd2), 1
+            else:
+                x, bm = hip.rmsnorm_apply_t(a.h1, w.ln2, a.rstd2), 0
+            g["wg"], g["wu"] = deliver_wgrad_nt((w.wg, w.wu), dgu, x, (need.wg, need.wu), 1, bm)
+            del x
+        elif want_w:
             xn2T = hip.rmsnorm_apply_t(a.h1, w.ln2, a.rstd2) if a.xn2 is None else hip.transpose(a.xn2)
             g["wg"], g["wu"] = deliver_wgrad_nt((w.wg, w.wu), dguT if fuse_t else hip.transpose(dgu), xn2T, (need.wg, need.wu))
             del xn2T
@@ -935,11 +1007,14 @@ class DecoderLayerFn(torch.autograd.Function):
         # ---- attention output projection, attention, q | k | v projection, input norm
         do = hip.gemm(dh1, _transposed((w.wo,)))
         dqkv, tr = _attn_bwd(a.qkv, a.o, a.lse, do, seqlens, cos, sin, B, S, nheads, ctx.groups,
-                             want_t=(need.wq or need.wk or need.wv) and need.wo)
+                             want_t=(need.wq or need.wk or need.wv) and need.wo and not rm["wqkv"])
         del do
-        if need.wo:
+        if need.wo and rm["wo"]:
+            o_t = tr[1] if (tr is not None and rm["wo"] == "a") else None      # o^T is there anyway when dqkv^T was asked for
+            g["wo"] = deliver_wgrad_nt((w.wo,), dh1, a.o if o_t is None else o_t, (True,), 1, 1 if o_t is None else 0)[0]
+        elif need.wo:
             g["wo"] = deliver_wgrad_nt((w.wo,), hip.transpose(dh1), tr[1] if tr is not None else hip.transpose(a.o), (True,))[0]
-        dxn1, (g["wq"], g["wk"], g["wv"]) = _qkv_bwd(dqkv, tr, h2, a.xn1, a.rstd1, w, need)
+        dxn1, (g["wq"], g["wk"], g["wv"]) = _qkv_bwd(dqkv, tr, h2, a.xn1, a.rstd1, w, need, wgrad_rm=True)
         del dqkv, tr
         dh, g["ln1"] = _rmsnorm_bwd(dxn1, h2, w.ln1, a.rstd1, dh1, need.ln1)
         return (_cut_rows(dh, B, S) if ctx.needs_input_grad[0] else None, *[None] * (DecoderLayerFn.N_ARGS - 1), *LayerWeights(**g))

@@ -1,6 +1,9 @@
 """gemm256 on reduction-major operands (ds_read_b64_tr_b16 fragments, untracked LDS-DMA staging) against the all-NT formulation it
 would replace (k-contiguous operands + the explicit transposes that make them). Decoder-layer backward shapes, random data.
-Usage: python tools/bench_gemm_modes.py [tokens]"""
+Usage: python tools/bench_gemm_modes.py [tokens]
+       python tools/bench_gemm_modes.py pairs [tokens]    per wgrad GEMM of a decoder layer: the reduction-major assembly launch on row-major
+           dY and X against the k-contiguous launch plus what that GEMM's transposed copies cost today, alternating on one GPU
+           (medians of 7 rounds); the (0, 1) rates of the dgrad shapes; -> profiles/wgrad_rm_gemm_pairs.txt"""
 import os
 import sys
 
@@ -8,6 +11,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from mla_amd import hip
 
+PAIRS = len(sys.argv) > 1 and sys.argv[1] == "pairs"      # the per-GEMM decision table of the MLA_WGRAD_RM switch (below)
+if PAIRS:
+    del sys.argv[1]
 T = int(sys.argv[1]) if len(sys.argv) > 1 else 17536
 dev = torch.device("cuda:0")
 H, I = 4096, 11008
@@ -29,6 +35,86 @@ def timeit(fn, iters=10):
 def rnd(*shape, scale=1.0):
     return (torch.randn(*shape, device=dev) * scale).to(torch.bfloat16)
 
+
+def alternating(fns, rounds=7, iters=4):
+    """Median ms per call of every fn, measured round-robin so that clock / temperature drift hits all of them alike."""
+    for f in fns.values():
+        f()
+    ts = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, f in fns.items():
+            torch.cuda.synchronize()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(iters):
+                f()
+            e.record()
+            torch.cuda.synchronize()
+            ts[k].append(s.elapsed_time(e) / iters)
+    return {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+
+
+def pairs():
+    print(f"wgrad pairs at T = {T}: dW[Nout, Kin] (fp32, accumulate) = dY^T X. NT = k-contiguous launch on dY^T, X^T; RM = (1, 1) on row-major "
+          f"dY, X: asm = generated main loop, cc = compiler-scheduled loop; (1, 0) / (0, 1) = one side as stored. ms, medians of 7 alternating rounds")
+    rows = {}
+    for name, nout, kin in (("wd", H, I), ("wg|wu", 2 * I, H), ("wo", H, H), ("wq|wk|wv", 3 * H, H)):
+        dy, x = rnd(T, nout), rnd(T, kin)
+        dyt, xt = hip.transpose(dy), hip.transpose(x)
+        out = torch.zeros(nout, kin, dtype=torch.float32, device=dev)
+
+        def rm(am, bm, loop):
+            def f():
+                hip.gemm_kloop(loop)
+                hip.gemm(dy if am else dyt, x if bm else xt, out=out, a_mode=am, b_mode=bm, accumulate=True)
+                hip.gemm_kloop(1)
+            return f
+        r = alternating({"nt": lambda: hip.gemm(dyt, xt, out=out, accumulate=True), "rm_asm": rm(1, 1, 1), "rm_cc": rm(1, 1, 0),
+                         "a_rm": rm(1, 0, 1), "b_rm": rm(0, 1, 1), "dyT": lambda: hip.transpose(dy), "xT": lambda: hip.transpose(x)})
+        rows[name] = r
+        fl = 2.0 * T * nout * kin / 1e9
+        print(f"  {name:9s} NT {r['nt']:6.3f} ({fl / r['nt']:5.0f} TF/s) | RM asm {r['rm_asm']:6.3f} ({fl / r['rm_asm']:5.0f} TF/s, {100 * (r['rm_asm'] / r['nt'] - 1):+5.1f} %)"
+              f" | RM cc {r['rm_cc']:6.3f} ({100 * (r['rm_cc'] / r['nt'] - 1):+5.1f} %) | (1,0) {r['a_rm']:6.3f} ({100 * (r['a_rm'] / r['nt'] - 1):+5.1f} %)"
+              f" | (0,1) {r['b_rm']:6.3f} ({100 * (r['b_rm'] / r['nt'] - 1):+5.1f} %) | tile_transpose dY {r['dyT']:6.3f}, X {r['xT']:6.3f}", flush=True)
+        del dy, x, dyt, xt, out
+    print("producer epilogues with and without their transposed output (the copy's price where no stand-alone transpose makes it)")
+    x, wgu = rnd(T, H), rnd(2 * I, H, scale=0.02)
+    r = alternating({"t": lambda: hip.gemm_gateup_swiglu(x, wgu, True), "n": lambda: hip.gemm_gateup_swiglu(x, wgu, False)})
+    print(f"  gate|up + SwiGLU (<0,0,1>): with act^T {r['t']:6.3f} | without {r['n']:6.3f} | act^T costs {1e3 * (r['t'] - r['n']):6.1f} us", flush=True)
+    act_t = 1e3 * (r["t"] - r["n"])
+    dy, wdT, gu = rnd(T, H), rnd(I, H, scale=0.02), rnd(T, 2 * I)
+    r = alternating({"t": lambda: hip.gemm_dact_swiglu_bwd(dy, wdT, gu), "n": lambda: hip.gemm_dact_swiglu_bwd(dy, wdT, gu, want_t=False)})
+    print(f"  d(act) + SwiGLU bwd (<0,0,2>): with dgu^T {r['t']:6.3f} | without {r['n']:6.3f} | dgu^T costs {1e3 * (r['t'] - r['n']):6.1f} us", flush=True)
+    dgu_t = 1e3 * (r["t"] - r["n"])
+    del x, wgu, dy, wdT, gu
+    # decision: RM asm against NT + today's copies of that GEMM. wd: tile_transpose(d2) + act^T from <0,0,1>; wg|wu: dgu^T from <0,0,2>
+    # (xn2^T comes from rmsnorm_apply_t, the same bytes as the row-major re-application: no saving counted); wo: tile_transpose(dh1)
+    # (o^T comes out of the attention backward, +123 us per layer together with dqkv^T by DESIGN 3.2, NOT measured here: credited to
+    # neither so that a win does not rest on it); wq|wk|wv: nothing measured here (dqkv^T as for wo, xn1^T as xn2^T)
+    # two candidates per GEMM: "1" = dy and x as stored (every copy above goes), "a" = dy as stored and x^T kept (only dy's copy goes:
+    # tile_transpose(d2), dgu^T, tile_transpose(dh1); act^T stays for wd). The setting with the lower net is the one MLA_WGRAD_RM ships.
+    print("decision per GEMM: launch penalty against the measured price of the copies that setting removes (us per layer; negative net wins)")
+    c11 = {"wd": 1e3 * rows["wd"]["dyT"] + act_t, "wg|wu": dgu_t, "wo": 1e3 * rows["wo"]["dyT"], "wq|wk|wv": 0.0}
+    c10 = {"wd": 1e3 * rows["wd"]["dyT"], "wg|wu": dgu_t, "wo": 1e3 * rows["wo"]["dyT"], "wq|wk|wv": 0.0}
+    for name, r in rows.items():
+        n11, n10 = 1e3 * (r["rm_asm"] - r["nt"]) - c11[name], 1e3 * (r["a_rm"] - r["nt"]) - c10[name]
+        pick = "0" if min(n11, n10) >= 0 else "1" if n11 <= n10 else "a"
+        print(f"  {name:9s} '1' (1,1): penalty {1e3 * (r['rm_asm'] - r['nt']):+7.1f} - copies {c11[name]:6.1f} = net {n11:+7.1f} us | "
+              f"'a' (1,0): penalty {1e3 * (r['a_rm'] - r['nt']):+7.1f} - copies {c10[name]:6.1f} = net {n10:+7.1f} us -> {pick}", flush=True)
+    print("dgrad shapes, B as stored (b_mode 1, generated main loop) against NT on W^T (out of scope here; the number for the next decision)")
+    for name, nout, kin in (("qkv", 3 * H, H), ("o", H, H), ("gate|up", 2 * I, H), ("down", H, I)):
+        dy, w = rnd(T, nout), rnd(nout, kin, scale=0.02)
+        wt = hip.transpose(w)
+        o = torch.empty(T, kin, dtype=torch.bfloat16, device=dev)
+        r = alternating({"nt": lambda: hip.gemm(dy, wt, out=o), "nn": lambda: hip.gemm(dy, w, out=o, b_mode=1), "wT": lambda: hip.transpose(w)})
+        fl = 2.0 * T * nout * kin / 1e9
+        print(f"  {name:8s} NT {r['nt']:6.3f} ({fl / r['nt']:5.0f} TF/s) | (0,1) {r['nn']:6.3f} ({fl / r['nn']:5.0f} TF/s, {100 * (r['nn'] / r['nt'] - 1):+5.1f} %) | W^T {r['wT']:6.3f}", flush=True)
+        del dy, w, wt, o
+
+
+if PAIRS:
+    pairs()
+    sys.exit(0)
 
 print("dgrad  dX[T, Kin] = dY[T, Nout] W[Nout, Kin]:  NT needs W^T (transpose pass), NN reads W as stored (b_mode 1)")
 for name, nout, kin in (("qkv", 3 * H, H), ("o", H, H), ("gate|up", 2 * I, H), ("down", H, I)):

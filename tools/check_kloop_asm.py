@@ -1,4 +1,5 @@
-"""Build-time check of gemm256's assembly-loop instantiations (gemm256_kernel<0, 0, EPI, true>).
+"""Build-time check of gemm256's assembly-loop instantiations (gemm256_kernel<0, 0, EPI, true> and the reduction-major
+gemm256_kernel<AM, BM_, 0, true>: six kernels).
 
 The accumulators of the hand-scheduled main loop live in a0..a127. In the plain kernel (EPI 0) they cross from the main inline-asm statement
 to a second one when the output needs the fp32 tile image (the loop's tail writes accumulator rows 0..3, gemm256_kloop_half1.inc rows 4..7
@@ -8,12 +9,13 @@ after the C++ side has consumed the first half). The compiler does not know that
     compiler may use the registers afterwards), and
   * no assembly-loop kernel spills (scratch_ access) anywhere.
 hipcc prints its own instructions behind a tab and the text of an inline-asm statement verbatim from column 0; that is how the two are told
-apart. Usage: check_kloop_asm.py <gemm256 device assembly .s>; exit status 1 on a finding."""
+apart. Usage: check_kloop_asm.py <gemm256 device assembly .s> [expected number of assembly-loop kernels]; exit status 1 on a finding
+or on another kernel count."""
 import re
 import sys
 
 
-def main(path):
+def main(path, expect=0):
     agpr = re.compile(r"(?<![\w.])a(\[\d+:\d+\]|\d+)\b|accvgpr")
     bad, seen = [], 0
     fn, cand, statements, prev_asm, mfma_in_asm = None, [], 0, False, 0
@@ -69,8 +71,11 @@ def main(path):
         print(f"{path}: no assembly-loop instantiation of gemm256_kernel found")
         return 1
     print(f"check_kloop_asm: {seen} assembly-loop kernels, {len(bad)} findings")
+    if expect and seen != expect:      # an instantiation that dropped out of the build would otherwise pass unaudited
+        print(f"{path}: {seen} assembly-loop kernels, expected {expect}")
+        return 1
     return 1 if bad else 0
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1]))
+    sys.exit(main(sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 0))

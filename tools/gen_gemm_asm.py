@@ -26,6 +26,8 @@ of loads is the whole CU's burst and stalls every MFMA issuer. m
   * gemm256_kloop.inc / _half1.inc / _clobbers.inc: the PRODUCT main loop of gemm256's k-contiguous instantiations (8 waves,
     gemm256's sub-tile map "map256", peeled last iteration "peel", barrier 3 at gap 8 "wb8", LDS tile-image tail "tail256");
     GEN256_FLAGS overrides the schedule flags for A/B builds;
+  * gemm256_kloop_rm11.inc / _rm10.inc / _rm01.inc / _rm_clobbers.inc: the same loop with an operand-layout mode per side (CfgK64 am / bm;
+    a_mode / b_mode 1 = reduction-major, [K, rows] storage): gemm256_kernel<AM, BM_, 0, true>, the wgrad on row-major dY and X;
   * gemm_asm_8w_loop.inc, gemm_asm_4w_loop.inc (+ clobbers, + the timing variants v1..v9): the stand-alone experiment kernels of
     gemm_asm.hip (MLA_EXPERIMENTAL=1 builds); GEN8W_FLAGS / GEN4W_FLAGS select schedules.
 Other flags: "wb<N>" gap of barrier 3, "rowmaj" / "colmaj" MFMA order, "noprio", "align" / "align4" loop-head placement, "spread" /
@@ -187,10 +189,11 @@ class Cfg:
                 f.write('"' + ln + '\\n"\n')
         return len(body)
 
-    def emit_clobbers(self, fname, macro):
-        regs = [f"v{i}" for i in range(self.nvgpr + (3 if "l2pf" in self.flags else 0))] + [f"a{i}" for i in range(self.nacc)]
-        with open(os.path.join(CSRC, fname), "w") as f:
-            f.write(f"// generated by tools/gen_gemm_asm.py -- do not edit\n#define {macro} \\\n")
+    def emit_clobbers(self, fname, macro, append=False):
+        regs = [f"v{i}" for i in range(self.nvgpr + (3 if "l2pf" in self.flags else 0)) if i not in getattr(self, "alias", {})]
+        regs += [f"a{i}" for i in range(self.nacc)]
+        with open(os.path.join(CSRC, fname), "a" if append else "w") as f:
+            f.write(("" if append else "// generated by tools/gen_gemm_asm.py -- do not edit\n") + f"#define {macro} \\\n")
             for k in range(0, len(regs), 16):
                 last = k + 16 >= len(regs)
                 f.write("  " + ", ".join(f'"{r}"' for r in regs[k:k + 16]) + ("\n" if last else ", \\\n"))
@@ -206,43 +209,93 @@ class CfgK64(Cfg):
 
     PFD = 2
 
-    def __init__(self, name, fi, fj, nload, flags=()):
+    def __init__(self, name, fi, fj, nload, flags=(), am=0, bm=0):
         super().__init__(name, fi, fj, nload, flags)
-        self.nvgpr = self.vbase + 8 + 2 * nload
+        # operand layout per side (gemm256's a_mode / b_mode): 0 = k-contiguous rows, 1 = reduction-major ([K, rows] storage). A
+        # reduction-major side keeps the LDS image of the compiler-scheduled gemm256_kernel<AM, BM_>: per 128-row half of the operand 64
+        # k-rows of 256 B (16-B chunk ^ (hsw(k) << 1)), and every fragment is two ds_read_b64_tr_b16 (k-rows +0 and +4) in place of one
+        # ds_read_b128. Its address registers are one per fragment index inside a half (the index is XORed into the chunk, so it cannot
+        # be an immediate offset) and tile set: A 4 x 2, B 2 x 2; half, k-step and the +4 rows are immediates.
+        self.am, self.bm = am, bm
+        assert not (am or bm) or ("map256" in self.flags and "hbl" in self.flags and "peel" in self.flags and (fi, fj, nload) == (8, 4, 4))
+        self.rA, self.rB = self.vbase, self.vbase + (8 if am else 4)     # first address register of A / of B
+        self.rV = self.rB + 4                                            # load voffsets: NLOAD for A, NLOAD for B
+        self.nvgpr = self.rV + 2 * nload
         self.npf = 2 if "l2pf" in self.flags else 0            # extra VMEM instructions per tile (vmcnt bookkeeping)
+        # A reduction-major side reads its first address register and the voffsets of loads 0 / 2 straight from the kernel's operands
+        # (never written here), so those three registers are neither copies nor clobbers: the kernel has 128 VGPRs for the loop's
+        # registers, the operands and what its epilogue keeps live
+        self.alias = {}
+        if am:
+            self.alias.update({self.rA: "%[vA0]", self.rV: "%[oA0]", self.rV + 2: "%[oA2]"})
+        if bm:
+            self.alias.update({self.rB: "%[vB0]", self.rV + nload: "%[oB0]", self.rV + nload + 2: "%[oB2]"})
+
+    def vr(self, n):
+        return self.alias.get(n, f"v{n}")
+
+    def frag_read(self, dst, is_b, tset, ks, idx):
+        """The instructions that read fragment idx (k-step ks of tile set tset) into the four registers dst = (first, last)."""
+        lo, hi = dst
+        if not (self.bm if is_b else self.am):
+            return [self.ds_read(f"v[{lo}:{hi}]", is_b, tset, ks, idx)]
+        half, sub = (idx >> 1, idx & 1) if is_b else (idx >> 2, idx & 3)
+        reg = (self.rB if is_b else self.rA) + 2 * sub + tset
+        off = half * 16384 + ks * 8192
+        return [f"ds_read_b64_tr_b16 v[{lo}:{lo + 1}], {self.vr(reg)} offset:{off}", f"ds_read_b64_tr_b16 v[{lo + 2}:{hi}], {self.vr(reg)} offset:{off + 1024}"]
+
+    def frag_regs(self, buf, is_b, idx):
+        b = buf * self.fbuf + (self.FI * 4 if is_b else 0) + idx * 4
+        return (b, b + 3)
+
+    def lds_dst(self, tset, q):
+        """m0 of load q (0 .. 2 NLOAD - 1: A's, then B's) of a tile: s47 / s58 = this wave's offset inside an operand's image."""
+        is_b, k = q >= self.NLOAD, q % self.NLOAD
+        rm = self.bm if is_b else self.am
+        off = tset * 65536 + (32768 if is_b else 0) + ((k >> 1) * 16384 + (k & 1) * 1024 if rm else k * 1024)
+        return f"s_add_i32 m0, {'s58' if is_b and (self.am or self.bm) else 's47'}, {off}"
+
+    def ptr_update(self):
+        """Source pointers of the next K-tile, s44 = its byte offset along a k-contiguous row (128 B per tile), clamped to the last tile.
+        A reduction-major side advances 64 rows per tile: offset = s44 * ld (ld in elements, %[kA] / %[kB]), 64 bits."""
+        out = ["s_min_u32 s52, s44, s45"]
+        for rm, base, dst, k, t in ((self.am, 40, 48, "%[kA]", 54), (self.bm, 42, 50, "%[kB]", 56)):
+            if rm:
+                out += [f"s_mul_i32 s{t}, s52, {k}", f"s_mul_hi_u32 s{t + 1}, s52, {k}", f"s_add_u32 s{dst}, s{base}, s{t}",
+                        f"s_addc_u32 s{dst + 1}, s{base + 1}, s{t + 1}"]
+            else:
+                out += [f"s_add_u32 s{dst}, s{base}, s52", f"s_addc_u32 s{dst + 1}, s{base + 1}, 0"]
+        return out + ["s_add_u32 s44, s44, 128"]
 
     def ds_read(self, dst, is_b, tset, ks, idx):
-        reg = self.vbase + (4 if is_b else 0) + 2 * ks + tset
+        reg = (self.rB if is_b else self.rA) + 2 * ks + tset
         off = idx * 2048
         if "map256" in self.flags:      # gemm256's wave -> sub-tile map: A fragments at rows (i>>2)*128 + wr*64 + (i&3)*16, B at (j>>1)*128 + wc*32 + (j&1)*16
             off = ((idx >> 1) * 16384 + (idx & 1) * 2048) if is_b else ((idx >> 2) * 16384 + (idx & 3) * 2048)
         return f"ds_read_b128 {dst}, v{reg} offset:{off}"
 
     def reads_for(self, tset, ks, buf):
-        a = [self.ds_read(self.afrag(buf, x), False, tset, ks, x) for x in range(self.FI)]
-        b = [self.ds_read(self.bfrag(buf, x), True, tset, ks, x) for x in range(self.FJ)]
+        a = [self.frag_read(self.frag_regs(buf, False, x), False, tset, ks, x) for x in range(self.FI)]
+        b = [self.frag_read(self.frag_regs(buf, True, x), True, tset, ks, x) for x in range(self.FJ)]
         out = []
         while a or b:
             if a:
-                out.append(a.pop(0))
+                out.extend(a.pop(0))
             if b:
-                out.append(b.pop(0))
+                out.extend(b.pop(0))
             if a and len(a) > len(b):
-                out.append(a.pop(0))
+                out.extend(a.pop(0))
         if "noreads" in self.flags:
             out = ["s_nop 0"] * len(out)
         return out
 
     def load_group(self, tset):
-        ptr = ["s_min_u32 s52, s44, s45", "s_add_u32 s48, s40, s52", "s_addc_u32 s49, s41, 0", "s_add_u32 s50, s42, s52",
-               "s_addc_u32 s51, s43, 0", "s_add_u32 s44, s44, 128"]
-        bundles = [ptr]
-        va, vb = self.vbase + 8, self.vbase + 8 + self.NLOAD
+        bundles = [self.ptr_update()]
+        va, vb = self.rV, self.rV + self.NLOAD
         for q in range(self.NLOAD):
-            bundles.append([f"s_add_i32 m0, s47, {tset * 65536 + q * 1024}", "s_nop 0", f"global_load_lds_dwordx4 v{va + q}, s[48:49]"])
+            bundles.append([self.lds_dst(tset, q), "s_nop 0", f"global_load_lds_dwordx4 {self.vr(va + q)}, s[48:49]"])
         for q in range(self.NLOAD):
-            bundles.append([f"s_add_i32 m0, s47, {tset * 65536 + 32768 + q * 1024}", "s_nop 0",
-                            f"global_load_lds_dwordx4 v{vb + q}, s[50:51]"])
+            bundles.append([self.lds_dst(tset, self.NLOAD + q), "s_nop 0", f"global_load_lds_dwordx4 {self.vr(vb + q)}, s[50:51]"])
         if "l2pf" in self.flags:
             # L2 prefetch: one dword per 128-B line of the rows this wave stages, PFD tiles beyond the tile being loaded, so the
             # LDS-DMA loads issued later hit L2 instead of exposing HBM latency (the ring only allows one tile of distance)
@@ -403,13 +456,13 @@ class CfgK64(Cfg):
         Every load is issued >= 165 MFMAs (1.3 tiles) before the wait that covers it."""
         nm = self.FI * self.FJ
         NL = self.NLOAD
-        va, vb = self.vbase + 8, self.vbase + 8 + NL
-        ra1 = [self.ds_read(self.afrag(1, x), False, tset, 1, x) for x in range(self.FI)]
-        rb1 = [self.ds_read(self.bfrag(1, x), True, tset, 1, x) for x in range(self.FJ)]
-        ra0 = [self.ds_read(self.afrag(0, x), False, tset ^ 1, 0, x) for x in range(self.FI)]
-        rb0 = [self.ds_read(self.bfrag(0, x), True, tset ^ 1, 0, x) for x in range(self.FJ)]
-        ptr = ["s_min_u32 s52, s44, s45", "s_add_u32 s48, s40, s52", "s_addc_u32 s49, s41, 0", "s_add_u32 s50, s42, s52",
-               "s_addc_u32 s51, s43, 0", "s_add_u32 s44, s44, 128"]
+        va, vb = self.rV, self.rV + NL
+        # a fragment's read is one ds_read_b128 or, on a reduction-major side, two ds_read_b64_tr_b16: either way it has its gap to itself
+        ra1 = [self.frag_read(self.frag_regs(1, False, x), False, tset, 1, x) for x in range(self.FI)]
+        rb1 = [self.frag_read(self.frag_regs(1, True, x), True, tset, 1, x) for x in range(self.FJ)]
+        ra0 = [self.frag_read(self.frag_regs(0, False, x), False, tset ^ 1, 0, x) for x in range(self.FI)]
+        rb0 = [self.frag_read(self.frag_regs(0, True, x), True, tset ^ 1, 0, x) for x in range(self.FJ)]
+        ptr = self.ptr_update()
         bar = [] if "nobarrier" in self.flags else ["s_barrier"]
 
         def put(aux, gap, *ins):
@@ -417,7 +470,7 @@ class CfgK64(Cfg):
                 # peeled last iteration ("peel"): tiles nt-2 (final 1) and nt-1 (final 2) prefetch nothing -- no pointer update, no loads,
                 # no barriers 1 / 2 (they only hand LDS regions back to the loads); the last tile does not read a next tile either
                 drop = ("global_load_lds", "s_add_i32 m0", "s_min_u32 s52", "s_add_u32 s48", "s_addc_u32 s49", "s_add_u32 s50",
-                        "s_addc_u32 s51", "s_add_u32 s44")
+                        "s_addc_u32 s51", "s_add_u32 s44", "s_mul_i32 s5", "s_mul_hi_u32 s5")
                 ins = [x for x in ins if not x.startswith(drop)]
             if "noglds" in self.flags:      # timing only
                 ins = ["s_nop 0" if x.startswith("global_load_lds") else x for x in ins]
@@ -433,19 +486,19 @@ class CfgK64(Cfg):
         dense = 2 * self.FI >= nm // 2                            # 8 waves: one read per gap (a gap is 32 wall cycles with 2 waves/SIMD)
         rstep, lat = (1, 3) if dense else (2, 6)
         for k, r in enumerate(ra1):
-            put(aux, rstep * k, r)
+            put(aux, rstep * k, *r)
         last = rstep * (self.FI - 1)
-        put(aux, last + 1, ptr[0], ptr[1])
-        put(aux, last + (2 if dense else 3), ptr[2], ptr[3])
-        put(aux, last + (3 if dense else 5), ptr[4], ptr[5])
-        L1 = last + (4 if dense else 6)
+        npair = len(ptr) // 2                                     # pointer update, two instructions per gap (3 gaps; + 1 per reduction-major side)
+        for k in range(npair):
+            put(aux, last + 1 + rstep * k, ptr[2 * k], ptr[2 * k + 1])
+        L1 = last + (1 + npair if dense else 2 * npair)
         put(aux, L1, "s_waitcnt lgkmcnt(0)")
         bar1, bar2, bar3 = ([] if f"nb{k}" in self.flags else bar for k in (1, 2, 3))     # timing only: drop one of the barriers
         if final:
             bar1 = bar2 = []
             if final == 2:
                 bar3, ra0, rb0 = [], [], []
-        put(aux, L1 + 1, *bar1, f"s_add_i32 m0, s47, {tset * 65536}")
+        put(aux, L1 + 1, *bar1, self.lds_dst(tset, 0))
         g = L1 + 2
         # load stride in MFMA gaps ("ls<S>", default 2 = back to back behind barriers 1 / 2). The four waves of the workgroup run in
         # lockstep (every barrier re-aligns them), so a cluster of loads in one wave is a cluster of 4x as many in the CU's one
@@ -459,12 +512,11 @@ class CfgK64(Cfg):
             assert pos[NL] >= g2 + 2 and pos[-1] < 2 * nm - 4, (pos, g2)
         else:
             pos = [g + 2 * q for q in range(NL)] + [g2 + 2 + 2 * q for q in range(NL)]
-        m0_of = lambda q: tset * 65536 + (q * 1024 if q < NL else 32768 + (q - NL) * 1024)
         load_at = {}
         for q in range(2 * NL):
-            ins = [f"global_load_lds_dwordx4 v{va + q if q < NL else vb + q - NL}, s[{'48:49' if q < NL else '50:51'}]"]
+            ins = [f"global_load_lds_dwordx4 {self.vr(va + q if q < NL else vb + q - NL)}, s[{'48:49' if q < NL else '50:51'}]"]
             if q + 1 < 2 * NL:
-                ins.append(f"s_add_i32 m0, s47, {m0_of(q + 1)}")
+                ins.append(self.lds_dst(tset, q + 1))
             load_at[pos[q]] = ins
         for gp, ins in load_at.items():
             if gp < nm:
@@ -472,7 +524,7 @@ class CfgK64(Cfg):
         free = [x for x in range(g + 1, g2 - (lat - 2)) if x not in load_at]
         assert len(free) >= nrb, (free, nrb)
         for q in range(nrb):                                       # B(ks1) reads in the gaps between the A loads
-            put(aux, free[(q * len(free)) // nrb], rb1[q])
+            put(aux, free[(q * len(free)) // nrb], *rb1[q])
         put(aux, g2, "s_waitcnt lgkmcnt(0)")
         put(aux, g2 + 1, *bar2)
         assert max(aux) < nm, (max(aux), nm)
@@ -503,7 +555,7 @@ class CfgK64(Cfg):
         free = [x for x in range(w + 2, nm - 2) if (x + nm) not in load_at]
         assert len(free) >= len(rd), (len(free), len(rd))
         for k, r in enumerate(rd):
-            put(aux, free[(k * len(free)) // len(rd)], r)
+            put(aux, free[(k * len(free)) // len(rd)], *r)
         aux = {g_: i_ for g_, i_ in aux.items() if i_}
         put(aux, nm - 2, "s_waitcnt lgkmcnt(0)")
         assert max(aux) < nm, (max(aux), nm)
@@ -514,18 +566,35 @@ class CfgK64(Cfg):
         vb = self.vbase
         knit = (["v_readfirstlane_b32 s45, %[kmax]", "v_readfirstlane_b32 s46, %[nit]"] if "tail256" in self.flags      # VGPR operands, see gemm256.hip
                 else ["s_mov_b32 s45, %[kmax]", "s_mov_b32 s46, %[nit]"])
-        lines = ["; ---- prologue", "s_mov_b64 s[40:41], %[pA]", "s_mov_b64 s[42:43], %[pB]", "s_mov_b32 s44, 0"] + knit + ["s_mov_b32 s47, %[ldsw]",
-                 f"v_mov_b32 v{vb}, %[vA0]", f"v_add_u32 v{vb + 1}, 0x10000, v{vb}", f"v_xor_b32 v{vb + 2}, 64, v{vb}",
-                 f"v_add_u32 v{vb + 3}, 0x10000, v{vb + 2}",
-                 f"v_mov_b32 v{vb + 4}, %[vB0]", f"v_add_u32 v{vb + 5}, 0x10000, v{vb + 4}", f"v_xor_b32 v{vb + 6}, 64, v{vb + 4}",
-                 f"v_add_u32 v{vb + 7}, 0x10000, v{vb + 6}"]
-        # load voffsets: row q*8 further down = + q * (8 rows * ld * 2 B), clamped to the last valid row of the operand
-        va, vbb = vb + 8, vb + 8 + self.NLOAD
-        lines += [f"v_mov_b32 v{va}, %[oA0]", f"v_mov_b32 v{vbb}, %[oB0]"]
-        for q in range(1, self.NLOAD):
-            lines += [f"v_add_u32 v{va + q}, %[sA8], v{va + q - 1}", f"v_add_u32 v{vbb + q}, %[sB8], v{vbb + q - 1}"]
+        if self.am or self.bm:      # the kernel is short of VGPRs for operands: nit, emode, alpha arrive in SGPRs; kmax = 128 nt - 128, nit = nt / 2
+            knit = ["s_mov_b32 s46, %[nit]", "s_lshl_b32 s45, s46, 8", "s_sub_u32 s45, s45, 128"]
+        lines = ["; ---- prologue", "s_mov_b64 s[40:41], %[pA]", "s_mov_b64 s[42:43], %[pB]", "s_mov_b32 s44, 0"] + knit + ["s_mov_b32 s47, %[ldsw]"]
+        if self.am or self.bm:
+            lines.append("s_mov_b32 s58, %[ldswB]")
+        for rm, r0, v0 in ((self.am, self.rA, "%[vA0]"), (self.bm, self.rB, "%[vB0]")):
+            if rm:      # one base per fragment index inside a half (index << 5 XORed in), each for both tile sets
+                nsub = 4 if r0 == self.rA else 2
+                lines += [f"v_xor_b32 v{r0 + 2 * k}, {hex(32 * k) if k == 3 else 32 * k}, {v0}" for k in range(1, nsub)]
+                lines += [f"v_add_u32 v{r0 + 2 * k + 1}, 0x10000, {self.vr(r0 + 2 * k)}" for k in range(nsub)]
+            else:
+                lines += [f"v_mov_b32 v{r0}, {v0}", f"v_add_u32 v{r0 + 1}, 0x10000, v{r0}", f"v_xor_b32 v{r0 + 2}, 64, v{r0}",
+                          f"v_add_u32 v{r0 + 3}, 0x10000, v{r0 + 2}"]
+        # load voffsets, k-contiguous side: row q*8 further down = + q * (8 rows * ld * 2 B), clamped to the last valid row of the operand;
+        # reduction-major side: loads 0 / 2 (the two 128-row halves; stage_src of gemm256.hip, columns past the edge already redirected)
+        # come from the kernel, loads 1 / 3 are the same columns four k-rows further down (%[sA4] / %[sB4] = 4 rows in bytes)
+        va, vbb = self.rV, self.rV + self.NLOAD
+        sides = ((self.am, va, "A"), (self.bm, vbb, "B"))
         for q in range(self.NLOAD):
-            lines += [f"v_min_u32 v{va + q}, v{va + q}, %[oAmax]", f"v_min_u32 v{vbb + q}, v{vbb + q}, %[oBmax]"]
+            for rm, v, n in sides:
+                if rm:
+                    if q & 1:
+                        lines.append(f"v_add_u32 v{v + q}, %[s{n}4], {self.vr(v + q - 1)}")
+                elif q == 0:
+                    lines.append(f"v_mov_b32 v{v}, %[o{n}0]")
+                else:
+                    lines.append(f"v_add_u32 v{v + q}, %[s{n}8], v{v + q - 1}")
+        for q in range(self.NLOAD):
+            lines += [f"v_min_u32 v{v + q}, v{v + q}, %[o{n}max]" for rm, v, n in sides if not rm]
         if "l2pf" in self.flags:
             lines += [f"v_mov_b32 v{self.nvgpr}, %[pfA]", f"v_mov_b32 v{self.nvgpr + 1}, %[pfB]"]
         for g in range(2):                     # the first two K-tiles are on their way before the accumulators are cleared
@@ -605,7 +674,8 @@ class CfgK64(Cfg):
 
     def tail256(self):
         assert (self.FI, self.FJ) == (8, 4)
-        return (["s_waitcnt vmcnt(0)", "s_waitcnt lgkmcnt(0)", "s_barrier", "v_readfirstlane_b32 s53, %[emode]", "s_cmp_eq_u32 s53, 0",
+        return (["s_waitcnt vmcnt(0)", "s_waitcnt lgkmcnt(0)", "s_barrier",
+                 "s_mov_b32 s53, %[emode]" if self.am or self.bm else "v_readfirstlane_b32 s53, %[emode]", "s_cmp_eq_u32 s53, 0",
                  "s_cbranch_scc0 2f"]
                 + self.image_bf16() + ["s_branch 3f", "2:", "s_cmp_eq_u32 s53, 1", "s_cbranch_scc0 4f"] + self.image_f32(0)
                 + ["s_branch 3f", "4:"] + self.image_bf16(rowscale=True) + ["3:", "s_waitcnt lgkmcnt(0)"])
@@ -615,6 +685,9 @@ class CfgK64(Cfg):
             f.write("// generated by tools/gen_gemm_asm.py -- do not edit\n")
             for ln in lines:
                 f.write('"' + ln + '\\n"\n')
+
+
+RM_MODES = ((1, 1), (1, 0), (0, 1))      # (a_mode, b_mode) of the reduction-major product loops: gemm256_kloop_rm<a><b>.inc
 
 
 VARIANTS = {1: {"noglds"}, 2: {"noreads"}, 3: {"noglds", "noreads"}, 4: {"nobarrier"}, 5: {"noprio"}, 6: {"noglds", "noreads", "nobarrier"}}
@@ -633,6 +706,13 @@ def main():
     ck.emit_lines("gemm256_kloop_half1.inc", ck.image_f32(1) + ["s_waitcnt lgkmcnt(0)"])
     ck.emit_clobbers("gemm256_kloop_clobbers.inc", "G256K_CLOBBERS")
     print(f"gemm256 k-loop: {nk} lines")
+    # the same loop on reduction-major operands (wgrad on row-major dY and X, dgrad on W as stored): layout mode per side. They share
+    # the tail (gemm256_kloop_half1.inc) and one clobber list, the largest register map (both sides reduction-major)
+    for am, bm in RM_MODES:
+        cr = CfgK64("8w", 8, 4, 4, ck.flags, am=am, bm=bm)
+        nr = cr.emit(f"gemm256_kloop_rm{am}{bm}.inc")
+        cr.emit_clobbers("gemm256_kloop_rm_clobbers.inc", f"G256K_RM{am}{bm}_CLOBBERS", append=(am, bm) != RM_MODES[0])
+        print(f"gemm256 k-loop, a_mode {am} b_mode {bm}: {nr} lines, {cr.nvgpr} VGPRs")
     # traffic per K-tile; every wave stages 64 rows of A and of B (8 + 8 loads per tile)
     c4 = CfgK64("4w", 8, 8, 8, set(os.environ.get("GEN4W_FLAGS", "hbl,noprio,ls6").split(",")))      # GEN4W_FLAGS: timing experiments
     n4 = c4.emit("gemm_asm_4w_loop.inc")
