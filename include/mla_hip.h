@@ -459,6 +459,28 @@ int mla_gemm_prefill_f8_qkv_rope(const void* xq, long long ldx, const float* x_s
 int mla_gemm_prefill_f8_gateup_swiglu(const void* xq, long long ldx, const float* x_scale, const void* wgu_q, long long ldw,
                                       const float* w_scale, void* act, long long ldo, long long out_batch_stride, int rows_per_batch, int M,
                                       int I, int K, void* workspace, size_t workspace_bytes, mla_stream_t stream);
+/* ---- the wide-row FP8 family (opt-in batch_prefill="fp8": the B x S_p prefix rows of a batched sampling call; the same templates of
+ * mla_amd/csrc/prefill.hip): the contract of mla_gemm_prefill_f8* in every respect -- codes and per-row scales as mla_quant_fp8_rows
+ * writes them, fp32 sums over the unscaled codes, (sum * x_scale[m]) * w_scale[n] before the rotation / SwiGLU / residual, one rounding,
+ * rows_per_batch / out_batch_stride addressing with RoPE table row m % rows_per_batch, deterministic split-K through the caller's
+ * workspace, no atomics, no state, graph-capturable, -1 refusals that launch nothing -- with 1 <= M <= 65536. The plan chooses the row
+ * tile: 64 (the compact kernels and their split rule; always for M <= 1024, where every entry point writes bit for bit what its
+ * mla_gemm_prefill_f8* twin writes) or, for M > 1024 once ceil(M / 128) * (N / 128) >= 3 x CUs, 128: a 2 x 2 grid of waves with 64 W
+ * rows x 64 x rows each (16 accumulators, 32 MACs per LDS byte read against 21), two LDS stages of 32 KiB. Workspace layout
+ * [split][ceil(M / row tile) * row tile][N] fp32. mla_gemm_prefill_f8_wide_plan: out4 = {row tile, column tile, split, workgroups};
+ * the pure-Python mirror is mla_amd/hip.py:plan_gemm_prefill_f8_wide. mla_gemm_prefill_f8* keep refusing M > 1024. */
+int mla_gemm_prefill_f8_wide_plan(int M, int N, int K, int cus, int* out4);
+long long mla_gemm_prefill_f8_wide_ws_bytes(int M, int N, int K);
+int mla_gemm_prefill_f8_wide(const void* xq, long long ldx, const float* x_scale, const void* Wq, long long ldw, const float* w_scale,
+                             void* out, long long ldo, long long out_batch_stride, int rows_per_batch, const void* residual,
+                             long long ld_res, int M, int N, int K, void* workspace, size_t workspace_bytes, mla_stream_t stream);
+int mla_gemm_prefill_f8_wide_qkv_rope(const void* xq, long long ldx, const float* x_scale, const void* Wq, long long ldw,
+                                      const float* w_scale, void* out, long long ldo, long long out_batch_stride, int rows_per_batch, int M,
+                                      int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols, int head_dim,
+                                      void* workspace, size_t workspace_bytes, mla_stream_t stream);
+int mla_gemm_prefill_f8_wide_gateup_swiglu(const void* xq, long long ldx, const float* x_scale, const void* wgu_q, long long ldw,
+                                           const float* w_scale, void* act, long long ldo, long long out_batch_stride, int rows_per_batch,
+                                           int M, int I, int K, void* workspace, size_t workspace_bytes, mla_stream_t stream);
 
 /* ---- device-resident DDIM loop (mla_amd/infer.py _CachedEpsBase.sample_ddim, opt-in sampler="device"; mla_amd/csrc/sampler.hip): the
  * sampler's glue between two suffix passes with the step index in device memory, so that a captured sampler step can be replayed

@@ -78,6 +78,14 @@ _SIGNATURES = {
                                      c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p],
     "mla_gemm_prefill_f8_gateup_swiglu": [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong,
                                           c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p],
+    "mla_gemm_prefill_f8_wide_plan": [c_int, c_int, c_int, c_int, c_void_p],
+    "mla_gemm_prefill_f8_wide_ws_bytes": [c_int, c_int, c_int],   # returns long long (restype fixed up in lib())
+    "mla_gemm_prefill_f8_wide": [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int,
+                                 c_void_p, c_longlong, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p],
+    "mla_gemm_prefill_f8_wide_qkv_rope": [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong,
+                                          c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p],
+    "mla_gemm_prefill_f8_wide_gateup_swiglu": [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong,
+                                               c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p],
     "mla_ddim_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "mla_sampler_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "mla_attn_chunk_split_plan": [c_int, c_int, c_int, c_int, c_int, c_void_p],
@@ -206,6 +214,7 @@ def lib():
         L.mla_attn_bwd_sync_ints.restype = c_longlong
         L.mla_gemm_prefill_ws_bytes.restype = c_longlong
         L.mla_gemm_prefill_f8_ws_bytes.restype = c_longlong
+        L.mla_gemm_prefill_f8_wide_ws_bytes.restype = c_longlong
         L.mla_attn_chunk_split_ws_bytes.restype = c_longlong
         _lib = L
     return _lib
@@ -1122,6 +1131,9 @@ class PrefillKind(NamedTuple):
 PREFILL_KINDS = {"bf16": PrefillKind("", 32, PREFILL_BK, torch.bfloat16),
                  "fp8": PrefillKind("_f8", PREFILL_F8_BK, PREFILL_F8_BK, torch.float8_e4m3fn)}
 _PF_BF16, _PF_F8 = PREFILL_KINDS["bf16"], PREFILL_KINDS["fp8"]
+# the wide-row FP8 family ("_f8_wide" names): _PF_F8's contract for 1 <= M <= 65536, the row tile (64 | 128) chosen by the plan
+PREFILL_WIDE_MMAX, PREFILL_WIDE_BM, PREFILL_WIDE_WGS_PER_CU = 65536, 128, 3
+_PF_F8_WIDE = PREFILL_KIND_F8_WIDE = PrefillKind("_f8_wide", PREFILL_F8_BK, PREFILL_F8_BK, torch.float8_e4m3fn)
 
 
 class PrefillGemmPlan(NamedTuple):
@@ -1138,16 +1150,21 @@ class PrefillGemmPlan(NamedTuple):
 
 
 def _prefill_fits(kind, M, N, K):
-    return 1 <= M <= PREFILL_MMAX and N >= PREFILL_BN and N % PREFILL_BN == 0 and K >= kind.k_gran and K % kind.k_gran == 0
+    return 1 <= M <= (PREFILL_WIDE_MMAX if kind is _PF_F8_WIDE else PREFILL_MMAX) and N >= PREFILL_BN and N % PREFILL_BN == 0 and K >= kind.k_gran and K % kind.k_gran == 0
 
 
 def _prefill_plan(kind, M, N, K, cus):
-    """The launcher's choice (prefill.hip:plan) for an operand kind: 64 x 128 tiles, split-K doubled while tiles x split < 2 x cus,
-    split < 16 and every slice keeps at least 8 K tiles."""
+    """The launcher's choice (prefill.hip:plan / plan_wide) for an operand kind: 64 x 128 tiles -- the wide family: 128 x 128 for M > 1024
+    once those alone give 3 x cus workgroups (measured: profiles/batch_prefill_fp8_infer_latency.txt) --, split-K doubled while tiles x split < 2 x cus, split < 16 and every slice keeps at least
+    8 K tiles."""
+    wide = kind is _PF_F8_WIDE
     if not _prefill_fits(kind, M, N, K):
-        raise ValueError(f"plan_gemm_prefill{kind.infix}: 1 <= M <= {PREFILL_MMAX}, N % {PREFILL_BN} == 0, K % {kind.k_gran} == 0 required "
-                         f"(M {M}, N {N}, K {K})")
-    mt, nt, ktiles = -(-M // PREFILL_BM), N // PREFILL_BN, -(-K // kind.k_tile)
+        raise ValueError(f"plan_gemm_prefill{kind.infix}: 1 <= M <= {PREFILL_WIDE_MMAX if wide else PREFILL_MMAX}, N % {PREFILL_BN} == 0, "
+                         f"K % {kind.k_gran} == 0 required (M {M}, N {N}, K {K})")
+    bm = PREFILL_BM
+    if wide and M > PREFILL_MMAX and -(-M // PREFILL_WIDE_BM) * (N // PREFILL_BN) >= PREFILL_WIDE_WGS_PER_CU * cus:
+        bm = PREFILL_WIDE_BM
+    mt, nt, ktiles = -(-M // bm), N // PREFILL_BN, -(-K // kind.k_tile)
     tiles = mt * nt
     split = 1
     while tiles * split < 2 * cus and split < PREFILL_MAX_SPLIT and ktiles // (split * 2) >= PREFILL_MIN_KTILES:
@@ -1158,7 +1175,7 @@ def _prefill_plan(kind, M, N, K, cus):
         note = (f"{wgs} workgroups < {cus} CUs: " +
                 (f"split-K is capped at {PREFILL_MAX_SPLIT}" if split == PREFILL_MAX_SPLIT else
                  f"K = {K} has {ktiles} K tiles, a slice keeps at least {PREFILL_MIN_KTILES}"))
-    return PrefillGemmPlan(PREFILL_BM, PREFILL_BN, split, wgs, mt * PREFILL_BM, split * mt * PREFILL_BM * N * 4 if split > 1 else 0, note)
+    return PrefillGemmPlan(bm, PREFILL_BN, split, wgs, mt * bm, split * mt * bm * N * 4 if split > 1 else 0, note)
 
 
 def gemm_prefill_fits(M: int, N: int, K: int) -> bool:
@@ -1181,6 +1198,22 @@ def plan_gemm_prefill_f8(M: int, N: int, K: int, cus: int = 256) -> PrefillGemmP
     return _prefill_plan(_PF_F8, M, N, K, cus)
 
 
+def gemm_prefill_f8_wide_fits(M: int, N: int, K: int) -> bool:
+    """As gemm_prefill_f8_fits, for the wide-row family: 1 <= M <= 65536."""
+    return _prefill_fits(_PF_F8_WIDE, M, N, K)
+
+
+def plan_gemm_prefill_f8_wide(M: int, N: int, K: int, cus: int = 256) -> PrefillGemmPlan:
+    """As plan_gemm_prefill_f8, for the wide-row family (mla_gemm_prefill_f8_wide_plan returns the library's): tile_m is 64 or 128; for
+    M <= 1024 it is plan_gemm_prefill_f8's plan."""
+    return _prefill_plan(_PF_F8_WIDE, M, N, K, cus)
+
+
+def gemm_prefill_f8_wide_ws_bytes(M: int, N: int, K: int) -> int:
+    """As gemm_prefill_f8_ws_bytes, for the wide-row family (mla_gemm_prefill_f8_wide_ws_bytes)."""
+    return _PF_F8_WIDE.ws_bytes(M, N, K)
+
+
 def gemm_prefill_ws_bytes(M: int, N: int, K: int) -> int:
     """Workspace bytes the library's launcher needs for the shape (mla_gemm_prefill_ws_bytes); -1 outside the contract."""
     return _PF_BF16.ws_bytes(M, N, K)
@@ -1191,10 +1224,12 @@ def gemm_prefill_f8_ws_bytes(M: int, N: int, K: int) -> int:
     return _PF_F8.ws_bytes(M, N, K)
 
 
-def _prefill(form, scales, x, W, out, ldo, out_batch_stride, rows_per_batch, ws, residual=None, out_col=0, rope=None, head_dim=128):
+def _prefill(form, scales, x, W, out, ldo, out_batch_stride, rows_per_batch, ws, residual=None, out_col=0, rope=None, head_dim=128,
+             wide=False):
     """One launch of the family in the form "" (plain + residual), "_qkv_rope" or "_gateup_swiglu", over bf16 operands x [M, K] / W [N, K]
-    (scales None) or over their FP8 codes with scales = (x_scale [M], w_scale [N])."""
-    kind, q = (_PF_BF16, "") if scales is None else (_PF_F8, "q")
+    (scales None) or over their FP8 codes with scales = (x_scale [M], w_scale [N]); wide: the wide-row entry points (codes only)."""
+    assert not wide or scales is not None
+    kind, q = (_PF_BF16, "") if scales is None else (_PF_F8_WIDE if wide else _PF_F8, "q")
     name = f"gemm_prefill{kind.infix}{form}"
     _req(x, kind.dtype, f"{name} x{q}")
     _req(W, kind.dtype, f"{name} W{q}")
@@ -1265,6 +1300,22 @@ def gemm_prefill_f8_gateup_swiglu(xq, x_scale, wgu_q, w_scale, act, ldo=None, ou
     """gemm_prefill_gateup_swiglu over codes (mla_gemm_prefill_f8_gateup_swiglu): wgu_q = the packed [2 I, K] gate|up codes, w_scale [2 I];
     gate and up are scaled with the scales of their own rows before silu(gate) * up."""
     _prefill("_gateup_swiglu", (x_scale, w_scale), xq, wgu_q, act, ldo, out_batch_stride, rows_per_batch, ws)
+
+
+def gemm_prefill_f8_wide(xq, x_scale, Wq, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, ws=None):
+    """gemm_prefill_f8 for 1 <= M <= 65536 rows (mla_gemm_prefill_f8_wide): the same contract; the plan (plan_gemm_prefill_f8_wide) chooses
+    64- or 128-row tiles, for M <= 1024 the bits are gemm_prefill_f8's. ws: at least gemm_prefill_f8_wide_ws_bytes(M, N, K) bytes."""
+    _prefill("", (x_scale, w_scale), xq, Wq, out, ldo, out_batch_stride, rows_per_batch, ws, residual=residual, out_col=out_col, wide=True)
+
+
+def gemm_prefill_f8_wide_qkv_rope(xq, x_scale, Wq, w_scale, out, ldo, out_batch_stride, rows_per_batch, rope, head_dim=128, ws=None):
+    """gemm_prefill_f8_qkv_rope for 1 <= M <= 65536 rows (mla_gemm_prefill_f8_wide_qkv_rope)."""
+    _prefill("_qkv_rope", (x_scale, w_scale), xq, Wq, out, ldo, out_batch_stride, rows_per_batch, ws, rope=rope, head_dim=head_dim, wide=True)
+
+
+def gemm_prefill_f8_wide_gateup_swiglu(xq, x_scale, wgu_q, w_scale, act, ldo=None, out_batch_stride=0, rows_per_batch=None, ws=None):
+    """gemm_prefill_f8_gateup_swiglu for 1 <= M <= 65536 rows (mla_gemm_prefill_f8_wide_gateup_swiglu)."""
+    _prefill("_gateup_swiglu", (x_scale, w_scale), xq, wgu_q, act, ldo, out_batch_stride, rows_per_batch, ws, wide=True)
 
 
 # --------------------------------------------------------------------------------------------- device-resident DDIM loop (sampler.hip)

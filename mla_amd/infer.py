@@ -32,6 +32,10 @@ Opt-in (`prefill="compact"`, `prefill_precision="fp8"`, see PREFILL_MODES / PREF
 the prefix rows of one observation run on the row-sized GEMMs of csrc/prefill.hip, and with "fp8" their four projections per layer on
 e4m3fn codes of weights AND activations (csrc/prefill.hip, the K = 128 FP8 MFMA) -- the same FP8 weight copy the suffix pass streams.
 
+Opt-in (`batch_prefill="fp8"`, see BATCH_PREFILL_MODES; BatchedPrefixCachedEps and BatchedSampleGroupsEps): the NB x S_pmax right-padded
+prefix rows of a batched call run through the same compact layer in ONE pass per layer, their projections on the wide-row FP8 GEMMs
+(mla_gemm_prefill_f8_wide*: up to 65 536 rows, 64- or 128-row tiles).
+
 Semantics vs the reference: identical arithmetic up to summation order (fp32 accumulation everywhere), with ONE stated difference -- the
 reference's point tokenizer draws fresh random FPS start indices inside every one of the 8 forwards (Point_PN.py:10); here they are
 drawn once per action chunk (the prefix is computed once). With given start indices (`fps_starts_override`, as in
@@ -99,6 +103,35 @@ def check_prefill_precision(mode, prefill="compact"):
     if mode != "bf16" and prefill != "compact":
         raise ValueError(f"prefill_precision={mode!r} runs on the compact prefill (prefill=\"compact\"); prefill={prefill!r} has the bf16 "
                          "kernels only")
+
+
+# How the batched engines prefill the NB x S_pmax right-padded prefix rows of a pass (MLA.predict_action_diff_batch(batch_prefill=...);
+# BatchedPrefixCachedEps, BatchedSampleGroupsEps):
+#   "train"        one varlen pass per layer on the training forward kernels, the bf16 weights (default)
+#   "fp8"          the compact prefill's layer (_compact_layer) over all NB x S_pmax rows at once, its four projections on e4m3fn codes of
+#                  BOTH operands: the wide-row GEMMs of mla_amd/csrc/prefill.hip (mla_gemm_prefill_f8_wide*, up to 65 536 rows, 64- or
+#                  128-row tiles) beyond 1024 rows, the compact ones up to there; the model's FP8 weight copy, shared with
+#                  suffix_weights="fp8"; attention, cache, norms and residual stream stay bf16
+#   "fp8_as_bf16"  per sample, the bf16 compact kernels on bf16(code * scale) of the same weight codes and on quantised-and-dequantised
+#                  inputs: the reference of the "fp8" path (slow: one pass over the layers per sample)
+BATCH_PREFILL_MODES = ("train", "fp8", "fp8_as_bf16")
+
+
+def check_batch_prefill(mode, reuse_prefix=True):
+    """The argument errors of batch_prefill=: an unknown value; anything but "train" without the cached prefix. A shape the engine does
+    not serve is the caller's ValueError (batch_prefill_needs_engine)."""
+    if mode not in BATCH_PREFILL_MODES:
+        raise ValueError(f"batch_prefill must be one of {BATCH_PREFILL_MODES}, got {mode!r}")
+    if mode != "train" and not reuse_prefix:
+        raise ValueError(f"batch_prefill={mode!r} runs on the cached-prefix engines (reuse_prefix=True); the whole-forward sampler has no "
+                         "separate prefill")
+
+
+def batch_prefill_needs_engine(mode, engine: str, n_action_rows: int):
+    """batch_prefill other than "train" on a shape the cached-prefix engine does not serve: an error, never the warned loop."""
+    if mode != "train":
+        raise ValueError(f"batch_prefill={mode!r}: the cached-prefix engine ({engine}) does not serve {1 + n_action_rows} suffix rows per "
+                         "sample at this head_dim; use batch_prefill=\"train\"")
 
 
 # Which attention launch the sampler steps of PrefixCachedEps use (MLA.predict_action_diff(suffix_attention=...)):
@@ -260,7 +293,7 @@ class _CachedEpsBase:
 
     @classmethod
     def _engine(cls, vlm, store: str, key: tuple, ctor: tuple, suffix_weights="bf16", prefill="train", suffix_attention="head",
-                prefill_precision="bf16"):
+                prefill_precision="bf16", batch_prefill="train"):
         """The vlm's engine for `key` in vlm.__dict__[store], constructed as cls(vlm, *ctor) on first use; at most 4 per store, the oldest
         leaves first. A mode other than the default is part of the key -- the engines coexist: a captured graph holds the addresses of
         ITS weights and ITS attention launches. The caller prefills."""
@@ -273,6 +306,8 @@ class _CachedEpsBase:
             key += ("attention:" + suffix_attention,)
         if prefill_precision != "bf16":
             key += ("precision:" + prefill_precision,)
+        if batch_prefill != "train":
+            key += ("batch_prefill:" + batch_prefill,)
         eng = engines.get(key)
         if eng is None:
             if len(engines) >= 4:
@@ -383,14 +418,19 @@ class _CachedEpsBase:
             raise ValueError(f"prefill=\"compact\" serves at most {hip.PREFILL_MMAX} prefix rows at head_dim 128 (got {rows} rows, head_dim "
                              f"{D}); use prefill=\"train\"")
 
-    def _compact_buffers(self, rows: int, dev):
+    def _compact_buffers(self, rows, dev, precision=None):
         """What the compact prefill keeps per engine, allocated once (call outside inference mode): ONE split-K workspace for the four
-        projections of a layer at `rows` rows (the launches of a prefill run one after the other) and, for prefill_precision "fp8", the
-        projection inputs' codes and scales."""
+        projections of a layer at `rows` rows (the launches of a prefill run one after the other) and, for precision "fp8" (default:
+        prefill_precision), the projection inputs' codes and scales. rows: the row count, or every row count the engine may launch (the
+        batched engines: a plan splits less as the rows grow, so the largest row count need not need the largest workspace)."""
         H, I = self.cfg.hidden_size, self.cfg.intermediate_size
-        fp8 = self.prefill_precision == "fp8"
+        fp8 = (self.prefill_precision if precision is None else precision) == "fp8"
+        counts = (rows,) if isinstance(rows, int) else tuple(rows)
+        rows = max(counts)
         kind = hip.PREFILL_KINDS["fp8" if fp8 else "bf16"]
-        need = [kind.ws_bytes(rows, N, K) for N, K in ((3 * H, H), (H, H), (2 * I, H), (H, I))]
+        if fp8 and rows > hip.PREFILL_MMAX:
+            kind = hip.PREFILL_KIND_F8_WIDE
+        need = [kind.ws_bytes(M, N, K) for M in counts for N, K in ((3 * H, H), (H, H), (2 * I, H), (H, I))]
         if min(need) < 0:
             raise ValueError(f"prefill=\"compact\": the projections of this model (hidden {H}, intermediate {I}) are outside the compact "
                              f"GEMMs' contract (N % 128 == 0, K % {kind.k_gran} == 0); use prefill=\"train\"")
@@ -412,15 +452,21 @@ class _CachedEpsBase:
             h = self._compact_layer(w, h, B, S_p, c, out_bs)
         return h
 
-    def _compact_layer(self, w, h, B, S_p, c, out_bs):
+    def _compact_layer(self, w, h, B, S_p, c, out_bs, precision=None, rope=None):
         """One decoder layer of the compact prefill on its weights w (an entry of _prefill_layers()) -> the layer's output rows: rmsnorm_fwd,
         q|k|v + RoPE into the cache c, the training flash attention on the cache's q / k / v views, o + residual, rmsnorm_fwd, gate|up +
         SwiGLU (the product only), down + residual. The precision only decides how a projection's input and weight are presented:
         "bf16" as they are; "fp8_as_bf16" the dequantised weights, every input quantised and dequantised per row; "fp8" the W8 codes and
         scales, every input quantised per row into the engine's code / scale buffers (mla_quant_fp8_rows) for the GEMMs over codes.
-        Norms, attention, cache and residual stream are bf16 throughout."""
-        H, D, ws, M, precision = self.H, self.D, self._prefill_ws, B * S_p, self.prefill_precision
-        if precision == "fp8":
+        Norms, attention, cache and residual stream are bf16 throughout. precision / rope: the batched engines' batch_prefill mode and
+        their tables for S_p rows (default: prefill_precision, cos_p / sin_p); more than 1024 rows of codes run on the wide-row GEMMs."""
+        H, D, ws, M = self.H, self.D, self._prefill_ws, B * S_p
+        precision = self.prefill_precision if precision is None else precision
+        cos_p, sin_p = (self.cos_p, self.sin_p) if rope is None else rope
+        if precision == "fp8" and M > hip.PREFILL_MMAX:
+            ln1, wqkv, wo, ln2, wgu, wd = w
+            plain, qkv_rope, gateup_swiglu = hip.gemm_prefill_f8_wide, hip.gemm_prefill_f8_wide_qkv_rope, hip.gemm_prefill_f8_wide_gateup_swiglu
+        elif precision == "fp8":
             ln1, wqkv, wo, ln2, wgu, wd = w
             plain, qkv_rope, gateup_swiglu = hip.gemm_prefill_f8, hip.gemm_prefill_f8_qkv_rope, hip.gemm_prefill_f8_gateup_swiglu
         else:
@@ -432,11 +478,11 @@ class _CachedEpsBase:
         def operands(x, W):
             if precision == "fp8":
                 K = x.shape[1]
-                return (*hip.quant_fp8_rows(x, self._prefill_xq[:M * K].view(M, K), self._prefill_xs), W.q, W.scale)
+                return (*hip.quant_fp8_rows(x, self._prefill_xq[:M * K].view(M, K), self._prefill_xs[:M]), W.q, W.scale)
             return (_fake_quant_rows(x) if precision == "fp8_as_bf16" else x), W
         ld = c.stride(-2)
         xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
-        qkv_rope(*operands(xn, wqkv), c, ld, out_bs, S_p, (self.cos_p, self.sin_p, 2 * H), D, ws=ws)
+        qkv_rope(*operands(xn, wqkv), c, ld, out_bs, S_p, (cos_p, sin_p, 2 * H), D, ws=ws)
         o = self._prefill_attention(c, B, S_p, ld, out_bs)
         h1 = torch.empty_like(h)
         plain(*operands(o, wo), h1, H, 0, M, residual=h, ws=ws)
@@ -794,6 +840,49 @@ class _RowGemmEps(_CachedEpsBase):
     MAX_ROWS = 256                   # suffix rows per pass (mla_gemm_suffix_bf16 / _w8 and their `_pos` forms); more are served as consecutive passes
     MAX_R = 64                       # rows per sample / group (mla_attn_chunk_ragged, mla_attn_chunk_groups, mla_attn_chunk_ragged_groups)
     BUCKET = 64                      # cache capacity granularity in rows (the engines with ragged prompts)
+    batch_prefill = "train"          # BATCH_PREFILL_MODES: how _varlen_prefill runs the prefix rows (the two engines with ragged prompts)
+
+    def _batch_prefill_buffers(self, NB: int, G: int, dev):
+        """batch_prefill "fp8" / "fp8_as_bf16": the compact prefill's buffers at the engine's capacity, allocated once (call outside
+        inference mode). An engine serves every S_pmax of its capacity bucket: S_cap - G R - BUCKET < S_pmax <= S_cap - G R."""
+        if self.batch_prefill == "train":
+            return
+        hi = self.S_cap - G * self.R
+        lengths = range(max(1, hi - self.BUCKET + 1), hi + 1)
+        if self.batch_prefill == "fp8":
+            self._compact_buffers([NB * S for S in lengths], dev, "fp8")
+        else:                                                                # the yardstick runs one sample at a time
+            self._compact_buffers(list(lengths), dev, "fp8_as_bf16")
+
+    def _check_batch_prefill(self, NB: int, S_pmax: int):
+        """What the batch prefill serves: "fp8" up to 65 536 rows per sub-batch (the wide-row GEMMs), "fp8_as_bf16" up to 1024 prefix rows
+        per sample (the compact bf16 GEMMs); anything else is an error, never a silent "train" prefill."""
+        if self.batch_prefill == "fp8" and NB * S_pmax > hip.PREFILL_WIDE_MMAX:
+            raise ValueError(f"batch_prefill=\"fp8\" serves at most {hip.PREFILL_WIDE_MMAX} prefill rows per sub-batch (got {NB} x {S_pmax} = "
+                             f"{NB * S_pmax}); use batch_prefill=\"train\" or fewer observations per call")
+        if self.batch_prefill == "fp8_as_bf16" and S_pmax > hip.PREFILL_MMAX:
+            raise ValueError(f"batch_prefill=\"fp8_as_bf16\" serves at most {hip.PREFILL_MMAX} prefix rows per sample (got {S_pmax}); use "
+                             "batch_prefill=\"train\"")
+
+    def _batch_compact_prefill(self, prefix, NB: int, S_pmax: int, rope):
+        """batch_prefill "fp8": every layer ONCE over the NB * S_pmax right-padded prefix rows (_compact_layer with B = NB: the q|k|v
+        epilogue writes sample b's rows at cache offset b * cache.stride(0)), on the wide-row GEMMs beyond 1024 rows. No ragged
+        addressing is needed: attention is causal and the padding is on the right, so a valid row never sees a pad row. A pad row
+        starts as zeros -- the quantiser gives it scale 1 and codes 0 -- and stays finite through every layer; pad rows land in cache
+        rows [S_p[b], S_pmax) that no suffix row reads before the suffix pass has overwritten them, exactly as the "train" prefill's
+        c[:, :S_pmax].copy_. "fp8_as_bf16": the same layers per sample (B = 1, at most 1024 rows) on the dequantised weight codes and
+        the quantised-and-dequantised inputs."""
+        self._weights()
+        layers = self._quantised(self._packed_key, self.batch_prefill)
+        if self.batch_prefill == "fp8":
+            h = prefix.reshape(NB * S_pmax, self.H)
+            for w, c in zip(layers, self.cache):
+                h = self._compact_layer(w, h, NB, S_pmax, c, c.stride(0), "fp8", rope)
+            return
+        for b in range(NB):
+            h = prefix[b]
+            for w, c in zip(layers, self.cache):
+                h = self._compact_layer(w, h, 1, S_pmax, c[b], 0, "fp8_as_bf16", rope)
 
     def _cache_write(self, c):
         """-> (ldo, out_batch_stride, keywords) of the q|k|v projection into the layer's cache c (rows_per_batch is R)."""
@@ -859,10 +948,11 @@ class _RowGemmEps(_CachedEpsBase):
     def _varlen_prefill(self, sub, front, proprio, G, index):
         """The prefill of observations [sub.start, sub.stop) with G groups of suffix rows each: the prefixes right-padded to S_pmax, one
         varlen pass per layer on the training kernels (ops.DecoderLayerFn._fwd with seqlens; the bf16 weights, whatever the suffix pass
-        streams), the rows copied into the [NB, S_cap, 3H] cache. index: {attribute: values} of the int32 device tensors the suffix
+        streams), the rows copied into the [NB, S_cap, 3H] cache -- or, batch_prefill "fp8" / "fp8_as_bf16", _batch_compact_prefill. index: {attribute: values} of the int32 device tensors the suffix
         pass's kernels read, allocated on the first call and refreshed by copy_ (a captured graph keeps their addresses)."""
         vlm, bf16, dev = self.vlm, torch.bfloat16, front.device
         NB, S_pmax = sub.stop - sub.start, sub.S_pmax
+        self._check_batch_prefill(NB, S_pmax)
         with torch.no_grad():
             proprio_e = vlm.proprio_embedder(proprio.to(bf16))                # [NB, 1, H]
             H = front.shape[2]
@@ -883,11 +973,15 @@ class _RowGemmEps(_CachedEpsBase):
                     for name, values in index.items():
                         setattr(self, name, torch.zeros(len(values), dtype=torch.int32, device=dev))
                     self._split_workspace(NB, G, self.S_cap, True, dev)
+                    self._batch_prefill_buffers(NB, G, dev)
             assert (NB, G, H, sub.S_cap, sub.R) == (self.NB, self.G, self.H, self.S_cap, self.R) and S_pmax + G * self.R <= self.S_cap
             for name, values in index.items():
                 getattr(self, name).copy_(torch.tensor(values, dtype=torch.int32))
             seqlens = torch.tensor(sub.S_p, dtype=torch.int32, device=dev)
             cos_p, sin_p = self.rot.tables(S_pmax, dev)
+            if self.batch_prefill != "train":
+                self._batch_compact_prefill(prefix, NB, S_pmax, (cos_p, sin_p))
+                return
             h = prefix.reshape(NB * S_pmax, H)
             for w, c in zip(self._weights(), self.cache):
                 h, acts = ops.DecoderLayerFn._fwd(h, seqlens, cos_p, sin_p, NB, S_pmax, self.nheads, self.eps, w)
@@ -896,7 +990,7 @@ class _RowGemmEps(_CachedEpsBase):
 
 
 class BatchedPrefixCachedEps(_RowGemmEps):
-    """PrefixCachedEps for B samples whose splice tags sit at different positions (bf16 weights only). The cache is [B, S_cap, 3H] and the
+    """PrefixCachedEps for B samples whose splice tags sit at different positions (bf16 suffix weights only; the prefill per batch_prefill). The cache is [B, S_cap, 3H] and the
     suffix rows of sample b live at rows S_p[b] .. S_p[b] + R (rows behind them are never read). `slot` and `kv_len` are device tensors
     the kernels read (mla_gemm_suffix_bf16, mla_attn_chunk_ragged), refreshed by copy_ in prefill(): one engine -- and one captured graph
     -- per (B, S_cap, R, device) serves every mix of prompt lengths in that capacity bucket."""
@@ -911,16 +1005,20 @@ class BatchedPrefixCachedEps(_RowGemmEps):
 
     @classmethod
     def for_batch(cls, vlm, ids_rows, n_action_rows: int, images=None, point_cloud=None, camera_name=None, proprio=None, add_tail=True,
-                  suffix_attention: str = "head", **unused):
+                  suffix_attention: str = "head", batch_prefill: str = "train", **unused):
         """Generator over the passes of one call: runs the encoders once over all samples, plans (plan_batch: ids_rows are the prompts as
         the caller has them, the prompt tail is handled there) and yields
         (SubBatchPlan, prefilled engine) per sub-batch. Two sub-batches may share an engine: finish sampling one before taking the next.
-        suffix_attention: "head" (mla_attn_chunk_ragged) or "split" (mla_attn_groups_split, one group per sample); one engine per mode."""
+        suffix_attention: "head" (mla_attn_chunk_ragged) or "split" (mla_attn_groups_split, one group per sample); batch_prefill:
+        BATCH_PREFILL_MODES; one engine per mode."""
         check_groups_attention(suffix_attention)
+        check_batch_prefill(batch_prefill)
         front = cls._front_tokens(vlm, images, point_cloud, camera_name)
         for sub in plan_batch(ids_rows, n_action_rows, int(front.shape[1]), cls.MAX_ROWS, cls.BUCKET, add_tail=add_tail):
             eng = cls._engine(vlm, "_prefix_engines_batched", (sub.stop - sub.start, sub.S_cap, sub.R, str(front.device)),
-                              (n_action_rows, "bf16", "train", suffix_attention), suffix_attention=suffix_attention)
+                              (n_action_rows, "bf16", "train", suffix_attention), suffix_attention=suffix_attention,
+                              batch_prefill=batch_prefill)
+            eng.batch_prefill = batch_prefill
             eng.prefill(sub, front[sub.start:sub.stop], proprio[sub.start:sub.stop])
             yield sub, eng
 
@@ -1120,12 +1218,14 @@ class BatchedSampleGroupsEps(_RowGemmEps):
 
     @classmethod
     def for_batch(cls, vlm, ids_rows, n_action_rows: int, num_samples: int, suffix_weights: str = "bf16", images=None, point_cloud=None,
-                  camera_name=None, proprio=None, add_tail=True, suffix_attention: str = "head", **unused):
+                  camera_name=None, proprio=None, add_tail=True, suffix_attention: str = "head", batch_prefill: str = "train", **unused):
         """Generator over the passes of one call: runs the encoders once over all observations, plans (plan_batch_samples) and yields
         (SampleSubBatchPlan, prefilled engine) per sub-batch. Two sub-batches may share an engine: finish sampling one before taking the
-        next. suffix_attention: "head" (mla_attn_chunk_ragged_groups) or "split" (mla_attn_groups_split); one engine per mode."""
+        next. suffix_attention: "head" (mla_attn_chunk_ragged_groups) or "split" (mla_attn_groups_split); batch_prefill:
+        BATCH_PREFILL_MODES; one engine per mode."""
         check_suffix_weights(suffix_weights)
         check_groups_attention(suffix_attention)
+        check_batch_prefill(batch_prefill)
         front = cls._front_tokens(vlm, images, point_cloud, camera_name)
         plans = plan_batch_samples(ids_rows, n_action_rows, int(front.shape[1]), num_samples, cls.MAX_ROWS, cls.BUCKET, add_tail=add_tail)
         if plans is None:
@@ -1133,7 +1233,8 @@ class BatchedSampleGroupsEps(_RowGemmEps):
         for sub in plans:
             eng = cls._engine(vlm, "_prefix_engines_batch_samples", (sub.stop - sub.start, sub.G, sub.S_cap, sub.R, str(front.device)),
                               (n_action_rows, suffix_weights, "train", suffix_attention), suffix_weights,
-                              suffix_attention=suffix_attention)
+                              suffix_attention=suffix_attention, batch_prefill=batch_prefill)
+            eng.batch_prefill = batch_prefill
             eng.prefill(sub, front[sub.start:sub.stop], proprio[sub.start:sub.stop])
             yield sub, eng
 

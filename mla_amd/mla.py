@@ -485,7 +485,7 @@ class MLA(nn.Module):
                                   reuse_prefix: bool = True, suffix_weights: str = "bf16",
                                   num_samples: Optional[int] = None, prefill: str = "train", sampler: str = "host",
                                   suffix_attention: str = "head", prefill_precision: str = "bf16",
-                                  groups_attention: str = "head") -> np.ndarray:
+                                  groups_attention: str = "head", batch_prefill: str = "train") -> np.ndarray:
         """B observations -> [B, T, action_dim]: by definition B independent `predict_action_diff` calls (the reference's
         `predict_action_batch`, model_mla.py:994, is dead code), computed on ONE cached prefix pass per DDIM step
         (mla_amd/infer.py:BatchedPrefixCachedEps): the prompts may have different lengths, the FPS start indices are drawn once per chunk.
@@ -505,10 +505,23 @@ class MLA(nn.Module):
         the engine does not serve warns once and loops the same way. All three ``suffix_weights`` modes are accepted (N = 1 included: this
         is how B >= 2 observations get FP8 suffix weights); anything but "bf16" raises ValueError when ``reuse_prefix=False`` or the
         engine does not serve the shape.
-        ``prefill``: only "train" -- the batched prefill has B x S rows and belongs to the training GEMMs; "compact" raises
-        NotImplementedError (use predict_action_diff / predict_action_diff_samples per observation).
+        ``prefill``: only "train" -- the one-observation compact prefill is predict_action_diff's / predict_action_diff_samples';
+        "compact" raises NotImplementedError (the batched engines take their FP8 prefill from ``batch_prefill``).
         ``prefill_precision``: only "bf16", for the same reason; "fp8" / "fp8_as_bf16" raise NotImplementedError, an unknown value
         ValueError.
+        ``batch_prefill`` (opt-in, cached prefix only), with and without ``num_samples``: "train" (default) prefills the B x S_p prefix
+        rows of a pass on the training kernels | "fp8": every prefill layer runs once over all right-padded prefix rows of the pass with
+        its four projections on e4m3fn codes of BOTH operands -- the wide-row GEMMs of mla_amd/csrc/prefill.hip
+        (mla_gemm_prefill_f8_wide*: up to 65 536 rows, 64- or 128-row tiles on the K = 128 MFMA), the model's FP8 weight copy (one per
+        model, shared with ``suffix_weights="fp8"``) and the projection inputs quantised per row; attention, cache and residual stream
+        stay bf16 | "fp8_as_bf16": per observation, the bf16 compact kernels on the dequantised weight codes and on
+        quantised-and-dequantised inputs -- the same function as "fp8" up to rounding, slow, the yardstick of "fp8" and what the format
+        costs on a checkpoint. The effect on a trained policy is not measured. Only the prefill changes: it composes with every
+        ``suffix_weights`` (with ``num_samples``), ``sampler`` and ``groups_attention`` mode; where the call ends in a single-observation
+        method (B = 1, N beyond a pass) it is forwarded as ``prefill="compact", prefill_precision=<value>``; it raises ValueError for an
+        unknown value, for anything but "train" when ``reuse_prefix=False`` or the batched engine does not serve the shape (never the
+        warned loop), for more than 65 536 prefill rows in a sub-batch ("fp8") and for more than 1024 prefix rows per observation
+        ("fp8_as_bf16"): there is never a silent bf16 prefill.
         ``sampler``: predict_action_diff's, with and without ``num_samples``: "device" runs every pass's DDIM loop on the device (the same
         bits) and raises ValueError where "host" would loop over whole-forward calls (``reuse_prefix=False``, a shape the batched engine
         does not serve) or run the DDPM sampler.
@@ -523,11 +536,12 @@ class MLA(nn.Module):
         call ends in predict_action_diff (B = 1, no ``num_samples`` or N = 1) it is forwarded as ``suffix_attention="split"``; it raises
         ValueError for an unknown value, and for "split" when ``reuse_prefix=False`` or the batched engine does not serve the shape: it is
         never the warned loop."""
-        from .infer import (BatchedPrefixCachedEps, check_prefill_precision, groups_attention_needs_engine, sampler_needs_engine,
-                            suffix_attention_single_only)
+        from .infer import (BatchedPrefixCachedEps, batch_prefill_needs_engine, check_batch_prefill, check_prefill_precision,
+                            groups_attention_needs_engine, sampler_needs_engine, suffix_attention_single_only)
         MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps,
                          groups_attention=groups_attention)
         check_prefill_precision(prefill_precision)                           # an unknown value only: no mode but "bf16" is served here
+        check_batch_prefill(batch_prefill, reuse_prefix)
         if prefill != "train":
             raise NotImplementedError(f"prefill={prefill!r}: the batched engines prefill B x S rows on the training GEMMs; the compact "
                                       "prefill serves one observation (predict_action_diff, predict_action_diff_samples)")
@@ -542,7 +556,8 @@ class MLA(nn.Module):
         if num_samples is not None:
             return self._predict_action_diff_batch_samples(images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix,
-                                                           suffix_weights, num_samples, sampler, suffix_attention, groups_attention)
+                                                           suffix_weights, num_samples, sampler, suffix_attention, groups_attention,
+                                                           batch_prefill)
         input_ids, pointclouds = MLA._batch_prompts(self, B, instructions, input_ids, pointclouds, cur_robot_states)
         if noise is not None and tuple(noise.shape[:2]) != (B, T):
             raise ValueError(f"noise must be [B, T, action_dim] = [{B}, {T}, ...], got {tuple(noise.shape)}")
@@ -553,9 +568,11 @@ class MLA(nn.Module):
             return self.predict_action_diff(images[b], pointclouds[b], None, cur_robot_states[b], unnorm_key, cfg_scale, use_ddim, num_ddim_steps,
                                             action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b:b + 1],
                                             camera_name=camera_name, **kw)
+        # a call that ends in a single-observation method takes the mode as that method's compact prefill
+        single = {} if batch_prefill == "train" else {"prefill": "compact", "prefill_precision": batch_prefill}
         if B == 1:
             return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler,
-                       suffix_attention="split" if groups_attention == "split" else suffix_attention)[None]
+                       suffix_attention="split" if groups_attention == "split" else suffix_attention, **single)[None]
         if suffix_weights != "bf16":
             raise NotImplementedError(f"suffix_weights={suffix_weights!r}: the batched engine (BatchedPrefixCachedEps, mla_gemm_suffix_bf16) "
                                       "streams bf16 weights only; sample B >= 2 observations with \"bf16\", one at a time, or pass "
@@ -563,6 +580,7 @@ class MLA(nn.Module):
         if reuse_prefix:
             if not BatchedPrefixCachedEps.supports_batch(self.vlm, T, warn=False):     # raised, not a warned loop of batch-1 calls
                 groups_attention_needs_engine(groups_attention, "BatchedPrefixCachedEps", T)
+                batch_prefill_needs_engine(batch_prefill, "BatchedPrefixCachedEps", T)
             reuse_prefix = BatchedPrefixCachedEps.supports_batch(self.vlm, T)
         if not reuse_prefix:
             sampler_needs_engine(sampler, "BatchedPrefixCachedEps", T)
@@ -570,14 +588,15 @@ class MLA(nn.Module):
         device, ids_rows, inputs = self._batch_inputs(images, pointclouds, cur_robot_states, ids_rows, unnorm_key, camera_name)
         x0 = self._draw_x0([None if noise is None else noise[b:b + 1] for b in range(B)], T, action_dim, device)
         out = []
-        for sub, eng in BatchedPrefixCachedEps.for_batch(self.vlm, ids_rows, T, suffix_attention=groups_attention, **inputs):
+        for sub, eng in BatchedPrefixCachedEps.for_batch(self.vlm, ids_rows, T, suffix_attention=groups_attention,
+                                                         batch_prefill=batch_prefill, **inputs):
             samples = self._sample(eng, x0[sub.start:sub.stop].contiguous(), sampler, use_ddim, num_ddim_steps, {})
             out.append(samples.float().cpu().numpy())
         return self._actions(out, unnorm_key)
 
     def _predict_action_diff_batch_samples(self, images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix, suffix_weights, num_samples,
-                                           sampler="host", suffix_attention="head", groups_attention="head"):
+                                           sampler="host", suffix_attention="head", groups_attention="head", batch_prefill="train"):
         """predict_action_diff_batch(num_samples=N) -> [B, N, T, action_dim] (called inside its inference mode; see its docstring)."""
         B, N, T = len(images), int(num_samples), self.future_action_window_size + 1
         if N < 1:
@@ -592,30 +611,33 @@ class MLA(nn.Module):
             return self.predict_action_diff_samples(images[b], pointclouds[b], None, cur_robot_states[b], unnorm_key, N, cfg_scale, use_ddim,
                                                     num_ddim_steps, action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b],
                                                     camera_name=camera_name, **kw)
+        single = {} if batch_prefill == "train" else {"prefill": "compact", "prefill_precision": batch_prefill}
         if B == 1:
             return samples_of(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler,
-                              suffix_attention=suffix_attention, groups_attention=groups_attention)[None]
+                              suffix_attention=suffix_attention, groups_attention=groups_attention, **single)[None]
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
                              "bf16 weights only")
         if reuse_prefix:
-            from .infer import BatchedSampleGroupsEps, groups_attention_needs_engine, sampler_needs_engine
+            from .infer import BatchedSampleGroupsEps, batch_prefill_needs_engine, groups_attention_needs_engine, sampler_needs_engine
             if not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T, warn=False):
                 sampler_needs_engine(sampler, "BatchedSampleGroupsEps", T)
                 groups_attention_needs_engine(groups_attention, "BatchedSampleGroupsEps", T)
+                batch_prefill_needs_engine(batch_prefill, "BatchedSampleGroupsEps", T)
             if suffix_weights != "bf16" and not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T, warn=False):
                 raise ValueError(f"suffix_weights={suffix_weights!r}: the batched shared-prefix engine (BatchedSampleGroupsEps) does not serve "
                                  f"{1 + T} suffix rows per sample at this head_dim; draw the samples with \"bf16\"")
             if not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T) or not BatchedSampleGroupsEps.fits_pass(T, N):
                 # one observation at a time: predict_action_diff_samples serves (or refuses) the shape and the mode itself
-                return np.stack([samples_of(b, suffix_weights=suffix_weights, sampler=sampler, groups_attention=groups_attention)
+                return np.stack([samples_of(b, suffix_weights=suffix_weights, sampler=sampler, groups_attention=groups_attention, **single)
                                  for b in range(B)])
         else:
             return np.stack([samples_of(b, reuse_prefix=False) for b in range(B)])
         device, ids_rows, inputs = self._batch_inputs(images, pointclouds, cur_robot_states, ids_rows, unnorm_key, camera_name)
         x0 = self._draw_x0([None if noise is None else noise[b, n:n + 1] for b in range(B) for n in range(N)], T, action_dim, device)   # rows (b, n)
         out = []
-        for sub, eng in BatchedSampleGroupsEps.for_batch(self.vlm, ids_rows, T, N, suffix_weights, suffix_attention=groups_attention, **inputs):
+        for sub, eng in BatchedSampleGroupsEps.for_batch(self.vlm, ids_rows, T, N, suffix_weights, suffix_attention=groups_attention,
+                                                         batch_prefill=batch_prefill, **inputs):
             samples = self._sample(eng, x0[sub.start * N:sub.stop * N].contiguous(), sampler, use_ddim, num_ddim_steps, {})
             out.append(samples.float().cpu().numpy().reshape(sub.stop - sub.start, N, T, -1))
         return self._actions(out, unnorm_key)

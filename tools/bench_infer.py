@@ -63,6 +63,14 @@
                                                           --kernel-table first prints, without the model, one launch (pair) per splits in
                                                           {1, 2, 3, plan} of mla_attn_groups_split against the route's head launch at 32
                                                           heads and 545 prefix rows; --pairs 0 stops after the table
+    python tools/bench_infer.py --batch B[,B..] --pair-batch-prefill [--chunks C[,C..]] [--pairs P] [--kernel-table]
+                                                          predict_action_diff_batch with batch_prefill="train" and "fp8" in one process,
+                                                          alternating: per-call latency and the engines' prefill behind the encoders
+                                                          (embedding + the decoder rows of the B x S_p prefix) with the 95 % interval of
+                                                          the pair differences; --kernel-table first prints, without the model, one launch
+                                                          per 7B projection shape at M = 1090, 2180 and 4360: the wide-row FP8 GEMM against
+                                                          the training kernel and against the 64-row FP8 kernel run in slices of at most
+                                                          1024 rows; --pairs 0 stops after the table
 Prints one JSON line per measurement (not the driver's bench contract -- that is bench.py)."""
 import argparse
 import json
@@ -146,6 +154,7 @@ def main():
     ap.add_argument("--pair-sampler", action="store_true", help="alternate sampler=\"host\" and sampler=\"device\" in one process, in pairs")
     ap.add_argument("--pair-attention", action="store_true", help="alternate suffix_attention=\"head\" and \"split\" in one process, in pairs; with --samples / --batch: groups_attention "
                     "on the multi-row routes")
+    ap.add_argument("--pair-batch-prefill", action="store_true", help="with --batch: alternate batch_prefill=\"train\" and \"fp8\" in one process, in pairs")
     ap.add_argument("--pairs", type=int, default=6)
     ap.add_argument("--kernel-table", action="store_true", help="with --pair-fp8: the two _w8 kernels per projection shape and M; with "
                     "--samples: mla_attn_chunk_groups per groups-per-workgroup against mla_attn_chunk_ragged")
@@ -155,6 +164,8 @@ def main():
     if args.pair_sampler:
         return main_pair_sampler(args)
     batches = [int(v) for v in args.batch.split(",")]
+    if args.pair_batch_prefill:
+        return main_pair_batch_prefill(args, batches)
     if args.pair_attention:
         return main_pair_groups_attention(args, batches) if args.samples or batches != [0] else main_pair_attention(args)
     if args.samples and batches != [0]:
@@ -1024,6 +1035,136 @@ def main_batch_samples(args, batches):
             for store in ("_prefix_engines_batch_samples", "_prefix_engines_samples"):     # the caches of this (B, N, mode)
                 m.vlm.__dict__.get(store, {}).clear()
             torch.cuda.empty_cache()
+
+
+def _wide_prefill_table(dev, Ms=(1090, 2180, 4360), H=4096, I=11008, S=545, copies=16, reps=3):
+    """One launch per 7B projection shape and row count, us per launch, captured into a graph as a run over `copies` weight matrices
+    (268 MB of codes for the smallest projection: nothing stays in the caches): "wide" = mla_gemm_prefill_f8_wide* with the library's
+    plan, "train" = the training kernel of the same form on bf16 operands, "fp8_64_sliced" = mla_gemm_prefill_f8* (64-row tiles) in
+    slices of at most 1024 rows. Random weights, no model."""
+    from mla_amd import hip
+    bf16 = torch.bfloat16
+    inv = 1.0 / (10000.0 ** (torch.arange(0, 128, 2).float() / 128))
+    fr = torch.outer(torch.arange(S).float(), inv)
+    cos, sin = fr.cos().contiguous().to(dev), fr.sin().contiguous().to(dev)
+    shapes = {"qkv_rope": (3 * H, H), "o_res": (H, H), "gateup_swiglu": (2 * I, H), "down_res": (H, I)}
+    table = {}
+    for name, (N, K) in shapes.items():
+        Wb = [(torch.randn(N, K, device=dev) * 0.02).to(bf16) for _ in range(copies)]
+        W8 = [hip.quant_fp8_rows(w) for w in Wb]
+        for M in Ms:
+            assert M % S == 0
+            x = (torch.randn(M, K, device=dev) * 0.5).to(bf16)
+            xq, xs = hip.quant_fp8_rows(x)
+            res = torch.randn(M, H, device=dev).to(bf16)
+            out = torch.empty(M, I if name == "gateup_swiglu" else N, dtype=bf16, device=dev)
+            slices = [(m0, min(1024, M - m0)) for m0 in range(0, M, 1024)]
+            ws = torch.empty(max([hip.gemm_prefill_f8_wide_ws_bytes(M, N, K), 16] +
+                                 [hip.gemm_prefill_f8_ws_bytes(n, N, K) for n in {S} | {n for _, n in slices}]), dtype=torch.uint8, device=dev)
+            if name == "qkv_rope":
+                rope = (cos, sin, 2 * H)
+                train = lambda i: hip.gemm_qkv_rope(x, Wb[i], out, cos, sin, S, 2 * H)                                   # noqa: E731
+                wide = lambda i: hip.gemm_prefill_f8_wide_qkv_rope(xq, xs, *W8[i], out, N, S * N, S, rope, 128, ws=ws)  # noqa: E731
+                # a slice of whole samples keeps the table rows right: 545-row samples, at most one per 1024-row slice
+                slices = [(m0, S) for m0 in range(0, M, S)]
+                sliced = lambda i: [hip.gemm_prefill_f8_qkv_rope(xq[a:a + n], xs[a:a + n], *W8[i], out[a:a + n], N, 0, S, rope, 128, ws=ws)   # noqa: E731
+                                    for a, n in slices]
+            elif name == "gateup_swiglu":
+                train = lambda i: hip.gemm_gateup_swiglu(x, Wb[i], False, want_gu=False) or False                       # noqa: E731
+                wide = lambda i: hip.gemm_prefill_f8_wide_gateup_swiglu(xq, xs, *W8[i], out, ws=ws)                     # noqa: E731
+                sliced = lambda i: [hip.gemm_prefill_f8_gateup_swiglu(xq[a:a + n], xs[a:a + n], *W8[i], out[a:a + n], ws=ws)   # noqa: E731
+                                    for a, n in slices]
+            else:
+                train = lambda i: hip.gemm(x, Wb[i], out, residual=res)                                                 # noqa: E731
+                wide = lambda i: hip.gemm_prefill_f8_wide(xq, xs, *W8[i], out, N, 0, M, residual=res, ws=ws)            # noqa: E731
+                sliced = lambda i: [hip.gemm_prefill_f8(xq[a:a + n], xs[a:a + n], *W8[i], out[a:a + n], N, 0, n, residual=res[a:a + n], ws=ws)   # noqa: E731
+                                    for a, n in slices]
+            cell = {}
+            for kname, fn in (("train", train), ("fp8_64_sliced", sliced), ("wide", wide)):
+                for i in range(2):
+                    assert fn(i) is not False
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    for i in range(copies):
+                        fn(i)
+                g.replay()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(reps):
+                    g.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                cell[kname] = round(e0.elapsed_time(e1) / (reps * copies) * 1e3, 1)
+            p = hip.plan_gemm_prefill_f8_wide(M, N, K)
+            cell["wide_plan"] = {"tile_m": p.tile_m, "split": p.split, "workgroups": p.workgroups}
+            cell["slices"] = len(slices)
+            for kname in ("train", "fp8_64_sliced", "wide"):
+                cell[kname + "_tflops"] = round(2.0 * M * N * K / (cell[kname] * 1e-6) / 1e12, 1)
+            table[f"{name}/M{M}"] = cell
+        del Wb, W8
+        torch.cuda.empty_cache()
+    return table
+
+
+def main_pair_batch_prefill(args, batches):
+    """predict_action_diff_batch(batch_prefill="train") vs (batch_prefill="fp8") on the same box, alternating, for every B of --batch and
+    chunk of --chunks: (a) the call, (b) engine.prefill() behind the encoders = embedding + the decoder rows of the B x S_pmax prefix."""
+    from mla_amd.infer import BatchedPrefixCachedEps
+    dev = torch.device("cuda", 0)
+    if args.kernel_table:
+        print(json.dumps({"metric": "wide-row FP8 prefill GEMMs, 7B projection shapes: us per launch", "unit": "us",
+                          "projection_us_per_launch": _wide_prefill_table(dev), "data": "synthetic"}), flush=True)
+    if args.pairs <= 0:
+        return
+    chunks = [int(v) for v in args.chunks.split(",")] if args.chunks else [args.chunk]
+    modes = ("train", "fp8")
+    m = None
+    for chunk in chunks:
+        for B in batches:
+            m, b, ids = _setup(chunk, B, model=m)
+            ids = list(ids)
+            images, pcs, states = (list(v) for v in zip(*(_observation(b, i) for i in range(B))))
+            noise = torch.randn(B, chunk, 7, device=dev)
+
+            def call(mode):
+                return m.predict_action_diff_batch(images, pcs, cur_robot_states=states, input_ids=ids, noise=noise, num_ddim_steps=args.steps,
+                                                   batch_prefill=mode)
+            acts = {mode: call(mode) for mode in modes}                      # engines, graphs, packed weights, the FP8 copy
+            mk = dict(images=torch.stack(images), point_cloud=torch.stack(pcs), camera_name="rlbench_front", proprio=b["proprio"][:B])
+            rows = [[int(t) for t in r] for r in ids]
+            with torch.inference_mode():
+                front = BatchedPrefixCachedEps._front_tokens(m.vlm, mk["images"], mk["point_cloud"], mk["camera_name"])
+                subs = {mode: list(BatchedPrefixCachedEps.for_batch(m.vlm, rows, chunk, batch_prefill=mode, **mk)) for mode in modes}
+
+            def prefill_ms(mode, reps=3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                with torch.inference_mode():
+                    e0.record()
+                    for _ in range(reps):
+                        for sub, eng in subs[mode]:
+                            eng.prefill(sub, front[sub.start:sub.stop], mk["proprio"][sub.start:sub.stop])
+                    e1.record()
+                    torch.cuda.synchronize()
+                return e0.elapsed_time(e1) / reps
+            call_ms, pre_ms = {mode: [] for mode in modes}, {mode: [] for mode in modes}
+            for _ in range(args.pairs):
+                for mode in modes:
+                    call_ms[mode].append(_time_ms(lambda: call(mode), args.iters))
+            for mode in modes:
+                prefill_ms(mode, 1)
+            for _ in range(args.pairs):
+                for mode in modes:
+                    pre_ms[mode].append(prefill_ms(mode))
+            rel = float(((acts["fp8"] - acts["train"]) ** 2).sum() ** 0.5 / (acts["train"] ** 2).sum() ** 0.5)
+            print(json.dumps({"metric": "predict_action_diff_batch, MLA-Llama2-7B: batch_prefill=train vs fp8 in alternating order", "batch": B,
+                              "action_chunk": chunk, "prefill_rows": [sub.S_pmax * (sub.stop - sub.start) for sub, _ in subs["fp8"]],
+                              "ddim_steps": args.steps, "pairs": args.pairs, "unit": "ms",
+                              "call_ms": {mode: [round(v, 2) for v in vs] for mode, vs in call_ms.items()},
+                              "call_fp8_minus_train": _pair_stats(call_ms["train"], call_ms["fp8"]),
+                              "prefill_behind_encoders_ms": {mode: [round(v, 2) for v in vs] for mode, vs in pre_ms.items()},
+                              "prefill_behind_encoders_fp8_minus_train": _pair_stats(pre_ms["train"], pre_ms["fp8"]),
+                              "fp8_vs_train_chunk_rel_diff_random_weights": round(rel, 4), "data": "synthetic"}), flush=True)
 
 
 def main_batch(args):
