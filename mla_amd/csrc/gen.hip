@@ -515,7 +515,7 @@ extern "C" int mla_softmax_rows_fwd(const float* scores, void* P, void* Pd, long
 }
 extern "C" int mla_softmax_rows_bwd(const void* dPd, int dpd_fp32, const void* P, void* dS, long long rows, int ncols, int nvalid, float p,
                                     unsigned long long seed, hipStream_t stream) {
-  MLA_CHECK_ARG(dPd && P && dS && rows > 0 && nvalid <= ncols, "mla_softmax_rows_bwd: bad args");
+  MLA_CHECK_ARG(dPd && P && dS && rows > 0 && nvalid > 0 && nvalid <= ncols && p >= 0.f && p < 1.f, "mla_softmax_rows_bwd: bad args");
   if (dpd_fp32)
     hipLaunchKernelGGL(softmax_rows_bwd_kernel<float>, dim3((unsigned)rows), dim3(256), 0, stream, (const float*)dPd, (const bf16_t*)P, (bf16_t*)dS,
                        ncols, nvalid, p, seed);
@@ -530,7 +530,7 @@ extern "C" int mla_dropout_fwd(const void* x, const void* residual, void* y, lon
   MLA_LAUNCH_CHECK();
 }
 extern "C" int mla_dropout_bwd(const void* dy, void* dx, long long n, float p, unsigned long long seed, hipStream_t stream) {
-  MLA_CHECK_ARG(dy && dx && n > 0, "mla_dropout_bwd: bad args");
+  MLA_CHECK_ARG(dy && dx && n > 0 && p >= 0.f && p < 1.f, "mla_dropout_bwd: bad args");
   hipLaunchKernelGGL(dropout_bwd_kernel, dim3(gridn(n)), dim3(256), 0, stream, (const bf16_t*)dy, (bf16_t*)dx, n, p, seed);
   MLA_LAUNCH_CHECK();
 }
@@ -566,7 +566,7 @@ extern "C" int mla_seqmean_fwd(const void* x, void* y, int B, int S, int C, hipS
   MLA_LAUNCH_CHECK();
 }
 extern "C" int mla_seqmean_bwd(const void* dy, void* dx, int B, int S, int C, hipStream_t stream) {
-  MLA_CHECK_ARG(dy && dx, "mla_seqmean_bwd: bad args");
+  MLA_CHECK_ARG(dy && dx && B > 0 && S > 0 && C > 0, "mla_seqmean_bwd: bad args");
   const long long n = (long long)B * S * C;
   hipLaunchKernelGGL(seqmean_bwd_kernel, dim3(gridn(n)), dim3(256), 0, stream, (const bf16_t*)dy, (bf16_t*)dx, S, C, n);
   MLA_LAUNCH_CHECK();
@@ -575,7 +575,7 @@ extern "C" int mla_bn_bwd_blocks(long long rows) { long long r = rows / 1024; re
 // workspace >= blocks*2*C + 2*C floats. dw/db (+)= sums; dx = BatchNorm(train) input gradient
 extern "C" int mla_bn_bwd(const void* dy, const void* x, const float* mean, const float* var, const void* w, void* dx, float* dw, float* db,
                           int accumulate, long long rows, int C, float eps, float* workspace, size_t workspace_bytes, hipStream_t stream) {
-  MLA_CHECK_ARG(dy && x && mean && var && w && dx && workspace && rows > 0, "mla_bn_bwd: bad args");
+  MLA_CHECK_ARG(dy && x && mean && var && w && dx && workspace && rows > 0 && C > 0, "mla_bn_bwd: bad args");
   const int P = mla_bn_bwd_blocks(rows);
   MLA_CHECK_ARG(workspace_bytes >= ((size_t)P * 2 * C + 2 * C) * sizeof(float), "mla_bn_bwd: workspace too small");
   float* sums = workspace + (size_t)P * 2 * C;
@@ -592,7 +592,8 @@ extern "C" int mla_bn_bwd(const void* dy, const void* x, const float* mean, cons
 // loss[0] = mean_b( mean_n d1 + mean_m d2 ); d1/i1 [B,N], d2/i2 [B,M] kept for backward. N, M <= 4096
 extern "C" int mla_chamfer_fwd(const float* pred, const float* gt, float* d1, int* i1, float* d2, int* i2, float* loss, int B, int N, int M,
                                float* workspace, size_t workspace_bytes, hipStream_t stream) {
-  MLA_CHECK_ARG(pred && gt && d1 && i1 && d2 && i2 && loss && workspace && N <= 4096 && M <= 4096, "mla_chamfer_fwd: bad args (N, M <= 4096)");
+  MLA_CHECK_ARG(pred && gt && d1 && i1 && d2 && i2 && loss && workspace && B > 0 && N > 0 && M > 0 && N <= 4096 && M <= 4096,
+                "mla_chamfer_fwd: bad args (N, M <= 4096)");
   MLA_CHECK_ARG(workspace_bytes >= 2 * sizeof(float), "mla_chamfer_fwd: workspace too small");
   hipLaunchKernelGGL(chamfer_min_kernel, dim3((N + 255) / 256, B), dim3(256), M * 3 * sizeof(float), stream, pred, gt, d1, i1, N, M);
   hipLaunchKernelGGL(chamfer_min_kernel, dim3((M + 255) / 256, B), dim3(256), N * 3 * sizeof(float), stream, gt, pred, d2, i2, M, N);
@@ -604,6 +605,7 @@ extern "C" int mla_chamfer_fwd(const float* pred, const float* gt, float* d1, in
 extern "C" int mla_chamfer_bwd(const float* pred, const float* gt, const float* d1, const int* i1, const float* d2, const int* i2,
                                const float* gscale, float* dpred, int B, int N, int M, hipStream_t stream) {
   MLA_CHECK_ARG(pred && gt && d1 && i1 && d2 && i2 && gscale && dpred, "mla_chamfer_bwd: null pointer");
+  MLA_CHECK_ARG(B > 0 && N > 0 && M > 0, "mla_chamfer_bwd: bad shape (B, N, M > 0)");
   hipLaunchKernelGGL(chamfer_bwd_kernel, dim3((N + 255) / 256, B), dim3(256), 0, stream, pred, gt, d1, i1, d2, i2, gscale, dpred, B, N, M);
   MLA_LAUNCH_CHECK();
 }
@@ -612,7 +614,7 @@ extern "C" int mla_chamfer_bwd(const float* pred, const float* gt, const float* 
 extern "C" int mla_imgloss_fwd(const void* delta_raw, int ld, const void* curr, const void* next, int img_fp32, float* sums, int B,
                                int CT_curr, int CT_next, int HW, int ps, float clip, float* workspace, size_t workspace_bytes,
                                hipStream_t stream) {
-  MLA_CHECK_ARG(delta_raw && curr && next && sums && workspace && HW % ps == 0 && ld >= 3 * ps * ps, "mla_imgloss_fwd: bad args");
+  MLA_CHECK_ARG(delta_raw && curr && next && sums && workspace && ps > 0 && HW % ps == 0 && ld >= 3 * ps * ps, "mla_imgloss_fwd: bad args");
   const int nb = 2048;
   MLA_CHECK_ARG(workspace_bytes >= (size_t)nb * 3 * sizeof(float), "mla_imgloss_fwd: workspace too small");
   const int npatch = (HW / ps) * (HW / ps);
@@ -628,6 +630,7 @@ extern "C" int mla_imgloss_fwd(const void* delta_raw, int ld, const void* curr, 
 extern "C" int mla_imgloss_bwd(const void* delta_raw, int ld, const void* curr, const void* next, int img_fp32, const float* gscale,
                                void* ddelta_raw, int B, int CT_curr, int CT_next, int HW, int ps, float clip, hipStream_t stream) {
   MLA_CHECK_ARG(delta_raw && curr && next && gscale && ddelta_raw, "mla_imgloss_bwd: null pointer");
+  MLA_CHECK_ARG(B > 0 && ps > 0 && HW > 0 && HW % ps == 0 && ld >= 3 * ps * ps, "mla_imgloss_bwd: bad shape (HW %% ps == 0, ld >= 3 ps^2)");
   const int npatch = (HW / ps) * (HW / ps);
   const long long n = (long long)B * npatch * 3 * ps * ps;
   if (img_fp32)
@@ -646,7 +649,7 @@ extern "C" int mla_imgroi_fwd(const void* delta_raw, int ld, const void* a_raw, 
                               const unsigned char* roi, const void* curr, const void* next, int img_fp32, float* sums, int B, int CT_curr,
                               int CT_next, int HW, int ps, float clip, float shift, float* workspace, size_t workspace_bytes,
                               hipStream_t stream) {
-  MLA_CHECK_ARG(delta_raw && a_raw && o_raw && roi && curr && next && sums && workspace && HW % ps == 0 && ld >= 3 * ps * ps && ldo >= 2,
+  MLA_CHECK_ARG(delta_raw && a_raw && o_raw && roi && curr && next && sums && workspace && ps > 0 && HW % ps == 0 && ld >= 3 * ps * ps && ldo >= 2,
                 "mla_imgroi_fwd: bad args");
   const int npatch = (HW / ps) * (HW / ps);
   MLA_CHECK_ARG(workspace_bytes >= (size_t)B * npatch * 4 * sizeof(float), "mla_imgroi_fwd: workspace too small");
@@ -668,6 +671,8 @@ extern "C" int mla_imgroi_bwd(const void* delta_raw, int ld, const void* a_raw, 
                               void* ddelta_raw, float* dalpha_raw, float* doff_raw, int B, int CT_curr, int CT_next, int HW, int ps,
                               float clip, float shift, hipStream_t stream) {
   MLA_CHECK_ARG(delta_raw && a_raw && o_raw && roi && curr && next && coef && ddelta_raw && dalpha_raw && doff_raw, "mla_imgroi_bwd: null pointer");
+  MLA_CHECK_ARG(B > 0 && ps > 0 && HW > 0 && HW % ps == 0 && ld >= 3 * ps * ps && ldo >= 2,
+                "mla_imgroi_bwd: bad shape (HW %% ps == 0, ld >= 3 ps^2, ldo >= 2)");
   const int npatch = (HW / ps) * (HW / ps);
   if (img_fp32)
     hipLaunchKernelGGL((imgroi_kernel<float, 1>), dim3(B * npatch), dim3(256), 0, stream, (const bf16_t*)delta_raw, ld, (const bf16_t*)a_raw, lda,

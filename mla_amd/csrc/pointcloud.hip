@@ -684,6 +684,7 @@ extern "C" int mla_lga_prep_bwd(const void* drows, const long long* fps_idx, con
 }
 extern "C" int mla_maxpool_k_bwd(const void* x, const void* dy, void* dx, long long groups, int K, int C, hipStream_t stream) {
   MLA_CHECK_ARG(x && dy && dx, "mla_maxpool_k_bwd: null pointer");
+  MLA_CHECK_ARG(groups > 0 && K > 0 && C > 0, "mla_maxpool_k_bwd: bad shape (groups, K, C > 0)");
   hipLaunchKernelGGL(maxpool_k_bwd_kernel, dim3(gridn(groups * C)), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx,
                      groups, K, C);
   MLA_LAUNCH_CHECK();

@@ -247,7 +247,7 @@ extern "C" int mla_local_attn_bwd(const void* q, const void* kv, const void* dou
 }
 
 extern "C" int mla_avgpool_tokens_bwd(const void* dy, const void* other, void* dx, int B, int gh, int gw, int C, int cs, hipStream_t stream) {
-  MLA_CHECK_ARG(dy && dx && gh % cs == 0 && gw % cs == 0, "mla_avgpool_tokens_bwd: bad args");
+  MLA_CHECK_ARG(dy && dx && B > 0 && gh > 0 && gw > 0 && C > 0 && cs > 0 && gh % cs == 0 && gw % cs == 0, "mla_avgpool_tokens_bwd: bad args");
   hipLaunchKernelGGL(avgpool_tokens_bwd_kernel, dim3(gridn((long long)B * gh * gw * C)), dim3(256), 0, stream, (const bf16_t*)dy,
                      (const bf16_t*)other, (bf16_t*)dx, B, gh, gw, C, cs);
   MLA_LAUNCH_CHECK();

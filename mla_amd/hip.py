@@ -1906,7 +1906,9 @@ def avgpool_tokens_bwd(dy, other, B, gh, gw, cs):
 
 
 def imgroi_fwd(delta_raw, a_raw, o_raw, roi_u8, curr, nxt, ps, clip, shift):
-    """sums[4] = ROI sum diff^2, ROI sum |diff|, background sum |diff|, sum |delta| (see mla_imgroi_fwd)."""
+    """sums[4] = ROI sum diff^2, ROI sum |diff|, background sum |diff|, sum |delta| (see mla_imgroi_fwd).
+    delta_raw is [B, npatch, ld]; a_raw and o_raw are 2-D, [B * npatch, lda] and [B * npatch, ldo >= 2], one row per patch (as
+    ops.ImageGenRoiLossFn passes them): stride(0) is taken as the row pitch, column 0 of a_raw and columns 0..1 of o_raw are read."""
     B, npatch, ld = delta_raw.shape
     if curr.dtype != nxt.dtype or curr.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError("imgroi: curr/next images must both be fp32 or both bf16")
@@ -1919,6 +1921,8 @@ def imgroi_fwd(delta_raw, a_raw, o_raw, roi_u8, curr, nxt, ps, clip, shift):
 
 
 def imgroi_bwd(delta_raw, a_raw, o_raw, roi_u8, curr, nxt, ps, clip, shift, coef):
+    """(ddelta_raw [B, npatch, ld] bf16 with the padding columns zeroed, dalpha_raw [B * npatch] fp32, doff_raw [B * npatch, 2] fp32).
+    a_raw and o_raw are 2-D with one row per patch, exactly as in imgroi_fwd: stride(0) is the row pitch."""
     B, npatch, ld = delta_raw.shape
     dev = delta_raw.device
     dd = torch.empty_like(delta_raw)
