@@ -102,6 +102,11 @@ int mla_gemm_gateup_swiglu(const void* x, const void* wgu, void* gu, void* act, 
  * (the wgrad then reads dgu as a reduction-major operand): the transposed strip and its LDS staging are skipped. */
 int mla_gemm_dact_swiglu_bwd(const void* dy, const void* wT, const void* gu, void* dgu, void* dguT, int M, int I, int K, int lda,
                              int ldb, long long ldt, mla_stream_t stream);
+/* the same launch on the down-projection weight AS STORED: w [K, I] row-major (K = hidden size, row stride ldb >= I, a reduction-major B
+ * operand like b_mode 1 of mla_gemm_bf16), so the caller keeps no W^T copy. Same K order and accumulation order per output:
+ * bit-identical to mla_gemm_dact_swiglu_bwd on transpose(w). Same shape contract; I % 8 == 0, ldb % 8 == 0. */
+int mla_gemm_dact_swiglu_bwd_rm(const void* dy, const void* w, const void* gu, void* dgu, void* dguT, int M, int I, int K, int lda,
+                                int ldb, long long ldt, mla_stream_t stream);
 
 /* ---- RMSNorm folded into the projections (round 6): fused RMSNorm + QKV + RoPE and fused RMSNorm + gate|up + SwiGLU, one launch each.
  * LlamaRMSNorm (modeling_llama.py:76-90) feeds only projections (:351-353 q/k/v, :240 gate/up), and y W^T with y = g * (x * rstd)

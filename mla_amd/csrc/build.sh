@@ -33,7 +33,7 @@ done
 for p in "${pids[@]}"; do wait $p; done
 # gemm256's assembly-loop kernels keep their accumulators in a0..a127 across two inline-asm statements: prove from the device assembly
 # that the compiler touches no accumulation register (and spills nothing) outside the assembly
-python3 "$HERE/../../tools/check_kloop_asm.py" "$BUILD/gemm256.s" 6     # <0,0,EPI,true> x 3 + the reduction-major <1,1> <1,0> <0,1>
+python3 "$HERE/../../tools/check_kloop_asm.py" "$BUILD/gemm256.s" 7     # <0,0,EPI,true> x 3 + the reduction-major <1,1> <1,0> <0,1> + <0,1,2,true> (SwiGLU backward, W as stored)
 # the opt-in assembly attention forward keeps accumulators, Q and the next tile's scores in physical registers between its statements
 python3 "$HERE/../../tools/check_attn_asm.py" "$BUILD/attention.s"
 # explicit object list: a stale build/<removed source>.o must not be linked

@@ -144,14 +144,16 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs p) {
   f32x4_t acc[8][4];
   if constexpr (ASM) {
     // ---- hand-scheduled main loop (gemm256_kloop.inc, generated by tools/gen_gemm_asm.py; an even number of K-tiles; k-contiguous
-    // operands, or -- plain epilogue only -- the gemm256_kloop_rm*.inc forms with a reduction-major side, further down).
+    // operands, or the gemm256_kloop_rm*.inc forms with a reduction-major side, further down: plain epilogue, and <0, 1> with the fused
+    // SwiGLU backward -- the down-projection dgrad on W_down [H, I] as stored).
     // Same LDS operand image, same K order and the same accumulation order per output as the compiler-scheduled loop below:
     // bit-identical results. Three barriers per K-tile instead of eight, no vmcnt(0) in the loop, and the 8 loads of a wave spread over
     // 43 of its 64 MFMA gaps (one per 6): the waves of a workgroup run in lockstep, so a burst of loads in one wave is a burst of eight
     // times as many in the CU's single address path and stalls every issuer (round 3: MfmaUtil 65 % -> 84 % on the 4-wave form of this
     // loop). The last pair of K-tiles runs in a peeled copy of the loop body that prefetches nothing.
     // The accumulators leave the assembly through LDS: the loop's tail writes the tile image the epilogues below read.
-    static_assert(EPI == 0 || (AMODE == 0 && BMODE == 0), "the fused epilogues take k-contiguous operands");
+    static_assert(EPI == 0 || (AMODE == 0 && BMODE == 0) || (EPI == 2 && AMODE == 0 && BMODE == 1),
+                  "the fused epilogues take k-contiguous operands (SwiGLU backward: or the weight as stored, B reduction-major)");
     const unsigned c0 = ((unsigned)lg ^ ((unsigned)li & 7u)) << 4;
     const unsigned vA0 = (unsigned)((wr * 64 + li) * 128) + c0, vB0 = 32768u + (unsigned)((wc * 32 + li) * 128) + c0;
     // staging: instruction q (0..3) of this wave writes LDS rows wave*32 + q*8 + (lane >> 3) of A and of B, lane's 16-B chunk pre-swizzled
@@ -1348,7 +1350,25 @@ int launch256(const GemmArgs& p, hipStream_t stream, int persistent_grid) {
     // and the whole-row epilogue (the loop's tail writes the tile image). Same bits as the compiler-scheduled loop below.
     const bool fast = (p.N & 7) == 0 && (p.ldc & 7) == 0 && (((uintptr_t)p.C) & 15) == 0 &&
                       (p.R == nullptr || ((p.ldr & 7) == 0 && (((uintptr_t)p.R) & 15) == 0)) && (p.bias == nullptr || (((uintptr_t)p.bias) & 15) == 0);
-    if (kloop_mode() && (p.K % 128) == 0 && fast) {
+    if (p.sw_gu) {       // fused d(act) + SwiGLU backward on the weight as stored (the dispatcher admits it for <0, 1> only, never with a tail)
+      if constexpr (AM == 0 && BM_ == 1) {
+        // LDS: the operand ring (a reduction-major half-tile fills its 16 KiB slot like a k-contiguous one) + the epilogue's second
+        // transposed strip = 160 KiB, the CU's whole LDS and what <0, 0, 2> asks for
+        if (kloop_mode() && (p.K % 128) == 0) {
+          launch_asm<2, 0, 1>(p, dim3(tiles), 2 * BUF + 32768, stream);
+        } else {
+          static bool attr_sw = false;
+          if (!attr_sw) {
+            hipFuncSetAttribute((const void*)gemm256_kernel<0, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * BUF + 32768);
+            attr_sw = true;
+          }
+          hipLaunchKernelGGL((gemm256_kernel<0, 1, 2>), dim3(tiles), dim3(512), 2 * BUF + 32768, stream, p);
+        }
+      } else {
+        mla_set_error("gemm256: the fused SwiGLU backward reads only its B operand reduction-major");
+        return -1;
+      }
+    } else if (kloop_mode() && (p.K % 128) == 0 && fast) {
       if (p.sk_split > 1) {
         const int tail = tiles - p.sk_full;
         launch_asm<0, AM, BM_>(p, dim3(p.sk_full + tail * p.sk_split), 2 * BUF, stream);
@@ -1502,6 +1522,26 @@ extern "C" int mla_gemm_dact_swiglu_bwd(const void* dy, const void* wT, const vo
   return mla_gemm256_dispatch(&p, 0, 0, 0, stream);     // no split-K tail (its fix-up pass has no SwiGLU epilogue)
 }
 
+// mla_gemm_dact_swiglu_bwd on the down-projection weight AS STORED: w [K = H, I] row-major with row stride ldb >= I (reduction-major B,
+// b_mode 1 of mla_gemm_bf16), so the caller keeps no W^T copy. Same K order and accumulation order per output as the k-contiguous launch
+// on transpose(w): bit-identical outputs.
+extern "C" int mla_gemm_dact_swiglu_bwd_rm(const void* dy, const void* w, const void* gu, void* dgu, void* dguT, int M, int I, int K,
+                                           int lda, int ldb, long long ldt, hipStream_t stream) {
+  MLA_CHECK_ARG(dy && w && gu && dgu, "mla_gemm_dact_swiglu_bwd_rm: null pointer");      // (dguT may be null: row-major output only)
+  MLA_CHECK_ARG(M >= 256 && I >= 256 && K > 0 && K % 64 == 0 && I % 8 == 0 && M % 8 == 0,
+                "mla_gemm_dact_swiglu_bwd_rm: needs M, I >= 256, K %% 64 == 0, I %% 8 == 0, M %% 8 == 0");
+  MLA_CHECK_ARG(lda >= K && ldb >= I && lda % 8 == 0 && ldb % 8 == 0 && ldt >= M && ldt % 8 == 0,
+                "mla_gemm_dact_swiglu_bwd_rm: leading dimensions must be multiples of 8 (lda >= K, ldb >= I, ldt >= M)");
+  MLA_CHECK_ARG((size_t)64 * (size_t)ldb * 2 < 0x80000000ULL, "mla_gemm_dact_swiglu_bwd_rm: ldb too large (64 weight rows must span < 2 GiB)");
+  MLA_CHECK_ARG(((((uintptr_t)dy) | ((uintptr_t)w) | ((uintptr_t)gu) | ((uintptr_t)dgu) | ((uintptr_t)dguT)) & 15) == 0,
+                "mla_gemm_dact_swiglu_bwd_rm: 16-B alignment required");
+  GemmArgs p{};
+  p.A = (const bf16_t*)dy; p.B = (const bf16_t*)w; p.C = dgu /* never written: the epilogue returns before the plain stores */;
+  p.M = M; p.N = I; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = 2 * I; p.alpha = 1.f;
+  p.sw_gu = (const bf16_t*)gu; p.sw_dgu = (bf16_t*)dgu; p.sw_dguT = (bf16_t*)dguT; p.sw_I = I; p.sw_ldt = ldt;
+  return mla_gemm256_dispatch(&p, 0, 1, 0, stream);     // no split-K tail (its fix-up pass has no SwiGLU epilogue)
+}
+
 // ---- RMSNorm folded into the projections (round 6; the kernel north_star names: fused RMSNorm + RoPE + QKV). LlamaRMSNorm
 // (modeling_llama.py:76-90) computes y = g * bf16(x * rstd) and the projection (:351-353, :240) y W^T. The row scale commutes with the
 // product: y W^T = rstd (.) ((x * g) W^T). So the GEMM that PRODUCES x (o_proj / down_proj + residual) also leaves x * g and the
@@ -1600,8 +1640,8 @@ extern "C" int mla_gemm_sq_slots(int M, int N, int K, size_t workspace_bytes) {
 
 int mla_gemm256_dispatch(const void* args, int a_mode, int b_mode, size_t ws_bytes, hipStream_t stream, int* sq_slots) {
   GemmArgs p = *(const GemmArgs*)args;
-  if ((a_mode != 0 || b_mode != 0) && (p.sf_I || p.sw_gu || p.rope_cos)) {
-    mla_set_error("gemm256: the fused epilogues take k-contiguous operands only");
+  if ((a_mode != 0 || b_mode != 0) && (p.sf_I || p.rope_cos || (p.sw_gu && !(a_mode == 0 && b_mode == 1)))) {
+    mla_set_error("gemm256: the fused epilogues take k-contiguous operands only (SwiGLU backward: or B reduction-major)");
     return -1;
   }
   p.sk_split = 1;
@@ -1664,7 +1704,8 @@ int mla_gemm256_dispatch(const void* args, int a_mode, int b_mode, size_t ws_byt
   const bool use_p = (persist || (p.debug & 0x100)) && (p.debug & 0x80) == 0 && tiles > grid && bytesA < 0x7fffffffULL && bytesB < 0x7fffffffULL &&
                      p.sf_I == 0 && p.sw_gu == nullptr && p.rope_cos == nullptr && p.sq_out == nullptr && p.nrm_xg == nullptr && p.rs_rstd == nullptr;     // the persistent walk has the plain epilogue only
   if (sq_slots) *sq_slots = p.sk_split > 1 ? p.sk_full + (tiles - p.sk_full) * 64 : tiles;
-  // reduction-major operands ([K, rows] storage, fragments gathered with ds_read_b64_tr_b16): plain epilogue, split-K tail allowed
+  // reduction-major operands ([K, rows] storage, fragments gathered with ds_read_b64_tr_b16): plain epilogue, split-K tail allowed;
+  // <0, 1> also with the fused SwiGLU backward (no tail)
   if (a_mode == 0 && b_mode == 1) return launch256<0, 1>(p, stream, 0);
   if (a_mode == 1 && b_mode == 0) return launch256<1, 0>(p, stream, 0);
   if (a_mode == 1 && b_mode == 1) return launch256<1, 1>(p, stream, 0);

@@ -113,6 +113,8 @@ _SIGNATURES = {
                                c_void_p],
     "mla_gemm_dact_swiglu_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong,
                                  c_void_p],
+    "mla_gemm_dact_swiglu_bwd_rm": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong,
+                                    c_void_p],
     "mla_rmsnorm_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
     "mla_rmsnorm_apply": [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p],
     "mla_rmsnorm_prep": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
@@ -503,6 +505,45 @@ def gemm_dact_swiglu_bwd(dy2d, wT, gu2d, want_t=True):
     if prof is not None:
         ev1.record()
         prof.append((ev0, ev1, 2.0 * T * I * K, (0, 0, T, I, K, "swiglu_bwd_epilogue")))
+    return dgu, dguT
+
+
+def dact_swiglu_bwd_rm_ok(dy2d, w, gu2d) -> bool:
+    """Whether gemm_dact_swiglu_bwd_rm serves these operands (the caller's dispatch; the library checks the same contract itself)."""
+    T, K = dy2d.shape
+    I = w.shape[1]
+    return (T >= 256 and I >= 256 and K % 64 == 0 and I % 8 == 0 and T % 8 == 0 and w.shape[0] == K and w.stride(1) == 1 and
+            gu2d.shape == (T, 2 * I) and gu2d.is_contiguous() and dy2d.stride(1) == 1 and dy2d.stride(0) % 8 == 0 and
+            w.stride(0) % 8 == 0 and all(t.data_ptr() % 16 == 0 for t in (dy2d, w, gu2d)))
+
+
+def gemm_dact_swiglu_bwd_rm(dy2d, w, gu2d, want_t=True, dgu=None, dguT=None):
+    """gemm_dact_swiglu_bwd on the down-projection weight AS STORED, w [K, I] (a row-strided view is fine): d(act) = dy2d @ w without a
+    W^T copy; the bits of gemm_dact_swiglu_bwd(dy2d, transpose(w), ...). No shape filter here: what the kernel does not serve is an
+    error from the library. dgu / dguT: optional output buffers ([T, 2I] / [2I, T] contiguous)."""
+    T, K = dy2d.shape
+    I = w.shape[1]
+    for t, nm in ((dy2d, "dy"), (w, "w"), (gu2d, "gu")):
+        _req(t, torch.bfloat16, "gemm_dact_swiglu_bwd_rm " + nm)
+    if w.shape[0] != K or w.stride(1) != 1 or dy2d.stride(1) != 1 or gu2d.shape != (T, 2 * I) or not gu2d.is_contiguous():
+        raise ValueError("gemm_dact_swiglu_bwd_rm: needs dy [T, K], w [K, I] (unit column stride), gu [T, 2I] contiguous")
+    if dgu is None:
+        dgu = torch.empty_like(gu2d)
+    if dguT is None and want_t:
+        dguT = torch.empty((2 * I, T), dtype=torch.bfloat16, device=gu2d.device)
+    if not want_t:
+        dguT = None
+    for t, shp, nm in ((dgu, (T, 2 * I), "dgu"), (dguT, (2 * I, T), "dguT")):
+        if t is not None and (t.shape != shp or not t.is_contiguous() or t.dtype != torch.bfloat16):
+            raise ValueError(f"gemm_dact_swiglu_bwd_rm: {nm} must be a contiguous bf16 {shp}")
+    prof = GEMM_PROFILE
+    if prof is not None:
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+    call("mla_gemm_dact_swiglu_bwd_rm", _p(dy2d), _p(w), _p(gu2d), _p(dgu), _p(dguT), T, I, K, dy2d.stride(0), w.stride(0), T)
+    if prof is not None:
+        ev1.record()
+        prof.append((ev0, ev1, 2.0 * T * I * K, (0, 1, T, I, K, "swiglu_bwd_epilogue")))
     return dgu, dguT
 
 

@@ -606,10 +606,13 @@ _RECOMPUTE_LEAN = os.environ.get("MLA_RECOMPUTE_LEAN", "1") != "0"   # A/B switc
 # 1 = dy AND x row-major, no transposed buffer is made for that GEMM at all; "a" = dy row-major, x^T where a producer leaves it for free
 # (rmsnorm_apply_t at save levels 0 / 1 / 3, o^T next to dqkv^T out of the attention backward), x row-major otherwise.
 # MLA_WGRAD_RM = 0 | 1 | comma list of name[=0|1|a]; unnamed GEMMs of a list are off. The results do not depend on it (same K order, same
-# bits). Default = what won its pair at T = 17 536 (profiles/wgrad_rm_gemm_pairs.txt): the reduction-major launch costs +1.8 ... +4.1 %
-# with both operands as stored, +1.0 ... +2.0 % with dy alone, against the price of the copies it removes; wq|wk|wv has no copy of its own
-# to remove while wo keeps the attention backward's transposed outputs.
+# bits). Default = what won its pair at T = 17 536 (profiles/backward_as_stored_gemm_pairs.txt; wgrad_rm_gemm_pairs.txt before it): the
+# reduction-major launch costs +2.1 ... +3.4 % with both operands as stored against the price of the copies it removes. wqkv = 1 and
+# wo = 1 TOGETHER let the attention backward drop its transposed outputs (-99 us per layer against +44 us of launch penalty), and at save
+# level 1 the forward's xn1 / xn2 are kept row-major for wqkv = 1 / wgu = 1 (DecoderLayerFn.forward), which removes the rmsnorm_apply_t
+# passes (-52 us each): every GEMM reads both operands as stored.
 _WGRAD_RM_NAMES = ("wd", "wgu", "wo", "wqkv")
+_WGRAD_RM_DEFAULT = "1"
 
 
 def _parse_wgrad_rm(spec: str):
@@ -625,7 +628,7 @@ def _parse_wgrad_rm(spec: str):
     return out
 
 
-_WGRAD_RM = _parse_wgrad_rm(os.environ.get("MLA_WGRAD_RM", "wd=1,wgu=a,wo=a"))
+_WGRAD_RM = _parse_wgrad_rm(os.environ.get("MLA_WGRAD_RM", _WGRAD_RM_DEFAULT))
 
 
 def set_wgrad_rm(spec) -> dict:
@@ -633,6 +636,56 @@ def set_wgrad_rm(spec) -> dict:
     global _WGRAD_RM
     prev, _WGRAD_RM = _WGRAD_RM, (dict(spec) if isinstance(spec, dict) else _parse_wgrad_rm(str(spec)))
     return prev
+
+
+# Input-gradient GEMMs of DecoderLayerFn on the weights AS STORED (reduction-major B operand, gemm256's generated main loop for b_mode 1;
+# the fused d(act) + SwiGLU-backward launch through mla_gemm_dact_swiglu_bwd_rm) instead of on a W^T copy made by a tile transpose in
+# front of every launch. Per GEMM: dqkv (dxn1 = dqkv [Wq|Wk|Wv]), do (do = dh1 Wo), dgu (dxn2 = dgu [Wg|Wu]), dd (d(act) = dy Wd).
+# MLA_DGRAD_RM = 0 | 1 | comma list of name[=0|1]; unnamed GEMMs of a list are off. Same K order, same bits. Weights that are not
+# adjacent in the flat buffer, and shapes outside the 256x256 kernel, take the copying path. Default = what won its line at T = 17 536
+# in profiles/backward_as_stored_gemm_pairs.txt (launch penalty against the W^T pass it removes).
+_DGRAD_RM_NAMES = ("dqkv", "do", "dgu", "dd")
+_DGRAD_RM_DEFAULT = "1"       # every line won: -27 (dqkv), -11 (do), -82 (dgu), -19 us (dd, the fused <0,1,2> launch) per layer
+
+
+def _parse_dgrad_rm(spec: str):
+    spec = spec.strip()
+    if spec in ("0", "1"):
+        return dict.fromkeys(_DGRAD_RM_NAMES, int(spec))
+    out = dict.fromkeys(_DGRAD_RM_NAMES, 0)
+    for item in filter(None, (s.strip() for s in spec.split(","))):
+        name, _, val = item.partition("=")
+        if name not in out or val not in ("", "0", "1"):
+            raise ValueError(f"MLA_DGRAD_RM: bad item {item!r} (names {_DGRAD_RM_NAMES}, values 0 / 1)")
+        out[name] = int(val or "1")
+    return out
+
+
+_DGRAD_RM = _parse_dgrad_rm(os.environ.get("MLA_DGRAD_RM", _DGRAD_RM_DEFAULT))
+
+
+def set_dgrad_rm(spec) -> dict:
+    """A/B switch for tests and tools (MLA_DGRAD_RM syntax, or a dict a previous call returned); returns the previous setting."""
+    global _DGRAD_RM
+    prev, _DGRAD_RM = _DGRAD_RM, (dict(spec) if isinstance(spec, dict) else _parse_dgrad_rm(str(spec)))
+    return prev
+
+
+def _stored_weight(weights, rows: int, name: str):
+    """The [sum N_i, K] view of the weights as stored when MLA_DGRAD_RM names this dgrad and the launch stays inside the 256x256 kernel
+    (the one the copying path runs on: same K order, same bits); else None -> the caller transposes."""
+    if not _DGRAD_RM[name] or rows % 8 != 0 or rows < 256:
+        return None
+    wcat = cat_view(weights)
+    if wcat is None or wcat.shape[0] % 64 != 0 or wcat.shape[1] < 256 or wcat.shape[1] % 8 != 0 or wcat.data_ptr() % 16 != 0:
+        return None
+    return wcat
+
+
+def _dgrad(dy, weights, name: str):
+    """dx = dy @ cat(W_i): on the weights as stored (b_mode 1) where MLA_DGRAD_RM says so, else on the tile-transposed copy."""
+    wcat = _stored_weight(weights, dy.shape[0], name)
+    return hip.gemm(dy, wcat, b_mode=1) if wcat is not None else hip.gemm(dy, _transposed(weights))
 
 
 # RMSNorm folded into the projections (round 6, mla_hip.h: mla_gemm_res_norm / _qkv_rope_rs / _gateup_swiglu_rs): the stand-alone norm passes
@@ -776,7 +829,8 @@ def _attn_bwd(qkv, o, lse, do, seqlens, cos, sin, B, S, nheads, groups, want_t):
 def _qkv_bwd(dqkv, tr, h2, xn1, rstd1, w, need, wgrad_rm=False):
     """q | k | v projection backward: (dxn1 [T, H], (dWq, dWk, dWv)); the weight gradients are delivered when any is wanted, from tr[0] =
     dqkv^T when the attention backward left it. xn1 None: the normalised input is rebuilt, already transposed, from h2 and rstd1."""
-    dxn1 = hip.gemm(dqkv, _transposed((w.wq, w.wk, w.wv)))               # [T, H], K = 3H
+    # [T, H], K = 3H; MLA_DGRAD_RM like MLA_WGRAD_RM: DecoderLayerFn only
+    dxn1 = _dgrad(dqkv, (w.wq, w.wk, w.wv), "dqkv") if wgrad_rm else hip.gemm(dqkv, _transposed((w.wq, w.wk, w.wv)))
     grads = (None, None, None)
     rm = _WGRAD_RM["wqkv"] if (wgrad_rm and dqkv.shape[0] % 8 == 0) else 0      # (DecoderLayerFn only; the read-out layer keeps its own path)
     if (need.wq or need.wk or need.wv) and rm:
@@ -900,6 +954,11 @@ class DecoderLayerFn(torch.autograd.Function):
         # MLA_WGRAD_RM: the down-projection wgrad reads the product row-major -- level 1 keeps act in place of act^T (the same bytes)
         keep_act = keep_t and bool(_WGRAD_RM["wd"]) and Tp % 8 == 0
         keep_t = keep_t and not keep_act
+        # level 1 keeps a normalised input row-major (the forward wrote it anyway) when its wgrad reads x as stored: the backward then runs
+        # neither rmsnorm_apply_t nor rmsnorm_apply for it
+        needs_w = LayerWeights(*ctx.needs_input_grad[DecoderLayerFn.N_ARGS:])
+        keep_xn1 = save_level == 1 and _WGRAD_RM["wqkv"] == 1 and Tp % 8 == 0 and (needs_w.wq or needs_w.wk or needs_w.wv)
+        keep_xn2 = save_level == 1 and _WGRAD_RM["wgu"] == 1 and Tp % 8 == 0 and (needs_w.wg or needs_w.wu)
         if save_level == 3:
             save_level = 1                         # "1-lean": same saved set as level 1 minus act^T
         ctx.groups = current_attn_groups()
@@ -919,7 +978,9 @@ class DecoderLayerFn(torch.autograd.Function):
             # level 1 = recompute the two normalised inputs in the backward (one HBM-bound pass each, written straight into the
             # transposed layout) and KEEP the SwiGLU product, already transposed (+0.39 GB per layer at 7B; 288 GB of HBM)
             ctx.kept_act = keep_act
+            ctx.kept_xn = (keep_xn1 and a.xn1 is not None, keep_xn2 and a.xn2 is not None)      # (a folded forward has neither)
             ctx.save_for_backward(*((h2, a.rstd1, a.qkv, a.o, a.lse, a.h1, a.rstd2, a.gu) +
+                                    ((a.xn1,) if ctx.kept_xn[0] else ()) + ((a.xn2,) if ctx.kept_xn[1] else ()) +
                                     ((a.act,) if keep_act else (a.actT,) if a.actT is not None else ())))
         elif ctx.folded:
             ctx.save_for_backward(h2, a.rstd1)     # the recomputation scales the QKV rows by the SAME rstd the forward used
@@ -929,10 +990,12 @@ class DecoderLayerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        """All-NT backward: every large GEMM gets k-contiguous operands (W^T, x^T, dy^T from the HBM-bound tile-transpose
-        kernels; x^T of the normalised inputs and of the SwiGLU product are recomputed straight into transposed layout),
-        so dgrad and wgrad run on the same 256x256 ds_read_b128 kernel as the forward (mla_amd/csrc/transpose.hip).
-        Except the weight gradients MLA_WGRAD_RM names: those read dy (and x) as stored and their copies are never made."""
+        """Every large GEMM on the 256x256 kernel. By default each reads its operands AS STORED (MLA_DGRAD_RM: W as the B operand of the
+        dgrads, the fused d(act) launch included; MLA_WGRAD_RM: dy and x of the wgrads): reduction-major sides go through the generated
+        ds_read_b64_tr_b16 main loop, same K order and bits as the k-contiguous launch, and no layout copy is made. A GEMM whose switch
+        is off (or whose weights are not adjacent in the flat buffer) takes the all-NT path: k-contiguous W^T, x^T, dy^T from the
+        HBM-bound tile-transpose kernels (mla_amd/csrc/transpose.hip), x^T of the normalised inputs and of the SwiGLU product
+        recomputed straight into transposed layout."""
         w = ctx.w
         B, S, H, nheads, eps = ctx.dims
         seqlens, cos, sin = ctx.aux
@@ -943,6 +1006,10 @@ class DecoderLayerFn(torch.autograd.Function):
         elif ctx.save_level == 1:
             rstd1, qkv, o, lse, h1, rstd2, gu, *kept_t = saved
             a = LayerActs(rstd1=rstd1, qkv=qkv, o=o, lse=lse, h1=h1, rstd2=rstd2, gu=gu)
+            if ctx.kept_xn[0]:
+                a.xn1, *kept_t = kept_t
+            if ctx.kept_xn[1]:
+                a.xn2, *kept_t = kept_t
             if kept_t:
                 a.act, a.actT = (kept_t[0], None) if ctx.kept_act else (None, kept_t[0])
         else:
@@ -959,10 +1026,18 @@ class DecoderLayerFn(torch.autograd.Function):
         want_w = need.wg or need.wu
         # MLA_WGRAD_RM per GEMM; a reduction-major operand's row count (the tokens) has to be a multiple of 8, as for the tile transposes
         rm = _WGRAD_RM if d2.shape[0] % 8 == 0 else dict.fromkeys(_WGRAD_RM_NAMES, 0)
-        wdT = _transposed((w.wd,))
-        fused = hip.gemm_dact_swiglu_bwd(d2, wdT, a.gu, want_t=not rm["wgu"]) if (want_w and _SWIGLU_BWD_EPILOGUE) else None   # d(act) never leaves the chip
-        dact = hip.gemm(d2, wdT) if fused is None else None              # [T, I]
-        del wdT
+        # MLA_DGRAD_RM dd: W_down [H, I] as stored -- the fused launch through its reduction-major form, no W^T pass
+        wd_rm = _stored_weight((w.wd,), d2.shape[0], "dd")
+        if wd_rm is not None and want_w and _SWIGLU_BWD_EPILOGUE and hip.dact_swiglu_bwd_rm_ok(d2, wd_rm, a.gu):
+            fused = hip.gemm_dact_swiglu_bwd_rm(d2, wd_rm, a.gu, want_t=not rm["wgu"])
+            dact = None
+        elif wd_rm is not None and not (want_w and _SWIGLU_BWD_EPILOGUE):
+            fused, dact = None, hip.gemm(d2, wd_rm, b_mode=1)
+        else:
+            wdT = _transposed((w.wd,))
+            fused = hip.gemm_dact_swiglu_bwd(d2, wdT, a.gu, want_t=not rm["wgu"]) if (want_w and _SWIGLU_BWD_EPILOGUE) else None   # d(act) never leaves the chip
+            dact = hip.gemm(d2, wdT) if fused is None else None              # [T, I]
+            del wdT
         if need.wd and rm["wd"]:
             if a.act is not None or (a.actT is None and rm["wd"] == 1):
                 act, bm = (a.act if a.act is not None else hip.swiglu_fwd(a.gu)), 1
@@ -984,7 +1059,7 @@ class DecoderLayerFn(torch.autograd.Function):
             dgu, _ = hip.swiglu_bwd(dact, a.gu)
         del dact, fused
         # ---- MLP: gate | up projection
-        dxn2 = hip.gemm(dgu, _transposed((w.wg, w.wu)))                  # [T, H], K = 2I
+        dxn2 = _dgrad(dgu, (w.wg, w.wu), "dgu")                          # [T, H], K = 2I
         if want_w and rm["wgu"]:
             if a.xn2 is not None:
                 x, bm = a.xn2, 1
@@ -1005,7 +1080,7 @@ class DecoderLayerFn(torch.autograd.Function):
         del dxn2
 
         # ---- attention output projection, attention, q | k | v projection, input norm
-        do = hip.gemm(dh1, _transposed((w.wo,)))
+        do = _dgrad(dh1, (w.wo,), "do")
         dqkv, tr = _attn_bwd(a.qkv, a.o, a.lse, do, seqlens, cos, sin, B, S, nheads, ctx.groups,
                              want_t=(need.wq or need.wk or need.wv) and need.wo and not rm["wqkv"])
         del do

@@ -3,7 +3,9 @@ would replace (k-contiguous operands + the explicit transposes that make them). 
 Usage: python tools/bench_gemm_modes.py [tokens]
        python tools/bench_gemm_modes.py pairs [tokens]    per wgrad GEMM of a decoder layer: the reduction-major assembly launch on row-major
            dY and X against the k-contiguous launch plus what that GEMM's transposed copies cost today, alternating on one GPU
-           (medians of 7 rounds); the (0, 1) rates of the dgrad shapes; -> profiles/wgrad_rm_gemm_pairs.txt"""
+           (medians of 7 rounds); then one decision line per dgrad (B as stored against NT + its W^T pass, the fused d(act) launch as
+           <0,1,2> against <0,0,2> + its transpose), the attention backward with / without its transposed outputs and what wqkv / wo /
+           wgu = 1 gain from them and from the kept normalised inputs; -> profiles/backward_as_stored_gemm_pairs.txt"""
 import os
 import sys
 
@@ -101,7 +103,8 @@ def pairs():
         pick = "0" if min(n11, n10) >= 0 else "1" if n11 <= n10 else "a"
         print(f"  {name:9s} '1' (1,1): penalty {1e3 * (r['rm_asm'] - r['nt']):+7.1f} - copies {c11[name]:6.1f} = net {n11:+7.1f} us | "
               f"'a' (1,0): penalty {1e3 * (r['a_rm'] - r['nt']):+7.1f} - copies {c10[name]:6.1f} = net {n10:+7.1f} us -> {pick}", flush=True)
-    print("dgrad shapes, B as stored (b_mode 1, generated main loop) against NT on W^T (out of scope here; the number for the next decision)")
+    print("dgrad shapes, B as stored (b_mode 1, generated main loop) against NT on W^T")
+    drows = {}
     for name, nout, kin in (("qkv", 3 * H, H), ("o", H, H), ("gate|up", 2 * I, H), ("down", H, I)):
         dy, w = rnd(T, nout), rnd(nout, kin, scale=0.02)
         wt = hip.transpose(w)
@@ -109,7 +112,57 @@ def pairs():
         r = alternating({"nt": lambda: hip.gemm(dy, wt, out=o), "nn": lambda: hip.gemm(dy, w, out=o, b_mode=1), "wT": lambda: hip.transpose(w)})
         fl = 2.0 * T * nout * kin / 1e9
         print(f"  {name:8s} NT {r['nt']:6.3f} ({fl / r['nt']:5.0f} TF/s) | (0,1) {r['nn']:6.3f} ({fl / r['nn']:5.0f} TF/s, {100 * (r['nn'] / r['nt'] - 1):+5.1f} %) | W^T {r['wT']:6.3f}", flush=True)
+        drows[name] = r
         del dy, w, wt, o
+    # the fused d(act) + SwiGLU-backward launch: <0,1,2> on W_down [H, I] as stored against <0,0,2> on W^T + the tile transpose that makes it
+    # (row-major d(gate|up) only, as the wg|wu wgrad reads it today; and with the transposed strip)
+    dy, w, gu = rnd(T, H), rnd(H, I, scale=0.02), rnd(T, 2 * I)
+    wt = hip.transpose(w)
+    r = alternating({"nt": lambda: hip.gemm_dact_swiglu_bwd(dy, wt, gu, want_t=False), "nn": lambda: hip.gemm_dact_swiglu_bwd_rm(dy, w, gu, want_t=False),
+                     "nt_t": lambda: hip.gemm_dact_swiglu_bwd(dy, wt, gu), "nn_t": lambda: hip.gemm_dact_swiglu_bwd_rm(dy, w, gu),
+                     "wT": lambda: hip.transpose(w)})
+    fl = 2.0 * T * H * I / 1e9
+    print(f"  down+bwd <0,0,2> {r['nt']:6.3f} ({fl / r['nt']:5.0f} TF/s) | <0,1,2> {r['nn']:6.3f} ({fl / r['nn']:5.0f} TF/s, {100 * (r['nn'] / r['nt'] - 1):+5.1f} %)"
+          f" | with dgu^T: <0,0,2> {r['nt_t']:6.3f} | <0,1,2> {r['nn_t']:6.3f} ({100 * (r['nn_t'] / r['nt_t'] - 1):+5.1f} %) | W^T {r['wT']:6.3f}", flush=True)
+    drows["down+bwd"] = r
+    del dy, w, gu, wt
+    print("decision per dgrad (MLA_DGRAD_RM): launch penalty of B as stored against the W^T pass it removes (us per layer; negative net wins)")
+    for key, name in (("dqkv", "qkv"), ("do", "o"), ("dgu", "gate|up"), ("dd", "down+bwd"), ("dd (plain)", "down")):
+        r = drows[name]
+        pen, copy = 1e3 * (r["nn"] - r["nt"]), 1e3 * r["wT"]
+        print(f"  {key:10s} penalty {pen:+7.1f} - W^T {copy:6.1f} = net {pen - copy:+7.1f} us -> {'1' if pen - copy < 0 else '0'}", flush=True)
+    # the attention backward with and without its transposed outputs (dqkv^T, o^T): what wqkv = 1 and wo = 1 together remove
+    nh, D, Bq = H // 128, 128, 32
+    Sq = T // Bq
+    if Sq * Bq == T and Sq % 4 == 0:
+        qkv = rnd(T, 3 * H, scale=0.5)
+        q, k, v = qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:]
+        sc = D ** -0.5
+        o, lse = hip.attn_fwd(q, k, v, Bq, Sq, nh, D, 3 * H, None, sc)
+        do, dqkv = rnd(T, H), torch.empty_like(qkv)
+        inv = 1.0 / (10000.0 ** (torch.arange(0, D, 2, device=dev).float() / D))
+        ang = torch.outer(torch.arange(Sq, device=dev).float(), inv)
+        cos, sin = ang.cos().contiguous(), ang.sin().contiguous()
+        tr = (torch.empty(3 * H, T, dtype=torch.bfloat16, device=dev), torch.empty(H, T, dtype=torch.bfloat16, device=dev))
+
+        def bwd(t):
+            return lambda: hip.attn_bwd(q, k, v, o, do, lse, None, dqkv[:, :H], dqkv[:, H:2 * H], dqkv[:, 2 * H:], Bq, Sq, nh, D, 3 * H, sc,
+                                        rope_cos=cos, rope_sin=sin, transposed=t)
+        r = alternating({"t": bwd(tr), "n": bwd(None)})
+        tcost = 1e3 * (r["t"] - r["n"])
+        print(f"attention backward (B = {Bq}, S = {Sq}): with dqkv^T, o^T {r['t']:6.3f} | without {r['n']:6.3f} | the transposed outputs cost {tcost:6.1f} us", flush=True)
+        del qkv, o, do, dqkv, tr
+        # level 1 keeps xn1 / xn2 row-major when wqkv / wgu = 1: the rmsnorm_apply_t pass that rebuilt x^T goes as well
+        h, g = rnd(T, H), rnd(H)
+        _, rstd = hip.rmsnorm_fwd(h, g, 1e-5)
+        napply = 1e3 * alternating({"t": lambda: hip.rmsnorm_apply_t(h, g, rstd)})["t"]
+        pq, po, pg = rows["wq|wk|wv"], rows["wo"], rows["wg|wu"]
+        pen = 1e3 * ((pq["rm_asm"] - pq["nt"]) + (po["rm_asm"] - po["a_rm"]))
+        net = pen - tcost - napply
+        print(f"  wqkv 0 -> 1 and wo a -> 1 (no dqkv^T / o^T, xn1 kept): launch penalty {pen:+7.1f} - transposed outputs {tcost:6.1f} - rmsnorm_apply_t {napply:6.1f}"
+              f" = net {net:+7.1f} us -> {'wqkv=1,wo=1' if net < 0 else 'wqkv=0,wo=a'}", flush=True)
+        pen = 1e3 * (pg["rm_asm"] - pg["a_rm"])
+        print(f"  wgu a -> 1 (xn2 kept): launch penalty {pen:+7.1f} - rmsnorm_apply_t {napply:6.1f} = net {pen - napply:+7.1f} us -> {'wgu=1' if pen - napply < 0 else 'wgu=a'}", flush=True)
 
 
 if PAIRS:
