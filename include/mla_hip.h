@@ -496,10 +496,19 @@ int mla_gemm_prefill_f8_wide_gateup_swiglu(const void* xq, long long ldx, const 
  *     e2 = (ax - px) / b; x = px c + d e2, every operation rounded on its own (no FMA contraction): the host loop's bits. x [n] fp32 is
  *     updated in place, eps [n] bf16, x_bf16 [n] = bf16_rne(x) is written; with `advance` the counter then becomes s - 1 (thread 0, behind
  *     a workgroup barrier). Any other s: nothing is written, the counter stays. One workgroup; 1 <= n <= 65 536.
+ *   mla_ddpm_step (sample_ddpm, opt-in ddpm_sampler="device"): mla_ddim_step's form and counter protocol for GaussianDiffusion.p_sample
+ *     (gaussian_diffusion.py:395-440, clip_denoised = False, fixed-small posterior variance) with coef[s] = {a, b, c1, c2, sig} ([steps, 5]
+ *     fp32: sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, posterior_mean_coef1, posterior_mean_coef2,
+ *     (s != 0) exp(0.5 posterior_log_variance_clipped), GaussianDiffusion.ddpm_tables) and the step's normal variates in row s of
+ *     noise [steps, n] fp32, filled by the host before the first step: ax = a x; px = ax - b eps; mean = c1 px + c2 x;
+ *     x = mean + sig noise[s n + i], every operation rounded on its own; at s = 0 the product 0 * noise is still formed and added (the
+ *     sign of a zero result is the host loop's). A counter outside [0, steps) reads neither table.
  *   mla_sampler_rows: with R = 1 + T, for 0 <= *step < steps: h_in row g R = t_table[*step] ([steps, H] bf16), row g R + 1 + p =
  *     x_e[g T + p] (g < G, p < T); any other *step writes nothing. h_in [G R, H], x_e [G T, H] bf16, H % 8 == 0, 16-B aligned rows. */
 int mla_ddim_step(float* x, const void* eps, void* x_bf16, const float* coef, int* step, int n, int steps, int advance,
                   mla_stream_t stream);
+int mla_ddpm_step(float* x, const void* eps, void* x_bf16, const float* coef, const float* noise, int* step, int n, int steps,
+                  int advance, mla_stream_t stream);
 int mla_sampler_rows(void* h_in, const void* t_table, const void* x_e, const int* step, int G, int T, int H, int steps,
                      mla_stream_t stream);
 

@@ -1,7 +1,8 @@
-// The DDIM sampler's glue on the device (mla_amd/infer.py:_CachedEpsBase.sample_ddim): the per-step update of the action chunk and the
-// assembly of the suffix pass's input rows. The step index lives in device memory and is counted down by the update kernel, so a sampler
-// step depends on nothing the host knows: the host enqueues `steps` replays of one captured step and reads the result.
-// Both kernels are stateless, allocate nothing, launch on the caller's stream and are graph-capturable.
+// The samplers' glue on the device (mla_amd/infer.py:_CachedEpsBase.sample_ddim / sample_ddpm): the per-step update of the action chunk
+// (DDIM at eta = 0, or the DDPM posterior step with its noise read from a table the host filled beforehand) and the assembly of the suffix
+// pass's input rows. The step index lives in device memory and is counted down by the update kernel, so a sampler step depends on
+// nothing the host knows: the host enqueues `steps` replays of one captured step and reads the result.
+// All kernels are stateless, allocate nothing, launch on the caller's stream and are graph-capturable.
 #include "common.h"
 
 namespace {
@@ -38,6 +39,41 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(float* __restrict__ x, c
   if (live && advance && threadIdx.x == 0) *step = s - 1;
 }
 
+// GaussianDiffusion.p_sample at clip_denoised = False with the fixed-small posterior variance (models/diffusion/gaussian_diffusion.py:395-440)
+// and the five per-step values coef[s] = {sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, posterior_mean_coef1,
+// posterior_mean_coef2, (s != 0) exp(0.5 posterior_log_variance_clipped)}, the step's normal variates in row s of noise [steps, n]:
+//   ax = a x;  px = ax - b eps;  mean = c1 px + c2 x;  x' = mean + sig noise
+// every operation rounded on its own, as in ddim_step_kernel (contraction off: c1 px + c2 x and mean + sig noise would become FMAs). At
+// s = 0 sig is 0 and the product 0 * noise is still formed and added, as the host loop does: the sign of a zero result is the host's.
+// The counter protocol is ddim_step_kernel's.
+__global__ __launch_bounds__(256) void ddpm_step_kernel(float* __restrict__ x, const bf16_t* __restrict__ eps, bf16_t* __restrict__ x_bf16,
+                                                        const float* __restrict__ coef, const float* __restrict__ noise, int* step, int n,
+                                                        int steps, int advance) {
+#pragma clang fp contract(off)
+  const int s = *(const volatile int*)step;
+  const bool live = s >= 0 && s < steps;                                      // a stale counter never indexes outside the tables
+  if (live) {
+    const float a = coef[5 * s + 0], b = coef[5 * s + 1], c1 = coef[5 * s + 2], c2 = coef[5 * s + 3], sig = coef[5 * s + 4];
+    const float* __restrict__ z = noise + (size_t)s * n;
+    for (int i = threadIdx.x; i < n; i += 256) {
+      const float e = bf2f(eps[i]);
+      const float xi = x[i];
+      const float ax = a * xi;
+      const float be = b * e;
+      const float px = ax - be;
+      const float m1 = c1 * px;
+      const float m2 = c2 * xi;
+      const float mean = m1 + m2;
+      const float sn = sig * z[i];
+      const float out = mean + sn;
+      x[i] = out;
+      x_bf16[i] = f2bf(out);
+    }
+  }
+  __syncthreads();
+  if (live && advance && threadIdx.x == 0) *step = s - 1;
+}
+
 // h_in row g R <- t_table[*step], rows g R + 1 + p <- x_e[g T + p] (R = 1 + T): cat([t_e, x_e], 1).reshape(G R, H) of the sampler's
 // model call, with the timestep embedding looked up instead of recomputed. One workgroup per row, 16 B per lane.
 __global__ __launch_bounds__(256) void sampler_rows_kernel(bf16_t* __restrict__ h_in, const bf16_t* __restrict__ t_table,
@@ -61,6 +97,16 @@ extern "C" int mla_ddim_step(float* x, const void* eps, void* x_bf16, const floa
   MLA_CHECK_ARG(n >= 1 && n <= 65536, "mla_ddim_step: n = %d outside [1, 65536] (one workgroup walks the chunk)", n);
   MLA_CHECK_ARG(steps >= 1, "mla_ddim_step: steps = %d", steps);
   hipLaunchKernelGGL(ddim_step_kernel, dim3(1), dim3(256), 0, stream, x, (const bf16_t*)eps, (bf16_t*)x_bf16, coef, step, n, steps,
+                     advance ? 1 : 0);
+  MLA_LAUNCH_CHECK();
+}
+
+extern "C" int mla_ddpm_step(float* x, const void* eps, void* x_bf16, const float* coef, const float* noise, int* step, int n, int steps,
+                             int advance, hipStream_t stream) {
+  MLA_CHECK_ARG(x && eps && x_bf16 && coef && noise && step, "mla_ddpm_step: null pointer");
+  MLA_CHECK_ARG(n >= 1 && n <= 65536, "mla_ddpm_step: n = %d outside [1, 65536] (one workgroup walks the chunk)", n);
+  MLA_CHECK_ARG(steps >= 1, "mla_ddpm_step: steps = %d", steps);
+  hipLaunchKernelGGL(ddpm_step_kernel, dim3(1), dim3(256), 0, stream, x, (const bf16_t*)eps, (bf16_t*)x_bf16, coef, noise, step, n, steps,
                      advance ? 1 : 0);
   MLA_LAUNCH_CHECK();
 }

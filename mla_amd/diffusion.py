@@ -156,6 +156,27 @@ class GaussianDiffusion:
         nonzero = (t != 0).float().view(-1, *([1] * (x.dim() - 1)))
         return {"sample": mean + nonzero * torch.exp(0.5 * logvar) * noise, "pred_xstart": pred_xstart}
 
+    def ddpm_tables(self, device):
+        """-> (coef [steps, 5] fp32, timesteps [steps] long) on `device`, cached per device like ddim_tables: what p_sample uses of step i
+        at clip_denoised=False, row i = [a, b, c1, c2, sig] = [sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod,
+        posterior_mean_coef1, posterior_mean_coef2, (i != 0) * exp(0.5 * posterior_log_variance_clipped)], built with p_sample's own
+        expressions on the target device (float64 table -> float32 value as _at does, 0.5 * logvar and torch.exp on the fp32 values,
+        times the fp32 0 / 1), and timestep_map. With
+            ax = a * x;  px = ax - b * eps;  mean = c1 * px + c2 * x;  out = mean + sig * noise
+        rounded one operation at a time, `out` is p_sample(...)["sample"] bit for bit for the same noise (hip.ddpm_step,
+        tests/test_sampler_ddpm_host.py)."""
+        key = ("ddpm", str(device))
+        if key not in self._dev_tables:
+            with torch.inference_mode(False), torch.no_grad():
+                t = torch.arange(self.num_timesteps, device=device)
+                at = lambda table: torch.from_numpy(table).to(device=device)[t].float()  # noqa: E731 -- _at without the broadcast
+                a, b = at(self.sqrt_recip_alphas_cumprod), at(self.sqrt_recipm1_alphas_cumprod)
+                c1, c2 = at(self.posterior_mean_coef1), at(self.posterior_mean_coef2)
+                sig = (t != 0).float() * torch.exp(0.5 * at(self.posterior_log_variance_clipped))
+                self._dev_tables[key] = (torch.stack([a, b, c1, c2, sig], dim=1).contiguous(),
+                                         torch.tensor(self.timestep_map, dtype=torch.long, device=device))
+        return self._dev_tables[key]
+
     def _loop(self, step, model, shape, noise, device, **kw):
         assert isinstance(shape, (tuple, list))
         img = noise if noise is not None else torch.randn(*shape, device=device)

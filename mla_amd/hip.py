@@ -87,6 +87,7 @@ _SIGNATURES = {
     "mla_gemm_prefill_f8_wide_gateup_swiglu": [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong,
                                                c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p],
     "mla_ddim_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    "mla_ddpm_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "mla_sampler_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "mla_attn_chunk_split_plan": [c_int, c_int, c_int, c_int, c_int, c_void_p],
     "mla_attn_chunk_split_ws_bytes": [c_int, c_int, c_int, c_int, c_int],      # returns long long (restype fixed up in lib())
@@ -1380,6 +1381,28 @@ def ddim_step(x, eps, x_bf16, coef, step, advance=True):
     if not 1 <= n <= DDIM_NMAX:
         raise ValueError(f"ddim_step: {n} elements outside [1, {DDIM_NMAX}]")
     call("mla_ddim_step", _p(x), _p(eps), _p(x_bf16), _p(coef), _p(step), n, coef.shape[0], 1 if advance else 0)
+
+
+def ddpm_step(x, eps, x_bf16, coef, noise, step, advance=True):
+    """mla_ddpm_step: the DDPM posterior step (GaussianDiffusion.p_sample, clip_denoised=False) of the chunk x (fp32, in place; any shape,
+    contiguous) with row step[0] of coef [steps, 5], the bf16 epsilons eps and row step[0] of noise [steps, x.numel()] fp32; x_bf16 <-
+    bf16(x); advance: step[0] -= 1. A step[0] outside [0, steps) writes nothing."""
+    _req(x, torch.float32, "ddpm_step x")
+    _req(eps, torch.bfloat16, "ddpm_step eps")
+    _req(x_bf16, torch.bfloat16, "ddpm_step x_bf16")
+    _req(coef, torch.float32, "ddpm_step coef")
+    _req(noise, torch.float32, "ddpm_step noise")
+    _req(step, torch.int32, "ddpm_step step")
+    n = x.numel()
+    if not (x.is_contiguous() and eps.is_contiguous() and x_bf16.is_contiguous() and coef.is_contiguous() and noise.is_contiguous()):
+        raise ValueError("ddpm_step: x, eps, x_bf16, coef and noise must be contiguous")
+    if eps.numel() != n or x_bf16.numel() != n or coef.dim() != 2 or coef.shape[1] != 5 or step.numel() != 1 \
+            or tuple(noise.shape) != (coef.shape[0], n):
+        raise ValueError(f"ddpm_step: x {tuple(x.shape)}, eps {tuple(eps.shape)}, x_bf16 {tuple(x_bf16.shape)}, coef {tuple(coef.shape)}, "
+                         f"noise {tuple(noise.shape)} (wanted [steps, x.numel()]), step {tuple(step.shape)}")
+    if not 1 <= n <= DDIM_NMAX:
+        raise ValueError(f"ddpm_step: {n} elements outside [1, {DDIM_NMAX}]")
+    call("mla_ddpm_step", _p(x), _p(eps), _p(x_bf16), _p(coef), _p(noise), _p(step), n, coef.shape[0], 1 if advance else 0)
 
 
 def sampler_rows(h_in, t_table, x_e, step, G, T):

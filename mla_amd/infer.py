@@ -22,6 +22,10 @@ Opt-in (`sampler="device"`, see SAMPLER_MODES): the DDIM loop around the suffix 
 captured sampler step (x_embedder, `mla_sampler_rows`, the suffix pass, final_layer, `mla_ddim_step`) per DDIM step with the step index in
 device memory: no copy to the device and no host wait between the steps, bit for bit the host loop's result.
 
+Opt-in (`ddpm_sampler="device"`, see DDPM_SAMPLER_MODES): the same for the DDPM loop of `use_ddim=False` -- `sample_ddpm` draws the steps'
+normal variates up front into a device table (asynchronous launches, the host loop's order) and replays the captured step with
+`mla_ddpm_step` as its update num_timesteps times: the host loop's bits and generator position.
+
 Opt-in (`suffix_attention="split"`, see SUFFIX_ATTENTION_MODES; PrefixCachedEps only): the attention launch of the suffix pass becomes
 `mla_attn_chunk_split` -- every head's key tiles cut over several workgroups, the partial softmax states merged in a fixed order by a
 second launch -- for every R; the same function up to summation order. The multi-row engines (BatchedPrefixCachedEps, SampleGroupsEps,
@@ -203,8 +207,8 @@ SAMPLER_MODES = ("host", "device")
 
 
 def check_sampler(mode, reuse_prefix=True, use_ddim=True, num_ddim_steps=8):
-    """The argument errors of sampler=: an unknown value; "device" without the cached prefix or without the DDIM sampler (the DDPM sampler
-    needs per-step noise values). A shape the engine does not serve is the caller's ValueError (sampler_needs_engine)."""
+    """The argument errors of sampler=: an unknown value; "device" without the cached prefix or without the DDIM sampler (the DDPM loop's
+    device form has its own keyword, ddpm_sampler=). A shape the engine does not serve is the caller's ValueError (sampler_needs_engine)."""
     if mode not in SAMPLER_MODES:
         raise ValueError(f"sampler must be one of {SAMPLER_MODES}, got {mode!r}")
     if mode == "device":
@@ -212,8 +216,8 @@ def check_sampler(mode, reuse_prefix=True, use_ddim=True, num_ddim_steps=8):
             raise ValueError("sampler=\"device\" runs on the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has the "
                              "host loop only")
         if not use_ddim or num_ddim_steps is None:
-            raise ValueError("sampler=\"device\" is the DDIM loop at eta = 0 (use_ddim=True and num_ddim_steps); the DDPM sampler needs "
-                             "per-step noise values")
+            raise ValueError("sampler=\"device\" is the DDIM loop at eta = 0 (use_ddim=True and num_ddim_steps); the DDPM loop's "
+                             "device form is ddpm_sampler=\"device\"")
 
 
 def sampler_needs_engine(mode, engine: str, n_action_rows: int):
@@ -223,13 +227,44 @@ def sampler_needs_engine(mode, engine: str, n_action_rows: int):
                          "sample at this head_dim; use sampler=\"host\"")
 
 
-_GRAPH_OFF = "MLA_INFER_GRAPH=0: the device sampler launches its steps one by one"      # graph_error of an eager sample_ddim
+# Who runs the DDPM loop (use_ddim=False: the training diffusion's p_sample_loop) around the suffix passes
+# (MLA.predict_action_diff(ddpm_sampler=...)); sampler= above keeps its meaning, the DDIM loop:
+#   "host"    GaussianDiffusion.p_sample_loop: torch expressions per step, a device wait in every step (default)
+#   "device"  _CachedEpsBase.sample_ddpm: the steps' normal variates drawn up front into a device table, then one captured sampler step
+#             replayed num_timesteps times; no copy to the device and no host wait between the steps; the same bits and generator position
+DDPM_SAMPLER_MODES = ("host", "device")
+
+
+def check_ddpm_sampler(mode, reuse_prefix=True, use_ddim=False, num_ddim_steps=None):
+    """The argument errors of ddpm_sampler=: an unknown value; "device" without the cached prefix, or on a call that runs the DDIM sampler
+    (the keyword is never silently ignored). A shape the engine does not serve is the caller's ValueError (ddpm_sampler_needs_engine)."""
+    if mode not in DDPM_SAMPLER_MODES:
+        raise ValueError(f"ddpm_sampler must be one of {DDPM_SAMPLER_MODES}, got {mode!r}")
+    if mode == "device":
+        if not reuse_prefix:
+            raise ValueError("ddpm_sampler=\"device\" runs on the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has "
+                             "the host loop only")
+        if use_ddim and num_ddim_steps is not None:
+            raise ValueError("ddpm_sampler=\"device\" is the DDPM loop (use_ddim=False or num_ddim_steps=None); this call runs the DDIM "
+                             "sampler, whose device loop is sampler=\"device\"")
+
+
+def ddpm_sampler_needs_engine(mode, engine: str, n_action_rows: int):
+    """ddpm_sampler="device" on a shape the cached-prefix engine does not serve: an error, never the warned loop of whole-forward calls."""
+    if mode == "device":
+        raise ValueError(f"ddpm_sampler=\"device\": the cached-prefix engine ({engine}) does not serve {1 + n_action_rows} suffix rows per "
+                         "sample at this head_dim; use ddpm_sampler=\"host\"")
+
+
+_GRAPH_OFF = "MLA_INFER_GRAPH=0: the device sampler launches its steps one by one"      # graph_error of an eager sample_ddim / sample_ddpm
 
 
 class _DdimState:
-    """What sample_ddim keeps per (engine, batch, action_dim, diffusion): the chunk x fp32 and its bf16 cast, the step counter, the
-    coefficient and timestep-embedding tables, and the captured step. All device tensors are allocated outside inference mode."""
-    __slots__ = ("diffusion", "steps", "x", "x_bf16", "step", "coef", "timesteps", "t_table", "t_key", "graph", "graph_key", "failed")
+    """What sample_ddim / sample_ddpm keep per (engine, batch, action_dim, diffusion): the chunk x fp32 and its bf16 cast, the step
+    counter, the coefficient and timestep-embedding tables, and the captured step; a DDPM state also has `noise` [steps, B T D] fp32, the
+    steps' normal variates (None in a DDIM state: it selects the update kernel). All device tensors are allocated outside inference mode."""
+    __slots__ = ("diffusion", "steps", "x", "x_bf16", "step", "coef", "timesteps", "t_table", "t_key", "graph", "graph_key", "failed",
+                 "noise")
 
 
 def _fake_quant_rows(x):
@@ -276,6 +311,7 @@ class _CachedEpsBase:
         self._packed_key = None
         self._suffix = None          # per layer: what the suffix pass streams -- _packed itself ("bf16") or a quantised copy (_quantised)
         self._ddim = {}              # sample_ddim's state per (B, action_dim): see _DdimState
+        self._ddpm = {}              # sample_ddpm's, kept apart: a DDIM and a DDPM call on one engine keep their captured steps
 
     @classmethod
     def _serves(cls, vlm, rows: int, limit: int, tag: tuple, message: str, warn: bool = True) -> bool:
@@ -536,15 +572,17 @@ class _CachedEpsBase:
             noise_pred = vlm.final_layer(picked).view(self.B, self.T, -1)
         return None, noise_pred
 
-    # ------------------------------------------------------------------------------------------ the DDIM loop on the device (sampler="device")
-    def _ddim_state(self, x0, diffusion):
-        """The persistent state for chunks shaped like x0 [B, T, D] under `diffusion` (per B: the group engines keep one per set_groups G)."""
+    # ----------------------------------------------------- the sampler loops on the device (sampler="device", ddpm_sampler="device")
+    def _sampler_state(self, x0, diffusion, ddpm: bool):
+        """The persistent state of the DDIM or of the DDPM loop (kept in _ddim / _ddpm: the two do not evict each other's captured steps)
+        for chunks shaped like x0 [B, T, D] under `diffusion` (per B: the group engines keep one per set_groups G)."""
         B, T, D = x0.shape
         assert B == self.B and T == self.T, (tuple(x0.shape), self.B, self.T)
-        st = self._ddim.get((B, D))
+        store = self._ddpm if ddpm else self._ddim
+        st = store.get((B, D))
         if st is None or st.diffusion is not diffusion:
             dev = self.h_in.device
-            coef, timesteps = diffusion.ddim_tables(dev, eta=0.0)
+            coef, timesteps = diffusion.ddpm_tables(dev) if ddpm else diffusion.ddim_tables(dev, eta=0.0)
             st = _DdimState()
             st.diffusion, st.steps, st.timesteps = diffusion, int(coef.shape[0]), timesteps
             with torch.inference_mode(False), torch.no_grad():                # the state outlives the (inference-mode) call that creates it
@@ -553,12 +591,13 @@ class _CachedEpsBase:
                 st.step = torch.full((1,), st.steps - 1, dtype=torch.int32, device=dev)
                 st.coef = coef.clone()
                 st.t_table = torch.zeros((st.steps, self.H), dtype=torch.bfloat16, device=dev)
+                st.noise = torch.zeros((st.steps, B * T * D), dtype=torch.float32, device=dev) if ddpm else None
             st.t_key = st.graph = st.graph_key = None
             st.failed = False
-            self._ddim[(B, D)] = st
+            store[(B, D)] = st
         return st
 
-    def _ddim_t_table(self, st):
+    def _sampler_t_table(self, st):
         """Row i of t_table = the timestep token of step i: vlm.t_embedder on the [B] batch of the mapped timestep cast to bf16, exactly
         as __call__ forms it per step (row 0 of B equal rows, checked once per build: the bits do not depend on how the GEMM treats the
         row count). Rebuilt in place -- a captured step keeps its address -- when a t_embedder parameter changes."""
@@ -568,23 +607,27 @@ class _CachedEpsBase:
         with torch.no_grad():
             rows = torch.stack([self.vlm.t_embedder(st.timesteps[i].expand(self.B).to(torch.bfloat16)) for i in range(st.steps)])
             if not bool((rows == rows[:, :1]).all()):
-                raise RuntimeError("sample_ddim: t_embedder gives different rows for the same timestep; the device sampler keeps one row "
-                                   "per step (use sampler=\"host\")")
+                raise RuntimeError("device sampler: t_embedder gives different rows for the same timestep; the device loop keeps one row "
+                                   "per step (use the host loop)")
             st.t_table.copy_(rows[:, 0])
         st.t_key = key
 
-    def _ddim_one_step(self, st):
+    def _sampler_one_step(self, st):
         """One sampler step, every launch on the current stream and none of them waiting for the host: the launches of __call__ with the
-        timestep token looked up (mla_sampler_rows), then the DDIM update, which counts the device-side step index down."""
+        timestep token looked up (mla_sampler_rows), then the state's update (DDIM, or DDPM with the step's row of st.noise), which counts
+        the device-side step index down."""
         vlm = self.vlm
         x_e = vlm.x_embedder(st.x_bf16)                                       # [B, T, H]
         hip.sampler_rows(self.h_in, st.t_table, x_e.contiguous(), st.step, self.B, self.T)
         self._suffix_pass()                                                   # launched directly: a graph cannot replay inside a capture
         picked = self.h_out.view(self.B, self.R, self.H)[:, 1:].reshape(self.B * self.T, self.H).contiguous()
         noise_pred = vlm.final_layer(picked)                                  # [B * T, D] bf16
-        hip.ddim_step(st.x, noise_pred.contiguous(), st.x_bf16, st.coef, st.step, advance=True)
+        if st.noise is None:
+            hip.ddim_step(st.x, noise_pred.contiguous(), st.x_bf16, st.coef, st.step, advance=True)
+        else:
+            hip.ddpm_step(st.x, noise_pred.contiguous(), st.x_bf16, st.coef, st.noise, st.step, advance=True)
 
-    def _ddim_graph(self, st):
+    def _sampler_graph(self, st):
         """The captured step for the current weights, or None (MLA_INFER_GRAPH=0 or a failed capture: eager launches of the same sequence,
         the reason in graph_error). Captured under _run's conditions; the warm-up launch runs a real step on the state, so this is called
         in front of the reset of a call."""
@@ -602,17 +645,37 @@ class _CachedEpsBase:
             st.graph = None
             try:
                 with torch.no_grad():
-                    self._ddim_one_step(st)                                   # warm-up outside the capture (function attributes, allocator)
+                    self._sampler_one_step(st)                                # warm-up outside the capture (function attributes, allocator)
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.inference_mode(False), torch.no_grad(), torch.cuda.graph(g):
-                    self._ddim_one_step(st)
+                    self._sampler_one_step(st)
                 st.graph, st.graph_key = g, key
             except Exception as e:   # noqa: BLE001 -- a failed capture is not fatal: the eager launches compute the same thing
                 st.failed, self.graph_error = True, repr(e)
                 st.graph = None
                 torch.cuda.synchronize()
         return st.graph
+
+    def _sampler_loop(self, st, x0):
+        """What the two device loops share behind the state lookup: the timestep-token table and the captured step for the current
+        weights, the reset of the state to x0 and step steps - 1, and st.steps replays (or eager steps). A DDPM state: in front of the
+        replays, one randn_like(x) per step in the host loop's order (step steps - 1 first) into row s of st.noise -- asynchronous
+        launches."""
+        self._sampler_t_table(st)
+        graph = self._sampler_graph(st)
+        with torch.no_grad():
+            st.x.copy_(x0)
+            st.x_bf16.copy_(x0.to(torch.bfloat16))
+            st.step.fill_(st.steps - 1)
+            if st.noise is not None:
+                for s in reversed(range(st.steps)):
+                    st.noise[s].copy_(torch.randn_like(st.x).view(-1))
+            for _ in range(st.steps):
+                if graph is not None:
+                    graph.replay()
+                else:
+                    self._sampler_one_step(st)
 
     def sample_ddim(self, x0, diffusion):
         """ddim_sample_loop(self, x0.shape, x0, clip_denoised=False, eta=0.0) of `diffusion` with the loop on the device -> samples
@@ -621,20 +684,24 @@ class _CachedEpsBase:
         device and the host never waits for the device between the steps. The generator ends where the host loop leaves it (one unused
         randn_like per step)."""
         x0 = x0.float()
-        st = self._ddim_state(x0, diffusion)
-        self._ddim_t_table(st)
-        graph = self._ddim_graph(st)
+        st = self._sampler_state(x0, diffusion, ddpm=False)
+        self._sampler_loop(st, x0)
         with torch.no_grad():
-            st.x.copy_(x0)
-            st.x_bf16.copy_(x0.to(torch.bfloat16))
-            st.step.fill_(st.steps - 1)
-            for _ in range(st.steps):
-                if graph is not None:
-                    graph.replay()
-                else:
-                    self._ddim_one_step(st)
             for _ in range(st.steps):
                 torch.randn_like(st.x)                                        # ddim_sample draws its noise even at eta = 0
+            return st.x.clone()
+
+    def sample_ddpm(self, x0, diffusion):
+        """p_sample_loop(self, x0.shape, x0, clip_denoised=False) of `diffusion` with the loop on the device -> samples [B, T, D] fp32,
+        the same bits. The host first enqueues the loop's num_timesteps randn_like draws, in the loop's order, into the state's noise
+        table -- the suffix pass draws nothing, so every step sees the values the host loop's own draw would have given it, and the
+        generator ends where the host loop leaves it -- then num_timesteps replays of one captured sampler step (x_embedder,
+        mla_sampler_rows, the suffix pass, final_layer, mla_ddpm_step reading row *step of the table). Nothing is copied to the device and
+        the host never waits for the device between the steps."""
+        x0 = x0.float()
+        st = self._sampler_state(x0, diffusion, ddpm=True)
+        self._sampler_loop(st, x0)
+        with torch.no_grad():
             return st.x.clone()
 
 

@@ -330,13 +330,14 @@ class MLA(nn.Module):
     # ---- what the four sampling entry points share (called as MLA._check_modes: the mode errors come before `self` is touched)
     @staticmethod
     def _check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision="bf16",
-                     groups_attention="head"):
-        from .infer import (check_groups_attention, check_prefill, check_prefill_precision, check_sampler, check_suffix_attention,
-                            check_suffix_weights)
+                     groups_attention="head", ddpm_sampler="host"):
+        from .infer import (check_ddpm_sampler, check_groups_attention, check_prefill, check_prefill_precision, check_sampler,
+                            check_suffix_attention, check_suffix_weights)
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
         check_prefill_precision(prefill_precision, prefill)
         check_sampler(sampler, reuse_prefix, use_ddim, num_ddim_steps)
+        check_ddpm_sampler(ddpm_sampler, reuse_prefix, use_ddim, num_ddim_steps)
         check_suffix_attention(suffix_attention, reuse_prefix)
         check_groups_attention(groups_attention, reuse_prefix)
 
@@ -349,8 +350,9 @@ class MLA(nn.Module):
             _ = torch.randint(0, self.diffusion.num_timesteps, (T,), device=device)
         return torch.cat(draws, dim=0).float()
 
-    def _sample(self, eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs):
-        """x0 [B, T, D] -> samples: the DDIM loop (eta = 0) on the device (an engine's sample_ddim) or on the host, or the DDPM loop."""
+    def _sample(self, eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs, ddpm_sampler="host"):
+        """x0 [B, T, D] -> samples: the DDIM loop (eta = 0) on the device (an engine's sample_ddim) or on the host, or the DDPM loop of the
+        training diffusion on the device (sample_ddpm) or on the host."""
         device = x0.device
         if use_ddim and num_ddim_steps is not None:
             if self.ddim_diffusion is None:
@@ -359,6 +361,8 @@ class MLA(nn.Module):
                 return eps_model.sample_ddim(x0, self.ddim_diffusion)
             return self.ddim_diffusion.ddim_sample_loop(eps_model, x0.shape, x0, clip_denoised=False, model_kwargs=model_kwargs,
                                                         progress=False, device=device, eta=0.0)
+        if ddpm_sampler == "device":
+            return eps_model.sample_ddpm(x0, self.diffusion)
         return self.diffusion.p_sample_loop(eps_model, x0.shape, x0, clip_denoised=False, model_kwargs=model_kwargs, progress=False,
                                             device=device)
 
@@ -400,7 +404,7 @@ class MLA(nn.Module):
                             action_dim: int = 7, *, input_ids: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                             camera_name: str = "rlbench_front", reuse_prefix: bool = True, suffix_weights: str = "bf16",
                             prefill: str = "train", sampler: str = "host", suffix_attention: str = "head",
-                            prefill_precision: str = "bf16", **kwargs) -> np.ndarray:
+                            prefill_precision: str = "bf16", ddpm_sampler: str = "host", **kwargs) -> np.ndarray:
         """model_mla.py:592-775: 8-step DDIM (eta = 0) over the action chunk with the VLM as the epsilon model, then
         un-normalisation.
         * ``image`` is a PIL image / uint8 HWC frame (pre-processed here like the reference does, :656-660) or an already
@@ -427,8 +431,17 @@ class MLA(nn.Module):
         "device" keeps the loop on the device (mla_amd/infer.py:_CachedEpsBase.sample_ddim): one captured sampler step replayed
         ``num_ddim_steps`` times with the step index in device memory, no copy to the device and no host wait between the steps, the same
         bits. It composes with every ``suffix_weights`` and ``prefill`` mode; it raises ValueError when ``reuse_prefix=False``, the
-        cached-prefix engine does not serve the shape, ``use_ddim=False`` or ``num_ddim_steps=None`` (the DDPM sampler needs per-step
-        noise values), and for an unknown value.
+        cached-prefix engine does not serve the shape, ``use_ddim=False`` or ``num_ddim_steps=None`` (the DDPM loop has its own keyword,
+        ``ddpm_sampler``), and for an unknown value.
+        ``ddpm_sampler`` (opt-in, cached prefix only): who runs the DDPM loop of ``use_ddim=False`` / ``num_ddim_steps=None`` (the 100-step
+        p_sample_loop of the training diffusion). "host" (default) runs it in torch expressions on the host, with a device wait in every
+        step; "device" keeps it on the device (mla_amd/infer.py:_CachedEpsBase.sample_ddpm): the steps' randn_like draws are enqueued up
+        front, in the host loop's order, into a device table, then one captured sampler step (its update is mla_ddpm_step) is replayed
+        once per step with the step index in device memory -- no copy to the device, no host wait between the steps, the same bits and
+        the same generator position afterwards. It composes with every ``suffix_weights``, ``prefill``, ``prefill_precision`` and
+        ``suffix_attention`` mode; it raises ValueError when ``reuse_prefix=False``, the cached-prefix engine does not serve the shape,
+        the call runs the DDIM sampler (``use_ddim=True`` with ``num_ddim_steps``: the keyword is never silently ignored), and for an
+        unknown value.
         ``suffix_attention`` (opt-in, cached prefix only): "head" (default) runs the sampler steps' attention as one workgroup per (head,
         16 queries) (mla_attn_decode / mla_attn_chunk); "split" cuts every head's key range over several workgroups and merges the partial
         softmax states in a fixed order with a second launch (mla_attn_chunk_split with the library's plan): the same function up to
@@ -442,8 +455,9 @@ class MLA(nn.Module):
         measured. It composes with every ``suffix_weights``, ``sampler`` and ``suffix_attention`` mode; it raises ValueError for an
         unknown value and for anything but "bf16" unless ``prefill="compact"`` (hence also when ``reuse_prefix=False``): there is never
         a silent bf16 prefill."""
-        from .infer import PrefixCachedEps, sampler_needs_engine, suffix_attention_needs_engine
-        MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision)
+        from .infer import PrefixCachedEps, ddpm_sampler_needs_engine, sampler_needs_engine, suffix_attention_needs_engine
+        MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision,
+                         ddpm_sampler=ddpm_sampler)
         if prefill != "train" and not reuse_prefix:
             raise ValueError(f"prefill={prefill!r} needs the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has no "
                              "separate prefill")
@@ -471,11 +485,12 @@ class MLA(nn.Module):
                              "64 suffix rows, head_dim 128); use prefill=\"train\"")
         if not reuse_prefix:
             sampler_needs_engine(sampler, "PrefixCachedEps", T)
+            ddpm_sampler_needs_engine(ddpm_sampler, "PrefixCachedEps", T)
             suffix_attention_needs_engine(suffix_attention, T)
         if reuse_prefix:
             eps_model = PrefixCachedEps.for_inputs(self.vlm, n_action_rows=T, suffix_weights=suffix_weights, prefill=prefill,
                                                    suffix_attention=suffix_attention, prefill_precision=prefill_precision, **model_kwargs)
-        samples = self._sample(eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs)
+        samples = self._sample(eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs, ddpm_sampler)
         return self._actions([samples[:1].float().cpu().numpy()], unnorm_key)[0]
 
     @torch.inference_mode()
@@ -485,7 +500,8 @@ class MLA(nn.Module):
                                   reuse_prefix: bool = True, suffix_weights: str = "bf16",
                                   num_samples: Optional[int] = None, prefill: str = "train", sampler: str = "host",
                                   suffix_attention: str = "head", prefill_precision: str = "bf16",
-                                  groups_attention: str = "head", batch_prefill: str = "train") -> np.ndarray:
+                                  groups_attention: str = "head", batch_prefill: str = "train",
+                                  ddpm_sampler: str = "host") -> np.ndarray:
         """B observations -> [B, T, action_dim]: by definition B independent `predict_action_diff` calls (the reference's
         `predict_action_batch`, model_mla.py:994, is dead code), computed on ONE cached prefix pass per DDIM step
         (mla_amd/infer.py:BatchedPrefixCachedEps): the prompts may have different lengths, the FPS start indices are drawn once per chunk.
@@ -525,6 +541,9 @@ class MLA(nn.Module):
         ``sampler``: predict_action_diff's, with and without ``num_samples``: "device" runs every pass's DDIM loop on the device (the same
         bits) and raises ValueError where "host" would loop over whole-forward calls (``reuse_prefix=False``, a shape the batched engine
         does not serve) or run the DDPM sampler.
+        ``ddpm_sampler``: predict_action_diff's, with and without ``num_samples``: "device" runs the DDPM loop (``use_ddim=False``) of
+        every pass or sub-batch on the device, one sample_ddpm each in the order the host path runs its p_sample_loop calls (the same
+        bits and generator position); it raises ValueError where "host" would loop over whole-forward calls or the call runs DDIM.
         ``suffix_attention``: predict_action_diff's, forwarded for B = 1; B >= 2 with "split" raises NotImplementedError (the ragged and
         groups engines take their split-key form from ``groups_attention``).
         ``groups_attention`` (opt-in, cached prefix only), with and without ``num_samples``: "head" (default) runs the sampler steps'
@@ -537,9 +556,9 @@ class MLA(nn.Module):
         ValueError for an unknown value, and for "split" when ``reuse_prefix=False`` or the batched engine does not serve the shape: it is
         never the warned loop."""
         from .infer import (BatchedPrefixCachedEps, batch_prefill_needs_engine, check_batch_prefill, check_prefill_precision,
-                            groups_attention_needs_engine, sampler_needs_engine, suffix_attention_single_only)
+                            ddpm_sampler_needs_engine, groups_attention_needs_engine, sampler_needs_engine, suffix_attention_single_only)
         MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps,
-                         groups_attention=groups_attention)
+                         groups_attention=groups_attention, ddpm_sampler=ddpm_sampler)
         check_prefill_precision(prefill_precision)                           # an unknown value only: no mode but "bf16" is served here
         check_batch_prefill(batch_prefill, reuse_prefix)
         if prefill != "train":
@@ -557,7 +576,7 @@ class MLA(nn.Module):
             return self._predict_action_diff_batch_samples(images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix,
                                                            suffix_weights, num_samples, sampler, suffix_attention, groups_attention,
-                                                           batch_prefill)
+                                                           batch_prefill, ddpm_sampler)
         input_ids, pointclouds = MLA._batch_prompts(self, B, instructions, input_ids, pointclouds, cur_robot_states)
         if noise is not None and tuple(noise.shape[:2]) != (B, T):
             raise ValueError(f"noise must be [B, T, action_dim] = [{B}, {T}, ...], got {tuple(noise.shape)}")
@@ -571,7 +590,7 @@ class MLA(nn.Module):
         # a call that ends in a single-observation method takes the mode as that method's compact prefill
         single = {} if batch_prefill == "train" else {"prefill": "compact", "prefill_precision": batch_prefill}
         if B == 1:
-            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler,
+            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler, ddpm_sampler=ddpm_sampler,
                        suffix_attention="split" if groups_attention == "split" else suffix_attention, **single)[None]
         if suffix_weights != "bf16":
             raise NotImplementedError(f"suffix_weights={suffix_weights!r}: the batched engine (BatchedPrefixCachedEps, mla_gemm_suffix_bf16) "
@@ -584,19 +603,21 @@ class MLA(nn.Module):
             reuse_prefix = BatchedPrefixCachedEps.supports_batch(self.vlm, T)
         if not reuse_prefix:
             sampler_needs_engine(sampler, "BatchedPrefixCachedEps", T)
+            ddpm_sampler_needs_engine(ddpm_sampler, "BatchedPrefixCachedEps", T)
             return np.stack([one(b, reuse_prefix=False) for b in range(B)])
         device, ids_rows, inputs = self._batch_inputs(images, pointclouds, cur_robot_states, ids_rows, unnorm_key, camera_name)
         x0 = self._draw_x0([None if noise is None else noise[b:b + 1] for b in range(B)], T, action_dim, device)
         out = []
         for sub, eng in BatchedPrefixCachedEps.for_batch(self.vlm, ids_rows, T, suffix_attention=groups_attention,
                                                          batch_prefill=batch_prefill, **inputs):
-            samples = self._sample(eng, x0[sub.start:sub.stop].contiguous(), sampler, use_ddim, num_ddim_steps, {})
+            samples = self._sample(eng, x0[sub.start:sub.stop].contiguous(), sampler, use_ddim, num_ddim_steps, {}, ddpm_sampler)
             out.append(samples.float().cpu().numpy())
         return self._actions(out, unnorm_key)
 
     def _predict_action_diff_batch_samples(self, images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix, suffix_weights, num_samples,
-                                           sampler="host", suffix_attention="head", groups_attention="head", batch_prefill="train"):
+                                           sampler="host", suffix_attention="head", groups_attention="head", batch_prefill="train",
+                                           ddpm_sampler="host"):
         """predict_action_diff_batch(num_samples=N) -> [B, N, T, action_dim] (called inside its inference mode; see its docstring)."""
         B, N, T = len(images), int(num_samples), self.future_action_window_size + 1
         if N < 1:
@@ -613,15 +634,17 @@ class MLA(nn.Module):
                                                     camera_name=camera_name, **kw)
         single = {} if batch_prefill == "train" else {"prefill": "compact", "prefill_precision": batch_prefill}
         if B == 1:
-            return samples_of(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler,
+            return samples_of(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler, ddpm_sampler=ddpm_sampler,
                               suffix_attention=suffix_attention, groups_attention=groups_attention, **single)[None]
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
                              "bf16 weights only")
         if reuse_prefix:
-            from .infer import BatchedSampleGroupsEps, batch_prefill_needs_engine, groups_attention_needs_engine, sampler_needs_engine
+            from .infer import (BatchedSampleGroupsEps, batch_prefill_needs_engine, ddpm_sampler_needs_engine, groups_attention_needs_engine,
+                                sampler_needs_engine)
             if not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T, warn=False):
                 sampler_needs_engine(sampler, "BatchedSampleGroupsEps", T)
+                ddpm_sampler_needs_engine(ddpm_sampler, "BatchedSampleGroupsEps", T)
                 groups_attention_needs_engine(groups_attention, "BatchedSampleGroupsEps", T)
                 batch_prefill_needs_engine(batch_prefill, "BatchedSampleGroupsEps", T)
             if suffix_weights != "bf16" and not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T, warn=False):
@@ -629,8 +652,8 @@ class MLA(nn.Module):
                                  f"{1 + T} suffix rows per sample at this head_dim; draw the samples with \"bf16\"")
             if not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T) or not BatchedSampleGroupsEps.fits_pass(T, N):
                 # one observation at a time: predict_action_diff_samples serves (or refuses) the shape and the mode itself
-                return np.stack([samples_of(b, suffix_weights=suffix_weights, sampler=sampler, groups_attention=groups_attention, **single)
-                                 for b in range(B)])
+                return np.stack([samples_of(b, suffix_weights=suffix_weights, sampler=sampler, ddpm_sampler=ddpm_sampler,
+                                            groups_attention=groups_attention, **single) for b in range(B)])
         else:
             return np.stack([samples_of(b, reuse_prefix=False) for b in range(B)])
         device, ids_rows, inputs = self._batch_inputs(images, pointclouds, cur_robot_states, ids_rows, unnorm_key, camera_name)
@@ -638,7 +661,7 @@ class MLA(nn.Module):
         out = []
         for sub, eng in BatchedSampleGroupsEps.for_batch(self.vlm, ids_rows, T, N, suffix_weights, suffix_attention=groups_attention,
                                                          batch_prefill=batch_prefill, **inputs):
-            samples = self._sample(eng, x0[sub.start * N:sub.stop * N].contiguous(), sampler, use_ddim, num_ddim_steps, {})
+            samples = self._sample(eng, x0[sub.start * N:sub.stop * N].contiguous(), sampler, use_ddim, num_ddim_steps, {}, ddpm_sampler)
             out.append(samples.float().cpu().numpy().reshape(sub.stop - sub.start, N, T, -1))
         return self._actions(out, unnorm_key)
 
@@ -649,7 +672,8 @@ class MLA(nn.Module):
                                     noise: Optional[torch.Tensor] = None, camera_name: str = "rlbench_front",
                                     reuse_prefix: bool = True, suffix_weights: str = "bf16", prefill: str = "train",
                                     sampler: str = "host", suffix_attention: str = "head",
-                                    prefill_precision: str = "bf16", groups_attention: str = "head") -> np.ndarray:
+                                    prefill_precision: str = "bf16", groups_attention: str = "head",
+                                    ddpm_sampler: str = "host") -> np.ndarray:
         """N action chunks for ONE observation -> [N, T, action_dim]: by definition N independent `predict_action_diff` calls on the same
         observation with the initial samples ``noise[n]`` (critic / best-of-N choice, uncertainty estimates, temporal ensembling), computed
         on ONE cached prefix (mla_amd/infer.py:SampleGroupsEps): the encoders and the decoder prefill run once per call, every sampler step
@@ -669,6 +693,10 @@ class MLA(nn.Module):
         ``sampler`` (opt-in): predict_action_diff's modes; "device" runs the DDIM loop of every pass on the device (the same bits).
         Forwarded for ``num_samples=1``; raises ValueError when ``reuse_prefix=False``, the shared-prefix engine does not serve the shape,
         ``use_ddim=False`` or ``num_ddim_steps=None``.
+        ``ddpm_sampler`` (opt-in): predict_action_diff's modes; "device" runs the DDPM loop (``use_ddim=False``) of every pass on the
+        device, one sample_ddpm per pass in the host path's order (the same bits and generator position). Forwarded for
+        ``num_samples=1``; raises ValueError when ``reuse_prefix=False``, the shared-prefix engine does not serve the shape, or the call
+        runs the DDIM sampler.
         ``suffix_attention``: predict_action_diff's, forwarded for ``num_samples=1``; more samples with "split" raise NotImplementedError
         (the groups engine keeps mla_attn_chunk_groups).
         ``prefill_precision`` (opt-in, ``prefill="compact"`` only): predict_action_diff's modes; "fp8" runs the projections of the one
@@ -679,9 +707,10 @@ class MLA(nn.Module):
         It composes with every ``suffix_weights``, ``sampler``, ``prefill`` and ``prefill_precision`` mode; forwarded as
         ``suffix_attention="split"`` for ``num_samples=1``; raises ValueError for an unknown value, and for "split" when
         ``reuse_prefix=False`` or the shared-prefix engine does not serve the shape."""
-        from .infer import SampleGroupsEps, groups_attention_needs_engine, sampler_needs_engine, suffix_attention_single_only
+        from .infer import (SampleGroupsEps, ddpm_sampler_needs_engine, groups_attention_needs_engine, sampler_needs_engine,
+                            suffix_attention_single_only)
         MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision,
-                         groups_attention)
+                         groups_attention, ddpm_sampler)
         if int(num_samples) != 1:
             suffix_attention_single_only(suffix_attention, f"predict_action_diff_samples with num_samples={num_samples}")
         if prefill != "train" and not reuse_prefix:
@@ -701,7 +730,7 @@ class MLA(nn.Module):
                                             camera_name=camera_name, **kw)
         if N == 1:
             return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, prefill=prefill, sampler=sampler,
-                       suffix_attention="split" if groups_attention == "split" else suffix_attention,
+                       ddpm_sampler=ddpm_sampler, suffix_attention="split" if groups_attention == "split" else suffix_attention,
                        prefill_precision=prefill_precision)[None]
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
@@ -709,6 +738,7 @@ class MLA(nn.Module):
         if reuse_prefix:
             if not SampleGroupsEps.supports_samples(self.vlm, T, warn=False):
                 sampler_needs_engine(sampler, "SampleGroupsEps", T)
+                ddpm_sampler_needs_engine(ddpm_sampler, "SampleGroupsEps", T)
                 groups_attention_needs_engine(groups_attention, "SampleGroupsEps", T)
             if prefill != "train" and not SampleGroupsEps.supports_samples(self.vlm, T, warn=False):
                 raise ValueError(f"prefill={prefill!r}: the shared-prefix engine (SampleGroupsEps) does not serve {1 + T} suffix rows per "
@@ -734,6 +764,6 @@ class MLA(nn.Module):
         out = []
         for start, stop in passes:                                           # one prefill, then the passes' sampler loops one after the other
             eng.set_groups(stop - start)
-            samples = self._sample(eng, x0[start:stop].contiguous(), sampler, use_ddim, num_ddim_steps, {})
+            samples = self._sample(eng, x0[start:stop].contiguous(), sampler, use_ddim, num_ddim_steps, {}, ddpm_sampler)
             out.append(samples.float().cpu().numpy())
         return self._actions(out, unnorm_key)

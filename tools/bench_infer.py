@@ -45,6 +45,10 @@
                                                           per-chunk latency with the 95 % interval of the pair differences, the prefill
                                                           (encoders + prefix rows) alone, and the per-step share (chunk - prefill) / steps
                                                           of both arms; also whether the two arms returned the same bits
+    python tools/bench_infer.py --pair-ddpm-sampler [--pairs P] [--chunks C[,C..]]
+                                                          the same for the DDPM loop: use_ddim=False calls (the 100 steps of the training
+                                                          diffusion) with ddpm_sampler="host" and ddpm_sampler="device" alternating in
+                                                          one process, in pairs
     python tools/bench_infer.py --pair-attention [--pairs P] [--chunks C[,C..]] [--kernel-table]
                                                           suffix_attention="head" and "split" chunks alternating in one process, in pairs,
                                                           for every chunk length (default 1,16) with bf16 and with fp8 suffix weights (the
@@ -152,6 +156,7 @@ def main():
     ap.add_argument("--pair-fp8", action="store_true", help="alternate bf16 and fp8 chunks in one process, in pairs")
     ap.add_argument("--pair-prefill", action="store_true", help="alternate prefill=\"train\", \"compact\" and \"compact\" with prefill_precision=\"fp8\" in one process")
     ap.add_argument("--pair-sampler", action="store_true", help="alternate sampler=\"host\" and sampler=\"device\" in one process, in pairs")
+    ap.add_argument("--pair-ddpm-sampler", action="store_true", help="alternate ddpm_sampler=\"host\" and ddpm_sampler=\"device\" on use_ddim=False calls in one process, in pairs")
     ap.add_argument("--pair-attention", action="store_true", help="alternate suffix_attention=\"head\" and \"split\" in one process, in pairs; with --samples / --batch: groups_attention "
                     "on the multi-row routes")
     ap.add_argument("--pair-batch-prefill", action="store_true", help="with --batch: alternate batch_prefill=\"train\" and \"fp8\" in one process, in pairs")
@@ -161,8 +166,8 @@ def main():
     ap.add_argument("--samples", type=str, default="", help="N[,N..]: predict_action_diff_samples vs the batched call on N copies vs N calls")
     ap.add_argument("--chunks", type=str, default="", help="with --samples / --pair-sampler: action chunk lengths to measure in one process (default: --chunk; --pair-sampler: 1,16)")
     args = ap.parse_args()
-    if args.pair_sampler:
-        return main_pair_sampler(args)
+    if args.pair_sampler or args.pair_ddpm_sampler:
+        return main_pair_sampler(args, ddpm=args.pair_ddpm_sampler)
     batches = [int(v) for v in args.batch.split(",")]
     if args.pair_batch_prefill:
         return main_pair_batch_prefill(args, batches)
@@ -306,31 +311,34 @@ def main_pair(args):
     print(json.dumps(out))
 
 
-def main_pair_sampler(args):
+def main_pair_sampler(args, ddpm=False):
     """sampler="host" vs sampler="device" on the same box, alternating, per chunk length and suffix-weight mode: predict_action_diff per
     chunk (host clock around `iters` calls that end in a device synchronise), the prefill alone (PrefixCachedEps.for_inputs: encoders +
     prefix rows, the same for both arms) and from the two the per-step share (chunk - prefill) / steps of each arm -- the suffix pass
-    plus the sampler's glue, which is what the mode changes."""
+    plus the sampler's glue, which is what the mode changes. ddpm: the same for ddpm_sampler= on use_ddim=False calls (the steps are the
+    training diffusion's; both arms draw the steps' noise, the warm-up calls under the same seed)."""
     from mla_amd.infer import PrefixCachedEps
     m, b, ids = _setup()
     dev = ids.device
     image, pc, state = _observation(b)
     mk = dict(input_ids=ids, **_engine_kw(b))
     arms = ("host", "device")
+    word, name = ("ddpm_sampler", "ddpm") if ddpm else ("sampler", "ddim")
+    steps = m.diffusion.num_timesteps if ddpm else args.steps
     for C in ([int(v) for v in args.chunks.split(",")] if args.chunks else [1, 16]):
         m.future_action_window_size = m.vlm.future_action_window_size = C - 1
         noise = torch.randn(1, C, 7, device=dev)
-        kw = dict(image=image, pointcloud=pc, cur_robot_state=state, input_ids=ids, num_ddim_steps=args.steps, noise=noise)
+        kw = dict(image=image, pointcloud=pc, cur_robot_state=state, input_ids=ids, num_ddim_steps=args.steps, noise=noise, use_ddim=not ddpm)
         for w in ("bf16", "fp8"):
             acts = {}
             for arm in arms:                                                # engines, graphs, tables; the same seed: the same FPS start indices
                 torch.manual_seed(1)
-                acts[arm] = m.predict_action_diff(suffix_weights=w, sampler=arm, **kw)
+                acts[arm] = m.predict_action_diff(suffix_weights=w, **{word: arm}, **kw)
             with torch.inference_mode():
                 eng = PrefixCachedEps.for_inputs(m.vlm, n_action_rows=C, suffix_weights=w, **mk)
 
             def chunk_ms(arm):
-                return _time_ms(lambda: m.predict_action_diff(suffix_weights=w, sampler=arm, **kw), args.iters)
+                return _time_ms(lambda: m.predict_action_diff(suffix_weights=w, **{word: arm}, **kw), args.iters)
 
             def prefill_ms():
                 with torch.inference_mode():
@@ -340,9 +348,9 @@ def main_pair_sampler(args):
                 for arm in arms:
                     chunk[arm].append(chunk_ms(arm))
                 prefill.append(prefill_ms())
-            step = {arm: [(c - p) / args.steps for c, p in zip(chunk[arm], prefill)] for arm in arms}
-            print(json.dumps({"metric": "predict_action_diff, MLA-Llama2-7B, batch 1: sampler=host vs sampler=device in alternating pairs",
-                              "action_chunk": C, "suffix_rows": C + 1, "suffix_weights": w, "ddim_steps": args.steps, "pairs": args.pairs,
+            step = {arm: [(c - p) / steps for c, p in zip(chunk[arm], prefill)] for arm in arms}
+            print(json.dumps({"metric": f"predict_action_diff, MLA-Llama2-7B, batch 1: {word}=host vs {word}=device in alternating pairs",
+                              "action_chunk": C, "suffix_rows": C + 1, "suffix_weights": w, f"{name}_steps": steps, "pairs": args.pairs,
                               "iters_per_arm_and_pair": args.iters, "unit": "ms",
                               "chunk_ms": {k: [round(v, 2) for v in vs] for k, vs in chunk.items()},
                               "chunk_device_minus_host": _pair_stats(chunk["host"], chunk["device"]),
@@ -350,7 +358,8 @@ def main_pair_sampler(args):
                               "per_step_share_ms": {k: [round(v, 3) for v in vs] for k, vs in step.items()},
                               "per_step_share_device_minus_host": _pair_stats(step["host"], step["device"]),
                               "same_bits": bool(np.array_equal(acts["host"], acts["device"])),
-                              "step_captured": all(st.graph is not None for st in eng._ddim.values()), "graph_error": eng.graph_error,
+                              "step_captured": all(st.graph is not None for st in (eng._ddpm if ddpm else eng._ddim).values()),
+                              "graph_error": eng.graph_error,
                               "data": "synthetic"}), flush=True)
 
 
