@@ -523,8 +523,8 @@ int mla_sampler_rows(void* h_in, const void* t_table, const void* x_e, const int
  *     un-normalised state (m, l, 128 fp32 sums) of its valid query rows to `ws`; a range wholly behind a query's causal limit writes the
  *     empty state (m = -inf, l = 0). Launch 2: one wave per (b, h, query): M = max_s m_s, numerator and denominator summed over
  *     s = 0, 1, ... with the weight exp2(m_s - M) (an empty state adds exactly zero, no inf - inf is formed), one division, one bf16
- *     rounding, the row of o ([B * R, H * 128], row stride ld_o, 4-B aligned). splits = 0: the plan's. splits == 1: launch 1 alone in its
- *     finishing form -- no workspace access, no second launch, o bit for bit mla_attn_chunk's. ws: caller-owned, 16-B aligned, at least
+ *     rounding, the row of o ([B * R, H * 128], row stride ld_o, 4-B aligned). splits = 0: the plan's. splits == 1: mla_attn_chunk's own
+ *     launch -- no workspace access, no second launch, o bit for bit mla_attn_chunk's. ws: caller-owned, 16-B aligned, at least
  *     mla_attn_chunk_split_ws_bytes(...) bytes (may be null when splits resolves to 1); no word of it is read that this call did not
  *     write, nothing behind the needed bytes is touched. No allocation, no state between calls, no counters, no atomics, no workgroup
  *     waits on another; deterministic, graph-capturable. Masked and padding loads never touch rows at or behind S_kv. All argument checks

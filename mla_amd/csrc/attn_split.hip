@@ -7,7 +7,7 @@
 //                          its valid query rows into the caller's workspace. launch 2: one wave per (b, h, query) merges the states in the
 //                          order s = 0, 1, ..., divides once, rounds once. No counters, no atomics, no workgroup waits on another: the
 //                          dependency is the kernel boundary (~1.2 us), which in-launch combines measured dearer than.
-//                          splits == 1: launch 1 alone in its finishing form -- no workspace access, and mla_attn_chunk's bits.
+//                          splits == 1: mla_attn_chunk itself -- no workspace access, no second launch.
 //   mla_attn_groups_split  the same two launches under the addressing of mla_attn_chunk_groups / mla_attn_chunk_ragged_groups (G groups of R
 //                          rows behind one prefix per sample, the prefix length optionally read on the device): opt-in
 //                          groups_attention="split" of the batched and N-sample calls. One split is the head form's own launch.
@@ -15,25 +15,14 @@
 //
 // Nothing here allocates, keeps state between calls or reads a workspace word this call did not write: graph-capturable, deterministic.
 #include "common.h"
+#include "attn_suffix_tile.h"
+#include "../../include/mla_hip.h"              // the head forms a single split resolves to (infer.hip), and this file's own entry points
 
 namespace {
 
-constexpr int SP_RMAX = 64;
-constexpr int SP_NW = 4;                        // waves per workgroup: wave w takes tiles t0 + w, t0 + w + 4, ... of its range
-constexpr int SP_VP = 68;                       // V^T row pitch in keys (136 B: 8-B aligned, staggered banks), as in attn_chunk_kernel
 constexpr int SP_CUS = 256;                     // the launcher plans for the MI355X's 256 CUs (no device query, no state)
 constexpr int SP_STATE = 130;                   // fp32 words per (b, h, query, s): 128 sums in the first array, (m, l) in the second
 constexpr int SP_CW = 4;                        // combine launch: waves (= states merged) per workgroup
-
-__device__ __forceinline__ bf16x8_t as_frag(const u32x4_t v) { return __builtin_bit_cast(bf16x8_t, v); }
-__device__ __forceinline__ bf16x8_t pack_pfrag(const f32x4_t lo, const f32x4_t hi) {
-  u32x4_t u;
-  u[0] = pack2bf(lo[0], lo[1]); u[1] = pack2bf(lo[2], lo[3]);
-  u[2] = pack2bf(hi[0], hi[1]); u[3] = pack2bf(hi[2], hi[3]);
-  return as_frag(u);
-}
-// the one normalisation both forms end in: one division, one bf16 rounding
-__device__ __forceinline__ bf16_t sp_finish(float O, float L) { return f2bf(O / L); }
 
 struct SplitPlan { int nT, splits, tps, wgs, cwgs; long long ws_bytes; };
 
@@ -41,7 +30,7 @@ inline long long sp_ws_bytes(int B, int H, int R, int splits) {
   return splits > 1 ? (long long)B * H * R * splits * SP_STATE * 4 : 0;
 }
 // splits grows by one while launch 1 still fits one workgroup per CU (measured: a second round of workgroups costs more than it saves),
-// splits < nT, and the largest range has more than SP_NW tiles: a workgroup's time is its passes over its range, four tiles per pass, and
+// splits < nT, and the largest range has more than SUF_NW tiles: a workgroup's time is its passes over its range, four tiles per pass, and
 // cutting below one pass saves nothing but adds states to merge (measured at 9 tiles: 3 ranges 12.3 us, 4: 12.5, 9: 14.0 per launch
 // pair). Every range so keeps at least 2 tiles. 1 when twice the unsplit grid no longer fits the chip.
 inline SplitPlan sp_plan(int B, int H, int R, int S_kv, int cus, int forced) {
@@ -51,7 +40,7 @@ inline SplitPlan sp_plan(int B, int H, int R, int S_kv, int cus, int forced) {
   p.splits = 1;
   if (forced > 0) p.splits = forced;
   else
-    while (base * (p.splits + 1) <= cus && p.splits < p.nT && (p.nT + p.splits - 1) / p.splits > SP_NW) ++p.splits;
+    while (base * (p.splits + 1) <= cus && p.splits < p.nT && (p.nT + p.splits - 1) / p.splits > SUF_NW) ++p.splits;
   p.tps = (p.nT + p.splits - 1) / p.splits;
   const long long wgs = base * p.splits;
   p.wgs = wgs > 0x7fffffffLL ? -1 : (int)wgs;
@@ -60,17 +49,18 @@ inline SplitPlan sp_plan(int B, int H, int R, int S_kv, int cus, int forced) {
   return p;
 }
 
-// attn_chunk_kernel over the tile range [t0, t0 + cnt) of split s = blockIdx.x % splits (ranges differ by at most one tile: the first
-// nT % splits ranges take one more). FINISH (splits == 1): the range is every tile, the trip count, the masks and the merge are
-// attn_chunk_kernel's, and so is every bit of o. Otherwise a wave whose tile lies behind the range skips the tile (it still meets the
-// barriers), and the merged, un-normalised state goes to ws: sums [(b H + h) R + r][s][128], then (m, l) [(b H + h) R + r][s][2].
-// GROUPS (mla_attn_groups_split, never with FINISH): attn_chunk_groups_kernel's addressing (infer.hip) under the same arithmetic. The
-// launch's "samples" are the B G (sample, group) pairs, S_kv arrives as S_p -- or, with prefix_len, is read from prefix_len[b] and clamped
-// to [0, S_cap - G R], one value per workgroup (readfirstlane), so trip and barrier counts stay uniform -- and a group's S_p + R logical
+// Launch 1 (splits > 1 only): attn_chunk_kernel's tile step (infer.hip; written out here, attn_suffix_tile.h says why) over the tile
+// range [t0, t0 + cnt) of split s = blockIdx.x % splits (ranges differ by at most one tile: the first nT % splits ranges take one
+// more). Wave w takes tiles t0 + w, t0 + w + 4, ... of its range; a wave whose tile lies behind the range skips the tile (it still
+// meets the barriers), and the merged, un-normalised state goes to ws: sums [(b H + h) R + r][s][128], then (m, l)
+// [(b H + h) R + r][s][2].
+// GROUPS (mla_attn_groups_split): attn_chunk_groups_kernel's addressing (infer.hip) under the same arithmetic. The launch's "samples"
+// are the B G (sample, group) pairs, S_kv arrives as S_p -- or, with prefix_len, is read from prefix_len[b] and clamped to
+// [0, S_cap - G R], one value per workgroup (readfirstlane), so trip and barrier counts stay uniform -- and a group's S_p + R logical
 // keys are tiled from key 0: logical key j is memory row j (j < S_p) or j + g R. ntiles then depends on the sample: a range behind the
 // sample's last tile has cnt == 0, skips the loop and writes the empty state. State and output rows need no map: (b G + g) is the sample
 // index of the layout above, and of the combine launch. The groups form is a kernel of its own over the same text
-// (attn_split_body.inc): the plain instantiations keep their argument list, and their code.
+// (attn_split_body.inc): each keeps its argument list, and its code.
 template <bool GROUPS>
 struct SpRows {                                                         // memory row of logical key j: j, or behind the prefix j + g R
   int S_p, goff;
@@ -81,28 +71,24 @@ struct SpRows<false> {
   int S_p, goff;
   __device__ __forceinline__ int operator()(int j) const { return j; }
 };
-struct SpGroups { int G; const int* prefix_len; int S_cap; };
 
-template <bool FINISH>
-__global__ __launch_bounds__(64 * SP_NW) void attn_chunk_split_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
-                                                                      const bf16_t* __restrict__ v, bf16_t* __restrict__ o, int H, int S_kv,
-                                                                      int R, long long ld, long long bs, long long ld_o, float scale,
-                                                                      int splits, float* __restrict__ ws, long long nstates) {
-  constexpr bool GROUPS = false;
-  const SpGroups gr = {1, nullptr, 0};
+__global__ __launch_bounds__(64 * SUF_NW) void attn_chunk_split_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+                                                                       const bf16_t* __restrict__ v, bf16_t* __restrict__ o, int H, int S_kv,
+                                                                       int R, long long ld, long long bs, long long ld_o, float scale,
+                                                                       int splits, float* __restrict__ ws, long long nstates) {
+  constexpr bool GROUPS = false;                                        // o and ld_o are the combine launch's
+  constexpr int G = 1, S_cap = 0;
+  const int* const prefix_len = nullptr;
 #include "attn_split_body.inc"
 }
 
-// launch 1 of mla_attn_groups_split (splits > 1 only: one split is the head form's own launch); S_kv is S_p without prefix_len
-__global__ __launch_bounds__(64 * SP_NW) void attn_groups_split_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
-                                                                       const bf16_t* __restrict__ v, int G, int H, int S_kv, int R,
-                                                                       long long ld, long long bs, float scale, int splits,
-                                                                       float* __restrict__ ws, long long nstates,
-                                                                       const int* __restrict__ prefix_len, int S_cap) {
-  constexpr bool FINISH = false, GROUPS = true;
-  bf16_t* const o = nullptr;                                            // the combine launch writes o
-  const long long ld_o = 0;
-  const SpGroups gr = {G, prefix_len, S_cap};
+// launch 1 of mla_attn_groups_split; S_kv is S_p without prefix_len
+__global__ __launch_bounds__(64 * SUF_NW) void attn_groups_split_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+                                                                        const bf16_t* __restrict__ v, int G, int H, int S_kv, int R,
+                                                                        long long ld, long long bs, float scale, int splits,
+                                                                        float* __restrict__ ws, long long nstates,
+                                                                        const int* __restrict__ prefix_len, int S_cap) {
+  constexpr bool GROUPS = true;
 #include "attn_split_body.inc"
 }
 
@@ -131,13 +117,13 @@ __global__ __launch_bounds__(64 * SP_CW) void attn_split_combine_kernel(const fl
   const long long bh = row / R;
   const int r = (int)(row - bh * R), h = (int)(bh % H);
   const long long b = bh / H;
-  const uint32_t pk = (uint32_t)sp_finish(O0, L) | ((uint32_t)sp_finish(O1, L) << 16);
+  const uint32_t pk = (uint32_t)f2bf(O0 / L) | ((uint32_t)f2bf(O1 / L) << 16);      // the head forms' finish: one division, one rounding
   *(uint32_t*)(o + (b * R + r) * ld_o + h * 128 + lane * 2) = pk;
 }
 
 #define AL16(p) ((((uintptr_t)(p)) & 15) == 0)
 
-inline bool sp_shape_ok(int B, int H, int R, int S_kv) { return B >= 1 && H >= 1 && R >= 1 && R <= SP_RMAX && S_kv >= R; }
+inline bool sp_shape_ok(int B, int H, int R, int S_kv) { return B >= 1 && H >= 1 && R >= 1 && R <= SUF_RMAX && S_kv >= R; }
 
 }  // namespace
 
@@ -172,33 +158,18 @@ extern "C" int mla_attn_chunk_split(const void* q, const void* k, const void* v,
   MLA_CHECK_ARG(splits >= 0 && splits <= nT, "mla_attn_chunk_split: splits must be in [0, %d] (0 = the plan's) for S_kv %d, got %d", nT, S_kv, splits);
   const SplitPlan p = sp_plan(B, H, R, S_kv, SP_CUS, splits);
   MLA_CHECK_ARG(p.wgs > 0, "mla_attn_chunk_split: grid too large (B %d, H %d, splits %d)", B, H, p.splits);
-  if (p.splits > 1) {
-    MLA_CHECK_ARG(ws, "mla_attn_chunk_split: splits %d needs a workspace (null)", p.splits);
-    MLA_CHECK_ARG(AL16(ws) && (long long)ws_bytes >= p.ws_bytes, "mla_attn_chunk_split: workspace of %lld bytes (16-B aligned) needed for splits %d, got %lld",
-                  p.ws_bytes, p.splits, (long long)ws_bytes);
-  }
-  const size_t lds = (size_t)SP_NW * 128 * SP_VP * 2;                  // >= the merge buffers ([4][128][17] + 128 floats)
-  if (p.splits == 1) {
-    (void)hipFuncSetAttribute((const void*)attn_chunk_split_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(attn_chunk_split_kernel<true>, dim3(p.wgs), dim3(64 * SP_NW), lds, stream, (const bf16_t*)q, (const bf16_t*)k,
-                       (const bf16_t*)v, (bf16_t*)o, H, S_kv, R, ld, batch_stride, ld_o, scale, 1, (float*)nullptr, 0LL);
-  } else {
-    const long long nrows = (long long)B * H * R;
-    (void)hipFuncSetAttribute((const void*)attn_chunk_split_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(attn_chunk_split_kernel<false>, dim3(p.wgs), dim3(64 * SP_NW), lds, stream, (const bf16_t*)q, (const bf16_t*)k,
-                       (const bf16_t*)v, (bf16_t*)o, H, S_kv, R, ld, batch_stride, ld_o, scale, p.splits, (float*)ws, nrows * p.splits);
-    hipLaunchKernelGGL(attn_split_combine_kernel, dim3(p.cwgs), dim3(64 * SP_CW), 0, stream, (const float*)ws, (bf16_t*)o, H, R, ld_o, p.splits,
-                       nrows);
-  }
+  if (p.splits == 1)                                                    // the head form itself: no workspace access, no second launch
+    return mla_attn_chunk(q, k, v, o, B, H, head_dim, S_kv, R, ld, batch_stride, ld_o, scale, stream);
+  MLA_CHECK_ARG(ws, "mla_attn_chunk_split: splits %d needs a workspace (null)", p.splits);
+  MLA_CHECK_ARG(AL16(ws) && (long long)ws_bytes >= p.ws_bytes, "mla_attn_chunk_split: workspace of %lld bytes (16-B aligned) needed for splits %d, got %lld",
+                p.ws_bytes, p.splits, (long long)ws_bytes);
+  const long long nrows = (long long)B * H * R;
+  (void)hipFuncSetAttribute((const void*)attn_chunk_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SUF_LDS_BYTES);
+  hipLaunchKernelGGL(attn_chunk_split_kernel, dim3(p.wgs), dim3(64 * SUF_NW), SUF_LDS_BYTES, stream, (const bf16_t*)q, (const bf16_t*)k,
+                     (const bf16_t*)v, (bf16_t*)o, H, S_kv, R, ld, batch_stride, ld_o, scale, p.splits, (float*)ws, nrows * p.splits);
+  hipLaunchKernelGGL(attn_split_combine_kernel, dim3(p.cwgs), dim3(64 * SP_CW), 0, stream, (const float*)ws, (bf16_t*)o, H, R, ld_o, p.splits, nrows);
   MLA_LAUNCH_CHECK();
 }
-
-// the head forms a single split resolves to (infer.hip)
-extern "C" int mla_attn_chunk_groups(const void* q, const void* k, const void* v, void* o, int G, int H, int head_dim, int S_p, int R, long long ld,
-                                     long long ld_o, float scale, hipStream_t stream);
-extern "C" int mla_attn_chunk_ragged_groups(const void* q, const void* k, const void* v, void* o, int B, int G, int H, int head_dim,
-                                            const int* prefix_len, int S_cap, int R, long long ld, long long batch_stride, long long ld_o,
-                                            float scale, hipStream_t stream);
 
 // mla_attn_chunk_groups' (prefix_len == nullptr: B == 1, S_p_or_cap = S_p) or mla_attn_chunk_ragged_groups' contract with the split of
 // mla_attn_chunk_split per (sample, group). Plan and workspace are mla_attn_chunk_split's at (B G, H, R, S_max), S_max the most logical keys
@@ -209,7 +180,7 @@ extern "C" int mla_attn_groups_split(const void* q, const void* k, const void* v
   const bool ragged = prefix_len != nullptr;
   MLA_CHECK_ARG(q && k && v && o, "mla_attn_groups_split: null pointer");
   MLA_CHECK_ARG(head_dim == 128, "mla_attn_groups_split: head_dim must be 128 (got %d)", head_dim);
-  MLA_CHECK_ARG(B >= 1 && G >= 1 && H >= 1 && R >= 1 && R <= SP_RMAX, "mla_attn_groups_split: B >= 1, G >= 1, 1 <= R <= 64 required (B %d, G %d, R %d)",
+  MLA_CHECK_ARG(B >= 1 && G >= 1 && H >= 1 && R >= 1 && R <= SUF_RMAX, "mla_attn_groups_split: B >= 1, G >= 1, 1 <= R <= 64 required (B %d, G %d, R %d)",
                 B, G, R);
   MLA_CHECK_ARG((long long)B * G * R <= 0x7fffffffLL, "mla_attn_groups_split: B * G * R output rows exceed the int range (B %d, G %d, R %d)", B, G, R);
   long long smax;
@@ -238,12 +209,11 @@ extern "C" int mla_attn_groups_split(const void* q, const void* k, const void* v
   MLA_CHECK_ARG(ws, "mla_attn_groups_split: splits %d needs a workspace (null)", p.splits);
   MLA_CHECK_ARG(AL16(ws) && (long long)ws_bytes >= p.ws_bytes, "mla_attn_groups_split: workspace of %lld bytes (16-B aligned) needed for splits %d, got %lld",
                 p.ws_bytes, p.splits, (long long)ws_bytes);
-  const size_t lds = (size_t)SP_NW * 128 * SP_VP * 2;
   const long long nrows = (long long)B * G * H * R;
-  (void)hipFuncSetAttribute((const void*)attn_groups_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(attn_groups_split_kernel, dim3(p.wgs), dim3(64 * SP_NW), lds, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, G, H,
-                     ragged ? 0 : S_p_or_cap, R, ld, ragged ? batch_stride : 0LL, scale, p.splits, (float*)ws, nrows * p.splits, prefix_len,
-                     ragged ? S_p_or_cap : 0);
+  (void)hipFuncSetAttribute((const void*)attn_groups_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SUF_LDS_BYTES);
+  hipLaunchKernelGGL(attn_groups_split_kernel, dim3(p.wgs), dim3(64 * SUF_NW), SUF_LDS_BYTES, stream, (const bf16_t*)q, (const bf16_t*)k,
+                     (const bf16_t*)v, G, H, ragged ? 0 : S_p_or_cap, R, ld, ragged ? batch_stride : 0LL, scale, p.splits, (float*)ws,
+                     nrows * p.splits, prefix_len, ragged ? S_p_or_cap : 0);
   hipLaunchKernelGGL(attn_split_combine_kernel, dim3(p.cwgs), dim3(64 * SP_CW), 0, stream, (const float*)ws, (bf16_t*)o, H, R, ld_o, p.splits, nrows);
   MLA_LAUNCH_CHECK();
 }

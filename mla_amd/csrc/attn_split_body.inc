@@ -1,23 +1,25 @@
-// The body of attn_chunk_split_kernel<FINISH> and attn_groups_split_kernel (attn_split.hip), included by both: one text, two kernels with
-// their own argument lists. The including kernel defines FINISH and GROUPS (constexpr bool), gr (SpGroups) and the names q, k, v, o, H,
-// S_kv (GROUPS: S_p on entry), R, ld, bs, ld_o, scale, splits, ws, nstates.
+// The body of attn_chunk_split_kernel and attn_groups_split_kernel (attn_split.hip), included by both: one text, two kernels with
+// their own argument lists. It stays a textual include: as a function called by the two kernels, or as one kernel template with the
+// union of the argument lists, the same text compiles to other code (profiles/suffix_attn_one_tile_step.txt). The including kernel
+// defines GROUPS (constexpr bool) and the names q, k, v, G, H, S_kv (GROUPS: S_p on entry), R, ld, bs, scale, splits, ws, nstates,
+// prefix_len, S_cap.
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int QB = (R + 15) >> 4;
-  const int s = FINISH ? 0 : (int)(blockIdx.x % splits);
-  const int wg = FINISH ? (int)blockIdx.x : (int)(blockIdx.x / splits);
-  const int qb = wg % QB, bh = wg / QB, h = bh % H, b = GROUPS ? bh / H / gr.G : bh / H;
+  const int s = (int)(blockIdx.x % splits);
+  const int wg = (int)(blockIdx.x / splits);
+  const int qb = wg % QB, bh = wg / QB, h = bh % H, b = GROUPS ? bh / H / G : bh / H;
   int S_p = 0;
   if (GROUPS) {
     S_p = S_kv;                                                         // arrives as S_p
-    if (gr.prefix_len) {
-      const int n = gr.prefix_len[b], room = gr.S_cap - gr.G * R;       // host: room >= 0
+    if (prefix_len) {
+      const int n = prefix_len[b], room = S_cap - G * R;                // host: room >= 0
       S_p = __builtin_amdgcn_readfirstlane(n < 0 ? 0 : (n > room ? room : n));
     }
     S_kv = S_p + R;
   }
-  const SpRows<GROUPS> row{S_p, GROUPS ? (bh / H % gr.G) * R : 0};
+  const SpRows<GROUPS> row{S_p, GROUPS ? (bh / H % G) * R : 0};
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
-  bf16_t* vt = (bf16_t*)smem + wave * 128 * SP_VP;                    // this wave's V tile, transposed: [128 channels][SP_VP keys]
+  bf16_t* vt = (bf16_t*)smem + wave * 128 * SUF_VP;                   // this wave's V tile, transposed: [128 channels][SUF_VP keys]
   const bf16_t* kb = k + b * bs + h * 128;
   const bf16_t* vb = v + b * bs + h * 128;
   const int r = qb * 16 + li;
@@ -38,13 +40,13 @@
   const int ntiles = (S_kv + 63) >> 6;
   const int tbase = ntiles / splits, trem = ntiles % splits;
   const int t0 = s * tbase + (s < trem ? s : trem), cnt = tbase + (s < trem ? 1 : 0);
-  const int iters = (cnt + SP_NW - 1) / SP_NW;
+  const int iters = (cnt + SUF_NW - 1) / SUF_NW;
   for (int it = 0; it < iters; ++it) {                                  // same trip count in every wave: the barriers below are uniform
-    const int tl = it * SP_NW + wave;                                   // tile of the range; behind it (FINISH: beyond S_kv): nothing visible
+    const int tl = it * SUF_NW + wave;                                  // tile of the range; behind it: nothing visible
     const bool live = tl < cnt;
     const int j0 = (t0 + tl) * 64;
     bf16x8_t pf0, pf1;
-    if (FINISH || live) {
+    if (live) {
       u32x4_t kf[4][4], vv[16];
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
@@ -100,15 +102,15 @@
       for (int u = 0; u < 16; ++u)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          vt[(li * 8 + 2 * e) * SP_VP + u * 4 + g] = (bf16_t)(vv[u][e] & 0xffffu);
-          vt[(li * 8 + 2 * e + 1) * SP_VP + u * 4 + g] = (bf16_t)(vv[u][e] >> 16);
+          vt[(li * 8 + 2 * e) * SUF_VP + u * 4 + g] = (bf16_t)(vv[u][e] & 0xffffu);
+          vt[(li * 8 + 2 * e + 1) * SUF_VP + u * 4 + g] = (bf16_t)(vv[u][e] >> 16);
         }
     }
     __syncthreads();
-    if (FINISH || live) {
+    if (live) {
 #pragma unroll
       for (int fd = 0; fd < 8; ++fd) {
-        const bf16_t* vr = vt + (fd * 16 + li) * SP_VP + g * 4;
+        const bf16_t* vr = vt + (fd * 16 + li) * SUF_VP + g * 4;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
           const u32x2_t lo = *(const u32x2_t*)(vr + ks * 32), hi = *(const u32x2_t*)(vr + ks * 32 + 16);
@@ -119,42 +121,38 @@
     }
     __syncthreads();
   }
-  // merge the waves' (max, sum, O^T) in wave order; O^T[d][query] of wave w: lane (d & 15) >> 2 ... as the MFMA left it. The split form
-  // pads the query pitch to 17 words: its read-out below walks d on the lanes (coalesced state rows)
-  constexpr int QP = FINISH ? 16 : 17;
-  float* mo = (float*)smem;                                             // [SP_NW][128][QP]
-  float* ml = mo + SP_NW * 128 * QP;                                    // [SP_NW][16] max, then [SP_NW][16] sum
+  // merge the waves' (max, sum, O^T) in wave order; O^T[d][query] of wave w: lane (d & 15) >> 2 ... as the MFMA left it. The query
+  // pitch is padded to 17 words: the read-out below walks d on the lanes (coalesced state rows)
+  constexpr int QP = 17;
+  float* mo = (float*)smem;                                             // [SUF_NW][128][QP]
+  float* ml = mo + SUF_NW * 128 * QP;                                   // [SUF_NW][16] max, then [SUF_NW][16] sum
 #pragma unroll
   for (int fd = 0; fd < 8; ++fd)
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) mo[(wave * 128 + fd * 16 + g * 4 + rr) * QP + li] = ot[fd][rr];
-  if (g == 0) { ml[wave * 16 + li] = m; ml[SP_NW * 16 + wave * 16 + li] = l; }
+  if (g == 0) { ml[wave * 16 + li] = m; ml[SUF_NW * 16 + wave * 16 + li] = l; }
   __syncthreads();
-  for (int e = threadIdx.x; e < 128 * 16; e += 64 * SP_NW) {
-    const int qq = FINISH ? (e & 15) : (e >> 7), d = FINISH ? (e >> 4) : (e & 127), rq = qb * 16 + qq;
+  for (int e = threadIdx.x; e < 128 * 16; e += 64 * SUF_NW) {
+    const int qq = e >> 7, d = e & 127, rq = qb * 16 + qq;
     if (rq >= R) continue;
     float mm = -INFINITY;
 #pragma unroll
-    for (int w = 0; w < SP_NW; ++w) mm = fmaxf(mm, ml[w * 16 + qq]);    // FINISH: finite -- wave 0's first tile holds key 0, seen by every query
-    if (!FINISH && mm == -INFINITY) mm = 0.f;                           // a range wholly behind the query's causal limit: every weight exp2(-inf) = 0
+    for (int w = 0; w < SUF_NW; ++w) mm = fmaxf(mm, ml[w * 16 + qq]);
+    if (mm == -INFINITY) mm = 0.f;                                      // a range wholly behind the query's causal limit: every weight exp2(-inf) = 0
     float L = 0.f, O = 0.f;
 #pragma unroll
-    for (int w = 0; w < SP_NW; ++w) {
+    for (int w = 0; w < SUF_NW; ++w) {
       const float fw = __builtin_amdgcn_exp2f(ml[w * 16 + qq] - mm);
-      L += fw * ml[SP_NW * 16 + w * 16 + qq];
+      L += fw * ml[SUF_NW * 16 + w * 16 + qq];
       O += fw * mo[(w * 128 + d) * QP + qq];
     }
-    if (FINISH) {
-      o[(long long)(b * R + rq) * ld_o + h * 128 + d] = sp_finish(O, L);
-    } else {
-      const long long st = ((long long)bh * R + rq) * splits + s;
-      ws[st * 128 + d] = O;                                             // the empty state: O = 0, l = 0, m = -inf
-      if (d == 0) {
-        float mw = -INFINITY;
+    const long long st = ((long long)bh * R + rq) * splits + s;
+    ws[st * 128 + d] = O;                                               // the empty state: O = 0, l = 0, m = -inf
+    if (d == 0) {
+      float mw = -INFINITY;
 #pragma unroll
-        for (int w = 0; w < SP_NW; ++w) mw = fmaxf(mw, ml[w * 16 + qq]);
-        ws[nstates * 128 + st * 2] = mw;
-        ws[nstates * 128 + st * 2 + 1] = L;
-      }
+      for (int w = 0; w < SUF_NW; ++w) mw = fmaxf(mw, ml[w * 16 + qq]);
+      ws[nstates * 128 + st * 2] = mw;
+      ws[nstates * 128 + st * 2 + 1] = L;
     }
   }

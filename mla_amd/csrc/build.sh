@@ -20,7 +20,7 @@ SRCS="api gemm gemm256 transpose elementwise attention loss pointcloud vision ge
 [ "$EXP" = 1 ] && SRCS="$SRCS gemm_asm"
 for f in $SRCS; do
   [ -f "$HERE/$f.hip" ] || continue
-  if [ ! -f "$BUILD/$f.o" ] || [ "$HERE/$f.hip" -nt "$BUILD/$f.o" ] || [ "$HERE/common.h" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm_args.h" -nt "$BUILD/$f.o" ] || { [ "$f" = gemm256 ] && { [ "$HERE/gemm256_kloop.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm256_kloop_half1.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm256_kloop_rm11.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm256_kloop_rm10.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm256_kloop_rm01.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm256_kloop_rm_clobbers.inc" -nt "$BUILD/$f.o" ] || [ ! -f "$BUILD/$f.s" ]; }; } || { [ "$f" = attention ] && { [ "$HERE/attn_fwd32p_tile0.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/attn_fwd32p_tile1.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/attn_fwd32p_tile0c.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/attn_fwd32p_tile1c.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/attn_fwd32p_clobbers.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/attention_exp.inc" -nt "$BUILD/$f.o" ] || [ ! -f "$BUILD/$f.s" ]; }; } || { [ "$f" = attn_split ] && [ "$HERE/attn_split_body.inc" -nt "$BUILD/$f.o" ]; } || { [ "$f" = gemm_asm ] && { [ "$HERE/gemm_asm_8w_loop.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm_asm_4w_loop.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm_asm_8w_clobbers.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm_asm_4w_clobbers.inc" -nt "$BUILD/$f.o" ]; }; }; then
+  if [ ! -f "$BUILD/$f.o" ] || [ "$HERE/$f.hip" -nt "$BUILD/$f.o" ] || [ "$HERE/common.h" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm_args.h" -nt "$BUILD/$f.o" ] || { [ "$f" = gemm256 ] && { [ "$HERE/gemm256_kloop.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm256_kloop_half1.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm256_kloop_rm11.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm256_kloop_rm10.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm256_kloop_rm01.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm256_kloop_rm_clobbers.inc" -nt "$BUILD/$f.o" ] || [ ! -f "$BUILD/$f.s" ]; }; } || { [ "$f" = attention ] && { [ "$HERE/attn_fwd32p_tile0.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/attn_fwd32p_tile1.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/attn_fwd32p_tile0c.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/attn_fwd32p_tile1c.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/attn_fwd32p_clobbers.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/attention_exp.inc" -nt "$BUILD/$f.o" ] || [ ! -f "$BUILD/$f.s" ]; }; } || { { [ "$f" = infer ] || [ "$f" = attn_split ]; } && [ "$HERE/attn_suffix_tile.h" -nt "$BUILD/$f.o" ]; } || { [ "$f" = attn_split ] && [ "$HERE/attn_split_body.inc" -nt "$BUILD/$f.o" ]; } || { [ "$f" = gemm_asm ] && { [ "$HERE/gemm_asm_8w_loop.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm_asm_4w_loop.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm_asm_8w_clobbers.inc" -nt "$BUILD/$f.o" ] || [ "$HERE/gemm_asm_4w_clobbers.inc" -nt "$BUILD/$f.o" ]; }; }; then
     XF=""; [ "$f" = api ] && XF="-DMLA_GEMM_SRC_ID=\"$GID\""
     $HIPCC $FLAGS $XF -c "$HERE/$f.hip" -o "$BUILD/$f.o" &
     pids+=($!)

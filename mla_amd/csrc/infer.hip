@@ -29,6 +29,7 @@
 // serve batched sampling (B observations with prompts of different lengths on one pass).
 // All are HBM-bound by construction: algorithmic bytes = the weight matrix (gemv) / the K and V rows of the head (decode).
 #include "common.h"
+#include "attn_suffix_tile.h"
 
 namespace {
 
@@ -417,7 +418,6 @@ __global__ __launch_bounds__(64 * DEC_NW) void attn_decode_kernel(const bf16_t* 
 // so that the epilogue holds both halves of every rotate-half pair.
 constexpr int SK_MMAX = 64;
 constexpr int SK_NW = 8;
-__device__ __forceinline__ bf16x8_t as_frag(const u32x4_t v) { return __builtin_bit_cast(bf16x8_t, v); }
 // W8 (e4m3fn weights, see gemv_kernel): a lane's 16-B load is 16 codes, k = 64 s + 16 (l >> 4) .. + 15 of a 64-wide step, decoded to bf16 into
 // the A fragments of TWO MFMAs (codes 0-7, then 8-15); the B fragments are the x elements of the same k, so the k order inside a step is a
 // permutation of the bf16 form's -- the sum is the same set of products. The conversions do not depend on M. K % 16 == 0: a lane's chunk is
@@ -797,26 +797,14 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* _
   }
 }
 
-// ---- suffix attention for 1 <= R <= 64 query rows: one workgroup per (sample, head, block of 16 queries), CH_NW waves taking the key
-// tiles of 64 in turn, each with its own online softmax (running max / sum per query, exp2 with the scale folded in); the waves' states
-// are merged in a fixed order at the end, so LDS does not grow with S_kv. The forward flash kernel's fragment layout: S^T = K Q^T (K rows
-// straight from global memory into the A fragments, Q in registers as the B fragments), P^T packed from the score registers as they are
-// (key order of pack_frag), O^T = V^T P^T with V^T read from a per-wave LDS transpose of the 64-row V tile. Every lane owns one query
-// (l & 15): the softmax needs two cross-lane steps per tile.
-constexpr int CH_RMAX = 64;
-constexpr int CH_NW = 4;
-constexpr int CH_VP = 68;                                              // V^T row pitch in keys (136 B: 8-B aligned, staggered banks)
-__device__ __forceinline__ bf16x8_t pack_pfrag(const f32x4_t lo, const f32x4_t hi) {
-  u32x4_t u;
-  u[0] = pack2bf(lo[0], lo[1]); u[1] = pack2bf(lo[2], lo[3]);
-  u[2] = pack2bf(hi[0], hi[1]); u[3] = pack2bf(hi[2], hi[3]);
-  return as_frag(u);
-}
+// ---- suffix attention for 1 <= R <= 64 query rows: one workgroup per (sample, head, block of 16 queries), SUF_NW waves taking the key
+// tiles of 64 in turn: tile t on wave t % 4 in iteration t / 4. The tile step, the fragment layout and the fixed-order merge of the
+// waves' states are attn_suffix_tile.h's.
 // RAGGED (mla_attn_chunk_ragged): the sample's key count comes from kv_len[b] on the device (clamped to [R, S_cap], the rows the caller owns)
 // instead of the launch argument; everything behind that line is the same code, so a sample's output is the B = 1 launch's bit for bit
 // (the waves' tile assignment starts at key 0 either way), and a captured graph serves any mix of lengths.
 template <bool RAGGED>
-__global__ __launch_bounds__(64 * CH_NW) void attn_chunk_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+__global__ __launch_bounds__(64 * SUF_NW) void attn_chunk_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                                 bf16_t* __restrict__ o, int H, int S_kv, int R, long long ld, long long bs,
                                                                 long long ld_o, float scale, const int* __restrict__ kv_len) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -827,7 +815,7 @@ __global__ __launch_bounds__(64 * CH_NW) void attn_chunk_kernel(const bf16_t* __
     S_kv = n < R ? R : (n > S_kv ? S_kv : n);                            // S_kv arrives as the capacity S_cap
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
-  bf16_t* vt = (bf16_t*)smem + wave * 128 * CH_VP;                    // this wave's V tile, transposed: [128 channels][CH_VP keys]
+  bf16_t* vt = (bf16_t*)smem + wave * 128 * SUF_VP;                   // this wave's V tile, transposed
   const bf16_t* kb = k + b * bs + h * 128;
   const bf16_t* vb = v + b * bs + h * 128;
   const int r = qb * 16 + li;
@@ -845,9 +833,9 @@ __global__ __launch_bounds__(64 * CH_NW) void attn_chunk_kernel(const bf16_t* __
 #pragma unroll
   for (int i = 0; i < 8; ++i) ot[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, l = 0.f;
-  const int ntiles = (S_kv + 63) >> 6, iters = (ntiles + CH_NW - 1) / CH_NW;
+  const int ntiles = (S_kv + 63) >> 6, iters = (ntiles + SUF_NW - 1) / SUF_NW;
   for (int it = 0; it < iters; ++it) {                                  // same trip count in every wave: the barriers below are uniform
-    const int j0 = (it * CH_NW + wave) * 64;                            // beyond S_kv: clamped loads, every score masked
+    const int j0 = (it * SUF_NW + wave) * 64;                           // beyond S_kv: clamped loads, every score masked
     u32x4_t kf[4][4], vv[16];
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
@@ -902,13 +890,13 @@ __global__ __launch_bounds__(64 * CH_NW) void attn_chunk_kernel(const bf16_t* __
     for (int u = 0; u < 16; ++u)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        vt[(li * 8 + 2 * e) * CH_VP + u * 4 + g] = (bf16_t)(vv[u][e] & 0xffffu);
-        vt[(li * 8 + 2 * e + 1) * CH_VP + u * 4 + g] = (bf16_t)(vv[u][e] >> 16);
+        vt[(li * 8 + 2 * e) * SUF_VP + u * 4 + g] = (bf16_t)(vv[u][e] & 0xffffu);
+        vt[(li * 8 + 2 * e + 1) * SUF_VP + u * 4 + g] = (bf16_t)(vv[u][e] >> 16);
       }
     __syncthreads();
 #pragma unroll
     for (int fd = 0; fd < 8; ++fd) {
-      const bf16_t* vr = vt + (fd * 16 + li) * CH_VP + g * 4;
+      const bf16_t* vr = vt + (fd * 16 + li) * SUF_VP + g * 4;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         const u32x2_t lo = *(const u32x2_t*)(vr + ks * 32), hi = *(const u32x2_t*)(vr + ks * 32 + 16);
@@ -918,26 +906,25 @@ __global__ __launch_bounds__(64 * CH_NW) void attn_chunk_kernel(const bf16_t* __
     }
     __syncthreads();
   }
-  // merge the waves' (max, sum, O^T) in wave order; O^T[d][query] of wave w: lane (d & 15) >> 2 ... as the MFMA left it
-  float* mo = (float*)smem;                                             // [CH_NW][128][16]
-  float* ml = mo + CH_NW * 128 * 16;                                    // [CH_NW][16] max, then [CH_NW][16] sum
+  float* mo = (float*)smem;                                             // [SUF_NW][128][16]
+  float* ml = mo + SUF_NW * 128 * 16;                                   // [SUF_NW][16] max, then [SUF_NW][16] sum
 #pragma unroll
   for (int fd = 0; fd < 8; ++fd)
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) mo[(wave * 128 + fd * 16 + g * 4 + rr) * 16 + li] = ot[fd][rr];
-  if (g == 0) { ml[wave * 16 + li] = m; ml[CH_NW * 16 + wave * 16 + li] = l; }
+  if (g == 0) { ml[wave * 16 + li] = m; ml[SUF_NW * 16 + wave * 16 + li] = l; }
   __syncthreads();
-  for (int e = threadIdx.x; e < 128 * 16; e += 64 * CH_NW) {
+  for (int e = threadIdx.x; e < 128 * 16; e += 64 * SUF_NW) {
     const int qq = e & 15, d = e >> 4, rq = qb * 16 + qq;
     if (rq >= R) continue;
     float mm = -INFINITY;
 #pragma unroll
-    for (int w = 0; w < CH_NW; ++w) mm = fmaxf(mm, ml[w * 16 + qq]);    // finite: wave 0's first tile holds key 0, seen by every query
+    for (int w = 0; w < SUF_NW; ++w) mm = fmaxf(mm, ml[w * 16 + qq]);    // finite: wave 0's first tile holds key 0, seen by every query
     float L = 0.f, O = 0.f;
 #pragma unroll
-    for (int w = 0; w < CH_NW; ++w) {
+    for (int w = 0; w < SUF_NW; ++w) {
       const float fw = __builtin_amdgcn_exp2f(ml[w * 16 + qq] - mm);
-      L += fw * ml[CH_NW * 16 + w * 16 + qq];
+      L += fw * ml[SUF_NW * 16 + w * 16 + qq];
       O += fw * mo[(w * 128 + d) * 16 + qq];
     }
     o[(long long)(b * R + rq) * ld_o + h * 128 + d] = f2bf(O / L);
@@ -961,7 +948,7 @@ constexpr int ATTN_GROUPS_XCD_CHUNKS = 0;                              // its wo
 // wave (readfirstlane keeps it in a scalar register). Everything behind that line is the same code: sample b's rows are bit for bit the
 // plain launch on its slice with S_p = S_p[b], the grid does not depend on the lengths and a captured graph serves any mix of them.
 template <int GW, bool RAGGED>
-__global__ __launch_bounds__(64 * CH_NW) void attn_chunk_groups_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+__global__ __launch_bounds__(64 * SUF_NW) void attn_chunk_groups_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                                        const bf16_t* __restrict__ v, bf16_t* __restrict__ o, int G, int H,
                                                                        int S_p, int R, long long ld, long long ld_o, float scale, int xcd_chunks,
                                                                        const int* __restrict__ prefix_len, int S_cap, long long bs) {
@@ -980,7 +967,7 @@ __global__ __launch_bounds__(64 * CH_NW) void attn_chunk_groups_kernel(const bf1
   }
   const int S_kv = S_p + R;                                             // logical keys of a group
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
-  bf16_t* vt = (bf16_t*)smem + wave * 128 * CH_VP;
+  bf16_t* vt = (bf16_t*)smem + wave * 128 * SUF_VP;
   const bf16_t* kb = k + h * 128;
   const bf16_t* vb = v + h * 128;
   const int r = qb * 16 + li;
@@ -1007,9 +994,9 @@ __global__ __launch_bounds__(64 * CH_NW) void attn_chunk_groups_kernel(const bf1
     m[gi] = -INFINITY;
     l[gi] = 0.f;
   }
-  const int ntiles = (S_kv + 63) >> 6, iters = (ntiles + CH_NW - 1) / CH_NW;
+  const int ntiles = (S_kv + 63) >> 6, iters = (ntiles + SUF_NW - 1) / SUF_NW;
   for (int it = 0; it < iters; ++it) {                                  // same trip count and barrier count in every wave
-    const int j0 = (it * CH_NW + wave) * 64;
+    const int j0 = (it * SUF_NW + wave) * 64;
     const bool shared = j0 + 64 <= S_p;                                 // wave-uniform: the tile holds prefix rows only
     u32x4_t kf[4][4];
 #pragma unroll
@@ -1070,14 +1057,14 @@ __global__ __launch_bounds__(64 * CH_NW) void attn_chunk_groups_kernel(const bf1
         for (int u = 0; u < 16; ++u)
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            vt[(li * 8 + 2 * e) * CH_VP + u * 4 + g] = (bf16_t)(vv[u][e] & 0xffffu);
-            vt[(li * 8 + 2 * e + 1) * CH_VP + u * 4 + g] = (bf16_t)(vv[u][e] >> 16);
+            vt[(li * 8 + 2 * e) * SUF_VP + u * 4 + g] = (bf16_t)(vv[u][e] & 0xffffu);
+            vt[(li * 8 + 2 * e + 1) * SUF_VP + u * 4 + g] = (bf16_t)(vv[u][e] >> 16);
           }
       }
       __syncthreads();
 #pragma unroll
       for (int fd = 0; fd < 8; ++fd) {
-        const bf16_t* vr = vt + (fd * 16 + li) * CH_VP + g * 4;
+        const bf16_t* vr = vt + (fd * 16 + li) * SUF_VP + g * 4;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
           const u32x2_t lo = *(const u32x2_t*)(vr + ks * 32), hi = *(const u32x2_t*)(vr + ks * 32 + 16);
@@ -1089,8 +1076,8 @@ __global__ __launch_bounds__(64 * CH_NW) void attn_chunk_groups_kernel(const bf1
     }
   }
   // attn_chunk_kernel's merge, one group after the other through the same buffers
-  float* mo = (float*)smem;                                             // [CH_NW][128][16]
-  float* ml = mo + CH_NW * 128 * 16;                                    // [CH_NW][16] max, then [CH_NW][16] sum
+  float* mo = (float*)smem;                                             // [SUF_NW][128][16]
+  float* ml = mo + SUF_NW * 128 * 16;                                   // [SUF_NW][16] max, then [SUF_NW][16] sum
 #pragma unroll
   for (int gi = 0; gi < GW; ++gi) {
     const int gg = gb * GW + gi;
@@ -1098,19 +1085,19 @@ __global__ __launch_bounds__(64 * CH_NW) void attn_chunk_groups_kernel(const bf1
     for (int fd = 0; fd < 8; ++fd)
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) mo[(wave * 128 + fd * 16 + g * 4 + rr) * 16 + li] = ot[gi][fd][rr];
-    if (g == 0) { ml[wave * 16 + li] = m[gi]; ml[CH_NW * 16 + wave * 16 + li] = l[gi]; }
+    if (g == 0) { ml[wave * 16 + li] = m[gi]; ml[SUF_NW * 16 + wave * 16 + li] = l[gi]; }
     __syncthreads();
-    for (int e = threadIdx.x; e < 128 * 16; e += 64 * CH_NW) {
+    for (int e = threadIdx.x; e < 128 * 16; e += 64 * SUF_NW) {
       const int qq = e & 15, d = e >> 4, rq = qb * 16 + qq;
       if (rq >= R || gg >= G) continue;
       float mm = -INFINITY;
 #pragma unroll
-      for (int w = 0; w < CH_NW; ++w) mm = fmaxf(mm, ml[w * 16 + qq]);
+      for (int w = 0; w < SUF_NW; ++w) mm = fmaxf(mm, ml[w * 16 + qq]);
       float L = 0.f, O = 0.f;
 #pragma unroll
-      for (int w = 0; w < CH_NW; ++w) {
+      for (int w = 0; w < SUF_NW; ++w) {
         const float fw = __builtin_amdgcn_exp2f(ml[w * 16 + qq] - mm);
-        L += fw * ml[CH_NW * 16 + w * 16 + qq];
+        L += fw * ml[SUF_NW * 16 + w * 16 + qq];
         O += fw * mo[(w * 128 + d) * 16 + qq];
       }
       o[(long long)((b * G + gg) * R + rq) * ld_o + h * 128 + d] = f2bf(O / L);
@@ -1303,12 +1290,12 @@ extern "C" int mla_attn_chunk(const void* q, const void* k, const void* v, void*
                               long long batch_stride, long long ld_o, float scale, hipStream_t stream) {
   MLA_CHECK_ARG(q && k && v && o, "mla_attn_chunk: null pointer");
   MLA_CHECK_ARG(head_dim == 128, "mla_attn_chunk: head_dim must be 128 (got %d)", head_dim);
-  MLA_CHECK_ARG(B >= 1 && H >= 1 && R >= 1 && R <= CH_RMAX && S_kv >= R, "mla_attn_chunk: 1 <= R <= 64, R <= S_kv required (R %d, S_kv %d)", R, S_kv);
+  MLA_CHECK_ARG(B >= 1 && H >= 1 && R >= 1 && R <= SUF_RMAX && S_kv >= R, "mla_attn_chunk: 1 <= R <= 64, R <= S_kv required (R %d, S_kv %d)", R, S_kv);
   MLA_CHECK_ARG(AL16(q) && AL16(k) && AL16(v) && ld % 8 == 0 && batch_stride % 8 == 0 && ld_o % 2 == 0, "mla_attn_chunk: 16-B aligned rows required");
-  const size_t lds = (size_t)CH_NW * 128 * CH_VP * 2;                  // >= the merge buffers ((CH_NW * 128 * 16 + 2 * CH_NW * 16) * 4)
+  const size_t lds = SUF_LDS_BYTES;
   static bool attr = false;
   if (!attr) { (void)hipFuncSetAttribute((const void*)attn_chunk_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-  hipLaunchKernelGGL(attn_chunk_kernel<false>, dim3(B * H * ((R + 15) / 16)), dim3(64 * CH_NW), lds, stream, (const bf16_t*)q, (const bf16_t*)k,
+  hipLaunchKernelGGL(attn_chunk_kernel<false>, dim3(B * H * ((R + 15) / 16)), dim3(64 * SUF_NW), lds, stream, (const bf16_t*)q, (const bf16_t*)k,
                      (const bf16_t*)v, (bf16_t*)o, H, S_kv, R, ld, batch_stride, ld_o, scale, (const int*)nullptr);
   MLA_LAUNCH_CHECK();
 }
@@ -1317,12 +1304,12 @@ extern "C" int mla_attn_chunk_ragged(const void* q, const void* k, const void* v
                                      int R, long long ld, long long batch_stride, long long ld_o, float scale, hipStream_t stream) {
   MLA_CHECK_ARG(q && k && v && o && kv_len, "mla_attn_chunk_ragged: null pointer");
   MLA_CHECK_ARG(head_dim == 128, "mla_attn_chunk_ragged: head_dim must be 128 (got %d)", head_dim);
-  MLA_CHECK_ARG(B >= 1 && H >= 1 && R >= 1 && R <= CH_RMAX && S_cap >= R, "mla_attn_chunk_ragged: 1 <= R <= 64, R <= S_cap required (R %d, S_cap %d)", R, S_cap);
+  MLA_CHECK_ARG(B >= 1 && H >= 1 && R >= 1 && R <= SUF_RMAX && S_cap >= R, "mla_attn_chunk_ragged: 1 <= R <= 64, R <= S_cap required (R %d, S_cap %d)", R, S_cap);
   MLA_CHECK_ARG(AL16(q) && AL16(k) && AL16(v) && ld % 8 == 0 && batch_stride % 8 == 0 && ld_o % 2 == 0, "mla_attn_chunk_ragged: 16-B aligned rows required");
-  const size_t lds = (size_t)CH_NW * 128 * CH_VP * 2;
+  const size_t lds = SUF_LDS_BYTES;
   static bool attr = false;
   if (!attr) { (void)hipFuncSetAttribute((const void*)attn_chunk_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-  hipLaunchKernelGGL(attn_chunk_kernel<true>, dim3(B * H * ((R + 15) / 16)), dim3(64 * CH_NW), lds, stream, (const bf16_t*)q, (const bf16_t*)k,
+  hipLaunchKernelGGL(attn_chunk_kernel<true>, dim3(B * H * ((R + 15) / 16)), dim3(64 * SUF_NW), lds, stream, (const bf16_t*)q, (const bf16_t*)k,
                      (const bf16_t*)v, (bf16_t*)o, H, S_cap, R, ld, batch_stride, ld_o, scale, kv_len);
   MLA_LAUNCH_CHECK();
 }
@@ -1335,7 +1322,7 @@ static int attn_groups_entry(const char* name, const void* q, const void* k, con
   const bool ragged = prefix_len != nullptr;
   MLA_CHECK_ARG(q && k && v && o, "%s: null pointer", name);
   MLA_CHECK_ARG(head_dim == 128, "%s: head_dim must be 128 (got %d)", name, head_dim);
-  MLA_CHECK_ARG(B >= 1 && G >= 1 && H >= 1 && R >= 1 && R <= CH_RMAX, "%s: B >= 1, G >= 1, 1 <= R <= 64 required (B %d, G %d, R %d)", name, B, G, R);
+  MLA_CHECK_ARG(B >= 1 && G >= 1 && H >= 1 && R >= 1 && R <= SUF_RMAX, "%s: B >= 1, G >= 1, 1 <= R <= 64 required (B %d, G %d, R %d)", name, B, G, R);
   if (ragged) {
     MLA_CHECK_ARG((long long)G * R <= (long long)S_p_or_cap, "%s: S_cap (%d) must hold the G * R suffix rows of a sample (G %d, R %d)", name,
                   S_p_or_cap, G, R);
@@ -1349,7 +1336,7 @@ static int attn_groups_entry(const char* name, const void* q, const void* k, con
   MLA_CHECK_ARG(order >= -1 && order <= 1, "%s: order must be -1 (default), 0 (as dispatched) or 1 (one chunk of the grid per XCD) (got %d)", name, order);
   if (gw == 0) gw = ATTN_GROUPS_GW;
   if (order < 0) order = ATTN_GROUPS_XCD_CHUNKS;
-  const size_t lds = (size_t)CH_NW * 128 * CH_VP * 2;                  // >= the merge buffers, as in mla_attn_chunk
+  const size_t lds = SUF_LDS_BYTES;
   const int QB = (R + 15) / 16;
   const long long grid = (long long)B * H * ((G + gw - 1) / gw) * QB;
   MLA_CHECK_ARG(grid <= 0x7fffffffLL, "%s: %lld workgroups exceed the grid range", name, grid);
@@ -1358,7 +1345,7 @@ static int attn_groups_entry(const char* name, const void* q, const void* k, con
   {                                                                                                                                    \
     static bool attr = false;                                                                                                          \
     if (!attr) { (void)hipFuncSetAttribute((const void*)attn_chunk_groups_kernel<GW, RG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; } \
-    hipLaunchKernelGGL((attn_chunk_groups_kernel<GW, RG>), dim3((unsigned)grid), dim3(64 * CH_NW), lds, stream, (const bf16_t*)q,       \
+    hipLaunchKernelGGL((attn_chunk_groups_kernel<GW, RG>), dim3((unsigned)grid), dim3(64 * SUF_NW), lds, stream, (const bf16_t*)q,       \
                        (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, G, H, RG ? 0 : S_p_or_cap, R, ld, ld_o, scale, xcd_chunks,         \
                        prefix_len, RG ? S_p_or_cap : 0, RG ? bs : 0LL);                                                                 \
   }

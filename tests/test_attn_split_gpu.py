@@ -39,7 +39,7 @@ def test_one_split_is_attn_chunk_bit_for_bit(dev, R, S_kv):
     for B, H in ((1, 2), (2, 2)):
         cache = _cache(dev, B, H, S_kv, R)
         want = hip.attn_chunk(cache, B, H, 128, S_kv, R, SCALE)
-        got = hip.attn_chunk_split(cache, B, H, 128, S_kv, R, SCALE, splits=1)       # ws=None: the finishing form touches no workspace
+        got = hip.attn_chunk_split(cache, B, H, 128, S_kv, R, SCALE, splits=1)       # ws=None: one split is attn_chunk's own launch, no workspace
         assert torch.equal(got, want), (B, H, float((got.float() - want.float()).abs().max()))
 
 
