@@ -323,6 +323,18 @@ int mla_gemv_w8(const void* x, long long ldx, const void* W, long long ldw, cons
 int mla_gemm_skinny_w8(const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
                        long long out_batch_stride, int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre,
                        const void* pre_w, float eps, const float* rope_cos, const float* rope_sin, int rope_cols, mla_stream_t stream);
+/* mla_gemm_skinny_gateup_swiglu_bf16 / _w8: the gate|up projection of 1 <= M <= 64 rows with SwiGLU in the epilogue (opt-in:
+ *   MLA.predict_action_diff(suffix_operand="once")). x [M, K] bf16 (ldx); W [2 I, K] the packed gate|up matrix, gate rows [0, I), up rows
+ *   [I, 2 I), bf16 or e4m3fn bytes with w_scale [2 I]; out [M, I] bf16 (ldo >= I):
+ *     out[m, n] = bf16(silu(g) * u),  g = bf16(x[m] . W[n]),  u = bf16(x[m] . W[I + n])   (W8: each fp32 sum times its own row's scale first)
+ *   Workgroup t holds gate rows 8 t .. 8 t + 7 and up rows I + 8 t .. I + 8 t + 7 as one 16-row tile; K split, MFMA order and the
+ *   fixed-order sum of the 8 wave partials are mla_gemm_skinny_*'s, so the result is bit for bit mla_swiglu_fwd of the plain form's
+ *   [M, 2 I] output, which never reaches memory. No residual, no rotary epilogue, no pre-transform; no atomics, no workspace,
+ *   graph-capturable. I % 8 == 0, K % 8 == 0 (bf16) / K % 16 == 0 (w8), 16-B aligned rows; otherwise -1 and nothing is launched. */
+int mla_gemm_skinny_gateup_swiglu_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, int M, int I,
+                                       int K, mla_stream_t stream);
+int mla_gemm_skinny_gateup_swiglu_w8(const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out,
+                                     long long ldo, int M, int I, int K, mla_stream_t stream);
 /* mla_attn_chunk: mla_attn_decode's contract for 1 <= R <= 64 query rows and any S_kv >= R: online softmax over key tiles of 64 (LDS does
  *   not grow with S_kv), QK^T and PV on the MFMA pipe, P rounded to bf16 before P V like the flash kernel; the key tiles are shared out
  *   over 4 waves per (sample, head, 16 queries) and their softmax states merged in a fixed order (deterministic, graph-capturable). */

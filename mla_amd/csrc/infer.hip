@@ -25,6 +25,9 @@
 //   mla_attn_chunk_ragged_groups  mla_attn_chunk_groups for B samples, each with its own prefix length read from a device array;
 //                      mla_gemm_suffix_bf16_pos / _w8_pos write its rows: the cache row and the rotary position come from two arrays
 //                      (N action chunks for each of B observations, BatchedSampleGroupsEps).
+//   mla_gemm_skinny_gateup_swiglu_bf16 / _w8  the skinny kernel on the packed gate|up matrix with SwiGLU in the epilogue: a workgroup's
+//                      tile is 8 gate rows and their 8 up rows, out [M, I] = silu(gate) * up; bit for bit mla_swiglu_fwd of the plain
+//                      form's [M, 2 I] rows, which never reach memory (suffix_operand="once").
 // infer.py keeps gemv / decode for every shape they accept and uses the other two beyond (action chunks of 8..63 steps); the last two
 // serve batched sampling (B observations with prompts of different lengths on one pass).
 // All are HBM-bound by construction: algorithmic bytes = the weight matrix (gemv) / the K and V rows of the head (decode).
@@ -422,7 +425,13 @@ constexpr int SK_NW = 8;
 // the A fragments of TWO MFMAs (codes 0-7, then 8-15); the B fragments are the x elements of the same k, so the k order inside a step is a
 // permutation of the bf16 form's -- the sum is the same set of products. The conversions do not depend on M. K % 16 == 0: a lane's chunk is
 // inside K or beyond it as a whole.
-template <int MB, int PRE, bool W8>
+// GU (mla_gemm_skinny_gateup_swiglu_*; PRE 0, no residual, no rotary columns): W is the packed gate|up matrix [2 N, K] and workgroup t
+// owns gate rows 8 t .. 8 t + 7 and up rows N + 8 t .. N + 8 t + 7 as the 16 rows of its A fragment -- the rotary columns' device of
+// holding both halves of a pair in one tile. The K loop is the same code; the epilogue sums both halves in the same wave order, rounds
+// each to bf16 (what the plain form would store), applies swiglu_fwd_elem and stores out [M, N]: a weight row's sum depends only on
+// the row, the K split and the order, so the result is swiglu_fwd of the plain form's output bit for bit, and the packed rows never
+// reach memory.
+template <int MB, int PRE, bool W8, bool GU = false>
 __global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* __restrict__ x, long long ldx, const typename welem<W8>::t* __restrict__ W,
                                                                  long long ldw, const float* __restrict__ w_scale, bf16_t* __restrict__ out,
                                                                  long long ldo, long long out_bs, int rpb,
@@ -474,9 +483,11 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* _
     }
   }
   const int tile = blockIdx.x;
-  const bool rot = rope_cos != nullptr && tile * 16 < rope_cols;
-  const int nrow = rot ? (tile >> 3) * 128 + ((li & 8) ? 64 : 0) + (tile & 7) * 8 + (li & 7) : tile * 16 + li;
-  const typename welem<W8>::t* wr = W + (long long)(nrow < N ? nrow : N - 1) * ldw;
+  const bool rot = !GU && rope_cos != nullptr && tile * 16 < rope_cols;
+  const int nrows = GU ? 2 * N : N;                                  // rows of W
+  const int nrow = GU ? ((li & 8) ? N : 0) + tile * 8 + (li & 7)
+                      : (rot ? (tile >> 3) * 128 + ((li & 8) ? 64 : 0) + (tile & 7) * 8 + (li & 7) : tile * 16 + li);
+  const typename welem<W8>::t* wr = W + (long long)(nrow < nrows ? nrow : nrows - 1) * ldw;
   const bf16_t* xr[MB];
   bool xok[MB];
   float xrs[MB];
@@ -601,6 +612,25 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* _
 #pragma unroll
     for (int r = 0; r < 4; ++r) lds[((wave * MB + mb) * 4 + r) * 64 + lane] = acc[mb][r];
   __syncthreads();
+  if constexpr (GU) {
+    // tile row i = gate column n, tile row i + 8 = its up column; n fastest, so 8 threads store 16 contiguous bytes of a row
+    for (int e = threadIdx.x; e < 8 * MB * 16; e += 64 * SK_NW) {
+      const int i = e & 7, m = e >> 3, n = tile * 8 + i;
+      if (m >= M || n >= N) continue;
+      const int mb = m >> 4, col = m & 15, iu = i + 8;
+      float gs = 0.f, us = 0.f;
+#pragma unroll
+      for (int w = 0; w < SK_NW; ++w) gs += lds[((w * MB + mb) * 4 + (i & 3)) * 64 + (i >> 2) * 16 + col];
+#pragma unroll
+      for (int w = 0; w < SK_NW; ++w) us += lds[((w * MB + mb) * 4 + (iu & 3)) * 64 + (iu >> 2) * 16 + col];
+      if constexpr (W8) {
+        gs = __fmul_rn(gs, w_scale[n]);
+        us = __fmul_rn(us, w_scale[N + n]);
+      }
+      out[(long long)m * ldo + n] = f2bf(swiglu_fwd_elem(bf2f(f2bf(gs)), bf2f(f2bf(us))));
+    }
+    return;
+  }
   for (int e = threadIdx.x; e < 16 * MB * 16; e += 64 * SK_NW) {
     const int m = e % (MB * 16), i = e / (MB * 16);
     const int n = rot ? (tile >> 3) * 128 + ((i & 8) ? 64 : 0) + (tile & 7) * 8 + (i & 7) : tile * 16 + i;
@@ -1275,6 +1305,37 @@ extern "C" int mla_gemm_skinny_w8(const void* x, long long ldx, const void* W, l
                                   hipStream_t stream) {
   return skinny_entry<true>("mla_gemm_skinny_w8", x, ldx, W, ldw, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual, ld_res, M, N, K,
                             pre, pre_w, eps, rope_cos, rope_sin, rope_cols, stream);
+}
+
+// mla_gemm_skinny_gateup_swiglu_bf16 / _w8: gemm_skinny_kernel's GU form (gate|up projection with the SwiGLU epilogue)
+template <bool W8>
+static int skinny_gateup_entry(const char* name, const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out,
+                               long long ldo, int M, int I, int K, hipStream_t stream) {
+  constexpr int KQ = W8 ? 16 : 8;
+  MLA_CHECK_ARG(x && W && out && (!W8 || w_scale), "%s: null pointer", name);
+  MLA_CHECK_ARG(M >= 1 && M <= SK_MMAX && I >= 8 && I % 8 == 0 && K >= KQ && K % KQ == 0,
+                "%s: 1 <= M <= 64, I %% 8 == 0, K %% %d == 0 required (M %d, I %d, K %d)", name, KQ, M, I, K);
+  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && ldw % KQ == 0 && ldx >= K && ldw >= K, "%s: x / W rows must be 16-B aligned and hold K elements", name);
+  MLA_CHECK_ARG(ldo >= I, "%s: ldo %lld < I %d", name, ldo, I);
+#define MLA_SKGU_CASE(MB)                                                                                                              \
+  case MB:                                                                                                                             \
+    hipLaunchKernelGGL((gemm_skinny_kernel<MB, 0, W8, true>), dim3(I / 8), dim3(64 * SK_NW), 0, stream, (const bf16_t*)x, ldx,          \
+                       (const typename welem<W8>::t*)W, ldw, w_scale, (bf16_t*)out, ldo, 0LL, M, (const bf16_t*)nullptr, 0LL, M, I, K,  \
+                       (const bf16_t*)nullptr, 0.f, (const float*)nullptr, (const float*)nullptr, 0);                                  \
+    break;
+  switch ((M + 15) / 16) { MLA_SKGU_CASE(1) MLA_SKGU_CASE(2) MLA_SKGU_CASE(3) MLA_SKGU_CASE(4) }
+#undef MLA_SKGU_CASE
+  return launch_status(name);
+}
+
+extern "C" int mla_gemm_skinny_gateup_swiglu_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, int M,
+                                                  int I, int K, hipStream_t stream) {
+  return skinny_gateup_entry<false>("mla_gemm_skinny_gateup_swiglu_bf16", x, ldx, W, ldw, nullptr, out, ldo, M, I, K, stream);
+}
+
+extern "C" int mla_gemm_skinny_gateup_swiglu_w8(const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out,
+                                                long long ldo, int M, int I, int K, hipStream_t stream) {
+  return skinny_gateup_entry<true>("mla_gemm_skinny_gateup_swiglu_w8", x, ldx, W, ldw, w_scale, out, ldo, M, I, K, stream);
 }
 
 // W [N, K] bf16 (ldw) -> q [N, K] e4m3fn codes (ldq, bytes) + scale [N] fp32; see quant_fp8_rows_kernel

@@ -42,6 +42,9 @@ _SIGNATURES = {
                     c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
     "mla_gemm_skinny_w8": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_longlong,
                            c_int, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
+    "mla_gemm_skinny_gateup_swiglu_bf16": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_int, c_int, c_void_p],
+    "mla_gemm_skinny_gateup_swiglu_w8": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int,
+                                         c_void_p],
     "mla_attn_chunk": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_float,
                        c_void_p],
     "mla_attn_chunk_ragged": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_longlong, c_longlong,
@@ -988,6 +991,41 @@ def gemm_skinny_w8(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, re
     operands."""
     _skinny_call("mla_gemm_skinny_w8", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope,
                  w_scale)
+
+
+def _skinny_gateup_call(name, x, W, out, ldo, w_scale=None):
+    """The shared call of the two gate|up + SwiGLU projections: _skinny_call's argument checks without a residual, a rotary epilogue or a
+    pre-transform; out [M, I] is allocated when not given (ldo: its row stride in elements, default out.stride(0))."""
+    _req(x, torch.bfloat16, f"{name} x")
+    _req(W, torch.bfloat16 if w_scale is None else torch.float8_e4m3fn, f"{name} W")
+    scale_arg = ()
+    if w_scale is not None:
+        _req(w_scale, torch.float32, f"{name} w_scale")
+        assert w_scale.numel() == W.shape[0] and w_scale.is_contiguous()
+        scale_arg = (_p(w_scale),)
+    M, K = x.shape
+    assert W.shape[0] % 2 == 0 and W.shape[1] == K and x.stride(1) == 1 and W.stride(1) == 1
+    I = W.shape[0] // 2
+    if out is None:
+        out = torch.empty((M, I), dtype=torch.bfloat16, device=x.device)
+    _req(out, torch.bfloat16, f"{name} out")
+    if ldo is None:
+        ldo = out.stride(0)
+    call(name, _p(x), x.stride(0), _p(W), W.stride(0), *scale_arg, _p(out), ldo, M, I, K)
+    return out
+
+
+def gemm_skinny_gateup_swiglu(x, W, out=None, ldo=None):
+    """silu(x @ Wg^T) * (x @ Wu^T) for 1 <= M <= 64 rows, W = the packed gate|up matrix [2 I, K] (mla_gemm_skinny_gateup_swiglu_bf16):
+    gemm_skinny's plain form with SwiGLU in the epilogue -- bit for bit swiglu_fwd(gemm_skinny(x, W)), the [M, 2 I] rows never reach
+    memory. Returns out [M, I] bf16 (`out` may be given: a base tensor with row stride ldo >= I)."""
+    return _skinny_gateup_call("mla_gemm_skinny_gateup_swiglu_bf16", x, W, out, ldo)
+
+
+def gemm_skinny_gateup_swiglu_w8(x, W, w_scale, out=None, ldo=None):
+    """gemm_skinny_gateup_swiglu over FP8 weights (mla_gemm_skinny_gateup_swiglu_w8): W [2 I, K] float8_e4m3fn, w_scale [2 I] fp32; each
+    finished fp32 sum times its own row's scale in front of the bf16 rounding, as gemm_skinny_w8 does. K % 16 == 0."""
+    return _skinny_gateup_call("mla_gemm_skinny_gateup_swiglu_w8", x, W, out, ldo, w_scale)
 
 
 def attn_decode(cache, B, nheads, D, S_kv, R, scale):

@@ -32,6 +32,10 @@ second launch -- for every R; the same function up to summation order. The multi
 BatchedSampleGroupsEps) take the same argument from the public `groups_attention="split"` (GROUPS_ATTENTION_MODES) and launch
 `mla_attn_groups_split`: that split per (sample, group), the prefix lengths still read on the device.
 
+Opt-in (`suffix_operand="once"`, see SUFFIX_OPERAND_MODES; PrefixCachedEps only): a pass over more than 8 suffix rows forms each RMSNorm
+operand once with the stand-alone kernel, runs every projection on the plain `mla_gemm_skinny_*` form and takes SwiGLU into the gate|up
+projection's epilogue (`mla_gemm_skinny_gateup_swiglu_*`) -- seven launches per layer instead of five, the same bits.
+
 Opt-in (`prefill="compact"`, `prefill_precision="fp8"`, see PREFILL_MODES / PREFILL_PRECISION_MODES; PrefixCachedEps and SampleGroupsEps):
 the prefix rows of one observation run on the row-sized GEMMs of csrc/prefill.hip, and with "fp8" their four projections per layer on
 e4m3fn codes of weights AND activations (csrc/prefill.hip, the K = 128 FP8 MFMA) -- the same FP8 weight copy the suffix pass streams.
@@ -171,6 +175,32 @@ def suffix_attention_single_only(mode, route: str):
                                   "groups_attention=\"split\"; suffix_attention serves predict_action_diff (one observation, one chunk) only")
 
 
+# How a pass of PrefixCachedEps over MORE than 8 suffix rows forms the RMSNorm / SwiGLU operands of its projections
+# (MLA.predict_action_diff(suffix_operand=...)); up to 8 rows the GEMV stages its input once per workgroup and both values are one pass:
+#   "fused"  inside the projections' input staging (mla_gemm_skinny_* pre 1 / 2): five launches per layer, the operand re-formed by every
+#            workgroup (default)
+#   "once"   RMSNorm by the stand-alone kernel once per pass, every projection on the plain skinny form, SwiGLU in the gate|up
+#            projection's epilogue (mla_gemm_skinny_gateup_swiglu_*): seven launches per layer, the same bits
+SUFFIX_OPERAND_MODES = ("fused", "once")
+
+
+def check_suffix_operand(mode, reuse_prefix=True):
+    """The argument errors of suffix_operand=: an unknown value; "once" without the cached prefix. A shape the engine does not serve is
+    the caller's ValueError (suffix_operand_needs_engine)."""
+    if mode not in SUFFIX_OPERAND_MODES:
+        raise ValueError(f"suffix_operand must be one of {SUFFIX_OPERAND_MODES}, got {mode!r}")
+    if mode == "once" and not reuse_prefix:
+        raise ValueError("suffix_operand=\"once\" runs on the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has no "
+                         "suffix pass")
+
+
+def suffix_operand_needs_engine(mode, n_action_rows: int):
+    """suffix_operand="once" on a shape PrefixCachedEps does not serve: an error, never the warned loop of whole-forward calls."""
+    if mode == "once":
+        raise ValueError(f"suffix_operand=\"once\": the cached-prefix engine (PrefixCachedEps) does not serve {1 + n_action_rows} suffix "
+                         "rows per sample at this head_dim; use suffix_operand=\"fused\"")
+
+
 # Which attention launch the sampler steps of the multi-row engines use (MLA.predict_action_diff_batch / predict_action_diff_samples
 # (groups_attention=...); BatchedPrefixCachedEps, SampleGroupsEps, BatchedSampleGroupsEps):
 #   "head"   mla_attn_chunk_ragged / mla_attn_chunk_groups / mla_attn_chunk_ragged_groups: one workgroup per (sample, group, head, 16
@@ -283,12 +313,16 @@ class _CachedEpsBase:
     """What the cached-prefix engines share: the packed weights, the captured suffix pass and the `model(x, t)` call of the samplers.
     A subclass provides prefill() and _suffix_pass() and sets B, R, T, H, h_in, h_out, cache."""
 
+    suffix_operand = "fused"         # SUFFIX_OPERAND_MODES: read by PrefixCachedEps._suffix_pass; the row-GEMM engines form the operand once anyway
+
     def __init__(self, vlm, n_action_rows: int = 1, suffix_weights: str = "bf16", prefill: str = "train", suffix_attention: str = "head",
-                 prefill_precision: str = "bf16"):
+                 prefill_precision: str = "bf16", suffix_operand: str = "fused"):
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
         check_suffix_attention(suffix_attention)
         check_prefill_precision(prefill_precision, prefill)
+        check_suffix_operand(suffix_operand)
+        self.suffix_operand = suffix_operand
         self.suffix_weights = suffix_weights
         self.prefill_mode = prefill
         self.prefill_precision = prefill_precision
@@ -329,7 +363,7 @@ class _CachedEpsBase:
 
     @classmethod
     def _engine(cls, vlm, store: str, key: tuple, ctor: tuple, suffix_weights="bf16", prefill="train", suffix_attention="head",
-                prefill_precision="bf16", batch_prefill="train"):
+                prefill_precision="bf16", batch_prefill="train", suffix_operand="fused"):
         """The vlm's engine for `key` in vlm.__dict__[store], constructed as cls(vlm, *ctor) on first use; at most 4 per store, the oldest
         leaves first. A mode other than the default is part of the key -- the engines coexist: a captured graph holds the addresses of
         ITS weights and ITS attention launches. The caller prefills."""
@@ -344,6 +378,8 @@ class _CachedEpsBase:
             key += ("precision:" + prefill_precision,)
         if batch_prefill != "train":
             key += ("batch_prefill:" + batch_prefill,)
+        if suffix_operand != "fused":
+            key += ("operand:" + suffix_operand,)
         eng = engines.get(key)
         if eng is None:
             if len(engines) >= 4:
@@ -733,16 +769,17 @@ class PrefixCachedEps(_CachedEpsBase):
 
     @classmethod
     def for_inputs(cls, vlm, input_ids, n_action_rows: int = 1, suffix_weights: str = "bf16", prefill: str = "train",
-                   suffix_attention: str = "head", prefill_precision: str = "bf16", **model_kwargs):
+                   suffix_attention: str = "head", prefill_precision: str = "bf16", suffix_operand: str = "fused", **model_kwargs):
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
         check_suffix_attention(suffix_attention)
         check_prefill_precision(prefill_precision, prefill)
+        check_suffix_operand(suffix_operand)
         k = cls._splice_position(input_ids)
         # a handful of prompt lengths per process; each engine holds 0.4 GB at 7B
         eng = cls._engine(vlm, "_prefix_engines", (int(input_ids.shape[0]), k, int(n_action_rows), str(input_ids.device)),
-                          (n_action_rows, suffix_weights, prefill, suffix_attention, prefill_precision), suffix_weights, prefill,
-                          suffix_attention, prefill_precision)
+                          (n_action_rows, suffix_weights, prefill, suffix_attention, prefill_precision, suffix_operand), suffix_weights,
+                          prefill, suffix_attention, prefill_precision, suffix_operand=suffix_operand)
         eng.prefill(input_ids, k, **model_kwargs)
         return eng
 
@@ -813,10 +850,45 @@ class PrefixCachedEps(_CachedEpsBase):
                 off += w.shape[0]
         return out
 
+    def _gate_up_act(self, xn2, gu_w):
+        """silu(xn2 @ Wg^T) * (xn2 @ Wu^T) -> act [M, I] of the "once" pass: the gate|up projection with the SwiGLU epilogue where gate|up
+        is one matrix (a W8, or bf16 views adjacent in memory) -- the packed rows never reach memory --, otherwise one plain launch per
+        matrix into a gate|up buffer and the stand-alone swiglu_fwd. The same bits either way."""
+        if isinstance(gu_w, W8):
+            return hip.gemm_skinny_gateup_swiglu_w8(xn2, gu_w.q, gu_w.scale)
+        wcat = ops.cat_view(gu_w)
+        if wcat is not None:
+            return hip.gemm_skinny_gateup_swiglu(xn2, wcat)
+        return hip.swiglu_fwd(self._gemv(xn2, gu_w))
+
+    def _suffix_pass_once(self):
+        """suffix_operand "once" over more than 8 rows: seven launches per layer. Each RMSNorm operand is formed once per pass by the
+        stand-alone kernel (the values the fused form re-forms per workgroup), every projection runs on the plain skinny form, and SwiGLU
+        sits in the gate|up projection's epilogue: bit for bit the "fused" pass."""
+        B, R, H, S_p, S_cap = self.B, self.R, self.H, self.S_p, self.S_cap
+        h = self.h_in
+        scale = 1.0 / math.sqrt(self.D)
+        attn = self._suffix_attn()
+        for (ln1, qkv, wo, ln2, gu_w, wd), c in self._suffix_layers():
+            fused = self.D == 128 and (isinstance(qkv, W8) or ops.cat_view(qkv) is not None)      # the rotary epilogue, as in _suffix_pass
+            xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
+            self._gemv(xn, qkv, out=c[:, S_p:], rpb=R, out_bs=c.stride(0), **({"rope": (self.cos_s, self.sin_s, 2 * H)} if fused else {}))
+            if not fused:
+                for b in range(B):
+                    hip.rope_inplace(c[b, S_p:], self.cos_s, self.sin_s, R, self.nheads, self.D, 0, H)
+            o = attn(c, B, self.nheads, self.D, S_cap, R, scale)
+            h1 = self._gemv(o, wo, residual=h)
+            xn2, _ = hip.rmsnorm_fwd(h1, ln2, self.eps)
+            h = self._gemv(self._gate_up_act(xn2, gu_w), wd, residual=h1)
+        self._finish(h)
+
     def _suffix_pass(self):
         """Five launches per layer, whatever the suffix pass streams (bf16 views or the FP8 copy: activations / cache / attention are the
-        same)."""
+        same). suffix_operand "once" with more than 8 rows: _suffix_pass_once's seven; up to 8 rows the GEMV stages its input once per
+        workgroup already, and the pass is this one in both modes."""
         B, R, H, S_p, S_cap = self.B, self.R, self.H, self.S_p, self.S_cap
+        if self.suffix_operand == "once" and B * R > hip.GEMV_MMAX:
+            return self._suffix_pass_once()
         h = self.h_in
         scale = 1.0 / math.sqrt(self.D)
         attn = self._suffix_attn()                                             # "head": R x S_kv scores in LDS vs online softmax

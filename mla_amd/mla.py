@@ -330,9 +330,10 @@ class MLA(nn.Module):
     # ---- what the four sampling entry points share (called as MLA._check_modes: the mode errors come before `self` is touched)
     @staticmethod
     def _check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision="bf16",
-                     groups_attention="head", ddpm_sampler="host"):
+                     groups_attention="head", ddpm_sampler="host", suffix_operand="fused"):
         from .infer import (check_ddpm_sampler, check_groups_attention, check_prefill, check_prefill_precision, check_sampler,
-                            check_suffix_attention, check_suffix_weights)
+                            check_suffix_attention, check_suffix_operand, check_suffix_weights)
+        check_suffix_operand(suffix_operand, reuse_prefix)
         check_suffix_weights(suffix_weights)
         check_prefill(prefill)
         check_prefill_precision(prefill_precision, prefill)
@@ -404,7 +405,8 @@ class MLA(nn.Module):
                             action_dim: int = 7, *, input_ids: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                             camera_name: str = "rlbench_front", reuse_prefix: bool = True, suffix_weights: str = "bf16",
                             prefill: str = "train", sampler: str = "host", suffix_attention: str = "head",
-                            prefill_precision: str = "bf16", ddpm_sampler: str = "host", **kwargs) -> np.ndarray:
+                            prefill_precision: str = "bf16", ddpm_sampler: str = "host", suffix_operand: str = "fused",
+                            **kwargs) -> np.ndarray:
         """model_mla.py:592-775: 8-step DDIM (eta = 0) over the action chunk with the VLM as the epsilon model, then
         un-normalisation.
         * ``image`` is a PIL image / uint8 HWC frame (pre-processed here like the reference does, :656-660) or an already
@@ -454,10 +456,20 @@ class MLA(nn.Module):
         the same function as "fp8" up to rounding, and what the format costs on a checkpoint. The effect on a trained policy is not
         measured. It composes with every ``suffix_weights``, ``sampler`` and ``suffix_attention`` mode; it raises ValueError for an
         unknown value and for anything but "bf16" unless ``prefill="compact"`` (hence also when ``reuse_prefix=False``): there is never
-        a silent bf16 prefill."""
-        from .infer import PrefixCachedEps, ddpm_sampler_needs_engine, sampler_needs_engine, suffix_attention_needs_engine
+        a silent bf16 prefill.
+        ``suffix_operand`` (opt-in, cached prefix only): how a sampler step over MORE than 8 suffix rows (window >= 8) forms the RMSNorm
+        and SwiGLU operands of its projections. "fused" (default): inside the projections' input staging (mla_gemm_skinny_* pre 1 / 2),
+        five launches per layer, every workgroup re-forms the operand. "once": each RMSNorm operand once per pass by the stand-alone
+        kernel, every projection on the plain skinny form, SwiGLU in the gate|up projection's epilogue
+        (mla_gemm_skinny_gateup_swiglu_*: the packed gate|up rows never reach memory) -- seven launches per layer, the same bits as
+        "fused". Up to 8 suffix rows both values run the same pass (the GEMV stages its input once per workgroup already). It composes
+        with every ``suffix_weights``, ``suffix_attention``, ``sampler``, ``ddpm_sampler``, ``prefill`` and ``prefill_precision`` mode; it
+        is validated in front of every other mode and raises ValueError for an unknown value, and for "once" when ``reuse_prefix=False``
+        or the cached-prefix engine does not serve the shape: no silent fallback."""
+        from .infer import (PrefixCachedEps, ddpm_sampler_needs_engine, sampler_needs_engine, suffix_attention_needs_engine,
+                            suffix_operand_needs_engine)
         MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision,
-                         ddpm_sampler=ddpm_sampler)
+                         ddpm_sampler=ddpm_sampler, suffix_operand=suffix_operand)
         if prefill != "train" and not reuse_prefix:
             raise ValueError(f"prefill={prefill!r} needs the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has no "
                              "separate prefill")
@@ -487,9 +499,11 @@ class MLA(nn.Module):
             sampler_needs_engine(sampler, "PrefixCachedEps", T)
             ddpm_sampler_needs_engine(ddpm_sampler, "PrefixCachedEps", T)
             suffix_attention_needs_engine(suffix_attention, T)
+            suffix_operand_needs_engine(suffix_operand, T)
         if reuse_prefix:
             eps_model = PrefixCachedEps.for_inputs(self.vlm, n_action_rows=T, suffix_weights=suffix_weights, prefill=prefill,
-                                                   suffix_attention=suffix_attention, prefill_precision=prefill_precision, **model_kwargs)
+                                                   suffix_attention=suffix_attention, prefill_precision=prefill_precision,
+                                                   suffix_operand=suffix_operand, **model_kwargs)
         samples = self._sample(eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs, ddpm_sampler)
         return self._actions([samples[:1].float().cpu().numpy()], unnorm_key)[0]
 
@@ -501,7 +515,7 @@ class MLA(nn.Module):
                                   num_samples: Optional[int] = None, prefill: str = "train", sampler: str = "host",
                                   suffix_attention: str = "head", prefill_precision: str = "bf16",
                                   groups_attention: str = "head", batch_prefill: str = "train",
-                                  ddpm_sampler: str = "host") -> np.ndarray:
+                                  ddpm_sampler: str = "host", suffix_operand: str = "fused") -> np.ndarray:
         """B observations -> [B, T, action_dim]: by definition B independent `predict_action_diff` calls (the reference's
         `predict_action_batch`, model_mla.py:994, is dead code), computed on ONE cached prefix pass per DDIM step
         (mla_amd/infer.py:BatchedPrefixCachedEps): the prompts may have different lengths, the FPS start indices are drawn once per chunk.
@@ -554,11 +568,15 @@ class MLA(nn.Module):
         31; beyond, "split" is the head launch by construction. It composes with every ``suffix_weights`` and ``sampler`` mode; where the
         call ends in predict_action_diff (B = 1, no ``num_samples`` or N = 1) it is forwarded as ``suffix_attention="split"``; it raises
         ValueError for an unknown value, and for "split" when ``reuse_prefix=False`` or the batched engine does not serve the shape: it is
-        never the warned loop."""
+        never the warned loop.
+        ``suffix_operand``: predict_action_diff's, forwarded where the call ends in it (B = 1, no ``num_samples`` or N = 1). The batched
+        engines (B >= 2, or N >= 2 chunks per observation) form every operand once per pass already (stand-alone RMSNorm / SwiGLU
+        kernels in front of the row GEMMs): they accept both values and launch what they launch without the keyword. An unknown value,
+        and "once" with ``reuse_prefix=False``, raise ValueError."""
         from .infer import (BatchedPrefixCachedEps, batch_prefill_needs_engine, check_batch_prefill, check_prefill_precision,
                             ddpm_sampler_needs_engine, groups_attention_needs_engine, sampler_needs_engine, suffix_attention_single_only)
         MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps,
-                         groups_attention=groups_attention, ddpm_sampler=ddpm_sampler)
+                         groups_attention=groups_attention, ddpm_sampler=ddpm_sampler, suffix_operand=suffix_operand)
         check_prefill_precision(prefill_precision)                           # an unknown value only: no mode but "bf16" is served here
         check_batch_prefill(batch_prefill, reuse_prefix)
         if prefill != "train":
@@ -576,7 +594,7 @@ class MLA(nn.Module):
             return self._predict_action_diff_batch_samples(images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix,
                                                            suffix_weights, num_samples, sampler, suffix_attention, groups_attention,
-                                                           batch_prefill, ddpm_sampler)
+                                                           batch_prefill, ddpm_sampler, suffix_operand)
         input_ids, pointclouds = MLA._batch_prompts(self, B, instructions, input_ids, pointclouds, cur_robot_states)
         if noise is not None and tuple(noise.shape[:2]) != (B, T):
             raise ValueError(f"noise must be [B, T, action_dim] = [{B}, {T}, ...], got {tuple(noise.shape)}")
@@ -591,7 +609,8 @@ class MLA(nn.Module):
         single = {} if batch_prefill == "train" else {"prefill": "compact", "prefill_precision": batch_prefill}
         if B == 1:
             return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler, ddpm_sampler=ddpm_sampler,
-                       suffix_attention="split" if groups_attention == "split" else suffix_attention, **single)[None]
+                       suffix_attention="split" if groups_attention == "split" else suffix_attention, suffix_operand=suffix_operand,
+                       **single)[None]
         if suffix_weights != "bf16":
             raise NotImplementedError(f"suffix_weights={suffix_weights!r}: the batched engine (BatchedPrefixCachedEps, mla_gemm_suffix_bf16) "
                                       "streams bf16 weights only; sample B >= 2 observations with \"bf16\", one at a time, or pass "
@@ -617,7 +636,7 @@ class MLA(nn.Module):
     def _predict_action_diff_batch_samples(self, images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix, suffix_weights, num_samples,
                                            sampler="host", suffix_attention="head", groups_attention="head", batch_prefill="train",
-                                           ddpm_sampler="host"):
+                                           ddpm_sampler="host", suffix_operand="fused"):
         """predict_action_diff_batch(num_samples=N) -> [B, N, T, action_dim] (called inside its inference mode; see its docstring)."""
         B, N, T = len(images), int(num_samples), self.future_action_window_size + 1
         if N < 1:
@@ -635,7 +654,8 @@ class MLA(nn.Module):
         single = {} if batch_prefill == "train" else {"prefill": "compact", "prefill_precision": batch_prefill}
         if B == 1:
             return samples_of(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler, ddpm_sampler=ddpm_sampler,
-                              suffix_attention=suffix_attention, groups_attention=groups_attention, **single)[None]
+                              suffix_attention=suffix_attention, groups_attention=groups_attention, suffix_operand=suffix_operand,
+                              **single)[None]
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
                              "bf16 weights only")
@@ -673,7 +693,7 @@ class MLA(nn.Module):
                                     reuse_prefix: bool = True, suffix_weights: str = "bf16", prefill: str = "train",
                                     sampler: str = "host", suffix_attention: str = "head",
                                     prefill_precision: str = "bf16", groups_attention: str = "head",
-                                    ddpm_sampler: str = "host") -> np.ndarray:
+                                    ddpm_sampler: str = "host", suffix_operand: str = "fused") -> np.ndarray:
         """N action chunks for ONE observation -> [N, T, action_dim]: by definition N independent `predict_action_diff` calls on the same
         observation with the initial samples ``noise[n]`` (critic / best-of-N choice, uncertainty estimates, temporal ensembling), computed
         on ONE cached prefix (mla_amd/infer.py:SampleGroupsEps): the encoders and the decoder prefill run once per call, every sampler step
@@ -706,11 +726,14 @@ class MLA(nn.Module):
         with the library's plan (at 7B it splits for N <= 4 at window <= 15 and N <= 2 up to window 31; beyond, it is the head launch).
         It composes with every ``suffix_weights``, ``sampler``, ``prefill`` and ``prefill_precision`` mode; forwarded as
         ``suffix_attention="split"`` for ``num_samples=1``; raises ValueError for an unknown value, and for "split" when
-        ``reuse_prefix=False`` or the shared-prefix engine does not serve the shape."""
+        ``reuse_prefix=False`` or the shared-prefix engine does not serve the shape.
+        ``suffix_operand``: predict_action_diff's, forwarded for ``num_samples=1``. With more samples the shared-prefix engine forms every
+        operand once per pass already: both values are accepted and launch what is launched without the keyword. An unknown value, and
+        "once" with ``reuse_prefix=False``, raise ValueError."""
         from .infer import (SampleGroupsEps, ddpm_sampler_needs_engine, groups_attention_needs_engine, sampler_needs_engine,
                             suffix_attention_single_only)
         MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision,
-                         groups_attention, ddpm_sampler)
+                         groups_attention, ddpm_sampler, suffix_operand)
         if int(num_samples) != 1:
             suffix_attention_single_only(suffix_attention, f"predict_action_diff_samples with num_samples={num_samples}")
         if prefill != "train" and not reuse_prefix:
@@ -731,7 +754,7 @@ class MLA(nn.Module):
         if N == 1:
             return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, prefill=prefill, sampler=sampler,
                        ddpm_sampler=ddpm_sampler, suffix_attention="split" if groups_attention == "split" else suffix_attention,
-                       prefill_precision=prefill_precision)[None]
+                       prefill_precision=prefill_precision, suffix_operand=suffix_operand)[None]
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
                              "bf16 weights only")

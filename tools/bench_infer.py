@@ -67,6 +67,14 @@
                                                           --kernel-table first prints, without the model, one launch (pair) per splits in
                                                           {1, 2, 3, plan} of mla_attn_groups_split against the route's head launch at 32
                                                           heads and 545 prefix rows; --pairs 0 stops after the table
+    python tools/bench_infer.py --pair-operand [--pairs P] [--chunks C[,C..]] [--kernel-table]
+                                                          suffix_operand="fused" and "once" chunks alternating in one process, in pairs,
+                                                          per chunk length (default 1, 8, 16), with bf16 and fp8 suffix weights, the device
+                                                          sampler in both arms: per-chunk latency and the captured suffix pass alone with
+                                                          the 95 % interval of the pair differences; --kernel-table first prints, without
+                                                          the model, one line per 7B projection shape at M = 9, 17, 33, 64 for bf16 and W8:
+                                                          the fused form, the plain form, and for gate|up the SwiGLU-epilogue form against
+                                                          plain gate|up + swiglu_fwd; --pairs 0 stops after the table
     python tools/bench_infer.py --batch B[,B..] --pair-batch-prefill [--chunks C[,C..]] [--pairs P] [--kernel-table]
                                                           predict_action_diff_batch with batch_prefill="train" and "fp8" in one process,
                                                           alternating: per-call latency and the engines' prefill behind the encoders
@@ -159,6 +167,7 @@ def main():
     ap.add_argument("--pair-ddpm-sampler", action="store_true", help="alternate ddpm_sampler=\"host\" and ddpm_sampler=\"device\" on use_ddim=False calls in one process, in pairs")
     ap.add_argument("--pair-attention", action="store_true", help="alternate suffix_attention=\"head\" and \"split\" in one process, in pairs; with --samples / --batch: groups_attention "
                     "on the multi-row routes")
+    ap.add_argument("--pair-operand", action="store_true", help="alternate suffix_operand=\"fused\" and \"once\" in one process, in pairs")
     ap.add_argument("--pair-batch-prefill", action="store_true", help="with --batch: alternate batch_prefill=\"train\" and \"fp8\" in one process, in pairs")
     ap.add_argument("--pairs", type=int, default=6)
     ap.add_argument("--kernel-table", action="store_true", help="with --pair-fp8: the two _w8 kernels per projection shape and M; with "
@@ -168,6 +177,8 @@ def main():
     args = ap.parse_args()
     if args.pair_sampler or args.pair_ddpm_sampler:
         return main_pair_sampler(args, ddpm=args.pair_ddpm_sampler)
+    if args.pair_operand:
+        return main_pair_operand(args)
     batches = [int(v) for v in args.batch.split(",")]
     if args.pair_batch_prefill:
         return main_pair_batch_prefill(args, batches)
@@ -466,6 +477,127 @@ def main_pair_attention(args):
                               "split_vs_head_chunk_rel_diff_random_weights":
                                   round(float(((acts["split"] - acts["head"]) ** 2).sum() ** 0.5 / (acts["head"] ** 2).sum() ** 0.5), 5),
                               "pass_captured": eng.graph is not None, "graph_error": eng.graph_error, "data": "synthetic"}), flush=True)
+
+
+def _operand_kernel_table(dev, Ms=(9, 17, 33, 64), H=4096, I=11008, copies=8, reps=5, rounds=3):
+    """The suffix projections of a 7B layer at M rows, per form, bf16 and W8 (e4m3fn codes of the same weights): "fused" = what
+    suffix_operand="fused" launches (RMSNorm / SwiGLU in the input staging: mla_gemm_skinny_* pre 1 / 2), "plain" = the same projection
+    on a ready operand (pre 0), and for gate|up "swiglu_epilogue" = mla_gemm_skinny_gateup_swiglu_* against "plain+swiglu_fwd" (two
+    launches, the packed rows through memory). Every form is captured as `copies` launches over `copies` different weight matrices (at
+    least 268 MB per graph: nothing stays in the caches), the forms alternate per round; microseconds per launch (sequence) = replay
+    time / copies: the median over the rounds and every round's value. Yields one row per (format, projection, M)."""
+    from mla_amd import hip
+    bf16 = torch.bfloat16
+    ln = torch.ones(H, dtype=bf16, device=dev)
+    shapes = (("qkv", 3 * H, H, "norm"), ("gate_up", 2 * I, H, "norm"), ("down", H, I, "swiglu"))
+    for fmt in ("bf16", "w8"):
+        for name, N, K, pre in shapes:
+            Ws = [(torch.randn(N, K, device=dev) * 0.02).to(bf16) for _ in range(copies)]
+            if fmt == "w8":
+                Ws = [hip.quant_fp8_rows(W) for W in Ws]
+            for M in Ms:
+                x = (torch.randn(M, K, device=dev) * 0.5).to(bf16)
+                x_pre = (torch.randn(M, 2 * K, device=dev) * 0.5).to(bf16) if pre == "swiglu" else x        # the fused form's input
+                res = torch.randn(M, N, device=dev).to(bf16) if name == "down" else None
+                out = torch.empty(M, N, dtype=bf16, device=dev)
+                kw = {"norm_weight": ln, "eps": 1e-5} if pre == "norm" else {"swiglu": True}
+
+                def gemm(xx, W, **k):
+                    if fmt == "w8":
+                        hip.gemm_skinny_w8(xx, W[0], W[1], out, N, 0, M, res, **k)
+                    else:
+                        hip.gemm_skinny(xx, W, out, N, 0, M, res, **k)
+                forms = {"fused": lambda W: gemm(x_pre, W, **kw), "plain": lambda W: gemm(x, W)}
+                if name == "gate_up":
+                    act = torch.empty(M, I, dtype=bf16, device=dev)
+                    forms["plain+swiglu_fwd"] = lambda W: (gemm(x, W), hip.swiglu_fwd(out))
+                    forms["swiglu_epilogue"] = (lambda W: hip.gemm_skinny_gateup_swiglu_w8(x, W[0], W[1], out=act)) if fmt == "w8" else \
+                        (lambda W: hip.gemm_skinny_gateup_swiglu(x, W, out=act))
+                graphs = {}
+                for form, fn in forms.items():
+                    for W in Ws[:2]:                                        # function attributes, allocator
+                        fn(W)
+                    torch.cuda.synchronize()
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        for W in Ws:
+                            fn(W)
+                    g.replay()
+                    graphs[form] = g
+                us = {form: [] for form in forms}
+                for _ in range(rounds):
+                    for form, g in graphs.items():
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for _ in range(reps):
+                            g.replay()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        us[form].append(round(e0.elapsed_time(e1) / (reps * copies) * 1e3, 2))
+                med = {k: sorted(v)[len(v) // 2] for k, v in us.items()}
+                wbytes = N * K * (1 if fmt == "w8" else 2)
+                yield {"weights": fmt, "projection": name, "N": N, "K": K, "M": M, "weight_bytes": wbytes, "us_per_launch_median": med,
+                       "weight_stream_tbps": {k: round(wbytes / 1e12 / (v * 1e-6), 2) for k, v in med.items()}, "us_per_launch_rounds": us}
+                del graphs
+            del Ws
+            torch.cuda.empty_cache()
+
+
+def main_pair_operand(args):
+    """suffix_operand="fused" vs "once" on the same box, alternating, per chunk length and suffix-weight mode: predict_action_diff per
+    chunk with the device sampler in both arms (host clock around `iters` calls that end in a device synchronise) and the captured
+    suffix pass alone (device events around 8 replays). Every figure's reference is the "fused" arm of the same process. The two arms
+    compute the same bits (asserted); at chunk 1 they launch the same pass."""
+    dev = torch.device("cuda", 0)
+    if args.kernel_table:
+        for row in _operand_kernel_table(dev):
+            print(json.dumps({"metric": "suffix projection per launch at 7B layer shapes: fused vs plain operand forms", "unit": "us", **row,
+                              "data": "synthetic"}), flush=True)
+    if args.pairs < 1:
+        return
+    from mla_amd.infer import PrefixCachedEps
+    m, b, ids = _setup()
+    image, pc, state = _observation(b)
+    mk = dict(input_ids=ids, **_engine_kw(b))
+    arms = ("fused", "once")
+    t91 = torch.tensor([91], device=dev)
+    for C in ([int(v) for v in args.chunks.split(",")] if args.chunks else [1, 8, 16]):
+        m.future_action_window_size = m.vlm.future_action_window_size = C - 1
+        noise = torch.randn(1, C, 7, device=dev)
+        kw = dict(image=image, pointcloud=pc, cur_robot_state=state, input_ids=ids, num_ddim_steps=args.steps, noise=noise, sampler="device")
+        for w in ("bf16", "fp8"):
+            acts = {}
+            for arm in arms:                                                # engines, graphs, tables; the same seed: the same FPS start indices
+                torch.manual_seed(1)
+                acts[arm] = m.predict_action_diff(suffix_weights=w, suffix_operand=arm, **kw)
+            assert np.array_equal(acts["fused"], acts["once"]), "suffix_operand=\"once\" must return the bits of \"fused\""
+
+            def chunk_ms(arm):
+                return _time_ms(lambda: m.predict_action_diff(suffix_weights=w, suffix_operand=arm, **kw), args.iters)
+
+            def pass_ms(arm):
+                with torch.inference_mode():
+                    eng = PrefixCachedEps.for_inputs(m.vlm, n_action_rows=C, suffix_weights=w, suffix_operand=arm, **mk)
+                    eng(noise, t91)
+                    return _replay_ms(eng), eng
+            chunk, suffix = {arm: [] for arm in arms}, {arm: [] for arm in arms}
+            for _ in range(args.pairs):                                     # fused, once, fused, once, ...: same box, interleaved
+                for arm in arms:
+                    chunk[arm].append(chunk_ms(arm))
+                for arm in arms:
+                    suffix[arm].append(pass_ms(arm)[0])
+            eng = pass_ms("once")[1]
+            print(json.dumps({"metric": "predict_action_diff, MLA-Llama2-7B, batch 1: suffix_operand=fused vs once in alternating pairs",
+                              "action_chunk": C, "suffix_rows": C + 1, "suffix_weights": w, "sampler": "device", "ddim_steps": args.steps,
+                              "pairs": args.pairs, "iters_per_arm_and_pair": args.iters, "unit": "ms",
+                              "chunk_ms": {k: [round(v, 2) for v in vs] for k, vs in chunk.items()},
+                              "chunk_once_minus_fused": _pair_stats(chunk["fused"], chunk["once"]),
+                              "suffix_pass_ms": {k: [round(v, 3) for v in vs] for k, vs in suffix.items()},
+                              "suffix_pass_once_minus_fused": _pair_stats(suffix["fused"], suffix["once"]),
+                              "weights_streamed_per_pass_gb": round(_stream_bytes(m, w) / 1e9, 2),
+                              "suffix_pass_weight_stream_tbps": {k: round(_stream_bytes(m, w) / 1e12 / (min(v) * 1e-3), 2) for k, v in suffix.items()},
+                              "same_bits": True, "pass_captured": eng.graph is not None, "graph_error": eng.graph_error,
+                              "data": "synthetic"}), flush=True)
 
 
 def _groups_split_table(dev, cases, H=32, S_p=545, layers=32, reps=5, rounds=3):
