@@ -14,33 +14,33 @@ or `mla_attn_chunk` (up to 64) against the cached keys / values, the same RMSNor
 kernels' arithmetic as training (RMSNorm and SwiGLU are applied inside the projections' input staging). The 6 x 32 launches of a pass
 (5 with the rotary embedding in the QKV kernel's epilogue) are captured once into a HIP graph and replayed per DDIM step.
 
-Opt-in (`suffix_weights="fp8"`, see SUFFIX_WEIGHT_MODES): the sampler steps stream a per-row e4m3fn copy of the projections through
+Opt-in (`suffix_weights="fp8"`, see MODES): the sampler steps stream a per-row e4m3fn copy of the projections through
 `mla_gemv_w8` / `mla_gemm_skinny_w8` (one chunk per call) or `mla_gemm_suffix_w8` (N chunks per observation, SampleGroupsEps) -- half the
 weight bytes per step; prefill, activations, cache and attention are untouched.
 
-Opt-in (`sampler="device"`, see SAMPLER_MODES): the DDIM loop around the suffix passes runs on the device -- `sample_ddim` replays one
+Opt-in (`sampler="device"`, see MODES): the DDIM loop around the suffix passes runs on the device -- `sample_ddim` replays one
 captured sampler step (x_embedder, `mla_sampler_rows`, the suffix pass, final_layer, `mla_ddim_step`) per DDIM step with the step index in
 device memory: no copy to the device and no host wait between the steps, bit for bit the host loop's result.
 
-Opt-in (`ddpm_sampler="device"`, see DDPM_SAMPLER_MODES): the same for the DDPM loop of `use_ddim=False` -- `sample_ddpm` draws the steps'
+Opt-in (`ddpm_sampler="device"`, see MODES): the same for the DDPM loop of `use_ddim=False` -- `sample_ddpm` draws the steps'
 normal variates up front into a device table (asynchronous launches, the host loop's order) and replays the captured step with
 `mla_ddpm_step` as its update num_timesteps times: the host loop's bits and generator position.
 
-Opt-in (`suffix_attention="split"`, see SUFFIX_ATTENTION_MODES; PrefixCachedEps only): the attention launch of the suffix pass becomes
+Opt-in (`suffix_attention="split"`, see MODES; PrefixCachedEps only): the attention launch of the suffix pass becomes
 `mla_attn_chunk_split` -- every head's key tiles cut over several workgroups, the partial softmax states merged in a fixed order by a
 second launch -- for every R; the same function up to summation order. The multi-row engines (BatchedPrefixCachedEps, SampleGroupsEps,
-BatchedSampleGroupsEps) take the same argument from the public `groups_attention="split"` (GROUPS_ATTENTION_MODES) and launch
+BatchedSampleGroupsEps) take the same argument from the public `groups_attention="split"` (MODES) and launch
 `mla_attn_groups_split`: that split per (sample, group), the prefix lengths still read on the device.
 
-Opt-in (`suffix_operand="once"`, see SUFFIX_OPERAND_MODES; PrefixCachedEps only): a pass over more than 8 suffix rows forms each RMSNorm
+Opt-in (`suffix_operand="once"`, see MODES; PrefixCachedEps only): a pass over more than 8 suffix rows forms each RMSNorm
 operand once with the stand-alone kernel, runs every projection on the plain `mla_gemm_skinny_*` form and takes SwiGLU into the gate|up
 projection's epilogue (`mla_gemm_skinny_gateup_swiglu_*`) -- seven launches per layer instead of five, the same bits.
 
-Opt-in (`prefill="compact"`, `prefill_precision="fp8"`, see PREFILL_MODES / PREFILL_PRECISION_MODES; PrefixCachedEps and SampleGroupsEps):
+Opt-in (`prefill="compact"`, `prefill_precision="fp8"`, see MODES; PrefixCachedEps and SampleGroupsEps):
 the prefix rows of one observation run on the row-sized GEMMs of csrc/prefill.hip, and with "fp8" their four projections per layer on
 e4m3fn codes of weights AND activations (csrc/prefill.hip, the K = 128 FP8 MFMA) -- the same FP8 weight copy the suffix pass streams.
 
-Opt-in (`batch_prefill="fp8"`, see BATCH_PREFILL_MODES; BatchedPrefixCachedEps and BatchedSampleGroupsEps): the NB x S_pmax right-padded
+Opt-in (`batch_prefill="fp8"`, see MODES; BatchedPrefixCachedEps and BatchedSampleGroupsEps): the NB x S_pmax right-padded
 prefix rows of a batched call run through the same compact layer in ONE pass per layer, their projections on the wide-row FP8 GEMMs
 (mla_gemm_prefill_f8_wide*: up to 65 536 rows, 64- or 128-row tiles).
 
@@ -50,6 +50,7 @@ drawn once per action chunk (the prefix is computed once). With given start indi
 tests/test_inference_gpu.py) the two are the same function."""
 from __future__ import annotations
 
+import collections
 import functools
 import logging
 import math
@@ -67,103 +68,161 @@ _LOG = logging.getLogger(__name__)
 SPLICE_TAG = 29871                                  # prismatic.py:882-887 (eval): the [t, x] tokens go in front of its last occurrence
 PROMPT_TAIL = (29871, 32001, 32002, 29871)          # model_mla.py:640-645: appended unless the row already ends with the tag, then [:-3]
 
-# What the suffix pass streams (MLA.predict_action_diff(suffix_weights=...)); the prefill does not depend on it (bf16 weights unless
-# prefill_precision says otherwise), so the prefix keys / values keep bf16-weight precision:
-#   "bf16"         the decoder weights as they are (default)
-#   "fp8"          a per-row e4m3fn copy (hip.quant_fp8_rows) through mla_gemv_w8 / mla_gemm_skinny_w8 (PrefixCachedEps) or
-#                  mla_gemm_suffix_w8 (SampleGroupsEps): half the bytes per sampler step
-#   "fp8_as_bf16"  the bf16 kernels on bf16(q * scale): the reference of the "fp8" path, and what the format costs on a checkpoint
-SUFFIX_WEIGHT_MODES = ("bf16", "fp8", "fp8_as_bf16")
+
+class Mode(NamedTuple):
+    """One opt-in keyword of MLA.predict_action_diff*: a row of MODES."""
+    name: str
+    values: tuple                    # the default first
+    needs: Optional[str] = None      # what a value other than the default requires of the call (check_mode): None, "reuse_prefix",
+                                     # "compact" (prefill="compact"), "ddim" / "ddpm" (reuse_prefix and that sampler loop)
+    tag: Optional[str] = None        # an engine's mode: tag + value joins the engine key (_engine); None: a mode of the call
+    lacks: str = ""                  # check_mode's clause: what the whole-forward sampler (reuse_prefix=False) has instead
 
 
-def check_suffix_weights(mode):
-    if mode not in SUFFIX_WEIGHT_MODES:
-        raise ValueError(f"suffix_weights must be one of {SUFFIX_WEIGHT_MODES}, got {mode!r}")
+# Every row: name, values, needs, tag, lacks. The order is the order of the engine key's suffix.
+MODES = (
+    # What the suffix pass streams (MLA.predict_action_diff(suffix_weights=...)); the prefill does not depend on it (bf16 weights unless
+    # prefill_precision says otherwise), so the prefix keys / values keep bf16-weight precision:
+    #   "bf16"         the decoder weights as they are (default)
+    #   "fp8"          a per-row e4m3fn copy (hip.quant_fp8_rows) through mla_gemv_w8 / mla_gemm_skinny_w8 (PrefixCachedEps) or
+    #                  mla_gemm_suffix_w8 (SampleGroupsEps): half the bytes per sampler step
+    #   "fp8_as_bf16"  the bf16 kernels on bf16(q * scale): the reference of the "fp8" path, and what the format costs on a checkpoint
+    # Without the cached prefix, or on a shape no engine serves, the public methods refuse it themselves (route by route).
+    Mode("suffix_weights", ("bf16", "fp8", "fp8_as_bf16"), None, ""),
+
+    # How the prefix rows are prefilled (MLA.predict_action_diff(prefill=...)):
+    #   "train"    the training forward kernels (ops.DecoderLayerFn._fwd: 256-row GEMM tiles built for 17 536 rows), default
+    #   "compact"  the row-sized GEMMs of mla_amd/csrc/prefill.hip (64 x 128 tiles, deterministic split-K): q|k|v + RoPE written straight into
+    #              the cache, gate|up + SwiGLU writing the product only; same function up to summation order and rounding points
+    # The batched method refuses "compact" as not implemented, the other two without the cached prefix: each says so itself.
+    Mode("prefill", ("train", "compact"), None, "prefill:"),
+
+    # Which attention launch the sampler steps of PrefixCachedEps use (MLA.predict_action_diff(suffix_attention=...)):
+    #   "head"   mla_attn_decode / mla_attn_chunk: one workgroup per (sample, head, 16 queries) reads the head's whole key range (default)
+    #   "split"  mla_attn_chunk_split with the library's plan for every R: each head's key tiles cut over several workgroups, the partial
+    #            softmax states merged in a fixed order by a second launch; same function up to summation order
+    Mode("suffix_attention", ("head", "split"), "reuse_prefix", "attention:", "has no suffix pass"),
+
+    # Which attention launch the sampler steps of the multi-row engines use (MLA.predict_action_diff_batch / predict_action_diff_samples
+    # (groups_attention=...); BatchedPrefixCachedEps, SampleGroupsEps, BatchedSampleGroupsEps: it is THEIR suffix_attention attribute):
+    #   "head"   mla_attn_chunk_ragged / mla_attn_chunk_groups / mla_attn_chunk_ragged_groups: one workgroup per (sample, group, head, 16
+    #            queries) reads its whole key range (default)
+    #   "split"  mla_attn_groups_split with the library's plan at the engine's capacity: the key tiles of every (sample, group, head) cut over
+    #            several workgroups, the partial softmax states merged in a fixed order by a second launch; same function up to summation
+    #            order. The plan splits for B * G <= 4 at R <= 16 and B * G <= 2 at 17 <= R <= 32 (32 heads, 256 CUs); beyond, it is the
+    #            head launch by construction
+    Mode("groups_attention", ("head", "split"), "reuse_prefix", "attention:", "has no suffix pass"),
+
+    # What the compact prefill's four projections per layer compute on (MLA.predict_action_diff(prefill="compact", prefill_precision=...)):
+    #   "bf16"         the bf16 weights and activations as they are (default)
+    #   "fp8"          e4m3fn codes of BOTH operands on the K = 128 MFMA (mla_amd/csrc/prefill.hip): the model's FP8 weight copy (one scale
+    #                  per output channel, shared with suffix_weights="fp8") and the projection inputs quantised per row (hip.quant_fp8_rows);
+    #                  attention, cache, norms and residual stream stay bf16
+    #   "fp8_as_bf16"  the bf16 compact kernels on bf16(code * scale) of the same weight codes, the projection inputs quantised and
+    #                  dequantised by the same statement: the reference of the "fp8" path, and what the format costs on a checkpoint
+    Mode("prefill_precision", ("bf16", "fp8", "fp8_as_bf16"), "compact", "precision:"),
+
+    # How the batched engines prefill the NB x S_pmax right-padded prefix rows of a pass (MLA.predict_action_diff_batch(batch_prefill=...);
+    # BatchedPrefixCachedEps, BatchedSampleGroupsEps):
+    #   "train"        one varlen pass per layer on the training forward kernels, the bf16 weights (default)
+    #   "fp8"          the compact prefill's layer (_compact_layer) over all NB x S_pmax rows at once, its four projections on e4m3fn codes of
+    #                  BOTH operands: the wide-row GEMMs of mla_amd/csrc/prefill.hip (mla_gemm_prefill_f8_wide*, up to 65 536 rows, 64- or
+    #                  128-row tiles) beyond 1024 rows, the compact ones up to there; the model's FP8 weight copy, shared with
+    #                  suffix_weights="fp8"; attention, cache, norms and residual stream stay bf16
+    #   "fp8_as_bf16"  per sample, the bf16 compact kernels on bf16(code * scale) of the same weight codes and on quantised-and-dequantised
+    #                  inputs: the reference of the "fp8" path (slow: one pass over the layers per sample)
+    Mode("batch_prefill", ("train", "fp8", "fp8_as_bf16"), "reuse_prefix", "batch_prefill:", "has no separate prefill"),
+
+    # How a pass of PrefixCachedEps over MORE than 8 suffix rows forms the RMSNorm / SwiGLU operands of its projections
+    # (MLA.predict_action_diff(suffix_operand=...)); up to 8 rows the GEMV stages its input once per workgroup and both values are one pass:
+    #   "fused"  inside the projections' input staging (mla_gemm_skinny_* pre 1 / 2): five launches per layer, the operand re-formed by every
+    #            workgroup (default)
+    #   "once"   RMSNorm by the stand-alone kernel once per pass, every projection on the plain skinny form, SwiGLU in the gate|up
+    #            projection's epilogue (mla_gemm_skinny_gateup_swiglu_*): seven launches per layer, the same bits
+    Mode("suffix_operand", ("fused", "once"), "reuse_prefix", "operand:", "has no suffix pass"),
+
+    # Who runs the DDIM loop around the suffix passes (MLA.predict_action_diff(sampler=...)):
+    #   "host"    GaussianDiffusion.ddim_sample_loop: torch expressions per step, tables copied to the device per step (default)
+    #   "device"  _CachedEpsBase.sample_ddim: one captured sampler step replayed num_ddim_steps times, the step index in device memory; no copy
+    #             to the device and no host wait between the steps; the same bits
+    Mode("sampler", ("host", "device"), "ddim", None, "has the host loop only"),
+
+    # Who runs the DDPM loop (use_ddim=False: the training diffusion's p_sample_loop) around the suffix passes
+    # (MLA.predict_action_diff(ddpm_sampler=...)); sampler= above keeps its meaning, the DDIM loop:
+    #   "host"    GaussianDiffusion.p_sample_loop: torch expressions per step, a device wait in every step (default)
+    #   "device"  _CachedEpsBase.sample_ddpm: the steps' normal variates drawn up front into a device table, then one captured sampler step
+    #             replayed num_timesteps times; no copy to the device and no host wait between the steps; the same bits and generator position
+    Mode("ddpm_sampler", ("host", "device"), "ddpm", None, "has the host loop only"),
+)
+MODES = {mode.name: mode for mode in MODES}
+# The order in which a public method validates them: the first wrong keyword is the one the error names.
+CHECK_ORDER = ("suffix_operand", "suffix_weights", "prefill", "prefill_precision", "sampler", "ddpm_sampler", "suffix_attention",
+               "groups_attention")
 
 
-# How the prefix rows are prefilled (MLA.predict_action_diff(prefill=...)):
-#   "train"    the training forward kernels (ops.DecoderLayerFn._fwd: 256-row GEMM tiles built for 17 536 rows), default
-#   "compact"  the row-sized GEMMs of mla_amd/csrc/prefill.hip (64 x 128 tiles, deterministic split-K): q|k|v + RoPE written straight into
-#              the cache, gate|up + SwiGLU writing the product only; same function up to summation order and rounding points
-PREFILL_MODES = ("train", "compact")
+class Modes(collections.namedtuple("Modes", list(MODES), defaults=[mode.values[0] for mode in MODES.values()])):
+    """The mode keywords of one call or one engine, every field at its default unless given: what the public methods, the factories,
+    _engine and the constructors hand to each other."""
+    __slots__ = ()
+
+    def forwarded(self, *names) -> dict:
+        """The keywords `names` as a call that ends in a single-observation method hands them on: without groups_attention among them,
+        its "split" is that method's suffix_attention="split"; batch_prefill is that method's compact prefill at that precision."""
+        keywords = {name: getattr(self, name) for name in names}
+        if "suffix_attention" in keywords and "groups_attention" not in keywords and self.groups_attention == "split":
+            keywords["suffix_attention"] = "split"
+        if self.batch_prefill != "train":
+            keywords.update(prefill="compact", prefill_precision=self.batch_prefill)
+        return keywords
 
 
-def check_prefill(mode):
-    if mode not in PREFILL_MODES:
-        raise ValueError(f"prefill must be one of {PREFILL_MODES}, got {mode!r}")
+def check_mode(name, value, reuse_prefix=True, use_ddim=True, num_ddim_steps=8, prefill="compact"):
+    """The argument errors of one keyword: an unknown value; a value other than the default in a call that does not run what the value
+    needs (Mode.needs) -- a keyword is never silently ignored, and there is never a silent bf16 prefill. A shape the engine does not
+    serve is the caller's ValueError (needs_engine)."""
+    mode = MODES[name]
+    if value not in mode.values:
+        raise ValueError(f"{name} must be one of {mode.values}, got {value!r}")
+    if value == mode.values[0] or mode.needs is None:
+        return
+    if mode.needs == "compact":
+        if prefill != "compact":
+            raise ValueError(f"{name}=\"{value}\" runs on the compact prefill (prefill=\"compact\"); prefill={prefill!r} has the bf16 "
+                             "kernels only")
+        return
+    if not reuse_prefix:
+        raise ValueError(f"{name}=\"{value}\" runs on the cached prefix (reuse_prefix=True); the whole-forward sampler {mode.lacks}")
+    ddim = use_ddim and num_ddim_steps is not None
+    if mode.needs == "ddim" and not ddim:
+        raise ValueError(f"{name}=\"{value}\" is the DDIM loop at eta = 0 (use_ddim=True and num_ddim_steps); the DDPM loop's device form "
+                         f"is ddpm_sampler=\"{value}\"")
+    if mode.needs == "ddpm" and ddim:
+        raise ValueError(f"{name}=\"{value}\" is the DDPM loop (use_ddim=False or num_ddim_steps=None); this call runs the DDIM sampler, "
+                         f"whose device loop is sampler=\"{value}\"")
 
 
-# What the compact prefill's four projections per layer compute on (MLA.predict_action_diff(prefill="compact", prefill_precision=...)):
-#   "bf16"         the bf16 weights and activations as they are (default)
-#   "fp8"          e4m3fn codes of BOTH operands on the K = 128 MFMA (mla_amd/csrc/prefill.hip): the model's FP8 weight copy (one scale
-#                  per output channel, shared with suffix_weights="fp8") and the projection inputs quantised per row (hip.quant_fp8_rows);
-#                  attention, cache, norms and residual stream stay bf16
-#   "fp8_as_bf16"  the bf16 compact kernels on bf16(code * scale) of the same weight codes, the projection inputs quantised and
-#                  dequantised by the same statement: the reference of the "fp8" path, and what the format costs on a checkpoint
-PREFILL_PRECISION_MODES = ("bf16", "fp8", "fp8_as_bf16")
+def check_modes(modes: Modes, reuse_prefix=True, use_ddim=True, num_ddim_steps=8):
+    """check_mode over a public method's keywords in CHECK_ORDER, before the model is touched (batch_prefill is the batched method's own
+    check, behind these)."""
+    for name in CHECK_ORDER:
+        check_mode(name, getattr(modes, name), reuse_prefix, use_ddim, num_ddim_steps, modes.prefill)
 
 
-def check_prefill_precision(mode, prefill="compact"):
-    """The argument errors of prefill_precision=: an unknown value; anything but "bf16" without prefill="compact" (there is never a silent
-    bf16 prefill)."""
-    if mode not in PREFILL_PRECISION_MODES:
-        raise ValueError(f"prefill_precision must be one of {PREFILL_PRECISION_MODES}, got {mode!r}")
-    if mode != "bf16" and prefill != "compact":
-        raise ValueError(f"prefill_precision={mode!r} runs on the compact prefill (prefill=\"compact\"); prefill={prefill!r} has the bf16 "
-                         "kernels only")
+def engine_modes(**keywords) -> Modes:
+    """The bundle of an engine's factory, its keywords validated in the order given (an engine IS the cached prefix)."""
+    modes = Modes(**keywords)
+    for name, value in keywords.items():
+        check_mode(name, value, prefill=modes.prefill)
+    return modes
 
 
-# How the batched engines prefill the NB x S_pmax right-padded prefix rows of a pass (MLA.predict_action_diff_batch(batch_prefill=...);
-# BatchedPrefixCachedEps, BatchedSampleGroupsEps):
-#   "train"        one varlen pass per layer on the training forward kernels, the bf16 weights (default)
-#   "fp8"          the compact prefill's layer (_compact_layer) over all NB x S_pmax rows at once, its four projections on e4m3fn codes of
-#                  BOTH operands: the wide-row GEMMs of mla_amd/csrc/prefill.hip (mla_gemm_prefill_f8_wide*, up to 65 536 rows, 64- or
-#                  128-row tiles) beyond 1024 rows, the compact ones up to there; the model's FP8 weight copy, shared with
-#                  suffix_weights="fp8"; attention, cache, norms and residual stream stay bf16
-#   "fp8_as_bf16"  per sample, the bf16 compact kernels on bf16(code * scale) of the same weight codes and on quantised-and-dequantised
-#                  inputs: the reference of the "fp8" path (slow: one pass over the layers per sample)
-BATCH_PREFILL_MODES = ("train", "fp8", "fp8_as_bf16")
-
-
-def check_batch_prefill(mode, reuse_prefix=True):
-    """The argument errors of batch_prefill=: an unknown value; anything but "train" without the cached prefix. A shape the engine does
-    not serve is the caller's ValueError (batch_prefill_needs_engine)."""
-    if mode not in BATCH_PREFILL_MODES:
-        raise ValueError(f"batch_prefill must be one of {BATCH_PREFILL_MODES}, got {mode!r}")
-    if mode != "train" and not reuse_prefix:
-        raise ValueError(f"batch_prefill={mode!r} runs on the cached-prefix engines (reuse_prefix=True); the whole-forward sampler has no "
-                         "separate prefill")
-
-
-def batch_prefill_needs_engine(mode, engine: str, n_action_rows: int):
-    """batch_prefill other than "train" on a shape the cached-prefix engine does not serve: an error, never the warned loop."""
-    if mode != "train":
-        raise ValueError(f"batch_prefill={mode!r}: the cached-prefix engine ({engine}) does not serve {1 + n_action_rows} suffix rows per "
-                         "sample at this head_dim; use batch_prefill=\"train\"")
-
-
-# Which attention launch the sampler steps of PrefixCachedEps use (MLA.predict_action_diff(suffix_attention=...)):
-#   "head"   mla_attn_decode / mla_attn_chunk: one workgroup per (sample, head, 16 queries) reads the head's whole key range (default)
-#   "split"  mla_attn_chunk_split with the library's plan for every R: each head's key tiles cut over several workgroups, the partial
-#            softmax states merged in a fixed order by a second launch; same function up to summation order
-SUFFIX_ATTENTION_MODES = ("head", "split")
-
-
-def check_suffix_attention(mode, reuse_prefix=True):
-    """The argument errors of suffix_attention=: an unknown value; "split" without the cached prefix. A shape the engine does not serve is
-    the caller's ValueError (suffix_attention_needs_engine)."""
-    if mode not in SUFFIX_ATTENTION_MODES:
-        raise ValueError(f"suffix_attention must be one of {SUFFIX_ATTENTION_MODES}, got {mode!r}")
-    if mode == "split" and not reuse_prefix:
-        raise ValueError("suffix_attention=\"split\" runs on the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has no "
-                         "suffix pass")
-
-
-def suffix_attention_needs_engine(mode, n_action_rows: int):
-    """suffix_attention="split" on a shape PrefixCachedEps does not serve: an error, never the warned loop of whole-forward calls."""
-    if mode == "split":
-        raise ValueError(f"suffix_attention=\"split\": the cached-prefix engine (PrefixCachedEps) does not serve {1 + n_action_rows} suffix "
-                         "rows per sample at this head_dim; use suffix_attention=\"head\"")
+def needs_engine(engine: str, n_action_rows: int, **keywords):
+    """A keyword with a value other than its default on a shape the cached-prefix engine does not serve: an error that names the first
+    such keyword, never the warned loop of whole-forward calls."""
+    for name, value in keywords.items():
+        if value != MODES[name].values[0]:
+            raise ValueError(f"{name}=\"{value}\": the cached-prefix engine ({engine}) does not serve {1 + n_action_rows} suffix rows per "
+                             f"sample at this head_dim; use {name}=\"{MODES[name].values[0]}\"")
 
 
 def suffix_attention_single_only(mode, route: str):
@@ -173,117 +232,6 @@ def suffix_attention_single_only(mode, route: str):
         raise NotImplementedError(f"suffix_attention=\"split\": {route} runs the ragged / groups engines, whose attention launches "
                                   "(mla_attn_chunk_ragged, mla_attn_chunk_groups and their batched forms) take their split-key form from "
                                   "groups_attention=\"split\"; suffix_attention serves predict_action_diff (one observation, one chunk) only")
-
-
-# How a pass of PrefixCachedEps over MORE than 8 suffix rows forms the RMSNorm / SwiGLU operands of its projections
-# (MLA.predict_action_diff(suffix_operand=...)); up to 8 rows the GEMV stages its input once per workgroup and both values are one pass:
-#   "fused"  inside the projections' input staging (mla_gemm_skinny_* pre 1 / 2): five launches per layer, the operand re-formed by every
-#            workgroup (default)
-#   "once"   RMSNorm by the stand-alone kernel once per pass, every projection on the plain skinny form, SwiGLU in the gate|up
-#            projection's epilogue (mla_gemm_skinny_gateup_swiglu_*): seven launches per layer, the same bits
-SUFFIX_OPERAND_MODES = ("fused", "once")
-
-
-def check_suffix_operand(mode, reuse_prefix=True):
-    """The argument errors of suffix_operand=: an unknown value; "once" without the cached prefix. A shape the engine does not serve is
-    the caller's ValueError (suffix_operand_needs_engine)."""
-    if mode not in SUFFIX_OPERAND_MODES:
-        raise ValueError(f"suffix_operand must be one of {SUFFIX_OPERAND_MODES}, got {mode!r}")
-    if mode == "once" and not reuse_prefix:
-        raise ValueError("suffix_operand=\"once\" runs on the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has no "
-                         "suffix pass")
-
-
-def suffix_operand_needs_engine(mode, n_action_rows: int):
-    """suffix_operand="once" on a shape PrefixCachedEps does not serve: an error, never the warned loop of whole-forward calls."""
-    if mode == "once":
-        raise ValueError(f"suffix_operand=\"once\": the cached-prefix engine (PrefixCachedEps) does not serve {1 + n_action_rows} suffix "
-                         "rows per sample at this head_dim; use suffix_operand=\"fused\"")
-
-
-# Which attention launch the sampler steps of the multi-row engines use (MLA.predict_action_diff_batch / predict_action_diff_samples
-# (groups_attention=...); BatchedPrefixCachedEps, SampleGroupsEps, BatchedSampleGroupsEps):
-#   "head"   mla_attn_chunk_ragged / mla_attn_chunk_groups / mla_attn_chunk_ragged_groups: one workgroup per (sample, group, head, 16
-#            queries) reads its whole key range (default)
-#   "split"  mla_attn_groups_split with the library's plan at the engine's capacity: the key tiles of every (sample, group, head) cut over
-#            several workgroups, the partial softmax states merged in a fixed order by a second launch; same function up to summation
-#            order. The plan splits for B * G <= 4 at R <= 16 and B * G <= 2 at 17 <= R <= 32 (32 heads, 256 CUs); beyond, it is the
-#            head launch by construction
-GROUPS_ATTENTION_MODES = ("head", "split")
-
-
-def check_groups_attention(mode, reuse_prefix=True):
-    """The argument errors of groups_attention=: an unknown value; "split" without the cached prefix. A shape the engine does not serve is
-    the caller's ValueError (groups_attention_needs_engine)."""
-    if mode not in GROUPS_ATTENTION_MODES:
-        raise ValueError(f"groups_attention must be one of {GROUPS_ATTENTION_MODES}, got {mode!r}")
-    if mode == "split" and not reuse_prefix:
-        raise ValueError("groups_attention=\"split\" runs on the cached-prefix engines (reuse_prefix=True); the whole-forward sampler has no "
-                         "suffix pass")
-
-
-def groups_attention_needs_engine(mode, engine: str, n_action_rows: int):
-    """groups_attention="split" on a shape the cached-prefix engine does not serve: an error, never the warned loop."""
-    if mode == "split":
-        raise ValueError(f"groups_attention=\"split\": the cached-prefix engine ({engine}) does not serve {1 + n_action_rows} suffix rows per "
-                         "sample at this head_dim; use groups_attention=\"head\"")
-
-
-# Who runs the DDIM loop around the suffix passes (MLA.predict_action_diff(sampler=...)):
-#   "host"    GaussianDiffusion.ddim_sample_loop: torch expressions per step, tables copied to the device per step (default)
-#   "device"  _CachedEpsBase.sample_ddim: one captured sampler step replayed num_ddim_steps times, the step index in device memory; no copy
-#             to the device and no host wait between the steps; the same bits
-SAMPLER_MODES = ("host", "device")
-
-
-def check_sampler(mode, reuse_prefix=True, use_ddim=True, num_ddim_steps=8):
-    """The argument errors of sampler=: an unknown value; "device" without the cached prefix or without the DDIM sampler (the DDPM loop's
-    device form has its own keyword, ddpm_sampler=). A shape the engine does not serve is the caller's ValueError (sampler_needs_engine)."""
-    if mode not in SAMPLER_MODES:
-        raise ValueError(f"sampler must be one of {SAMPLER_MODES}, got {mode!r}")
-    if mode == "device":
-        if not reuse_prefix:
-            raise ValueError("sampler=\"device\" runs on the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has the "
-                             "host loop only")
-        if not use_ddim or num_ddim_steps is None:
-            raise ValueError("sampler=\"device\" is the DDIM loop at eta = 0 (use_ddim=True and num_ddim_steps); the DDPM loop's "
-                             "device form is ddpm_sampler=\"device\"")
-
-
-def sampler_needs_engine(mode, engine: str, n_action_rows: int):
-    """sampler="device" on a shape the cached-prefix engine does not serve: an error, never the warned loop of whole-forward calls."""
-    if mode == "device":
-        raise ValueError(f"sampler=\"device\": the cached-prefix engine ({engine}) does not serve {1 + n_action_rows} suffix rows per "
-                         "sample at this head_dim; use sampler=\"host\"")
-
-
-# Who runs the DDPM loop (use_ddim=False: the training diffusion's p_sample_loop) around the suffix passes
-# (MLA.predict_action_diff(ddpm_sampler=...)); sampler= above keeps its meaning, the DDIM loop:
-#   "host"    GaussianDiffusion.p_sample_loop: torch expressions per step, a device wait in every step (default)
-#   "device"  _CachedEpsBase.sample_ddpm: the steps' normal variates drawn up front into a device table, then one captured sampler step
-#             replayed num_timesteps times; no copy to the device and no host wait between the steps; the same bits and generator position
-DDPM_SAMPLER_MODES = ("host", "device")
-
-
-def check_ddpm_sampler(mode, reuse_prefix=True, use_ddim=False, num_ddim_steps=None):
-    """The argument errors of ddpm_sampler=: an unknown value; "device" without the cached prefix, or on a call that runs the DDIM sampler
-    (the keyword is never silently ignored). A shape the engine does not serve is the caller's ValueError (ddpm_sampler_needs_engine)."""
-    if mode not in DDPM_SAMPLER_MODES:
-        raise ValueError(f"ddpm_sampler must be one of {DDPM_SAMPLER_MODES}, got {mode!r}")
-    if mode == "device":
-        if not reuse_prefix:
-            raise ValueError("ddpm_sampler=\"device\" runs on the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has "
-                             "the host loop only")
-        if use_ddim and num_ddim_steps is not None:
-            raise ValueError("ddpm_sampler=\"device\" is the DDPM loop (use_ddim=False or num_ddim_steps=None); this call runs the DDIM "
-                             "sampler, whose device loop is sampler=\"device\"")
-
-
-def ddpm_sampler_needs_engine(mode, engine: str, n_action_rows: int):
-    """ddpm_sampler="device" on a shape the cached-prefix engine does not serve: an error, never the warned loop of whole-forward calls."""
-    if mode == "device":
-        raise ValueError(f"ddpm_sampler=\"device\": the cached-prefix engine ({engine}) does not serve {1 + n_action_rows} suffix rows per "
-                         "sample at this head_dim; use ddpm_sampler=\"host\"")
 
 
 _GRAPH_OFF = "MLA_INFER_GRAPH=0: the device sampler launches its steps one by one"      # graph_error of an eager sample_ddim / sample_ddpm
@@ -313,20 +261,13 @@ class _CachedEpsBase:
     """What the cached-prefix engines share: the packed weights, the captured suffix pass and the `model(x, t)` call of the samplers.
     A subclass provides prefill() and _suffix_pass() and sets B, R, T, H, h_in, h_out, cache."""
 
-    suffix_operand = "fused"         # SUFFIX_OPERAND_MODES: read by PrefixCachedEps._suffix_pass; the row-GEMM engines form the operand once anyway
+    suffix_operand = "fused"         # MODES: read by PrefixCachedEps._suffix_pass; the row-GEMM engines form the operand once anyway
 
-    def __init__(self, vlm, n_action_rows: int = 1, suffix_weights: str = "bf16", prefill: str = "train", suffix_attention: str = "head",
-                 prefill_precision: str = "bf16", suffix_operand: str = "fused"):
-        check_suffix_weights(suffix_weights)
-        check_prefill(prefill)
-        check_suffix_attention(suffix_attention)
-        check_prefill_precision(prefill_precision, prefill)
-        check_suffix_operand(suffix_operand)
-        self.suffix_operand = suffix_operand
-        self.suffix_weights = suffix_weights
-        self.prefill_mode = prefill
-        self.prefill_precision = prefill_precision
-        self.suffix_attention = suffix_attention
+    def __init__(self, vlm, n_action_rows: int = 1, modes: Modes = Modes()):
+        """modes: as the factory validated them (engine_modes). The multi-row engines' attention mode is groups_attention."""
+        self.suffix_weights, self.prefill_mode, self.prefill_precision = modes.suffix_weights, modes.prefill, modes.prefill_precision
+        self.suffix_attention = "split" if "split" in (modes.suffix_attention, modes.groups_attention) else "head"
+        self.suffix_operand, self.batch_prefill = modes.suffix_operand, modes.batch_prefill
         self._attn_ws = None         # "split": the partial softmax states of mla_attn_chunk_split, allocated once beside h_in / h_out
         self._prefill_ws = None      # "compact": the split-K workspace of the prefill GEMMs, allocated once beside h_in / h_out
         self._prefill_xq = None      # prefill_precision "fp8": the projection inputs' codes (one buffer, viewed [rows, K]) ...
@@ -362,24 +303,12 @@ class _CachedEpsBase:
         return False
 
     @classmethod
-    def _engine(cls, vlm, store: str, key: tuple, ctor: tuple, suffix_weights="bf16", prefill="train", suffix_attention="head",
-                prefill_precision="bf16", batch_prefill="train", suffix_operand="fused"):
+    def _engine(cls, vlm, store: str, key: tuple, ctor: tuple, **modes):
         """The vlm's engine for `key` in vlm.__dict__[store], constructed as cls(vlm, *ctor) on first use; at most 4 per store, the oldest
-        leaves first. A mode other than the default is part of the key -- the engines coexist: a captured graph holds the addresses of
-        ITS weights and ITS attention launches. The caller prefills."""
+        leaves first. An engine's mode (Modes' fields as keywords) other than the default is part of the key, as its row of MODES tags it
+        -- the engines coexist: a captured graph holds the addresses of ITS weights and ITS attention launches. The caller prefills."""
         engines = vlm.__dict__.setdefault(store, {})
-        if suffix_weights != "bf16":
-            key += (suffix_weights,)
-        if prefill != "train":
-            key += ("prefill:" + prefill,)
-        if suffix_attention != "head":
-            key += ("attention:" + suffix_attention,)
-        if prefill_precision != "bf16":
-            key += ("precision:" + prefill_precision,)
-        if batch_prefill != "train":
-            key += ("batch_prefill:" + batch_prefill,)
-        if suffix_operand != "fused":
-            key += ("operand:" + suffix_operand,)
+        key += tuple(mode.tag + value for mode, value in zip(MODES.values(), Modes(**modes)) if mode.tag is not None and value != mode.values[0])
         eng = engines.get(key)
         if eng is None:
             if len(engines) >= 4:
@@ -770,16 +699,12 @@ class PrefixCachedEps(_CachedEpsBase):
     @classmethod
     def for_inputs(cls, vlm, input_ids, n_action_rows: int = 1, suffix_weights: str = "bf16", prefill: str = "train",
                    suffix_attention: str = "head", prefill_precision: str = "bf16", suffix_operand: str = "fused", **model_kwargs):
-        check_suffix_weights(suffix_weights)
-        check_prefill(prefill)
-        check_suffix_attention(suffix_attention)
-        check_prefill_precision(prefill_precision, prefill)
-        check_suffix_operand(suffix_operand)
+        modes = engine_modes(suffix_weights=suffix_weights, prefill=prefill, suffix_attention=suffix_attention,
+                             prefill_precision=prefill_precision, suffix_operand=suffix_operand)
         k = cls._splice_position(input_ids)
         # a handful of prompt lengths per process; each engine holds 0.4 GB at 7B
         eng = cls._engine(vlm, "_prefix_engines", (int(input_ids.shape[0]), k, int(n_action_rows), str(input_ids.device)),
-                          (n_action_rows, suffix_weights, prefill, suffix_attention, prefill_precision, suffix_operand), suffix_weights,
-                          prefill, suffix_attention, prefill_precision, suffix_operand=suffix_operand)
+                          (n_action_rows, modes), **modes._asdict())
         eng.prefill(input_ids, k, **model_kwargs)
         return eng
 
@@ -979,7 +904,7 @@ class _RowGemmEps(_CachedEpsBase):
     MAX_ROWS = 256                   # suffix rows per pass (mla_gemm_suffix_bf16 / _w8 and their `_pos` forms); more are served as consecutive passes
     MAX_R = 64                       # rows per sample / group (mla_attn_chunk_ragged, mla_attn_chunk_groups, mla_attn_chunk_ragged_groups)
     BUCKET = 64                      # cache capacity granularity in rows (the engines with ragged prompts)
-    batch_prefill = "train"          # BATCH_PREFILL_MODES: how _varlen_prefill runs the prefix rows (the two engines with ragged prompts)
+    batch_prefill = "train"          # MODES: how _varlen_prefill runs the prefix rows (the two engines with ragged prompts)
 
     def _batch_prefill_buffers(self, NB: int, G: int, dev):
         """batch_prefill "fp8" / "fp8_as_bf16": the compact prefill's buffers at the engine's capacity, allocated once (call outside
@@ -1149,15 +1074,12 @@ class BatchedPrefixCachedEps(_RowGemmEps):
         the caller has them, the prompt tail is handled there) and yields
         (SubBatchPlan, prefilled engine) per sub-batch. Two sub-batches may share an engine: finish sampling one before taking the next.
         suffix_attention: "head" (mla_attn_chunk_ragged) or "split" (mla_attn_groups_split, one group per sample); batch_prefill:
-        BATCH_PREFILL_MODES; one engine per mode."""
-        check_groups_attention(suffix_attention)
-        check_batch_prefill(batch_prefill)
+        MODES' batch_prefill; one engine per mode."""
+        modes = engine_modes(groups_attention=suffix_attention, batch_prefill=batch_prefill)
         front = cls._front_tokens(vlm, images, point_cloud, camera_name)
         for sub in plan_batch(ids_rows, n_action_rows, int(front.shape[1]), cls.MAX_ROWS, cls.BUCKET, add_tail=add_tail):
             eng = cls._engine(vlm, "_prefix_engines_batched", (sub.stop - sub.start, sub.S_cap, sub.R, str(front.device)),
-                              (n_action_rows, "bf16", "train", suffix_attention), suffix_attention=suffix_attention,
-                              batch_prefill=batch_prefill)
-            eng.batch_prefill = batch_prefill
+                              (n_action_rows, modes), **modes._asdict())
             eng.prefill(sub, front[sub.start:sub.stop], proprio[sub.start:sub.stop])
             yield sub, eng
 
@@ -1214,22 +1136,18 @@ class SampleGroupsEps(_RowGemmEps):
         """-> (engine, prefilled for this observation; passes [(start, stop), ...] of plan_sample_groups). One engine -- and its graphs --
         per suffix_weights, prefill and attention mode, as in PrefixCachedEps.for_inputs. suffix_attention: "head"
         (mla_attn_chunk_groups) or "split" (mla_attn_groups_split)."""
-        check_suffix_weights(suffix_weights)
-        check_prefill(prefill)
-        check_prefill_precision(prefill_precision, prefill)
-        check_groups_attention(suffix_attention)
+        modes = engine_modes(suffix_weights=suffix_weights, prefill=prefill, prefill_precision=prefill_precision,
+                             groups_attention=suffix_attention)
         k = PrefixCachedEps._splice_position(input_ids)
         passes = plan_sample_groups(num_samples, 1 + n_action_rows, cls.MAX_ROWS)
         capacity = max(stop - start for start, stop in passes)
         eng = cls._engine(vlm, "_prefix_engines_samples", (k, int(n_action_rows), capacity, str(input_ids.device)),
-                          (n_action_rows, capacity, suffix_weights, prefill, prefill_precision, suffix_attention), suffix_weights, prefill,
-                          suffix_attention, prefill_precision)
+                          (n_action_rows, capacity, modes), **modes._asdict())
         eng.prefill(input_ids, k, **model_kwargs)
         return eng, passes
 
-    def __init__(self, vlm, n_action_rows: int, capacity: int, suffix_weights: str = "bf16", prefill: str = "train",
-                 prefill_precision: str = "bf16", suffix_attention: str = "head"):
-        super().__init__(vlm, n_action_rows, suffix_weights, prefill, suffix_attention, prefill_precision)
+    def __init__(self, vlm, n_action_rows: int, capacity: int, modes: Modes = Modes()):
+        super().__init__(vlm, n_action_rows, modes)
         self.capacity = int(capacity)
         self._graphs = {}            # G -> captured pass over G groups
         self._graphs_packed = None   # the weights those graphs hold the addresses of
@@ -1361,19 +1279,15 @@ class BatchedSampleGroupsEps(_RowGemmEps):
         """Generator over the passes of one call: runs the encoders once over all observations, plans (plan_batch_samples) and yields
         (SampleSubBatchPlan, prefilled engine) per sub-batch. Two sub-batches may share an engine: finish sampling one before taking the
         next. suffix_attention: "head" (mla_attn_chunk_ragged_groups) or "split" (mla_attn_groups_split); batch_prefill:
-        BATCH_PREFILL_MODES; one engine per mode."""
-        check_suffix_weights(suffix_weights)
-        check_groups_attention(suffix_attention)
-        check_batch_prefill(batch_prefill)
+        MODES' batch_prefill; one engine per mode."""
+        modes = engine_modes(suffix_weights=suffix_weights, groups_attention=suffix_attention, batch_prefill=batch_prefill)
         front = cls._front_tokens(vlm, images, point_cloud, camera_name)
         plans = plan_batch_samples(ids_rows, n_action_rows, int(front.shape[1]), num_samples, cls.MAX_ROWS, cls.BUCKET, add_tail=add_tail)
         if plans is None:
             raise ValueError(f"{num_samples} groups of {1 + n_action_rows} rows exceed the {cls.MAX_ROWS} rows of a pass (fits_pass)")
         for sub in plans:
             eng = cls._engine(vlm, "_prefix_engines_batch_samples", (sub.stop - sub.start, sub.G, sub.S_cap, sub.R, str(front.device)),
-                              (n_action_rows, suffix_weights, "train", suffix_attention), suffix_weights,
-                              suffix_attention=suffix_attention, batch_prefill=batch_prefill)
-            eng.batch_prefill = batch_prefill
+                              (n_action_rows, modes), **modes._asdict())
             eng.prefill(sub, front[sub.start:sub.stop], proprio[sub.start:sub.stop])
             yield sub, eng
 

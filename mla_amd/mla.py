@@ -327,21 +327,8 @@ class MLA(nn.Module):
         st = self.normalize_proprio(np.asarray(cur_robot_state), unnorm_key) if self.norm_stats is not None else np.asarray(cur_robot_state)
         return torch.tensor(st, dtype=torch.float32).reshape(1, 1, -1).to(device)
 
-    # ---- what the four sampling entry points share (called as MLA._check_modes: the mode errors come before `self` is touched)
-    @staticmethod
-    def _check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision="bf16",
-                     groups_attention="head", ddpm_sampler="host", suffix_operand="fused"):
-        from .infer import (check_ddpm_sampler, check_groups_attention, check_prefill, check_prefill_precision, check_sampler,
-                            check_suffix_attention, check_suffix_operand, check_suffix_weights)
-        check_suffix_operand(suffix_operand, reuse_prefix)
-        check_suffix_weights(suffix_weights)
-        check_prefill(prefill)
-        check_prefill_precision(prefill_precision, prefill)
-        check_sampler(sampler, reuse_prefix, use_ddim, num_ddim_steps)
-        check_ddpm_sampler(ddpm_sampler, reuse_prefix, use_ddim, num_ddim_steps)
-        check_suffix_attention(suffix_attention, reuse_prefix)
-        check_groups_attention(groups_attention, reuse_prefix)
-
+    # ---- what the four sampling entry points share (their mode keywords: infer.Modes, validated by infer.check_modes before `self` is
+    # touched)
     def _draw_x0(self, given, T, action_dim, device):
         """The initial samples [len(given), T, action_dim] fp32 and the RNG draws of one predict_action_diff call per chunk, in call order
         (:707-708): randn(1, T, D) unless the chunk's noise row [1, T, D] is given, then the unused randint."""
@@ -466,10 +453,9 @@ class MLA(nn.Module):
         with every ``suffix_weights``, ``suffix_attention``, ``sampler``, ``ddpm_sampler``, ``prefill`` and ``prefill_precision`` mode; it
         is validated in front of every other mode and raises ValueError for an unknown value, and for "once" when ``reuse_prefix=False``
         or the cached-prefix engine does not serve the shape: no silent fallback."""
-        from .infer import (PrefixCachedEps, ddpm_sampler_needs_engine, sampler_needs_engine, suffix_attention_needs_engine,
-                            suffix_operand_needs_engine)
-        MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision,
-                         ddpm_sampler=ddpm_sampler, suffix_operand=suffix_operand)
+        from .infer import Modes, PrefixCachedEps, check_modes, needs_engine
+        check_modes(Modes(suffix_weights=suffix_weights, prefill=prefill, suffix_attention=suffix_attention, prefill_precision=prefill_precision,
+                          suffix_operand=suffix_operand, sampler=sampler, ddpm_sampler=ddpm_sampler), reuse_prefix, use_ddim, num_ddim_steps)
         if prefill != "train" and not reuse_prefix:
             raise ValueError(f"prefill={prefill!r} needs the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has no "
                              "separate prefill")
@@ -492,18 +478,13 @@ class MLA(nn.Module):
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached-prefix engine (reuse_prefix=True and a shape "
                              "PrefixCachedEps.supports); the whole-forward sampler has bf16 weights only")
-        if prefill != "train" and not reuse_prefix:
-            raise ValueError(f"prefill={prefill!r}: the cached-prefix engine does not serve this shape (PrefixCachedEps.supports: at most "
-                             "64 suffix rows, head_dim 128); use prefill=\"train\"")
-        if not reuse_prefix:
-            sampler_needs_engine(sampler, "PrefixCachedEps", T)
-            ddpm_sampler_needs_engine(ddpm_sampler, "PrefixCachedEps", T)
-            suffix_attention_needs_engine(suffix_attention, T)
-            suffix_operand_needs_engine(suffix_operand, T)
         if reuse_prefix:
             eps_model = PrefixCachedEps.for_inputs(self.vlm, n_action_rows=T, suffix_weights=suffix_weights, prefill=prefill,
                                                    suffix_attention=suffix_attention, prefill_precision=prefill_precision,
                                                    suffix_operand=suffix_operand, **model_kwargs)
+        else:
+            needs_engine("PrefixCachedEps", T, prefill=prefill, sampler=sampler, ddpm_sampler=ddpm_sampler, suffix_attention=suffix_attention,
+                         suffix_operand=suffix_operand)
         samples = self._sample(eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs, ddpm_sampler)
         return self._actions([samples[:1].float().cpu().numpy()], unnorm_key)[0]
 
@@ -573,12 +554,12 @@ class MLA(nn.Module):
         engines (B >= 2, or N >= 2 chunks per observation) form every operand once per pass already (stand-alone RMSNorm / SwiGLU
         kernels in front of the row GEMMs): they accept both values and launch what they launch without the keyword. An unknown value,
         and "once" with ``reuse_prefix=False``, raise ValueError."""
-        from .infer import (BatchedPrefixCachedEps, batch_prefill_needs_engine, check_batch_prefill, check_prefill_precision,
-                            ddpm_sampler_needs_engine, groups_attention_needs_engine, sampler_needs_engine, suffix_attention_single_only)
-        MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps,
-                         groups_attention=groups_attention, ddpm_sampler=ddpm_sampler, suffix_operand=suffix_operand)
-        check_prefill_precision(prefill_precision)                           # an unknown value only: no mode but "bf16" is served here
-        check_batch_prefill(batch_prefill, reuse_prefix)
+        from .infer import BatchedPrefixCachedEps, Modes, check_mode, check_modes, needs_engine, suffix_attention_single_only
+        modes = Modes(suffix_weights=suffix_weights, prefill=prefill, suffix_attention=suffix_attention, groups_attention=groups_attention,
+                      batch_prefill=batch_prefill, suffix_operand=suffix_operand, sampler=sampler, ddpm_sampler=ddpm_sampler)
+        check_modes(modes, reuse_prefix, use_ddim, num_ddim_steps)
+        check_mode("prefill_precision", prefill_precision)                    # an unknown value only: no mode but "bf16" is served here
+        check_mode("batch_prefill", batch_prefill, reuse_prefix)
         if prefill != "train":
             raise NotImplementedError(f"prefill={prefill!r}: the batched engines prefill B x S rows on the training GEMMs; the compact "
                                       "prefill serves one observation (predict_action_diff, predict_action_diff_samples)")
@@ -593,8 +574,7 @@ class MLA(nn.Module):
         if num_samples is not None:
             return self._predict_action_diff_batch_samples(images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix,
-                                                           suffix_weights, num_samples, sampler, suffix_attention, groups_attention,
-                                                           batch_prefill, ddpm_sampler, suffix_operand)
+                                                           num_samples, modes)
         input_ids, pointclouds = MLA._batch_prompts(self, B, instructions, input_ids, pointclouds, cur_robot_states)
         if noise is not None and tuple(noise.shape[:2]) != (B, T):
             raise ValueError(f"noise must be [B, T, action_dim] = [{B}, {T}, ...], got {tuple(noise.shape)}")
@@ -605,24 +585,18 @@ class MLA(nn.Module):
             return self.predict_action_diff(images[b], pointclouds[b], None, cur_robot_states[b], unnorm_key, cfg_scale, use_ddim, num_ddim_steps,
                                             action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b:b + 1],
                                             camera_name=camera_name, **kw)
-        # a call that ends in a single-observation method takes the mode as that method's compact prefill
-        single = {} if batch_prefill == "train" else {"prefill": "compact", "prefill_precision": batch_prefill}
         if B == 1:
-            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler, ddpm_sampler=ddpm_sampler,
-                       suffix_attention="split" if groups_attention == "split" else suffix_attention, suffix_operand=suffix_operand,
-                       **single)[None]
+            return one(0, reuse_prefix=reuse_prefix,
+                       **modes.forwarded("suffix_weights", "sampler", "ddpm_sampler", "suffix_attention", "suffix_operand"))[None]
         if suffix_weights != "bf16":
             raise NotImplementedError(f"suffix_weights={suffix_weights!r}: the batched engine (BatchedPrefixCachedEps, mla_gemm_suffix_bf16) "
                                       "streams bf16 weights only; sample B >= 2 observations with \"bf16\", one at a time, or pass "
                                       "`num_samples` (BatchedSampleGroupsEps serves every mode)")
-        if reuse_prefix:
-            if not BatchedPrefixCachedEps.supports_batch(self.vlm, T, warn=False):     # raised, not a warned loop of batch-1 calls
-                groups_attention_needs_engine(groups_attention, "BatchedPrefixCachedEps", T)
-                batch_prefill_needs_engine(batch_prefill, "BatchedPrefixCachedEps", T)
-            reuse_prefix = BatchedPrefixCachedEps.supports_batch(self.vlm, T)
+        if reuse_prefix and not BatchedPrefixCachedEps.supports_batch(self.vlm, T, warn=False):
+            needs_engine("BatchedPrefixCachedEps", T, groups_attention=groups_attention, batch_prefill=batch_prefill, sampler=sampler,
+                         ddpm_sampler=ddpm_sampler)                              # raised, not a warned loop of batch-1 calls
+            reuse_prefix = BatchedPrefixCachedEps.supports_batch(self.vlm, T)   # warns once
         if not reuse_prefix:
-            sampler_needs_engine(sampler, "BatchedPrefixCachedEps", T)
-            ddpm_sampler_needs_engine(ddpm_sampler, "BatchedPrefixCachedEps", T)
             return np.stack([one(b, reuse_prefix=False) for b in range(B)])
         device, ids_rows, inputs = self._batch_inputs(images, pointclouds, cur_robot_states, ids_rows, unnorm_key, camera_name)
         x0 = self._draw_x0([None if noise is None else noise[b:b + 1] for b in range(B)], T, action_dim, device)
@@ -634,10 +608,10 @@ class MLA(nn.Module):
         return self._actions(out, unnorm_key)
 
     def _predict_action_diff_batch_samples(self, images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
-                                           num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix, suffix_weights, num_samples,
-                                           sampler="host", suffix_attention="head", groups_attention="head", batch_prefill="train",
-                                           ddpm_sampler="host", suffix_operand="fused"):
-        """predict_action_diff_batch(num_samples=N) -> [B, N, T, action_dim] (called inside its inference mode; see its docstring)."""
+                                           num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix, num_samples, modes):
+        """predict_action_diff_batch(num_samples=N) -> [B, N, T, action_dim] (called inside its inference mode; see its docstring).
+        modes: its keywords as infer.Modes, validated there."""
+        from .infer import BatchedSampleGroupsEps, needs_engine
         B, N, T = len(images), int(num_samples), self.future_action_window_size + 1
         if N < 1:
             raise ValueError(f"num_samples must be >= 1, got {num_samples}")
@@ -651,37 +625,29 @@ class MLA(nn.Module):
             return self.predict_action_diff_samples(images[b], pointclouds[b], None, cur_robot_states[b], unnorm_key, N, cfg_scale, use_ddim,
                                                     num_ddim_steps, action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b],
                                                     camera_name=camera_name, **kw)
-        single = {} if batch_prefill == "train" else {"prefill": "compact", "prefill_precision": batch_prefill}
         if B == 1:
-            return samples_of(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, sampler=sampler, ddpm_sampler=ddpm_sampler,
-                              suffix_attention=suffix_attention, groups_attention=groups_attention, suffix_operand=suffix_operand,
-                              **single)[None]
-        if suffix_weights != "bf16" and not reuse_prefix:
-            raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
-                             "bf16 weights only")
+            return samples_of(0, reuse_prefix=reuse_prefix, **modes.forwarded("suffix_weights", "sampler", "ddpm_sampler", "suffix_attention",
+                                                                              "groups_attention", "suffix_operand"))[None]
+        if modes.suffix_weights != "bf16" and not reuse_prefix:
+            raise ValueError(f"suffix_weights={modes.suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler "
+                             "has bf16 weights only")
         if reuse_prefix:
-            from .infer import (BatchedSampleGroupsEps, batch_prefill_needs_engine, ddpm_sampler_needs_engine, groups_attention_needs_engine,
-                                sampler_needs_engine)
             if not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T, warn=False):
-                sampler_needs_engine(sampler, "BatchedSampleGroupsEps", T)
-                ddpm_sampler_needs_engine(ddpm_sampler, "BatchedSampleGroupsEps", T)
-                groups_attention_needs_engine(groups_attention, "BatchedSampleGroupsEps", T)
-                batch_prefill_needs_engine(batch_prefill, "BatchedSampleGroupsEps", T)
-            if suffix_weights != "bf16" and not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T, warn=False):
-                raise ValueError(f"suffix_weights={suffix_weights!r}: the batched shared-prefix engine (BatchedSampleGroupsEps) does not serve "
-                                 f"{1 + T} suffix rows per sample at this head_dim; draw the samples with \"bf16\"")
+                needs_engine("BatchedSampleGroupsEps", T, sampler=modes.sampler, ddpm_sampler=modes.ddpm_sampler,
+                             groups_attention=modes.groups_attention, batch_prefill=modes.batch_prefill, suffix_weights=modes.suffix_weights)
             if not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T) or not BatchedSampleGroupsEps.fits_pass(T, N):
                 # one observation at a time: predict_action_diff_samples serves (or refuses) the shape and the mode itself
-                return np.stack([samples_of(b, suffix_weights=suffix_weights, sampler=sampler, ddpm_sampler=ddpm_sampler,
-                                            groups_attention=groups_attention, **single) for b in range(B)])
+                return np.stack([samples_of(b, **modes.forwarded("suffix_weights", "sampler", "ddpm_sampler", "groups_attention"))
+                                 for b in range(B)])
         else:
             return np.stack([samples_of(b, reuse_prefix=False) for b in range(B)])
         device, ids_rows, inputs = self._batch_inputs(images, pointclouds, cur_robot_states, ids_rows, unnorm_key, camera_name)
         x0 = self._draw_x0([None if noise is None else noise[b, n:n + 1] for b in range(B) for n in range(N)], T, action_dim, device)   # rows (b, n)
         out = []
-        for sub, eng in BatchedSampleGroupsEps.for_batch(self.vlm, ids_rows, T, N, suffix_weights, suffix_attention=groups_attention,
-                                                         batch_prefill=batch_prefill, **inputs):
-            samples = self._sample(eng, x0[sub.start * N:sub.stop * N].contiguous(), sampler, use_ddim, num_ddim_steps, {}, ddpm_sampler)
+        for sub, eng in BatchedSampleGroupsEps.for_batch(self.vlm, ids_rows, T, N, modes.suffix_weights,
+                                                         suffix_attention=modes.groups_attention, batch_prefill=modes.batch_prefill, **inputs):
+            samples = self._sample(eng, x0[sub.start * N:sub.stop * N].contiguous(), modes.sampler, use_ddim, num_ddim_steps, {},
+                                   modes.ddpm_sampler)
             out.append(samples.float().cpu().numpy().reshape(sub.stop - sub.start, N, T, -1))
         return self._actions(out, unnorm_key)
 
@@ -730,10 +696,10 @@ class MLA(nn.Module):
         ``suffix_operand``: predict_action_diff's, forwarded for ``num_samples=1``. With more samples the shared-prefix engine forms every
         operand once per pass already: both values are accepted and launch what is launched without the keyword. An unknown value, and
         "once" with ``reuse_prefix=False``, raise ValueError."""
-        from .infer import (SampleGroupsEps, ddpm_sampler_needs_engine, groups_attention_needs_engine, sampler_needs_engine,
-                            suffix_attention_single_only)
-        MLA._check_modes(suffix_weights, prefill, sampler, suffix_attention, reuse_prefix, use_ddim, num_ddim_steps, prefill_precision,
-                         groups_attention, ddpm_sampler, suffix_operand)
+        from .infer import Modes, SampleGroupsEps, check_modes, needs_engine, suffix_attention_single_only
+        modes = Modes(suffix_weights=suffix_weights, prefill=prefill, suffix_attention=suffix_attention, groups_attention=groups_attention,
+                      prefill_precision=prefill_precision, suffix_operand=suffix_operand, sampler=sampler, ddpm_sampler=ddpm_sampler)
+        check_modes(modes, reuse_prefix, use_ddim, num_ddim_steps)
         if int(num_samples) != 1:
             suffix_attention_single_only(suffix_attention, f"predict_action_diff_samples with num_samples={num_samples}")
         if prefill != "train" and not reuse_prefix:
@@ -752,24 +718,15 @@ class MLA(nn.Module):
                                             action_dim, input_ids=input_ids, noise=None if noise is None else noise[n:n + 1],
                                             camera_name=camera_name, **kw)
         if N == 1:
-            return one(0, reuse_prefix=reuse_prefix, suffix_weights=suffix_weights, prefill=prefill, sampler=sampler,
-                       ddpm_sampler=ddpm_sampler, suffix_attention="split" if groups_attention == "split" else suffix_attention,
-                       prefill_precision=prefill_precision, suffix_operand=suffix_operand)[None]
+            return one(0, reuse_prefix=reuse_prefix, **modes.forwarded("suffix_weights", "prefill", "sampler", "ddpm_sampler", "suffix_attention",
+                                                                       "prefill_precision", "suffix_operand"))[None]
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
                              "bf16 weights only")
         if reuse_prefix:
-            if not SampleGroupsEps.supports_samples(self.vlm, T, warn=False):
-                sampler_needs_engine(sampler, "SampleGroupsEps", T)
-                ddpm_sampler_needs_engine(ddpm_sampler, "SampleGroupsEps", T)
-                groups_attention_needs_engine(groups_attention, "SampleGroupsEps", T)
-            if prefill != "train" and not SampleGroupsEps.supports_samples(self.vlm, T, warn=False):
-                raise ValueError(f"prefill={prefill!r}: the shared-prefix engine (SampleGroupsEps) does not serve {1 + T} suffix rows per "
-                                 "sample at this head_dim; use prefill=\"train\"")
-            if suffix_weights != "bf16" and not SampleGroupsEps.supports_samples(self.vlm, T, warn=False):   # raised, not a warned loop of batch-1 calls
-                raise ValueError(f"suffix_weights={suffix_weights!r}: the shared-prefix engine (SampleGroupsEps) does not serve {1 + T} "
-                                 "suffix rows per sample at this head_dim; draw the samples with \"bf16\" or one predict_action_diff call "
-                                 "each")
+            if not SampleGroupsEps.supports_samples(self.vlm, T, warn=False):       # raised, not a warned loop of batch-1 calls
+                needs_engine("SampleGroupsEps", T, sampler=sampler, ddpm_sampler=ddpm_sampler, groups_attention=groups_attention,
+                             prefill=prefill, suffix_weights=suffix_weights)
             reuse_prefix = SampleGroupsEps.supports_samples(self.vlm, T)
         if not reuse_prefix:
             return np.stack([one(n, reuse_prefix=False) for n in range(N)])

@@ -98,19 +98,19 @@ def test_wrapper_rejects_host_tensors():
 
 def test_check_groups_attention():
     from mla_amd import infer
-    assert infer.GROUPS_ATTENTION_MODES == ("head", "split")
-    assert infer.SUFFIX_ATTENTION_MODES == ("head", "split")
-    infer.check_groups_attention("head")
-    infer.check_groups_attention("head", reuse_prefix=False)
-    infer.check_groups_attention("split")
+    assert infer.MODES["groups_attention"].values == ("head", "split")
+    assert infer.MODES["suffix_attention"].values == ("head", "split")
+    infer.check_mode("groups_attention", "head")
+    infer.check_mode("groups_attention", "head", reuse_prefix=False)
+    infer.check_mode("groups_attention", "split")
     for bad in ("bogus", "Split", None, ""):
         with pytest.raises(ValueError, match="groups_attention"):
-            infer.check_groups_attention(bad)
+            infer.check_mode("groups_attention", bad)
     with pytest.raises(ValueError, match="reuse_prefix=True"):
-        infer.check_groups_attention("split", reuse_prefix=False)
+        infer.check_mode("groups_attention", "split", reuse_prefix=False)
     with pytest.raises(ValueError, match="does not serve"):
-        infer.groups_attention_needs_engine("split", "SampleGroupsEps", 70)
-    infer.groups_attention_needs_engine("head", "SampleGroupsEps", 70)
+        infer.needs_engine("SampleGroupsEps", 70, groups_attention="split")
+    infer.needs_engine("SampleGroupsEps", 70, groups_attention="head")
 
 
 def test_engines_take_the_mode():

@@ -128,19 +128,19 @@ def test_wrapper_rejects_host_tensors():
 
 def test_check_suffix_attention():
     from mla_amd import infer
-    assert infer.SUFFIX_ATTENTION_MODES == ("head", "split")
-    infer.check_suffix_attention("head")
-    infer.check_suffix_attention("head", reuse_prefix=False)               # today's path takes every combination
-    infer.check_suffix_attention("split")
-    infer.check_suffix_attention("split", True)
+    assert infer.MODES["suffix_attention"].values == ("head", "split")
+    infer.check_mode("suffix_attention", "head")
+    infer.check_mode("suffix_attention", "head", reuse_prefix=False)   # today's path takes every combination
+    infer.check_mode("suffix_attention", "split")
+    infer.check_mode("suffix_attention", "split", True)
     for bad in ("bogus", "Split", None, "", "decode"):
         with pytest.raises(ValueError, match="suffix_attention"):
-            infer.check_suffix_attention(bad)
+            infer.check_mode("suffix_attention", bad)
     with pytest.raises(ValueError, match="reuse_prefix=True"):
-        infer.check_suffix_attention("split", reuse_prefix=False)
+        infer.check_mode("suffix_attention", "split", reuse_prefix=False)
     with pytest.raises(ValueError, match="does not serve"):
-        infer.suffix_attention_needs_engine("split", 70)
-    infer.suffix_attention_needs_engine("head", 70)
+        infer.needs_engine("PrefixCachedEps", 70, suffix_attention="split")
+    infer.needs_engine("PrefixCachedEps", 70, suffix_attention="head")
     with pytest.raises(NotImplementedError, match="ragged / groups"):
         infer.suffix_attention_single_only("split", "predict_action_diff_batch with 2 observations")
     infer.suffix_attention_single_only("head", "anything")
@@ -152,9 +152,9 @@ def test_engine_key_and_constructor_take_the_mode():
     import inspect
     from mla_amd import infer
     assert inspect.signature(infer.PrefixCachedEps.for_inputs).parameters["suffix_attention"].default == "head"
-    assert inspect.signature(infer._CachedEpsBase.__init__).parameters["suffix_attention"].default == "head"
+    assert inspect.signature(infer._CachedEpsBase.__init__).parameters["modes"].default.suffix_attention == "head"
     with pytest.raises(ValueError, match="suffix_attention"):
-        infer.PrefixCachedEps(object(), 1, "bf16", "train", "bogus")
+        infer.PrefixCachedEps(object(), 1, infer.engine_modes(suffix_weights="bf16", prefill="train", suffix_attention="bogus"))
     with pytest.raises(ValueError, match="suffix_attention"):
         infer.PrefixCachedEps.for_inputs(object(), None, suffix_attention="bogus")
 

@@ -58,12 +58,12 @@ def test_suffix_weights_is_a_named_argument_and_checked():
     for fn in (MLA.predict_action_diff, MLA.predict_action_diff_batch):
         p = inspect.signature(fn).parameters["suffix_weights"]
         assert p.default == "bf16" and p.kind in (p.KEYWORD_ONLY, p.POSITIONAL_OR_KEYWORD)
-    assert infer.SUFFIX_WEIGHT_MODES == ("bf16", "fp8", "fp8_as_bf16")
+    assert infer.MODES["suffix_weights"].values == ("bf16", "fp8", "fp8_as_bf16")
     with pytest.raises(ValueError, match="suffix_weights"):
         MLA.predict_action_diff(object(), suffix_weights="int4")
     with pytest.raises(ValueError, match="suffix_weights"):
         MLA.predict_action_diff_batch(object(), [None], [None], suffix_weights="FP8")
     with pytest.raises(ValueError, match="suffix_weights"):
         infer.PrefixCachedEps.for_inputs(object(), None, suffix_weights="e5m2")
-    for mode in infer.SUFFIX_WEIGHT_MODES:
-        infer.check_suffix_weights(mode)
+    for mode in infer.MODES["suffix_weights"].values:
+        infer.check_mode("suffix_weights", mode)

@@ -259,7 +259,7 @@ def test_once_epsilon_at_7b_layer_dimensions(dev, model_7b_layers, weights):
     kw = dict(input_ids=ids.to(dev), images=image.to(dev), point_cloud=pc.to(dev), proprio=proprio.to(dev), camera_name="rlbench_front")
     rows, eps = {}, {}
     with torch.inference_mode():
-        for operand in infer.SUFFIX_OPERAND_MODES:
+        for operand in infer.MODES["suffix_operand"].values:
             eng = infer.PrefixCachedEps.for_inputs(m.vlm, n_action_rows=T, suffix_weights=weights, suffix_operand=operand, **kw)
             _, e = eng(noise.to(dev), torch.tensor([91], device=dev))
             assert eng.suffix_operand == operand and eng.R == 17 and eng.graph is not None, eng.graph_error

@@ -141,28 +141,30 @@ def test_once_at_8_rows_of_two_samples_is_the_fused_pass(monkeypatch):
 
 
 def test_mode_validation():
-    assert infer.SUFFIX_OPERAND_MODES == ("fused", "once")
-    infer.check_suffix_operand("fused")
-    infer.check_suffix_operand("once")
-    infer.check_suffix_operand("fused", reuse_prefix=False)
+    assert infer.MODES["suffix_operand"].values == ("fused", "once")
+    infer.check_mode("suffix_operand", "fused")
+    infer.check_mode("suffix_operand", "once")
+    infer.check_mode("suffix_operand", "fused", reuse_prefix=False)
     for bad in ("Once", "", None, "plain"):
         with pytest.raises(ValueError, match="suffix_operand"):
-            infer.check_suffix_operand(bad)
+            infer.check_mode("suffix_operand", bad)
     with pytest.raises(ValueError, match="reuse_prefix"):
-        infer.check_suffix_operand("once", reuse_prefix=False)
+        infer.check_mode("suffix_operand", "once", reuse_prefix=False)
     with pytest.raises(ValueError, match="suffix_operand"):
-        infer.suffix_operand_needs_engine("once", 70)
-    infer.suffix_operand_needs_engine("fused", 70)
+        infer.needs_engine("PrefixCachedEps", 70, suffix_operand="once")
+    infer.needs_engine("PrefixCachedEps", 70, suffix_operand="fused")
 
 
 def test_public_methods_validate_the_mode_in_front_of_everything_else():
     from mla_amd.mla import MLA
     # every other mode is wrong too: the error names suffix_operand
     with pytest.raises(ValueError, match="suffix_operand"):
-        MLA._check_modes("nope", "nope", "nope", "nope", True, True, 8, "nope", "nope", "nope", suffix_operand="nope")
+        infer.check_modes(infer.Modes(suffix_weights="nope", prefill="nope", sampler="nope", suffix_attention="nope", prefill_precision="nope",
+                                      groups_attention="nope", ddpm_sampler="nope", suffix_operand="nope"), True, True, 8)
+    base = dict(suffix_weights="bf16", prefill="train", sampler="host", suffix_attention="head")
     with pytest.raises(ValueError, match="suffix_operand"):
-        MLA._check_modes("bf16", "train", "host", "head", False, True, 8, suffix_operand="once")
-    MLA._check_modes("bf16", "train", "host", "head", True, True, 8, suffix_operand="once")
+        infer.check_modes(infer.Modes(**base, suffix_operand="once"), False, True, 8)
+    infer.check_modes(infer.Modes(**base, suffix_operand="once"), True, True, 8)
     stand_in = types.SimpleNamespace()                                        # the mode errors come before `self` is touched
     for method, args in ((MLA.predict_action_diff, ()), (MLA.predict_action_diff_samples, ()), (MLA.predict_action_diff_batch, ([None], [None]))):
         with pytest.raises(ValueError, match="suffix_operand"):

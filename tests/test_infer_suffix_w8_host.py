@@ -50,5 +50,5 @@ def test_samples_suffix_weights_is_a_named_argument_and_checked():
         MLA.predict_action_diff_samples(object(), suffix_weights="int4")
     with pytest.raises(ValueError, match="suffix_weights"):
         infer.SampleGroupsEps.for_inputs(object(), None, 1, 2, suffix_weights="e5m2")
-    p = inspect.signature(infer.SampleGroupsEps.__init__).parameters["suffix_weights"]
-    assert p.default == "bf16"
+    p = inspect.signature(infer.SampleGroupsEps.__init__).parameters["modes"]
+    assert p.default.suffix_weights == "bf16"

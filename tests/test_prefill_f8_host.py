@@ -12,11 +12,11 @@ def test_prefill_precision_is_a_named_argument_and_checked():
     and "fp8" without the cached prefix are ValueErrors; the batched call refuses everything but "bf16" with NotImplementedError."""
     from mla_amd import infer
     from mla_amd.mla import MLA
-    assert infer.PREFILL_PRECISION_MODES == ("bf16", "fp8", "fp8_as_bf16")
-    assert infer.PREFILL_MODES == ("train", "compact")
-    for mode in infer.PREFILL_PRECISION_MODES:
-        infer.check_prefill_precision(mode, "compact")
-    infer.check_prefill_precision("bf16", "train")
+    assert infer.MODES["prefill_precision"].values == ("bf16", "fp8", "fp8_as_bf16")
+    assert infer.MODES["prefill"].values == ("train", "compact")
+    for mode in infer.MODES["prefill_precision"].values:
+        infer.check_mode("prefill_precision", mode, prefill="compact")
+    infer.check_mode("prefill_precision", "bf16", prefill="train")
     with pytest.raises(ValueError, match="prefill_precision"):
         MLA.predict_action_diff(object(), prefill="compact", prefill_precision="fp16")
     with pytest.raises(ValueError, match="prefill_precision"):
@@ -31,7 +31,7 @@ def test_prefill_precision_is_a_named_argument_and_checked():
         with pytest.raises(ValueError, match="compact"):
             MLA.predict_action_diff_samples(object(), prefill="train", prefill_precision=mode, num_samples=3)
         with pytest.raises(ValueError, match="compact"):
-            infer.check_prefill_precision(mode, "train")
+            infer.check_mode("prefill_precision", mode, prefill="train")
         with pytest.raises(ValueError, match="reuse_prefix=True"):
             MLA.predict_action_diff(object(), prefill="compact", prefill_precision=mode, reuse_prefix=False)
         with pytest.raises(ValueError, match="reuse_prefix=True"):

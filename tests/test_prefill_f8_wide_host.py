@@ -155,16 +155,16 @@ def test_launchers_check_their_arguments_on_the_host():
 
 
 def test_batch_prefill_is_a_named_argument_and_checked():
-    """Validated in _check_modes' position, before `self` is touched (no model, no GPU needed to see the error): an unknown value and
+    """Validated in check_modes' position, before `self` is touched (no model, no GPU needed to see the error): an unknown value and
     anything but "train" without the cached prefix are ValueErrors, on both routes; what the existing tests pin for the batched call
     stays."""
     from mla_amd import infer
     from mla_amd.mla import MLA
-    assert infer.BATCH_PREFILL_MODES == ("train", "fp8", "fp8_as_bf16")
-    assert infer.PREFILL_MODES == ("train", "compact")
-    for mode in infer.BATCH_PREFILL_MODES:
-        infer.check_batch_prefill(mode)
-    infer.check_batch_prefill("train", reuse_prefix=False)
+    assert infer.MODES["batch_prefill"].values == ("train", "fp8", "fp8_as_bf16")
+    assert infer.MODES["prefill"].values == ("train", "compact")
+    for mode in infer.MODES["batch_prefill"].values:
+        infer.check_mode("batch_prefill", mode)
+    infer.check_mode("batch_prefill", "train", reuse_prefix=False)
     for kw in ({}, {"num_samples": 2}):
         with pytest.raises(ValueError, match="batch_prefill"):
             MLA.predict_action_diff_batch(object(), [None, None], [None, None], batch_prefill="int8", **kw)
@@ -178,11 +178,11 @@ def test_batch_prefill_is_a_named_argument_and_checked():
             with pytest.raises(NotImplementedError, match="prefill_precision"):
                 MLA.predict_action_diff_batch(object(), [None, None], [None, None], batch_prefill=mode, prefill_precision="fp8", **kw)
     with pytest.raises(ValueError, match="batch_prefill"):
-        infer.check_batch_prefill("compact")
+        infer.check_mode("batch_prefill", "compact")
     for mode in ("fp8", "fp8_as_bf16"):
         with pytest.raises(ValueError, match="does not serve"):
-            infer.batch_prefill_needs_engine(mode, "BatchedPrefixCachedEps", 70)
-    infer.batch_prefill_needs_engine("train", "BatchedPrefixCachedEps", 70)
+            infer.needs_engine("BatchedPrefixCachedEps", 70, batch_prefill=mode)
+    infer.needs_engine("BatchedPrefixCachedEps", 70, batch_prefill="train")
 
 
 def test_a_batch_prefill_mode_has_an_engine_of_its_own():

@@ -111,9 +111,9 @@ def test_prefill_is_a_named_argument_and_checked():
     without the cached prefix are ValueErrors, the batched call refuses "compact" with NotImplementedError."""
     from mla_amd import infer
     from mla_amd.mla import MLA
-    assert infer.PREFILL_MODES == ("train", "compact")
-    for mode in infer.PREFILL_MODES:
-        infer.check_prefill(mode)
+    assert infer.MODES["prefill"].values == ("train", "compact")
+    for mode in infer.MODES["prefill"].values:
+        infer.check_mode("prefill", mode)
     with pytest.raises(ValueError, match="prefill"):
         MLA.predict_action_diff(object(), prefill="nonsense")
     with pytest.raises(ValueError, match="prefill"):

@@ -121,40 +121,40 @@ def test_noise_drawn_up_front_is_p_sample_loop_bit_for_bit(respacing, shape):
 
 def test_check_ddpm_sampler():
     from mla_amd import infer
-    assert infer.DDPM_SAMPLER_MODES == ("host", "device")
-    assert infer.SAMPLER_MODES == ("host", "device")
-    infer.check_ddpm_sampler("host")
-    infer.check_ddpm_sampler("host", reuse_prefix=False, use_ddim=True, num_ddim_steps=8)    # the default takes every combination
-    infer.check_ddpm_sampler("device", True, False, 8)
-    infer.check_ddpm_sampler("device", True, True, None)                     # num_ddim_steps=None runs the DDPM loop
+    assert infer.MODES["ddpm_sampler"].values == ("host", "device")
+    assert infer.MODES["sampler"].values == ("host", "device")
+    infer.check_mode("ddpm_sampler", "host")
+    infer.check_mode("ddpm_sampler", "host", reuse_prefix=False, use_ddim=True, num_ddim_steps=8)     # the default takes every combination
+    infer.check_mode("ddpm_sampler", "device", True, False, 8)
+    infer.check_mode("ddpm_sampler", "device", True, True, None)      # num_ddim_steps=None runs the DDPM loop
     for bad in ("bogus", "Device", None, ""):
         with pytest.raises(ValueError, match="ddpm_sampler"):
-            infer.check_ddpm_sampler(bad)
+            infer.check_mode("ddpm_sampler", bad)
     with pytest.raises(ValueError, match="reuse_prefix=True"):
-        infer.check_ddpm_sampler("device", reuse_prefix=False)
+        infer.check_mode("ddpm_sampler", "device", reuse_prefix=False)
     with pytest.raises(ValueError, match="DDIM"):
-        infer.check_ddpm_sampler("device", True, True, 8)
+        infer.check_mode("ddpm_sampler", "device", True, True, 8)
     with pytest.raises(ValueError, match="does not serve"):
-        infer.ddpm_sampler_needs_engine("device", "PrefixCachedEps", 16)
-    infer.ddpm_sampler_needs_engine("host", "PrefixCachedEps", 16)
+        infer.needs_engine("PrefixCachedEps", 16, ddpm_sampler="device")
+    infer.needs_engine("PrefixCachedEps", 16, ddpm_sampler="host")
     with pytest.raises(ValueError, match="DDIM"):                            # sampler= keeps its meaning
-        infer.check_sampler("device", use_ddim=False)
+        infer.check_mode("sampler", "device", use_ddim=False)
 
 
 def test_check_modes_accepts_and_forwards_the_keyword():
-    from mla_amd.mla import MLA
-    base = ("bf16", "train", "host", "head")
-    MLA._check_modes(*base, True, False, 8)                                  # the default: "host"
-    MLA._check_modes(*base, True, False, 8, ddpm_sampler="device")
-    MLA._check_modes(*base, True, True, None, ddpm_sampler="device")
+    from mla_amd.infer import Modes, check_modes
+    base = dict(suffix_weights="bf16", prefill="train", sampler="host", suffix_attention="head")
+    check_modes(Modes(**base), True, False, 8)                               # the default: "host"
+    check_modes(Modes(**base, ddpm_sampler="device"), True, False, 8)
+    check_modes(Modes(**base, ddpm_sampler="device"), True, True, None)
     with pytest.raises(ValueError, match="ddpm_sampler"):
-        MLA._check_modes(*base, True, False, 8, ddpm_sampler="bogus")
+        check_modes(Modes(**base, ddpm_sampler="bogus"), True, False, 8)
     with pytest.raises(ValueError, match="reuse_prefix=True"):
-        MLA._check_modes(*base, False, False, 8, ddpm_sampler="device")
+        check_modes(Modes(**base, ddpm_sampler="device"), False, False, 8)
     with pytest.raises(ValueError, match="DDIM"):
-        MLA._check_modes(*base, True, True, 8, ddpm_sampler="device")
+        check_modes(Modes(**base, ddpm_sampler="device"), True, True, 8)
     with pytest.raises(ValueError, match="DDIM"):                            # sampler="device" on a DDPM call raises as before
-        MLA._check_modes("bf16", "train", "device", "head", True, False, 8, ddpm_sampler="device")
+        check_modes(Modes(suffix_weights="bf16", prefill="train", sampler="device", suffix_attention="head", ddpm_sampler="device"), True, False, 8)
 
 
 def _public_calls():

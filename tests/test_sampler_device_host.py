@@ -76,22 +76,22 @@ def test_eta_other_than_zero_raises():
 
 def test_check_sampler():
     from mla_amd import infer
-    assert infer.SAMPLER_MODES == ("host", "device")
-    infer.check_sampler("host")
-    infer.check_sampler("host", reuse_prefix=False, use_ddim=False, num_ddim_steps=None)     # today's path takes every combination
-    infer.check_sampler("device", True, True, 8)
+    assert infer.MODES["sampler"].values == ("host", "device")
+    infer.check_mode("sampler", "host")
+    infer.check_mode("sampler", "host", reuse_prefix=False, use_ddim=False, num_ddim_steps=None)      # today's path takes every combination
+    infer.check_mode("sampler", "device", True, True, 8)
     for bad in ("bogus", "Device", None, ""):
         with pytest.raises(ValueError, match="sampler"):
-            infer.check_sampler(bad)
+            infer.check_mode("sampler", bad)
     with pytest.raises(ValueError, match="reuse_prefix=True"):
-        infer.check_sampler("device", reuse_prefix=False)
+        infer.check_mode("sampler", "device", reuse_prefix=False)
     with pytest.raises(ValueError, match="DDIM"):
-        infer.check_sampler("device", use_ddim=False)
+        infer.check_mode("sampler", "device", use_ddim=False)
     with pytest.raises(ValueError, match="DDIM"):
-        infer.check_sampler("device", num_ddim_steps=None)
+        infer.check_mode("sampler", "device", num_ddim_steps=None)
     with pytest.raises(ValueError, match="does not serve"):
-        infer.sampler_needs_engine("device", "PrefixCachedEps", 16)
-    infer.sampler_needs_engine("host", "PrefixCachedEps", 16)
+        infer.needs_engine("PrefixCachedEps", 16, sampler="device")
+    infer.needs_engine("PrefixCachedEps", 16, sampler="host")
 
 
 def _public_calls():
