@@ -906,8 +906,10 @@ def attn_bwd(q, k, v, o, dout, lse, seqlens, dq, dk, dv, B, S, H, D, ld_qkv, sca
 
 
 # --------------------------------------------------------------------------------------------- inference (mla_amd/infer.py)
-def _skinny_call(name, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope, w_scale=None):
-    """The shared call of the four suffix projections; w_scale (fp32 [N]) selects the `_w8` argument list (W: float8_e4m3fn)."""
+def _proj_operands(name, x, W, w_scale, out=None):
+    """The operand checks every suffix projection call opens with: x bf16, W bf16 -- or float8_e4m3fn with w_scale (fp32, one per row
+    of W), which selects the `_w8` argument list --, out bf16 where it is given, unit inner strides. Returns the scale argument(s) of
+    the call: () for bf16 weights."""
     _req(x, torch.bfloat16, f"{name} x")
     _req(W, torch.bfloat16 if w_scale is None else torch.float8_e4m3fn, f"{name} W")
     scale_arg = ()
@@ -915,11 +917,19 @@ def _skinny_call(name, x, W, out, ldo, out_batch_stride, rows_per_batch, residua
         _req(w_scale, torch.float32, f"{name} w_scale")
         assert w_scale.numel() == W.shape[0] and w_scale.is_contiguous()
         scale_arg = (_p(w_scale),)
-    _req(out, torch.bfloat16, f"{name} out")
+    if out is not None:
+        _req(out, torch.bfloat16, f"{name} out")
+    assert x.stride(1) == 1 and W.stride(1) == 1
+    return scale_arg
+
+
+def _skinny_call(name, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope, w_scale=None):
+    """The shared call of the four suffix projections; w_scale (fp32 [N]) selects the `_w8` argument list (W: float8_e4m3fn)."""
+    scale_arg = _proj_operands(name, x, W, w_scale, out)
     M = x.shape[0]
     K = x.shape[1] // 2 if swiglu else x.shape[1]
     N = W.shape[0]
-    assert W.shape[1] == K and x.stride(1) == 1 and W.stride(1) == 1 and not (swiglu and norm_weight is not None)
+    assert W.shape[1] == K and not (swiglu and norm_weight is not None)
     pre = 2 if swiglu else (1 if norm_weight is not None else 0)
     if norm_weight is not None:
         _req(norm_weight, torch.bfloat16, f"{name} norm weight")
@@ -996,15 +1006,9 @@ def gemm_skinny_w8(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, re
 def _skinny_gateup_call(name, x, W, out, ldo, w_scale=None):
     """The shared call of the two gate|up + SwiGLU projections: _skinny_call's argument checks without a residual, a rotary epilogue or a
     pre-transform; out [M, I] is allocated when not given (ldo: its row stride in elements, default out.stride(0))."""
-    _req(x, torch.bfloat16, f"{name} x")
-    _req(W, torch.bfloat16 if w_scale is None else torch.float8_e4m3fn, f"{name} W")
-    scale_arg = ()
-    if w_scale is not None:
-        _req(w_scale, torch.float32, f"{name} w_scale")
-        assert w_scale.numel() == W.shape[0] and w_scale.is_contiguous()
-        scale_arg = (_p(w_scale),)
+    scale_arg = _proj_operands(name, x, W, w_scale)
     M, K = x.shape
-    assert W.shape[0] % 2 == 0 and W.shape[1] == K and x.stride(1) == 1 and W.stride(1) == 1
+    assert W.shape[0] % 2 == 0 and W.shape[1] == K
     I = W.shape[0] // 2
     if out is None:
         out = torch.empty((M, I), dtype=torch.bfloat16, device=x.device)
@@ -1131,17 +1135,10 @@ def _suffix_call(sym, name, x, W, out, ldo, out_batch_stride, rows_per_batch, re
                  rope_pos=None, rope_rows=None):
     """The shared call of the two batched suffix projections; w_scale (fp32 [N]) selects the `_w8` argument list (W: float8_e4m3fn),
     rope_pos (int32, one rotary position per sample) the `_pos` entry point."""
-    _req(x, torch.bfloat16, f"{name} x")
-    _req(W, torch.bfloat16 if w_scale is None else torch.float8_e4m3fn, f"{name} W")
-    scale_arg = ()
-    if w_scale is not None:
-        _req(w_scale, torch.float32, f"{name} w_scale")
-        assert w_scale.numel() == W.shape[0] and w_scale.is_contiguous()
-        scale_arg = (_p(w_scale),)
-    _req(out, torch.bfloat16, f"{name} out")
+    scale_arg = _proj_operands(name, x, W, w_scale, out)
     M, K = x.shape
     N = W.shape[0]
-    assert W.shape[1] == K and x.stride(1) == 1 and W.stride(1) == 1
+    assert W.shape[1] == K
     if slot is not None:
         _req(slot, torch.int32, f"{name} slot")
         assert cap_rows is not None and slot.is_contiguous() and slot.numel() * rows_per_batch >= M

@@ -7,38 +7,12 @@ compared bit for bit, workspace states of the split forms included:
                                                                          the 7B sampler shapes (device events around graph replays)
     python tools/exp_suffix_attn_bits.py --pair-libs <a> <b> [--pairs 6] child processes a, b, a, a per round: the paired difference b - a
                                                                          per kernel with its 95 % interval, beside the a - a null's"""
-import argparse, json, math, os, subprocess, sys
+import argparse, json, math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-T95 = {2: 12.706, 3: 4.303, 4: 3.182, 5: 2.776, 6: 2.571, 7: 2.447, 8: 2.365, 9: 2.306, 10: 2.262, 11: 2.228, 12: 2.201}
+from lib_pairing import _us_per_launch, pair_libs
 
-
-def _interval(d):
-    n, mean = len(d), sum(d) / len(d)
-    half = T95.get(n, 1.96) * math.sqrt(sum((x - mean) ** 2 for x in d) / (n - 1) / n) if n > 1 else float("nan")
-    return {"mean": round(mean, 3), "lo": round(mean - half, 3), "hi": round(mean + half, 3)}
-
-
-def pair_libs(lib_a, lib_b, pairs):
-    def child(lib):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--time"], env=dict(os.environ, MLA_HIP_LIB=os.path.abspath(lib)),
-                           capture_output=True, text=True, timeout=300)
-        if r.returncode != 0:
-            sys.exit(f"child on {lib} ended with {r.returncode}: {r.stderr[-800:]}")
-        return json.loads(r.stdout.strip().splitlines()[-1])["us_per_launch"]
-    diff, null, level = {}, {}, {}
-    for _ in range(pairs):
-        a0, b0, a1, a2 = child(lib_a), child(lib_b), child(lib_a), child(lib_a)
-        for k in a0:
-            diff.setdefault(k, []).append(b0[k] - a0[k])
-            null.setdefault(k, []).append(a2[k] - a1[k])
-            level.setdefault(k, []).append(a0[k])
-    table = {k: {"a_us": round(sum(level[k]) / pairs, 2), "b_minus_a": _interval(diff[k]), "a_minus_a": _interval(null[k]),
-                 "b_interval_wholly_above_null": _interval(diff[k])["lo"] > _interval(null[k])["hi"]} for k in diff}
-    print(json.dumps({"metric": "suffix attention, microseconds per launch at the 7B sampler shapes: library b - library a, paired", "unit": "us",
-                      "a": lib_a, "b": lib_b, "pairs": pairs, "table": table, "data": "synthetic"}))
-    return 1 if any(v["b_interval_wholly_above_null"] for v in table.values()) else 0
-
+METRIC = "suffix attention, microseconds per launch at the 7B sampler shapes: library b - library a, paired"
 
 ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
 ap.add_argument("paths", nargs="*", metavar="FILE.pt", help="one path: dump under MLA_HIP_LIB; two paths: compare the dumps")
@@ -49,7 +23,7 @@ args = ap.parse_args()
 if not args.time and not args.pair_libs and len(args.paths) not in (1, 2):
     ap.error("give one path to dump, two to compare, --time or --pair-libs A B")
 if args.pair_libs:
-    sys.exit(pair_libs(args.pair_libs[0], args.pair_libs[1], args.pairs))
+    sys.exit(pair_libs(__file__, METRIC, args.pair_libs[0], args.pair_libs[1], args.pairs))
 
 import torch
 
@@ -121,29 +95,6 @@ def dump_groups(out, H, R, G, S_p, seed, gws=(1, 2, 4)):
             out[name] = _bits(hip.attn_groups_split(c, B, G, H, D, p, R, scale, splits=sp, ws=ws))
             if n > 1:
                 out[name + "_ws"] = ws[:need].view(torch.int32).cpu()
-
-
-def _us_per_launch(fn, caches, window_ms=150.0):
-    """`len(caches)` launches over as many caches per graph; device events around enough replays to fill the window, after warm-up"""
-    for c in caches[:2]:                                                   # function attributes, allocator
-        fn(c)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for c in caches:
-            fn(c)
-
-    def run(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            g.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1)
-    run(3)
-    reps = max(3, int(window_ms / max(run(3) / 3, 1e-3)))
-    return run(reps) / (reps * len(caches)) * 1e3
 
 
 def time_entries(H=32, S_p=547, G=8, layers=32):
