@@ -204,6 +204,19 @@ int mla_adamw_step(float* p, const float* g, float* m, float* v, void* p16, long
  * both AdamW parameter groups of a sharding unit (training/strategies/fsdp.py:231-257) in one launch */
 int mla_adamw_step_groups(float* p, const float* g, float* m, float* v, void* p16, long long n, long long n_decay, float lr, float beta1,
                           float beta2, float eps, float weight_decay, int step, const float* grad_scale, mla_stream_t stream);
+/* ---- weight average (EMA) of the fp32 masters (update_ema, training/strategies/base_strategy_mla.py:33-41: ema.mul_(decay).add_(param,
+ * alpha=1 - decay)). The two steps above with one more fp32 stream ema [n]: after the update, ema = ema_one_minus_decay * p_new +
+ * ema_decay * ema, the product rounded and the sum one fma, on the fp32 master (never the bf16 copy). p, m, v, p16 come out as from
+ * the plain step, bit for bit. The caller forms both factors: decay cast to fp32, 1 - decay formed in double and cast once (the
+ * convention of the bias corrections above). ema == NULL, n < 0 or a factor outside [0, 1]: invalid argument, never a plain step. */
+int mla_adamw_ema_step(float* p, const float* g, float* m, float* v, float* ema, void* p16, long long n, float lr, float beta1,
+                       float beta2, float eps, float weight_decay, int step, const float* grad_scale, float ema_decay,
+                       float ema_one_minus_decay, mla_stream_t stream);
+int mla_adamw_ema_step_groups(float* p, const float* g, float* m, float* v, float* ema, void* p16, long long n, long long n_decay, float lr,
+                              float beta1, float beta2, float eps, float weight_decay, int step, const float* grad_scale,
+                              float ema_decay, float ema_one_minus_decay, mla_stream_t stream);
+/* the same average as a pass of its own, for weights held outside the optimizer: ema = one_minus_decay * p + decay * ema over fp32 [n] */
+int mla_ema_update(float* ema, const float* p, long long n, float decay, float one_minus_decay, mla_stream_t stream);
 int mla_sumsq_f32(const float* x, long long n, float* out, int accumulate, float* workspace, size_t workspace_bytes,
                   mla_stream_t stream);
 /* out[0] (+)= sum(partial[0 .. n)), fixed order: second stage of the gradient norm over mla_gemm_bf16_ws_sq partials */

@@ -734,10 +734,18 @@ __device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v
   m = mm;
   v = vv;
 }
+// One element of the weight average kept next to the master (EMA = true; reference: update_ema,
+// training/strategies/base_strategy_mla.py:33-41, ema.mul_(decay).add_(param, alpha=1 - decay) on the fp32 parameter): e = omd * p + decay * e
+// with p the NEW master, never its bf16 copy. The contraction is spelled out for adamw_elem's reason: the fused launches, the scalar
+// tail and the stand-alone pass must agree bit for bit.
+__device__ __forceinline__ float ema_elem(float e, float p, float decay, float omd) { return fmaf(omd, p, decay * e); }
+// EMA = true: one more fp32 stream `ema`, read and written once per element (mla_adamw_ema_step); false: ema is never touched.
+template <bool EMA>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, bf16_t* __restrict__ p16, long long n, float lr,
                                                     float beta1, float beta2, float eps, float wd, float bc1, float bc2,
-                                                    const float* __restrict__ grad_scale, long long n_decay) {
+                                                    const float* __restrict__ grad_scale, long long n_decay, float* __restrict__ ema,
+                                                    float ema_decay, float ema_omd) {
   const float gs = grad_scale ? *grad_scale : 1.f;
   const float step = lr / bc1, isq = 1.f / sqrtf(bc2);
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
@@ -745,23 +753,26 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     adamw_elem(pp, g[i], mm, vv, gs, i < n_decay ? 1.f - lr * wd : 1.f, beta1, beta2, step, isq, eps);
     p[i] = pp; m[i] = mm; v[i] = vv;
     if (p16) p16[i] = f2bf(pp);
+    if (EMA) ema[i] = ema_elem(ema[i], pp, ema_decay, ema_omd);
   }
 }
 
 // same update, 4 elements per lane per trip (16-B accesses on the seven fp32 streams, 8-B on the bf16 copy): the update is
 // element-wise, so the results are bit-identical to adamw_kernel; n4 = number of whole float4 groups.
-// UNR = float4 groups per lane and trip (all their loads issued before the first use); NT = non-temporal accesses.
-template <int UNR, bool NT>
+// UNR = float4 groups per lane and trip (all their loads issued before the first use); NT = non-temporal accesses; EMA as above (an
+// eighth fp32 stream under the same access policy: it too is touched exactly once per step).
+template <int UNR, bool NT, bool EMA>
 __global__ __launch_bounds__(256) void adamw_vec4_kernel(f32x4_t* __restrict__ p, const f32x4_t* __restrict__ g, f32x4_t* __restrict__ m,
                                                          f32x4_t* __restrict__ v, u32x2_t* __restrict__ p16, long long n4, float lr,
                                                          float beta1, float beta2, float eps, float wd, float bc1, float bc2,
-                                                         const float* __restrict__ grad_scale, long long n4_decay) {
+                                                         const float* __restrict__ grad_scale, long long n4_decay,
+                                                         f32x4_t* __restrict__ ema, float ema_decay, float ema_omd) {
   const float gs = grad_scale ? *grad_scale : 1.f;
   const float step = lr / bc1, isq = 1.f / sqrtf(bc2), decay_on = 1.f - lr * wd;
   const long long chunk = ((((n4) + gridDim.x - 1) / gridDim.x) + 256 * UNR - 1) / (256 * UNR) * (256 * UNR);
   const long long lo = (long long)blockIdx.x * chunk, hi = lo + chunk < n4 ? lo + chunk : n4;
   for (long long i0 = lo + threadIdx.x; i0 < hi; i0 += 256 * UNR) {
-    f32x4_t g4[UNR], p4[UNR], m4[UNR], v4[UNR];
+    f32x4_t g4[UNR], p4[UNR], m4[UNR], v4[UNR], e4[EMA ? UNR : 1];
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       const long long i = i0 + u * 256;
@@ -772,6 +783,7 @@ __global__ __launch_bounds__(256) void adamw_vec4_kernel(f32x4_t* __restrict__ p
         } else {
           g4[u] = g[i]; p4[u] = p[i]; m4[u] = m[i]; v4[u] = v[i];
         }
+        if (EMA) e4[EMA ? u : 0] = NT ? __builtin_nontemporal_load(ema + i) : ema[i];
       }
     }
 #pragma unroll
@@ -791,6 +803,12 @@ __global__ __launch_bounds__(256) void adamw_vec4_kernel(f32x4_t* __restrict__ p
       } else {
         p[i] = p4[u]; m[i] = m4[u]; v[i] = v4[u];
       }
+      if (EMA) {
+        f32x4_t e = e4[EMA ? u : 0];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) e[r] = ema_elem(e[r], p4[u][r], ema_decay, ema_omd);
+        if (NT) __builtin_nontemporal_store(e, ema + i); else ema[i] = e;
+      }
       if (p16) {
         u32x2_t o;
         o[0] = pack2bf(p4[u][0], p4[u][1]);
@@ -799,6 +817,35 @@ __global__ __launch_bounds__(256) void adamw_vec4_kernel(f32x4_t* __restrict__ p
       }
     }
   }
+}
+
+// The weight average as a pass of its own (weights held outside the optimizer; the A/B arm that prices the fusion above): the same
+// capped grid and chunked walk over the n4 whole float4 groups, non-temporal (both streams are touched once).
+__global__ __launch_bounds__(256) void ema_vec4_kernel(f32x4_t* __restrict__ ema, const f32x4_t* __restrict__ p, long long n4, float decay,
+                                                       float omd) {
+  constexpr int UNR = 4;
+  const long long chunk = ((((n4) + gridDim.x - 1) / gridDim.x) + 256 * UNR - 1) / (256 * UNR) * (256 * UNR);
+  const long long lo = (long long)blockIdx.x * chunk, hi = lo + chunk < n4 ? lo + chunk : n4;
+  for (long long i0 = lo + threadIdx.x; i0 < hi; i0 += 256 * UNR) {
+    f32x4_t p4[UNR], e4[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const long long i = i0 + u * 256;
+      if (i < hi) { p4[u] = __builtin_nontemporal_load(p + i); e4[u] = __builtin_nontemporal_load(ema + i); }
+    }
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const long long i = i0 + u * 256;
+      if (i >= hi) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) e4[u][r] = ema_elem(e4[u][r], p4[u][r], decay, omd);
+      __builtin_nontemporal_store(e4[u], ema + i);
+    }
+  }
+}
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, long long n, float decay, float omd) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+    ema[i] = ema_elem(ema[i], p[i], decay, omd);
 }
 
 // partial[blockIdx] = sum of squares of this block's slice (deterministic two-stage grad-norm); 16-B loads
@@ -1076,20 +1123,27 @@ static int adamw_grid_cap() {
   static const int cap = getenv("MLA_ADAMW_BLOCKS") ? atoi(getenv("MLA_ADAMW_BLOCKS")) : 8192;
   return cap;
 }
+// EMA = true: the launches carry the weight average `ema` (mla_adamw_ema_step*); false: the plain launches, ema unused.
+template <bool EMA>
 static int adamw_impl(float* p, const float* g, float* m, float* v, void* p16, long long n, long long n_decay, float lr, float beta1,
-                      float beta2, float eps, float weight_decay, int step, const float* grad_scale, hipStream_t stream) {
+                      float beta2, float eps, float weight_decay, int step, const float* grad_scale, hipStream_t stream,
+                      float* ema = nullptr, float ema_decay = 0.f, float ema_omd = 0.f) {
   MLA_CHECK_ARG(p && g && m && v && n >= 0 && step >= 1 && n_decay >= 0 && n_decay <= n, "mla_adamw_step: bad args");
+  if (EMA)
+    MLA_CHECK_ARG(ema && ema_decay >= 0.f && ema_decay <= 1.f && ema_omd >= 0.f && ema_omd <= 1.f,
+                  "mla_adamw_ema_step: ema is null or a decay outside [0, 1]");
   if (n == 0) return 0;
   // formed in double and cast once: in fp32, 1 - beta2^step cancels at small step numbers (beta2 = 0.999, step 2: the correction was
   // off by 112 x 2^-24, the update by half that -- tests/test_trunk_cases_host.py); torch.optim.AdamW and the host backend use double too
   const float bc1 = (float)(1.0 - pow((double)beta1, step)), bc2 = (float)(1.0 - pow((double)beta2, step));
   // (the decay boundary must not cut a 16-B group: otherwise everything goes through the scalar kernel)
-  const long long n4 = (AL16(p) && AL16(g) && AL16(m) && AL16(v) && (p16 == nullptr || ((uintptr_t)p16 & 7) == 0) && (n_decay & 3) == 0) ? n / 4 : 0;
+  const long long n4 = (AL16(p) && AL16(g) && AL16(m) && AL16(v) && (!EMA || AL16(ema)) && (p16 == nullptr || ((uintptr_t)p16 & 7) == 0) && (n_decay & 3) == 0) ? n / 4 : 0;
   if (n4) {
     static const int variant = getenv("MLA_ADAMW_VARIANT") ? atoi(getenv("MLA_ADAMW_VARIANT")) : 0;   // A/B only (tools/bench_adamw.py)
     const dim3 grid(grid_for(n4, adamw_grid_cap()));
-#define ADAMW_LAUNCH(U, N) hipLaunchKernelGGL((adamw_vec4_kernel<U, N>), grid, dim3(256), 0, stream, (f32x4_t*)p, (const f32x4_t*)g, (f32x4_t*)m, \
-                       (f32x4_t*)v, (u32x2_t*)p16, n4, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, n_decay / 4)
+#define ADAMW_LAUNCH(U, N) hipLaunchKernelGGL((adamw_vec4_kernel<U, N, EMA>), grid, dim3(256), 0, stream, (f32x4_t*)p, (const f32x4_t*)g, (f32x4_t*)m, \
+                       (f32x4_t*)v, (u32x2_t*)p16, n4, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, n_decay / 4,                    \
+                       (f32x4_t*)ema, ema_decay, ema_omd)
     // default: four float4 groups per lane and trip, non-temporal (stand-alone 6.20-6.29 TB/s vs 5.99-6.15 with one group, same box,
     // alternating; plain accesses 5.9-6.0) -- tools/ab_adamw.sh
     if (variant == 1) ADAMW_LAUNCH(2, true);
@@ -1101,15 +1155,15 @@ static int adamw_impl(float* p, const float* g, float* m, float* v, void* p16, l
   }
   const long long done = n4 * 4;
   if (done < n)
-    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n - done, 8192)), dim3(256), 0, stream, p + done, g + done, m + done, v + done,
+    hipLaunchKernelGGL(adamw_kernel<EMA>, dim3(grid_for(n - done, 8192)), dim3(256), 0, stream, p + done, g + done, m + done, v + done,
                        p16 ? (bf16_t*)p16 + done : (bf16_t*)nullptr, n - done, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale,
-                       n_decay > done ? n_decay - done : 0);
+                       n_decay > done ? n_decay - done : 0, EMA ? ema + done : (float*)nullptr, ema_decay, ema_omd);
   MLA_LAUNCH_CHECK();
 }
 extern "C" int mla_adamw_step(float* p, const float* g, float* m, float* v, void* p16, long long n, float lr, float beta1,
                               float beta2, float eps, float weight_decay, int step, const float* grad_scale,
                               hipStream_t stream) {
-  return adamw_impl(p, g, m, v, p16, n, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream);
+  return adamw_impl<false>(p, g, m, v, p16, n, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream);
 }
 // One launch for a flat parameter range laid out [weight-decayed | not decayed] (FlatUnit: matrices first, then norm weights and
 // biases): elements [0, n_decay) get `weight_decay`, the rest none -- the reference's two AdamW parameter groups
@@ -1117,7 +1171,38 @@ extern "C" int mla_adamw_step(float* p, const float* g, float* m, float* v, void
 extern "C" int mla_adamw_step_groups(float* p, const float* g, float* m, float* v, void* p16, long long n, long long n_decay, float lr,
                                      float beta1, float beta2, float eps, float weight_decay, int step, const float* grad_scale,
                                      hipStream_t stream) {
-  return adamw_impl(p, g, m, v, p16, n, n_decay, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream);
+  return adamw_impl<false>(p, g, m, v, p16, n, n_decay, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream);
+}
+// The two entry points above with the weight average folded in: after the update, ema = ema_one_minus_decay * p_new + ema_decay * ema on
+// the fp32 master (8 B per parameter on top of the step's 30, instead of the 12 B of a pass of its own). ema: fp32 [n]; it joins the
+// alignment test of the 16-byte kernel. Both factors come from the caller (1 - decay formed in double and cast once).
+extern "C" int mla_adamw_ema_step(float* p, const float* g, float* m, float* v, float* ema, void* p16, long long n, float lr, float beta1,
+                                  float beta2, float eps, float weight_decay, int step, const float* grad_scale, float ema_decay,
+                                  float ema_one_minus_decay, hipStream_t stream) {
+  return adamw_impl<true>(p, g, m, v, p16, n, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream, ema, ema_decay,
+                          ema_one_minus_decay);
+}
+extern "C" int mla_adamw_ema_step_groups(float* p, const float* g, float* m, float* v, float* ema, void* p16, long long n, long long n_decay,
+                                         float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                         const float* grad_scale, float ema_decay, float ema_one_minus_decay, hipStream_t stream) {
+  return adamw_impl<true>(p, g, m, v, p16, n, n_decay, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream, ema, ema_decay,
+                          ema_one_minus_decay);
+}
+// ema = one_minus_decay * p + decay * ema over fp32 [n], the same arithmetic as a pass of its own: 16-byte accesses where both
+// pointers allow them, a scalar tail (or the scalar kernel for everything)
+extern "C" int mla_ema_update(float* ema, const float* p, long long n, float decay, float one_minus_decay, hipStream_t stream) {
+  MLA_CHECK_ARG(ema && p && n >= 0 && decay >= 0.f && decay <= 1.f && one_minus_decay >= 0.f && one_minus_decay <= 1.f,
+                "mla_ema_update: null pointer, n < 0 or a decay outside [0, 1]");
+  if (n == 0) return 0;
+  const long long n4 = (AL16(ema) && AL16(p)) ? n / 4 : 0;
+  if (n4)
+    hipLaunchKernelGGL(ema_vec4_kernel, dim3(grid_for(n4, adamw_grid_cap())), dim3(256), 0, stream, (f32x4_t*)ema, (const f32x4_t*)p, n4,
+                       decay, one_minus_decay);
+  const long long done = n4 * 4;
+  if (done < n)
+    hipLaunchKernelGGL(ema_kernel, dim3(grid_for(n - done, 8192)), dim3(256), 0, stream, ema + done, p + done, n - done, decay,
+                       one_minus_decay);
+  MLA_LAUNCH_CHECK();
 }
 
 // out[0] (+)= sum(x^2); workspace >= 2048 floats

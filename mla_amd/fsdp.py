@@ -41,6 +41,17 @@ class HipLocalOps:
     def adamw_groups(self, p32, g32, m, v, p16, n_decay, lr, betas, eps, wd, step, grad_scale):
         self.hip.adamw_step_groups(p32, g32, m, v, p16, n_decay, lr, betas[0], betas[1], eps, wd, step, grad_scale)
 
+    # the two steps above with the weight average folded in (ema = (1 - ema_decay) * p_new + ema_decay * ema), and the average as a
+    # pass of its own
+    def adamw_ema(self, p32, g32, m, v, ema, p16, lr, betas, eps, wd, step, grad_scale, ema_decay):
+        self.hip.adamw_ema_step(p32, g32, m, v, ema, p16, lr, betas[0], betas[1], eps, wd, step, grad_scale, ema_decay)
+
+    def adamw_ema_groups(self, p32, g32, m, v, ema, p16, n_decay, lr, betas, eps, wd, step, grad_scale, ema_decay):
+        self.hip.adamw_ema_step_groups(p32, g32, m, v, ema, p16, n_decay, lr, betas[0], betas[1], eps, wd, step, grad_scale, ema_decay)
+
+    def ema_update(self, ema, p32, decay):
+        self.hip.ema_update(ema, p32, decay)
+
     def sumsq(self, x32, out1, accumulate):
         self.hip.sumsq(x32, out1, accumulate)
 
@@ -210,7 +221,8 @@ class FlatUnit:
 
     def __init__(self, name: str, named_params: Sequence[Tuple[str, nn.Parameter]], device, world: int, rank: int, ops,
                  no_decay: Callable[[str, nn.Parameter], bool], process_group=None, sync_from_rank0: bool = True,
-                 collectives: Optional[bool] = None, inplace_reduce: bool = False, arenas: Optional["_Arenas"] = None):
+                 collectives: Optional[bool] = None, inplace_reduce: bool = False, arenas: Optional["_Arenas"] = None,
+                 with_ema: bool = False):
         self.name, self.world, self.rank, self.ops, self.device = name, world, rank, ops, device
         # buffers come from per-kind arenas when the owner provides them (ShardedModel), else from torch one by one
         def take(kind, n, dtype):
@@ -258,6 +270,11 @@ class FlatUnit:
                 self.gshard = take("gshard", self.shard_train, torch.float32)
             self.exp_avg = take("exp_avg", self.shard_train, torch.float32)
             self.exp_avg_sq = take("exp_avg_sq", self.shard_train, torch.float32)
+            if with_ema:
+                # weight average of the trainable masters (ShardedModel ema_decay): starts as a copy of this rank's master shard,
+                # padding 0 like the master's -- and (1 - d) * 0 + d * 0 keeps it 0. Units without it have no such attribute.
+                self.ema = take("ema", self.shard_train, torch.float32)
+                self.ema.copy_(self.master_train[:self.shard_train])
         # ---- re-point the module parameters at the bf16 compute storage; install fp32 main_grad views
         # gradient-norm partials delivered by the wgrad GEMM epilogues (ops._gemm_into_main_grad): offset -> (numel, partials, count).
         # Only without collectives: under FSDP the norm is taken over the REDUCED shards, which no local epilogue has seen.
@@ -403,6 +420,8 @@ class FlatUnit:
         n = self.flat16.numel() * 2 + (self.master_train.numel() + self.master_frozen.numel()) * 4
         if self.trainable:
             n += self.grad32.numel() * 4 + (self.exp_avg.numel() + self.exp_avg_sq.numel()) * 4
+            if hasattr(self, "ema"):
+                n += self.ema.numel() * 4
             if self.gshard is not self.grad32 and not self.inplace_reduce:
                 n += self.gshard.numel() * 4
         return n
@@ -413,7 +432,10 @@ class ShardedModel:
 
     def __init__(self, model: nn.Module, unit_policy: Callable[[nn.Module], bool], device, ops=None,
                  process_group=None, no_decay: Optional[Callable[[str, nn.Parameter], bool]] = None,
-                 inplace_reduce: Optional[bool] = None):
+                 inplace_reduce: Optional[bool] = None, ema_decay: Optional[float] = None, ema_update_every: int = 1):
+        """ema_decay (None: off, nothing changes): keep an exponential moving average of every TRAINABLE fp32 master, sharded like
+        the AdamW moments (FlatUnit.ema), advanced inside the AdamW launch of every ``ema_update_every``-th optimizer step
+        (reference: update_ema, training/strategies/base_strategy_mla.py:33-41). Frozen parameters have none: theirs is their value."""
         self.model, self.device = model, device
         self.pg = process_group
         import os
@@ -423,6 +445,18 @@ class ShardedModel:
         # used to validate the collective plumbing on a single-GPU box
         self.coll = self.world > 1 or (os.environ.get("MLA_FORCE_COLLECTIVES") == "1" and dist.is_available() and dist.is_initialized())
         self.ops = ops if ops is not None else HipLocalOps()
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_update_every = int(ema_update_every)
+        self.ema_updates = 0          # optimizer steps that advanced the average
+        self._ema_swapped = False     # inside ema_weights()
+        if self.ema_decay is not None:
+            if not 0.0 <= self.ema_decay <= 1.0:
+                raise ValueError(f"ema_decay must lie in [0, 1], got {ema_decay}")
+            if self.ema_update_every < 1:
+                raise ValueError(f"ema_update_every must be >= 1, got {ema_update_every}")
+            lacking = [m for m in ("adamw_ema", "adamw_ema_groups", "ema_update") if not hasattr(self.ops, m)]
+            if lacking:      # never a run that quietly keeps no average
+                raise TypeError(f"ema_decay is set but {type(self.ops).__name__} lacks {', '.join(lacking)}")
         # RCCL: in-place SUM reduce-scatter, mean folded into the scales (see FlatUnit). gloo (CPU tests) keeps separate mean shards.
         # (inplace_reduce=True with gloo is for the CPU tests: it runs the same SUM-shard bookkeeping over an in-place all-reduce)
         # MLA_FSDP_INPLACE_RS=0: back to an out-of-place reduce-scatter into separate shard buffers (the round-2 layout; a SUM like the
@@ -458,6 +492,10 @@ class ShardedModel:
                 sizes["exp_avg_sq"] += n_train // self.world
                 if self.coll and not self.inplace_reduce:
                     sizes["gshard"] += n_train // self.world
+                if self.ema_decay is not None:
+                    sizes["ema"] = sizes.get("ema", 0) + n_train // self.world
+            if self.ema_decay is not None and "exp_avg" in kinds:
+                kinds = kinds + ["ema"]      # an eighth stream of the AdamW pass: placed like the moments, and switched with them
             self._arenas = _Arenas({k: v for k, v in sizes.items() if k in kinds}, device, slices=2 * len(found))
         for name, mod, named in found:
             self._add_unit(name, mod, named, no_decay)
@@ -512,7 +550,7 @@ class ShardedModel:
         if not named:
             return
         u = FlatUnit(name, named, self.device, self.world, self.rank, self.ops, no_decay, self.pg, collectives=self.coll,
-                     inplace_reduce=self.inplace_reduce, arenas=self._arenas)
+                     inplace_reduce=self.inplace_reduce, arenas=self._arenas, with_ema=self.ema_decay is not None)
         u.module = mod
         self.units.append(u)
 
@@ -666,7 +704,14 @@ class ShardedModel:
         return self._norm
 
     def optimizer_step(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
+        if self._ema_swapped:
+            raise RuntimeError("optimizer_step inside ema_weights(): the bf16 replica holds the average, not the weights")
         self.step_count += 1
+        # an EMA step runs the same launches over the same ranges with the average as one more stream; every other step (and every
+        # step without ema_decay) runs exactly the plain launches
+        ema_step = self.ema_decay is not None and self.step_count % self.ema_update_every == 0
+        if ema_step:
+            self.ema_updates += 1
 
         for u in self.units:
             if not u.trainable:
@@ -679,13 +724,23 @@ class ShardedModel:
                 n_local = ranges[-1][1]
                 n_dec = sum(le - ls for ls, le, _, dec in ranges if dec)
                 g0 = ranges[0][2]
-                self.ops.adamw_groups(u.master_train[:n_local], u.gshard[:n_local], u.exp_avg[:n_local], u.exp_avg_sq[:n_local],
-                                      u.flat16[g0:g0 + n_local], n_dec, lr, betas, eps, weight_decay, self.step_count, self._coef)
+                if ema_step:
+                    self.ops.adamw_ema_groups(u.master_train[:n_local], u.gshard[:n_local], u.exp_avg[:n_local], u.exp_avg_sq[:n_local],
+                                              u.ema[:n_local], u.flat16[g0:g0 + n_local], n_dec, lr, betas, eps, weight_decay,
+                                              self.step_count, self._coef, self.ema_decay)
+                else:
+                    self.ops.adamw_groups(u.master_train[:n_local], u.gshard[:n_local], u.exp_avg[:n_local], u.exp_avg_sq[:n_local],
+                                          u.flat16[g0:g0 + n_local], n_dec, lr, betas, eps, weight_decay, self.step_count, self._coef)
             else:
                 for ls, le, g0, decayed in ranges:
-                    self.ops.adamw(u.master_train[ls:le], u.gshard[ls:le], u.exp_avg[ls:le], u.exp_avg_sq[ls:le],
-                                   u.flat16[g0:g0 + (le - ls)], lr, betas, eps, weight_decay if decayed else 0.0, self.step_count,
-                                   self._coef)
+                    if ema_step:
+                        self.ops.adamw_ema(u.master_train[ls:le], u.gshard[ls:le], u.exp_avg[ls:le], u.exp_avg_sq[ls:le], u.ema[ls:le],
+                                           u.flat16[g0:g0 + (le - ls)], lr, betas, eps, weight_decay if decayed else 0.0,
+                                           self.step_count, self._coef, self.ema_decay)
+                    else:
+                        self.ops.adamw(u.master_train[ls:le], u.gshard[ls:le], u.exp_avg[ls:le], u.exp_avg_sq[ls:le],
+                                       u.flat16[g0:g0 + (le - ls)], lr, betas, eps, weight_decay if decayed else 0.0, self.step_count,
+                                       self._coef)
             if self.coll:
                 if self.on_gpu:
                     ev = torch.cuda.Event()
@@ -813,6 +868,137 @@ class ShardedModel:
                 for dst, src in zip((u.exp_avg, u.exp_avg_sq), state[n]):
                     dst[a - lo:b - lo].copy_(src.detach().reshape(-1)[a - o:b - o])
         self.step_count = int(step_count)
+
+    # ------------------------------------------------------------------------------------------ weight average (EMA)
+    def _require_ema(self, what: str) -> None:
+        if self.ema_decay is None:
+            raise RuntimeError(f"{what} needs a ShardedModel built with ema_decay (this one keeps no weight average)")
+
+    def _gather_ema(self, u: FlatUnit):
+        if not self.coll:
+            return u.ema
+        parts = [torch.empty(u.shard_train, dtype=torch.float32, device=self.device) for _ in range(self.world)]
+        dist.all_gather(parts, u.ema, group=self.pg)
+        return torch.cat(parts)
+
+    def iter_ema_state(self, to_cpu_on_rank0: bool = False):
+        """Twin of ``iter_optimizer_state`` for the weight average: yields ``(name, fp32 tensor in the parameter's shape)`` for every
+        TRAINABLE parameter, one unit at a time (every rank takes part in the gathers), padding dropped. With ``to_cpu_on_rank0`` only
+        rank 0 receives (host) tensors, the other ranks ``(name, None)``."""
+        self._require_ema("iter_ema_state")
+        if self.on_gpu:
+            self.wait_all()
+        keep = (not to_cpu_on_rank0) or self.rank == 0
+        for u in self.units:
+            if not u.trainable:
+                continue
+            e = self._gather_ema(u)
+            for n, p, o in u.params:
+                if not p.requires_grad:
+                    continue
+                if not keep:
+                    yield n, None
+                    continue
+                t = e[o:o + p.numel()].view(p.shape)
+                yield (n, t.cpu()) if (to_cpu_on_rank0 and t.is_cuda) else (n, t.clone())
+            del e
+
+    def load_ema_state(self, state, ema_updates: int) -> None:
+        """Inverse of ``iter_ema_state``, twin of ``load_optimizer_state``: ``state`` maps parameter name -> FULL fp32 tensor (host or
+        device); every rank copies its own slice of every unit (padding = 0) and ``ema_updates`` is restored. Keyed by name: loads at
+        any world size. Everything is validated BEFORE the first write: a missing name, an unknown name or a shape mismatch raises
+        ValueError and leaves the average as it was."""
+        self._require_ema("load_ema_state")
+        want = {n: p for u in self.units if u.trainable for n, p, _ in u.params if p.requires_grad}
+        missing = [n for n in want if n not in state]
+        extra = [n for n in state if n not in want]
+        bad = []
+        for n, p in want.items():
+            if n in state:
+                t = state[n]
+                if not torch.is_tensor(t):
+                    bad.append(f"{n} (not a tensor)")
+                elif tuple(t.shape) != tuple(p.shape):
+                    bad.append(f"{n} {tuple(t.shape)} != {tuple(p.shape)}")
+        if missing or extra or bad:
+            raise ValueError("EMA state does not match the model's trainable parameters: "
+                             + "; ".join(f"{k}: {', '.join(v)}" for k, v in (("missing", missing), ("unexpected", extra), ("wrong shape", bad)) if v))
+        if self.on_gpu:
+            self.wait_all()
+        for u in self.units:
+            if not u.trainable:
+                continue
+            lo = self.rank * u.shard_train
+            hi = lo + u.shard_train
+            u.ema.zero_()
+            for n, p, o in u.params:
+                if not p.requires_grad:
+                    continue
+                a, b = max(o, lo), min(o + p.numel(), hi)
+                if b > a:
+                    u.ema[a - lo:b - lo].copy_(state[n].detach().reshape(-1)[a - o:b - o])
+        self.ema_updates = int(ema_updates)
+
+    def reset_ema(self) -> None:
+        """The average restarts as a copy of the masters, as at construction; ``ema_updates`` = 0."""
+        self._require_ema("reset_ema")
+        if self.on_gpu:
+            self.wait_all()
+        for u in self.units:
+            if u.trainable:
+                u.ema.copy_(u.master_train[:u.shard_train])
+        self.ema_updates = 0
+
+    def _swap_replica(self, from_ema: bool) -> None:
+        """bf16 replica of every trainable parameter <- bf16(average) or bf16(master): the local shard through the cast the units were
+        built with, then the unit's all-gather. The optimizer's writes into the replica go through raw pointers and leave the
+        parameters' version counters alone (nothing in optimizer_step touches them), so the counters are advanced here: copies keyed
+        on (data_ptr, _version) -- mla_amd/infer.py's packed and FP8 weights and its captured graphs -- rebuild after either swap."""
+        if self.on_gpu:
+            self.wait_all()
+        for u in self.units:
+            if not u.trainable:
+                continue
+            lo = self.rank * u.shard_train
+            self.ops.cast_to_bf16(u.ema if from_ema else u.master_train[:u.shard_train], u.flat16[lo:lo + u.shard_train])
+            if self.coll:
+                if self.on_gpu:
+                    ev = torch.cuda.Event()
+                    ev.record(torch.cuda.current_stream(self.device))
+                    with torch.cuda.stream(self.comm_stream):
+                        self.comm_stream.wait_event(ev)
+                        self._all_gather(u)
+                        u.gather_event = torch.cuda.Event()
+                        u.gather_event.record(self.comm_stream)
+                else:
+                    self._all_gather(u)
+            for _, p, _ in u.params:
+                if p.requires_grad:
+                    torch.autograd.graph.increment_version(p)
+        if self.on_gpu:
+            self.wait_all()
+
+    def ema_weights(self):
+        """Context manager: inside, the bf16 replica of every trainable parameter holds bf16(average) -- evaluate or sample from the
+        averaged policy; on exit it is cast back from the masters, bit-identical to what it held before (the cast equals AdamW's fused
+        bf16 write). Masters, moments and the average itself are not touched. Raises inside an open accumulation window and on re-entry."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def swapped():
+            self._require_ema("ema_weights")
+            if self._ema_swapped:
+                raise RuntimeError("ema_weights() is already open")
+            if self.defer_reduce:
+                raise RuntimeError("ema_weights() inside an open accumulation window: finish the window's last micro-batch first")
+            self._ema_swapped = True
+            try:
+                self._swap_replica(from_ema=True)
+                yield self
+            finally:
+                self._swap_replica(from_ema=False)
+                self._ema_swapped = False
+        return swapped()
 
     def state_bytes(self):
         return sum(u.state_bytes() for u in self.units)

@@ -151,6 +151,11 @@ _SIGNATURES = {
                               c_float, c_int, c_void_p, c_void_p],
     "mla_adamw_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_float, c_float, c_float, c_float,
                        c_float, c_int, c_void_p, c_void_p],
+    "mla_adamw_ema_step_groups": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_longlong, c_float, c_float,
+                                  c_float, c_float, c_float, c_int, c_void_p, c_float, c_float, c_void_p],
+    "mla_adamw_ema_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_float, c_float, c_float, c_float,
+                           c_float, c_int, c_void_p, c_float, c_float, c_void_p],
+    "mla_ema_update": [c_void_p, c_void_p, c_longlong, c_float, c_float, c_void_p],
     "mla_sumsq_f32": [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_size_t, c_void_p],
     "mla_clip_coef": [c_void_p, c_float, c_void_p, c_void_p, c_void_p],
     "mla_q_sample": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
@@ -740,6 +745,42 @@ def adamw_step_groups(p32, g32, m, v, p16, n_decay, lr, beta1, beta2, eps, wd, s
     """adamw_step over a flat range laid out [decayed | not decayed]: weight decay on the first n_decay elements only."""
     call("mla_adamw_step_groups", _p(p32), _p(g32), _p(m), _p(v), _p(p16), p32.numel(), int(n_decay), float(lr), float(beta1), float(beta2),
          float(eps), float(wd), int(step), _p(grad_scale))
+
+
+def ema_factors(decay):
+    """(decay, 1 - decay) as the library takes them: decay cast to fp32, 1 - decay formed in double and cast once (the convention of
+    the bias corrections, include/mla_hip.h). ctypes rounds a Python float to fp32 the same way."""
+    d = float(decay)
+    if not 0.0 <= d <= 1.0:
+        raise ValueError(f"ema decay must lie in [0, 1], got {decay}")
+    return d, 1.0 - d
+
+
+def adamw_ema_step(p32, g32, m, v, ema, p16, lr, beta1, beta2, eps, wd, step, grad_scale, ema_decay):
+    """adamw_step that also advances the weight average: ema = (1 - ema_decay) * p_new + ema_decay * ema on the fp32 master."""
+    _req(ema, torch.float32, "adamw_ema_step ema")
+    assert ema.numel() == p32.numel() and ema.is_contiguous()
+    d, omd = ema_factors(ema_decay)
+    call("mla_adamw_ema_step", _p(p32), _p(g32), _p(m), _p(v), _p(ema), _p(p16), p32.numel(), float(lr), float(beta1), float(beta2),
+         float(eps), float(wd), int(step), _p(grad_scale), d, omd)
+
+
+def adamw_ema_step_groups(p32, g32, m, v, ema, p16, n_decay, lr, beta1, beta2, eps, wd, step, grad_scale, ema_decay):
+    """adamw_step_groups that also advances the weight average (see adamw_ema_step)."""
+    _req(ema, torch.float32, "adamw_ema_step_groups ema")
+    assert ema.numel() == p32.numel() and ema.is_contiguous()
+    d, omd = ema_factors(ema_decay)
+    call("mla_adamw_ema_step_groups", _p(p32), _p(g32), _p(m), _p(v), _p(ema), _p(p16), p32.numel(), int(n_decay), float(lr), float(beta1),
+         float(beta2), float(eps), float(wd), int(step), _p(grad_scale), d, omd)
+
+
+def ema_update(ema, p32, decay):
+    """ema = (1 - decay) * p32 + decay * ema, fp32, in place: the weight average as a pass of its own."""
+    _req(ema, torch.float32, "ema_update ema")
+    _req(p32, torch.float32, "ema_update p32")
+    assert ema.numel() == p32.numel() and ema.is_contiguous() and p32.is_contiguous()
+    d, omd = ema_factors(decay)
+    call("mla_ema_update", _p(ema), _p(p32), p32.numel(), d, omd)
 
 
 def sumsq(x32, out1, accumulate):

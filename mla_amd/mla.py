@@ -34,7 +34,8 @@ class MLA(nn.Module):
         self.all_module_keys = ["vlm." + k for k in self.vlm.all_module_keys]
         if use_ema:
             raise NotImplementedError("use_ema is non-functional in the reference (no ema_diffusion is ever built, "
-                                      "model_mla.py:47-97, 305-309); keep it False")
+                                      "model_mla.py:47-97, 305-309); keep it False. A weight average of the trainable parameters "
+                                      "is a strategy option here: FSDPStrategy(ema_decay=0.9999)")
         self.use_ema = use_ema
         self.norm_stats = norm_stats
         self._trainable_module_keys: List[str] = []

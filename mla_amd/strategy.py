@@ -33,7 +33,8 @@ class FSDPStrategy:
                  enable_mixed_precision_training: bool = True, reduce_in_full_precision: bool = True,
                  repeated_diffusion_steps: int = 4, cast_forward_inputs: bool = True, local_ops=None,
                  mixed_precision_dtype: torch.dtype = torch.bfloat16, worker_init_fn=None, requires_cliploss: bool = False,
-                 sharding_strategy: str = "full-shard", save_optimizer_state: bool = False, **_):
+                 sharding_strategy: str = "full-shard", save_optimizer_state: bool = False, ema_decay: Optional[float] = None,
+                 ema_update_every: int = 1, **_):
         """Constructor arguments of the reference's FSDPStrategy (training/strategies/fsdp.py:47-96) -- get_train_strategy passes
         them through unchanged. `sharding_strategy` "full-shard" and "shard-grad-op" run the same schedule here: bf16 weights stay
         replicated between the optimizer step and the next use (13.5 GB of 288 GB), master weights / gradients / AdamW moments are
@@ -79,12 +80,18 @@ class FSDPStrategy:
         # opt-in: save_checkpoint also writes `<stem>-optimizer.pt` (AdamW moments, step counters, generator states) so that a run can
         # be continued bit for bit; off by default as in the reference, whose write side is commented out
         self.save_optimizer_state = bool(save_optimizer_state)
+        # opt-in: an exponential moving average of every trainable fp32 master, advanced inside the AdamW launch (the reference's
+        # cfg.use_ema / update_ema(decay=0.9999), base_strategy_mla.py:33-41, whose call site points at modules MLA never builds;
+        # here the VLM is the epsilon model, so the average covers every trainable parameter). None = off: nothing changes. Both may
+        # also be set as attributes before run_setup() (get_train_strategy keeps the reference's signature).
+        self.ema_decay, self.ema_update_every = ema_decay, ema_update_every
 
     def run_setup(self, n_train_examples: int = 0, run_dir=None) -> None:
         """fsdp.py:176-306: shard, (checkpointing), AdamW groups (no decay on <2-D / bias), LR schedule."""
         if self.enable_gradient_checkpointing:
             self.vlm.llm_backbone.enable_gradient_checkpointing()
-        self.sharded = ShardedModel(self.vlm, self.vlm.get_fsdp_wrapping_policy(), self.device, ops=self.local_ops)
+        self.sharded = ShardedModel(self.vlm, self.vlm.get_fsdp_wrapping_policy(), self.device, ops=self.local_ops,
+                                    ema_decay=self.ema_decay, ema_update_every=self.ema_update_every)
         n = math.ceil(max(n_train_examples, 1) / self.global_batch_size) * self.global_batch_size
         self.num_training_steps = self.max_steps if self.max_steps is not None else (n * self.epochs) // self.global_batch_size
         if self.lr_scheduler_type == "linear-warmup+cosine-decay":
@@ -169,8 +176,9 @@ class FSDPStrategy:
         Same control flow: an "infinite" DataLoader over the IterableDataset (batch = per_device_batch_size, the given collator,
         num_workers 0), one `train_step` per batch, metric commits with the reference's seven loss keys, an optimizer step every
         grad_accumulation_steps batches followed by the epoch / lr / step-time commit and `metrics.push()`, a checkpoint at
-        max_steps or at every `save_interval`-th epoch boundary, termination after `epochs` passes. Not reproduced: tqdm, EMA of the
-        (absent) DiT action model, and the non-diffusion branch (dead in the reference: SURVEY Appendix A #15)."""
+        max_steps or at every `save_interval`-th epoch boundary, termination after `epochs` passes. Not reproduced: tqdm, the
+        update_ema call on the (absent) DiT action model -- with `ema_decay` set the average of every trainable parameter advances
+        inside the optimizer step instead --, and the non-diffusion branch (dead in the reference: SURVEY Appendix A #15)."""
         from torch.utils.data import DataLoader, IterableDataset
         assert isinstance(vla_dataset, IterableDataset), "VLA training expects an IterableDataset!"
         if not use_diff:
@@ -240,6 +248,20 @@ class FSDPStrategy:
         self.sharded.load_optimizer_state({n: (d["exp_avg"], d["exp_avg_sq"]) for n, d in blob["state"].items()}, int(blob["step_count"]))
         self.step = int(blob["step"])
         self._micro = 0
+        # the weight average: restored when both sides have one (the resume is then bit-exact in the average too); every other
+        # combination is said aloud, and the current run's settings win as for the other hyper-parameters
+        ema_on, ema_saved = self.sharded.ema_decay is not None, "ema" in blob
+        if ema_on and ema_saved:
+            self.sharded.load_ema_state(dict(blob["ema"]), int(blob["ema_updates"]))
+            saved, mine_ema = (blob.get("ema_decay"), blob.get("ema_update_every")), (self.sharded.ema_decay, self.sharded.ema_update_every)
+            if saved != mine_ema:
+                warnings.warn(f"optimizer checkpoint kept its weight average with (decay, update_every) = {saved}, this run uses {mine_ema}: "
+                              "the current values are used")
+        elif ema_on:
+            warnings.warn(f"{opt} holds no weight average (EMA): it restarts from the loaded master weights")
+            self.sharded.reset_ema()
+        elif ema_saved:
+            warnings.warn(f"{opt} holds a weight average (EMA) but this run keeps none (ema_decay=None): it is ignored")
         mine = self._hyper()
         diff = {k: (blob["hyper"].get(k), v) for k, v in mine.items() if blob["hyper"].get(k) != v}
         if diff:
@@ -267,7 +289,7 @@ class FSDPStrategy:
 
     # ------------------------------------------------------------------------------------------ checkpoints
     def save_checkpoint(self, run_dir, global_step: int, epoch: int, train_loss: Optional[float] = None, only_trainable: bool = True,
-                        save_optimizer: Optional[bool] = None):
+                        save_optimizer: Optional[bool] = None, save_ema: Optional[bool] = None):
         """training/strategies/fsdp.py:100-141: gather the full fp32 state dict (every rank takes part in the gathers), split it
         by module key (``vlm.`` prefix dropped), rank 0 writes ``{"model": {mkey: OrderedDict}}`` to
         ``run_dir/checkpoints/step-XXXXXX-epoch-XX-loss=....pt``. Returns the path (rank 0) or None.
@@ -277,12 +299,23 @@ class FSDPStrategy:
         (``torch.load(..., weights_only=True)``): format tag, ``step`` / ``step_count``, the schedule's hyper-parameters, both AdamW moments per
         trainable parameter under the names of the model file's gather (full tensors: loads at any world size), every rank's generator
         states. Weights are not repeated there. Summed gradients of an open accumulation window are not part of the format, so
-        saving inside one raises."""
+        saving inside one raises.
+
+        ``save_ema`` (None = "the strategy keeps a weight average"): rank 0 also writes ``<same stem>-ema.pt`` in the model file's exact
+        layout -- the same module keys and entries in the same order, trainable parameters carrying their average, everything else
+        (frozen parameters, buffers) what the model file carries -- so ``MLA.from_pretrained`` and the reference's loader read it
+        unchanged. With ``save_optimizer`` and the average on, the optimizer file additionally holds ``"ema"`` (name -> full fp32
+        tensor), ``"ema_updates"``, ``"ema_decay"`` and ``"ema_update_every"``; without the average it is unchanged, key for key."""
         from collections import OrderedDict
         from pathlib import Path
         assert self.sharded is not None, "save_checkpoint needs run_setup() first"
         if save_optimizer is None:
             save_optimizer = self.save_optimizer_state
+        ema_on = self.sharded.ema_decay is not None
+        if save_ema is None:
+            save_ema = ema_on
+        if save_ema and not ema_on:
+            raise RuntimeError("save_ema=True needs a strategy built with ema_decay (this one keeps no weight average)")
         if save_optimizer and self._micro != 0:
             raise RuntimeError(f"optimizer state cannot be saved inside an accumulation window ({self._micro} of "
                                f"{self.grad_accumulation_steps} micro-batches seen): the summed gradients are not part of the file")
@@ -305,6 +338,16 @@ class FSDPStrategy:
             out = OrderedDict((k[4:] if k.startswith("vlm.") else k, v) for k, v in model_state_dicts.items())
             torch.save({"model": out}, path)
             del out
+        if save_ema:
+            # same route as the weights (one unit at a time, host copies on rank 0 only), laid over the model file's own entries
+            ema = {k: v for k, v in self.sharded.iter_ema_state(to_cpu_on_rank0=True) if v is not None}
+            if rank == 0:
+                out = OrderedDict((mkey[4:] if mkey.startswith("vlm.") else mkey,
+                                   OrderedDict((k, ema.get(f"{mkey}.{k}", v)) for k, v in sd.items()))
+                                  for mkey, sd in model_state_dicts.items())
+                torch.save({"model": out}, path.with_name(path.stem + "-ema.pt"))
+                del out
+            del ema
         del full, model_state_dicts          # rank 0's host copy of the weights goes before the moments arrive
         if save_optimizer:
             # same route as the weights: one unit at a time through the device, host copies on rank 0 only
@@ -316,17 +359,30 @@ class FSDPStrategy:
                 dist.all_gather_object(every, tuple(None if t is None else t.cpu() for t in mine))
             else:
                 every = [mine]
+            blob = {"format": self.OPTIMIZER_FORMAT, "step": int(self.step), "step_count": int(self.sharded.step_count),
+                    "hyper": self._hyper(), "state": state,
+                    "rng": {"world": int(self.world), "cpu": [c for c, _ in every], "device": [d for _, d in every]}}
+            if ema_on:       # what a bit-exact resume of the average needs; absent (not empty) without one
+                blob["ema"] = OrderedDict((n, e) for n, e in self.sharded.iter_ema_state(to_cpu_on_rank0=True) if e is not None)
+                blob["ema_updates"] = int(self.sharded.ema_updates)
+                blob["ema_decay"], blob["ema_update_every"] = float(self.sharded.ema_decay), int(self.sharded.ema_update_every)
             if rank == 0:
-                torch.save({"format": self.OPTIMIZER_FORMAT, "step": int(self.step), "step_count": int(self.sharded.step_count),
-                            "hyper": self._hyper(), "state": state,
-                            "rng": {"world": int(self.world), "cpu": [c for c, _ in every], "device": [d for _, d in every]}},
-                           path.with_name(path.stem + "-optimizer.pt"))
+                torch.save(blob, path.with_name(path.stem + "-optimizer.pt"))
         if dist.is_available() and dist.is_initialized():
             dist.barrier()
         return path
 
     def clip_grad_norm(self):
         return self.sharded.grad_norm_and_clip(self.max_grad_norm)
+
+    def ema_weights(self):
+        """Context manager: inside, the model computes with bf16(weight average) in place of the weights (evaluation, action sampling);
+        on exit the weights are back bit for bit. See ShardedModel.ema_weights. Not inside an accumulation window."""
+        assert self.sharded is not None, "ema_weights needs run_setup() first"
+        if self._micro != 0:
+            raise RuntimeError(f"ema_weights() inside an accumulation window ({self._micro} of {self.grad_accumulation_steps} "
+                               "micro-batches seen)")
+        return self.sharded.ema_weights()
 
 
 # training/materialize.py:16-68 -- the registry and factory scripts/train.py:367-385 uses
