@@ -528,12 +528,25 @@ int mla_gemm_prefill_f8_wide_gateup_swiglu(const void* xq, long long ldx, const 
  *     noise [steps, n] fp32, filled by the host before the first step: ax = a x; px = ax - b eps; mean = c1 px + c2 x;
  *     x = mean + sig noise[s n + i], every operation rounded on its own; at s = 0 the product 0 * noise is still formed and added (the
  *     sign of a zero result is the host loop's). A counter outside [0, steps) reads neither table.
+ *   mla_ddim_step_pin / mla_ddpm_step_pin (sample_ddim / sample_ddpm with pin=, MLA.predict_action_diff*(known_actions=...)): the same two
+ *     steps -- one kernel body each, the pinned form a template instance -- with the reference's denoised_fn hook
+ *     (GaussianDiffusion.p_mean_variance, gaussian_diffusion.py:318-321, clip_denoised = False) as replacement inpainting: with known [n]
+ *     fp32 and pin [n] uint8 (non-zero = pinned), px = pin[i] ? known[i] : px right behind px = ax - b eps; everything behind it reads the
+ *     replaced px (DDIM: e2 = (ax - px) / b; x = px c + d e2. DDPM: mean = c1 px + c2 x; x = mean + sig noise), every operation rounded on
+ *     its own: the bits of the host loops with denoised_fn = where(pin, known, px). The same counter protocol, one workgroup,
+ *     1 <= n <= 65 536; a counter outside [0, steps) writes nothing and reads neither a table nor known / pin. pin all zero: the bits of
+ *     mla_ddim_step / mla_ddpm_step. At the last step (s = 0: c = 1 and d = 0; c1 = 1, c2 = 0 and sig = 0) a pinned x == known
+ *     for finite x, eps and noise.
  *   mla_sampler_rows: with R = 1 + T, for 0 <= *step < steps: h_in row g R = t_table[*step] ([steps, H] bf16), row g R + 1 + p =
  *     x_e[g T + p] (g < G, p < T); any other *step writes nothing. h_in [G R, H], x_e [G T, H] bf16, H % 8 == 0, 16-B aligned rows. */
 int mla_ddim_step(float* x, const void* eps, void* x_bf16, const float* coef, int* step, int n, int steps, int advance,
                   mla_stream_t stream);
 int mla_ddpm_step(float* x, const void* eps, void* x_bf16, const float* coef, const float* noise, int* step, int n, int steps,
                   int advance, mla_stream_t stream);
+int mla_ddim_step_pin(float* x, const void* eps, void* x_bf16, const float* coef, const float* known, const unsigned char* pin, int* step,
+                      int n, int steps, int advance, mla_stream_t stream);
+int mla_ddpm_step_pin(float* x, const void* eps, void* x_bf16, const float* coef, const float* noise, const float* known,
+                      const unsigned char* pin, int* step, int n, int steps, int advance, mla_stream_t stream);
 int mla_sampler_rows(void* h_in, const void* t_table, const void* x_e, const int* step, int G, int T, int H, int steps,
                      mla_stream_t stream);
 

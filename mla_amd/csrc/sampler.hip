@@ -14,8 +14,13 @@ namespace {
 // the result is the host loop's, bit for bit. Contraction is switched off for the function (hipcc would fuse a x - b eps into an FMA; the
 // __f*_rn spellings are plain operators in this toolchain and would be fused just the same).
 // ONE workgroup: the counter is read by every thread in front of the barrier and written by thread 0 behind it.
+// PIN (mla_ddim_step_pin / mla_ddpm_step_pin): the reference's denoised_fn hook (gaussian_diffusion.py:318-321) as replacement inpainting --
+// px <- known[i] where pin[i], right behind px = ax - b eps and in front of everything that reads px; the rest of the step is unchanged.
+// PIN = false compiles the select away and never reads known / pin (null there).
+template <bool PIN>
 __global__ __launch_bounds__(256) void ddim_step_kernel(float* __restrict__ x, const bf16_t* __restrict__ eps, bf16_t* __restrict__ x_bf16,
-                                                        const float* __restrict__ coef, int* step, int n, int steps, int advance) {
+                                                        const float* __restrict__ coef, const float* __restrict__ known,
+                                                        const uint8_t* __restrict__ pin, int* step, int n, int steps, int advance) {
 #pragma clang fp contract(off)
   const int s = *(const volatile int*)step;
   const bool live = s >= 0 && s < steps;                                      // a stale counter never indexes outside the table
@@ -25,7 +30,8 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(float* __restrict__ x, c
       const float e = bf2f(eps[i]);
       const float ax = a * x[i];
       const float be = b * e;
-      const float px = ax - be;
+      float px = ax - be;
+      if (PIN && pin[i]) px = known[i];
       const float df = ax - px;
       const float e2 = df / b;
       const float pc = px * c;
@@ -45,9 +51,11 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(float* __restrict__ x, c
 //   ax = a x;  px = ax - b eps;  mean = c1 px + c2 x;  x' = mean + sig noise
 // every operation rounded on its own, as in ddim_step_kernel (contraction off: c1 px + c2 x and mean + sig noise would become FMAs). At
 // s = 0 sig is 0 and the product 0 * noise is still formed and added, as the host loop does: the sign of a zero result is the host's.
-// The counter protocol is ddim_step_kernel's.
+// The counter protocol and PIN are ddim_step_kernel's.
+template <bool PIN>
 __global__ __launch_bounds__(256) void ddpm_step_kernel(float* __restrict__ x, const bf16_t* __restrict__ eps, bf16_t* __restrict__ x_bf16,
-                                                        const float* __restrict__ coef, const float* __restrict__ noise, int* step, int n,
+                                                        const float* __restrict__ coef, const float* __restrict__ noise,
+                                                        const float* __restrict__ known, const uint8_t* __restrict__ pin, int* step, int n,
                                                         int steps, int advance) {
 #pragma clang fp contract(off)
   const int s = *(const volatile int*)step;
@@ -60,7 +68,8 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(float* __restrict__ x, c
       const float xi = x[i];
       const float ax = a * xi;
       const float be = b * e;
-      const float px = ax - be;
+      float px = ax - be;
+      if (PIN && pin[i]) px = known[i];
       const float m1 = c1 * px;
       const float m2 = c2 * xi;
       const float mean = m1 + m2;
@@ -89,26 +98,49 @@ __global__ __launch_bounds__(256) void sampler_rows_kernel(bf16_t* __restrict__ 
 
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// The checks and the launch of mla_ddim_step / mla_ddim_step_pin (`who` names the export in the messages).
+template <bool PIN>
+int ddim_step_launch(const char* who, float* x, const void* eps, void* x_bf16, const float* coef, const float* known, const uint8_t* pin,
+                     int* step, int n, int steps, int advance, hipStream_t stream) {
+  MLA_CHECK_ARG(x && eps && x_bf16 && coef && step && (!PIN || (known && pin)), "%s: null pointer", who);
+  MLA_CHECK_ARG(n >= 1 && n <= 65536, "%s: n = %d outside [1, 65536] (one workgroup walks the chunk)", who, n);
+  MLA_CHECK_ARG(steps >= 1, "%s: steps = %d", who, steps);
+  hipLaunchKernelGGL(ddim_step_kernel<PIN>, dim3(1), dim3(256), 0, stream, x, (const bf16_t*)eps, (bf16_t*)x_bf16, coef, known, pin, step, n,
+                     steps, advance ? 1 : 0);
+  MLA_LAUNCH_CHECK();
+}
+
+template <bool PIN>
+int ddpm_step_launch(const char* who, float* x, const void* eps, void* x_bf16, const float* coef, const float* noise, const float* known,
+                     const uint8_t* pin, int* step, int n, int steps, int advance, hipStream_t stream) {
+  MLA_CHECK_ARG(x && eps && x_bf16 && coef && noise && step && (!PIN || (known && pin)), "%s: null pointer", who);
+  MLA_CHECK_ARG(n >= 1 && n <= 65536, "%s: n = %d outside [1, 65536] (one workgroup walks the chunk)", who, n);
+  MLA_CHECK_ARG(steps >= 1, "%s: steps = %d", who, steps);
+  hipLaunchKernelGGL(ddpm_step_kernel<PIN>, dim3(1), dim3(256), 0, stream, x, (const bf16_t*)eps, (bf16_t*)x_bf16, coef, noise, known, pin,
+                     step, n, steps, advance ? 1 : 0);
+  MLA_LAUNCH_CHECK();
+}
+
 }  // namespace
 
 extern "C" int mla_ddim_step(float* x, const void* eps, void* x_bf16, const float* coef, int* step, int n, int steps, int advance,
                              hipStream_t stream) {
-  MLA_CHECK_ARG(x && eps && x_bf16 && coef && step, "mla_ddim_step: null pointer");
-  MLA_CHECK_ARG(n >= 1 && n <= 65536, "mla_ddim_step: n = %d outside [1, 65536] (one workgroup walks the chunk)", n);
-  MLA_CHECK_ARG(steps >= 1, "mla_ddim_step: steps = %d", steps);
-  hipLaunchKernelGGL(ddim_step_kernel, dim3(1), dim3(256), 0, stream, x, (const bf16_t*)eps, (bf16_t*)x_bf16, coef, step, n, steps,
-                     advance ? 1 : 0);
-  MLA_LAUNCH_CHECK();
+  return ddim_step_launch<false>("mla_ddim_step", x, eps, x_bf16, coef, nullptr, nullptr, step, n, steps, advance, stream);
+}
+
+extern "C" int mla_ddim_step_pin(float* x, const void* eps, void* x_bf16, const float* coef, const float* known, const unsigned char* pin,
+                                 int* step, int n, int steps, int advance, hipStream_t stream) {
+  return ddim_step_launch<true>("mla_ddim_step_pin", x, eps, x_bf16, coef, known, pin, step, n, steps, advance, stream);
 }
 
 extern "C" int mla_ddpm_step(float* x, const void* eps, void* x_bf16, const float* coef, const float* noise, int* step, int n, int steps,
                              int advance, hipStream_t stream) {
-  MLA_CHECK_ARG(x && eps && x_bf16 && coef && noise && step, "mla_ddpm_step: null pointer");
-  MLA_CHECK_ARG(n >= 1 && n <= 65536, "mla_ddpm_step: n = %d outside [1, 65536] (one workgroup walks the chunk)", n);
-  MLA_CHECK_ARG(steps >= 1, "mla_ddpm_step: steps = %d", steps);
-  hipLaunchKernelGGL(ddpm_step_kernel, dim3(1), dim3(256), 0, stream, x, (const bf16_t*)eps, (bf16_t*)x_bf16, coef, noise, step, n, steps,
-                     advance ? 1 : 0);
-  MLA_LAUNCH_CHECK();
+  return ddpm_step_launch<false>("mla_ddpm_step", x, eps, x_bf16, coef, noise, nullptr, nullptr, step, n, steps, advance, stream);
+}
+
+extern "C" int mla_ddpm_step_pin(float* x, const void* eps, void* x_bf16, const float* coef, const float* noise, const float* known,
+                                 const unsigned char* pin, int* step, int n, int steps, int advance, hipStream_t stream) {
+  return ddpm_step_launch<true>("mla_ddpm_step_pin", x, eps, x_bf16, coef, noise, known, pin, step, n, steps, advance, stream);
 }
 
 extern "C" int mla_sampler_rows(void* h_in, const void* t_table, const void* x_e, const int* step, int G, int T, int H, int steps,

@@ -109,13 +109,16 @@ class GaussianDiffusion:
             out = out[1]
         return out.float()        # bf16 -> fp32 is exact; the fp32 tables promote the arithmetic in the reference as well
 
-    def _pred_xstart(self, x, t, eps, clip_denoised):
+    def _pred_xstart(self, x, t, eps, clip_denoised, denoised_fn=None):
+        """process_xstart of p_mean_variance (gaussian_diffusion.py:318-324): denoised_fn on the fp32 x0 prediction, then the clamp."""
         px = self._at(self.sqrt_recip_alphas_cumprod, t, x) * x - self._at(self.sqrt_recipm1_alphas_cumprod, t, x) * eps
+        if denoised_fn is not None:
+            px = denoised_fn(px)
         return px.clamp(-1, 1) if clip_denoised else px
 
-    def ddim_sample(self, model, x, t, clip_denoised=True, model_kwargs=None, eta=0.0):
+    def ddim_sample(self, model, x, t, clip_denoised=True, model_kwargs=None, eta=0.0, denoised_fn=None):
         """gaussian_diffusion.py:520-568 (Song et al. eq. 12)."""
-        pred_xstart = self._pred_xstart(x, t, self._eps(model, x, t, model_kwargs), clip_denoised)
+        pred_xstart = self._pred_xstart(x, t, self._eps(model, x, t, model_kwargs), clip_denoised, denoised_fn)
         eps = (self._at(self.sqrt_recip_alphas_cumprod, t, x) * x - pred_xstart) / self._at(self.sqrt_recipm1_alphas_cumprod, t, x)
         ab, ab_prev = self._at(self.alphas_cumprod, t, x), self._at(self.alphas_cumprod_prev, t, x)
         sigma = eta * torch.sqrt((1 - ab_prev) / (1 - ab)) * torch.sqrt(1 - ab / ab_prev)
@@ -147,9 +150,9 @@ class GaussianDiffusion:
                                          torch.tensor(self.timestep_map, dtype=torch.long, device=device))
         return self._dev_tables[key]
 
-    def p_sample(self, model, x, t, clip_denoised=True, model_kwargs=None):
+    def p_sample(self, model, x, t, clip_denoised=True, model_kwargs=None, denoised_fn=None):
         """gaussian_diffusion.py:395-440 with the fixed-small posterior variance."""
-        pred_xstart = self._pred_xstart(x, t, self._eps(model, x, t, model_kwargs), clip_denoised)
+        pred_xstart = self._pred_xstart(x, t, self._eps(model, x, t, model_kwargs), clip_denoised, denoised_fn)
         mean = self._at(self.posterior_mean_coef1, t, x) * pred_xstart + self._at(self.posterior_mean_coef2, t, x) * x
         logvar = self._at(self.posterior_log_variance_clipped, t, x)
         noise = torch.randn_like(x)
@@ -188,17 +191,21 @@ class GaussianDiffusion:
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                          device=None, progress=False, eta=0.0):
-        """gaussian_diffusion.py:608-688."""
-        if denoised_fn is not None or cond_fn is not None:
-            raise NotImplementedError("denoised_fn / cond_fn are never passed by MLA (model_mla.py:742-763)")
-        return self._loop(self.ddim_sample, model, shape, noise, device, clip_denoised=clip_denoised, model_kwargs=model_kwargs, eta=eta)
+        """gaussian_diffusion.py:608-688. denoised_fn: a callable on the fp32 x0 prediction of every step, applied in front of the clamp
+        (p_mean_variance :318-321) -- MLA.predict_action_diff*(known_actions=...) pins known chunk entries with it; None is the loop
+        without the hook."""
+        if cond_fn is not None:
+            raise NotImplementedError("cond_fn (gradient guidance) is never passed by MLA (model_mla.py:742-763)")
+        kw = {} if denoised_fn is None else {"denoised_fn": denoised_fn}
+        return self._loop(self.ddim_sample, model, shape, noise, device, clip_denoised=clip_denoised, model_kwargs=model_kwargs, eta=eta, **kw)
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                       device=None, progress=False):
-        """gaussian_diffusion.py:442-518."""
-        if denoised_fn is not None or cond_fn is not None:
-            raise NotImplementedError("denoised_fn / cond_fn are never passed by MLA (model_mla.py:742-763)")
-        return self._loop(self.p_sample, model, shape, noise, device, clip_denoised=clip_denoised, model_kwargs=model_kwargs)
+        """gaussian_diffusion.py:442-518. denoised_fn: as in ddim_sample_loop."""
+        if cond_fn is not None:
+            raise NotImplementedError("cond_fn (gradient guidance) is never passed by MLA (model_mla.py:742-763)")
+        kw = {} if denoised_fn is None else {"denoised_fn": denoised_fn}
+        return self._loop(self.p_sample, model, shape, noise, device, clip_denoised=clip_denoised, model_kwargs=model_kwargs, **kw)
 
 
 def create_diffusion(timestep_respacing="", noise_schedule="squaredcos_cap_v2", diffusion_steps=100, **kwargs):

@@ -91,6 +91,8 @@ _SIGNATURES = {
                                                c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p],
     "mla_ddim_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "mla_ddpm_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    "mla_ddim_step_pin": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    "mla_ddpm_step_pin": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "mla_sampler_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "mla_attn_chunk_split_plan": [c_int, c_int, c_int, c_int, c_int, c_void_p],
     "mla_attn_chunk_split_ws_bytes": [c_int, c_int, c_int, c_int, c_int],      # returns long long (restype fixed up in lib())
@@ -1440,45 +1442,84 @@ def gemm_prefill_f8_wide_gateup_swiglu(xq, x_scale, wgu_q, w_scale, act, ldo=Non
 DDIM_NMAX = 65536
 
 
+def _ddim_step_checks(who, x, eps, x_bf16, coef, step):
+    """The argument checks of ddim_step / ddim_step_pin -> x.numel()."""
+    _req(x, torch.float32, who + " x")
+    _req(eps, torch.bfloat16, who + " eps")
+    _req(x_bf16, torch.bfloat16, who + " x_bf16")
+    _req(coef, torch.float32, who + " coef")
+    _req(step, torch.int32, who + " step")
+    n = x.numel()
+    if not (x.is_contiguous() and eps.is_contiguous() and x_bf16.is_contiguous() and coef.is_contiguous()):
+        raise ValueError(f"{who}: x, eps, x_bf16 and coef must be contiguous")
+    if eps.numel() != n or x_bf16.numel() != n or coef.dim() != 2 or coef.shape[1] != 4 or step.numel() != 1:
+        raise ValueError(f"{who}: x {tuple(x.shape)}, eps {tuple(eps.shape)}, x_bf16 {tuple(x_bf16.shape)}, coef {tuple(coef.shape)}, "
+                         f"step {tuple(step.shape)}")
+    if not 1 <= n <= DDIM_NMAX:
+        raise ValueError(f"{who}: {n} elements outside [1, {DDIM_NMAX}]")
+    return n
+
+
+def _ddpm_step_checks(who, x, eps, x_bf16, coef, noise, step):
+    """The argument checks of ddpm_step / ddpm_step_pin -> x.numel()."""
+    _req(x, torch.float32, who + " x")
+    _req(eps, torch.bfloat16, who + " eps")
+    _req(x_bf16, torch.bfloat16, who + " x_bf16")
+    _req(coef, torch.float32, who + " coef")
+    _req(noise, torch.float32, who + " noise")
+    _req(step, torch.int32, who + " step")
+    n = x.numel()
+    if not (x.is_contiguous() and eps.is_contiguous() and x_bf16.is_contiguous() and coef.is_contiguous() and noise.is_contiguous()):
+        raise ValueError(f"{who}: x, eps, x_bf16, coef and noise must be contiguous")
+    if eps.numel() != n or x_bf16.numel() != n or coef.dim() != 2 or coef.shape[1] != 5 or step.numel() != 1 \
+            or tuple(noise.shape) != (coef.shape[0], n):
+        raise ValueError(f"{who}: x {tuple(x.shape)}, eps {tuple(eps.shape)}, x_bf16 {tuple(x_bf16.shape)}, coef {tuple(coef.shape)}, "
+                         f"noise {tuple(noise.shape)} (wanted [steps, x.numel()]), step {tuple(step.shape)}")
+    if not 1 <= n <= DDIM_NMAX:
+        raise ValueError(f"{who}: {n} elements outside [1, {DDIM_NMAX}]")
+    return n
+
+
+def _pin_checks(who, n, known, pin):
+    """known fp32 and pin uint8, contiguous, x.numel() elements each."""
+    _req(known, torch.float32, who + " known")
+    _req(pin, torch.uint8, who + " pin")
+    if not (known.is_contiguous() and pin.is_contiguous()):
+        raise ValueError(f"{who}: known and pin must be contiguous")
+    if known.numel() != n or pin.numel() != n:
+        raise ValueError(f"{who}: known {tuple(known.shape)} and pin {tuple(pin.shape)} need x.numel() = {n} elements each")
+
+
 def ddim_step(x, eps, x_bf16, coef, step, advance=True):
     """mla_ddim_step: the eta = 0 DDIM update of the chunk x (fp32, in place; any shape, contiguous) with row step[0] of coef [steps, 4] and
     the bf16 epsilons eps (same number of elements); x_bf16 <- bf16(x); advance: step[0] -= 1. A step[0] outside [0, steps) writes nothing."""
-    _req(x, torch.float32, "ddim_step x")
-    _req(eps, torch.bfloat16, "ddim_step eps")
-    _req(x_bf16, torch.bfloat16, "ddim_step x_bf16")
-    _req(coef, torch.float32, "ddim_step coef")
-    _req(step, torch.int32, "ddim_step step")
-    n = x.numel()
-    if not (x.is_contiguous() and eps.is_contiguous() and x_bf16.is_contiguous() and coef.is_contiguous()):
-        raise ValueError("ddim_step: x, eps, x_bf16 and coef must be contiguous")
-    if eps.numel() != n or x_bf16.numel() != n or coef.dim() != 2 or coef.shape[1] != 4 or step.numel() != 1:
-        raise ValueError(f"ddim_step: x {tuple(x.shape)}, eps {tuple(eps.shape)}, x_bf16 {tuple(x_bf16.shape)}, coef {tuple(coef.shape)}, "
-                         f"step {tuple(step.shape)}")
-    if not 1 <= n <= DDIM_NMAX:
-        raise ValueError(f"ddim_step: {n} elements outside [1, {DDIM_NMAX}]")
+    n = _ddim_step_checks("ddim_step", x, eps, x_bf16, coef, step)
     call("mla_ddim_step", _p(x), _p(eps), _p(x_bf16), _p(coef), _p(step), n, coef.shape[0], 1 if advance else 0)
+
+
+def ddim_step_pin(x, eps, x_bf16, coef, known, pin, step, advance=True):
+    """mla_ddim_step_pin: ddim_step with the x0 prediction replaced by known (fp32) where pin (uint8) is non-zero, x.numel() elements
+    each: ddim_sample with denoised_fn = where(pin, known, .), the same bits. pin all zero: ddim_step's bits."""
+    n = _ddim_step_checks("ddim_step_pin", x, eps, x_bf16, coef, step)
+    _pin_checks("ddim_step_pin", n, known, pin)
+    call("mla_ddim_step_pin", _p(x), _p(eps), _p(x_bf16), _p(coef), _p(known), _p(pin), _p(step), n, coef.shape[0], 1 if advance else 0)
 
 
 def ddpm_step(x, eps, x_bf16, coef, noise, step, advance=True):
     """mla_ddpm_step: the DDPM posterior step (GaussianDiffusion.p_sample, clip_denoised=False) of the chunk x (fp32, in place; any shape,
     contiguous) with row step[0] of coef [steps, 5], the bf16 epsilons eps and row step[0] of noise [steps, x.numel()] fp32; x_bf16 <-
     bf16(x); advance: step[0] -= 1. A step[0] outside [0, steps) writes nothing."""
-    _req(x, torch.float32, "ddpm_step x")
-    _req(eps, torch.bfloat16, "ddpm_step eps")
-    _req(x_bf16, torch.bfloat16, "ddpm_step x_bf16")
-    _req(coef, torch.float32, "ddpm_step coef")
-    _req(noise, torch.float32, "ddpm_step noise")
-    _req(step, torch.int32, "ddpm_step step")
-    n = x.numel()
-    if not (x.is_contiguous() and eps.is_contiguous() and x_bf16.is_contiguous() and coef.is_contiguous() and noise.is_contiguous()):
-        raise ValueError("ddpm_step: x, eps, x_bf16, coef and noise must be contiguous")
-    if eps.numel() != n or x_bf16.numel() != n or coef.dim() != 2 or coef.shape[1] != 5 or step.numel() != 1 \
-            or tuple(noise.shape) != (coef.shape[0], n):
-        raise ValueError(f"ddpm_step: x {tuple(x.shape)}, eps {tuple(eps.shape)}, x_bf16 {tuple(x_bf16.shape)}, coef {tuple(coef.shape)}, "
-                         f"noise {tuple(noise.shape)} (wanted [steps, x.numel()]), step {tuple(step.shape)}")
-    if not 1 <= n <= DDIM_NMAX:
-        raise ValueError(f"ddpm_step: {n} elements outside [1, {DDIM_NMAX}]")
+    n = _ddpm_step_checks("ddpm_step", x, eps, x_bf16, coef, noise, step)
     call("mla_ddpm_step", _p(x), _p(eps), _p(x_bf16), _p(coef), _p(noise), _p(step), n, coef.shape[0], 1 if advance else 0)
+
+
+def ddpm_step_pin(x, eps, x_bf16, coef, noise, known, pin, step, advance=True):
+    """mla_ddpm_step_pin: ddpm_step with the x0 prediction replaced by known (fp32) where pin (uint8) is non-zero, x.numel() elements
+    each: p_sample with denoised_fn = where(pin, known, .), the same bits. pin all zero: ddpm_step's bits."""
+    n = _ddpm_step_checks("ddpm_step_pin", x, eps, x_bf16, coef, noise, step)
+    _pin_checks("ddpm_step_pin", n, known, pin)
+    call("mla_ddpm_step_pin", _p(x), _p(eps), _p(x_bf16), _p(coef), _p(noise), _p(known), _p(pin), _p(step), n, coef.shape[0],
+         1 if advance else 0)
 
 
 def sampler_rows(h_in, t_table, x_e, step, G, T):

@@ -26,6 +26,10 @@ Opt-in (`ddpm_sampler="device"`, see MODES): the same for the DDPM loop of `use_
 normal variates up front into a device table (asynchronous launches, the host loop's order) and replays the captured step with
 `mla_ddpm_step` as its update num_timesteps times: the host loop's bits and generator position.
 
+Pinned chunk steps (`MLA.predict_action_diff*(known_actions=...)`): `sample_ddim` / `sample_ddpm` take `pin=(known, mask)` and run the same
+loops with `mla_ddim_step_pin` / `mla_ddpm_step_pin` as the update -- the x0 prediction of every step is `known` where `mask` is set, the
+reference's `denoised_fn` hook -- on a state and a captured step of their own; the un-pinned loops keep theirs.
+
 Opt-in (`suffix_attention="split"`, see MODES; PrefixCachedEps only): the attention launch of the suffix pass becomes
 `mla_attn_chunk_split` -- every head's key tiles cut over several workgroups, the partial softmax states merged in a fixed order by a
 second launch -- for every R; the same function up to summation order. The multi-row engines (BatchedPrefixCachedEps, SampleGroupsEps,
@@ -240,9 +244,11 @@ _GRAPH_OFF = "MLA_INFER_GRAPH=0: the device sampler launches its steps one by on
 class _DdimState:
     """What sample_ddim / sample_ddpm keep per (engine, batch, action_dim, diffusion): the chunk x fp32 and its bf16 cast, the step
     counter, the coefficient and timestep-embedding tables, and the captured step; a DDPM state also has `noise` [steps, B T D] fp32, the
-    steps' normal variates (None in a DDIM state: it selects the update kernel). All device tensors are allocated outside inference mode."""
+    steps' normal variates (None in a DDIM state: it selects the update kernel). A pinned state (sample_ddim / sample_ddpm with pin=)
+    also has `known` [B, T, D] fp32 and `pin` [B, T, D] uint8, refilled per call (None in an un-pinned state: the update is the plain
+    kernel). All device tensors are allocated outside inference mode."""
     __slots__ = ("diffusion", "steps", "x", "x_bf16", "step", "coef", "timesteps", "t_table", "t_key", "graph", "graph_key", "failed",
-                 "noise")
+                 "noise", "known", "pin")
 
 
 def _fake_quant_rows(x):
@@ -287,6 +293,8 @@ class _CachedEpsBase:
         self._suffix = None          # per layer: what the suffix pass streams -- _packed itself ("bf16") or a quantised copy (_quantised)
         self._ddim = {}              # sample_ddim's state per (B, action_dim): see _DdimState
         self._ddpm = {}              # sample_ddpm's, kept apart: a DDIM and a DDPM call on one engine keep their captured steps
+        self._ddim_pin = {}          # the states of the pinned calls (pin=), kept apart in the same way: the un-pinned call replays ...
+        self._ddpm_pin = {}          # ... the step it replays without them, whatever pinned calls ran in between
 
     @classmethod
     def _serves(cls, vlm, rows: int, limit: int, tag: tuple, message: str, warn: bool = True) -> bool:
@@ -538,12 +546,13 @@ class _CachedEpsBase:
         return None, noise_pred
 
     # ----------------------------------------------------- the sampler loops on the device (sampler="device", ddpm_sampler="device")
-    def _sampler_state(self, x0, diffusion, ddpm: bool):
-        """The persistent state of the DDIM or of the DDPM loop (kept in _ddim / _ddpm: the two do not evict each other's captured steps)
-        for chunks shaped like x0 [B, T, D] under `diffusion` (per B: the group engines keep one per set_groups G)."""
+    def _sampler_state(self, x0, diffusion, ddpm: bool, pinned: bool = False):
+        """The persistent state of the DDIM or of the DDPM loop (kept in _ddim / _ddpm, a pinned call's in _ddim_pin / _ddpm_pin: the four
+        do not evict each other's captured steps) for chunks shaped like x0 [B, T, D] under `diffusion` (per B: the group engines keep
+        one per set_groups G)."""
         B, T, D = x0.shape
         assert B == self.B and T == self.T, (tuple(x0.shape), self.B, self.T)
-        store = self._ddpm if ddpm else self._ddim
+        store = (self._ddpm_pin if ddpm else self._ddim_pin) if pinned else (self._ddpm if ddpm else self._ddim)
         st = store.get((B, D))
         if st is None or st.diffusion is not diffusion:
             dev = self.h_in.device
@@ -557,6 +566,8 @@ class _CachedEpsBase:
                 st.coef = coef.clone()
                 st.t_table = torch.zeros((st.steps, self.H), dtype=torch.bfloat16, device=dev)
                 st.noise = torch.zeros((st.steps, B * T * D), dtype=torch.float32, device=dev) if ddpm else None
+                st.known = torch.zeros((B, T, D), dtype=torch.float32, device=dev) if pinned else None
+                st.pin = torch.zeros((B, T, D), dtype=torch.uint8, device=dev) if pinned else None
             st.t_key = st.graph = st.graph_key = None
             st.failed = False
             store[(B, D)] = st
@@ -579,18 +590,23 @@ class _CachedEpsBase:
 
     def _sampler_one_step(self, st):
         """One sampler step, every launch on the current stream and none of them waiting for the host: the launches of __call__ with the
-        timestep token looked up (mla_sampler_rows), then the state's update (DDIM, or DDPM with the step's row of st.noise), which counts
-        the device-side step index down."""
+        timestep token looked up (mla_sampler_rows), then the state's update (DDIM, or DDPM with the step's row of st.noise; the pinned
+        kernels on a pinned state), which counts the device-side step index down."""
         vlm = self.vlm
         x_e = vlm.x_embedder(st.x_bf16)                                       # [B, T, H]
         hip.sampler_rows(self.h_in, st.t_table, x_e.contiguous(), st.step, self.B, self.T)
         self._suffix_pass()                                                   # launched directly: a graph cannot replay inside a capture
         picked = self.h_out.view(self.B, self.R, self.H)[:, 1:].reshape(self.B * self.T, self.H).contiguous()
         noise_pred = vlm.final_layer(picked)                                  # [B * T, D] bf16
-        if st.noise is None:
-            hip.ddim_step(st.x, noise_pred.contiguous(), st.x_bf16, st.coef, st.step, advance=True)
+        if st.pin is None:
+            if st.noise is None:
+                hip.ddim_step(st.x, noise_pred.contiguous(), st.x_bf16, st.coef, st.step, advance=True)
+            else:
+                hip.ddpm_step(st.x, noise_pred.contiguous(), st.x_bf16, st.coef, st.noise, st.step, advance=True)
+        elif st.noise is None:
+            hip.ddim_step_pin(st.x, noise_pred.contiguous(), st.x_bf16, st.coef, st.known, st.pin, st.step, advance=True)
         else:
-            hip.ddpm_step(st.x, noise_pred.contiguous(), st.x_bf16, st.coef, st.noise, st.step, advance=True)
+            hip.ddpm_step_pin(st.x, noise_pred.contiguous(), st.x_bf16, st.coef, st.noise, st.known, st.pin, st.step, advance=True)
 
     def _sampler_graph(self, st):
         """The captured step for the current weights, or None (MLA_INFER_GRAPH=0 or a failed capture: eager launches of the same sequence,
@@ -622,17 +638,21 @@ class _CachedEpsBase:
                 torch.cuda.synchronize()
         return st.graph
 
-    def _sampler_loop(self, st, x0):
+    def _sampler_loop(self, st, x0, pin=None):
         """What the two device loops share behind the state lookup: the timestep-token table and the captured step for the current
         weights, the reset of the state to x0 and step steps - 1, and st.steps replays (or eager steps). A DDPM state: in front of the
         replays, one randn_like(x) per step in the host loop's order (step steps - 1 first) into row s of st.noise -- asynchronous
-        launches."""
+        launches. A pinned state: pin = (known, mask) is copied into st.known / st.pin in front of the replays (behind the capture: its
+        warm-up step runs on whatever the last call left there)."""
         self._sampler_t_table(st)
         graph = self._sampler_graph(st)
         with torch.no_grad():
             st.x.copy_(x0)
             st.x_bf16.copy_(x0.to(torch.bfloat16))
             st.step.fill_(st.steps - 1)
+            if pin is not None:
+                st.known.copy_(pin[0])
+                st.pin.copy_(pin[1])
             if st.noise is not None:
                 for s in reversed(range(st.steps)):
                     st.noise[s].copy_(torch.randn_like(st.x).view(-1))
@@ -642,30 +662,45 @@ class _CachedEpsBase:
                 else:
                     self._sampler_one_step(st)
 
-    def sample_ddim(self, x0, diffusion):
+    @staticmethod
+    def _check_pin(x0, pin):
+        """pin = (known, mask) of a pinned device loop: both shaped like x0, known floating point, mask bool."""
+        if pin is None:
+            return
+        known, mask = pin
+        if tuple(known.shape) != tuple(x0.shape) or tuple(mask.shape) != tuple(x0.shape) or mask.dtype != torch.bool \
+                or not known.is_floating_point():
+            raise ValueError(f"pin: known {tuple(known.shape)} {known.dtype} and mask {tuple(mask.shape)} {mask.dtype} must be a "
+                             f"floating-point and a bool tensor shaped like the chunk {tuple(x0.shape)}")
+
+    def sample_ddim(self, x0, diffusion, pin=None):
         """ddim_sample_loop(self, x0.shape, x0, clip_denoised=False, eta=0.0) of `diffusion` with the loop on the device -> samples
-        [B, T, D] fp32, the same bits. After the (already done) prefill the host enqueues diffusion.num_timesteps replays of one captured
+        [B, T, D] fp32, the same bits. pin = (known [B, T, D] fp32, mask [B, T, D] bool): the loop with denoised_fn =
+        where(mask, known, .) -- every step's x0 prediction is `known` where `mask` is set (mla_ddim_step_pin; the result there == known)
+        -- on a state and a captured step of its own: the un-pinned call replays the step it replays without pinned calls. After the (already done) prefill the host enqueues diffusion.num_timesteps replays of one captured
         sampler step (x_embedder, mla_sampler_rows, the suffix pass, final_layer, mla_ddim_step) and returns; nothing is copied to the
         device and the host never waits for the device between the steps. The generator ends where the host loop leaves it (one unused
         randn_like per step)."""
         x0 = x0.float()
-        st = self._sampler_state(x0, diffusion, ddpm=False)
-        self._sampler_loop(st, x0)
+        self._check_pin(x0, pin)
+        st = self._sampler_state(x0, diffusion, ddpm=False, pinned=pin is not None)
+        self._sampler_loop(st, x0, pin)
         with torch.no_grad():
             for _ in range(st.steps):
                 torch.randn_like(st.x)                                        # ddim_sample draws its noise even at eta = 0
             return st.x.clone()
 
-    def sample_ddpm(self, x0, diffusion):
+    def sample_ddpm(self, x0, diffusion, pin=None):
         """p_sample_loop(self, x0.shape, x0, clip_denoised=False) of `diffusion` with the loop on the device -> samples [B, T, D] fp32,
-        the same bits. The host first enqueues the loop's num_timesteps randn_like draws, in the loop's order, into the state's noise
+        the same bits. pin: sample_ddim's (mla_ddpm_step_pin), the draws and the generator position are the un-pinned call's. The host first enqueues the loop's num_timesteps randn_like draws, in the loop's order, into the state's noise
         table -- the suffix pass draws nothing, so every step sees the values the host loop's own draw would have given it, and the
         generator ends where the host loop leaves it -- then num_timesteps replays of one captured sampler step (x_embedder,
         mla_sampler_rows, the suffix pass, final_layer, mla_ddpm_step reading row *step of the table). Nothing is copied to the device and
         the host never waits for the device between the steps."""
         x0 = x0.float()
-        st = self._sampler_state(x0, diffusion, ddpm=True)
-        self._sampler_loop(st, x0)
+        self._check_pin(x0, pin)
+        st = self._sampler_state(x0, diffusion, ddpm=True, pinned=pin is not None)
+        self._sampler_loop(st, x0, pin)
         with torch.no_grad():
             return st.x.clone()
 

@@ -271,6 +271,68 @@ class MLA(nn.Module):
             a[..., g] = np.where(a[..., g] < 0.5, 0, 1)
         return np.where(mask, 0.5 * (a + 1) * (hi - lo) + lo, a)
 
+    def normalize_actions(self, actions, unnorm_key=None) -> np.ndarray:
+        """The inverse of unnormalize_actions (no counterpart in model_mla.py; the form of normalize_proprio): on the masked dimensions
+        2 (a - q01) / (q99 - q01 + 1e-8) - 1, clipped to [-1, 1]; the other dimensions pass through (a binarised gripper channel stays
+        0 / 1 and comes back as it is). Without ``norm_stats`` it is the identity, like the return path of predict_action_diff. The round
+        trip through unnormalize_actions returns a - 1e-8 (a - q01) / (q99 - q01 + 1e-8) on a masked dimension, for q01 <= a <= q99."""
+        a = np.asarray(actions)
+        if self.norm_stats is None:
+            return a
+        st = self.get_action_stats(unnorm_key)
+        mask = st.get("mask", np.ones_like(st["q01"], dtype=bool))
+        hi, lo = np.array(st["q99"]), np.array(st["q01"])
+        return np.where(mask, np.clip(2 * (a - lo) / (hi - lo + 1e-8) - 1, -1, 1), a)
+
+    # ---- known_actions of the four sampling entry points: validated before the model is touched, then one (known, mask) pair per call
+    @staticmethod
+    def _known_entry(entry, T, action_dim, who="known_actions"):
+        """One observation's known actions -> float64 [d, action_dim] (None stays None); ValueError for anything else."""
+        if entry is None:
+            return None
+        try:
+            a = np.asarray(entry.detach().cpu().numpy() if torch.is_tensor(entry) else entry, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"{who}: not a numeric array [d, {action_dim}]: {e}") from None
+        if a.ndim != 2 or a.shape[1] != action_dim or not 1 <= a.shape[0] <= T:
+            raise ValueError(f"{who} must be [d, action_dim] = [1..{T}, {action_dim}] (the first d steps of the chunk), got {tuple(a.shape)}")
+        if not np.isfinite(a).all():
+            raise ValueError(f"{who} has non-finite values")
+        return a
+
+    @staticmethod
+    def _known_entries(known_actions, B, T, action_dim):
+        """predict_action_diff_batch's known_actions -> a list of B validated entries (None: B times None)."""
+        if known_actions is None:
+            return [None] * B
+        if (isinstance(known_actions, np.ndarray) or torch.is_tensor(known_actions)) and known_actions.ndim == 3:
+            known_actions = list(known_actions)                                # a stacked [B, d, action_dim] array: the same d everywhere
+        if not isinstance(known_actions, (list, tuple)) or len(known_actions) != B:
+            raise ValueError(f"known_actions must be a list with one entry ([d, action_dim] or None) per observation, {B} here")
+        return [MLA._known_entry(k, T, action_dim, f"known_actions[{b}]") for b, k in enumerate(known_actions)]
+
+    @staticmethod
+    def _fwd_known(entry):
+        """The keyword of a call that ends in another public method: handed on only when given."""
+        return {} if entry is None else {"known_actions": entry}
+
+    def _pin(self, entries, T, action_dim, unnorm_key, device, repeat=1):
+        """Validated entries, one per observation -> None (nothing known) or (known [B * repeat, T, action_dim] fp32, mask bool) on
+        `device`: chunk steps 0 .. d - 1 of observation b hold its entry in the sampler's (normalised) units, each observation's rows
+        `repeat` times (the N chunks of an observation share what is known)."""
+        if all(e is None for e in entries):
+            return None
+        known = np.zeros((len(entries), T, action_dim), dtype=np.float32)
+        mask = np.zeros((len(entries), T, action_dim), dtype=bool)
+        for b, e in enumerate(entries):
+            if e is not None:
+                known[b, :e.shape[0]] = MLA.normalize_actions(self, e, unnorm_key)
+                mask[b, :e.shape[0]] = True
+        known, mask = torch.from_numpy(known).to(device), torch.from_numpy(mask).to(device)
+        if repeat != 1:
+            known, mask = known.repeat_interleave(repeat, dim=0), mask.repeat_interleave(repeat, dim=0)
+        return known.contiguous(), mask.contiguous()
+
     # ---- the per-sample preprocessing of predict_action_diff, shared with predict_action_diff_batch
     def _prompt_ids(self, instruction, who):
         # :626-632 -- prompt text from the backbone's builder, ids from the backbone's tokenizer (the Llama tokenizer files are not
@@ -339,21 +401,29 @@ class MLA(nn.Module):
             _ = torch.randint(0, self.diffusion.num_timesteps, (T,), device=device)
         return torch.cat(draws, dim=0).float()
 
-    def _sample(self, eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs, ddpm_sampler="host"):
+    def _sample(self, eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs, ddpm_sampler="host", pin=None):
         """x0 [B, T, D] -> samples: the DDIM loop (eta = 0) on the device (an engine's sample_ddim) or on the host, or the DDPM loop of the
-        training diffusion on the device (sample_ddpm) or on the host."""
+        training diffusion on the device (sample_ddpm) or on the host. pin = (known, mask) shaped like x0 (see _pin): the device loops'
+        pin=, the host loops' denoised_fn = where(mask, known, .); None is the call without it."""
         device = x0.device
+        on_device = {} if pin is None else {"pin": pin}
+        on_host = {} if pin is None else {"denoised_fn": lambda px: torch.where(pin[1], pin[0], px)}
         if use_ddim and num_ddim_steps is not None:
             if self.ddim_diffusion is None:
                 self.create_ddim(ddim_step=num_ddim_steps)
             if sampler == "device":
-                return eps_model.sample_ddim(x0, self.ddim_diffusion)
+                return eps_model.sample_ddim(x0, self.ddim_diffusion, **on_device)
             return self.ddim_diffusion.ddim_sample_loop(eps_model, x0.shape, x0, clip_denoised=False, model_kwargs=model_kwargs,
-                                                        progress=False, device=device, eta=0.0)
+                                                        progress=False, device=device, eta=0.0, **on_host)
         if ddpm_sampler == "device":
-            return eps_model.sample_ddpm(x0, self.diffusion)
+            return eps_model.sample_ddpm(x0, self.diffusion, **on_device)
         return self.diffusion.p_sample_loop(eps_model, x0.shape, x0, clip_denoised=False, model_kwargs=model_kwargs, progress=False,
-                                            device=device)
+                                            device=device, **on_host)
+
+    @staticmethod
+    def _pin_rows(pin, start, stop):
+        """The rows [start, stop) of a call's (known, mask) pair for one pass or sub-batch."""
+        return None if pin is None else (pin[0][start:stop].contiguous(), pin[1][start:stop].contiguous())
 
     def _actions(self, chunks, unnorm_key):
         """The sampled chunks of a call, in order (numpy, stacked on axis 0) -> un-normalised actions."""
@@ -394,7 +464,7 @@ class MLA(nn.Module):
                             camera_name: str = "rlbench_front", reuse_prefix: bool = True, suffix_weights: str = "bf16",
                             prefill: str = "train", sampler: str = "host", suffix_attention: str = "head",
                             prefill_precision: str = "bf16", ddpm_sampler: str = "host", suffix_operand: str = "fused",
-                            **kwargs) -> np.ndarray:
+                            known_actions=None, **kwargs) -> np.ndarray:
         """model_mla.py:592-775: 8-step DDIM (eta = 0) over the action chunk with the VLM as the epsilon model, then
         un-normalisation.
         * ``image`` is a PIL image / uint8 HWC frame (pre-processed here like the reference does, :656-660) or an already
@@ -453,7 +523,19 @@ class MLA(nn.Module):
         "fused". Up to 8 suffix rows both values run the same pass (the GEMV stages its input once per workgroup already). It composes
         with every ``suffix_weights``, ``suffix_attention``, ``sampler``, ``ddpm_sampler``, ``prefill`` and ``prefill_precision`` mode; it
         is validated in front of every other mode and raises ValueError for an unknown value, and for "once" when ``reuse_prefix=False``
-        or the cached-prefix engine does not serve the shape: no silent fallback."""
+        or the cached-prefix engine does not serve the shape: no silent fallback.
+        ``known_actions`` (default None: the call without the keyword, bit for bit): an array [d, action_dim], 1 <= d <= T, in the units
+        of the return value -- the first d steps of this chunk are already decided (the robot is executing them while this call runs) and
+        the sampler pins them: in every sampler step the x0 prediction of chunk steps 0 .. d - 1 is replaced by the given values
+        (normalize_actions of them when the model has ``norm_stats``: values outside [q01, q99] are clipped as the return path clips),
+        the reference's ``denoised_fn`` hook (gaussian_diffusion.py:318-321) used as replacement inpainting; the keyword itself has no
+        counterpart in model_mla.py. The initial sample is the call's noise on the pinned rows too, every draw is the un-pinned call's,
+        and the sampled normalised chunk equals the given values on the pinned entries exactly; the free steps see them only through
+        the model's attention over the chunk rows. Indexing: when the previous chunk was sampled from an observation taken k control
+        steps ago, new chunk step j is old chunk step j + k, so ``known_actions = old_chunk[k:k + d]``. It composes with every mode
+        keyword, with ``sampler`` / ``ddpm_sampler`` "host" and "device" (mla_ddim_step_pin / mla_ddpm_step_pin on a captured step of
+        its own) and with ``reuse_prefix=False`` (the host loop with ``denoised_fn``). A wrong shape, d > T or non-finite values raise
+        ValueError before the model is touched. What pinning does to a trained policy is not measured."""
         from .infer import Modes, PrefixCachedEps, check_modes, needs_engine
         check_modes(Modes(suffix_weights=suffix_weights, prefill=prefill, suffix_attention=suffix_attention, prefill_precision=prefill_precision,
                           suffix_operand=suffix_operand, sampler=sampler, ddpm_sampler=ddpm_sampler), reuse_prefix, use_ddim, num_ddim_steps)
@@ -461,6 +543,7 @@ class MLA(nn.Module):
             raise ValueError(f"prefill={prefill!r} needs the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has no "
                              "separate prefill")
         T = self.future_action_window_size + 1
+        known_actions = MLA._known_entry(known_actions, T, action_dim)
         self.vlm.eval()
         device = next(self.vlm.parameters()).device
         if input_ids is None:
@@ -486,7 +569,8 @@ class MLA(nn.Module):
         else:
             needs_engine("PrefixCachedEps", T, prefill=prefill, sampler=sampler, ddpm_sampler=ddpm_sampler, suffix_attention=suffix_attention,
                          suffix_operand=suffix_operand)
-        samples = self._sample(eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs, ddpm_sampler)
+        pin = MLA._pin(self, [known_actions], T, action_dim, unnorm_key, device)
+        samples = self._sample(eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs, ddpm_sampler, pin)
         return self._actions([samples[:1].float().cpu().numpy()], unnorm_key)[0]
 
     @torch.inference_mode()
@@ -497,7 +581,7 @@ class MLA(nn.Module):
                                   num_samples: Optional[int] = None, prefill: str = "train", sampler: str = "host",
                                   suffix_attention: str = "head", prefill_precision: str = "bf16",
                                   groups_attention: str = "head", batch_prefill: str = "train",
-                                  ddpm_sampler: str = "host", suffix_operand: str = "fused") -> np.ndarray:
+                                  ddpm_sampler: str = "host", suffix_operand: str = "fused", known_actions=None) -> np.ndarray:
         """B observations -> [B, T, action_dim]: by definition B independent `predict_action_diff` calls (the reference's
         `predict_action_batch`, model_mla.py:994, is dead code), computed on ONE cached prefix pass per DDIM step
         (mla_amd/infer.py:BatchedPrefixCachedEps): the prompts may have different lengths, the FPS start indices are drawn once per chunk.
@@ -554,7 +638,11 @@ class MLA(nn.Module):
         ``suffix_operand``: predict_action_diff's, forwarded where the call ends in it (B = 1, no ``num_samples`` or N = 1). The batched
         engines (B >= 2, or N >= 2 chunks per observation) form every operand once per pass already (stand-alone RMSNorm / SwiGLU
         kernels in front of the row GEMMs): they accept both values and launch what they launch without the keyword. An unknown value,
-        and "once" with ``reuse_prefix=False``, raise ValueError."""
+        and "once" with ``reuse_prefix=False``, raise ValueError.
+        ``known_actions``: predict_action_diff's, as a list with one entry per observation -- an array [d_b, action_dim] (its own d_b) or
+        None (nothing of that chunk is pinned); with ``num_samples`` the N chunks of an observation share its entry. None, or a list of
+        only None, is the call without the keyword, bit for bit. A list of another length raises ValueError before the model is
+        touched."""
         from .infer import BatchedPrefixCachedEps, Modes, check_mode, check_modes, needs_engine, suffix_attention_single_only
         modes = Modes(suffix_weights=suffix_weights, prefill=prefill, suffix_attention=suffix_attention, groups_attention=groups_attention,
                       batch_prefill=batch_prefill, suffix_operand=suffix_operand, sampler=sampler, ddpm_sampler=ddpm_sampler)
@@ -572,10 +660,11 @@ class MLA(nn.Module):
         if B != 1:
             suffix_attention_single_only(suffix_attention, f"predict_action_diff_batch with {B} observations")
         T = self.future_action_window_size + 1
+        known = MLA._known_entries(known_actions, B, T, action_dim)
         if num_samples is not None:
             return self._predict_action_diff_batch_samples(images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix,
-                                                           num_samples, modes)
+                                                           num_samples, modes, known)
         input_ids, pointclouds = MLA._batch_prompts(self, B, instructions, input_ids, pointclouds, cur_robot_states)
         if noise is not None and tuple(noise.shape[:2]) != (B, T):
             raise ValueError(f"noise must be [B, T, action_dim] = [{B}, {T}, ...], got {tuple(noise.shape)}")
@@ -585,7 +674,7 @@ class MLA(nn.Module):
         def one(b, **kw):
             return self.predict_action_diff(images[b], pointclouds[b], None, cur_robot_states[b], unnorm_key, cfg_scale, use_ddim, num_ddim_steps,
                                             action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b:b + 1],
-                                            camera_name=camera_name, **kw)
+                                            camera_name=camera_name, **MLA._fwd_known(known[b]), **kw)
         if B == 1:
             return one(0, reuse_prefix=reuse_prefix,
                        **modes.forwarded("suffix_weights", "sampler", "ddpm_sampler", "suffix_attention", "suffix_operand"))[None]
@@ -601,17 +690,20 @@ class MLA(nn.Module):
             return np.stack([one(b, reuse_prefix=False) for b in range(B)])
         device, ids_rows, inputs = self._batch_inputs(images, pointclouds, cur_robot_states, ids_rows, unnorm_key, camera_name)
         x0 = self._draw_x0([None if noise is None else noise[b:b + 1] for b in range(B)], T, action_dim, device)
+        pin = MLA._pin(self, known, T, action_dim, unnorm_key, device)
         out = []
         for sub, eng in BatchedPrefixCachedEps.for_batch(self.vlm, ids_rows, T, suffix_attention=groups_attention,
                                                          batch_prefill=batch_prefill, **inputs):
-            samples = self._sample(eng, x0[sub.start:sub.stop].contiguous(), sampler, use_ddim, num_ddim_steps, {}, ddpm_sampler)
+            samples = self._sample(eng, x0[sub.start:sub.stop].contiguous(), sampler, use_ddim, num_ddim_steps, {}, ddpm_sampler,
+                                   MLA._pin_rows(pin, sub.start, sub.stop))
             out.append(samples.float().cpu().numpy())
         return self._actions(out, unnorm_key)
 
     def _predict_action_diff_batch_samples(self, images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
-                                           num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix, num_samples, modes):
+                                           num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix, num_samples, modes,
+                                           known):
         """predict_action_diff_batch(num_samples=N) -> [B, N, T, action_dim] (called inside its inference mode; see its docstring).
-        modes: its keywords as infer.Modes, validated there."""
+        modes: its keywords as infer.Modes, known: its known_actions as one entry per observation, both validated there."""
         from .infer import BatchedSampleGroupsEps, needs_engine
         B, N, T = len(images), int(num_samples), self.future_action_window_size + 1
         if N < 1:
@@ -625,7 +717,7 @@ class MLA(nn.Module):
         def samples_of(b, **kw):
             return self.predict_action_diff_samples(images[b], pointclouds[b], None, cur_robot_states[b], unnorm_key, N, cfg_scale, use_ddim,
                                                     num_ddim_steps, action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b],
-                                                    camera_name=camera_name, **kw)
+                                                    camera_name=camera_name, **MLA._fwd_known(known[b]), **kw)
         if B == 1:
             return samples_of(0, reuse_prefix=reuse_prefix, **modes.forwarded("suffix_weights", "sampler", "ddpm_sampler", "suffix_attention",
                                                                               "groups_attention", "suffix_operand"))[None]
@@ -644,11 +736,12 @@ class MLA(nn.Module):
             return np.stack([samples_of(b, reuse_prefix=False) for b in range(B)])
         device, ids_rows, inputs = self._batch_inputs(images, pointclouds, cur_robot_states, ids_rows, unnorm_key, camera_name)
         x0 = self._draw_x0([None if noise is None else noise[b, n:n + 1] for b in range(B) for n in range(N)], T, action_dim, device)   # rows (b, n)
+        pin = MLA._pin(self, known, T, action_dim, unnorm_key, device, repeat=N)
         out = []
         for sub, eng in BatchedSampleGroupsEps.for_batch(self.vlm, ids_rows, T, N, modes.suffix_weights,
                                                          suffix_attention=modes.groups_attention, batch_prefill=modes.batch_prefill, **inputs):
             samples = self._sample(eng, x0[sub.start * N:sub.stop * N].contiguous(), modes.sampler, use_ddim, num_ddim_steps, {},
-                                   modes.ddpm_sampler)
+                                   modes.ddpm_sampler, MLA._pin_rows(pin, sub.start * N, sub.stop * N))
             out.append(samples.float().cpu().numpy().reshape(sub.stop - sub.start, N, T, -1))
         return self._actions(out, unnorm_key)
 
@@ -660,7 +753,7 @@ class MLA(nn.Module):
                                     reuse_prefix: bool = True, suffix_weights: str = "bf16", prefill: str = "train",
                                     sampler: str = "host", suffix_attention: str = "head",
                                     prefill_precision: str = "bf16", groups_attention: str = "head",
-                                    ddpm_sampler: str = "host", suffix_operand: str = "fused") -> np.ndarray:
+                                    ddpm_sampler: str = "host", suffix_operand: str = "fused", known_actions=None) -> np.ndarray:
         """N action chunks for ONE observation -> [N, T, action_dim]: by definition N independent `predict_action_diff` calls on the same
         observation with the initial samples ``noise[n]`` (critic / best-of-N choice, uncertainty estimates, temporal ensembling), computed
         on ONE cached prefix (mla_amd/infer.py:SampleGroupsEps): the encoders and the decoder prefill run once per call, every sampler step
@@ -696,7 +789,9 @@ class MLA(nn.Module):
         ``reuse_prefix=False`` or the shared-prefix engine does not serve the shape.
         ``suffix_operand``: predict_action_diff's, forwarded for ``num_samples=1``. With more samples the shared-prefix engine forms every
         operand once per pass already: both values are accepted and launch what is launched without the keyword. An unknown value, and
-        "once" with ``reuse_prefix=False``, raise ValueError."""
+        "once" with ``reuse_prefix=False``, raise ValueError.
+        ``known_actions``: predict_action_diff's -- one array [d, action_dim] for the observation, pinned in every one of the N chunks
+        (the engine sees it repeated over the samples). None is the call without the keyword, bit for bit."""
         from .infer import Modes, SampleGroupsEps, check_modes, needs_engine, suffix_attention_single_only
         modes = Modes(suffix_weights=suffix_weights, prefill=prefill, suffix_attention=suffix_attention, groups_attention=groups_attention,
                       prefill_precision=prefill_precision, suffix_operand=suffix_operand, sampler=sampler, ddpm_sampler=ddpm_sampler)
@@ -712,12 +807,13 @@ class MLA(nn.Module):
             raise ValueError(f"num_samples must be >= 1, got {num_samples}")
         if noise is not None and tuple(noise.shape) != (N, T, action_dim):
             raise ValueError(f"noise must be [N, T, action_dim] = [{N}, {T}, {action_dim}], got {tuple(noise.shape)}")
+        known_actions = MLA._known_entry(known_actions, T, action_dim)
         self._check_cfg_scale(cfg_scale)
 
         def one(n, **kw):
             return self.predict_action_diff(image, pointcloud, instruction, cur_robot_state, unnorm_key, cfg_scale, use_ddim, num_ddim_steps,
                                             action_dim, input_ids=input_ids, noise=None if noise is None else noise[n:n + 1],
-                                            camera_name=camera_name, **kw)
+                                            camera_name=camera_name, **MLA._fwd_known(known_actions), **kw)
         if N == 1:
             return one(0, reuse_prefix=reuse_prefix, **modes.forwarded("suffix_weights", "prefill", "sampler", "ddpm_sampler", "suffix_attention",
                                                                        "prefill_precision", "suffix_operand"))[None]
@@ -740,11 +836,13 @@ class MLA(nn.Module):
         model_kwargs = {"images": self._image_batch(image, device), "point_cloud": self._pointcloud_batch(pointcloud, device),
                         "camera_name": camera_name, "proprio": self._proprio_token(cur_robot_state, unnorm_key, device)}
         x0 = self._draw_x0([None if noise is None else noise[n:n + 1] for n in range(N)], T, action_dim, device)
+        pin = MLA._pin(self, [known_actions], T, action_dim, unnorm_key, device, repeat=N)
         eng, passes = SampleGroupsEps.for_inputs(self.vlm, input_ids, T, N, suffix_weights=suffix_weights, prefill=prefill,
                                                  prefill_precision=prefill_precision, suffix_attention=groups_attention, **model_kwargs)
         out = []
         for start, stop in passes:                                           # one prefill, then the passes' sampler loops one after the other
             eng.set_groups(stop - start)
-            samples = self._sample(eng, x0[start:stop].contiguous(), sampler, use_ddim, num_ddim_steps, {}, ddpm_sampler)
+            samples = self._sample(eng, x0[start:stop].contiguous(), sampler, use_ddim, num_ddim_steps, {}, ddpm_sampler,
+                                   MLA._pin_rows(pin, start, stop))
             out.append(samples.float().cpu().numpy())
         return self._actions(out, unnorm_key)

@@ -49,6 +49,12 @@
                                                           the same for the DDPM loop: use_ddim=False calls (the 100 steps of the training
                                                           diffusion) with ddpm_sampler="host" and ddpm_sampler="device" alternating in
                                                           one process, in pairs
+    python tools/bench_infer.py --pair-pinned [--pairs P] [--chunks C[,C..]]
+                                                          sampler="device" chunks without and with known_actions (the first min(3, C)
+                                                          chunk steps pinned) alternating in one process, in pairs, for every chunk length
+                                                          (default 1,16) with bf16 and with fp8 suffix weights: per-chunk latency with the
+                                                          95 % interval of the pair differences; also whether the pinned steps came back
+                                                          exactly and whether sampler="host" returns the pinned chunk's bits
     python tools/bench_infer.py --pair-attention [--pairs P] [--chunks C[,C..]] [--kernel-table]
                                                           suffix_attention="head" and "split" chunks alternating in one process, in pairs,
                                                           for every chunk length (default 1,16) with bf16 and with fp8 suffix weights (the
@@ -165,6 +171,7 @@ def main():
     ap.add_argument("--pair-prefill", action="store_true", help="alternate prefill=\"train\", \"compact\" and \"compact\" with prefill_precision=\"fp8\" in one process")
     ap.add_argument("--pair-sampler", action="store_true", help="alternate sampler=\"host\" and sampler=\"device\" in one process, in pairs")
     ap.add_argument("--pair-ddpm-sampler", action="store_true", help="alternate ddpm_sampler=\"host\" and ddpm_sampler=\"device\" on use_ddim=False calls in one process, in pairs")
+    ap.add_argument("--pair-pinned", action="store_true", help="alternate sampler=\"device\" chunks without and with known_actions in one process, in pairs")
     ap.add_argument("--pair-attention", action="store_true", help="alternate suffix_attention=\"head\" and \"split\" in one process, in pairs; with --samples / --batch: groups_attention "
                     "on the multi-row routes")
     ap.add_argument("--pair-operand", action="store_true", help="alternate suffix_operand=\"fused\" and \"once\" in one process, in pairs")
@@ -177,6 +184,8 @@ def main():
     args = ap.parse_args()
     if args.pair_sampler or args.pair_ddpm_sampler:
         return main_pair_sampler(args, ddpm=args.pair_ddpm_sampler)
+    if args.pair_pinned:
+        return main_pair_pinned(args)
     if args.pair_operand:
         return main_pair_operand(args)
     batches = [int(v) for v in args.batch.split(",")]
@@ -371,6 +380,44 @@ def main_pair_sampler(args, ddpm=False):
                               "same_bits": bool(np.array_equal(acts["host"], acts["device"])),
                               "step_captured": all(st.graph is not None for st in (eng._ddpm if ddpm else eng._ddim).values()),
                               "graph_error": eng.graph_error,
+                              "data": "synthetic"}), flush=True)
+
+
+def main_pair_pinned(args):
+    """The un-pinned call vs the call with known_actions on the same box, alternating, per chunk length and suffix-weight mode, the
+    device sampler in both arms: predict_action_diff per chunk (host clock around `iters` calls that end in a device synchronise). The
+    pinned arm adds the validation and normalisation of the known rows, two small copies to the device per call and one select per
+    chunk element in the update kernel (mla_ddim_step_pin on a captured step of its own)."""
+    m, b, ids = _setup()
+    dev = ids.device
+    image, pc, state = _observation(b)
+    for C in ([int(v) for v in args.chunks.split(",")] if args.chunks else [1, 16]):
+        m.future_action_window_size = m.vlm.future_action_window_size = C - 1
+        noise = torch.randn(1, C, 7, device=dev)
+        d = min(3, C)
+        known = (torch.rand(d, 7, generator=torch.Generator().manual_seed(C)) * 2 - 1).numpy()
+        kw = dict(image=image, pointcloud=pc, cur_robot_state=state, input_ids=ids, num_ddim_steps=args.steps, noise=noise)
+        arms = {"plain": {}, "pinned": {"known_actions": known}}
+        for w in ("bf16", "fp8"):
+            acts = {}
+            for arm, extra in arms.items():                                 # engines, graphs, tables; the same seed: the same FPS start indices
+                torch.manual_seed(1)
+                acts[arm] = m.predict_action_diff(suffix_weights=w, sampler="device", **extra, **kw)
+            torch.manual_seed(1)
+            host = m.predict_action_diff(suffix_weights=w, sampler="host", known_actions=known, **kw)
+            chunk = {arm: [] for arm in arms}
+            for _ in range(args.pairs):                                     # plain, pinned, plain, pinned, ...: same box, interleaved
+                for arm, extra in arms.items():
+                    chunk[arm].append(_time_ms(lambda: m.predict_action_diff(suffix_weights=w, sampler="device", **extra, **kw), args.iters))
+            sent = known if m.norm_stats is None else m.unnormalize_actions(m.normalize_actions(known))
+            print(json.dumps({"metric": "predict_action_diff, MLA-Llama2-7B, batch 1, sampler=device: without vs with known_actions in alternating pairs",
+                              "action_chunk": C, "suffix_rows": C + 1, "pinned_steps": d, "suffix_weights": w, "ddim_steps": args.steps,
+                              "pairs": args.pairs, "iters_per_arm_and_pair": args.iters, "unit": "ms",
+                              "chunk_ms": {k: [round(v, 2) for v in vs] for k, vs in chunk.items()},
+                              "chunk_pinned_minus_plain": _pair_stats(chunk["plain"], chunk["pinned"]),
+                              "pinned_steps_max_abs_diff": float(np.abs(acts["pinned"][:d] - sent).max()),
+                              "pinned_host_same_bits": bool(np.array_equal(host, acts["pinned"])),
+                              "pinned_differs_from_plain": not np.array_equal(acts["pinned"], acts["plain"]),
                               "data": "synthetic"}), flush=True)
 
 
