@@ -348,6 +348,43 @@ int mla_gemm_skinny_gateup_swiglu_bf16(const void* x, long long ldx, const void*
                                        int K, mla_stream_t stream);
 int mla_gemm_skinny_gateup_swiglu_w8(const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out,
                                      long long ldo, int M, int I, int K, mla_stream_t stream);
+/* ---- weight-only MXFP4 for the suffix projections (opt-in: MLA.predict_action_diff(suffix_mx="fp4")). Format (OCP MXFP4), for W [N, K]
+ *   bf16 with K % 32 == 0: codes q [N, K / 2] bytes, element 2 j in the low nibble of byte j and element 2 j + 1 in the high one, nibble =
+ *   sign (8) | index into {0, 0.5, 1, 1.5, 2, 3, 4, 6}; scales s [N, K / 32] bytes, one e8m0 byte per block of 32 consecutive k of a row,
+ *   byte = e + 127 with e = clamp(floor(log2(block amax)) - 2, -125, 125) taken from the exponent bits (127 and all codes +0 for an
+ *   all-zero block; 255 is never written). |w| / 2^e is rounded to the nearest grid value, ties to the even mantissa bit (0.25 -> 0,
+ *   0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4), saturating at 6; the sign is kept. Blocks never cross rows, so packed
+ *   q|k|v and gate|up matrices quantise as one.
+ * mla_quant_mxfp4_rows: W [N, K] bf16 (row stride ldw elements) -> q (row stride ldq bytes, 16-B aligned rows, ldq >= K / 2) + s (row
+ *   stride lds bytes >= K / 32). One workgroup per row, one thread per block, integer work on the bf16 bits: deterministic, no workspace,
+ *   no atomics. Non-finite input is NOT supported. Runs once per weight version.
+ * mla_gemv_w4 / mla_gemm_skinny_w4 / mla_gemm_skinny_gateup_swiglu_w4 / mla_gemm_suffix_w4 / mla_gemm_suffix_w4_pos: the `_w8` entry
+ *   points' contracts, argument checks and epilogues with W = the code bytes (ldw in BYTES, ldw % 16 == 0, ldw >= K / 2), w_scale = the
+ *   scale bytes and ld_scale their row stride (>= K / 32). K % 32 == 0. The codes are decoded WITH their block scale in registers
+ *   (v_cvt_scalef32_pk_f32_fp4 in the gemv, v_cvt_scalef32_pk_bf16_fp4 into the MFMA A fragments): every e2m1 value has two significant
+ *   bits and the scale is a power of two, so the decode is exact in bf16 and out = the bf16 kernels on the dequantised matrix up to
+ *   summation order -- no scale multiply behind the sum, no new rounding point; residual, rotary and SwiGLU epilogues are the bf16 forms'.
+ *   The MFMA forms keep the `_w8` kernels' 64-wide K steps, wave split and summation order (a lane's 16 codes are 8 B inside one scale
+ *   block), so every 64-row slice of mla_gemm_suffix_w4 is bit for bit mla_gemm_skinny_w4's output and the gate|up form is
+ *   mla_swiglu_fwd of the plain form's output. A quarter of the bf16 forms' weight bytes per call (+ 1 / 16 of that in scales). */
+int mla_quant_mxfp4_rows(const void* W, long long ldw, void* q, long long ldq, void* s, long long lds, int N, int K, mla_stream_t stream);
+int mla_gemv_w4(const void* x, long long ldx, const void* W, long long ldw, const void* w_scale, long long ld_scale, void* out, long long ldo,
+                long long out_batch_stride, int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre,
+                const void* pre_w, float eps, const float* rope_cos, const float* rope_sin, int rope_cols, mla_stream_t stream);
+int mla_gemm_skinny_w4(const void* x, long long ldx, const void* W, long long ldw, const void* w_scale, long long ld_scale, void* out,
+                       long long ldo, long long out_batch_stride, int rows_per_batch, const void* residual, long long ld_res, int M, int N,
+                       int K, int pre, const void* pre_w, float eps, const float* rope_cos, const float* rope_sin, int rope_cols,
+                       mla_stream_t stream);
+int mla_gemm_skinny_gateup_swiglu_w4(const void* x, long long ldx, const void* W, long long ldw, const void* w_scale, long long ld_scale,
+                                     void* out, long long ldo, int M, int I, int K, mla_stream_t stream);
+int mla_gemm_suffix_w4(const void* x, long long ldx, const void* W, long long ldw, const void* w_scale, long long ld_scale, void* out,
+                       long long ldo, long long out_batch_stride, int rows_per_batch, const int* slot, int cap_rows, const void* residual,
+                       long long ld_res, int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols,
+                       mla_stream_t stream);
+int mla_gemm_suffix_w4_pos(const void* x, long long ldx, const void* W, long long ldw, const void* w_scale, long long ld_scale, void* out,
+                           long long ldo, long long out_batch_stride, int rows_per_batch, const int* slot, int cap_rows, const void* residual,
+                           long long ld_res, int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols,
+                           const int* rope_pos, int rope_rows, mla_stream_t stream);
 /* mla_attn_chunk: mla_attn_decode's contract for 1 <= R <= 64 query rows and any S_kv >= R: online softmax over key tiles of 64 (LDS does
  *   not grow with S_kv), QK^T and PV on the MFMA pipe, P rounded to bf16 before P V like the flash kernel; the key tiles are shared out
  *   over 4 waves per (sample, head, 16 queries) and their softmax states merged in a fixed order (deterministic, graph-capturable). */

@@ -28,6 +28,11 @@
 //   mla_gemm_skinny_gateup_swiglu_bf16 / _w8  the skinny kernel on the packed gate|up matrix with SwiGLU in the epilogue: a workgroup's
 //                      tile is 8 gate rows and their 8 up rows, out [M, I] = silu(gate) * up; bit for bit mla_swiglu_fwd of the plain
 //                      form's [M, 2 I] rows, which never reach memory (suffix_operand="once").
+//   mla_gemv_w4 / mla_gemm_skinny_w4 / mla_gemm_skinny_gateup_swiglu_w4 / mla_gemm_suffix_w4(_pos)  the same five contracts over weight-only
+//                      OCP MXFP4 (e2m1 codes, one e8m0 scale byte per 32 k of a row; mla_quant_mxfp4_rows writes both): same kernels,
+//                      WFmt = WF_W4 -- a quarter of the bf16 bytes per weight, decoded WITH the block scale in registers
+//                      (v_cvt_scalef32_pk_f32_fp4 / v_cvt_scalef32_pk_bf16_fp4), exactly: no scale multiply behind the sum. The MFMA
+//                      forms keep the W8 forms' K steps, wave split and summation order (suffix_mx="fp4").
 // infer.py keeps gemv / decode for every shape they accept and uses the other two beyond (action chunks of 8..63 steps); the last two
 // serve batched sampling (B observations with prompts of different lengths on one pass).
 // All are HBM-bound by construction: algorithmic bytes = the weight matrix (gemv) / the K and V rows of the head (decode).
@@ -68,8 +73,18 @@ __device__ __forceinline__ u32x4_t pack8f(const float* f) {
 // W8: the weight operand is OCP e4m3fn (one byte per element, ldw in elements = bytes) with one fp32 scale per W row. Every e4m3 value is
 // a bf16 value, so decoding loses nothing; the scale multiplies the FINISHED fp32 sum (never a partial one), in front of the residual add /
 // the rotation and the one bf16 rounding. 16 B per lane and load as in the bf16 form = 16 weights instead of 8: K % 16 == 0.
-template <bool W8> struct welem { typedef bf16_t t; };
-template <> struct welem<true> { typedef uint8_t t; };
+// W4: the weight operand is OCP MXFP4 -- e2m1 codes, two per byte (element 2 j in the low nibble of byte j; ldw in BYTES), with one e8m0
+// scale byte per block of 32 consecutive k of a row (w_scale.p [N, ld]: byte = e + 127, the block's values are code * 2^e). Every e2m1
+// value has at most two significant bits and the scale is a power of two within [2^-125, 2^125], so the decode WITH its scale
+// (v_cvt_scalef32_pk_f32_fp4 / v_cvt_scalef32_pk_bf16_fp4) is exact in bf16: the kernels are the bf16 kernels on the dequantised matrix up
+// to summation order, with no scale multiply behind the sum and no new rounding point. K % 32 == 0: blocks never cross a row's end.
+enum WFmt { WF_BF16 = 0, WF_W8 = 1, WF_W4 = 2 };
+struct w4_scales { const uint8_t* p; long long ld; };
+template <WFmt F> struct welem { typedef bf16_t t; typedef const float* __restrict__ scale_t; };
+template <> struct welem<WF_W8> { typedef uint8_t t; typedef const float* __restrict__ scale_t; typedef u32x4_t load_t; };
+template <> struct welem<WF_W4> { typedef uint8_t t; typedef w4_scales scale_t; typedef u32x2_t load_t; };
+// the scale of an e8m0 byte as the fp32 operand of the scaled conversions: 2^(byte - 127), bytes 1 .. 254
+__device__ __forceinline__ float e8m0_to_f32(const uint8_t b) { return __builtin_bit_cast(float, (uint32_t)b << 23); }
 // the 4 codes of one 32-bit word -> floats (v_cvt_pk_f32_fp8: bytes 0, 1 / bytes 2, 3)
 __device__ __forceinline__ void fp8x4_to_f32(const uint32_t w, float* f) {
   const mla_f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8(w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
@@ -84,36 +99,68 @@ __device__ __forceinline__ u32x4_t fp8x8_to_bf16(const uint32_t w0, const uint32
   v[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true));
   return v;
 }
+// 8 e2m1 codes (one word, element order = nibble order from the low end) times the block scale -> one bf16 MFMA fragment
+__device__ __forceinline__ u32x4_t fp4x8_to_bf16(const uint32_t w, const float scale) {
+  u32x4_t v;
+  v[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0));
+  v[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1));
+  v[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2));
+  v[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3));
+  return v;
+}
+// the 8 codes of one word times the block scale -> floats (v_cvt_scalef32_pk_f32_fp4: byte 0 .. 3, low nibble first)
+__device__ __forceinline__ void fp4x8_to_f32(const uint32_t w, const float scale, float* f) {
+  const mla_f32x2_t a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 0), b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 1);
+  const mla_f32x2_t c = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 2), d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 3);
+  f[0] = a[0]; f[1] = a[1]; f[2] = b[0]; f[3] = b[1]; f[4] = c[0]; f[5] = c[1]; f[6] = d[0]; f[7] = d[1];
+}
+// half h (codes 8 h .. 8 h + 7) of a lane's 16 codes of a 64-wide K step -> the A fragment of one MFMA: W8 two words at scale 1, W4 one word
+// at the block's scale
+template <WFmt F>
+__device__ __forceinline__ u32x4_t wq_frag(const typename welem<F>::load_t a, const int h, const float scale) {
+  if constexpr (F == WF_W4) return fp4x8_to_bf16(a[h], scale);
+  else return fp8x8_to_bf16(a[2 * h], a[2 * h + 1]);
+}
 // The W8 form of gemv_kernel's K loop for one wave's GEMV_ROWS rows: a lane's 16 B are the codes of k = 16 c .. 16 c + 15, i.e. the x chunks
 // 2 c and 2 c + 1 of xs ([M][kc] chunks of 8 bf16); a K step is 64 lanes x 16 = 1024 weights. Same batching as the bf16 loop: the loads of
 // GEMV_UNR steps are issued before the first use.
-template <int M>
-__device__ __forceinline__ void gemv_w8_rows(const uint8_t* const* wr, const u32x4_t* xs, int kc, int lane, float (*acc)[M]) {
-  const int kc16 = kc >> 1;
+// W4: a lane's 16 B are the 32 codes of ONE scale block, k = 32 c .. 32 c + 31 = the x chunks 4 c .. 4 c + 3, decoded with the block's scale
+// (its byte is fetched with the codes); a K step is 2048 weights, the bytes in flight per lane are the W8 form's.
+template <int M, WFmt F>
+__device__ __forceinline__ void gemv_wq_rows(const uint8_t* const* wr, const uint8_t* const* sr, const u32x4_t* xs, int kc, int lane,
+                                             float (*acc)[M]) {
+  constexpr int XC = F == WF_W4 ? 4 : 2;                // x chunks of 8 per lane and load
+  const int kc16 = kc >> (F == WF_W4 ? 2 : 1);          // 16-B loads per row
   for (int s0 = 0; s0 < ((kc16 + 63) >> 6); s0 += GEMV_UNR) {
     u32x4_t w[GEMV_UNR][GEMV_ROWS];
+    float sc[GEMV_UNR][GEMV_ROWS];
 #pragma unroll
     for (int u = 0; u < GEMV_UNR; ++u) {
       const int c = (s0 + u) * 64 + lane;
 #pragma unroll
-      for (int r = 0; r < GEMV_ROWS; ++r)
+      for (int r = 0; r < GEMV_ROWS; ++r) {
         w[u][r] = c < kc16 ? __builtin_nontemporal_load((const u32x4_t*)(wr[r] + c * 16)) : u32x4_t{0u, 0u, 0u, 0u};   // code 0 = +0
+        if constexpr (F == WF_W4) sc[u][r] = c < kc16 ? e8m0_to_f32(sr[r][c]) : 1.0f;
+      }
     }
 #pragma unroll
     for (int u = 0; u < GEMV_UNR; ++u) {
       const int c = (s0 + u) * 64 + lane;
       if ((s0 + u) * 64 < kc16) {                       // (wave-uniform: whole steps beyond K are skipped)
         const int cc = c < kc16 ? c : kc16 - 1;          // lanes past the end read valid chunks against their zero weights
-        float wf[GEMV_ROWS][16];
+        float wf[GEMV_ROWS][8 * XC];
 #pragma unroll
         for (int r = 0; r < GEMV_ROWS; ++r)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) fp8x4_to_f32(w[u][r][j], &wf[r][4 * j]);
+          for (int j = 0; j < 4; ++j) {
+            if constexpr (F == WF_W4) fp4x8_to_f32(w[u][r][j], sc[u][r], &wf[r][8 * j]);
+            else fp8x4_to_f32(w[u][r][j], &wf[r][4 * j]);
+          }
 #pragma unroll
         for (int m = 0; m < M; ++m) {
 #pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const u32x4_t xv = xs[m * kc + 2 * cc + h];
+          for (int h = 0; h < XC; ++h) {
+            const u32x4_t xv = xs[m * kc + XC * cc + h];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               const float xl = bflo(xv[j]), xh = bfhi(xv[j]);
@@ -127,9 +174,9 @@ __device__ __forceinline__ void gemv_w8_rows(const uint8_t* const* wr, const u32
     }
   }
 }
-template <int M, int PRE, bool W8>
-__global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x, long long ldx, const typename welem<W8>::t* __restrict__ W,
-                                                   long long ldw, const float* __restrict__ w_scale, bf16_t* __restrict__ out, long long ldo,
+template <int M, int PRE, WFmt F>
+__global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x, long long ldx, const typename welem<F>::t* __restrict__ W,
+                                                   long long ldw, typename welem<F>::scale_t w_scale, bf16_t* __restrict__ out, long long ldo,
                                                    long long out_bs, int rpb, const bf16_t* __restrict__ res, long long ld_res, int N, int K,
                                                    const bf16_t* __restrict__ pre_w, float eps, const float* __restrict__ rope_cos,
                                                    const float* __restrict__ rope_sin, int rope_cols) {
@@ -205,14 +252,17 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
     const int n0 = rot ? (set >> 6) * 128 + (set & 63) : set * GEMV_ROWS;
     const int nstep = rot ? 64 : 1;
     float acc[GEMV_ROWS][M];
-    const typename welem<W8>::t* wr[GEMV_ROWS];
+    const typename welem<F>::t* wr[GEMV_ROWS];
+    const uint8_t* sr[GEMV_ROWS];                         // W4: the rows' scale bytes
 #pragma unroll
     for (int r = 0; r < GEMV_ROWS; ++r) {
       wr[r] = W + (long long)(n0 + r * nstep < N ? n0 + r * nstep : N - 1) * ldw;
+      if constexpr (F == WF_W4) sr[r] = w_scale.p + (long long)(n0 + r * nstep < N ? n0 + r * nstep : N - 1) * w_scale.ld;
+      else sr[r] = nullptr;
 #pragma unroll
       for (int m = 0; m < M; ++m) acc[r][m] = 0.f;
     }
-    if constexpr (W8) gemv_w8_rows<M>(wr, xs, kc, lane, acc);
+    if constexpr (F != WF_BF16) gemv_wq_rows<M, F>(wr, sr, xs, kc, lane, acc);
     else
     for (int s0 = 0; s0 < steps; s0 += GEMV_UNR) {
       u32x4_t w[GEMV_UNR][GEMV_ROWS];
@@ -256,7 +306,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
             v = (rr == r && mm == m) ? acc[rr][mm] : v;
             partner = (rr != r && mm == m) ? acc[rr][mm] : partner;
           }
-        if constexpr (W8) {
+        if constexpr (F == WF_W8) {
           v = __fmul_rn(v, w_scale[n0 + r * nstep]);
           if (rot) partner = __fmul_rn(partner, w_scale[n0 + (1 - r) * nstep]);
         }
@@ -431,9 +481,9 @@ constexpr int SK_NW = 8;
 // each to bf16 (what the plain form would store), applies swiglu_fwd_elem and stores out [M, N]: a weight row's sum depends only on
 // the row, the K split and the order, so the result is swiglu_fwd of the plain form's output bit for bit, and the packed rows never
 // reach memory.
-template <int MB, int PRE, bool W8, bool GU = false>
-__global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* __restrict__ x, long long ldx, const typename welem<W8>::t* __restrict__ W,
-                                                                 long long ldw, const float* __restrict__ w_scale, bf16_t* __restrict__ out,
+template <int MB, int PRE, WFmt F, bool GU = false>
+__global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* __restrict__ x, long long ldx, const typename welem<F>::t* __restrict__ W,
+                                                                 long long ldw, typename welem<F>::scale_t w_scale, bf16_t* __restrict__ out,
                                                                  long long ldo, long long out_bs, int rpb,
                                                                  const bf16_t* __restrict__ res, long long ld_res, int M, int N, int K,
                                                                  const bf16_t* __restrict__ pre_w, float eps, const float* __restrict__ rope_cos,
@@ -487,7 +537,9 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* _
   const int nrows = GU ? 2 * N : N;                                  // rows of W
   const int nrow = GU ? ((li & 8) ? N : 0) + tile * 8 + (li & 7)
                       : (rot ? (tile >> 3) * 128 + ((li & 8) ? 64 : 0) + (tile & 7) * 8 + (li & 7) : tile * 16 + li);
-  const typename welem<W8>::t* wr = W + (long long)(nrow < nrows ? nrow : nrows - 1) * ldw;
+  const typename welem<F>::t* wr = W + (long long)(nrow < nrows ? nrow : nrows - 1) * ldw;
+  const uint8_t* sr = nullptr;                                       // W4: the row's scale bytes
+  if constexpr (F == WF_W4) sr = w_scale.p + (long long)(nrow < nrows ? nrow : nrows - 1) * w_scale.ld;
   const bf16_t* xr[MB];
   bool xok[MB];
   float xrs[MB];
@@ -498,22 +550,28 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* _
     xr[mb] = x + (long long)(xok[mb] ? m : 0) * ldx;
     xrs[mb] = (PRE == 1 && xok[mb]) ? rstd[m] : 0.f;
   }
-  const int steps = W8 ? (K + 63) >> 6 : (K + 31) >> 5, spw = (steps + SK_NW - 1) / SK_NW;
+  const int steps = F != WF_BF16 ? (K + 63) >> 6 : (K + 31) >> 5, spw = (steps + SK_NW - 1) / SK_NW;
   const int s_beg = wave * spw, s_end = s_beg + spw < steps ? s_beg + spw : steps;
   f32x4_t acc[MB];
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb) acc[mb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   const u32x4_t zero = {0u, 0u, 0u, 0u};
-  if constexpr (W8) {
+  if constexpr (F != WF_BF16) {
     // the W loads of UW steps are issued first (the bytes in flight per lane of the bf16 form at MB <= 2), the x / norm-weight loads
     // (L2 hits, twice as many per W load as in the bf16 form) in rounds of UX steps behind them
+    // W4: the same 64-wide step and lane map -- a lane's 16 codes are 8 B inside ONE scale block (k >> 5), whose byte is fetched with them
     constexpr int UW = 8, UX = NB <= 1 ? 8 : (NB <= 2 ? 4 : (NB <= 4 ? 2 : 1));
+    typedef typename welem<F>::load_t wload_t;
     for (int s0 = s_beg; s0 < s_end; s0 += UW) {
-      u32x4_t a[UW];
+      wload_t a[UW];
+      float sc[UW];
 #pragma unroll
       for (int u = 0; u < UW; ++u) {
         const int k = (s0 + u) * 64 + g * 16;
-        a[u] = (s0 + u < s_end && k < K) ? __builtin_nontemporal_load((const u32x4_t*)(wr + k)) : zero;   // code 0 = +0
+        const bool ok = s0 + u < s_end && k < K;
+        a[u] = ok ? __builtin_nontemporal_load((const wload_t*)(wr + (F == WF_W4 ? k >> 1 : k))) : wload_t{};   // code 0 = +0
+        if constexpr (F == WF_W4) sc[u] = ok ? e8m0_to_f32(sr[k >> 5]) : 1.0f;
+        else sc[u] = 1.0f;
       }
 #pragma unroll
       for (int u0 = 0; u0 < UW; u0 += UX) {
@@ -537,7 +595,7 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* _
           if (s0 + u0 + u < s_end) {                                   // wave-uniform
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-              const u32x4_t af = fp8x8_to_bf16(a[u0 + u][2 * h], a[u0 + u][2 * h + 1]);
+              const u32x4_t af = wq_frag<F>(a[u0 + u], h, sc[u0 + u]);
               float wv[8];
               if (PRE == 1) unpack8f(nw[u][h], wv);
 #pragma unroll
@@ -623,7 +681,7 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* _
       for (int w = 0; w < SK_NW; ++w) gs += lds[((w * MB + mb) * 4 + (i & 3)) * 64 + (i >> 2) * 16 + col];
 #pragma unroll
       for (int w = 0; w < SK_NW; ++w) us += lds[((w * MB + mb) * 4 + (iu & 3)) * 64 + (iu >> 2) * 16 + col];
-      if constexpr (W8) {
+      if constexpr (F == WF_W8) {
         gs = __fmul_rn(gs, w_scale[n]);
         us = __fmul_rn(us, w_scale[N + n]);
       }
@@ -639,13 +697,13 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* _
     float v = 0.f, partner = 0.f;
 #pragma unroll
     for (int w = 0; w < SK_NW; ++w) v += lds[((w * MB + mb) * 4 + (i & 3)) * 64 + (i >> 2) * 16 + col];
-    if constexpr (W8) v = __fmul_rn(v, w_scale[n]);
+    if constexpr (F == WF_W8) v = __fmul_rn(v, w_scale[n]);
     if (res) v += bf2f(res[(long long)m * ld_res + n]);
     if (rot) {
       const int ip = i ^ 8;
 #pragma unroll
       for (int w = 0; w < SK_NW; ++w) partner += lds[((w * MB + mb) * 4 + (ip & 3)) * 64 + (ip >> 2) * 16 + col];
-      if constexpr (W8) partner = __fmul_rn(partner, w_scale[n ^ 64]);  // the rotation partner's row: d <-> d + 64 of the same head
+      if constexpr (F == WF_W8) partner = __fmul_rn(partner, w_scale[n ^ 64]);  // the rotation partner's row: d <-> d + 64 of the same head
       // gemv_kernel's epilogue: rope_kernel's arithmetic on the bf16-rounded projection
       const int d = n & 63, pos = m % rpb;
       const float c = rope_cos[pos * 64 + d], sn = rope_sin[pos * 64 + d];
@@ -674,9 +732,9 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_skinny_kernel(const bf16_t* _
 // all 16 at once spilled; the decode of its A fragments is common to both rounds and compiled once: 16 conversions per 64 MFMAs of a
 // K step in the gfx950 code) --, the W loads of UW steps are issued in front of them. Per accumulator the MFMA order is (s, h) ascending over gemm_skinny_kernel<MB, 0, true>'s K ranges, the
 // waves are summed in its order and w_scale[n] multiplies the finished sum: every 64-row slice is bit for bit that kernel's output.
-template <int NT, int MB, bool W8>
-__global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* __restrict__ x, long long ldx, const typename welem<W8>::t* __restrict__ W,
-                                                                 long long ldw, const float* __restrict__ w_scale,
+template <int NT, int MB, WFmt F>
+__global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* __restrict__ x, long long ldx, const typename welem<F>::t* __restrict__ W,
+                                                                 long long ldw, typename welem<F>::scale_t w_scale,
                                                                  bf16_t* __restrict__ out, long long ldo, long long out_bs, int rpb,
                                                                  const int* __restrict__ slot, int cap_rows, const bf16_t* __restrict__ res,
                                                                  long long ld_res, int M, int N, int K, const float* __restrict__ rope_cos,
@@ -689,13 +747,16 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* _
   __shared__ __attribute__((aligned(16))) float lds[SK_NW * MG * 256];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
   const int tile0 = blockIdx.x * NT;
-  const typename welem<W8>::t* wr[NT];
+  const typename welem<F>::t* wr[NT];
+  const uint8_t* sr[NT];                                               // W4: the rows' scale bytes
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     const int tile = tile0 + nt;
     const bool rot = rope_cos != nullptr && tile * 16 < rope_cols;
     const int nrow = rot ? (tile >> 3) * 128 + ((li & 8) ? 64 : 0) + (tile & 7) * 8 + (li & 7) : tile * 16 + li;
     wr[nt] = W + (long long)(nrow < N ? nrow : N - 1) * ldw;
+    if constexpr (F == WF_W4) sr[nt] = w_scale.p + (long long)(nrow < N ? nrow : N - 1) * w_scale.ld;
+    else sr[nt] = nullptr;
   }
   const bf16_t* xr[MB];
   bool xok[MB];
@@ -705,7 +766,7 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* _
     xok[mb] = m < M;
     xr[mb] = x + (long long)(xok[mb] ? m : 0) * ldx;
   }
-  const int steps = W8 ? (K + 63) >> 6 : (K + 31) >> 5, spw = (steps + SK_NW - 1) / SK_NW;
+  const int steps = F != WF_BF16 ? (K + 63) >> 6 : (K + 31) >> 5, spw = (steps + SK_NW - 1) / SK_NW;
   const int s_beg = wave * spw, s_end = s_beg + spw < steps ? s_beg + spw : steps;
   f32x4_t acc[NT][MB];
 #pragma unroll
@@ -713,19 +774,25 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* _
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) acc[nt][mb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   const u32x4_t zero = {0u, 0u, 0u, 0u};
-  if constexpr (W8) {
+  if constexpr (F != WF_BF16) {
+    typedef typename welem<F>::load_t wload_t;                         // gemm_skinny_kernel's: 16 B (W8) / 8 B inside one scale block (W4)
     constexpr int UW = U;                                              // the bf16 form's W bytes in flight per lane
     constexpr int HX = MB <= 1 ? 16 : (MB <= 2 ? 8 : (MB <= 4 ? 4 : (MB <= 8 ? 2 : 1)));   // half steps per x load round: <= 16 loads
     constexpr int MX = MB <= 8 ? MB : 8;                               // x blocks per load round (16 blocks: two rounds per half step)
     static_assert((2 * UW) % HX == 0 && HX <= 2 * UW && MB % MX == 0, "x load rounds tile the W batch");
     for (int s0 = s_beg; s0 < s_end; s0 += UW) {
-      u32x4_t a[UW][NT];
+      wload_t a[UW][NT];
+      float sc[UW][NT];                                                // W4: the block's scale, fetched with the codes
 #pragma unroll
       for (int u = 0; u < UW; ++u) {
         const int k = (s0 + u) * 64 + g * 16;
         const bool ok = s0 + u < s_end && k < K;
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) a[u][nt] = ok ? __builtin_nontemporal_load((const u32x4_t*)(wr[nt] + k)) : zero;   // code 0 = +0
+        for (int nt = 0; nt < NT; ++nt) {
+          a[u][nt] = ok ? __builtin_nontemporal_load((const wload_t*)(wr[nt] + (F == WF_W4 ? k >> 1 : k))) : wload_t{};   // code 0 = +0
+          if constexpr (F == WF_W4) sc[u][nt] = ok ? e8m0_to_f32(sr[nt][k >> 5]) : 1.0f;
+          else sc[u][nt] = 1.0f;
+        }
       }
 #pragma unroll
       for (int q0 = 0; q0 < 2 * UW; q0 += HX) {
@@ -746,7 +813,7 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* _
             if (s0 + u < s_end) {                                      // wave-uniform
 #pragma unroll
               for (int nt = 0; nt < NT; ++nt) {
-                const u32x4_t af = fp8x8_to_bf16(a[u][nt][2 * h], a[u][nt][2 * h + 1]);
+                const u32x4_t af = wq_frag<F>(a[u][nt], h, sc[u][nt]);
 #pragma unroll
                 for (int mb = 0; mb < MX; ++mb)
                   acc[nt][m0 + mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(af), as_frag(b[j][mb]), acc[nt][m0 + mb], 0, 0, 0);
@@ -807,13 +874,13 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_suffix_kernel(const bf16_t* _
         float v = 0.f, partner = 0.f;
 #pragma unroll
         for (int w = 0; w < SK_NW; ++w) v += lds[((w * MG + mb) * 4 + (i & 3)) * 64 + (i >> 2) * 16 + col];
-        if constexpr (W8) v = __fmul_rn(v, w_scale[n]);
+        if constexpr (F == WF_W8) v = __fmul_rn(v, w_scale[n]);
         if (res) v += bf2f(res[(long long)m * ld_res + n]);
         if (rot) {
           const int ip = i ^ 8;
 #pragma unroll
           for (int w = 0; w < SK_NW; ++w) partner += lds[((w * MG + mb) * 4 + (ip & 3)) * 64 + (ip >> 2) * 16 + col];
-          if constexpr (W8) partner = __fmul_rn(partner, w_scale[n ^ 64]);   // the rotation partner's row: d <-> d + 64 of the same head
+          if constexpr (F == WF_W8) partner = __fmul_rn(partner, w_scale[n ^ 64]);   // the rotation partner's row: d <-> d + 64 of the same head
           // gemv_kernel's epilogue: rope_kernel's arithmetic on the bf16-rounded projection, at the row's position in its sample
           const int d = n & 63;
           const float c = rope_cos[(long long)pos * 64 + d], sn = rope_sin[(long long)pos * 64 + d];
@@ -1180,6 +1247,57 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16_t* __res
   }
 }
 
+// ---- weight quantiser for the W4 projections (OCP MXFP4): one workgroup per row of W [N, K] bf16, one thread per block of 32 elements
+// (64 B in, 16 B of codes + one scale byte out). Everything is integer work on the bf16 bits or an exact fp32 product, so the CPU
+// statement gives the same bytes:
+//   amax = the block's largest |w|, E = its exponent field - 127;  e = clamp(E - 2, -125, 125);  scale byte = e + 127
+//   code = sign | index of round-to-nearest(|w| / 2^e) on {0, 0.5, 1, 1.5, 2, 3, 4, 6}, ties to the even mantissa bit, saturating at 6
+// |w| * 2^-e is exact in fp32 (a power-of-two factor; what underflows is far below the first threshold 0.25). An all-zero block gives
+// byte 127 and codes +0. Non-finite input is not supported. No reduction across threads, no atomics: two runs give the same bytes.
+__device__ __forceinline__ uint32_t e2m1_index(const float a) {
+  // thresholds with their ties: 0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4
+  return a <= 0.25f ? 0u : (a < 0.75f ? 1u : (a <= 1.25f ? 2u : (a < 1.75f ? 3u : (a <= 2.5f ? 4u : (a < 3.5f ? 5u : (a <= 5.0f ? 6u : 7u))))));
+}
+__global__ __launch_bounds__(256) void quant_mxfp4_rows_kernel(const bf16_t* __restrict__ W, long long ldw, uint8_t* __restrict__ q, long long ldq,
+                                                               uint8_t* __restrict__ s, long long lds, int K) {
+  const bf16_t* wr = W + (long long)blockIdx.x * ldw;
+  uint8_t* qr = q + (long long)blockIdx.x * ldq;
+  uint8_t* sr = s + (long long)blockIdx.x * lds;
+  for (int b = threadIdx.x; b < (K >> 5); b += 256) {
+    u32x4_t v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = *(const u32x4_t*)(wr + b * 32 + i * 8);
+    uint32_t amax = 0u;                                  // bf16 bits without the sign: ordered like the magnitudes
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t lo = v[i][j] & 0x7fffu, hi = (v[i][j] >> 16) & 0x7fffu;
+        amax = amax > lo ? amax : lo;
+        amax = amax > hi ? amax : hi;
+      }
+    int e = (int)(amax >> 7) - 127 - 2;
+    e = e < -125 ? -125 : (e > 125 ? 125 : e);
+    if (amax == 0u) e = 0;
+    const float inv = __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);     // 2^-e
+    u32x4_t o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      uint32_t word = 0u;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t lo = v[i][j] & 0xffffu, hi = v[i][j] >> 16;
+        const uint32_t cl = e2m1_index(__builtin_bit_cast(float, (lo & 0x7fffu) << 16) * inv) | ((lo >> 12) & 8u);
+        const uint32_t ch = e2m1_index(__builtin_bit_cast(float, (hi & 0x7fffu) << 16) * inv) | ((hi >> 12) & 8u);
+        word |= (cl | (ch << 4)) << (8 * j);
+      }
+      o[i] = amax == 0u ? 0u : word;
+    }
+    *(u32x4_t*)(qr + b * 16) = o;
+    sr[b] = (uint8_t)(e + 127);
+  }
+}
+
 }  // namespace
 
 // launch epilogue of the entry points that serve two exported names (MLA_LAUNCH_CHECK reports __func__)
@@ -1192,18 +1310,31 @@ static int launch_status(const char* name) {
 
 #define AL16(p) ((((uintptr_t)(p)) & 15) == 0)
 
+// What the entry points check and pass per weight format: K must be a multiple of KQ (bf16: a 16-B load; W8: a lane's 16 codes; W4: a
+// scale block), ldw (elements of W's type: bf16 elements, or bytes) a multiple of LQ (16-B aligned rows), a W4 row holds K / 2 bytes and
+// its scale row K / 32
+template <WFmt F> struct wfmt_args {
+  static constexpr int KQ = F == WF_W4 ? 32 : (F == WF_W8 ? 16 : 8), LQ = F == WF_BF16 ? 8 : 16;
+  static bool scale_ok(const void* w_scale, long long ld_scale, int K) { return F == WF_BF16 || (w_scale && (F != WF_W4 || ld_scale >= K / 32)); }
+  static bool row_ok(long long ldw, int K) { return ldw % LQ == 0 && (F != WF_W4 || ldw >= K / 2); }
+  static typename welem<F>::scale_t scale(const void* w_scale, long long ld_scale) {
+    if constexpr (F == WF_W4) return w4_scales{(const uint8_t*)w_scale, ld_scale};
+    else return (const float*)w_scale;
+  }
+};
+
 // mla_gemv_bf16 / mla_gemv_w8: one validation + launch path, W8 selects the weight format (ldw in elements of it)
-template <bool W8>
-static int gemv_entry(const char* name, const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
+template <WFmt F>
+static int gemv_entry(const char* name, const void* x, long long ldx, const void* W, long long ldw, const void* w_scale, long long ld_scale, void* out, long long ldo,
                       long long out_batch_stride, int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre,
                       const void* pre_w, float eps, const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
-  constexpr int KQ = W8 ? 16 : 8;                                         // weights per 16-B load
-  MLA_CHECK_ARG(x && W && out && (!W8 || w_scale), "%s: null pointer", name);
+  constexpr int KQ = wfmt_args<F>::KQ;
+  MLA_CHECK_ARG(x && W && out && wfmt_args<F>::scale_ok(w_scale, ld_scale, K > 0 ? K : 0), "%s: null pointer (or a W4 scale row shorter than K / 32)", name);
   MLA_CHECK_ARG((rope_cos == nullptr) == (rope_sin == nullptr) && (!rope_cos || (rope_cols > 0 && rope_cols % 128 == 0 && rope_cols <= N && !residual)),
                 "%s: the RoPE epilogue needs both tables, rope_cols a multiple of 128 and <= N, and no residual", name);
   MLA_CHECK_ARG(pre >= 0 && pre <= 2 && (pre != 1 || (pre_w && AL16(pre_w))), "%s: pre must be 0, 1 (RMSNorm: 16-B aligned weight needed) or 2 (SwiGLU)", name);
   MLA_CHECK_ARG(M >= 1 && M <= GEMV_MMAX && N >= 1 && K >= KQ && K % KQ == 0 && rows_per_batch >= 1, "%s: 1 <= M <= 8, K %% %d == 0 required (M %d, N %d, K %d)", name, KQ, M, N, K);
-  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && ldw % KQ == 0, "%s: x / W rows must be 16-B aligned", name);
+  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && wfmt_args<F>::row_ok(ldw, K), "%s: x / W rows must be 16-B aligned", name);
   const size_t lds = (size_t)M * K * 2 + 64;
   MLA_CHECK_ARG(lds <= 160 * 1024, "%s: M x K x 2 bytes of input rows (+ 64) must fit the 160 KiB of LDS (M %d, K %d)", name, M, K);
   static int cus = 0;
@@ -1217,9 +1348,9 @@ static int gemv_entry(const char* name, const void* x, long long ldx, const void
 #define MLA_GEMV_LAUNCH(MM, PP)                                                                                                        \
   {                                                                                                                                    \
     static bool attr = false;                                                                                                          \
-    if (!attr) { (void)hipFuncSetAttribute((const void*)gemv_kernel<MM, PP, W8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-    hipLaunchKernelGGL((gemv_kernel<MM, PP, W8>), dim3(blocks), dim3(256), lds, stream, (const bf16_t*)x, ldx, (const typename welem<W8>::t*)W, ldw, \
-                       w_scale, (bf16_t*)out, ldo, out_batch_stride, rows_per_batch, (const bf16_t*)residual, ld_res, N, K, (const bf16_t*)pre_w, eps, \
+    if (!attr) { (void)hipFuncSetAttribute((const void*)gemv_kernel<MM, PP, F>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
+    hipLaunchKernelGGL((gemv_kernel<MM, PP, F>), dim3(blocks), dim3(256), lds, stream, (const bf16_t*)x, ldx, (const typename welem<F>::t*)W, ldw, \
+                       wfmt_args<F>::scale(w_scale, ld_scale), (bf16_t*)out, ldo, out_batch_stride, rows_per_batch, (const bf16_t*)residual, ld_res, N, K, (const bf16_t*)pre_w, eps, \
                        rope_cos, rope_sin, rope_cos ? rope_cols : 0);                                                                  \
   }
 #define MLA_GEMV_CASE(MM)                                                                                                              \
@@ -1237,15 +1368,23 @@ static int gemv_entry(const char* name, const void* x, long long ldx, const void
 extern "C" int mla_gemv_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
                              int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre, const void* pre_w, float eps,
                              const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
-  return gemv_entry<false>("mla_gemv_bf16", x, ldx, W, ldw, nullptr, out, ldo, out_batch_stride, rows_per_batch, residual, ld_res, M, N, K, pre, pre_w,
+  return gemv_entry<WF_BF16>("mla_gemv_bf16", x, ldx, W, ldw, nullptr, 0, out, ldo, out_batch_stride, rows_per_batch, residual, ld_res, M, N, K, pre, pre_w,
                            eps, rope_cos, rope_sin, rope_cols, stream);
 }
 
 extern "C" int mla_gemv_w8(const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
                            long long out_batch_stride, int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre,
                            const void* pre_w, float eps, const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
-  return gemv_entry<true>("mla_gemv_w8", x, ldx, W, ldw, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual, ld_res, M, N, K, pre, pre_w,
-                          eps, rope_cos, rope_sin, rope_cols, stream);
+  return gemv_entry<WF_W8>("mla_gemv_w8", x, ldx, W, ldw, w_scale, 0, out, ldo, out_batch_stride, rows_per_batch, residual, ld_res, M, N, K, pre, pre_w,
+                           eps, rope_cos, rope_sin, rope_cols, stream);
+}
+
+extern "C" int mla_gemv_w4(const void* x, long long ldx, const void* W, long long ldw, const void* w_scale, long long ld_scale, void* out,
+                           long long ldo, long long out_batch_stride, int rows_per_batch, const void* residual, long long ld_res, int M, int N,
+                           int K, int pre, const void* pre_w, float eps, const float* rope_cos, const float* rope_sin, int rope_cols,
+                           hipStream_t stream) {
+  return gemv_entry<WF_W4>("mla_gemv_w4", x, ldx, W, ldw, w_scale, ld_scale, out, ldo, out_batch_stride, rows_per_batch, residual, ld_res, M, N, K,
+                           pre, pre_w, eps, rope_cos, rope_sin, rope_cols, stream);
 }
 
 extern "C" int mla_attn_decode(const void* q, const void* k, const void* v, void* o, int B, int H, int head_dim, int S_kv, int R, long long ld,
@@ -1264,23 +1403,23 @@ extern "C" int mla_attn_decode(const void* q, const void* k, const void* v, void
 }
 
 // mla_gemm_skinny_bf16 / mla_gemm_skinny_w8: one validation + launch path, W8 selects the weight format
-template <bool W8>
-static int skinny_entry(const char* name, const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
+template <WFmt F>
+static int skinny_entry(const char* name, const void* x, long long ldx, const void* W, long long ldw, const void* w_scale, long long ld_scale, void* out, long long ldo,
                         long long out_batch_stride, int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre,
                         const void* pre_w, float eps, const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
-  constexpr int KQ = W8 ? 16 : 8;
-  MLA_CHECK_ARG(x && W && out && (!W8 || w_scale), "%s: null pointer", name);
+  constexpr int KQ = wfmt_args<F>::KQ;
+  MLA_CHECK_ARG(x && W && out && wfmt_args<F>::scale_ok(w_scale, ld_scale, K > 0 ? K : 0), "%s: null pointer (or a W4 scale row shorter than K / 32)", name);
   MLA_CHECK_ARG((rope_cos == nullptr) == (rope_sin == nullptr) && (!rope_cos || (rope_cols > 0 && rope_cols % 128 == 0 && rope_cols <= N && !residual)),
                 "%s: the RoPE epilogue needs both tables, rope_cols a multiple of 128 and <= N, and no residual", name);
   MLA_CHECK_ARG(pre >= 0 && pre <= 2 && (pre != 1 || (pre_w && AL16(pre_w))),
                 "%s: pre must be 0, 1 (RMSNorm: 16-B aligned weight needed) or 2 (SwiGLU)", name);
   MLA_CHECK_ARG(M >= 1 && M <= SK_MMAX && N >= 1 && K >= KQ && K % KQ == 0 && rows_per_batch >= 1,
                 "%s: 1 <= M <= 64, K %% %d == 0 required (M %d, N %d, K %d)", name, KQ, M, N, K);
-  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && ldw % KQ == 0, "%s: x / W rows must be 16-B aligned", name);
+  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && wfmt_args<F>::row_ok(ldw, K), "%s: x / W rows must be 16-B aligned", name);
   const int tiles = (N + 15) / 16;
 #define MLA_SK_LAUNCH(MB, PP)                                                                                                          \
-  hipLaunchKernelGGL((gemm_skinny_kernel<MB, PP, W8>), dim3(tiles), dim3(64 * SK_NW), 0, stream, (const bf16_t*)x, ldx,                 \
-                     (const typename welem<W8>::t*)W, ldw, w_scale, (bf16_t*)out, ldo, out_batch_stride, rows_per_batch,                \
+  hipLaunchKernelGGL((gemm_skinny_kernel<MB, PP, F>), dim3(tiles), dim3(64 * SK_NW), 0, stream, (const bf16_t*)x, ldx,                  \
+                     (const typename welem<F>::t*)W, ldw, wfmt_args<F>::scale(w_scale, ld_scale), (bf16_t*)out, ldo, out_batch_stride, rows_per_batch,                \
                      (const bf16_t*)residual, ld_res, M, N, K, (const bf16_t*)pre_w, eps, rope_cos, rope_sin, rope_cos ? rope_cols : 0)
 #define MLA_SK_CASE(MB)                                                                                                                \
   case MB:                                                                                                                             \
@@ -1295,7 +1434,7 @@ static int skinny_entry(const char* name, const void* x, long long ldx, const vo
 extern "C" int mla_gemm_skinny_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
                                     int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K, int pre, const void* pre_w,
                                     float eps, const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
-  return skinny_entry<false>("mla_gemm_skinny_bf16", x, ldx, W, ldw, nullptr, out, ldo, out_batch_stride, rows_per_batch, residual, ld_res, M, N, K,
+  return skinny_entry<WF_BF16>("mla_gemm_skinny_bf16", x, ldx, W, ldw, nullptr, 0, out, ldo, out_batch_stride, rows_per_batch, residual, ld_res, M, N, K,
                              pre, pre_w, eps, rope_cos, rope_sin, rope_cols, stream);
 }
 
@@ -1303,24 +1442,33 @@ extern "C" int mla_gemm_skinny_w8(const void* x, long long ldx, const void* W, l
                                   long long out_batch_stride, int rows_per_batch, const void* residual, long long ld_res, int M, int N, int K,
                                   int pre, const void* pre_w, float eps, const float* rope_cos, const float* rope_sin, int rope_cols,
                                   hipStream_t stream) {
-  return skinny_entry<true>("mla_gemm_skinny_w8", x, ldx, W, ldw, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual, ld_res, M, N, K,
-                            pre, pre_w, eps, rope_cos, rope_sin, rope_cols, stream);
+  return skinny_entry<WF_W8>("mla_gemm_skinny_w8", x, ldx, W, ldw, w_scale, 0, out, ldo, out_batch_stride, rows_per_batch, residual, ld_res, M, N, K,
+                             pre, pre_w, eps, rope_cos, rope_sin, rope_cols, stream);
+}
+
+extern "C" int mla_gemm_skinny_w4(const void* x, long long ldx, const void* W, long long ldw, const void* w_scale, long long ld_scale, void* out,
+                                  long long ldo, long long out_batch_stride, int rows_per_batch, const void* residual, long long ld_res, int M,
+                                  int N, int K, int pre, const void* pre_w, float eps, const float* rope_cos, const float* rope_sin, int rope_cols,
+                                  hipStream_t stream) {
+  return skinny_entry<WF_W4>("mla_gemm_skinny_w4", x, ldx, W, ldw, w_scale, ld_scale, out, ldo, out_batch_stride, rows_per_batch, residual, ld_res,
+                             M, N, K, pre, pre_w, eps, rope_cos, rope_sin, rope_cols, stream);
 }
 
 // mla_gemm_skinny_gateup_swiglu_bf16 / _w8: gemm_skinny_kernel's GU form (gate|up projection with the SwiGLU epilogue)
-template <bool W8>
-static int skinny_gateup_entry(const char* name, const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out,
+template <WFmt F>
+static int skinny_gateup_entry(const char* name, const void* x, long long ldx, const void* W, long long ldw, const void* w_scale, long long ld_scale, void* out,
                                long long ldo, int M, int I, int K, hipStream_t stream) {
-  constexpr int KQ = W8 ? 16 : 8;
-  MLA_CHECK_ARG(x && W && out && (!W8 || w_scale), "%s: null pointer", name);
+  constexpr int KQ = wfmt_args<F>::KQ;
+  MLA_CHECK_ARG(x && W && out && wfmt_args<F>::scale_ok(w_scale, ld_scale, K > 0 ? K : 0), "%s: null pointer (or a W4 scale row shorter than K / 32)", name);
   MLA_CHECK_ARG(M >= 1 && M <= SK_MMAX && I >= 8 && I % 8 == 0 && K >= KQ && K % KQ == 0,
                 "%s: 1 <= M <= 64, I %% 8 == 0, K %% %d == 0 required (M %d, I %d, K %d)", name, KQ, M, I, K);
-  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && ldw % KQ == 0 && ldx >= K && ldw >= K, "%s: x / W rows must be 16-B aligned and hold K elements", name);
+  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && wfmt_args<F>::row_ok(ldw, K) && ldx >= K && (F == WF_W4 || ldw >= K),
+                "%s: x / W rows must be 16-B aligned and hold K elements", name);
   MLA_CHECK_ARG(ldo >= I, "%s: ldo %lld < I %d", name, ldo, I);
 #define MLA_SKGU_CASE(MB)                                                                                                              \
   case MB:                                                                                                                             \
-    hipLaunchKernelGGL((gemm_skinny_kernel<MB, 0, W8, true>), dim3(I / 8), dim3(64 * SK_NW), 0, stream, (const bf16_t*)x, ldx,          \
-                       (const typename welem<W8>::t*)W, ldw, w_scale, (bf16_t*)out, ldo, 0LL, M, (const bf16_t*)nullptr, 0LL, M, I, K,  \
+    hipLaunchKernelGGL((gemm_skinny_kernel<MB, 0, F, true>), dim3(I / 8), dim3(64 * SK_NW), 0, stream, (const bf16_t*)x, ldx,           \
+                       (const typename welem<F>::t*)W, ldw, wfmt_args<F>::scale(w_scale, ld_scale), (bf16_t*)out, ldo, 0LL, M, (const bf16_t*)nullptr, 0LL, M, I, K,  \
                        (const bf16_t*)nullptr, 0.f, (const float*)nullptr, (const float*)nullptr, 0);                                  \
     break;
   switch ((M + 15) / 16) { MLA_SKGU_CASE(1) MLA_SKGU_CASE(2) MLA_SKGU_CASE(3) MLA_SKGU_CASE(4) }
@@ -1330,12 +1478,17 @@ static int skinny_gateup_entry(const char* name, const void* x, long long ldx, c
 
 extern "C" int mla_gemm_skinny_gateup_swiglu_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, int M,
                                                   int I, int K, hipStream_t stream) {
-  return skinny_gateup_entry<false>("mla_gemm_skinny_gateup_swiglu_bf16", x, ldx, W, ldw, nullptr, out, ldo, M, I, K, stream);
+  return skinny_gateup_entry<WF_BF16>("mla_gemm_skinny_gateup_swiglu_bf16", x, ldx, W, ldw, nullptr, 0, out, ldo, M, I, K, stream);
 }
 
 extern "C" int mla_gemm_skinny_gateup_swiglu_w8(const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out,
                                                 long long ldo, int M, int I, int K, hipStream_t stream) {
-  return skinny_gateup_entry<true>("mla_gemm_skinny_gateup_swiglu_w8", x, ldx, W, ldw, w_scale, out, ldo, M, I, K, stream);
+  return skinny_gateup_entry<WF_W8>("mla_gemm_skinny_gateup_swiglu_w8", x, ldx, W, ldw, w_scale, 0, out, ldo, M, I, K, stream);
+}
+
+extern "C" int mla_gemm_skinny_gateup_swiglu_w4(const void* x, long long ldx, const void* W, long long ldw, const void* w_scale, long long ld_scale,
+                                                void* out, long long ldo, int M, int I, int K, hipStream_t stream) {
+  return skinny_gateup_entry<WF_W4>("mla_gemm_skinny_gateup_swiglu_w4", x, ldx, W, ldw, w_scale, ld_scale, out, ldo, M, I, K, stream);
 }
 
 // W [N, K] bf16 (ldw) -> q [N, K] e4m3fn codes (ldq, bytes) + scale [N] fp32; see quant_fp8_rows_kernel
@@ -1344,6 +1497,16 @@ extern "C" int mla_quant_fp8_rows(const void* W, long long ldw, void* q, long lo
   MLA_CHECK_ARG(N >= 1 && K >= 16 && K % 16 == 0, "mla_quant_fp8_rows: N >= 1, K %% 16 == 0 required (N %d, K %d)", N, K);
   MLA_CHECK_ARG(AL16(W) && AL16(q) && ldw % 8 == 0 && ldq % 16 == 0 && ldw >= K && ldq >= K, "mla_quant_fp8_rows: W / q rows must be 16-B aligned and hold K elements");
   hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3(N), dim3(256), 0, stream, (const bf16_t*)W, ldw, (uint8_t*)q, ldq, scale, K);
+  MLA_LAUNCH_CHECK();
+}
+
+// W [N, K] bf16 (ldw) -> q [N, K / 2] e2m1 code pairs (ldq, bytes) + s [N, K / 32] e8m0 scale bytes (lds, bytes); see quant_mxfp4_rows_kernel
+extern "C" int mla_quant_mxfp4_rows(const void* W, long long ldw, void* q, long long ldq, void* s, long long lds, int N, int K, hipStream_t stream) {
+  MLA_CHECK_ARG(W && q && s, "mla_quant_mxfp4_rows: null pointer");
+  MLA_CHECK_ARG(N >= 1 && K >= 32 && K % 32 == 0, "mla_quant_mxfp4_rows: N >= 1, K %% 32 == 0 required (N %d, K %d)", N, K);
+  MLA_CHECK_ARG(AL16(W) && AL16(q) && ldw % 8 == 0 && ldq % 16 == 0 && ldw >= K && ldq >= K / 2 && lds >= K / 32,
+                "mla_quant_mxfp4_rows: W / q rows must be 16-B aligned and hold K elements, a scale row K / 32 bytes");
+  hipLaunchKernelGGL(quant_mxfp4_rows_kernel, dim3(N), dim3(256), 0, stream, (const bf16_t*)W, ldw, (uint8_t*)q, ldq, (uint8_t*)s, lds, K);
   MLA_LAUNCH_CHECK();
 }
 
@@ -1447,25 +1610,25 @@ extern "C" int mla_attn_chunk_ragged_groups_gw(const void* q, const void* k, con
 
 // mla_gemm_suffix_bf16(_pos) / mla_gemm_suffix_w8(_pos): one validation + launch path, W8 selects the weight format; rope_pos == nullptr
 // is the form without a separate rotary position (the table row is the cache row)
-template <bool W8>
-static int suffix_entry(const char* name, const void* x, long long ldx, const void* W, long long ldw, const float* w_scale, void* out, long long ldo,
+template <WFmt F>
+static int suffix_entry(const char* name, const void* x, long long ldx, const void* W, long long ldw, const void* w_scale, long long ld_scale, void* out, long long ldo,
                         long long out_batch_stride, int rows_per_batch, const int* slot, int cap_rows, const void* residual, long long ld_res,
                         int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols, const int* rope_pos, int rope_rows,
                         hipStream_t stream) {
-  constexpr int KQ = W8 ? 16 : 8;                                      // elements per 16-B load of W (fp8: ldw is in bytes)
-  MLA_CHECK_ARG(x && W && out && (!W8 || w_scale), "%s: null pointer", name);
+  constexpr int KQ = wfmt_args<F>::KQ;
+  MLA_CHECK_ARG(x && W && out && wfmt_args<F>::scale_ok(w_scale, ld_scale, K > 0 ? K : 0), "%s: null pointer (or a W4 scale row shorter than K / 32)", name);
   MLA_CHECK_ARG((rope_cos == nullptr) == (rope_sin == nullptr) && (!rope_cos || (rope_cols > 0 && rope_cols % 128 == 0 && rope_cols <= N && !residual)),
                 "%s: the RoPE epilogue needs both tables, rope_cols a multiple of 128 and <= N, and no residual", name);
   MLA_CHECK_ARG(M >= 1 && M <= 256 && N >= 1 && K >= KQ && K % KQ == 0 && rows_per_batch >= 1,
                 "%s: 1 <= M <= 256, K %% %d == 0 required (M %d, N %d, K %d)", name, KQ, M, N, K);
   MLA_CHECK_ARG(!slot || cap_rows >= rows_per_batch, "%s: cap_rows (%d) must hold the %d rows of a sample", name, cap_rows, rows_per_batch);
   MLA_CHECK_ARG(!rope_pos || (rope_cos && rope_rows >= 1), "%s: rope_pos needs the RoPE tables and rope_rows >= 1 (got %d)", name, rope_rows);
-  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && ldw % KQ == 0, "%s: x / W rows must be 16-B aligned", name);
+  MLA_CHECK_ARG(AL16(x) && AL16(W) && ldx % 8 == 0 && wfmt_args<F>::row_ok(ldw, K), "%s: x / W rows must be 16-B aligned", name);
   if (!slot) cap_rows = rows_per_batch;
   const int tiles = (N + 15) / 16, blocks = (M + 15) / 16;
 #define MLA_SX_LAUNCH(NT, MB)                                                                                                          \
-  hipLaunchKernelGGL((gemm_suffix_kernel<NT, MB, W8>), dim3((tiles + NT - 1) / NT), dim3(64 * SK_NW), 0, stream, (const bf16_t*)x, ldx,  \
-                     (const typename welem<W8>::t*)W, ldw, w_scale, (bf16_t*)out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows, \
+  hipLaunchKernelGGL((gemm_suffix_kernel<NT, MB, F>), dim3((tiles + NT - 1) / NT), dim3(64 * SK_NW), 0, stream, (const bf16_t*)x, ldx,   \
+                     (const typename welem<F>::t*)W, ldw, wfmt_args<F>::scale(w_scale, ld_scale), (bf16_t*)out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows, \
                      (const bf16_t*)residual, ld_res, M, N, K, rope_cos, rope_sin, rope_cos ? rope_cols : 0, rope_pos, rope_rows)
   if (blocks <= 1) MLA_SX_LAUNCH(1, 1);
   else if (blocks == 2) MLA_SX_LAUNCH(1, 2);
@@ -1481,7 +1644,7 @@ static int suffix_entry(const char* name, const void* x, long long ldx, const vo
 extern "C" int mla_gemm_suffix_bf16(const void* x, long long ldx, const void* W, long long ldw, void* out, long long ldo, long long out_batch_stride,
                                     int rows_per_batch, const int* slot, int cap_rows, const void* residual, long long ld_res, int M, int N, int K,
                                     const float* rope_cos, const float* rope_sin, int rope_cols, hipStream_t stream) {
-  return suffix_entry<false>("mla_gemm_suffix_bf16", x, ldx, W, ldw, nullptr, out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows, residual,
+  return suffix_entry<WF_BF16>("mla_gemm_suffix_bf16", x, ldx, W, ldw, nullptr, 0, out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows, residual,
                              ld_res, M, N, K, rope_cos, rope_sin, rope_cols, nullptr, 0, stream);
 }
 
@@ -1489,7 +1652,7 @@ extern "C" int mla_gemm_suffix_bf16_pos(const void* x, long long ldx, const void
                                         long long out_batch_stride, int rows_per_batch, const int* slot, int cap_rows, const void* residual,
                                         long long ld_res, int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols,
                                         const int* rope_pos, int rope_rows, hipStream_t stream) {
-  return suffix_entry<false>("mla_gemm_suffix_bf16_pos", x, ldx, W, ldw, nullptr, out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows,
+  return suffix_entry<WF_BF16>("mla_gemm_suffix_bf16_pos", x, ldx, W, ldw, nullptr, 0, out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows,
                              residual, ld_res, M, N, K, rope_cos, rope_sin, rope_cols, rope_pos, rope_rows, stream);
 }
 
@@ -1497,7 +1660,7 @@ extern "C" int mla_gemm_suffix_w8(const void* x, long long ldx, const void* W, l
                                   long long out_batch_stride, int rows_per_batch, const int* slot, int cap_rows, const void* residual,
                                   long long ld_res, int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols,
                                   hipStream_t stream) {
-  return suffix_entry<true>("mla_gemm_suffix_w8", x, ldx, W, ldw, w_scale, out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows, residual,
+  return suffix_entry<WF_W8>("mla_gemm_suffix_w8", x, ldx, W, ldw, w_scale, 0, out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows, residual,
                             ld_res, M, N, K, rope_cos, rope_sin, rope_cols, nullptr, 0, stream);
 }
 
@@ -1505,6 +1668,22 @@ extern "C" int mla_gemm_suffix_w8_pos(const void* x, long long ldx, const void* 
                                       long long out_batch_stride, int rows_per_batch, const int* slot, int cap_rows, const void* residual,
                                       long long ld_res, int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols,
                                       const int* rope_pos, int rope_rows, hipStream_t stream) {
-  return suffix_entry<true>("mla_gemm_suffix_w8_pos", x, ldx, W, ldw, w_scale, out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows,
+  return suffix_entry<WF_W8>("mla_gemm_suffix_w8_pos", x, ldx, W, ldw, w_scale, 0, out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows,
                             residual, ld_res, M, N, K, rope_cos, rope_sin, rope_cols, rope_pos, rope_rows, stream);
+}
+
+extern "C" int mla_gemm_suffix_w4(const void* x, long long ldx, const void* W, long long ldw, const void* w_scale, long long ld_scale, void* out,
+                                  long long ldo, long long out_batch_stride, int rows_per_batch, const int* slot, int cap_rows, const void* residual,
+                                  long long ld_res, int M, int N, int K, const float* rope_cos, const float* rope_sin, int rope_cols,
+                                  hipStream_t stream) {
+  return suffix_entry<WF_W4>("mla_gemm_suffix_w4", x, ldx, W, ldw, w_scale, ld_scale, out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows,
+                             residual, ld_res, M, N, K, rope_cos, rope_sin, rope_cols, nullptr, 0, stream);
+}
+
+extern "C" int mla_gemm_suffix_w4_pos(const void* x, long long ldx, const void* W, long long ldw, const void* w_scale, long long ld_scale, void* out,
+                                      long long ldo, long long out_batch_stride, int rows_per_batch, const int* slot, int cap_rows,
+                                      const void* residual, long long ld_res, int M, int N, int K, const float* rope_cos, const float* rope_sin,
+                                      int rope_cols, const int* rope_pos, int rope_rows, hipStream_t stream) {
+  return suffix_entry<WF_W4>("mla_gemm_suffix_w4_pos", x, ldx, W, ldw, w_scale, ld_scale, out, ldo, out_batch_stride, rows_per_batch, slot, cap_rows,
+                             residual, ld_res, M, N, K, rope_cos, rope_sin, rope_cols, rope_pos, rope_rows, stream);
 }

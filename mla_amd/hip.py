@@ -45,6 +45,17 @@ _SIGNATURES = {
     "mla_gemm_skinny_gateup_swiglu_bf16": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_int, c_int, c_void_p],
     "mla_gemm_skinny_gateup_swiglu_w8": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int,
                                          c_void_p],
+    "mla_quant_mxfp4_rows": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_int, c_void_p],
+    "mla_gemv_w4": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p,
+                    c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
+    "mla_gemm_skinny_w4": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p,
+                           c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
+    "mla_gemm_skinny_gateup_swiglu_w4": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_int,
+                                         c_int, c_void_p],
+    "mla_gemm_suffix_w4": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p,
+                           c_int, c_void_p, c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
+    "mla_gemm_suffix_w4_pos": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int,
+                               c_void_p, c_int, c_void_p, c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p],
     "mla_attn_chunk": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_float,
                        c_void_p],
     "mla_attn_chunk_ragged": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_longlong, c_longlong,
@@ -951,9 +962,18 @@ def attn_bwd(q, k, v, o, dout, lse, seqlens, dq, dk, dv, B, S, H, D, ld_qkv, sca
 # --------------------------------------------------------------------------------------------- inference (mla_amd/infer.py)
 def _proj_operands(name, x, W, w_scale, out=None):
     """The operand checks every suffix projection call opens with: x bf16, W bf16 -- or float8_e4m3fn with w_scale (fp32, one per row
-    of W), which selects the `_w8` argument list --, out bf16 where it is given, unit inner strides. Returns the scale argument(s) of
-    the call: () for bf16 weights."""
+    of W), which selects the `_w8` argument list, or MXFP4 code bytes [N, K / 2] uint8 with w_scale [N, K / 32] uint8 (one e8m0 byte per
+    block of 32; its row stride is an argument), which selects the `_w4` one --, out bf16 where it is given, unit inner strides. Returns
+    the scale argument(s) of the call: () for bf16 weights."""
     _req(x, torch.bfloat16, f"{name} x")
+    if w_scale is not None and w_scale.dtype == torch.uint8:
+        _req(W, torch.uint8, f"{name} W")
+        _req(w_scale, torch.uint8, f"{name} w_scale")
+        assert W.dim() == 2 and w_scale.dim() == 2 and w_scale.shape == (W.shape[0], W.shape[1] // 16) and W.shape[1] % 16 == 0
+        assert x.stride(1) == 1 and W.stride(1) == 1 and w_scale.stride(1) == 1
+        if out is not None:
+            _req(out, torch.bfloat16, f"{name} out")
+        return (_p(w_scale), w_scale.stride(0))
     _req(W, torch.bfloat16 if w_scale is None else torch.float8_e4m3fn, f"{name} W")
     scale_arg = ()
     if w_scale is not None:
@@ -966,13 +986,19 @@ def _proj_operands(name, x, W, w_scale, out=None):
     return scale_arg
 
 
+def _weight_k(W) -> int:
+    """K of a projection weight [N, K]: MXFP4 code bytes (uint8) hold two elements each."""
+    return W.shape[1] * (2 if W.dtype == torch.uint8 else 1)
+
+
 def _skinny_call(name, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope, w_scale=None):
-    """The shared call of the four suffix projections; w_scale (fp32 [N]) selects the `_w8` argument list (W: float8_e4m3fn)."""
+    """The shared call of the six suffix projections; w_scale selects the argument list: fp32 [N] the `_w8` one (W: float8_e4m3fn), uint8
+    [N, K / 32] the `_w4` one (W: uint8 code pairs [N, K / 2])."""
     scale_arg = _proj_operands(name, x, W, w_scale, out)
     M = x.shape[0]
     K = x.shape[1] // 2 if swiglu else x.shape[1]
     N = W.shape[0]
-    assert W.shape[1] == K and not (swiglu and norm_weight is not None)
+    assert _weight_k(W) == K and not (swiglu and norm_weight is not None)
     pre = 2 if swiglu else (1 if norm_weight is not None else 0)
     if norm_weight is not None:
         _req(norm_weight, torch.bfloat16, f"{name} norm weight")
@@ -1046,12 +1072,49 @@ def gemm_skinny_w8(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, re
                  w_scale)
 
 
+def quant_mxfp4_rows(W, q=None, s=None):
+    """OCP MXFP4 quantisation of W [N, K] bf16 (rows may be strided; K % 32 == 0) for the `_w4` projections (mla_quant_mxfp4_rows):
+    q [N, K / 2] uint8 -- element 2 j in the low nibble of byte j, nibble = sign (8) | index into {0, 0.5, 1, 1.5, 2, 3, 4, 6} -- and
+    s [N, K / 32] uint8, one e8m0 byte (e + 127) per block of 32 consecutive k of a row, e = clamp(floor(log2 amax) - 2, -125, 125) from
+    the exponent bits; round to nearest, ties to the even mantissa bit, saturating at 6 (include/mla_hip.h has the whole statement).
+    Returns (q, s); both may be given (views of a packed buffer: q rows 16-B aligned, unit inner strides; the scale row stride is passed
+    on). Non-finite input is not supported."""
+    _req(W, torch.bfloat16, "quant_mxfp4_rows W")
+    N, K = W.shape
+    assert W.stride(1) == 1 and K % 32 == 0, "quant_mxfp4_rows: K % 32 == 0 required"
+    if q is None:
+        q = torch.empty((N, K // 2), dtype=torch.uint8, device=W.device)
+    if s is None:
+        s = torch.empty((N, K // 32), dtype=torch.uint8, device=W.device)
+    _req(q, torch.uint8, "quant_mxfp4_rows q")
+    _req(s, torch.uint8, "quant_mxfp4_rows s")
+    assert q.shape == (N, K // 2) and q.stride(1) == 1 and s.shape == (N, K // 32) and s.stride(1) == 1
+    call("mla_quant_mxfp4_rows", _p(W), W.stride(0), _p(q), q.stride(0), _p(s), s.stride(0), N, K)
+    return q, s
+
+
+def gemv_w4(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, norm_weight=None, eps=0.0, swiglu=False,
+            rope=None):
+    """gemv over MXFP4 weights (mla_gemv_w4): W [N, K / 2] uint8 codes, w_scale [N, K / 32] uint8 as quant_mxfp4_rows writes them; the codes
+    are decoded with their block scale (exact in bf16), so out row m = f(x[m]) @ dequantised(W)^T (+ residual[m]) with gemv's single bf16
+    rounding. K % 32 == 0; everything else is gemv's."""
+    _skinny_call("mla_gemv_w4", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope, w_scale)
+
+
+def gemm_skinny_w4(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, norm_weight=None, eps=0.0,
+                   swiglu=False, rope=None):
+    """gemv_w4's contract for 1 <= M <= 64 rows and any K % 32 == 0 (mla_gemm_skinny_w4): the codes are decoded to bf16 into the MFMA
+    operands, on gemm_skinny_w8's K steps."""
+    _skinny_call("mla_gemm_skinny_w4", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope,
+                 w_scale)
+
+
 def _skinny_gateup_call(name, x, W, out, ldo, w_scale=None):
     """The shared call of the two gate|up + SwiGLU projections: _skinny_call's argument checks without a residual, a rotary epilogue or a
     pre-transform; out [M, I] is allocated when not given (ldo: its row stride in elements, default out.stride(0))."""
     scale_arg = _proj_operands(name, x, W, w_scale)
     M, K = x.shape
-    assert W.shape[0] % 2 == 0 and W.shape[1] == K
+    assert W.shape[0] % 2 == 0 and _weight_k(W) == K
     I = W.shape[0] // 2
     if out is None:
         out = torch.empty((M, I), dtype=torch.bfloat16, device=x.device)
@@ -1073,6 +1136,12 @@ def gemm_skinny_gateup_swiglu_w8(x, W, w_scale, out=None, ldo=None):
     """gemm_skinny_gateup_swiglu over FP8 weights (mla_gemm_skinny_gateup_swiglu_w8): W [2 I, K] float8_e4m3fn, w_scale [2 I] fp32; each
     finished fp32 sum times its own row's scale in front of the bf16 rounding, as gemm_skinny_w8 does. K % 16 == 0."""
     return _skinny_gateup_call("mla_gemm_skinny_gateup_swiglu_w8", x, W, out, ldo, w_scale)
+
+
+def gemm_skinny_gateup_swiglu_w4(x, W, w_scale, out=None, ldo=None):
+    """gemm_skinny_gateup_swiglu over MXFP4 weights (mla_gemm_skinny_gateup_swiglu_w4): W [2 I, K / 2] uint8 codes, w_scale [2 I, K / 32]
+    uint8; bit for bit swiglu_fwd of gemm_skinny_w4's output. K % 32 == 0."""
+    return _skinny_gateup_call("mla_gemm_skinny_gateup_swiglu_w4", x, W, out, ldo, w_scale)
 
 
 def attn_decode(cache, B, nheads, D, S_kv, R, scale):
@@ -1181,7 +1250,7 @@ def _suffix_call(sym, name, x, W, out, ldo, out_batch_stride, rows_per_batch, re
     scale_arg = _proj_operands(name, x, W, w_scale, out)
     M, K = x.shape
     N = W.shape[0]
-    assert W.shape[1] == K
+    assert _weight_k(W) == K
     if slot is not None:
         _req(slot, torch.int32, f"{name} slot")
         assert cap_rows is not None and slot.is_contiguous() and slot.numel() * rows_per_batch >= M
@@ -1225,6 +1294,15 @@ def gemm_suffix_w8(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, re
     w_scale * (x[m] @ float(W)^T) (+ residual[m]), the scale applied to the finished fp32 sum (gemm_skinny_w8's arithmetic: every 64-row
     slice is bit for bit its output). K % 16 == 0; rows, slots, rope, rope_pos (mla_gemm_suffix_w8_pos) and addressing are gemm_suffix's."""
     _suffix_call("mla_gemm_suffix_w8", "gemm_suffix_w8", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows,
+                 w_scale, rope_pos=rope_pos, rope_rows=rope_rows)
+
+
+def gemm_suffix_w4(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, rope=None, slot=None, cap_rows=None,
+                   rope_pos=None, rope_rows=None):
+    """gemm_suffix over MXFP4 weights (mla_gemm_suffix_w4): W [N, K / 2] uint8 codes, w_scale [N, K / 32] uint8 as quant_mxfp4_rows writes
+    them; gemm_skinny_w4's arithmetic (every 64-row slice is bit for bit its output). K % 32 == 0; rows, slots, rope, rope_pos
+    (mla_gemm_suffix_w4_pos) and addressing are gemm_suffix's."""
+    _suffix_call("mla_gemm_suffix_w4", "gemm_suffix_w4", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows,
                  w_scale, rope_pos=rope_pos, rope_rows=rope_rows)
 
 

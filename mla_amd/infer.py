@@ -18,6 +18,10 @@ Opt-in (`suffix_weights="fp8"`, see MODES): the sampler steps stream a per-row e
 `mla_gemv_w8` / `mla_gemm_skinny_w8` (one chunk per call) or `mla_gemm_suffix_w8` (N chunks per observation, SampleGroupsEps) -- half the
 weight bytes per step; prefill, activations, cache and attention are untouched.
 
+Opt-in (`suffix_mx="fp4"`, see MODES): the same with an OCP MXFP4 copy (e2m1 codes, one e8m0 scale byte per 32 elements of a weight row)
+through `mla_gemv_w4` / `mla_gemm_skinny_w4` / `mla_gemm_suffix_w4` -- a quarter of the weight bytes, decoded exactly in registers; a
+4-bit weight error whose effect on a trained policy is not measured.
+
 Opt-in (`sampler="device"`, see MODES): the DDIM loop around the suffix passes runs on the device -- `sample_ddim` replays one
 captured sampler step (x_embedder, `mla_sampler_rows`, the suffix pass, final_layer, `mla_ddim_step`) per DDIM step with the step index in
 device memory: no copy to the device and no host wait between the steps, bit for bit the host loop's result.
@@ -157,10 +161,22 @@ MODES = (
     #   "device"  _CachedEpsBase.sample_ddpm: the steps' normal variates drawn up front into a device table, then one captured sampler step
     #             replayed num_timesteps times; no copy to the device and no host wait between the steps; the same bits and generator position
     Mode("ddpm_sampler", ("host", "device"), "ddpm", None, "has the host loop only"),
+
+    # A block-scaled 4-bit copy for the suffix pass (MLA.predict_action_diff(suffix_mx=...)). Like suffix_weights it chooses what the
+    # suffix pass streams, so a value other than "off" together with suffix_weights other than "bf16" is an error (check_modes); it has
+    # its own row because it has its own copy, kernels and cost. The prefill does not depend on it:
+    #   "off"          whatever suffix_weights says (default)
+    #   "fp4"          the model's OCP MXFP4 copy (hip.quant_mxfp4_rows: e2m1 codes, one e8m0 scale byte per 32 elements of a row) through
+    #                  mla_gemv_w4 / mla_gemm_skinny_w4 (PrefixCachedEps) or mla_gemm_suffix_w4 (the row-GEMM engines): a quarter of the
+    #                  bf16 bytes per sampler step. The weight error of the format is a 4-bit one (relative Frobenius error 0.11 on
+    #                  Gaussian weights, against 0.012 for "fp8"); what it does to a trained policy is not measured
+    #   "fp4_as_bf16"  the bf16 kernels on the dequantised copy (exactly the values the `_w4` kernels decode): the reference of the "fp4"
+    #                  path, and what the format costs on a checkpoint, without the new kernels
+    Mode("suffix_mx", ("off", "fp4", "fp4_as_bf16"), "reuse_prefix", "mx:", "has bf16 weights only"),
 )
 MODES = {mode.name: mode for mode in MODES}
 # The order in which a public method validates them: the first wrong keyword is the one the error names.
-CHECK_ORDER = ("suffix_operand", "suffix_weights", "prefill", "prefill_precision", "sampler", "ddpm_sampler", "suffix_attention",
+CHECK_ORDER = ("suffix_operand", "suffix_weights", "suffix_mx", "prefill", "prefill_precision", "sampler", "ddpm_sampler", "suffix_attention",
                "groups_attention")
 
 
@@ -173,6 +189,8 @@ class Modes(collections.namedtuple("Modes", list(MODES), defaults=[mode.values[0
         """The keywords `names` as a call that ends in a single-observation method hands them on: without groups_attention among them,
         its "split" is that method's suffix_attention="split"; batch_prefill is that method's compact prefill at that precision."""
         keywords = {name: getattr(self, name) for name in names}
+        if keywords.get("suffix_mx") == "off":                               # the default: the call is the one without the keyword
+            del keywords["suffix_mx"]
         if "suffix_attention" in keywords and "groups_attention" not in keywords and self.groups_attention == "split":
             keywords["suffix_attention"] = "split"
         if self.batch_prefill != "train":
@@ -210,6 +228,15 @@ def check_modes(modes: Modes, reuse_prefix=True, use_ddim=True, num_ddim_steps=8
     check, behind these)."""
     for name in CHECK_ORDER:
         check_mode(name, getattr(modes, name), reuse_prefix, use_ddim, num_ddim_steps, modes.prefill)
+        if name == "suffix_mx":
+            check_one_suffix_copy(modes)
+
+
+def check_one_suffix_copy(modes: Modes):
+    """suffix_mx and suffix_weights both choose what the suffix pass streams: at most one of them away from its default."""
+    if modes.suffix_mx != "off" and modes.suffix_weights != "bf16":
+        raise ValueError(f"suffix_mx=\"{modes.suffix_mx}\" and suffix_weights=\"{modes.suffix_weights}\" both choose what the suffix pass "
+                         "streams; use suffix_mx with suffix_weights=\"bf16\"")
 
 
 def engine_modes(**keywords) -> Modes:
@@ -217,6 +244,7 @@ def engine_modes(**keywords) -> Modes:
     modes = Modes(**keywords)
     for name, value in keywords.items():
         check_mode(name, value, prefill=modes.prefill)
+    check_one_suffix_copy(modes)
     return modes
 
 
@@ -263,17 +291,34 @@ class W8(NamedTuple):
     scale: torch.Tensor
 
 
+class W4(NamedTuple):
+    """An MXFP4 projection weight: q [N, K / 2] uint8 (two e2m1 codes per byte), s [N, K / 32] uint8 (one e8m0 scale byte per block of 32)."""
+    q: torch.Tensor
+    s: torch.Tensor
+
+
+def _mxfp4_dequantised(w: W4) -> torch.Tensor:
+    """bf16 [N, K] of an MXFP4 weight, exact: sign * {0, 0.5, 1, 1.5, 2, 3, 4, 6}[index] * 2^(s - 127) is a bf16 value."""
+    grid = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0], device=w.q.device)
+    N, K = w.q.shape[0], w.q.shape[1] * 2
+    q = w.q.to(torch.int64)
+    val = grid[torch.stack([q & 15, q >> 4], dim=-1).view(N, K)]
+    scale = torch.pow(2.0, w.s.to(torch.float32) - 127.0)                   # exact: integer exponents within [-125, 125]
+    return (val.view(N, K // 32, 32) * scale[..., None]).view(N, K).to(torch.bfloat16)
+
+
 class _CachedEpsBase:
     """What the cached-prefix engines share: the packed weights, the captured suffix pass and the `model(x, t)` call of the samplers.
     A subclass provides prefill() and _suffix_pass() and sets B, R, T, H, h_in, h_out, cache."""
 
     suffix_operand = "fused"         # MODES: read by PrefixCachedEps._suffix_pass; the row-GEMM engines form the operand once anyway
+    suffix_mx = "off"                # MODES: read by _weights / _suffix_layers; "off" leaves the choice to suffix_weights
 
     def __init__(self, vlm, n_action_rows: int = 1, modes: Modes = Modes()):
         """modes: as the factory validated them (engine_modes). The multi-row engines' attention mode is groups_attention."""
         self.suffix_weights, self.prefill_mode, self.prefill_precision = modes.suffix_weights, modes.prefill, modes.prefill_precision
         self.suffix_attention = "split" if "split" in (modes.suffix_attention, modes.groups_attention) else "head"
-        self.suffix_operand, self.batch_prefill = modes.suffix_operand, modes.batch_prefill
+        self.suffix_operand, self.batch_prefill, self.suffix_mx = modes.suffix_operand, modes.batch_prefill, modes.suffix_mx
         self._attn_ws = None         # "split": the partial softmax states of mla_attn_chunk_split, allocated once beside h_in / h_out
         self._prefill_ws = None      # "compact": the split-K workspace of the prefill GEMMs, allocated once beside h_in / h_out
         self._prefill_xq = None      # prefill_precision "fp8": the projection inputs' codes (one buffer, viewed [rows, K]) ...
@@ -348,7 +393,10 @@ class _CachedEpsBase:
         if self._packed is not shared["packed"]:
             self.graph = None            # a captured pass holds the previous buffers' addresses
             self._packed, self._packed_key = shared["packed"], key
-        suffix = self._packed if self.suffix_weights == "bf16" else self._quantised(key)
+        if self.suffix_mx != "off":
+            suffix = self._quantised_mx(key)
+        else:
+            suffix = self._packed if self.suffix_weights == "bf16" else self._quantised(key)
         if self._suffix is not suffix:
             self.graph = None
             self._suffix = suffix
@@ -383,11 +431,40 @@ class _CachedEpsBase:
             shared["fp8_as_bf16"] = deq
         return shared[mode]
 
+    def _quantised_mx(self, key):
+        """_quantised's twin for suffix_mx: the model's MXFP4 weight copy in the form self.suffix_mx -- per layer q|k|v, o, gate|up and
+        down of the packed copy (hip.quant_mxfp4_rows; blocks never cross rows, so the packed matrices quantise as one), in its own slot
+        beside the FP8 copy and independent of it: one per model, shared by its engines, keyed on (data_ptr, _version) of the layer
+        weights and rebuilt when that changes. "fp4": per layer (ln1, W4 qkv, W4 o, ln2, W4 gate|up, W4 down). "fp4_as_bf16": the packed
+        tuple's layout with the dequantised matrices (built from the same codes on first use)."""
+        shared = self.vlm.__dict__.setdefault("_prefix_mxfp4", {})
+        if shared.get("key") != key:
+            layers, nbytes = [], 0
+            with torch.no_grad(), torch.inference_mode(False):
+                for ln1, wq, wk, wv, wo, ln2, wg, wu, wd in self._packed:
+                    mats = [W4(*hip.quant_mxfp4_rows(m)) for m in (ops.cat_view((wq, wk, wv)), wo, ops.cat_view((wg, wu)), wd)]
+                    nbytes += sum(m.q.numel() + m.s.numel() for m in mats)
+                    layers.append((ln1, mats[0], mats[1], ln2, mats[2], mats[3]))
+            shared.clear()
+            shared["key"], shared["fp4"] = key, layers
+            _LOG.info("suffix_mx: MXFP4 copy of the decoder projections, %.2f GB beside the bf16 weights", nbytes / 1e9)
+        if self.suffix_mx == "fp4_as_bf16" and "fp4_as_bf16" not in shared:
+            deq = []
+            with torch.no_grad(), torch.inference_mode(False):
+                for (ln1, qkv, o, ln2, gu, d), packed in zip(shared["fp4"], self._packed):
+                    qkv, o, gu, d = (_mxfp4_dequantised(m) for m in (qkv, o, gu, d))
+                    nq, nk, ng = packed[1].shape[0], packed[2].shape[0], packed[6].shape[0]
+                    deq.append((ln1, qkv[:nq], qkv[nq:nq + nk], qkv[nq + nk:], o, ln2, gu[:ng], gu[ng:], d))
+            shared["fp4_as_bf16"] = deq
+        return shared[self.suffix_mx]
+
     def _suffix_layers(self):
-        """Per layer ((ln1, qkv, o, ln2, gate_up, down), cache) of a suffix pass: every projection one W8 ("fp8", _quantised) or a tuple
-        of bf16 matrices -- views of the packed 9-tuple ("bf16") or of its dequantised twin ("fp8_as_bf16")."""
+        """Per layer ((ln1, qkv, o, ln2, gate_up, down), cache) of a suffix pass: every projection one W8 ("fp8", _quantised), one W4
+        (suffix_mx "fp4", _quantised_mx) or a tuple of bf16 matrices -- views of the packed 9-tuple ("bf16") or of a dequantised twin
+        ("fp8_as_bf16", "fp4_as_bf16")."""
+        coded = self.suffix_mx == "fp4" or (self.suffix_mx == "off" and self.suffix_weights == "fp8")
         for w, c in zip(self._suffix, self.cache):
-            yield (w if self.suffix_weights == "fp8" else (w[0], w[1:4], w[4:5], w[5], w[6:8], w[8:9])), c
+            yield (w if coded else (w[0], w[1:4], w[4:5], w[5], w[6:8], w[8:9])), c
 
     def _finish(self, h):
         """The end of every suffix pass: the model's final norm over the rows, into the static output rows."""
@@ -620,7 +697,7 @@ class _CachedEpsBase:
             return None
         if self.graph_error == _GRAPH_OFF:
             self.graph_error = None
-        key = (self._packed_key, self.suffix_weights,
+        key = (self._packed_key, self.suffix_weights, self.suffix_mx,
                tuple(p.data_ptr() for m in (self.vlm.x_embedder, self.vlm.final_layer) for p in m.parameters()))
         if st.graph is None or st.graph_key != key:
             st.graph = None
@@ -733,8 +810,9 @@ class PrefixCachedEps(_CachedEpsBase):
 
     @classmethod
     def for_inputs(cls, vlm, input_ids, n_action_rows: int = 1, suffix_weights: str = "bf16", prefill: str = "train",
-                   suffix_attention: str = "head", prefill_precision: str = "bf16", suffix_operand: str = "fused", **model_kwargs):
-        modes = engine_modes(suffix_weights=suffix_weights, prefill=prefill, suffix_attention=suffix_attention,
+                   suffix_attention: str = "head", prefill_precision: str = "bf16", suffix_operand: str = "fused", suffix_mx: str = "off",
+                   **model_kwargs):
+        modes = engine_modes(suffix_weights=suffix_weights, suffix_mx=suffix_mx, prefill=prefill, suffix_attention=suffix_attention,
                              prefill_precision=prefill_precision, suffix_operand=suffix_operand)
         k = cls._splice_position(input_ids)
         # a handful of prompt lengths per process; each engine holds 0.4 GB at 7B
@@ -785,8 +863,11 @@ class PrefixCachedEps(_CachedEpsBase):
         """f(x) [M, K] @ W^T (+ residual) -> [M, N]; `weights` is a tuple of bf16 matrices (one launch when they are adjacent in memory) or
         one W8 (always packed: one launch).
         pre: norm_weight= / eps= (RMSNorm of the rows) or swiglu=True (x = packed gate|up rows), applied inside the kernel's input staging."""
-        M, w8 = x.shape[0], isinstance(weights, W8)
-        N, K = weights.q.shape if w8 else (sum(w.shape[0] for w in weights), weights[0].shape[1])
+        M, w8, w4 = x.shape[0], isinstance(weights, W8), isinstance(weights, W4)
+        if w4:
+            N, K = weights.q.shape[0], weights.q.shape[1] * 2
+        else:
+            N, K = weights.q.shape if w8 else (sum(w.shape[0] for w in weights), weights[0].shape[1])
         if out is None:
             out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
             rpb, out_bs = M, 0
@@ -798,6 +879,9 @@ class PrefixCachedEps(_CachedEpsBase):
         fits = hip.gemv_fits(M, K)
         if w8:
             (hip.gemv_w8 if fits else hip.gemm_skinny_w8)(x, weights.q, weights.scale, out, ldo, out_bs, rpb, residual, **pre)
+            return out
+        if w4:                                                               # the same switch point: not measured apart from w8's
+            (hip.gemv_w4 if fits else hip.gemm_skinny_w4)(x, weights.q, weights.s, out, ldo, out_bs, rpb, residual, **pre)
             return out
         gemv = hip.gemv if fits else hip.gemm_skinny
         wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
@@ -816,6 +900,8 @@ class PrefixCachedEps(_CachedEpsBase):
         matrix into a gate|up buffer and the stand-alone swiglu_fwd. The same bits either way."""
         if isinstance(gu_w, W8):
             return hip.gemm_skinny_gateup_swiglu_w8(xn2, gu_w.q, gu_w.scale)
+        if isinstance(gu_w, W4):
+            return hip.gemm_skinny_gateup_swiglu_w4(xn2, gu_w.q, gu_w.s)
         wcat = ops.cat_view(gu_w)
         if wcat is not None:
             return hip.gemm_skinny_gateup_swiglu(xn2, wcat)
@@ -830,7 +916,7 @@ class PrefixCachedEps(_CachedEpsBase):
         scale = 1.0 / math.sqrt(self.D)
         attn = self._suffix_attn()
         for (ln1, qkv, wo, ln2, gu_w, wd), c in self._suffix_layers():
-            fused = self.D == 128 and (isinstance(qkv, W8) or ops.cat_view(qkv) is not None)      # the rotary epilogue, as in _suffix_pass
+            fused = self.D == 128 and (isinstance(qkv, (W8, W4)) or ops.cat_view(qkv) is not None)      # the rotary epilogue, as in _suffix_pass
             xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
             self._gemv(xn, qkv, out=c[:, S_p:], rpb=R, out_bs=c.stride(0), **({"rope": (self.cos_s, self.sin_s, 2 * H)} if fused else {}))
             if not fused:
@@ -855,7 +941,7 @@ class PrefixCachedEps(_CachedEpsBase):
         for (ln1, qkv, wo, ln2, gu_w, wd), c in self._suffix_layers():
             # north_star's "fused RMSNorm + RoPE + QKV" as ONE kernel: RMSNorm inside the projection's input staging, the rotary embedding of
             # the q and k columns in its epilogue; the rows go straight into the cache slots [S_p, S_p + R) of every sample
-            fused = self.D == 128 and (isinstance(qkv, W8) or ops.cat_view(qkv) is not None)
+            fused = self.D == 128 and (isinstance(qkv, (W8, W4)) or ops.cat_view(qkv) is not None)
             self._gemv(h, qkv, out=c[:, S_p:], rpb=R, out_bs=c.stride(0), norm_weight=ln1, eps=self.eps,
                        **({"rope": (self.cos_s, self.sin_s, 2 * H)} if fused else {}))
             if not fused:
@@ -1010,6 +1096,8 @@ class _RowGemmEps(_CachedEpsBase):
         out = a layer's cache: the q|k|v rows go to their samples' / groups' slots."""
         if isinstance(weights, W8):
             N, gemm = weights.q.shape[0], functools.partial(hip.gemm_suffix_w8, x, weights.q, weights.scale)
+        elif isinstance(weights, W4):
+            N, gemm = weights.q.shape[0], functools.partial(hip.gemm_suffix_w4, x, weights.q, weights.s)
         else:
             wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
             assert wcat is not None, "the packed weights are adjacent in memory (_weights)"
@@ -1167,11 +1255,11 @@ class SampleGroupsEps(_RowGemmEps):
 
     @classmethod
     def for_inputs(cls, vlm, input_ids, n_action_rows: int, num_samples: int, suffix_weights: str = "bf16", prefill: str = "train",
-                   prefill_precision: str = "bf16", suffix_attention: str = "head", **model_kwargs):
+                   prefill_precision: str = "bf16", suffix_attention: str = "head", suffix_mx: str = "off", **model_kwargs):
         """-> (engine, prefilled for this observation; passes [(start, stop), ...] of plan_sample_groups). One engine -- and its graphs --
         per suffix_weights, prefill and attention mode, as in PrefixCachedEps.for_inputs. suffix_attention: "head"
         (mla_attn_chunk_groups) or "split" (mla_attn_groups_split)."""
-        modes = engine_modes(suffix_weights=suffix_weights, prefill=prefill, prefill_precision=prefill_precision,
+        modes = engine_modes(suffix_weights=suffix_weights, suffix_mx=suffix_mx, prefill=prefill, prefill_precision=prefill_precision,
                              groups_attention=suffix_attention)
         k = PrefixCachedEps._splice_position(input_ids)
         passes = plan_sample_groups(num_samples, 1 + n_action_rows, cls.MAX_ROWS)
@@ -1310,12 +1398,13 @@ class BatchedSampleGroupsEps(_RowGemmEps):
 
     @classmethod
     def for_batch(cls, vlm, ids_rows, n_action_rows: int, num_samples: int, suffix_weights: str = "bf16", images=None, point_cloud=None,
-                  camera_name=None, proprio=None, add_tail=True, suffix_attention: str = "head", batch_prefill: str = "train", **unused):
+                  camera_name=None, proprio=None, add_tail=True, suffix_attention: str = "head", batch_prefill: str = "train",
+                  suffix_mx: str = "off", **unused):
         """Generator over the passes of one call: runs the encoders once over all observations, plans (plan_batch_samples) and yields
         (SampleSubBatchPlan, prefilled engine) per sub-batch. Two sub-batches may share an engine: finish sampling one before taking the
         next. suffix_attention: "head" (mla_attn_chunk_ragged_groups) or "split" (mla_attn_groups_split); batch_prefill:
         MODES' batch_prefill; one engine per mode."""
-        modes = engine_modes(suffix_weights=suffix_weights, groups_attention=suffix_attention, batch_prefill=batch_prefill)
+        modes = engine_modes(suffix_weights=suffix_weights, suffix_mx=suffix_mx, groups_attention=suffix_attention, batch_prefill=batch_prefill)
         front = cls._front_tokens(vlm, images, point_cloud, camera_name)
         plans = plan_batch_samples(ids_rows, n_action_rows, int(front.shape[1]), num_samples, cls.MAX_ROWS, cls.BUCKET, add_tail=add_tail)
         if plans is None:

@@ -464,7 +464,7 @@ class MLA(nn.Module):
                             camera_name: str = "rlbench_front", reuse_prefix: bool = True, suffix_weights: str = "bf16",
                             prefill: str = "train", sampler: str = "host", suffix_attention: str = "head",
                             prefill_precision: str = "bf16", ddpm_sampler: str = "host", suffix_operand: str = "fused",
-                            known_actions=None, **kwargs) -> np.ndarray:
+                            known_actions=None, suffix_mx: str = "off", **kwargs) -> np.ndarray:
         """model_mla.py:592-775: 8-step DDIM (eta = 0) over the action chunk with the VLM as the epsilon model, then
         un-normalisation.
         * ``image`` is a PIL image / uint8 HWC frame (pre-processed here like the reference does, :656-660) or an already
@@ -524,6 +524,16 @@ class MLA(nn.Module):
         with every ``suffix_weights``, ``suffix_attention``, ``sampler``, ``ddpm_sampler``, ``prefill`` and ``prefill_precision`` mode; it
         is validated in front of every other mode and raises ValueError for an unknown value, and for "once" when ``reuse_prefix=False``
         or the cached-prefix engine does not serve the shape: no silent fallback.
+        ``suffix_mx`` (opt-in, cached prefix only): "off" (default) | "fp4": the sampler steps stream the model's OCP MXFP4 copy of the
+        decoder weights (e2m1 codes with one e8m0 scale byte per 32 elements of a weight row; mla_gemv_w4 / mla_gemm_skinny_w4 /
+        mla_gemm_suffix_w4: a quarter of the bf16 bytes per step, decoded exactly in registers; the prefill keeps the bf16 weights) |
+        "fp4_as_bf16": the bf16 kernels on the dequantised copy -- the same function as "fp4" up to summation order, and what the
+        format costs on a checkpoint, without the 4-bit kernels. The weight error of the format is a 4-bit one: relative Frobenius error
+        0.11 on Gaussian weights (round to nearest), against 0.012 for ``suffix_weights="fp8"``; the effect on a trained policy is not
+        measured. It composes with every ``sampler``, ``ddpm_sampler``, ``suffix_attention`` / ``groups_attention``, ``suffix_operand``,
+        ``prefill`` and ``prefill_precision`` mode and with ``known_actions``; together with ``suffix_weights`` other than "bf16" it
+        raises ValueError (both choose what the suffix pass streams), as it does for an unknown value, when ``reuse_prefix=False`` and
+        when the cached-prefix engine does not serve the shape: no silent fallback.
         ``known_actions`` (default None: the call without the keyword, bit for bit): an array [d, action_dim], 1 <= d <= T, in the units
         of the return value -- the first d steps of this chunk are already decided (the robot is executing them while this call runs) and
         the sampler pins them: in every sampler step the x0 prediction of chunk steps 0 .. d - 1 is replaced by the given values
@@ -538,7 +548,8 @@ class MLA(nn.Module):
         ValueError before the model is touched. What pinning does to a trained policy is not measured."""
         from .infer import Modes, PrefixCachedEps, check_modes, needs_engine
         check_modes(Modes(suffix_weights=suffix_weights, prefill=prefill, suffix_attention=suffix_attention, prefill_precision=prefill_precision,
-                          suffix_operand=suffix_operand, sampler=sampler, ddpm_sampler=ddpm_sampler), reuse_prefix, use_ddim, num_ddim_steps)
+                          suffix_operand=suffix_operand, sampler=sampler, ddpm_sampler=ddpm_sampler, suffix_mx=suffix_mx),
+                    reuse_prefix, use_ddim, num_ddim_steps)
         if prefill != "train" and not reuse_prefix:
             raise ValueError(f"prefill={prefill!r} needs the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has no "
                              "separate prefill")
@@ -565,10 +576,10 @@ class MLA(nn.Module):
         if reuse_prefix:
             eps_model = PrefixCachedEps.for_inputs(self.vlm, n_action_rows=T, suffix_weights=suffix_weights, prefill=prefill,
                                                    suffix_attention=suffix_attention, prefill_precision=prefill_precision,
-                                                   suffix_operand=suffix_operand, **model_kwargs)
+                                                   suffix_operand=suffix_operand, suffix_mx=suffix_mx, **model_kwargs)
         else:
-            needs_engine("PrefixCachedEps", T, prefill=prefill, sampler=sampler, ddpm_sampler=ddpm_sampler, suffix_attention=suffix_attention,
-                         suffix_operand=suffix_operand)
+            needs_engine("PrefixCachedEps", T, suffix_mx=suffix_mx, prefill=prefill, sampler=sampler, ddpm_sampler=ddpm_sampler,
+                         suffix_attention=suffix_attention, suffix_operand=suffix_operand)
         pin = MLA._pin(self, [known_actions], T, action_dim, unnorm_key, device)
         samples = self._sample(eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs, ddpm_sampler, pin)
         return self._actions([samples[:1].float().cpu().numpy()], unnorm_key)[0]
@@ -581,7 +592,8 @@ class MLA(nn.Module):
                                   num_samples: Optional[int] = None, prefill: str = "train", sampler: str = "host",
                                   suffix_attention: str = "head", prefill_precision: str = "bf16",
                                   groups_attention: str = "head", batch_prefill: str = "train",
-                                  ddpm_sampler: str = "host", suffix_operand: str = "fused", known_actions=None) -> np.ndarray:
+                                  ddpm_sampler: str = "host", suffix_operand: str = "fused", known_actions=None,
+                                  suffix_mx: str = "off") -> np.ndarray:
         """B observations -> [B, T, action_dim]: by definition B independent `predict_action_diff` calls (the reference's
         `predict_action_batch`, model_mla.py:994, is dead code), computed on ONE cached prefix pass per DDIM step
         (mla_amd/infer.py:BatchedPrefixCachedEps): the prompts may have different lengths, the FPS start indices are drawn once per chunk.
@@ -601,6 +613,11 @@ class MLA(nn.Module):
         the engine does not serve warns once and loops the same way. All three ``suffix_weights`` modes are accepted (N = 1 included: this
         is how B >= 2 observations get FP8 suffix weights); anything but "bf16" raises ValueError when ``reuse_prefix=False`` or the
         engine does not serve the shape.
+        ``suffix_mx``: predict_action_diff's ("fp4": the MXFP4 copy through the `_w4` kernels, "fp4_as_bf16": the bf16 kernels on the
+        dequantised copy; a 4-bit weight error, the effect on a trained policy is not measured), on the routes of ``suffix_weights``:
+        forwarded for B = 1; B >= 2 without ``num_samples`` raises NotImplementedError; with ``num_samples`` (N = 1 included) every
+        pass streams the copy through mla_gemm_suffix_w4_pos. Together with ``suffix_weights`` other than "bf16", with
+        ``reuse_prefix=False`` or on a shape the engine does not serve it raises ValueError.
         ``prefill``: only "train" -- the one-observation compact prefill is predict_action_diff's / predict_action_diff_samples';
         "compact" raises NotImplementedError (the batched engines take their FP8 prefill from ``batch_prefill``).
         ``prefill_precision``: only "bf16", for the same reason; "fp8" / "fp8_as_bf16" raise NotImplementedError, an unknown value
@@ -645,7 +662,8 @@ class MLA(nn.Module):
         touched."""
         from .infer import BatchedPrefixCachedEps, Modes, check_mode, check_modes, needs_engine, suffix_attention_single_only
         modes = Modes(suffix_weights=suffix_weights, prefill=prefill, suffix_attention=suffix_attention, groups_attention=groups_attention,
-                      batch_prefill=batch_prefill, suffix_operand=suffix_operand, sampler=sampler, ddpm_sampler=ddpm_sampler)
+                      batch_prefill=batch_prefill, suffix_operand=suffix_operand, sampler=sampler, ddpm_sampler=ddpm_sampler,
+                      suffix_mx=suffix_mx)
         check_modes(modes, reuse_prefix, use_ddim, num_ddim_steps)
         check_mode("prefill_precision", prefill_precision)                    # an unknown value only: no mode but "bf16" is served here
         check_mode("batch_prefill", batch_prefill, reuse_prefix)
@@ -677,7 +695,11 @@ class MLA(nn.Module):
                                             camera_name=camera_name, **MLA._fwd_known(known[b]), **kw)
         if B == 1:
             return one(0, reuse_prefix=reuse_prefix,
-                       **modes.forwarded("suffix_weights", "sampler", "ddpm_sampler", "suffix_attention", "suffix_operand"))[None]
+                       **modes.forwarded("suffix_weights", "suffix_mx", "sampler", "ddpm_sampler", "suffix_attention", "suffix_operand"))[None]
+        if suffix_mx != "off":
+            raise NotImplementedError(f"suffix_mx={suffix_mx!r}: the batched engine (BatchedPrefixCachedEps, mla_gemm_suffix_bf16) streams "
+                                      "bf16 weights only; sample B >= 2 observations with \"off\", one at a time, or pass `num_samples` "
+                                      "(BatchedSampleGroupsEps serves every mode)")
         if suffix_weights != "bf16":
             raise NotImplementedError(f"suffix_weights={suffix_weights!r}: the batched engine (BatchedPrefixCachedEps, mla_gemm_suffix_bf16) "
                                       "streams bf16 weights only; sample B >= 2 observations with \"bf16\", one at a time, or pass "
@@ -719,18 +741,19 @@ class MLA(nn.Module):
                                                     num_ddim_steps, action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b],
                                                     camera_name=camera_name, **MLA._fwd_known(known[b]), **kw)
         if B == 1:
-            return samples_of(0, reuse_prefix=reuse_prefix, **modes.forwarded("suffix_weights", "sampler", "ddpm_sampler", "suffix_attention",
-                                                                              "groups_attention", "suffix_operand"))[None]
+            return samples_of(0, reuse_prefix=reuse_prefix, **modes.forwarded("suffix_weights", "suffix_mx", "sampler", "ddpm_sampler",
+                                                                              "suffix_attention", "groups_attention", "suffix_operand"))[None]
         if modes.suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={modes.suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler "
                              "has bf16 weights only")
         if reuse_prefix:
             if not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T, warn=False):
                 needs_engine("BatchedSampleGroupsEps", T, sampler=modes.sampler, ddpm_sampler=modes.ddpm_sampler,
-                             groups_attention=modes.groups_attention, batch_prefill=modes.batch_prefill, suffix_weights=modes.suffix_weights)
+                             groups_attention=modes.groups_attention, batch_prefill=modes.batch_prefill, suffix_weights=modes.suffix_weights,
+                             suffix_mx=modes.suffix_mx)
             if not BatchedSampleGroupsEps.supports_batch_samples(self.vlm, T) or not BatchedSampleGroupsEps.fits_pass(T, N):
                 # one observation at a time: predict_action_diff_samples serves (or refuses) the shape and the mode itself
-                return np.stack([samples_of(b, **modes.forwarded("suffix_weights", "sampler", "ddpm_sampler", "groups_attention"))
+                return np.stack([samples_of(b, **modes.forwarded("suffix_weights", "suffix_mx", "sampler", "ddpm_sampler", "groups_attention"))
                                  for b in range(B)])
         else:
             return np.stack([samples_of(b, reuse_prefix=False) for b in range(B)])
@@ -739,7 +762,8 @@ class MLA(nn.Module):
         pin = MLA._pin(self, known, T, action_dim, unnorm_key, device, repeat=N)
         out = []
         for sub, eng in BatchedSampleGroupsEps.for_batch(self.vlm, ids_rows, T, N, modes.suffix_weights,
-                                                         suffix_attention=modes.groups_attention, batch_prefill=modes.batch_prefill, **inputs):
+                                                         suffix_attention=modes.groups_attention, batch_prefill=modes.batch_prefill,
+                                                         suffix_mx=modes.suffix_mx, **inputs):
             samples = self._sample(eng, x0[sub.start * N:sub.stop * N].contiguous(), modes.sampler, use_ddim, num_ddim_steps, {},
                                    modes.ddpm_sampler, MLA._pin_rows(pin, sub.start * N, sub.stop * N))
             out.append(samples.float().cpu().numpy().reshape(sub.stop - sub.start, N, T, -1))
@@ -753,7 +777,8 @@ class MLA(nn.Module):
                                     reuse_prefix: bool = True, suffix_weights: str = "bf16", prefill: str = "train",
                                     sampler: str = "host", suffix_attention: str = "head",
                                     prefill_precision: str = "bf16", groups_attention: str = "head",
-                                    ddpm_sampler: str = "host", suffix_operand: str = "fused", known_actions=None) -> np.ndarray:
+                                    ddpm_sampler: str = "host", suffix_operand: str = "fused", known_actions=None,
+                                    suffix_mx: str = "off") -> np.ndarray:
         """N action chunks for ONE observation -> [N, T, action_dim]: by definition N independent `predict_action_diff` calls on the same
         observation with the initial samples ``noise[n]`` (critic / best-of-N choice, uncertainty estimates, temporal ensembling), computed
         on ONE cached prefix (mla_amd/infer.py:SampleGroupsEps): the encoders and the decoder prefill run once per call, every sampler step
@@ -767,6 +792,12 @@ class MLA(nn.Module):
         (mla_gemm_suffix_w8: half the weight bytes per sampler step; the prefill and the prefix keys / values keep the bf16 weights);
         "fp8_as_bf16": the bf16 kernel on the dequantised copy. Forwarded for ``num_samples=1``. Anything but "bf16" raises ValueError
         when ``reuse_prefix=False`` or the shared-prefix engine does not serve the shape: no silent bf16 fallback, no silent loop.
+        ``suffix_mx`` (opt-in): predict_action_diff's modes. "fp4": every pass streams the model's MXFP4 copy of the decoder weights
+        (mla_gemm_suffix_w4: a quarter of the bf16 weight bytes per sampler step, gemm_skinny_w4's summation order, so every sample is
+        what its own predict_action_diff(suffix_mx="fp4") call computes up to the attention launch); "fp4_as_bf16": the bf16 kernel on
+        the dequantised copy. A 4-bit weight error (0.11 relative Frobenius on Gaussian weights); the effect on a trained policy is not
+        measured. Forwarded for ``num_samples=1``. Anything but "off" raises ValueError together with ``suffix_weights`` other than
+        "bf16", when ``reuse_prefix=False`` or when the shared-prefix engine does not serve the shape.
         ``prefill`` (opt-in): predict_action_diff's modes; "compact" runs the one prefill of the call on the row-sized GEMMs. Forwarded
         for ``num_samples=1``; raises ValueError when ``reuse_prefix=False``, the shared-prefix engine does not serve the shape, the prefix
         has more than 1024 rows or head_dim is not 128.
@@ -794,7 +825,8 @@ class MLA(nn.Module):
         (the engine sees it repeated over the samples). None is the call without the keyword, bit for bit."""
         from .infer import Modes, SampleGroupsEps, check_modes, needs_engine, suffix_attention_single_only
         modes = Modes(suffix_weights=suffix_weights, prefill=prefill, suffix_attention=suffix_attention, groups_attention=groups_attention,
-                      prefill_precision=prefill_precision, suffix_operand=suffix_operand, sampler=sampler, ddpm_sampler=ddpm_sampler)
+                      prefill_precision=prefill_precision, suffix_operand=suffix_operand, sampler=sampler, ddpm_sampler=ddpm_sampler,
+                      suffix_mx=suffix_mx)
         check_modes(modes, reuse_prefix, use_ddim, num_ddim_steps)
         if int(num_samples) != 1:
             suffix_attention_single_only(suffix_attention, f"predict_action_diff_samples with num_samples={num_samples}")
@@ -815,15 +847,15 @@ class MLA(nn.Module):
                                             action_dim, input_ids=input_ids, noise=None if noise is None else noise[n:n + 1],
                                             camera_name=camera_name, **MLA._fwd_known(known_actions), **kw)
         if N == 1:
-            return one(0, reuse_prefix=reuse_prefix, **modes.forwarded("suffix_weights", "prefill", "sampler", "ddpm_sampler", "suffix_attention",
-                                                                       "prefill_precision", "suffix_operand"))[None]
+            return one(0, reuse_prefix=reuse_prefix, **modes.forwarded("suffix_weights", "suffix_mx", "prefill", "sampler", "ddpm_sampler",
+                                                                       "suffix_attention", "prefill_precision", "suffix_operand"))[None]
         if suffix_weights != "bf16" and not reuse_prefix:
             raise ValueError(f"suffix_weights={suffix_weights!r} needs the cached prefix (reuse_prefix=True); the whole-forward sampler has "
                              "bf16 weights only")
         if reuse_prefix:
             if not SampleGroupsEps.supports_samples(self.vlm, T, warn=False):       # raised, not a warned loop of batch-1 calls
                 needs_engine("SampleGroupsEps", T, sampler=sampler, ddpm_sampler=ddpm_sampler, groups_attention=groups_attention,
-                             prefill=prefill, suffix_weights=suffix_weights)
+                             prefill=prefill, suffix_weights=suffix_weights, suffix_mx=suffix_mx)
             reuse_prefix = SampleGroupsEps.supports_samples(self.vlm, T)
         if not reuse_prefix:
             return np.stack([one(n, reuse_prefix=False) for n in range(N)])
@@ -838,7 +870,8 @@ class MLA(nn.Module):
         x0 = self._draw_x0([None if noise is None else noise[n:n + 1] for n in range(N)], T, action_dim, device)
         pin = MLA._pin(self, [known_actions], T, action_dim, unnorm_key, device, repeat=N)
         eng, passes = SampleGroupsEps.for_inputs(self.vlm, input_ids, T, N, suffix_weights=suffix_weights, prefill=prefill,
-                                                 prefill_precision=prefill_precision, suffix_attention=groups_attention, **model_kwargs)
+                                                 prefill_precision=prefill_precision, suffix_attention=groups_attention, suffix_mx=suffix_mx,
+                                                 **model_kwargs)
         out = []
         for start, stop in passes:                                           # one prefill, then the passes' sampler loops one after the other
             eng.set_groups(stop - start)

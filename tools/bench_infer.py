@@ -11,6 +11,13 @@
                                                           latency and the suffix pass alone, per pair, with the 95 % interval of the pair
                                                           differences; --kernel-table adds mla_gemv_w8 vs mla_gemm_skinny_w8 per 7B
                                                           projection shape at M = 2, 5, 8, 17 (the engine's selection rule is set from it)
+    python tools/bench_infer.py --pair-mx [--pairs P] [--chunks C[,C..]] [--operand fused|once|both] [--kernel-table]
+                                                         bf16 / fp8 / fp4 (suffix_mx="fp4": the MXFP4 copy) chunks with sampler="device",
+                                                         alternating in one process, and their captured suffix passes; mean and 95 %
+                                                         interval of the pair differences fp8 - bf16, fp4 - bf16 and fp4 - fp8, one
+                                                         line per chunk length (and, with "both", a second one with
+                                                         suffix_operand="once" where the pass has more than 8 rows);
+                                                         --kernel-table adds the _w8 and _w4 kernels per 7B projection shape and M
     python tools/bench_infer.py --samples N[,N..] [--chunks C[,C..]] [--pairs P] [--kernel-table]
                                                           N action chunks for ONE observation, three forms of the same work alternating in
                                                           one process (same box, same clocks), per pair, with the 95 % interval of the pair
@@ -168,6 +175,8 @@ def main():
                     "--samples: B[,B..] paired with N[,N..]")
     ap.add_argument("--suffix-weights", choices=["bf16", "fp8", "fp8_as_bf16"], default="bf16")
     ap.add_argument("--pair-fp8", action="store_true", help="alternate bf16 and fp8 chunks in one process, in pairs")
+    ap.add_argument("--pair-mx", action="store_true", help="alternate bf16, fp8 and fp4 (suffix_mx) chunks with sampler=\"device\" in one process, in pairs")
+    ap.add_argument("--operand", choices=["fused", "once", "both"], default="fused", help="with --pair-mx: suffix_operand of every arm")
     ap.add_argument("--pair-prefill", action="store_true", help="alternate prefill=\"train\", \"compact\" and \"compact\" with prefill_precision=\"fp8\" in one process")
     ap.add_argument("--pair-sampler", action="store_true", help="alternate sampler=\"host\" and sampler=\"device\" in one process, in pairs")
     ap.add_argument("--pair-ddpm-sampler", action="store_true", help="alternate ddpm_sampler=\"host\" and ddpm_sampler=\"device\" on use_ddim=False calls in one process, in pairs")
@@ -202,6 +211,8 @@ def main():
         return main_batch(args)
     if args.pair_prefill:
         return main_pair_prefill(args)
+    if args.pair_mx:
+        return main_pair_mx(args)
     if args.pair_fp8:
         return main_pair(args)
     m, b, ids = _setup(args)
@@ -329,6 +340,111 @@ def main_pair(args):
             table[f"M{M}"] = row
         out["w8_kernel_us_per_launch"] = table
     print(json.dumps(out))
+
+
+_MX_ARMS = {"bf16": {}, "fp8": {"suffix_weights": "fp8"}, "fp4": {"suffix_mx": "fp4"}}
+
+
+def _mx_kernel_table(m, dev, Ms=(2, 5, 8, 17, 33, 64)):
+    """The _w8 and _w4 projection kernels per projection shape of a 7B layer and M, as the engine launches them (the fused input forms,
+    one launch per layer's weights in a captured graph: 32 different matrices, nothing stays in the caches) -> us per launch."""
+    from mla_amd import hip
+    copies = {"w8": m.vlm.__dict__["_prefix_fp8"]["fp8"], "w4": m.vlm.__dict__["_prefix_mxfp4"]["fp4"]}
+    kernels = {"w8": (("gemv", hip.gemv_w8), ("skinny", hip.gemm_skinny_w8)), "w4": (("gemv", hip.gemv_w4), ("skinny", hip.gemm_skinny_w4))}
+    names = {1: "qkv(norm)", 2: "o(res)", 4: "gate_up(norm)", 5: "down(swiglu,res)"}
+    table = {}
+    for M in Ms:
+        row = {}
+        for idx, name in names.items():
+            N, K = copies["w8"][0][idx].q.shape
+            x = (torch.randn(M, 2 * K if idx == 5 else K, device=dev) * 0.5).to(torch.bfloat16)
+            res = torch.randn(M, N, device=dev).to(torch.bfloat16) if idx in (2, 5) else None
+            o = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
+            pre = {"norm_weight": copies["w8"][0][0], "eps": 1e-5} if idx in (1, 4) else ({"swiglu": True} if idx == 5 else {})
+            cell = {}
+            for fmt, layers in copies.items():
+                for kname, fn in kernels[fmt]:
+                    if (kname == "gemv" and not hip.gemv_fits(M, K)) or (kname == "gemv" and M > 8):
+                        continue
+                    for L in layers[:2]:                                    # function attributes, allocator
+                        fn(x, *L[idx], o, N, 0, M, res, **pre)
+                    torch.cuda.synchronize()
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        for L in layers:
+                            fn(x, *L[idx], o, N, 0, M, res, **pre)
+                    g.replay()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(3):
+                        g.replay()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    cell[f"{kname}_{fmt}"] = round(e0.elapsed_time(e1) / (3 * len(layers)) * 1e3, 1)
+            row[name] = cell
+        table[f"M{M}"] = row
+    return table
+
+
+def main_pair_mx(args):
+    """bf16 / fp8 / fp4 suffix weights, sampler="device", in alternating rounds in one process: chunk latency and the captured suffix pass."""
+    m = None
+    for chunk in ([int(v) for v in args.chunks.split(",")] if args.chunks else [args.chunk]):
+        for operand in (["fused"] + (["once"] if chunk > 7 else []) if args.operand == "both" else [args.operand]):
+            args.chunk = chunk
+            m = _pair_mx_case(args, m, operand, kernel_table=args.kernel_table and m is None)
+
+
+def _pair_mx_case(args, m, operand, kernel_table):
+    from mla_amd.infer import PrefixCachedEps
+    m, b, ids = _setup(args, model=m)
+    dev = ids.device
+    noise = torch.randn(1, args.chunk, 7, device=dev)
+    image, pc, state = _observation(b)
+    kw = dict(image=image, pointcloud=pc, cur_robot_state=state, input_ids=ids, num_ddim_steps=args.steps, noise=noise, sampler="device",
+              suffix_operand=operand)
+    mk = dict(input_ids=ids, suffix_operand=operand, **_engine_kw(b))
+    acts = {arm: m.predict_action_diff(**extra, **kw) for arm, extra in _MX_ARMS.items()}       # engines, graphs, packed + quantised weights
+    t91 = torch.tensor([91], device=dev)
+
+    def chunk_ms(arm):
+        return _time_ms(lambda: m.predict_action_diff(**_MX_ARMS[arm], **kw), args.iters)
+
+    def pass_ms(arm):
+        with torch.inference_mode():
+            eng = PrefixCachedEps.for_inputs(m.vlm, n_action_rows=args.chunk, **_MX_ARMS[arm], **mk)
+            eng(noise, t91)
+            return _replay_ms(eng)
+    chunk = {arm: [] for arm in _MX_ARMS}
+    suffix = {arm: [] for arm in _MX_ARMS}
+    for _ in range(args.pairs):                                             # bf16, fp8, fp4, bf16, ...: same box, interleaved
+        for arm in _MX_ARMS:
+            chunk[arm].append(chunk_ms(arm))
+        for arm in _MX_ARMS:
+            suffix[arm].append(pass_ms(arm))
+    n = sum(p.numel() for l in m.vlm.llm_backbone.llm.model.layers for p in l.parameters())
+    gb = {"bf16": 2 * n / 1e9, "fp8": n / 1e9, "fp4": (n / 2 + n / 32) / 1e9}
+
+    def rel(a, ref):
+        return round(float(((acts[a] - acts[ref]) ** 2).sum() ** 0.5 / (acts[ref] ** 2).sum() ** 0.5), 4)
+    out = {"metric": "predict_action_diff, MLA-Llama2-7B, batch 1, sampler=device: bf16 vs fp8 vs fp4 (MXFP4) suffix weights in alternating "
+                     "rounds", "action_chunk": args.chunk, "suffix_rows": args.chunk + 1, "suffix_operand": operand,
+           "ddim_steps": args.steps, "pairs": args.pairs, "unit": "ms",
+           "chunk_ms": {k: [round(v, 2) for v in vs] for k, vs in chunk.items()},
+           "chunk_fp8_minus_bf16": _pair_stats(chunk["bf16"], chunk["fp8"]), "chunk_fp4_minus_bf16": _pair_stats(chunk["bf16"], chunk["fp4"]),
+           "chunk_fp4_minus_fp8": _pair_stats(chunk["fp8"], chunk["fp4"]),
+           "suffix_pass_ms": {k: [round(v, 3) for v in vs] for k, vs in suffix.items()},
+           "suffix_pass_fp8_minus_bf16": _pair_stats(suffix["bf16"], suffix["fp8"]),
+           "suffix_pass_fp4_minus_bf16": _pair_stats(suffix["bf16"], suffix["fp4"]),
+           "suffix_pass_fp4_minus_fp8": _pair_stats(suffix["fp8"], suffix["fp4"]),
+           "weights_streamed_per_pass_gb": {k: round(v, 2) for k, v in gb.items()},
+           "suffix_pass_weight_stream_tbps": {k: round(gb[k] / 1e3 / (min(suffix[k]) * 1e-3), 2) for k in _MX_ARMS},
+           "chunk_rel_diff_vs_bf16_random_weights": {"fp8": rel("fp8", "bf16"), "fp4": rel("fp4", "bf16")},
+           "data": "synthetic"}
+    if kernel_table:
+        out["kernel_us_per_launch"] = _mx_kernel_table(m, dev)
+    print(json.dumps(out), flush=True)
+    return m
 
 
 def main_pair_sampler(args, ddpm=False):
