@@ -1,5 +1,9 @@
 """ctypes binding of libmla_hip.so (C-ABI declared in include/mla_hip.h).
 
+The header is the one statement of every signature: the build shows it to the compiler next to each definition, and the argtypes and
+restypes set in lib() are parsed from it at import (abi.py), so a new entry point needs its definition, its declaration and its
+wrapper here -- no ctypes row.
+
 Every wrapper launches on torch's current HIP stream, never synchronises, and raises RuntimeError on a
 non-zero return code. There is deliberately NO fallback: if the shared library is missing or a kernel rejects its
 arguments the product path fails loudly (oracle/ is test infrastructure only).
@@ -8,10 +12,12 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_float, c_int, c_longlong, c_size_t, c_void_p
+from ctypes import c_float, c_int, c_void_p
 from typing import NamedTuple, Optional
 
 import torch
+
+from . import abi
 
 _LIB_PATH = os.environ.get("MLA_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libmla_hip.so")   # override: A/B experiments
 _lib = None
@@ -25,196 +31,14 @@ SPLITK_WS_BYTES = int(os.environ.get("MLA_GEMM_SPLITK_WS_MB", "64")) << 20     #
 # bench.py sets this to a list to time every GEMM launch with HIP events on the launch stream (roofline.achieved)
 GEMM_PROFILE = None
 
-# name -> argtypes (restype is always int unless noted) -- mirrors include/mla_hip.h
-_SIGNATURES = {
-    "mla_query": [c_int],
-    "mla_selftest": [c_void_p, c_void_p, c_void_p, c_void_p],
-    "mla_dispatch_probe": [c_void_p, c_int, c_int, c_void_p],
-    "mla_calib_mfma": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
-    "mla_gemv_bf16": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_longlong, c_int, c_int,
-                      c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
-    "mla_attn_decode": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_float,
-                        c_void_p],
-    "mla_gemm_skinny_bf16": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_longlong, c_int,
-                             c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
-    "mla_quant_fp8_rows": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_int, c_int, c_void_p],
-    "mla_gemv_w8": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_longlong, c_int,
-                    c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
-    "mla_gemm_skinny_w8": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_longlong,
-                           c_int, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
-    "mla_gemm_skinny_gateup_swiglu_bf16": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_int, c_int, c_void_p],
-    "mla_gemm_skinny_gateup_swiglu_w8": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int,
-                                         c_void_p],
-    "mla_quant_mxfp4_rows": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_int, c_void_p],
-    "mla_gemv_w4": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p,
-                    c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
-    "mla_gemm_skinny_w4": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p,
-                           c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
-    "mla_gemm_skinny_gateup_swiglu_w4": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_int,
-                                         c_int, c_void_p],
-    "mla_gemm_suffix_w4": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p,
-                           c_int, c_void_p, c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
-    "mla_gemm_suffix_w4_pos": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int,
-                               c_void_p, c_int, c_void_p, c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p],
-    "mla_attn_chunk": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_float,
-                       c_void_p],
-    "mla_attn_chunk_ragged": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_longlong, c_longlong,
-                              c_longlong, c_float, c_void_p],
-    "mla_attn_chunk_groups": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_float,
-                              c_void_p],
-    "mla_attn_chunk_groups_gw": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_float,
-                                 c_int, c_int, c_void_p],
-    "mla_gemm_suffix_bf16": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_int, c_void_p,
-                             c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
-    "mla_gemm_suffix_w8": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_int,
-                           c_void_p, c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
-    "mla_attn_chunk_ragged_groups": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_longlong,
-                                     c_longlong, c_longlong, c_float, c_void_p],
-    "mla_attn_chunk_ragged_groups_gw": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_longlong,
-                                        c_longlong, c_longlong, c_float, c_int, c_int, c_void_p],
-    "mla_gemm_suffix_bf16_pos": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_int, c_void_p,
-                                 c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p],
-    "mla_gemm_suffix_w8_pos": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_int,
-                               c_void_p, c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p],
-    "mla_gemm_prefill_plan": [c_int, c_int, c_int, c_int, c_void_p],
-    "mla_gemm_prefill_ws_bytes": [c_int, c_int, c_int],      # returns long long (restype fixed up in lib())
-    "mla_gemm_prefill_bf16": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_longlong, c_int,
-                              c_int, c_int, c_void_p, c_size_t, c_void_p],
-    "mla_gemm_prefill_qkv_rope": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_int, c_int, c_int,
-                                  c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p],
-    "mla_gemm_prefill_gateup_swiglu": [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_int, c_int,
-                                       c_int, c_void_p, c_size_t, c_void_p],
-    "mla_gemm_prefill_f8_plan": [c_int, c_int, c_int, c_int, c_void_p],
-    "mla_gemm_prefill_f8_ws_bytes": [c_int, c_int, c_int],   # returns long long (restype fixed up in lib())
-    "mla_gemm_prefill_f8": [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_void_p,
-                            c_longlong, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p],
-    "mla_gemm_prefill_f8_qkv_rope": [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int,
-                                     c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p],
-    "mla_gemm_prefill_f8_gateup_swiglu": [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong,
-                                          c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p],
-    "mla_gemm_prefill_f8_wide_plan": [c_int, c_int, c_int, c_int, c_void_p],
-    "mla_gemm_prefill_f8_wide_ws_bytes": [c_int, c_int, c_int],   # returns long long (restype fixed up in lib())
-    "mla_gemm_prefill_f8_wide": [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_int,
-                                 c_void_p, c_longlong, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p],
-    "mla_gemm_prefill_f8_wide_qkv_rope": [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong,
-                                          c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p],
-    "mla_gemm_prefill_f8_wide_gateup_swiglu": [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong,
-                                               c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p],
-    "mla_ddim_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "mla_ddpm_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "mla_ddim_step_pin": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "mla_ddpm_step_pin": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "mla_sampler_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
-    "mla_attn_chunk_split_plan": [c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "mla_attn_chunk_split_ws_bytes": [c_int, c_int, c_int, c_int, c_int],      # returns long long (restype fixed up in lib())
-    "mla_attn_chunk_split": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong,
-                             c_float, c_int, c_void_p, c_size_t, c_void_p],
-    "mla_attn_groups_split": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_longlong, c_longlong,
-                              c_longlong, c_float, c_int, c_void_p, c_size_t, c_void_p],
-    "mla_gemm_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                      c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
-    "mla_gemm_bf16_ws": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                         c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p],
-    "mla_gemm_qkv_rope": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
-                          c_void_p],
-    "mla_gemm_bf16_ws_sq": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_size_t,
-                            c_void_p, c_int, c_void_p, c_void_p],
-    "mla_gemm_bf16_ws_sq_rm": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
-                               c_size_t, c_void_p, c_int, c_void_p, c_void_p],
-    "mla_sum_partials": [c_void_p, c_int, c_void_p, c_int, c_void_p],
-    "mla_gemm_sq_slots": [c_int, c_int, c_int, c_size_t],
-    "mla_gemm_kloop": [c_int],
-    "mla_gemm_cus": [c_int],
-    "mla_side_traffic": [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_void_p],
-    "mla_gemm_gateup_swiglu": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong,
-                               c_void_p],
-    "mla_gemm_dact_swiglu_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong,
-                                 c_void_p],
-    "mla_gemm_dact_swiglu_bwd_rm": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong,
-                                    c_void_p],
-    "mla_rmsnorm_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
-    "mla_rmsnorm_apply": [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p],
-    "mla_rmsnorm_prep": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
-    "mla_gemm_res_norm": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                          c_int, c_void_p, c_size_t, c_void_p],
-    "mla_gemm_qkv_rope_rs": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
-                             c_void_p, c_int, c_float, c_void_p, c_void_p],
-    "mla_gemm_gateup_swiglu_rs": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong,
-                                  c_void_p, c_int, c_float, c_void_p, c_void_p],
-    "mla_rmsnorm_bwd_blocks": [c_int],
-    "mla_timm_rmsnorm_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
-    "mla_timm_rmsnorm_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
-                             c_size_t, c_void_p],
-    "mla_rmsnorm_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
-                        c_size_t, c_void_p],
-    "mla_colsum_blocks": [c_int],
-    "mla_colsum_bf16": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p],
-    "mla_layernorm_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
-    "mla_rope_inplace": [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "mla_swiglu_fwd": [c_void_p, c_void_p, c_longlong, c_int, c_void_p],
-    "mla_swiglu_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p],
-    "mla_act_fwd": [c_void_p, c_void_p, c_longlong, c_int, c_void_p],
-    "mla_act_bwd": [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p],
-    "mla_cast_f32_to_bf16": [c_void_p, c_void_p, c_longlong, c_void_p],
-    "mla_cast_bf16_to_f32": [c_void_p, c_void_p, c_longlong, c_void_p],
-    "mla_add_bf16": [c_void_p, c_void_p, c_void_p, c_longlong, c_void_p],
-    "mla_embedding_fwd": [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p],
-    "mla_embedding_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p],
-    "mla_adamw_step_groups": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_longlong, c_float, c_float, c_float, c_float,
-                              c_float, c_int, c_void_p, c_void_p],
-    "mla_adamw_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_float, c_float, c_float, c_float,
-                       c_float, c_int, c_void_p, c_void_p],
-    "mla_adamw_ema_step_groups": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_longlong, c_float, c_float,
-                                  c_float, c_float, c_float, c_int, c_void_p, c_float, c_float, c_void_p],
-    "mla_adamw_ema_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_float, c_float, c_float, c_float,
-                           c_float, c_int, c_void_p, c_float, c_float, c_void_p],
-    "mla_ema_update": [c_void_p, c_void_p, c_longlong, c_float, c_float, c_void_p],
-    "mla_sumsq_f32": [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_size_t, c_void_p],
-    "mla_clip_coef": [c_void_p, c_float, c_void_p, c_void_p, c_void_p],
-    "mla_q_sample": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "mla_attn_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_longlong,
-                     c_longlong, c_float, c_void_p],
-    "mla_attn_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                     c_void_p, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_float, c_void_p, c_void_p, c_void_p, c_longlong,
-                     c_void_p],
-    "mla_attn_bwd_t": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                       c_void_p, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_float, c_void_p, c_void_p,
-                       c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p],
-    "mla_attn_bwd_sync_ints": [c_int, c_int],                # returns long long (restype fixed up in lib())
-    "mla_attn_fwd_g": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_longlong,
-                       c_longlong, c_float, c_int, c_int, c_void_p, c_void_p],
-    "mla_attn_bwd_g": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                       c_void_p, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_float, c_void_p, c_void_p,
-                       c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_int, c_void_p, c_int, c_void_p],
-    "mla_attn_bwd_ws_bytes": [c_int, c_int, c_int],          # returns long long (restype fixed up in lib())
-    "mla_attn_bwd_ws": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                        c_void_p, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_float, c_void_p, c_void_p,
-                        c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p],
-    "mla_ce_fwd": [c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_int, c_longlong, c_void_p],
-    "mla_ce_bwd": [c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_longlong, c_int, c_int,
-                   c_longlong, c_void_p],
-    "mla_infonce_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
-    "mla_l2norm_fwd": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
-    "mla_l2norm_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
-}
+# name -> argtypes / restype of every entry point, derived from the header's declarations (abi.py): there is no hand-written ctypes row
+_HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mla_hip.h")
+_RESTYPES, _SIGNATURES = abi.load(_HEADER_PATH)
 
 
 def exported_symbols():
-    """Names every build of libmla_hip.so must export (checked by the CPU test-suite)."""
-    return sorted(list(_SIGNATURES.keys()) + ["mla_last_error", "mla_gemm_source_id"] + list(_EXTRA_SIGNATURES.keys()))
-
-
-_EXTRA_SIGNATURES = {}  # filled by optional kernel groups (pointcloud / vision) below
-
-
-def register_signatures(sigs):
-    _EXTRA_SIGNATURES.update(sigs)
-    global _lib
-    if _lib is not None:
-        for name, argt in sigs.items():
-            fn = getattr(_lib, name)
-            fn.argtypes = argt
-            fn.restype = c_int
+    """Names every build of libmla_hip.so must export: the header's declarations (checked by the CPU test-suite)."""
+    return sorted(_SIGNATURES)
 
 
 def lib():
@@ -226,20 +50,10 @@ def lib():
                 f"{_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(mla_amd has no CPU fallback)")
         L = ctypes.CDLL(_LIB_PATH)
-        L.mla_last_error.restype = ctypes.c_char_p
-        L.mla_last_error.argtypes = []
-        L.mla_gemm_source_id.restype = ctypes.c_char_p
-        L.mla_gemm_source_id.argtypes = []
-        for name, argt in {**_SIGNATURES, **_EXTRA_SIGNATURES}.items():
+        for name, argt in _SIGNATURES.items():
             fn = getattr(L, name)
             fn.argtypes = argt
-            fn.restype = c_int
-        L.mla_attn_bwd_ws_bytes.restype = c_longlong
-        L.mla_attn_bwd_sync_ints.restype = c_longlong
-        L.mla_gemm_prefill_ws_bytes.restype = c_longlong
-        L.mla_gemm_prefill_f8_ws_bytes.restype = c_longlong
-        L.mla_gemm_prefill_f8_wide_ws_bytes.restype = c_longlong
-        L.mla_attn_chunk_split_ws_bytes.restype = c_longlong
+            fn.restype = _RESTYPES[name]
         _lib = L
     return _lib
 
@@ -1813,36 +1627,6 @@ def selftest(device="cuda"):
 
 
 # --------------------------------------------------------------------------------------------- point cloud / vision
-register_signatures({
-    "mla_project_points": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_int, c_int, c_void_p],
-    "mla_fps": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "mla_knn": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
-    "mla_lga_prep": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
-                     c_float, c_void_p],
-    "mla_colstats_bf16": [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p, c_size_t, c_void_p],
-    "mla_bn_apply": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_float, c_int,
-                     c_void_p],
-    "mla_maxpool_k": [c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p],
-    "mla_gather_rows_f32": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
-    "mla_im2col_patch": [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "mla_avgpool_tokens": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "mla_local_attn": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p],
-    "mla_local_attn_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p],
-    "mla_swiglu_bwd_t": [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_longlong, c_void_p],
-    "mla_lga_prep_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "mla_maxpool_k_bwd": [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p],
-    "mla_clip_preprocess": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
-                            c_int, c_void_p, c_void_p, c_int, c_void_p],
-    "mla_avgpool_tokens_bwd": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "mla_colstats_blocks": [c_longlong],
-    "mla_gather_rows_bf16": [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p],
-    "mla_transpose_bf16": [c_void_p, c_void_p, c_longlong, c_int, c_longlong, c_longlong, c_void_p],
-    "mla_rmsnorm_apply_t": [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_longlong, c_void_p],
-    "mla_swiglu_fwd_t": [c_void_p, c_void_p, c_longlong, c_int, c_longlong, c_void_p],
-    "mla_swiglu_fwd_dual": [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_longlong, c_void_p],
-})
-
-
 def transpose(x2d, out=None):
     """out[c][r] = x2d[r][c] (bf16, unit inner stride, any row stride)."""
     R, C = x2d.shape
@@ -1984,39 +1768,6 @@ def local_attn(q, kv, B, gh, gw, cs, heads, scale):
 
 
 # --------------------------------------------------------------------------------------------- generation heads
-from ctypes import c_ulonglong  # noqa: E402
-
-register_signatures({
-    "mla_gemm_batched_bf16": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
-                              c_int, c_int, c_longlong, c_longlong, c_longlong, c_longlong, c_longlong, c_longlong, c_void_p],
-    "mla_softmax_rows_fwd": [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_float, c_ulonglong, c_void_p],
-    "mla_softmax_rows_bwd": [c_void_p, c_int, c_void_p, c_void_p, c_longlong, c_int, c_int, c_float, c_ulonglong, c_void_p],
-    "mla_dropout_fwd": [c_void_p, c_void_p, c_void_p, c_longlong, c_float, c_ulonglong, c_void_p],
-    "mla_dropout_bwd": [c_void_p, c_void_p, c_longlong, c_float, c_ulonglong, c_void_p],
-    "mla_scale_batch": [c_void_p, c_void_p, c_void_p, c_longlong, c_longlong, c_void_p],
-    "mla_layernorm_stats_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_float, c_void_p],
-    "mla_layernorm_bwd_blocks": [c_longlong],
-    "mla_layernorm_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_int,
-                          c_void_p, c_size_t, c_void_p],
-    "mla_seqmean_fwd": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "mla_seqmean_bwd": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "mla_bn_bwd_blocks": [c_longlong],
-    "mla_bn_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_int, c_float,
-                   c_void_p, c_size_t, c_void_p],
-    "mla_chamfer_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t,
-                        c_void_p],
-    "mla_chamfer_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "mla_imgloss_fwd": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
-                        c_size_t, c_void_p],
-    "mla_imgroi_fwd": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
-                       c_int, c_int, c_float, c_float, c_void_p, c_size_t, c_void_p],
-    "mla_imgroi_bwd": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                       c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p],
-    "mla_imgloss_bwd": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
-                        c_void_p],
-})
-
-
 def gemm_batched(a, b, out, *, M, N, K, lda, ldb, ldc, a_mode=0, b_mode=0, alpha=1.0, n_outer, n_inner, sA, sB, sC):
     """out[o,i] = alpha * Aop[o,i] . Bop[o,i]^T over a two-level batch; a/b/out are base tensors (offset = data_ptr), strides in
     elements as (outer, inner) pairs. out may be bf16 or fp32."""

@@ -21,8 +21,82 @@ def test_library_exports_every_declared_symbol():
     assert len(syms) >= 45
     missing = [s for s in syms if not hasattr(lib, s)]
     assert not missing, f"declared in include/mla_hip.h but not exported: {missing}"
-    # the ctypes binding and the header agree on the symbol set
+    # the ctypes binding and the header agree on the symbol set. The binding is parsed from the header (mla_amd/abi.py), so this holds by
+    # construction as long as the parser's declaration pattern skips nothing this file's looser regex finds: that is what it still checks
     assert set(hip.exported_symbols()) == set(syms), set(hip.exported_symbols()) ^ set(syms)
+    # every function of the library hip.lib() hands out carries the derived objects: no entry point is left on ctypes' defaults
+    # (int return, arguments converted by guesswork)
+    L = hip.lib()
+    assert set(hip._SIGNATURES) == set(hip._RESTYPES) == set(syms)
+    for s in syms:
+        fn = getattr(L, s)
+        assert fn.restype is hip._RESTYPES[s] and list(fn.argtypes) == hip._SIGNATURES[s], s
+
+
+def _names(restype, argtypes):
+    return {"restype": restype.__name__, "argtypes": [t.__name__ for t in argtypes]}
+
+
+def test_derived_binding_equals_the_last_hand_written_one():
+    """tests/golden/abi_signatures.json is the binding the hand-written ctypes tables gave (tools/capture_abi_golden.py, taken before
+    they were deleted): what mla_amd/abi.py parses out of include/mla_hip.h is the same, symbol for symbol, return type included. A
+    header edit that changes a signature shows up here by name and needs the golden regenerated on purpose."""
+    import json
+    from mla_amd import hip
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "abi_signatures.json")))
+    derived = {s: _names(hip._RESTYPES[s], hip._SIGNATURES[s]) for s in hip._SIGNATURES}
+    assert len(golden) == 153 and set(derived) == set(golden), set(derived) ^ set(golden)
+    wrong = {s: (derived[s], golden[s]) for s in golden if derived[s] != golden[s]}
+    assert not wrong, wrong
+    long_long = sorted(s for s in golden if golden[s]["restype"] == ctypes.c_longlong.__name__)
+    assert long_long == ["mla_attn_bwd_sync_ints", "mla_attn_bwd_ws_bytes", "mla_attn_chunk_split_ws_bytes", "mla_gemm_prefill_f8_wide_ws_bytes",
+                         "mla_gemm_prefill_f8_ws_bytes", "mla_gemm_prefill_ws_bytes"]
+    assert sorted(s for s in golden if golden[s]["restype"] == "c_char_p") == ["mla_gemm_source_id", "mla_last_error"]
+
+
+def test_header_parser_on_literal_declarations():
+    import pytest
+    from ctypes import c_char_p, c_float, c_int, c_longlong, c_size_t, c_ulonglong, c_void_p
+    from mla_amd.abi import parse_header
+    got = parse_header("""
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        typedef struct ihipStream_t* mla_stream_t; /* == hipStream_t; not mla_a_comment(int) */
+        const char * mla_name(void);
+        long long mla_bytes();
+        int mla_spread(const void* a,   /* rows (of a); see mla_other(x); */
+                       const float *b,  // until ) the ( end; of the line
+                       long long n,
+                       mla_stream_t stream);
+        int mla_unnamed(int, const unsigned char*, float, mla_stream_t);
+        int mla_wide(unsigned long long seed, size_t bytes, const size_t n, double* out);
+        #ifdef __cplusplus
+        }
+        #endif
+    """)
+    assert got == {"mla_name": (c_char_p, []), "mla_bytes": (c_longlong, []),
+                   "mla_spread": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p]),
+                   "mla_unnamed": (c_int, [c_void_p if t == "p" else t for t in (c_int, "p", c_float, "p")]),
+                   "mla_wide": (c_int, [c_ulonglong, c_size_t, c_size_t, c_void_p])}
+    for bad in ("double x", "short n", "struct foo v", "int (*cb)(int)", "int a[4]", "...", "int n, ...", "unsigned n", "int64_t n"):
+        with pytest.raises(ValueError, match="mla_bad"):
+            parse_header(f"int mla_ok(int n);\nint mla_bad(void* p, {bad});")
+    for ret in ("void", "float", "double", "void*", "static int", "unsigned long long"):
+        with pytest.raises(ValueError, match="mla_bad"):
+            parse_header(f"{ret} mla_bad(int n);")
+    with pytest.raises(ValueError, match="mla_twice"):
+        parse_header("int mla_twice(int n);\nint mla_twice(int n);")
+    # a spelling the declaration pattern does not take is an error, not a missing symbol
+    with pytest.raises(ValueError, match="mla_braced"):
+        parse_header("int mla_ok(int n);\nint mla_braced(int n) { return n; }")
+
+
+def test_missing_header_is_one_clear_error(tmp_path):
+    import pytest
+    from mla_amd import abi
+    with pytest.raises(RuntimeError, match="no_such_dir/mla_hip.h"):
+        abi.load(str(tmp_path / "no_such_dir" / "mla_hip.h"))
 
 
 def test_attention_object_allocates_nothing_and_keeps_no_state():

@@ -189,7 +189,9 @@ def test_every_entry_point_has_the_keyword():
 
 
 def test_argtypes_match_the_header_and_the_launcher_rejects_bad_sizes():
-    """The ctypes signature has the header's parameter count; no CPU path; the launcher validates on the host before any launch."""
+    """The ctypes signature has the header's parameter count; no CPU path; the launcher validates on the host before any launch.
+    (hip._SIGNATURES is parsed from the header since mla_amd/abi.py, so the count and the pointer positions agree by construction; the
+    comparison stays as an independent reading of the one declaration.)"""
     from mla_amd import hip
     txt = open(os.path.join(ROOT, "include", "mla_hip.h")).read()
     m = re.search(r"\bint\s+mla_ddpm_step\s*\(([^)]*)\)\s*;", txt)
