@@ -774,60 +774,97 @@ def attn_bwd(q, k, v, o, dout, lse, seqlens, dq, dk, dv, B, S, H, D, ld_qkv, sca
 
 
 # --------------------------------------------------------------------------------------------- inference (mla_amd/infer.py)
-def _proj_operands(name, x, W, w_scale, out=None):
-    """The operand checks every suffix projection call opens with: x bf16, W bf16 -- or float8_e4m3fn with w_scale (fp32, one per row
-    of W), which selects the `_w8` argument list, or MXFP4 code bytes [N, K / 2] uint8 with w_scale [N, K / 32] uint8 (one e8m0 byte per
-    block of 32; its row stride is an argument), which selects the `_w4` one --, out bf16 where it is given, unit inner strides. Returns
-    the scale argument(s) of the call: () for bf16 weights."""
+class WeightFormat(NamedTuple):
+    """How the suffix projections (PROJ_FAMILIES) read a weight W [N, K] and its scale: a row of WEIGHT_FORMATS."""
+    name: str                            # mla_<family>_<name>[_pos] in the library, hip.<family>_<name> here (bf16: hip.<family>)
+    dtype: torch.dtype                   # of W
+    k_per_col: int                       # elements of K per stored column of W (2: MXFP4 code pairs, W [N, K / 2])
+    scale_dtype: Optional[torch.dtype]   # of w_scale; None: no scale argument
+    scale_block: int                     # K per scale: w_scale [N, K / scale_block], its row stride passed on; 0: one per row, [N] contiguous
+    k_gran: int                          # K granularity of the launchers
+
+    @property
+    def suffix(self) -> str:
+        return "" if self.scale_dtype is None else "_" + self.name
+
+
+# bf16 as stored; w8: e4m3fn codes and one fp32 scale per row (quant_fp8_rows); w4: MXFP4 code pairs and e8m0 block scales (quant_mxfp4_rows)
+WEIGHT_FORMATS = {f.name: f for f in (WeightFormat("bf16", torch.bfloat16, 1, None, 0, 8),
+                                      WeightFormat("w8", torch.float8_e4m3fn, 1, torch.float32, 0, 16),
+                                      WeightFormat("w4", torch.uint8, 2, torch.uint8, 32, 32))}
+_WF_BF16, _WF_W8, _WF_W4 = WEIGHT_FORMATS.values()
+PROJ_FAMILIES = ("gemv", "gemm_skinny", "gemm_skinny_gateup_swiglu", "gemm_suffix")   # hip.<family><suffix> calls mla_<family>_<name>
+
+
+def _scale_args(fmt, N: int, K: int, scale):
+    """The scale of an [N, K] matrix against the row's shape rule (a K off a bf16 / w8 granularity is the launchers' refusal) -> its call arguments."""
+    if fmt.scale_block:
+        assert K % fmt.k_gran == 0 and scale.shape == (N, K // fmt.scale_block) and scale.stride(1) == 1, f"K % {fmt.k_gran} == 0 required"
+        return _p(scale), scale.stride(0)
+    assert scale.numel() == N and scale.is_contiguous()
+    return (_p(scale),)
+
+
+def _quant_rows(fmt, name, W, q, scale, scale_name):
+    """The quantisers' shared body (mla_<name>): W [N, K] bf16, rows may be strided -> (q, scale) of the row's dtypes and shapes, allocated where not given."""
+    _req(W, torch.bfloat16, f"{name} W")
+    N, K = W.shape
+    if q is None:
+        q = torch.empty((N, K // fmt.k_per_col), dtype=fmt.dtype, device=W.device)
+    if scale is None:
+        scale = torch.empty((N, K // fmt.scale_block) if fmt.scale_block else N, dtype=fmt.scale_dtype, device=W.device)
+    _req(q, fmt.dtype, f"{name} q")
+    _req(scale, fmt.scale_dtype, f"{name} {scale_name}")
+    assert W.stride(1) == 1 and q.shape == (N, K // fmt.k_per_col) and q.stride(1) == 1
+    call("mla_" + name, _p(W), W.stride(0), _p(q), q.stride(0), *_scale_args(fmt, N, K, scale), N, K)
+    return q, scale
+
+
+def _proj_operands(fmt, name, x, W, w_scale, out=None):
+    """The operand checks every suffix projection call opens with, against the format's row: x and out (where given) bf16, W and w_scale
+    of the row's dtypes, the scale of the row's shape, unit inner strides -> (K, the scale arguments of the call: () for bf16 weights)."""
     _req(x, torch.bfloat16, f"{name} x")
-    if w_scale is not None and w_scale.dtype == torch.uint8:
-        _req(W, torch.uint8, f"{name} W")
-        _req(w_scale, torch.uint8, f"{name} w_scale")
-        assert W.dim() == 2 and w_scale.dim() == 2 and w_scale.shape == (W.shape[0], W.shape[1] // 16) and W.shape[1] % 16 == 0
-        assert x.stride(1) == 1 and W.stride(1) == 1 and w_scale.stride(1) == 1
-        if out is not None:
-            _req(out, torch.bfloat16, f"{name} out")
-        return (_p(w_scale), w_scale.stride(0))
-    _req(W, torch.bfloat16 if w_scale is None else torch.float8_e4m3fn, f"{name} W")
-    scale_arg = ()
-    if w_scale is not None:
-        _req(w_scale, torch.float32, f"{name} w_scale")
-        assert w_scale.numel() == W.shape[0] and w_scale.is_contiguous()
-        scale_arg = (_p(w_scale),)
+    _req(W, fmt.dtype, f"{name} W")
+    K, scale_arg = W.shape[1] * fmt.k_per_col, ()
+    if fmt.scale_dtype is not None:
+        _req(w_scale, fmt.scale_dtype, f"{name} w_scale")
+        scale_arg = _scale_args(fmt, W.shape[0], K, w_scale)
     if out is not None:
         _req(out, torch.bfloat16, f"{name} out")
     assert x.stride(1) == 1 and W.stride(1) == 1
-    return scale_arg
+    return K, scale_arg
 
 
-def _weight_k(W) -> int:
-    """K of a projection weight [N, K]: MXFP4 code bytes (uint8) hold two elements each."""
-    return W.shape[1] * (2 if W.dtype == torch.uint8 else 1)
+def _proj_epilogue(name, M, residual, out_col, rope, rope_rows):
+    """The residual and rotary-epilogue checks of the suffix projections -> (residual arguments, rope arguments) of the call. rope =
+    (cos [rope_rows, 64], sin, rope_cols) goes with neither a residual nor a column offset."""
+    res_arg, rope_arg = (None, 0), (None, None, 0)
+    if rope is not None:
+        _req(rope[0], torch.float32, f"{name} rope cos")
+        _req(rope[1], torch.float32, f"{name} rope sin")
+        assert rope[0].shape == (rope_rows, 64) and rope[1].shape == rope[0].shape and rope[0].is_contiguous() and rope[1].is_contiguous()
+        assert out_col == 0 and residual is None
+        rope_arg = (_p(rope[0]), _p(rope[1]), int(rope[2]))
+    if residual is not None:
+        _req(residual, torch.bfloat16, f"{name} residual")
+        assert residual.shape[0] == M and residual.stride(1) == 1
+        res_arg = (_p(residual), residual.stride(0))
+    return res_arg, rope_arg
 
 
-def _skinny_call(name, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope, w_scale=None):
-    """The shared call of the six suffix projections; w_scale selects the argument list: fp32 [N] the `_w8` one (W: float8_e4m3fn), uint8
-    [N, K / 32] the `_w4` one (W: uint8 code pairs [N, K / 2])."""
-    scale_arg = _proj_operands(name, x, W, w_scale, out)
-    M = x.shape[0]
-    K = x.shape[1] // 2 if swiglu else x.shape[1]
-    N = W.shape[0]
-    assert _weight_k(W) == K and not (swiglu and norm_weight is not None)
+def _skinny_call(family, fmt, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope, w_scale=None):
+    """gemv and gemm_skinny in every weight format: mla_<family>_<fmt.name>, the format's scale arguments behind W's."""
+    name = f"mla_{family}_{fmt.name}"
+    K, scale_arg = _proj_operands(fmt, name, x, W, w_scale, out)
+    M, N = x.shape[0], W.shape[0]
+    assert K == (x.shape[1] // 2 if swiglu else x.shape[1]) and not (swiglu and norm_weight is not None)
     pre = 2 if swiglu else (1 if norm_weight is not None else 0)
     if norm_weight is not None:
         _req(norm_weight, torch.bfloat16, f"{name} norm weight")
         assert norm_weight.numel() == K and norm_weight.is_contiguous()
-    if rope is not None:
-        _req(rope[0], torch.float32, f"{name} rope cos")
-        _req(rope[1], torch.float32, f"{name} rope sin")
-        assert rope[0].shape == (rows_per_batch, 64) and rope[1].shape == rope[0].shape and rope[0].is_contiguous() and rope[1].is_contiguous()
-        assert out_col == 0 and residual is None
-    if residual is not None:
-        _req(residual, torch.bfloat16, f"{name} residual")
-        assert residual.shape[0] == M and residual.stride(1) == 1
+    res_arg, rope_arg = _proj_epilogue(name, M, residual, out_col, rope, rows_per_batch)
     call(name, _p(x), x.stride(0), _p(W), W.stride(0), *scale_arg, c_void_p(out.data_ptr() + 2 * out_col), ldo, out_batch_stride, rows_per_batch,
-         _p(residual), residual.stride(0) if residual is not None else 0, M, N, K, pre, _p(norm_weight), float(eps),
-         _p(rope[0]) if rope is not None else None, _p(rope[1]) if rope is not None else None, int(rope[2]) if rope is not None else 0)
+         *res_arg, M, N, K, pre, _p(norm_weight), float(eps), *rope_arg)
 
 
 GEMV_MMAX, GEMV_LDS = 8, 160 * 1024
@@ -843,13 +880,13 @@ def gemv(x, W, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_co
     M <= 8 rows, every weight row read once (mla_gemv_bf16). `out` is a base tensor: only its data pointer is used.
     f = identity; or LlamaRMSNorm(x; norm_weight, eps); or (swiglu=True, x = packed gate|up rows [M, 2 K]) silu(gate) * up.
     rope = (cos [rows_per_batch, 64], sin, rope_cols): output columns [0, rope_cols) are rotated per head of 128 in the epilogue."""
-    _skinny_call("mla_gemv_bf16", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope)
+    _skinny_call("gemv", _WF_BF16, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope)
 
 
 def gemm_skinny(x, W, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, norm_weight=None, eps=0.0, swiglu=False, rope=None):
     """gemv's contract for 1 <= M <= 64 rows and any K (mla_gemm_skinny_bf16): every weight row read once, on the MFMA pipe, x never
     staged in LDS. Same arguments, output addressing, fused RMSNorm / SwiGLU inputs and RoPE epilogue as gemv."""
-    _skinny_call("mla_gemm_skinny_bf16", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope)
+    _skinny_call("gemm_skinny", _WF_BF16, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope)
 
 
 def quant_fp8_rows(W, q=None, scale=None):
@@ -857,33 +894,21 @@ def quant_fp8_rows(W, q=None, scale=None):
     scale[n] = amax[n] / 448 (1 for an all-zero row), q = e4m3fn_rne(clamp(W / scale, -448, 448)); the CPU statement
     (W.float() / scale[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn) gives the same bytes. Returns (q [N, K] float8_e4m3fn,
     scale [N] fp32); q / scale may be given (views of a packed buffer). Non-finite input is not supported."""
-    _req(W, torch.bfloat16, "quant_fp8_rows W")
-    N, K = W.shape
-    assert W.stride(1) == 1
-    if q is None:
-        q = torch.empty((N, K), dtype=torch.float8_e4m3fn, device=W.device)
-    if scale is None:
-        scale = torch.empty(N, dtype=torch.float32, device=W.device)
-    _req(q, torch.float8_e4m3fn, "quant_fp8_rows q")
-    _req(scale, torch.float32, "quant_fp8_rows scale")
-    assert q.shape == (N, K) and q.stride(1) == 1 and scale.numel() == N and scale.is_contiguous()
-    call("mla_quant_fp8_rows", _p(W), W.stride(0), _p(q), q.stride(0), _p(scale), N, K)
-    return q, scale
+    return _quant_rows(_WF_W8, "quant_fp8_rows", W, q, scale, "scale")
 
 
 def gemv_w8(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, norm_weight=None, eps=0.0, swiglu=False,
             rope=None):
     """gemv over FP8 weights (mla_gemv_w8): W [N, K] float8_e4m3fn, w_scale [N] fp32 as quant_fp8_rows writes them; out row m =
     w_scale * (f(x[m]) @ float(W)^T) (+ residual[m]), the scale applied to the finished fp32 sum. K % 16 == 0; everything else is gemv's."""
-    _skinny_call("mla_gemv_w8", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope, w_scale)
+    _skinny_call("gemv", _WF_W8, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope, w_scale)
 
 
 def gemm_skinny_w8(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, norm_weight=None, eps=0.0,
                    swiglu=False, rope=None):
     """gemv_w8's contract for 1 <= M <= 64 rows and any K % 16 == 0 (mla_gemm_skinny_w8): the codes are decoded to bf16 into the MFMA
     operands."""
-    _skinny_call("mla_gemm_skinny_w8", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope,
-                 w_scale)
+    _skinny_call("gemm_skinny", _WF_W8, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope, w_scale)
 
 
 def quant_mxfp4_rows(W, q=None, s=None):
@@ -893,18 +918,7 @@ def quant_mxfp4_rows(W, q=None, s=None):
     the exponent bits; round to nearest, ties to the even mantissa bit, saturating at 6 (include/mla_hip.h has the whole statement).
     Returns (q, s); both may be given (views of a packed buffer: q rows 16-B aligned, unit inner strides; the scale row stride is passed
     on). Non-finite input is not supported."""
-    _req(W, torch.bfloat16, "quant_mxfp4_rows W")
-    N, K = W.shape
-    assert W.stride(1) == 1 and K % 32 == 0, "quant_mxfp4_rows: K % 32 == 0 required"
-    if q is None:
-        q = torch.empty((N, K // 2), dtype=torch.uint8, device=W.device)
-    if s is None:
-        s = torch.empty((N, K // 32), dtype=torch.uint8, device=W.device)
-    _req(q, torch.uint8, "quant_mxfp4_rows q")
-    _req(s, torch.uint8, "quant_mxfp4_rows s")
-    assert q.shape == (N, K // 2) and q.stride(1) == 1 and s.shape == (N, K // 32) and s.stride(1) == 1
-    call("mla_quant_mxfp4_rows", _p(W), W.stride(0), _p(q), q.stride(0), _p(s), s.stride(0), N, K)
-    return q, s
+    return _quant_rows(_WF_W4, "quant_mxfp4_rows", W, q, s, "s")
 
 
 def gemv_w4(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, norm_weight=None, eps=0.0, swiglu=False,
@@ -912,30 +926,27 @@ def gemv_w4(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=
     """gemv over MXFP4 weights (mla_gemv_w4): W [N, K / 2] uint8 codes, w_scale [N, K / 32] uint8 as quant_mxfp4_rows writes them; the codes
     are decoded with their block scale (exact in bf16), so out row m = f(x[m]) @ dequantised(W)^T (+ residual[m]) with gemv's single bf16
     rounding. K % 32 == 0; everything else is gemv's."""
-    _skinny_call("mla_gemv_w4", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope, w_scale)
+    _skinny_call("gemv", _WF_W4, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope, w_scale)
 
 
 def gemm_skinny_w4(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, norm_weight=None, eps=0.0,
                    swiglu=False, rope=None):
     """gemv_w4's contract for 1 <= M <= 64 rows and any K % 32 == 0 (mla_gemm_skinny_w4): the codes are decoded to bf16 into the MFMA
     operands, on gemm_skinny_w8's K steps."""
-    _skinny_call("mla_gemm_skinny_w4", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope,
-                 w_scale)
+    _skinny_call("gemm_skinny", _WF_W4, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, norm_weight, eps, swiglu, rope, w_scale)
 
 
-def _skinny_gateup_call(name, x, W, out, ldo, w_scale=None):
-    """The shared call of the two gate|up + SwiGLU projections: _skinny_call's argument checks without a residual, a rotary epilogue or a
-    pre-transform; out [M, I] is allocated when not given (ldo: its row stride in elements, default out.stride(0))."""
-    scale_arg = _proj_operands(name, x, W, w_scale)
-    M, K = x.shape
-    assert W.shape[0] % 2 == 0 and _weight_k(W) == K
-    I = W.shape[0] // 2
+def _skinny_gateup_call(fmt, x, W, out, ldo, w_scale=None):
+    """The shared call of the gate|up + SwiGLU projection in every weight format: _skinny_call's argument checks without a residual, a
+    rotary epilogue or a pre-transform; out [M, I] is allocated when not given (ldo: its row stride in elements, default out.stride(0))."""
+    name = f"mla_gemm_skinny_gateup_swiglu_{fmt.name}"
+    K, scale_arg = _proj_operands(fmt, name, x, W, w_scale)
+    assert W.shape[0] % 2 == 0 and x.shape[1] == K
+    M, I = x.shape[0], W.shape[0] // 2
     if out is None:
         out = torch.empty((M, I), dtype=torch.bfloat16, device=x.device)
     _req(out, torch.bfloat16, f"{name} out")
-    if ldo is None:
-        ldo = out.stride(0)
-    call(name, _p(x), x.stride(0), _p(W), W.stride(0), *scale_arg, _p(out), ldo, M, I, K)
+    call(name, _p(x), x.stride(0), _p(W), W.stride(0), *scale_arg, _p(out), out.stride(0) if ldo is None else ldo, M, I, K)
     return out
 
 
@@ -943,19 +954,19 @@ def gemm_skinny_gateup_swiglu(x, W, out=None, ldo=None):
     """silu(x @ Wg^T) * (x @ Wu^T) for 1 <= M <= 64 rows, W = the packed gate|up matrix [2 I, K] (mla_gemm_skinny_gateup_swiglu_bf16):
     gemm_skinny's plain form with SwiGLU in the epilogue -- bit for bit swiglu_fwd(gemm_skinny(x, W)), the [M, 2 I] rows never reach
     memory. Returns out [M, I] bf16 (`out` may be given: a base tensor with row stride ldo >= I)."""
-    return _skinny_gateup_call("mla_gemm_skinny_gateup_swiglu_bf16", x, W, out, ldo)
+    return _skinny_gateup_call(_WF_BF16, x, W, out, ldo)
 
 
 def gemm_skinny_gateup_swiglu_w8(x, W, w_scale, out=None, ldo=None):
     """gemm_skinny_gateup_swiglu over FP8 weights (mla_gemm_skinny_gateup_swiglu_w8): W [2 I, K] float8_e4m3fn, w_scale [2 I] fp32; each
     finished fp32 sum times its own row's scale in front of the bf16 rounding, as gemm_skinny_w8 does. K % 16 == 0."""
-    return _skinny_gateup_call("mla_gemm_skinny_gateup_swiglu_w8", x, W, out, ldo, w_scale)
+    return _skinny_gateup_call(_WF_W8, x, W, out, ldo, w_scale)
 
 
 def gemm_skinny_gateup_swiglu_w4(x, W, w_scale, out=None, ldo=None):
     """gemm_skinny_gateup_swiglu over MXFP4 weights (mla_gemm_skinny_gateup_swiglu_w4): W [2 I, K / 2] uint8 codes, w_scale [2 I, K / 32]
     uint8; bit for bit swiglu_fwd of gemm_skinny_w4's output. K % 32 == 0."""
-    return _skinny_gateup_call("mla_gemm_skinny_gateup_swiglu_w4", x, W, out, ldo, w_scale)
+    return _skinny_gateup_call(_WF_W4, x, W, out, ldo, w_scale)
 
 
 def attn_decode(cache, B, nheads, D, S_kv, R, scale):
@@ -1057,14 +1068,14 @@ def attn_chunk_split(cache, B, nheads, D, S_kv, R, scale, splits=None, ws=None):
 SUFFIX_MMAX = 256
 
 
-def _suffix_call(sym, name, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows, w_scale=None,
+def _suffix_call(fmt, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows, w_scale=None,
                  rope_pos=None, rope_rows=None):
-    """The shared call of the two batched suffix projections; w_scale (fp32 [N]) selects the `_w8` argument list (W: float8_e4m3fn),
-    rope_pos (int32, one rotary position per sample) the `_pos` entry point."""
-    scale_arg = _proj_operands(name, x, W, w_scale, out)
-    M, K = x.shape
-    N = W.shape[0]
-    assert _weight_k(W) == K
+    """The shared call of the batched suffix projection in every weight format: mla_gemm_suffix_<fmt.name>, the format's scale arguments
+    behind W's; rope_pos (int32, one rotary position per sample) selects the `_pos` entry point."""
+    sym, name = f"mla_gemm_suffix_{fmt.name}", "gemm_suffix" + fmt.suffix
+    K, scale_arg = _proj_operands(fmt, name, x, W, w_scale, out)
+    M, N = x.shape[0], W.shape[0]
+    assert x.shape[1] == K
     if slot is not None:
         _req(slot, torch.int32, f"{name} slot")
         assert cap_rows is not None and slot.is_contiguous() and slot.numel() * rows_per_batch >= M
@@ -1075,19 +1086,9 @@ def _suffix_call(sym, name, x, W, out, ldo, out_batch_stride, rows_per_batch, re
         assert rope is not None and rope_rows is not None and rope_pos.is_contiguous() and rope_pos.numel() * rows_per_batch >= M
         pos_arg = (_p(rope_pos), int(rope_rows))
         sym += "_pos"
-    if rope is not None:
-        _req(rope[0], torch.float32, f"{name} rope cos")
-        _req(rope[1], torch.float32, f"{name} rope sin")
-        assert rope[0].shape == (cap if rope_pos is None else int(rope_rows), 64) and rope[1].shape == rope[0].shape
-        assert rope[0].is_contiguous() and rope[1].is_contiguous()
-        assert out_col == 0 and residual is None
-    if residual is not None:
-        _req(residual, torch.bfloat16, f"{name} residual")
-        assert residual.shape[0] == M and residual.stride(1) == 1
+    res_arg, rope_arg = _proj_epilogue(name, M, residual, out_col, rope, cap if rope_pos is None else int(rope_rows))
     call(sym, _p(x), x.stride(0), _p(W), W.stride(0), *scale_arg, c_void_p(out.data_ptr() + 2 * out_col), ldo, out_batch_stride,
-         rows_per_batch, _p(slot), cap, _p(residual), residual.stride(0) if residual is not None else 0, M, N, K,
-         _p(rope[0]) if rope is not None else None, _p(rope[1]) if rope is not None else None, int(rope[2]) if rope is not None else 0,
-         *pos_arg)
+         rows_per_batch, _p(slot), cap, *res_arg, M, N, K, *rope_arg, *pos_arg)
 
 
 def gemm_suffix(x, W, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, rope=None, slot=None, cap_rows=None,
@@ -1098,8 +1099,7 @@ def gemm_suffix(x, W, out, ldo, out_batch_stride, rows_per_batch, residual=None,
     None = every slot 0. rope = (cos [cap_rows or rows_per_batch, 64], sin, rope_cols): row slot[b] + p of the tables rotates the row.
     rope_pos (mla_gemm_suffix_bf16_pos): int32 [B] device tensor with rope_rows = rows of the tables ([rope_rows, 64]); the row is then
     rotated with table row rope_pos[b] + p instead, and not written when that lies outside [0, rope_rows). None = the call above."""
-    _suffix_call("mla_gemm_suffix_bf16", "gemm_suffix", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows,
-                 rope_pos=rope_pos, rope_rows=rope_rows)
+    _suffix_call(_WF_BF16, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows, rope_pos=rope_pos, rope_rows=rope_rows)
 
 
 def gemm_suffix_w8(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, rope=None, slot=None, cap_rows=None,
@@ -1107,8 +1107,7 @@ def gemm_suffix_w8(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, re
     """gemm_suffix over FP8 weights (mla_gemm_suffix_w8): W [N, K] float8_e4m3fn, w_scale [N] fp32 as quant_fp8_rows writes them; out row m =
     w_scale * (x[m] @ float(W)^T) (+ residual[m]), the scale applied to the finished fp32 sum (gemm_skinny_w8's arithmetic: every 64-row
     slice is bit for bit its output). K % 16 == 0; rows, slots, rope, rope_pos (mla_gemm_suffix_w8_pos) and addressing are gemm_suffix's."""
-    _suffix_call("mla_gemm_suffix_w8", "gemm_suffix_w8", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows,
-                 w_scale, rope_pos=rope_pos, rope_rows=rope_rows)
+    _suffix_call(_WF_W8, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows, w_scale, rope_pos, rope_rows)
 
 
 def gemm_suffix_w4(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, residual=None, out_col=0, rope=None, slot=None, cap_rows=None,
@@ -1116,8 +1115,7 @@ def gemm_suffix_w4(x, W, w_scale, out, ldo, out_batch_stride, rows_per_batch, re
     """gemm_suffix over MXFP4 weights (mla_gemm_suffix_w4): W [N, K / 2] uint8 codes, w_scale [N, K / 32] uint8 as quant_mxfp4_rows writes
     them; gemm_skinny_w4's arithmetic (every 64-row slice is bit for bit its output). K % 32 == 0; rows, slots, rope, rope_pos
     (mla_gemm_suffix_w4_pos) and addressing are gemm_suffix's."""
-    _suffix_call("mla_gemm_suffix_w4", "gemm_suffix_w4", x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows,
-                 w_scale, rope_pos=rope_pos, rope_rows=rope_rows)
+    _suffix_call(_WF_W4, x, W, out, ldo, out_batch_stride, rows_per_batch, residual, out_col, rope, slot, cap_rows, w_scale, rope_pos, rope_rows)
 
 
 # ---- compact prefill GEMMs (mla_amd/csrc/prefill.hip): 1 <= M <= 1024 rows, 64 x 128 tiles, deterministic split-K through a workspace. Two

@@ -279,32 +279,65 @@ class _DdimState:
                  "noise", "known", "pin")
 
 
+class _Coded:
+    """What the coded projection weights share. A class is a tuple (q, scale) as its quantiser writes them and says: fmt, its row of
+    hip.WEIGHT_FORMATS; name, the mode value that streams the codes (name + "_as_bf16": the bf16 kernels on their dequantisation);
+    slot and label, where vlm.__dict__ keeps the model's copy and what the log calls it; of(W), the quantiser; dequantised(), the
+    exact bf16 matrix. A new format is a row of hip.WEIGHT_FORMATS, a class here and its entry in CODED."""
+    __slots__ = ()
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self)
+
+
+class W8(_Coded, collections.namedtuple("W8", "q scale")):
+    """A quantised projection weight: q [N, K] float8_e4m3fn codes, scale [N] fp32 (one per output channel)."""
+    __slots__ = ()
+    fmt, name, slot, label = hip.WEIGHT_FORMATS["w8"], "fp8", "_prefix_fp8", "suffix_weights: FP8"
+
+    @classmethod
+    def of(cls, W):
+        return cls(*hip.quant_fp8_rows(W))
+
+    def dequantised(self) -> torch.Tensor:
+        return (self.q.float() * self.scale[:, None]).to(torch.bfloat16)
+
+
+class W4(_Coded, collections.namedtuple("W4", "q scale")):
+    """An MXFP4 projection weight: q [N, K / 2] uint8 (two e2m1 codes per byte), scale [N, K / 32] uint8 (one e8m0 byte per block of 32)."""
+    __slots__ = ()
+    fmt, name, slot, label = hip.WEIGHT_FORMATS["w4"], "fp4", "_prefix_mxfp4", "suffix_mx: MXFP4"
+
+    @classmethod
+    def of(cls, W):
+        return cls(*hip.quant_mxfp4_rows(W))
+
+    def dequantised(self) -> torch.Tensor:
+        """bf16 [N, K], exact: sign * {0, 0.5, 1, 1.5, 2, 3, 4, 6}[index] * 2^(scale - 127) is a bf16 value."""
+        grid = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0], device=self.q.device)
+        N, K = self.q.shape[0], self.q.shape[1] * 2
+        q = self.q.to(torch.int64)
+        val = grid[torch.stack([q & 15, q >> 4], dim=-1).view(N, K)]
+        scale = torch.pow(2.0, self.scale.to(torch.float32) - 127.0)         # exact: integer exponents within [-125, 125]
+        return (val.view(N, K // 32, 32) * scale[..., None]).view(N, K).to(torch.bfloat16)
+
+
+CODED = {cls.name: cls for cls in (W8, W4)}          # by the mode value (suffix_weights / suffix_mx / prefill_precision / batch_prefill)
+
+
 def _fake_quant_rows(x):
     """bf16(code * scale) of hip.quant_fp8_rows(x): what a projection of prefill_precision="fp8" sees of its input rows, as bf16."""
-    q, scale = hip.quant_fp8_rows(x)
-    return (q.float() * scale[:, None]).to(torch.bfloat16)
+    return W8.of(x).dequantised()
 
 
-class W8(NamedTuple):
-    """A quantised projection weight: q [N, K] float8_e4m3fn codes, scale [N] fp32 (one per output channel)."""
-    q: torch.Tensor
-    scale: torch.Tensor
-
-
-class W4(NamedTuple):
-    """An MXFP4 projection weight: q [N, K / 2] uint8 (two e2m1 codes per byte), s [N, K / 32] uint8 (one e8m0 scale byte per block of 32)."""
-    q: torch.Tensor
-    s: torch.Tensor
-
-
-def _mxfp4_dequantised(w: W4) -> torch.Tensor:
-    """bf16 [N, K] of an MXFP4 weight, exact: sign * {0, 0.5, 1, 1.5, 2, 3, 4, 6}[index] * 2^(s - 127) is a bf16 value."""
-    grid = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0], device=w.q.device)
-    N, K = w.q.shape[0], w.q.shape[1] * 2
-    q = w.q.to(torch.int64)
-    val = grid[torch.stack([q & 15, q >> 4], dim=-1).view(N, K)]
-    scale = torch.pow(2.0, w.s.to(torch.float32) - 127.0)                   # exact: integer exponents within [-125, 125]
-    return (val.view(N, K // 32, 32) * scale[..., None]).view(N, K).to(torch.bfloat16)
+def _operands(weights):
+    """(format row, the W [and scale] arguments) of a projection's weights as ONE launch reads them: a coded weight as it is, bf16 views
+    as their common view -- None when they are not adjacent in memory."""
+    if isinstance(weights, _Coded):
+        return weights.fmt, tuple(weights)
+    wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
+    return hip.WEIGHT_FORMATS["bf16"], (None if wcat is None else (wcat,))
 
 
 class _CachedEpsBase:
@@ -312,7 +345,7 @@ class _CachedEpsBase:
     A subclass provides prefill() and _suffix_pass() and sets B, R, T, H, h_in, h_out, cache."""
 
     suffix_operand = "fused"         # MODES: read by PrefixCachedEps._suffix_pass; the row-GEMM engines form the operand once anyway
-    suffix_mx = "off"                # MODES: read by _weights / _suffix_layers; "off" leaves the choice to suffix_weights
+    suffix_mx = "off"                # MODES: read by _stream; "off" leaves the choice to suffix_weights
 
     def __init__(self, vlm, n_action_rows: int = 1, modes: Modes = Modes()):
         """modes: as the factory validated them (engine_modes). The multi-row engines' attention mode is groups_attention."""
@@ -335,7 +368,7 @@ class _CachedEpsBase:
         self.graph_error = None      # why the suffix pass could not be captured (eager launches then), for diagnostics
         self._packed = None          # per layer: the 9 weights with q|k|v and gate|up as views of ONE buffer each (see _weights)
         self._packed_key = None
-        self._suffix = None          # per layer: what the suffix pass streams -- _packed itself ("bf16") or a quantised copy (_quantised)
+        self._suffix = None          # per layer: what the suffix pass streams -- _packed itself ("bf16") or a form of a coded copy (_weight_copy)
         self._ddim = {}              # sample_ddim's state per (B, action_dim): see _DdimState
         self._ddpm = {}              # sample_ddpm's, kept apart: a DDIM and a DDPM call on one engine keep their captured steps
         self._ddim_pin = {}          # the states of the pinned calls (pin=), kept apart in the same way: the un-pinned call replays ...
@@ -393,78 +426,53 @@ class _CachedEpsBase:
         if self._packed is not shared["packed"]:
             self.graph = None            # a captured pass holds the previous buffers' addresses
             self._packed, self._packed_key = shared["packed"], key
-        if self.suffix_mx != "off":
-            suffix = self._quantised_mx(key)
-        else:
-            suffix = self._packed if self.suffix_weights == "bf16" else self._quantised(key)
+        coded = CODED.get(self._stream.removesuffix("_as_bf16"))
+        suffix = self._packed if coded is None else self._weight_copy(coded, self._stream)
         if self._suffix is not suffix:
             self.graph = None
             self._suffix = suffix
         return self._packed
 
-    def _quantised(self, key, mode=None):
-        """The model's FP8 weight copy in the form `mode` ("fp8" / "fp8_as_bf16"; default: what the suffix pass streams) -- also what the
-        prefill of prefill_precision "fp8" / "fp8_as_bf16" runs on, whatever self.suffix_weights is: per layer q|k|v, o, gate|up and down
-        of the packed copy quantised per output channel (hip.quant_fp8_rows; the scale is per row, so the packed matrices quantise as one), kept beside the packed copy:
-        one per model, shared by its engines, keyed like it on (data_ptr, _version) of the layer weights and rebuilt when that changes.
-        "fp8": per layer (ln1, W8 qkv, W8 o, ln2, W8 gate|up, W8 down). "fp8_as_bf16": the packed tuple's layout with bf16(q * scale) in
-        place of every projection (built from the same codes on first use)."""
-        shared = self.vlm.__dict__.setdefault("_prefix_fp8", {})
-        if shared.get("key") != key:
-            layers, nbytes = [], 0
-            with torch.no_grad(), torch.inference_mode(False):
-                for ln1, wq, wk, wv, wo, ln2, wg, wu, wd in self._packed:
-                    mats = [W8(*hip.quant_fp8_rows(m)) for m in (ops.cat_view((wq, wk, wv)), wo, ops.cat_view((wg, wu)), wd)]
-                    nbytes += sum(m.q.numel() + 4 * m.scale.numel() for m in mats)
-                    layers.append((ln1, mats[0], mats[1], ln2, mats[2], mats[3]))
-            shared.clear()
-            shared["key"], shared["fp8"] = key, layers
-            _LOG.info("suffix_weights: FP8 copy of the decoder projections, %.2f GB beside the bf16 weights", nbytes / 1e9)
-        mode = self.suffix_weights if mode is None else mode
-        if mode == "fp8_as_bf16" and "fp8_as_bf16" not in shared:
-            deq = []
-            with torch.no_grad(), torch.inference_mode(False):
-                for (ln1, qkv, o, ln2, gu, d), packed in zip(shared["fp8"], self._packed):
-                    qkv, o, gu, d = ((m.q.float() * m.scale[:, None]).to(torch.bfloat16) for m in (qkv, o, gu, d))
-                    nq, nk, ng = packed[1].shape[0], packed[2].shape[0], packed[6].shape[0]
-                    deq.append((ln1, qkv[:nq], qkv[nq:nq + nk], qkv[nq + nk:], o, ln2, gu[:ng], gu[ng:], d))
-            shared["fp8_as_bf16"] = deq
-        return shared[mode]
+    @property
+    def _stream(self) -> str:
+        """What the suffix pass streams, as the value of the one keyword that says so: suffix_mx unless it is "off", else suffix_weights
+        (check_one_suffix_copy: at most one of the two is away from its default). A key of CODED: the pass streams codes."""
+        return self.suffix_weights if self.suffix_mx == "off" else self.suffix_mx
 
-    def _quantised_mx(self, key):
-        """_quantised's twin for suffix_mx: the model's MXFP4 weight copy in the form self.suffix_mx -- per layer q|k|v, o, gate|up and
-        down of the packed copy (hip.quant_mxfp4_rows; blocks never cross rows, so the packed matrices quantise as one), in its own slot
-        beside the FP8 copy and independent of it: one per model, shared by its engines, keyed on (data_ptr, _version) of the layer
-        weights and rebuilt when that changes. "fp4": per layer (ln1, W4 qkv, W4 o, ln2, W4 gate|up, W4 down). "fp4_as_bf16": the packed
-        tuple's layout with the dequantised matrices (built from the same codes on first use)."""
-        shared = self.vlm.__dict__.setdefault("_prefix_mxfp4", {})
-        if shared.get("key") != key:
+    def _weight_copy(self, coded, form):
+        """The model's copy of the decoder projections in the format `coded` (W8 / W4), as `form` (call behind _weights()):
+        coded.name -- per layer (ln1, coded q|k|v, coded o, ln2, coded gate|up, coded down), quantised from the packed copy (a scale
+        belongs to one row or to a block inside one, so the packed matrices quantise as one);
+        coded.name + "_as_bf16" -- the packed tuple's layout with the dequantised matrices, built from the same codes on first use.
+        One per model and format in its own slot of vlm.__dict__, independent of the other format's and shared by the model's engines --
+        the suffix pass, and for W8 the prefill of prefill_precision / batch_prefill whatever the suffix pass streams --, keyed like the
+        packed copy on (data_ptr, _version) of the layer weights and rebuilt when that changes."""
+        shared = self.vlm.__dict__.setdefault(coded.slot, {})
+        if shared.get("key") != self._packed_key:
             layers, nbytes = [], 0
             with torch.no_grad(), torch.inference_mode(False):
                 for ln1, wq, wk, wv, wo, ln2, wg, wu, wd in self._packed:
-                    mats = [W4(*hip.quant_mxfp4_rows(m)) for m in (ops.cat_view((wq, wk, wv)), wo, ops.cat_view((wg, wu)), wd)]
-                    nbytes += sum(m.q.numel() + m.s.numel() for m in mats)
+                    mats = [coded.of(m) for m in (ops.cat_view((wq, wk, wv)), wo, ops.cat_view((wg, wu)), wd)]
+                    nbytes += sum(m.nbytes for m in mats)
                     layers.append((ln1, mats[0], mats[1], ln2, mats[2], mats[3]))
             shared.clear()
-            shared["key"], shared["fp4"] = key, layers
-            _LOG.info("suffix_mx: MXFP4 copy of the decoder projections, %.2f GB beside the bf16 weights", nbytes / 1e9)
-        if self.suffix_mx == "fp4_as_bf16" and "fp4_as_bf16" not in shared:
+            shared["key"], shared[coded.name] = self._packed_key, layers
+            _LOG.info("%s copy of the decoder projections, %.2f GB beside the bf16 weights", coded.label, nbytes / 1e9)
+        if form not in shared:
             deq = []
             with torch.no_grad(), torch.inference_mode(False):
-                for (ln1, qkv, o, ln2, gu, d), packed in zip(shared["fp4"], self._packed):
-                    qkv, o, gu, d = (_mxfp4_dequantised(m) for m in (qkv, o, gu, d))
+                for (ln1, qkv, o, ln2, gu, d), packed in zip(shared[coded.name], self._packed):
+                    qkv, o, gu, d = (m.dequantised() for m in (qkv, o, gu, d))
                     nq, nk, ng = packed[1].shape[0], packed[2].shape[0], packed[6].shape[0]
                     deq.append((ln1, qkv[:nq], qkv[nq:nq + nk], qkv[nq + nk:], o, ln2, gu[:ng], gu[ng:], d))
-            shared["fp4_as_bf16"] = deq
-        return shared[self.suffix_mx]
+            shared[form] = deq
+        return shared[form]
 
     def _suffix_layers(self):
-        """Per layer ((ln1, qkv, o, ln2, gate_up, down), cache) of a suffix pass: every projection one W8 ("fp8", _quantised), one W4
-        (suffix_mx "fp4", _quantised_mx) or a tuple of bf16 matrices -- views of the packed 9-tuple ("bf16") or of a dequantised twin
-        ("fp8_as_bf16", "fp4_as_bf16")."""
-        coded = self.suffix_mx == "fp4" or (self.suffix_mx == "off" and self.suffix_weights == "fp8")
+        """Per layer ((ln1, qkv, o, ln2, gate_up, down), cache) of a suffix pass: every projection one coded weight (_stream "fp8" / "fp4")
+        or a tuple of bf16 matrices -- views of the packed 9-tuple ("bf16") or of a dequantised twin ("fp8_as_bf16", "fp4_as_bf16")."""
         for w, c in zip(self._suffix, self.cache):
-            yield (w if coded else (w[0], w[1:4], w[4:5], w[5], w[6:8], w[8:9])), c
+            yield (w if self._stream in CODED else (w[0], w[1:4], w[4:5], w[5], w[6:8], w[8:9])), c
 
     def _finish(self, h):
         """The end of every suffix pass: the model's final norm over the rows, into the static output rows."""
@@ -527,9 +535,9 @@ class _CachedEpsBase:
 
     def _prefill_layers(self):
         """Per layer what _compact_layer runs on: the packed 9-tuple ("bf16"), its dequantised twin ("fp8_as_bf16") or the W8 6-tuple
-        ("fp8") of the model's FP8 copy (_quantised)."""
+        ("fp8") of the model's FP8 copy (_weight_copy)."""
         packed = self._weights()
-        return packed if self.prefill_precision == "bf16" else self._quantised(self._packed_key, self.prefill_precision)
+        return packed if self.prefill_precision == "bf16" else self._weight_copy(W8, self.prefill_precision)
 
     def _compact_prefill(self, h, B, S_p, cache_out, out_bs):
         """The decoder layers over the B * S_p prefix rows h [B * S_p, H] on the compact GEMMs; cache_out[l] is layer l's cache tensor whose
@@ -860,33 +868,23 @@ class PrefixCachedEps(_CachedEpsBase):
 
     # ------------------------------------------------------------------------------------------ one pass over the suffix rows
     def _gemv(self, x, weights, out=None, residual=None, rpb=1, out_bs=0, **pre):
-        """f(x) [M, K] @ W^T (+ residual) -> [M, N]; `weights` is a tuple of bf16 matrices (one launch when they are adjacent in memory) or
-        one W8 (always packed: one launch).
+        """f(x) [M, K] @ W^T (+ residual) -> [M, N]; `weights` is one coded weight or a tuple of bf16 matrices: one launch (_operands),
+        or one per matrix when the bf16 matrices are not adjacent in memory.
         pre: norm_weight= / eps= (RMSNorm of the rows) or swiglu=True (x = packed gate|up rows), applied inside the kernel's input staging."""
-        M, w8, w4 = x.shape[0], isinstance(weights, W8), isinstance(weights, W4)
-        if w4:
-            N, K = weights.q.shape[0], weights.q.shape[1] * 2
-        else:
-            N, K = weights.q.shape if w8 else (sum(w.shape[0] for w in weights), weights[0].shape[1])
+        fmt, W = _operands(weights)
+        M = x.shape[0]
+        N, K = (sum(w.shape[0] for w in weights), weights[0].shape[1]) if W is None else (W[0].shape[0], W[0].shape[1] * fmt.k_per_col)
         if out is None:
             out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
             rpb, out_bs = M, 0
         ldo = out.stride(-2)
-        # mla_gemv_bf16 / mla_gemv_w8 wherever they accept the rows (the results of every configuration they served stay bit for bit the
-        # same), the MFMA skinny GEMM beyond (M > 8, or the M x K input rows do not fit the LDS: 7B down projection at M = 8). Measured
-        # for w8 at 7B (DESIGN 3.5, profiles/fp8_infer_latency.txt): right at M = 2; at M = 5 .. 8 the MFMA form would be 2-7 % faster per
-        # layer, M = 3, 4 not measured -- the switch point is left here until they are.
-        fits = hip.gemv_fits(M, K)
-        if w8:
-            (hip.gemv_w8 if fits else hip.gemm_skinny_w8)(x, weights.q, weights.scale, out, ldo, out_bs, rpb, residual, **pre)
-            return out
-        if w4:                                                               # the same switch point: not measured apart from w8's
-            (hip.gemv_w4 if fits else hip.gemm_skinny_w4)(x, weights.q, weights.s, out, ldo, out_bs, rpb, residual, **pre)
-            return out
-        gemv = hip.gemv if fits else hip.gemm_skinny
-        wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
-        if wcat is not None:
-            gemv(x, wcat, out, ldo, out_bs, rpb, residual, **pre)
+        # mla_gemv_* wherever it accepts the rows (the results of every configuration it served stay bit for bit the same), the MFMA
+        # skinny GEMM beyond (M > 8, or the M x K input rows do not fit the LDS: 7B down projection at M = 8). Measured for w8 at 7B
+        # (DESIGN 3.5, profiles/fp8_infer_latency.txt): right at M = 2; at M = 5 .. 8 the MFMA form would be 2-7 % faster per layer,
+        # M = 3, 4 not measured -- the switch point is left here, for every format, until they are.
+        gemv = getattr(hip, ("gemv" if hip.gemv_fits(M, K) else "gemm_skinny") + fmt.suffix)
+        if W is not None:
+            gemv(x, *W, out, ldo, out_bs, rpb, residual, **pre)
         else:                                                                # parameters not laid out back to back (no FlatUnit): one launch each
             off = 0
             for w in weights:
@@ -896,15 +894,11 @@ class PrefixCachedEps(_CachedEpsBase):
 
     def _gate_up_act(self, xn2, gu_w):
         """silu(xn2 @ Wg^T) * (xn2 @ Wu^T) -> act [M, I] of the "once" pass: the gate|up projection with the SwiGLU epilogue where gate|up
-        is one matrix (a W8, or bf16 views adjacent in memory) -- the packed rows never reach memory --, otherwise one plain launch per
-        matrix into a gate|up buffer and the stand-alone swiglu_fwd. The same bits either way."""
-        if isinstance(gu_w, W8):
-            return hip.gemm_skinny_gateup_swiglu_w8(xn2, gu_w.q, gu_w.scale)
-        if isinstance(gu_w, W4):
-            return hip.gemm_skinny_gateup_swiglu_w4(xn2, gu_w.q, gu_w.s)
-        wcat = ops.cat_view(gu_w)
-        if wcat is not None:
-            return hip.gemm_skinny_gateup_swiglu(xn2, wcat)
+        is one matrix (a coded weight, or bf16 views adjacent in memory) -- the packed rows never reach memory --, otherwise one plain
+        launch per matrix into a gate|up buffer and the stand-alone swiglu_fwd. The same bits either way."""
+        fmt, W = _operands(gu_w)
+        if W is not None:
+            return getattr(hip, "gemm_skinny_gateup_swiglu" + fmt.suffix)(xn2, *W)
         return hip.swiglu_fwd(self._gemv(xn2, gu_w))
 
     def _suffix_pass_once(self):
@@ -916,7 +910,7 @@ class PrefixCachedEps(_CachedEpsBase):
         scale = 1.0 / math.sqrt(self.D)
         attn = self._suffix_attn()
         for (ln1, qkv, wo, ln2, gu_w, wd), c in self._suffix_layers():
-            fused = self.D == 128 and (isinstance(qkv, (W8, W4)) or ops.cat_view(qkv) is not None)      # the rotary epilogue, as in _suffix_pass
+            fused = self.D == 128 and _operands(qkv)[1] is not None          # the rotary epilogue, as in _suffix_pass
             xn, _ = hip.rmsnorm_fwd(h, ln1, self.eps)
             self._gemv(xn, qkv, out=c[:, S_p:], rpb=R, out_bs=c.stride(0), **({"rope": (self.cos_s, self.sin_s, 2 * H)} if fused else {}))
             if not fused:
@@ -941,7 +935,7 @@ class PrefixCachedEps(_CachedEpsBase):
         for (ln1, qkv, wo, ln2, gu_w, wd), c in self._suffix_layers():
             # north_star's "fused RMSNorm + RoPE + QKV" as ONE kernel: RMSNorm inside the projection's input staging, the rotary embedding of
             # the q and k columns in its epilogue; the rows go straight into the cache slots [S_p, S_p + R) of every sample
-            fused = self.D == 128 and (isinstance(qkv, (W8, W4)) or ops.cat_view(qkv) is not None)
+            fused = self.D == 128 and _operands(qkv)[1] is not None
             self._gemv(h, qkv, out=c[:, S_p:], rpb=R, out_bs=c.stride(0), norm_weight=ln1, eps=self.eps,
                        **({"rope": (self.cos_s, self.sin_s, 2 * H)} if fused else {}))
             if not fused:
@@ -1058,7 +1052,7 @@ class _RowGemmEps(_CachedEpsBase):
         c[:, :S_pmax].copy_. "fp8_as_bf16": the same layers per sample (B = 1, at most 1024 rows) on the dequantised weight codes and
         the quantised-and-dequantised inputs."""
         self._weights()
-        layers = self._quantised(self._packed_key, self.batch_prefill)
+        layers = self._weight_copy(W8, self.batch_prefill)
         if self.batch_prefill == "fp8":
             h = prefix.reshape(NB * S_pmax, self.H)
             for w, c in zip(layers, self.cache):
@@ -1092,17 +1086,11 @@ class _RowGemmEps(_CachedEpsBase):
         self._attn_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
 
     def _proj(self, x, weights, out=None, residual=None):
-        """x [M, K] @ W^T (+ residual): `weights` is a tuple of adjacent bf16 views (mla_gemm_suffix_bf16) or one W8 (mla_gemm_suffix_w8);
-        out = a layer's cache: the q|k|v rows go to their samples' / groups' slots."""
-        if isinstance(weights, W8):
-            N, gemm = weights.q.shape[0], functools.partial(hip.gemm_suffix_w8, x, weights.q, weights.scale)
-        elif isinstance(weights, W4):
-            N, gemm = weights.q.shape[0], functools.partial(hip.gemm_suffix_w4, x, weights.q, weights.s)
-        else:
-            wcat = ops.cat_view(weights) if len(weights) > 1 else weights[0]
-            assert wcat is not None, "the packed weights are adjacent in memory (_weights)"
-            N, gemm = wcat.shape[0], functools.partial(hip.gemm_suffix, x, wcat)
-        M = x.shape[0]
+        """x [M, K] @ W^T (+ residual): `weights` is a tuple of adjacent bf16 views or one coded weight (mla_gemm_suffix_<format>); out =
+        a layer's cache: the q|k|v rows go to their samples' / groups' slots."""
+        fmt, W = _operands(weights)
+        assert W is not None, "the packed weights are adjacent in memory (_weights)"
+        M, N, gemm = x.shape[0], W[0].shape[0], functools.partial(getattr(hip, "gemm_suffix" + fmt.suffix), x, *W)
         if out is None:
             out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
             gemm(out, out.stride(0), 0, M, residual)

@@ -20,18 +20,18 @@ import pytest
 import torch
 
 from mla_amd import hip, infer
-from test_infer_suffix_plan_host import (BF16, D, EPS, H, I, LAYERS, NHEADS, SCALE, Recorder, _check, _layer_weights, _prefix_engine, _w,
-                                         expected_prefix)
+from test_infer_suffix_plan_host import (BF16, D, EPS, H, I, LAYERS, NHEADS, SCALE, SUFFIX, Recorder, _check, _layer_weights, _prefix_engine,
+                                         _w, expected_prefix)
 
 R17 = 17
 
 
 class OperandRecorder(Recorder):
-    """The plan test's recorder plus the two wrappers of the gate|up + SwiGLU projection."""
+    """The plan test's recorder plus the three wrappers of the gate|up + SwiGLU projection."""
 
     def __init__(self, monkeypatch, **kw):
         super().__init__(monkeypatch, **kw)
-        for name in ("gemm_skinny_gateup_swiglu", "gemm_skinny_gateup_swiglu_w8"):
+        for name in ("gemm_skinny_gateup_swiglu", "gemm_skinny_gateup_swiglu_w8", "gemm_skinny_gateup_swiglu_w4"):
             monkeypatch.setattr(hip, name, self._wrap(name, getattr(hip, name), self._act))
 
     @staticmethod
@@ -44,7 +44,8 @@ def _engine17(rec, mode, packed=True, operand="once", attention="head"):
     B, S_p = 1, 12
     S_cap = S_p + R17
     e = infer.PrefixCachedEps.__new__(infer.PrefixCachedEps)
-    e.suffix_weights, e.suffix_attention, e._attn_ws, e.suffix_operand = mode, attention, None, operand
+    e.suffix_weights, e.suffix_mx = ("bf16", "fp4") if mode == "fp4" else (mode, "off")
+    e.suffix_attention, e._attn_ws, e.suffix_operand = attention, None, operand
     e.R, e.T, e.H, e.D, e.nheads, e.eps = R17, R17 - 1, H, D, NHEADS, EPS
     e.model = types.SimpleNamespace(norm=types.SimpleNamespace(weight=rec.know("norm", torch.ones(H, dtype=BF16))))
     e._suffix = e._packed = _layer_weights(rec, mode, packed)
@@ -61,7 +62,7 @@ def expected_once(mode, packed=True, attention="attn_chunk"):
     """The contract's launch list at B = 1, R = 17, S_p = 12 + the final norm."""
     B, S_p, M = 1, 12, R17
     S_cap = S_p + R17
-    kernel = "gemm_skinny_w8" if mode == "fp8" else "gemm_skinny"
+    kernel = "gemm_skinny" + SUFFIX[mode]
     fresh = lambda out, N: {"out": out, "ldo": N, "out_batch_stride": 0, "rows_per_batch": M}            # noqa: E731
     calls, h = [], "h_in"
     for l in range(LAYERS):
@@ -82,7 +83,7 @@ def expected_once(mode, packed=True, attention="attn_chunk"):
         calls.append(("rmsnorm_fwd", {"x2d": h1, "w": f"L{l}.ln2", "eps": EPS}))
         if packed:
             act = f"@{i + 3}.ret[{M}, {I}]"
-            calls.append(("gemm_skinny_gateup_swiglu_w8" if mode == "fp8" else "gemm_skinny_gateup_swiglu", {"x": xn2, **_w(l, "gu", mode)}))
+            calls.append(("gemm_skinny_gateup_swiglu" + SUFFIX[mode], {"x": xn2, **_w(l, "gu", mode)}))
         else:
             gu, act = f"@{i + 3}.out[{M}, {2 * I}]", f"@{i + 5}.ret[{M}, {I}]"
             calls += [(kernel, {"x": xn2, "W": f"L{l}.{n}", **fresh(gu, 2 * I), **({"out_col": j * I} if j else {})}) for j, n in enumerate("gu")]
@@ -94,7 +95,7 @@ def expected_once(mode, packed=True, attention="attn_chunk"):
     return calls
 
 
-@pytest.mark.parametrize("mode", ["bf16", "fp8"])
+@pytest.mark.parametrize("mode", ["bf16", "fp8", "fp4"])
 def test_once_pass_is_seven_launches_per_layer(monkeypatch, mode):
     rec = OperandRecorder(monkeypatch, gemv_fits=False, decode_fits=False)
     want = expected_once(mode)
@@ -122,7 +123,7 @@ def test_default_mode_at_17_rows_keeps_the_fused_pass(monkeypatch):
     assert rec.calls[0][1]["norm_weight"] == "L0.ln1" and rec.calls[4][1]["swiglu"] is True
 
 
-@pytest.mark.parametrize("mode,kernel", [("bf16", "gemv"), ("fp8", "gemv_w8")])
+@pytest.mark.parametrize("mode,kernel", [("bf16", "gemv"), ("fp8", "gemv_w8"), ("fp4", "gemv_w4")])
 def test_once_up_to_8_rows_is_the_fused_pass(monkeypatch, mode, kernel):
     """R = 4 (gemv_fits true): the list of "once" is the list of "fused", launch for launch."""
     rec = OperandRecorder(monkeypatch, gemv_fits=True)

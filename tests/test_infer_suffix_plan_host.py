@@ -40,7 +40,8 @@ class Recorder:
         self.calls, self.roots, self.keep = [], [], []
         for name, ret in (("rmsnorm_fwd", self._rms), ("swiglu_fwd", self._swiglu), ("rope_inplace", None),
                           ("gemv", None), ("gemm_skinny", None), ("gemv_w8", None), ("gemm_skinny_w8", None),
-                          ("gemm_suffix", None), ("gemm_suffix_w8", None),
+                          ("gemv_w4", None), ("gemm_skinny_w4", None),
+                          ("gemm_suffix", None), ("gemm_suffix_w8", None), ("gemm_suffix_w4", None),
                           ("attn_decode", self._attn), ("attn_chunk", self._attn), ("attn_chunk_split", self._attn),
                           ("attn_chunk_ragged", self._attn), ("attn_chunk_groups", self._attn_groups),
                           ("attn_chunk_ragged_groups", self._attn_ragged_groups)):
@@ -115,7 +116,8 @@ def _same(v, default):
 # ---------------------------------------------------------------------------------------------------- fake weights and engines
 def _layer_weights(rec, mode, packed=True):
     """Per layer: what _weights() / _quantised() hand a pass in `mode`, every tensor known to the recorder.
-    bf16: (ln1, wq, wk, wv, wo, ln2, wg, wu, wd) with q|k|v and gate|up adjacent (packed) or apart; fp8: (ln1, W8, W8, ln2, W8, W8)."""
+    bf16: (ln1, wq, wk, wv, wo, ln2, wg, wu, wd) with q|k|v and gate|up adjacent (packed) or apart; fp8: (ln1, W8, W8, ln2, W8, W8);
+    fp4: (ln1, W4, W4, ln2, W4, W4) -- code pairs [N, K / 2] and block scales [N, K / 32], both uint8."""
     out = []
     for l in range(LAYERS):
         ln1, ln2 = rec.know(f"L{l}.ln1", torch.ones(H, dtype=BF16)), rec.know(f"L{l}.ln2", torch.ones(H, dtype=BF16))
@@ -124,6 +126,13 @@ def _layer_weights(rec, mode, packed=True):
             for name, (N, K) in (("qkv", (3 * H, H)), ("o", (H, H)), ("gu", (2 * I, H)), ("d", (H, I))):
                 mats.append(infer.W8(rec.know(f"L{l}.{name}.q", torch.zeros((N, K), dtype=torch.float8_e4m3fn)),
                                      rec.know(f"L{l}.{name}.scale", torch.ones(N, dtype=torch.float32))))
+            out.append((ln1, mats[0], mats[1], ln2, mats[2], mats[3]))
+            continue
+        if mode == "fp4":
+            mats = []
+            for name, (N, K) in (("qkv", (3 * H, H)), ("o", (H, H)), ("gu", (2 * I, H)), ("d", (H, I))):
+                mats.append(infer.W4(rec.know(f"L{l}.{name}.q", torch.zeros((N, K // 2), dtype=torch.uint8)),
+                                     rec.know(f"L{l}.{name}.s", torch.zeros((N, K // 32), dtype=torch.uint8))))
             out.append((ln1, mats[0], mats[1], ln2, mats[2], mats[3]))
             continue
         wo, wd = rec.know(f"L{l}.o", torch.zeros((H, H), dtype=BF16)), rec.know(f"L{l}.d", torch.zeros((H, I), dtype=BF16))
@@ -140,7 +149,8 @@ def _layer_weights(rec, mode, packed=True):
 def _fake(cls, rec, mode, rows, caches, weights=None, **attrs):
     """cls.__new__ plus what a suffix pass reads. ---- the only lines that follow the engines' attributes ----"""
     e = cls.__new__(cls)
-    e.suffix_weights, e.suffix_attention, e._attn_ws = mode, "head", None
+    e.suffix_weights, e.suffix_mx = ("bf16", "fp4") if mode == "fp4" else (mode, "off")
+    e.suffix_attention, e._attn_ws = "head", None
     e.R, e.T, e.H, e.D, e.nheads, e.eps = R, R - 1, H, D, NHEADS, EPS
     e.model = types.SimpleNamespace(norm=types.SimpleNamespace(weight=rec.know("norm", torch.ones(H, dtype=BF16))))
     e._suffix = e._packed = weights if weights is not None else _layer_weights(rec, mode)
@@ -156,14 +166,19 @@ def _i32(n):
 
 
 # ---------------------------------------------------------------------------------------------------- expected lists
+SUFFIX = {"bf16": "", "fp8": "_w8", "fp4": "_w4"}                             # of the wrapper a pass over `mode` weights calls
+
+
 def _w(l, name, mode):
-    return {"W": f"L{l}.{name}.q", "w_scale": f"L{l}.{name}.scale"} if mode == "fp8" else {"W": f"L{l}.{name}"}
+    if mode == "bf16":
+        return {"W": f"L{l}.{name}"}
+    return {"W": f"L{l}.{name}.q", "w_scale": f"L{l}.{name}." + {"fp8": "scale", "fp4": "s"}[mode]}
 
 
 def expected_row_gemm(mode, M, qkv_out, attention):
     """The eight launches per layer of the row-GEMM engines + the final norm. qkv_out(l): (ldo, out_batch_stride, rows_per_batch, keywords)
     of the cache write; attention(l): (wrapper, arguments)."""
-    gemm = "gemm_suffix_w8" if mode == "fp8" else "gemm_suffix"
+    gemm = "gemm_suffix" + SUFFIX[mode]
     calls, h = [], "h_in"
     for l in range(LAYERS):
         i = len(calls)
@@ -206,7 +221,7 @@ def test_batched_prefix_engine_launches(monkeypatch):
         lambda l: ("attn_chunk_ragged", {"cache": f"cache{l}", "B": B, "nheads": NHEADS, "D": D, "kv_len": "kv_len", "R": R, "scale": SCALE})))
 
 
-@pytest.mark.parametrize("mode", ["bf16", "fp8"])
+@pytest.mark.parametrize("mode", ["bf16", "fp8", "fp4"])
 def test_sample_groups_engine_launches(monkeypatch, mode):
     rec = Recorder(monkeypatch)
     G, capacity, S_p = 2, 3, 10
@@ -221,7 +236,7 @@ def test_sample_groups_engine_launches(monkeypatch, mode):
         lambda l: ("attn_chunk_groups", {"cache": f"cache{l}", "G": G, "nheads": NHEADS, "D": D, "S_p": S_p, "R": R, "scale": SCALE})))
 
 
-@pytest.mark.parametrize("mode", ["bf16", "fp8"])
+@pytest.mark.parametrize("mode", ["bf16", "fp8", "fp4"])
 def test_batched_sample_groups_engine_launches(monkeypatch, mode):
     rec = Recorder(monkeypatch)
     NB, G, S_cap = 2, 2, 64
@@ -281,7 +296,8 @@ def expected_prefix(mode, B, S_p, kernel, attention, packed=True):
 
 
 @pytest.mark.parametrize("mode,fits,kernel", [("bf16", True, "gemv"), ("bf16", False, "gemm_skinny"),
-                                               ("fp8", True, "gemv_w8"), ("fp8", False, "gemm_skinny_w8")])
+                                               ("fp8", True, "gemv_w8"), ("fp8", False, "gemm_skinny_w8"),
+                                               ("fp4", True, "gemv_w4"), ("fp4", False, "gemm_skinny_w4")])
 def test_prefix_engine_launches_packed(monkeypatch, mode, fits, kernel):
     rec = Recorder(monkeypatch, gemv_fits=fits)
     B, S_p = 1, 12
@@ -296,11 +312,11 @@ def test_prefix_engine_launches_weights_apart(monkeypatch, fits, kernel):
     _check(rec, _prefix_engine(rec, "bf16", B, S_p, packed=False), expected_prefix("bf16", B, S_p, kernel, "attn_decode", packed=False))
 
 
-@pytest.mark.parametrize("mode", ["bf16", "fp8"])
+@pytest.mark.parametrize("mode", ["bf16", "fp8", "fp4"])
 @pytest.mark.parametrize("attention,decode_fits,wrapper", [("head", False, "attn_chunk"), ("split", True, "attn_chunk_split"),
                                                             ("split", False, "attn_chunk_split")])
 def test_prefix_engine_attention_launch(monkeypatch, mode, attention, decode_fits, wrapper):
     rec = Recorder(monkeypatch, gemv_fits=True, decode_fits=decode_fits)
     B, S_p = 1, 12
     _check(rec, _prefix_engine(rec, mode, B, S_p, attention=attention),
-           expected_prefix(mode, B, S_p, "gemv_w8" if mode == "fp8" else "gemv", wrapper))
+           expected_prefix(mode, B, S_p, "gemv" + SUFFIX[mode], wrapper))

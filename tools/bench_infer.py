@@ -212,7 +212,7 @@ def main():
     if args.pair_prefill:
         return main_pair_prefill(args)
     if args.pair_mx:
-        return main_pair_mx(args)
+        return main_pair(args, mx=True)
     if args.pair_fp8:
         return main_pair(args)
     m, b, ids = _setup(args)
@@ -246,10 +246,13 @@ def main():
 
 
 def _stream_bytes(m, mode):
-    """Bytes of decoder weights one suffix pass streams: every layer parameter in bf16, or one byte per weight in the "fp8" mode (the
-    per-row scales and the norm weights are noise next to it)."""
-    n = sum(p.numel() for l in m.vlm.llm_backbone.llm.model.layers for p in l.parameters())
-    return n * (1 if mode == "fp8" else 2)
+    """Bytes of decoder weights one suffix pass streams in `mode` (a value of suffix_weights / suffix_mx): the byte count of the model's
+    coded copy, codes and scales (it exists once a call in that mode has run), or every layer parameter in bf16 (the norm weights are
+    noise next to it)."""
+    from mla_amd.infer import CODED
+    if mode in CODED:
+        return sum(w.nbytes for layer in m.vlm.__dict__[CODED[mode].slot][mode] for w in layer if isinstance(w, CODED[mode]))
+    return 2 * sum(p.numel() for l in m.vlm.llm_backbone.llm.model.layers for p in l.parameters())
 
 
 _T95 = {2: 12.71, 3: 4.30, 4: 3.18, 5: 2.78, 6: 2.57, 7: 2.45, 8: 2.36, 9: 2.31, 10: 2.26}      # two-sided Student t, n - 1 degrees of freedom
@@ -267,105 +270,34 @@ def _pair_stats(a, b):
     return {"mean_diff": round(mean, 4), "ci95": [round(mean - h, 4), round(mean + h, 4)], "excludes_zero": bool(mean + h < 0 or mean - h > 0)}
 
 
-def main_pair(args):
+_ARMS = {"bf16": {}, "fp8": {"suffix_weights": "fp8"}, "fp4": {"suffix_mx": "fp4"}}
+
+
+def _kernel_table(m, dev, modes, Ms):
+    """The gemv and skinny projection kernels over the model's coded copies (`modes`: keys of infer.CODED) per projection shape of a 7B
+    layer and M, as the engine launches them (the fused input forms, one launch per layer's weights in a captured graph: 32 different
+    matrices, 1.6 GB in FP8, nothing stays in the caches; eager launches from Python are host-bound below ~15 us per kernel) -> us per
+    launch, the cells "gemv" / "skinny" for one mode and "gemv_w8", ... for several."""
     from mla_amd import hip
-    from mla_amd.infer import PrefixCachedEps
-    m, b, ids = _setup(args)
-    dev = ids.device
-    noise = torch.randn(1, args.chunk, 7, device=dev)
-    image, pc, state = _observation(b)
-    kw = dict(image=image, pointcloud=pc, cur_robot_state=state, input_ids=ids, num_ddim_steps=args.steps, noise=noise)
-    mk = dict(input_ids=ids, **_engine_kw(b))
-    modes = ("bf16", "fp8")
-    acts = {mode: m.predict_action_diff(suffix_weights=mode, **kw) for mode in modes}          # engines, graphs, packed + quantised weights
-    t91 = torch.tensor([91], device=dev)
-
-    def chunk_ms(mode):
-        return _time_ms(lambda: m.predict_action_diff(suffix_weights=mode, **kw), args.iters)
-
-    def pass_ms(mode):
-        with torch.inference_mode():
-            eng = PrefixCachedEps.for_inputs(m.vlm, n_action_rows=args.chunk, suffix_weights=mode, **mk)
-            eng(noise, t91)
-            return _replay_ms(eng)
-    chunk = {mode: [] for mode in modes}
-    suffix = {mode: [] for mode in modes}
-    for _ in range(args.pairs):                                             # bf16, fp8, bf16, fp8, ...: same box, interleaved
-        for mode in modes:
-            chunk[mode].append(chunk_ms(mode))
-        for mode in modes:
-            suffix[mode].append(pass_ms(mode))
-    out = {"metric": "predict_action_diff, MLA-Llama2-7B, batch 1: bf16 vs fp8 suffix weights in alternating pairs", "action_chunk": args.chunk,
-           "suffix_rows": args.chunk + 1, "ddim_steps": args.steps, "pairs": args.pairs, "unit": "ms",
-           "chunk_ms": {k: [round(v, 2) for v in vs] for k, vs in chunk.items()}, "chunk_fp8_minus_bf16": _pair_stats(chunk["bf16"], chunk["fp8"]),
-           "suffix_pass_ms": {k: [round(v, 3) for v in vs] for k, vs in suffix.items()},
-           "suffix_pass_fp8_minus_bf16": _pair_stats(suffix["bf16"], suffix["fp8"]),
-           "weights_streamed_per_pass_gb": {k: round(_stream_bytes(m, k) / 1e9, 2) for k in modes},
-           "suffix_pass_weight_stream_tbps": {k: round(_stream_bytes(m, k) / 1e12 / (min(suffix[k]) * 1e-3), 2) for k in modes},
-           "fp8_vs_bf16_chunk_rel_diff_random_weights": round(float(((acts["fp8"] - acts["bf16"]) ** 2).sum() ** 0.5 / (acts["bf16"] ** 2).sum() ** 0.5), 4),
-           "data": "synthetic"}
-    if args.kernel_table:
-        # the two _w8 kernels per projection shape of a 7B layer, cycling through the 32 layers' weights (1.6 GB: nothing stays in the caches)
-        layers = m.vlm.__dict__["_prefix_fp8"]["fp8"]
-        names = {1: "qkv(norm)", 2: "o(res)", 4: "gate_up(norm)", 5: "down(swiglu,res)"}
-        table = {}
-        for M in (2, 5, 8, 17):
-            row = {}
-            for idx, name in names.items():
-                N, K = layers[0][idx].q.shape
-                x = (torch.randn(M, 2 * K if idx == 5 else K, device=dev) * 0.5).to(torch.bfloat16)
-                res = torch.randn(M, N, device=dev).to(torch.bfloat16) if idx in (2, 5) else None
-                o = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
-                pre = {"norm_weight": layers[0][0], "eps": 1e-5} if idx in (1, 4) else ({"swiglu": True} if idx == 5 else {})
-                cell = {}
-                for kname, fn in (("gemv", hip.gemv_w8), ("skinny", hip.gemm_skinny_w8)):
-                    if kname == "gemv" and not hip.gemv_fits(M, K):
-                        continue
-                    for L in layers[:2]:                                    # function attributes, allocator
-                        fn(x, L[idx].q, L[idx].scale, o, N, 0, M, res, **pre)
-                    torch.cuda.synchronize()
-                    g = torch.cuda.CUDAGraph()                              # as the engine launches them: eager launches from Python
-                    with torch.cuda.graph(g):                               # are host-bound below ~15 us per kernel
-                        for L in layers:
-                            fn(x, L[idx].q, L[idx].scale, o, N, 0, M, res, **pre)
-                    g.replay()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(3):
-                        g.replay()
-                    e1.record()
-                    torch.cuda.synchronize()
-                    cell[kname] = round(e0.elapsed_time(e1) / (3 * len(layers)) * 1e3, 1)
-                row[name] = cell
-            table[f"M{M}"] = row
-        out["w8_kernel_us_per_launch"] = table
-    print(json.dumps(out))
-
-
-_MX_ARMS = {"bf16": {}, "fp8": {"suffix_weights": "fp8"}, "fp4": {"suffix_mx": "fp4"}}
-
-
-def _mx_kernel_table(m, dev, Ms=(2, 5, 8, 17, 33, 64)):
-    """The _w8 and _w4 projection kernels per projection shape of a 7B layer and M, as the engine launches them (the fused input forms,
-    one launch per layer's weights in a captured graph: 32 different matrices, nothing stays in the caches) -> us per launch."""
-    from mla_amd import hip
-    copies = {"w8": m.vlm.__dict__["_prefix_fp8"]["fp8"], "w4": m.vlm.__dict__["_prefix_mxfp4"]["fp4"]}
-    kernels = {"w8": (("gemv", hip.gemv_w8), ("skinny", hip.gemm_skinny_w8)), "w4": (("gemv", hip.gemv_w4), ("skinny", hip.gemm_skinny_w4))}
+    from mla_amd.infer import CODED
+    copies = {CODED[mode].fmt: m.vlm.__dict__[CODED[mode].slot][mode] for mode in modes}
+    fmt0, first = next(iter(copies.items()))
     names = {1: "qkv(norm)", 2: "o(res)", 4: "gate_up(norm)", 5: "down(swiglu,res)"}
     table = {}
     for M in Ms:
         row = {}
         for idx, name in names.items():
-            N, K = copies["w8"][0][idx].q.shape
+            N, K = first[0][idx].q.shape[0], first[0][idx].q.shape[1] * fmt0.k_per_col
             x = (torch.randn(M, 2 * K if idx == 5 else K, device=dev) * 0.5).to(torch.bfloat16)
             res = torch.randn(M, N, device=dev).to(torch.bfloat16) if idx in (2, 5) else None
             o = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
-            pre = {"norm_weight": copies["w8"][0][0], "eps": 1e-5} if idx in (1, 4) else ({"swiglu": True} if idx == 5 else {})
+            pre = {"norm_weight": first[0][0], "eps": 1e-5} if idx in (1, 4) else ({"swiglu": True} if idx == 5 else {})
             cell = {}
             for fmt, layers in copies.items():
-                for kname, fn in kernels[fmt]:
-                    if (kname == "gemv" and not hip.gemv_fits(M, K)) or (kname == "gemv" and M > 8):
+                for kname, family in (("gemv", "gemv"), ("skinny", "gemm_skinny")):
+                    if kname == "gemv" and not hip.gemv_fits(M, K):
                         continue
+                    fn = getattr(hip, family + fmt.suffix)
                     for L in layers[:2]:                                    # function attributes, allocator
                         fn(x, *L[idx], o, N, 0, M, res, **pre)
                     torch.cuda.synchronize()
@@ -380,69 +312,70 @@ def _mx_kernel_table(m, dev, Ms=(2, 5, 8, 17, 33, 64)):
                         g.replay()
                     e1.record()
                     torch.cuda.synchronize()
-                    cell[f"{kname}_{fmt}"] = round(e0.elapsed_time(e1) / (3 * len(layers)) * 1e3, 1)
+                    cell[kname if len(copies) == 1 else f"{kname}_{fmt.name}"] = round(e0.elapsed_time(e1) / (3 * len(layers)) * 1e3, 1)
             row[name] = cell
         table[f"M{M}"] = row
     return table
 
 
-def main_pair_mx(args):
-    """bf16 / fp8 / fp4 suffix weights, sampler="device", in alternating rounds in one process: chunk latency and the captured suffix pass."""
+def main_pair(args, mx=False):
+    """--pair-fp8: bf16 / fp8 suffix weights on the host sampler at --chunk. --pair-mx: bf16 / fp8 / fp4, sampler="device", over --chunks
+    and --operand. The arms alternate in rounds in one process: chunk latency and the captured suffix pass, one JSON line per case."""
+    arms = ("bf16", "fp8", "fp4") if mx else ("bf16", "fp8")
     m = None
-    for chunk in ([int(v) for v in args.chunks.split(",")] if args.chunks else [args.chunk]):
-        for operand in (["fused"] + (["once"] if chunk > 7 else []) if args.operand == "both" else [args.operand]):
+    for chunk in ([int(v) for v in args.chunks.split(",")] if mx and args.chunks else [args.chunk]):
+        for operand in ((["fused"] + (["once"] if chunk > 7 else []) if args.operand == "both" else [args.operand]) if mx else [None]):
             args.chunk = chunk
-            m = _pair_mx_case(args, m, operand, kernel_table=args.kernel_table and m is None)
+            m = _pair_case(args, m, arms, {"sampler": "device", "suffix_operand": operand} if mx else {}, args.kernel_table and m is None)
 
 
-def _pair_mx_case(args, m, operand, kernel_table):
+def _pair_case(args, m, arms, modes, kernel_table):
     from mla_amd.infer import PrefixCachedEps
     m, b, ids = _setup(args, model=m)
     dev = ids.device
+    mx = len(arms) > 2
     noise = torch.randn(1, args.chunk, 7, device=dev)
     image, pc, state = _observation(b)
-    kw = dict(image=image, pointcloud=pc, cur_robot_state=state, input_ids=ids, num_ddim_steps=args.steps, noise=noise, sampler="device",
-              suffix_operand=operand)
-    mk = dict(input_ids=ids, suffix_operand=operand, **_engine_kw(b))
-    acts = {arm: m.predict_action_diff(**extra, **kw) for arm, extra in _MX_ARMS.items()}       # engines, graphs, packed + quantised weights
+    kw = dict(image=image, pointcloud=pc, cur_robot_state=state, input_ids=ids, num_ddim_steps=args.steps, noise=noise, **modes)
+    mk = dict(input_ids=ids, **{k: v for k, v in modes.items() if k != "sampler"}, **_engine_kw(b))
+    acts = {arm: m.predict_action_diff(**_ARMS[arm], **kw) for arm in arms}                      # engines, graphs, packed + quantised weights
     t91 = torch.tensor([91], device=dev)
 
     def chunk_ms(arm):
-        return _time_ms(lambda: m.predict_action_diff(**_MX_ARMS[arm], **kw), args.iters)
+        return _time_ms(lambda: m.predict_action_diff(**_ARMS[arm], **kw), args.iters)
 
     def pass_ms(arm):
         with torch.inference_mode():
-            eng = PrefixCachedEps.for_inputs(m.vlm, n_action_rows=args.chunk, **_MX_ARMS[arm], **mk)
+            eng = PrefixCachedEps.for_inputs(m.vlm, n_action_rows=args.chunk, **_ARMS[arm], **mk)
             eng(noise, t91)
             return _replay_ms(eng)
-    chunk = {arm: [] for arm in _MX_ARMS}
-    suffix = {arm: [] for arm in _MX_ARMS}
-    for _ in range(args.pairs):                                             # bf16, fp8, fp4, bf16, ...: same box, interleaved
-        for arm in _MX_ARMS:
+    chunk = {arm: [] for arm in arms}
+    suffix = {arm: [] for arm in arms}
+    for _ in range(args.pairs):                                             # bf16, fp8[, fp4], bf16, ...: same box, interleaved
+        for arm in arms:
             chunk[arm].append(chunk_ms(arm))
-        for arm in _MX_ARMS:
+        for arm in arms:
             suffix[arm].append(pass_ms(arm))
-    n = sum(p.numel() for l in m.vlm.llm_backbone.llm.model.layers for p in l.parameters())
-    gb = {"bf16": 2 * n / 1e9, "fp8": n / 1e9, "fp4": (n / 2 + n / 32) / 1e9}
+    gb = {arm: _stream_bytes(m, arm) / 1e9 for arm in arms}
+    against = [(arm, ref) for i, ref in enumerate(arms) for arm in arms[i + 1:]]                 # fp8 - bf16[, fp4 - bf16, fp4 - fp8]
 
     def rel(a, ref):
         return round(float(((acts[a] - acts[ref]) ** 2).sum() ** 0.5 / (acts[ref] ** 2).sum() ** 0.5), 4)
-    out = {"metric": "predict_action_diff, MLA-Llama2-7B, batch 1, sampler=device: bf16 vs fp8 vs fp4 (MXFP4) suffix weights in alternating "
-                     "rounds", "action_chunk": args.chunk, "suffix_rows": args.chunk + 1, "suffix_operand": operand,
+    metric = ("predict_action_diff, MLA-Llama2-7B, batch 1, sampler=device: bf16 vs fp8 vs fp4 (MXFP4) suffix weights in alternating rounds"
+              if mx else "predict_action_diff, MLA-Llama2-7B, batch 1: bf16 vs fp8 suffix weights in alternating pairs")
+    out = {"metric": metric, "action_chunk": args.chunk, "suffix_rows": args.chunk + 1, **({"suffix_operand": modes["suffix_operand"]} if mx else {}),
            "ddim_steps": args.steps, "pairs": args.pairs, "unit": "ms",
            "chunk_ms": {k: [round(v, 2) for v in vs] for k, vs in chunk.items()},
-           "chunk_fp8_minus_bf16": _pair_stats(chunk["bf16"], chunk["fp8"]), "chunk_fp4_minus_bf16": _pair_stats(chunk["bf16"], chunk["fp4"]),
-           "chunk_fp4_minus_fp8": _pair_stats(chunk["fp8"], chunk["fp4"]),
+           **{f"chunk_{a}_minus_{ref}": _pair_stats(chunk[ref], chunk[a]) for a, ref in against},
            "suffix_pass_ms": {k: [round(v, 3) for v in vs] for k, vs in suffix.items()},
-           "suffix_pass_fp8_minus_bf16": _pair_stats(suffix["bf16"], suffix["fp8"]),
-           "suffix_pass_fp4_minus_bf16": _pair_stats(suffix["bf16"], suffix["fp4"]),
-           "suffix_pass_fp4_minus_fp8": _pair_stats(suffix["fp8"], suffix["fp4"]),
+           **{f"suffix_pass_{a}_minus_{ref}": _pair_stats(suffix[ref], suffix[a]) for a, ref in against},
            "weights_streamed_per_pass_gb": {k: round(v, 2) for k, v in gb.items()},
-           "suffix_pass_weight_stream_tbps": {k: round(gb[k] / 1e3 / (min(suffix[k]) * 1e-3), 2) for k in _MX_ARMS},
-           "chunk_rel_diff_vs_bf16_random_weights": {"fp8": rel("fp8", "bf16"), "fp4": rel("fp4", "bf16")},
+           "suffix_pass_weight_stream_tbps": {k: round(gb[k] / 1e3 / (min(suffix[k]) * 1e-3), 2) for k in arms},
+           **({"chunk_rel_diff_vs_bf16_random_weights": {a: rel(a, "bf16") for a in arms[1:]}} if mx else
+              {"fp8_vs_bf16_chunk_rel_diff_random_weights": rel("fp8", "bf16")}),
            "data": "synthetic"}
     if kernel_table:
-        out["kernel_us_per_launch"] = _mx_kernel_table(m, dev)
+        out["kernel_us_per_launch" if mx else "w8_kernel_us_per_launch"] = _kernel_table(m, dev, arms[1:], (2, 5, 8, 17, 33, 64) if mx else (2, 5, 8, 17))
     print(json.dumps(out), flush=True)
     return m
 
@@ -1298,12 +1231,11 @@ def main_batch_samples(args, batches):
         print(json.dumps({"metric": "mla_attn_chunk_ragged_groups (one launch) vs mla_attn_chunk_groups per sample (B launches), 32 heads, one "
                                     "layer cache each", "unit": "us", "table": _ragged_groups_table(dev, cases, chunk), "data": "synthetic"}),
               flush=True)
-    m, wbytes = None, None
+    m = None
     modes = ("bf16", "fp8") if args.pair_fp8 else ("bf16",)
     for B, N in cases:
         m, b, ids = _setup(chunk, B, model=m)                                 # the model once, a batch per case
         ids = list(ids)
-        wbytes = wbytes or {mode: _stream_bytes(m, mode) for mode in modes}
         images, pcs, states = (list(v) for v in zip(*(_observation(b, i) for i in range(B))))
         noise = torch.randn(B, N, chunk, 7, device=dev)
 
@@ -1334,7 +1266,7 @@ def main_batch_samples(args, batches):
                               "speedup_vs_b": round(min(ms["b_sequential_samples"]) / min(ms["a_batch_samples"]), 2),
                               "ms_per_chunk": round(min(ms["a_batch_samples"]) / (B * N), 1), "prompt_ids": [int(r.numel()) for r in ids],
                               "passes": len(engines), "engine_graph": bool(engines) and all(e.graph is not None for e in engines.values()),
-                              "weights_streamed_per_pass_gb": round(wbytes[mode] / 1e9, 2), "a_vs_b_rel_diff_random_weights": round(rel, 5),
+                              "weights_streamed_per_pass_gb": round(_stream_bytes(m, mode) / 1e9, 2), "a_vs_b_rel_diff_random_weights": round(rel, 5),
                               "data": "synthetic"}), flush=True)
             for store in ("_prefix_engines_batch_samples", "_prefix_engines_samples"):     # the caches of this (B, N, mode)
                 m.vlm.__dict__.get(store, {}).clear()
