@@ -739,19 +739,58 @@ __device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v
 // with p the NEW master, never its bf16 copy. The contraction is spelled out for adamw_elem's reason: the fused launches, the scalar
 // tail and the stand-alone pass must agree bit for bit.
 __device__ __forceinline__ float ema_elem(float e, float p, float decay, float omd) { return fmaf(omd, p, decay * e); }
+// ---- bf16 moments (opt-in, mla_adamw_m16_step): exp_avg / exp_avg_sq stored as bf16 bit patterns, rounded STOCHASTICALLY on the way
+// back -- round-to-nearest cannot hold the second moment (bf16(0.999 v) == v: it would never decay). The random bits come from a
+// counter-based generator, so they are a function of (seed, step, global element index) alone: reruns and any split of a range into
+// launches give the same bits.
+// Philox4x32-10 (Salmon et al., SC'11), the standard constants; known answers in tests/test_adamw_m16_cases_host.py.
+struct Philox4 { uint32_t w[4]; };
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0, h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return Philox4{{c0, c1, c2, c3}};
+}
+// generator state of the bf16-moment instances: key = the seed's halves, step = third counter word, base = global index of element 0
+struct Sr16Args { uint32_t k0, k1, step; long long base; };
+// the four words of the float4 group e4 (= e >> 2 of its elements): counter (lo32(e4), hi32(e4), step, 0)
+__device__ __forceinline__ Philox4 sr16_words(const Sr16Args& a, long long e4) {
+  return philox4x32_10((uint32_t)e4, (uint32_t)((unsigned long long)e4 >> 32), a.step, 0u, a.k0, a.k1);
+}
+// fp32 -> bf16 bits, rounded up with probability (dropped bits) / 2^16: add 16 random bits below the cut and truncate; a carry into
+// the exponent is the correct round-up. inf / NaN: round-to-nearest (the addition would walk a NaN's payload into another class).
+__device__ __forceinline__ uint32_t sr16(float x, uint32_t r16) {
+  const uint32_t b = __float_as_uint(x);
+  return (b & 0x7f800000u) != 0x7f800000u ? (b + r16) >> 16 : (uint32_t)f2bf(x);
+}
 // EMA = true: one more fp32 stream `ema`, read and written once per element (mla_adamw_ema_step); false: ema is never touched.
-template <bool EMA>
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, bf16_t* __restrict__ p16, long long n, float lr,
+// MT = float: fp32 moments, RNG empty -- the kernel of mla_adamw_step*, its parameter list included. MT = bf16_t with one Sr16Args: the
+// moments are decoded from / stochastically rounded to bf16, one Philox call per element; p, p16 and ema come from the unrounded moments.
+template <bool EMA, typename MT = float, typename... RNG>
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, MT* __restrict__ m,
+                                                    MT* __restrict__ v, bf16_t* __restrict__ p16, long long n, float lr,
                                                     float beta1, float beta2, float eps, float wd, float bc1, float bc2,
                                                     const float* __restrict__ grad_scale, long long n_decay, float* __restrict__ ema,
-                                                    float ema_decay, float ema_omd) {
+                                                    float ema_decay, float ema_omd, RNG... rng) {
+  constexpr bool M16 = sizeof...(RNG) != 0;
   const float gs = grad_scale ? *grad_scale : 1.f;
   const float step = lr / bc1, isq = 1.f / sqrtf(bc2);
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    float pp = p[i], mm = m[i], vv = v[i];
+    float pp = p[i], mm, vv;
+    if constexpr (M16) { mm = bf2f(m[i]); vv = bf2f(v[i]); } else { mm = m[i]; vv = v[i]; }
     adamw_elem(pp, g[i], mm, vv, gs, i < n_decay ? 1.f - lr * wd : 1.f, beta1, beta2, step, isq, eps);
-    p[i] = pp; m[i] = mm; v[i] = vv;
+    p[i] = pp;
+    if constexpr (M16) {
+      const Sr16Args a(rng...);
+      const long long e = a.base + i;
+      const uint32_t r = sr16_words(a, e >> 2).w[e & 3];
+      m[i] = (bf16_t)sr16(mm, r & 0xffffu); v[i] = (bf16_t)sr16(vv, r >> 16);
+    } else {
+      m[i] = mm; v[i] = vv;
+    }
     if (p16) p16[i] = f2bf(pp);
     if (EMA) ema[i] = ema_elem(ema[i], pp, ema_decay, ema_omd);
   }
@@ -761,23 +800,34 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 // element-wise, so the results are bit-identical to adamw_kernel; n4 = number of whole float4 groups.
 // UNR = float4 groups per lane and trip (all their loads issued before the first use); NT = non-temporal accesses; EMA as above (an
 // eighth fp32 stream under the same access policy: it too is touched exactly once per step).
-template <int UNR, bool NT, bool EMA>
-__global__ __launch_bounds__(256) void adamw_vec4_kernel(f32x4_t* __restrict__ p, const f32x4_t* __restrict__ g, f32x4_t* __restrict__ m,
-                                                         f32x4_t* __restrict__ v, u32x2_t* __restrict__ p16, long long n4, float lr,
+// MV = f32x4_t: fp32 moments, RNG empty. MV = u32x2_t with one Sr16Args (base % 4 == 0): bf16 moments, 8-B accesses on their two streams
+// like p16's, one Philox call per float4 group (its four words serve the group's four elements, as in adamw_kernel).
+template <int UNR, bool NT, bool EMA, typename MV = f32x4_t, typename... RNG>
+__global__ __launch_bounds__(256) void adamw_vec4_kernel(f32x4_t* __restrict__ p, const f32x4_t* __restrict__ g, MV* __restrict__ m,
+                                                         MV* __restrict__ v, u32x2_t* __restrict__ p16, long long n4, float lr,
                                                          float beta1, float beta2, float eps, float wd, float bc1, float bc2,
                                                          const float* __restrict__ grad_scale, long long n4_decay,
-                                                         f32x4_t* __restrict__ ema, float ema_decay, float ema_omd) {
+                                                         f32x4_t* __restrict__ ema, float ema_decay, float ema_omd, RNG... rng) {
+  constexpr bool M16 = sizeof...(RNG) != 0;
   const float gs = grad_scale ? *grad_scale : 1.f;
   const float step = lr / bc1, isq = 1.f / sqrtf(bc2), decay_on = 1.f - lr * wd;
   const long long chunk = ((((n4) + gridDim.x - 1) / gridDim.x) + 256 * UNR - 1) / (256 * UNR) * (256 * UNR);
   const long long lo = (long long)blockIdx.x * chunk, hi = lo + chunk < n4 ? lo + chunk : n4;
   for (long long i0 = lo + threadIdx.x; i0 < hi; i0 += 256 * UNR) {
     f32x4_t g4[UNR], p4[UNR], m4[UNR], v4[UNR], e4[EMA ? UNR : 1];
+    MV mw[M16 ? UNR : 1], vw[M16 ? UNR : 1];      // bf16 moments as loaded
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       const long long i = i0 + u * 256;
       if (i < hi) {
-        if (NT) {
+        if constexpr (M16) {
+          if (NT) {
+            g4[u] = __builtin_nontemporal_load(g + i); p4[u] = __builtin_nontemporal_load(p + i);
+            mw[u] = __builtin_nontemporal_load(m + i); vw[u] = __builtin_nontemporal_load(v + i);
+          } else {
+            g4[u] = g[i]; p4[u] = p[i]; mw[u] = m[i]; vw[u] = v[i];
+          }
+        } else if (NT) {
           g4[u] = __builtin_nontemporal_load(g + i); p4[u] = __builtin_nontemporal_load(p + i);
           m4[u] = __builtin_nontemporal_load(m + i); v4[u] = __builtin_nontemporal_load(v + i);
         } else {
@@ -791,6 +841,10 @@ __global__ __launch_bounds__(256) void adamw_vec4_kernel(f32x4_t* __restrict__ p
       const long long i = i0 + u * 256;
       if (i >= hi) continue;
       const float decay = i < n4_decay ? decay_on : 1.f;     // groups [0, n4_decay) are weight-decayed, the rest (norms, biases) not
+      if constexpr (M16) {
+        m4[u][0] = bflo(mw[u][0]); m4[u][1] = bfhi(mw[u][0]); m4[u][2] = bflo(mw[u][1]); m4[u][3] = bfhi(mw[u][1]);
+        v4[u][0] = bflo(vw[u][0]); v4[u][1] = bfhi(vw[u][0]); v4[u][2] = bflo(vw[u][1]); v4[u][3] = bfhi(vw[u][1]);
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float pp = p4[u][r], mm = m4[u][r], vv = v4[u][r];
@@ -798,7 +852,20 @@ __global__ __launch_bounds__(256) void adamw_vec4_kernel(f32x4_t* __restrict__ p
         p4[u][r] = pp; m4[u][r] = mm; v4[u][r] = vv;
       }
       // every stream is touched exactly once per step: non-temporal loads and stores (+3 % stand-alone, tools/bench_adamw.py)
-      if (NT) {
+      if constexpr (M16) {
+        const Sr16Args a(rng...);
+        const Philox4 r = sr16_words(a, (a.base >> 2) + i);
+        MV om, ov;
+        om[0] = sr16(m4[u][0], r.w[0] & 0xffffu) | (sr16(m4[u][1], r.w[1] & 0xffffu) << 16);
+        om[1] = sr16(m4[u][2], r.w[2] & 0xffffu) | (sr16(m4[u][3], r.w[3] & 0xffffu) << 16);
+        ov[0] = sr16(v4[u][0], r.w[0] >> 16) | (sr16(v4[u][1], r.w[1] >> 16) << 16);
+        ov[1] = sr16(v4[u][2], r.w[2] >> 16) | (sr16(v4[u][3], r.w[3] >> 16) << 16);
+        if (NT) {
+          __builtin_nontemporal_store(p4[u], p + i); __builtin_nontemporal_store(om, m + i); __builtin_nontemporal_store(ov, v + i);
+        } else {
+          p[i] = p4[u]; m[i] = om; v[i] = ov;
+        }
+      } else if (NT) {
         __builtin_nontemporal_store(p4[u], p + i); __builtin_nontemporal_store(m4[u], m + i); __builtin_nontemporal_store(v4[u], v + i);
       } else {
         p[i] = p4[u]; m[i] = m4[u]; v[i] = v4[u];
@@ -1187,6 +1254,48 @@ extern "C" int mla_adamw_ema_step_groups(float* p, const float* g, float* m, flo
                                          const float* grad_scale, float ema_decay, float ema_one_minus_decay, hipStream_t stream) {
   return adamw_impl<true>(p, g, m, v, p16, n, n_decay, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream, ema, ema_decay,
                           ema_one_minus_decay);
+}
+// mla_adamw_step_groups / mla_adamw_ema_step_groups (ema != NULL) with the two moments stored as bf16 and rounded stochastically
+// (include/mla_hip_optim.h): the same launches over the same ranges -- capped grid, chunked walk, four groups per trip, non-temporal --
+// with 8-B accesses on the moment streams; 22 B per element instead of 30 (30 instead of 38 with the average).
+template <bool EMA>
+static int adamw_m16_launch(float* p, const float* g, bf16_t* m, bf16_t* v, float* ema, void* p16, long long n, long long n_decay, float lr,
+                            float beta1, float beta2, float eps, float weight_decay, float bc1, float bc2, const float* grad_scale,
+                            float ema_decay, float ema_omd, Sr16Args sr, hipStream_t stream) {
+#define AL8(q) (((uintptr_t)(q) & 7) == 0)
+  // (neither the decay boundary nor a Philox counter may cut a 16-B group: otherwise everything goes through the scalar kernel)
+  const long long n4 = (AL16(p) && AL16(g) && AL8(m) && AL8(v) && (!EMA || AL16(ema)) && (p16 == nullptr || AL8(p16)) && (n_decay & 3) == 0 &&
+                        (sr.base & 3) == 0) ? n / 4 : 0;
+#undef AL8
+  if (n4)
+    hipLaunchKernelGGL((adamw_vec4_kernel<4, true, EMA, u32x2_t, Sr16Args>), dim3(grid_for(n4, adamw_grid_cap())), dim3(256), 0, stream,
+                       (f32x4_t*)p, (const f32x4_t*)g, (u32x2_t*)m, (u32x2_t*)v, (u32x2_t*)p16, n4, lr, beta1, beta2, eps, weight_decay, bc1, bc2,
+                       grad_scale, n_decay / 4, (f32x4_t*)ema, ema_decay, ema_omd, sr);
+  const long long done = n4 * 4;
+  if (done < n) {
+    sr.base += done;
+    hipLaunchKernelGGL((adamw_kernel<EMA, bf16_t, Sr16Args>), dim3(grid_for(n - done, 8192)), dim3(256), 0, stream, p + done, g + done,
+                       m + done, v + done, p16 ? (bf16_t*)p16 + done : (bf16_t*)nullptr, n - done, lr, beta1, beta2, eps, weight_decay, bc1, bc2,
+                       grad_scale, n_decay > done ? n_decay - done : 0, EMA ? ema + done : (float*)nullptr, ema_decay, ema_omd, sr);
+  }
+  MLA_LAUNCH_CHECK();
+}
+extern "C" int mla_adamw_m16_step(float* p, const float* g, void* m16, void* v16, float* ema, void* p16, long long n, long long n_decay,
+                                  float lr, float beta1, float beta2, float eps, float weight_decay, int step, const float* grad_scale,
+                                  float ema_decay, float ema_one_minus_decay, unsigned long long seed, long long index_base,
+                                  hipStream_t stream) {
+  MLA_CHECK_ARG(p && g && m16 && v16 && n >= 0 && step >= 1 && n_decay >= 0 && n_decay <= n && index_base >= 0,
+                "mla_adamw_m16_step: null p / g / m16 / v16, n < 0, step < 1, n_decay outside [0, n] or index_base < 0");
+  if (ema)      // (a NaN fails every comparison)
+    MLA_CHECK_ARG(ema_decay >= 0.f && ema_decay <= 1.f && ema_one_minus_decay >= 0.f && ema_one_minus_decay <= 1.f,
+                  "mla_adamw_m16_step: an ema decay factor outside [0, 1]");
+  if (n == 0) return 0;
+  const float bc1 = (float)(1.0 - pow((double)beta1, step)), bc2 = (float)(1.0 - pow((double)beta2, step));      // as adamw_impl
+  const Sr16Args sr{(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step, index_base};
+  return ema ? adamw_m16_launch<true>(p, g, (bf16_t*)m16, (bf16_t*)v16, ema, p16, n, n_decay, lr, beta1, beta2, eps, weight_decay, bc1, bc2,
+                                      grad_scale, ema_decay, ema_one_minus_decay, sr, stream)
+             : adamw_m16_launch<false>(p, g, (bf16_t*)m16, (bf16_t*)v16, nullptr, p16, n, n_decay, lr, beta1, beta2, eps, weight_decay, bc1,
+                                       bc2, grad_scale, 0.f, 0.f, sr, stream);
 }
 // ema = one_minus_decay * p + decay * ema over fp32 [n], the same arithmetic as a pass of its own: 16-byte accesses where both
 // pointers allow them, a scalar tail (or the scalar kernel for everything)

@@ -52,6 +52,12 @@ class HipLocalOps:
     def ema_update(self, ema, p32, decay):
         self.hip.ema_update(ema, p32, decay)
 
+    # adamw_groups / adamw_ema_groups (ema not None) with the moments stored as bf16 and rounded stochastically (ShardedModel
+    # moments="bf16"): the random bits of element i are a function of (seed, step, index_base + i)
+    def adamw_m16(self, p32, g32, m16, v16, ema, p16, n_decay, lr, betas, eps, wd, step, grad_scale, ema_decay, seed, index_base):
+        self.hip.adamw_m16_step(p32, g32, m16, v16, ema, p16, n_decay, lr, betas[0], betas[1], eps, wd, step, grad_scale, ema_decay, seed,
+                                index_base)
+
     def sumsq(self, x32, out1, accumulate):
         self.hip.sumsq(x32, out1, accumulate)
 
@@ -162,13 +168,18 @@ def discover_units(model: nn.Module, unit_policy: Callable[[nn.Module], bool]):
     return [x for x in out if x[2]]
 
 
+MOMENT_FORMATS = {"fp32": torch.float32, "bf16": torch.bfloat16}      # ShardedModel(moments=...): storage of exp_avg / exp_avg_sq
+
+
 def plan_sharded_layout(model: nn.Module, unit_policy: Callable[[nn.Module], bool], world: int, no_decay: Callable = default_no_decay,
-                        inplace_reduce: bool = True):
+                        inplace_reduce: bool = True, moments: str = "fp32"):
     """Per-unit layout and per-rank memory of ``ShardedModel(model, unit_policy)`` at ``world`` ranks WITHOUT allocating anything (the
     model may live on the meta device): the audit the 8-GPU run is planned with. Bytes per rank and unit:
     bf16 replica (whole unit: the all-gathered weights stay resident), fp32 gradient buffer (whole trainable region: the in-place
     reduce-scatter leaves the rank's shard inside it), fp32 master + two AdamW moments (1/world of the trainable region), fp32
-    master of the frozen region (1/world). ``inplace_reduce=False`` adds the separate fp32 gradient shard of the gloo / out-of-place path."""
+    master of the frozen region (1/world). ``inplace_reduce=False`` adds the separate fp32 gradient shard of the gloo / out-of-place path.
+    ``moments="bf16"`` halves the two moments (ShardedModel's keyword)."""
+    moment_bytes = 2 * MOMENT_FORMATS[moments].itemsize
     units = []
     for name, mod, named in discover_units(model, unit_policy):
         params, n_decay, n_train, n_total = plan_flat_layout(named, world, no_decay)
@@ -181,7 +192,7 @@ def plan_sharded_layout(model: nn.Module, unit_policy: Callable[[nn.Module], boo
         units.append(dict(name=name, is_layer=mod is not None and hasattr(mod, "self_attn"), params=params, n_decay=n_decay, n_train=n_train,
                           n_total=n_total, shard_train=shard_train, shard_frozen=shard_frozen, shard_ranges=ranges,
                           bytes_bf16_replica=2 * n_total, bytes_grad32=4 * n_train,
-                          bytes_master=4 * (shard_train + shard_frozen), bytes_moments=8 * shard_train,
+                          bytes_master=4 * (shard_train + shard_frozen), bytes_moments=moment_bytes * shard_train,
                           bytes_grad_shard=0 if (inplace_reduce or world == 1) else 4 * shard_train))
     return units
 
@@ -196,18 +207,20 @@ class _Arenas:
     ALIGN_BYTES = 2 << 20      # every slice starts on a 2 MiB boundary, like a separate allocation would: a weight matrix whose rows do
     #                            not start on 128-B lines costs the GEMMs' 1-KiB LDS-DMA reads an extra line each (measured: -3 % on the step)
 
-    def __init__(self, sizes: Dict[str, int], device, slices: int = 0):
-        dt = {"flat16": torch.bfloat16}
-        pad = {k: slices * (self.ALIGN_BYTES // (2 if k == "flat16" else 4)) for k in sizes}
+    def __init__(self, sizes: Dict[str, int], device, slices: int = 0, dtypes: Optional[Dict[str, torch.dtype]] = None):
+        """sizes in elements; dtypes: kinds that are not fp32 (the bf16 replica always is bf16; bf16 moments name theirs)."""
+        dt = dict({"flat16": torch.bfloat16}, **(dtypes or {}))
+        pad = {k: slices * (self.ALIGN_BYTES // dt.get(k, torch.float32).itemsize) for k in sizes}
         self.buf = {k: torch.zeros(max(n + pad[k], 1), dtype=dt.get(k, torch.float32), device=device) for k, n in sizes.items() if n > 0}
         self.used = {k: 0 for k in self.buf}
+        self.dtype = {k: b.dtype for k, b in self.buf.items()}
 
     def has(self, kind: str) -> bool:
         return kind in self.buf
 
     def take(self, kind: str, n: int):
         if n == 0:
-            return torch.zeros(0, dtype=torch.bfloat16 if kind == "flat16" else torch.float32, device=next(iter(self.buf.values())).device)
+            return torch.zeros(0, dtype=self.dtype[kind], device=next(iter(self.buf.values())).device)
         gran = self.ALIGN_BYTES // self.buf[kind].element_size()
         o = (self.used[kind] + gran - 1) // gran * gran
         assert o + n <= self.buf[kind].numel(), f"arena {kind}: {o} + {n} > {self.buf[kind].numel()}"
@@ -222,7 +235,7 @@ class FlatUnit:
     def __init__(self, name: str, named_params: Sequence[Tuple[str, nn.Parameter]], device, world: int, rank: int, ops,
                  no_decay: Callable[[str, nn.Parameter], bool], process_group=None, sync_from_rank0: bool = True,
                  collectives: Optional[bool] = None, inplace_reduce: bool = False, arenas: Optional["_Arenas"] = None,
-                 with_ema: bool = False):
+                 with_ema: bool = False, moment_dtype: torch.dtype = torch.float32):
         self.name, self.world, self.rank, self.ops, self.device = name, world, rank, ops, device
         # buffers come from per-kind arenas when the owner provides them (ShardedModel), else from torch one by one
         def take(kind, n, dtype):
@@ -268,8 +281,9 @@ class FlatUnit:
                 self.gshard = self.grad32[rank * self.shard_train:(rank + 1) * self.shard_train]
             else:
                 self.gshard = take("gshard", self.shard_train, torch.float32)
-            self.exp_avg = take("exp_avg", self.shard_train, torch.float32)
-            self.exp_avg_sq = take("exp_avg_sq", self.shard_train, torch.float32)
+            self.exp_avg = take("exp_avg", self.shard_train, moment_dtype)       # fp32, or bf16 (ShardedModel moments="bf16")
+            self.exp_avg_sq = take("exp_avg_sq", self.shard_train, moment_dtype)
+            assert self.exp_avg.dtype == moment_dtype and self.exp_avg_sq.dtype == moment_dtype
             if with_ema:
                 # weight average of the trainable masters (ShardedModel ema_decay): starts as a copy of this rank's master shard,
                 # padding 0 like the master's -- and (1 - d) * 0 + d * 0 keeps it 0. Units without it have no such attribute.
@@ -419,7 +433,7 @@ class FlatUnit:
     def state_bytes(self):
         n = self.flat16.numel() * 2 + (self.master_train.numel() + self.master_frozen.numel()) * 4
         if self.trainable:
-            n += self.grad32.numel() * 4 + (self.exp_avg.numel() + self.exp_avg_sq.numel()) * 4
+            n += self.grad32.numel() * 4 + (self.exp_avg.numel() + self.exp_avg_sq.numel()) * self.exp_avg.element_size()
             if hasattr(self, "ema"):
                 n += self.ema.numel() * 4
             if self.gshard is not self.grad32 and not self.inplace_reduce:
@@ -432,8 +446,15 @@ class ShardedModel:
 
     def __init__(self, model: nn.Module, unit_policy: Callable[[nn.Module], bool], device, ops=None,
                  process_group=None, no_decay: Optional[Callable[[str, nn.Parameter], bool]] = None,
-                 inplace_reduce: Optional[bool] = None, ema_decay: Optional[float] = None, ema_update_every: int = 1):
-        """ema_decay (None: off, nothing changes): keep an exponential moving average of every TRAINABLE fp32 master, sharded like
+                 inplace_reduce: Optional[bool] = None, ema_decay: Optional[float] = None, ema_update_every: int = 1,
+                 moments: str = "fp32", moments_seed: int = 0):
+        """moments ("fp32": nothing changes): "bf16" stores exp_avg / exp_avg_sq as bf16 -- half their memory, 22 instead of 30 B per
+        element through the AdamW pass -- rounded STOCHASTICALLY inside the launch (round-to-nearest cannot hold exp_avg_sq:
+        bf16(0.999 v) == v). The random bits of an element are a function of (moments_seed, step_count, unit ordinal, position in the
+        unit's flat trainable region): same world size and same seed give bit-exact reruns and resumes; at another world size the
+        moments load exactly and the run continues, but on other random bits (plan_flat_layout pads regions to 8 x world, so flat
+        positions move). No counterpart in the reference (torch.optim.AdamW keeps fp32); the masters and the EMA stay fp32.
+        ema_decay (None: off, nothing changes): keep an exponential moving average of every TRAINABLE fp32 master, sharded like
         the AdamW moments (FlatUnit.ema), advanced inside the AdamW launch of every ``ema_update_every``-th optimizer step
         (reference: update_ema, training/strategies/base_strategy_mla.py:33-41). Frozen parameters have none: theirs is their value."""
         self.model, self.device = model, device
@@ -445,6 +466,11 @@ class ShardedModel:
         # used to validate the collective plumbing on a single-GPU box
         self.coll = self.world > 1 or (os.environ.get("MLA_FORCE_COLLECTIVES") == "1" and dist.is_available() and dist.is_initialized())
         self.ops = ops if ops is not None else HipLocalOps()
+        if moments not in MOMENT_FORMATS:
+            raise ValueError(f"moments must be one of {sorted(MOMENT_FORMATS)}, got {moments!r}")
+        if moments == "bf16" and not hasattr(self.ops, "adamw_m16"):      # never a run that quietly keeps fp32 moments
+            raise TypeError(f"moments='bf16' but {type(self.ops).__name__} lacks adamw_m16")
+        self.moments, self.moments_seed = moments, int(moments_seed)
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.ema_update_every = int(ema_update_every)
         self.ema_updates = 0          # optimizer steps that advanced the average
@@ -496,7 +522,8 @@ class ShardedModel:
                     sizes["ema"] = sizes.get("ema", 0) + n_train // self.world
             if self.ema_decay is not None and "exp_avg" in kinds:
                 kinds = kinds + ["ema"]      # an eighth stream of the AdamW pass: placed like the moments, and switched with them
-            self._arenas = _Arenas({k: v for k, v in sizes.items() if k in kinds}, device, slices=2 * len(found))
+            self._arenas = _Arenas({k: v for k, v in sizes.items() if k in kinds}, device, slices=2 * len(found),
+                                   dtypes={k: MOMENT_FORMATS[self.moments] for k in ("exp_avg", "exp_avg_sq")})
         for name, mod, named in found:
             self._add_unit(name, mod, named, no_decay)
         # buffers (BatchNorm statistics, ...) just move to the device in fp32 (FSDP buffer_dtype fp32)
@@ -550,7 +577,8 @@ class ShardedModel:
         if not named:
             return
         u = FlatUnit(name, named, self.device, self.world, self.rank, self.ops, no_decay, self.pg, collectives=self.coll,
-                     inplace_reduce=self.inplace_reduce, arenas=self._arenas, with_ema=self.ema_decay is not None)
+                     inplace_reduce=self.inplace_reduce, arenas=self._arenas, with_ema=self.ema_decay is not None,
+                     moment_dtype=MOMENT_FORMATS[self.moments])
         u.module = mod
         self.units.append(u)
 
@@ -713,11 +741,27 @@ class ShardedModel:
         if ema_step:
             self.ema_updates += 1
 
-        for u in self.units:
+        for ordinal, u in enumerate(self.units):
             if not u.trainable:
                 continue
             ranges = u._shard_ranges()
-            if hasattr(self.ops, "adamw_groups") and ranges and ranges[0][0] == 0 and \
+            if self.moments == "bf16":
+                # the same ranges through the bf16-moment launch (one entry point: n_decay = n or 0 is the one-group case, ema=None
+                # the plain step). index_base = the element's position in the unit's flat trainable region, under the unit's
+                # ordinal: the random bits do not depend on how the ranks cut the region, nor on how a shard is cut into launches
+                base = (ordinal << 40) + u.rank * u.shard_train
+                ema = u.ema if ema_step else None
+                if ranges and ranges[0][0] == 0 and all(ranges[i][1] == ranges[i + 1][0] and
+                                                        ranges[i][2] + (ranges[i][1] - ranges[i][0]) == ranges[i + 1][2]
+                                                        for i in range(len(ranges) - 1)):
+                    merged = [(0, ranges[-1][1], ranges[0][2], sum(le - ls for ls, le, _, dec in ranges if dec))]
+                else:
+                    merged = [(ls, le, g0, le - ls if dec else 0) for ls, le, g0, dec in ranges]
+                for ls, le, g0, n_dec in merged:
+                    self.ops.adamw_m16(u.master_train[ls:le], u.gshard[ls:le], u.exp_avg[ls:le], u.exp_avg_sq[ls:le],
+                                       None if ema is None else ema[ls:le], u.flat16[g0:g0 + (le - ls)], n_dec, lr, betas, eps, weight_decay,
+                                       self.step_count, self._coef, self.ema_decay, self.moments_seed, base + ls)
+            elif hasattr(self.ops, "adamw_groups") and ranges and ranges[0][0] == 0 and \
                     all(ranges[i][1] == ranges[i + 1][0] and ranges[i][2] + (ranges[i][1] - ranges[i][0]) == ranges[i + 1][2]
                         for i in range(len(ranges) - 1)):
                 # the local shard is [decayed | not decayed] back to back: both parameter groups in one launch
@@ -798,14 +842,15 @@ class ShardedModel:
             return u.exp_avg, u.exp_avg_sq           # world 1 without collectives: the shard IS the region
         out = []
         for shard in (u.exp_avg, u.exp_avg_sq):
-            parts = [torch.empty(u.shard_train, dtype=torch.float32, device=self.device) for _ in range(self.world)]
+            parts = [torch.empty(u.shard_train, dtype=shard.dtype, device=self.device) for _ in range(self.world)]      # stored dtype
             dist.all_gather(parts, shard, group=self.pg)
             out.append(torch.cat(parts))
         return out[0], out[1]
 
     def iter_optimizer_state(self, to_cpu_on_rank0: bool = False):
-        """Twin of ``iter_full_state_fp32`` for AdamW's moments: yields ``(name, exp_avg, exp_avg_sq)`` as fp32 tensors in the parameter's
-        shape for every TRAINABLE parameter, one unit at a time (every rank takes part in the gathers; the peak extra device memory is
+        """Twin of ``iter_full_state_fp32`` for AdamW's moments: yields ``(name, exp_avg, exp_avg_sq)`` as tensors of the stored
+        dtype (fp32; bf16 with ``moments="bf16"``: the same bits, never a conversion) in the parameter's shape for every TRAINABLE
+        parameter, one unit at a time (every rank takes part in the gathers; the peak extra device memory is
         one unit's two moments). The 8-element padding between tensors is dropped. With ``to_cpu_on_rank0`` only rank 0 receives
         (host) tensors, the other ranks ``(name, None, None)``. The layouts differ only in where the GRADIENT shard lives (no
         collectives / separate shard / in-place reduce-scatter); the moments are 1/world shards of the trainable region in all three."""
@@ -833,11 +878,12 @@ class ShardedModel:
         shards (padding = 0) and ``step_count`` is restored. The mapping is keyed by name, not by shard, so a state written at one
         world size loads at any other. Only the pieces that intersect the rank's shard are moved, tensor by tensor: no rank ever holds
         a unit's full moments on the device. Everything is validated BEFORE the first write: a missing name, an unknown name or a
-        shape mismatch raises ValueError and leaves the optimizer state as it was."""
+        shape mismatch raises ValueError and leaves the optimizer state as it was. So does a tensor of another dtype than the
+        moments are stored in (``moments``): a state of the other format is refused, never converted in either direction."""
         want = {n: p for u in self.units if u.trainable for n, p, _ in u.params if p.requires_grad}
         missing = [n for n in want if n not in state]
         extra = [n for n in state if n not in want]
-        bad = []
+        bad, fmt, want_dtype = [], [], MOMENT_FORMATS[self.moments]
         for n, p in want.items():
             if n in state:
                 pair = state[n]
@@ -847,6 +893,13 @@ class ShardedModel:
                 for kind, t in zip(("exp_avg", "exp_avg_sq"), pair):
                     if tuple(t.shape) != tuple(p.shape):
                         bad.append(f"{n}.{kind} {tuple(t.shape)} != {tuple(p.shape)}")
+                    if t.dtype != want_dtype:
+                        fmt.append(f"{n}.{kind}")
+        if fmt and not (missing or extra or bad):
+            theirs = sorted({str(t.dtype) for pair in state.values() for t in pair})
+            raise ValueError(f"optimizer state holds {', '.join(theirs)} moments but this model stores them as {want_dtype} "
+                             f"(moments={self.moments!r}; formats: {', '.join(f'{k!r} = {v}' for k, v in MOMENT_FORMATS.items())}): "
+                             f"no conversion in either direction ({len(fmt)} tensors, first {fmt[0]})")
         if missing or extra or bad:
             raise ValueError("optimizer state does not match the model's trainable parameters: "
                              + "; ".join(f"{k}: {', '.join(v)}" for k, v in (("missing", missing), ("unexpected", extra), ("wrong shape", bad)) if v))

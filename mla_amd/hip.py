@@ -2,7 +2,8 @@
 
 The header is the one statement of every signature: the build shows it to the compiler next to each definition, and the argtypes and
 restypes set in lib() are parsed from it at import (abi.py), so a new entry point needs its definition, its declaration and its
-wrapper here -- no ctypes row.
+wrapper here -- no ctypes row. Entry points added after the first header's symbol set was pinned (tests/test_abi.py) are declared
+in its sibling include/mla_hip_optim.h, which is treated the same way.
 
 Every wrapper launches on torch's current HIP stream, never synchronises, and raises RuntimeError on a
 non-zero return code. There is deliberately NO fallback: if the shared library is missing or a kernel rejects its
@@ -34,6 +35,10 @@ GEMM_PROFILE = None
 # name -> argtypes / restype of every entry point, derived from the header's declarations (abi.py): there is no hand-written ctypes row
 _HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mla_hip.h")
 _RESTYPES, _SIGNATURES = abi.load(_HEADER_PATH)
+# the sibling header (entry points added after mla_hip.h's symbol set was pinned, see its opening comment): a second derived table.
+# _SIGNATURES, _RESTYPES and exported_symbols() keep describing mla_hip.h alone; lib() binds both.
+_OPTIM_HEADER_PATH = os.path.join(os.path.dirname(_HEADER_PATH), "mla_hip_optim.h")
+_OPTIM_RESTYPES, _OPTIM_SIGNATURES = abi.load(_OPTIM_HEADER_PATH)
 
 
 def exported_symbols():
@@ -50,10 +55,11 @@ def lib():
                 f"{_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(mla_amd has no CPU fallback)")
         L = ctypes.CDLL(_LIB_PATH)
-        for name, argt in _SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.argtypes = argt
-            fn.restype = _RESTYPES[name]
+        for sigs, rets in ((_SIGNATURES, _RESTYPES), (_OPTIM_SIGNATURES, _OPTIM_RESTYPES)):
+            for name, argt in sigs.items():
+                fn = getattr(L, name)
+                fn.argtypes = argt
+                fn.restype = rets[name]
         _lib = L
     return _lib
 
@@ -599,6 +605,28 @@ def adamw_ema_step_groups(p32, g32, m, v, ema, p16, n_decay, lr, beta1, beta2, e
     d, omd = ema_factors(ema_decay)
     call("mla_adamw_ema_step_groups", _p(p32), _p(g32), _p(m), _p(v), _p(ema), _p(p16), p32.numel(), int(n_decay), float(lr), float(beta1),
          float(beta2), float(eps), float(wd), int(step), _p(grad_scale), d, omd)
+
+
+def adamw_m16_step(p32, g32, m16, v16, ema, p16, n_decay, lr, beta1, beta2, eps, wd, step, grad_scale, ema_decay, seed, index_base):
+    """adamw_step_groups with both moments stored as bf16 and rounded stochastically (mla_adamw_m16_step, include/mla_hip_optim.h);
+    ema: the fp32 weight average advanced in the same launch, or None (ema_decay is then ignored). The random bits are a function
+    of (seed, step, index_base + i): index_base is the global index of element 0, so consecutive launches continue one stream."""
+    _req(p32, torch.float32, "adamw_m16_step p32")
+    _req(g32, torch.float32, "adamw_m16_step g32")
+    _req(m16, torch.bfloat16, "adamw_m16_step m16")
+    _req(v16, torch.bfloat16, "adamw_m16_step v16")
+    n = p32.numel()
+    assert g32.numel() == n and m16.numel() == n and v16.numel() == n and all(t.is_contiguous() for t in (p32, g32, m16, v16))
+    d, omd = 0.0, 0.0
+    if ema is not None:
+        _req(ema, torch.float32, "adamw_m16_step ema")
+        assert ema.numel() == n and ema.is_contiguous()
+        d, omd = ema_factors(ema_decay)
+    if p16 is not None:
+        _req(p16, torch.bfloat16, "adamw_m16_step p16")
+        assert p16.numel() == n and p16.is_contiguous()
+    call("mla_adamw_m16_step", _p(p32), _p(g32), _p(m16), _p(v16), _p(ema), _p(p16), n, int(n_decay), float(lr), float(beta1),
+         float(beta2), float(eps), float(wd), int(step), _p(grad_scale), d, omd, int(seed) & 0xFFFFFFFFFFFFFFFF, int(index_base))
 
 
 def ema_update(ema, p32, decay):

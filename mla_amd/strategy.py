@@ -9,6 +9,7 @@ reference's loop are out of scope; the loss dict keys are the r
 from __future__ import annotations
 
 import math
+import os
 from typing import Dict, Optional
 
 import torch
@@ -34,7 +35,7 @@ class FSDPStrategy:
                  repeated_diffusion_steps: int = 4, cast_forward_inputs: bool = True, local_ops=None,
                  mixed_precision_dtype: torch.dtype = torch.bfloat16, worker_init_fn=None, requires_cliploss: bool = False,
                  sharding_strategy: str = "full-shard", save_optimizer_state: bool = False, ema_decay: Optional[float] = None,
-                 ema_update_every: int = 1, **_):
+                 ema_update_every: int = 1, moments: Optional[str] = None, moments_seed: int = 0, **_):
         """Constructor arguments of the reference's FSDPStrategy (training/strategies/fsdp.py:47-96) -- get_train_strategy passes
         them through unchanged. `sharding_strategy` "full-shard" and "shard-grad-op" run the same schedule here: bf16 weights stay
         replicated between the optimizer step and the next use (13.5 GB of 288 GB), master weights / gradients / AdamW moments are
@@ -85,13 +86,20 @@ class FSDPStrategy:
         # here the VLM is the epsilon model, so the average covers every trainable parameter). None = off: nothing changes. Both may
         # also be set as attributes before run_setup() (get_train_strategy keeps the reference's signature).
         self.ema_decay, self.ema_update_every = ema_decay, ema_update_every
+        # opt-in: AdamW's two moments stored as bf16, rounded stochastically inside the AdamW launch (ShardedModel moments="bf16": half
+        # the moment memory, 22 instead of 30 B per element through the pass; no counterpart in the reference, torch.optim.AdamW keeps
+        # fp32; its effect on a trained policy is unmeasured). None reads MLA_MOMENTS from the environment (default "fp32": nothing
+        # changes), so that `MLA_MOMENTS=bf16 python bench.py ...` measures the step. Both may also be set as attributes before run_setup().
+        self.moments = moments if moments is not None else (os.environ.get("MLA_MOMENTS") or "fp32")
+        self.moments_seed = int(moments_seed)
 
     def run_setup(self, n_train_examples: int = 0, run_dir=None) -> None:
         """fsdp.py:176-306: shard, (checkpointing), AdamW groups (no decay on <2-D / bias), LR schedule."""
         if self.enable_gradient_checkpointing:
             self.vlm.llm_backbone.enable_gradient_checkpointing()
         self.sharded = ShardedModel(self.vlm, self.vlm.get_fsdp_wrapping_policy(), self.device, ops=self.local_ops,
-                                    ema_decay=self.ema_decay, ema_update_every=self.ema_update_every)
+                                    ema_decay=self.ema_decay, ema_update_every=self.ema_update_every, moments=self.moments,
+                                    moments_seed=self.moments_seed)
         n = math.ceil(max(n_train_examples, 1) / self.global_batch_size) * self.global_batch_size
         self.num_training_steps = self.max_steps if self.max_steps is not None else (n * self.epochs) // self.global_batch_size
         if self.lr_scheduler_type == "linear-warmup+cosine-decay":
@@ -245,7 +253,15 @@ class FSDPStrategy:
         fmt = blob.get("format") if isinstance(blob, dict) else None
         if fmt != self.OPTIMIZER_FORMAT:
             raise ValueError(f"{opt}: unknown optimizer checkpoint format {fmt!r} (this build reads {self.OPTIMIZER_FORMAT!r})")
+        # the moment format has to be the run's: a file of the other format is refused before anything is written (no conversion in
+        # either direction); the stochastic rounding continues on the FILE's seed, which is what makes the resume bit-exact
+        saved_moments = blob.get("moments", "fp32")
+        if saved_moments != self.sharded.moments:
+            raise ValueError(f"{opt} holds {saved_moments!r} AdamW moments but this run keeps {self.sharded.moments!r} moments "
+                             "(FSDPStrategy(moments=...) / MLA_MOMENTS): build the strategy with the file's format")
         self.sharded.load_optimizer_state({n: (d["exp_avg"], d["exp_avg_sq"]) for n, d in blob["state"].items()}, int(blob["step_count"]))
+        if "moments_seed" in blob:
+            self.sharded.moments_seed = self.moments_seed = int(blob["moments_seed"])
         self.step = int(blob["step"])
         self._micro = 0
         # the weight average: restored when both sides have one (the resume is then bit-exact in the average too); every other
@@ -305,7 +321,9 @@ class FSDPStrategy:
         layout -- the same module keys and entries in the same order, trainable parameters carrying their average, everything else
         (frozen parameters, buffers) what the model file carries -- so ``MLA.from_pretrained`` and the reference's loader read it
         unchanged. With ``save_optimizer`` and the average on, the optimizer file additionally holds ``"ema"`` (name -> full fp32
-        tensor), ``"ema_updates"``, ``"ema_decay"`` and ``"ema_update_every"``; without the average it is unchanged, key for key."""
+        tensor), ``"ema_updates"``, ``"ema_decay"`` and ``"ema_update_every"``; without the average it is unchanged, key for key. With
+        ``moments="bf16"`` the moments are bf16 tensors (the stored bits) and the file also holds ``"moments"`` and ``"moments_seed"``;
+        with fp32 moments both keys are absent."""
         from collections import OrderedDict
         from pathlib import Path
         assert self.sharded is not None, "save_checkpoint needs run_setup() first"
@@ -362,6 +380,8 @@ class FSDPStrategy:
             blob = {"format": self.OPTIMIZER_FORMAT, "step": int(self.step), "step_count": int(self.sharded.step_count),
                     "hyper": self._hyper(), "state": state,
                     "rng": {"world": int(self.world), "cpu": [c for c, _ in every], "device": [d for _, d in every]}}
+            if self.sharded.moments != "fp32":      # bf16 moments (saved as bf16 tensors, the stored bits) and the seed of their rounding;
+                blob["moments"], blob["moments_seed"] = self.sharded.moments, int(self.sharded.moments_seed)      # absent with fp32 moments
             if ema_on:       # what a bit-exact resume of the average needs; absent (not empty) without one
                 blob["ema"] = OrderedDict((n, e) for n, e in self.sharded.iter_ema_state(to_cpu_on_rank0=True) if e is not None)
                 blob["ema_updates"] = int(self.sharded.ema_updates)
