@@ -41,6 +41,29 @@ int mla_adamw_m16_step(float* p, const float* g, void* m16, void* v16, float* em
                        float lr, float beta1, float beta2, float eps, float weight_decay, int step, const float* grad_scale,
                        float ema_decay, float ema_one_minus_decay, unsigned long long seed, long long index_base, mla_stream_t stream);
 
+/* ---- Skip the optimizer step on a non-finite gradient norm (opt-in; no counterpart in the reference: clip_grad_norm_ with
+ * error_if_nonfinite=False followed by torch.optim.AdamW lets the NaN through) ----
+ * mla_clip_coef plus a device-side verdict. Finite sumsq[0]: coef[0] and norm_out[0] are bit for bit what mla_clip_coef writes and
+ * skip[0] = 0. sumsq[0] = +inf or NaN (exponent bits all ones; a finite gradient whose sum of squares overflows fp32 counts too):
+ * skip[0] = 1, coef[0] = 0, norm_out[0] = sqrt(sumsq[0]), the non-finite norm itself, for the log. norm_out may be NULL.
+ * One thread, ordinary stores. Returns -1 (nothing launched) for a null sumsq, coef or skip. */
+int mla_clip_coef_guard(const float* sumsq, float max_norm, float* coef, float* norm_out, int* skip, mla_stream_t stream);
+
+/* Every form of the AdamW pass behind the verdict above: moments_bf16 = 0: m, v fp32 [n] (mla_adamw_step_groups, or
+ * mla_adamw_ema_step_groups with ema != NULL; seed and index_base are unused); moments_bf16 = 1: m, v bf16 [n]
+ * (mla_adamw_m16_step). ema: fp32 [n] or NULL; p16: bf16 [n] or NULL; elements [0, n_decay) are weight-decayed.
+ * skip: one int on the device, read ONCE by every workgroup before anything else (a wave-uniform load). skip[0] != 0: the launch
+ * returns without reading or writing p, g, m, v, ema, p16 or grad_scale -- the step did not happen. skip[0] == 0: every output is
+ * bit for bit that of the entry point named above for the same arguments (the guarded kernels are further instances of the same
+ * two templates; 16-byte or scalar kernel by the same alignment / n_decay / index_base rules, the n % 4 tail through the scalar one).
+ * Bias corrections are formed in double on the host. Returns -1 (nothing launched) for what mla_adamw_m16_step refuses (null p / g
+ * / m / v, n < 0, step < 1, n_decay outside [0, n], index_base < 0, with ema a factor outside [0, 1] or NaN), a null skip, or
+ * moments_bf16 outside {0, 1}. n == 0 is a valid no-op. */
+int mla_adamw_guard_step(float* p, const float* g, void* m, void* v, float* ema, void* p16, long long n, long long n_decay, float lr,
+                         float beta1, float beta2, float eps, float weight_decay, int step, const float* grad_scale, float ema_decay,
+                         float ema_one_minus_decay, int moments_bf16, unsigned long long seed, long long index_base, const int* skip,
+                         mla_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,6 +2,7 @@
 // accumulates in fp32 and makes exactly one pass over its inputs (DESIGN.md "HBM-bound kernels").
 #include "common.h"
 #include <math.h>
+#include <type_traits>
 
 namespace {
 
@@ -766,16 +767,24 @@ __device__ __forceinline__ uint32_t sr16(float x, uint32_t r16) {
   const uint32_t b = __float_as_uint(x);
   return (b & 0x7f800000u) != 0x7f800000u ? (b + r16) >> 16 : (uint32_t)f2bf(x);
 }
+// the one trailing argument of a GUARD instance of the two AdamW kernels (below): the device flag of mla_clip_coef_guard, alone
+// (fp32 moments) or behind the generator state (bf16 moments: the instance copies its Sr16Args part exactly as the unguarded one does)
+struct GuardArgs { const int* skip; };
+struct Sr16GuardArgs : Sr16Args { const int* skip; };
 // EMA = true: one more fp32 stream `ema`, read and written once per element (mla_adamw_ema_step); false: ema is never touched.
 // MT = float: fp32 moments, RNG empty -- the kernel of mla_adamw_step*, its parameter list included. MT = bf16_t with one Sr16Args: the
 // moments are decoded from / stochastically rounded to bf16, one Philox call per element; p, p16 and ema come from the unrounded moments.
-template <bool EMA, typename MT = float, typename... RNG>
+// GUARD (mla_adamw_guard_step): the trailing argument is a GuardArgs / Sr16GuardArgs. Its flag is read once, through a kernel argument
+// (the same address in every lane: a scalar load), before anything else; non-zero = the step is skipped and the launch touches no
+// stream, grad_scale included. With the flag 0 the instance computes what its GUARD = false twin computes.
+template <bool EMA, typename MT = float, bool GUARD = false, typename... RNG>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, MT* __restrict__ m,
                                                     MT* __restrict__ v, bf16_t* __restrict__ p16, long long n, float lr,
                                                     float beta1, float beta2, float eps, float wd, float bc1, float bc2,
                                                     const float* __restrict__ grad_scale, long long n_decay, float* __restrict__ ema,
                                                     float ema_decay, float ema_omd, RNG... rng) {
-  constexpr bool M16 = sizeof...(RNG) != 0;
+  constexpr bool M16 = (std::is_base_of<Sr16Args, RNG>::value || ... || false);
+  if constexpr (GUARD) { if ((*rng.skip, ...) != 0) return; }
   const float gs = grad_scale ? *grad_scale : 1.f;
   const float step = lr / bc1, isq = 1.f / sqrtf(bc2);
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
@@ -801,14 +810,15 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 // UNR = float4 groups per lane and trip (all their loads issued before the first use); NT = non-temporal accesses; EMA as above (an
 // eighth fp32 stream under the same access policy: it too is touched exactly once per step).
 // MV = f32x4_t: fp32 moments, RNG empty. MV = u32x2_t with one Sr16Args (base % 4 == 0): bf16 moments, 8-B accesses on their two streams
-// like p16's, one Philox call per float4 group (its four words serve the group's four elements, as in adamw_kernel).
-template <int UNR, bool NT, bool EMA, typename MV = f32x4_t, typename... RNG>
+// like p16's, one Philox call per float4 group (its four words serve the group's four elements, as in adamw_kernel). GUARD as there.
+template <int UNR, bool NT, bool EMA, typename MV = f32x4_t, bool GUARD = false, typename... RNG>
 __global__ __launch_bounds__(256) void adamw_vec4_kernel(f32x4_t* __restrict__ p, const f32x4_t* __restrict__ g, MV* __restrict__ m,
                                                          MV* __restrict__ v, u32x2_t* __restrict__ p16, long long n4, float lr,
                                                          float beta1, float beta2, float eps, float wd, float bc1, float bc2,
                                                          const float* __restrict__ grad_scale, long long n4_decay,
                                                          f32x4_t* __restrict__ ema, float ema_decay, float ema_omd, RNG... rng) {
-  constexpr bool M16 = sizeof...(RNG) != 0;
+  constexpr bool M16 = (std::is_base_of<Sr16Args, RNG>::value || ... || false);
+  if constexpr (GUARD) { if ((*rng.skip, ...) != 0) return; }
   const float gs = grad_scale ? *grad_scale : 1.f;
   const float step = lr / bc1, isq = 1.f / sqrtf(bc2), decay_on = 1.f - lr * wd;
   const long long chunk = ((((n4) + gridDim.x - 1) / gridDim.x) + 256 * UNR - 1) / (256 * UNR) * (256 * UNR);
@@ -958,6 +968,18 @@ __global__ void clip_coef_kernel(const float* __restrict__ sumsq, float max_norm
   const float c = max_norm / (nrm + 1e-6f);
   coef[0] = c < 1.f ? c : 1.f;
   if (norm_out) norm_out[0] = nrm;
+}
+// clip_coef_kernel with a verdict for mla_adamw_guard_step: a finite sumsq[0] gives the same coef / norm_out and skip[0] = 0; +inf or
+// NaN (exponent bits all ones) gives skip[0] = 1, coef[0] = 0 and the non-finite norm in norm_out. One thread, ordinary stores.
+__global__ void clip_coef_guard_kernel(const float* __restrict__ sumsq, float max_norm, float* __restrict__ coef,
+                                       float* __restrict__ norm_out, int* __restrict__ skip) {
+  const float ss = sumsq[0];
+  const bool bad = (__float_as_uint(ss) & 0x7f800000u) == 0x7f800000u;
+  const float nrm = sqrtf(ss);
+  const float c = max_norm / (nrm + 1e-6f);
+  coef[0] = bad ? 0.f : (c < 1.f ? c : 1.f);
+  if (norm_out) norm_out[0] = nrm;
+  skip[0] = bad ? 1 : 0;
 }
 
 // x_t = sqrt_ac[t]*x0 + sqrt_1mac[t]*noise   (GaussianDiffusion.q_sample, models/diffusion/gaussian_diffusion.py:214-229)
@@ -1191,10 +1213,12 @@ static int adamw_grid_cap() {
   return cap;
 }
 // EMA = true: the launches carry the weight average `ema` (mla_adamw_ema_step*); false: the plain launches, ema unused.
-template <bool EMA>
+// guard: empty, or the one GuardArgs of mla_adamw_guard_step -- then the GUARD instances of the same kernels run, the flag last.
+template <bool EMA, typename... G>
 static int adamw_impl(float* p, const float* g, float* m, float* v, void* p16, long long n, long long n_decay, float lr, float beta1,
                       float beta2, float eps, float weight_decay, int step, const float* grad_scale, hipStream_t stream,
-                      float* ema = nullptr, float ema_decay = 0.f, float ema_omd = 0.f) {
+                      float* ema, float ema_decay, float ema_omd, G... guard) {
+  constexpr bool GUARD = sizeof...(G) != 0;
   MLA_CHECK_ARG(p && g && m && v && n >= 0 && step >= 1 && n_decay >= 0 && n_decay <= n, "mla_adamw_step: bad args");
   if (EMA)
     MLA_CHECK_ARG(ema && ema_decay >= 0.f && ema_decay <= 1.f && ema_omd >= 0.f && ema_omd <= 1.f,
@@ -1208,9 +1232,9 @@ static int adamw_impl(float* p, const float* g, float* m, float* v, void* p16, l
   if (n4) {
     static const int variant = getenv("MLA_ADAMW_VARIANT") ? atoi(getenv("MLA_ADAMW_VARIANT")) : 0;   // A/B only (tools/bench_adamw.py)
     const dim3 grid(grid_for(n4, adamw_grid_cap()));
-#define ADAMW_LAUNCH(U, N) hipLaunchKernelGGL((adamw_vec4_kernel<U, N, EMA>), grid, dim3(256), 0, stream, (f32x4_t*)p, (const f32x4_t*)g, (f32x4_t*)m, \
-                       (f32x4_t*)v, (u32x2_t*)p16, n4, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, n_decay / 4,                    \
-                       (f32x4_t*)ema, ema_decay, ema_omd)
+#define ADAMW_LAUNCH(U, N) hipLaunchKernelGGL((adamw_vec4_kernel<U, N, EMA, f32x4_t, GUARD, G...>), grid, dim3(256), 0, stream, (f32x4_t*)p,     \
+                       (const f32x4_t*)g, (f32x4_t*)m, (f32x4_t*)v, (u32x2_t*)p16, n4, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, \
+                       n_decay / 4, (f32x4_t*)ema, ema_decay, ema_omd, guard...)
     // default: four float4 groups per lane and trip, non-temporal (stand-alone 6.20-6.29 TB/s vs 5.99-6.15 with one group, same box,
     // alternating; plain accesses 5.9-6.0) -- tools/ab_adamw.sh
     if (variant == 1) ADAMW_LAUNCH(2, true);
@@ -1222,15 +1246,15 @@ static int adamw_impl(float* p, const float* g, float* m, float* v, void* p16, l
   }
   const long long done = n4 * 4;
   if (done < n)
-    hipLaunchKernelGGL(adamw_kernel<EMA>, dim3(grid_for(n - done, 8192)), dim3(256), 0, stream, p + done, g + done, m + done, v + done,
-                       p16 ? (bf16_t*)p16 + done : (bf16_t*)nullptr, n - done, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale,
-                       n_decay > done ? n_decay - done : 0, EMA ? ema + done : (float*)nullptr, ema_decay, ema_omd);
+    hipLaunchKernelGGL((adamw_kernel<EMA, float, GUARD, G...>), dim3(grid_for(n - done, 8192)), dim3(256), 0, stream, p + done, g + done,
+                       m + done, v + done, p16 ? (bf16_t*)p16 + done : (bf16_t*)nullptr, n - done, lr, beta1, beta2, eps, weight_decay, bc1, bc2,
+                       grad_scale, n_decay > done ? n_decay - done : 0, EMA ? ema + done : (float*)nullptr, ema_decay, ema_omd, guard...);
   MLA_LAUNCH_CHECK();
 }
 extern "C" int mla_adamw_step(float* p, const float* g, float* m, float* v, void* p16, long long n, float lr, float beta1,
                               float beta2, float eps, float weight_decay, int step, const float* grad_scale,
                               hipStream_t stream) {
-  return adamw_impl<false>(p, g, m, v, p16, n, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream);
+  return adamw_impl<false>(p, g, m, v, p16, n, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream, nullptr, 0.f, 0.f);
 }
 // One launch for a flat parameter range laid out [weight-decayed | not decayed] (FlatUnit: matrices first, then norm weights and
 // biases): elements [0, n_decay) get `weight_decay`, the rest none -- the reference's two AdamW parameter groups
@@ -1238,7 +1262,7 @@ extern "C" int mla_adamw_step(float* p, const float* g, float* m, float* v, void
 extern "C" int mla_adamw_step_groups(float* p, const float* g, float* m, float* v, void* p16, long long n, long long n_decay, float lr,
                                      float beta1, float beta2, float eps, float weight_decay, int step, const float* grad_scale,
                                      hipStream_t stream) {
-  return adamw_impl<false>(p, g, m, v, p16, n, n_decay, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream);
+  return adamw_impl<false>(p, g, m, v, p16, n, n_decay, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream, nullptr, 0.f, 0.f);
 }
 // The two entry points above with the weight average folded in: after the update, ema = ema_one_minus_decay * p_new + ema_decay * ema on
 // the fp32 master (8 B per parameter on top of the step's 30, instead of the 12 B of a pass of its own). ema: fp32 [n]; it joins the
@@ -1258,23 +1282,24 @@ extern "C" int mla_adamw_ema_step_groups(float* p, const float* g, float* m, flo
 // mla_adamw_step_groups / mla_adamw_ema_step_groups (ema != NULL) with the two moments stored as bf16 and rounded stochastically
 // (include/mla_hip_optim.h): the same launches over the same ranges -- capped grid, chunked walk, four groups per trip, non-temporal --
 // with 8-B accesses on the moment streams; 22 B per element instead of 30 (30 instead of 38 with the average).
-template <bool EMA>
+template <bool EMA, typename SR>      // SR = Sr16Args, or Sr16GuardArgs (mla_adamw_guard_step): then the GUARD instances run
 static int adamw_m16_launch(float* p, const float* g, bf16_t* m, bf16_t* v, float* ema, void* p16, long long n, long long n_decay, float lr,
                             float beta1, float beta2, float eps, float weight_decay, float bc1, float bc2, const float* grad_scale,
-                            float ema_decay, float ema_omd, Sr16Args sr, hipStream_t stream) {
+                            float ema_decay, float ema_omd, SR sr, hipStream_t stream) {
+  constexpr bool GUARD = !std::is_same<SR, Sr16Args>::value;
 #define AL8(q) (((uintptr_t)(q) & 7) == 0)
   // (neither the decay boundary nor a Philox counter may cut a 16-B group: otherwise everything goes through the scalar kernel)
   const long long n4 = (AL16(p) && AL16(g) && AL8(m) && AL8(v) && (!EMA || AL16(ema)) && (p16 == nullptr || AL8(p16)) && (n_decay & 3) == 0 &&
                         (sr.base & 3) == 0) ? n / 4 : 0;
 #undef AL8
   if (n4)
-    hipLaunchKernelGGL((adamw_vec4_kernel<4, true, EMA, u32x2_t, Sr16Args>), dim3(grid_for(n4, adamw_grid_cap())), dim3(256), 0, stream,
+    hipLaunchKernelGGL((adamw_vec4_kernel<4, true, EMA, u32x2_t, GUARD, SR>), dim3(grid_for(n4, adamw_grid_cap())), dim3(256), 0, stream,
                        (f32x4_t*)p, (const f32x4_t*)g, (u32x2_t*)m, (u32x2_t*)v, (u32x2_t*)p16, n4, lr, beta1, beta2, eps, weight_decay, bc1, bc2,
                        grad_scale, n_decay / 4, (f32x4_t*)ema, ema_decay, ema_omd, sr);
   const long long done = n4 * 4;
   if (done < n) {
     sr.base += done;
-    hipLaunchKernelGGL((adamw_kernel<EMA, bf16_t, Sr16Args>), dim3(grid_for(n - done, 8192)), dim3(256), 0, stream, p + done, g + done,
+    hipLaunchKernelGGL((adamw_kernel<EMA, bf16_t, GUARD, SR>), dim3(grid_for(n - done, 8192)), dim3(256), 0, stream, p + done, g + done,
                        m + done, v + done, p16 ? (bf16_t*)p16 + done : (bf16_t*)nullptr, n - done, lr, beta1, beta2, eps, weight_decay, bc1, bc2,
                        grad_scale, n_decay > done ? n_decay - done : 0, EMA ? ema + done : (float*)nullptr, ema_decay, ema_omd, sr);
   }
@@ -1296,6 +1321,32 @@ extern "C" int mla_adamw_m16_step(float* p, const float* g, void* m16, void* v16
                                       grad_scale, ema_decay, ema_one_minus_decay, sr, stream)
              : adamw_m16_launch<false>(p, g, (bf16_t*)m16, (bf16_t*)v16, nullptr, p16, n, n_decay, lr, beta1, beta2, eps, weight_decay, bc1,
                                        bc2, grad_scale, 0.f, 0.f, sr, stream);
+}
+// Every form of the pass behind the device flag of mla_clip_coef_guard (include/mla_hip_optim.h): the launches of adamw_impl (fp32
+// moments) or adamw_m16_launch (bf16), chosen by the same rules, with the GUARD instances of the two kernels. A set flag makes every
+// workgroup return at once; a clear one leaves the bits of the unguarded entry points.
+extern "C" int mla_adamw_guard_step(float* p, const float* g, void* m, void* v, float* ema, void* p16, long long n, long long n_decay,
+                                    float lr, float beta1, float beta2, float eps, float weight_decay, int step, const float* grad_scale,
+                                    float ema_decay, float ema_one_minus_decay, int moments_bf16, unsigned long long seed,
+                                    long long index_base, const int* skip, hipStream_t stream) {
+  MLA_CHECK_ARG(p && g && m && v && n >= 0 && step >= 1 && n_decay >= 0 && n_decay <= n && index_base >= 0,
+                "mla_adamw_guard_step: null p / g / m / v, n < 0, step < 1, n_decay outside [0, n] or index_base < 0");
+  MLA_CHECK_ARG(skip && (moments_bf16 == 0 || moments_bf16 == 1), "mla_adamw_guard_step: null skip, or moments_bf16 outside {0, 1}");
+  if (ema)      // (a NaN fails every comparison)
+    MLA_CHECK_ARG(ema_decay >= 0.f && ema_decay <= 1.f && ema_one_minus_decay >= 0.f && ema_one_minus_decay <= 1.f,
+                  "mla_adamw_guard_step: an ema decay factor outside [0, 1]");
+  if (n == 0) return 0;
+  if (!moments_bf16)
+    return ema ? adamw_impl<true>(p, g, (float*)m, (float*)v, p16, n, n_decay, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream,
+                                  ema, ema_decay, ema_one_minus_decay, GuardArgs{skip})
+               : adamw_impl<false>(p, g, (float*)m, (float*)v, p16, n, n_decay, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream,
+                                   nullptr, 0.f, 0.f, GuardArgs{skip});
+  const float bc1 = (float)(1.0 - pow((double)beta1, step)), bc2 = (float)(1.0 - pow((double)beta2, step));      // as adamw_impl
+  const Sr16GuardArgs sr{{(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step, index_base}, skip};
+  return ema ? adamw_m16_launch<true>(p, g, (bf16_t*)m, (bf16_t*)v, ema, p16, n, n_decay, lr, beta1, beta2, eps, weight_decay, bc1, bc2,
+                                      grad_scale, ema_decay, ema_one_minus_decay, sr, stream)
+             : adamw_m16_launch<false>(p, g, (bf16_t*)m, (bf16_t*)v, nullptr, p16, n, n_decay, lr, beta1, beta2, eps, weight_decay, bc1, bc2,
+                                       grad_scale, 0.f, 0.f, sr, stream);
 }
 // ema = one_minus_decay * p + decay * ema over fp32 [n], the same arithmetic as a pass of its own: 16-byte accesses where both
 // pointers allow them, a scalar tail (or the scalar kernel for everything)
@@ -1333,6 +1384,11 @@ extern "C" int mla_sum_partials(const float* partial, int n, float* out, int acc
 extern "C" int mla_clip_coef(const float* sumsq, float max_norm, float* coef, float* norm_out, hipStream_t stream) {
   MLA_CHECK_ARG(sumsq && coef, "mla_clip_coef: bad args");
   hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(1), 0, stream, sumsq, max_norm, coef, norm_out);
+  MLA_LAUNCH_CHECK();
+}
+extern "C" int mla_clip_coef_guard(const float* sumsq, float max_norm, float* coef, float* norm_out, int* skip, hipStream_t stream) {
+  MLA_CHECK_ARG(sumsq && coef && skip, "mla_clip_coef_guard: null sumsq, coef or skip");
+  hipLaunchKernelGGL(clip_coef_guard_kernel, dim3(1), dim3(1), 0, stream, sumsq, max_norm, coef, norm_out, skip);
   MLA_LAUNCH_CHECK();
 }
 

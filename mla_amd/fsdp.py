@@ -58,6 +58,16 @@ class HipLocalOps:
         self.hip.adamw_m16_step(p32, g32, m16, v16, ema, p16, n_decay, lr, betas[0], betas[1], eps, wd, step, grad_scale, ema_decay, seed,
                                 index_base)
 
+    # skip_nonfinite (ShardedModel): clip_coef that also writes the one-int device flag skip1 (1 = the norm is not finite), and every
+    # form of the AdamW launch above behind that flag -- m, v fp32 (seed / index_base unused) or bf16, ema or None -- which touches
+    # nothing when the flag is set and writes the bits of the unguarded launch when it is not
+    def clip_coef_guard(self, sumsq1, max_norm, coef1, norm1, skip1):
+        self.hip.clip_coef_guard(sumsq1, max_norm, coef1, norm1, skip1)
+
+    def adamw_guard(self, p32, g32, m, v, ema, p16, n_decay, lr, betas, eps, wd, step, grad_scale, ema_decay, seed, index_base, skip1):
+        self.hip.adamw_guard_step(p32, g32, m, v, ema, p16, n_decay, lr, betas[0], betas[1], eps, wd, step, grad_scale, ema_decay, seed,
+                                  index_base, skip1)
+
     def sumsq(self, x32, out1, accumulate):
         self.hip.sumsq(x32, out1, accumulate)
 
@@ -447,8 +457,17 @@ class ShardedModel:
     def __init__(self, model: nn.Module, unit_policy: Callable[[nn.Module], bool], device, ops=None,
                  process_group=None, no_decay: Optional[Callable[[str, nn.Parameter], bool]] = None,
                  inplace_reduce: Optional[bool] = None, ema_decay: Optional[float] = None, ema_update_every: int = 1,
-                 moments: str = "fp32", moments_seed: int = 0):
-        """moments ("fp32": nothing changes): "bf16" stores exp_avg / exp_avg_sq as bf16 -- half their memory, 22 instead of 30 B per
+                 moments: str = "fp32", moments_seed: int = 0, skip_nonfinite: bool = False, max_consecutive_skips: int = 16):
+        """skip_nonfinite (False: nothing changes): when the global gradient norm of a step is +inf or NaN, that optimizer step does
+        nothing -- on every rank, for every unit -- and the run goes on as if the batch had never been seen. The verdict is a device
+        flag written by the clip-coefficient launch (after the all-reduce of the sum of squares, so every rank sees the same one)
+        and read by every AdamW launch: no host round trip. ``step_count`` and ``ema_updates`` count APPLIED steps; the host learns a
+        step's flag one step late (an asynchronous copy to pinned memory, resolved before the next step's launches are formed and
+        by every read of the counters or of ``skipped_steps``), so it never waits for work of the current step. After
+        ``max_consecutive_skips`` skipped steps in a row the resolution raises: weights that are themselves non-finite must not skip
+        for ever. Not covered: buffers updated in the forward (BatchNorm statistics) are not rolled back; a finite gradient whose
+        sum of squares overflows fp32 counts as non-finite. No counterpart in the reference.
+        moments ("fp32": nothing changes): "bf16" stores exp_avg / exp_avg_sq as bf16 -- half their memory, 22 instead of 30 B per
         element through the AdamW pass -- rounded STOCHASTICALLY inside the launch (round-to-nearest cannot hold exp_avg_sq:
         bf16(0.999 v) == v). The random bits of an element are a function of (moments_seed, step_count, unit ordinal, position in the
         unit's flat trainable region): same world size and same seed give bit-exact reruns and resumes; at another world size the
@@ -471,9 +490,16 @@ class ShardedModel:
         if moments == "bf16" and not hasattr(self.ops, "adamw_m16"):      # never a run that quietly keeps fp32 moments
             raise TypeError(f"moments='bf16' but {type(self.ops).__name__} lacks adamw_m16")
         self.moments, self.moments_seed = moments, int(moments_seed)
+        self.skip_nonfinite, self.max_consecutive_skips = bool(skip_nonfinite), int(max_consecutive_skips)
+        if self.skip_nonfinite:
+            lacking = [m for m in ("clip_coef_guard", "adamw_guard") if not hasattr(self.ops, m)]
+            if lacking:      # never a run that is quietly unguarded
+                raise TypeError(f"skip_nonfinite is set but {type(self.ops).__name__} lacks {', '.join(lacking)}")
+            if self.max_consecutive_skips < 1:
+                raise ValueError(f"max_consecutive_skips must be >= 1, got {max_consecutive_skips}")
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.ema_update_every = int(ema_update_every)
-        self.ema_updates = 0          # optimizer steps that advanced the average
+        self._ema_updates = 0         # optimizer steps that advanced the average (property ema_updates)
         self._ema_swapped = False     # inside ema_weights()
         if self.ema_decay is not None:
             if not 0.0 <= self.ema_decay <= 1.0:
@@ -529,7 +555,7 @@ class ShardedModel:
         # buffers (BatchNorm statistics, ...) just move to the device in fp32 (FSDP buffer_dtype fp32)
         for b in model.buffers():
             b.data = b.data.to(device)
-        self.step_count = 0
+        self._step_count = 0          # applied optimizer steps (property step_count)
         self.defer_reduce = False     # gradient accumulation: micro-batches before the last one only add into main_grad
         self._sumsq = torch.zeros(1, dtype=torch.float32, device=device)
         # arena of the wgrad epilogues' sum-of-squares partials (FlatUnit._sq_sink): ~1.4 K floats per decoder-layer GEMM at 7B
@@ -540,6 +566,18 @@ class ShardedModel:
         self._coef = torch.ones(1, dtype=torch.float32, device=device)
         self._norm = torch.zeros(1, dtype=torch.float32, device=device)
         self.on_gpu = self.device.type == "cuda"
+        # ---- skip_nonfinite bookkeeping (all None / 0 and never touched with the guard off)
+        self._skipped_steps = 0       # steps whose flag was set (property skipped_steps)
+        self._consecutive_skips = 0
+        self._norm_fresh = False      # grad_norm_and_clip ran since the last optimizer_step
+        self._skip_pending = None     # (event or None, that step advanced the average) of the last step, until its flag is resolved
+        self._skip_copied = None      # event behind the flag's copy to the host, between grad_norm_and_clip and optimizer_step
+        self._skip = self._skip_host = None
+        if self.skip_nonfinite:
+            self._skip = torch.zeros(1, dtype=torch.int32, device=device)
+            if self.on_gpu:      # [flag, bits of the norm]: where the device's verdict lands, one step late, without a synchronisation
+                self._skip_host = torch.zeros(2, dtype=torch.int32).pin_memory()
+                self._skip_stage = torch.zeros(2, dtype=torch.int32, device=device)
         if self.on_gpu:
             # every launch of libmla_hip.so goes to the CURRENT device's current stream (hip._stream): the owner of this object
             # must have made `device` current (FSDPStrategy.__init__ does), otherwise kernels would run on another device's stream
@@ -572,6 +610,67 @@ class ShardedModel:
             mod = getattr(u, "module", None)
             if mod is not None and hasattr(mod, "_grad_hook") and u.trainable and self.coll:
                 mod._grad_hook = (lambda uu=u: self._launch_reduce_scatter(uu))
+
+    # ------------------------------------------------------------------------------------------ applied-step counters
+    # Plain integers with the guard off. With skip_nonfinite the last step was counted when it was launched, before the host could
+    # know its flag; every read (and write) first settles that.
+    @property
+    def step_count(self) -> int:
+        """AdamW's bias-correction step and the Philox step of bf16 moments: optimizer steps that were APPLIED."""
+        self._resolve_skip()
+        return self._step_count
+
+    @step_count.setter
+    def step_count(self, value: int) -> None:
+        self._resolve_skip()
+        self._step_count = int(value)
+
+    @property
+    def ema_updates(self) -> int:
+        self._resolve_skip()
+        return self._ema_updates
+
+    @ema_updates.setter
+    def ema_updates(self, value: int) -> None:
+        self._resolve_skip()
+        self._ema_updates = int(value)
+
+    @property
+    def skipped_steps(self) -> int:
+        """Optimizer steps that did nothing because their gradient norm was not finite (skip_nonfinite); 0 without the guard."""
+        self._resolve_skip()
+        return self._skipped_steps
+
+    @skipped_steps.setter
+    def skipped_steps(self, value: int) -> None:
+        self._resolve_skip()
+        self._skipped_steps = int(value)
+
+    def _resolve_skip(self) -> None:
+        """Settle the counters of the last launched step against its flag. On the GPU the flag was copied to pinned memory right
+        after it was written; the wait is for that copy alone (work of the step before the current one when called from
+        grad_norm_and_clip, which is where a training loop resolves). On a CPU device the flag is just read."""
+        pending = self._skip_pending
+        if pending is None:
+            return
+        self._skip_pending = None
+        event, ema_step = pending
+        if event is not None:
+            event.synchronize()
+            flag, norm = int(self._skip_host[0]), float(self._skip_host[1:].view(torch.float32))
+        else:
+            flag, norm = int(self._skip), float(self._norm)
+        if not flag:
+            self._consecutive_skips = 0
+            return
+        self._step_count -= 1         # the step was launched as applied; it was not
+        if ema_step:
+            self._ema_updates -= 1
+        self._skipped_steps += 1
+        self._consecutive_skips += 1
+        if self._consecutive_skips >= self.max_consecutive_skips:
+            raise RuntimeError(f"{self._consecutive_skips} consecutive optimizer steps skipped on a non-finite gradient norm (last norm "
+                               f"{norm}; max_consecutive_skips={self.max_consecutive_skips}): the weights or the data are broken")
 
     def _add_unit(self, name, mod, named, no_decay):
         if not named:
@@ -726,7 +825,21 @@ class ShardedModel:
             dist.all_reduce(self._sumsq, op=dist.ReduceOp.SUM, group=self.pg)
         if self.grad_div != 1.0:
             self._sumsq.mul_(1.0 / (self.grad_div * self.grad_div))     # the shards hold SUMS over ranks: norm of the mean gradient
-        self.ops.clip_coef(self._sumsq, float(max_norm) if max_norm is not None else 3.0e38, self._coef, self._norm)
+        if self.skip_nonfinite:
+            # the previous step's flag: copied to the host a whole step ago. Settled HERE, before its buffers are reused and before
+            # optimizer_step forms this step's number -- a skipped step k means step k + 1 runs under k's number.
+            self._resolve_skip()
+            # decided after the all-reduce: every rank writes the same flag, whichever rank held the bad value
+            self.ops.clip_coef_guard(self._sumsq, float(max_norm) if max_norm is not None else 3.0e38, self._coef, self._norm, self._skip)
+            if self._skip_host is not None:
+                self._skip_stage[:1].copy_(self._skip)
+                self._skip_stage[1:].copy_(self._norm.view(torch.int32))
+                self._skip_host.copy_(self._skip_stage, non_blocking=True)
+                self._skip_copied = torch.cuda.Event()
+                self._skip_copied.record(torch.cuda.current_stream(self.device))
+            self._norm_fresh = True
+        else:
+            self.ops.clip_coef(self._sumsq, float(max_norm) if max_norm is not None else 3.0e38, self._coef, self._norm)
         if self.grad_div != 1.0:
             self._coef.mul_(1.0 / self.grad_div)                        # AdamW's gradient scale = clip coefficient x 1 / world
         return self._norm
@@ -734,21 +847,30 @@ class ShardedModel:
     def optimizer_step(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
         if self._ema_swapped:
             raise RuntimeError("optimizer_step inside ema_weights(): the bf16 replica holds the average, not the weights")
+        if self.skip_nonfinite:
+            if not self._norm_fresh:      # the flag would be an earlier step's
+                raise RuntimeError("optimizer_step with skip_nonfinite needs grad_norm_and_clip() first: no gradient norm since the last step")
+            self._norm_fresh = False
         self.step_count += 1
         # an EMA step runs the same launches over the same ranges with the average as one more stream; every other step (and every
         # step without ema_decay) runs exactly the plain launches
         ema_step = self.ema_decay is not None and self.step_count % self.ema_update_every == 0
         if ema_step:
             self.ema_updates += 1
+        if self.skip_nonfinite:
+            # counted as applied; _resolve_skip takes it back if the flag (on its way to the host since grad_norm_and_clip) says otherwise
+            self._skip_pending = (self._skip_copied, ema_step)
+            self._skip_copied = None
 
         for ordinal, u in enumerate(self.units):
             if not u.trainable:
                 continue
             ranges = u._shard_ranges()
-            if self.moments == "bf16":
+            if self.moments == "bf16" or self.skip_nonfinite:
                 # the same ranges through the bf16-moment launch (one entry point: n_decay = n or 0 is the one-group case, ema=None
-                # the plain step). index_base = the element's position in the unit's flat trainable region, under the unit's
-                # ordinal: the random bits do not depend on how the ranks cut the region, nor on how a shard is cut into launches
+                # the plain step) or, with skip_nonfinite, through the guarded launch of either moment format behind the step's flag.
+                # index_base = the element's position in the unit's flat trainable region, under the unit's ordinal: the random bits
+                # do not depend on how the ranks cut the region, nor on how a shard is cut into launches
                 base = (ordinal << 40) + u.rank * u.shard_train
                 ema = u.ema if ema_step else None
                 if ranges and ranges[0][0] == 0 and all(ranges[i][1] == ranges[i + 1][0] and
@@ -758,9 +880,13 @@ class ShardedModel:
                 else:
                     merged = [(ls, le, g0, le - ls if dec else 0) for ls, le, g0, dec in ranges]
                 for ls, le, g0, n_dec in merged:
-                    self.ops.adamw_m16(u.master_train[ls:le], u.gshard[ls:le], u.exp_avg[ls:le], u.exp_avg_sq[ls:le],
-                                       None if ema is None else ema[ls:le], u.flat16[g0:g0 + (le - ls)], n_dec, lr, betas, eps, weight_decay,
-                                       self.step_count, self._coef, self.ema_decay, self.moments_seed, base + ls)
+                    args = (u.master_train[ls:le], u.gshard[ls:le], u.exp_avg[ls:le], u.exp_avg_sq[ls:le],
+                            None if ema is None else ema[ls:le], u.flat16[g0:g0 + (le - ls)], n_dec, lr, betas, eps, weight_decay,
+                            self._step_count, self._coef, self.ema_decay, self.moments_seed, base + ls)
+                    if self.skip_nonfinite:
+                        self.ops.adamw_guard(*args, self._skip)
+                    else:
+                        self.ops.adamw_m16(*args)
             elif hasattr(self.ops, "adamw_groups") and ranges and ranges[0][0] == 0 and \
                     all(ranges[i][1] == ranges[i + 1][0] and ranges[i][2] + (ranges[i][1] - ranges[i][0]) == ranges[i + 1][2]
                         for i in range(len(ranges) - 1)):

@@ -629,6 +629,30 @@ def adamw_m16_step(p32, g32, m16, v16, ema, p16, n_decay, lr, beta1, beta2, eps,
          float(beta2), float(eps), float(wd), int(step), _p(grad_scale), d, omd, int(seed) & 0xFFFFFFFFFFFFFFFF, int(index_base))
 
 
+def adamw_guard_step(p32, g32, m, v, ema, p16, n_decay, lr, beta1, beta2, eps, wd, step, grad_scale, ema_decay, seed, index_base, skip1):
+    """Every form of the AdamW pass behind the device flag skip1 of clip_coef_guard (mla_adamw_guard_step, include/mla_hip_optim.h):
+    skip1[0] != 0 and the launch touches nothing; skip1[0] == 0 and it writes the bits of adamw_step_groups / adamw_ema_step_groups (m, v
+    fp32; seed and index_base unused) or of adamw_m16_step (m, v bf16). ema: the fp32 weight average, or None."""
+    _req(p32, torch.float32, "adamw_guard_step p32")
+    _req(g32, torch.float32, "adamw_guard_step g32")
+    _req(skip1, torch.int32, "adamw_guard_step skip1")
+    if m.dtype not in (torch.float32, torch.bfloat16) or v.dtype != m.dtype:
+        raise TypeError(f"adamw_guard_step: moments must both be fp32 or both bf16, got {m.dtype} and {v.dtype}")
+    n = p32.numel()
+    assert g32.numel() == n and m.numel() == n and v.numel() == n and all(t.is_contiguous() for t in (p32, g32, m, v))
+    d, omd = 0.0, 0.0
+    if ema is not None:
+        _req(ema, torch.float32, "adamw_guard_step ema")
+        assert ema.numel() == n and ema.is_contiguous()
+        d, omd = ema_factors(ema_decay)
+    if p16 is not None:
+        _req(p16, torch.bfloat16, "adamw_guard_step p16")
+        assert p16.numel() == n and p16.is_contiguous()
+    call("mla_adamw_guard_step", _p(p32), _p(g32), _p(m), _p(v), _p(ema), _p(p16), n, int(n_decay), float(lr), float(beta1), float(beta2),
+         float(eps), float(wd), int(step), _p(grad_scale), d, omd, int(m.dtype == torch.bfloat16), int(seed) & 0xFFFFFFFFFFFFFFFF,
+         int(index_base), _p(skip1))
+
+
 def ema_update(ema, p32, decay):
     """ema = (1 - decay) * p32 + decay * ema, fp32, in place: the weight average as a pass of its own."""
     _req(ema, torch.float32, "ema_update ema")
@@ -645,6 +669,13 @@ def sumsq(x32, out1, accumulate):
 
 def clip_coef(sumsq1, max_norm, coef1, norm1=None):
     call("mla_clip_coef", _p(sumsq1), float(max_norm), _p(coef1), _p(norm1))
+
+
+def clip_coef_guard(sumsq1, max_norm, coef1, norm1, skip1):
+    """clip_coef plus the verdict of the skip_nonfinite guard (mla_clip_coef_guard, include/mla_hip_optim.h): skip1, one int32 on the
+    device, becomes 1 when sumsq1 is +inf or NaN (coef1 = 0, norm1 = the non-finite norm) and 0 otherwise (coef1, norm1 as clip_coef)."""
+    _req(skip1, torch.int32, "clip_coef_guard skip1")
+    call("mla_clip_coef_guard", _p(sumsq1), float(max_norm), _p(coef1), _p(norm1), _p(skip1))
 
 
 def q_sample(x0, noise, t, sqrt_ac, sqrt_1mac):

@@ -35,7 +35,8 @@ class FSDPStrategy:
                  repeated_diffusion_steps: int = 4, cast_forward_inputs: bool = True, local_ops=None,
                  mixed_precision_dtype: torch.dtype = torch.bfloat16, worker_init_fn=None, requires_cliploss: bool = False,
                  sharding_strategy: str = "full-shard", save_optimizer_state: bool = False, ema_decay: Optional[float] = None,
-                 ema_update_every: int = 1, moments: Optional[str] = None, moments_seed: int = 0, **_):
+                 ema_update_every: int = 1, moments: Optional[str] = None, moments_seed: int = 0,
+                 skip_nonfinite: Optional[bool] = None, max_consecutive_skips: int = 16, **_):
         """Constructor arguments of the reference's FSDPStrategy (training/strategies/fsdp.py:47-96) -- get_train_strategy passes
         them through unchanged. `sharding_strategy` "full-shard" and "shard-grad-op" run the same schedule here: bf16 weights stay
         replicated between the optimizer step and the next use (13.5 GB of 288 GB), master weights / gradients / AdamW moments are
@@ -75,7 +76,9 @@ class FSDPStrategy:
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         assert self.global_batch_size % (self.per_device_batch_size * self.world) == 0
         self.grad_accumulation_steps = self.global_batch_size // self.per_device_batch_size // self.world
-        self.step = 0               # optimizer steps taken
+        # index of the LR schedule: accumulation windows seen. It advances on every window, skipped or not (skip_nonfinite), because
+        # the schedule's length comes from the dataset size; the APPLIED steps are sharded.step_count.
+        self.step = 0
         self._micro = 0             # micro-batches seen inside the current accumulation window
         self.num_training_steps = self.num_warmup_steps = 0
         # opt-in: save_checkpoint also writes `<stem>-optimizer.pt` (AdamW moments, step counters, generator states) so that a run can
@@ -92,6 +95,18 @@ class FSDPStrategy:
         # changes), so that `MLA_MOMENTS=bf16 python bench.py ...` measures the step. Both may also be set as attributes before run_setup().
         self.moments = moments if moments is not None else (os.environ.get("MLA_MOMENTS") or "fp32")
         self.moments_seed = int(moments_seed)
+        # opt-in: a window whose global gradient norm is +inf or NaN leaves weights, moments, replica and average untouched on every
+        # rank (ShardedModel skip_nonfinite: a device flag, no host round trip; no counterpart in the reference, where the NaN lands
+        # in every parameter; the effect on a trained policy is unmeasured). None reads MLA_SKIP_NONFINITE from the environment (unset
+        # or "0": off, nothing changes), so that `MLA_SKIP_NONFINITE=1 python bench.py ...` measures the step. Both may also be set as
+        # attributes before run_setup().
+        self.skip_nonfinite = (os.environ.get("MLA_SKIP_NONFINITE", "0") not in ("", "0")) if skip_nonfinite is None else bool(skip_nonfinite)
+        self.max_consecutive_skips = int(max_consecutive_skips)
+
+    @property
+    def skipped_steps(self) -> int:
+        """Windows whose optimizer step was skipped on a non-finite gradient norm (0 without skip_nonfinite, or before run_setup)."""
+        return 0 if self.sharded is None else self.sharded.skipped_steps
 
     def run_setup(self, n_train_examples: int = 0, run_dir=None) -> None:
         """fsdp.py:176-306: shard, (checkpointing), AdamW groups (no decay on <2-D / bias), LR schedule."""
@@ -99,7 +114,8 @@ class FSDPStrategy:
             self.vlm.llm_backbone.enable_gradient_checkpointing()
         self.sharded = ShardedModel(self.vlm, self.vlm.get_fsdp_wrapping_policy(), self.device, ops=self.local_ops,
                                     ema_decay=self.ema_decay, ema_update_every=self.ema_update_every, moments=self.moments,
-                                    moments_seed=self.moments_seed)
+                                    moments_seed=self.moments_seed, skip_nonfinite=self.skip_nonfinite,
+                                    max_consecutive_skips=self.max_consecutive_skips)
         n = math.ceil(max(n_train_examples, 1) / self.global_batch_size) * self.global_batch_size
         self.num_training_steps = self.max_steps if self.max_steps is not None else (n * self.epochs) // self.global_batch_size
         if self.lr_scheduler_type == "linear-warmup+cosine-decay":
@@ -135,7 +151,9 @@ class FSDPStrategy:
         """One micro-batch of the hot loop (base_strategy_mla.py:296-377). With grad_accumulation_steps == 1 (every shipped
         script) that is one optimizer step; otherwise the loss is divided by the window length (:365), gradients add up in the
         fp32 main_grad buffers, and only the last micro-batch of the window reduce-scatters, clips and steps (:370-377). The
-        reference's FSDP reduces after every micro-batch; reducing the fp32 sum once is the same sum with fewer collectives."""
+        reference's FSDP reduces after every micro-batch; reducing the fp32 sum once is the same sum with fewer collectives.
+        With ``skip_nonfinite`` a window whose gradient norm is not finite (one bad micro-batch poisons its window) steps nothing;
+        ``self.step``, the schedule's index, advances all the same (``skipped_steps`` counts them), and the returned keys are unchanged."""
         sm = self.sharded
         acc = self.grad_accumulation_steps
         last = self._micro == acc - 1
@@ -262,6 +280,8 @@ class FSDPStrategy:
         self.sharded.load_optimizer_state({n: (d["exp_avg"], d["exp_avg_sq"]) for n, d in blob["state"].items()}, int(blob["step_count"]))
         if "moments_seed" in blob:
             self.sharded.moments_seed = self.moments_seed = int(blob["moments_seed"])
+        if self.sharded.skip_nonfinite:      # (a file written without the guard has no such key: 0)
+            self.sharded.skipped_steps = int(blob.get("skipped_steps", 0))
         self.step = int(blob["step"])
         self._micro = 0
         # the weight average: restored when both sides have one (the resume is then bit-exact in the average too); every other
@@ -323,7 +343,8 @@ class FSDPStrategy:
         unchanged. With ``save_optimizer`` and the average on, the optimizer file additionally holds ``"ema"`` (name -> full fp32
         tensor), ``"ema_updates"``, ``"ema_decay"`` and ``"ema_update_every"``; without the average it is unchanged, key for key. With
         ``moments="bf16"`` the moments are bf16 tensors (the stored bits) and the file also holds ``"moments"`` and ``"moments_seed"``;
-        with fp32 moments both keys are absent."""
+        with fp32 moments both keys are absent. With ``skip_nonfinite`` the flag of the last step is settled first and the file also
+        holds ``"skipped_steps"``; without the guard the key is absent."""
         from collections import OrderedDict
         from pathlib import Path
         assert self.sharded is not None, "save_checkpoint needs run_setup() first"
@@ -382,6 +403,8 @@ class FSDPStrategy:
                     "rng": {"world": int(self.world), "cpu": [c for c, _ in every], "device": [d for _, d in every]}}
             if self.sharded.moments != "fp32":      # bf16 moments (saved as bf16 tensors, the stored bits) and the seed of their rounding;
                 blob["moments"], blob["moments_seed"] = self.sharded.moments, int(self.sharded.moments_seed)      # absent with fp32 moments
+            if self.sharded.skip_nonfinite:      # (step_count above was read through the settled flag of the last step)
+                blob["skipped_steps"] = int(self.sharded.skipped_steps)
             if ema_on:       # what a bit-exact resume of the average needs; absent (not empty) without one
                 blob["ema"] = OrderedDict((n, e) for n, e in self.sharded.iter_ema_state(to_cpu_on_rank0=True) if e is not None)
                 blob["ema_updates"] = int(self.sharded.ema_updates)
