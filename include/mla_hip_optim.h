@@ -1,4 +1,5 @@
-/* mla_hip_optim.h -- sibling of mla_hip.h: the optimizer entry points of libmla_hip.so added after the ABI pin.
+/* mla_hip_optim.h -- sibling of mla_hip.h: the entry points of libmla_hip.so added after the ABI pin (the optimizer's, and the
+ * DPM-Solver++(2M) sampler step).
  *
  * Why a second header: tests/test_abi.py pins the SET of symbols derived from include/mla_hip.h to the 153 names of
  * tests/golden/abi_signatures.json (the binding the hand-written ctypes tables gave, kept as the record of that hand-over). A new
@@ -63,6 +64,28 @@ int mla_adamw_guard_step(float* p, const float* g, void* m, void* v, float* ema,
                          float beta1, float beta2, float eps, float weight_decay, int step, const float* grad_scale, float ema_decay,
                          float ema_one_minus_decay, int moments_bf16, unsigned long long seed, long long index_base, const int* skip,
                          mla_stream_t stream);
+
+/* ---- DPM-Solver++(2M) step of the device-resident sampler loop (opt-in solver="dpmpp2m"; no counterpart in the reference, whose only
+ * deterministic solver is first-order DDIM; mla_amd/csrc/sampler.hip, mla_amd/infer.py _CachedEpsBase.sample_dpmpp2m) ----
+ * mla_ddim_step's form and counter protocol (mla_hip.h) for the second-order multistep solver on the respaced process. s = *step; for
+ * 0 <= s < steps, with coef[s] = {a, b, kx, k0, k1} ([steps, 5] fp32, GaussianDiffusion.dpmpp2m_tables: a, b as in mla_ddim_step's
+ * table, kx, k0, k1 formed in double and rounded once) and hist [n] fp32, the previous step's x0 prediction:
+ *   ax = a x; be = b eps; D = ax - be; t0 = kx x; t1 = k0 D; t2 = k1 hist; x = (t0 + t1) + t2; hist = D,
+ * every operation rounded on its own (no FMA contraction): the bits of GaussianDiffusion.dpmpp2m_sample_loop. D is mla_ddim_step's x0
+ * prediction bit for bit. x [n] fp32 and hist [n] fp32 are updated in place, eps [n] bf16, x_bf16 [n] = bf16_rne(x) is written; with
+ * `advance` the counter then becomes s - 1 (thread 0, behind a workgroup barrier). Any other s: nothing is written (hist included),
+ * the counter stays. hist is always read, also where k1 = 0 (the first step): the caller zeroes it in front of a loop, a stale
+ * non-finite value would reach x through 0 * hist. One workgroup; 1 <= n <= 65 536.
+ * mla_dpmpp2m_step_pin: the same step with known [n] fp32 and pin [n] uint8 (non-zero = pinned): D = pin[i] ? known[i] : D right behind
+ * D = ax - be, in front of every use of D and of the store into hist -- the bits of the host loop with denoised_fn =
+ * where(pin, known, D). pin all zero: the bits of mla_dpmpp2m_step. At the last step (s = 0: kx = 0, k0 = 1, k1 = 0) a pinned
+ * x == known for finite x, eps and hist.
+ * Stateless, no allocation, no host access, on `stream`, graph-capturable. Return -1 (nothing launched) for a null pointer (known and
+ * pin count for the pinned form only), n outside [1, 65 536] or steps < 1. */
+int mla_dpmpp2m_step(float* x, const void* eps, void* x_bf16, float* hist, const float* coef, int* step, int n, int steps, int advance,
+                     mla_stream_t stream);
+int mla_dpmpp2m_step_pin(float* x, const void* eps, void* x_bf16, float* hist, const float* coef, const float* known,
+                         const unsigned char* pin, int* step, int n, int steps, int advance, mla_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
-// The samplers' glue on the device (mla_amd/infer.py:_CachedEpsBase.sample_ddim / sample_ddpm): the per-step update of the action chunk
-// (DDIM at eta = 0, or the DDPM posterior step with its noise read from a table the host filled beforehand) and the assembly of the suffix
+// The samplers' glue on the device (mla_amd/infer.py:_CachedEpsBase.sample_ddim / sample_ddpm / sample_dpmpp2m): the per-step update of the
+// action chunk (DDIM at eta = 0, the DDPM posterior step with its noise read from a table the host filled beforehand, or the
+// DPM-Solver++(2M) step with the previous x0 prediction kept in device memory) and the assembly of the suffix
 // pass's input rows. The step index lives in device memory and is counted down by the update kernel, so a sampler step depends on
 // nothing the host knows: the host enqueues `steps` replays of one captured step and reads the result.
 // All kernels are stateless, allocate nothing, launch on the caller's stream and are graph-capturable.
@@ -83,6 +84,45 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(float* __restrict__ x, c
   if (live && advance && threadIdx.x == 0) *step = s - 1;
 }
 
+// DPM-Solver++(2M) (Lu et al. 2022, the data-prediction multistep form; no counterpart in the reference) on the respaced process, with the
+// five per-step values coef[s] = {sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, kx, k0, k1} (GaussianDiffusion.dpmpp2m_tables)
+// and the previous step's x0 prediction in hist [n] fp32, read and written in place:
+//   ax = a x;  D = ax - b eps;  x' = (kx x + k0 D) + k1 hist;  hist <- D
+// every operation rounded on its own, as in ddim_step_kernel (contraction off). D is ddim_step_kernel's px bit for bit. At the first step
+// k1 is 0 and the product 0 * hist is still formed and added, as the host loop does: the loop zeroes hist at every reset, so the product
+// is a zero. At s = 0 the row is {., ., 0, 1, 0}: x' is the x0 prediction. The counter protocol and PIN are ddim_step_kernel's; the pin
+// replaces D in front of every use and of the store into hist. A stale counter leaves hist alone too.
+template <bool PIN>
+__global__ __launch_bounds__(256) void dpmpp2m_step_kernel(float* __restrict__ x, const bf16_t* __restrict__ eps, bf16_t* __restrict__ x_bf16,
+                                                           float* __restrict__ hist, const float* __restrict__ coef,
+                                                           const float* __restrict__ known, const uint8_t* __restrict__ pin, int* step, int n,
+                                                           int steps, int advance) {
+#pragma clang fp contract(off)
+  const int s = *(const volatile int*)step;
+  const bool live = s >= 0 && s < steps;                                      // a stale counter never indexes outside the table
+  if (live) {
+    const float a = coef[5 * s + 0], b = coef[5 * s + 1], kx = coef[5 * s + 2], k0 = coef[5 * s + 3], k1 = coef[5 * s + 4];
+    for (int i = threadIdx.x; i < n; i += 256) {
+      const float e = bf2f(eps[i]);
+      const float xi = x[i];
+      const float ax = a * xi;
+      const float be = b * e;
+      float px = ax - be;
+      if (PIN && pin[i]) px = known[i];
+      const float t0 = kx * xi;
+      const float t1 = k0 * px;
+      const float t2 = k1 * hist[i];
+      const float t01 = t0 + t1;
+      const float out = t01 + t2;
+      x[i] = out;
+      x_bf16[i] = f2bf(out);
+      hist[i] = px;
+    }
+  }
+  __syncthreads();
+  if (live && advance && threadIdx.x == 0) *step = s - 1;
+}
+
 // h_in row g R <- t_table[*step], rows g R + 1 + p <- x_e[g T + p] (R = 1 + T): cat([t_e, x_e], 1).reshape(G R, H) of the sampler's
 // model call, with the timestep embedding looked up instead of recomputed. One workgroup per row, 16 B per lane.
 __global__ __launch_bounds__(256) void sampler_rows_kernel(bf16_t* __restrict__ h_in, const bf16_t* __restrict__ t_table,
@@ -121,6 +161,17 @@ int ddpm_step_launch(const char* who, float* x, const void* eps, void* x_bf16, c
   MLA_LAUNCH_CHECK();
 }
 
+template <bool PIN>
+int dpmpp2m_step_launch(const char* who, float* x, const void* eps, void* x_bf16, float* hist, const float* coef, const float* known,
+                        const uint8_t* pin, int* step, int n, int steps, int advance, hipStream_t stream) {
+  MLA_CHECK_ARG(x && eps && x_bf16 && hist && coef && step && (!PIN || (known && pin)), "%s: null pointer", who);
+  MLA_CHECK_ARG(n >= 1 && n <= 65536, "%s: n = %d outside [1, 65536] (one workgroup walks the chunk)", who, n);
+  MLA_CHECK_ARG(steps >= 1, "%s: steps = %d", who, steps);
+  hipLaunchKernelGGL(dpmpp2m_step_kernel<PIN>, dim3(1), dim3(256), 0, stream, x, (const bf16_t*)eps, (bf16_t*)x_bf16, hist, coef, known, pin,
+                     step, n, steps, advance ? 1 : 0);
+  MLA_LAUNCH_CHECK();
+}
+
 }  // namespace
 
 extern "C" int mla_ddim_step(float* x, const void* eps, void* x_bf16, const float* coef, int* step, int n, int steps, int advance,
@@ -141,6 +192,16 @@ extern "C" int mla_ddpm_step(float* x, const void* eps, void* x_bf16, const floa
 extern "C" int mla_ddpm_step_pin(float* x, const void* eps, void* x_bf16, const float* coef, const float* noise, const float* known,
                                  const unsigned char* pin, int* step, int n, int steps, int advance, hipStream_t stream) {
   return ddpm_step_launch<true>("mla_ddpm_step_pin", x, eps, x_bf16, coef, noise, known, pin, step, n, steps, advance, stream);
+}
+
+extern "C" int mla_dpmpp2m_step(float* x, const void* eps, void* x_bf16, float* hist, const float* coef, int* step, int n, int steps,
+                                int advance, hipStream_t stream) {
+  return dpmpp2m_step_launch<false>("mla_dpmpp2m_step", x, eps, x_bf16, hist, coef, nullptr, nullptr, step, n, steps, advance, stream);
+}
+
+extern "C" int mla_dpmpp2m_step_pin(float* x, const void* eps, void* x_bf16, float* hist, const float* coef, const float* known,
+                                    const unsigned char* pin, int* step, int n, int steps, int advance, hipStream_t stream) {
+  return dpmpp2m_step_launch<true>("mla_dpmpp2m_step_pin", x, eps, x_bf16, hist, coef, known, pin, step, n, steps, advance, stream);
 }
 
 extern "C" int mla_sampler_rows(void* h_in, const void* t_table, const void* x_e, const int* step, int G, int T, int H, int steps,

@@ -1471,6 +1471,44 @@ def ddpm_step_pin(x, eps, x_bf16, coef, noise, known, pin, step, advance=True):
          1 if advance else 0)
 
 
+def _dpmpp2m_step_checks(who, x, eps, x_bf16, hist, coef, step):
+    """The argument checks of dpmpp2m_step / dpmpp2m_step_pin -> x.numel()."""
+    _req(x, torch.float32, who + " x")
+    _req(eps, torch.bfloat16, who + " eps")
+    _req(x_bf16, torch.bfloat16, who + " x_bf16")
+    _req(hist, torch.float32, who + " hist")
+    _req(coef, torch.float32, who + " coef")
+    _req(step, torch.int32, who + " step")
+    n = x.numel()
+    if not (x.is_contiguous() and eps.is_contiguous() and x_bf16.is_contiguous() and hist.is_contiguous() and coef.is_contiguous()):
+        raise ValueError(f"{who}: x, eps, x_bf16, hist and coef must be contiguous")
+    if eps.numel() != n or x_bf16.numel() != n or hist.numel() != n or coef.dim() != 2 or coef.shape[1] != 5 or step.numel() != 1:
+        raise ValueError(f"{who}: x {tuple(x.shape)}, eps {tuple(eps.shape)}, x_bf16 {tuple(x_bf16.shape)}, hist {tuple(hist.shape)}, "
+                         f"coef {tuple(coef.shape)}, step {tuple(step.shape)}")
+    if not 1 <= n <= DDIM_NMAX:
+        raise ValueError(f"{who}: {n} elements outside [1, {DDIM_NMAX}]")
+    return n
+
+
+def dpmpp2m_step(x, eps, x_bf16, hist, coef, step, advance=True):
+    """mla_dpmpp2m_step (include/mla_hip_optim.h): the DPM-Solver++(2M) update of the chunk x (fp32, in place; any shape, contiguous) with
+    row step[0] of coef [steps, 5] (GaussianDiffusion.dpmpp2m_tables), the bf16 epsilons eps and hist (fp32, x.numel() elements, in place:
+    the previous step's x0 prediction in, this step's out; zeros in front of the first step); x_bf16 <- bf16(x); advance: step[0] -= 1.
+    A step[0] outside [0, steps) writes nothing."""
+    n = _dpmpp2m_step_checks("dpmpp2m_step", x, eps, x_bf16, hist, coef, step)
+    call("mla_dpmpp2m_step", _p(x), _p(eps), _p(x_bf16), _p(hist), _p(coef), _p(step), n, coef.shape[0], 1 if advance else 0)
+
+
+def dpmpp2m_step_pin(x, eps, x_bf16, hist, coef, known, pin, step, advance=True):
+    """mla_dpmpp2m_step_pin: dpmpp2m_step with the x0 prediction replaced by known (fp32) where pin (uint8) is non-zero, x.numel()
+    elements each, in front of every use and of the store into hist: dpmpp2m_sample_loop with denoised_fn = where(pin, known, .), the
+    same bits. pin all zero: dpmpp2m_step's bits."""
+    n = _dpmpp2m_step_checks("dpmpp2m_step_pin", x, eps, x_bf16, hist, coef, step)
+    _pin_checks("dpmpp2m_step_pin", n, known, pin)
+    call("mla_dpmpp2m_step_pin", _p(x), _p(eps), _p(x_bf16), _p(hist), _p(coef), _p(known), _p(pin), _p(step), n, coef.shape[0],
+         1 if advance else 0)
+
+
 def sampler_rows(h_in, t_table, x_e, step, G, T):
     """mla_sampler_rows: rows [0, G (1 + T)) of h_in <- per group [t_table[step[0]] | x_e rows g T .. g T + T); rows behind them are not
     touched. h_in [>= G (1 + T), H], t_table [steps, H], x_e [>= G T, H] (or [G, T, H]) bf16, contiguous."""

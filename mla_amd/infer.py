@@ -34,6 +34,11 @@ Pinned chunk steps (`MLA.predict_action_diff*(known_actions=...)`): `sample_ddim
 loops with `mla_ddim_step_pin` / `mla_ddpm_step_pin` as the update -- the x0 prediction of every step is `known` where `mask` is set, the
 reference's `denoised_fn` hook -- on a state and a captured step of their own; the un-pinned loops keep theirs.
 
+DPM-Solver++(2M) (`MLA.predict_action_diff*(solver="dpmpp2m")`; no row of MODES: the solver belongs to the diffusion process, not to an
+engine): with `sampler="device"`, `sample_dpmpp2m` runs the second-order multistep solver over the respaced process on the same loop --
+`mla_dpmpp2m_step[_pin]` as the update, the previous step's x0 prediction in the state's `hist`, zeroed at every reset -- on states and
+captured steps of its own: the bits of GaussianDiffusion.dpmpp2m_sample_loop, and the DDIM and DDPM loops keep theirs.
+
 Opt-in (`suffix_attention="split"`, see MODES; PrefixCachedEps only): the attention launch of the suffix pass becomes
 `mla_attn_chunk_split` -- every head's key tiles cut over several workgroups, the partial softmax states merged in a fixed order by a
 second launch -- for every R; the same function up to summation order. The multi-row engines (BatchedPrefixCachedEps, SampleGroupsEps,
@@ -270,13 +275,14 @@ _GRAPH_OFF = "MLA_INFER_GRAPH=0: the device sampler launches its steps one by on
 
 
 class _DdimState:
-    """What sample_ddim / sample_ddpm keep per (engine, batch, action_dim, diffusion): the chunk x fp32 and its bf16 cast, the step
-    counter, the coefficient and timestep-embedding tables, and the captured step; a DDPM state also has `noise` [steps, B T D] fp32, the
-    steps' normal variates (None in a DDIM state: it selects the update kernel). A pinned state (sample_ddim / sample_ddpm with pin=)
-    also has `known` [B, T, D] fp32 and `pin` [B, T, D] uint8, refilled per call (None in an un-pinned state: the update is the plain
-    kernel). All device tensors are allocated outside inference mode."""
+    """What sample_ddim / sample_ddpm / sample_dpmpp2m keep per (engine, batch, action_dim, diffusion): the chunk x fp32 and its bf16 cast,
+    the step counter, the coefficient and timestep-embedding tables, and the captured step; a DDPM state also has `noise`
+    [steps, B T D] fp32, the steps' normal variates, and a DPM-Solver++(2M) state `hist` [B, T, D] fp32, the previous step's x0
+    prediction, zeroed at every reset (both None in a DDIM state: they select the update kernel). A pinned state (pin=) also has `known`
+    [B, T, D] fp32 and `pin` [B, T, D] uint8, refilled per call (None in an un-pinned state: the update is the plain kernel). All
+    device tensors are allocated outside inference mode."""
     __slots__ = ("diffusion", "steps", "x", "x_bf16", "step", "coef", "timesteps", "t_table", "t_key", "graph", "graph_key", "failed",
-                 "noise", "known", "pin")
+                 "noise", "known", "pin", "hist")
 
 
 class _Coded:
@@ -373,6 +379,8 @@ class _CachedEpsBase:
         self._ddpm = {}              # sample_ddpm's, kept apart: a DDIM and a DDPM call on one engine keep their captured steps
         self._ddim_pin = {}          # the states of the pinned calls (pin=), kept apart in the same way: the un-pinned call replays ...
         self._ddpm_pin = {}          # ... the step it replays without them, whatever pinned calls ran in between
+        self._dpmpp2m = {}           # sample_dpmpp2m's states, kept apart like the DDPM ones: a DDIM call replays the step it always ...
+        self._dpmpp2m_pin = {}       # ... replayed, whatever solver ran in between
 
     @classmethod
     def _serves(cls, vlm, rows: int, limit: int, tag: tuple, message: str, warn: bool = True) -> bool:
@@ -631,17 +639,19 @@ class _CachedEpsBase:
         return None, noise_pred
 
     # ----------------------------------------------------- the sampler loops on the device (sampler="device", ddpm_sampler="device")
-    def _sampler_state(self, x0, diffusion, ddpm: bool, pinned: bool = False):
-        """The persistent state of the DDIM or of the DDPM loop (kept in _ddim / _ddpm, a pinned call's in _ddim_pin / _ddpm_pin: the four
-        do not evict each other's captured steps) for chunks shaped like x0 [B, T, D] under `diffusion` (per B: the group engines keep
-        one per set_groups G)."""
+    def _sampler_state(self, x0, diffusion, loop: str, pinned: bool = False):
+        """The persistent state of the "ddim", "ddpm" or "dpmpp2m" loop (kept in _ddim / _ddpm / _dpmpp2m, a pinned call's in _ddim_pin /
+        _ddpm_pin / _dpmpp2m_pin: the six do not evict each other's captured steps) for chunks shaped like x0 [B, T, D] under
+        `diffusion` (per B: the group engines keep one per set_groups G)."""
         B, T, D = x0.shape
         assert B == self.B and T == self.T, (tuple(x0.shape), self.B, self.T)
-        store = (self._ddpm_pin if ddpm else self._ddim_pin) if pinned else (self._ddpm if ddpm else self._ddim)
+        ddpm = loop == "ddpm"
+        store = getattr(self, "_" + loop + ("_pin" if pinned else ""))
         st = store.get((B, D))
         if st is None or st.diffusion is not diffusion:
             dev = self.h_in.device
-            coef, timesteps = diffusion.ddpm_tables(dev) if ddpm else diffusion.ddim_tables(dev, eta=0.0)
+            coef, timesteps = {"ddim": lambda: diffusion.ddim_tables(dev, eta=0.0), "ddpm": lambda: diffusion.ddpm_tables(dev),
+                               "dpmpp2m": lambda: diffusion.dpmpp2m_tables(dev)}[loop]()
             st = _DdimState()
             st.diffusion, st.steps, st.timesteps = diffusion, int(coef.shape[0]), timesteps
             with torch.inference_mode(False), torch.no_grad():                # the state outlives the (inference-mode) call that creates it
@@ -651,6 +661,7 @@ class _CachedEpsBase:
                 st.coef = coef.clone()
                 st.t_table = torch.zeros((st.steps, self.H), dtype=torch.bfloat16, device=dev)
                 st.noise = torch.zeros((st.steps, B * T * D), dtype=torch.float32, device=dev) if ddpm else None
+                st.hist = torch.zeros((B, T, D), dtype=torch.float32, device=dev) if loop == "dpmpp2m" else None
                 st.known = torch.zeros((B, T, D), dtype=torch.float32, device=dev) if pinned else None
                 st.pin = torch.zeros((B, T, D), dtype=torch.uint8, device=dev) if pinned else None
             st.t_key = st.graph = st.graph_key = None
@@ -675,15 +686,20 @@ class _CachedEpsBase:
 
     def _sampler_one_step(self, st):
         """One sampler step, every launch on the current stream and none of them waiting for the host: the launches of __call__ with the
-        timestep token looked up (mla_sampler_rows), then the state's update (DDIM, or DDPM with the step's row of st.noise; the pinned
-        kernels on a pinned state), which counts the device-side step index down."""
+        timestep token looked up (mla_sampler_rows), then the state's update (DDIM, DDPM with the step's row of st.noise, or
+        DPM-Solver++(2M) with st.hist; the pinned kernels on a pinned state), which counts the device-side step index down."""
         vlm = self.vlm
         x_e = vlm.x_embedder(st.x_bf16)                                       # [B, T, H]
         hip.sampler_rows(self.h_in, st.t_table, x_e.contiguous(), st.step, self.B, self.T)
         self._suffix_pass()                                                   # launched directly: a graph cannot replay inside a capture
         picked = self.h_out.view(self.B, self.R, self.H)[:, 1:].reshape(self.B * self.T, self.H).contiguous()
         noise_pred = vlm.final_layer(picked)                                  # [B * T, D] bf16
-        if st.pin is None:
+        if st.hist is not None:
+            if st.pin is None:
+                hip.dpmpp2m_step(st.x, noise_pred.contiguous(), st.x_bf16, st.hist, st.coef, st.step, advance=True)
+            else:
+                hip.dpmpp2m_step_pin(st.x, noise_pred.contiguous(), st.x_bf16, st.hist, st.coef, st.known, st.pin, st.step, advance=True)
+        elif st.pin is None:
             if st.noise is None:
                 hip.ddim_step(st.x, noise_pred.contiguous(), st.x_bf16, st.coef, st.step, advance=True)
             else:
@@ -724,17 +740,20 @@ class _CachedEpsBase:
         return st.graph
 
     def _sampler_loop(self, st, x0, pin=None):
-        """What the two device loops share behind the state lookup: the timestep-token table and the captured step for the current
+        """What the device loops share behind the state lookup: the timestep-token table and the captured step for the current
         weights, the reset of the state to x0 and step steps - 1, and st.steps replays (or eager steps). A DDPM state: in front of the
         replays, one randn_like(x) per step in the host loop's order (step steps - 1 first) into row s of st.noise -- asynchronous
-        launches. A pinned state: pin = (known, mask) is copied into st.known / st.pin in front of the replays (behind the capture: its
-        warm-up step runs on whatever the last call left there)."""
+        launches. A DPM-Solver++(2M) state: st.hist is zeroed in the reset (behind the capture, whose warm-up step wrote a prediction
+        there: the first step forms 0 * hist). A pinned state: pin = (known, mask) is copied into st.known / st.pin in front of the
+        replays (behind the capture: its warm-up step runs on whatever the last call left there)."""
         self._sampler_t_table(st)
         graph = self._sampler_graph(st)
         with torch.no_grad():
             st.x.copy_(x0)
             st.x_bf16.copy_(x0.to(torch.bfloat16))
             st.step.fill_(st.steps - 1)
+            if st.hist is not None:
+                st.hist.zero_()
             if pin is not None:
                 st.known.copy_(pin[0])
                 st.pin.copy_(pin[1])
@@ -768,7 +787,7 @@ class _CachedEpsBase:
         randn_like per step)."""
         x0 = x0.float()
         self._check_pin(x0, pin)
-        st = self._sampler_state(x0, diffusion, ddpm=False, pinned=pin is not None)
+        st = self._sampler_state(x0, diffusion, "ddim", pinned=pin is not None)
         self._sampler_loop(st, x0, pin)
         with torch.no_grad():
             for _ in range(st.steps):
@@ -784,7 +803,21 @@ class _CachedEpsBase:
         the host never waits for the device between the steps."""
         x0 = x0.float()
         self._check_pin(x0, pin)
-        st = self._sampler_state(x0, diffusion, ddpm=True, pinned=pin is not None)
+        st = self._sampler_state(x0, diffusion, "ddpm", pinned=pin is not None)
+        self._sampler_loop(st, x0, pin)
+        with torch.no_grad():
+            return st.x.clone()
+
+    def sample_dpmpp2m(self, x0, diffusion, pin=None):
+        """dpmpp2m_sample_loop(self, x0.shape, x0, clip_denoised=False) of `diffusion` (DPM-Solver++(2M) on the respaced process) with the
+        loop on the device -> samples [B, T, D] fp32, the same bits. pin: sample_ddim's (mla_dpmpp2m_step_pin: the pinned entries of
+        every step's x0 prediction, of the history and of the result == known). A state and a captured step of its own (x_embedder,
+        mla_sampler_rows, the suffix pass, final_layer, mla_dpmpp2m_step[_pin]), which also holds the previous step's x0 prediction,
+        zeroed at the reset: the DDIM and DDPM states and their captured steps are not touched. Nothing is copied to the device, the host
+        never waits for the device between the steps, and nothing is drawn: the generator stays where the host loop leaves it."""
+        x0 = x0.float()
+        self._check_pin(x0, pin)
+        st = self._sampler_state(x0, diffusion, "dpmpp2m", pinned=pin is not None)
         self._sampler_loop(st, x0, pin)
         with torch.no_grad():
             return st.x.clone()

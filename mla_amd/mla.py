@@ -401,16 +401,39 @@ class MLA(nn.Module):
             _ = torch.randint(0, self.diffusion.num_timesteps, (T,), device=device)
         return torch.cat(draws, dim=0).float()
 
-    def _sample(self, eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs, ddpm_sampler="host", pin=None):
-        """x0 [B, T, D] -> samples: the DDIM loop (eta = 0) on the device (an engine's sample_ddim) or on the host, or the DDPM loop of the
-        training diffusion on the device (sample_ddpm) or on the host. pin = (known, mask) shaped like x0 (see _pin): the device loops'
-        pin=, the host loops' denoised_fn = where(mask, known, .); None is the call without it."""
+    SOLVERS = ("ddim", "dpmpp2m")
+
+    @staticmethod
+    def _check_solver(solver, use_ddim, num_ddim_steps):
+        """``solver`` of the sampling entry points, validated before the model is touched: never silently ignored, never a silent DDIM."""
+        if solver not in MLA.SOLVERS:
+            raise ValueError(f"solver={solver!r}: unknown value, choose from {MLA.SOLVERS}")
+        if solver != "ddim" and not (use_ddim and num_ddim_steps is not None):
+            raise ValueError(f"solver={solver!r} runs the respaced process of the DDIM sampler (use_ddim=True and num_ddim_steps); this "
+                             "call runs the DDPM loop of the training diffusion, which has no deterministic solver")
+
+    @staticmethod
+    def _fwd_solver(solver):
+        """The keyword of a call that ends in another public method: handed on only when it is not the default (as _fwd_known)."""
+        return {} if solver == "ddim" else {"solver": solver}
+
+    def _sample(self, eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs, ddpm_sampler="host", pin=None, solver="ddim"):
+        """x0 [B, T, D] -> samples: the DDIM loop (eta = 0) on the device (an engine's sample_ddim) or on the host, solver "dpmpp2m" the
+        DPM-Solver++(2M) loop over the same respaced process on the device (sample_dpmpp2m) or on the host (dpmpp2m_sample_loop), or
+        the DDPM loop of the training diffusion on the device (sample_ddpm) or on the host. pin = (known, mask) shaped like x0 (see
+        _pin): the device loops' pin=, the host loops' denoised_fn = where(mask, known, .); None is the call without it."""
         device = x0.device
         on_device = {} if pin is None else {"pin": pin}
         on_host = {} if pin is None else {"denoised_fn": lambda px: torch.where(pin[1], pin[0], px)}
+        MLA._check_solver(solver, use_ddim, num_ddim_steps)
         if use_ddim and num_ddim_steps is not None:
             if self.ddim_diffusion is None:
                 self.create_ddim(ddim_step=num_ddim_steps)
+            if solver == "dpmpp2m":
+                if sampler == "device":
+                    return eps_model.sample_dpmpp2m(x0, self.ddim_diffusion, **on_device)
+                return self.ddim_diffusion.dpmpp2m_sample_loop(eps_model, x0.shape, x0, clip_denoised=False, model_kwargs=model_kwargs,
+                                                               progress=False, device=device, **on_host)
             if sampler == "device":
                 return eps_model.sample_ddim(x0, self.ddim_diffusion, **on_device)
             return self.ddim_diffusion.ddim_sample_loop(eps_model, x0.shape, x0, clip_denoised=False, model_kwargs=model_kwargs,
@@ -464,7 +487,7 @@ class MLA(nn.Module):
                             camera_name: str = "rlbench_front", reuse_prefix: bool = True, suffix_weights: str = "bf16",
                             prefill: str = "train", sampler: str = "host", suffix_attention: str = "head",
                             prefill_precision: str = "bf16", ddpm_sampler: str = "host", suffix_operand: str = "fused",
-                            known_actions=None, suffix_mx: str = "off", **kwargs) -> np.ndarray:
+                            known_actions=None, suffix_mx: str = "off", solver: str = "ddim", **kwargs) -> np.ndarray:
         """model_mla.py:592-775: 8-step DDIM (eta = 0) over the action chunk with the VLM as the epsilon model, then
         un-normalisation.
         * ``image`` is a PIL image / uint8 HWC frame (pre-processed here like the reference does, :656-660) or an already
@@ -545,11 +568,25 @@ class MLA(nn.Module):
         steps ago, new chunk step j is old chunk step j + k, so ``known_actions = old_chunk[k:k + d]``. It composes with every mode
         keyword, with ``sampler`` / ``ddpm_sampler`` "host" and "device" (mla_ddim_step_pin / mla_ddpm_step_pin on a captured step of
         its own) and with ``reuse_prefix=False`` (the host loop with ``denoised_fn``). A wrong shape, d > T or non-finite values raise
-        ValueError before the model is touched. What pinning does to a trained policy is not measured."""
+        ValueError before the model is touched. What pinning does to a trained policy is not measured.
+        ``solver`` (default "ddim": the call without the keyword, bit for bit -- the same launches, the same captured step, the same
+        generator position): which deterministic solver walks the respaced process of ``num_ddim_steps`` steps. "dpmpp2m":
+        DPM-Solver++(2M) (Lu et al. 2022; no counterpart in model_mla.py), the second-order multistep solver in its data-prediction
+        form -- one model call per step like DDIM, the previous step's x0 prediction reused, the last step first order
+        (GaussianDiffusion.dpmpp2m_sample_loop is the definition; its coefficients are formed in float64 from the process's
+        alphas_cumprod). On an analytic Gaussian model four 2M steps are closer to the exact solution than eight DDIM steps
+        (profiles/solver_dpmpp_error.txt), which is what it is for: fewer suffix passes per chunk (``create_ddim(ddim_step=4)`` in
+        front of the call, as for any other step count). The effect on a trained policy is not measured. It runs on the host loop
+        (``reuse_prefix=False`` and the warned whole-forward fallback included) and, with ``sampler="device"``, on the device
+        (sample_dpmpp2m: a state and a captured step of its own, mla_dpmpp2m_step[_pin], the host loop's bits); it draws nothing in the
+        loop, so the generator stays where the initial draw left it (DDIM's unused randn_like per step is DDIM's). It composes with
+        every mode keyword and with ``known_actions`` (the pinned entries come back exactly). An unknown value, and "dpmpp2m" with
+        ``use_ddim=False`` or ``num_ddim_steps=None``, raise ValueError before the model is touched: there is never a silent DDIM."""
         from .infer import Modes, PrefixCachedEps, check_modes, needs_engine
         check_modes(Modes(suffix_weights=suffix_weights, prefill=prefill, suffix_attention=suffix_attention, prefill_precision=prefill_precision,
                           suffix_operand=suffix_operand, sampler=sampler, ddpm_sampler=ddpm_sampler, suffix_mx=suffix_mx),
                     reuse_prefix, use_ddim, num_ddim_steps)
+        MLA._check_solver(solver, use_ddim, num_ddim_steps)
         if prefill != "train" and not reuse_prefix:
             raise ValueError(f"prefill={prefill!r} needs the cached-prefix engine (reuse_prefix=True); the whole-forward sampler has no "
                              "separate prefill")
@@ -581,7 +618,7 @@ class MLA(nn.Module):
             needs_engine("PrefixCachedEps", T, suffix_mx=suffix_mx, prefill=prefill, sampler=sampler, ddpm_sampler=ddpm_sampler,
                          suffix_attention=suffix_attention, suffix_operand=suffix_operand)
         pin = MLA._pin(self, [known_actions], T, action_dim, unnorm_key, device)
-        samples = self._sample(eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs, ddpm_sampler, pin)
+        samples = self._sample(eps_model, x0, sampler, use_ddim, num_ddim_steps, model_kwargs, ddpm_sampler, pin, solver)
         return self._actions([samples[:1].float().cpu().numpy()], unnorm_key)[0]
 
     @torch.inference_mode()
@@ -593,7 +630,7 @@ class MLA(nn.Module):
                                   suffix_attention: str = "head", prefill_precision: str = "bf16",
                                   groups_attention: str = "head", batch_prefill: str = "train",
                                   ddpm_sampler: str = "host", suffix_operand: str = "fused", known_actions=None,
-                                  suffix_mx: str = "off") -> np.ndarray:
+                                  suffix_mx: str = "off", solver: str = "ddim") -> np.ndarray:
         """B observations -> [B, T, action_dim]: by definition B independent `predict_action_diff` calls (the reference's
         `predict_action_batch`, model_mla.py:994, is dead code), computed on ONE cached prefix pass per DDIM step
         (mla_amd/infer.py:BatchedPrefixCachedEps): the prompts may have different lengths, the FPS start indices are drawn once per chunk.
@@ -659,12 +696,16 @@ class MLA(nn.Module):
         ``known_actions``: predict_action_diff's, as a list with one entry per observation -- an array [d_b, action_dim] (its own d_b) or
         None (nothing of that chunk is pinned); with ``num_samples`` the N chunks of an observation share its entry. None, or a list of
         only None, is the call without the keyword, bit for bit. A list of another length raises ValueError before the model is
-        touched."""
+        touched.
+        ``solver``: predict_action_diff's, with and without ``num_samples``: "dpmpp2m" runs DPM-Solver++(2M) over every pass's or
+        sub-batch's respaced process, on the host loop or (``sampler="device"``) on the device, the same bits; handed on where the
+        call ends in another public method. An unknown value, and "dpmpp2m" where the call runs the DDPM sampler, raise ValueError."""
         from .infer import BatchedPrefixCachedEps, Modes, check_mode, check_modes, needs_engine, suffix_attention_single_only
         modes = Modes(suffix_weights=suffix_weights, prefill=prefill, suffix_attention=suffix_attention, groups_attention=groups_attention,
                       batch_prefill=batch_prefill, suffix_operand=suffix_operand, sampler=sampler, ddpm_sampler=ddpm_sampler,
                       suffix_mx=suffix_mx)
         check_modes(modes, reuse_prefix, use_ddim, num_ddim_steps)
+        MLA._check_solver(solver, use_ddim, num_ddim_steps)
         check_mode("prefill_precision", prefill_precision)                    # an unknown value only: no mode but "bf16" is served here
         check_mode("batch_prefill", batch_prefill, reuse_prefix)
         if prefill != "train":
@@ -682,7 +723,7 @@ class MLA(nn.Module):
         if num_samples is not None:
             return self._predict_action_diff_batch_samples(images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix,
-                                                           num_samples, modes, known)
+                                                           num_samples, modes, known, solver)
         input_ids, pointclouds = MLA._batch_prompts(self, B, instructions, input_ids, pointclouds, cur_robot_states)
         if noise is not None and tuple(noise.shape[:2]) != (B, T):
             raise ValueError(f"noise must be [B, T, action_dim] = [{B}, {T}, ...], got {tuple(noise.shape)}")
@@ -692,7 +733,7 @@ class MLA(nn.Module):
         def one(b, **kw):
             return self.predict_action_diff(images[b], pointclouds[b], None, cur_robot_states[b], unnorm_key, cfg_scale, use_ddim, num_ddim_steps,
                                             action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b:b + 1],
-                                            camera_name=camera_name, **MLA._fwd_known(known[b]), **kw)
+                                            camera_name=camera_name, **MLA._fwd_known(known[b]), **MLA._fwd_solver(solver), **kw)
         if B == 1:
             return one(0, reuse_prefix=reuse_prefix,
                        **modes.forwarded("suffix_weights", "suffix_mx", "sampler", "ddpm_sampler", "suffix_attention", "suffix_operand"))[None]
@@ -717,15 +758,16 @@ class MLA(nn.Module):
         for sub, eng in BatchedPrefixCachedEps.for_batch(self.vlm, ids_rows, T, suffix_attention=groups_attention,
                                                          batch_prefill=batch_prefill, **inputs):
             samples = self._sample(eng, x0[sub.start:sub.stop].contiguous(), sampler, use_ddim, num_ddim_steps, {}, ddpm_sampler,
-                                   MLA._pin_rows(pin, sub.start, sub.stop))
+                                   MLA._pin_rows(pin, sub.start, sub.stop), solver)
             out.append(samples.float().cpu().numpy())
         return self._actions(out, unnorm_key)
 
     def _predict_action_diff_batch_samples(self, images, pointclouds, instructions, cur_robot_states, unnorm_key, cfg_scale, use_ddim,
                                            num_ddim_steps, action_dim, input_ids, noise, camera_name, reuse_prefix, num_samples, modes,
-                                           known):
+                                           known, solver="ddim"):
         """predict_action_diff_batch(num_samples=N) -> [B, N, T, action_dim] (called inside its inference mode; see its docstring).
-        modes: its keywords as infer.Modes, known: its known_actions as one entry per observation, both validated there."""
+        modes: its keywords as infer.Modes, known: its known_actions as one entry per observation, solver: its solver, all validated
+        there."""
         from .infer import BatchedSampleGroupsEps, needs_engine
         B, N, T = len(images), int(num_samples), self.future_action_window_size + 1
         if N < 1:
@@ -739,7 +781,7 @@ class MLA(nn.Module):
         def samples_of(b, **kw):
             return self.predict_action_diff_samples(images[b], pointclouds[b], None, cur_robot_states[b], unnorm_key, N, cfg_scale, use_ddim,
                                                     num_ddim_steps, action_dim, input_ids=ids_rows[b], noise=None if noise is None else noise[b],
-                                                    camera_name=camera_name, **MLA._fwd_known(known[b]), **kw)
+                                                    camera_name=camera_name, **MLA._fwd_known(known[b]), **MLA._fwd_solver(solver), **kw)
         if B == 1:
             return samples_of(0, reuse_prefix=reuse_prefix, **modes.forwarded("suffix_weights", "suffix_mx", "sampler", "ddpm_sampler",
                                                                               "suffix_attention", "groups_attention", "suffix_operand"))[None]
@@ -765,7 +807,7 @@ class MLA(nn.Module):
                                                          suffix_attention=modes.groups_attention, batch_prefill=modes.batch_prefill,
                                                          suffix_mx=modes.suffix_mx, **inputs):
             samples = self._sample(eng, x0[sub.start * N:sub.stop * N].contiguous(), modes.sampler, use_ddim, num_ddim_steps, {},
-                                   modes.ddpm_sampler, MLA._pin_rows(pin, sub.start * N, sub.stop * N))
+                                   modes.ddpm_sampler, MLA._pin_rows(pin, sub.start * N, sub.stop * N), solver)
             out.append(samples.float().cpu().numpy().reshape(sub.stop - sub.start, N, T, -1))
         return self._actions(out, unnorm_key)
 
@@ -778,7 +820,7 @@ class MLA(nn.Module):
                                     sampler: str = "host", suffix_attention: str = "head",
                                     prefill_precision: str = "bf16", groups_attention: str = "head",
                                     ddpm_sampler: str = "host", suffix_operand: str = "fused", known_actions=None,
-                                    suffix_mx: str = "off") -> np.ndarray:
+                                    suffix_mx: str = "off", solver: str = "ddim") -> np.ndarray:
         """N action chunks for ONE observation -> [N, T, action_dim]: by definition N independent `predict_action_diff` calls on the same
         observation with the initial samples ``noise[n]`` (critic / best-of-N choice, uncertainty estimates, temporal ensembling), computed
         on ONE cached prefix (mla_amd/infer.py:SampleGroupsEps): the encoders and the decoder prefill run once per call, every sampler step
@@ -822,12 +864,16 @@ class MLA(nn.Module):
         operand once per pass already: both values are accepted and launch what is launched without the keyword. An unknown value, and
         "once" with ``reuse_prefix=False``, raise ValueError.
         ``known_actions``: predict_action_diff's -- one array [d, action_dim] for the observation, pinned in every one of the N chunks
-        (the engine sees it repeated over the samples). None is the call without the keyword, bit for bit."""
+        (the engine sees it repeated over the samples). None is the call without the keyword, bit for bit.
+        ``solver``: predict_action_diff's; "dpmpp2m" runs DPM-Solver++(2M) over every pass's respaced process, on the host loop or
+        (``sampler="device"``) on the device, the same bits. Handed on for ``num_samples=1`` and in the loops over predict_action_diff.
+        An unknown value, and "dpmpp2m" with ``use_ddim=False`` or ``num_ddim_steps=None``, raise ValueError."""
         from .infer import Modes, SampleGroupsEps, check_modes, needs_engine, suffix_attention_single_only
         modes = Modes(suffix_weights=suffix_weights, prefill=prefill, suffix_attention=suffix_attention, groups_attention=groups_attention,
                       prefill_precision=prefill_precision, suffix_operand=suffix_operand, sampler=sampler, ddpm_sampler=ddpm_sampler,
                       suffix_mx=suffix_mx)
         check_modes(modes, reuse_prefix, use_ddim, num_ddim_steps)
+        MLA._check_solver(solver, use_ddim, num_ddim_steps)
         if int(num_samples) != 1:
             suffix_attention_single_only(suffix_attention, f"predict_action_diff_samples with num_samples={num_samples}")
         if prefill != "train" and not reuse_prefix:
@@ -845,7 +891,7 @@ class MLA(nn.Module):
         def one(n, **kw):
             return self.predict_action_diff(image, pointcloud, instruction, cur_robot_state, unnorm_key, cfg_scale, use_ddim, num_ddim_steps,
                                             action_dim, input_ids=input_ids, noise=None if noise is None else noise[n:n + 1],
-                                            camera_name=camera_name, **MLA._fwd_known(known_actions), **kw)
+                                            camera_name=camera_name, **MLA._fwd_known(known_actions), **MLA._fwd_solver(solver), **kw)
         if N == 1:
             return one(0, reuse_prefix=reuse_prefix, **modes.forwarded("suffix_weights", "suffix_mx", "prefill", "sampler", "ddpm_sampler",
                                                                        "suffix_attention", "prefill_precision", "suffix_operand"))[None]
@@ -876,6 +922,6 @@ class MLA(nn.Module):
         for start, stop in passes:                                           # one prefill, then the passes' sampler loops one after the other
             eng.set_groups(stop - start)
             samples = self._sample(eng, x0[start:stop].contiguous(), sampler, use_ddim, num_ddim_steps, {}, ddpm_sampler,
-                                   MLA._pin_rows(pin, start, stop))
+                                   MLA._pin_rows(pin, start, stop), solver)
             out.append(samples.float().cpu().numpy())
         return self._actions(out, unnorm_key)

@@ -96,6 +96,17 @@
                                                           per 7B projection shape at M = 1090, 2180 and 4360: the wide-row FP8 GEMM against
                                                           the training kernel and against the 64-row FP8 kernel run in slices of at most
                                                           1024 rows; --pairs 0 stops after the table
+    python tools/bench_infer.py --pair-solver [--ddim-steps K] [--pairs P] [--chunks C[,C..]]
+                                                          solver="ddim" and solver="dpmpp2m" (DPM-Solver++(2M)) chunks with
+                                                          sampler="device", alternating in one process, in pairs, for every chunk length
+                                                          (default 1,16) with bf16 and with fp8 suffix weights, two cases per setting: both
+                                                          solvers at --steps (what the solver's own update costs), and dpmpp2m at K steps
+                                                          (default 4) against ddim at --steps (what the solver is for); per-chunk latency
+                                                          with the 95 % interval of the pair differences, and whether sampler="host"
+                                                          returns the 2M chunk's bits
+    python tools/bench_infer.py --solver dpmpp2m --ddim-steps K [--sampler device] [--chunk C] [--suffix-weights W]
+                                                          the single measurement with the solver keyword and create_ddim(ddim_step=K) in
+                                                          front of the first call (without --ddim-steps: --steps)
 Prints one JSON line per measurement (not the driver's bench contract -- that is bench.py)."""
 import argparse
 import json
@@ -185,6 +196,11 @@ def main():
                     "on the multi-row routes")
     ap.add_argument("--pair-operand", action="store_true", help="alternate suffix_operand=\"fused\" and \"once\" in one process, in pairs")
     ap.add_argument("--pair-batch-prefill", action="store_true", help="with --batch: alternate batch_prefill=\"train\" and \"fp8\" in one process, in pairs")
+    ap.add_argument("--pair-solver", action="store_true", help="alternate solver=\"ddim\" and solver=\"dpmpp2m\" chunks with sampler=\"device\" in one process, in pairs")
+    ap.add_argument("--solver", choices=["ddim", "dpmpp2m"], default="ddim", help="the single measurement: solver of predict_action_diff")
+    ap.add_argument("--sampler", choices=["host", "device"], default="host", help="the single measurement: sampler of predict_action_diff")
+    ap.add_argument("--ddim-steps", type=int, default=None, help="steps of the respaced process (create_ddim in front of the first call); --pair-solver: "
+                    "the step count of the short dpmpp2m arm (default 4)")
     ap.add_argument("--pairs", type=int, default=6)
     ap.add_argument("--kernel-table", action="store_true", help="with --pair-fp8: the two _w8 kernels per projection shape and M; with "
                     "--samples: mla_attn_chunk_groups per groups-per-workgroup against mla_attn_chunk_ragged")
@@ -195,6 +211,8 @@ def main():
         return main_pair_sampler(args, ddpm=args.pair_ddpm_sampler)
     if args.pair_pinned:
         return main_pair_pinned(args)
+    if args.pair_solver:
+        return main_pair_solver(args)
     if args.pair_operand:
         return main_pair_operand(args)
     batches = [int(v) for v in args.batch.split(",")]
@@ -218,8 +236,15 @@ def main():
     m, b, ids = _setup(args)
     dev = ids.device
     image, pc, state = _observation(b)
+    if args.ddim_steps is not None:
+        args.steps = args.ddim_steps
+        m.create_ddim(ddim_step=args.steps)
     kw = dict(image=image, pointcloud=pc, cur_robot_state=state, input_ids=ids, num_ddim_steps=args.steps,
               reuse_prefix=not args.no_reuse_prefix, suffix_weights=args.suffix_weights)
+    if args.solver != "ddim":
+        kw["solver"] = args.solver
+    if args.sampler != "host":
+        kw["sampler"] = args.sampler
     act = m.predict_action_diff(**kw)
     ms = _time_ms(lambda: m.predict_action_diff(**kw), args.iters)
     parts = {}
@@ -240,7 +265,7 @@ def main():
                  "suffix_pass_graph_replay_ms": round(pass_ms, 3), "weights_streamed_per_pass_gb": round(wbytes / 1e9, 2),
                  "suffix_pass_weight_stream_tbps": round(wbytes / 1e12 / (pass_ms * 1e-3), 2)}
     print(json.dumps({"metric": "predict_action_diff latency, MLA-Llama2-7B bf16, batch 1", "suffix_weights": args.suffix_weights,
-                      "value": round(ms, 1), "unit": "ms",
+                      "solver": args.solver, "sampler": args.sampler, "value": round(ms, 1), "unit": "ms",
                       "ddim_steps": args.steps, "ms_per_ddim_step": round(ms / args.steps, 1), "seq_len": int(ids.shape[1]) + 513 + 2 + args.chunk,
                       "action_chunk": args.chunk, "reuse_prefix": not args.no_reuse_prefix, **parts, "action": [round(float(v), 4) for v in act.reshape(-1)[:7]], "data": "synthetic"}))
 
@@ -468,6 +493,52 @@ def main_pair_pinned(args):
                               "pinned_host_same_bits": bool(np.array_equal(host, acts["pinned"])),
                               "pinned_differs_from_plain": not np.array_equal(acts["pinned"], acts["plain"]),
                               "data": "synthetic"}), flush=True)
+
+
+def main_pair_solver(args):
+    """solver="ddim" vs solver="dpmpp2m" on the same box, alternating, per chunk length and suffix-weight mode, the device sampler in
+    both arms: predict_action_diff per chunk (host clock around `iters` calls that end in a device synchronise). Two cases: "same_steps"
+    -- both solvers over the --steps process (the 2M update reads and writes one more fp32 array of the chunk's size than DDIM's and
+    skips DDIM's unused randn_like per step); "fewer_steps" -- dpmpp2m over --ddim-steps (default 4) against ddim over --steps. The
+    two processes are two objects handed to the model per arm (the DDIM and the 2M device states are separate: neither arm
+    rebuilds its state or recaptures its step when the other ran)."""
+    from mla_amd.diffusion import create_diffusion
+    m, b, ids = _setup()
+    dev = ids.device
+    image, pc, state = _observation(b)
+    short = args.ddim_steps or 4
+    procs = {n: create_diffusion(timestep_respacing=f"ddim{n}") for n in {args.steps, short}}
+    cases = {"same_steps": {"ddim": ("ddim", args.steps), "dpmpp2m": ("dpmpp2m", args.steps)},
+             "fewer_steps": {"ddim": ("ddim", args.steps), "dpmpp2m": ("dpmpp2m", short)}}
+    for C in ([int(v) for v in args.chunks.split(",")] if args.chunks else [1, 16]):
+        m.future_action_window_size = m.vlm.future_action_window_size = C - 1
+        noise = torch.randn(1, C, 7, device=dev)
+        kw = dict(image=image, pointcloud=pc, cur_robot_state=state, input_ids=ids, noise=noise)
+        for w in ("bf16", "fp8"):
+            for case, arms in cases.items():
+                def call(arm, sampler="device"):
+                    solver, n = arms[arm]
+                    m.ddim_diffusion = procs[n]
+                    return m.predict_action_diff(suffix_weights=w, sampler=sampler, solver=solver, num_ddim_steps=n, **kw)
+                acts = {}
+                for arm in arms:                                            # engines, graphs, tables; the same seed: the same FPS start indices
+                    torch.manual_seed(1)
+                    acts[arm] = call(arm)
+                torch.manual_seed(1)
+                host = call("dpmpp2m", sampler="host")
+                chunk = {arm: [] for arm in arms}
+                for _ in range(args.pairs):                                 # ddim, dpmpp2m, ddim, dpmpp2m, ...: same box, interleaved
+                    for arm in arms:
+                        chunk[arm].append(_time_ms(lambda: call(arm), args.iters))
+                print(json.dumps({"metric": "predict_action_diff, MLA-Llama2-7B, batch 1, sampler=device: solver=ddim vs solver=dpmpp2m in alternating pairs",
+                                  "case": case, "action_chunk": C, "suffix_rows": C + 1, "suffix_weights": w,
+                                  "steps": {arm: n for arm, (_, n) in arms.items()}, "pairs": args.pairs, "iters_per_arm_and_pair": args.iters,
+                                  "unit": "ms", "chunk_ms": {k: [round(v, 2) for v in vs] for k, vs in chunk.items()},
+                                  "chunk_ms_mean": {k: round(sum(vs) / len(vs), 2) for k, vs in chunk.items()},
+                                  "chunk_dpmpp2m_minus_ddim": _pair_stats(chunk["ddim"], chunk["dpmpp2m"]),
+                                  "dpmpp2m_host_same_bits": bool(np.array_equal(host, acts["dpmpp2m"])),
+                                  "dpmpp2m_differs_from_ddim": not np.array_equal(acts["dpmpp2m"], acts["ddim"]),
+                                  "data": "synthetic"}), flush=True)
 
 
 def _attn_split_table(dev, shapes=((2, 547), (17, 562)), H=32, layers=32, reps=5, rounds=3):
